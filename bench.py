@@ -18,7 +18,13 @@ resident in HBM, outputs left in HBM.
   --config c5 (BASELINE.json configs[4]): 2048 x 2048 x 1024 unsigned short grid (8 GiB), ONE resident grid,
         a step = the sweep over the 8 isovalues 15268.5 + 5000 k; z-slabs over the N GPUs (strong scaling: the grid
         is fixed).
-Rank 0 prints ONE JSON line (contract in the task statement) extended with `roofline` and `cpu_baseline`.
+Rank 0 prints ONE JSON line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload.
+A plain run sets up, warms up, times the K steps and prints that line, nothing more.  `--full` adds what takes runs of
+its own: the K steps again with the library's per-pass events (`with_event_records`, `roofline` with the kernel split and
+the read ceiling), the CPU reference (`cpu_baseline`), the C API walls (`c_api`), the configs[4] workload riding on the
+single-GPU c3 line (`c5`) and, with N > 1, the exchange modes timed alone.
+`--dump-outputs DIR`: after the timed steps, the surface that the last step left to its caller, as DIR/<name>.npy
+(dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -51,13 +57,18 @@ def parse():
     ap.add_argument("--cpu-sample", type=int, default=int(os.environ.get("MC33_BENCH_CPU_N", "0")),
                     help="planes (c5) / points per axis (c3) of the sub-grid the CPU reference is timed on")
     ap.add_argument("--with-c5", choices=("auto", "on", "off"), default=os.environ.get("MC33_BENCH_WITH_C5", "auto"),
-                    help="append the configs[4] workload (2048x2048x1024 ushort, 8 isovalues) to the default c3 line as a compact \"c5\" object")
+                    help="--full: append the configs[4] workload (2048x2048x1024 ushort, 8 isovalues) to the c3 line as a compact \"c5\" object")
     ap.add_argument("--no-c-api", action="store_true", default=os.environ.get("MC33_BENCH_NO_C_API", "0") == "1",
                     help="leave out the `c_api` object (host walls of create_MC33 / calculate_isosurface through libMC33_f32.so)")
     ap.add_argument("--c5-points", type=int, default=int(os.environ.get("MC33_BENCH_C5_POINTS", "0")), help="points along z of the appended c5 grid (default 1024)")
     ap.add_argument("--c5-steps", type=int, default=int(os.environ.get("MC33_BENCH_C5_STEPS", "5")))
     ap.add_argument("--rank-timeout", type=int, default=int(os.environ.get("MC33_BENCH_RANK_TIMEOUT", "1500")),
                     help="self-launched N > 1 runs: seconds after which the parent kills ranks that have not finished and exits non-zero")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline figure: event-timed kernel split and roofline, read ceiling, CPU baseline, "
+                         "C API walls, the c5 rider, the exchange modes alone (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the surface (V, N, T) of the last timed step and its counts to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -256,16 +267,42 @@ def spread(a):
     return {"min": s[0], "median": s[len(s) // 2], "max": s[-1]}
 
 
+DUMP_ROWS = 1 << 19  # rows kept per array: V, N (float32) and T (float64) of a sample stay near 25 MB together
+
+
+def dump_outputs(d, V, N, T):
+    """The surface a caller of the timed path receives, as d/V.npy, d/N.npy (float32 [nV, 3]), d/T.npy (the vertex ids of the
+    triangles as float64 [nT, 3], exact) and d/counts.npy ([nV, nT], float64).  An array of more than DUMP_ROWS rows is cut
+    to the rows of a fixed sample: np.random.default_rng(0).choice(rows, DUMP_ROWS, replace=False), sorted - the same rows
+    for the same counts, so that two builds can be compared array for array."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+
+    def sample(t):
+        n = t.shape[0]
+        if n <= DUMP_ROWS:
+            return t.cpu().numpy()
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+        return t.index_select(0, torch.from_numpy(rows).to(t.device)).cpu().numpy()
+
+    np.save(os.path.join(d, "counts.npy"), np.array([V.shape[0], T.shape[0]], dtype=np.float64))
+    np.save(os.path.join(d, "V.npy"), sample(V).astype(np.float32))
+    np.save(os.path.join(d, "N.npy"), sample(N).astype(np.float32))
+    np.save(os.path.join(d, "T.npy"), sample(T).astype(np.float64))
+
+
 class Env:
     """what every config of one process shares: ranks, device, the distributed helpers"""
     pass
 
 
-def run_config(args, cfg, E, points=0, steps=None, warmup=None, cpu=True, capi=False):
+def run_config(args, cfg, E, points=0, steps=None, warmup=None, cpu=True, capi=False, dump=None):
     """One workload on this process's GPU (all ranks run it together when world > 1).  Returns the result object on rank 0
-    (None elsewhere).  cfg: "c3" | "c5"."""
+    (None elsewhere).  cfg: "c3" | "c5".  dump: directory for dump_outputs, or None."""
     import torch
     dist = E.dist
+    full = args.full
     from mc33_c_library_amd import DeviceGrid
     from mc33_c_library_amd.fields import cos_field_slab, cos_field_u16
     from mc33_c_library_amd.slabs import Slab, SurfaceExchange, extract_slab, extract_slab_many, extract_slab_on_device
@@ -383,6 +420,7 @@ def run_config(args, cfg, E, points=0, steps=None, warmup=None, cpu=True, capi=F
                     t = grid.timing()
                     sweep_ms.append(t.sweep_ms); scan_ms.append(t.scan_ms)
             nV += c.nV; nT += c.nT
+        state["c"] = c
         if record == 1:
             step_ms.append((time.perf_counter() - t0) * 1e3)
         return nV, nT
@@ -404,15 +442,21 @@ def run_config(args, cfg, E, points=0, steps=None, warmup=None, cpu=True, capi=F
         return time.perf_counter() - t0, last
 
     # The timed region = K steps of the library as a caller gets it: no event in the stream (MC33_HIP_TIMING=0, the library's
-    # default) - `value` and `ms_per_step` are these steps.  Then the same K steps once more with the library's per-pass
+    # default) - `value` and `ms_per_step` are these steps.  With --full, the same K steps once more with the library's per-pass
     # hipEvents RECORDED on the stream (timing level 2: nobody waits for them): the kernel split and `roofline` are computed
     # from those, live, and their step time is reported beside (`with_event_records`: 1 - 2 % slower).
     for _ in range(warmup):
         step(0)
     grid.set_timing(0)
     dt, last = timed(steps, 1)
-    grid.set_timing(2)
-    dt_events, _ = timed(steps, 2)
+    if dump and rank == 0:  # what the last timed step left to its caller (the last isovalue's surface)
+        if multi:
+            dump_outputs(dump, *ex.concatenated(state["b"], state["counts"]))
+        else:
+            dump_outputs(dump, V[:state["c"].nV], N[:state["c"].nV], T[:state["c"].nT])
+    if full:
+        grid.set_timing(2)
+        dt_events, _ = timed(steps, 2)
 
     if multi and (os.environ.get("MC33_BENCH_VERIFY", "0") == "1" or os.environ.get("MC33_BENCH_DUMP")):
         # the exchanged surface of the LAST isovalue (checked before anything below reuses the buffers): concatenation in
@@ -438,14 +482,14 @@ def run_config(args, cfg, E, points=0, steps=None, warmup=None, cpu=True, capi=F
     # the sweep's rate "of peak" AND "of a measured read ceiling" - a plain read-only kernel over the same
     # resident buffer, in this process (where the buffer lies physically decides 5 - 8 % of any read stream: DESIGN.md App. B)
     read_ceiling = None
-    if not multi:
+    if full and not multi:
         best_ms, med_ms, nbytes = grid.probe_read(10)
         read_ceiling = {"GBps": nbytes / (best_ms * 1e-3) / 1e9, "GBps_median": nbytes / (med_ms * 1e-3) / 1e9, "ms_best": best_ms, "bytes": nbytes,
                         "what": "mc33hip_probe_read: every 16-byte chunk of the resident grid read once (nontemporal loads, every block a contiguous piece, 16 loads in flight per lane: the best plain-read shape of tools/read_ceiling_probe.hip), nothing written; best of 10 launches, hipEvents"}
     gather_info = None
     extract_only_ms = None
     rank_sweep = None
-    if multi:
+    if multi and full:
         # what one un-overlapped exchange of the last surface costs, in each mode
         gather_info = {}
         counts = state["counts"]
@@ -482,17 +526,20 @@ def run_config(args, cfg, E, points=0, steps=None, warmup=None, cpu=True, capi=F
                 grid.emit_into(Vt, Nt, Tt, ex.bases(cs, rank)[0])
         torch.cuda.synchronize()
         extract_only_ms = (time.perf_counter() - t1) / reps * 1e3
-        tmax = torch.tensor([dt, extract_only_ms], dtype=torch.float64, device=dev)
-        all_reduce(tmax, dist.ReduceOp.MAX)
-        dt, extract_only_ms = (float(x) for x in tmax.tolist())
-        tot = torch.tensor([cells_rank, last[0], last[1]], dtype=torch.int64, device=dev)
-        all_reduce(tot)
-        cells_all, nV_all, nT_all = (int(x) for x in tot.tolist())
         # every rank's own sweep time, so that a straggler is visible on the N > 1 line
         mine = (sum(sweep_ms) / len(sweep_ms)) if sweep_ms else 0.0
         lo_t = torch.tensor([mine], dtype=torch.float64, device=dev); hi_t = lo_t.clone()
         all_reduce(lo_t, dist.ReduceOp.MIN); all_reduce(hi_t, dist.ReduceOp.MAX)
         rank_sweep = {"min": float(lo_t.item()), "max": float(hi_t.item())}
+    if multi:
+        tmax = torch.tensor([dt, extract_only_ms or 0.0], dtype=torch.float64, device=dev)
+        all_reduce(tmax, dist.ReduceOp.MAX)
+        dt, extract_max = (float(x) for x in tmax.tolist())
+        if full:
+            extract_only_ms = extract_max
+        tot = torch.tensor([cells_rank, last[0], last[1]], dtype=torch.int64, device=dev)
+        all_reduce(tot)
+        cells_all, nV_all, nT_all = (int(x) for x in tot.tolist())
     else:
         cells_all, nV_all, nT_all = cells_rank, last[0], last[1]
 
@@ -500,54 +547,6 @@ def run_config(args, cfg, E, points=0, steps=None, warmup=None, cpu=True, capi=F
     if rank == 0:
         nis = len(isos)
         ms_step = dt / steps * 1e3
-        avg = lambda a: (sum(a) / len(a)) if a else 0.0
-        sw = avg(sweep_ms)
-        grid_bytes_alg = samples_rank * sample_bytes
-        # V, N + T written once per isovalue (SURVEY.md 8(d) also counts 4 B of colour per vertex: that array is filled
-        # by the host layer outside the timed device path, so it is not credited here)
-        out_bytes = (last[0] * 24 + last[1] * 12) / nis
-        dev_ms = (sw + avg(scan_ms) + avg(emit_ms)) if (sw and emit_ms) else None
-        # The dominant kernel is the sweep.  One launch reads every sample of the rank's slab once = its algorithmic bytes;
-        # with the iso sweep (c5) that one read serves `per_launch` isovalues, and the library reports each isovalue's
-        # share of the launch time: launch time = share x per_launch.
-        per_launch = 4 if sweep_many else 1
-        launch_ms = sw * per_launch
-        passes = (nis + per_launch - 1) // per_launch  # grid reads one step really makes
-        step_bytes = passes * grid_bytes_alg + out_bytes * nis
-        step_dev_ms = dev_ms * nis if dev_ms else None
-        roof = {"bound": "hbm", "kernel": "k_sweep" + ("<%d isovalues per launch>" % per_launch if sweep_many else ""),
-                "achieved": grid_bytes_alg / (launch_ms * 1e-3) / 1e9 if sw else None,
-                "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                "frac": (grid_bytes_alg / (launch_ms * 1e-3) / 1e9 / PEAK_HBM_GBS) if sw else None,
-                "traffic": None, "traffic_source": None,
-                "read_ceiling": read_ceiling,
-                "frac_of_ceiling": (grid_bytes_alg / (launch_ms * 1e-3) / 1e9 / read_ceiling["GBps"]) if (sw and read_ceiling) else None,
-                "algorithmic_bytes_per_launch": grid_bytes_alg,
-                "isovalues_per_launch": per_launch,
-                "launch_ms": launch_ms,
-                # hipEvent brackets of the library, average per isovalue: the sweep (its share of a launch); k_cells +
-                # slow-cell planning + the scan kernels; the emit kernels
-                "kernel_ms": {"k_sweep": sw, "k_cells_slow_scans": avg(scan_ms), "k_emit": avg(emit_ms) if emit_ms else None},
-                "kernel_ms_spread": {"k_sweep": spread(sweep_ms), "k_cells_slow_scans": spread(scan_ms), "k_emit": spread(emit_ms)},
-                # what one step really has to move: the grid once per launch of the sweep (not once per isovalue) + V, N, T of
-                # every isovalue - and the fraction of the HBM peak that is over the device time of the step
-                "step_bytes_moved": step_bytes, "step_device_ms": step_dev_ms,
-                "step_frac": (step_bytes / (step_dev_ms * 1e-3) / 1e9 / PEAK_HBM_GBS) if step_dev_ms else None,
-                # per calculate_isosurface call as the REFERENCE makes it: the grid once + V, N, T - bytes the
-                # call would have to move on its own.  With the iso sweep the library moves less than that per call (that is
-                # the point of it), so this figure grows with the isovalues per launch: reference-equivalent bytes, not traffic
-                "whole_call_reference_equivalent": {"bytes": grid_bytes_alg + out_bytes, "device_ms": dev_ms,
-                                                    "frac": ((grid_bytes_alg + out_bytes) / (dev_ms * 1e-3) / 1e9 / PEAK_HBM_GBS) if dev_ms else None}}
-        pmc = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        if os.path.exists(pmc) and not multi:  # NOT measured in this run: replayed from the committed PMC passes of the same workload
-            try:
-                j = json.load(open(pmc))
-                e = j.get((cfg + ("" if not sweep_many else "_sweep_many")) if (points or 1024) == 1024 else "none")
-                if e:
-                    roof["traffic"] = e.get("k_sweep_bytes_per_launch")
-                    roof["traffic_source"] = "replayed: %s (rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes of this workload, build %s)" % (e.get("source"), e.get("build"))
-            except Exception:
-                pass
         res = {"metric": "Mvoxels/s", "value": cells_all * nis / (dt / steps) / 1e6, "unit": "Mvoxels/s",
                "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": ms_step,
                "step_ms_min": spread(step_ms)["min"], "step_ms_median": spread(step_ms)["median"], "step_ms_max": spread(step_ms)["max"],
@@ -558,21 +557,72 @@ def run_config(args, cfg, E, points=0, steps=None, warmup=None, cpu=True, capi=F
                           "parallelism": "z-slab x%d" % world if multi else "single GPU"},
                "mtris_per_s": nT_all / (dt / steps) / 1e6,
                "ms_per_isovalue": ms_step / nis,
-               "timed_region": "K steps with the library's default settings (no event records); roofline / kernel_ms from the same K steps run again with per-pass hipEvents recorded on the stream (none waited for)",
-               "roofline": roof}
-        res["with_event_records"] = {"ms_per_step": dt_events / steps * 1e3, "value": cells_all * nis / (dt_events / steps) / 1e6,
-                                     "note": "the same %d steps again with MC33_HIP_TIMING=2 (what roofline / kernel_ms were measured in)" % steps}
+               "timed_region": "K steps with the library's default settings (no event records)"}
+        if full:
+            avg = lambda a: (sum(a) / len(a)) if a else 0.0
+            sw = avg(sweep_ms)
+            grid_bytes_alg = samples_rank * sample_bytes
+            # V, N + T written once per isovalue (SURVEY.md 8(d) also counts 4 B of colour per vertex: that array is filled
+            # by the host layer outside the timed device path, so it is not credited here)
+            out_bytes = (last[0] * 24 + last[1] * 12) / nis
+            dev_ms = (sw + avg(scan_ms) + avg(emit_ms)) if (sw and emit_ms) else None
+            # The dominant kernel is the sweep.  One launch reads every sample of the rank's slab once = its algorithmic bytes;
+            # with the iso sweep (c5) that one read serves `per_launch` isovalues, and the library reports each isovalue's
+            # share of the launch time: launch time = share x per_launch.
+            per_launch = 4 if sweep_many else 1
+            launch_ms = sw * per_launch
+            passes = (nis + per_launch - 1) // per_launch  # grid reads one step really makes
+            step_bytes = passes * grid_bytes_alg + out_bytes * nis
+            step_dev_ms = dev_ms * nis if dev_ms else None
+            roof = {"bound": "hbm", "kernel": "k_sweep" + ("<%d isovalues per launch>" % per_launch if sweep_many else ""),
+                    "achieved": grid_bytes_alg / (launch_ms * 1e-3) / 1e9 if sw else None,
+                    "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                    "frac": (grid_bytes_alg / (launch_ms * 1e-3) / 1e9 / PEAK_HBM_GBS) if sw else None,
+                    "traffic": None, "traffic_source": None,
+                    "read_ceiling": read_ceiling,
+                    "frac_of_ceiling": (grid_bytes_alg / (launch_ms * 1e-3) / 1e9 / read_ceiling["GBps"]) if (sw and read_ceiling) else None,
+                    "algorithmic_bytes_per_launch": grid_bytes_alg,
+                    "isovalues_per_launch": per_launch,
+                    "launch_ms": launch_ms,
+                    # hipEvent brackets of the library, average per isovalue: the sweep (its share of a launch); k_cells +
+                    # slow-cell planning + the scan kernels; the emit kernels
+                    "kernel_ms": {"k_sweep": sw, "k_cells_slow_scans": avg(scan_ms), "k_emit": avg(emit_ms) if emit_ms else None},
+                    "kernel_ms_spread": {"k_sweep": spread(sweep_ms), "k_cells_slow_scans": spread(scan_ms), "k_emit": spread(emit_ms)},
+                    # what one step really has to move: the grid once per launch of the sweep (not once per isovalue) + V, N, T of
+                    # every isovalue - and the fraction of the HBM peak that is over the device time of the step
+                    "step_bytes_moved": step_bytes, "step_device_ms": step_dev_ms,
+                    "step_frac": (step_bytes / (step_dev_ms * 1e-3) / 1e9 / PEAK_HBM_GBS) if step_dev_ms else None,
+                    # per calculate_isosurface call as the REFERENCE makes it: the grid once + V, N, T - bytes the
+                    # call would have to move on its own.  With the iso sweep the library moves less than that per call (that is
+                    # the point of it), so this figure grows with the isovalues per launch: reference-equivalent bytes, not traffic
+                    "whole_call_reference_equivalent": {"bytes": grid_bytes_alg + out_bytes, "device_ms": dev_ms,
+                                                        "frac": ((grid_bytes_alg + out_bytes) / (dev_ms * 1e-3) / 1e9 / PEAK_HBM_GBS) if dev_ms else None}}
+            pmc = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+            if os.path.exists(pmc) and not multi:  # NOT measured in this run: replayed from the committed PMC passes of the same workload
+                try:
+                    j = json.load(open(pmc))
+                    e = j.get((cfg + ("" if not sweep_many else "_sweep_many")) if (points or 1024) == 1024 else "none")
+                    if e:
+                        roof["traffic"] = e.get("k_sweep_bytes_per_launch")
+                        roof["traffic_source"] = "replayed: %s (rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes of this workload, build %s)" % (e.get("source"), e.get("build"))
+                except Exception:
+                    pass
+            res["timed_region"] += "; roofline / kernel_ms from the same K steps run again with per-pass hipEvents recorded on the stream (none waited for)"
+            res["roofline"] = roof
+            res["with_event_records"] = {"ms_per_step": dt_events / steps * 1e3, "value": cells_all * nis / (dt_events / steps) / 1e6,
+                                         "note": "the same %d steps again with MC33_HIP_TIMING=2 (what roofline / kernel_ms were measured in)" % steps}
         if multi:
-            res["gather"] = {"mode": args.gather, "overlapped_with_next_extraction": bool(overlap), "alone": gather_info,
-                             "xgmi_inbound_peak_GBps": 76.8 * (world - 1),
+            res["gather"] = {"mode": args.gather, "overlapped_with_next_extraction": bool(overlap), "xgmi_inbound_peak_GBps": 76.8 * (world - 1),
                              "note": "allgather / pairs: the surface arrays of all ranks on every rank (north_star); root: on rank 0 only. "
                                      "One link per peer, ~153 GB/s both ways = ~76.8 GB/s inbound each"}
+        if multi and full:
+            res["gather"]["alone"] = gather_info
             res["gather_ms"] = gather_info[args.gather]["ms"]
             # informational: the extraction without the surface exchange scales with the slabs
             res["extract_only_ms_per_step"] = extract_only_ms
             res["value_without_surface_gather"] = cells_all * nis / (extract_only_ms * 1e-3) / 1e6
             res["rank_sweep_ms"] = rank_sweep
-        if cpu and not args.no_cpu_baseline and not multi:
+        if full and cpu and not args.no_cpu_baseline and not multi:
             if cfg == "c3":
                 m = min(args.cpu_sample or 1024, npx)
                 sub = field[:m, :m, :m].contiguous().cpu().numpy()
@@ -585,7 +635,7 @@ def run_config(args, cfg, E, points=0, steps=None, warmup=None, cpu=True, capi=F
                                                    "%dx%dx%d-point slab (the first %d planes) of the same grid, all 8 isovalues" % (npx, npy, m, m))
             if res["cpu_baseline"]:
                 res["vs_cpu_baseline"] = res["value"] / res["cpu_baseline"]["value"]
-        if capi and cfg == "c3" and not multi:
+        if full and capi and cfg == "c3" and not multi:
             res["c_api"] = c_api_walls(field, r0, dd, isos[0])
     grid.close()
     del grid, field, V, N, T, ex
@@ -637,13 +687,15 @@ def main():
     E.all_reduce = all_reduce
 
     plain = not E.multi and args.config == "c3" and not args.points   # the invocation the driver makes
-    res = run_config(args, args.config, E, points=args.points, capi=plain and not args.no_c_api)
-    # The ushort / 8-isovalue workload of BASELINE configs[4] rides on the default line as a compact object, so that the
-    # driver's `bench.py --gpus 1` carries it: on by default when this is the plain single-GPU c3 run, the c3 part was quick
+    res = run_config(args, args.config, E, points=args.points, capi=plain and not args.no_c_api, dump=args.dump_outputs)
+    # The ushort / 8-isovalue workload of BASELINE configs[4] rides on the --full line as a compact object, so that
+    # `bench.py --gpus 1 --full` carries it: on by default when this is the plain single-GPU c3 run, the c3 part was quick
     # and the device has room for the 8 GiB grid and its lanes.
     # (deterministic: `auto` = on for exactly that invocation, and a run that leaves it out says why)
     with_c5, why_not = args.with_c5, None
-    if with_c5 == "auto":
+    if not args.full:
+        with_c5, why_not = "off", "not a --full run"
+    elif with_c5 == "auto":
         free = torch.cuda.mem_get_info(E.dev)[0]
         if not plain:
             with_c5, why_not = "off", "not the plain single-GPU c3 invocation (--gpus / --config / --points given)"

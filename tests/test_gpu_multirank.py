@@ -4,11 +4,13 @@ process touched the GPU)."""
 import json
 import os
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
 import fixtures as fx
+from parity import assert_surface_parity
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -50,7 +52,7 @@ def test_bench_self_launch_c3_rehearsal(launcher, reflibs, tmp_path, gather):
     dump it; here it is compared with oracle/_ref on the same field."""
     dump = str(tmp_path / "surf.npz")
     n = 80
-    res, out = bench(launcher, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--points", str(n), "--gather", gather], {"MC33_BENCH_DUMP": dump})
+    res, out = bench(launcher, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--points", str(n), "--gather", gather, "--full"], {"MC33_BENCH_DUMP": dump})
     assert res["n_gpus"] == 2 and res["config"]["name"] == "c3" and res["gather"]["mode"] == gather and res["scaling"] == "weak"
     assert set(res["gather"]["alone"]) == {"allgather", "pairs", "root"} and res["value"] > 0 and res["step_ms_min"] <= res["step_ms_max"]
     assert "equals whole-volume result: True" in out["stderr"]
@@ -67,10 +69,11 @@ def test_bench_self_launch_c3_rehearsal(launcher, reflibs, tmp_path, gather):
 
 def test_bench_self_launch_c3_strong_scaling(launcher, reflibs, tmp_path):
     """`--strong`: BASELINE configs[3] read literally - ONE n^3 grid cut into z-slabs over the ranks (here 3 ranks, 26 / 27 / 26
-    slices) - against oracle/_ref on the whole grid."""
+    slices) - against oracle/_ref on the whole grid.  A plain run (no --full): its --dump-outputs files are that surface too."""
     dump = str(tmp_path / "surf.npz")
     n = 80
-    res, out = bench(launcher, ["--gpus", "3", "--steps", "2", "--warmup", "1", "--points", str(n), "--gather", "root", "--strong"], {"MC33_BENCH_DUMP": dump})
+    res, out = bench(launcher, ["--gpus", "3", "--steps", "2", "--warmup", "1", "--points", str(n), "--gather", "root", "--strong",
+                                "--dump-outputs", str(tmp_path / "out")], {"MC33_BENCH_DUMP": dump})
     assert res["n_gpus"] == 3 and res["scaling"] == "strong" and "equals whole-volume result: True" in out["stderr"]
     data, r0, d = fx.cos_field(n)
     ref = reflibs["f32"].isosurface(data, 0.0, r0, d)
@@ -78,6 +81,34 @@ def test_bench_self_launch_c3_strong_scaling(launcher, reflibs, tmp_path):
     assert res["config"]["vertices"] == ref.nV and res["config"]["triangles"] == ref.nT
     assert np.array_equal(got["T"], ref.T) and np.array_equal(got["V"].view(np.uint32), ref.V.view(np.uint32))
     assert np.array_equal(got["N"].view(np.uint32), ref.N.view(np.uint32))
+    assert "roofline" not in res and "alone" not in res["gather"]
+    assert_dump_is(str(tmp_path / "out"), ref, "strong scaling dump")
+
+
+def assert_dump_is(d, ref, label):
+    """--dump-outputs files (a small surface: whole arrays) against a reference surface, bit for bit."""
+    nV, nT = (int(x) for x in np.load(os.path.join(d, "counts.npy")))
+    V, N, T = (np.load(os.path.join(d, k + ".npy")) for k in ("V", "N", "T"))
+    assert V.dtype == N.dtype == np.float32 and T.dtype == np.float64
+    assert_surface_parity(SimpleNamespace(nV=nV, nT=nT, V=V, N=N, T=T.astype(np.uint32)), ref, 4.0, label, bit_exact=True)
+
+
+def test_bench_plain_single_gpu_line_and_dump(launcher, oracles, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line only (no second pass, no baselines, no c5
+    rider), K timed steps; --dump-outputs writes the surface of the last step, checked against the C restatement."""
+    n = 64
+    res, _ = bench(launcher, ["--gpus", "1", "--steps", "4", "--warmup", "1", "--points", str(n), "--dump-outputs", str(tmp_path / "out")],
+                   {"MC33_BENCH_REHEARSAL": "0", "MC33_BENCH_VERIFY": "0"})
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in res, key
+    assert res["steps"] == 4 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0 and res["dtype"] == "f32"
+    for key in ("roofline", "with_event_records", "cpu_baseline", "c_api"):
+        assert key not in res, key
+    assert "skipped" in res["c5"]
+    data, r0, d = fx.cos_field(n)
+    ref = oracles["f32"].isosurface(data, 0.0, r0, d)
+    assert (res["config"]["vertices"], res["config"]["triangles"]) == (ref.nV, ref.nT)
+    assert_dump_is(str(tmp_path / "out"), ref, "plain line dump")
 
 
 @pytest.mark.parametrize("gather", ["allgather", "pairs", "root"])
@@ -88,7 +119,7 @@ def test_bench_strong_scaling_five_rank_processes(launcher, reflibs, tmp_path, g
     oracle/_ref on the whole grid."""
     dump = str(tmp_path / "surf.npz")
     n = 256
-    res, out = bench(launcher, ["--gpus", "5", "--steps", "2", "--warmup", "1", "--points", str(n), "--gather", gather, "--strong", "--rank-timeout", "600"],
+    res, out = bench(launcher, ["--gpus", "5", "--steps", "2", "--warmup", "1", "--points", str(n), "--gather", gather, "--strong", "--rank-timeout", "600", "--full"],
                      {"MC33_BENCH_DUMP": dump, "OMP_NUM_THREADS": "2"}, timeout=900)
     assert res["n_gpus"] == 5 and res["scaling"] == "strong" and res["gather"]["mode"] == gather
     assert "equals whole-volume result: True" in out["stderr"]
@@ -113,7 +144,7 @@ def test_bench_parent_kills_stuck_ranks(launcher):
 def test_bench_self_launch_c5_rehearsal(launcher, reflibs, tmp_path):
     """The ushort / 8-isovalue config on 3 rank processes (strong scaling: one grid cut into z-slabs)."""
     dump = str(tmp_path / "surf.npz")
-    res, out = bench(launcher, ["--gpus", "3", "--steps", "2", "--warmup", "1", "--config", "c5", "--points", "40", "--gather", "pairs"], {"MC33_BENCH_DUMP": dump})
+    res, out = bench(launcher, ["--gpus", "3", "--steps", "2", "--warmup", "1", "--config", "c5", "--points", "40", "--gather", "pairs", "--full"], {"MC33_BENCH_DUMP": dump})
     assert res["n_gpus"] == 3 and res["dtype"] == "u16" and res["config"]["isovalues_per_step"] == 8 and res["scaling"] == "strong"
     data = fx.cos_field_u16(80, 80, 40)
     total_v = total_t = 0
@@ -129,7 +160,7 @@ def test_bench_self_launch_c5_rehearsal(launcher, reflibs, tmp_path):
 def test_bench_single_gpu_lines(launcher):
     """The default line and the C5 line at reduced size: contract keys, roofline and cpu_baseline objects."""
     for args, name in ((["--points", "128", "--with-c5", "on", "--c5-points", "48", "--c5-steps", "2"], "c3"), (["--config", "c5", "--points", "64"], "c5")):
-        res, _ = bench(launcher, ["--steps", "3", "--warmup", "1"] + args, {"MC33_BENCH_REHEARSAL": "0", "MC33_BENCH_VERIFY": "0"})
+        res, _ = bench(launcher, ["--steps", "3", "--warmup", "1", "--full"] + args, {"MC33_BENCH_REHEARSAL": "0", "MC33_BENCH_VERIFY": "0"})
         for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
                     "data", "config", "roofline", "cpu_baseline", "step_ms_min", "step_ms_median", "step_ms_max"):
             assert key in res, key
@@ -178,7 +209,7 @@ def test_bench_rccl_code_path_with_one_rank(launcher, gather):
     box allows: MC33_BENCH_FORCE_DIST=1 runs one rank through init_process_group("nccl"), the second communicator of
     the count exchange, the device-tensor collectives and the overlapped (async) exchange of two buffer sets."""
     for args in (["--points", "160"], ["--config", "c5", "--points", "64"]):
-        res, out = bench(launcher, ["--steps", "4", "--warmup", "2", "--gather", gather, "--no-cpu-baseline"] + args,
+        res, out = bench(launcher, ["--steps", "4", "--warmup", "2", "--gather", gather, "--no-cpu-baseline", "--full"] + args,
                          {"MC33_BENCH_REHEARSAL": "0", "MC33_BENCH_FORCE_DIST": "1", "MC33_BENCH_VERIFY": "1", "MASTER_PORT": str(PORT[0] + 500)})
         PORT[0] += 1
         assert res["n_gpus"] == 1 and res["gather"]["mode"] == gather and res["gather"]["overlapped_with_next_extraction"] is True
