@@ -540,13 +540,15 @@ MC33_HD uint32_t count_triangles(const CellPlan &p, const Tables &tab, const Par
 // ---------------------------------------------------------------------------------------------------
 // Vertex geometry.  r[0..2]: position in grid-index units, r[3..5]: gradient of v = iso - F
 // ---------------------------------------------------------------------------------------------------
-template <typename T>
-MC33_HD void vertex_on_edge(const Params &P, const GridView<T> &G, uint32_t x, uint32_t y, uint32_t z, uint32_t e,
-                            const VRef &v, real_t *r) {  // MC:810-816 ... 1212-1220, SURVEY.md Appendix C
+// (v: the corner values in any memory - VRef - or in registers - Corner8; G: the grid, or anything that answers at(x, y, z) for the
+// samples this cell's vertices need - the vertex pass keeps a FACE record's in LDS)
+template <typename GV, typename V>
+MC33_HD void vertex_on_edge(const Params &P, const GV &G, uint32_t x, uint32_t y, uint32_t z, uint32_t e,
+                            const V &v, real_t *r) {  // MC:810-816 ... 1212-1220, SURVEY.md Appendix C
 	const uint32_t a = edge_a(e), b = edge_b(e), axis = edge_axis(e);
 	const uint32_t ca = corner_code(a), cb = corner_code(b);
 	const uint32_t cell[3] = {x, y, z}, lim[3] = {P.nx, P.ny, P.nz};
-	const real_t va = v[(int)a], vb = v[(int)b];
+	const real_t va = corner_value(v, (int)a), vb = corner_value(v, (int)b);
 	const real_t t = va / (va - vb);
 	for (uint32_t ax = 0; ax < 3; ax++) {
 		if (ax == axis) {
@@ -570,8 +572,8 @@ MC33_HD void vertex_on_edge(const Params &P, const GridView<T> &G, uint32_t x, u
 		} else {
 			// one-sided: difference of v across the cell at both end points
 			const uint32_t bitax = 1u << ax;
-			const real_t da = v[(int)corner_at(ca | bitax)] - v[(int)corner_at(ca & ~bitax)];
-			const real_t db = v[(int)corner_at(cb | bitax)] - v[(int)corner_at(cb & ~bitax)];
+			const real_t da = corner_value(v, (int)corner_at(ca | bitax)) - corner_value(v, (int)corner_at(ca & ~bitax));
+			const real_t db = corner_value(v, (int)corner_at(cb | bitax)) - corner_value(v, (int)corner_at(cb & ~bitax));
 			r[3 + ax] = da * (1 - t) + db * t;
 		}
 	}
@@ -592,7 +594,8 @@ MC33_HD void vertex_on_point(const Params &P, const GridView<T> &G, uint32_t x, 
 	}
 }
 
-MC33_HD void vertex_centre(uint32_t x, uint32_t y, uint32_t z, const VRef &v, real_t *r) {  // MC:1225-1230
+template <typename V>
+MC33_HD void vertex_centre(uint32_t x, uint32_t y, uint32_t z, const V &v, real_t *r) {  // MC:1225-1230
 	r[0] = (real_t)x + 0.5f; r[1] = (real_t)y + 0.5f; r[2] = (real_t)z + 0.5f;
 	r[3] = v[4] + v[5] + v[6] + v[7] - v[0] - v[1] - v[2] - v[3];
 	r[4] = v[1] + v[2] + v[5] + v[6] - v[0] - v[3] - v[4] - v[7];
@@ -669,6 +672,7 @@ struct Entry {
 constexpr uint32_t ENTRY_SLOW = 1u << 20;    // the generic per-cell code writes the cell (k_emit_slow)
 constexpr uint32_t ENTRY_TESTED = 1u << 21;  // pattern chosen by the face / interior tests, written by the fast emit passes (see cell_is_tested)
 constexpr uint32_t ENTRY_COUNT = 1u << 22;   // slow record whose triangles are still to be counted by vertex identity (k_slow_count)
+constexpr uint32_t ENTRY_FACE = 1u << 23;    // (with ENTRY_TESTED) a cell on the x / y / z = 0 faces of the grid: ranks of all its owned edges (make_face_entry)
 MC33_HD Entry make_entry(uint32_t xl, uint32_t i, const CellPlan &p, uint32_t nt, uint32_t voff, uint32_t toff, bool slow) {
 	Entry e;
 	e.w0 = xl | i << 8 | (uint32_t)p.poff << 16 | (uint32_t)p.nnew << 28;
@@ -711,15 +715,15 @@ MC33_HD Entry make_pending_entry(uint32_t xl, uint32_t i) {
 
 // Storage of the work records.  In registers a record is an Entry; in HBM it is split in two 8-byte halves kept in two
 // arrays with the same index:
-//   A: x in the segment (8) | sign index (8) | nnew (4) | triangles (4) | slow flag (1 << 24) | tested flag (1 << 25) | count flag (1 << 26)   ;   vertex offset (16) | triangle offset (16)
+//   A: x in the segment (8) | sign index (8) | nnew (4) | triangles (4) | slow flag (1 << 24) | tested flag (1 << 25) | count flag (1 << 26) | face flag (1 << 27)   ;   vertex offset (16) | triangle offset (16)
 //   B: ranks of edges 0..7   ;   ranks of edges 8..11 (16) | pattern offset (12) << 16 | rank of the centre vertex (4) << 28
 // Half B of a FAST record is a function of its sign index (fast_b_table): it is never written or read - a fast
 // record costs 8 bytes of HBM traffic per pass instead of 16 (writes are what the passes after the sweep pay for most).
 struct EntryA { uint32_t a0, a1; };
 struct EntryB { uint32_t b0, b1; };
-constexpr uint32_t ENTRYA_SLOW = 1u << 24, ENTRYA_TESTED = 1u << 25, ENTRYA_COUNT = 1u << 26;
+constexpr uint32_t ENTRYA_SLOW = 1u << 24, ENTRYA_TESTED = 1u << 25, ENTRYA_COUNT = 1u << 26, ENTRYA_FACE = 1u << 27;
 MC33_HD EntryA entry_a(const Entry &e) {
-	return EntryA{(e.w0 & 0xFFFFu) | (e.w0 >> 28) << 16 | ((e.w3 >> 16) & 15u) << 20 | ((e.w3 >> 20) & 7u) << 24, e.w1};
+	return EntryA{(e.w0 & 0xFFFFu) | (e.w0 >> 28) << 16 | ((e.w3 >> 16) & 15u) << 20 | ((e.w3 >> 20) & 15u) << 24, e.w1};
 }
 MC33_HD EntryB entry_b(const Entry &e) { return EntryB{e.w2, (e.w3 & 0xFFFFu) | ((e.w0 >> 16) & 0xFFFu) << 16 | (e.w3 >> 24) << 28}; }
 MC33_HD Entry entry_join(const EntryA &a, const EntryB &b) {
@@ -727,7 +731,7 @@ MC33_HD Entry entry_join(const EntryA &a, const EntryB &b) {
 	e.w0 = (a.a0 & 0xFFFFu) | ((b.b1 >> 16) & 0xFFFu) << 16 | ((a.a0 >> 16) & 15u) << 28;
 	e.w1 = a.a1;
 	e.w2 = b.b0;
-	e.w3 = (b.b1 & 0xFFFFu) | ((a.a0 >> 20) & 15u) << 16 | ((a.a0 >> 24) & 7u) << 20 | (b.b1 >> 28) << 24;
+	e.w3 = (b.b1 & 0xFFFFu) | ((a.a0 >> 20) & 15u) << 16 | ((a.a0 >> 24) & 15u) << 20 | (b.b1 >> 28) << 24;
 	return e;
 }
 MC33_HD uint32_t entrya_nnew(const EntryA &a) { return (a.a0 >> 16) & 15u; }
@@ -832,6 +836,64 @@ MC33_HD Entry make_tested_entry(uint32_t xl, uint32_t i, uint32_t poff, uint32_t
 	e.w2 = 0xF00FFFFFu | (info & 15u) << 20 | ((info >> 4) & 15u) << 24;
 	e.w3 = 0xF0FFu | ((info >> 8) & 15u) << 8 | ((info >> 16) & 15u) << 16 | ENTRY_TESTED | ((info >> 12) & 15u) << 24;
 	return e;
+}
+
+// The order in which the pattern that starts at table offset p names its slots 0..12 for the first time (MC:780-784):
+//   order[p] = nibble k: the k-th slot named (15: fewer slots).  A cell on the grid's 0-faces without a corner equal to the
+// isovalue creates the vertex of every slot it owns, in that order (plan_visit: no alias, no rule is consulted) - its ranks are
+// this list filtered by the slots it owns (make_face_entry).
+inline void build_pattern_order(const uint16_t *lut, uint32_t n, uint64_t *order) {
+	for (uint32_t p = 0; p < n; p++) {
+		uint32_t visited = 0, ntri = 0, pos = p, word = 0, k = 0;
+		uint64_t o = ~0ull;
+		do {
+			if (++pos >= n) break;
+			word = lut[pos];
+			ntri++;
+			uint32_t w = word;
+			for (int q = 0; q < 3; q++, w >>= 4) {
+				const uint32_t e = w & 15u;
+				if (e > 12u || (visited & (1u << e))) continue;
+				visited |= 1u << e;
+				o = (o & ~(15ull << (4 * k))) | (uint64_t)e << (4 * k);
+				k++;
+			}
+		} while ((word >> 12) && ntri < 15u);
+		order[p] = o;
+	}
+}
+// which of the grid's 0-faces a cell lies on: bit 0 x = 0, bit 1 y = 0, bit 2 z = 0 (edge_own's bits)
+MC33_HD uint32_t face_flags(uint32_t x, uint32_t y, uint32_t z) { return (x == 0 ? 1u : 0u) | (y == 0 ? 2u : 0u) | (z == 0 ? 4u : 0u); }
+// the slots a cell with these face flags owns (plan_visit's owner rule): edge e when every face edge_own(e) names is one of the
+// cell's, and the centre.  flags = 0: edges 5, 6, 10 and the centre.
+MC33_HD uint32_t owned_slots(uint32_t flags) {
+	uint32_t m = 1u << 12;
+	for (uint32_t e = 0; e < 12; e++) m |= (edge_own(e) & ~flags) == 0u ? 1u << e : 0u;
+	return m;
+}
+// Record of a FACE cell (on the x / y / z = 0 faces, no corner equal to the isovalue) from its pattern offset, the pattern's
+// triangles, its slot order (build_pattern_order) and the slots it owns: what make_entry makes of its plan, flagged TESTED | FACE.
+MC33_HD Entry make_face_entry(uint32_t xl, uint32_t i, uint32_t poff, uint32_t ntri, uint64_t order, uint32_t owned, uint32_t voff, uint32_t toff) {
+	uint64_t rank = ~0ull;
+	uint32_t n = 0;
+	for (int k = 0; k < 13; k++) {
+		const uint32_t e = (uint32_t)(order >> (4 * k)) & 15u;
+		if (e < 13u && ((owned >> e) & 1u)) { rank = (rank & ~(15ull << (4 * e))) | (uint64_t)n << (4 * e); n++; }
+	}
+	Entry en;
+	en.w0 = xl | i << 8 | poff << 16 | n << 28;
+	en.w1 = voff | toff << 16;
+	en.w2 = (uint32_t)rank;
+	en.w3 = ((uint32_t)(rank >> 32) & 0xFFFFu) | ntri << 16 | ENTRY_TESTED | ENTRY_FACE | ((uint32_t)(rank >> 48) & 15u) << 24;
+	return en;
+}
+// The owner of foreign edge e of a face cell (flags: face_flags): which of the six neighbours o0 .. o5 of emit_fast_triangles
+// (clamped to the grid: owner_of) and the edge's index there.  Returns o | edge << 4; 15 in the low nibble: the cell owns e.
+MC33_HD uint32_t face_owner(uint32_t e, uint32_t flags) {
+	const uint32_t lx = (flags & 1u) ? 0u : 1u, ly = (flags & 2u) ? 0u : 1u, lz = (flags & 4u) ? 0u : 1u, ca = corner_code(edge_a(e));
+	const OwnerRef o = owner_of(edge_axis(e), lx + (ca & 1u), ly + ((ca >> 1) & 1u), lz + (ca >> 2));
+	const uint32_t key = (lx - o.x) | (ly - o.y) << 1 | (lz - o.z) << 2;  // offset of the owner: (-1, 0, -1) = o0, (-1, 0, 0) = o1, ...
+	return ((0x0503241Fu >> (4 * key)) & 15u) | o.e << 4;
 }
 
 // A TESTED cell: its sign index needs the face / interior tests (so the sweep could not finish it), but it is an interior
@@ -1250,6 +1312,22 @@ struct FastSamples {
 	T F[4][3];
 	T Y2[2][2], Z2[2][2];
 };
+// The same 20 samples as a grid view of cell (x0, y0, z0) - at(x, y, z) for every sample vertex_on_edge reads for this cell - kept
+// in a column of LDS (stride 64: a lane each): sample k = F[r][c] at 3 r + c, Y2[q][c] at 12 + 2 q + c, Z2[q][c] at 16 + 2 q + c.
+template <typename T>
+struct FaceSampleView {
+	T *p;
+	uint32_t x0, y0, z0;
+	static constexpr uint32_t COUNT = 20;
+	MC33_HD static uint32_t slot(uint32_t dx, uint32_t dy, uint32_t dz) { return dz == 2u ? 16u + 2u * dy + dx : dy == 2u ? 12u + 2u * dz + dx : 3u * (dy + 2u * dz) + dx; }
+	MC33_HD T at(uint32_t x, uint32_t y, uint32_t z) const { return p[64u * slot(x - x0, y - y0, z - z0)]; }
+	MC33_HD void put(const FastSamples<T> &S) const {
+		for (uint32_t r = 0; r < 4; r++)
+			for (uint32_t q = 0; q < 3; q++) p[64u * (3u * r + q)] = S.F[r][q];
+		for (uint32_t q = 0; q < 2; q++)
+			for (uint32_t k = 0; k < 2; k++) { p[64u * (12u + 2u * q + k)] = S.Y2[q][k]; p[64u * (16u + 2u * q + k)] = S.Z2[q][k]; }
+	}
+};
 // ... fetched from the grid by the thread itself: 12 loads, all asked for together (the round-2 vertex pass; the host
 // emulator; in the round-3 kernel the records whose rows are not staged in LDS)
 template <typename T>
@@ -1331,17 +1409,46 @@ MC33_HD void fast_vertices_compute(const EmitCtx<T> &c, uint32_t x, uint32_t y, 
 	}
 }
 
+// Vertices of one FACE record (a cell on the grid's 0-faces without a corner equal to the isovalue): every slot it ranks (edges
+// 0..11, the centre), one after the other through vertex_on_edge / vertex_centre themselves, the corner values in registers.  G: the
+// grid, or a view of the record's FastSamples (the vertex pass: FaceSampleView).  Rare (the faces of the grid), so one copy of the
+// code and few registers rather than speed.
+template <typename T, int MODE = -1, typename GV>
+MC33_HD void face_vertices_direct(const EmitCtx<T> &c, const GV &G, uint32_t x, uint32_t y, uint32_t z, uint32_t vbase, const Entry &en) {
+	const Params &P = c.P;
+	Corner8 v;
+	for (uint32_t k = 0; k < 8; k++) {
+		const uint32_t cc = corner_code(k);
+		v.a[k] = iso_diff(P.iso, (real_t)G.at(x + (cc & 1u), y + ((cc >> 1) & 1u), z + (cc >> 2)));  // (as load_cell)
+	}
+	// the slots it ranks, as a mask walked lowest first: the slot number differs from lane to lane (a vector register) - a loop over
+	// all 13 with the same number in every lane put a dozen more scalars into the vertex pass, which has none to spare
+	uint32_t todo = 0;
+	for (uint32_t e = 0; e < 13; e++) todo |= (e < 12u ? entry_rank(en, e) : entry_rank_centre(en)) != 15u ? 1u << e : 0u;
+	while (todo) {
+		const uint32_t e = (uint32_t)__builtin_ctz(todo);
+		todo &= todo - 1u;
+		const uint32_t rk = e < 12u ? entry_rank(en, e) : entry_rank_centre(en);
+		real_t r[6];
+		if (e == 12u) vertex_centre(x, y, z, v, r);
+		else vertex_on_edge(P, G, x, y, z, e, v, r);
+		store_vertex<MODE>(P, r, c.V, c.N, vbase + rk - c.v_skip);
+	}
+}
+
 // Vertices of one FAST record, one thread on its own: the samples by 12 loads of its own (fast_samples_direct), then the
 // arithmetic.  (The host emulator's vertex pass; the GPU runs k_emit_vertices, which stages the rows of 64 records in LDS.)
 template <typename T>
 MC33_HD void emit_fast_vertices(const EmitCtx<T> &c, const Entry &en, uint32_t s) {
 	const uint32_t r5 = (en.w2 >> 20) & 15u, r6 = (en.w2 >> 24) & 15u, r10 = (en.w3 >> 8) & 15u, r12 = entry_rank_centre(en);
-	if ((r5 & r6 & r10 & r12) == 15u) return;  // the cell creates no vertex
+	const bool face = (en.w3 & ENTRY_FACE) != 0u;
+	if (face ? entry_nnew(en) == 0u : (r5 & r6 & r10 & r12) == 15u) return;  // the cell creates no vertex
 	const SegCoord sc = segment_coord(c.P, s);
 	const uint32_t y = sc.y, z = sc.z;
 	if (z < c.z_emit) return;
 	const uint32_t x = sc.xbase + (en.w0 & 0xFFu);
 	const uint32_t vbase = c.seg_base[s].vbase + (en.w1 & 0xFFFFu);
+	if (face) { face_vertices_direct(c, c.G, x, y, z, vbase, en); return; }
 	FastSamples<T> S;
 	fast_samples_direct(c.G, x, y, z, x + 1 < c.P.nx, y + 1 < c.P.ny, z + 1 < c.P.nz, S);
 	fast_vertices_compute(c, x, y, z, vbase, r5, r6, r10, r12, S);
@@ -1358,7 +1465,8 @@ MC33_HD void emit_fast_vertices(const EmitCtx<T> &c, const Entry &en, uint32_t s
 // addresses), so the loads carry no control flow.  The edges have no end point equal to the isovalue (they
 // are edges of a fast cell), so their owners created regular vertices: no alias to follow.
 template <typename T>
-MC33_HD void fast_triangles_write(const EmitCtx<T> &c, const Entry &en, const Entry (&oe)[6], const uint32_t (&ovb)[6], const SegBase &sb, const URef &ids);
+MC33_HD void fast_triangles_write(const EmitCtx<T> &c, const Entry &en, const Entry (&oe)[6], const uint32_t (&ovb)[6], const SegBase &sb, const URef &ids,
+                                  uint32_t fflags);
 // Two records next to each other in ONE load (16 bytes; the records of x - 1 and x in a row segment are neighbours in the
 // array): what costs the triangle pass is the number of load instructions of a wave - each looks up every distinct line its
 // lanes touch - not their width.  (Round 3: 15 -> 12 load instructions per record, triangle pass 91 -> 88 us at 1024^3,
@@ -1388,7 +1496,19 @@ MC33_HD void emit_fast_triangles(const EmitCtx<T> &c, const Entry &en, const Ent
 	const bool cut3 = MC33_SIDE(0) != MC33_SIDE(3), cut4 = MC33_SIDE(4) != MC33_SIDE(5), cut9 = MC33_SIDE(1) != MC33_SIDE(5);
 	const bool cut7 = MC33_SIDE(4) != MC33_SIDE(7), cut11 = MC33_SIDE(3) != MC33_SIDE(7), cut8 = MC33_SIDE(0) != MC33_SIDE(4);
 #undef MC33_SIDE
-	const bool need[6] = {cut0, cut1 || cut2, cut3, cut4 || cut9, cut7 || cut11, cut8};
+	bool need[6] = {cut0, cut1 || cut2, cut3, cut4 || cut9, cut7 || cut11, cut8};
+	uint32_t fflags = 0;
+	if (en.w3 & ENTRY_FACE) {  // a FACE record (rare, wave-divergent): the owners of its cut foreign edges, clamped to the grid (face_owner)
+		const SegCoord sc = segment_coord(c.P, s);
+		fflags = face_flags(sc.xbase + xl, sc.y, sc.z);
+		uint32_t nm = 0;  // bit o: owner o is wanted
+		for (uint32_t e = 0; e < 12; e++) {
+			const uint32_t fo = face_owner(e, fflags) & 15u;
+			const bool cut = ((i >> (7 - edge_a(e))) ^ (i >> (7 - edge_b(e)))) & 1u;
+			nm |= (cut && fo < 6u) ? 1u << fo : 0u;
+		}
+		for (int o = 0; o < 6; o++) need[o] = (nm >> o) & 1u;
+	}
 	// the bases of this row segment and of the one before it (y - 1: segment B) in one load
 	// (asked for here, looked at only behind the neighbours' loads: a select on it up here made the directory words below
 	// wait for it - a round trip of its own in every record's chain, round 4)
@@ -1455,13 +1575,15 @@ MC33_HD void emit_fast_triangles(const EmitCtx<T> &c, const Entry &en, const Ent
 		for (int o = 0; o < 6; o++) oe[o] = entry_join(oa[o], ctx_half_b(c, oa[o], oi[o]));
 	}
 	const SegBase sb = s ? sp.hi : sp.lo;
-	fast_triangles_write(c, en, oe, ovb, sb, ids);
+	fast_triangles_write(c, en, oe, ovb, sb, ids, fflags);
 }
 
 // ... the second half: the triangles of the record from its six owner records oe[] (o0 .. o5 above; a record that is not
-// needed may be anything) and the first vertex of each owner's row segment ovb[]; sb: the record's own segment.
+// needed may be anything) and the first vertex of each owner's row segment ovb[]; sb: the record's own segment; fflags: the face
+// flags of a FACE record (face_flags).
 template <typename T>
-MC33_HD void fast_triangles_write(const EmitCtx<T> &c, const Entry &en, const Entry (&oe)[6], const uint32_t (&ovb)[6], const SegBase &sb, const URef &ids) {
+MC33_HD void fast_triangles_write(const EmitCtx<T> &c, const Entry &en, const Entry (&oe)[6], const uint32_t (&ovb)[6], const SegBase &sb, const URef &ids,
+                                  uint32_t fflags) {
 	const uint32_t i = (en.w0 >> 8) & 0xFFu;
 	uint32_t ob[6];
 	for (int o = 0; o < 6; o++) ob[o] = ovb[o] + (oe[o].w1 & 0xFFFFu);
@@ -1475,6 +1597,18 @@ MC33_HD void fast_triangles_write(const EmitCtx<T> &c, const Entry &en, const En
 	uint32_t tpos = sb.tbase + (en.w1 >> 16) - c.t_skip;
 	ids[5] = vbase + ((en.w2 >> 20) & 15u); ids[6] = vbase + ((en.w2 >> 24) & 15u); ids[10] = vbase + ((en.w3 >> 8) & 15u);
 	ids[12] = vbase + entry_rank_centre(en);
+	if (en.w3 & ENTRY_FACE) {  // every slot again: its own rank, or the clamped owner's record (an edge on a 0-face plane is no 5 / 6 / 10 edge there)
+		for (uint32_t e = 0; e < 12; e++) {
+			const uint32_t fo = face_owner(e, fflags), o = fo & 15u;
+			if (o == 15u) { ids[(int)e] = vbase + entry_rank(en, e); continue; }
+			// (picked by selects of values: a run-time index into oe / ob puts them in scratch memory)
+			const uint32_t base = o == 0u ? ob[0] : o == 1u ? ob[1] : o == 2u ? ob[2] : o == 3u ? ob[3] : o == 4u ? ob[4] : ob[5];
+			const uint32_t w2 = o == 0u ? oe[0].w2 : o == 1u ? oe[1].w2 : o == 2u ? oe[2].w2 : o == 3u ? oe[3].w2 : o == 4u ? oe[4].w2 : oe[5].w2;
+			const uint32_t w3 = o == 0u ? oe[0].w3 : o == 1u ? oe[1].w3 : o == 2u ? oe[2].w3 : o == 3u ? oe[3].w3 : o == 4u ? oe[4].w3 : oe[5].w3;
+			const uint32_t eo = fo >> 4;
+			ids[(int)e] = base + (eo < 8u ? (w2 >> (4 * eo)) & 15u : (w3 >> (4 * (eo - 8u))) & 15u);
+		}
+	}
 	// winding (MC:683-691): n = 1 swaps the first two indices
 	const uint32_t n = ((c.tab.lut[(i & 0x80) ? (i ^ 0xFF) : i] >> 11) ^ (i >> 7) ^ 1u ^ (uint32_t)c.P.normal_neg) & 1u;
 	uint32_t pos = (en.w0 >> 16) & 0xFFFu, word;

@@ -70,6 +70,9 @@ struct TailSet {
 	uint32_t records_hint;    // work records of the last extraction whose counters were read (grid of the triangle pass, first guess of a new set)
 	uint32_t slow_hint;       // ... and its slow records + 1 (0: not known yet): the grid of k_emit_slow
 	bool count_known, count_needed;  // ... and whether it had records waiting for k_slow_count (corners equal to the isovalue): see enqueue_tail
+	bool alias_known;         // ... and whether it had slow cells at all (Counters::alias_cells; alias_last: how many)
+	uint32_t alias_last;
+	bool alias_gated;         // the last tail into this set left the slow kernels out (enqueue_tail): its counts and surface stand only if it had no slow cells
 	Counters *d_ctr, *h_ctr;
 	bool ctr_published;       // the emit pass enqueued last leaves the counters in h_ctr itself (k_emit_fast_triangles)
 };
@@ -99,6 +102,7 @@ struct mc33hip_ctx {
 	uint4 *d_fast;
 	EntryB *d_fast_b;
 	uint32_t *d_pat;
+	uint64_t *d_pat_order;  // build_pattern_order
 	IsoLane lanes[MC33_LANES]; // what a sweep leaves behind, per isovalue (lane 0: the single-isovalue calls)
 	TailSet ts[MC33_LANES];    // ... and what its tail leaves behind (set k belongs to lane k)
 	TailSet *w;                // the set of the lane the last count used: what emit and the counters refer to
@@ -122,6 +126,8 @@ struct mc33hip_ctx {
 	unsigned long long *d_bases;  // {id base, output vertex row, output triangle row} made on the device (mc33hip_bases_from_table)
 	bool async_count;         // the last count was enqueued without waiting for its counters (mc33hip_count_async)
 	bool count_unused;        // the last mc33hip_count has not served an emit yet: a count of the same isovalue and range may reuse it
+	bool alias_gate;          // the call under way reads the counters before it returns and repeats its tail on a miss: the tail may leave the
+	                          // slow kernels out (enqueue_tail)
 	hipEvent_t ev_dl[2];      // mc33hip_emit_download: behind the pass that completes T / behind the one that completes V and N
 	bool emit_pending;        // an emit was enqueued after the last timing read
 	int timing_level;         // MC33_HIP_TIMING: 0 none (default), 1 whole call, 2 per pass - the event records cost ~20 us per call
@@ -266,6 +272,10 @@ extern "C" int mc33hip_create(mc33hip_ctx **out, const mc33hip_grid_desc *d) {
 		build_pattern_info(mc33_lut, lut_n, pat);
 		CREATE_TRY(hipMalloc(&c->d_pat, sizeof pat));
 		CREATE_TRY(hipMemcpy(c->d_pat, pat, sizeof pat, hipMemcpyHostToDevice));
+		uint64_t order[lut_n];
+		build_pattern_order(mc33_lut, lut_n, order);
+		CREATE_TRY(hipMalloc(&c->d_pat_order, sizeof order));
+		CREATE_TRY(hipMemcpy(c->d_pat_order, order, sizeof order, hipMemcpyHostToDevice));
 	}
 	c->w = &c->ts[0];  // (the sets get their memory when a range is known: ensure_set)
 	for (int k = 0; k < 4; k++) CREATE_TRY(hipEventCreate(&c->ev[k]));
@@ -291,7 +301,7 @@ extern "C" void mc33hip_destroy(mc33hip_ctx *c) {
 	else (void)hipDeviceSynchronize();
 	if (c->owns_grid) (void)hipFree(c->d_grid);
 	(void)hipFree(c->d_lut); (void)hipFree(c->d_rules); (void)hipFree(c->d_rule_index); (void)hipFree(c->d_fast);
-	(void)hipFree(c->d_fast_b); (void)hipFree(c->d_pat);
+	(void)hipFree(c->d_fast_b); (void)hipFree(c->d_pat); (void)hipFree(c->d_pat_order);
 	for (int k = 0; k < MC33_LANES; k++) free_set(c->ts[k]);
 	for (int k = 0; k < MC33_LANES; k++) {
 		IsoLane &L = c->lanes[k];

@@ -21,6 +21,7 @@ struct EmitArgs {
 	uint32_t batch_cap;
 	uint32_t stage_rows;  // every sample row of the grid starts on a 16-byte boundary: k_emit_vertices may stage rows in LDS
 	Counters *host_ctr;   // pinned host copy of the counters: the triangle pass (the last kernel of an extraction) leaves them there
+	uint32_t alias_gated; // the tail left the slow kernels out (enqueue_tail): with slow cells after all, its records are not complete - refuse
 #ifdef MC33_DEV
 	uint32_t *below_idx;  // [record][3] (developer experiment MC33_HIP_TRI_BELOW): positions of x in the three neighbouring row segments
 #endif
@@ -57,9 +58,9 @@ __device__ __forceinline__ bool emit_prepare(const EmitArgs &a, EmitCtx<sample_t
 	if (a.dev_base) { idb = a.dev_base[0]; vo = a.dev_base[1]; to = a.dev_base[2]; }
 	// TOGETHER: `|`, not `||` - every counter is asked for before the first is looked at; with short circuits the compiler fetches
 	// them one comparison at a time, a scalar round trip each (the triangle pass, whose waves live for one record per lane)
-	const bool over = TOGETHER ? (bool)((ctr.entry_cursor > a.entry_cap) | (vo + (ctr.totV - gV) > a.capV) | (to + (ctr.totT - gT) > a.capT) | (ctr.totV > 0xFFFFFFFFull) |
+	const bool over = TOGETHER ? (bool)((ctr.entry_cursor > a.entry_cap) | (a.alias_gated & (ctr.alias_cells != 0u)) | (vo + (ctr.totV - gV) > a.capV) | (to + (ctr.totT - gT) > a.capT) | (ctr.totV > 0xFFFFFFFFull) |
 	                                    (ctr.totT > 0xFFFFFFFFull) | (idb + (ctr.totV - gV) > 0xFFFFFFFFull))
-	                           : (ctr.entry_cursor > a.entry_cap || vo + (ctr.totV - gV) > a.capV || to + (ctr.totT - gT) > a.capT || ctr.totV > 0xFFFFFFFFull ||
+	                           : (ctr.entry_cursor > a.entry_cap || (a.alias_gated && ctr.alias_cells) || vo + (ctr.totV - gV) > a.capV || to + (ctr.totT - gT) > a.capT || ctr.totV > 0xFFFFFFFFull ||
 	                              ctr.totT > 0xFFFFFFFFull || idb + (ctr.totV - gV) > 0xFFFFFFFFull);
 	if (over) {
 		if (blockIdx.x == 0 && threadIdx.x == 0) a.ctr->emit_skipped = 1;
@@ -312,8 +313,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC33_EV_WAV
 		const Entry en = entry_join(ea, rec0.b);
 		if (more) rec1 = load_rec(d1);
 		const uint32_t r5 = (en.w2 >> 20) & 15u, r6 = (en.w2 >> 24) & 15u, r10 = (en.w3 >> 8) & 15u, r12 = entry_rank_centre(en);
-		// (a ghost slice of a z-slab - z < z_emit - has its vertices written by the rank below)
-		const bool creates = on && z >= c.z_emit && !(en.w3 & ENTRY_SLOW) && (r5 & r6 & r10 & r12) != 15u;
+		// (a ghost slice of a z-slab - z < z_emit - has its vertices written by the rank below; a FACE record may create the vertices
+		// of any of its edges)
+		const bool face = (en.w3 & ENTRY_FACE) != 0u;
+		const bool creates = on && z >= c.z_emit && !(en.w3 & ENTRY_SLOW) && (face ? entry_nnew(en) != 0u : (r5 & r6 & r10 & r12) != 15u);
 		if (__ballot(creates)) {
 			const uint32_t rho = seg - sidx0, xl = en.w0 & 0xFFu;  // cell row in the tile (0..62), x in the segment
 			const uint32_t x = xbase + xl, y = y0 + rho;
@@ -455,7 +458,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC33_EV_WAV
 			// along axis k: t = vA / (vA - vB); along the edge the gradient is vB - vA, across it (axes u1, u2) central
 			// differences at both ends blended by t, or one-sided ones on the far faces of the grid - vertex_on_edge's
 			// arithmetic in its order (MC:990-1000 edge 5, 1029-1039 edge 6, 1175-1185 edge 10), whatever the axis.
-			const bool direct = creates && (!staged_lane || r12 != 15u);  // (a centre vertex needs all 8 corners: rare, the record's own loads)
+			const bool direct = creates && (!staged_lane || r12 != 15u || face);  // (a centre vertex needs all 8 corners, a face record any edge: rare, the record's own loads)
 			const bool viaimg = creates && !direct;
 			const uint64_t m5 = __ballot(viaimg && r5 != 15u), m6 = __ballot(viaimg && r6 != 15u), m10 = __ballot(viaimg && r10 != 15u);
 			const uint32_t n5 = (uint32_t)__popcll(m5), n6 = (uint32_t)__popcll(m6), nv = n5 + n6 + (uint32_t)__popcll(m10);
@@ -542,11 +545,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC33_EV_WAV
 					}
 				}
 			}
-			if (__ballot(direct)) {  // (wave-uniform: records of rows that are not staged, tested records with a centre vertex)
-				if (direct) {
+			__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the image's reads above before the face records' writes below)
+			if (__ballot(direct)) {  // (wave-uniform: records of rows that are not staged, tested records with a centre vertex, face records)
+				if (direct && !face) {
 					FastSamples<sample_t> S;
 					fast_samples_direct(G, x, y, z, xin, yin, zin, S);
 					fast_vertices_compute<sample_t, MODE>(c, x, y, z, vbase, r5, r6, r10, r12, S);
+				} else if (direct) {
+					// face records: the same 12 loads, the samples into this lane's column of the batch image (its vertices are written:
+					// free until the next batch is staged), every slot the record ranks one after the other from there
+					static_assert(FaceSampleView<sample_t>::COUNT * 64u * sizeof(sample_t) <= sizeof(L.data), "a FACE record's samples in the image");
+					FastSamples<sample_t> S;
+					fast_samples_direct(G, x, y, z, xin, yin, zin, S);
+					const FaceSampleView<sample_t> fv{(sample_t *)L.data + lane, x, y, z};
+					fv.put(S);
+					face_vertices_direct<sample_t, MODE>(c, fv, x, y, z, vbase, en);
 				}
 			}
 		} else next_batch();
@@ -628,7 +641,7 @@ __global__ __launch_bounds__(256) void k_emit_fast_triangles(const EmitArgs a) {
 	}
 }
 
-// k_emit_slow: the records the generic per-cell code writes (cells on the grid's 0-faces, corners equal to the isovalue, aliases), one
+// k_emit_slow: the records the generic per-cell code writes (corners equal to the isovalue, aliases), one
 // thread per record walking its up to 13 pattern slots one after the other (emit_cell).  The form for MANY slow records (noise,
 // integer isovalues on integer grids: 2 M of them at 1024^3 in 0.75 ms); with few the call waits for the length of one thread's chain
 // of 20 - 30 dependent round trips - see k_emit_slow_slots.

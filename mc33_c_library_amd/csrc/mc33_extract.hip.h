@@ -421,7 +421,7 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 		ca.dev = c->sw.cells_dev;
 #endif
 		ca.G.p = c->d_grid; ca.G.pitch = (uint32_t)c->pitch; ca.G.z0 = c->desc.plane0; ca.G.slice = c->slice;
-		ca.P = P; ca.fast = c->d_fast; ca.pat = c->d_pat;
+		ca.P = P; ca.fast = c->d_fast; ca.pat = c->d_pat; ca.pat_order = c->d_pat_order;
 		ca.ze = ze; ca.sd = g.sd;
 		ca.slice_hdr = L.slice_hdr; ca.slice_bits = L.slice_bits; ca.slice_compact = L.slice_compact; ca.plane_fmt = L.plane_fmt; ca.slot_base = w.slot_base;
 		// the tag of this tail's row-segment counts; the array is cleared whenever the tags start over
@@ -463,7 +463,7 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 		sa.lc = w.lc; sa.slot_base = w.slot_base;
 		sa.entry_cap = (uint32_t)w.entry_cap; sa.ctr = w.d_ctr;
 		uint64_t *grV = nb >= SCAN_GROUPED_FROM ? w.bsV + 2 * w.bs_cap : nullptr, *grT = grV ? grV + scan_groups(w.bs_cap) : nullptr;
-		NA.a[q] = ScanArgs{w.seg_cnt, seg_tag, w.bsV, w.bsT, grV, grT, w.seg_base, w.d_ctr};
+		NA.a[q] = ScanArgs{w.seg_cnt, seg_tag, w.lc.slow_cnt, w.lc.n, w.bsV, w.bsT, grV, grT, w.seg_base, w.d_ctr};
 		// k_slots appends to live_list from Counters::live_cursor on, and k_scan_apply - the last kernel of a tail - leaves the
 		// cursor zero for the next.  A tail that was cut short (a launch error) leaves it wherever it was: the next one starts clean.
 		if (w.tail_incomplete) HIP_TRY(hipMemsetAsync(&w.d_ctr->live_cursor, 0, sizeof(uint32_t), st));
@@ -485,11 +485,20 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 	const uint32_t slow_blocks = c->sw.slow_blocks ? c->sw.slow_blocks : 1024u;
 	// planning, identity counts and segment offsets: three launches - or, with MC33_HIP_SLOW_MERGED=1, ONE whose blocks wait for
 	// each other (k_slow_all: 64 blocks at most, all resident together)
+	// The slow kernels serve the cells with a corner equal to the isovalue (cells on the grid's faces are finished by k_cells: FACE
+	// records) - none at all on most fields, where the three launches cost ~25 us of nothing.  A call that reads the counters before it
+	// returns (mc33hip_extract, mc33hip_count: alias_gate) leaves them out when the last extraction of the set had no slow cells; k_scan_apply
+	// counts them all the same (Counters::alias_cells), the emit passes refuse such a tail (emit_prepare), and the call makes it again
+	// with them (a miss).  Everything that hands counts on before a host synchronisation keeps them.
+	bool gate = c->alias_gate && n == 1;
+	for (int q = 0; q < n; q++) gate = gate && c->ts[sidx[q]].alias_known && c->ts[sidx[q]].alias_last == 0u;
+	for (int q = 0; q < n; q++) c->ts[sidx[q]].alias_gated = gate;
 	bool merged = false;  // (measured and lost: see k_slow_all)
 	uint32_t hint = 0;
 	for (int q = 0; q < n; q++) hint = std::max(hint, c->ts[sidx[q]].slow_hint);
 	if (c->sw.slow_merged >= 0) merged = c->sw.slow_merged != 0;
-	if (merged) {
+	if (gate) {
+	} else if (merged) {
 		const uint32_t blocks = std::min(SLOW_ALL_MAX_BLOCKS, std::max(1u, (hint + hint / 4u + 255u) / 256u));  // (any number is right: the phases stride)
 		hipLaunchKernelGGL(k_slow_all, dim3(blocks, ny), dim3(256), 0, st, WA);
 	} else {
@@ -686,6 +695,7 @@ static int enqueue_emit(mc33hip_ctx *c, void *dV, void *dN, void *dT, uint64_t c
 	a.id_base = c->range.id_base;
 	a.batches = c->w->batches; a.batch_cap = (uint32_t)std::min<uint64_t>(c->w->batch_cap, 0xFFFFFFFFull);
 	a.host_ctr = c->w->h_ctr;  // (hipHostMalloc'ed: the same address on the device)
+	a.alias_gated = c->w->alias_gated ? 1u : 0u;
 	c->w->ctr_published = true;
 	// rows may be staged in 16-byte chunks when every row of the grid starts on a 16-byte boundary (always so for the library's
 	// own copy; a caller's device buffer may have any pitch: its records then load for themselves)
@@ -739,7 +749,7 @@ static int enqueue_emit(mc33hip_ctx *c, void *dV, void *dN, void *dT, uint64_t c
 	const uint32_t slow_grid = c->sw.slow_blocks ? c->sw.slow_blocks
 	                           : slow_slots ? std::max(1024u, (c->w->slow_hint + c->w->slow_hint / 8u + 15u) / 16u)
 	                           : c->w->slow_hint ? std::min(1024u, std::max(64u, (c->w->slow_hint + 255u) / 256u * 4u)) : 1024u;
-#define MC33_LAUNCH_SLOW(st) do { if (slow_slots) hipLaunchKernelGGL(k_emit_slow_slots, dim3(slow_grid), dim3(256), 0, st, a); else hipLaunchKernelGGL(k_emit_slow, dim3(slow_grid), dim3(256), 0, st, a); } while (0)
+#define MC33_LAUNCH_SLOW(st) do { if (a.alias_gated) break; if (slow_slots) hipLaunchKernelGGL(k_emit_slow_slots, dim3(slow_grid), dim3(256), 0, st, a); else hipLaunchKernelGGL(k_emit_slow, dim3(slow_grid), dim3(256), 0, st, a); } while (0)
 	if (fork_slow) {  // (first: it is the one with the long chains)
 		MC33_LAUNCH_SLOW(ss);
 		HIP_TRY(hipEventRecord(c->ev_join2, c->aux2));
@@ -826,9 +836,11 @@ static int fetch_counters(mc33hip_ctx *c) {
 	c->w->records_hint = c->w->h_ctr->entry_cursor == 0xFFFFFFFFu ? 0u : c->w->h_ctr->entry_cursor;
 	c->w->slow_hint = c->w->h_ctr->slow_cursor + 1u;
 	c->w->count_known = true; c->w->count_needed = c->w->h_ctr->count_pending != 0u;
+	c->w->alias_known = true; c->w->alias_last = c->w->h_ctr->alias_cells;
 	if (c->sw.verbose)
-		fprintf(stderr, "[mc33hip] cut cells %u (slow %u, dirty segments %u, record batches %u)\n", c->w->h_ctr->entry_cursor,
-		        c->w->h_ctr->slow_cursor, c->w->h_ctr->dirty_cursor, c->w->h_ctr->batch_cursor);
+		fprintf(stderr, "[mc33hip] cut cells %u (slow %u - cells with a corner equal to the isovalue %u -, dirty segments %u, record batches %u%s)\n",
+		        c->w->h_ctr->entry_cursor, c->w->h_ctr->slow_cursor, c->w->h_ctr->alias_cells, c->w->h_ctr->dirty_cursor, c->w->h_ctr->batch_cursor,
+		        c->w->alias_gated ? "; slow kernels left out" : "");
 	if (c->w->h_ctr->debug[0])
 		fprintf(stderr, "[mc33hip] DEBUG words %u: first %u count %u z %u y0 %u xbase %u batch %u of %u\n", c->w->h_ctr->debug[0], c->w->h_ctr->debug[1], c->w->h_ctr->debug[2],
 		        c->w->h_ctr->debug[3], c->w->h_ctr->debug[4], c->w->h_ctr->debug[5], c->w->h_ctr->debug[6], c->w->h_ctr->debug[7]);
@@ -915,11 +927,15 @@ extern "C" int mc33hip_count(mc33hip_ctx *c, double iso, const mc33hip_range *ra
 	if ((rc = ensure_workspaces(c))) return rc;
 	unsigned launches = 0;
 	for (;;) {
-		if ((rc = enqueue_count(c, launches > 0))) return rc;
+		c->alias_gate = true;
+		rc = enqueue_count(c, launches > 0);
+		c->alias_gate = false;
+		if (rc) return rc;
 		launches++;
 		if ((rc = fetch_counters(c))) return rc;
-		if (c->w->h_ctr->entry_cursor <= c->w->entry_cap) break;
-		if ((rc = grow_entries(*c->w, c->w->h_ctr->entry_cursor))) return rc;
+		const bool miss = c->w->alias_gated && c->w->h_ctr->alias_cells != 0u;  // (slow cells, and their kernels left out: the tail again, with them)
+		if (c->w->h_ctr->entry_cursor <= c->w->entry_cap && !miss) break;
+		if (c->w->h_ctr->entry_cursor > c->w->entry_cap && (rc = grow_entries(*c->w, c->w->h_ctr->entry_cursor))) return rc;
 	}
 	read_timing(c, false, launches);
 	if ((rc = finish_counts(c, out))) return rc;
@@ -1080,12 +1096,16 @@ extern "C" int mc33hip_extract(mc33hip_ctx *c, double iso, const mc33hip_range *
 	if ((rc = ensure_workspaces(c))) return rc;
 	unsigned launches = 0;
 	for (;;) {
-		if ((rc = enqueue_count(c, launches > 0))) return rc;
+		c->alias_gate = true;
+		rc = enqueue_count(c, launches > 0);
+		c->alias_gate = false;
+		if (rc) return rc;
 		launches++;
-		if ((rc = enqueue_emit(c, dV, dN, dT, capV, capT))) return rc;  // checks capacities on the device
+		if ((rc = enqueue_emit(c, dV, dN, dT, capV, capT))) return rc;  // checks capacities (and a miss of the slow kernels) on the device
 		if ((rc = fetch_counters(c))) return rc;
-		if (c->w->h_ctr->entry_cursor <= c->w->entry_cap) break;
-		if ((rc = grow_entries(*c->w, c->w->h_ctr->entry_cursor))) return rc;
+		const bool miss = c->w->alias_gated && c->w->h_ctr->alias_cells != 0u;  // (the emit passes refused: the tail again, with the slow kernels)
+		if (c->w->h_ctr->entry_cursor <= c->w->entry_cap && !miss) break;
+		if (c->w->h_ctr->entry_cursor > c->w->entry_cap && (rc = grow_entries(*c->w, c->w->h_ctr->entry_cursor))) return rc;
 	}
 	read_timing(c, true, launches);
 	if ((rc = finish_counts(c, out))) return rc;

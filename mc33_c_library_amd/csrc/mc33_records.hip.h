@@ -16,6 +16,8 @@ struct Counters {
 	uint64_t totV, totT;    // totals over all classified slices (ghost included)
 	uint64_t ghostV, ghostT;
 	uint32_t debug[8];      // (-DMC33_DEV: what a guarded kernel found wrong)
+	uint32_t alias_cells;   // cells k_cells left to the slow kernels - a corner equal to the isovalue (k_scan_apply adds up the list groups)
+	uint32_t pad_;
 };
 
 // One record per (wave tile, cell slice) of the sweep: the sign-bit rows of the two planes of the slice,

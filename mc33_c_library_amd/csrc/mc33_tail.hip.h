@@ -207,6 +207,7 @@ struct CellsArgs {
 	EntryB *entries_b;       // ... half B: written here for TESTED cells, by k_slow_plan for slow ones, never for fast ones
 	const uint32_t *pat;     // what an interior cell makes of each pattern of the reference's table (build_pattern_info): for the
 	                         // cells whose sign index needs the face / interior tests (their table word rides in `fast`)
+	const uint64_t *pat_order;  // ... and the order in which each pattern names its slots (build_pattern_order): for the cells on the 0-faces
 	uint32_t *entry_seg;
 	uint32_t *slow_list, *dirty_list;
 	ListChunks lc;
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 			}
 	}
 
-	// rows whose cells cannot take the fast path: on the y = 0 / z = 0 faces (extra owned edges), or in a
+	// rows whose cells cannot take the fast path: on the y = 0 / z = 0 faces (extra owned edges: FACE records), or in a
 	// tile plane pair that holds a sample equal to the isovalue
 	const uint64_t zc = u64(h.zc_lo, h.zc_hi);  // ... and the sweep lanes that loaded one
 	const uint64_t zr = u64(h.zr_lo, h.zr_hi);  // sample rows with a sample equal to the isovalue: the cells of rows r - 1 and r
@@ -353,8 +354,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 	L.bits[lane][8] = (bc >> lane) & 1ull;  // the halo-column bit of the upper plane's row: the bit after its last word
 	L.incl[lane] = incl;
 	L.run[lane] = 0;
-	// bit 0: no cell of the row can take the fast path (grid faces); bit 2: a corner may equal the isovalue - the cell's
-	// own 8 samples decide; bit 1 is set when a cell of the row went to the slow list
+	// bit 0: no cell of the row can take the fast path (grid faces: its cells make FACE records); bit 2: a corner may equal the
+	// isovalue - the cell's own 8 samples decide; bit 1 is set when a cell of the row went to the slow list
 	L.slowrow[lane] = ((y == 0 || z == 0) ? 1u : 0u) | (((zr >> lane) & 3ull) ? 4u : 0u);
 	const uint32_t first = ebase + incl - cnt;
 	const unsigned long long t_rows = a.trace ? __builtin_amdgcn_s_memrealtime() + (first & 0u) : 0ull;
@@ -397,13 +398,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 		}
 		const uint4 f = s_fast[i];
 		const uint32_t rowflag = L.slowrow[r];
+		// a cell on the grid's 0-faces (its row: y = 0 or z = 0; or x = 0) owns more edges than 5, 6, 10: without a corner equal to
+		// the isovalue it is finished here all the same, as a FACE record (its ranks: make_face_entry)
+		const bool facecell = (rowflag & 1u) || (xbase + xl) == 0;
 		bool zero_corner = false;
 		// (its row may hold such a sample, and so may one of its two columns: then the cell's own 8 samples decide)
-		const bool look = on && (rowflag & 5u) == 4u && f.x != FAST_NONE &&
+		const bool look = on && (rowflag & 4u) && f.x != FAST_NONE &&
 		                  (xl == 255u || ((zc >> lane_of_column(xl, a.pack)) | (zc >> lane_of_column(min(xl + 1u, 255u), a.pack))) & 1ull);
-		// an interior cell whose sign index needs the face / interior tests: the tests are made here on its 8 samples, and
-		// unless one of them equals the isovalue the cell is finished like a fast one (TESTED record, mc33_cell.h)
-		const bool amb = on && !(rowflag & 1u) && f.x == FAST_NONE && (xbase + xl) != 0;
+		// a cell whose sign index needs the face / interior tests: the tests are made here on its 8 samples, and unless one of them
+		// equals the isovalue the cell is finished like a fast one (TESTED record, mc33_cell.h; a FACE record on the 0-faces)
+		const bool amb = on && f.x == FAST_NONE;
 		uint32_t tpoff = 0, tinfo = 0;
 #ifdef MC33_DEV
 		if (a.dev & 1u) zero_corner = look;  // experiment: no look at the samples (every candidate goes the slow way)
@@ -417,10 +421,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 				if (!zero_corner) { tpoff = t.x; tinfo = t.y; }
 			}
 		}
-		const bool tested = tinfo != 0;  // (a pattern has at least one triangle)
-		const bool fastcell = on && !(rowflag & 1u) && !zero_corner && f.x != FAST_NONE && (xbase + xl) != 0;
+		const bool facerec = on && facecell && !zero_corner;
+		const bool tested = tinfo != 0 && !facerec;  // (a pattern has at least one triangle)
+		const bool fastcell = on && !facecell && !zero_corner && f.x != FAST_NONE;
+		Entry fe{};
+		if (facerec) {  // (rare: the grid's faces; wave-divergent)
+			const uint32_t poff = tinfo ? tpoff : (f.x >> 16) & 0xFFFu, ntri = tinfo ? (tinfo >> 16) & 15u : f.w >> 8;
+			fe = make_face_entry(xl, i, poff, ntri, a.pat_order[poff], owned_slots(face_flags(xbase + xl, y0 + r, z)), 0u, 0u);
+		}
 		// new vertices | triangles << 16
-		const uint32_t val = fastcell ? ((f.w & 0xFFu) | (f.w >> 8) << 16) : tested ? (((tinfo >> 20) & 15u) | ((tinfo >> 16) & 15u) << 16) : 0u;
+		const uint32_t val = fastcell ? ((f.w & 0xFFu) | (f.w >> 8) << 16) : tested ? (((tinfo >> 20) & 15u) | ((tinfo >> 16) & 15u) << 16)
+		                   : facerec ? (entry_nnew(fe) | entry_ntri(fe) << 16) : 0u;
 		// offsets inside the row segment: exclusive scan over the cells of the same row
 		const uint32_t sc = wave_scan_add(val);
 		// ... minus the scan value before the first cell of my row inside this batch: both halves of the packed sums only
@@ -429,7 +440,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 		const uint32_t carry = kin > lane ? L.run[r] : 0u;  // the row began in an earlier batch
 		const uint32_t off = carry + (sc - val) - before_head;
 		{  // the slow cells of the batch go on the list of the slot's group, one atomic per wave
-			const bool slowlane = on && !fastcell && !tested && ebase + g < a.entry_cap;
+			const bool slowlane = on && !fastcell && !tested && !facerec && ebase + g < a.entry_cap;
 			const uint64_t sm = __ballot(slowlane);
 			if (sm) {
 				const uint32_t leader = (uint32_t)__builtin_ctzll(sm);
@@ -444,13 +455,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 			Entry e;
 			if (fastcell) { e.w0 = f.x | xl; e.w1 = off; e.w2 = f.y; e.w3 = f.z; }
 			else if (tested) e = make_tested_entry(xl, i, tpoff, tinfo, off & 0xFFFFu, off >> 16);
+			else if (facerec) { e = fe; e.w1 = off; }
 			else {
 				e = make_pending_entry(xl, i);
 				L.slowrow[r] = rowflag | 2u;
 			}
 			if (ri < a.entry_cap) {
 				a.entries_a[ri] = entry_a(e);  // (half B of a fast record follows from its sign index; k_slow_plan writes the slow ones')
-				if (tested) a.entries_b[ri] = entry_b(e);
+				if (tested || facerec) a.entries_b[ri] = entry_b(e);
 				a.entry_seg[ri] = (uint32_t)(sidx0 + r);
 			}
 			if (kin + 1u == rowcnt || lane == 63u) L.run[r] = off + val;  // last cell of the row in this batch
@@ -493,8 +505,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 }
 
 // ---------------------------------------------------------------------------------------------------
-// k_slow_plan: cells the sweep could not finish from the sign index (ambiguous MC33 cases: face and
-// interior tests MC:347-462; cells on the x/y/z = 0 faces; corners equal to the isovalue MC:788-1224)
+// k_slow_plan: cells k_cells could not finish from their own 8 samples - a corner equal to the isovalue (aliases, MC:788-1224);
+// the ambiguous cases (face and interior tests MC:347-462) and the cells on the x/y/z = 0 faces are TESTED / FACE records
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t wave_sum(uint64_t x) {
 #pragma unroll
@@ -732,6 +744,8 @@ struct SweepWalk {
 struct ScanArgs {  // per isovalue
 	const uint32_t *seg_cnt;
 	uint32_t tag;
+	const uint32_t *slow_cnt;  // the slow list's group counts (ListChunks) ...
+	uint32_t slow_groups;      // ... and how many groups
 	uint64_t *bsV, *bsT, *grV, *grT;
 	SegBase *seg_base;
 	Counters *ctr;
@@ -809,6 +823,12 @@ __global__ __launch_bounds__(256) void k_scan_apply(const PerLane<ScanArgs> A, u
 		v += cv[k]; t += ct[k];
 	}
 	if (blockIdx.x == 0 && threadIdx.x == 0) ctr->live_cursor = 0u;  // the last kernel of a tail leaves the cursor of k_slots' list zero for the next
+	if (blockIdx.x == 0 && threadIdx.x < 64u) {  // the slow cells of the tail, for the host (whether the next tail may leave the slow kernels out)
+		uint32_t n = 0;
+		for (uint32_t k = threadIdx.x; k < sa.slow_groups; k += 64u) n += sa.slow_cnt[k];
+		n = (uint32_t)wave_sum((uint64_t)n);
+		if (threadIdx.x == 0) ctr->alias_cells = n;
+	}
 	uint32_t iv = v, it = t;
 	const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
 #pragma unroll
