@@ -77,14 +77,15 @@ struct TailSet {
 	bool ctr_published;       // the emit pass enqueued last leaves the counters in h_ctr itself (k_emit_fast_triangles)
 };
 
-// The environment switches (developer A/B, the tests that force a code path), read ONCE when a context is created: a getenv walks
+// The environment switches (tuning knobs, the tests that force a code path, developer tracing), read ONCE when a context is created: a getenv walks
 // the whole environment, and there were some twenty of them on every call.  0 / -1 / nullptr = not set: the library decides.
 struct Switches {
 	uint32_t rz, sweep_blocks_per_cu, min_depth, cells_blocks, slow_blocks, emit_blocks, emit_v_blocks_per_cu, slow_slots_max;
 	bool no_pack, no_stage, verbose;
-	int slow_count, tails_ahead, no_fork, slow_slots, tri_first, slow_merged;  // -1: not set
+	int slow_count, no_fork, slow_slots, tri_first;  // -1: not set
 	char *trace_cells, *trace_file;                               // (developer tracing: file names; copies)
-	uint32_t debug, cells_dev, sweep_subtract, tri_below, old_vertex_pass;  // (looked at by -DMC33_DEV builds only)
+	uint32_t debug, cells_dev;  // (looked at by -DMC33_DEV builds only)
+	uint32_t pad_[6];           // (the words of five removed developer switches: with the context 24 bytes smaller, the C3 emit stage measured 4 us slower)
 };
 
 struct mc33hip_ctx {
@@ -159,12 +160,11 @@ static void read_switches(Switches &w) {
 	w.cells_blocks = env_u32("MC33_HIP_CELLS_BLOCKS", 0); w.slow_blocks = env_u32("MC33_HIP_SLOW_BLOCKS", 0); w.emit_blocks = env_u32("MC33_HIP_EMIT_BLOCKS", 0);
 	w.emit_v_blocks_per_cu = env_u32("MC33_HIP_EMIT_V_BLOCKS_PER_CU", 0); w.slow_slots_max = env_u32("MC33_HIP_SLOW_SLOTS_MAX", 0);
 	w.no_pack = env_u32("MC33_HIP_NO_PACK", 0) != 0; w.no_stage = env_u32("MC33_HIP_NO_STAGE", 0) != 0; w.verbose = getenv("MC33_HIP_VERBOSE") != nullptr;
-	w.slow_count = env_flag("MC33_HIP_SLOW_COUNT"); w.tails_ahead = env_flag("MC33_HIP_TAILS_AHEAD"); w.no_fork = env_flag("MC33_HIP_NO_FORK");
-	w.slow_slots = env_flag("MC33_HIP_SLOW_SLOTS"); w.tri_first = env_flag("MC33_HIP_TRI_FIRST"); w.slow_merged = env_flag("MC33_HIP_SLOW_MERGED");
+	w.slow_count = env_flag("MC33_HIP_SLOW_COUNT"); w.no_fork = env_flag("MC33_HIP_NO_FORK");
+	w.slow_slots = env_flag("MC33_HIP_SLOW_SLOTS"); w.tri_first = env_flag("MC33_HIP_TRI_FIRST");
 	w.trace_cells = getenv("MC33_HIP_TRACE_CELLS") ? strdup(getenv("MC33_HIP_TRACE_CELLS")) : nullptr;
 	w.trace_file = getenv("MC33_HIP_TRACE_FILE") ? strdup(getenv("MC33_HIP_TRACE_FILE")) : nullptr;
-	w.debug = env_u32("MC33_HIP_DEBUG", 0); w.cells_dev = env_u32("MC33_HIP_CELLS_DEV", 0); w.sweep_subtract = env_u32("MC33_HIP_SWEEP_SUBTRACT", 0);
-	w.tri_below = env_u32("MC33_HIP_TRI_BELOW", 0); w.old_vertex_pass = env_u32("MC33_HIP_OLD_VERTEX_PASS", 0);
+	w.debug = env_u32("MC33_HIP_DEBUG", 0); w.cells_dev = env_u32("MC33_HIP_CELLS_DEV", 0);
 }
 
 static int use_device(mc33hip_ctx *c) {

@@ -2,8 +2,8 @@
 // the emit passes: k_emit_vertices, k_emit_fast_triangles, k_emit_slow_slots / k_emit_slow, and the small kernels of the device-side count exchange.
 
 // ---------------------------------------------------------------------------------------------------
-// emit: one thread per work record.  k_emit_fast_vertices / k_emit_fast_triangles handle the records the
-// sweep finished itself, k_emit_slow the ones k_slow_plan planned (generic path: aliases, cells on the grid faces, ...)
+// emit: k_emit_vertices / k_emit_fast_triangles handle the records k_cells finished itself, k_emit_slow the ones
+// k_slow_plan planned (generic path: corners equal to the isovalue)
 // ---------------------------------------------------------------------------------------------------
 struct EmitArgs {
 	EmitCtx<sample_t> c;
@@ -22,9 +22,6 @@ struct EmitArgs {
 	uint32_t stage_rows;  // every sample row of the grid starts on a 16-byte boundary: k_emit_vertices may stage rows in LDS
 	Counters *host_ctr;   // pinned host copy of the counters: the triangle pass (the last kernel of an extraction) leaves them there
 	uint32_t alias_gated; // the tail left the slow kernels out (enqueue_tail): with slow cells after all, its records are not complete - refuse
-#ifdef MC33_DEV
-	uint32_t *below_idx;  // [record][3] (developer experiment MC33_HIP_TRI_BELOW): positions of x in the three neighbouring row segments
-#endif
 };
 
 // The fast emit passes take the records in storage order, which k_slots made (4 slices of a tile column, next
@@ -73,33 +70,11 @@ __device__ __forceinline__ bool emit_prepare(const EmitArgs &a, EmitCtx<sample_t
 	return true;
 }
 
-#ifdef MC33_DEV
-// vertices of the fast records (positions + normals), one thread per record with 12 loads of its own: the round-2 pass,
-// kept in developer builds for A/B timing against k_emit_vertices (MC33_HIP_OLD_VERTEX_PASS=1)
-__global__ __launch_bounds__(256) void k_emit_fast_vertices(const EmitArgs a) {
-	__shared__ EntryB s_fast_b[256];
-	s_fast_b[threadIdx.x] = a.c.fast_b[threadIdx.x];
-	__syncthreads();
-	const Counters ctr = *a.ctr;
-	EmitCtx<sample_t> c = a.c;
-	c.fast_b = s_fast_b; c.fast_b_in_lds = true;
-	if (!emit_prepare(a, c, ctr)) return;
-	const XcdWalk w(ctr.entry_cursor);
-	for (uint32_t e = w.first; e < w.end; e += w.stride) {
-		const uint32_t seg = c.entry_seg[e];  // (asked for together with the record, not after its flags are known)
-		const EntryA ea = c.entries_a[e];
-		asm volatile("" ::"v"(seg), "v"(ea.a0));  // (both wanted here: the compiler would move the segment's load behind the flag test)
-		const Entry en = entry_join(ea, ctx_half_b(c, ea, e));
-		if (!(en.w3 & ENTRY_SLOW)) emit_fast_vertices(c, en, seg);
-	}
-}
-#endif
-
 // ---------------------------------------------------------------------------------------------------
 // k_emit_vertices: the vertices of the fast and tested records, one WAVE per batch of <= 64 records of one slice slot.
 //
-// The round-2 pass (k_emit_fast_vertices; developer builds keep it for A/B) was one thread per record with 12 short sample
-// loads each; its 64 lanes sit in 64 different sample rows, so every load instruction is 64 cache-line look-ups in the
+// The round-2 pass (EXPERIMENTS.md, "Removed experiment code") was one thread per record with 12 short sample loads each; its 64
+// lanes sit in 64 different sample rows, so every load instruction is 64 cache-line look-ups in the
 // CU's L1 - 65 cycles whatever its width, against 17 when four lanes share a row (tools/tcp_probe.hip,
 // profiles/r03_tcp_probe.txt) - ~800 cycles per 64 records, although the 64 records of a batch share their rows: record
 // (x, y, z) reads rows y, y+1, y+2 of planes z, z+1 and rows y, y+1 of plane z+2, and its neighbour one row up reads two
@@ -138,30 +113,13 @@ __global__ __launch_bounds__(256) void k_emit_fast_vertices(const EmitArgs a) {
 constexpr uint32_t EV_W = MC33_EV_W;
 constexpr uint32_t EV_ROWS = 65;         // sample rows 0..64 of a tile (63 cell rows, y + 2 above the last)
 constexpr uint32_t EV_EMPTY = 0xFFFFFFFFu;
-// The image as a RING of planes (round 5; built, measured, NOT the form that runs: MC33_EV_RING=1 in developer builds).  Plane z
-// lives in slot z % 3 and stays there while the wave goes on to the next batch - a wave takes a CONTIGUOUS piece of the batches
-// (MC33_EV_PIECE; or runs of MC33_EV_RUN batches), i.e. the batches of a slice one after the other and then the next slice of the
-// same tile column (slice_slot: the four slices of a group are adjacent), whose stencils (MC:990-1000, 1029-1039, 1175-1185) read
-// two of the same three planes.  Every (slot, row) carries a tag - which chunks of the row it holds - and a batch loads only the
-// windows its records need that are not there yet.  Bit-identical (148 GPU tests), and slower (profiles/r05_vertex_ring.txt):
-// float 1024^3 123 -> 150 us, 322 -> 518 MB read; ushort 2048 x 2048 x 1024 485 -> 750 us per isovalue, 1.42 -> 1.71 GB.  What the
-// strided walk shares between neighbouring waves at the same moment is whole 128-byte LINES in L2 (32 floats of a row: any shift
-// of the surface from slice to slice stays inside), what the ring keeps is the 48-byte window one batch needed - the next slice's
-// records, a cell or two further along x, miss it half of the time; and a wave that walks consecutive batches alone has no
-// neighbour to share lines with (the reads grow with the run: 326 / 438 / 497 / 495 MB for runs of 1 / 4 / 8 / 16).  The tags and
-// selects cost 14 % more vector instructions on top (46.2 M against 40.5 M per launch; 138 us with the ring's code on the strided
-// walk, where it can reuse nothing).
-#ifndef MC33_EV_RING
-#define MC33_EV_RING 0
-#endif
-constexpr uint32_t TS = MC33_EV_RING ? 1u : 0u;  // (the ring's tags exist only with the ring: every index into them goes through this)
+// (Tried in round 5: the image as a ring of planes carried from batch to batch - slower: EXPERIMENTS.md, profiles/r05_vertex_ring.txt)
 struct EmitVLds {                        // per wave
 	uint32_t rowA[64], rowB[64];         // cell rows 0..62 of the tile: first / last record of the batch in that row, lane << 8 | x in the segment
 	uint32_t rowvb[64];                  // cell rows: id of the first vertex of the row segment (seg_base)
 	uint32_t rowinfo[EV_ROWS + 1];       // sample rows: staged << 31 | chunks - 1 << 16 | first chunk - chunk of the segment's first sample
 	uint32_t vlist[256];                 // vertices of the batch: record (lane) | kind << 8, by kind
-	uint32_t tag[MC33_EV_RING ? 3 : 1][MC33_EV_RING ? EV_ROWS + 1 : 1];  // (ring only) what slot s holds of sample row r: valid << 31 | chunks - 1 << 16 | first chunk (as rowinfo)
-	uint4 data[3 * EV_ROWS * EV_W];      // [slot][row][chunk]
+	uint4 data[3 * EV_ROWS * EV_W];      // [plane][row][chunk]
 };
 
 // Which wave takes which batch: each XCD gets one contiguous eighth of the batches (its own L2: see XcdWalk), and the waves
@@ -172,45 +130,16 @@ struct EmitVLds {                        // per wave
 // over their ~20 batches; blocks of 4 batches in launch order, nothing prefetched: 383 MB (the vertex writes then cost
 // exactly their bytes) but 157 us, every block paying its start-up chain; the same with 2-4 rounds per block 139 us;
 // batches handed out in order by per-XCD atomic counters: 402 MB but 171 us (the compiler waits for every atomic on the
-// spot).  MC33_EV_BLOCKED: every block a contiguous piece of its XCD's eighth instead.
-#ifndef MC33_EV_RUN
-#define MC33_EV_RUN 1  // batches a wave takes back to back before it strides on (developer A/B, round 4: consecutive batches are consecutive slices of a tile column)
-#endif
+// spot).  Runs of consecutive batches per wave and contiguous pieces per block or wave were slower too (EXPERIMENTS.md).
 struct XcdBatchWalk {
 	uint32_t first, end, stride;
-	// the t-th batch of this wave: runs of MC33_EV_RUN consecutive batches, the runs dealt to the waves of the XCD in turn
-	__device__ uint32_t at(uint32_t t) const {
-		constexpr uint32_t R = MC33_EV_RUN;
-		if (R == 1) return first + t * stride;
-		return base + ((t / R) * waves + wave) * R + (t % R);
-	}
-	uint32_t base, waves, wave;
+	__device__ uint32_t at(uint32_t t) const { return first + t * stride; }  // the t-th batch of this wave
 	__device__ XcdBatchWalk(uint32_t n) {
 		const uint32_t per_xcd = (n + 7u) / 8u;
 		const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, blocks_per_xcd = (gridDim.x + 7u) >> 3;
-		const uint32_t xend = min((xcd + 1u) * per_xcd, n);
-#ifdef MC33_EV_BLOCKED
-		const uint32_t piece = ((per_xcd + blocks_per_xcd - 1u) / blocks_per_xcd + 3u) & ~3u;  // batches per block
-		first = xcd * per_xcd + slot * piece + (threadIdx.x >> 6);
-		end = min(xcd * per_xcd + (slot + 1u) * piece, xend);
-		stride = 4u;
-#else
+		end = min((xcd + 1u) * per_xcd, n);
 		first = xcd * per_xcd + slot * 4u + (threadIdx.x >> 6);
-		end = xend;
 		stride = blocks_per_xcd * 4u;
-#endif
-		base = xcd * per_xcd; waves = blocks_per_xcd * 4u; wave = slot * 4u + (threadIdx.x >> 6);
-		if (MC33_EV_RUN > 1) first = at(0u);
-#ifndef MC33_EV_PIECE
-#define MC33_EV_PIECE MC33_EV_RING
-#endif
-#if MC33_EV_PIECE
-		// every wave ONE contiguous piece of its XCD's eighth (the image in LDS is carried from batch to batch)
-		const uint32_t piece = (per_xcd + waves - 1u) / waves;
-		first = min(base + wave * piece, xend);
-		end = min(first + piece, xend);
-		stride = 1u;
-#endif
 	}
 };
 
@@ -292,8 +221,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC33_EV_WAV
 		}
 		asm volatile("" ::"v"(r.seg), "v"(r.rowvb));
 	};
-	// ring of planes: the image holds the planes ring_z .. ring_z + 2 of tile column (ring_y0, ring_xbase) - those of the batch staged last (wave-uniform)
-	uint32_t ring_z = 0u, ring_y0 = 0xFFFFFFFFu, ring_xbase = 0xFFFFFFFFu;
 	uint32_t t = 0, j = w.at(0u);
 	BatchInfo d0 = load_batch(a.batches, j), d1 = d0;
 	if (w.at(1u) < w.end) d1 = load_batch(a.batches, w.at(1u));
@@ -385,35 +312,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC33_EV_WAV
 				const uint32_t pitchB = G.pitch * SZ;
 				constexpr uint32_t NITEM = EV_ROWS * EV_W, NGRP = (NITEM + 63u) / 64u;
 				static_assert(NGRP <= 5, "groups of the staging loads");
-				// ring: plane z + k of this slice lives in slot (z + k) % 3.  A slot that holds another plane, or a plane of another
-				// tile column, is empty: its tags are cleared (wave-uniform decisions) before anybody looks at them.
-				const uint32_t s0 = MC33_EV_RING ? z % 3u : 0u, s1 = s0 == 2u ? 0u : s0 + 1u, s2 = s1 == 2u ? 0u : s1 + 1u;
-				if (MC33_EV_RING) {
-					const bool other = ring_y0 != y0 || ring_xbase != xbase;
-					const uint32_t sk[3] = {s0, s1, s2};
-#pragma unroll
-					for (uint32_t k = 0; k < 3u; k++)
-						if (other || z + k - ring_z > 2u) {  // (unsigned: also a plane below the ones held)
-							L.tag[sk[k]][lane] = 0u;
-							if (lane < EV_ROWS + 1u - 64u) L.tag[sk[k]][64u + lane] = 0u;
-						}
-					ring_z = z; ring_y0 = y0; ring_xbase = xbase;
-					__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-				}
 				// (the row words of all groups first: one LDS wait, not one per group)
 				uint32_t info[NGRP];
-				uint32_t have0[NGRP], have1[NGRP], have2[NGRP];
 #pragma unroll
-				for (uint32_t g = 0; g < NGRP; g++) {
-					const uint32_t rr = min((g * 64u + lane) / EV_W, EV_ROWS - 1u);
-					info[g] = L.rowinfo[rr];
-					if (MC33_EV_RING) { have0[g] = L.tag[(s0) * TS][(rr) * TS]; have1[g] = L.tag[(s1) * TS][(rr) * TS]; have2[g] = L.tag[(s2) * TS][(rr) * TS]; }
-				}
-				// does the window a slot holds of a row (tag) cover the one the batch needs (rowinfo)?
-				auto covers = [](uint32_t have, uint32_t want) -> bool {
-					const uint32_t hl = have & 0xFFFFu, wl = want & 0xFFFFu;
-					return (have >> 31) && hl <= wl && wl + ((want >> 16) & 3u) <= hl + ((have >> 16) & 3u);
-				};
+				for (uint32_t g = 0; g < NGRP; g++) info[g] = L.rowinfo[min((g * 64u + lane) / EV_W, EV_ROWS - 1u)];
 				const uint4 zero4 = {0u, 0u, 0u, 0u};
 				uint4 qa0 = zero4, qa1 = zero4, qa2 = zero4, qb0 = zero4, qb1 = zero4, qb2 = zero4, qc0 = zero4, qc1 = zero4, qc2 = zero4;
 				uint4 qd0 = zero4, qd1 = zero4, qd2 = zero4, qe0 = zero4, qe1 = zero4, qe2 = zero4;
@@ -429,19 +331,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC33_EV_WAV
 					uint32_t got = 0u;
 					if (need) {
 						const char *addr = plane0 + (uint64_t)r * pitchB + (uint64_t)((info[g] & 0xFFFFu) + ck) * 16u;
-						if (!MC33_EV_RING || !covers(have0[g], info[g])) { q0 = *(const uint4 *)addr; got |= 1u; }
-						if (!MC33_EV_RING || !covers(have1[g], info[g])) { q1 = *(const uint4 *)(addr + sliceB); got |= 2u; }
-						if (zin && (!MC33_EV_RING || !covers(have2[g], info[g]))) { q2 = *(const uint4 *)(addr + 2u * sliceB); got |= 4u; }
+						q0 = *(const uint4 *)addr; got |= 1u;
+						q1 = *(const uint4 *)(addr + sliceB); got |= 2u;
+						if (zin) { q2 = *(const uint4 *)(addr + 2u * sliceB); got |= 4u; }
 					}
 					return got;
 				};
-				// (the chunk goes to its slot, and the lane of a row's first chunk notes what the slot now holds of the row)
 				auto put = [&](uint32_t g, uint32_t got, const uint4 &q0, const uint4 &q1, const uint4 &q2) {
 					const uint32_t it = g * 64u + lane;
-					const uint32_t r = it / EV_W, ck = it - r * EV_W;
-					if (got & 1u) { L.data[s0 * NITEM + it] = q0; if (MC33_EV_RING && ck == 0u) L.tag[(s0) * TS][(r) * TS] = info[g]; }
-					if (got & 2u) { L.data[s1 * NITEM + it] = q1; if (MC33_EV_RING && ck == 0u) L.tag[(s1) * TS][(r) * TS] = info[g]; }
-					if (got & 4u) { L.data[s2 * NITEM + it] = q2; if (MC33_EV_RING && ck == 0u) L.tag[(s2) * TS][(r) * TS] = info[g]; }
+					if (got & 1u) L.data[it] = q0;
+					if (got & 2u) L.data[NITEM + it] = q1;
+					if (got & 4u) L.data[2u * NITEM + it] = q2;
 				};
 				const uint32_t na = fetch(0u, qa0, qa1, qa2), nb = fetch(1u, qb0, qb1, qb2), nc = fetch(2u, qc0, qc1, qc2);
 				const uint32_t nd = NGRP > 3 ? fetch(3u, qd0, qd1, qd2) : 0u, ne = NGRP > 4 ? fetch(4u, qe0, qe1, qe2) : 0u;
@@ -471,11 +371,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC33_EV_WAV
 				const uint32_t rw0 = xl | rho << 8 | r5 << 16 | r6 << 20 | r10 << 24 | (xin ? 1u << 28 : 0u) | (yin ? 1u << 29 : 0u);
 				const uint32_t rw1 = (i0 & 0xFFu) | (i1 & 0xFFu) << 8 | (i2 & 0xFFu) << 16;  // first chunk of rows rho, rho + 1, rho + 2 | rho
 				const char *img = (const char *)L.data;
-#ifdef MC33_EV_ONE_ITER  // (developer timing experiment, results wrong: what would the pass take if no batch had more than 64 vertices?)
-				for (uint32_t v0 = 0; v0 < min(nv, 64u); v0 += 64u) {
-#else
 				for (uint32_t v0 = 0; v0 < nv; v0 += 64u) {  // wave-uniform
-#endif
 					const bool act = v0 + lane < nv;
 					const uint32_t ent = L.vlist[act ? v0 + lane : 0u];
 					const uint32_t src = (ent & 63u) << 2, kind = ent >> 8;
@@ -488,31 +384,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC33_EV_WAV
 						// sample (dx, dy, dz) of the cell: byte in the image
 						const uint32_t xb0 = vxl * SZ + ((xbase * SZ) & 15u);
 						// (the byte of sample x in the three rows of the cell, once; a plane is EV_ROWS * EV_W chunks on)
-#if MC33_EV_RING
-						// ring: plane z + dz sits in slot (z + dz) % 3, and what a slot holds of a row begins at the chunk its TAG names
-						// (the window may have been staged for an earlier batch with other records)
-						const uint32_t zs0 = z % 3u, zs1 = zs0 == 2u ? 0u : zs0 + 1u, zs2 = zs1 == 2u ? 0u : zs1 + 1u;
-						const uint32_t vr2 = vyin ? vrho + 2u : vrho;
-						auto rowbyte = [&](uint32_t sl, uint32_t rw) -> uint32_t {  // byte of the cell's sample x in slot sl, row rw
-							return sl * (EV_ROWS * EV_W * 16u) + (rw * EV_W - (L.tag[(sl) * TS][(rw) * TS] & 0xFFFFu)) * 16u + xb0;
-						};
-						// (nine named values and selects: an array indexed by dy / dz - some are per-lane values - lived in scratch memory)
-						const uint32_t b00 = rowbyte(zs0, vrho), b01 = rowbyte(zs0, vrho + 1u), b02 = rowbyte(zs0, vr2);
-						const uint32_t b10 = rowbyte(zs1, vrho), b11 = rowbyte(zs1, vrho + 1u), b12 = rowbyte(zs1, vr2);
-						const uint32_t b20 = rowbyte(zs2, vrho), b21 = rowbyte(zs2, vrho + 1u), b22 = rowbyte(zs2, vr2);
-						(void)w1;
-						auto smp = [&](uint32_t dx, uint32_t dy, uint32_t dz) -> sample_t {
-							const uint32_t p0 = dy == 0u ? b00 : dy == 1u ? b01 : b02, p1 = dy == 0u ? b10 : dy == 1u ? b11 : b12, p2 = dy == 0u ? b20 : dy == 1u ? b21 : b22;
-							return *(const sample_t *)(img + (dz == 0u ? p0 : dz == 1u ? p1 : p2) + dx * SZ);
-						};
-#else
 						const uint32_t rb0 = (vrho * EV_W - (w1 & 0xFFu)) * 16u + xb0, rb1 = ((vrho + 1u) * EV_W - ((w1 >> 8) & 0xFFu)) * 16u + xb0,
 						               rb2 = ((vrho + 2u) * EV_W - ((w1 >> 16) & 0xFFu)) * 16u + xb0;
 						auto smp = [&](uint32_t dx, uint32_t dy, uint32_t dz) -> sample_t {
 							const uint32_t rb = dy == 0u ? rb0 : dy == 1u ? rb1 : rb2;
 							return *(const sample_t *)(img + rb + dz * (EV_ROWS * EV_W * 16u) + dx * SZ);
 						};
-#endif
 						// corner A of the edge: (1,1,0) edge 5 | (1,0,1) edge 6 | (0,1,1) edge 10; B = (1,1,1)
 						const uint32_t ax = kind != 2u, ay = kind != 1u, az = kind != 0u;
 						const real_t iso = P.iso;
@@ -576,11 +453,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC33_EV_WAV
 // instructions per 64 records.  Bit-identical, and slower: 568 against 395 us per isovalue at C5.  A batch is a chain of
 // dependent steps - directory words, run bounds, staging, LDS, ids - and 16 waves per CU do not hide it; one thread per
 // record at 32 waves per CU does.  Dropped.)
-#ifdef MC33_DEV
-template <int BELOW = 0>  // developer experiment: 1 = keep the owner positions found through the directory, 2 = take them from that array instead
-#else
-[[maybe_unused]] constexpr int BELOW = 0;
-#endif
 __global__ __launch_bounds__(256) void k_emit_fast_triangles(const EmitArgs a) {
 	__shared__ uint32_t s_id[13][256];
 	__shared__ EntryB s_fast_b[256];
@@ -598,11 +470,8 @@ __global__ __launch_bounds__(256) void k_emit_fast_triangles(const EmitArgs a) {
 	const uint32_t e0 = ok && e < w.end ? e : 0u;  // (records 0 and 1 exist in every allocation)
 	uint32_t seg = c.entry_seg[e0];
 	EntryA2 pair = entry_pair(c.entries_a + (e0 ? e0 - 1u : 0u));  // the record and the one before it (the owner of two of its edges, mostly)
-	uint32_t kb[3] = {0u, 0u, 0u};
-#ifdef MC33_DEV
-	if (BELOW == 2) { kb[0] = a.below_idx[3ull * e0]; kb[1] = a.below_idx[3ull * e0 + 1u]; kb[2] = a.below_idx[3ull * e0 + 2u]; }  // (with the record)
-#endif
-	asm volatile("" ::"v"(seg), "v"(pair.lo.a0), "v"(pair.hi.a0), "v"(kb[0]), "v"(kb[1]), "v"(kb[2]));
+	// (the zero operand is a leftover of a removed experiment, kept: without it the compiler orders the first record's loads differently)
+	asm volatile("" ::"v"(seg), "v"(pair.lo.a0), "v"(pair.hi.a0), "v"(0u));
 	s_fast_b[threadIdx.x] = fb;
 	__syncthreads();
 	// The counters of the extraction for the host, straight into its pinned copy (everything before this kernel on the stream
@@ -624,19 +493,11 @@ __global__ __launch_bounds__(256) void k_emit_fast_triangles(const EmitArgs a) {
 	while (e < w.end) {
 		const EntryA ea = e ? pair.hi : pair.lo;
 		const Entry en = entry_join(ea, ctx_half_b(c, ea, e));
-#ifdef MC33_DEV
-		if (BELOW == 1) { uint32_t kept[3] = {e, e, e}; if (!(en.w3 & ENTRY_SLOW)) emit_fast_triangles(c, en, pair.lo, seg, e, ids, nullptr, kept); for (int g = 0; g < 3; g++) a.below_idx[3ull * e + g] = kept[g]; }
-		else if (BELOW == 2) { if (!(en.w3 & ENTRY_SLOW)) emit_fast_triangles(c, en, pair.lo, seg, e, ids, kb); }
-		else
-#endif
 		if (!(en.w3 & ENTRY_SLOW)) emit_fast_triangles(c, en, pair.lo, seg, e, ids);
 		e += w.stride;
 		if (e >= w.end) break;
 		seg = c.entry_seg[e];
 		pair = entry_pair(c.entries_a + e - 1u);
-#ifdef MC33_DEV
-		if (BELOW == 2) { kb[0] = a.below_idx[3ull * e]; kb[1] = a.below_idx[3ull * e + 1u]; kb[2] = a.below_idx[3ull * e + 2u]; }
-#endif
 		asm volatile("" ::"v"(seg), "v"(pair.lo.a0), "v"(pair.hi.a0));
 	}
 }

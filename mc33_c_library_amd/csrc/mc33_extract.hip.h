@@ -347,11 +347,7 @@ static uint32_t launch_sweep_ni(mc33hip_ctx *c, const SweepArgs &a, hipStream_t 
 		negzero |= iso == 0 && sign_of(iso);
 		can_equal |= iso >= 0 && iso <= (real_t)std::numeric_limits<sample_t>::max() && iso == std::floor(iso);
 	}
-	bool subtract = negzero;
-#ifdef MC33_DEV
-	subtract |= c->sw.sweep_subtract != 0;  // (A/B of the two forms; same results)
-#endif
-	if (!subtract) {
+	if (!negzero) {
 		if (can_equal) return launch_sweep_zm<NI, 1>(c, a, st);
 		return launch_sweep_zm<NI, 2>(c, a, st);
 	}
@@ -483,8 +479,7 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 	// whose 8 820 slow cells are 35 blocks' worth - changes nothing: 13.5 / 6 / 8.7 us either way.  What these kernels take is
 	// the chain of dependent loads of the cells that ARE slow, not their empty blocks; round 3)
 	const uint32_t slow_blocks = c->sw.slow_blocks ? c->sw.slow_blocks : 1024u;
-	// planning, identity counts and segment offsets: three launches - or, with MC33_HIP_SLOW_MERGED=1, ONE whose blocks wait for
-	// each other (k_slow_all: 64 blocks at most, all resident together)
+	// planning, identity counts and segment offsets: three launches (as one launch with grid barriers: slower, EXPERIMENTS.md).
 	// The slow kernels serve the cells with a corner equal to the isovalue (cells on the grid's faces are finished by k_cells: FACE
 	// records) - none at all on most fields, where the three launches cost ~25 us of nothing.  A call that reads the counters before it
 	// returns (mc33hip_extract, mc33hip_count: alias_gate) leaves them out when the last extraction of the set had no slow cells; k_scan_apply
@@ -493,23 +488,14 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 	bool gate = c->alias_gate && n == 1;
 	for (int q = 0; q < n; q++) gate = gate && c->ts[sidx[q]].alias_known && c->ts[sidx[q]].alias_last == 0u;
 	for (int q = 0; q < n; q++) c->ts[sidx[q]].alias_gated = gate;
-	bool merged = false;  // (measured and lost: see k_slow_all)
-	uint32_t hint = 0;
-	for (int q = 0; q < n; q++) hint = std::max(hint, c->ts[sidx[q]].slow_hint);
-	if (c->sw.slow_merged >= 0) merged = c->sw.slow_merged != 0;
-	if (gate) {
-	} else if (merged) {
-		const uint32_t blocks = std::min(SLOW_ALL_MAX_BLOCKS, std::max(1u, (hint + hint / 4u + 255u) / 256u));  // (any number is right: the phases stride)
-		hipLaunchKernelGGL(k_slow_all, dim3(blocks, ny), dim3(256), 0, st, WA);
-	} else {
-	hipLaunchKernelGGL(k_slow_plan, dim3(slow_blocks, ny), dim3(256), 0, st, WA);
-	{  // k_slow_count only when the last extraction of (one of) the set(s) had records for it, or nothing is known: k_seg_fix counts what is left over
+	if (!gate) {
+		hipLaunchKernelGGL(k_slow_plan, dim3(slow_blocks, ny), dim3(256), 0, st, WA);
+		// k_slow_count only when the last extraction of (one of) the set(s) had records for it, or nothing is known: k_seg_fix counts what is left over
 		bool wanted = false;
 		for (int q = 0; q < n; q++) wanted |= !c->ts[sidx[q]].count_known || c->ts[sidx[q]].count_needed;
 		if (c->sw.slow_count >= 0) wanted = c->sw.slow_count != 0;
 		if (wanted) hipLaunchKernelGGL(k_slow_count, dim3(slow_blocks, ny), dim3(256), 0, st, WA);
-	}
-	hipLaunchKernelGGL(k_seg_fix, dim3(slow_blocks, ny), dim3(256), 0, st, WA);
+		hipLaunchKernelGGL(k_seg_fix, dim3(slow_blocks, ny), dim3(256), 0, st, WA);
 	}
 	hipLaunchKernelGGL(k_scan_reduce, dim3(nb, ny), dim3(256), 0, st, NA, c->nsegs, c->P);
 	hipLaunchKernelGGL(k_scan_apply, dim3(nb, ny), dim3(256), 0, st, NA, c->nsegs, c->P, c->ghost_segs);
@@ -617,7 +603,6 @@ static int enqueue_sweep_many(mc33hip_ctx *c, const double *isos, int n, bool ta
 	if (int rc = plan_sweep(c, c->P.zs, c->range.z_end)) return rc;
 	SlotGeom g;
 	if (int rc = slot_geometry(c, g)) return rc;
-	if (c->sw.tails_ahead >= 0) tails_ahead = c->sw.tails_ahead != 0;  // (developer A/B of the two flows)
 	if (tails_ahead) {
 		// records to make room for in a new set: what the last extraction of this context needed
 		uint64_t hint = 0;
@@ -771,48 +756,26 @@ static int enqueue_emit(mc33hip_ctx *c, void *dV, void *dN, void *dT, uint64_t c
 		if (dl->bN) HIP_TRY(hipMemcpyAsync(dl->hN, dN, dl->bN, hipMemcpyDeviceToHost, c->copy));
 		return 0;
 	};
-#ifdef MC33_DEV
-	// developer experiment (MC33_HIP_TRI_BELOW=1): what would the triangle pass take if every record knew where its owners' records
-	// are?  A first pass keeps the positions it finds through the directory (k_emit_fast_triangles<1>), a second one takes them from
-	// that array with the record and never looks at the directory (<2>: same triangles) - the second is the one to time.
-	static uint32_t *s_below = nullptr; static uint64_t s_below_cap = 0;
-	const bool tri_below = c->sw.tri_below != 0;
-	a.below_idx = nullptr;
-	if (tri_below) {
-		if (s_below_cap < c->w->entry_cap) { (void)hipFree(s_below); s_below = nullptr; HIP_TRY(hipMalloc(&s_below, c->w->entry_cap * 12ull)); s_below_cap = c->w->entry_cap; }
-		a.below_idx = s_below;
-	}
-#define MC33_LAUNCH_TRI(st) do { if (tri_below) { hipLaunchKernelGGL(k_emit_fast_triangles<1>, dim3(blocks), dim3(256), 0, st, a); hipLaunchKernelGGL(k_emit_fast_triangles<2>, dim3(blocks), dim3(256), 0, st, a); } else hipLaunchKernelGGL(k_emit_fast_triangles<0>, dim3(blocks), dim3(256), 0, st, a); } while (0)
-#else
-#define MC33_LAUNCH_TRI(st) hipLaunchKernelGGL(k_emit_fast_triangles, dim3(blocks), dim3(256), 0, st, a)
-#endif
 	if (tri_first) {
-		MC33_LAUNCH_TRI(sv);
+		hipLaunchKernelGGL(k_emit_fast_triangles, dim3(blocks), dim3(256), 0, sv, a);
 		if (dl_split) { if (int rc = copy_T()) return rc; }
 	}
-#ifdef MC33_DEV
-	if (c->sw.old_vertex_pass) hipLaunchKernelGGL(k_emit_fast_vertices, dim3(blocks), dim3(256), 0, c->stream, a);  // (the round-2 pass, for A/B timing)
-	else
-#endif
-	{
-		// as many blocks as the device holds at once (one more round of blocks would run with most of the GPU idle); every wave
-		// walks many batches, its next batch's records in flight while it works on one
-		if (!c->emit_v_blocks_per_cu) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c->emit_v_blocks_per_cu, k_emit_vertices<3>, 256, 0));
-		const uint32_t vblocks = (uint32_t)std::max(1, c->cus) * (c->sw.emit_v_blocks_per_cu ? c->sw.emit_v_blocks_per_cu : (uint32_t)std::max(1, c->emit_v_blocks_per_cu));
-		const dim3 vgrid((vblocks + 7u) & ~7u);
-		switch (c->P.store_mode) {
-		case 0: hipLaunchKernelGGL(k_emit_vertices<0>, vgrid, dim3(256), 0, c->stream, a); break;
-		case 1: hipLaunchKernelGGL(k_emit_vertices<1>, vgrid, dim3(256), 0, c->stream, a); break;
-		case 2: hipLaunchKernelGGL(k_emit_vertices<2>, vgrid, dim3(256), 0, c->stream, a); break;
-		default: hipLaunchKernelGGL(k_emit_vertices<3>, vgrid, dim3(256), 0, c->stream, a); break;
-		}
+	// as many blocks as the device holds at once (one more round of blocks would run with most of the GPU idle); every wave
+	// walks many batches, its next batch's records in flight while it works on one
+	if (!c->emit_v_blocks_per_cu) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c->emit_v_blocks_per_cu, k_emit_vertices<3>, 256, 0));
+	const uint32_t vblocks = (uint32_t)std::max(1, c->cus) * (c->sw.emit_v_blocks_per_cu ? c->sw.emit_v_blocks_per_cu : (uint32_t)std::max(1, c->emit_v_blocks_per_cu));
+	const dim3 vgrid((vblocks + 7u) & ~7u);
+	switch (c->P.store_mode) {
+	case 0: hipLaunchKernelGGL(k_emit_vertices<0>, vgrid, dim3(256), 0, c->stream, a); break;
+	case 1: hipLaunchKernelGGL(k_emit_vertices<1>, vgrid, dim3(256), 0, c->stream, a); break;
+	case 2: hipLaunchKernelGGL(k_emit_vertices<2>, vgrid, dim3(256), 0, c->stream, a); break;
+	default: hipLaunchKernelGGL(k_emit_vertices<3>, vgrid, dim3(256), 0, c->stream, a); break;
 	}
 	if (dl_split) { if (int rc = copy_VN()) return rc; }
 	if (!tri_first) {
-		MC33_LAUNCH_TRI(sv);
+		hipLaunchKernelGGL(k_emit_fast_triangles, dim3(blocks), dim3(256), 0, sv, a);
 		if (dl_split) { if (int rc = copy_T()) return rc; }
 	}
-#undef MC33_LAUNCH_TRI
 	if (fork_all) HIP_TRY(hipEventRecord(c->ev_join, c->aux));
 	if (!fork_slow && !dl_split) MC33_LAUNCH_SLOW(ss);
 #undef MC33_LAUNCH_SLOW

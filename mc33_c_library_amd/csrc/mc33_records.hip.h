@@ -12,7 +12,7 @@ struct Counters {
 	uint32_t emit_skipped;  // set by the emit kernels when they refused to run (capacity / overflow)
 	uint32_t count_pending; // set by k_slow_plan when a record waits for k_slow_count
 	uint32_t live_cursor;   // slice slots with cut cells listed by k_slots for k_cells (k_scan_apply, the last kernel of a tail, clears it)
-	uint32_t slow_barrier;  // blocks of k_slow_all that have finished a phase (k_slots zeroes it)
+	uint32_t pad0_;         // (unused: keeps the offsets of the fields below)
 	uint64_t totV, totT;    // totals over all classified slices (ghost included)
 	uint64_t ghostV, ghostT;
 	uint32_t debug[8];      // (-DMC33_DEV: what a guarded kernel found wrong)
@@ -52,35 +52,15 @@ struct SweepTile { uint32_t seg, yt, z_lo, z_hi; };  // the piece of the volume 
 // slice record of (cell slice z, y tile, row segment): groups of 4 consecutive slices of one tile column are
 // adjacent (one k_cells block).  The order of the groups is the order the work records are stored in and the emit
 // passes walk them in - it has nothing to do with the numbering of vertices and triangles, which comes from the scan
-// over the row segments.  z group outermost (order 0).  Measured against y tile / z group / segment (1) and y tile /
-// segment / z group (2), which keep the groups of a tile column - three of a slice's four sample planes are the next
-// slice's too - close together in an XCD's share of the walk (round 3, profiles/r03_slot_order.txt): the vertex pass
-// fetches 5 % (float 1024^3) to 10 % (ushort 2048 x 2048 x 1024) less with (1) and is 2 - 6 us faster, k_cells is
-// 6 - 33 us slower (its row-segment counts and directory lines, stored [z][segment][y], are then written far apart by
-// blocks that run together); (2) loses everywhere.  The L2 fetches 128-byte lines: what the vertex pass moves is
-// within 1.5 x (float) / 2.2 x (ushort) of the distinct lines its stencils touch under ANY order.
-#ifndef MC33_SLOT_ORDER
-#define MC33_SLOT_ORDER 0
-#endif
+// over the row segments.  z group outermost (the two orders that keep a tile column's groups together, measured in round 3:
+// EXPERIMENTS.md).
 struct SlotDims { uint32_t nZG, nYT, nseg; };  // z groups (planes: one more than slices), y tiles, row segments
 __host__ __device__ inline uint64_t slice_slot(uint32_t dz, uint32_t yt, uint32_t seg, const SlotDims &d) {
-#if MC33_SLOT_ORDER == 0
 	return ((((uint64_t)(dz >> 2) * d.nYT + yt) * d.nseg + seg) << 2) | (dz & 3u);
-#elif MC33_SLOT_ORDER == 1
-	return ((((uint64_t)yt * d.nZG + (dz >> 2)) * d.nseg + seg) << 2) | (dz & 3u);
-#else
-	return ((((uint64_t)yt * d.nseg + seg) * d.nZG + (dz >> 2)) << 2) | (dz & 3u);
-#endif
 }
 // the inverse for a group of four slots (slot >> 2) -> (z group, y tile, row segment)
 __device__ inline void slot_group_coords(uint32_t b, const SlotDims &d, uint32_t &zq, uint32_t &yt, uint32_t &seg) {
-#if MC33_SLOT_ORDER == 0
 	seg = b % d.nseg; const uint32_t t = b / d.nseg; yt = t % d.nYT; zq = t / d.nYT;
-#elif MC33_SLOT_ORDER == 1
-	seg = b % d.nseg; const uint32_t t = b / d.nseg; zq = t % d.nZG; yt = t / d.nZG;
-#else
-	zq = b % d.nZG; const uint32_t t = b / d.nZG; seg = t % d.nseg; yt = t / d.nseg;
-#endif
 }
 
 // What one sweep leaves behind for ONE isovalue.  k_sweep can classify the samples it streams against several isovalues
@@ -418,18 +398,6 @@ struct SweepLog {  // per wave
 	uint64_t hdr_slot[LOG_SLICES];
 	uint32_t edge[64];               // the tile's first plane for k_boundary (compact)
 	uint32_t edge_hdr[8];
-};
-
-// The same for the passes over several isovalues (MC33_SWEEP_DEFER_N, round 5): one log per wave for all its isovalue lanes, so an
-// entry carries where it goes.  Small - 12 compact planes, 12 headers, 3.8 KB per wave - because the 4-isovalue forms keep the bit
-// rows of the plane below in LDS already (32 KB per block) and the log costs them the fourth block per CU.
-constexpr uint32_t LOGN_PLANES = 12, LOGN_SLICES = 12;
-struct SweepLogN {  // per wave
-	uint32_t plane[LOGN_PLANES][64];  // compact records: dword r = row r
-	uint64_t plane_dst[LOGN_PLANES];  // the record's place in its lane's slice_compact ...
-	uint64_t fmt_dst[LOGN_PLANES];    // ... and its byte in plane_fmt
-	uint32_t hdr[LOGN_SLICES][10];    // the ten words of a SliceHeader
-	uint64_t hdr_dst[LOGN_SLICES];
 };
 
 // (slot: of the slice; slot_up: of the slice above = the slot of the upper plane; write_prev / write_cur: the

@@ -21,34 +21,10 @@
 // below is put together by k_boundary from the bit rows both tiles leave behind (2 KiB each) - re-reading that
 // plane instead cost 1/depth of the traffic (6 % at depth 16).
 // ---------------------------------------------------------------------------------------------------
-// How a ballot (the sign bits of 64 samples of one row, an SGPR pair) is parked in the lane of its row: 0 = two v_writelane_b32
-// (rounds 1 - 3), 1 = ONE v_mov_b64 with EXEC narrowed to that lane (gfx940+ moves 64 bits in one instruction, and an SGPR
-// pair is a legal source): 4 instead of 8 vector instructions per row and isovalue - the passes over four isovalues of narrow
-// samples are bound by exactly these (round 4)
-#ifndef MC33_PARK
-#define MC33_PARK 2
-#endif
-#ifndef MC33_SWEEP_BUFS
-#define MC33_SWEEP_BUFS 2  // register buffers of loaded batches in k_sweep's single-isovalue forms (3: developer A/B, round 4)
-#endif
-#ifndef MC33_EDGE_UNIFORM
-#define MC33_EDGE_UNIFORM 1  // (0: developer A/B - an edge record for every plane, as until round 4)
-#endif
-#ifndef MC33_SWEEP_DEFER
-#define MC33_SWEEP_DEFER 1  // (0: developer A/B - every store of the sweep where its data is made, as until round 4)
-#endif
-#ifndef MC33_SWEEP_DEFER_N
-#define MC33_SWEEP_DEFER_N 0  // (1: the hand-over of the passes over several isovalues through a log in LDS too - SweepLogN; round 5, measured, off)
-#endif
-#ifndef MC33_EDGE_LAST_COMPACT
-#define MC33_EDGE_LAST_COMPACT 1
-#endif
-#ifndef MC33_LOG_EARLY_PLANES
-#define MC33_LOG_EARLY_PLANES 0u
-#endif
-#ifndef MC33_EDGE_COMPACT
-#define MC33_EDGE_COMPACT 0  // (developer A/B: the edge records of the single-isovalue pass in compact form too - leave_edge)
-#endif
+// How a ballot (the sign bits of 64 samples of one row, an SGPR pair) is parked in the lane of its row: ONE v_mov_b64 with EXEC
+// narrowed to that lane (gfx940+ moves 64 bits in one instruction, and an SGPR pair is a legal source), the passes over several
+// isovalues two isovalues per EXEC switch: 4 instead of 8 vector instructions per row and isovalue - the passes over four
+// isovalues of narrow samples are bound by exactly these (round 4; the v_writelane_b32 form of rounds 1 - 3: EXPERIMENTS.md)
 #if defined(MC33_GRD_U16)
 constexpr int SWEEP_PACK = 2;  // samples per dword
 #elif defined(MC33_GRD_U8)
@@ -85,11 +61,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 	// completed (one ballot) in an LDS mailbox, one block barrier per PLANE (the four waves run in step anyway: a plane is
 	// ~270 loads), and only the last segment of the group still loads its halo.  All four waves complete the same number
 	// of planes (same rows, same z range), so every wave reaches every barrier; blocks of unrelated tiles keep the load.
-#ifdef MC33_NO_MAILBOX  // (developer A/B: every wave loads its halo column itself)
-	bool grouped = false;
-#else
 	bool grouped = true;
-#endif
 	{
 		const uint32_t t0 = blockIdx.x * 4u;
 		if (t0 + 3u >= a.ntiles) grouped = false;
@@ -139,24 +111,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 	__shared__ uint64_t s_prev[PREV_LDS ? NI : 1][4][PREV_LDS ? 256 : 1];
 	__shared__ uint64_t s_prevz[PREV_LDS ? NI : 1][2][4];  // ... and its 'sample equals the isovalue' row / lane masks, per wave
 	__shared__ uint32_t s_prevh[PREV_LDS ? NI : 1][PREV_LDS ? 256 : 1];  // ... and its halo-column bits
-	constexpr bool DEFER = NI == 1 && MC33_SWEEP_DEFER;   // the hand-over goes through the wave's log in LDS (SweepLog)
+	constexpr bool DEFER = NI == 1;   // the hand-over goes through the wave's log in LDS (SweepLog)
 	__shared__ typename std::conditional<DEFER, SweepLog, uint32_t>::type s_log[DEFER ? 4 : 1];
 	uint32_t log_np = 0, log_ns = 0, log_edge = LOG_NONE;  // planes / slices in the log; the format of the pending first edge record (wave-uniform)
-	constexpr bool DEFER_N = NI >= 2 && MC33_SWEEP_DEFER_N;
-	__shared__ typename std::conditional<DEFER_N, SweepLogN, uint32_t>::type s_logn[DEFER_N ? 4 : 1];
-	uint32_t logn_np = 0, logn_ns = 0;
-#if defined(MC33_DEV) && defined(MC33_SWEEP_LDS_PAD)  // (developer A/B: the LDS of a log without the log - what the lost block per CU costs by itself)
-	__shared__ uint32_t s_pad[NI >= 4 ? MC33_SWEEP_LDS_PAD / 4 : 1];
-	if (a.ntiles == 0xFFFFFFFFu) s_pad[threadIdx.x & 0u] = 1u;
-#endif
 	uint32_t pend_chunk[NI];            // (NI >= 2) partial sums not yet added to memory: their chunk of slots ...
 	unsigned long long pend_sum[NI];    // ... batches << 32 | cells (wave-uniform)
 #pragma unroll
 	for (int q = 0; q < NI; q++) { pend_chunk[q] = 0u; pend_sum[q] = 0ull; }
 	const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	uint64_t cur[NI][4], prev[PREV_LDS ? 1 : NI][4];
-	uint32_t c_lo[MC33_PARK ? 1 : NI][4], c_hi[MC33_PARK ? 1 : NI][4];  // the rows being assembled: as halves (MC33_PARK 0) ...
-	uint64_t c64[MC33_PARK ? NI : 1][4];                                 // ... or as words (MC33_PARK 1)
+	uint64_t c64[NI][4];  // the rows being assembled
 	uint32_t cur_h[NI], prev_h[PREV_LDS ? 1 : NI];
 	uint64_t cur_zc[NI], prev_zc[PREV_LDS ? 1 : NI], zcacc[NI];  // ... and the lanes that loaded one
 	uint64_t cur_z[NI], prev_z[PREV_LDS ? 1 : NI], zacc[NI];  // sample rows of the plane that hold a sample equal to the isovalue (wave-uniform),
@@ -171,7 +135,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 #pragma unroll
 		for (int k = 0; k < 4; k++) {
 			if constexpr (PREV_LDS) s_prev[q][k][threadIdx.x] = 0; else prev[q][k] = 0;
-			if constexpr (MC33_PARK) c64[q][k] = 0; else c_lo[q][k] = c_hi[q][k] = 0;
+			c64[q][k] = 0;
 		}
 		cur_h[q] = 0; cur_z[q] = zacc[q] = 0; cur_zc[q] = zcacc[q] = 0;
 		if constexpr (PREV_LDS) { s_prevz[q][0][wv] = 0; s_prevz[q][1][wv] = 0; s_prevh[q][threadIdx.x] = 0; } else { prev_z[q] = 0; prev_zc[q] = 0; prev_h[q] = 0; }
@@ -244,10 +208,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 	};
 	// ---- the wave's log of what it hands on (DEFER; see SweepLog) ----
 	auto log_flush = [&]() __attribute__((always_inline)) {
-#ifdef MC33_LOG_NO_FLUSH  // (developer timing experiment: the log is kept and dropped - results wrong)
-		log_np = 0; log_ns = 0; log_edge = LOG_NONE;
-		return;
-#endif
 		if constexpr (DEFER) {
 			SweepLog &G = s_log[wv];
 			const SweepLane &L0 = a.lane[0];
@@ -329,80 +289,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 			log_ns++;
 		}
 	};
-	// ---- the same for the passes over several isovalues (DEFER_N; see SweepLogN) ----
-	auto logn_flush = [&](bool at_end = false) __attribute__((always_inline)) {
-		if constexpr (DEFER_N) {
-#if defined(MC33_DEV) && defined(MC33_LOGN_DROP)  // (developer timing experiment: a log that is full is dropped, only the tile's end writes - results wrong)
-			if (!at_end) { logn_np = 0; logn_ns = 0; return; }
-#endif
-			SweepLogN &G = s_logn[wv];
-			const uint32_t ln = fresh_lane();
-			__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-			for (uint32_t k = 0; k < logn_np; k++) {  // wave-uniform
-				const uint64_t dst = readlane64(G.plane_dst[k], 0), fdst = readlane64(G.fmt_dst[k], 0);
-				__builtin_amdgcn_raw_buffer_store_b32(G.plane[k][ln], record_rsrc((const void *)dst, 256u), ln * 4u, 0u, 0);
-				if (ln == 0) *(uint8_t *)fdst = (uint8_t)PLANE_COMPACT;
-			}
-			if (ln < logn_ns) {
-				const uint32_t *w = G.hdr[ln];
-				uint32_t *h = (uint32_t *)G.hdr_dst[ln];
-				*(uint4 *)h = uint4{w[0], w[1], w[2], w[3]};
-				*(uint4 *)(h + 4) = uint4{w[4], w[5], w[6], w[7]};
-				*(uint2 *)(h + 8) = uint2{w[8], w[9]};
-			}
-			__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the log is written again)
-			logn_np = 0; logn_ns = 0;
-		}
-	};
-	auto logn_plane = [&](const SweepLane &L, uint64_t slot, const uint64_t (&w)[4], uint32_t ln) __attribute__((always_inline)) {
-		if constexpr (DEFER_N) {
-			uint32_t desc;
-			if (encode_plane<S>(w, desc)) {  // (wave-uniform)
-				if (logn_np == LOGN_PLANES) logn_flush();
-				SweepLogN &G = s_logn[wv];
-				G.plane[logn_np][ln] = desc;
-				if (ln == 0) { G.plane_dst[logn_np] = (uint64_t)(L.slice_compact + slot * 64u); G.fmt_dst[logn_np] = (uint64_t)(L.plane_fmt + slot); }
-				logn_np++;
-			} else {
-				store_plane_raw<S>(L.slice_bits + slot * 128u, w, ln);
-				if (ln == 0) L.plane_fmt[slot] = (uint8_t)PLANE_RAW;
-			}
-		}
-	};
-	// (the partial sums per chunk of slots as in hand_over_slice: one atomic when the wave's slices leave a chunk)
-	auto logn_header = [&](const SweepLane &L, uint64_t slot, uint64_t bp, uint64_t bc, uint64_t zrows, uint64_t zcols, const uint64_t (&act)[4], uint32_t ln,
-	                       uint32_t &pchunk, unsigned long long &psum) __attribute__((always_inline)) {
-		if constexpr (DEFER_N) {
-			uint32_t ncell = __popcll(act[0]) + __popcll(act[1]) + __popcll(act[2]) + __popcll(act[3]);
-#pragma unroll
-			for (int dlt = 32; dlt; dlt >>= 1) ncell += __shfl_xor(ncell, dlt);
-			if (logn_ns == LOGN_SLICES) logn_flush();
-			if (ln == 0) {
-				SweepLogN &G = s_logn[wv];
-				uint32_t *w = G.hdr[logn_ns];
-				w[0] = L.epoch << 2 | SLICE_VALID | (zrows ? SLICE_HAS_ISO : 0u);
-				w[1] = (uint32_t)bp; w[2] = (uint32_t)(bp >> 32); w[3] = (uint32_t)bc; w[4] = (uint32_t)(bc >> 32); w[5] = ncell;
-				w[6] = (uint32_t)zrows; w[7] = (uint32_t)(zrows >> 32); w[8] = (uint32_t)zcols; w[9] = (uint32_t)(zcols >> 32);
-				G.hdr_dst[logn_ns] = (uint64_t)(L.slice_hdr + slot);
-			}
-			logn_ns++;
-			const uint32_t chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(slot / SLOT_CHUNK));
-			const uint32_t nc = (uint32_t)__builtin_amdgcn_readfirstlane((int)ncell);
-			if (pchunk != chunk) {
-				if (psum && ln == 0) atomicAdd(L.slot_part + pchunk, psum);
-				pchunk = chunk; psum = 0ull;
-			}
-			psum += (unsigned long long)((nc + 63u) >> 6) << 32 | nc;
-		}
-	};
 	real_t halo = 0;  // lane r: halo sample of row r of the plane being assembled
 	// (always_inline: the body is called twice, and in the largest forms - packed uchar samples, four isovalues, equality tests - the
 	// compiler made a real FUNCTION of it, every captured array behind a pointer into 1.5 KiB of scratch memory per lane)
 	auto process = [&](const raw_t (&dd)[16], const real_t &hv, uint32_t p, uint32_t bi) __attribute__((always_inline)) {
-		// (developer A/B, MC33_LOG_EARLY_PLANES = n: the log goes out n planes before the tile's end instead of behind it.  Every wave of
-		// the launch ends at the same moment, and what they all store then is the kernel's tail - 0.03 of 0.68 ms at 1024^3 - but
-		// stores beside even the last planes' loads cost more: 0.691 / 0.703 / 0.694 -> 0.711 / 0.708 / 0.704 (n = 1) -> 0.716 / 0.724 / 0.725 (2))
-		if (DEFER && MC33_LOG_EARLY_PLANES && bi == 0u && p + MC33_LOG_EARLY_PLANES == z_hi + 1u && z_hi - pl0 >= 2u * MC33_LOG_EARLY_PLANES) log_flush();
 		const uint32_t r = bi * (uint32_t)RB;
 		halo = (lane / (uint32_t)RB) == bi ? hv : halo;
 		unrolled_for<RB, (S >= 4)>([&](auto rc) __attribute__((always_inline)) {
@@ -410,7 +300,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 			real_t f[4];
 #pragma unroll
 			for (int k = 0; k < 4; k++) f[k] = sample(dd, rr, k);
-			uint64_t bwq[NI][4];  // (MC33_PARK 2: the ballots of the row for all isovalues, parked two isovalues per EXEC switch)
+			uint64_t bwq[NI][4];  // (NI >= 2: the ballots of the row for all isovalues, parked two isovalues per EXEC switch)
 			static_for<NI>([&](auto qc) __attribute__((always_inline)) {
 				constexpr int q = decltype(qc)::value;
 				uint64_t bw[4];
@@ -443,10 +333,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 				// the row number through readfirstlane - uniform anyway, but short of SGPRs the compiler moved the batch counter into
 				// a vector register and handed THAT to the "s" operand)
 				const uint32_t rowsel = (uint32_t)__builtin_amdgcn_readfirstlane((int)(r + (uint32_t)rr));
-				if constexpr (MC33_PARK == 2 && NI >= 2) {
+				if constexpr (NI >= 2) {
 #pragma unroll
 					for (int k = 0; k < 4; k++) bwq[q][k] = bw[k];
-				} else if constexpr (MC33_PARK) {
+				} else {
 					// EXEC = that one lane, four 64-bit moves from the SGPR pairs, EXEC back (it is all ones here: the wave's control flow is
 					// uniform; saved and restored all the same).  SALU writes of EXEC need no wait states before a VALU instruction.
 					uint64_t &w0 = c64[q][0], &w1 = c64[q][1], &w2 = c64[q][2], &w3 = c64[q][3];
@@ -459,23 +349,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 					    : "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3), "=&s"(saved)
 					    : "s"(bw[0]), "s"(bw[1]), "s"(bw[2]), "s"(bw[3]), "s"(rowsel)
 					    : "scc");  // (s_lshl_b64 sets SCC: without the clobber the compiler carried a loop condition across the statement in it)
-				} else {
-					// v_writelane takes its lane select from M0 when the data operand is an SGPR too (one SGPR per VOP3 on gfx9-class encodings)
-					uint32_t &l0 = c_lo[q][0], &h0 = c_hi[q][0], &l1 = c_lo[q][1], &h1 = c_hi[q][1], &l2 = c_lo[q][2], &h2 = c_hi[q][2], &l3 = c_lo[q][3], &h3 = c_hi[q][3];
-					const uint32_t m0 = (uint32_t)bw[0], m1 = (uint32_t)(bw[0] >> 32), m2 = (uint32_t)bw[1], m3 = (uint32_t)(bw[1] >> 32);
-					const uint32_t m4 = (uint32_t)bw[2], m5 = (uint32_t)(bw[2] >> 32), m6 = (uint32_t)bw[3], m7 = (uint32_t)(bw[3] >> 32);
-					asm volatile(
-					    "s_mov_b32 m0, %16\n\t"
-					    "v_writelane_b32 %0, %8, m0\n\tv_writelane_b32 %1, %9, m0\n\t"
-					    "v_writelane_b32 %2, %10, m0\n\tv_writelane_b32 %3, %11, m0\n\t"
-					    "v_writelane_b32 %4, %12, m0\n\tv_writelane_b32 %5, %13, m0\n\t"
-					    "v_writelane_b32 %6, %14, m0\n\tv_writelane_b32 %7, %15, m0"
-					    : "+v"(l0), "+v"(h0), "+v"(l1), "+v"(h1), "+v"(l2), "+v"(h2), "+v"(l3), "+v"(h3)
-					    : "s"(m0), "s"(m1), "s"(m2), "s"(m3), "s"(m4), "s"(m5), "s"(m6), "s"(m7), "s"(rowsel)
-					    : "m0");
 				}
 			});
-			if constexpr (MC33_PARK == 2 && NI >= 2) {
+			if constexpr (NI >= 2) {
 				static_for<NI / 2>([&](auto hc) __attribute__((always_inline)) {
 					constexpr int q0 = 2 * decltype(hc)::value;
 					const uint32_t rowsel = (uint32_t)__builtin_amdgcn_readfirstlane((int)(r + (uint32_t)rr));
@@ -512,7 +388,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 		if (grouped) {  // (block-uniform) column 0 of this plane for the wave to the left; the right neighbour's for this wave
 			static_for<NI>([&](auto qc) __attribute__((always_inline)) {
 				constexpr int q = decltype(qc)::value;
-				const uint64_t hb = __ballot(((MC33_PARK ? (uint32_t)c64[MC33_PARK ? q : 0][0] : c_lo[MC33_PARK ? 0 : q][0]) & 1u) != 0u);  // (word 0 bit 0 is the segment's first sample in every layout S)
+				const uint64_t hb = __ballot(((uint32_t)c64[q][0] & 1u) != 0u);  // (word 0 bit 0 is the segment's first sample in every layout S)
 				if (lp == 0) {
 					s_mail[par][wv][q][0] = hb;
 					s_mail[par][wv][q][1] = (ZM != 2 && (zcacc[q] & 1ull)) ? zacc[q] : 0ull;  // (lane 0 loaded column 0; rows to the batch: a superset is fine)
@@ -525,10 +401,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 			constexpr int q = decltype(qc)::value;
 			const SweepLane &L = a.lane[q];
 #pragma unroll
-			for (int k = 0; k < 4; k++) {
-				if constexpr (MC33_PARK) { cur[q][k] = c64[q][k]; c64[q][k] = 0; }
-				else { cur[q][k] = u64(c_lo[q][k], c_hi[q][k]); c_lo[q][k] = c_hi[q][k] = 0; }
-			}
+			for (int k = 0; k < 4; k++) { cur[q][k] = c64[q][k]; c64[q][k] = 0; }
 			if (from_right) {  // (wave-uniform; the mailbox word is read here, per isovalue: held over the loop it cost the 4-isovalue form registers it does not have)
 				const uint64_t nb_bits = s_mail[par][wv + 1u][q][0], nb_zero = ZM != 2 ? s_mail[par][wv + 1u][q][1] : 0ull;
 				cur_h[q] = (uint32_t)((nb_bits >> lp) & 1ull);
@@ -548,20 +421,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 				zacc[q] = zcacc[q] = 0;
 			}
 			auto leave_edge = [&](uint32_t which) __attribute__((always_inline)) {  // bit rows of this plane for k_boundary (a plane record like those of slice_bits)
-				// (in compact form where it fits only in the passes over several isovalues, which are bound by what they write:
-				// 2.26 -> 2.19 ms per 4-isovalue pass at C5; the single-isovalue pass lost with it - 0.789 -> 0.818 ms at C3,
-				// eight processes each way, and again in round 3: 0.73 -> 0.77 - 0.81 - and keeps the raw form.  These 17 MB (1024^3, two records per tile) cost the float
-				// sweep 0.065 of its 0.73 ms - the first plane's 0.045, the last one's 0.02 - and three times what the 25 MB of the
-				// slices handed on cost; it is the two 1 KiB stores, not the header; holding the first plane's record back in registers
-				// for 1 - 8 planes by tile number, or to the tile's end, or storing it nontemporal, changes nothing - and with the
-				// slices handed on, as in every real extraction, the sweep WITHOUT edge records is no faster at all: 0.72 - 0.75 ->
-				// 0.75 - 0.78 ms; the costs of the sweep's stores do not add (round 3, profiles/r03_sweep_parts.txt))
+				// (in compact form where it fits.  The tile's first plane of a single-isovalue pass waits in the log; its last plane comes at
+				// the tile's end anyway and is stored at once.  As raw records these cost the round-3 float sweep 0.065 of its 0.73 ms - the
+				// two 1 KiB stores, not the header: profiles/r03_sweep_parts.txt; the other forms measured: EXPERIMENTS.md)
 				uint32_t fmt = PLANE_RAW;
 				uint4 *rec = L.edge_bits + ((uint64_t)wtile * 2u + which) * 128u;
 				// A plane of the tile that lies wholly on one side of the surface - two thirds of them on a smooth field - leaves no
 				// record, only the header with its side (round 4: the records are two thirds of what the single-isovalue sweep writes)
 				const uint64_t w_or = cur[q][0] | cur[q][1] | cur[q][2] | cur[q][3], w_and = cur[q][0] & cur[q][1] & cur[q][2] & cur[q][3];
-				const bool all0 = MC33_EDGE_UNIFORM && __ballot(w_or != 0ull) == 0ull, all1 = MC33_EDGE_UNIFORM && __ballot(w_and != ~0ull) == 0ull;
+				const bool all0 = __ballot(w_or != 0ull) == 0ull, all1 = __ballot(w_and != ~0ull) == 0ull;
 				bool deferred = false;  // (the tile's FIRST plane: its record, when it is small, waits in the log with everything else)
 				if (all0 || all1) { fmt = all0 ? PLANE_UNIFORM0 : PLANE_UNIFORM1; deferred = DEFER && which == 0u && !MC33_DEBUG_BITS(a); }
 				else if (DEFER && which == 0u && !MC33_DEBUG_BITS(a)) {
@@ -571,14 +439,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 						fmt = PLANE_COMPACT; deferred = true;
 					} else store_plane_raw<S>(rec, cur[q], lp);
 				}
-				else if constexpr (NI >= 2 || MC33_EDGE_COMPACT || (DEFER && MC33_EDGE_LAST_COMPACT)) fmt = store_plane_record<S>(rec, (uint32_t *)rec, cur[q], lp);  // (DEFER: the last plane's record, stored at the tile's end with the rest: the compact form where it fits)
-				else if (!(MC33_DEBUG_BITS(a) & 8192u)) {  // (developer builds: 8192 no record, 4096 no header)
-					uint64_t o[4];
-					to_standard<S>(cur[q], o);
-					const __amdgpu_buffer_rsrc_t rs = record_rsrc(rec, 2048u);
-					__builtin_amdgcn_raw_buffer_store_b128(u32x4_t{(uint32_t)o[0], (uint32_t)(o[0] >> 32), (uint32_t)o[1], (uint32_t)(o[1] >> 32)}, rs, lp * 16u, 0u, 0);
-					__builtin_amdgcn_raw_buffer_store_b128(u32x4_t{(uint32_t)o[2], (uint32_t)(o[2] >> 32), (uint32_t)o[3], (uint32_t)(o[3] >> 32)}, rs, lp * 16u, 1024u, 0);
-				}
+				else fmt = store_plane_record<S>(rec, (uint32_t *)rec, cur[q], lp);
 				const uint64_t bh = __ballot(cur_h[q] != 0);
 				if (deferred) {
 					if constexpr (DEFER) {
@@ -590,7 +451,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 						log_edge = fmt;
 					}
 				} else
-				if (lp == 0 && !(MC33_DEBUG_BITS(a) & 4096u)) {
+				if (lp == 0 && !(MC33_DEBUG_BITS(a) & 4096u)) {  // (developer builds: 4096 no header)
 					L.edge_hdr[((uint64_t)wtile * 2u + which) * 2u] = uint4{(uint32_t)bh, (uint32_t)(bh >> 32), (uint32_t)cur_z[q], (uint32_t)(cur_z[q] >> 32)};
 					L.edge_hdr[((uint64_t)wtile * 2u + which) * 2u + 1u] = uint4{(uint32_t)cur_zc[q], (uint32_t)(cur_zc[q] >> 32), fmt, 0u};
 				}
@@ -617,11 +478,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 							if (!prev_written[q]) log_plane(slot, pq, lp);
 							log_plane(slot_up, cur[q], lp);
 							log_header(slot, __ballot(ph != 0), __ballot(cur_h[q] != 0), pz | cur_z[q], pzc | cur_zc[q], act, lp);
-						} else if (DEFER_N && !MC33_DEBUG_BITS(a)) {
-							const uint64_t slot = slice_slot(p - 1 - P.zs, yt, seg, a.sd), slot_up = slice_slot(p - P.zs, yt, seg, a.sd);
-							if (!prev_written[q]) logn_plane(L, slot, pq, lp);
-							logn_plane(L, slot_up, cur[q], lp);
-							logn_header(L, slot, __ballot(ph != 0), __ballot(cur_h[q] != 0), pz | cur_z[q], pzc | cur_zc[q], act, lp, pend_chunk[q], pend_sum[q]);
 						} else
 						hand_over_slice<S>(L, slice_slot(p - 1 - P.zs, yt, seg, a.sd), slice_slot(p - P.zs, yt, seg, a.sd), pq, cur[q],
 						                   !prev_written[q], true, __ballot(ph != 0), __ballot(cur_h[q] != 0), pz | cur_z[q], pzc | cur_zc[q], act, lp,
@@ -673,21 +529,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 		return;
 	}
 #endif
-	if constexpr (MC33_SWEEP_BUFS == 3 && NI == 1) {
-		// Three buffers (round 4, single-isovalue passes): TWO batches stay in flight while one is turned into bit rows - also across
-		// the work on a complete plane (cut-cell test, hand-over stores), which with two buffers ran with one batch in flight.
-		raw_t dC[16];
-		real_t hC = 0;
-		issue(dB, hB, ip, ib); MC33_ADV_ISSUE();
-		for (uint32_t t = 0; t < T; t += 3) {
-			issue(dC, hC, ip, ib); MC33_ADV_ISSUE();
-			process(dA, hA, pp, pb); MC33_ADV(pp, pb);
-			issue(dA, hA, ip, ib); MC33_ADV_ISSUE();
-			if (t + 1 < T) { process(dB, hB, pp, pb); MC33_ADV(pp, pb); }
-			issue(dB, hB, ip, ib); MC33_ADV_ISSUE();
-			if (t + 2 < T) { process(dC, hC, pp, pb); MC33_ADV(pp, pb); }
-		}
-	} else
 	for (uint32_t t = 0; t < T; t += 2) {
 		issue(dB, hB, ip, ib); MC33_ADV_ISSUE();
 		process(dA, hA, pp, pb); MC33_ADV(pp, pb);
@@ -695,7 +536,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 		if (t + 1 < T) { process(dB, hB, pp, pb); MC33_ADV(pp, pb); }
 	}
 	log_flush();  // (DEFER: everything the tile hands on, behind its last load)
-	logn_flush(true);
 	if constexpr (NI >= 2) {
 #pragma unroll
 		for (int q = 0; q < NI; q++)

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void k_slots(const PerLane<SlotsArgs> A, uint6
 	if (c == 0) for (uint32_t q = gridDim.x + t; q < part_cap; q += 256u) part_next[q] = 0;  // (a later range may be longer)
 	if (c == 0) for (uint32_t q = t; q < LIST_CHUNKS; q += 256u) { lc.slow_cnt[q] = 0; lc.dirty_cnt[q] = 0; }  // the list cursors of this extraction
 	if (c == 0 && t == 0) {        // ... and so are the counters the later passes of this one add to
-		ctr->slow_cursor = 0; ctr->dirty_cursor = 0; ctr->emit_skipped = 0; ctr->count_pending = 0; ctr->slow_barrier = 0;
+		ctr->slow_cursor = 0; ctr->dirty_cursor = 0; ctr->emit_skipped = 0; ctr->count_pending = 0;
 		ctr->totV = ctr->totT = ctr->ghostV = ctr->ghostT = 0;
 		for (int q = 0; q < 8; q++) ctr->debug[q] = 0;
 	}
@@ -535,7 +535,8 @@ struct SlowArgs {
 	Counters *ctr;
 };
 
-// (the bodies of the three kernels as functions: each is a kernel of its own, and all three are the phases of k_slow_all)
+// (the bodies of the three kernels as functions, each a kernel of its own.  The three as one launch with grid barriers between
+// them was measured slower: EXPERIMENTS.md, "Removed experiment code")
 __device__ __forceinline__ void slow_plan_body(const SlowArgs &a, real_t (*s_v)[256], uint32_t *s_pre, uint32_t *s_red, uint32_t *s_dirty) {
 	ChunkMap cm;
 	cm.build(s_pre, s_red, a.lc.slow_cnt, a.lc.n);  // (first: its loads and the one of the cursor below go out together)
@@ -668,42 +669,6 @@ __global__ __launch_bounds__(256) void k_seg_fix(const PerLane<SlowArgs> A) {
 	__shared__ real_t s_w[8][256];
 	__shared__ uint64_t s_key[12][256];
 	seg_fix_body(A.a[blockIdx.y], s_w, s_key, s_pre, s_red);
-}
-
-// The three as ONE launch (round 5; built, bit-identical, SLOWER - MC33_HIP_SLOW_MERGED=1 runs it, the library does not): for the
-// usual case of FEW slow records - cells on the grid's faces, a corner equal to the isovalue here and there: 8 800 at 1024^3 are 35
-// blocks' worth of work behind three launches, each a grid-wide dependency (plans must all be stored before identities are
-// counted, counts before the offsets of a row segment are rebuilt).  The blocks of this kernel - as few as the last extraction's
-// slow records need, 64 at most, all resident at once - pass two barriers instead: every block adds one to a counter in the
-// isovalue's Counters (k_slots has zeroed it) when its share of a phase is stored, and waits until all have.  Measured at 1024^3
-// (profiles/r05_tail_merge.txt): 39 us against 13 + 10 for k_slow_plan + k_seg_fix as launches of their own, the tail 0.141
-// against 0.126 ms.  The blocks sit on eight XCDs, each behind an L2 of its own: a barrier between them is a write-back of that
-// L2 (buffer_wbl2 sc1), a device-scope atomic, a polling loop on a line that comes from memory every time, and an invalidate
-// (buffer_inv sc1) - ~8 us each, where the end of a kernel does the same for every XCD at once in ~1 us (the sum of the tail's
-// kernel durations IS its event time: there is no gap between launches to win back).  The same holds for anything else that
-// would fold a grid-wide dependency of the tail into a kernel - the slice between two sweep tiles done by whichever wave ends
-// second, k_slots at the head of k_cells: each needs this release / acquire pair per wave or block.  Not pursued.
-constexpr uint32_t SLOW_ALL_MAX_BLOCKS = 64;
-__device__ __forceinline__ void slow_barrier(uint32_t *counter, uint32_t target) {
-	__threadfence();   // (every thread: its stores of the phase, released to the device - the blocks run on different XCDs, each behind an L2 of its own)
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-		while (__hip_atomic_load(counter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) __builtin_amdgcn_s_sleep(2);
-	}
-	__syncthreads();
-	__threadfence();   // (acquire: nothing read below may come from a line cached before the others' stores)
-}
-__global__ __launch_bounds__(256) void k_slow_all(const PerLane<SlowArgs> A) {
-	const SlowArgs &a = A.a[blockIdx.y];
-	__shared__ real_t s_w[8][256];
-	__shared__ uint64_t s_key[12][256];
-	__shared__ uint32_t s_pre[LIST_CHUNKS + 1], s_red[256], s_dirty[4];
-	slow_plan_body(a, s_w, s_pre, s_red, s_dirty);
-	slow_barrier(&a.ctr->slow_barrier, gridDim.x);
-	slow_count_body(a, s_w, s_key, s_pre, s_red);
-	slow_barrier(&a.ctr->slow_barrier, 2u * gridDim.x);
-	seg_fix_body(a, s_w, s_key, s_pre, s_red);
 }
 
 // ---------------------------------------------------------------------------------------------------

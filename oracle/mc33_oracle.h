@@ -4,7 +4,7 @@
  * (reference source/marching_cubes_33.c:1816-1889 sweep, :673-1253 MC33_findCase, :347-462
  * ambiguity tests, :485-585 vertex stores, :628-649 MC33_surfint).  It exists to CHECK the HIP
  * path; nothing in the product library may include, link or call it.  Pinned against the real
- * reference built by oracle/Makefile (oracle/_ref) in tests/test_oracle_vs_reference.py and
+ * reference built by oracle/Makefile (oracle/_ref) in tests/test_oracle.py and
  * against the committed fixtures under tests/golden/.
  */
 #ifndef MC33_ORACLE_H
