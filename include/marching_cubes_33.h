@@ -152,6 +152,18 @@ unsigned calculate_isosurfaces(MC33 *extractor, const MC33_real *isovalues, unsi
  * that before EVERY extraction, for callers that cannot be changed.) */
 void MC33_grid_changed(MC33 *extractor);
 
+/* extension (not in the reference, which gives every vertex DefaultColorMC, source/marching_cubes_33.c:1875-1877): colours from
+ * a second grid - a density to cut the surface from, a potential to paint on it.
+ * MC33_set_property_grid uploads `property` (same N as the extractor's grid, same GRD_data_type; orthogonal grids only) beside
+ * the grid in HBM; NULL detaches it; calling it again uploads again (that is also how a caller says "I rewrote the samples").
+ * MC33_set_color_map keeps a copy of `count` palette words (0xAABBGGRR, 2 <= count <= 256) and the value range lo < hi they
+ * span; NULL removes it.  Both return 0, or -1 when refused (nothing changes then).
+ * While both are set, calculate_isosurface(s) samples the property grid at every vertex on the GPU - trilinear, in double, at
+ * (v - r0) / d - and writes palette[round((p - lo) / (hi - lo) * (count - 1))] into surface.color, the ends of the palette
+ * beyond the range, DefaultColorMC where the value is NaN.  With either missing the colours are DefaultColorMC as before. */
+int MC33_set_property_grid(MC33 *extractor, _GRD *property);
+int MC33_set_color_map(MC33 *extractor, const int *palette, unsigned count, double lo, double hi);
+
 /* ---- inclined grids (reference header :186-191) ---------------------------------------------------------
  * c = A b (transposed == 0) or A^T b for a 3x3 matrix; _multTSA_bf assumes an upper triangular A.  A caller may
  * point mult_Abf at either; calculate_isosurface looks at the pointer when it is called and runs the matching

@@ -191,6 +191,39 @@ int mc33hip_download_concurrent(mc33hip_ctx *c, void *host_dst, const void *devi
  * stream like mc33hip_download, != 0 uses the side stream like mc33hip_download_concurrent. */
 int mc33hip_download_many(mc33hip_ctx *c, int n, void *const *host_dst, const void *const *device_src, const size_t *bytes,
                           int concurrent);
+/* --- property grid: a second scalar field sampled at the vertices (no counterpart in the reference, which fills surface.color
+ * with DefaultColorMC, MC:1875-1877) ----------------------------------------------------------------------------------------
+ * The property grid has the extractor grid's points per axis and sample type; it is resident as a window of whole planes of its
+ * own: global planes [plane0, plane0 + nplanes), independent of desc.plane0 / npz_resident.  Orthogonal grids only.
+ *   upload_rows       : F[k][j] row pointers, k counts the window's planes (F = _GRD.F + plane0); staged like mc33hip_upload_rows
+ *   upload_contiguous : the window's planes back to back in host memory
+ *   adopt_device      : a caller-owned device buffer used in place, pitch / slice in samples
+ *   drop              : detaches (and frees the library's copy)
+ * Attaching again replaces the window.  All four wait for the context's stream first. */
+int mc33hip_property_upload_rows(mc33hip_ctx *c, const void *const *const *F, unsigned int plane0, unsigned int nplanes);
+int mc33hip_property_upload_contiguous(mc33hip_ctx *c, const void *host_samples, unsigned int plane0, unsigned int nplanes);
+int mc33hip_property_adopt_device(mc33hip_ctx *c, const void *device_samples, size_t pitch, size_t slice, unsigned int plane0,
+                                  unsigned int nplanes);
+int mc33hip_property_drop(mc33hip_ctx *c);
+
+/* The property at nV vertices, dV: nV x 3 MC33_real in device memory (what mc33hip_emit wrote).  For a vertex v, in IEEE double
+ * throughout: g = (v - r0) / d per axis; i = floor(g) clamped to [0, N]; f = g - i clamped to [0, 1], 0 where i == N;
+ * lerp(p, q, f) = f == 0 ? p : p * (1 - f) + q * f (q is not read when f == 0) along x, then y, then z; the result rounded to
+ * float.  mc33hip_sample_property leaves that float per vertex in dP; mc33hip_color_vertices maps it through n palette words
+ * (0xAABBGGRR, 2 <= n <= 256, a HOST array, copied on the context's stream): s = (value - lo) / (hi - lo) clamped to [0, 1],
+ * dC[v] = palette[(int)floor(s * (n - 1) + 0.5)], nan_color where the value is NaN.
+ * Both only enqueue on the context's stream: behind an mc33hip_emit on it they see its vertices.  A vertex that needs a plane
+ * outside the attached window is counted on the device (its result is NaN / nan_color): the next mc33hip_synchronize,
+ * mc33hip_download, mc33hip_download_many (not concurrent) or mc33hip_download_wait returns MC33HIP_ERUNTIME and
+ * mc33hip_last_error names the count.  MC33HIP_EINVAL: nothing attached, an inclined context (mc33hip_set_inclined with
+ * matrices), n outside 2..256, lo >= hi or a NaN bound. */
+int mc33hip_sample_property(mc33hip_ctx *c, const void *dV, unsigned long long nV, float *dP);
+int mc33hip_color_vertices(mc33hip_ctx *c, const void *dV, unsigned long long nV, const int *palette, unsigned int n, double lo,
+                           double hi, int nan_color, int *dC);
+/* One more array for the pipelined download of mc33hip_emit_download: copied to the host on the context's copy stream as soon as
+ * everything enqueued on the context's stream so far is through.  Only enqueues; mc33hip_download_wait waits for it too. */
+int mc33hip_download_enqueue(mc33hip_ctx *c, void *host_dst, const void *device_src, size_t bytes);
+
 /* Plain device allocations on the context's device (for language bindings). */
 int mc33hip_device_alloc(mc33hip_ctx *c, void **dptr, size_t bytes);
 int mc33hip_device_free(mc33hip_ctx *c, void *dptr);

@@ -37,12 +37,15 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_emit", "mc33hip_extract", "mc33hip_last_timing", "mc33hip_download",
            "mc33hip_device_alloc", "mc33hip_device_free", "mc33hip_set_inclined", "mc33hip_download_concurrent", "mc33hip_synchronize", "mc33hip_download_many", "mc33hip_set_normal_neg", "mc33hip_sweep_many", "mc33hip_set_timing", "mc33hip_probe_read", "mc33hip_prepare_many",
            "mc33hip_emit_download", "mc33hip_download_wait", "mc33hip_own_stream", "mc33hip_device_count", "mc33hip_count_async",
-           "mc33hip_counts_to_device", "mc33hip_bases_from_table", "mc33hip_emit_at_device_bases", "mc33hip_count_finish"]
+           "mc33hip_counts_to_device", "mc33hip_bases_from_table", "mc33hip_emit_at_device_bases", "mc33hip_count_finish",
+           "mc33hip_property_upload_rows", "mc33hip_property_upload_contiguous", "mc33hip_property_adopt_device", "mc33hip_property_drop",
+           "mc33hip_sample_property", "mc33hip_color_vertices", "mc33hip_download_enqueue"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
                  "write_bin_s", "read_bin_s", "write_txt_s", "write_obj_s", "write_ply_s",
-                 "read_grd", "read_grd_binary", "read_scanfiles", "read_raw_file", "read_dat_file", "calculate_isosurfaces", "MC33_grid_changed"]
+                 "read_grd", "read_grd_binary", "read_scanfiles", "read_raw_file", "read_dat_file", "calculate_isosurfaces", "MC33_grid_changed",
+                 "MC33_set_property_grid", "MC33_set_color_map"]
 
 
 class MC33Error(RuntimeError):
@@ -100,6 +103,14 @@ def load_library(dtype="f32"):
     lib.mc33hip_bases_from_table.argtypes = [V, V, C.c_int, C.c_int, C.c_int]
     lib.mc33hip_emit_at_device_bases.argtypes = [V, V, V, V, C.c_ulonglong, C.c_ulonglong]
     lib.mc33hip_count_finish.argtypes = [V, P(Counts)]
+    lib.mc33hip_synchronize.argtypes = [V]
+    lib.mc33hip_property_upload_rows.argtypes = [V, V, C.c_uint, C.c_uint]
+    lib.mc33hip_property_upload_contiguous.argtypes = [V, V, C.c_uint, C.c_uint]
+    lib.mc33hip_property_adopt_device.argtypes = [V, V, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint]
+    lib.mc33hip_property_drop.argtypes = [V]
+    lib.mc33hip_sample_property.argtypes = [V, V, C.c_ulonglong, V]
+    lib.mc33hip_color_vertices.argtypes = [V, V, C.c_ulonglong, P(C.c_int), C.c_uint, C.c_double, C.c_double, C.c_int, V]
+    lib.mc33hip_download_enqueue.argtypes = [V, V, V, C.c_size_t]
     _libs[dtype] = lib
     return lib
 
@@ -240,8 +251,51 @@ class DeviceGrid:
         _check(self.lib, rc, allow=(ECAPACITY,))
         return cnt, rc == OK
 
-    def extract(self, iso, rng=None):
-        """Count, allocate exact-size outputs with torch, emit.  Returns (V, N, T, Counts)."""
+    # -- a second scalar grid sampled at the vertices (mc33_hip.h: property grid) ------------------------------------------------
+    def attach_property(self, tensor, plane0=None):
+        """A device tensor [z, y, x] of the grid's dtype, adopted in place: the property grid, as many points per row and rows
+        per plane as the grid; its planes are global planes [plane0, plane0 + z) (default: the grid's own plane0)."""
+        assert tensor.is_cuda and tensor.dim() == 3 and tensor.stride(2) == 1, "need a device tensor [z, y, x]"
+        assert tensor.dtype == self.tensor.dtype and tensor.device == self.device, "the property grid has the grid's dtype and device"
+        assert tensor.shape[1] == self.desc.npy and tensor.shape[2] >= self.desc.npx
+        _check(self.lib, self.lib.mc33hip_property_adopt_device(self.ctx, C.c_void_p(tensor.data_ptr()), tensor.stride(1), tensor.stride(0),
+                                                                self.desc.plane0 if plane0 is None else int(plane0), tensor.shape[0]))
+        self.property = tensor  # keeps the memory alive
+
+    def detach_property(self):
+        _check(self.lib, self.lib.mc33hip_property_drop(self.ctx))
+        self.property = None
+
+    def _vertex_rows(self, V):
+        import torch
+        assert V.is_cuda and V.dim() == 2 and V.shape[1] == 3 and V.is_contiguous()
+        assert V.dtype == (torch.float64 if self.dtype == "f64" else torch.float32), "V as extract() returns it"
+
+    def sample_property(self, V):
+        """The property grid interpolated at the vertices V [n, 3] (device, as extract() returns them): a float32 tensor [n].
+        Raises MC33Error(ERUNTIME) when a vertex needs a plane outside the attached window."""
+        import torch
+        self._vertex_rows(V)
+        out = torch.empty((V.shape[0],), dtype=torch.float32, device=self.device)
+        _check(self.lib, self.lib.mc33hip_sample_property(self.ctx, C.c_void_p(V.data_ptr()), V.shape[0], C.c_void_p(out.data_ptr())))
+        _check(self.lib, self.lib.mc33hip_synchronize(self.ctx))
+        return out
+
+    def color_vertices(self, V, palette, lo, hi, nan_color=0xff5c5c5c - (1 << 32)):
+        """sample_property mapped through 2..256 palette words (0xAABBGGRR as int32) over the value range [lo, hi]: an int32
+        tensor [n]; nan_color (default: the library's DefaultColorMC grey) where the value is NaN."""
+        import torch
+        self._vertex_rows(V)
+        pal = (C.c_int * len(palette))(*[((int(x) + (1 << 31)) % (1 << 32)) - (1 << 31) for x in palette])
+        out = torch.empty((V.shape[0],), dtype=torch.int32, device=self.device)
+        _check(self.lib, self.lib.mc33hip_color_vertices(self.ctx, C.c_void_p(V.data_ptr()), V.shape[0], pal, len(palette), C.c_double(lo),
+                                                         C.c_double(hi), int(nan_color), C.c_void_p(out.data_ptr())))
+        _check(self.lib, self.lib.mc33hip_synchronize(self.ctx))
+        return out
+
+    def extract(self, iso, rng=None, with_property=False):
+        """Count, allocate exact-size outputs with torch, emit.  Returns (V, N, T, Counts); with_property: and the attached
+        property grid's value at every vertex as a fifth element."""
         import torch
         rng = rng or self.full_range()
         cnt = self.count(iso, rng)
@@ -250,6 +304,8 @@ class DeviceGrid:
         T = torch.empty((max(cnt.nT, 1), 3), dtype=torch.int32, device=self.device)
         _check(self.lib, self.lib.mc33hip_emit(self.ctx, C.c_void_p(V.data_ptr()), C.c_void_p(N.data_ptr()),
                                                C.c_void_p(T.data_ptr()), V.shape[0], T.shape[0]))
+        if with_property:
+            return V[:cnt.nV], N[:cnt.nV], T[:cnt.nT], cnt, self.sample_property(V[:cnt.nV])
         self.stream.synchronize()
         return V[:cnt.nV], N[:cnt.nV], T[:cnt.nT], cnt
 

@@ -55,6 +55,13 @@ _Static_assert(sizeof(MC33) == 160 + MC33_MATS && offsetof(MC33, memoryfault) ==
 #endif
 int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 
+/* The property-grid entry points of the device layer are referenced weakly: a device layer without them (the emulated one of
+ * the CPU tests of this file's host logic) leaves their addresses null, and MC33_set_property_grid then refuses. */
+#pragma weak mc33hip_property_upload_rows
+#pragma weak mc33hip_property_drop
+#pragma weak mc33hip_color_vertices
+#pragma weak mc33hip_download_enqueue
+
 /* One z-slab of the grid on one device (the same cut as mc33_c_library_amd/slabs.py makes per rank): cell slices
  * [z_begin, z_end), one ghost slice below (its vertices belong to the slab underneath, but the slab's triangles refer to them),
  * resident sample planes [p_lo, p_hi] = the cells' own, one above for the central differences of the normals (MC:888-890,
@@ -64,6 +71,8 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 struct staging {     /* device staging of a result, grown on demand; two sets so that calculate_isosurfaces can */
 	void *dV, *dN, *dT; /* download one surface while the next is being extracted                           */
 	unsigned long long capV, capT;
+	void *dC;           /* colours of the vertices in dV (only with a property grid and a colour map)           */
+	unsigned long long capC;
 };
 struct mc33_private_s;
 typedef struct {
@@ -90,6 +99,12 @@ typedef struct mc33_private_s {
 	int grid_dirty;      /* MC33_grid_changed: the caller rewrote samples of G->F, upload them before the next extraction */
 	int inclined;        /* G->nonortho at create time: the MC33_spnC store */
 	double grd_A[9], grd_Ai[9];
+	_GRD *prop;          /* MC33_set_property_grid: attached on every slab (only read while it is being uploaded) */
+	int has_map;         /* MC33_set_color_map */
+	unsigned map_n;
+	int map[256];
+	double map_lo, map_hi;
+	int nan_color;       /* DefaultColorMC when the surface under way was made */
 } mc33_private;
 #define MC33_MAGIC 0x4D43333348495031ull /* "MC33HIP1" */
 
@@ -263,6 +278,7 @@ void free_MC33(MC33 *M) {
 			if (s->set[k].dV) mc33hip_device_free(s->ctx, s->set[k].dV);
 			if (s->set[k].dN) mc33hip_device_free(s->ctx, s->set[k].dN);
 			if (s->set[k].dT) mc33hip_device_free(s->ctx, s->set[k].dT);
+			if (s->set[k].dC) mc33hip_device_free(s->ctx, s->set[k].dC);
 		}
 		mc33hip_destroy(s->ctx);
 	}
@@ -322,6 +338,80 @@ void MC33_grid_changed(MC33 *M) {
 	mc33_private *p = priv(M);
 	if (p)
 		p->grid_dirty = 1;
+}
+
+/* --- extension: colours from a property grid ------------------------------------------------------------------------------
+ * A slab's own vertices lie in its cell slices [z_begin, z_end) - up to rounding: a vertex on a grid plane inverts to a hair
+ * below or above it - so the slab holds property planes [max(z_begin, 1) - 1, min(z_end + 1, nz)]. */
+static void *slab_property(void *arg) {
+	mc33_slab *s = (mc33_slab *)arg;
+	const _GRD *P = s->owner->prop;
+	const unsigned lo = (s->z_begin > 1u ? s->z_begin : 1u) - 1u, hi = s->z_end + 1u < P->N[2] ? s->z_end + 1u : P->N[2];
+	s->rc = mc33hip_property_upload_rows(s->ctx, (const void *const *const *)(P->F + lo), lo, hi - lo + 1u);
+	return 0;
+}
+
+static int coloured(const mc33_private *p) { return p->prop != 0 && p->has_map; }
+
+int MC33_set_property_grid(MC33 *M, _GRD *P) {
+	mc33_private *p = priv(M);
+	if (!p || !mc33hip_property_upload_rows || !mc33hip_property_drop || !mc33hip_color_vertices || !mc33hip_download_enqueue)
+		return -1;
+	if (!P) {
+		for (int k = 0; k != p->nslab; k++) (void)mc33hip_property_drop(p->slab[k].ctx);
+		p->prop = 0;
+		return 0;
+	}
+	if (p->inclined || !P->F || P->N[0] != M->nx || P->N[1] != M->ny || P->N[2] != M->nz)
+		return -1;
+#ifndef GRD_ORTHOGONAL
+	if (P->nonortho)
+		return -1;
+#endif
+	p->prop = P;
+	for_each_slab(p, slab_property);
+	for (int k = 0; k != p->nslab; k++)
+		if (p->slab[k].rc != MC33HIP_OK) { /* a slab without its planes: no colours from any */
+			for (int q = 0; q != p->nslab; q++) (void)mc33hip_property_drop(p->slab[q].ctx);
+			p->prop = 0;
+			return -1;
+		}
+	return 0;
+}
+
+int MC33_set_color_map(MC33 *M, const int *palette, unsigned n, double lo, double hi) {
+	mc33_private *p = priv(M);
+	if (!p)
+		return -1;
+	if (!palette) {
+		p->has_map = 0;
+		return 0;
+	}
+	if (n < 2u || n > 256u || !(lo < hi))
+		return -1;
+	memcpy(p->map, palette, n * sizeof(int));
+	p->map_n = n; p->map_lo = lo; p->map_hi = hi;
+	p->has_map = 1;
+	return 0;
+}
+
+/* room for the colours of nV vertices in staging set g */
+static int ensure_color_staging(mc33_slab *s, struct staging *g, unsigned long long nV) {
+	if (g->capC >= nV && g->dC)
+		return 0;
+	if (g->dC) mc33hip_device_free(s->ctx, g->dC);
+	g->dC = 0; g->capC = 0;
+	const unsigned long long cap = nV + nV / 8 + 1024;
+	if (mc33hip_device_alloc(s->ctx, &g->dC, cap * sizeof(int)) != MC33HIP_OK) return -1;
+	g->capC = cap;
+	return 0;
+}
+
+/* the colour kernel over the nV vertices in g->dV, behind whatever wrote them on the context's stream (enqueues only) */
+static int enqueue_colors(mc33_slab *s, struct staging *g, unsigned long long nV) {
+	const mc33_private *p = s->owner;
+	if (ensure_color_staging(s, g, nV)) return MC33HIP_ENOMEM;
+	return mc33hip_color_vertices(s->ctx, g->dV, nV, p->map, p->map_n, p->map_lo, p->map_hi, p->nan_color, (int *)g->dC);
 }
 
 /* count pass of one slab (blocks until its counters are on the host) */
@@ -403,6 +493,12 @@ static int extract_to_staging(mc33_private *p, struct staging *g, MC33_real iso,
 		rc = ensure_staging(s, g, cnt->nV, cnt->nT) ? MC33HIP_ENOMEM : mc33hip_emit(s->ctx, g->dV, g->dN, g->dT, g->capV, g->capT);
 		/* mc33hip_emit only enqueues: the set must be complete before anybody reads it - the helper thread of
 		 * calculate_isosurfaces copies on a stream of its own, which is not ordered after this one */
+		if (rc == MC33HIP_OK)
+			rc = mc33hip_synchronize(s->ctx);
+	}
+	if (rc == MC33HIP_OK && coloured(p) && cnt->nV) { /* the colours into the set as well, complete like its other arrays */
+		p->nan_color = DefaultColorMC;
+		rc = enqueue_colors(s, g, cnt->nV);
 		if (rc == MC33HIP_OK)
 			rc = mc33hip_synchronize(s->ctx);
 	}
@@ -650,14 +746,16 @@ static surface *surface_from_staging(mc33_private *p, const struct staging *g, c
 	if (!S || !S->nV)
 		return S;
 	populate_fresh();
-	void *const dst[3] = {S->V, S->N, S->T};
-	const void *const src[3] = {g->dV, g->dN, g->dT};
-	const size_t bytes[3] = {(size_t)S->nV * 3 * sizeof(MC33_real), (size_t)S->nV * 12, (size_t)S->nT * 12};
-	if (mc33hip_download_many(p->slab[0].ctx, 3, dst, src, bytes, concurrent) != MC33HIP_OK) {
+	const int col = coloured(p); /* (extract_to_staging has left the colours in the set then) */
+	void *const dst[4] = {S->V, S->N, S->T, S->color};
+	const void *const src[4] = {g->dV, g->dN, g->dT, g->dC};
+	const size_t bytes[4] = {(size_t)S->nV * 3 * sizeof(MC33_real), (size_t)S->nV * 12, (size_t)S->nT * 12, (size_t)S->nV * sizeof(int)};
+	if (mc33hip_download_many(p->slab[0].ctx, col ? 4 : 3, dst, src, bytes, concurrent) != MC33HIP_OK) {
 		free_surface_memory(S);
 		return 0;
 	}
-	fill_color(S);
+	if (!col)
+		fill_color(S);
 	return S;
 }
 
@@ -672,6 +770,11 @@ static void *slab_emit(void *arg) {
 	if (ensure_staging(s, g, s->cnt.nV, s->cnt.nT)) { s->rc = MC33HIP_ENOMEM; return 0; }
 	if ((s->rc = mc33hip_set_id_base(s->ctx, (unsigned int)s->vbase)) != MC33HIP_OK) return 0;
 	s->rc = mc33hip_emit_download(s->ctx, g->dV, g->dN, g->dT, g->capV, g->capT, S->V + s->vbase, S->N + s->vbase, S->T + s->tbase);
+	if (s->rc == MC33HIP_OK && coloured(s->owner) && s->cnt.nV) { /* the colour kernel behind the vertex pass, its array behind the other copies */
+		s->rc = enqueue_colors(s, g, s->cnt.nV);
+		if (s->rc == MC33HIP_OK)
+			s->rc = mc33hip_download_enqueue(s->ctx, S->color + s->vbase, g->dC, (size_t)s->cnt.nV * sizeof(int));
+	}
 	const int w = mc33hip_download_wait(s->ctx); /* (also after a failure: nothing may still be writing into the blocks when they are released) */
 	if (s->rc == MC33HIP_OK) s->rc = w;
 	return 0;
@@ -713,13 +816,15 @@ surface *calculate_isosurface(MC33 *M, MC33_real iso) {
 			vb += s->cnt.nV; tb += s->cnt.nT;
 		}
 		pthread_t ct;
-		const int helper = S->nV >= 65536u && pthread_create(&ct, 0, fill_color_thread, S) == 0; /* 16 MB at 1024^3: 0.8 ms beside 3.4 ms of copies */
+		const int col = coloured(p); /* the colours come from the device with the other arrays: nothing to fill */
+		p->nan_color = DefaultColorMC;
+		const int helper = !col && S->nV >= 65536u && pthread_create(&ct, 0, fill_color_thread, S) == 0; /* 16 MB at 1024^3: 0.8 ms beside 3.4 ms of copies */
 		populate_fresh(); /* (blocks that did not come from the cache: their pages, before the copies need them) */
 		if (trace) t[3] = now_ms();
 		for_each_slab(p, slab_emit);
 		if (trace) t[4] = now_ms();
 		if (helper) pthread_join(ct, 0);
-		else fill_color(S);
+		else if (!col) fill_color(S);
 		for (int k = 0; k != p->nslab; k++)
 			if (p->slab[k].rc != MC33HIP_OK)
 				ok = 0;

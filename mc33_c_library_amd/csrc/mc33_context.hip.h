@@ -146,7 +146,18 @@ struct mc33hip_ctx {
 	uint64_t nsegs, ghost_segs;
 	mc33hip_counts counts;
 	mc33hip_timing timing;
+	// the property grid (mc33_property.hip.h): a second scalar field sampled at the vertices; its plane window is its own
+	sample_t *d_prop;
+	bool prop_owned;          // the library's pitched copy (mc33hip_property_upload*), not a caller's buffer
+	bool prop_pending;        // a sampling kernel was enqueued since the violation word was last looked at (prop_check)
+	size_t prop_pitch, prop_slice, prop_cap;  // in samples
+	unsigned prop_plane0, prop_nplanes;
+	uint32_t *d_prop_pal;     // the palette of the colour kernel enqueued last
+	unsigned long long *d_prop_viol, *h_prop_viol;  // vertices that needed a plane outside the window: device word, pinned copy
+	hipEvent_t ev_prop;       // mc33hip_download_enqueue
 };
+static void prop_destroy(mc33hip_ctx *c);
+static int prop_check(mc33hip_ctx *c);
 
 extern "C" const char *mc33hip_last_error(void) { return g_err; }
 static uint32_t env_u32(const char *name, uint32_t dflt);
@@ -300,6 +311,7 @@ extern "C" void mc33hip_destroy(mc33hip_ctx *c) {
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	else (void)hipDeviceSynchronize();
 	if (c->owns_grid) (void)hipFree(c->d_grid);
+	prop_destroy(c);
 	(void)hipFree(c->d_lut); (void)hipFree(c->d_rules); (void)hipFree(c->d_rule_index); (void)hipFree(c->d_fast);
 	(void)hipFree(c->d_fast_b); (void)hipFree(c->d_pat); (void)hipFree(c->d_pat_order);
 	for (int k = 0; k < MC33_LANES; k++) free_set(c->ts[k]);
@@ -373,11 +385,12 @@ static int ensure_grid(mc33hip_ctx *c) {
 // readers make, MC33_util_grd.c:147-169): 240 ms on one core, whether or not the copies over the link (77 ms) run beside it - so
 // large grids are packed by up to four threads, each with two buffers of its own in turn (a group is packed while the thread's
 // group before it goes over the link) and every fourth group of planes: profiles/r05_upload_rows.txt.
+// dst / npz / pitch: the pitched device copy that is filled - the sample grid's own, or the property grid's (mc33_property.hip.h).
 template <typename RowFn>
-static int upload_staged(mc33hip_ctx *c, RowFn row) {
-	const uint32_t npy = c->desc.npy, npz = c->desc.npz_resident;
+static int upload_staged(mc33hip_ctx *c, RowFn row, sample_t *dst, uint32_t npz, size_t pitch) {
+	const uint32_t npy = c->desc.npy;
 	const size_t rowb = (size_t)c->desc.npx * sizeof(sample_t);
-	const size_t planeb = c->slice * sizeof(sample_t);
+	const size_t planeb = pitch * npy * sizeof(sample_t);
 	size_t planes_per = (16u << 20) / planeb;
 	if (planes_per < 1) planes_per = 1;
 	if (planes_per > npz) planes_per = npz;
@@ -401,8 +414,8 @@ static int upload_staged(mc33hip_ctx *c, RowFn row) {
 			if (turn >= (two ? 2u : 1u) && (e = hipEventSynchronize(done[b])) != hipSuccess) break;  // (the buffer's last copy has left it)
 			for (uint32_t k = 0; k < kn; k++)
 				for (uint32_t j = 0; j < npy; j++)
-					memcpy(stage[b] + k * planeb + (size_t)j * c->pitch * sizeof(sample_t), row(k0 + k, j), rowb);
-			if ((e = hipMemcpyAsync((char *)c->d_grid + (size_t)k0 * planeb, stage[b], (size_t)kn * planeb, hipMemcpyHostToDevice, c->copy)) == hipSuccess)
+					memcpy(stage[b] + k * planeb + (size_t)j * pitch * sizeof(sample_t), row(k0 + k, j), rowb);
+			if ((e = hipMemcpyAsync((char *)dst + (size_t)k0 * planeb, stage[b], (size_t)kn * planeb, hipMemcpyHostToDevice, c->copy)) == hipSuccess)
 				e = hipEventRecord(done[b], c->copy);
 		}
 		for (int b = 0; b < 2; b++) {  // (its own copies done before its buffers go)
@@ -439,7 +452,7 @@ extern "C" int mc33hip_upload_contiguous(mc33hip_ctx *c, const void *host) {
 		// pageable memory falls to 0.1-0.3 GB/s (3 s for a 0.8 GB grid); packing the rows ourselves runs at memcpy speed
 		const char *h = (const char *)host;
 		const size_t npy = c->desc.npy;
-		if ((rc = upload_staged(c, [=](uint32_t k, uint32_t j) { return h + ((size_t)k * npy + j) * rowb; }))) return rc;
+		if ((rc = upload_staged(c, [=](uint32_t k, uint32_t j) { return h + ((size_t)k * npy + j) * rowb; }, c->d_grid, c->desc.npz_resident, c->pitch))) return rc;
 	} else
 		HIP_TRY(hipMemcpy2D(c->d_grid, c->pitch * sizeof(sample_t), host, rowb, rowb, (size_t)c->desc.npy * c->desc.npz_resident,
 		                    hipMemcpyHostToDevice));
@@ -463,7 +476,7 @@ extern "C" int mc33hip_upload_rows(mc33hip_ctx *c, const void *const *const *F) 
 			if ((const char *)F[k][j] != expect) { contiguous = false; break; }
 	if (contiguous) return mc33hip_upload_contiguous(c, F[0][0]);
 	// rows are separate allocations (alloc_F, reference MC33_util_grd.c:147-169)
-	if ((rc = upload_staged(c, [=](uint32_t k, uint32_t j) { return (const char *)F[k][j]; }))) return rc;
+	if ((rc = upload_staged(c, [=](uint32_t k, uint32_t j) { return (const char *)F[k][j]; }, c->d_grid, c->desc.npz_resident, c->pitch))) return rc;
 	c->counted = false;
 	forget_sweeps(c);
 	return MC33HIP_OK;

@@ -1045,7 +1045,7 @@ extern "C" int mc33hip_download_wait(mc33hip_ctx *c) {
 	if (hipSetDevice(c->device) != hipSuccess) return MC33HIP_ERUNTIME;
 	HIP_TRY(hipStreamSynchronize(c->copy));    // (ordered behind the passes by the events: the arrays are complete and on the host)
 	HIP_TRY(hipStreamSynchronize(c->stream));  // (... and nothing of the emit is left running when the caller gets its surface)
-	return MC33HIP_OK;
+	return prop_check(c);
 }
 
 extern "C" int mc33hip_extract(mc33hip_ctx *c, double iso, const mc33hip_range *range, void *dV, void *dN, void *dT,
@@ -1165,7 +1165,7 @@ extern "C" int mc33hip_synchronize(mc33hip_ctx *c) {
 	int rc = use_device(c);
 	if (rc) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	return MC33HIP_OK;
+	return prop_check(c);
 }
 
 extern "C" int mc33hip_download_many(mc33hip_ctx *c, int n, void *const *dst, const void *const *src, const size_t *bytes, int concurrent) {
@@ -1177,7 +1177,8 @@ extern "C" int mc33hip_download_many(mc33hip_ctx *c, int n, void *const *dst, co
 		if (!dst[k] || !src[k]) return MC33HIP_EINVAL;
 		if (hipMemcpyAsync(dst[k], src[k], bytes[k], hipMemcpyDeviceToHost, st) != hipSuccess) { (void)hipStreamSynchronize(st); return MC33HIP_ERUNTIME; }
 	}
-	return hipStreamSynchronize(st) == hipSuccess ? MC33HIP_OK : MC33HIP_ERUNTIME;
+	if (hipStreamSynchronize(st) != hipSuccess) return MC33HIP_ERUNTIME;
+	return concurrent ? MC33HIP_OK : prop_check(c);  // (the side stream says nothing about the sampling kernels on the context's own)
 }
 
 extern "C" int mc33hip_download_concurrent(mc33hip_ctx *c, void *dst, const void *src, size_t bytes) {
@@ -1195,7 +1196,7 @@ extern "C" int mc33hip_download(mc33hip_ctx *c, void *dst, const void *src, size
 	if (!bytes) return MC33HIP_OK;
 	HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	return MC33HIP_OK;
+	return prop_check(c);
 }
 
 extern "C" int mc33hip_device_alloc(mc33hip_ctx *c, void **dptr, size_t bytes) {

@@ -34,6 +34,8 @@
 //   k_emit_slow_slots / k_emit_slow - the generic emit of the slow records: 16 lanes per record (a lane per pattern slot) in
 //                   sequence behind the fast passes when they are few; a thread per record, on large grids on a second
 //                   stream beside the fast passes, when they are many.
+// Not part of an extraction: k_property<R,COLOR> - a property grid sampled at the vertices of a finished V array, one lane per
+//                   vertex; float values or palette colours (mc33_property.hip.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -89,3 +91,4 @@ typedef float sample_t;
 #include "mc33_emit.hip.h"
 #include "mc33_context.hip.h"
 #include "mc33_extract.hip.h"
+#include "mc33_property.hip.h"
