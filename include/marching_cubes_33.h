@@ -164,6 +164,34 @@ void MC33_grid_changed(MC33 *extractor);
 int MC33_set_property_grid(MC33 *extractor, _GRD *property);
 int MC33_set_color_map(MC33 *extractor, const int *palette, unsigned count, double lo, double hi);
 
+/* extension (not in the reference): questions about an isosurface answered on the GPU - the surface is extracted into device
+ * memory and measured there; no `surface` is allocated and nothing but these structs comes back.
+ * For triangle i with vertices q0, q1, q2 (T's order), in double, about origin[a] = r0[a] + 0.5 * (N[a] * d[a]): p_k = q_k - origin,
+ *   area     = sum 0.5 * |(p1 - p0) x (p2 - p0)|
+ *   volume   = sum p0 . (p1 x p2) / 6      SIGNED, with the winding as T stores it: the reference's winding gives a sphere whose
+ *              samples grow outwards (the README example) a NEGATIVE volume, the _nneg flavours of the library the opposite
+ *              sign.  It is the enclosed volume only for a surface that does not reach the grid's faces.
+ *   moment   = sum area_i * (p0 + p1 + p2) / 3      (the area centroid is origin + moment / area)
+ *   property_integral = sum area_i * (P(q0) + P(q1) + P(q2)) / 3 with the property grid of MC33_set_property_grid sampled at
+ *              the vertices (a colour map is not needed); 0, and has_property 0, when none is attached
+ *   bbox_min, bbox_max = the extent of the vertices (+inf / -inf for an empty surface)
+ * The exact order of operations is in mc33_hip.h (mc33hip_measure_surface).  MC33_measure_components lists the connected
+ * components (vertices joined through triangles) that have at least one triangle, in ascending order of `root`, the smallest
+ * vertex index of the component; *unreferenced = vertices no triangle names.  With `capacity` below the number of components it
+ * returns -2, the number in *components, and writes no row (table NULL, capacity 0 asks for the number).
+ * MC33_measure_isosurface returns 0, or -1; MC33_measure_isosurfaces measures `count` isovalues, classifying up to eight per
+ * pass over the grid like calculate_isosurfaces, and returns how many succeeded (a failed one leaves its struct zeroed).
+ * All set extractor->iso like size_of_isosurface and leave memoryfault alone.
+ * Refused with -1: an extractor spread over several devices (MC33_HIP_DEVICES with more than one slab: a slab's triangles name
+ * vertices that live in its neighbour's arrays, so neither the sums nor the components are local to a device). */
+typedef struct mc33_measure { unsigned nV, nT; double area, volume, moment[3], origin[3], bbox_min[3], bbox_max[3];
+                              double property_integral; int has_property; } mc33_measure;
+typedef struct mc33_component { unsigned root, nV, nT; double area, volume; } mc33_component;
+int MC33_measure_isosurface(MC33 *extractor, MC33_real isovalue, mc33_measure *out);
+unsigned MC33_measure_isosurfaces(MC33 *extractor, const MC33_real *isovalues, unsigned count, mc33_measure *out);
+int MC33_measure_components(MC33 *extractor, MC33_real isovalue, mc33_component *table, unsigned capacity, unsigned *components,
+                            unsigned *unreferenced);
+
 /* ---- inclined grids (reference header :186-191) ---------------------------------------------------------
  * c = A b (transposed == 0) or A^T b for a 3x3 matrix; _multTSA_bf assumes an upper triangular A.  A caller may
  * point mult_Abf at either; calculate_isosurface looks at the pointer when it is called and runs the matching

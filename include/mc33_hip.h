@@ -224,6 +224,50 @@ int mc33hip_color_vertices(mc33hip_ctx *c, const void *dV, unsigned long long nV
  * everything enqueued on the context's stream so far is through.  Only enqueues; mc33hip_download_wait waits for it too. */
 int mc33hip_download_enqueue(mc33hip_ctx *c, void *host_dst, const void *device_src, size_t bytes);
 
+/* --- measures of a finished mesh, taken on the device (no counterpart in the reference) -----------------------------------------
+ * V (nV x 3 MC33_real) and T (nT x 3 unsigned) in device memory as mc33hip_emit wrote them for a whole grid (id base 0: T indexes
+ * V directly); any such mesh, inclined grids and every sample type included.  Everything in IEEE double, nothing fused, for
+ * triangle i with rows q0, q1, q2 = V[T[i][0..2]] and the reference point c[a] = r0[a] + 0.5 * ((double)N[a] * d[a]) of the
+ * context's grid (it only conditions the sums):
+ *   p_k = (double)q_k - c;  u = p1 - p0, w = p2 - p0;  n = u x w;  A_i = 0.5 * sqrt((n.x*n.x + n.y*n.y) + n.z*n.z)
+ *   m = p1 x p2;  W_i = ((p0.x*m.x + p0.y*m.y) + p0.z*m.z) / 6.0;  M_i[a] = A_i * (((p0[a] + p1[a]) + p2[a]) / 3.0)
+ *   Q_i = A_i * ((((double)P[T[i][0]] + (double)P[T[i][1]]) + (double)P[T[i][2]]) / 3.0),  P: what mc33hip_sample_property left
+ * volume is SIGNED, with the winding as T stores it: the reference's winding gives a sphere whose samples grow outwards a
+ * NEGATIVE volume, a context with mc33hip_set_normal_neg on the opposite sign.  It is the enclosed volume only for a surface
+ * that does not reach the grid's faces (an open sheet has no inside; nothing here reports closedness).  The area centroid is
+ * origin + moment / area.  bbox_min / bbox_max: exact minimum / maximum of the rows of V per axis (+inf / -inf for nV == 0, a NaN
+ * coordinate is skipped); NaN in V or P otherwise propagates into the sums.  The sums are accumulated in double from the first
+ * addition on, without floating-point atomics: two calls on the same mesh in one process return the same bits.
+ *
+ * Components: two vertices are connected when a triangle names both; label[v] = the smallest vertex index connected to v; a
+ * vertex no triangle names keeps label[v] = v and is unreferenced; a component is a connected set with at least one triangle.
+ * The table lists the components in ascending order of root (= their label); a triangle belongs to label[T[i][0]].  The two
+ * double columns are added with atomics and may differ in their last bits from call to call.
+ *
+ * All three enqueue on the context's stream behind whatever is on it, wait, and bring the small results to the host.  A triangle
+ * that names a vertex >= nV is counted on the device, contributes nothing - nothing outside V is read - and the call returns
+ * MC33HIP_ERUNTIME with the count in mc33hip_last_error.  MC33HIP_EINVAL: a null pointer where the size is not zero, nV or nT
+ * above 2^32-1.  mc33hip_measure_components with capacity below the number of components returns MC33HIP_ECAPACITY with that
+ * number in *components and leaves the table untouched (host_table NULL, capacity 0 asks for it); dLabel is what
+ * mc33hip_label_components made for the same T and nV. */
+typedef struct {
+	unsigned long long nV, nT;
+	double area, volume;          /* sum A_i, sum W_i                                  */
+	double moment[3], origin[3];  /* sum M_i about origin = c                          */
+	double bbox_min[3], bbox_max[3];
+	double property_integral;     /* sum Q_i; 0 and has_property 0 when dP == NULL     */
+	int has_property;
+} mc33hip_measures;
+typedef struct { unsigned root, nV, nT; double area, volume; } mc33hip_component;
+
+int mc33hip_measure_surface(mc33hip_ctx *c, const void *dV, unsigned long long nV, const void *dT, unsigned long long nT,
+                            const float *dP, mc33hip_measures *out);
+int mc33hip_label_components(mc33hip_ctx *c, const void *dT, unsigned long long nT, unsigned long long nV, unsigned *dLabel,
+                             unsigned long long *components, unsigned long long *unreferenced);
+int mc33hip_measure_components(mc33hip_ctx *c, const void *dV, unsigned long long nV, const void *dT, unsigned long long nT,
+                               const unsigned *dLabel, mc33hip_component *host_table, unsigned long long capacity,
+                               unsigned long long *components);
+
 /* Plain device allocations on the context's device (for language bindings). */
 int mc33hip_device_alloc(mc33hip_ctx *c, void **dptr, size_t bytes);
 int mc33hip_device_free(mc33hip_ctx *c, void *dptr);

@@ -32,6 +32,16 @@ class Timing(C.Structure):
                 ("sweep_launches", C.c_uint)]
 
 
+class Measures(C.Structure):
+    _fields_ = [("nV", C.c_ulonglong), ("nT", C.c_ulonglong), ("area", C.c_double), ("volume", C.c_double),
+                ("moment", C.c_double * 3), ("origin", C.c_double * 3), ("bbox_min", C.c_double * 3), ("bbox_max", C.c_double * 3),
+                ("property_integral", C.c_double), ("has_property", C.c_int)]
+
+
+class Component(C.Structure):
+    _fields_ = [("root", C.c_uint), ("nV", C.c_uint), ("nT", C.c_uint), ("area", C.c_double), ("volume", C.c_double)]
+
+
 HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_last_error", "mc33hip_upload_rows",
            "mc33hip_upload_contiguous", "mc33hip_adopt_device", "mc33hip_set_stream", "mc33hip_count",
            "mc33hip_emit", "mc33hip_extract", "mc33hip_last_timing", "mc33hip_download",
@@ -39,13 +49,15 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_emit_download", "mc33hip_download_wait", "mc33hip_own_stream", "mc33hip_device_count", "mc33hip_count_async",
            "mc33hip_counts_to_device", "mc33hip_bases_from_table", "mc33hip_emit_at_device_bases", "mc33hip_count_finish",
            "mc33hip_property_upload_rows", "mc33hip_property_upload_contiguous", "mc33hip_property_adopt_device", "mc33hip_property_drop",
-           "mc33hip_sample_property", "mc33hip_color_vertices", "mc33hip_download_enqueue"]
+           "mc33hip_sample_property", "mc33hip_color_vertices", "mc33hip_download_enqueue",
+           "mc33hip_measure_surface", "mc33hip_label_components", "mc33hip_measure_components"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
                  "write_bin_s", "read_bin_s", "write_txt_s", "write_obj_s", "write_ply_s",
                  "read_grd", "read_grd_binary", "read_scanfiles", "read_raw_file", "read_dat_file", "calculate_isosurfaces", "MC33_grid_changed",
-                 "MC33_set_property_grid", "MC33_set_color_map"]
+                 "MC33_set_property_grid", "MC33_set_color_map",
+                 "MC33_measure_isosurface", "MC33_measure_isosurfaces", "MC33_measure_components"]
 
 
 class MC33Error(RuntimeError):
@@ -111,8 +123,29 @@ def load_library(dtype="f32"):
     lib.mc33hip_sample_property.argtypes = [V, V, C.c_ulonglong, V]
     lib.mc33hip_color_vertices.argtypes = [V, V, C.c_ulonglong, P(C.c_int), C.c_uint, C.c_double, C.c_double, C.c_int, V]
     lib.mc33hip_download_enqueue.argtypes = [V, V, V, C.c_size_t]
+    lib.mc33hip_measure_surface.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V, P(Measures)]
+    lib.mc33hip_label_components.argtypes = [V, V, C.c_ulonglong, C.c_ulonglong, V, P(C.c_ulonglong), P(C.c_ulonglong)]
+    lib.mc33hip_measure_components.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V, V, C.c_ulonglong, P(C.c_ulonglong)]
     _libs[dtype] = lib
     return lib
+
+
+class SurfaceMeasures:
+    """What DeviceGrid.measure returns: nV, nT, area, volume (signed, with the winding of T), moment and origin (the area
+    centroid is origin + moment / area: `centroid`), bbox_min, bbox_max, property_integral, has_property."""
+
+    def __init__(self, m):
+        self.nV, self.nT, self.area, self.volume = int(m.nV), int(m.nT), m.area, m.volume
+        self.moment, self.origin = tuple(m.moment), tuple(m.origin)
+        self.bbox_min, self.bbox_max = tuple(m.bbox_min), tuple(m.bbox_max)
+        self.property_integral, self.has_property = m.property_integral, int(m.has_property)
+
+    @property
+    def centroid(self):
+        return tuple(o + (q / self.area if self.area else float("nan")) for o, q in zip(self.origin, self.moment))
+
+    def __repr__(self):
+        return "SurfaceMeasures(nV=%d, nT=%d, area=%r, volume=%r, centroid=%r)" % (self.nV, self.nT, self.area, self.volume, self.centroid)
 
 
 def _check(lib, rc, allow=()):
@@ -308,6 +341,73 @@ class DeviceGrid:
             return V[:cnt.nV], N[:cnt.nV], T[:cnt.nT], cnt, self.sample_property(V[:cnt.nV])
         self.stream.synchronize()
         return V[:cnt.nV], N[:cnt.nV], T[:cnt.nT], cnt
+
+    # -- measures of a finished mesh, taken on the device (mc33_hip.h: mc33hip_measure_surface and its siblings) ------------------
+    def _triangle_rows(self, T):
+        import torch
+        assert T.is_cuda and T.dim() == 2 and T.shape[1] == 3 and T.is_contiguous() and T.dtype == torch.int32, "T as extract() returns it"
+
+    def measure(self, V, T, P=None):
+        """Area, signed volume, first moments, bounding box of the mesh V [n, 3], T [m, 3] (device tensors, as extract() returns
+        them) and, with P (float32 [n], what sample_property returned), the integral of P over the surface: a SurfaceMeasures.
+        Raises MC33Error(ERUNTIME) when a triangle names a vertex >= n."""
+        import torch
+        self._vertex_rows(V)
+        self._triangle_rows(T)
+        if P is not None:
+            assert P.is_cuda and P.dtype == torch.float32 and P.is_contiguous() and P.numel() == V.shape[0]
+        m = Measures()
+        _check(self.lib, self.lib.mc33hip_measure_surface(self.ctx, C.c_void_p(V.data_ptr()), V.shape[0], C.c_void_p(T.data_ptr()), T.shape[0],
+                                                          C.c_void_p(P.data_ptr()) if P is not None else None, C.byref(m)))
+        return SurfaceMeasures(m)
+
+    def label_components(self, T, nV):
+        """(labels, components, unreferenced): labels an int32 tensor [nV] holding the uint32 words label[v] = the smallest
+        vertex index connected to v through triangles of T."""
+        import torch
+        self._triangle_rows(T)
+        labels = torch.empty((int(nV),), dtype=torch.int32, device=self.device)
+        nc, nu = C.c_ulonglong(), C.c_ulonglong()
+        _check(self.lib, self.lib.mc33hip_label_components(self.ctx, C.c_void_p(T.data_ptr()), T.shape[0], int(nV), C.c_void_p(labels.data_ptr()),
+                                                           C.byref(nc), C.byref(nu)))
+        return labels, nc.value, nu.value
+
+    def measure_components(self, V, T, labels=None):
+        """The component table - root, nV, nT, area, volume per component, in ascending order of root - as a numpy structured
+        array; labels: what label_components returned for T (made here when None)."""
+        import numpy as np
+        self._vertex_rows(V)
+        self._triangle_rows(T)
+        if labels is None:
+            labels = self.label_components(T, V.shape[0])[0]
+        assert labels.is_cuda and labels.is_contiguous() and labels.numel() == V.shape[0] and labels.element_size() == 4
+        args = (self.ctx, C.c_void_p(V.data_ptr()), V.shape[0], C.c_void_p(T.data_ptr()), T.shape[0], C.c_void_p(labels.data_ptr()))
+        n = C.c_ulonglong()
+        _check(self.lib, self.lib.mc33hip_measure_components(*args, None, 0, C.byref(n)), allow=(ECAPACITY,))
+        table = np.zeros(n.value, dtype=np.dtype(Component))
+        if n.value:
+            _check(self.lib, self.lib.mc33hip_measure_components(*args, C.c_void_p(table.ctypes.data), n.value, C.byref(n)))
+        return table
+
+    def measure_iso(self, iso, rng=None, with_property=False):
+        """Count, emit into torch tensors, measure - nothing but the result crosses the link; with_property: the attached
+        property grid is sampled at the vertices first and its integral over the surface filled in."""
+        import torch
+        rng = rng or self.full_range()
+        cnt = self.count(iso, rng)
+        V = torch.empty((max(cnt.nV, 1), 3), dtype=torch.float64 if self.dtype == "f64" else torch.float32, device=self.device)
+        N = torch.empty((max(cnt.nV, 1), 3), dtype=torch.float32, device=self.device)
+        T = torch.empty((max(cnt.nT, 1), 3), dtype=torch.int32, device=self.device)
+        _check(self.lib, self.lib.mc33hip_emit(self.ctx, C.c_void_p(V.data_ptr()), C.c_void_p(N.data_ptr()),
+                                               C.c_void_p(T.data_ptr()), V.shape[0], T.shape[0]))
+        P = None
+        if with_property:
+            P = torch.empty((max(cnt.nV, 1),), dtype=torch.float32, device=self.device)
+            _check(self.lib, self.lib.mc33hip_sample_property(self.ctx, C.c_void_p(V.data_ptr()), cnt.nV, C.c_void_p(P.data_ptr())))
+        m = Measures()
+        _check(self.lib, self.lib.mc33hip_measure_surface(self.ctx, C.c_void_p(V.data_ptr()), cnt.nV, C.c_void_p(T.data_ptr()), cnt.nT,
+                                                          C.c_void_p(P.data_ptr()) if P is not None else None, C.byref(m)))
+        return SurfaceMeasures(m)
 
     def probe_read(self, reps=10):
         """A plain read of the resident grid (nothing to do with an extraction): (best ms, median ms, bytes)."""

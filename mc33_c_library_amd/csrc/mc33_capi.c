@@ -61,6 +61,13 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_property_drop
 #pragma weak mc33hip_color_vertices
 #pragma weak mc33hip_download_enqueue
+/* ... and so are the measuring ones (MC33_measure_*): without them these functions return -1 */
+#pragma weak mc33hip_sample_property
+#pragma weak mc33hip_measure_surface
+#pragma weak mc33hip_label_components
+#pragma weak mc33hip_measure_components
+_Static_assert(sizeof(mc33_component) == sizeof(mc33hip_component) && offsetof(mc33_component, area) == offsetof(mc33hip_component, area),
+               "mc33_component and mc33hip_component are one layout");
 
 /* One z-slab of the grid on one device (the same cut as mc33_c_library_amd/slabs.py makes per rank): cell slices
  * [z_begin, z_end), one ghost slice below (its vertices belong to the slab underneath, but the slab's triangles refer to them),
@@ -105,6 +112,8 @@ typedef struct mc33_private_s {
 	int map[256];
 	double map_lo, map_hi;
 	int nan_color;       /* DefaultColorMC when the surface under way was made */
+	void *dP, *dL;       /* MC33_measure_*: property values / component labels of the vertices in slab[0].set[0] (device) */
+	unsigned long long capP, capL;
 } mc33_private;
 #define MC33_MAGIC 0x4D43333348495031ull /* "MC33HIP1" */
 
@@ -280,6 +289,8 @@ void free_MC33(MC33 *M) {
 			if (s->set[k].dT) mc33hip_device_free(s->ctx, s->set[k].dT);
 			if (s->set[k].dC) mc33hip_device_free(s->ctx, s->set[k].dC);
 		}
+		if (q == 0 && p->dP) mc33hip_device_free(s->ctx, p->dP);
+		if (q == 0 && p->dL) mc33hip_device_free(s->ctx, p->dL);
 		mc33hip_destroy(s->ctx);
 	}
 	p->magic = 0;
@@ -476,9 +487,9 @@ static int ensure_staging(mc33_slab *s, struct staging *g, unsigned long long nV
 	return 0;
 }
 
-/* GPU part of one surface of calculate_isosurfaces (one slab: the whole grid): the surface of `iso` into staging set g (device
- * memory), its sizes into *cnt */
-static int extract_to_staging(mc33_private *p, struct staging *g, MC33_real iso, mc33hip_counts *cnt) {
+/* count, grow, emit (one slab: the whole grid): V, N, T of the surface of `iso` into staging set g (device memory), its sizes
+ * into *cnt */
+static int extract_geometry(mc33_private *p, struct staging *g, MC33_real iso, mc33hip_counts *cnt) {
 	mc33_slab *s = &p->slab[0];
 	mc33hip_range r;
 	r.z_begin = 0; r.z_end = p->pub.nz; r.ghost_below = 0; r.id_base = 0;
@@ -496,6 +507,13 @@ static int extract_to_staging(mc33_private *p, struct staging *g, MC33_real iso,
 		if (rc == MC33HIP_OK)
 			rc = mc33hip_synchronize(s->ctx);
 	}
+	return rc;
+}
+
+/* GPU part of one surface of calculate_isosurfaces: extract_geometry, and the colours where they come from the device */
+static int extract_to_staging(mc33_private *p, struct staging *g, MC33_real iso, mc33hip_counts *cnt) {
+	mc33_slab *s = &p->slab[0];
+	int rc = extract_geometry(p, g, iso, cnt);
 	if (rc == MC33HIP_OK && coloured(p) && cnt->nV) { /* the colours into the set as well, complete like its other arrays */
 		p->nan_color = DefaultColorMC;
 		rc = enqueue_colors(s, g, cnt->nV);
@@ -925,6 +943,113 @@ unsigned int calculate_isosurfaces(MC33 *M, const MC33_real *iso, unsigned int n
 		else M->memoryfault = 1;
 	}
 	return done;
+}
+
+/* --- extension: measures of an isosurface, taken on the device ----------------------------------------------------------------
+ * The surface goes into staging set 0 - count, grow, emit, without the colour pass - and is measured there. */
+static mc33_private *measurable(MC33 *M) {
+	mc33_private *p = priv(M);
+	if (!p || p->nslab != 1 || !mc33hip_measure_surface || !mc33hip_label_components || !mc33hip_measure_components || !mc33hip_sample_property)
+		return 0;
+	return p;
+}
+
+static int ensure_words(mc33_slab *s, void **d, unsigned long long *cap, unsigned long long n) { /* n 4-byte words of device memory */
+	if (*d && *cap >= n)
+		return 0;
+	if (*d) mc33hip_device_free(s->ctx, *d);
+	*d = 0; *cap = 0;
+	const unsigned long long c = n + n / 8 + 1024;
+	if (mc33hip_device_alloc(s->ctx, d, c * 4) != MC33HIP_OK) return -1;
+	*cap = c;
+	return 0;
+}
+
+static int measure_one(mc33_private *p, MC33_real iso, mc33_measure *out) {
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0];
+	mc33hip_counts cnt;
+	mc33hip_measures m;
+	memset(out, 0, sizeof *out);
+	p->pub.iso = iso;
+	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK)
+		return -1;
+	const float *dP = 0;
+	if (p->prop) { /* the property at the vertices first, into a float array of its own */
+		if (ensure_words(s, &p->dP, &p->capP, cnt.nV) || mc33hip_sample_property(s->ctx, g->dV, cnt.nV, (float *)p->dP) != MC33HIP_OK)
+			return -1;
+		dP = (const float *)p->dP;
+	}
+	if (mc33hip_measure_surface(s->ctx, g->dV, cnt.nV, g->dT, cnt.nT, dP, &m) != MC33HIP_OK)
+		return -1;
+	out->nV = (unsigned)m.nV; out->nT = (unsigned)m.nT;
+	out->area = m.area; out->volume = m.volume;
+	for (int a = 0; a != 3; a++) {
+		out->moment[a] = m.moment[a]; out->origin[a] = m.origin[a];
+		out->bbox_min[a] = m.bbox_min[a]; out->bbox_max[a] = m.bbox_max[a];
+	}
+	out->property_integral = m.property_integral;
+	out->has_property = m.has_property;
+	return 0;
+}
+
+int MC33_measure_isosurface(MC33 *M, MC33_real iso, mc33_measure *out) {
+	mc33_private *p = measurable(M);
+	if (!p || !out)
+		return -1;
+	return measure_one(p, iso, out);
+}
+
+unsigned MC33_measure_isosurfaces(MC33 *M, const MC33_real *iso, unsigned count, mc33_measure *out) {
+	mc33_private *p = measurable(M);
+	unsigned done = 0;
+	if (!out)
+		return 0;
+	memset(out, 0, (size_t)count * sizeof *out);
+	if (!p || !iso)
+		return 0;
+	if (refresh_grid(p) != MC33HIP_OK)
+		return 0;
+	for (unsigned k = 0; k != count; k++) {
+		if (k % 8 == 0 && count - k > 1) { /* the sweeps of the next (up to) 8 isovalues in one or two passes over the grid */
+			double many[8];
+			const unsigned m = count - k < 8 ? count - k : 8;
+			mc33hip_range r;
+			r.z_begin = 0; r.z_end = M->nz; r.ghost_below = 0; r.id_base = 0;
+			for (unsigned q = 0; q != m; q++) many[q] = iso[k + q];
+			if (!p->reupload)
+				(void)mc33hip_sweep_many(p->slab[0].ctx, many, (int)m, &r); /* (on failure the single calls sweep for themselves) */
+		}
+		if (measure_one(p, iso[k], &out[k]) == 0)
+			done++;
+		else
+			memset(&out[k], 0, sizeof out[k]);
+	}
+	return done;
+}
+
+int MC33_measure_components(MC33 *M, MC33_real iso, mc33_component *table, unsigned capacity, unsigned *components, unsigned *unreferenced) {
+	mc33_private *p = measurable(M);
+	if (components) *components = 0;
+	if (unreferenced) *unreferenced = 0;
+	if (!p || (capacity && !table))
+		return -1;
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0];
+	mc33hip_counts cnt;
+	M->iso = iso;
+	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK || ensure_words(s, &p->dL, &p->capL, cnt.nV))
+		return -1;
+	unsigned long long nc = 0, nu = 0;
+	if (mc33hip_label_components(s->ctx, g->dT, cnt.nT, cnt.nV, (unsigned *)p->dL, &nc, &nu) != MC33HIP_OK)
+		return -1;
+	if (components) *components = (unsigned)nc;
+	if (unreferenced) *unreferenced = (unsigned)nu;
+	if (capacity < nc)
+		return -2;
+	if (!nc)
+		return 0;
+	return mc33hip_measure_components(s->ctx, g->dV, cnt.nV, g->dT, cnt.nT, (const unsigned *)p->dL, (mc33hip_component *)table, capacity, &nc) == MC33HIP_OK ? 0 : -1;
 }
 
 void free_surface_memory(surface *S) { /* MC:84-92 */

@@ -155,8 +155,10 @@ struct mc33hip_ctx {
 	uint32_t *d_prop_pal;     // the palette of the colour kernel enqueued last
 	unsigned long long *d_prop_viol, *h_prop_viol;  // vertices that needed a plane outside the window: device word, pinned copy
 	hipEvent_t ev_prop;       // mc33hip_download_enqueue
+	struct MeasureState *meas;  // scratch of the measuring passes (mc33_measure.hip.h), made by the first of them
 };
 static void prop_destroy(mc33hip_ctx *c);
+static void meas_destroy(mc33hip_ctx *c);
 static int prop_check(mc33hip_ctx *c);
 
 extern "C" const char *mc33hip_last_error(void) { return g_err; }
@@ -312,6 +314,7 @@ extern "C" void mc33hip_destroy(mc33hip_ctx *c) {
 	else (void)hipDeviceSynchronize();
 	if (c->owns_grid) (void)hipFree(c->d_grid);
 	prop_destroy(c);
+	meas_destroy(c);
 	(void)hipFree(c->d_lut); (void)hipFree(c->d_rules); (void)hipFree(c->d_rule_index); (void)hipFree(c->d_fast);
 	(void)hipFree(c->d_fast_b); (void)hipFree(c->d_pat); (void)hipFree(c->d_pat_order);
 	for (int k = 0; k < MC33_LANES; k++) free_set(c->ts[k]);

@@ -36,6 +36,8 @@
 //                   stream beside the fast passes, when they are many.
 // Not part of an extraction: k_property<R,COLOR> - a property grid sampled at the vertices of a finished V array, one lane per
 //                   vertex; float values or palette colours (mc33_property.hip.h).
+//                   k_measure_* / k_cc_* - area, volume, moments, bounding box and connected components of a finished V, T pair;
+//                   a few doubles come back instead of the mesh (mc33_measure.hip.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -92,3 +94,4 @@ typedef float sample_t;
 #include "mc33_context.hip.h"
 #include "mc33_extract.hip.h"
 #include "mc33_property.hip.h"
+#include "mc33_measure.hip.h"

@@ -1,0 +1,464 @@
+"""GPU tests of the surface measures taken on the device (include/mc33_hip.h: mc33hip_measure_surface, mc33hip_label_components,
+mc33hip_measure_components; include/marching_cubes_33.h: MC33_measure_isosurface(s), MC33_measure_components).
+
+V, T always come from the reference twin (oracle/_ref), which tests/test_gpu_parity.py proves bit-equal to the product's; the
+expected values come from tests/measure_oracle.py, the definition in numpy float64.  Every double sum S = sum x_i over n terms
+must satisfy |got - fsum(x)| <= (n + 8) * 2^-53 * fsum(|x_i|) - a bound that holds for every order of the additions as long as
+they are made in double - integers, labels and the bounding box are compared exactly."""
+import ctypes as C
+import os
+import struct
+import sys
+
+import numpy as np
+import pytest
+
+import fixtures as fx
+import measure_oracle as mo
+import property_oracle as po
+from mc33_capi import MC33Lib, product_path, ref_path
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+AWKWARD_R0, AWKWARD_D = mo.AWKWARD_R0, mo.AWKWARD_D
+
+
+def to_device(a):
+    import torch
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.uint32:
+        a = a.view(np.int32)
+    elif a.dtype == np.uint16:
+        a = a.view(np.int16)
+    return torch.from_numpy(a).cuda()
+
+
+def device_grid(data, r0, d, prop=None):
+    from mc33_c_library_amd import DeviceGrid
+    g = DeviceGrid(to_device(data), r0=r0, d=d)
+    if prop is not None:
+        g.attach_property(to_device(prop))
+    return g
+
+
+def reference_mesh(reflibs, name, dtype="f32"):
+    """(data, r0, d, iso, reference surface) of a fixture row; the row's figures are asserted on the reference's mesh first"""
+    field, iso, (nV, nT, _, _, edges) = mo.FIXTURES[name]
+    data, r0, d = field()
+    s = reflibs[dtype].isosurface(data, iso, r0, d)
+    assert (s.nV, s.nT) == (nV, nT) and mo.open_edges(s.T) == edges, "fixture %s drifted: %d vertices, %d triangles" % (name, s.nV, s.nT)
+    return data, r0, d, iso, s
+
+
+def check_sum(what, got, want, bound):
+    err = abs(got - want)
+    print("%-22s got %.17g  oracle %.17g  |diff| %.3g  bound %.3g" % (what, got, want, err, bound))
+    assert err <= bound, "%s: |%.17g - %.17g| = %.3g exceeds the bound %.3g" % (what, got, want, err, bound)
+
+
+def check_measures(label, got, want):
+    assert (got.nV, got.nT) == (want.nV, want.nT)
+    check_sum(label + " area", got.area, want.area, want.area_bound)
+    check_sum(label + " volume", got.volume, want.volume, want.volume_bound)
+    for a in range(3):
+        check_sum(label + " moment[%d]" % a, got.moment[a], want.moment[a], want.moment_bound[a])
+    assert tuple(got.origin) == tuple(want.origin.tolist())
+    assert tuple(got.bbox_min) == tuple(want.bbox_min.tolist()) and tuple(got.bbox_max) == tuple(want.bbox_max.tolist()), (got.bbox_min, got.bbox_max, want.bbox_min, want.bbox_max)
+    assert got.has_property == want.has_property
+    if want.has_property:
+        check_sum(label + " property", got.property_integral, want.property_integral, want.property_bound)
+    else:
+        assert got.property_integral == 0.0
+
+
+def all_bits(m):
+    return struct.pack("<15d", m.area, m.volume, *m.moment, *m.origin, *m.bbox_min, *m.bbox_max, m.property_integral)
+
+
+def check_table(label, got, want, ab, wb, totals=None):
+    assert got.shape[0] == want.shape[0], "%s: %d components, oracle %d" % (label, got.shape[0], want.shape[0])
+    for col in ("root", "nV", "nT"):
+        assert np.array_equal(got[col], want[col]), "%s: column %s differs in %d rows" % (label, col, np.count_nonzero(got[col] != want[col]))
+    assert np.all(np.diff(got["root"].astype(np.int64)) > 0)
+    ea, ew = np.abs(got["area"] - want["area"]), np.abs(got["volume"] - want["volume"])
+    print("%s: %d components; worst area diff / bound %.3g, volume %.3g" % (label, got.shape[0], float(np.max(ea / ab, initial=0.0)), float(np.max(ew / wb, initial=0.0))))
+    assert np.all(ea <= ab) and np.all(ew <= wb)
+    if totals is not None:  # the columns add up to the surface's totals
+        check_sum(label + " sum of areas", mo.fsum(got["area"]), totals.area, totals.area_bound)
+        check_sum(label + " sum of volumes", mo.fsum(got["volume"]), totals.volume, totals.volume_bound)
+        assert int(got["nT"].sum()) == totals.nT
+
+
+# ---- 1 - 3: the five fixture rows, float ---------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", list(mo.FIXTURES))
+def test_measure_f32(reflibs, name):
+    data, r0, d, iso, s = reference_mesh(reflibs, name)
+    want = mo.measure(s.V, s.T, r0, d, data.shape)
+    g = device_grid(data, r0, d)
+    V, T = to_device(s.V), to_device(s.T)
+    got = g.measure(V, T)
+    check_measures(name, got, want)
+    assert all_bits(g.measure(V, T)) == all_bits(got), "two calls on the same mesh differ"
+    own = g.measure_iso(iso)  # the product's own extraction: its V, T are the reference's bit for bit
+    check_measures(name + " (measure_iso)", own, want)
+    c = got.centroid
+    assert all(abs(c[a] - want.centroid[a]) <= 1e-9 * (1.0 + abs(want.centroid[a])) for a in range(3))
+
+
+@pytest.mark.parametrize("name", list(mo.FIXTURES))
+def test_label_components_f32(reflibs, name):
+    data, r0, d, iso, s = reference_mesh(reflibs, name)
+    lab, ncomp, unref, _ = mo.label_components(s.T, s.nV)
+    assert (ncomp, unref) == mo.FIXTURES[name][2][2:4]
+    g = device_grid(data, r0, d)
+    got, gc, gu = g.label_components(to_device(s.T), s.nV)
+    got = got.cpu().numpy().view(np.uint32)
+    assert np.array_equal(got, lab), "%d of %d labels differ" % (np.count_nonzero(got != lab), lab.size)
+    assert (gc, gu) == (ncomp, unref)
+    again = g.label_components(to_device(s.T), s.nV)[0].cpu().numpy().view(np.uint32)
+    assert np.array_equal(again, lab)
+
+
+@pytest.mark.parametrize("name", list(mo.FIXTURES))
+def test_measure_components_f32(reflibs, name):
+    from mc33_c_library_amd.api import Component, ECAPACITY
+    data, r0, d, iso, s = reference_mesh(reflibs, name)
+    totals = mo.measure(s.V, s.T, r0, d, data.shape)
+    lab = mo.label_components(s.T, s.nV)[0]
+    want, ab, wb = mo.component_table(s.V, s.T, lab, totals.origin)
+    assert want.shape[0] == mo.FIXTURES[name][2][2]
+    g = device_grid(data, r0, d)
+    V, T = to_device(s.V), to_device(s.T)
+    labels = g.label_components(T, s.nV)[0]
+    got = g.measure_components(V, T, labels)
+    check_table(name, got, want, ab, wb, totals)
+    check_table(name + " (labels made inside)", g.measure_components(V, T), want, ab, wb)
+    # the size query, and a table one row too small: ECAPACITY, the needed number, nothing written
+    n = C.c_ulonglong(0)
+    args = (g.ctx, C.c_void_p(V.data_ptr()), s.nV, C.c_void_p(T.data_ptr()), s.nT, C.c_void_p(labels.data_ptr()))
+    assert g.lib.mc33hip_measure_components(*args, None, 0, C.byref(n)) == ECAPACITY and n.value == want.shape[0]
+    small = np.full(max(want.shape[0] - 1, 1), 0x55, np.uint8).repeat(C.sizeof(Component))
+    n = C.c_ulonglong(0)
+    assert g.lib.mc33hip_measure_components(*args, C.c_void_p(small.ctypes.data), want.shape[0] - 1, C.byref(n)) == ECAPACITY
+    assert n.value == want.shape[0] and np.all(small == 0x55)
+
+
+# ---- 4: the property integral -------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ["sheet", "noise"])
+def test_property_integral(reflibs, name):
+    data, r0, d, iso, s = reference_mesh(reflibs, name)
+    P = fx.noise_f32(0, 77, shape=data.shape) * np.float32(1000.0)
+    Pv = po.sample_property(s.V, r0, d, P)
+    want = mo.measure(s.V, s.T, r0, d, data.shape, P=Pv)
+    assert want.has_property == 1 and want.property_integral != 0.0
+    g = device_grid(data, r0, d, P)
+    V, T = to_device(s.V), to_device(s.T)
+    dP = g.sample_property(V)
+    assert np.array_equal(dP.cpu().numpy().view(np.uint32), Pv.view(np.uint32))
+    check_measures(name, g.measure(V, T, dP), want)
+    check_measures(name + " (measure_iso)", g.measure_iso(iso, with_property=True), want)
+    plain = g.measure(V, T)
+    assert plain.has_property == 0 and plain.property_integral == 0.0
+
+
+# ---- 5: the other builds ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dtype", ["u8", "u16", "u32", "f64"])
+def test_other_sample_types(reflibs, dtype):
+    n = 40
+    if dtype == "f64":
+        data, iso = fx.cos_field(n, dtype=np.float64)[0], 0.0
+    elif dtype == "u8":
+        data, iso = fx.cos_field_int(n, np.uint8, 40.0, 128.0), 128.5
+    elif dtype == "u16":
+        data, iso = fx.cos_field_int(n, np.uint16, 10000.0, 32768.0), 32768.5
+    else:
+        data, iso = fx.cos_field_int(n, np.uint32, 5.0e8, 2147483648.0), 2147483648.5
+    s = reflibs[dtype].isosurface(data, iso, AWKWARD_R0, AWKWARD_D)
+    assert s.V.dtype == (np.float64 if dtype == "f64" else np.float32) and s.nV > 1000
+    want = mo.measure(s.V, s.T, AWKWARD_R0, AWKWARD_D, data.shape)
+    g = device_grid(data, AWKWARD_R0, AWKWARD_D)
+    V, T = to_device(s.V), to_device(s.T)
+    check_measures(dtype, g.measure(V, T), want)
+    check_measures(dtype + " (measure_iso)", g.measure_iso(iso), want)
+    lab, ncomp, unref, _ = mo.label_components(s.T, s.nV)
+    got, gc, gu = g.label_components(T, s.nV)
+    assert np.array_equal(got.cpu().numpy().view(np.uint32), lab) and (gc, gu) == (ncomp, unref)
+    tab, ab, wb = mo.component_table(s.V, s.T, lab, want.origin)
+    check_table(dtype, g.measure_components(V, T, got), tab, ab, wb, want)
+
+
+def test_inclined_grid(reflibs):
+    """V is Cartesian by the time it is measured: an inclined grid (triangular cell matrices) is a mesh like any other."""
+    data, r0, d = fx.cos_field(48)
+    mats = fx.cell_matrices(80.0, 75.0, 100.0)
+    lib = reflibs["f32"]
+    lib.set_triangular(True)
+    try:
+        s = lib.isosurface(data, 0.1, r0, d, inclined=mats)
+    finally:
+        lib.set_triangular(False)
+    assert s.nV > 5000
+    want = mo.measure(s.V, s.T, r0, d, data.shape)
+    g = device_grid(data, r0, d)
+    g.set_inclined(mats[0], mats[1], True)
+    check_measures("inclined", g.measure(to_device(s.V), to_device(s.T)), want)
+    check_measures("inclined (measure_iso)", g.measure_iso(0.1), want)
+
+
+# ---- 6: input validation ------------------------------------------------------------------------------------------------------
+
+def test_a_triangle_outside_v_is_counted_not_read(reflibs):
+    """One index set to nV: the kernels test it before they gather - ERUNTIME, the message names 1 triangle, the triangle is
+    left out of every sum, and the context works afterwards.  V is the first nV rows of a tensor with 16 spare rows behind
+    them, so that not even a wrong kernel could touch memory this test does not own."""
+    import torch
+    from mc33_c_library_amd.api import MC33Error, ERUNTIME, EINVAL, Measures
+    data, r0, d, iso, s = reference_mesh(reflibs, "blobs")
+    g = device_grid(data, r0, d)
+    room = torch.zeros((s.nV + 16, 3), dtype=torch.float32, device="cuda")
+    room[:s.nV] = to_device(s.V)
+    V = room[:s.nV]
+    badT = s.T.copy()
+    badT[777, 1] = s.nV
+    T, Tbad = to_device(s.T), to_device(badT)
+    with pytest.raises(MC33Error) as e:
+        g.measure(V, Tbad)
+    assert e.value.code == ERUNTIME and "1 triangle " in str(e.value), str(e.value)
+    with pytest.raises(MC33Error) as e:
+        g.label_components(Tbad, s.nV)
+    assert e.value.code == ERUNTIME and "1 triangle " in str(e.value), str(e.value)
+    labels = g.label_components(T, s.nV)[0]
+    with pytest.raises(MC33Error) as e:
+        g.measure_components(V, Tbad, labels)
+    assert e.value.code == ERUNTIME and "1 triangle " in str(e.value), str(e.value)
+    # what the failed call computed leaves the triangle out
+    m = Measures()
+    rc = g.lib.mc33hip_measure_surface(g.ctx, C.c_void_p(V.data_ptr()), s.nV, C.c_void_p(Tbad.data_ptr()), s.nT, None, C.byref(m))
+    without = mo.measure(s.V, badT, r0, d, data.shape)
+    assert rc == ERUNTIME
+    check_sum("area without the triangle", m.area, without.area, without.area_bound)
+    # the next call on the same context succeeds
+    check_measures("after the error", g.measure(V, T), mo.measure(s.V, s.T, r0, d, data.shape))
+    # nT == 0: zeros, no component, every vertex unreferenced
+    none = torch.zeros((0, 3), dtype=torch.int32, device="cuda")
+    z = g.measure(V, none)
+    assert (z.nV, z.nT, z.area, z.volume, z.moment) == (s.nV, 0, 0.0, 0.0, (0.0, 0.0, 0.0))
+    assert z.bbox_min == tuple(s.V.min(axis=0).astype(np.float64).tolist())
+    lab, nc, nu = g.label_components(none, s.nV)
+    assert (nc, nu) == (0, s.nV) and np.array_equal(lab.cpu().numpy(), np.arange(s.nV, dtype=np.int32))
+    assert g.measure_components(V, none, lab).shape[0] == 0
+    e0 = g.measure(V[:0], none)
+    assert e0.bbox_min == (np.inf,) * 3 and e0.bbox_max == (-np.inf,) * 3 and e0.area == 0.0
+    # EINVAL: null pointers where sizes are not zero, sizes above 2^32-1
+    L, ctx, n = g.lib, g.ctx, C.c_ulonglong()
+    pv, pt, pl = C.c_void_p(V.data_ptr()), C.c_void_p(T.data_ptr()), C.c_void_p(labels.data_ptr())
+    assert L.mc33hip_measure_surface(ctx, None, s.nV, pt, s.nT, None, C.byref(m)) == EINVAL
+    assert L.mc33hip_measure_surface(ctx, pv, s.nV, None, s.nT, None, C.byref(m)) == EINVAL
+    assert L.mc33hip_measure_surface(ctx, pv, s.nV, pt, s.nT, None, None) == EINVAL
+    assert L.mc33hip_measure_surface(ctx, pv, 1 << 32, pt, s.nT, None, C.byref(m)) == EINVAL
+    assert L.mc33hip_measure_surface(ctx, pv, s.nV, pt, 1 << 32, None, C.byref(m)) == EINVAL
+    assert L.mc33hip_label_components(ctx, pt, s.nT, s.nV, None, C.byref(n), C.byref(n)) == EINVAL
+    assert L.mc33hip_label_components(ctx, None, s.nT, s.nV, pl, C.byref(n), C.byref(n)) == EINVAL
+    assert L.mc33hip_label_components(ctx, pt, 1 << 32, s.nV, pl, C.byref(n), C.byref(n)) == EINVAL
+    assert L.mc33hip_measure_components(ctx, pv, s.nV, pt, s.nT, None, None, 0, C.byref(n)) == EINVAL
+    assert L.mc33hip_measure_components(ctx, pv, s.nV, pt, s.nT, pl, None, 5, C.byref(n)) == EINVAL
+    assert L.mc33hip_measure_components(ctx, pv, s.nV, pt, s.nT, pl, None, 0, None) == EINVAL
+
+
+# ---- 7: the C API -------------------------------------------------------------------------------------------------------------
+
+class CMeasure(C.Structure):
+    _fields_ = [("nV", C.c_uint), ("nT", C.c_uint), ("area", C.c_double), ("volume", C.c_double), ("moment", C.c_double * 3),
+                ("origin", C.c_double * 3), ("bbox_min", C.c_double * 3), ("bbox_max", C.c_double * 3), ("property_integral", C.c_double),
+                ("has_property", C.c_int)]
+
+
+class CComponent(C.Structure):
+    _fields_ = [("root", C.c_uint), ("nV", C.c_uint), ("nT", C.c_uint), ("area", C.c_double), ("volume", C.c_double)]
+
+
+def capi(dtype="f32", nneg=False):
+    lib = MC33Lib(product_path(dtype, nneg=nneg), dtype)
+    bind_measure_api(lib)
+    return lib
+
+
+def bind_measure_api(lib):
+    L = lib.lib
+    M = C.POINTER(lib.MC33)
+    L.MC33_measure_isosurface.restype = C.c_int
+    L.MC33_measure_isosurface.argtypes = [M, lib.real, C.POINTER(CMeasure)]
+    L.MC33_measure_isosurfaces.restype = C.c_uint
+    L.MC33_measure_isosurfaces.argtypes = [M, C.POINTER(lib.real), C.c_uint, C.POINTER(CMeasure)]
+    L.MC33_measure_components.restype = C.c_int
+    L.MC33_measure_components.argtypes = [M, lib.real, C.POINTER(CComponent), C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    L.MC33_set_property_grid.restype = C.c_int
+    L.MC33_set_property_grid.argtypes = [M, C.POINTER(lib.GRD)]
+
+
+class View:
+    """a CMeasure with tuples where check_measures wants them"""
+
+    def __init__(self, m):
+        self.nV, self.nT, self.area, self.volume = m.nV, m.nT, m.area, m.volume
+        self.moment, self.origin, self.bbox_min, self.bbox_max = tuple(m.moment), tuple(m.origin), tuple(m.bbox_min), tuple(m.bbox_max)
+        self.property_integral, self.has_property = m.property_integral, m.has_property
+
+
+@pytest.mark.parametrize("name", ["sphere", "blobs"])
+def test_c_api(reflibs, name):
+    data, r0, d, iso, s = reference_mesh(reflibs, name)
+    want = mo.measure(s.V, s.T, r0, d, data.shape)
+    lib = capi()
+    L = lib.lib
+    G, keep = lib.make_grid(data, r0, d)
+    M = L.create_MC33(G)
+    assert M
+    try:
+        m = CMeasure()
+        assert L.MC33_measure_isosurface(M, lib.real(iso), C.byref(m)) == 0
+        check_measures(name, View(m), want)
+        assert M.contents.iso == np.float32(iso) and M.contents.memoryfault == 0
+        # the component table: the size query, a table too small, the table
+        lab = mo.label_components(s.T, s.nV)[0]
+        tab, ab, wb = mo.component_table(s.V, s.T, lab, want.origin)
+        nc, nu = C.c_uint(), C.c_uint(99)
+        assert L.MC33_measure_components(M, lib.real(iso), None, 0, C.byref(nc), C.byref(nu)) == -2 and (nc.value, nu.value) == (tab.shape[0], 0)
+        rows = (CComponent * tab.shape[0])()
+        if tab.shape[0] > 1:
+            assert L.MC33_measure_components(M, lib.real(iso), rows, tab.shape[0] - 1, C.byref(nc), None) == -2 and nc.value == tab.shape[0]
+        assert L.MC33_measure_components(M, lib.real(iso), rows, tab.shape[0], C.byref(nc), C.byref(nu)) == 0
+        got = np.frombuffer(rows, dtype=np.dtype(CComponent)).copy()
+        check_table(name + " (C API)", got, tab, ab, wb, want)
+        # the object is still good for calculate_isosurface, and that surface is the reference's
+        S = L.calculate_isosurface(M, lib.real(iso))
+        assert S
+        mine = lib.copy_surface(S)
+        L.free_surface_memory(S)
+        assert np.array_equal(mine.V.view(np.uint32), s.V.view(np.uint32)) and np.array_equal(mine.T, s.T) and np.array_equal(mine.N.view(np.uint32), s.N.view(np.uint32))
+        assert L.MC33_measure_isosurface(M, lib.real(iso), None) == -1
+    finally:
+        L.free_MC33(M)
+        L.free_memory_grd(G)
+        del keep
+
+
+def test_c_api_several_isovalues_equal_single_calls(reflibs):
+    """11 isovalues - more than one group of 8 - through MC33_measure_isosurfaces equal 11 single calls bit for bit, and one of
+    them the oracle."""
+    data, r0, d = fx.cos_field(64)
+    isos = [-1.5 + 0.3 * k for k in range(11)]
+    lib = capi()
+    L = lib.lib
+    G, keep = lib.make_grid(data, r0, d)
+    M = L.create_MC33(G)
+    assert M
+    try:
+        many = (CMeasure * 11)()
+        assert L.MC33_measure_isosurfaces(M, (lib.real * 11)(*isos), 11, many) == 11
+        for k, iso in enumerate(isos):
+            one = CMeasure()
+            assert L.MC33_measure_isosurface(M, lib.real(iso), C.byref(one)) == 0
+            assert bytes(one) == bytes(many[k]) and one.nT > 0, "isovalue %g" % iso
+        s = reflibs["f32"].isosurface(data, float(np.float32(isos[5])), r0, d)
+        check_measures("isovalue %g" % isos[5], View(many[5]), mo.measure(s.V, s.T, r0, d, data.shape))
+        assert L.MC33_measure_isosurfaces(M, None, 3, many) == 0 and many[0].nT == 0
+    finally:
+        L.free_MC33(M)
+        L.free_memory_grd(G)
+        del keep
+
+
+def test_c_api_property_integral(reflibs):
+    data, r0, d, iso, s = reference_mesh(reflibs, "noise")
+    P = fx.noise_f32(0, 79, shape=data.shape) * np.float32(10.0)
+    want = mo.measure(s.V, s.T, r0, d, data.shape, P=po.sample_property(s.V, r0, d, P))
+    lib = capi()
+    L = lib.lib
+    G, keep = lib.make_grid(data, r0, d)
+    Pg, keep2 = lib.make_grid(P, r0, d)
+    M = L.create_MC33(G)
+    assert M
+    try:
+        m = CMeasure()
+        assert L.MC33_measure_isosurface(M, lib.real(iso), C.byref(m)) == 0 and m.has_property == 0 and m.property_integral == 0.0
+        assert L.MC33_set_property_grid(M, Pg) == 0  # (no colour map: none is needed)
+        assert L.MC33_measure_isosurface(M, lib.real(iso), C.byref(m)) == 0
+        check_measures("noise with a property grid", View(m), want)
+        assert L.MC33_set_property_grid(M, None) == 0
+        assert L.MC33_measure_isosurface(M, lib.real(iso), C.byref(m)) == 0 and m.has_property == 0
+    finally:
+        L.free_MC33(M)
+        L.free_memory_grd(G)
+        L.free_memory_grd(Pg)
+        del keep, keep2
+
+
+def test_c_api_nneg_flavour_has_the_opposite_sign():
+    """The oracle on the nneg reference's own T: the README sphere's volume is negative with the reference's winding, positive
+    with front and back exchanged."""
+    field, iso, _ = mo.FIXTURES["sphere"]
+    data, r0, d = field()
+    s = MC33Lib(ref_path("f32", nneg=True), "f32").isosurface(data, iso, r0, d)
+    want = mo.measure(s.V, s.T, r0, d, data.shape)
+    assert want.volume > 4.18
+    lib = capi(nneg=True)
+    L = lib.lib
+    G, keep = lib.make_grid(data, r0, d)
+    M = L.create_MC33(G)
+    assert M
+    try:
+        m = CMeasure()
+        assert L.MC33_measure_isosurface(M, lib.real(iso), C.byref(m)) == 0
+        check_measures("sphere, nneg", View(m), want)
+    finally:
+        L.free_MC33(M)
+        L.free_memory_grd(G)
+        del keep
+
+
+def test_c_api_refuses_an_object_on_several_slabs(launcher):
+    """MC33_HIP_DEVICES=0,0 in a fresh process, before the library is loaded: two slabs on one device, and all three functions
+    return -1 (tests/measure_slab_worker.py)."""
+    out = launcher.run([sys.executable, os.path.join(HERE, "measure_slab_worker.py")], env={"MC33_HIP_DEVICES": "0,0"}, timeout=300)
+    assert out["rc"] == 0 and "refused: -1 0 -1" in out["stdout"], out
+
+
+# ---- 8: past 2^24 vertices -----------------------------------------------------------------------------------------------------
+
+def test_more_than_2_pow_24_vertices(reflibs):
+    """cos x + cos y + cos z with the bench field's spacing over a five times wider domain, isovalue 2: some 15 000 closed
+    blobs, more than 2^24 vertices - vertex indices a float does not hold, byte offsets a 32-bit product does not.  Sums and
+    table in full; labels by an exact 64-bit checksum and 10^5 sampled rows."""
+    import torch
+    data, r0, d = fx.cos_field(1024, -80.0, 80.0)
+    s = reflibs["f32"].isosurface(data, 2.0, r0, d)
+    print("vertices %d, triangles %d" % (s.nV, s.nT))
+    assert s.nV > (1 << 24)
+    g = device_grid(data, r0, d)
+    shape = data.shape
+    del data
+    V, T = torch.from_numpy(s.V).cuda(), torch.from_numpy(s.T.view(np.int32)).cuda()
+    got = g.measure(V, T)
+    assert all_bits(g.measure(V, T)) == all_bits(got)
+    labels, gc, gu = g.label_components(T, s.nV)
+    table = g.measure_components(V, T, labels)
+    labels = labels.cpu().numpy().view(np.uint32)
+    del V, T
+    want = mo.measure(s.V, s.T, r0, d, shape)
+    check_measures("1024^3", got, want)
+    lab, ncomp, unref, rounds = mo.label_components(s.T, s.nV)
+    print("components %d, unreferenced %d, oracle rounds %d" % (ncomp, unref, rounds))
+    assert (gc, gu) == (ncomp, unref) and ncomp > 10000
+    idx = (np.arange(100000, dtype=np.int64) * 2654435761) % s.nV
+    weights = np.arange(1, s.nV + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+
+    def checksum(a):
+        return int((a.astype(np.uint64) * weights).sum(dtype=np.uint64))  # (modulo 2^64)
+    assert np.array_equal(labels[idx], lab[idx]) and checksum(labels) == checksum(lab)
+    tab, ab, wb = mo.component_table(s.V, s.T, lab, want.origin)
+    check_table("1024^3", table, tab, ab, wb, want)
