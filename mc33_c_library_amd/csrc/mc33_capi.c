@@ -122,6 +122,27 @@ static mc33_private *priv(MC33 *M) {
 	return (p && p->magic == MC33_MAGIC) ? p : 0;
 }
 
+/* Growable device arrays (the staging arrays, the measuring words): dev_room is the one place where one is made to hold at least n
+ * elements of elem_bytes - released and made anew with an eighth and 1024 elements to spare when it is missing or too small; what
+ * it held is not kept.  Success leaves *cap >= n; failure leaves (0, 0) and returns -1. */
+static void dev_release(mc33hip_ctx *ctx, void **ptr, unsigned long long *cap) {
+	if (*ptr) mc33hip_device_free(ctx, *ptr);
+	*ptr = 0; *cap = 0;
+}
+static int dev_room(mc33hip_ctx *ctx, void **ptr, unsigned long long *cap, unsigned long long n, size_t elem_bytes) {
+	if (*ptr && *cap >= n)
+		return 0;
+	dev_release(ctx, ptr, cap);
+	const unsigned long long c = n + n / 8 + 1024;
+	if (mc33hip_device_alloc(ctx, ptr, c * elem_bytes) != MC33HIP_OK) return -1;
+	*cap = c;
+	return 0;
+}
+static void staging_release(mc33hip_ctx *ctx, struct staging *g) {
+	unsigned long long capN = 0; /* (V and N share capV) */
+	dev_release(ctx, &g->dV, &g->capV); dev_release(ctx, &g->dN, &capN); dev_release(ctx, &g->dT, &g->capT); dev_release(ctx, &g->dC, &g->capC);
+}
+
 /* runs fn on every slab: the slabs of one device one after the other, the devices side by side - the device-level calls block
  * (count: until the counters are on the host; emit: the runtime's copies into pageable memory return when the data has arrived),
  * so every device gets a thread and its link is busy at the same time as the others'.  (Slabs that share a device - the
@@ -156,6 +177,15 @@ static void for_each_slab(mc33_private *p, void *(*fn)(void *)) {
 		if (started[g]) pthread_join(th[g], 0);
 		else slab_group_run(&grp[g]);
 	}
+}
+
+/* ... and the code of the first slab whose fn failed (MC33HIP_OK: none did) */
+static int run_slabs(mc33_private *p, void *(*fn)(void *)) {
+	for_each_slab(p, fn);
+	for (int k = 0; k != p->nslab; k++)
+		if (p->slab[k].rc != MC33HIP_OK)
+			return p->slab[k].rc;
+	return MC33HIP_OK;
 }
 
 static void *slab_create(void *arg) {
@@ -266,12 +296,10 @@ MC33 *create_MC33(_GRD *G) {
 		s->p_lo = s->z_begin >= s->ghost + 1u ? s->z_begin - s->ghost - 1u : 0u;
 		s->p_hi = s->z_end + 1u <= G->N[2] ? s->z_end + 1u : G->N[2];
 	}
-	for_each_slab(p, slab_create); /* the 1 / n of G->F of every device goes over its own link */
-	for (int k = 0; k != n; k++)
-		if (p->slab[k].rc != MC33HIP_OK) {
-			free_MC33(M);
-			return 0;
-		}
+	if (run_slabs(p, slab_create) != MC33HIP_OK) { /* the 1 / n of G->F of every device goes over its own link */
+		free_MC33(M);
+		return 0;
+	}
 	return M;
 }
 
@@ -283,14 +311,9 @@ void free_MC33(MC33 *M) {
 		mc33_slab *s = &p->slab[q];
 		if (!s->ctx)
 			continue;
-		for (int k = 0; k != 2; k++) {
-			if (s->set[k].dV) mc33hip_device_free(s->ctx, s->set[k].dV);
-			if (s->set[k].dN) mc33hip_device_free(s->ctx, s->set[k].dN);
-			if (s->set[k].dT) mc33hip_device_free(s->ctx, s->set[k].dT);
-			if (s->set[k].dC) mc33hip_device_free(s->ctx, s->set[k].dC);
-		}
-		if (q == 0 && p->dP) mc33hip_device_free(s->ctx, p->dP);
-		if (q == 0 && p->dL) mc33hip_device_free(s->ctx, p->dL);
+		for (int k = 0; k != 2; k++)
+			staging_release(s->ctx, &s->set[k]);
+		if (q == 0) { dev_release(s->ctx, &p->dP, &p->capP); dev_release(s->ctx, &p->dL, &p->capL); }
 		mc33hip_destroy(s->ctx);
 	}
 	p->magic = 0;
@@ -335,11 +358,7 @@ static int refresh_grid(mc33_private *p) {
 	if (!p->reupload && !p->grid_dirty)
 		return 0;
 	p->grid_dirty = 0;
-	for_each_slab(p, slab_upload);
-	for (int k = 0; k != p->nslab; k++)
-		if (p->slab[k].rc != MC33HIP_OK)
-			return p->slab[k].rc;
-	return MC33HIP_OK;
+	return run_slabs(p, slab_upload);
 }
 
 /* Extension (not in the reference, which reads G->F anew on every call, MC:1792, 1832-1868): tells the extractor that
@@ -380,13 +399,11 @@ int MC33_set_property_grid(MC33 *M, _GRD *P) {
 		return -1;
 #endif
 	p->prop = P;
-	for_each_slab(p, slab_property);
-	for (int k = 0; k != p->nslab; k++)
-		if (p->slab[k].rc != MC33HIP_OK) { /* a slab without its planes: no colours from any */
-			for (int q = 0; q != p->nslab; q++) (void)mc33hip_property_drop(p->slab[q].ctx);
-			p->prop = 0;
-			return -1;
-		}
+	if (run_slabs(p, slab_property) != MC33HIP_OK) { /* a slab without its planes: no colours from any */
+		for (int q = 0; q != p->nslab; q++) (void)mc33hip_property_drop(p->slab[q].ctx);
+		p->prop = 0;
+		return -1;
+	}
 	return 0;
 }
 
@@ -406,22 +423,10 @@ int MC33_set_color_map(MC33 *M, const int *palette, unsigned n, double lo, doubl
 	return 0;
 }
 
-/* room for the colours of nV vertices in staging set g */
-static int ensure_color_staging(mc33_slab *s, struct staging *g, unsigned long long nV) {
-	if (g->capC >= nV && g->dC)
-		return 0;
-	if (g->dC) mc33hip_device_free(s->ctx, g->dC);
-	g->dC = 0; g->capC = 0;
-	const unsigned long long cap = nV + nV / 8 + 1024;
-	if (mc33hip_device_alloc(s->ctx, &g->dC, cap * sizeof(int)) != MC33HIP_OK) return -1;
-	g->capC = cap;
-	return 0;
-}
-
 /* the colour kernel over the nV vertices in g->dV, behind whatever wrote them on the context's stream (enqueues only) */
 static int enqueue_colors(mc33_slab *s, struct staging *g, unsigned long long nV) {
 	const mc33_private *p = s->owner;
-	if (ensure_color_staging(s, g, nV)) return MC33HIP_ENOMEM;
+	if (dev_room(s->ctx, &g->dC, &g->capC, nV, sizeof(int))) return MC33HIP_ENOMEM;
 	return mc33hip_color_vertices(s->ctx, g->dV, nV, p->map, p->map_n, p->map_lo, p->map_hi, p->nan_color, (int *)g->dC);
 }
 
@@ -443,10 +448,9 @@ static int count_slabs(mc33_private *p, MC33_real iso, mc33hip_counts *tot) {
 	if (rc != MC33HIP_OK)
 		return rc;
 	for (int k = 0; k != p->nslab; k++) p->slab[k].iso = iso;
-	for_each_slab(p, slab_count);
+	if ((rc = run_slabs(p, slab_count)) != MC33HIP_OK)
+		return rc;
 	for (int k = 0; k != p->nslab; k++) {
-		if (p->slab[k].rc != MC33HIP_OK)
-			return p->slab[k].rc;
 		tot->nV += p->slab[k].cnt.nV; tot->nT += p->slab[k].cnt.nT; tot->active_cells += p->slab[k].cnt.active_cells;
 	}
 	return (tot->nV > 0xFFFFFFFFull || tot->nT > 0xFFFFFFFFull) ? MC33HIP_EOVERFLOW : MC33HIP_OK;
@@ -467,24 +471,16 @@ unsigned long long size_of_isosurface(MC33 *M, MC33_real iso, unsigned int *nV, 
 	return cnt.nV * (6 * sizeof(MC33_real) + sizeof(int)) + cnt.nT * (3 * sizeof(int)) + sizeof(surface);
 }
 
-static int ensure_staging(mc33_slab *s, struct staging *g, unsigned long long nV, unsigned long long nT) {
+/* room for nV vertices and nT triangles in staging set g.  V and N grow together, under the one capacity capV: both go before
+ * either is made anew, and capV stands only when both are there */
+static int staging_room(mc33_slab *s, struct staging *g, unsigned long long nV, unsigned long long nT) {
 	if (g->capV < nV) {
-		if (g->dV) mc33hip_device_free(s->ctx, g->dV);
-		if (g->dN) mc33hip_device_free(s->ctx, g->dN);
-		g->dV = g->dN = 0; g->capV = 0;
-		unsigned long long cap = nV + nV / 8 + 1024;
-		if (mc33hip_device_alloc(s->ctx, &g->dV, cap * 3 * sizeof(MC33_real)) != MC33HIP_OK) return -1;
-		if (mc33hip_device_alloc(s->ctx, &g->dN, cap * 12) != MC33HIP_OK) return -1;
-		g->capV = cap;
+		unsigned long long capN = 0;
+		dev_release(s->ctx, &g->dV, &g->capV); dev_release(s->ctx, &g->dN, &capN);
+		if (dev_room(s->ctx, &g->dV, &g->capV, nV, 3 * sizeof(MC33_real))) return -1;
+		if (dev_room(s->ctx, &g->dN, &capN, nV, 12)) { g->capV = 0; return -1; }
 	}
-	if (g->capT < nT) {
-		if (g->dT) mc33hip_device_free(s->ctx, g->dT);
-		g->dT = 0; g->capT = 0;
-		unsigned long long cap = nT + nT / 8 + 1024;
-		if (mc33hip_device_alloc(s->ctx, &g->dT, cap * 12) != MC33HIP_OK) return -1;
-		g->capT = cap;
-	}
-	return 0;
+	return g->capT < nT ? dev_room(s->ctx, &g->dT, &g->capT, nT, 12) : 0;
 }
 
 /* count, grow, emit (one slab: the whole grid): V, N, T of the surface of `iso` into staging set g (device memory), its sizes
@@ -501,7 +497,7 @@ static int extract_geometry(mc33_private *p, struct staging *g, MC33_real iso, m
 	 * anyway, the buffers grow and only the emit pass is repeated */
 	rc = mc33hip_extract(s->ctx, iso, &r, g->dV, g->dN, g->dT, g->capV, g->capT, cnt);
 	if (rc == MC33HIP_ECAPACITY) {
-		rc = ensure_staging(s, g, cnt->nV, cnt->nT) ? MC33HIP_ENOMEM : mc33hip_emit(s->ctx, g->dV, g->dN, g->dT, g->capV, g->capT);
+		rc = staging_room(s, g, cnt->nV, cnt->nT) ? MC33HIP_ENOMEM : mc33hip_emit(s->ctx, g->dV, g->dN, g->dT, g->capV, g->capT);
 		/* mc33hip_emit only enqueues: the set must be complete before anybody reads it - the helper thread of
 		 * calculate_isosurfaces copies on a stream of its own, which is not ordered after this one */
 		if (rc == MC33HIP_OK)
@@ -785,7 +781,7 @@ static void *slab_emit(void *arg) {
 	s->rc = MC33HIP_OK;
 	if (!s->cnt.nV && !s->cnt.nT)
 		return 0;
-	if (ensure_staging(s, g, s->cnt.nV, s->cnt.nT)) { s->rc = MC33HIP_ENOMEM; return 0; }
+	if (staging_room(s, g, s->cnt.nV, s->cnt.nT)) { s->rc = MC33HIP_ENOMEM; return 0; }
 	if ((s->rc = mc33hip_set_id_base(s->ctx, (unsigned int)s->vbase)) != MC33HIP_OK) return 0;
 	s->rc = mc33hip_emit_download(s->ctx, g->dV, g->dN, g->dT, g->capV, g->capT, S->V + s->vbase, S->N + s->vbase, S->T + s->tbase);
 	if (s->rc == MC33HIP_OK && coloured(s->owner) && s->cnt.nV) { /* the colour kernel behind the vertex pass, its array behind the other copies */
@@ -826,7 +822,6 @@ surface *calculate_isosurface(MC33 *M, MC33_real iso) {
 	surface *S = crc == MC33HIP_OK ? surface_alloc((size_t)tot.nV, (size_t)tot.nT, iso) : 0;
 	if (trace) t[2] = now_ms();
 	if (S && S->nV) {
-		int ok = 1;
 		unsigned long long vb = 0, tb = 0;
 		for (int k = 0; k != p->nslab; k++) {
 			mc33_slab *s = &p->slab[k];
@@ -839,13 +834,10 @@ surface *calculate_isosurface(MC33 *M, MC33_real iso) {
 		const int helper = !col && S->nV >= 65536u && pthread_create(&ct, 0, fill_color_thread, S) == 0; /* 16 MB at 1024^3: 0.8 ms beside 3.4 ms of copies */
 		populate_fresh(); /* (blocks that did not come from the cache: their pages, before the copies need them) */
 		if (trace) t[3] = now_ms();
-		for_each_slab(p, slab_emit);
+		const int ok = run_slabs(p, slab_emit) == MC33HIP_OK;
 		if (trace) t[4] = now_ms();
 		if (helper) pthread_join(ct, 0);
 		else if (!col) fill_color(S);
-		for (int k = 0; k != p->nslab; k++)
-			if (p->slab[k].rc != MC33HIP_OK)
-				ok = 0;
 		if (trace) {
 			t[5] = now_ms();
 			fprintf(stderr, "[mc33 capi] count %.3f  blocks %.3f  helper + fresh pages %.3f  emit + copies %.3f  colours joined %.3f  total %.3f ms\n", t[1] - t[0], t[2] - t[1],
@@ -868,6 +860,16 @@ surface *calculate_isosurface(MC33 *M, MC33_real iso) {
 }
 
 /* --- extension: several isovalues of the resident grid ---------------------------------------------------- */
+/* the sweeps of the next m (up to 8) isovalues in one or two passes over the grid */
+static void sweep_ahead(mc33_private *p, const MC33_real *iso, unsigned m) {
+	double many[8];
+	mc33hip_range r;
+	r.z_begin = 0; r.z_end = p->pub.nz; r.ghost_below = 0; r.id_base = 0;
+	for (unsigned q = 0; q != m; q++) many[q] = iso[q];
+	if (!p->reupload) /* (the re-upload of every call would drop the sweeps made ahead) */
+		(void)mc33hip_sweep_many(p->slab[0].ctx, many, (int)m, &r); /* (on failure the single calls sweep for themselves) */
+}
+
 struct download_job {
 	mc33_private *p;
 	const struct staging *g;
@@ -906,15 +908,8 @@ unsigned int calculate_isosurfaces(MC33 *M, const MC33_real *iso, unsigned int n
 	int running = 0;
 	unsigned int running_k = 0;
 	for (unsigned int k = 0; k != n; k++) {
-		if (k % 8 == 0 && n - k > 1) { /* the sweeps of the next (up to) 8 isovalues in one or two passes over the grid */
-			double many[8];
-			const unsigned int m = n - k < 8 ? n - k : 8;
-			mc33hip_range r;
-			r.z_begin = 0; r.z_end = M->nz; r.ghost_below = 0; r.id_base = 0;
-			for (unsigned int q = 0; q != m; q++) many[q] = iso[k + q];
-			if (!p->reupload) /* (the re-upload of every call would drop the sweeps made ahead) */
-				(void)mc33hip_sweep_many(p->slab[0].ctx, many, (int)m, &r); /* (on failure the single calls sweep for themselves) */
-		}
+		if (k % 8 == 0 && n - k > 1)
+			sweep_ahead(p, iso + k, n - k < 8 ? n - k : 8);
 		/* surface k is computed into set k&1 while the helper thread copies surface k-1 out of the other set */
 		struct staging *g = &p->slab[0].set[k & 1];
 		mc33hip_counts cnt;
@@ -954,17 +949,6 @@ static mc33_private *measurable(MC33 *M) {
 	return p;
 }
 
-static int ensure_words(mc33_slab *s, void **d, unsigned long long *cap, unsigned long long n) { /* n 4-byte words of device memory */
-	if (*d && *cap >= n)
-		return 0;
-	if (*d) mc33hip_device_free(s->ctx, *d);
-	*d = 0; *cap = 0;
-	const unsigned long long c = n + n / 8 + 1024;
-	if (mc33hip_device_alloc(s->ctx, d, c * 4) != MC33HIP_OK) return -1;
-	*cap = c;
-	return 0;
-}
-
 static int measure_one(mc33_private *p, MC33_real iso, mc33_measure *out) {
 	mc33_slab *s = &p->slab[0];
 	struct staging *g = &s->set[0];
@@ -976,7 +960,7 @@ static int measure_one(mc33_private *p, MC33_real iso, mc33_measure *out) {
 		return -1;
 	const float *dP = 0;
 	if (p->prop) { /* the property at the vertices first, into a float array of its own */
-		if (ensure_words(s, &p->dP, &p->capP, cnt.nV) || mc33hip_sample_property(s->ctx, g->dV, cnt.nV, (float *)p->dP) != MC33HIP_OK)
+		if (dev_room(s->ctx, &p->dP, &p->capP, cnt.nV, sizeof(float)) || mc33hip_sample_property(s->ctx, g->dV, cnt.nV, (float *)p->dP) != MC33HIP_OK)
 			return -1;
 		dP = (const float *)p->dP;
 	}
@@ -1011,15 +995,8 @@ unsigned MC33_measure_isosurfaces(MC33 *M, const MC33_real *iso, unsigned count,
 	if (refresh_grid(p) != MC33HIP_OK)
 		return 0;
 	for (unsigned k = 0; k != count; k++) {
-		if (k % 8 == 0 && count - k > 1) { /* the sweeps of the next (up to) 8 isovalues in one or two passes over the grid */
-			double many[8];
-			const unsigned m = count - k < 8 ? count - k : 8;
-			mc33hip_range r;
-			r.z_begin = 0; r.z_end = M->nz; r.ghost_below = 0; r.id_base = 0;
-			for (unsigned q = 0; q != m; q++) many[q] = iso[k + q];
-			if (!p->reupload)
-				(void)mc33hip_sweep_many(p->slab[0].ctx, many, (int)m, &r); /* (on failure the single calls sweep for themselves) */
-		}
+		if (k % 8 == 0 && count - k > 1)
+			sweep_ahead(p, iso + k, count - k < 8 ? count - k : 8);
 		if (measure_one(p, iso[k], &out[k]) == 0)
 			done++;
 		else
@@ -1038,7 +1015,7 @@ int MC33_measure_components(MC33 *M, MC33_real iso, mc33_component *table, unsig
 	struct staging *g = &s->set[0];
 	mc33hip_counts cnt;
 	M->iso = iso;
-	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK || ensure_words(s, &p->dL, &p->capL, cnt.nV))
+	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK || dev_room(s->ctx, &p->dL, &p->capL, cnt.nV, sizeof(unsigned)))
 		return -1;
 	unsigned long long nc = 0, nu = 0;
 	if (mc33hip_label_components(s->ctx, g->dT, cnt.nT, cnt.nV, (unsigned *)p->dL, &nc, &nu) != MC33HIP_OK)

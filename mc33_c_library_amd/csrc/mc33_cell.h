@@ -1257,49 +1257,6 @@ MC33_HD void emit_cell(const EmitCtx<T> &c, uint32_t entry_index, const VRef &v,
 	} while (word >> 12);
 }
 
-// --- fast emit ---------------------------------------------------------------------------------------
-// vertex of one of the three owned edges (5: z-edge, 6: y-edge, 10: x-edge, all through corner 6) of an
-// interior cell; same arithmetic as vertex_on_edge, written out so that every index is static
-template <typename T, int E>
-MC33_HD void fast_owned_vertex(const EmitCtx<T> &c, uint32_t x, uint32_t y, uint32_t z, const real_t *v, uint32_t id) {
-	const Params &P = c.P;
-	const GridView<T> &G = c.G;
-	real_t r[6];
-	const real_t v6 = v[6];
-	if (E == 5) {
-		const real_t va = v[5], t = va / (va - v6);
-		r[0] = (real_t)(x + 1); r[1] = (real_t)(y + 1); r[2] = (real_t)z + t;
-		r[3] = (x + 1 < P.nx) ? 0.5f * (sample_diff(G.at(x, y + 1, z), G.at(x + 2, y + 1, z)) * (1 - t) +
-		                               sample_diff(G.at(x, y + 1, z + 1), G.at(x + 2, y + 1, z + 1)) * t)
-		                      : (v[5] - v[1]) * (1 - t) + (v6 - v[2]) * t;
-		r[4] = (y + 1 < P.ny) ? 0.5f * (sample_diff(G.at(x + 1, y, z), G.at(x + 1, y + 2, z)) * (1 - t) +
-		                               sample_diff(G.at(x + 1, y, z + 1), G.at(x + 1, y + 2, z + 1)) * t)
-		                      : (v[5] - v[4]) * (1 - t) + (v6 - v[7]) * t;
-		r[5] = v6 - va;
-	} else if (E == 6) {
-		const real_t va = v[7], t = va / (va - v6);
-		r[0] = (real_t)(x + 1); r[1] = (real_t)y + t; r[2] = (real_t)(z + 1);
-		r[3] = (x + 1 < P.nx) ? 0.5f * (sample_diff(G.at(x, y, z + 1), G.at(x + 2, y, z + 1)) * (1 - t) +
-		                               sample_diff(G.at(x, y + 1, z + 1), G.at(x + 2, y + 1, z + 1)) * t)
-		                      : (v[7] - v[3]) * (1 - t) + (v6 - v[2]) * t;
-		r[4] = v6 - va;
-		r[5] = (z + 1 < P.nz) ? 0.5f * (sample_diff(G.at(x + 1, y, z), G.at(x + 1, y, z + 2)) * (1 - t) +
-		                               sample_diff(G.at(x + 1, y + 1, z), G.at(x + 1, y + 1, z + 2)) * t)
-		                      : (v[7] - v[4]) * (1 - t) + (v6 - v[5]) * t;
-	} else {
-		const real_t va = v[2], t = va / (va - v6);
-		r[0] = (real_t)x + t; r[1] = (real_t)(y + 1); r[2] = (real_t)(z + 1);
-		r[3] = v6 - va;
-		r[4] = (y + 1 < P.ny) ? 0.5f * (sample_diff(G.at(x, y, z + 1), G.at(x, y + 2, z + 1)) * (1 - t) +
-		                               sample_diff(G.at(x + 1, y, z + 1), G.at(x + 1, y + 2, z + 1)) * t)
-		                      : (v[2] - v[3]) * (1 - t) + (v6 - v[7]) * t;
-		r[5] = (z + 1 < P.nz) ? 0.5f * (sample_diff(G.at(x, y + 1, z), G.at(x, y + 1, z + 2)) * (1 - t) +
-		                               sample_diff(G.at(x + 1, y + 1, z), G.at(x + 1, y + 1, z + 2)) * t)
-		                      : (v[2] - v[1]) * (1 - t) + (v6 - v[5]) * t;
-	}
-	store_vertex(P, r, c.V, c.N, id - c.v_skip);
-}
-
 // ---- fast emit, split in two passes so that each has a short dependency chain and few registers -------
 // The samples the (up to three) owned vertices of a FAST record and the centre vertex of a TESTED one are made from:
 // short runs along x - the 2x2 rows of the cell (x..x+2) and the four rows one step outside it (y+2 on both planes,

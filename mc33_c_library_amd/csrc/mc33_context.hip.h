@@ -18,6 +18,38 @@ static void set_err(const char *fmt, ...) {
 		}                                                                                     \
 	} while (0)
 
+// Growable device arrays: plain pointer and capacity fields (the context is calloc'ed and free'd); dev_release is how one is
+// released, dev_room / dev_room_all how it is made to hold at least n elements.  The caller adds its slack to n and names the
+// bytes; a caller with something to do when an array is new looks at the capacity first.  What an array held is not kept.
+//   success: *cap >= n, every array there;   failure: every array nullptr, *cap = 0, set_err called, the code HIP_TRY returns.
+// dev_room_all is all or nothing for arrays that share one capacity: they are released together and allocated in the order
+// given (where a buffer lands moves the emit kernels, DESIGN.md 7.1: the order of the allocations is part of the behaviour).
+struct DevArray { void **p; uint64_t bytes; };
+template <typename E>
+static DevArray dev_array(E **p, uint64_t n, uint64_t elem_bytes = sizeof(E)) { return DevArray{(void **)p, n * elem_bytes}; }
+template <typename E>
+static void dev_release(E **p) { (void)hipFree(*p); *p = nullptr; }
+static int dev_room_all(const char *what, uint64_t *cap, uint64_t n, std::initializer_list<DevArray> arrays) {
+	bool there = *cap >= n;
+	for (const DevArray &a : arrays) there = there && *a.p;
+	if (there) return 0;
+	for (const DevArray &a : arrays) dev_release(a.p);
+	*cap = 0;
+	for (const DevArray &a : arrays) {
+		const hipError_t e = hipMalloc(a.p, a.bytes);
+		if (e == hipSuccess) continue;
+		for (const DevArray &b : arrays) dev_release(b.p);
+		set_err("%s (%llu elements) failed: %s", what, (unsigned long long)n, hipGetErrorString(e));
+		return e == hipErrorOutOfMemory ? MC33HIP_ENOMEM : MC33HIP_ERUNTIME;
+	}
+	*cap = n;
+	return 0;
+}
+template <typename E>
+static int dev_room(const char *what, E **p, uint64_t *cap, uint64_t n, uint64_t elem_bytes = sizeof(E)) {
+	return dev_room_all(what, cap, n, {dev_array(p, n, elem_bytes)});
+}
+
 // Per-isovalue output of the sweep (SweepLane) and its bookkeeping on the host
 constexpr int MC33_LANES = 8;
 constexpr int MC33_MANY_PASSES = 4;  // passes of one mc33hip_sweep_many call: 8 isovalues = 4 + 4, 7 = 4 + 2 + 1
@@ -229,9 +261,9 @@ static size_t own_pitch(size_t npx) {
 }
 
 static void free_set(TailSet &w) {  // (everything of the set; it can be filled again by ensure_set)
-	(void)hipFree(w.seg_cnt); (void)hipFree(w.seg_dir); (void)hipFree(w.seg_base); (void)hipFree(w.bsV);
-	(void)hipFree(w.entries_a); (void)hipFree(w.entries_b); (void)hipFree(w.entries_c); (void)hipFree(w.entry_seg); (void)hipFree(w.slow_list); (void)hipFree(w.dirty_list);
-	(void)hipFree(w.batches); (void)hipFree(w.list_cnt); (void)hipFree(w.slot_base); (void)hipFree(w.live_list); (void)hipFree(w.d_ctr);
+	dev_release(&w.seg_cnt); dev_release(&w.seg_dir); dev_release(&w.seg_base); dev_release(&w.bsV);
+	dev_release(&w.entries_a); dev_release(&w.entries_b); dev_release(&w.entries_c); dev_release(&w.entry_seg); dev_release(&w.slow_list); dev_release(&w.dirty_list);
+	dev_release(&w.batches); dev_release(&w.list_cnt); dev_release(&w.slot_base); dev_release(&w.live_list); dev_release(&w.d_ctr);
 	if (w.h_ctr) (void)hipHostFree(w.h_ctr);
 	w = TailSet{};
 }
@@ -312,20 +344,20 @@ extern "C" void mc33hip_destroy(mc33hip_ctx *c) {
 	(void)hipSetDevice(c->device);
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	else (void)hipDeviceSynchronize();
-	if (c->owns_grid) (void)hipFree(c->d_grid);
+	if (c->owns_grid) dev_release(&c->d_grid);
 	prop_destroy(c);
 	meas_destroy(c);
-	(void)hipFree(c->d_lut); (void)hipFree(c->d_rules); (void)hipFree(c->d_rule_index); (void)hipFree(c->d_fast);
-	(void)hipFree(c->d_fast_b); (void)hipFree(c->d_pat); (void)hipFree(c->d_pat_order);
+	dev_release(&c->d_lut); dev_release(&c->d_rules); dev_release(&c->d_rule_index); dev_release(&c->d_fast);
+	dev_release(&c->d_fast_b); dev_release(&c->d_pat); dev_release(&c->d_pat_order);
 	for (int k = 0; k < MC33_LANES; k++) free_set(c->ts[k]);
 	for (int k = 0; k < MC33_LANES; k++) {
 		IsoLane &L = c->lanes[k];
-		(void)hipFree(L.slice_hdr); (void)hipFree(L.slice_bits); (void)hipFree(L.slice_compact); (void)hipFree(L.plane_fmt); (void)hipFree(L.slot_part); (void)hipFree(L.edge_bits); (void)hipFree(L.edge_hdr);
+		dev_release(&L.slice_hdr); dev_release(&L.slice_bits); dev_release(&L.slice_compact); dev_release(&L.plane_fmt); dev_release(&L.slot_part); dev_release(&L.edge_bits); dev_release(&L.edge_hdr);
 	}
-	(void)hipFree(c->d_tiles);
-	(void)hipFree(c->d_bounds);
-	(void)hipFree(c->d_bases);
-	(void)hipFree(c->trace); (void)hipFree(c->trace_cells);
+	dev_release(&c->d_tiles);
+	dev_release(&c->d_bounds);
+	dev_release(&c->d_bases);
+	dev_release(&c->trace); dev_release(&c->trace_cells);
 	if (c->aux) (void)hipStreamSynchronize(c->aux);
 	if (c->aux2) (void)hipStreamSynchronize(c->aux2);
 	if (c->copy) (void)hipStreamSynchronize(c->copy);
@@ -489,7 +521,7 @@ extern "C" int mc33hip_adopt_device(mc33hip_ctx *c, const void *dptr, size_t pit
 	if (!c || !dptr || pitch < c->desc.npx || slice < pitch * c->desc.npy) return MC33HIP_EINVAL;
 	int rc = use_device(c);
 	if (rc) return rc;
-	if (c->owns_grid) (void)hipFree(c->d_grid);
+	if (c->owns_grid) dev_release(&c->d_grid);
 	c->d_grid = (sample_t *)dptr;
 	c->owns_grid = false;
 	c->pitch = pitch;

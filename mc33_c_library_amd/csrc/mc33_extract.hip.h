@@ -53,28 +53,14 @@ static uint32_t env_u32(const char *name, uint32_t dflt) {
 	return v > 0 ? (uint32_t)v : dflt;
 }
 
+// the record arrays of a set, all or nothing: a set with some of its arrays would pass for a complete one (ensure_set looks at entries_a)
 static int alloc_entries(TailSet &w, uint64_t cap) {
-	(void)hipFree(w.entries_a); (void)hipFree(w.entries_b); (void)hipFree(w.entries_c); (void)hipFree(w.entry_seg); (void)hipFree(w.slow_list); (void)hipFree(w.dirty_list);
-	w.entries_a = nullptr; w.entries_b = nullptr; w.entries_c = nullptr; w.entry_seg = nullptr; w.slow_list = nullptr; w.dirty_list = nullptr;
-	w.entry_cap = 0;
 	if (cap > 0xFFFFFF00ull) cap = 0xFFFFFF00ull;
-	const hipError_t e = [&]() -> hipError_t {
-		hipError_t r;
-		if ((r = hipMalloc(&w.entries_a, (cap + 2) * sizeof(EntryA))) != hipSuccess) return r;  // (+ 2: the triangle pass reads records in pairs)
-		if ((r = hipMalloc(&w.entries_b, cap * sizeof(EntryB))) != hipSuccess) return r;        // (touched for tested and slow records only)
-		if ((r = hipMalloc(&w.entries_c, cap * sizeof(EntryC))) != hipSuccess) return r;        // (... for slow records only)
-		if ((r = hipMalloc(&w.entry_seg, cap * 4)) != hipSuccess) return r;
-		if ((r = hipMalloc(&w.slow_list, cap * 4)) != hipSuccess) return r;
-		return hipMalloc(&w.dirty_list, cap * 4);
-	}();
-	if (e != hipSuccess) {  // all or nothing: a set with some of its arrays would pass for a complete one (ensure_set looks at entries_a)
-		(void)hipFree(w.entries_a); (void)hipFree(w.entries_b); (void)hipFree(w.entries_c); (void)hipFree(w.entry_seg); (void)hipFree(w.slow_list); (void)hipFree(w.dirty_list);
-		w.entries_a = nullptr; w.entries_b = nullptr; w.entries_c = nullptr; w.entry_seg = nullptr; w.slow_list = nullptr; w.dirty_list = nullptr;
-		set_err("work-record buffers (%llu records) failed: %s", (unsigned long long)cap, hipGetErrorString(e));
-		return e == hipErrorOutOfMemory ? MC33HIP_ENOMEM : MC33HIP_ERUNTIME;
-	}
-	w.entry_cap = cap;
-	return 0;
+	return dev_room_all("work-record buffers", &w.entry_cap, cap,
+	                    {dev_array(&w.entries_a, cap + 2),  // (+ 2: the triangle pass reads records in pairs)
+	                     dev_array(&w.entries_b, cap),      // (touched for tested and slow records only)
+	                     dev_array(&w.entries_c, cap),      // (... for slow records only)
+	                     dev_array(&w.entry_seg, cap), dev_array(&w.slow_list, cap), dev_array(&w.dirty_list, cap)});
 }
 
 // the buffers of set w for the current range (c->nsegs, c->P, c->range); hint: work records to make room for at first (0: a guess from the range)
@@ -86,23 +72,17 @@ static int ensure_set(mc33hip_ctx *c, TailSet &w, uint64_t hint = 0) {
 		HIP_TRY(hipHostMalloc(&w.h_ctr, sizeof(Counters), hipHostMallocDefault));
 	}
 	if (w.seg_cap < c->nsegs) {
-		(void)hipFree(w.seg_cnt); (void)hipFree(w.seg_dir); (void)hipFree(w.seg_base);
-		w.seg_cnt = nullptr; w.seg_dir = nullptr; w.seg_base = nullptr;
-		w.seg_cap = 0;
-		HIP_TRY(hipMalloc(&w.seg_cnt, c->nsegs * 4));
-		w.tail_serial = 0;  // (the first tail clears the new array)
-		HIP_TRY(hipMalloc(&w.seg_dir, c->nsegs * sizeof(SegDir)));
-		HIP_TRY(hipMalloc(&w.seg_base, (c->nsegs + 1) * sizeof(SegBase)));  // (+ 1: the triangle pass reads bases in pairs)
-		w.seg_cap = c->nsegs;
+		if (int rc = dev_room_all("row-segment arrays", &w.seg_cap, c->nsegs,
+		                          {dev_array(&w.seg_cnt, c->nsegs), dev_array(&w.seg_dir, c->nsegs),
+		                           dev_array(&w.seg_base, c->nsegs + 1)}))  // (+ 1: the triangle pass reads bases in pairs)
+			return rc;
+		w.tail_serial = 0;  // (the first tail clears the new seg_cnt)
 	}
 	const uint64_t nb = (c->nsegs + SCAN_CHUNK - 1) / SCAN_CHUNK;
 	if (w.bs_cap < nb) {
-		(void)hipFree(w.bsV);
-		w.bsV = w.bsT = nullptr;
-		w.bs_cap = 0;
-		HIP_TRY(hipMalloc(&w.bsV, 2 * (nb + scan_groups(nb)) * 8));  // chunk sums V, T; then group sums V, T
+		w.bsT = nullptr;
+		if (int rc = dev_room_all("scan sums", &w.bs_cap, nb, {dev_array(&w.bsV, 2 * (nb + scan_groups(nb)))})) return rc;  // chunk sums V, T; then group sums V, T
 		w.bsT = w.bsV + nb;
-		w.bs_cap = nb;
 	}
 	if (!w.entries_a || !w.entry_cap) {
 		// first guess: one cell in 32 is cut (BASELINE fields: 0.4-6 % of the cells); grown on demand
@@ -203,19 +183,14 @@ static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze) {
 	// A sweep made ahead by mc33hip_sweep_many may still be reading the old plan: the copies below go through the null stream,
 	// which a non-blocking stream (any torch.cuda.Stream) is not ordered with
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (c->tiles_cap < tiles.size()) {
-		(void)hipFree(c->d_tiles);
-		c->d_tiles = nullptr; c->tiles_cap = 0;
-		HIP_TRY(hipMalloc(&c->d_tiles, tiles.size() * sizeof(SweepTile)));
-		c->tiles_cap = tiles.size();
-	}
+	if (c->tiles_cap < tiles.size())
+		if (int rc = dev_room("sweep tiles", &c->d_tiles, &c->tiles_cap, tiles.size())) return rc;
 	HIP_TRY(hipMemcpy(c->d_tiles, tiles.data(), tiles.size() * sizeof(SweepTile), hipMemcpyHostToDevice));
 	c->ntiles = tiles.size();
-	(void)hipFree(c->d_bounds);
-	c->d_bounds = nullptr;
-	c->nbounds = bounds.size();
-	if (c->nbounds) {
-		HIP_TRY(hipMalloc(&c->d_bounds, bounds.size() * sizeof(TileBoundary)));
+	dev_release(&c->d_bounds);  // (made to measure for every plan: nbounds is its capacity)
+	c->nbounds = 0;
+	if (!bounds.empty()) {
+		if (int rc = dev_room("tile boundaries", &c->d_bounds, &c->nbounds, bounds.size())) return rc;
 		HIP_TRY(hipMemcpy(c->d_bounds, bounds.data(), bounds.size() * sizeof(TileBoundary), hipMemcpyHostToDevice));
 	}
 	c->tiles_zs = zs; c->tiles_ze = ze; c->tiles_depth = depth;
@@ -246,27 +221,23 @@ static int slot_geometry(mc33hip_ctx *c, SlotGeom &g) {
 // buffers of one isovalue lane for the current range and tile plan; a new extraction number (epoch)
 static int begin_lane(mc33hip_ctx *c, IsoLane &L, const SlotGeom &g, hipStream_t st) {
 	if (L.slice_cap < g.nslots) {
-		(void)hipFree(L.slice_hdr); (void)hipFree(L.slice_bits); (void)hipFree(L.slice_compact); (void)hipFree(L.plane_fmt); (void)hipFree(L.slot_part);
-		L.slice_hdr = nullptr; L.slice_bits = nullptr; L.slice_compact = nullptr; L.plane_fmt = nullptr; L.slot_part = nullptr; L.slice_cap = 0;
-		HIP_TRY(hipMalloc(&L.slice_hdr, g.nslots * sizeof(SliceHeader)));
-		HIP_TRY(hipMalloc(&L.slice_bits, g.nslots * 2048));  // (slots of planes: SlotDims)
-		HIP_TRY(hipMalloc(&L.slice_compact, g.nslots * 256));
-		HIP_TRY(hipMalloc(&L.plane_fmt, g.nslots));
 		const uint64_t part_bytes = ((g.nslots + SLOT_CHUNK - 1) / SLOT_CHUNK) * 8;
-		HIP_TRY(hipMalloc(&L.slot_part, 2 * part_bytes));  // two halves, used by alternate extractions
+		if (int rc = dev_room_all("slice buffers", &L.slice_cap, g.nslots,
+		                          {dev_array(&L.slice_hdr, g.nslots), dev_array(&L.slice_bits, g.nslots, 2048),  // (slots of planes: SlotDims)
+		                           dev_array(&L.slice_compact, g.nslots, 256), dev_array(&L.plane_fmt, g.nslots),
+		                           dev_array(&L.slot_part, 2, part_bytes)}))  // two halves, used by alternate extractions
+			return rc;
+		L.slice_cap = 0;  // (not this lane's until they are clean: a failure below has them made again)
 		HIP_TRY(hipMemsetAsync(L.slice_hdr, 0, g.nslots * sizeof(SliceHeader), st));
 		HIP_TRY(hipMemsetAsync(L.slot_part, 0, 2 * part_bytes, st));
 		L.epoch = 0;
 		L.tail_pending = false;
 		L.slice_cap = g.nslots;
 	}
-	if (L.edge_cap < c->ntiles) {
-		(void)hipFree(L.edge_bits); (void)hipFree(L.edge_hdr);
-		L.edge_bits = nullptr; L.edge_hdr = nullptr; L.edge_cap = 0;
-		HIP_TRY(hipMalloc(&L.edge_bits, c->ntiles * 2 * 128 * sizeof(uint4)));
-		HIP_TRY(hipMalloc(&L.edge_hdr, c->ntiles * 2 * 2 * sizeof(uint4)));
-		L.edge_cap = c->ntiles;
-	}
+	if (L.edge_cap < c->ntiles)
+		if (int rc = dev_room_all("tile edge buffers", &L.edge_cap, c->ntiles,
+		                          {dev_array(&L.edge_bits, c->ntiles, 2 * 128 * sizeof(uint4)), dev_array(&L.edge_hdr, c->ntiles, 2 * 2 * sizeof(uint4))}))
+			return rc;
 	const uint64_t nchunks = (L.slice_cap + SLOT_CHUNK - 1) / SLOT_CHUNK;  // (capacity: the halves keep their place)
 	if (++L.epoch >= c->epoch_wrap) {  // stamps wrap: start over with clean headers AND clean partial sums - the call before
 		// accumulated into the half an odd epoch selects and cleared only the other one, and epoch 1 is odd again
@@ -292,8 +263,19 @@ static unsigned long long *lane_part(const IsoLane &L, bool next) {
 	return L.slot_part + ((L.epoch + (next ? 1u : 0u)) & 1u) * nchunks;
 }
 
+// Kernel arguments that come from the context: the resident grid, the reference's tables, and the arrays of a TailSet under the
+// names the argument structs share - rec: CellsArgs, SlowArgs or EmitCtx; lists: CellsArgs, SlowArgs or EmitArgs (w.lc first)
+static GridView<sample_t> grid_view(const mc33hip_ctx *c) { return GridView<sample_t>{c->d_grid, (uint32_t)c->pitch, c->desc.plane0, c->slice}; }
+static Tables tables(const mc33hip_ctx *c) { return Tables{c->d_lut, c->d_rules, c->d_rule_index}; }
+template <typename Rec, typename Lists>
+static void set_arrays(const TailSet &w, Rec &rec, Lists &lists) {
+	rec.entries_a = w.entries_a; rec.entries_b = w.entries_b; rec.entry_seg = w.entry_seg; rec.seg_dir = w.seg_dir;
+	lists.slow_list = w.slow_list; lists.lc = w.lc; lists.slot_base = w.slot_base;
+	lists.entry_cap = (uint32_t)w.entry_cap; lists.ctr = w.d_ctr;
+}
+
 static void sweep_args(mc33hip_ctx *c, const SlotGeom &g, SweepArgs &a) {
-	a.G.p = c->d_grid; a.G.pitch = (uint32_t)c->pitch; a.G.z0 = c->desc.plane0; a.G.slice = c->slice;
+	a.G = grid_view(c);
 	a.P = c->P;
 	a.sd = g.sd;
 	a.tiles = c->d_tiles;
@@ -392,22 +374,11 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 		IsoLane &L = c->lanes[idx[q]];
 		TailSet &w = c->ts[sidx[q]];
 		const Params P = lane_params(c, isos[q]);
-		if (w.slot_base_cap < g.nslots) {
-			(void)hipFree(w.slot_base); (void)hipFree(w.live_list);
-			w.slot_base = nullptr; w.live_list = nullptr; w.slot_base_cap = 0;
-			HIP_TRY(hipMalloc(&w.slot_base, g.nslots * sizeof(uint2)));
-			HIP_TRY(hipMalloc(&w.live_list, g.nslots * sizeof(uint32_t)));
-			w.slot_base_cap = g.nslots;
-		}
-		{  // batch descriptors: every 64 records one, plus at most one partly filled batch per slice slot
-			const uint64_t need = w.entry_cap / 64 + g.nslots + 64;
-			if (w.batch_cap < need) {
-				(void)hipFree(w.batches);
-				w.batches = nullptr; w.batch_cap = 0;
-				HIP_TRY(hipMalloc(&w.batches, need * sizeof(BatchDesc)));
-				w.batch_cap = need;
-			}
-		}
+		if (w.slot_base_cap < g.nslots)
+			if (int rc = dev_room_all("slot bases", &w.slot_base_cap, g.nslots, {dev_array(&w.slot_base, g.nslots), dev_array(&w.live_list, g.nslots)})) return rc;
+		// batch descriptors: every 64 records one, plus at most one partly filled batch per slice slot
+		if (const uint64_t need = w.entry_cap / 64 + g.nslots + 64; w.batch_cap < need)
+			if (int rc = dev_room("batch descriptors", &w.batches, &w.batch_cap, need)) return rc;
 		set_lane(a, q, L, isos[q]);
 		boundaries |= !L.boundary_done;
 		CellsArgs &ca = CA.a[q];
@@ -416,10 +387,10 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 #ifdef MC33_DEV
 		ca.dev = c->sw.cells_dev;
 #endif
-		ca.G.p = c->d_grid; ca.G.pitch = (uint32_t)c->pitch; ca.G.z0 = c->desc.plane0; ca.G.slice = c->slice;
+		ca.G = grid_view(c);
 		ca.P = P; ca.fast = c->d_fast; ca.pat = c->d_pat; ca.pat_order = c->d_pat_order;
 		ca.ze = ze; ca.sd = g.sd;
-		ca.slice_hdr = L.slice_hdr; ca.slice_bits = L.slice_bits; ca.slice_compact = L.slice_compact; ca.plane_fmt = L.plane_fmt; ca.slot_base = w.slot_base;
+		ca.slice_hdr = L.slice_hdr; ca.slice_bits = L.slice_bits; ca.slice_compact = L.slice_compact; ca.plane_fmt = L.plane_fmt;
 		// the tag of this tail's row-segment counts; the array is cleared whenever the tags start over
 		if (w.tail_serial % SEG_TAGS == 0) HIP_TRY(hipMemsetAsync(w.seg_cnt, 0, w.seg_cap * 4, st));
 		const uint32_t seg_tag = w.tail_serial % SEG_TAGS + 1u;
@@ -427,17 +398,12 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 		ca.seg_tag = seg_tag;
 		ca.live_list = w.live_list; ca.live_cap = (uint32_t)std::min<uint64_t>(g.nslots, 0xFFFFFFFFull);
 		ca.epoch = L.epoch;
-		ca.seg_cnt = w.seg_cnt; ca.seg_dir = w.seg_dir;
-		ca.entries_a = w.entries_a; ca.entries_b = w.entries_b; ca.entry_seg = w.entry_seg; ca.slow_list = w.slow_list; ca.dirty_list = w.dirty_list;
-		ca.entry_cap = (uint32_t)w.entry_cap;
+		ca.seg_cnt = w.seg_cnt; ca.dirty_list = w.dirty_list;
 		ca.batches = w.batches; ca.batch_cap = (uint32_t)std::min<uint64_t>(w.batch_cap, 0xFFFFFFFFull);
-		ca.ctr = w.d_ctr;
 		ca.trace = nullptr;
 		if (n == 1 && c->sw.trace_cells) {
-			(void)hipFree(c->trace_cells);
-			c->trace_cells = nullptr;
-			c->trace_cells_n = g.nslots;
-			HIP_TRY(hipMalloc(&c->trace_cells, g.nslots * 32));
+			c->trace_cells_n = 0;  // (a new one for every tail)
+			if (int rc = dev_room("cell trace", &c->trace_cells, &c->trace_cells_n, g.nslots, 32)) return rc;
 			HIP_TRY(hipMemsetAsync(c->trace_cells, 0, g.nslots * 32, st));
 			ca.trace = c->trace_cells;
 		}
@@ -446,18 +412,17 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 			while (((g.nslots + (1ull << shift) - 1) >> shift) > LIST_CHUNKS) shift++;
 			w.lc = ListChunks{w.list_cnt, w.list_cnt + LIST_CHUNKS, (uint32_t)((g.nslots + (1ull << shift) - 1) >> shift), shift};
 		}
-		ca.lc = w.lc;
+		set_arrays(w, ca, ca);
 		const uint64_t nchunks = (L.slice_cap + SLOT_CHUNK - 1) / SLOT_CHUNK;
 		SA.a[q] = SlotsArgs{L.slice_hdr, lane_part(L, false), lane_part(L, true), (uint32_t)nchunks, L.epoch, w.slot_base, w.d_ctr, w.lc,
 		                    (unsigned long long *)(w.bsV + 2 * w.bs_cap), (uint32_t)(2 * scan_groups(w.bs_cap)), w.live_list, ca.live_cap};
 		SlowArgs &sa = WA.a[q];
 		sa.G = ca.G; sa.P = P;
-		sa.tab.lut = c->d_lut; sa.tab.rule_words = c->d_rules; sa.tab.rule_index = c->d_rule_index;
+		sa.tab = tables(c);
 		sa.z_emit = c->range.z_begin;
-		sa.entries_a = w.entries_a; sa.entries_b = w.entries_b; sa.entries_c = w.entries_c; sa.fast_b = c->d_fast_b; sa.entry_seg = w.entry_seg; sa.slow_list = w.slow_list;
-		sa.seg_cnt = w.seg_cnt; sa.seg_tag = seg_tag; sa.seg_dir = w.seg_dir; sa.dirty_list = w.dirty_list;
-		sa.lc = w.lc; sa.slot_base = w.slot_base;
-		sa.entry_cap = (uint32_t)w.entry_cap; sa.ctr = w.d_ctr;
+		set_arrays(w, sa, sa);
+		sa.entries_c = w.entries_c; sa.fast_b = c->d_fast_b;
+		sa.seg_cnt = w.seg_cnt; sa.seg_tag = seg_tag; sa.dirty_list = w.dirty_list;
 		uint64_t *grV = nb >= SCAN_GROUPED_FROM ? w.bsV + 2 * w.bs_cap : nullptr, *grT = grV ? grV + scan_groups(w.bs_cap) : nullptr;
 		NA.a[q] = ScanArgs{w.seg_cnt, seg_tag, w.lc.slow_cnt, w.lc.n, w.bsV, w.bsT, grV, grT, w.seg_base, w.d_ctr};
 		// k_slots appends to live_list from Counters::live_cursor on, and k_scan_apply - the last kernel of a tail - leaves the
@@ -553,10 +518,8 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 		}
 #endif
 		if (c->sw.trace_file) {
-			(void)hipFree(c->trace);
-			c->trace = nullptr;
-			c->trace_waves = ((c->ntiles + 3) / 4) * 4;
-			HIP_TRY(hipMalloc(&c->trace, c->trace_waves * 32));
+			c->trace_waves = 0;  // (a new one for every sweep)
+			if (int rc = dev_room("sweep trace", &c->trace, &c->trace_waves, ((c->ntiles + 3) / 4) * 4, 32)) return rc;
 			HIP_TRY(hipMemsetAsync(c->trace, 0, c->trace_waves * 32, st));
 			a.trace = c->trace;
 			if (c->timing_level > 0) HIP_TRY(hipEventRecord(c->ev[0], st));
@@ -664,17 +627,13 @@ static int enqueue_emit(mc33hip_ctx *c, void *dV, void *dN, void *dT, uint64_t c
 	EmitArgs a;
 	a.dev_base = dev_base;
 	c->count_unused = false;  // (the count has served an emit: the next count of this isovalue is made anew)
-	a.c.tab.lut = c->d_lut; a.c.tab.rule_words = c->d_rules; a.c.tab.rule_index = c->d_rule_index;
+	a.c.tab = tables(c);
 	a.c.P = c->P;
-	a.c.G.p = c->d_grid; a.c.G.pitch = (uint32_t)c->pitch; a.c.G.z0 = c->desc.plane0; a.c.G.slice = c->slice;
-	a.c.seg_base = c->w->seg_base; a.c.seg_dir = c->w->seg_dir;
-	a.c.entries_a = c->w->entries_a; a.c.entries_b = c->w->entries_b; a.c.entries_c = c->w->entries_c; a.c.fast_b = c->d_fast_b; a.c.fast_b_in_lds = false; a.c.entry_seg = c->w->entry_seg;
+	a.c.G = grid_view(c);
+	set_arrays(*c->w, a.c, a);
+	a.c.seg_base = c->w->seg_base; a.c.entries_c = c->w->entries_c; a.c.fast_b = c->d_fast_b; a.c.fast_b_in_lds = false;
 	a.c.V = (real_t *)dV; a.c.N = (float *)dN; a.c.Tri = (uint32_t *)dT;
 	a.c.z_emit = c->range.z_begin; a.c.v_skip = a.c.t_skip = a.c.id_delta = 0;
-	a.ctr = c->w->d_ctr;
-	a.slow_list = c->w->slow_list;
-	a.lc = c->w->lc; a.slot_base = c->w->slot_base;
-	a.entry_cap = (uint32_t)c->w->entry_cap;
 	a.capV = capV; a.capT = capT;
 	a.ghost_segs = c->ghost_segs;
 	a.id_base = c->range.id_base;
@@ -870,64 +829,71 @@ static void read_timing(mc33hip_ctx *c, bool with_emit, unsigned launches) {
 	}
 }
 
-extern "C" int mc33hip_count(mc33hip_ctx *c, double iso, const mc33hip_range *range, mc33hip_counts *out) {
-	if (!c) return MC33HIP_EINVAL;
+// What every call that classifies the grid begins with: the device, the range, the last count forgotten, c->P / c->range / c->nsegs
+// for this isovalue and range, the buffers of set 0
+static int begin_call(mc33hip_ctx *c, double iso, const mc33hip_range *range) {
 	int rc = use_device(c);
 	if (rc) return rc;
 	if ((rc = check_range(c, range))) return rc;
+	c->counted = false;
+	fill_params(c, iso, range);
+	return ensure_workspaces(c);
+}
+
+// Count until it fits, for the calls that read the counters before they return: sweep and tail - with emit targets, the emit passes
+// right behind them, which check the capacities of the targets on the device - then the counters, and again
+//   - when the tail left the slow kernels out (alias_gate: enqueue_tail) and there were slow cells after all: a miss.  The counts
+//     do not stand and the emit passes have refused (emit_prepare); the tail again, with the slow kernels - fetch_counters has noted
+//     that the set has slow cells;
+//   - when the records did not fit: nothing was emitted, the record arrays grow to what the counters ask for.
+// A repeated round keeps the sweep's result (enqueue_count: rerun).
+struct EmitTargets { void *dV, *dN, *dT; unsigned long long capV, capT; };
+static int count_until_fits(mc33hip_ctx *c, const EmitTargets *emit) {
+	unsigned launches = 0;
+	for (;;) {
+		c->alias_gate = true;
+		int rc = enqueue_count(c, launches > 0);
+		c->alias_gate = false;
+		if (rc) return rc;
+		launches++;
+		if (emit && (rc = enqueue_emit(c, emit->dV, emit->dN, emit->dT, emit->capV, emit->capT))) return rc;
+		if ((rc = fetch_counters(c))) return rc;
+		const bool miss = c->w->alias_gated && c->w->h_ctr->alias_cells != 0u;
+		if (c->w->h_ctr->entry_cursor <= c->w->entry_cap && !miss) break;
+		if (c->w->h_ctr->entry_cursor > c->w->entry_cap && (rc = grow_entries(*c->w, c->w->h_ctr->entry_cursor))) return rc;
+	}
+	read_timing(c, emit != nullptr, launches);
+	return 0;
+}
+
+extern "C" int mc33hip_count(mc33hip_ctx *c, double iso, const mc33hip_range *range, mc33hip_counts *out) {
+	if (!c) return MC33HIP_EINVAL;
 	// The same isovalue over the same range of the library's OWN copy of the grid, counted by the call before and not emitted yet
 	// (size_of_isosurface and then calculate_isosurface of the value it asked about: what a viewer does to show the memory a
 	// surface will take, reference MC:1892-1940 / 1816-1889): everything the count made is still there - nothing is streamed
 	// again.  Only a COUNT is reused, once: an extraction repeated with the same isovalue does all its work again, like the
 	// reference's.  Not for a caller's device buffer (mc33hip_adopt_device): its samples may have been rewritten without this
-	// library knowing.
-	if (c->counted && c->count_unused && !c->async_count && c->owns_grid && c->timing_level == 0 && same_bits((real_t)iso, c->P.iso) && same_range(*range, c->range)) {
+	// library knowing.  (The range is the one that count checked, and nothing here touches the device.)
+	if (range && c->counted && c->count_unused && !c->async_count && c->owns_grid && c->timing_level == 0 && same_bits((real_t)iso, c->P.iso) && same_range(*range, c->range)) {
 		c->range.id_base = range->id_base;
 		return finish_counts(c, out);
 	}
-	c->counted = false;
-	fill_params(c, iso, range);
-	if ((rc = ensure_workspaces(c))) return rc;
-	unsigned launches = 0;
-	for (;;) {
-		c->alias_gate = true;
-		rc = enqueue_count(c, launches > 0);
-		c->alias_gate = false;
-		if (rc) return rc;
-		launches++;
-		if ((rc = fetch_counters(c))) return rc;
-		const bool miss = c->w->alias_gated && c->w->h_ctr->alias_cells != 0u;  // (slow cells, and their kernels left out: the tail again, with them)
-		if (c->w->h_ctr->entry_cursor <= c->w->entry_cap && !miss) break;
-		if (c->w->h_ctr->entry_cursor > c->w->entry_cap && (rc = grow_entries(*c->w, c->w->h_ctr->entry_cursor))) return rc;
-	}
-	read_timing(c, false, launches);
+	int rc = begin_call(c, iso, range);
+	if (rc) return rc;
+	if ((rc = count_until_fits(c, nullptr))) return rc;
 	if ((rc = finish_counts(c, out))) return rc;
 	c->counted = true;
 	c->count_unused = true;
 	return MC33HIP_OK;
 }
 
-extern "C" int mc33hip_sweep_many(mc33hip_ctx *c, const double *isos, int n, const mc33hip_range *range) {
+static int sweep_many(mc33hip_ctx *c, const double *isos, int n, const mc33hip_range *range, bool tails_ahead) {
 	if (!c || !isos || n < 1 || n > MC33_LANES) return MC33HIP_EINVAL;
-	int rc = use_device(c);
-	if (rc) return rc;
-	if ((rc = check_range(c, range))) return rc;
-	c->counted = false;
-	fill_params(c, isos[0], range);
-	if ((rc = ensure_workspaces(c))) return rc;
-	return enqueue_sweep_many(c, isos, n, false);
+	if (int rc = begin_call(c, isos[0], range)) return rc;
+	return enqueue_sweep_many(c, isos, n, tails_ahead);
 }
-
-extern "C" int mc33hip_prepare_many(mc33hip_ctx *c, const double *isos, int n, const mc33hip_range *range) {
-	if (!c || !isos || n < 1 || n > MC33_LANES) return MC33HIP_EINVAL;
-	int rc = use_device(c);
-	if (rc) return rc;
-	if ((rc = check_range(c, range))) return rc;
-	c->counted = false;
-	fill_params(c, isos[0], range);
-	if ((rc = ensure_workspaces(c))) return rc;
-	return enqueue_sweep_many(c, isos, n, true);
-}
+extern "C" int mc33hip_sweep_many(mc33hip_ctx *c, const double *isos, int n, const mc33hip_range *range) { return sweep_many(c, isos, n, range, false); }
+extern "C" int mc33hip_prepare_many(mc33hip_ctx *c, const double *isos, int n, const mc33hip_range *range) { return sweep_many(c, isos, n, range, true); }
 
 extern "C" int mc33hip_set_inclined(mc33hip_ctx *c, const double *grd_A, const double *grd_Ai, int triangular) {
 	if (!c) return MC33HIP_EINVAL;
@@ -970,12 +936,8 @@ extern "C" int mc33hip_emit(mc33hip_ctx *c, void *dV, void *dN, void *dT, unsign
 // ---- a z-slab's count, exchange and emit without a host round trip in between (slabs.py: extract_slab) ----
 extern "C" int mc33hip_count_async(mc33hip_ctx *c, double iso, const mc33hip_range *range) {
 	if (!c) return MC33HIP_EINVAL;
-	int rc = use_device(c);
+	int rc = begin_call(c, iso, range);
 	if (rc) return rc;
-	if ((rc = check_range(c, range))) return rc;
-	c->counted = false;
-	fill_params(c, iso, range);
-	if ((rc = ensure_workspaces(c))) return rc;
 	if ((rc = enqueue_count(c, false))) return rc;
 	memset(&c->counts, 0, sizeof c->counts);  // (not known on the host until mc33hip_count_finish)
 	c->counted = true;
@@ -1051,26 +1013,10 @@ extern "C" int mc33hip_download_wait(mc33hip_ctx *c) {
 extern "C" int mc33hip_extract(mc33hip_ctx *c, double iso, const mc33hip_range *range, void *dV, void *dN, void *dT,
                                unsigned long long capV, unsigned long long capT, mc33hip_counts *out) {
 	if (!c) return MC33HIP_EINVAL;
-	int rc = use_device(c);
+	int rc = begin_call(c, iso, range);
 	if (rc) return rc;
-	if ((rc = check_range(c, range))) return rc;
-	c->counted = false;
-	fill_params(c, iso, range);
-	if ((rc = ensure_workspaces(c))) return rc;
-	unsigned launches = 0;
-	for (;;) {
-		c->alias_gate = true;
-		rc = enqueue_count(c, launches > 0);
-		c->alias_gate = false;
-		if (rc) return rc;
-		launches++;
-		if ((rc = enqueue_emit(c, dV, dN, dT, capV, capT))) return rc;  // checks capacities (and a miss of the slow kernels) on the device
-		if ((rc = fetch_counters(c))) return rc;
-		const bool miss = c->w->alias_gated && c->w->h_ctr->alias_cells != 0u;  // (the emit passes refused: the tail again, with the slow kernels)
-		if (c->w->h_ctr->entry_cursor <= c->w->entry_cap && !miss) break;
-		if (c->w->h_ctr->entry_cursor > c->w->entry_cap && (rc = grow_entries(*c->w, c->w->h_ctr->entry_cursor))) return rc;
-	}
-	read_timing(c, true, launches);
+	const EmitTargets emit{dV, dN, dT, capV, capT};
+	if ((rc = count_until_fits(c, &emit))) return rc;
 	if ((rc = finish_counts(c, out))) return rc;
 	c->counted = true;
 	if (c->w->h_ctr->emit_skipped) { set_err("output buffers too small: need %llu vertices, %llu triangles", c->counts.nV, c->counts.nT); return MC33HIP_ECAPACITY; }

@@ -491,7 +491,7 @@ __global__ __launch_bounds__(256) void k_cc_table_vertices(const uint32_t *__res
 static void meas_destroy(mc33hip_ctx *c) {
 	MeasureState *m = c->meas;
 	if (!m) return;
-	(void)hipFree(m->d_out); (void)hipFree(m->d_part); (void)hipFree(m->d_flags); (void)hipFree(m->d_rank); (void)hipFree(m->d_bsum); (void)hipFree(m->d_table);
+	dev_release(&m->d_out); dev_release(&m->d_part); dev_release(&m->d_flags); dev_release(&m->d_rank); dev_release(&m->d_bsum); dev_release(&m->d_table);
 	if (m->h_out) (void)hipHostFree(m->h_out);
 	free(m);
 	c->meas = nullptr;
@@ -508,16 +508,11 @@ static int meas_state(mc33hip_ctx *c) {
 	return 0;
 }
 
-// room for `need` elements; nothing of an earlier call is in flight (every entry point waits before it returns)
+// room for `need` elements, with an eighth and 256 to spare when the array has to be made anew; nothing of an earlier call is in
+// flight (every entry point waits before it returns)
 template <typename E>
 static int meas_room(E **p, uint64_t *cap, uint64_t need) {
-	if (*cap >= need && *p) return 0;
-	(void)hipFree(*p);
-	*p = nullptr; *cap = 0;
-	const uint64_t n = need + need / 8u + 256u;
-	HIP_TRY(hipMalloc(p, n * sizeof(E)));
-	*cap = n;
-	return 0;
+	return *cap >= need && *p ? 0 : dev_room("measuring scratch", p, cap, need + need / 8u + 256u);
 }
 
 static uint32_t meas_grid(const mc33hip_ctx *c, uint64_t n, uint32_t per_cu) {  // lanes of 256 up to per_cu blocks per CU

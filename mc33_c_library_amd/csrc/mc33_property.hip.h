@@ -84,8 +84,8 @@ __global__ __launch_bounds__(256) void k_property(PropArgs a, const R *__restric
 
 // --- host side ----------------------------------------------------------------------------------------------------------
 
-static void prop_release(mc33hip_ctx *c) {
-	if (c->prop_owned) (void)hipFree(c->d_prop);
+static void prop_release(mc33hip_ctx *c) {  // (a caller's buffer is let go of, the library's copy released)
+	if (c->prop_owned) dev_release(&c->d_prop);
 	c->d_prop = nullptr;
 	c->prop_owned = false;
 	c->prop_cap = 0;
@@ -93,7 +93,7 @@ static void prop_release(mc33hip_ctx *c) {
 
 static void prop_destroy(mc33hip_ctx *c) {
 	prop_release(c);
-	(void)hipFree(c->d_prop_pal); (void)hipFree(c->d_prop_viol);
+	dev_release(&c->d_prop_pal); dev_release(&c->d_prop_viol);
 	if (c->h_prop_viol) (void)hipHostFree(c->h_prop_viol);
 	if (c->ev_prop) (void)hipEventDestroy(c->ev_prop);
 }
@@ -107,12 +107,10 @@ static int prop_window(mc33hip_ctx *c, unsigned plane0, unsigned nplanes) {
 static int prop_ensure_own(mc33hip_ctx *c, unsigned plane0, unsigned nplanes) {
 	const size_t pitch = own_pitch(c->desc.npx), slice = pitch * c->desc.npy, need = slice * nplanes;
 	HIP_TRY(hipStreamSynchronize(c->stream));  // (nothing enqueued earlier may still be sampling the old copy)
-	if (!c->prop_owned || c->prop_cap < need) {
-		prop_release(c);
-		HIP_TRY(hipMalloc(&c->d_prop, need * sizeof(sample_t)));
-		c->prop_owned = true;
-		c->prop_cap = need;
-	}
+	if (!c->prop_owned) prop_release(c);
+	c->prop_owned = false;
+	if (int rc = dev_room("property grid", &c->d_prop, &c->prop_cap, need)) return rc;
+	c->prop_owned = true;
 	c->prop_pitch = pitch; c->prop_slice = slice;
 	c->prop_plane0 = plane0; c->prop_nplanes = nplanes;
 	return 0;
