@@ -192,6 +192,29 @@ unsigned MC33_measure_isosurfaces(MC33 *extractor, const MC33_real *isovalues, u
 int MC33_measure_components(MC33 *extractor, MC33_real isovalue, mc33_component *table, unsigned capacity, unsigned *components,
                             unsigned *unreferenced);
 
+/* extension (not in the reference): the topology of an isosurface, answered on the GPU from the triangle list alone - is it
+ * closed, edge-manifold, consistently wound, and what is its genus.  The surface is extracted into device memory as for
+ * MC33_measure_isosurface and nothing but these structs comes back.  Every side a -> b (a != b) of a triangle uses the edge
+ * {min, max}: edges = distinct edges, boundary_edges = used once, nonmanifold_edges = used more than twice, misoriented_edges =
+ * used twice in the same direction; degenerate_triangles name a vertex twice; boundary_loops = connected sets of boundary
+ * edges; euler = referenced_vertices - edges + nT; closed = no boundary edge, oriented = no misoriented edge, manifold = no
+ * non-manifold edge and no degenerate triangle (edge-manifold only: a pinched vertex is not detected).  Per component - the
+ * rows of MC33_measure_components - the same counts and genus = (2 - euler - boundary_loops) / 2 where the component is manifold
+ * and oriented and that is a whole number >= 0, else -1; genus_sum adds the rows with genus >= 0, genus_defined is 1 iff no row
+ * has -1.  The exact definitions are in mc33_hip.h (mc33hip_surface_topology).
+ * MC33_isosurface_topology returns 0, or -1; MC33_component_topology returns 0, -1, or -2 with the number in *components and
+ * no row written when `capacity` is below it (table NULL, capacity 0 asks for the number).  Both set extractor->iso, leave
+ * memoryfault alone and refuse with -1 an extractor spread over several devices. */
+typedef struct mc33_topology { unsigned nV, nT; unsigned long long referenced_vertices, edges, boundary_edges, nonmanifold_edges,
+                               misoriented_edges, degenerate_triangles, boundary_loops, components, closed_components, genus_sum;
+                               long long euler; int closed, manifold, oriented, genus_defined; } mc33_topology;
+typedef struct mc33_component_topology { unsigned root, nV, nT; unsigned long long edges, boundary_edges, nonmanifold_edges,
+                                         misoriented_edges, degenerate_triangles, boundary_loops; long long euler; int genus;
+                                       } mc33_component_topology;
+int MC33_isosurface_topology(MC33 *extractor, MC33_real isovalue, mc33_topology *out);
+int MC33_component_topology(MC33 *extractor, MC33_real isovalue, mc33_component_topology *table, unsigned capacity,
+                            unsigned *components);
+
 /* ---- inclined grids (reference header :186-191) ---------------------------------------------------------
  * c = A b (transposed == 0) or A^T b for a 3x3 matrix; _multTSA_bf assumes an upper triangular A.  A caller may
  * point mult_Abf at either; calculate_isosurface looks at the pointer when it is called and runs the matching

@@ -234,7 +234,7 @@ int mc33hip_download_enqueue(mc33hip_ctx *c, void *host_dst, const void *device_
  *   Q_i = A_i * ((((double)P[T[i][0]] + (double)P[T[i][1]]) + (double)P[T[i][2]]) / 3.0),  P: what mc33hip_sample_property left
  * volume is SIGNED, with the winding as T stores it: the reference's winding gives a sphere whose samples grow outwards a
  * NEGATIVE volume, a context with mc33hip_set_normal_neg on the opposite sign.  It is the enclosed volume only for a surface
- * that does not reach the grid's faces (an open sheet has no inside; nothing here reports closedness).  The area centroid is
+ * that does not reach the grid's faces (an open sheet has no inside: `closed` of mc33hip_surface_topology below tells).  The area centroid is
  * origin + moment / area.  bbox_min / bbox_max: exact minimum / maximum of the rows of V per axis (+inf / -inf for nV == 0, a NaN
  * coordinate is skipped); NaN in V or P otherwise propagates into the sums.  The sums are accumulated in double from the first
  * addition on, without floating-point atomics: two calls on the same mesh in one process return the same bits.
@@ -266,6 +266,59 @@ int mc33hip_label_components(mc33hip_ctx *c, const void *dT, unsigned long long 
                              unsigned long long *components, unsigned long long *unreferenced);
 int mc33hip_measure_components(mc33hip_ctx *c, const void *dV, unsigned long long nV, const void *dT, unsigned long long nT,
                                const unsigned *dLabel, mc33hip_component *host_table, unsigned long long capacity,
+                               unsigned long long *components);
+
+/* --- topology of a finished mesh, taken on the device (no counterpart in the reference) ----------------------------------------
+ * T (nT x 3 unsigned) in device memory and nV, as for mc33hip_label_components; V is not read.  Everything is an integer, and
+ * two calls on the same T return the same bytes, whatever the scheduling.
+ *   invalid triangle     names a vertex >= nV: counted, contributes nothing; the call returns MC33HIP_ERUNTIME with the count in
+ *                        mc33hip_last_error, in the words of the measuring calls.
+ *   degenerate triangle  a valid triangle with two equal indices.  Its sides a -> a are skipped, its other sides enter the
+ *                        table like any side, and it still counts in nT.
+ *   edge                 every other side a -> b of a valid triangle, in the order T0 -> T1, T1 -> T2, T2 -> T0, is a use of the
+ *                        undirected edge {lo, hi} = {min(a, b), max(a, b)}: FORWARD if a < b, else BACKWARD.  Use counts are
+ *                        exact 32-bit numbers per direction.
+ *   edges                distinct edges;   boundary_edges: edges with exactly one use;   nonmanifold_edges: more than two uses;
+ *   misoriented_edges    exactly two uses, both forward or both backward.
+ *   referenced_vertices  vertices a valid triangle names: nV - unreferenced of mc33hip_label_components.
+ *   euler                (long long) referenced_vertices - edges + (nT - invalid)
+ *   boundary_loops       connected components of the graph the boundary edges form.  A count of loops only where every boundary
+ *                        vertex ends two boundary edges (where corners equal the isovalue some end more); defined all the same.
+ *   closed = boundary_edges == 0;  oriented = misoriented_edges == 0;
+ *   manifold = nonmanifold_edges == 0 && degenerate_triangles == 0: EDGE-manifold only - a pinched vertex (two fans of
+ *                        triangles that meet in one vertex and in no edge) is not detected.
+ * Per component - the rows of mc33hip_measure_components, in ascending order of root: an edge belongs to label[lo] (both ends
+ * have one label), a degenerate triangle to label[T[i][0]], a boundary loop to the label of its smallest vertex.  The columns
+ * are the same counts, euler = nV - edges + nT of the component, and
+ *   genus = (2 - euler - boundary_loops) / 2  when the component has no non-manifold edge, no degenerate triangle and no
+ *           misoriented edge and that numerator is even and >= 0; else -1.
+ * The surface's struct adds components, closed_components (rows with boundary_edges == 0), genus_sum (over the rows with
+ * genus >= 0) and genus_defined (1 iff no row has -1).  nV and nT repeat the arguments; with nT == 0 everything else is 0,
+ * closed = manifold = oriented = genus_defined = 1 and the table is empty.
+ *
+ * Both calls enqueue on the context's stream behind whatever is on it, wait, and bring the small results to the host.  They
+ * build an edge table in device memory - 16 bytes per slot, a power of two >= 4 nT slots: 4.3 GB for 55.8 M triangles -
+ * MC33HIP_ENOMEM when it cannot be had; it stays with the context until mc33hip_destroy.  mc33hip_surface_topology labels the
+ * components itself, in scratch of its own, and fills *out also when it returns MC33HIP_ERUNTIME for invalid triangles (they
+ * are left out).  mc33hip_component_topology takes dLabel from mc33hip_label_components for the same T and nV; MC33HIP_EINVAL,
+ * MC33HIP_ECAPACITY (the number in *components, the table untouched; host_table NULL, capacity 0 asks for it) and
+ * MC33HIP_ERUNTIME as mc33hip_measure_components. */
+typedef struct {
+	unsigned long long nV, nT, referenced_vertices, edges, boundary_edges, nonmanifold_edges, misoriented_edges,
+	                   degenerate_triangles, boundary_loops, components, closed_components, genus_sum;
+	long long euler;
+	int closed, manifold, oriented, genus_defined;
+} mc33hip_topology;
+struct mc33hip_component_topology { /* (a tag, not a typedef: C keeps the function of the same name in another name space) */
+	unsigned root, nV, nT;
+	unsigned long long edges, boundary_edges, nonmanifold_edges, misoriented_edges, degenerate_triangles, boundary_loops;
+	long long euler;
+	int genus;
+};
+
+int mc33hip_surface_topology(mc33hip_ctx *c, const void *dT, unsigned long long nT, unsigned long long nV, mc33hip_topology *out);
+int mc33hip_component_topology(mc33hip_ctx *c, const void *dT, unsigned long long nT, unsigned long long nV, const unsigned *dLabel,
+                               struct mc33hip_component_topology *host_table, unsigned long long capacity,
                                unsigned long long *components);
 
 /* Plain device allocations on the context's device (for language bindings). */

@@ -42,6 +42,18 @@ class Component(C.Structure):
     _fields_ = [("root", C.c_uint), ("nV", C.c_uint), ("nT", C.c_uint), ("area", C.c_double), ("volume", C.c_double)]
 
 
+class Topology(C.Structure):
+    _fields_ = [(n, C.c_ulonglong) for n in ("nV", "nT", "referenced_vertices", "edges", "boundary_edges", "nonmanifold_edges", "misoriented_edges",
+                                             "degenerate_triangles", "boundary_loops", "components", "closed_components", "genus_sum")] + \
+               [("euler", C.c_longlong)] + [(n, C.c_int) for n in ("closed", "manifold", "oriented", "genus_defined")]
+
+
+class ComponentTopology(C.Structure):
+    _fields_ = [("root", C.c_uint), ("nV", C.c_uint), ("nT", C.c_uint)] + \
+               [(n, C.c_ulonglong) for n in ("edges", "boundary_edges", "nonmanifold_edges", "misoriented_edges", "degenerate_triangles", "boundary_loops")] + \
+               [("euler", C.c_longlong), ("genus", C.c_int)]
+
+
 HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_last_error", "mc33hip_upload_rows",
            "mc33hip_upload_contiguous", "mc33hip_adopt_device", "mc33hip_set_stream", "mc33hip_count",
            "mc33hip_emit", "mc33hip_extract", "mc33hip_last_timing", "mc33hip_download",
@@ -50,14 +62,16 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_counts_to_device", "mc33hip_bases_from_table", "mc33hip_emit_at_device_bases", "mc33hip_count_finish",
            "mc33hip_property_upload_rows", "mc33hip_property_upload_contiguous", "mc33hip_property_adopt_device", "mc33hip_property_drop",
            "mc33hip_sample_property", "mc33hip_color_vertices", "mc33hip_download_enqueue",
-           "mc33hip_measure_surface", "mc33hip_label_components", "mc33hip_measure_components"]
+           "mc33hip_measure_surface", "mc33hip_label_components", "mc33hip_measure_components",
+           "mc33hip_surface_topology", "mc33hip_component_topology"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
                  "write_bin_s", "read_bin_s", "write_txt_s", "write_obj_s", "write_ply_s",
                  "read_grd", "read_grd_binary", "read_scanfiles", "read_raw_file", "read_dat_file", "calculate_isosurfaces", "MC33_grid_changed",
                  "MC33_set_property_grid", "MC33_set_color_map",
-                 "MC33_measure_isosurface", "MC33_measure_isosurfaces", "MC33_measure_components"]
+                 "MC33_measure_isosurface", "MC33_measure_isosurfaces", "MC33_measure_components",
+                 "MC33_isosurface_topology", "MC33_component_topology"]
 
 
 class MC33Error(RuntimeError):
@@ -126,6 +140,8 @@ def load_library(dtype="f32"):
     lib.mc33hip_measure_surface.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V, P(Measures)]
     lib.mc33hip_label_components.argtypes = [V, V, C.c_ulonglong, C.c_ulonglong, V, P(C.c_ulonglong), P(C.c_ulonglong)]
     lib.mc33hip_measure_components.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V, V, C.c_ulonglong, P(C.c_ulonglong)]
+    lib.mc33hip_surface_topology.argtypes = [V, V, C.c_ulonglong, C.c_ulonglong, P(Topology)]
+    lib.mc33hip_component_topology.argtypes = [V, V, C.c_ulonglong, C.c_ulonglong, V, V, C.c_ulonglong, P(C.c_ulonglong)]
     _libs[dtype] = lib
     return lib
 
@@ -146,6 +162,26 @@ class SurfaceMeasures:
 
     def __repr__(self):
         return "SurfaceMeasures(nV=%d, nT=%d, area=%r, volume=%r, centroid=%r)" % (self.nV, self.nT, self.area, self.volume, self.centroid)
+
+
+class SurfaceTopology:
+    """What DeviceGrid.topology returns - the fields of mc33hip_topology (include/mc33_hip.h) as Python ints: nV, nT,
+    referenced_vertices, edges, boundary_edges, nonmanifold_edges, misoriented_edges, degenerate_triangles, boundary_loops,
+    components, closed_components, genus_sum, euler, and the flags closed, manifold (edge-manifold), oriented, genus_defined."""
+    FIELDS = tuple(n for n, _ in Topology._fields_)
+
+    def __init__(self, t):
+        for n in self.FIELDS:
+            setattr(self, n, int(getattr(t, n)))
+
+    def as_tuple(self):
+        return tuple(getattr(self, n) for n in self.FIELDS)
+
+    def __eq__(self, other):
+        return isinstance(other, SurfaceTopology) and self.as_tuple() == other.as_tuple()
+
+    def __repr__(self):
+        return "SurfaceTopology(%s)" % ", ".join("%s=%d" % (n, getattr(self, n)) for n in self.FIELDS)
 
 
 def _check(lib, rc, allow=()):
@@ -408,6 +444,46 @@ class DeviceGrid:
         _check(self.lib, self.lib.mc33hip_measure_surface(self.ctx, C.c_void_p(V.data_ptr()), cnt.nV, C.c_void_p(T.data_ptr()), cnt.nT,
                                                           C.c_void_p(P.data_ptr()) if P is not None else None, C.byref(m)))
         return SurfaceMeasures(m)
+
+    # -- topology of a finished triangle list, taken on the device (mc33_hip.h: mc33hip_surface_topology) --------------------------
+    def topology(self, T, nV):
+        """Edges, boundary / non-manifold / misoriented edges, degenerate triangles, boundary loops, Euler number, components and
+        genus of the triangle list T [m, 3] over nV vertices: a SurfaceTopology.  Raises MC33Error(ERUNTIME) when a triangle
+        names a vertex >= nV."""
+        self._triangle_rows(T)
+        t = Topology()
+        _check(self.lib, self.lib.mc33hip_surface_topology(self.ctx, C.c_void_p(T.data_ptr()), T.shape[0], int(nV), C.byref(t)))
+        return SurfaceTopology(t)
+
+    def component_topology(self, T, nV, labels=None):
+        """The same counts per component, with euler and genus (-1: not defined) - the rows of measure_components, in ascending
+        order of root - as a numpy structured array; labels: what label_components returned for T (made here when None)."""
+        import numpy as np
+        self._triangle_rows(T)
+        if labels is None:
+            labels = self.label_components(T, nV)[0]
+        assert labels.is_cuda and labels.is_contiguous() and labels.numel() == int(nV) and labels.element_size() == 4
+        args = (self.ctx, C.c_void_p(T.data_ptr()), T.shape[0], int(nV), C.c_void_p(labels.data_ptr()))
+        n = C.c_ulonglong()
+        _check(self.lib, self.lib.mc33hip_component_topology(*args, None, 0, C.byref(n)), allow=(ECAPACITY,))
+        table = np.zeros(n.value, dtype=np.dtype(ComponentTopology))
+        if n.value:
+            _check(self.lib, self.lib.mc33hip_component_topology(*args, C.c_void_p(table.ctypes.data), n.value, C.byref(n)))
+        return table
+
+    def topology_iso(self, iso, rng=None):
+        """Count, emit into torch tensors, topology - nothing but the result crosses the link."""
+        import torch
+        rng = rng or self.full_range()
+        cnt = self.count(iso, rng)
+        V = torch.empty((max(cnt.nV, 1), 3), dtype=torch.float64 if self.dtype == "f64" else torch.float32, device=self.device)
+        N = torch.empty((max(cnt.nV, 1), 3), dtype=torch.float32, device=self.device)
+        T = torch.empty((max(cnt.nT, 1), 3), dtype=torch.int32, device=self.device)
+        _check(self.lib, self.lib.mc33hip_emit(self.ctx, C.c_void_p(V.data_ptr()), C.c_void_p(N.data_ptr()),
+                                               C.c_void_p(T.data_ptr()), V.shape[0], T.shape[0]))
+        t = Topology()
+        _check(self.lib, self.lib.mc33hip_surface_topology(self.ctx, C.c_void_p(T.data_ptr()), cnt.nT, cnt.nV, C.byref(t)))
+        return SurfaceTopology(t)
 
     def probe_read(self, reps=10):
         """A plain read of the resident grid (nothing to do with an extraction): (best ms, median ms, bytes)."""

@@ -66,6 +66,8 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_measure_surface
 #pragma weak mc33hip_label_components
 #pragma weak mc33hip_measure_components
+#pragma weak mc33hip_surface_topology
+#pragma weak mc33hip_component_topology
 _Static_assert(sizeof(mc33_component) == sizeof(mc33hip_component) && offsetof(mc33_component, area) == offsetof(mc33hip_component, area),
                "mc33_component and mc33hip_component are one layout");
 
@@ -1027,6 +1029,58 @@ int MC33_measure_components(MC33 *M, MC33_real iso, mc33_component *table, unsig
 	if (!nc)
 		return 0;
 	return mc33hip_measure_components(s->ctx, g->dV, cnt.nV, g->dT, cnt.nT, (const unsigned *)p->dL, (mc33hip_component *)table, capacity, &nc) == MC33HIP_OK ? 0 : -1;
+}
+
+/* --- extension: topology of an isosurface, from its triangle list in staging set 0 ------------------------------------------ */
+static mc33_private *topology_capable(MC33 *M) {
+	mc33_private *p = priv(M);
+	if (!p || p->nslab != 1 || !mc33hip_surface_topology || !mc33hip_component_topology || !mc33hip_label_components)
+		return 0;
+	return p;
+}
+
+int MC33_isosurface_topology(MC33 *M, MC33_real iso, mc33_topology *out) {
+	mc33_private *p = topology_capable(M);
+	if (!p || !out)
+		return -1;
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0];
+	mc33hip_counts cnt;
+	mc33hip_topology t;
+	memset(out, 0, sizeof *out);
+	M->iso = iso;
+	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK || mc33hip_surface_topology(s->ctx, g->dT, cnt.nT, cnt.nV, &t) != MC33HIP_OK)
+		return -1;
+	out->nV = (unsigned)t.nV; out->nT = (unsigned)t.nT;
+	out->referenced_vertices = t.referenced_vertices; out->edges = t.edges; out->boundary_edges = t.boundary_edges;
+	out->nonmanifold_edges = t.nonmanifold_edges; out->misoriented_edges = t.misoriented_edges;
+	out->degenerate_triangles = t.degenerate_triangles; out->boundary_loops = t.boundary_loops; out->components = t.components;
+	out->closed_components = t.closed_components; out->genus_sum = t.genus_sum; out->euler = t.euler;
+	out->closed = t.closed; out->manifold = t.manifold; out->oriented = t.oriented; out->genus_defined = t.genus_defined;
+	return 0;
+}
+
+int MC33_component_topology(MC33 *M, MC33_real iso, mc33_component_topology *table, unsigned capacity, unsigned *components) {
+	mc33_private *p = topology_capable(M);
+	if (components) *components = 0;
+	if (!p || (capacity && !table))
+		return -1;
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0];
+	mc33hip_counts cnt;
+	M->iso = iso;
+	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK || dev_room(s->ctx, &p->dL, &p->capL, cnt.nV, sizeof(unsigned)))
+		return -1;
+	unsigned long long nc = 0, nu = 0;
+	if (mc33hip_label_components(s->ctx, g->dT, cnt.nT, cnt.nV, (unsigned *)p->dL, &nc, &nu) != MC33HIP_OK)
+		return -1;
+	if (components) *components = (unsigned)nc;
+	if (capacity < nc)
+		return -2;
+	if (!nc)
+		return 0;
+	/* (mc33_component_topology has the members of struct mc33hip_component_topology, in its order) */
+	return mc33hip_component_topology(s->ctx, g->dT, cnt.nT, cnt.nV, (const unsigned *)p->dL, (struct mc33hip_component_topology *)table, capacity, &nc) == MC33HIP_OK ? 0 : -1;
 }
 
 void free_surface_memory(surface *S) { /* MC:84-92 */

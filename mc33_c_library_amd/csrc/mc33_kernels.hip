@@ -38,6 +38,8 @@
 //                   vertex; float values or palette colours (mc33_property.hip.h).
 //                   k_measure_* / k_cc_* - area, volume, moments, bounding box and connected components of a finished V, T pair;
 //                   a few doubles come back instead of the mesh (mc33_measure.hip.h).
+//                   k_topo_* - an edge table of a finished T in device memory: boundary, non-manifold and misoriented edges,
+//                   boundary loops, Euler number and genus, for the surface and per component (mc33_topology.hip.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -95,3 +97,4 @@ typedef float sample_t;
 #include "mc33_extract.hip.h"
 #include "mc33_property.hip.h"
 #include "mc33_measure.hip.h"
+#include "mc33_topology.hip.h"

@@ -1,0 +1,202 @@
+"""Surface topology (edges, boundary, Euler number, genus), the part that needs no GPU: the numpy oracle of the definition on the
+unmodified reference's five fixture meshes against the figures computed from them once and written down here, the new names in
+the headers and in every built library, the new kernels in the code object, and the host-logic build of mc33_capi.c, whose
+emulated device layer has no edge table."""
+import collections
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import fixtures as fx
+import measure_oracle as mo
+import topology_oracle as to
+from mc33_capi import MC33Lib, product_path
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+HIP_NAMES = ["mc33hip_surface_topology", "mc33hip_component_topology"]
+C_NAMES = ["MC33_isosurface_topology", "MC33_component_topology"]
+KERNELS = ["k_topo_clear", "k_topo_insert", "k_topo_classify", "k_topo_rows_triangles", "k_topo_rows_vertices", "k_topo_finish"]
+
+# fixture -> unique edges, used once, used more than twice, most uses of one edge, used twice in the same direction, degenerate
+# triangles, Euler number nV_ref - E + nT, boundary loops, boundary vertices that do not end exactly two boundary edges
+FIGURES = {
+    "sphere": (63084, 0, 0, 2, 0, 0, 2, 0, 0),
+    "blobs": (78246, 0, 0, 2, 0, 0, 54, 0, 0),
+    "sheet": (44508, 720, 0, 2, 0, 0, -4, 6, 0),
+    "noise": (157201, 5778, 14, 4, 0, 0, -5508, 314, 0),
+    "quant": (51777, 2603, 430, 8, 0, 0, -2054, 91, 72),
+}
+# fixture -> {(closed, Euler number of the component): how many}
+CHI = {
+    "sphere": {(True, 2): 1},
+    "blobs": {(True, 2): 27},
+    "sheet": {(False, -4): 1},
+    "noise": {(True, 2): 86, (False, 1): 65, (False, -5745): 1},
+    "quant": {(True, 2): 7, (False, 1): 6, (False, -2074): 1},
+}
+
+_cache = {}
+
+
+def figures(reflibs, name):
+    """(surface dict, component table, edge table) of the oracle on the reference's mesh of a fixture, made once"""
+    if name not in _cache:
+        field, iso, (nV, nT, _, _, _) = mo.FIXTURES[name]
+        data, r0, d = field()
+        s = reflibs["f32"].isosurface(data, iso, r0, d)
+        assert (s.nV, s.nT) == (nV, nT)
+        lab = mo.label_components(s.T, s.nV)[0]
+        e = to.EdgeTable(s.T, s.nV)
+        surf, tab = to.surface(s.T, s.nV, lab, e)
+        _cache[name] = (surf, tab, e, s.T)
+    return _cache[name]
+
+
+@pytest.mark.parametrize("name", list(mo.FIXTURES))
+def test_oracle_reproduces_the_table(reflibs, name):
+    surf, tab, e, T = figures(reflibs, name)
+    ends = np.bincount(np.concatenate([e.lo[e.boundary], e.hi[e.boundary]]))
+    got = (surf["edges"], surf["boundary_edges"], surf["nonmanifold_edges"], int(e.uses.max()), surf["misoriented_edges"], surf["degenerate_triangles"],
+           surf["euler"], surf["boundary_loops"], int(np.count_nonzero((ends != 0) & (ends != 2))))
+    print(name, got)
+    assert got == FIGURES[name]
+    assert surf["boundary_edges"] == mo.open_edges(T) == mo.FIXTURES[name][2][4]
+    nV, nT, ncomp, unref, _ = mo.FIXTURES[name][2]
+    assert (surf["nV"], surf["nT"], surf["components"], surf["referenced_vertices"]) == (nV, nT, ncomp, nV - unref)
+    assert (surf["closed"], surf["manifold"], surf["oriented"]) == (int(FIGURES[name][1] == 0), int(FIGURES[name][2] == 0), 1)
+
+
+@pytest.mark.parametrize("name", list(mo.FIXTURES))
+def test_oracle_per_component(reflibs, name):
+    surf, tab, e, T = figures(reflibs, name)
+    hist = collections.Counter((bool(r["boundary_edges"] == 0), int(r["euler"])) for r in tab)
+    assert dict(hist) == CHI[name]
+    # the columns add up to the surface's figures
+    for col in to.COUNTS:
+        assert int(tab[col].sum()) == surf[col], col
+    assert int(tab["nV"].sum()) == surf["referenced_vertices"] and int(tab["nT"].sum()) == surf["nT"]
+    assert int(tab["euler"].sum()) == surf["euler"]
+    assert surf["closed_components"] == sum(n for (closed, _), n in CHI[name].items() if closed)
+    assert np.all(np.diff(tab["root"].astype(np.int64)) > 0)
+    if name in ("sphere", "blobs", "sheet"):  # genus 0 everywhere: the sheet's (2 + 4 - 6) / 2
+        assert np.all(tab["genus"] == 0) and surf["genus_sum"] == 0 and surf["genus_defined"] == 1
+    else:  # the large component has non-manifold edges; every other one is a sphere or a disc
+        assert sorted(tab["genus"].tolist())[:2] == [-1, 0] and surf["genus_sum"] == 0 and surf["genus_defined"] == 0
+
+
+def test_oracle_on_small_meshes():
+    """a tetrahedron, the same with one triangle turned over, a torus of 3 x 3 quads, a strip with a degenerate triangle"""
+    tet = np.array([[0, 1, 2], [0, 3, 1], [1, 3, 2], [2, 3, 0]])
+    s, tab = to.surface(tet, 4, np.zeros(4, np.uint32))
+    assert (s["edges"], s["euler"], s["closed"], s["oriented"], s["genus_sum"], tab["genus"].tolist()) == (6, 2, 1, 1, 0, [0])
+    flipped = tet.copy()
+    flipped[1] = flipped[1, [1, 0, 2]]
+    s, tab = to.surface(flipped, 4, np.zeros(4, np.uint32))
+    assert (s["misoriented_edges"], s["oriented"], s["genus_defined"], tab["genus"].tolist()) == (3, 0, 0, [-1])
+    n, tris = 3, []
+    for i in range(n):
+        for j in range(n):
+            a, b, c, d = i * n + j, ((i + 1) % n) * n + j, ((i + 1) % n) * n + (j + 1) % n, i * n + (j + 1) % n
+            tris += [[a, b, c], [a, c, d]]
+    s, tab = to.surface(np.array(tris), 9, np.zeros(9, np.uint32))
+    assert (s["edges"], s["euler"], s["closed"], s["manifold"], s["oriented"], s["genus_sum"]) == (27, 0, 1, 1, 1, 1)
+    strip = np.array([[0, 1, 2], [2, 1, 3], [3, 4, 3], [7, 1, 2]])  # vertex 5 unreferenced, the last triangle invalid for nV = 6
+    s, tab = to.surface(strip, 6, np.array([0, 0, 0, 0, 0, 5], np.uint32))
+    assert (s["degenerate_triangles"], s["manifold"], s["referenced_vertices"], s["edges"], s["boundary_edges"], s["boundary_loops"]) == (1, 0, 5, 6, 4, 1)  # ({3, 4} is used twice: 3 -> 4 forward, 4 -> 3 backward, and 3 -> 3 is skipped)
+    assert s["euler"] == 5 - 6 + 3 and tab["genus"].tolist() == [-1] and tab["nT"].tolist() == [3]
+    s, tab = to.surface(np.zeros((0, 3), np.uint32), 6, np.arange(6))
+    assert tab.shape[0] == 0 and [s[k] for k in ("closed", "manifold", "oriented", "genus_defined", "euler", "edges")] == [1, 1, 1, 1, 0, 0]
+
+
+def test_new_names_are_declared():
+    hip = open(os.path.join(ROOT, "include", "mc33_hip.h")).read()
+    pub = open(os.path.join(ROOT, "include", "marching_cubes_33.h")).read()
+    for n in HIP_NAMES:
+        assert re.search(r"\bint %s\(mc33hip_ctx \*" % n, hip), n
+    for n in C_NAMES:
+        assert re.search(r"\bint %s\(MC33 \*" % n, pub), n
+    assert re.search(r"\} mc33hip_topology;", hip) and re.search(r"\bstruct mc33hip_component_topology \{", hip)
+    for t in ("mc33_topology", "mc33_component_topology"):
+        assert re.search(r"\} %s;" % t, pub), t
+    assert "pinched vertex" in hip
+    from mc33_c_library_amd import HIP_API, REFERENCE_API
+    assert set(HIP_NAMES) <= set(HIP_API) and set(C_NAMES) <= set(REFERENCE_API)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
+def test_every_library_exports_the_new_names(dtype):
+    for ortho, nneg in ((False, False), (True, False), (False, True), (True, True)):
+        path = product_path(dtype, ortho=ortho, nneg=nneg)
+        assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
+        syms = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
+        defined = set(line.split()[-1] for line in syms.splitlines() if line.split())
+        for n in HIP_NAMES + C_NAMES:
+            assert n in defined, "%s not exported by %s" % (n, os.path.basename(path))
+
+
+def test_topology_kernels_are_in_the_code_object():
+    from test_code_objects import kernel_metadata
+    ks = {k["pretty"].split("(")[0]: k for k in kernel_metadata(product_path("f32"))}
+    for name in KERNELS:
+        assert name in ks, (name, sorted(ks))
+        assert ks[name]["private_segment_fixed_size"] == 0 and ks[name]["vgpr_spill_count"] == 0, (name, ks[name])
+        assert ks[name]["vgpr_count"] <= 128, (name, ks[name])  # (two blocks of 256 per SIMD at least)
+
+
+def test_python_structs_match_the_header():
+    from mc33_c_library_amd.api import ComponentTopology, Topology
+    assert C.sizeof(Topology) == 12 * 8 + 8 + 4 * 4 and Topology.euler.offset == 96 and Topology.closed.offset == 104
+    assert C.sizeof(ComponentTopology) == 80 and ComponentTopology.edges.offset == 16 and ComponentTopology.genus.offset == 72
+    assert np.dtype(ComponentTopology).itemsize == to.COMPONENT.itemsize == 80
+    assert [to.COMPONENT.fields[n][1] for n in to.COMPONENT.names] == [np.dtype(ComponentTopology).fields[n][1] for n in to.COMPONENT.names]
+
+
+class CTopology(C.Structure):
+    _fields_ = [("nV", C.c_uint), ("nT", C.c_uint)] + \
+               [(n, C.c_ulonglong) for n in ("referenced_vertices", "edges", "boundary_edges", "nonmanifold_edges", "misoriented_edges", "degenerate_triangles",
+                                             "boundary_loops", "components", "closed_components", "genus_sum")] + \
+               [("euler", C.c_longlong)] + [(n, C.c_int) for n in ("closed", "manifold", "oriented", "genus_defined")]
+
+
+class CComponentTopology(C.Structure):
+    _fields_ = [("root", C.c_uint), ("nV", C.c_uint), ("nT", C.c_uint)] + [(n, C.c_ulonglong) for n in to.COUNTS] + [("euler", C.c_longlong), ("genus", C.c_int)]
+
+
+def bind_topology_api(lib):
+    L = lib.lib
+    M = C.POINTER(lib.MC33)
+    L.MC33_isosurface_topology.restype = C.c_int
+    L.MC33_isosurface_topology.argtypes = [M, lib.real, C.POINTER(CTopology)]
+    L.MC33_component_topology.restype = C.c_int
+    L.MC33_component_topology.argtypes = [M, lib.real, C.POINTER(CComponentTopology), C.c_uint, C.POINTER(C.c_uint)]
+
+
+@pytest.mark.parametrize("dtype", ["f32", "u16"])
+def test_host_logic_library_refuses(dtype):
+    """mc33_capi.c linked with the emulated device layer, which has neither entry point: the library still loads (they are weak
+    references), both functions return -1, and the object extracts as before."""
+    from mc33_emu import build_hostlogic
+    lib = MC33Lib(build_hostlogic(dtype), dtype)
+    bind_topology_api(lib)
+    L = lib.lib
+    data = fx.cos_field(20)[0] if dtype == "f32" else fx.cos_field_u16(20, 20, 20)
+    iso = 0.0 if dtype == "f32" else 30000.0
+    G, keep = lib.make_grid(data)
+    M = L.create_MC33(G)
+    assert M
+    try:
+        t, rows, n = CTopology(), (CComponentTopology * 4)(), C.c_uint(7)
+        assert L.MC33_isosurface_topology(M, lib.real(iso), C.byref(t)) == -1
+        assert L.MC33_component_topology(M, lib.real(iso), rows, 4, C.byref(n)) == -1 and n.value == 0
+        S = L.calculate_isosurface(M, lib.real(iso))
+        assert S and S.contents.nV > 0
+        L.free_surface_memory(S)
+    finally:
+        L.free_MC33(M)
+        L.free_memory_grd(G)
+        del keep
