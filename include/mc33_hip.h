@@ -68,7 +68,22 @@ const char *mc33hip_last_error(void);
  * this library keeps a pitched copy in HBM.
  *   upload_rows : F[k][j] row pointers exactly as _GRD.F holds them (rows may be separate mallocs,
  *                 reference MC33_util_grd.c:147-169), k counts resident planes
- *   adopt_device: use a caller-owned device buffer in place (no copy); pitch/slice in samples      */
+ *   adopt_device: use a caller-owned device buffer in place (no copy); pitch/slice in samples
+ *
+ * Layout of an adopted buffer: sample (x, y, k) of resident plane k at device_samples[k * slice + y * pitch + x], any
+ * pitch >= npx, any slice >= pitch * npy, any base address a sample may have.  The result never depends on the layout or on
+ * what the padding holds; the speed does:
+ *   - base, pitch and slice all multiples of 4 BYTES: 1- and 2-byte samples are classified a dword at a time (otherwise a
+ *     sample per lane and load);
+ *   - base, pitch and slice all multiples of 16 BYTES: the vertex pass stages rows in 16-byte chunks (otherwise every work
+ *     record loads its own samples).
+ *   (The library's own copy has both.)  Those dwords and chunks start at multiples of 4 / 16 bytes from the row's first sample and
+ *   may end behind its last one, inside the pitch.  READABLE EXTENT: every row, the last row of the last resident plane
+ *   included, must be readable from its first sample to the next 16-byte address boundary behind its last grid point or to
+ *   the end of its pitch, whichever comes first - at most 15 bytes more than the npx samples (the next 4-byte boundary where only the first
+ *   condition holds, nothing behind the last grid point where neither does).  Nothing else is read.
+ *   - EINVAL: pitch < npx, slice < pitch * npy, pitch > 0xFFFFFFFF samples, or 64 rows of pitch samples take more than
+ *     0xFFFFFFFF bytes (the sweep addresses a tile's rows with 32-bit offsets).                                             */
 int mc33hip_upload_rows(mc33hip_ctx *c, const void *const *const *F);
 int mc33hip_upload_contiguous(mc33hip_ctx *c, const void *host_samples);
 int mc33hip_adopt_device(mc33hip_ctx *c, const void *device_samples, size_t pitch, size_t slice);
@@ -197,7 +212,8 @@ int mc33hip_download_many(mc33hip_ctx *c, int n, void *const *host_dst, const vo
  * own: global planes [plane0, plane0 + nplanes), independent of desc.plane0 / npz_resident.  Orthogonal grids only.
  *   upload_rows       : F[k][j] row pointers, k counts the window's planes (F = _GRD.F + plane0); staged like mc33hip_upload_rows
  *   upload_contiguous : the window's planes back to back in host memory
- *   adopt_device      : a caller-owned device buffer used in place, pitch / slice in samples
+ *   adopt_device      : a caller-owned device buffer used in place, pitch / slice in samples (any pitch >= npx up to
+ *                       0xFFFFFFFF, any slice >= pitch * npy, any alignment; only grid points are read)
  *   drop              : detaches (and frees the library's copy)
  * Attaching again replaces the window.  All four wait for the context's stream first. */
 int mc33hip_property_upload_rows(mc33hip_ctx *c, const void *const *const *F, unsigned int plane0, unsigned int nplanes);

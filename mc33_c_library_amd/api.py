@@ -184,6 +184,24 @@ class SurfaceTopology:
         return "SurfaceTopology(%s)" % ", ".join("%s=%d" % (n, getattr(self, n)) for n in self.FIELDS)
 
 
+def _assert_readable(tensor, npx, whole_words):
+    """The readable extent mc33hip_adopt_device asks for (include/mc33_hip.h), checked on the last row of the last plane against
+    the tensor's storage (every other row is followed by memory of the same storage): its npx samples and, whole_words, what
+    follows them up to the next 4-byte (16-byte) boundary where base, pitch and slice are all multiples of 4 (16) bytes - never
+    beyond the pitch."""
+    sb = tensor.element_size()
+    row = tensor.data_ptr() + ((tensor.shape[0] - 1) * tensor.stride(0) + (tensor.shape[1] - 1) * tensor.stride(1)) * sb
+    end = row + npx * sb
+    if whole_words:
+        terms = (tensor.data_ptr(), tensor.stride(1) * sb, tensor.stride(0) * sb)
+        word = 16 if all(t % 16 == 0 for t in terms) else 4 if all(t % 4 == 0 for t in terms) else 1
+        end = min(row + tensor.stride(1) * sb, -(-end // word) * word)
+    st = tensor.untyped_storage()
+    assert end <= st.data_ptr() + st.nbytes(), \
+        "the last row of the buffer is read in whole 4- / 16-byte words (include/mc33_hip.h: readable extent): %d bytes behind " \
+        "its last sample are not part of the tensor's storage" % (end - st.data_ptr() - st.nbytes())
+
+
 def _check(lib, rc, allow=()):
     if rc != OK and rc not in allow:
         raise MC33Error(rc, lib.mc33hip_last_error().decode(errors="replace"))
@@ -192,7 +210,10 @@ def _check(lib, rc, allow=()):
 
 class DeviceGrid:
     """A grid (or a z-slab of one) resident in HBM as a torch tensor [planes, rows, pitch], plus the
-    extraction context working on it.  dtype float32 or uint16 (carried as torch.int16 bit patterns)."""
+    extraction context working on it.  dtype float32 or uint16 (carried as torch.int16 bit patterns).
+    The tensor is used in place with its strides: any stride(1) >= npx, any stride(0) >= stride(1) * rows, any storage offset
+    (include/mc33_hip.h, mc33hip_adopt_device: which alignment allows which kernel form, and what must be readable behind the
+    last row); npx: the grid's points per row when the tensor's rows are wider."""
 
     def __init__(self, tensor, nz_total=None, plane0=0, r0=(0.0, 0.0, 0.0), d=(1.0, 1.0, 1.0), npx=None):
         import torch
@@ -213,6 +234,8 @@ class DeviceGrid:
         self.tensor = tensor  # keeps the memory alive
         npz, npy, pitch = tensor.shape[0], tensor.shape[1], tensor.stride(1)
         npx = npx if npx is not None else tensor.shape[2]
+        assert 2 <= npx <= tensor.shape[2], "npx: the grid's points per row, at most the tensor's width"
+        _assert_readable(tensor, npx, True)
         desc = GridDesc(npx, npy, npz, plane0, (nz_total if nz_total is not None else npz - 1),
                         (C.c_double * 3)(*r0), (C.c_double * 3)(*d), sb, tensor.device.index)
         self.desc = desc
@@ -327,6 +350,7 @@ class DeviceGrid:
         assert tensor.is_cuda and tensor.dim() == 3 and tensor.stride(2) == 1, "need a device tensor [z, y, x]"
         assert tensor.dtype == self.tensor.dtype and tensor.device == self.device, "the property grid has the grid's dtype and device"
         assert tensor.shape[1] == self.desc.npy and tensor.shape[2] >= self.desc.npx
+        _assert_readable(tensor, self.desc.npx, False)  # (the property grid is read at grid points only)
         _check(self.lib, self.lib.mc33hip_property_adopt_device(self.ctx, C.c_void_p(tensor.data_ptr()), tensor.stride(1), tensor.stride(0),
                                                                 self.desc.plane0 if plane0 is None else int(plane0), tensor.shape[0]))
         self.property = tensor  # keeps the memory alive

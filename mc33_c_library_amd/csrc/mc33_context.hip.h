@@ -518,7 +518,13 @@ extern "C" int mc33hip_upload_rows(mc33hip_ctx *c, const void *const *const *F) 
 }
 
 extern "C" int mc33hip_adopt_device(mc33hip_ctx *c, const void *dptr, size_t pitch, size_t slice) {
-	if (!c || !dptr || pitch < c->desc.npx || slice < pitch * c->desc.npy) return MC33HIP_EINVAL;
+	if (!c || !dptr || pitch < c->desc.npx || slice < pitch * c->desc.npy || pitch > 0xFFFFFFFFull) return MC33HIP_EINVAL;
+	// (k_sweep addresses the 64 sample rows of a tile with 32-bit byte offsets from the tile's first row)
+	if ((uint64_t)pitch * sizeof(sample_t) * 64u > 0xFFFFFFFFull) {
+		set_err("pitch of %llu samples: the 64 rows of a tile (%llu bytes) do not fit 32-bit offsets", (unsigned long long)pitch,
+		        (unsigned long long)pitch * sizeof(sample_t) * 64u);
+		return MC33HIP_EINVAL;
+	}
 	int rc = use_device(c);
 	if (rc) return rc;
 	if (c->owns_grid) dev_release(&c->d_grid);

@@ -298,6 +298,10 @@ static void set_lane(SweepArgs &a, int q, const IsoLane &L, double iso) {
 
 // narrow samples are loaded as dwords when every row of the grid starts on a dword boundary (always true for the
 // library's own pitched copy; a caller's device buffer may have any pitch)
+// (The three terms are about aligned loads, not about the result: a dword is addressed from its row's first sample, so with a
+// base, pitch or slice that is no multiple of 4 bytes the same bytes would come from misaligned dword loads, which this device
+// serves - dropping the slice term leaves every surface of tests/test_gpu_layouts.py bit-identical, layout slice_odd included.
+// The terms keep the packed form to loads that are aligned on every device, and to one cache line each.)
 static bool sweep_packed(const mc33hip_ctx *c) {
 	return SWEEP_PACK > 1 && !c->sw.no_pack && ((uintptr_t)c->d_grid % 4u) == 0 && (c->pitch * sizeof(sample_t)) % 4u == 0 &&
 	       (c->slice * sizeof(sample_t)) % 4u == 0;
@@ -643,6 +647,8 @@ static int enqueue_emit(mc33hip_ctx *c, void *dV, void *dN, void *dT, uint64_t c
 	c->w->ctr_published = true;
 	// rows may be staged in 16-byte chunks when every row of the grid starts on a 16-byte boundary (always so for the library's
 	// own copy; a caller's device buffer may have any pitch: its records then load for themselves)
+	// (as in sweep_packed: chunks are addressed from the row's first sample, so the terms - the slice term too: a plane above the
+	// first starts at base + k * slice - keep the 16-byte loads aligned; without them the result is the same, bit for bit)
 	a.stage_rows = ((uintptr_t)c->d_grid % 16u) == 0 && (c->pitch * sizeof(sample_t)) % 16u == 0 && (c->slice * sizeof(sample_t)) % 16u == 0 &&
 	               !c->sw.no_stage;
 	// The triangle pass is fastest with a thread per record (C5, 14.4 M records: 16 384 / 32 768 / 65 536 blocks 392 / 363 /

@@ -30,8 +30,9 @@ struct emu_slab {
 };
 
 template <typename T>
-static int run(const T *data, uint32_t npx, uint32_t npy, uint32_t npz, const double *r0, const double *d, float iso,
+static int run(const T *data, uint32_t npx, uint32_t npy, uint32_t npz, uint64_t pitch, uint64_t slice, const double *r0, const double *d, float iso,
                emu_surface *out, const emu_slab *slab = nullptr) {
+	if (pitch < npx || pitch > 0xFFFFFFFFull || slice < pitch * npy) return -12;
 	memset(out, 0, sizeof *out);
 	Params P{};
 	P.nx = npx - 1; P.ny = npy - 1; P.nz = npz - 1;
@@ -48,7 +49,7 @@ static int run(const T *data, uint32_t npx, uint32_t npy, uint32_t npz, const do
 	if (d[0] != d[1] || d[1] != d[2]) { P.store_mode = 2; P.ca = (float)(d[2] / d[0]); P.cb = (float)(d[2] / d[1]); }
 	else { P.store_mode = (d[0] == 1 && r0[0] == 0 && r0[1] == 0 && r0[2] == 0) ? 0 : 1; P.ca = P.cb = 1; }
 	for (int k = 0; k < 3; k++) { P.O[k] = (float)r0[k]; P.D[k] = (float)d[k]; }
-	GridView<T> G{data, npx, 0, (uint64_t)npx * npy};
+	GridView<T> G{data, (uint32_t)pitch, 0, slice};  // (as mc33hip_adopt_device takes a buffer: any pitch >= npx, any slice >= pitch * npy)
 	Tables tab{mc33_lut, mc33_rule_words, &mc33_rule_index[0][0]};
 
 	const uint64_t nsegs = (uint64_t)(ze - P.zs) * P.ny * P.nseg;
@@ -187,29 +188,46 @@ static int run(const T *data, uint32_t npx, uint32_t npy, uint32_t npz, const do
 	return 0;
 }
 
+// `data` points at sample (0, 0, 0); pitch / slice in samples, as mc33hip_adopt_device takes them
+extern "C" int emu_isosurface_pitched_f32(const float *data, uint32_t npx, uint32_t npy, uint32_t npz, uint64_t pitch, uint64_t slice,
+                                          const double *r0, const double *d, float iso, emu_surface *out) {
+	return run<float>(data, npx, npy, npz, pitch, slice, r0, d, iso, out);
+}
+extern "C" int emu_isosurface_pitched_u16(const uint16_t *data, uint32_t npx, uint32_t npy, uint32_t npz, uint64_t pitch, uint64_t slice,
+                                          const double *r0, const double *d, float iso, emu_surface *out) {
+	return run<uint16_t>(data, npx, npy, npz, pitch, slice, r0, d, iso, out);
+}
 extern "C" int emu_isosurface_f32(const float *data, uint32_t npx, uint32_t npy, uint32_t npz, const double *r0,
                                   const double *d, float iso, emu_surface *out) {
-	return run<float>(data, npx, npy, npz, r0, d, iso, out);
+	return emu_isosurface_pitched_f32(data, npx, npy, npz, npx, (uint64_t)npx * npy, r0, d, iso, out);
 }
 extern "C" int emu_isosurface_u16(const uint16_t *data, uint32_t npx, uint32_t npy, uint32_t npz, const double *r0,
                                   const double *d, float iso, emu_surface *out) {
-	return run<uint16_t>(data, npx, npy, npz, r0, d, iso, out);
+	return emu_isosurface_pitched_u16(data, npx, npy, npz, npx, (uint64_t)npx * npy, r0, d, iso, out);
 }
 extern "C" void emu_free(emu_surface *s) { free(s->V); free(s->N); free(s->T); memset(s, 0, sizeof *s); }
 
-extern "C" int emu_slab_f32(const float *data, uint32_t npx, uint32_t npy, uint32_t npz, const double *r0, const double *d,
-                            float iso, const emu_slab *slab, emu_surface *out, unsigned long long *violations) {
+extern "C" int emu_slab_pitched_f32(const float *data, uint32_t npx, uint32_t npy, uint32_t npz, uint64_t pitch, uint64_t slice, const double *r0,
+                                    const double *d, float iso, const emu_slab *slab, emu_surface *out, unsigned long long *violations) {
 	g_violations = 0;
-	int rc = run<float>(data, npx, npy, npz, r0, d, iso, out, slab);
+	int rc = run<float>(data, npx, npy, npz, pitch, slice, r0, d, iso, out, slab);
 	*violations = g_violations;
 	return rc;
 }
-extern "C" int emu_slab_u16(const uint16_t *data, uint32_t npx, uint32_t npy, uint32_t npz, const double *r0, const double *d,
-                            float iso, const emu_slab *slab, emu_surface *out, unsigned long long *violations) {
+extern "C" int emu_slab_pitched_u16(const uint16_t *data, uint32_t npx, uint32_t npy, uint32_t npz, uint64_t pitch, uint64_t slice, const double *r0,
+                                    const double *d, float iso, const emu_slab *slab, emu_surface *out, unsigned long long *violations) {
 	g_violations = 0;
-	int rc = run<uint16_t>(data, npx, npy, npz, r0, d, iso, out, slab);
+	int rc = run<uint16_t>(data, npx, npy, npz, pitch, slice, r0, d, iso, out, slab);
 	*violations = g_violations;
 	return rc;
+}
+extern "C" int emu_slab_f32(const float *data, uint32_t npx, uint32_t npy, uint32_t npz, const double *r0, const double *d,
+                            float iso, const emu_slab *slab, emu_surface *out, unsigned long long *violations) {
+	return emu_slab_pitched_f32(data, npx, npy, npz, npx, (uint64_t)npx * npy, r0, d, iso, slab, out, violations);
+}
+extern "C" int emu_slab_u16(const uint16_t *data, uint32_t npx, uint32_t npy, uint32_t npz, const double *r0, const double *d,
+                            float iso, const emu_slab *slab, emu_surface *out, unsigned long long *violations) {
+	return emu_slab_pitched_u16(data, npx, npy, npz, npx, (uint64_t)npx * npy, r0, d, iso, slab, out, violations);
 }
 extern "C" unsigned long long emu_last_violations(void) { return g_violations; }
 

@@ -6,6 +6,7 @@ import subprocess
 
 import numpy as np
 
+import layouts
 from mc33_capi import ROOT, Surface
 from mc33_oracle import OSURF
 
@@ -56,32 +57,38 @@ class Emu:
         self.dtype = dtype
         self.np_dtype = np.float32 if dtype == "f32" else np.uint16
         self.lib = C.CDLL(build_emu())
-        self.fn = getattr(self.lib, "emu_isosurface_" + dtype)
+        self.fn = getattr(self.lib, "emu_isosurface_pitched_" + dtype)
         self.fn.restype = C.c_int
-        self.fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+        self.fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                             C.c_float, C.POINTER(OSURF)]
         self.lib.emu_free.argtypes = [C.POINTER(OSURF)]
-        self.slab_fn = getattr(self.lib, "emu_slab_" + dtype)
+        self.slab_fn = getattr(self.lib, "emu_slab_pitched_" + dtype)
         self.slab_fn.restype = C.c_int
-        self.slab_fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+        self.slab_fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                  C.c_float, C.POINTER(SLAB), C.POINTER(OSURF), C.POINTER(C.c_ulonglong)]
         self.lib.emu_last_violations.restype = C.c_ulonglong
 
-    def isosurface(self, data, iso, r0=None, d=None, slab=None):
+    def isosurface(self, data, iso, r0=None, d=None, slab=None, layout=None):
         """slab = (z_begin, z_end, ghost, id_base, plane_lo, plane_hi) emulates one rank of a z-slab run;
-        self.violations then holds the number of reads outside planes [plane_lo, plane_hi]."""
+        self.violations then holds the number of reads outside planes [plane_lo, plane_hi] (or outside the grid's rows).
+        layout = (pitch, slice, off) in samples: the grid is read from a flat array in that layout whose other samples hold
+        poison (tests/layouts.py), the way a caller's device buffer reaches mc33hip_adopt_device."""
         data = np.ascontiguousarray(data, dtype=self.np_dtype)
         nz, ny, nx = data.shape
+        pitch, slc, off = layout if layout is not None else (nx, nx * ny, 0)
+        if layout is not None:
+            data = layouts.place(data, layout, [iso])  # (the flat array; kept alive to the end of the call)
+        ptr = data.ctypes.data + off * data.dtype.itemsize
         r0a = (C.c_double * 3)(*(r0 if r0 is not None else (0.0, 0.0, 0.0)))
         da = (C.c_double * 3)(*(d if d is not None else (1.0, 1.0, 1.0)))
         s = OSURF()
         if slab is None:
-            rc = self.fn(data.ctypes.data, nx, ny, nz, r0a, da, C.c_float(iso), C.byref(s))
+            rc = self.fn(ptr, nx, ny, nz, pitch, slc, r0a, da, C.c_float(iso), C.byref(s))
             assert rc == 0, "emulator failed: %d" % rc
             self.violations = self.lib.emu_last_violations()
         else:
             viol = C.c_ulonglong(0)
-            rc = self.slab_fn(data.ctypes.data, nx, ny, nz, r0a, da, C.c_float(iso), C.byref(SLAB(*slab)), C.byref(s), C.byref(viol))
+            rc = self.slab_fn(ptr, nx, ny, nz, pitch, slc, r0a, da, C.c_float(iso), C.byref(SLAB(*slab)), C.byref(s), C.byref(viol))
             assert rc == 0, "emulator failed: %d" % rc
             self.violations = viol.value
 

@@ -72,6 +72,45 @@ def test_z_slabs_reproduce_whole_volume_and_stay_in_window(emus, case, cuts):
     assert bits_equal(np.concatenate(Vs), whole.V) and bits_equal(np.concatenate(Ns), whole.N)
 
 
+LAYOUT_GRIDS = {
+    "noise": lambda: ("f32", fx.noise_f32(0, 11, shape=(6, 70, 300)), 0.05),
+    "quant": lambda: ("f32", fx.noise_quant(0, 3, L=3, shape=(6, 70, 300)), 0.0),
+    "u16": lambda: ("u16", fx.noise_u16(0, 2, 7, shape=(6, 70, 300)), 3.0),
+}
+
+
+@pytest.mark.parametrize("layout", ["pady", "slice_odd", "padx_odd", "all"])
+@pytest.mark.parametrize("grid", list(LAYOUT_GRIDS))
+def test_pitch_and_slice_of_an_adopted_buffer(emus, oracles, grid, layout):
+    """The grid read through GridView from a flat array with pitch > npx, slice > pitch * npy and an offset, everything that is
+    not a grid point holding poison (tests/layouts.py): the surface is the oracle's bit for bit and no read leaves the rows."""
+    import layouts
+    dt, data, iso = LAYOUT_GRIDS[grid]()
+    lay = layouts.layout(layout, data.shape, data.dtype.itemsize)
+    s =emus[dt].isosurface(data, iso, layout=lay)
+    assert emus[dt].violations == 0
+    assert s.nV > 10000 and _same(s, oracles[dt].isosurface(data, iso))
+
+
+def test_z_slabs_of_an_adopted_buffer(emus):
+    """One z-slab case of test_z_slabs_reproduce_whole_volume_and_stay_in_window on layout `all`"""
+    import layouts
+    em, data, iso, cuts = emus["f32"], fx.noise_quant(0, 5, shape=(48, 24, 40)), 0.0, (7, 8, 30)
+    lay = layouts.layout("all", data.shape, data.dtype.itemsize)
+    whole = em.isosurface(data, iso)
+    nzt = data.shape[0] - 1
+    bounds = [0] + list(cuts) + [nzt]
+    Vs, Ns, Ts, base = [], [], [], 0
+    for zb, ze in zip(bounds[:-1], bounds[1:]):
+        ghost = 1 if zb else 0
+        s = em.isosurface(data, iso, slab=(zb, ze, ghost, base, max(zb - ghost - 1, 0), min(ze + 1, nzt)), layout=lay)
+        assert em.violations == 0
+        Vs.append(s.V); Ns.append(s.N); Ts.append(s.T)
+        base += s.nV
+    assert np.array_equal(np.concatenate(Ts), whole.T)
+    assert bits_equal(np.concatenate(Vs), whole.V) and bits_equal(np.concatenate(Ns), whole.N)
+
+
 def test_tested_records_for_every_sign_index(emus):
     """254 sign indices x 3000 random corner-value sets (ties included): the record `k_cells` builds for an ambiguous
     interior cell from the pattern offset and the pattern-info table equals the one the generic plan builds; the face /
