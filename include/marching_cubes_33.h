@@ -215,6 +215,28 @@ int MC33_isosurface_topology(MC33 *extractor, MC33_real isovalue, mc33_topology 
 int MC33_component_topology(MC33 *extractor, MC33_real isovalue, mc33_component_topology *table, unsigned capacity,
                             unsigned *components);
 
+/* extension (not in the reference): keep or drop whole components of an isosurface on the GPU, so that only the kept rows cross
+ * the link.  MC33_select_components is the ONE place where components are chosen - host C, no GPU: from the n rows of
+ * MC33_measure_components (and, for closed_only, the n rows of MC33_component_topology; NULL otherwise) it writes the roots of the
+ * rows to keep into roots[n], ascending, and returns how many; -1 on bad arguments (a null filter, null arrays with n > 0,
+ * closed_only without topology rows).  A row passes when nT >= min_triangles AND area >= min_area AND |volume| >= min_abs_volume
+ * AND (closed_only == 0 OR its boundary_edges == 0).  With largest > 0 only the `largest` passing rows with the most triangles
+ * stay; ties go to the smaller root.  A zeroed filter keeps every row.  The area and volume columns are summed with atomics and
+ * differ in their last bits from call to call: a threshold that close to a component's value may fall either way.
+ * MC33_calculate_filtered_isosurface extracts the surface into device memory, colours it when a property grid and a colour map
+ * are set, labels and measures its components there (and their topology, only when closed_only is set: the edge table takes
+ * 16 bytes x 4 nT of device memory), selects, compacts on the device - vertices in ascending order, triangles in their order,
+ * indices renumbered; a vertex no triangle names is always dropped (the definition is in mc33_hip.h, mc33hip_compact_components)
+ * - and downloads the kept rows into a caller-owned `surface` like calculate_isosurface's.  *kept / *dropped count components
+ * (either may be NULL).  Without colours surface.color is DefaultColorMC.  The extractor's iso, nV, nT and memoryfault are left as
+ * calculate_isosurface leaves them for a surface of the returned size.  NULL on failure, for a null filter and for an extractor
+ * spread over several devices. */
+typedef struct { unsigned min_triangles; double min_area, min_abs_volume; unsigned largest; int closed_only; } mc33_component_filter;
+int MC33_select_components(const mc33_component *table, const mc33_component_topology *topo /* NULL unless closed_only */,
+                           unsigned n, const mc33_component_filter *f, unsigned *roots /* n */);   /* returns how many, -1 on bad arguments */
+surface *MC33_calculate_filtered_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_component_filter *f, unsigned *kept,
+                                            unsigned *dropped);
+
 /* ---- inclined grids (reference header :186-191) ---------------------------------------------------------
  * c = A b (transposed == 0) or A^T b for a 3x3 matrix; _multTSA_bf assumes an upper triangular A.  A caller may
  * point mult_Abf at either; calculate_isosurface looks at the pointer when it is called and runs the matching

@@ -337,6 +337,52 @@ int mc33hip_component_topology(mc33hip_ctx *c, const void *dT, unsigned long lon
                                struct mc33hip_component_topology *host_table, unsigned long long capacity,
                                unsigned long long *components);
 
+/* --- keep or drop components of a finished mesh, on the device (no counterpart in the reference) ----------------------------------
+ * An order-preserving, deterministic stream compaction of V (nV x 3 MC33_real), N (nV x 3 float), T (nT x 3 unsigned, id base 0)
+ * and n_attr <= 2 arrays of one 4-byte word per vertex (a colour, a sampled property, anything) by component; label[nV] is what
+ * mc33hip_label_components made for this T and nV; roots: a HOST array of n_roots component roots, in any order, duplicates
+ * allowed.  Everything is an integer or a row moved as it is: no tolerance anywhere, and two calls on the same inputs return the
+ * same bytes.
+ *   valid triangle   its three indices are below nV;            referenced[v]  a valid triangle names v
+ *   selected[v]      (label[v] is one of the roots) XOR (invert != 0)
+ *   keep[v]          referenced[v] AND selected[v];             new[v]         the number of kept u < v
+ *   kept triangle    valid, and keep[T[i][0]] holds
+ *   oV[new[v]], oN[new[v]], oAttr[k][new[v]] = the bytes of row v for every kept v (ascending);  oT = the kept triangles in their
+ *   original order, each index replaced by new[...];  oMap[nV] (optional) = new[v] for kept v, 0xFFFFFFFF otherwise - it lets a
+ *   caller carry further arrays of its own.
+ * A vertex no triangle names is always dropped: a compaction with every root selected (n_roots 0, invert 1) removes the
+ * unreferenced vertices and nothing else.  A root that is not the root of a component with at least one triangle selects nothing
+ * and is no error.  The call fills nV_out, nT_out and components_kept (the kept v with label[v] == v); nT == 0 gives 0, 0 and
+ * success.
+ *   MC33HIP_ERUNTIME   an invalid triangle is counted and left out, and so is a kept triangle that names a vertex that is not
+ *                      kept (labels that are not those of this T); the count is in mc33hip_last_error, in the words of the
+ *                      measuring calls, the outputs are otherwise complete, nothing outside the arrays is read or written.
+ *   MC33HIP_ECAPACITY  capV < nV_out or capT < nT_out: the needed sizes are in the struct and no output array is touched (null
+ *                      outputs with capacity 0 are the size query; nV and nT are always enough).
+ *   MC33HIP_EINVAL     a null pointer where a size is not zero, nV or nT above 2^32-1, n_attr > 2, a root >= nV, an output byte
+ *                      range (capV / capT rows, nV words of oMap) that meets an input byte range - the compaction is not in
+ *                      place; the check is made on the host, on addresses.
+ * The call enqueues on the context's stream behind whatever is on it, waits, and brings the three counts to the host, as
+ * mc33hip_measure_components does.  Scratch: 6 bytes per vertex and a word per 1024 vertices and triangles, with the context
+ * until mc33hip_destroy. */
+typedef struct {
+	const void *V, *N, *T;                    /* in: the mesh (device)                                  */
+	const unsigned *label;                    /* in: nV words (device)                                  */
+	unsigned long long nV, nT;
+	const void *attr[2];                      /* in: n_attr arrays of nV 4-byte words (device)          */
+	unsigned n_attr;
+	int invert;
+	const unsigned *roots;                    /* in: n_roots words (HOST)                               */
+	unsigned long long n_roots;
+	void *oV, *oN, *oT;                       /* out: capV, capV, capT rows (device)                    */
+	void *oAttr[2];                           /* out: capV words each                                   */
+	unsigned *oMap;                           /* out: nV words, or NULL                                 */
+	unsigned long long capV, capT;
+	unsigned long long nV_out, nT_out, components_kept; /* filled by the call                           */
+} mc33hip_compaction;
+
+int mc33hip_compact_components(mc33hip_ctx *c, mc33hip_compaction *a);
+
 /* Plain device allocations on the context's device (for language bindings). */
 int mc33hip_device_alloc(mc33hip_ctx *c, void **dptr, size_t bytes);
 int mc33hip_device_free(mc33hip_ctx *c, void *dptr);

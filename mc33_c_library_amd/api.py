@@ -54,6 +54,20 @@ class ComponentTopology(C.Structure):
                [("euler", C.c_longlong), ("genus", C.c_int)]
 
 
+class Compaction(C.Structure):
+    """mc33hip_compaction (include/mc33_hip.h)"""
+    _fields_ = [("V", C.c_void_p), ("N", C.c_void_p), ("T", C.c_void_p), ("label", C.c_void_p), ("nV", C.c_ulonglong), ("nT", C.c_ulonglong),
+                ("attr", C.c_void_p * 2), ("n_attr", C.c_uint), ("invert", C.c_int), ("roots", C.c_void_p), ("n_roots", C.c_ulonglong),
+                ("oV", C.c_void_p), ("oN", C.c_void_p), ("oT", C.c_void_p), ("oAttr", C.c_void_p * 2), ("oMap", C.c_void_p),
+                ("capV", C.c_ulonglong), ("capT", C.c_ulonglong),
+                ("nV_out", C.c_ulonglong), ("nT_out", C.c_ulonglong), ("components_kept", C.c_ulonglong)]
+
+
+class ComponentFilter(C.Structure):
+    """mc33_component_filter (include/marching_cubes_33.h); a zeroed one keeps every component"""
+    _fields_ = [("min_triangles", C.c_uint), ("min_area", C.c_double), ("min_abs_volume", C.c_double), ("largest", C.c_uint), ("closed_only", C.c_int)]
+
+
 HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_last_error", "mc33hip_upload_rows",
            "mc33hip_upload_contiguous", "mc33hip_adopt_device", "mc33hip_set_stream", "mc33hip_count",
            "mc33hip_emit", "mc33hip_extract", "mc33hip_last_timing", "mc33hip_download",
@@ -63,7 +77,7 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_property_upload_rows", "mc33hip_property_upload_contiguous", "mc33hip_property_adopt_device", "mc33hip_property_drop",
            "mc33hip_sample_property", "mc33hip_color_vertices", "mc33hip_download_enqueue",
            "mc33hip_measure_surface", "mc33hip_label_components", "mc33hip_measure_components",
-           "mc33hip_surface_topology", "mc33hip_component_topology"]
+           "mc33hip_surface_topology", "mc33hip_component_topology", "mc33hip_compact_components"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -71,7 +85,8 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "read_grd", "read_grd_binary", "read_scanfiles", "read_raw_file", "read_dat_file", "calculate_isosurfaces", "MC33_grid_changed",
                  "MC33_set_property_grid", "MC33_set_color_map",
                  "MC33_measure_isosurface", "MC33_measure_isosurfaces", "MC33_measure_components",
-                 "MC33_isosurface_topology", "MC33_component_topology"]
+                 "MC33_isosurface_topology", "MC33_component_topology",
+                 "MC33_select_components", "MC33_calculate_filtered_isosurface"]
 
 
 class MC33Error(RuntimeError):
@@ -142,6 +157,8 @@ def load_library(dtype="f32"):
     lib.mc33hip_measure_components.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V, V, C.c_ulonglong, P(C.c_ulonglong)]
     lib.mc33hip_surface_topology.argtypes = [V, V, C.c_ulonglong, C.c_ulonglong, P(Topology)]
     lib.mc33hip_component_topology.argtypes = [V, V, C.c_ulonglong, C.c_ulonglong, V, V, C.c_ulonglong, P(C.c_ulonglong)]
+    lib.mc33hip_compact_components.argtypes = [V, P(Compaction)]
+    lib.MC33_select_components.argtypes = [V, V, C.c_uint, P(ComponentFilter), V]
     _libs[dtype] = lib
     return lib
 
@@ -508,6 +525,75 @@ class DeviceGrid:
         t = Topology()
         _check(self.lib, self.lib.mc33hip_surface_topology(self.ctx, C.c_void_p(T.data_ptr()), cnt.nT, cnt.nV, C.byref(t)))
         return SurfaceTopology(t)
+
+    # -- keep or drop components of a finished mesh, on the device (mc33_hip.h: mc33hip_compact_components) ------------------------
+    def select_components(self, table, topo_table=None, **criteria):
+        """The roots of the rows of `table` (measure_components) that pass the criteria - min_triangles, min_area, min_abs_volume,
+        largest, closed_only (needs topo_table: component_topology) - ascending, as a numpy uint32 array.  The rule is the
+        library's MC33_select_components (include/marching_cubes_33.h): there is no second implementation."""
+        import numpy as np
+        f = ComponentFilter(**criteria)
+        table = np.ascontiguousarray(table, dtype=np.dtype(Component))
+        if topo_table is not None:
+            topo_table = np.ascontiguousarray(topo_table, dtype=np.dtype(ComponentTopology))
+            assert topo_table.shape[0] == table.shape[0]
+        roots = np.zeros(max(table.shape[0], 1), np.uint32)
+        n = self.lib.MC33_select_components(C.c_void_p(table.ctypes.data) if table.shape[0] else None,
+                                            C.c_void_p(topo_table.ctypes.data) if topo_table is not None else None, table.shape[0], C.byref(f),
+                                            C.c_void_p(roots.ctypes.data))
+        if n < 0:
+            raise ValueError("MC33_select_components refused its arguments (closed_only needs topo_table)")
+        return roots[:n].copy()
+
+    def compact_components(self, V, N, T, labels, roots, invert=False, attrs=()):
+        """Keeps the components of the mesh V, N, T (device tensors, as extract() returns them) whose root is in `roots` - or, with
+        invert, all others - and drops every vertex no triangle names: (V2, N2, T2, attrs2, vmap, components_kept), exact-size
+        device tensors in the order of the input, T2 renumbered; attrs: up to two device tensors of one 4-byte word per vertex,
+        compacted alongside; vmap (int32 [nV], the uint32 words new[v], 0xFFFFFFFF where v was dropped) carries further arrays.
+        labels: what label_components returned for T."""
+        import numpy as np
+        import torch
+        self._vertex_rows(V)
+        self._triangle_rows(T)
+        nV = V.shape[0]
+        assert N.is_cuda and N.is_contiguous() and N.dtype == torch.float32 and tuple(N.shape) == (nV, 3)
+        assert labels.is_cuda and labels.is_contiguous() and labels.numel() == nV and labels.element_size() == 4
+        attrs = tuple(attrs)
+        for a in attrs:
+            assert a.is_cuda and a.is_contiguous() and a.numel() == nV and a.element_size() == 4, "an attribute is one 4-byte word per vertex"
+        roots = np.ascontiguousarray(np.asarray(roots).reshape(-1), dtype=np.uint32)
+        a = Compaction()
+        a.V, a.N, a.T, a.label, a.nV, a.nT = V.data_ptr(), N.data_ptr(), T.data_ptr(), labels.data_ptr(), nV, T.shape[0]
+        for k, x in enumerate(attrs[:2]):
+            a.attr[k] = x.data_ptr()
+        a.n_attr, a.invert = len(attrs), int(bool(invert))
+        a.roots, a.n_roots = (roots.ctypes.data if roots.size else None), roots.size
+        _check(self.lib, self.lib.mc33hip_compact_components(self.ctx, C.byref(a)), allow=(ECAPACITY,))  # null outputs: the size query
+        nV2, nT2 = int(a.nV_out), int(a.nT_out)
+        V2 = torch.empty((max(nV2, 1), 3), dtype=V.dtype, device=self.device)
+        N2 = torch.empty((max(nV2, 1), 3), dtype=torch.float32, device=self.device)
+        T2 = torch.empty((max(nT2, 1), 3), dtype=torch.int32, device=self.device)
+        attrs2 = [torch.empty((max(nV2, 1),), dtype=x.dtype, device=self.device) for x in attrs]
+        vmap = torch.empty((max(nV, 1),), dtype=torch.int32, device=self.device)
+        a.oV, a.oN, a.oT, a.oMap, a.capV, a.capT = V2.data_ptr(), N2.data_ptr(), T2.data_ptr(), vmap.data_ptr(), nV2, nT2
+        for k, x in enumerate(attrs2):
+            a.oAttr[k] = x.data_ptr()
+        _check(self.lib, self.lib.mc33hip_compact_components(self.ctx, C.byref(a)))
+        return V2[:nV2], N2[:nV2], T2[:nT2], [x[:nV2] for x in attrs2], vmap[:nV], int(a.components_kept)
+
+    def extract_filtered(self, iso, rng=None, with_property=False, **criteria):
+        """extract, label, measure (and component_topology, only for closed_only), select_components(**criteria), compact - the
+        whole surface never leaves the device.  Returns (V, N, T, kept, dropped) - components kept and dropped - and, with
+        with_property, the attached property grid's value at the kept vertices as a sixth element."""
+        got = self.extract(iso, rng, with_property)
+        V, N, T = got[0], got[1], got[2]
+        labels = self.label_components(T, V.shape[0])[0]
+        table = self.measure_components(V, T, labels)
+        topo = self.component_topology(T, V.shape[0], labels) if criteria.get("closed_only") else None
+        roots = self.select_components(table, topo, **criteria)
+        V2, N2, T2, attrs2, _, kept = self.compact_components(V, N, T, labels, roots, attrs=(got[4],) if with_property else ())
+        out = (V2, N2, T2, kept, table.shape[0] - kept)
+        return out + (attrs2[0],) if with_property else out
 
     def probe_read(self, reps=10):
         """A plain read of the resident grid (nothing to do with an extraction): (best ms, median ms, bytes)."""

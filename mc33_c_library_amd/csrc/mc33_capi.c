@@ -68,6 +68,7 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_measure_components
 #pragma weak mc33hip_surface_topology
 #pragma weak mc33hip_component_topology
+#pragma weak mc33hip_compact_components
 _Static_assert(sizeof(mc33_component) == sizeof(mc33hip_component) && offsetof(mc33_component, area) == offsetof(mc33hip_component, area),
                "mc33_component and mc33hip_component are one layout");
 
@@ -1081,6 +1082,129 @@ int MC33_component_topology(MC33 *M, MC33_real iso, mc33_component_topology *tab
 		return 0;
 	/* (mc33_component_topology has the members of struct mc33hip_component_topology, in its order) */
 	return mc33hip_component_topology(s->ctx, g->dT, cnt.nT, cnt.nV, (const unsigned *)p->dL, (struct mc33hip_component_topology *)table, capacity, &nc) == MC33HIP_OK ? 0 : -1;
+}
+
+/* --- extension: keep or drop components of an isosurface ------------------------------------------------------------------------
+ * The one selection rule (include/marching_cubes_33.h): host C, no GPU. */
+struct sel_row { unsigned nT, root; };
+static int sel_by_size(const void *a, const void *b) { /* most triangles first, ties to the smaller root */
+	const struct sel_row *x = (const struct sel_row *)a, *y = (const struct sel_row *)b;
+	if (x->nT != y->nT) return x->nT > y->nT ? -1 : 1;
+	return x->root < y->root ? -1 : x->root > y->root;
+}
+static int sel_by_root(const void *a, const void *b) {
+	const unsigned x = *(const unsigned *)a, y = *(const unsigned *)b;
+	return x < y ? -1 : x > y;
+}
+
+int MC33_select_components(const mc33_component *table, const mc33_component_topology *topo, unsigned n, const mc33_component_filter *f, unsigned *roots) {
+	if (!f || (n && (!table || !roots)) || (f->closed_only && !topo))
+		return -1;
+	unsigned m = 0;
+	for (unsigned k = 0; k != n; k++) {
+		const double w = table[k].volume < 0 ? -table[k].volume : table[k].volume;
+		if (table[k].nT >= f->min_triangles && table[k].area >= f->min_area && w >= f->min_abs_volume && (!f->closed_only || topo[k].boundary_edges == 0))
+			roots[m++] = k; /* (the row for now) */
+	}
+	if (f->largest && m > f->largest) {
+		struct sel_row *r = (struct sel_row *)malloc((size_t)m * sizeof *r);
+		if (!r)
+			return -1;
+		for (unsigned k = 0; k != m; k++) { r[k].nT = table[roots[k]].nT; r[k].root = table[roots[k]].root; }
+		qsort(r, m, sizeof *r, sel_by_size);
+		m = f->largest;
+		for (unsigned k = 0; k != m; k++) roots[k] = r[k].root;
+		free(r);
+	} else
+		for (unsigned k = 0; k != m; k++) roots[k] = table[roots[k]].root;
+	if (m > 1) /* (n == 0 may come with roots == NULL) */
+		qsort(roots, m, sizeof *roots, sel_by_root);
+	return (int)m;
+}
+
+/* the surface of `iso` into staging set 0, its colours, labels, tables -> the roots to keep -> compacted into staging set 1 ->
+ * the kept rows into a caller-owned surface */
+static surface *filtered_surface(mc33_private *p, MC33_real iso, const mc33_component_filter *f, unsigned *kept, unsigned *dropped) {
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0], *h = &s->set[1];
+	mc33hip_counts cnt;
+	const int col = coloured(p);
+	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK)
+		return 0;
+	if (col && cnt.nV) {
+		p->nan_color = DefaultColorMC;
+		if (enqueue_colors(s, g, cnt.nV) != MC33HIP_OK)
+			return 0;
+	}
+	if (dev_room(s->ctx, &p->dL, &p->capL, cnt.nV, sizeof(unsigned)))
+		return 0;
+	unsigned long long nc = 0, nu = 0;
+	if (mc33hip_label_components(s->ctx, g->dT, cnt.nT, cnt.nV, (unsigned *)p->dL, &nc, &nu) != MC33HIP_OK)
+		return 0;
+	mc33_component *table = (mc33_component *)malloc((size_t)(nc ? nc : 1) * sizeof *table);
+	mc33_component_topology *topo = f->closed_only ? (mc33_component_topology *)malloc((size_t)(nc ? nc : 1) * sizeof *topo) : 0;
+	unsigned *roots = (unsigned *)malloc((size_t)(nc ? nc : 1) * sizeof *roots);
+	surface *S = 0;
+	int nk = -1;
+	unsigned long long n2 = nc;
+	if (table && roots && (topo || !f->closed_only) &&
+	    (!nc || mc33hip_measure_components(s->ctx, g->dV, cnt.nV, g->dT, cnt.nT, (const unsigned *)p->dL, (mc33hip_component *)table, nc, &n2) == MC33HIP_OK) &&
+	    (!nc || !topo ||
+	     mc33hip_component_topology(s->ctx, g->dT, cnt.nT, cnt.nV, (const unsigned *)p->dL, (struct mc33hip_component_topology *)topo, nc, &n2) == MC33HIP_OK))
+		nk = MC33_select_components(table, topo, (unsigned)nc, f, roots);
+	if (nk >= 0) {
+		mc33hip_compaction a;
+		memset(&a, 0, sizeof a);
+		a.V = g->dV; a.N = g->dN; a.T = g->dT; a.label = (const unsigned *)p->dL;
+		a.nV = cnt.nV; a.nT = cnt.nT;
+		a.roots = roots; a.n_roots = (unsigned long long)nk;
+		if (col && cnt.nV) { a.attr[0] = g->dC; a.n_attr = 1; }
+		int rc = MC33HIP_ECAPACITY;
+		for (int attempt = 0; attempt != 2 && rc == MC33HIP_ECAPACITY; attempt++) { /* with the set as it is; grown to the sizes that came back */
+			if (attempt && (staging_room(s, h, a.nV_out, a.nT_out) || (a.n_attr && dev_room(s->ctx, &h->dC, &h->capC, a.nV_out, sizeof(int))))) {
+				rc = MC33HIP_ENOMEM;
+				break;
+			}
+			a.oV = h->dV; a.oN = h->dN; a.oT = h->dT; a.oAttr[0] = h->dC;
+			a.capV = a.n_attr && h->capC < h->capV ? h->capC : h->capV;
+			a.capT = h->capT;
+			rc = mc33hip_compact_components(s->ctx, &a);
+		}
+		if (rc == MC33HIP_OK) {
+			mc33hip_counts out;
+			memset(&out, 0, sizeof out);
+			out.nV = a.nV_out; out.nT = a.nT_out;
+			S = surface_from_staging(p, h, &out, iso, 0);
+			if (S) {
+				if (kept) *kept = (unsigned)a.components_kept;
+				if (dropped) *dropped = (unsigned)(nc - a.components_kept);
+			}
+		}
+	}
+	free(table); free(topo); free(roots);
+	return S;
+}
+
+surface *MC33_calculate_filtered_isosurface(MC33 *M, MC33_real iso, const mc33_component_filter *f, unsigned *kept, unsigned *dropped) {
+	mc33_private *p = priv(M);
+	if (kept) *kept = 0;
+	if (dropped) *dropped = 0;
+	if (!p || !f || p->nslab != 1 || !mc33hip_compact_components || !mc33hip_label_components || !mc33hip_measure_components || !mc33hip_component_topology ||
+	    !mc33hip_color_vertices)
+		return 0;
+	M->nT = M->nV = 0;
+	M->memoryfault = 0;
+	M->iso = iso;
+	surface *S = filtered_surface(p, iso, f, kept, dropped);
+	if (!S) {
+		M->memoryfault = 1;
+		return 0;
+	}
+	if (S->nV) { /* as calculate_isosurface leaves the public prefix */
+		M->T = S->T; M->V = S->V; M->N = S->N; M->color = S->color;
+		M->nT = S->nT; M->capt = S->capt; M->capv = S->capv;
+	}
+	return S;
 }
 
 void free_surface_memory(surface *S) { /* MC:84-92 */

@@ -40,6 +40,8 @@
 //                   a few doubles come back instead of the mesh (mc33_measure.hip.h).
 //                   k_topo_* - an edge table of a finished T in device memory: boundary, non-manifold and misoriented edges,
 //                   boundary loops, Euler number and genus, for the surface and per component (mc33_topology.hip.h).
+//                   k_filt_* - keep or drop whole components of a finished V, N, T: flags, two exclusive scans, two copying passes;
+//                   the rows keep their order (mc33_filter.hip.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -98,3 +100,4 @@ typedef float sample_t;
 #include "mc33_property.hip.h"
 #include "mc33_measure.hip.h"
 #include "mc33_topology.hip.h"
+#include "mc33_filter.hip.h"

@@ -37,8 +37,10 @@ struct MeasureState {       // scratch of these passes: on the context from the 
 	mc33hip_component *d_table;
 	uint64_t table_cap;
 	struct TopoState *topo;  // scratch of the topology passes (mc33_topology.hip.h), made by the first of them
+	struct FilterState *filt;  // scratch of the compaction (mc33_filter.hip.h), likewise
 };
 static void topo_destroy(MeasureState *m);
+static void filt_destroy(MeasureState *m);
 
 constexpr uint32_t CC_TILE = 1024u;  // vertices per block of k_cc_count / k_cc_rank: 256 lanes x 4
 
@@ -494,6 +496,7 @@ static void meas_destroy(mc33hip_ctx *c) {
 	MeasureState *m = c->meas;
 	if (!m) return;
 	topo_destroy(m);
+	filt_destroy(m);
 	dev_release(&m->d_out); dev_release(&m->d_part); dev_release(&m->d_flags); dev_release(&m->d_rank); dev_release(&m->d_bsum); dev_release(&m->d_table);
 	if (m->h_out) (void)hipHostFree(m->h_out);
 	free(m);
