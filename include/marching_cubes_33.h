@@ -237,6 +237,21 @@ int MC33_select_components(const mc33_component *table, const mc33_component_top
 surface *MC33_calculate_filtered_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_component_filter *f, unsigned *kept,
                                             unsigned *dropped);
 
+/* extension (not in the reference): a smoothed isosurface.  The integer grids of CT and MRI give staircase surfaces; Taubin's
+ * lambda | mu smoothing - `iterations` times a pass with factor lambda in (0, 1] followed by one with mu in [-1, 0], every vertex
+ * moved by the factor times (the mean of its edge neighbours - itself) - removes the steps without shrinking the surface.
+ * pin_boundary != 0 leaves the vertices of open edges (the surface's rim on the grid's faces) where they are; a vertex without
+ * neighbours never moves.  The exact order of operations is in mc33_hip.h (mc33hip_smooth_surface).
+ * MC33_calculate_smoothed_isosurface extracts the surface into device memory, colours it from the UNSMOOTHED vertices when a
+ * property grid and a colour map are set, smooths in place, recomputes N from the smoothed triangles (the sum of their cross
+ * products per vertex, normalised; the stored winding decides the sign, in the _nneg flavours too) and downloads into a
+ * caller-owned `surface` like calculate_isosurface's: T, nV and nT are unchanged.  The extractor's iso, nV, nT and memoryfault are
+ * left as calculate_isosurface leaves them.  NULL for a null struct and for refused parameters (lambda, mu outside their ranges
+ * or NaN, iterations above 1000) - the extractor is not touched then -, for an extractor spread over several devices, and on
+ * failure (memoryfault 1). */
+typedef struct { unsigned iterations; double lambda, mu; int pin_boundary; } mc33_smoothing;
+surface *MC33_calculate_smoothed_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_smoothing *s);
+
 /* ---- inclined grids (reference header :186-191) ---------------------------------------------------------
  * c = A b (transposed == 0) or A^T b for a 3x3 matrix; _multTSA_bf assumes an upper triangular A.  A caller may
  * point mult_Abf at either; calculate_isosurface looks at the pointer when it is called and runs the matching

@@ -383,6 +383,57 @@ typedef struct {
 
 int mc33hip_compact_components(mc33hip_ctx *c, mc33hip_compaction *a);
 
+/* --- smooth a finished mesh on the device: Taubin's lambda | mu passes, new normals (no counterpart in the reference) -------------
+ * V (nV x 3 MC33_real) and T (nT x 3 unsigned, id base 0) in device memory, as for mc33hip_label_components; any mesh, inclined
+ * grids and every sample type included.  N is not read.  T is not changed: what mc33hip_surface_topology and the component calls
+ * reported stays true.  Everything is a gather in a fixed order: two calls on the same inputs return the same bytes.
+ *   valid triangle   its three indices are below nV.  Every side a -> b with a != b of a valid triangle, in the order T0 -> T1,
+ *                    T1 -> T2, T2 -> T0, is one use of the edge {a, b} (the words of the topology block).  An invalid triangle is
+ *                    counted and contributes nothing - nothing outside V is read; the call still completes and returns
+ *                    MC33HIP_ERUNTIME with the count in mc33hip_last_error, in the words of the measuring calls.
+ *   nb(v)            the distinct w for which {v, w} has at least one use, in ascending order;  deg(v) = |nb(v)|
+ *   boundary(v)      some edge {v, w} has exactly one use
+ *   fixed(v)         deg(v) == 0, or pin_boundary != 0 and boundary(v)
+ *   one pass with factor f, P -> P', rows of MC33_real: for a fixed v row v is copied as it is; otherwise per axis a, in IEEE
+ *                    double, nothing fused:
+ *                      s = (double)P[w1][a];  s = s + (double)P[wk][a] for k = 2 .. deg, in ascending w;  m = s / (double)deg
+ *                      L = m - (double)P[v][a];  P'[v][a] = (MC33_real)((double)P[v][a] + f * L)
+ *                    All neighbours are read from P, never from P' (a Jacobi update).
+ *   one iteration    pass(lambda) followed by pass(mu).  A factor equal to 0 skips its pass - the rows stay as they are bit for
+ *                    bit; it is not p + 0 * L, which turns -0 into +0.  With iterations == 0 oV holds V's bytes.
+ *   normals          from the final positions Q.  inc(v): the valid triangles that name v, ascending, each once even if it names v
+ *                    twice.  g_i = u x w with p_k = (double)Q[T[i][k]], u = p1 - p0, w = p2 - p0, that is
+ *                    (u.y*w.z - u.z*w.y, u.z*w.x - u.x*w.z, u.x*w.y - u.y*w.x);  n = the g_i added in that order, starting from
+ *                    the first;  len = sqrt((n.x*n.x + n.y*n.y) + n.z*n.z);  oN[v][a] = (float)(n[a] / len) when len > 0 and
+ *                    finite, otherwise - and for empty inc(v) - (0, 0, 0).  The stored winding decides the sign: with the
+ *                    reference's winding this agrees with the emitted N, and so it does with mc33hip_set_normal_neg on, which
+ *                    exchanges two indices and negates N.
+ *   NaN propagates; nothing is special-cased.
+ * The call fills max_degree, isolated_vertices (deg 0), boundary_vertices (whether pinned or not) and invalid_triangles.
+ * mc33hip_vertex_normals is the normals alone, of V as it is.
+ *   MC33HIP_EINVAL (checked on the host, nothing is written): a null pointer where the size is not zero (oN of the struct may be
+ *                    NULL: no normals); nV or nT above 2^32-1; lambda outside (0, 1], mu outside [-1, 0], or a NaN; iterations
+ *                    above 1000; oV meeting V other than oV == V (in place), oV or oN meeting any other array of the call.
+ *   MC33HIP_ENOMEM   the scratch cannot be had - or nT is above 715 827 882: the rows of the lists begin at 32-bit offsets.
+ *   nT == 0 is success: oV holds V's bytes, oN is zeros, the four counts are 0 apart from isolated_vertices = nV.
+ * Both calls enqueue on the context's stream behind whatever is on it, wait, and bring the four integers to the host, as
+ * mc33hip_compact_components does.  Scratch, with the context until mc33hip_destroy: 9 bytes and one row of MC33_real (12; 24 in
+ * libMC33_f64) per vertex, 24 bytes per triangle (mc33hip_vertex_normals: 9 per vertex, 12 per triangle), a word per 1024
+ * vertices.  The list of the normals is built in the arrays of the adjacency when the passes are through. */
+typedef struct {
+	const void *V, *T;  unsigned long long nV, nT;      /* in (device) */
+	unsigned iterations;  double lambda, mu;  int pin_boundary;
+	void *oV;           /* out: nV x 3 MC33_real; may be exactly V (in place), otherwise must not meet V, T */
+	float *oN;          /* out: nV x 3, or NULL */
+	unsigned long long max_degree, isolated_vertices /* deg 0 */, boundary_vertices, invalid_triangles;   /* filled */
+} mc33hip_smoothing;
+int mc33hip_smooth_surface(mc33hip_ctx *c, mc33hip_smoothing *a);
+int mc33hip_vertex_normals(mc33hip_ctx *c, const void *dV, unsigned long long nV, const void *dT, unsigned long long nT, float *oN);
+/* Measurement aid: hipEvent times of the context's last mc33hip_smooth_surface / mc33hip_vertex_normals, recorded only at timing
+ * level 2 (mc33hip_set_timing) - the adjacency build, the normals, and the first *passes <= 64 passes (pass_ms[capacity]); zeros
+ * otherwise. */
+int mc33hip_smooth_timing(mc33hip_ctx *c, float *adjacency_ms, float *normals_ms, float *pass_ms, unsigned capacity, unsigned *passes);
+
 /* Plain device allocations on the context's device (for language bindings). */
 int mc33hip_device_alloc(mc33hip_ctx *c, void **dptr, size_t bytes);
 int mc33hip_device_free(mc33hip_ctx *c, void *dptr);

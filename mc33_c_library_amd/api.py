@@ -68,6 +68,20 @@ class ComponentFilter(C.Structure):
     _fields_ = [("min_triangles", C.c_uint), ("min_area", C.c_double), ("min_abs_volume", C.c_double), ("largest", C.c_uint), ("closed_only", C.c_int)]
 
 
+class Smoothing(C.Structure):
+    """mc33hip_smoothing (include/mc33_hip.h)"""
+    _fields_ = [("V", C.c_void_p), ("T", C.c_void_p), ("nV", C.c_ulonglong), ("nT", C.c_ulonglong),
+                ("iterations", C.c_uint), ("lam", C.c_double), ("mu", C.c_double), ("pin_boundary", C.c_int),
+                ("oV", C.c_void_p), ("oN", C.c_void_p),
+                ("max_degree", C.c_ulonglong), ("isolated_vertices", C.c_ulonglong), ("boundary_vertices", C.c_ulonglong),
+                ("invalid_triangles", C.c_ulonglong)]
+
+
+class SurfaceSmoothing(C.Structure):
+    """mc33_smoothing (include/marching_cubes_33.h)"""
+    _fields_ = [("iterations", C.c_uint), ("lam", C.c_double), ("mu", C.c_double), ("pin_boundary", C.c_int)]
+
+
 HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_last_error", "mc33hip_upload_rows",
            "mc33hip_upload_contiguous", "mc33hip_adopt_device", "mc33hip_set_stream", "mc33hip_count",
            "mc33hip_emit", "mc33hip_extract", "mc33hip_last_timing", "mc33hip_download",
@@ -77,7 +91,8 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_property_upload_rows", "mc33hip_property_upload_contiguous", "mc33hip_property_adopt_device", "mc33hip_property_drop",
            "mc33hip_sample_property", "mc33hip_color_vertices", "mc33hip_download_enqueue",
            "mc33hip_measure_surface", "mc33hip_label_components", "mc33hip_measure_components",
-           "mc33hip_surface_topology", "mc33hip_component_topology", "mc33hip_compact_components"]
+           "mc33hip_surface_topology", "mc33hip_component_topology", "mc33hip_compact_components",
+           "mc33hip_smooth_surface", "mc33hip_vertex_normals", "mc33hip_smooth_timing"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -86,7 +101,7 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "MC33_set_property_grid", "MC33_set_color_map",
                  "MC33_measure_isosurface", "MC33_measure_isosurfaces", "MC33_measure_components",
                  "MC33_isosurface_topology", "MC33_component_topology",
-                 "MC33_select_components", "MC33_calculate_filtered_isosurface"]
+                 "MC33_select_components", "MC33_calculate_filtered_isosurface", "MC33_calculate_smoothed_isosurface"]
 
 
 class MC33Error(RuntimeError):
@@ -158,6 +173,9 @@ def load_library(dtype="f32"):
     lib.mc33hip_surface_topology.argtypes = [V, V, C.c_ulonglong, C.c_ulonglong, P(Topology)]
     lib.mc33hip_component_topology.argtypes = [V, V, C.c_ulonglong, C.c_ulonglong, V, V, C.c_ulonglong, P(C.c_ulonglong)]
     lib.mc33hip_compact_components.argtypes = [V, P(Compaction)]
+    lib.mc33hip_smooth_surface.argtypes = [V, P(Smoothing)]
+    lib.mc33hip_vertex_normals.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V]
+    lib.mc33hip_smooth_timing.argtypes = [V, P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint, P(C.c_uint)]
     lib.MC33_select_components.argtypes = [V, V, C.c_uint, P(ComponentFilter), V]
     _libs[dtype] = lib
     return lib
@@ -594,6 +612,57 @@ class DeviceGrid:
         V2, N2, T2, attrs2, _, kept = self.compact_components(V, N, T, labels, roots, attrs=(got[4],) if with_property else ())
         out = (V2, N2, T2, kept, table.shape[0] - kept)
         return out + (attrs2[0],) if with_property else out
+
+    # -- smooth a finished mesh on the device (mc33_hip.h: mc33hip_smooth_surface) -------------------------------------------------
+    def smooth(self, V, T, iterations=10, lam=0.5, mu=-0.53, pin_boundary=True, normals=True, out=None):
+        """Taubin's lambda | mu smoothing of the mesh V [n, 3], T [m, 3] (device tensors, as extract() returns them): `iterations`
+        times a pass with factor lam, then one with mu; pin_boundary leaves the vertices of open edges where they are.  Returns
+        (V2, N2, info): the smoothed vertices - in `out` when given, which may be V itself (in place) -, the normals recomputed
+        from them (None with normals=False) and a dict of max_degree, isolated_vertices, boundary_vertices, invalid_triangles.
+        T is not changed.  Raises MC33Error(ERUNTIME) when a triangle names a vertex >= n (the outputs are complete without it)."""
+        import torch
+        self._vertex_rows(V)
+        self._triangle_rows(T)
+        nV = V.shape[0]
+        if out is None:
+            out = torch.empty_like(V)
+        self._vertex_rows(out)
+        assert out.dtype == V.dtype and out.shape[0] == nV and out.device == V.device
+        N2 = torch.empty((nV, 3), dtype=torch.float32, device=self.device) if normals else None
+        a = Smoothing()
+        a.V, a.T, a.nV, a.nT = V.data_ptr(), T.data_ptr(), nV, T.shape[0]
+        a.iterations, a.lam, a.mu, a.pin_boundary = int(iterations), float(lam), float(mu), int(bool(pin_boundary))
+        a.oV, a.oN = out.data_ptr(), (N2.data_ptr() if normals else None)
+        _check(self.lib, self.lib.mc33hip_smooth_surface(self.ctx, C.byref(a)))
+        return out, N2, {k: int(getattr(a, k)) for k in ("max_degree", "isolated_vertices", "boundary_vertices", "invalid_triangles")}
+
+    def vertex_normals(self, V, T):
+        """Normals of the mesh V, T recomputed from its triangles - per vertex the sum of the cross products of the triangles
+        that name it, normalised; the stored winding decides the sign: a float32 tensor [n, 3]."""
+        import torch
+        self._vertex_rows(V)
+        self._triangle_rows(T)
+        N2 = torch.empty((V.shape[0], 3), dtype=torch.float32, device=self.device)
+        _check(self.lib, self.lib.mc33hip_vertex_normals(self.ctx, C.c_void_p(V.data_ptr()), V.shape[0], C.c_void_p(T.data_ptr()), T.shape[0],
+                                                         C.c_void_p(N2.data_ptr())))
+        return N2
+
+    def extract_smoothed(self, iso, rng=None, with_property=False, **smoothing):
+        """extract, then smooth(**smoothing) in place - the surface never leaves the device.  Returns (V, N, T, Counts) with the
+        smoothed vertices and their recomputed normals (the extracted N with normals=False) and, with with_property, the attached
+        property grid's value at the UNSMOOTHED vertices as a fifth element."""
+        got = self.extract(iso, rng, with_property)
+        V, N, T, cnt = got[:4]
+        V2, N2, _ = self.smooth(V, T, out=V, **smoothing)
+        out = (V2, N2 if N2 is not None else N, T, cnt)
+        return out + (got[4],) if with_property else out
+
+    def smooth_timing(self):
+        """hipEvent times of the last smooth / vertex_normals after set_timing(2): (adjacency ms, normals ms, [ms per pass])."""
+        adj, nrm, n = C.c_float(), C.c_float(), C.c_uint()
+        ms = (C.c_float * 64)()
+        _check(self.lib, self.lib.mc33hip_smooth_timing(self.ctx, C.byref(adj), C.byref(nrm), ms, 64, C.byref(n)))
+        return adj.value, nrm.value, [ms[k] for k in range(n.value)]
 
     def probe_read(self, reps=10):
         """A plain read of the resident grid (nothing to do with an extraction): (best ms, median ms, bytes)."""

@@ -69,6 +69,7 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_surface_topology
 #pragma weak mc33hip_component_topology
 #pragma weak mc33hip_compact_components
+#pragma weak mc33hip_smooth_surface
 _Static_assert(sizeof(mc33_component) == sizeof(mc33hip_component) && offsetof(mc33_component, area) == offsetof(mc33hip_component, area),
                "mc33_component and mc33hip_component are one layout");
 
@@ -1196,6 +1197,48 @@ surface *MC33_calculate_filtered_isosurface(MC33 *M, MC33_real iso, const mc33_c
 	M->memoryfault = 0;
 	M->iso = iso;
 	surface *S = filtered_surface(p, iso, f, kept, dropped);
+	if (!S) {
+		M->memoryfault = 1;
+		return 0;
+	}
+	if (S->nV) { /* as calculate_isosurface leaves the public prefix */
+		M->T = S->T; M->V = S->V; M->N = S->N; M->color = S->color;
+		M->nT = S->nT; M->capt = S->capt; M->capv = S->capv;
+	}
+	return S;
+}
+
+/* --- extension: a smoothed isosurface -----------------------------------------------------------------------------------------
+ * The surface of `iso` into staging set 0, its colours from the vertices as they were extracted, the Taubin passes in place,
+ * the normals from the smoothed positions, then the download: T, nV and nT are those of calculate_isosurface. */
+surface *MC33_calculate_smoothed_isosurface(MC33 *M, MC33_real iso, const mc33_smoothing *sm) {
+	mc33_private *p = priv(M);
+	if (!p || !sm || p->nslab != 1 || !mc33hip_smooth_surface || !mc33hip_color_vertices)
+		return 0;
+	if (!(sm->lambda > 0.0 && sm->lambda <= 1.0) || !(sm->mu >= -1.0 && sm->mu <= 0.0) || sm->iterations > 1000u)
+		return 0; /* (what mc33hip_smooth_surface refuses, before anything is extracted) */
+	M->nT = M->nV = 0;
+	M->memoryfault = 0;
+	M->iso = iso;
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0];
+	mc33hip_counts cnt;
+	surface *S = 0;
+	int rc = extract_geometry(p, g, iso, &cnt);
+	if (rc == MC33HIP_OK && coloured(p) && cnt.nV) {
+		p->nan_color = DefaultColorMC;
+		rc = enqueue_colors(s, g, cnt.nV);
+	}
+	if (rc == MC33HIP_OK && cnt.nV) {
+		mc33hip_smoothing a;
+		memset(&a, 0, sizeof a);
+		a.V = g->dV; a.T = g->dT; a.nV = cnt.nV; a.nT = cnt.nT;
+		a.iterations = sm->iterations; a.lambda = sm->lambda; a.mu = sm->mu; a.pin_boundary = sm->pin_boundary;
+		a.oV = g->dV; a.oN = (float *)g->dN;
+		rc = mc33hip_smooth_surface(s->ctx, &a);
+	}
+	if (rc == MC33HIP_OK)
+		S = surface_from_staging(p, g, &cnt, iso, 0);
 	if (!S) {
 		M->memoryfault = 1;
 		return 0;

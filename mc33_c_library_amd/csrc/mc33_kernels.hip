@@ -42,6 +42,8 @@
 //                   boundary loops, Euler number and genus, for the surface and per component (mc33_topology.hip.h).
 //                   k_filt_* - keep or drop whole components of a finished V, N, T: flags, two exclusive scans, two copying passes;
 //                   the rows keep their order (mc33_filter.hip.h).
+//                   k_sm_* - Taubin smoothing of a finished V over the adjacency of T, a CSR list made on the device, and vertex
+//                   normals recomputed from the triangles; k_sm_pass is its hot path (mc33_smooth.hip.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -101,3 +103,4 @@ typedef float sample_t;
 #include "mc33_measure.hip.h"
 #include "mc33_topology.hip.h"
 #include "mc33_filter.hip.h"
+#include "mc33_smooth.hip.h"
