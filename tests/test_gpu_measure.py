@@ -82,7 +82,9 @@ def check_table(label, got, want, ab, wb, totals=None):
         assert np.array_equal(got[col], want[col]), "%s: column %s differs in %d rows" % (label, col, np.count_nonzero(got[col] != want[col]))
     assert np.all(np.diff(got["root"].astype(np.int64)) > 0)
     ea, ew = np.abs(got["area"] - want["area"]), np.abs(got["volume"] - want["volume"])
-    print("%s: %d components; worst area diff / bound %.3g, volume %.3g" % (label, got.shape[0], float(np.max(ea / ab, initial=0.0)), float(np.max(ew / wb, initial=0.0))))
+    def worst(e, b):  # (for the printout only; a row whose terms are all 0 has the bound 0)
+        return float(np.max(np.divide(e, b, out=np.where(e > 0, np.inf, 0.0), where=b > 0), initial=0.0))
+    print("%s: %d components; worst area diff / bound %.3g, volume %.3g" % (label, got.shape[0], worst(ea, ab), worst(ew, wb)))
     assert np.all(ea <= ab) and np.all(ew <= wb)
     if totals is not None:  # the columns add up to the surface's totals
         check_sum(label + " sum of areas", mo.fsum(got["area"]), totals.area, totals.area_bound)

@@ -1,5 +1,5 @@
 """The topology figures of include/mc33_hip.h (mc33hip_surface_topology, mc33hip_component_topology) restated in
-numpy: np.unique over the 64-bit edge keys lo << 32 | hi, a plain union-find over the boundary edges.  T and nV only; integers
+numpy: np.unique over the 64-bit edge keys lo << 32 | hi, minimum propagation over the boundary edges (a plain union-find beside it, to hold it against).  T and nV only; integers
 only.  numpy only."""
 import numpy as np
 
@@ -35,8 +35,42 @@ class EdgeTable:
         self.misoriented = (self.uses == 2) & (self.fwd != 1)
 
 
+def loop_labels(lo, hi, nV):
+    """(labels int64 [nV], rounds): label[v] = the smallest vertex connected to v through the edges lo - hi, by minimum propagation
+    over the edges with pointer jumping between the rounds, until nothing changes (as measure_oracle.label_components does over
+    triangles).  At the fixed point both ends of every edge carry one label, no label exceeds its vertex and labels only travel
+    inside a connected set: the label is the set's smallest vertex.  Hooking the old label's own entry makes whole sets merge in
+    a round, so the rounds grow with the logarithm of a loop's length, not with the length."""
+    lo, hi = np.asarray(lo, np.int64), np.asarray(hi, np.int64)
+    lab = np.arange(nV, dtype=np.int64)
+    rounds = 0
+    while lo.size:
+        rounds += 1
+        m = np.minimum(lab[lo], lab[hi])
+        new = lab.copy()
+        for ends in (lo, hi):
+            np.minimum.at(new, ends, m)
+            np.minimum.at(new, lab[ends], m)  # (the old label's own entry: hooks the whole set, not the vertex alone)
+        while True:  # pointer jumping
+            nn = new[new]
+            if np.array_equal(nn, new):
+                break
+            new = nn
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    return lab, rounds
+
+
 def loop_roots(lo, hi, nV):
-    """the smallest vertex of every connected set of the graph with the edges lo - hi (a plain union-find, smaller root wins)"""
+    """the smallest vertex of every connected set of the graph with the edges lo - hi; tests/test_mesh_pieces_cpu.py holds it
+    against loop_roots_plain"""
+    lo, hi = np.asarray(lo, np.int64), np.asarray(hi, np.int64)
+    return np.unique(loop_labels(lo, hi, nV)[0][np.concatenate([lo, hi])])
+
+
+def loop_roots_plain(lo, hi, nV):
+    """the same by a plain union-find, smaller root wins: one Python step per edge, for meshes of a few thousand edges"""
     parent = np.arange(nV, dtype=np.int64)
 
     def find(x):
