@@ -252,6 +252,22 @@ surface *MC33_calculate_filtered_isosurface(MC33 *extractor, MC33_real isovalue,
 typedef struct { unsigned iterations; double lambda, mu; int pin_boundary; } mc33_smoothing;
 surface *MC33_calculate_smoothed_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_smoothing *s);
 
+/* extension (not in the reference): a simplified isosurface.  A 1024^3 extraction has tens of millions of triangles where a viewer,
+ * a file or a remote client wants a few hundred thousand.  Vertex clustering: the vertices inside one cell of a lattice - origin
+ * the grid's r0, cell[a] grid spacings d[a] wide along axis a; any positive finite number, 2 halves the resolution - become one
+ * vertex, the mean of the cell's vertices (mode 0) or the first of them, which stays on the isosurface (mode 1); triangles that
+ * lose a corner that way go and, with drop_duplicates != 0, so do triangles that repeat another; the winding of the others is
+ * kept.  The exact definition is in mc33_hip.h (mc33hip_simplify_surface).
+ * MC33_calculate_simplified_isosurface extracts the surface into device memory, colours it from the extracted vertices when a
+ * property grid and a colour map are set (a merged vertex has the colour of the first of its cell), clusters on the device,
+ * recomputes N from the simplified triangles (the stored winding decides the sign, in the _nneg flavours too) and downloads the
+ * kept rows into a caller-owned `surface` like calculate_isosurface's.  The extractor's iso, nV, nT and memoryfault are left as
+ * calculate_isosurface leaves them for a surface of the returned size.  NULL for a null struct and for refused parameters (a cell
+ * component that is not finite and > 0, a mode that is neither) - the extractor is not touched then -, for an inclined grid, for an
+ * extractor spread over several devices, and on failure (memoryfault 1). */
+typedef struct { double cell[3]; int mode; int drop_duplicates; } mc33_simplification;   /* cell in units of the grid spacing d */
+surface *MC33_calculate_simplified_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_simplification *s);
+
 /* ---- inclined grids (reference header :186-191) ---------------------------------------------------------
  * c = A b (transposed == 0) or A^T b for a 3x3 matrix; _multTSA_bf assumes an upper triangular A.  A caller may
  * point mult_Abf at either; calculate_isosurface looks at the pointer when it is called and runs the matching

@@ -434,6 +434,69 @@ int mc33hip_vertex_normals(mc33hip_ctx *c, const void *dV, unsigned long long nV
  * otherwise. */
 int mc33hip_smooth_timing(mc33hip_ctx *c, float *adjacency_ms, float *normals_ms, float *pass_ms, unsigned capacity, unsigned *passes);
 
+/* --- simplify a finished mesh on the device: vertex clustering on a lattice (no counterpart in the reference) ---------------------
+ * V (nV x 3 MC33_real) and T (nT x 3 unsigned, id base 0) in device memory, as for mc33hip_label_components, and n_attr <= 2
+ * arrays of one 4-byte word per vertex.  The vertices that fall into one cell of an axis-aligned lattice become one vertex;
+ * triangles that lose a corner that way go, and so do, when asked, triangles that repeat another.  Integer atomics and exclusive
+ * sums decide everything: the result is an exact function of the input, nothing has a tolerance, and two calls on the same inputs
+ * return the same bytes.  Arithmetic is IEEE double, nothing fused.
+ *   valid triangle   its three indices are below nV.  An invalid triangle is counted and contributes nothing; nothing outside V
+ *                    is read.
+ *   referenced[v]    a valid triangle names v.  Only referenced vertices take part in anything below; an unreferenced vertex is
+ *                    dropped, as in the compaction.
+ *   key of v         per axis a:  g = ((double)V[v][a] - origin[a]) / cell[a];  k_a = floor(g), but k_a = 0 when !(g >= 0) - a
+ *                    NaN too - and k_a = 2097151 when g >= 2097152;  t_a = g - (double)k_a, clamped to [0, 1] and 0 for a NaN;
+ *                    key = k_x | k_y << 21 | k_z << 42.  A referenced vertex clamped on any axis counts once in clamped_vertices:
+ *                    a statistic, not an error.
+ *   cluster          the referenced vertices that share one key.  rep(v): the smallest index in v's cluster;  clusters: how many
+ *                    there are;  max_cluster: the largest member count.
+ *   image            of valid triangle i: (rep(T0), rep(T1), rep(T2)).  Collapsed when two of the three are equal - counted in
+ *                    collapsed_triangles.  With drop_duplicates != 0, images that are not collapsed and consist of the same three
+ *                    representatives, in any order and either winding, are duplicates: of each such set the triangle with the
+ *                    smallest i survives, the others count in duplicate_triangles.
+ *   survivors        the valid triangles that are neither collapsed nor dropped as duplicates;  nT_out: how many.
+ *   kept cluster     a survivor names its representative;  new[r]: the number of kept representatives below r;  nV_out: how many.
+ *   oT               the survivors in their original order, each index replaced by new[rep(.)], the winding as stored.
+ *   oV[new[r]]       MC33HIP_SIMPLIFY_FIRST: the bytes of row r of V - the vertex stays on the isosurface; -0 and NaN payloads
+ *                    are preserved.  MC33HIP_SIMPLIFY_MEAN, per axis a, over ALL members of the cluster (n of them):
+ *                      q = (unsigned long long)floor(t_a * 4294967296.0);   S_a = the sum of the q, an exact 64-bit integer in
+ *                      any order of addition (at most (2^32 - 1) members x 2^32 < 2^64);
+ *                      m = (double)S_a / ((double)n * 4294967296.0);   oV = (MC33_real)(origin[a] + cell[a] * ((double)k_a + m))
+ *                    The quantisation moves the mean by less than cell[a] * 2^-32.
+ *   oAttr[j][new[r]] = attr[j][r], the representative's word.
+ *   oMap[v]          new[rep(v)] for a referenced v of a kept cluster, otherwise 0xFFFFFFFF (optional).
+ *   oN               when not NULL, exactly what mc33hip_vertex_normals(oV, nV_out, oT, nT_out) writes: the incidence and normal
+ *                    passes of the smoothing block run on the outputs.
+ *   MC33HIP_ERUNTIME   invalid triangles: the count is in mc33hip_last_error, in the words of the measuring calls; the outputs
+ *                      are complete without them.
+ *   MC33HIP_ECAPACITY  capV < nV_out or capT < nT_out: every filled field is valid and no output array is touched (null outputs
+ *                      with capacity 0 are the size query; nV and nT are always enough).
+ *   MC33HIP_EINVAL     checked on the host, nothing is written: a null pointer where a size is not zero (oN and oMap may be
+ *                      NULL); nV or nT above 2^32-1; n_attr > 2; a mode that is neither; a cell component that is not finite and
+ *                      > 0; an origin component that is not finite; an output byte range (capV / capT rows, nV words of oMap)
+ *                      that meets an input range or another output range - the call is not in place.
+ *   MC33HIP_ENOMEM     the scratch cannot be had.
+ *   nT == 0 is success with every count 0 (oMap, when given, is all 0xFFFFFFFF).
+ * The call enqueues on the context's stream behind whatever is on it, waits, and brings the eight integers to the host, as
+ * mc33hip_compact_components does; with oN it waits a second time, behind the normals.  Scratch, with the context until
+ * mc33hip_destroy: 14 bytes per vertex and a cluster table of 40 bytes per slot, a power of two >= 2 nV slots (80 to 160 bytes per
+ * vertex); 1 byte per triangle and, with drop_duplicates, a table of 4-byte words, a power of two >= 2 nT of them (8 to 16 bytes
+ * per triangle); a word per 1024 vertices and triangles; with oN the scratch of mc33hip_vertex_normals for the OUTPUT's sizes. */
+#define MC33HIP_SIMPLIFY_MEAN 0
+#define MC33HIP_SIMPLIFY_FIRST 1
+typedef struct {
+	const void *V, *T;  unsigned long long nV, nT;   /* in (device): nV x 3 MC33_real, nT x 3 unsigned, id base 0 */
+	const void *attr[2]; unsigned n_attr;            /* in: <= 2 arrays of nV 4-byte words (device) */
+	double origin[3], cell[3];                       /* the lattice */
+	int mode;                                        /* MC33HIP_SIMPLIFY_MEAN 0, MC33HIP_SIMPLIFY_FIRST 1 */
+	int drop_duplicates;
+	void *oV, *oT;  float *oN /* or NULL */;  void *oAttr[2];  unsigned *oMap /* nV words, or NULL */;
+	unsigned long long capV, capT;
+	unsigned long long nV_out, nT_out, clusters, max_cluster, collapsed_triangles, duplicate_triangles,
+	                   invalid_triangles, clamped_vertices;   /* filled */
+} mc33hip_simplification;
+int mc33hip_simplify_surface(mc33hip_ctx *c, mc33hip_simplification *a);
+
 /* Plain device allocations on the context's device (for language bindings). */
 int mc33hip_device_alloc(mc33hip_ctx *c, void **dptr, size_t bytes);
 int mc33hip_device_free(mc33hip_ctx *c, void *dptr);

@@ -82,6 +82,24 @@ class SurfaceSmoothing(C.Structure):
     _fields_ = [("iterations", C.c_uint), ("lam", C.c_double), ("mu", C.c_double), ("pin_boundary", C.c_int)]
 
 
+class Simplification(C.Structure):
+    """mc33hip_simplification (include/mc33_hip.h)"""
+    _fields_ = [("V", C.c_void_p), ("T", C.c_void_p), ("nV", C.c_ulonglong), ("nT", C.c_ulonglong),
+                ("attr", C.c_void_p * 2), ("n_attr", C.c_uint), ("origin", C.c_double * 3), ("cell", C.c_double * 3),
+                ("mode", C.c_int), ("drop_duplicates", C.c_int),
+                ("oV", C.c_void_p), ("oT", C.c_void_p), ("oN", C.c_void_p), ("oAttr", C.c_void_p * 2), ("oMap", C.c_void_p),
+                ("capV", C.c_ulonglong), ("capT", C.c_ulonglong)] + \
+               [(n, C.c_ulonglong) for n in ("nV_out", "nT_out", "clusters", "max_cluster", "collapsed_triangles", "duplicate_triangles",
+                                             "invalid_triangles", "clamped_vertices")]
+
+
+class SurfaceSimplification(C.Structure):
+    """mc33_simplification (include/marching_cubes_33.h); cell in units of the grid spacing"""
+    _fields_ = [("cell", C.c_double * 3), ("mode", C.c_int), ("drop_duplicates", C.c_int)]
+
+
+SIMPLIFY_MODES = {"mean": 0, "first": 1}
+
 HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_last_error", "mc33hip_upload_rows",
            "mc33hip_upload_contiguous", "mc33hip_adopt_device", "mc33hip_set_stream", "mc33hip_count",
            "mc33hip_emit", "mc33hip_extract", "mc33hip_last_timing", "mc33hip_download",
@@ -92,7 +110,7 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_sample_property", "mc33hip_color_vertices", "mc33hip_download_enqueue",
            "mc33hip_measure_surface", "mc33hip_label_components", "mc33hip_measure_components",
            "mc33hip_surface_topology", "mc33hip_component_topology", "mc33hip_compact_components",
-           "mc33hip_smooth_surface", "mc33hip_vertex_normals", "mc33hip_smooth_timing"]
+           "mc33hip_smooth_surface", "mc33hip_vertex_normals", "mc33hip_smooth_timing", "mc33hip_simplify_surface"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -101,7 +119,8 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "MC33_set_property_grid", "MC33_set_color_map",
                  "MC33_measure_isosurface", "MC33_measure_isosurfaces", "MC33_measure_components",
                  "MC33_isosurface_topology", "MC33_component_topology",
-                 "MC33_select_components", "MC33_calculate_filtered_isosurface", "MC33_calculate_smoothed_isosurface"]
+                 "MC33_select_components", "MC33_calculate_filtered_isosurface", "MC33_calculate_smoothed_isosurface",
+                 "MC33_calculate_simplified_isosurface"]
 
 
 class MC33Error(RuntimeError):
@@ -176,6 +195,7 @@ def load_library(dtype="f32"):
     lib.mc33hip_smooth_surface.argtypes = [V, P(Smoothing)]
     lib.mc33hip_vertex_normals.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V]
     lib.mc33hip_smooth_timing.argtypes = [V, P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint, P(C.c_uint)]
+    lib.mc33hip_simplify_surface.argtypes = [V, P(Simplification)]
     lib.MC33_select_components.argtypes = [V, V, C.c_uint, P(ComponentFilter), V]
     _libs[dtype] = lib
     return lib
@@ -663,6 +683,58 @@ class DeviceGrid:
         ms = (C.c_float * 64)()
         _check(self.lib, self.lib.mc33hip_smooth_timing(self.ctx, C.byref(adj), C.byref(nrm), ms, 64, C.byref(n)))
         return adj.value, nrm.value, [ms[k] for k in range(n.value)]
+
+    # -- simplify a finished mesh on the device (mc33_hip.h: mc33hip_simplify_surface) ---------------------------------------------
+    def simplify(self, V, T, cell, origin=None, mode="mean", drop_duplicates=True, normals=True, attrs=()):
+        """Vertex clustering of the mesh V [n, 3], T [m, 3] (device tensors, as extract() returns them) on the lattice of cells
+        `cell` (a number or three, world units) wide from `origin` (default: the grid's r0): the vertices of a cell become their
+        mean (mode "mean") or the first of them ("first"), triangles that lose a corner go and, with drop_duplicates, so do
+        repeated ones.  Returns (V2, N2, T2, attrs2, vmap, info): exact-size device tensors - N2 the normals recomputed from the
+        output (None with normals=False); attrs: up to two device tensors of one 4-byte word per vertex, the word of a cell's first
+        vertex is kept; vmap int32 [n], the uint32 words of the new index, 0xFFFFFFFF where the vertex left - and a dict of the
+        call's counts and `ratio`, output over input triangles.  Raises MC33Error(ERUNTIME) when a triangle names a vertex >= n."""
+        import torch
+        self._vertex_rows(V)
+        self._triangle_rows(T)
+        nV = V.shape[0]
+        attrs = tuple(attrs)
+        for x in attrs:
+            assert x.is_cuda and x.is_contiguous() and x.numel() == nV and x.element_size() == 4, "an attribute is one 4-byte word per vertex"
+        cell = (float(cell),) * 3 if not hasattr(cell, "__len__") else tuple(float(x) for x in cell)
+        origin = tuple(self.desc.r0) if origin is None else tuple(float(x) for x in origin)
+        a = Simplification()
+        a.V, a.T, a.nV, a.nT = V.data_ptr(), T.data_ptr(), nV, T.shape[0]
+        for k, x in enumerate(attrs[:2]):
+            a.attr[k] = x.data_ptr()
+        a.n_attr = len(attrs)
+        a.origin, a.cell = (C.c_double * 3)(*origin), (C.c_double * 3)(*cell)
+        a.mode, a.drop_duplicates = SIMPLIFY_MODES[mode], int(bool(drop_duplicates))
+        _check(self.lib, self.lib.mc33hip_simplify_surface(self.ctx, C.byref(a)), allow=(ECAPACITY,))  # null outputs: the size query
+        nV2, nT2 = int(a.nV_out), int(a.nT_out)
+        V2 = torch.empty((max(nV2, 1), 3), dtype=V.dtype, device=self.device)
+        N2 = torch.empty((max(nV2, 1), 3), dtype=torch.float32, device=self.device) if normals else None
+        T2 = torch.empty((max(nT2, 1), 3), dtype=torch.int32, device=self.device)
+        attrs2 = [torch.empty((max(nV2, 1),), dtype=x.dtype, device=self.device) for x in attrs]
+        vmap = torch.empty((max(nV, 1),), dtype=torch.int32, device=self.device)
+        a.oV, a.oT, a.oN, a.oMap, a.capV, a.capT = V2.data_ptr(), T2.data_ptr(), (N2.data_ptr() if normals else None), vmap.data_ptr(), nV2, nT2
+        for k, x in enumerate(attrs2):
+            a.oAttr[k] = x.data_ptr()
+        _check(self.lib, self.lib.mc33hip_simplify_surface(self.ctx, C.byref(a)))
+        info = {n: int(getattr(a, n)) for n in ("nV_out", "nT_out", "clusters", "max_cluster", "collapsed_triangles", "duplicate_triangles",
+                                                "invalid_triangles", "clamped_vertices")}
+        info["ratio"] = nT2 / T.shape[0] if T.shape[0] else 0.0
+        return V2[:nV2], (N2[:nV2] if normals else None), T2[:nT2], [x[:nV2] for x in attrs2], vmap[:nV], info
+
+    def extract_simplified(self, iso, cell_in_grid_cells, rng=None, with_property=False, **kw):
+        """extract, then simplify on the lattice of the grid - origin r0, cells of cell_in_grid_cells (a number or three) grid
+        spacings - the whole surface never leaves the device.  Returns (V, N, T, info) and, with with_property, the attached
+        property grid's value at the first vertex of every kept cell as a fifth element.  **kw: mode, drop_duplicates."""
+        got = self.extract(iso, rng, with_property)
+        c = (float(cell_in_grid_cells),) * 3 if not hasattr(cell_in_grid_cells, "__len__") else tuple(float(x) for x in cell_in_grid_cells)
+        cell = tuple(c[k] * self.desc.d[k] for k in range(3))
+        V2, N2, T2, attrs2, _, info = self.simplify(got[0], got[2], cell, attrs=(got[4],) if with_property else (), **kw)
+        out = (V2, N2, T2, info)
+        return out + (attrs2[0],) if with_property else out
 
     def probe_read(self, reps=10):
         """A plain read of the resident grid (nothing to do with an extraction): (best ms, median ms, bytes)."""

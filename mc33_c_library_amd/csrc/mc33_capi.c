@@ -12,6 +12,7 @@
  * rewrites G->F between calls sets MC33_HIP_REUPLOAD=1 (re-upload before every extraction).
  */
 #define _DEFAULT_SOURCE /* madvise, clock_gettime */
+#include <float.h>
 #include <malloc.h> /* malloc_usable_size: asked only about blocks this library allocated itself */
 #include <pthread.h>
 #include <stddef.h>
@@ -70,6 +71,7 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_component_topology
 #pragma weak mc33hip_compact_components
 #pragma weak mc33hip_smooth_surface
+#pragma weak mc33hip_simplify_surface
 _Static_assert(sizeof(mc33_component) == sizeof(mc33hip_component) && offsetof(mc33_component, area) == offsetof(mc33hip_component, area),
                "mc33_component and mc33hip_component are one layout");
 
@@ -110,6 +112,7 @@ typedef struct mc33_private_s {
 	int grid_dirty;      /* MC33_grid_changed: the caller rewrote samples of G->F, upload them before the next extraction */
 	int inclined;        /* G->nonortho at create time: the MC33_spnC store */
 	double grd_A[9], grd_Ai[9];
+	double grd_r0[3], grd_d[3]; /* G->r0, G->d at create time: the lattice of MC33_calculate_simplified_isosurface */
 	_GRD *prop;          /* MC33_set_property_grid: attached on every slab (only read while it is being uploaded) */
 	int has_map;         /* MC33_set_color_map */
 	unsigned map_n;
@@ -260,6 +263,7 @@ MC33 *create_MC33(_GRD *G) {
 	for (int j = 0; j != 3; j++) { /* MC:1779-1782 */
 		M->O[j] = (MC33_real)G->r0[j];
 		M->D[j] = (MC33_real)G->d[j];
+		p->grd_r0[j] = G->r0[j]; p->grd_d[j] = G->d[j];
 	}
 #ifndef GRD_ORTHOGONAL
 	if (G->nonortho) { /* MC:1763-1770: the matrices MC33_spnC multiplies with */
@@ -1239,6 +1243,74 @@ surface *MC33_calculate_smoothed_isosurface(MC33 *M, MC33_real iso, const mc33_s
 	}
 	if (rc == MC33HIP_OK)
 		S = surface_from_staging(p, g, &cnt, iso, 0);
+	if (!S) {
+		M->memoryfault = 1;
+		return 0;
+	}
+	if (S->nV) { /* as calculate_isosurface leaves the public prefix */
+		M->T = S->T; M->V = S->V; M->N = S->N; M->color = S->color;
+		M->nT = S->nT; M->capt = S->capt; M->capv = S->capv;
+	}
+	return S;
+}
+
+/* --- extension: a simplified isosurface ------------------------------------------------------------------------------------------
+ * The surface of `iso` into staging set 0, its colours from the extracted vertices (attribute 0), clustered on the lattice
+ * (r0, cell x d) into staging set 1 with the normals of the output, then the kept rows into a caller-owned surface. */
+static int simplification_ok(const mc33_simplification *sp) {
+	for (int j = 0; j != 3; j++)
+		if (!(sp->cell[j] > 0.0 && sp->cell[j] <= DBL_MAX))
+			return 0;
+	return sp->mode == MC33HIP_SIMPLIFY_MEAN || sp->mode == MC33HIP_SIMPLIFY_FIRST;
+}
+
+static surface *simplified_surface(mc33_private *p, MC33_real iso, const mc33_simplification *sp) {
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0], *h = &s->set[1];
+	mc33hip_counts cnt;
+	const int col = coloured(p);
+	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK)
+		return 0;
+	if (col && cnt.nV) {
+		p->nan_color = DefaultColorMC;
+		if (enqueue_colors(s, g, cnt.nV) != MC33HIP_OK)
+			return 0;
+	}
+	mc33hip_simplification a;
+	memset(&a, 0, sizeof a);
+	a.V = g->dV; a.T = g->dT; a.nV = cnt.nV; a.nT = cnt.nT;
+	if (col && cnt.nV) { a.attr[0] = g->dC; a.n_attr = 1; }
+	for (int j = 0; j != 3; j++) { a.origin[j] = p->grd_r0[j]; a.cell[j] = sp->cell[j] * p->grd_d[j]; }
+	a.mode = sp->mode; a.drop_duplicates = sp->drop_duplicates;
+	int rc = MC33HIP_ECAPACITY;
+	for (int attempt = 0; attempt != 2 && rc == MC33HIP_ECAPACITY; attempt++) { /* with the set as it is; grown to the sizes that came back */
+		if (attempt && (staging_room(s, h, a.nV_out, a.nT_out) || (a.n_attr && dev_room(s->ctx, &h->dC, &h->capC, a.nV_out, sizeof(int))))) {
+			rc = MC33HIP_ENOMEM;
+			break;
+		}
+		a.oV = h->dV; a.oN = (float *)h->dN; a.oT = h->dT; a.oAttr[0] = h->dC;
+		a.capV = a.n_attr && h->capC < h->capV ? h->capC : h->capV;
+		a.capT = h->capT;
+		rc = mc33hip_simplify_surface(s->ctx, &a);
+	}
+	if (rc != MC33HIP_OK)
+		return 0;
+	mc33hip_counts out;
+	memset(&out, 0, sizeof out);
+	out.nV = a.nV_out; out.nT = a.nT_out;
+	return surface_from_staging(p, h, &out, iso, 0);
+}
+
+surface *MC33_calculate_simplified_isosurface(MC33 *M, MC33_real iso, const mc33_simplification *sp) {
+	mc33_private *p = priv(M);
+	if (!p || !sp || p->nslab != 1 || p->inclined || !mc33hip_simplify_surface || !mc33hip_color_vertices)
+		return 0;
+	if (!simplification_ok(sp))
+		return 0; /* (what mc33hip_simplify_surface refuses, before anything is extracted) */
+	M->nT = M->nV = 0;
+	M->memoryfault = 0;
+	M->iso = iso;
+	surface *S = simplified_surface(p, iso, sp);
 	if (!S) {
 		M->memoryfault = 1;
 		return 0;

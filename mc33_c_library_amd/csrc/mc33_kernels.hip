@@ -44,6 +44,9 @@
 //                   the rows keep their order (mc33_filter.hip.h).
 //                   k_sm_* - Taubin smoothing of a finished V over the adjacency of T, a CSR list made on the device, and vertex
 //                   normals recomputed from the triangles; k_sm_pass is its hot path (mc33_smooth.hip.h).
+//                   k_simp_* - vertex clustering of a finished V, T on a lattice: a table of clusters filled by 64-bit compare-and-swap,
+//                   duplicate triangles through a table of triangle indices, two exclusive scans, two writing passes;
+//                   k_simp_cluster is its hot path (mc33_simplify.hip.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -104,3 +107,4 @@ typedef float sample_t;
 #include "mc33_topology.hip.h"
 #include "mc33_filter.hip.h"
 #include "mc33_smooth.hip.h"
+#include "mc33_simplify.hip.h"
