@@ -268,6 +268,30 @@ surface *MC33_calculate_smoothed_isosurface(MC33 *extractor, MC33_real isovalue,
 typedef struct { double cell[3]; int mode; int drop_duplicates; } mc33_simplification;   /* cell in units of the grid spacing d */
 surface *MC33_calculate_simplified_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_simplification *s);
 
+/* extension (not in the reference): the grid resampled on the GPU before anything is extracted from it.  A Gaussian of about one
+ * sample removes the speckle of CT / MRI volumes that otherwise becomes thousands of tiny components; a stride of 2 or 3 per axis
+ * gives a preview surface of an eighth or a twenty-seventh of the triangles without extracting the full one first.  Per axis a
+ * (x, y, z): a Gaussian of sigma[a] SAMPLES cut off at radius[a] <= 8 samples (0: ceil(3 sigma), at least 1; sigma 0: no smoothing
+ * along that axis), then every stride[a]-th point is kept, the first included: (N[a] / stride[a]) intervals, d[a] * stride[a] wide,
+ * r0 unchanged.  Edge samples are replicated.  Integer grids are rounded to nearest and clamped to their range.  The arithmetic is
+ * double and its order is fixed: the exact definition is in mc33_hip.h (mc33hip_resample_grid).
+ * MC33_gaussian_taps is host C, no GPU: the 2 r + 1 weights into taps[] (room for 17), e_i = exp(-(i * i) / (2 sigma^2)) for
+ * i = 0 .. r, normalised by S = e_0 + sum of (e_i + e_i) in ascending i.  It returns r, or -1 for a negative, NaN or infinite sigma,
+ * a NULL taps or r > 8.
+ * MC33_create_resampled returns a NEW, independent extractor whose grid exists only in device memory (the library allocates it and
+ * free_MC33 releases it; `source` may be freed first): nx, ny, nz are the new interval counts, O is unchanged, D, ca, cb follow
+ * from the new spacing by the rules of create_MC33, F is NULL; an inclined source stays inclined.  The property grid and the colour
+ * map are not carried over (MC33_set_property_grid with a _GRD of the new size works as on any object); MC33_grid_changed and
+ * MC33_HIP_REUPLOAD do nothing on it; every other entry point works as on any object, MC33_create_resampled included.
+ * NULL, with `source` untouched: a null or refused struct (the rules of MC33_gaussian_taps, a zero stride, fewer than 2 points left
+ * on an axis), a source spread over several devices (MC33_HIP_DEVICES), a failure of the device.
+ * MC33_resampled_grid downloads that grid into a fresh _GRD with alloc_F rows - N, r0, the new d, the inclined members - to be
+ * released with free_memory_grd; NULL for an object that MC33_create_resampled did not make. */
+typedef struct { double sigma[3]; unsigned radius[3]; unsigned stride[3]; } mc33_resampling;  /* sigma in samples; 0: none; radius 0: ceil(3 sigma) */
+int MC33_gaussian_taps(double sigma, unsigned radius, double *taps);
+MC33 *MC33_create_resampled(MC33 *source, const mc33_resampling *r);
+_GRD *MC33_resampled_grid(MC33 *resampled);
+
 /* ---- inclined grids (reference header :186-191) ---------------------------------------------------------
  * c = A b (transposed == 0) or A^T b for a 3x3 matrix; _multTSA_bf assumes an upper triangular A.  A caller may
  * point mult_Abf at either; calculate_isosurface looks at the pointer when it is called and runs the matching

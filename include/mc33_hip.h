@@ -497,6 +497,45 @@ typedef struct {
 } mc33hip_simplification;
 int mc33hip_simplify_surface(mc33hip_ctx *c, mc33hip_simplification *a);
 
+/* --- resample the resident grid into a second device grid: taps and strides (no counterpart in the reference) --------------------
+ * A separable correlation with up to 17 taps per axis, the grid's edge samples replicated, and an integer stride per axis: a
+ * Gaussian before the extraction, a volume reduced by 2 or 3 per axis for a preview surface, or both, without the samples leaving
+ * the device.  The result is an exact function of the input: nothing has a tolerance, and two calls return the same bytes.
+ *   source      the grid resident in the context - the library's own copy or an adopted buffer - with np[a] points per axis
+ *               (a: x = 0, y = 1, z = 2) and samples F[z][y][x] of the library's sample type.  The context must hold a WHOLE grid:
+ *               plane0 == 0 and npz_resident == nz_total + 1; a z-slab context is MC33HIP_EINVAL.
+ *   per axis a  ntaps[a] odd, radius r[a] = (ntaps[a] - 1) / 2 <= 8; taps[a] a HOST array of ntaps[a] finite doubles;
+ *               taps[a] == NULL means the single tap {1.0} (ntaps[a] is ignored then); stride[a] >= 1.
+ *   output size np_out[a] = (np[a] - 1) / stride[a] + 1 in integer division; at least 2 on every axis, else MC33HIP_EINVAL.
+ *   arithmetic  IEEE double, nothing fused; every sum starts from its first product and adds the others in ascending tap index;
+ *               cl(i, n) = min(max(i, 0), n - 1).  A correlation, not a flipped convolution: tap i multiplies the sample at
+ *               offset i - r.
+ *                 A(x, y, z)   = (double)F[z][y][x]
+ *                 Sx(X, y, z)  = sum_i  taps[0][i] * A(cl(X*stride[0] + i - r[0], np[0]), y, z)
+ *                 Sy(X, Y, z)  = sum_j  taps[1][j] * Sx(X, cl(Y*stride[1] + j - r[1], np[1]), z)
+ *                 Sz(X, Y, Z)  = sum_k  taps[2][k] * Sy(X, Y, cl(Z*stride[2] + k - r[2], np[2]))
+ *                 out[Z][Y][X] = convert(Sz(X, Y, Z))
+ *   conversion  double samples: the value itself; float: (float)v; unsigned char / short / int with MAX of the type: 0 when
+ *               !(v > 0) - a NaN included -, MAX when v >= MAX, otherwise (T)floor(v + 0.5).
+ *               The intermediates are exact doubles: any tiling, fusion of axes or order of passes gives the same bits.
+ *   geometry    of the output grid: r0_out = r0, d_out[a] = d[a] * (double)stride[a], nz_total_out = np_out[2] - 1.
+ *   dst         device memory with the layout mc33hip_adopt_device takes - pitch / slice in samples, pitch >= np_out[0],
+ *               slice >= pitch * np_out[1], any base address a sample may have.  ONLY the np_out grid points are written: padding
+ *               keeps its bytes.  Of the source only grid points are read, which lies within the readable extent
+ *               mc33hip_adopt_device states.  The result never depends on either layout; the speed may.
+ *   MC33HIP_EINVAL  checked on the host, nothing is written: a null pointer; an even ntaps or a radius above 8; a tap that is not
+ *               finite; a zero stride; an output axis below 2 points; a slab context (or one without a grid); a bad pitch /
+ *               slice; a dst byte range - first to last grid point - that meets the source grid's (the call is not in place).
+ *   MC33HIP_ENOMEM  the scratch - the taps in device memory, 416 bytes, with the context until mc33hip_destroy - cannot be had.
+ * mc33hip_resample_grid copies the taps to the device, enqueues on the context's stream behind whatever is on it, and waits.
+ * mc33hip_resampled_size makes the same checks of the struct and leaves np_out; nothing is enqueued. */
+typedef struct { const double *taps[3]; unsigned ntaps[3]; unsigned stride[3]; } mc33hip_resampling;
+int mc33hip_resampled_size(mc33hip_ctx *c, const mc33hip_resampling *r, unsigned np_out[3]);
+int mc33hip_resample_grid(mc33hip_ctx *c, const mc33hip_resampling *r, void *dst, size_t pitch, size_t slice);
+/* The HIP device ordinal the context works on - what desc.device = -1 resolved to in mc33hip_create (MC33HIP_EINVAL for NULL): a
+ * second context for the resampled grid is created on this device, whatever the current device has become since. */
+int mc33hip_context_device(mc33hip_ctx *c);
+
 /* Plain device allocations on the context's device (for language bindings). */
 int mc33hip_device_alloc(mc33hip_ctx *c, void **dptr, size_t bytes);
 int mc33hip_device_free(mc33hip_ctx *c, void *dptr);

@@ -100,6 +100,17 @@ class SurfaceSimplification(C.Structure):
 
 SIMPLIFY_MODES = {"mean": 0, "first": 1}
 
+
+class Resampling(C.Structure):
+    """mc33hip_resampling (include/mc33_hip.h): taps are HOST arrays of doubles, NULL = the single tap 1.0"""
+    _fields_ = [("taps", C.POINTER(C.c_double) * 3), ("ntaps", C.c_uint * 3), ("stride", C.c_uint * 3)]
+
+
+class GridResampling(C.Structure):
+    """mc33_resampling (include/marching_cubes_33.h); sigma in samples, radius 0 = ceil(3 sigma)"""
+    _fields_ = [("sigma", C.c_double * 3), ("radius", C.c_uint * 3), ("stride", C.c_uint * 3)]
+
+
 HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_last_error", "mc33hip_upload_rows",
            "mc33hip_upload_contiguous", "mc33hip_adopt_device", "mc33hip_set_stream", "mc33hip_count",
            "mc33hip_emit", "mc33hip_extract", "mc33hip_last_timing", "mc33hip_download",
@@ -110,7 +121,8 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_sample_property", "mc33hip_color_vertices", "mc33hip_download_enqueue",
            "mc33hip_measure_surface", "mc33hip_label_components", "mc33hip_measure_components",
            "mc33hip_surface_topology", "mc33hip_component_topology", "mc33hip_compact_components",
-           "mc33hip_smooth_surface", "mc33hip_vertex_normals", "mc33hip_smooth_timing", "mc33hip_simplify_surface"]
+           "mc33hip_smooth_surface", "mc33hip_vertex_normals", "mc33hip_smooth_timing", "mc33hip_simplify_surface",
+           "mc33hip_resampled_size", "mc33hip_resample_grid", "mc33hip_context_device"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -120,7 +132,8 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "MC33_measure_isosurface", "MC33_measure_isosurfaces", "MC33_measure_components",
                  "MC33_isosurface_topology", "MC33_component_topology",
                  "MC33_select_components", "MC33_calculate_filtered_isosurface", "MC33_calculate_smoothed_isosurface",
-                 "MC33_calculate_simplified_isosurface"]
+                 "MC33_calculate_simplified_isosurface",
+                 "MC33_gaussian_taps", "MC33_create_resampled", "MC33_resampled_grid"]
 
 
 class MC33Error(RuntimeError):
@@ -197,8 +210,27 @@ def load_library(dtype="f32"):
     lib.mc33hip_smooth_timing.argtypes = [V, P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint, P(C.c_uint)]
     lib.mc33hip_simplify_surface.argtypes = [V, P(Simplification)]
     lib.MC33_select_components.argtypes = [V, V, C.c_uint, P(ComponentFilter), V]
+    lib.mc33hip_resampled_size.argtypes = [V, P(Resampling), P(C.c_uint * 3)]
+    lib.mc33hip_resample_grid.argtypes = [V, P(Resampling), V, C.c_size_t, C.c_size_t]
+    lib.mc33hip_context_device.argtypes = [V]
+    lib.MC33_gaussian_taps.argtypes = [C.c_double, C.c_uint, P(C.c_double)]
     _libs[dtype] = lib
     return lib
+
+
+def gaussian_taps(sigma, radius=0):
+    """The 2 r + 1 weights of a Gaussian of `sigma` samples cut off at `radius` (0: ceil(3 sigma), at least 1; sigma 0: the single
+    tap 1.0) as a list of floats - the library's MC33_gaussian_taps (include/marching_cubes_33.h), host C that needs no GPU: there
+    is no second implementation.  ValueError for what it refuses: a negative, NaN or infinite sigma, a radius above 8."""
+    lib = load_library("f32")
+    taps = (C.c_double * 17)()
+    try:
+        r = lib.MC33_gaussian_taps(float(sigma), int(radius), taps)
+    except (C.ArgumentError, OverflowError):
+        r = -1
+    if r < 0:
+        raise ValueError("MC33_gaussian_taps refused sigma=%r radius=%r" % (sigma, radius))
+    return [taps[k] for k in range(2 * r + 1)]
 
 
 class SurfaceMeasures:
@@ -314,10 +346,12 @@ class DeviceGrid:
         """Non-orthogonal grid: _GRD._A / _GRD.A_ (3x3, row major); None switches back."""
         if A is None:
             _check(self.lib, self.lib.mc33hip_set_inclined(self.ctx, None, None, 0))
+            self.inclined = None
             return
         a = (C.c_double * 9)(*[float(x) for row in A for x in row])
         ai = (C.c_double * 9)(*[float(x) for row in Ai for x in row])
         _check(self.lib, self.lib.mc33hip_set_inclined(self.ctx, a, ai, int(bool(triangular))))
+        self.inclined = ([list(row) for row in A], [list(row) for row in Ai], bool(triangular))  # (resampled() hands them on)
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -735,6 +769,55 @@ class DeviceGrid:
         V2, N2, T2, attrs2, _, info = self.simplify(got[0], got[2], cell, attrs=(got[4],) if with_property else (), **kw)
         out = (V2, N2, T2, info)
         return out + (attrs2[0],) if with_property else out
+
+    # -- the grid resampled into a second device grid (mc33_hip.h: mc33hip_resample_grid) ------------------------------------------
+    def _resampling(self, taps, stride, sigma):
+        if sigma is not None:
+            sig = (sigma,) * 3 if not hasattr(sigma, "__len__") else tuple(sigma)
+            taps = tuple(gaussian_taps(x) for x in sig)
+        r = Resampling()
+        keep = []
+        for a in range(3):
+            if taps[a] is not None:
+                w = (C.c_double * len(taps[a]))(*[float(x) for x in taps[a]])
+                keep.append(w)
+                r.taps[a] = C.cast(w, C.POINTER(C.c_double))
+                r.ntaps[a] = len(taps[a])
+            r.stride[a] = int(stride[a])
+        return r, keep
+
+    def resampled_size(self, taps=(None, None, None), stride=(1, 1, 1), sigma=None):
+        """(npx', npy', npz') of what resampled() with these arguments returns; MC33Error(EINVAL) for what it refuses."""
+        r, keep = self._resampling(taps, stride, sigma)
+        n = (C.c_uint * 3)()
+        _check(self.lib, self.lib.mc33hip_resampled_size(self.ctx, C.byref(r), C.byref(n)))
+        return n[0], n[1], n[2]
+
+    def resample_into(self, out, npx, taps=(None, None, None), stride=(1, 1, 1), sigma=None):
+        """mc33hip_resample_grid into `out`, a device tensor [npz', npy', >= npx] of the grid's dtype used with its strides (any
+        stride(1) >= npx, any stride(0)): only the grid points are written."""
+        assert out.is_cuda and out.dim() == 3 and out.stride(2) == 1 and out.dtype == self.tensor.dtype and out.device == self.device
+        r, keep = self._resampling(taps, stride, sigma)
+        _check(self.lib, self.lib.mc33hip_resample_grid(self.ctx, C.byref(r), C.c_void_p(out.data_ptr()), out.stride(1), out.stride(0)))
+
+    def resampled(self, taps=(None, None, None), stride=(1, 1, 1), sigma=None):
+        """The grid resampled on the device - per axis a correlation with `taps` (an odd number of weights up to 17, None: none),
+        edge samples replicated, then every stride-th point - into a new torch tensor [npz', npy', pitch'] with rows on 16-byte
+        boundaries; `sigma` (a number or three, in samples) is shorthand for Gaussian taps (gaussian_taps).  Returns a new
+        DeviceGrid over that tensor with the grid's r0, spacing d * stride, the current stream and the inclined matrices of this
+        one.  Whole grids only (not a z-slab).  The definition is in include/mc33_hip.h."""
+        import torch
+        npx, npy, npz = self.resampled_size(taps, stride, sigma)
+        sb = self.tensor.element_size()
+        unit = max(1, 16 // sb)
+        pitch = (npx + unit - 1) // unit * unit
+        out = torch.empty((npz, npy, pitch), dtype=self.tensor.dtype, device=self.device)
+        self.resample_into(out, npx, taps, stride, sigma)
+        d = tuple(self.desc.d[k] * float(int(stride[k])) for k in range(3))
+        g = DeviceGrid(out, r0=tuple(self.desc.r0), d=d, npx=npx)
+        if getattr(self, "inclined", None):
+            g.set_inclined(*self.inclined)
+        return g
 
     def probe_read(self, reps=10):
         """A plain read of the resident grid (nothing to do with an extraction): (best ms, median ms, bytes)."""

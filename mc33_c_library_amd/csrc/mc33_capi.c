@@ -13,6 +13,7 @@
  */
 #define _DEFAULT_SOURCE /* madvise, clock_gettime */
 #include <float.h>
+#include <math.h>
 #include <malloc.h> /* malloc_usable_size: asked only about blocks this library allocated itself */
 #include <pthread.h>
 #include <stddef.h>
@@ -72,6 +73,11 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_compact_components
 #pragma weak mc33hip_smooth_surface
 #pragma weak mc33hip_simplify_surface
+/* ... and the resampling ones (MC33_create_resampled): without them it returns NULL */
+#pragma weak mc33hip_resampled_size
+#pragma weak mc33hip_resample_grid
+#pragma weak mc33hip_context_device
+#pragma weak mc33hip_adopt_device /* (the host layer uses it for the resampled grid only) */
 _Static_assert(sizeof(mc33_component) == sizeof(mc33hip_component) && offsetof(mc33_component, area) == offsetof(mc33hip_component, area),
                "mc33_component and mc33hip_component are one layout");
 
@@ -119,6 +125,8 @@ typedef struct mc33_private_s {
 	int map[256];
 	double map_lo, map_hi;
 	int nan_color;       /* DefaultColorMC when the surface under way was made */
+	void *own_grid;      /* MC33_create_resampled: the grid, in device memory only, adopted by slab[0].ctx; released in free_MC33 */
+	size_t own_pitch, own_slice; /* ... its layout, in samples */
 	void *dP, *dL;       /* MC33_measure_*: property values / component labels of the vertices in slab[0].set[0] (device) */
 	unsigned long long capP, capL;
 } mc33_private;
@@ -322,6 +330,11 @@ void free_MC33(MC33 *M) {
 		for (int k = 0; k != 2; k++)
 			staging_release(s->ctx, &s->set[k]);
 		if (q == 0) { dev_release(s->ctx, &p->dP, &p->capP); dev_release(s->ctx, &p->dL, &p->capL); }
+		if (q == 0 && p->own_grid) { /* the grid of MC33_create_resampled: through the context while it lives, when nothing reads it any more */
+			(void)mc33hip_synchronize(s->ctx);
+			(void)mc33hip_device_free(s->ctx, p->own_grid);
+			p->own_grid = 0;
+		}
 		mc33hip_destroy(s->ctx);
 	}
 	p->magic = 0;
@@ -363,7 +376,7 @@ static int refresh_grid(mc33_private *p) {
 			if (mc33hip_set_inclined(p->slab[k].ctx, p->grd_A, p->grd_Ai, mult_Abf == _multTSA_bf) != MC33HIP_OK)
 				return MC33HIP_EINVAL;
 	}
-	if (!p->reupload && !p->grid_dirty)
+	if (!p->grid || (!p->reupload && !p->grid_dirty)) /* (no host grid: the object of MC33_create_resampled) */
 		return 0;
 	p->grid_dirty = 0;
 	return run_slabs(p, slab_upload);
@@ -374,7 +387,7 @@ static int refresh_grid(mc33_private *p) {
  * uploads G->F again first.  The _GRD and its rows must still be alive then, as for the reference's own M->F. */
 void MC33_grid_changed(MC33 *M) {
 	mc33_private *p = priv(M);
-	if (p)
+	if (p && p->grid)
 		p->grid_dirty = 1;
 }
 
@@ -1458,5 +1471,151 @@ _GRD *generate_grid_from_fn(double xi, double yi, double zi, double xf, double y
 		Z->L[i] = (float)(Z->N[i] * Z->d[i]);
 	}
 	set_orthogonal(Z);
+	return Z;
+}
+
+/* --- extension: the grid resampled on the device before extraction -------------------------------------------------------------- */
+int MC33_gaussian_taps(double sigma, unsigned radius, double *taps) {
+	if (!taps || !(sigma >= 0.0 && sigma <= DBL_MAX))
+		return -1;
+	if (sigma == 0.0) {
+		taps[0] = 1.0;
+		return 0;
+	}
+	if (radius > 8u || (!radius && 3.0 * sigma > 8.0)) /* (before the cast: ceil(3 sigma) may be beyond an unsigned) */
+		return -1;
+	unsigned r = radius;
+	if (!r) {
+		r = (unsigned)ceil(3.0 * sigma);
+		if (r < 1u) r = 1u;
+	}
+	double e[9];
+	for (unsigned i = 0; i <= r; i++)
+		e[i] = exp(-(double)(i * i) / (2.0 * sigma * sigma));
+	double S = e[0];
+	for (unsigned i = 1; i <= r; i++)
+		S = S + (e[i] + e[i]);
+	for (unsigned i = 0; i <= r; i++)
+		taps[r - i] = taps[r + i] = e[i] / S;
+	return (int)r;
+}
+
+/* the row pitch of a grid this library allocates: rows on 16-byte boundaries (the rule of the device layer's own copy) */
+static size_t resampled_pitch(size_t npx) {
+	const size_t unit = sizeof(GRD_data_type) >= 4 ? 4 : 16 / sizeof(GRD_data_type);
+	return (npx + unit - 1) / unit * unit;
+}
+
+MC33 *MC33_create_resampled(MC33 *source, const mc33_resampling *r) {
+	mc33_private *sp = priv(source);
+	if (!sp || !r || sp->nslab != 1 || !mc33hip_resampled_size || !mc33hip_resample_grid || !mc33hip_context_device || !mc33hip_adopt_device)
+		return 0;
+	double w[3][17];
+	mc33hip_resampling hr;
+	unsigned npo[3];
+	for (int a = 0; a != 3; a++) {
+		const int rad = MC33_gaussian_taps(r->sigma[a], r->radius[a], w[a]);
+		if (rad < 0 || !r->stride[a])
+			return 0;
+		hr.taps[a] = w[a]; hr.ntaps[a] = 2u * (unsigned)rad + 1u; hr.stride[a] = r->stride[a];
+	}
+	mc33_slab *ss = &sp->slab[0];
+	if (mc33hip_resampled_size(ss->ctx, &hr, npo) != MC33HIP_OK) /* (fewer than 2 points left on an axis) */
+		return 0;
+	mc33_private *p = (mc33_private *)calloc(1, sizeof *p);
+	if (!p)
+		return 0;
+	p->magic = MC33_MAGIC;
+	MC33 *M = &p->pub;
+	M->nx = npo[0] - 1u; M->ny = npo[1] - 1u; M->nz = npo[2] - 1u;
+	for (int j = 0; j != 3; j++) {
+		p->grd_r0[j] = sp->grd_r0[j];
+		p->grd_d[j] = sp->grd_d[j] * (double)r->stride[j];
+		M->O[j] = (MC33_real)p->grd_r0[j];
+		M->D[j] = (MC33_real)p->grd_d[j];
+	}
+#ifndef GRD_ORTHOGONAL
+	if (sp->inclined) { /* the matrices of the source's _GRD, scaled by the new spacing (create_MC33) */
+		p->inclined = 1;
+		memcpy(p->grd_A, sp->grd_A, sizeof p->grd_A);
+		memcpy(p->grd_Ai, sp->grd_Ai, sizeof p->grd_Ai);
+		for (int j = 0; j != 3; j++)
+			for (int i = 0; i != 3; i++) {
+				M->_A[j][i] = p->grd_A[3 * j + i] * p->grd_d[i];
+				M->A_[j][i] = p->grd_Ai[3 * j + i] / p->grd_d[j];
+			}
+	} else
+#endif
+	if (p->grd_d[0] != p->grd_d[1] || p->grd_d[1] != p->grd_d[2]) {
+		M->ca = (MC33_real)(p->grd_d[2] / p->grd_d[0]);
+		M->cb = (MC33_real)(p->grd_d[2] / p->grd_d[1]);
+	}
+	__atomic_add_fetch(&g_objects, 1, __ATOMIC_RELAXED);
+	p->nslab = 1;
+	mc33_slab *s = &p->slab[0];
+	s->owner = p;
+	s->device = mc33hip_context_device(ss->ctx); /* (the ordinal the source's context resolved: -1 would mean today's current device) */
+	s->z_begin = 0; s->z_end = M->nz; s->ghost = 0; s->p_lo = 0; s->p_hi = M->nz;
+	mc33hip_grid_desc d;
+	memset(&d, 0, sizeof d);
+	d.npx = npo[0]; d.npy = npo[1]; d.npz_resident = npo[2];
+	d.plane0 = 0; d.nz_total = M->nz;
+	for (int j = 0; j != 3; j++) { d.r0[j] = p->grd_r0[j]; d.d[j] = p->grd_d[j]; }
+	d.sample_bytes = (int)sizeof(GRD_data_type);
+	d.device = s->device;
+	p->own_pitch = resampled_pitch(npo[0]);
+	p->own_slice = p->own_pitch * npo[1];
+	int rc = mc33hip_create(&s->ctx, &d);
+	if (rc == MC33HIP_OK) rc = mc33hip_set_normal_neg(s->ctx, MC33_NORMAL_NEG);
+	if (rc == MC33HIP_OK) rc = refresh_grid(sp); /* (samples the caller said it rewrote: uploaded first, as before an extraction) */
+	if (rc == MC33HIP_OK) /* (64 samples to spare behind the last row, like the device layer's own copy) */
+		rc = mc33hip_device_alloc(s->ctx, &p->own_grid, (p->own_slice * npo[2] + 64) * sizeof(GRD_data_type));
+	if (rc == MC33HIP_OK) rc = mc33hip_resample_grid(ss->ctx, &hr, p->own_grid, p->own_pitch, p->own_slice); /* (waits) */
+	if (rc == MC33HIP_OK) rc = mc33hip_adopt_device(s->ctx, p->own_grid, p->own_pitch, p->own_slice);
+	if (rc != MC33HIP_OK) {
+		free_MC33(M);
+		return 0;
+	}
+	return M;
+}
+
+_GRD *MC33_resampled_grid(MC33 *M) {
+	mc33_private *p = priv(M);
+	if (!p || !p->own_grid)
+		return 0;
+	_GRD *Z = (_GRD *)calloc(1, sizeof(_GRD));
+	if (!Z)
+		return 0;
+	Z->N[0] = M->nx; Z->N[1] = M->ny; Z->N[2] = M->nz;
+	for (int i = 0; i != 3; i++) {
+		Z->r0[i] = p->grd_r0[i];
+		Z->d[i] = p->grd_d[i];
+		Z->L[i] = (float)(Z->N[i] * Z->d[i]);
+	}
+	set_orthogonal(Z);
+#ifndef GRD_ORTHOGONAL
+	if (p->inclined) {
+		Z->nonortho = 1;
+		memcpy(Z->_A, p->grd_A, sizeof Z->_A);
+		memcpy(Z->A_, p->grd_Ai, sizeof Z->A_);
+	}
+#endif
+	const size_t npx = (size_t)M->nx + 1, npy = (size_t)M->ny + 1, npz = (size_t)M->nz + 1;
+	const size_t plane = (npy - 1) * p->own_pitch + npx; /* samples from a plane's first to its last grid point */
+	GRD_data_type *stage = (GRD_data_type *)malloc(plane * sizeof(GRD_data_type));
+	int ok = stage && alloc_F(Z) == 0;
+	for (size_t k = 0; ok && k != npz; k++) { /* a plane at a time through one block, its rows into the rows of alloc_F */
+		void *const to = stage;
+		const void *const from = (const GRD_data_type *)p->own_grid + k * p->own_slice;
+		const size_t bytes = plane * sizeof(GRD_data_type);
+		ok = mc33hip_download_many(p->slab[0].ctx, 1, &to, &from, &bytes, 0) == MC33HIP_OK;
+		for (size_t j = 0; ok && j != npy; j++)
+			memcpy(Z->F[k][j], stage + j * p->own_pitch, npx * sizeof(GRD_data_type));
+	}
+	free(stage);
+	if (!ok) {
+		free_memory_grd(Z);
+		return 0;
+	}
 	return Z;
 }
