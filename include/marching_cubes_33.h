@@ -292,6 +292,28 @@ int MC33_gaussian_taps(double sigma, unsigned radius, double *taps);
 MC33 *MC33_create_resampled(MC33 *source, const mc33_resampling *r);
 _GRD *MC33_resampled_grid(MC33 *resampled);
 
+/* extension (not in the reference): the contour spectrum of the grid - what a caller needs to choose an isovalue, from one pass
+ * over the volume on the GPU instead of one size_of_isosurface per candidate.  For `count` <= 255 isovalues, strictly ascending as
+ * MC33_real, none a NaN: cut_cells[k] is the number of cells the surface of isovalues[k] cuts, histogram[j], j <= count, the number
+ * of grid points whose sample lies above exactly j of the isovalues (a NaN sample: count when its sign bit is set, else 0), and
+ * *info (may be NULL) the totals, the NaN samples and the exact range of the other samples as MC33_real.  count == 0 is legal:
+ * histogram[0] grid points and the range - the first call of a two-step ladder.  The exact definition is in mc33_hip.h
+ * (mc33hip_grid_spectrum).  A grid marked by MC33_grid_changed / MC33_HIP_REUPLOAD is uploaded first, as size_of_isosurface does;
+ * the MC33 struct stays byte for byte as it was, iso, nV, nT and memoryfault included.  Works on objects made by
+ * MC33_create_resampled and - unlike the mesh extensions - on an extractor spread over several devices (MC33_HIP_DEVICES): every
+ * slab counts its own slices, the integers are added and the extremes combined.  Returns 0, or -1 - nothing is written then - for a
+ * refused argument or a failure of the device.
+ * MC33_isovalue_ladder is host C, no GPU: n <= 255 steps strictly between lo and hi,
+ * out[k] = (MC33_real)(lo + (hi - lo) * ((double)(k + 1) / (double)(n + 1))).  It returns n, or -1 for bounds that are not finite,
+ * lo >= hi, n > 255, a NULL array, or steps that are not strictly ascending after the conversion. */
+typedef struct {
+	unsigned long long points, cells, nan_samples;
+	double sample_min, sample_max;   /* +inf / -inf when every sample is a NaN */
+} mc33_spectrum_info;
+int MC33_grid_spectrum(MC33 *M, const MC33_real *isovalues, unsigned count, unsigned long long *cut_cells, unsigned long long *histogram,
+                       mc33_spectrum_info *info);
+int MC33_isovalue_ladder(double lo, double hi, unsigned n, MC33_real *out);
+
 /* ---- inclined grids (reference header :186-191) ---------------------------------------------------------
  * c = A b (transposed == 0) or A^T b for a 3x3 matrix; _multTSA_bf assumes an upper triangular A.  A caller may
  * point mult_Abf at either; calculate_isosurface looks at the pointer when it is called and runs the matching

@@ -536,6 +536,48 @@ int mc33hip_resample_grid(mc33hip_ctx *c, const mc33hip_resampling *r, void *dst
  * second context for the resampled grid is created on this device, whatever the current device has become since. */
 int mc33hip_context_device(mc33hip_ctx *c);
 
+/* --- contour spectrum of the resident grid: cut cells and histogram per isovalue (Bajaj, Pascucci, Schikore 1997; no counterpart
+ * in the reference) ---------------------------------------------------------------------------------------------------------------
+ * For a ladder of isovalues: how many cells the surface cuts at each one, a histogram of the samples between the steps, and the
+ * range of the samples - what a caller needs to choose an isovalue, from one pass over the grid instead of one mc33hip_count per
+ * candidate.  Everything is an integer: nothing has a tolerance, and two calls return the same bytes.
+ *   isovalues   isos: a HOST array of n doubles, 0 <= n <= 255, each converted to MC33_real as mc33hip_count converts its iso;
+ *               after the conversion strictly ascending, none a NaN; +-inf is allowed.
+ *   rank        of a grid point with sample F, r = (MC33_real)F: for a non-NaN r, rank(r) = #{ j : iso_j < r }, in 0 .. n; a NaN
+ *               has rank n when its sign bit is set, else 0.  This is the side bit of every pass here and of the reference, for
+ *               every isovalue at once: the bit for iso_k is rank > k (a NaN's sign is its own: mc33_cell.h, iso_diff).  For the
+ *               isovalue -0.0 on a grid holding zeros the rule above stands (the one input that is not comparable
+ *               with the reference).
+ *   range       cell slices [z_begin, z_end) of the WHOLE grid; ghost_below and id_base are ignored.  z_begin < z_end <= nz_total,
+ *               and the planes z_begin .. z_end must be resident in the context: whole grids and z-slab contexts both work.
+ *   cut_cells[k], k < n      the cells of the range with min_rank <= k < max_rank over their eight corners: the cells
+ *               mc33hip_count of iso_k reports as active_cells for the same range without a ghost slice.
+ *   histogram[j], j <= n     the grid points with rank j, counted over the planes [z_begin, z_end) and plane z_end exactly when
+ *               z_end == nz_total: disjoint ranges that tile the grid add up to the whole grid's histogram.
+ *   points, cells            the totals just described.
+ *   nan_samples              the NaN samples among the points: a statistic - they still sit in bin 0 or n.
+ *   sample_min, sample_max   exact minimum and maximum of the non-NaN r as doubles, +inf / -inf when there are none; which zero
+ *               is returned where both signs occur is unspecified.
+ *   n == 0 is legal: histogram[0] == points and the range of the samples - the first call of a two-step ladder.
+ * The result never depends on pitch, slice, alignment or what the padding holds, and only memory inside the readable extent
+ * mc33hip_adopt_device states is read.  No extraction state is touched: a count waiting for its emit, sweeps and prepared
+ * isovalues made ahead, the count-reuse rule, timing and attached property grids are as they were, and a mc33hip_emit or
+ * mc33hip_extract behind a spectrum returns what it would have returned without it.
+ *   MC33HIP_EINVAL  checked on the host, nothing is enqueued: a null pointer where a size is not zero (cut_cells and isos may be
+ *               NULL with n == 0), n > 255, a NaN isovalue, isovalues not strictly ascending after the conversion (two doubles
+ *               that round to one float included), a bad range, a context without a grid.
+ *   MC33HIP_ENOMEM  the scratch - 6 KB, with the context until mc33hip_destroy - cannot be had.
+ * The call enqueues on the context's stream behind whatever is on it, waits, and brings the small result to the host. */
+typedef struct {
+	const double *isos;               /* in: n isovalues (HOST)                              */
+	unsigned n;
+	unsigned long long *cut_cells;    /* out: n counts (HOST)                                */
+	unsigned long long *histogram;    /* out: n + 1 counts (HOST)                            */
+	unsigned long long points, cells, nan_samples;   /* filled by the call                   */
+	double sample_min, sample_max;
+} mc33hip_spectrum;
+int mc33hip_grid_spectrum(mc33hip_ctx *c, const mc33hip_range *range, mc33hip_spectrum *s);
+
 /* Plain device allocations on the context's device (for language bindings). */
 int mc33hip_device_alloc(mc33hip_ctx *c, void **dptr, size_t bytes);
 int mc33hip_device_free(mc33hip_ctx *c, void *dptr);

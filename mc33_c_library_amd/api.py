@@ -111,6 +111,19 @@ class GridResampling(C.Structure):
     _fields_ = [("sigma", C.c_double * 3), ("radius", C.c_uint * 3), ("stride", C.c_uint * 3)]
 
 
+class Spectrum(C.Structure):
+    """mc33hip_spectrum (include/mc33_hip.h): isos, cut_cells and histogram are HOST arrays"""
+    _fields_ = [("isos", C.POINTER(C.c_double)), ("n", C.c_uint), ("cut_cells", C.POINTER(C.c_ulonglong)), ("histogram", C.POINTER(C.c_ulonglong)),
+                ("points", C.c_ulonglong), ("cells", C.c_ulonglong), ("nan_samples", C.c_ulonglong),
+                ("sample_min", C.c_double), ("sample_max", C.c_double)]
+
+
+class SpectrumInfo(C.Structure):
+    """mc33_spectrum_info (include/marching_cubes_33.h)"""
+    _fields_ = [("points", C.c_ulonglong), ("cells", C.c_ulonglong), ("nan_samples", C.c_ulonglong),
+                ("sample_min", C.c_double), ("sample_max", C.c_double)]
+
+
 HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_last_error", "mc33hip_upload_rows",
            "mc33hip_upload_contiguous", "mc33hip_adopt_device", "mc33hip_set_stream", "mc33hip_count",
            "mc33hip_emit", "mc33hip_extract", "mc33hip_last_timing", "mc33hip_download",
@@ -122,7 +135,7 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_measure_surface", "mc33hip_label_components", "mc33hip_measure_components",
            "mc33hip_surface_topology", "mc33hip_component_topology", "mc33hip_compact_components",
            "mc33hip_smooth_surface", "mc33hip_vertex_normals", "mc33hip_smooth_timing", "mc33hip_simplify_surface",
-           "mc33hip_resampled_size", "mc33hip_resample_grid", "mc33hip_context_device"]
+           "mc33hip_resampled_size", "mc33hip_resample_grid", "mc33hip_context_device", "mc33hip_grid_spectrum"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -133,7 +146,8 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "MC33_isosurface_topology", "MC33_component_topology",
                  "MC33_select_components", "MC33_calculate_filtered_isosurface", "MC33_calculate_smoothed_isosurface",
                  "MC33_calculate_simplified_isosurface",
-                 "MC33_gaussian_taps", "MC33_create_resampled", "MC33_resampled_grid"]
+                 "MC33_gaussian_taps", "MC33_create_resampled", "MC33_resampled_grid",
+                 "MC33_grid_spectrum", "MC33_isovalue_ladder"]
 
 
 class MC33Error(RuntimeError):
@@ -214,6 +228,8 @@ def load_library(dtype="f32"):
     lib.mc33hip_resample_grid.argtypes = [V, P(Resampling), V, C.c_size_t, C.c_size_t]
     lib.mc33hip_context_device.argtypes = [V]
     lib.MC33_gaussian_taps.argtypes = [C.c_double, C.c_uint, P(C.c_double)]
+    lib.mc33hip_grid_spectrum.argtypes = [V, P(Range), P(Spectrum)]
+    lib.MC33_isovalue_ladder.argtypes = [C.c_double, C.c_double, C.c_uint, V]
     _libs[dtype] = lib
     return lib
 
@@ -231,6 +247,41 @@ def gaussian_taps(sigma, radius=0):
     if r < 0:
         raise ValueError("MC33_gaussian_taps refused sigma=%r radius=%r" % (sigma, radius))
     return [taps[k] for k in range(2 * r + 1)]
+
+
+def isovalue_ladder(lo, hi, n, dtype="f32"):
+    """n isovalues strictly between lo and hi, (MC33_real)(lo + (hi - lo) * (k + 1) / (n + 1)), as a list of floats - the
+    library's MC33_isovalue_ladder (include/marching_cubes_33.h), host C that needs no GPU: there is no second implementation.
+    dtype: the grid's sample type (MC33_real is double for "f64", float otherwise).  ValueError for what it refuses: bounds that
+    are not finite, lo >= hi, n > 255, steps that MC33_real does not tell apart."""
+    lib = load_library(dtype)
+    out = ((C.c_double if dtype == "f64" else C.c_float) * 256)()
+    try:
+        r = lib.MC33_isovalue_ladder(float(lo), float(hi), int(n), C.cast(out, C.c_void_p))
+    except (C.ArgumentError, OverflowError, TypeError, ValueError):
+        r = -1
+    if r < 0:
+        raise ValueError("MC33_isovalue_ladder refused lo=%r hi=%r n=%r" % (lo, hi, n))
+    return [float(out[k]) for k in range(r)]
+
+
+class GridSpectrum:
+    """What DeviceGrid.spectrum returns (include/mc33_hip.h: mc33hip_grid_spectrum): isovalues (the doubles that were passed),
+    cut_cells (numpy uint64 [n]: cells the surface of isovalue k cuts), histogram (numpy uint64 [n + 1]: grid points above exactly
+    j of the isovalues), points, cells, nan_samples, sample_min, sample_max."""
+
+    def __init__(self, isovalues, cut_cells, histogram, points, cells, nan_samples, sample_min, sample_max):
+        self.isovalues, self.cut_cells, self.histogram = list(isovalues), cut_cells, histogram
+        self.points, self.cells, self.nan_samples = int(points), int(cells), int(nan_samples)
+        self.sample_min, self.sample_max = float(sample_min), float(sample_max)
+
+    def busiest(self):
+        """the isovalue whose surface cuts the most cells (None without isovalues)"""
+        return self.isovalues[int(self.cut_cells.argmax())] if len(self.isovalues) else None
+
+    def __repr__(self):
+        return "GridSpectrum(n=%d, points=%d, cells=%d, nan_samples=%d, range=[%r, %r])" % (
+            len(self.isovalues), self.points, self.cells, self.nan_samples, self.sample_min, self.sample_max)
 
 
 class SurfaceMeasures:
@@ -818,6 +869,37 @@ class DeviceGrid:
         if getattr(self, "inclined", None):
             g.set_inclined(*self.inclined)
         return g
+
+    # -- the contour spectrum of the resident grid (mc33_hip.h: mc33hip_grid_spectrum) ----------------------------------------------
+    def resident_range(self):
+        """the cell slices whose planes are all resident: the whole grid, or a z-slab's own"""
+        return Range(self.desc.plane0, self.desc.plane0 + self.desc.npz_resident - 1, 0, 0)
+
+    def spectrum(self, isos, rng=None):
+        """For up to 255 isovalues, strictly ascending as MC33_real: how many cells of cell slices rng (default: every slice
+        whose planes are resident) the surface cuts at each, the histogram of the samples between them, the NaN samples and the
+        range of the others - one pass over the grid, a few KB come back: a GridSpectrum.  MC33Error(EINVAL) for what the
+        library refuses (include/mc33_hip.h)."""
+        import numpy as np
+        rng = rng or self.resident_range()
+        isos = [float(x) for x in isos]
+        n = len(isos)
+        arr = (C.c_double * max(n, 1))(*isos)
+        cut = np.zeros(n, np.uint64)
+        hist = np.zeros(n + 1, np.uint64)
+        a = Spectrum()
+        a.isos, a.n = C.cast(arr, C.POINTER(C.c_double)), min(n, 0xFFFFFFFF)
+        a.cut_cells = cut.ctypes.data_as(C.POINTER(C.c_ulonglong)) if n else None
+        a.histogram = hist.ctypes.data_as(C.POINTER(C.c_ulonglong))
+        _check(self.lib, self.lib.mc33hip_grid_spectrum(self.ctx, C.byref(rng), C.byref(a)))
+        return GridSpectrum(isos, cut, hist, a.points, a.cells, a.nan_samples, a.sample_min, a.sample_max)
+
+    def spectrum_ladder(self, n, rng=None):
+        """The spectrum at n isovalues spread evenly strictly inside the range of the samples: a first call without isovalues
+        finds that range, isovalue_ladder makes the steps.  ValueError when the samples have no range to spread steps over (a
+        constant or all-NaN grid, infinite samples)."""
+        first = self.spectrum([], rng)
+        return self.spectrum(isovalue_ladder(first.sample_min, first.sample_max, n, self.dtype), rng)
 
     def probe_read(self, reps=10):
         """A plain read of the resident grid (nothing to do with an extraction): (best ms, median ms, bytes)."""

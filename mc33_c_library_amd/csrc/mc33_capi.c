@@ -78,6 +78,8 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_resample_grid
 #pragma weak mc33hip_context_device
 #pragma weak mc33hip_adopt_device /* (the host layer uses it for the resampled grid only) */
+/* ... and the contour spectrum (MC33_grid_spectrum): without it that function returns -1 */
+#pragma weak mc33hip_grid_spectrum
 _Static_assert(sizeof(mc33_component) == sizeof(mc33hip_component) && offsetof(mc33_component, area) == offsetof(mc33hip_component, area),
                "mc33_component and mc33hip_component are one layout");
 
@@ -105,6 +107,7 @@ typedef struct {
 	int rc;
 	struct mc33_surface *out;   /* the surface being filled, and where this slab's vertices / triangles begin in it */
 	unsigned long long vbase, tbase;
+	mc33hip_spectrum *spectrum; /* MC33_grid_spectrum: this slab's share, for the length of the call */
 } mc33_slab;
 
 /* private object: the public MC33 first, so callers can keep treating the pointer as MC33* */
@@ -1618,4 +1621,66 @@ _GRD *MC33_resampled_grid(MC33 *M) {
 		return 0;
 	}
 	return Z;
+}
+
+/* --- extension: the contour spectrum of the grid, one pass per slab ------------------------------------------------------------------ */
+int MC33_isovalue_ladder(double lo, double hi, unsigned n, MC33_real *out) {
+	if (!out || n > 255u || !(lo >= -DBL_MAX && lo <= DBL_MAX) || !(hi >= -DBL_MAX && hi <= DBL_MAX) || !(lo < hi))
+		return -1;
+	for (unsigned k = 0; k != n; k++) {
+		out[k] = (MC33_real)(lo + (hi - lo) * ((double)(k + 1u) / (double)(n + 1u)));
+		if (k && !(out[k - 1u] < out[k])) /* (steps closer than MC33_real resolves) */
+			return -1;
+	}
+	return (int)n;
+}
+
+static void *slab_spectrum(void *arg) {
+	mc33_slab *s = (mc33_slab *)arg;
+	mc33hip_range r;
+	r.z_begin = s->z_begin; r.z_end = s->z_end; r.ghost_below = 0; r.id_base = 0;
+	s->rc = mc33hip_grid_spectrum(s->ctx, &r, s->spectrum);
+	return 0;
+}
+
+int MC33_grid_spectrum(MC33 *M, const MC33_real *isovalues, unsigned count, unsigned long long *cut_cells, unsigned long long *histogram,
+                       mc33_spectrum_info *info) {
+	mc33_private *p = priv(M);
+	if (!p || !mc33hip_grid_spectrum || count > 255u || !histogram || (count && (!isovalues || !cut_cells)))
+		return -1;
+	/* every slab's struct, the isovalues as doubles and every slab's two arrays in one block */
+	const size_t ns = (size_t)p->nslab, words = 2u * (size_t)count + 1u;
+	char *blk = (char *)malloc(ns * sizeof(mc33hip_spectrum) + 256u * sizeof(double) + ns * words * sizeof(unsigned long long));
+	if (!blk)
+		return -1;
+	mc33hip_spectrum *sp = (mc33hip_spectrum *)blk;
+	double *iso = (double *)(sp + ns);
+	unsigned long long *w = (unsigned long long *)(iso + 256);
+	for (unsigned k = 0; k != count; k++) iso[k] = (double)isovalues[k];
+	for (size_t k = 0; k != ns; k++) {
+		memset(&sp[k], 0, sizeof sp[k]);
+		sp[k].isos = iso; sp[k].n = count;
+		sp[k].cut_cells = w + k * words; sp[k].histogram = w + k * words + count;
+		p->slab[k].spectrum = &sp[k];
+	}
+	int rc = refresh_grid(p); /* (samples the caller said it rewrote: uploaded first, as before a count) */
+	if (rc == MC33HIP_OK) rc = run_slabs(p, slab_spectrum);
+	for (size_t k = 0; k != ns; k++) p->slab[k].spectrum = 0;
+	if (rc == MC33HIP_OK) { /* integers add, extremes combine; nothing is written on failure */
+		mc33_spectrum_info t;
+		memset(&t, 0, sizeof t);
+		t.sample_min = sp[0].sample_min; t.sample_max = sp[0].sample_max;
+		for (unsigned j = 0; j != count; j++) cut_cells[j] = 0;
+		for (unsigned j = 0; j <= count; j++) histogram[j] = 0;
+		for (size_t k = 0; k != ns; k++) {
+			for (unsigned j = 0; j != count; j++) cut_cells[j] += sp[k].cut_cells[j];
+			for (unsigned j = 0; j <= count; j++) histogram[j] += sp[k].histogram[j];
+			t.points += sp[k].points; t.cells += sp[k].cells; t.nan_samples += sp[k].nan_samples;
+			if (sp[k].sample_min < t.sample_min) t.sample_min = sp[k].sample_min;
+			if (sp[k].sample_max > t.sample_max) t.sample_max = sp[k].sample_max;
+		}
+		if (info) *info = t;
+	}
+	free(blk);
+	return rc == MC33HIP_OK ? 0 : -1;
 }

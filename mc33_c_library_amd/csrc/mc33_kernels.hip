@@ -50,6 +50,9 @@
 // Before an extraction: k_rs_resample - the resident grid into a second device grid, a separable correlation of up to 17 taps per axis
 //                   with an integer stride, one pass over the source: a block stages the rows its tile of outputs needs in LDS,
 //                   sums along x and y into a ring of planes and along z out of it (mc33_resample.hip.h).
+//                   k_sp_spectrum - the contour spectrum of the resident grid for up to 255 isovalues in one pass: every sample
+//                   ranked among the isovalues in LDS, cells cut and samples counted per rank in the block's LDS counters, 64-bit
+//                   device counters once per block; k_sp_init clears those (mc33_spectrum.hip.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -112,3 +115,4 @@ typedef float sample_t;
 #include "mc33_smooth.hip.h"
 #include "mc33_simplify.hip.h"
 #include "mc33_resample.hip.h"
+#include "mc33_spectrum.hip.h"

@@ -270,3 +270,23 @@ def extract_slab_many(grid, slab, exchange, isos, b0=0, async_op=False, on_emitt
             on_emitted(i)
         out.append((counts, mine[i]))
     return out
+
+
+def reduce_spectrum(spectrum, group=None):
+    """The contour spectrum of the whole grid from the ranks' own: every rank passes what DeviceGrid.spectrum returned for ITS
+    cell slices (Slab.range(); the same isovalues on every rank) and receives the sums of the integer fields - cut_cells,
+    histogram, points, cells, nan_samples - and the extremes of sample_min / sample_max over the ranks of `group`, as a new
+    GridSpectrum.  The integers travel as int64 and the extremes as float64: nothing is rounded.  The tensors are host tensors
+    (a few KB), so the group needs a backend that reduces them (gloo, or a group made for counts)."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    from .api import GridSpectrum
+    n = len(spectrum.isovalues)
+    ints = torch.from_numpy(np.concatenate([np.asarray(spectrum.cut_cells, np.uint64), np.asarray(spectrum.histogram, np.uint64),
+                                            np.array([spectrum.points, spectrum.cells, spectrum.nan_samples], np.uint64)]).view(np.int64).copy())
+    ext = torch.tensor([-spectrum.sample_min, spectrum.sample_max], dtype=torch.float64)   # (one MAX serves both)
+    dist.all_reduce(ints, op=dist.ReduceOp.SUM, group=group)
+    dist.all_reduce(ext, op=dist.ReduceOp.MAX, group=group)
+    w = ints.numpy().view(np.uint64)
+    return GridSpectrum(spectrum.isovalues, w[:n].copy(), w[n:2 * n + 1].copy(), w[2 * n + 1], w[2 * n + 2], w[2 * n + 3], -float(ext[0]), float(ext[1]))
