@@ -99,7 +99,9 @@ int mc33hip_set_inclined(mc33hip_ctx *c, const double *grd_A, const double *grd_
  * 1246-1250).  The libMC33_<type>_nneg.so flavour of the host layer switches it on in create_MC33. */
 int mc33hip_set_normal_neg(mc33hip_ctx *c, int on);
 
-/* Stream all work is enqueued on (a hipStream_t passed as void*; NULL = the default stream). */
+/* Stream all work is enqueued on (a hipStream_t passed as void*; NULL = the default stream).  A caller that names its stream
+ * orders its own work by it, and mc33hip_extract makes use of that: see "Completion" there.  Waits for whatever the context still
+ * has on the stream it leaves. */
 int mc33hip_set_stream(mc33hip_ctx *c, void *hip_stream);
 /* ... or a non-blocking stream of the context's own, for callers without a HIP runtime of their own that drive several contexts
  * side by side (create_MC33 with MC33_HIP_DEVICES: one context per z-slab). */
@@ -170,9 +172,24 @@ int mc33hip_emit_download(mc33hip_ctx *c, void *dV, void *dN, void *dT, unsigned
                           void *hV, void *hN, void *hT);
 int mc33hip_download_wait(mc33hip_ctx *c);
 
-/* Whole extraction (count + emit) with ONE synchronisation at the end; fails with MC33HIP_ECAPACITY
+/* Whole extraction (count + emit) with ONE wait; fails with MC33HIP_ECAPACITY
  * (and reports the needed sizes in *out) when the buffers are too small.  This is the path
- * calculate_isosurface (MC:1816-1889) and bench.py use. */
+ * calculate_isosurface (MC:1816-1889) and bench.py use.
+ * Completion.  The COUNTS (*out, the return code, MC33HIP_ECAPACITY included) are complete on return, always.  The OUTPUT ARRAYS are
+ *   - complete on return when the context works on the default stream it was created with or on a stream of its own
+ *     (mc33hip_own_stream), when timing is on (mc33hip_set_timing > 0), and whenever the call fails;
+ *   - complete IN STREAM ORDER when the caller named the stream (mc33hip_set_stream, NULL included): the call returns as soon as
+ *     the device has handed over the counters, with emit passes still queued or running on that stream.  The pass that writes
+ *     the triangles hands them over as it starts: it runs first - and the call returns a whole emit stage early - up to 6 M work
+ *     records; beyond that, or when the slow records run beside the fast ones, it runs behind the pass that writes
+ *     V and N, and the call returns when only the triangle pass (and the slow pass) are left.  Kernels and copies
+ *     the caller enqueues on the same stream behind the call see the arrays complete, and so does the next mc33hip_extract,
+ *     which is enqueued behind the passes at once.  Every other entry point of the context - mc33hip_count, mc33hip_emit,
+ *     mc33hip_synchronize, the downloads (the concurrent ones too), mc33hip_set_stream, mc33hip_set_timing, mc33hip_last_timing,
+ *     uploads, mc33hip_adopt_device, the measuring / filtering / smoothing calls, mc33hip_destroy - waits for them first.  Reading
+ *     the arrays by a road that is NOT ordered by the stream (another stream, a host pointer to the same memory, another
+ *     process) needs mc33hip_synchronize first, as after mc33hip_emit.
+ * When the arrays are too small, or the call fails otherwise, nothing has been written to them. */
 int mc33hip_extract(mc33hip_ctx *c, double iso, const mc33hip_range *range, void *dV, void *dN, void *dT,
                     unsigned long long capV, unsigned long long capT, mc33hip_counts *out);
 

@@ -105,6 +105,7 @@ struct TailSet {
 	bool alias_known;         // ... and whether it had slow cells at all (Counters::alias_cells; alias_last: how many)
 	uint32_t alias_last;
 	bool alias_gated;         // the last tail into this set left the slow kernels out (enqueue_tail): its counts and surface stand only if it had no slow cells
+	uint32_t seq;             // the sequence word of the last extraction that returned at its counts (counters_seq(h_ctr): wait_counters)
 	Counters *d_ctr, *h_ctr;
 	bool ctr_published;       // the emit pass enqueued last leaves the counters in h_ctr itself (k_emit_fast_triangles)
 };
@@ -126,6 +127,7 @@ struct mc33hip_ctx {
 	int device;
 	hipStream_t stream;
 	bool own_stream;          // the stream came from the pool (mc33hip_own_stream) and goes back there
+	bool stream_given;        // the caller named the stream (mc33hip_set_stream): its work is ordered by it, and mc33hip_extract may return at the counts
 	sample_t *d_grid;
 	bool owns_grid;
 	size_t pitch, slice;  // in samples
@@ -163,6 +165,8 @@ struct mc33hip_ctx {
 	                          // slow kernels out (enqueue_tail)
 	hipEvent_t ev_dl[2];      // mc33hip_emit_download: behind the pass that completes T / behind the one that completes V and N
 	bool emit_pending;        // an emit was enqueued after the last timing read
+	uint32_t emit_queued;     // extractions that returned when their counts were known, their emit passes still queued or running ...
+	uint32_t emit_finished;   // ... and up to which of them the stream has been waited for since (finish_pending_emit)
 	int timing_level;         // MC33_HIP_TIMING: 0 none (default), 1 whole call, 2 per pass - the event records cost ~20 us per call
 	bool inclined, triangular;   // non-orthogonal grid (MC33_spnC): _GRD._A / _GRD.A_ as given
 	bool normal_neg;             // front and back exchanged (the reference's MC33_NORMAL_NEG compile-time switch)
@@ -212,9 +216,29 @@ static void read_switches(Switches &w) {
 	w.debug = env_u32("MC33_HIP_DEBUG", 0); w.cells_dev = env_u32("MC33_HIP_CELLS_DEV", 0);
 }
 
-static int use_device(mc33hip_ctx *c) {
-	HIP_TRY(hipSetDevice(c->device));
+// An extraction on a caller's stream returns when its counts are known (count_until_fits), with its emit passes still queued or
+// running.  Whatever is ordered by that stream needs nothing: the next extraction, a caller's kernels and copies.  Everything else
+// waits here first: what reads the outputs by another road (the copy stream), what frees or regrows buffers the passes use, what
+// changes the stream, what reads events.  Every entry point comes through use_device, which is where most of them get it.
+// (Two counters, not a flag: mc33hip_download_concurrent / mc33hip_download_many may come from another thread than the context's.
+// A thread notes how many extractions had returned early when it came, waits for the stream - which covers all of them, their
+// passes were enqueued before they were counted - and only then records that number as finished, never lowering it: a thread
+// that arrives while another is still waiting waits too, and an extraction that returns meanwhile stays pending.)
+static bool emit_pending_now(const mc33hip_ctx *c) {
+	return __atomic_load_n(&c->emit_finished, __ATOMIC_ACQUIRE) != __atomic_load_n(&c->emit_queued, __ATOMIC_ACQUIRE);
+}
+static int finish_pending_emit(mc33hip_ctx *c) {
+	const uint32_t upto = __atomic_load_n(&c->emit_queued, __ATOMIC_ACQUIRE);
+	if (__atomic_load_n(&c->emit_finished, __ATOMIC_ACQUIRE) == upto) return 0;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	uint32_t seen = __atomic_load_n(&c->emit_finished, __ATOMIC_RELAXED);
+	while ((int32_t)(upto - seen) > 0 && !__atomic_compare_exchange_n(&c->emit_finished, &seen, upto, false, __ATOMIC_ACQ_REL, __ATOMIC_RELAXED)) {}
 	return 0;
+}
+// keep_emit: the call is the next extraction over the same range on the same stream - nothing of the host's is in the passes' way
+static int use_device(mc33hip_ctx *c, bool keep_emit = false) {
+	HIP_TRY(hipSetDevice(c->device));
+	return keep_emit ? 0 : finish_pending_emit(c);
 }
 
 // Side streams are taken from a process-wide pool and handed back, never destroyed: hipStreamDestroy of a stream
@@ -380,8 +404,10 @@ static void forget_sweeps(mc33hip_ctx *c) {  // the grid changed: sweeps made ah
 
 extern "C" int mc33hip_set_stream(mc33hip_ctx *c, void *s) {
 	if (!c) return MC33HIP_EINVAL;
+	if (int rc = use_device(c)) return rc;  // (what the old stream still holds is finished on the old stream)
 	if (c->own_stream) { pool_give(c->device, c->stream); c->own_stream = false; }
 	c->stream = (hipStream_t)s;
+	c->stream_given = true;
 	return MC33HIP_OK;
 }
 
@@ -395,6 +421,7 @@ extern "C" int mc33hip_own_stream(mc33hip_ctx *c) {
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	c->stream = st;
 	c->own_stream = true;
+	c->stream_given = false;
 	return MC33HIP_OK;
 }
 

@@ -22,6 +22,7 @@ struct EmitArgs {
 	uint32_t stage_rows;  // every sample row of the grid starts on a 16-byte boundary: k_emit_vertices may stage rows in LDS
 	Counters *host_ctr;   // pinned host copy of the counters: the triangle pass (the last kernel of an extraction) leaves them there
 	uint32_t alias_gated; // the tail left the slow kernels out (enqueue_tail): with slow cells after all, its records are not complete - refuse
+	uint32_t seq;         // (or 0) what the triangle pass stores behind the counters in host_ctr (counters_seq): the host is waiting for it
 };
 
 // The fast emit passes take the records in storage order, which k_slots made (4 slices of a tile column, next
@@ -487,6 +488,12 @@ __global__ __launch_bounds__(256) void k_emit_fast_triangles(const EmitArgs a) {
 		volatile uint32_t *dst = (volatile uint32_t *)a.host_ctr;
 		const uint32_t k = threadIdx.x;
 		dst[k] = k == offsetof(Counters, emit_skipped) / 4 ? (ok ? 0u : 1u) : src[k];
+		// A host that returns at the counts (count_until_fits) spins on the sequence word: it goes last, behind a system-scope
+		// release of the wave's counter words (all in this one wave), by a plain vector store of one lane.
+		if (a.seq) {
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+			if (k == 0) __hip_atomic_store(counters_seq(a.host_ctr), a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+		}
 	}
 	if (!ok) return;
 	const URef ids{&s_id[0][threadIdx.x], 256};

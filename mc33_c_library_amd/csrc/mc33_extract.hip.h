@@ -69,7 +69,9 @@ static int ensure_set(mc33hip_ctx *c, TailSet &w, uint64_t hint = 0) {
 		HIP_TRY(hipMalloc(&w.d_ctr, sizeof(Counters)));
 		HIP_TRY(hipMemset(w.d_ctr, 0, sizeof(Counters)));  // (live_cursor: every tail leaves it zero for the next)
 		HIP_TRY(hipMalloc(&w.list_cnt, 2 * LIST_CHUNKS * sizeof(uint32_t)));
-		HIP_TRY(hipHostMalloc(&w.h_ctr, sizeof(Counters), hipHostMallocDefault));
+		HIP_TRY(hipHostMalloc(&w.h_ctr, COUNTERS_HOST_BYTES, hipHostMallocDefault));  // (counters, then the sequence word: counters_seq)
+		memset(w.h_ctr, 0, COUNTERS_HOST_BYTES);
+		w.seq = 0;
 	}
 	if (w.seg_cap < c->nsegs) {
 		if (int rc = dev_room_all("row-segment arrays", &w.seg_cap, c->nsegs,
@@ -627,9 +629,10 @@ static int enqueue_sweep_many(mc33hip_ctx *c, const double *isos, int n, bool ta
 struct DownloadPlan { void *hV, *hN, *hT; size_t bV, bN, bT; };
 
 static int enqueue_emit(mc33hip_ctx *c, void *dV, void *dN, void *dT, uint64_t capV, uint64_t capT, const DownloadPlan *dl = nullptr,
-                        const unsigned long long *dev_base = nullptr) {
+                        const unsigned long long *dev_base = nullptr, uint32_t seq = 0) {
 	EmitArgs a;
 	a.dev_base = dev_base;
+	a.seq = seq;
 	c->count_unused = false;  // (the count has served an emit: the next count of this isovalue is made anew)
 	a.c.tab = tables(c);
 	a.c.P = c->P;
@@ -756,11 +759,8 @@ static int enqueue_emit(mc33hip_ctx *c, void *dV, void *dN, void *dT, uint64_t c
 	return 0;
 }
 
-static int fetch_counters(mc33hip_ctx *c) {
-	// (after an emit pass the triangle kernel has already written them into h_ctr: only the wait is left)
-	if (!c->w->ctr_published) HIP_TRY(hipMemcpyAsync(c->w->h_ctr, c->w->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-	c->w->ctr_published = true;  // (h_ctr matches the set's counters until the next tail into this set: enqueue_tail)
-	HIP_TRY(hipStreamSynchronize(c->stream));  // (polling the stream before blocking - hipStreamQuery for up to 3 ms - gains nothing: 1.086 / 1.087 / 1.097 against 1.063 / 1.094 / 1.126 ms per step at 1024^3, round 4)
+// what the host keeps of a set's counters once they are in h_ctr: the shape of the next tail and emit into this set
+static void note_counters(mc33hip_ctx *c) {
 	c->w->records_hint = c->w->h_ctr->entry_cursor == 0xFFFFFFFFu ? 0u : c->w->h_ctr->entry_cursor;
 	c->w->slow_hint = c->w->h_ctr->slow_cursor + 1u;
 	c->w->count_known = true; c->w->count_needed = c->w->h_ctr->count_pending != 0u;
@@ -769,6 +769,46 @@ static int fetch_counters(mc33hip_ctx *c) {
 		fprintf(stderr, "[mc33hip] cut cells %u (slow %u - cells with a corner equal to the isovalue %u -, dirty segments %u, record batches %u%s)\n",
 		        c->w->h_ctr->entry_cursor, c->w->h_ctr->slow_cursor, c->w->h_ctr->alias_cells, c->w->h_ctr->dirty_cursor, c->w->h_ctr->batch_cursor,
 		        c->w->alias_gated ? "; slow kernels left out" : "");
+}
+
+// The counters of an extraction whose triangle pass was given the sequence word `seq` (enqueue_emit), without waiting for all of
+// the emit passes: the first wave of that pass leaves counters, emit_skipped and then the word in pinned memory.  How early that
+// is depends on where enqueue_emit puts the pass: first behind the tail while the record set fits the last-level cache (tri_first:
+// up to 6 M records, the single-GPU float bench) - the call then returns with both fast passes still to run - but behind the
+// vertex pass with more records or with the slow pass on its own stream (2048 x 2048 x 1024 ushort), where the call returns
+// only once k_emit_vertices is through and little is gained.  That is the price of publishing from this pass and not from
+// k_scan_apply (count_until_fits says why).  The wait is bounded: past the deadline the stream is synchronised as ever, which
+// finds the counters there all the same.
+static inline void spin_pause() {
+#if defined(__x86_64__) || defined(__i386__)
+	__builtin_ia32_pause();
+#elif defined(__aarch64__)
+	asm volatile("yield" ::: "memory");
+#else
+	std::this_thread::yield();
+#endif
+}
+static int wait_counters(mc33hip_ctx *c, uint32_t seq) {
+	const uint32_t *word = counters_seq(c->w->h_ctr);
+	const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(50);
+	for (uint32_t spins = 0; __atomic_load_n(word, __ATOMIC_ACQUIRE) != seq; spins++) {
+		spin_pause();
+		if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() > deadline) {
+			HIP_TRY(hipStreamSynchronize(c->stream));
+			if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != seq) { set_err("the counters of the extraction did not arrive"); return MC33HIP_ERUNTIME; }
+			break;
+		}
+	}
+	note_counters(c);
+	return 0;
+}
+
+static int fetch_counters(mc33hip_ctx *c) {
+	// (after an emit pass the triangle kernel has already written them into h_ctr: only the wait is left)
+	if (!c->w->ctr_published) HIP_TRY(hipMemcpyAsync(c->w->h_ctr, c->w->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+	c->w->ctr_published = true;  // (h_ctr matches the set's counters until the next tail into this set: enqueue_tail)
+	HIP_TRY(hipStreamSynchronize(c->stream));  // (polling the stream before blocking - hipStreamQuery for up to 3 ms - gains nothing: 1.086 / 1.087 / 1.097 against 1.063 / 1.094 / 1.126 ms per step at 1024^3, round 4)
+	note_counters(c);
 	if (c->w->h_ctr->debug[0])
 		fprintf(stderr, "[mc33hip] DEBUG words %u: first %u count %u z %u y0 %u xbase %u batch %u of %u\n", c->w->h_ctr->debug[0], c->w->h_ctr->debug[1], c->w->h_ctr->debug[2],
 		        c->w->h_ctr->debug[3], c->w->h_ctr->debug[4], c->w->h_ctr->debug[5], c->w->h_ctr->debug[6], c->w->h_ctr->debug[7]);
@@ -837,8 +877,8 @@ static void read_timing(mc33hip_ctx *c, bool with_emit, unsigned launches) {
 
 // What every call that classifies the grid begins with: the device, the range, the last count forgotten, c->P / c->range / c->nsegs
 // for this isovalue and range, the buffers of set 0
-static int begin_call(mc33hip_ctx *c, double iso, const mc33hip_range *range) {
-	int rc = use_device(c);
+static int begin_call(mc33hip_ctx *c, double iso, const mc33hip_range *range, bool keep_emit = false) {
+	int rc = use_device(c, keep_emit);
 	if (rc) return rc;
 	if ((rc = check_range(c, range))) return rc;
 	c->counted = false;
@@ -853,19 +893,44 @@ static int begin_call(mc33hip_ctx *c, double iso, const mc33hip_range *range) {
 //     that the set has slow cells;
 //   - when the records did not fit: nothing was emitted, the record arrays grow to what the counters ask for.
 // A repeated round keeps the sweep's result (enqueue_count: rerun).
+// A call that emits on a stream the caller named returns when its counts are known (returns_at_counts): the triangle pass hands
+// counters and emit_skipped - the device's own verdict on capacity, record overflow and alias miss, the one every emit kernel
+// reaches (emit_prepare) - to the host as it starts, and an extraction that fits leaves its emit passes to the stream
+// (mc33hip_ctx::emit_queued, finish_pending_emit).  A round that does not fit has emitted nothing; the stream is drained as before.
+// Where this departs from the plan it was built to (k_scan_apply publishes; emit_skipped in a pinned word of its own; the host
+// decides the fit with a function it shares with emit_prepare):
+//   - the counters are published by k_emit_fast_triangles.  No block of k_scan_apply has them all: the totals are written by its
+//     last block, live_cursor and alias_cells by block 0, the ghost offsets by the block that holds the first emitted segment,
+//     so publishing from there takes a grid-wide ticket - an atomic per block on one word, 2 045 of them at 1024^3 in a 12 us
+//     kernel that everything behind it waits for.  The triangle pass already left the counters in h_ctr as its first wave starts;
+//   - emit_skipped stays a word of h_ctr: that same wave writes the verdict of ITS emit_prepare there, in front of the sequence
+//     word, so the host has the device's own decision when it has the counters and needs neither a second pinned word nor a
+//     comparison of its own that could differ from the device's.
 struct EmitTargets { void *dV, *dN, *dT; unsigned long long capV, capT; };
+static bool returns_at_counts(const mc33hip_ctx *c) {
+	// (the developer traces are read back through the null stream when the counters are there: fetch_counters)
+	return c->stream_given && !c->own_stream && c->timing_level == 0 && !c->sw.trace_cells && !c->sw.trace_file;
+}
 static int count_until_fits(mc33hip_ctx *c, const EmitTargets *emit) {
 	unsigned launches = 0;
+	const bool early = emit && returns_at_counts(c);
 	for (;;) {
 		c->alias_gate = true;
 		int rc = enqueue_count(c, launches > 0);
 		c->alias_gate = false;
 		if (rc) return rc;
 		launches++;
-		if (emit && (rc = enqueue_emit(c, emit->dV, emit->dN, emit->dT, emit->capV, emit->capT))) return rc;
-		if ((rc = fetch_counters(c))) return rc;
+		uint32_t seq = 0;
+		if (early) seq = ++c->w->seq ? c->w->seq : ++c->w->seq;  // (never 0: no word asked for)
+		if (emit && (rc = enqueue_emit(c, emit->dV, emit->dN, emit->dT, emit->capV, emit->capT, nullptr, nullptr, seq))) return rc;
+		if ((rc = early ? wait_counters(c, seq) : fetch_counters(c))) return rc;
 		const bool miss = c->w->alias_gated && c->w->h_ctr->alias_cells != 0u;
-		if (c->w->h_ctr->entry_cursor <= c->w->entry_cap && !miss) break;
+		const bool fits = c->w->h_ctr->entry_cursor <= c->w->entry_cap && !miss;
+		if (early) {
+			if (fits && !c->w->h_ctr->emit_skipped) __atomic_fetch_add(&c->emit_queued, 1u, __ATOMIC_ACQ_REL);
+			else HIP_TRY(hipStreamSynchronize(c->stream));  // (nothing was emitted; what follows frees or reuses what the passes look at)
+		}
+		if (fits) break;
 		if (c->w->h_ctr->entry_cursor > c->w->entry_cap && (rc = grow_entries(*c->w, c->w->h_ctr->entry_cursor))) return rc;
 	}
 	read_timing(c, emit != nullptr, launches);
@@ -919,6 +984,7 @@ extern "C" int mc33hip_set_normal_neg(mc33hip_ctx *c, int on) {
 
 extern "C" int mc33hip_set_timing(mc33hip_ctx *c, int level) {
 	if (!c || level < 0 || level > 2) return MC33HIP_EINVAL;
+	if (int rc = use_device(c)) return rc;  // (an emit still queued was enqueued without events)
 	c->timing_level = level;
 	return MC33HIP_OK;
 }
@@ -1010,7 +1076,7 @@ extern "C" int mc33hip_emit_download(mc33hip_ctx *c, void *dV, void *dN, void *d
 
 extern "C" int mc33hip_download_wait(mc33hip_ctx *c) {
 	if (!c) return MC33HIP_EINVAL;
-	if (hipSetDevice(c->device) != hipSuccess) return MC33HIP_ERUNTIME;
+	if (use_device(c)) return MC33HIP_ERUNTIME;
 	HIP_TRY(hipStreamSynchronize(c->copy));    // (ordered behind the passes by the events: the arrays are complete and on the host)
 	HIP_TRY(hipStreamSynchronize(c->stream));  // (... and nothing of the emit is left running when the caller gets its surface)
 	return prop_check(c);
@@ -1019,7 +1085,11 @@ extern "C" int mc33hip_download_wait(mc33hip_ctx *c) {
 extern "C" int mc33hip_extract(mc33hip_ctx *c, double iso, const mc33hip_range *range, void *dV, void *dN, void *dT,
                                unsigned long long capV, unsigned long long capT, mc33hip_counts *out) {
 	if (!c) return MC33HIP_EINVAL;
-	int rc = begin_call(c, iso, range);
+	// The extraction before this one may still be emitting (it returned at its counts).  Over the same range on the same stream
+	// this one is enqueued behind it as it is: no buffer of the context changes size between two extractions of one range, and
+	// the host reads nothing of the set before this call's own counters arrive.  Anything else waits for the emit first.
+	const bool keep_emit = emit_pending_now(c) && range && same_range(*range, c->range) && returns_at_counts(c);
+	int rc = begin_call(c, iso, range, keep_emit);
 	if (rc) return rc;
 	const EmitTargets emit{dV, dN, dT, capV, capT};
 	if ((rc = count_until_fits(c, &emit))) return rc;
@@ -1031,6 +1101,7 @@ extern "C" int mc33hip_extract(mc33hip_ctx *c, double iso, const mc33hip_range *
 
 extern "C" int mc33hip_last_timing(mc33hip_ctx *c, mc33hip_timing *t) {
 	if (!c || !t) return MC33HIP_EINVAL;
+	if (int rc = use_device(c)) return rc;
 	if (c->timing_level == 0) {  // no events were recorded for the last call: zeros, not an older call's numbers
 		c->emit_pending = false;
 		c->timing.sweep_ms = c->timing.scan_ms = c->timing.emit_ms = c->timing.total_ms = 0.f;
@@ -1122,7 +1193,7 @@ extern "C" int mc33hip_synchronize(mc33hip_ctx *c) {
 
 extern "C" int mc33hip_download_many(mc33hip_ctx *c, int n, void *const *dst, const void *const *src, const size_t *bytes, int concurrent) {
 	if (!c || n < 0 || (n && (!dst || !src || !bytes))) return MC33HIP_EINVAL;
-	if (hipSetDevice(c->device) != hipSuccess) return MC33HIP_ERUNTIME;  // (the concurrent form may come from another thread)
+	if (use_device(c)) return MC33HIP_ERUNTIME;  // (the concurrent form may come from another thread; the copy stream is not ordered behind an emit still queued)
 	hipStream_t st = concurrent ? c->copy : c->stream;
 	for (int k = 0; k < n; k++) {
 		if (!bytes[k]) continue;
@@ -1136,7 +1207,7 @@ extern "C" int mc33hip_download_many(mc33hip_ctx *c, int n, void *const *dst, co
 extern "C" int mc33hip_download_concurrent(mc33hip_ctx *c, void *dst, const void *src, size_t bytes) {
 	if (!c || (bytes && (!dst || !src))) return MC33HIP_EINVAL;
 	if (!bytes) return MC33HIP_OK;
-	if (hipSetDevice(c->device) != hipSuccess) return MC33HIP_ERUNTIME;  // (may be another thread than the context's)
+	if (use_device(c)) return MC33HIP_ERUNTIME;  // (may be another thread than the context's; as above)
 	if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->copy) != hipSuccess) return MC33HIP_ERUNTIME;
 	return hipStreamSynchronize(c->copy) == hipSuccess ? MC33HIP_OK : MC33HIP_ERUNTIME;
 }

@@ -19,6 +19,11 @@ struct Counters {
 	uint32_t alias_cells;   // cells k_cells left to the slow kernels - a corner equal to the isovalue (k_scan_apply adds up the list groups)
 	uint32_t pad_;
 };
+// The pinned host copy of a set's counters is followed, in a cache line of its own, by a sequence word: the kernel that leaves the
+// counters there stores the number the host chose for this extraction behind them, and the host waits for that number
+constexpr size_t COUNTERS_HOST_BYTES = 256;
+__host__ __device__ inline uint32_t *counters_seq(Counters *host_ctr) { return (uint32_t *)((char *)host_ctr + 128); }
+static_assert(sizeof(Counters) <= 128, "the sequence word lies behind the counters");
 
 // One record per (wave tile, cell slice) of the sweep: the sign-bit rows of the two planes of the slice,
 // exactly as the wave held them (word k of sample row r in lane r).  k_sweep fills the records of slices

@@ -172,8 +172,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 #define MC33_LOAD(rs, vo, so) (__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, so, MC33_SWEEP_AUX)))
 #endif
 	typedef typename std::conditional<S == 1, real_t, uint32_t>::type raw_t;  // what a load leaves in a register
-	// every batch is exactly 17 loads, whatever the position in the tile (the wait counts the compiler
-	// derives are then exact and the prefetched batch really stays in flight)
+	// A batch is the same number of loads whatever the position in the tile, so that the wait counts the compiler derives keep
+	// the prefetched batch in flight: exactly 17 in the forms that always issue the halo load (several isovalues, double
+	// samples); 16 or 17 in the single-isovalue forms over 1- to 4-byte samples, whose halo load stands behind a branch (below)
 	auto issue = [&](raw_t (&d)[16], real_t &hv, uint32_t p, uint32_t bi) __attribute__((always_inline)) {
 		const sample_t *base = a.G.p + (uint64_t)(p - a.G.z0) * a.G.slice + (uint64_t)y0 * a.G.pitch;
 		const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, tile_bytes, 0x00020000);
@@ -188,6 +189,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 			}
 		}
 		// (MC33_HIP_DEBUG 64, developer builds: no halo sample is ever fetched - what the one-sample-per-row load costs the stream)
+		if constexpr (NI == 1 && sizeof(real_t) == 4) {  // (double samples: the form costs k_sweep<1, 1, 0> its 129th register - they keep the old one)
+			// The 17th load under a lane condition: a lane that is switched off costs the memory pipeline nothing, a lane that is
+			// refused by the descriptor's range check does (the same measurement as at `fetch` in mc33_emit.hip.h) - and until round 7
+			// 60 lanes of this load were refused in the waves that need it, all 64 in the three waves of a grouped block that take
+			// their halo bits from the mailbox.  What the compiler makes of it (read in the gfx950 code of k_sweep<1, 1, 0>):
+			// s_and_saveexec_b64 / s_cbranch_execz around the load - it keeps such a branch around any memory instruction - so a wave
+			// whose lanes all stay out (from_right) issues 16 loads per batch, every other wave 17 with four lanes on, and the waits
+			// are derived for the smaller number: vmcnt(16) where the old form had vmcnt(17).  Exact for the three mailbox waves of a
+			// grouped block; a wave that does load its halo - the fourth of a grouped block, every wave of an ungrouped one (grids
+			// narrower than four row segments, the segments behind the last whole group) - waits until the FIRST load of the
+			// prefetched batch has come back as well, the other 16 still in flight.  Two copies of the batch loop, one per kind of
+			// wave, would make the counts exact in both and double a 30 KB kernel; measured instead, grouped and ungrouped shapes:
+			// profiles/r07_dead_time.txt.  The lanes left out keep the value they had, which `process` does not look at.
+			const bool wanted = ((lane / (uint32_t)RB) == bi) & !from_right & !(MC33_DEBUG_BITS(a) & 64u);
+			if (wanted) hv = MC33_LOAD(rs, xh, 0u);
+		} else
 		hv = MC33_LOAD(rs, ((lane / (uint32_t)RB) == bi && !from_right && !(MC33_DEBUG_BITS(a) & 64u)) ? xh : 0xFFFFFFF0u, 0u);
 	};
 	// the four samples of row rr of a batch in word order of layout S
