@@ -268,6 +268,25 @@ surface *MC33_calculate_smoothed_isosurface(MC33 *extractor, MC33_real isovalue,
 typedef struct { double cell[3]; int mode; int drop_duplicates; } mc33_simplification;   /* cell in units of the grid spacing d */
 surface *MC33_calculate_simplified_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_simplification *s);
 
+/* extension (not in the reference): an isosurface cut open by planes, or cropped to a box - what a viewer of nested or closed
+ * surfaces does first.  Of every plane a x + b y + c z + w, in the coordinates of surface.V, the half space >= 0 stays: triangles
+ * inside stay, triangles the plane crosses are cut, and the new vertices on the cut edges are shared by the triangles on either
+ * side, with interpolated normals.  A vertex that lies exactly on a plane is never duplicated.  The cut is not capped.  The exact
+ * definition is in mc33_hip.h (mc33hip_clip_surface).
+ * MC33_clip_box is host C, no GPU: the six planes of the box [lo, hi] in the fixed order x - lo[0], hi[0] - x, y - lo[1],
+ * hi[1] - y, z - lo[2], hi[2] - z - plane[2 a] = +1 on axis a with w = -lo[a], plane[2 a + 1] = -1 on axis a with w = hi[a] -
+ * and n = 6.  It returns 0, or -1 - nothing is written then - for a null pointer, a bound that is not finite or lo[a] >= hi[a].
+ * MC33_calculate_clipped_isosurface extracts the surface into device memory, applies the n <= 6 planes one after another on the
+ * device, colours the FINAL vertices when a property grid and a colour map are set (a new vertex gets the colour of its own
+ * position) and downloads only the kept rows into a caller-owned `surface` like calculate_isosurface's.  n == 0 is plain
+ * extraction; a result without triangles is an empty surface, not a failure.  Inclined grids are accepted: the planes are in the
+ * coordinates of the returned vertices.  The extractor's iso, nV, nT and memoryfault are left as calculate_isosurface leaves them
+ * for a surface of the returned size.  NULL for a null struct, n > 6 and a refused plane (a component that is not finite, or a, b,
+ * c all zero) - the extractor is not touched then -, for an extractor spread over several devices, and on failure (memoryfault 1). */
+typedef struct { unsigned n; double plane[6][4]; } mc33_clip;   /* the coordinates of surface.V */
+surface *MC33_calculate_clipped_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_clip *planes);
+int MC33_clip_box(const double lo[3], const double hi[3], mc33_clip *out);
+
 /* extension (not in the reference): the grid resampled on the GPU before anything is extracted from it.  A Gaussian of about one
  * sample removes the speckle of CT / MRI volumes that otherwise becomes thousands of tiny components; a stride of 2 or 3 per axis
  * gives a preview surface of an eighth or a twenty-seventh of the triangles without extracting the full one first.  Per axis a

@@ -595,6 +595,68 @@ typedef struct {
 } mc33hip_spectrum;
 int mc33hip_grid_spectrum(mc33hip_ctx *c, const mc33hip_range *range, mc33hip_spectrum *s);
 
+/* --- clip a finished mesh by a plane on the device: cut edges, new vertices (no counterpart in the reference) -------------------
+ * V (nV x 3 MC33_real), N (nV x 3 float, may be NULL), T (nT x 3 unsigned, id base 0) in device memory, as for
+ * mc33hip_compact_components, and n_attr <= 2 arrays of one 4-byte word per vertex.  The half space s >= 0 of plane[4] = a, b, c, w
+ * stays (negate the four numbers for the other side): triangles inside it are kept, triangles the plane crosses are cut, and the
+ * new vertex of a cut edge is shared by every triangle that uses the edge, so that a manifold input stays manifold.  Integer
+ * atomics and exclusive sums decide who makes a new vertex and where every row lands; the arithmetic is IEEE double, nothing
+ * fused: the result is an exact function of the input, nothing has a tolerance, two calls on the same inputs return the same bytes.
+ *   s[v]             (((double)V[v][0] * a + (double)V[v][1] * b) + (double)V[v][2] * c) + w
+ *   class of v       IN when s > 0, ON when s == 0, OUT otherwise - a NaN is OUT.
+ *   valid triangle   its three indices are below nV.  An invalid triangle is counted and contributes nothing; nothing outside V
+ *                    is read.
+ *   walk             a valid triangle without an IN corner is dropped (dropped_triangles): triangles that lie in the plane or
+ *                    touch it from outside go.  Otherwise its directed sides p -> q are taken in the stored order, side e =
+ *                    T[e] -> T[(e + 1) % 3]: p is emitted unless it is OUT; then the cut vertex of {p, q} is emitted when one of
+ *                    p, q is IN and the other OUT.  A side with an ON end is never cut: the vertices of an isosurface lie on
+ *                    grid edges, a plane through a grid plane meets many of them exactly, and no zero-area triangle is planted
+ *                    there.  The polygon has 3 or 4 entries e0 .. e3; the output is (e0, e1, e2) and, with four, (e0, e2, e3): the
+ *                    winding is kept.  A triangle without an OUT corner is whole (whole_triangles), any other has a cut
+ *                    (cut_triangles).  A triangle with two equal indices takes the same walk.
+ *   cut edge         the undirected pair {lo, hi}, lo < hi by index.  t = s[lo] / (s[lo] - s[hi]); per axis the new row is
+ *                    (MC33_real)((double)V[lo] + t * ((double)V[hi] - (double)V[lo])).  When s[lo] or s[hi] is not finite the new
+ *                    vertex is a byte copy of the rows of the IN end: V, N and the attribute words.  nonfinite_vertices: the
+ *                    vertices a valid triangle names whose s is not finite.
+ *   oN               of a new vertex: x, y, z the same interpolation of the rows of N in double, m = sqrt((x*x + y*y) + z*z),
+ *                    (float)(x / m), (float)(y / m), (float)(z / m); 0, 0, 0 when !(m > 0).  A kept vertex keeps the bytes of
+ *                    its row.  oN needs N; with oN == NULL no normals are written.
+ *   attributes       of a new vertex, by attr_mode[k]: MC33HIP_CLIP_COPY the word of the IN end; MC33HIP_CLIP_LERP_F32 the words
+ *                    taken as floats, (float)((double)a_lo + t * ((double)a_hi - (double)a_lo)).  A kept vertex keeps its word.
+ *   numbering        an old vertex is kept when an output triangle names it; new[v] = the number of kept vertices below v
+ *                    (kept_vertices of them; on_plane_vertices: the kept ones whose class is ON).  The cut_vertices new vertices
+ *                    follow at kept_vertices + rank, in ascending order of their owner: the smallest i << 2 | e over the uses
+ *                    (triangle i, side e) of the cut edge.  nV_out = kept_vertices + cut_vertices.
+ *   oT               the output triangles in the order of their input triangles, the one or two of a triangle side by side.
+ *   oMap[v]          new[v] for a kept vertex, otherwise 0xFFFFFFFF (optional).
+ *   MC33HIP_ERUNTIME   invalid triangles: the count is in mc33hip_last_error, in the words of the measuring calls; the outputs
+ *                      are complete without them.
+ *   MC33HIP_ECAPACITY  capV < nV_out or capT < nT_out: every filled field is valid and no output array is touched (null outputs
+ *                      with capacity 0 are the size query; nV + 2 nT rows and 2 nT triangles are always enough).
+ *   MC33HIP_EINVAL     checked on the host, nothing is written: a null pointer where a size is not zero (N, oN and oMap may be
+ *                      NULL); nV or nT above 2^32-1; n_attr > 2; a mode of a used attribute that is neither; a plane with a
+ *                      component that is not finite or with a, b, c all zero; oN without N; an output byte range (capV / capT
+ *                      rows, nV words of oMap) that meets an input range or another output range - the call is not in place.
+ *   MC33HIP_ENOMEM     the scratch cannot be had.
+ *   nT == 0 is success with every count 0 (oMap, when given, is all 0xFFFFFFFF).
+ * The call enqueues on the context's stream behind whatever is on it, waits once, and brings the ten integers to the host, as
+ * mc33hip_compact_components does.  Scratch, with the context until mc33hip_destroy: 7 bytes per vertex, 1 byte per triangle, a
+ * word per 1024 vertices and two per 1024 triangles, and the table of cut edges: 16 bytes per slot, a power of two >= 4 nT slots
+ * (64 to 128 bytes per triangle). */
+#define MC33HIP_CLIP_COPY 0
+#define MC33HIP_CLIP_LERP_F32 1
+typedef struct {
+	const void *V, *N, *T;  unsigned long long nV, nT;   /* in (device): nV x 3 MC33_real, nV x 3 float or NULL, nT x 3 unsigned */
+	const void *attr[2]; unsigned n_attr;                /* in: <= 2 arrays of nV 4-byte words (device) */
+	int attr_mode[2];                                    /* MC33HIP_CLIP_COPY 0, MC33HIP_CLIP_LERP_F32 1 */
+	double plane[4];                                     /* a, b, c, w: s = a x + b y + c z + w, s >= 0 stays */
+	void *oV;  float *oN /* or NULL */;  void *oT;  void *oAttr[2];  unsigned *oMap /* nV words, or NULL */;
+	unsigned long long capV, capT;
+	unsigned long long nV_out, nT_out, kept_vertices, cut_vertices, on_plane_vertices, whole_triangles, cut_triangles,
+	                   dropped_triangles, invalid_triangles, nonfinite_vertices;   /* filled */
+} mc33hip_clipping;
+int mc33hip_clip_surface(mc33hip_ctx *c, mc33hip_clipping *a);
+
 /* Plain device allocations on the context's device (for language bindings). */
 int mc33hip_device_alloc(mc33hip_ctx *c, void **dptr, size_t bytes);
 int mc33hip_device_free(mc33hip_ctx *c, void *dptr);

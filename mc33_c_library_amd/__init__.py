@@ -6,4 +6,4 @@ of include/mc33_hip.h.  This package only holds the build recipe, thin ctypes/to
 and the host-side z-slab orchestration over several GPUs (slabs.py).
 """
 from .api import (Counts, DeviceGrid, GridDesc, GridResampling, GridSpectrum, MC33Error, Range, Resampling, Spectrum, SpectrumInfo, Timing,  # noqa: F401
-                  HIP_API, REFERENCE_API, gaussian_taps, isovalue_ladder, library_path, load_library)
+                  HIP_API, REFERENCE_API, clip_box, gaussian_taps, isovalue_ladder, library_path, load_library)

@@ -101,6 +101,26 @@ class SurfaceSimplification(C.Structure):
 SIMPLIFY_MODES = {"mean": 0, "first": 1}
 
 
+class Clipping(C.Structure):
+    """mc33hip_clipping (include/mc33_hip.h)"""
+    _fields_ = [("V", C.c_void_p), ("N", C.c_void_p), ("T", C.c_void_p), ("nV", C.c_ulonglong), ("nT", C.c_ulonglong),
+                ("attr", C.c_void_p * 2), ("n_attr", C.c_uint), ("attr_mode", C.c_int * 2), ("plane", C.c_double * 4),
+                ("oV", C.c_void_p), ("oN", C.c_void_p), ("oT", C.c_void_p), ("oAttr", C.c_void_p * 2), ("oMap", C.c_void_p),
+                ("capV", C.c_ulonglong), ("capT", C.c_ulonglong)] + \
+               [(n, C.c_ulonglong) for n in ("nV_out", "nT_out", "kept_vertices", "cut_vertices", "on_plane_vertices", "whole_triangles", "cut_triangles",
+                                             "dropped_triangles", "invalid_triangles", "nonfinite_vertices")]
+
+
+class SurfaceClip(C.Structure):
+    """mc33_clip (include/marching_cubes_33.h): n <= 6 planes a, b, c, w in the coordinates of the vertices; s >= 0 stays"""
+    _fields_ = [("n", C.c_uint), ("plane", (C.c_double * 4) * 6)]
+
+
+CLIP_MODES = {"copy": 0, "lerp_f32": 1}
+CLIP_COUNTS = ("nV_out", "nT_out", "kept_vertices", "cut_vertices", "on_plane_vertices", "whole_triangles", "cut_triangles", "dropped_triangles",
+               "invalid_triangles", "nonfinite_vertices")
+
+
 class Resampling(C.Structure):
     """mc33hip_resampling (include/mc33_hip.h): taps are HOST arrays of doubles, NULL = the single tap 1.0"""
     _fields_ = [("taps", C.POINTER(C.c_double) * 3), ("ntaps", C.c_uint * 3), ("stride", C.c_uint * 3)]
@@ -135,7 +155,8 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_measure_surface", "mc33hip_label_components", "mc33hip_measure_components",
            "mc33hip_surface_topology", "mc33hip_component_topology", "mc33hip_compact_components",
            "mc33hip_smooth_surface", "mc33hip_vertex_normals", "mc33hip_smooth_timing", "mc33hip_simplify_surface",
-           "mc33hip_resampled_size", "mc33hip_resample_grid", "mc33hip_context_device", "mc33hip_grid_spectrum"]
+           "mc33hip_resampled_size", "mc33hip_resample_grid", "mc33hip_context_device", "mc33hip_grid_spectrum",
+           "mc33hip_clip_surface"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -147,7 +168,8 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "MC33_select_components", "MC33_calculate_filtered_isosurface", "MC33_calculate_smoothed_isosurface",
                  "MC33_calculate_simplified_isosurface",
                  "MC33_gaussian_taps", "MC33_create_resampled", "MC33_resampled_grid",
-                 "MC33_grid_spectrum", "MC33_isovalue_ladder"]
+                 "MC33_grid_spectrum", "MC33_isovalue_ladder",
+                 "MC33_calculate_clipped_isosurface", "MC33_clip_box"]
 
 
 class MC33Error(RuntimeError):
@@ -230,6 +252,8 @@ def load_library(dtype="f32"):
     lib.MC33_gaussian_taps.argtypes = [C.c_double, C.c_uint, P(C.c_double)]
     lib.mc33hip_grid_spectrum.argtypes = [V, P(Range), P(Spectrum)]
     lib.MC33_isovalue_ladder.argtypes = [C.c_double, C.c_double, C.c_uint, V]
+    lib.mc33hip_clip_surface.argtypes = [V, P(Clipping)]
+    lib.MC33_clip_box.argtypes = [P(C.c_double * 3), P(C.c_double * 3), P(SurfaceClip)]
     _libs[dtype] = lib
     return lib
 
@@ -263,6 +287,21 @@ def isovalue_ladder(lo, hi, n, dtype="f32"):
     if r < 0:
         raise ValueError("MC33_isovalue_ladder refused lo=%r hi=%r n=%r" % (lo, hi, n))
     return [float(out[k]) for k in range(r)]
+
+
+def clip_box(lo, hi):
+    """The six planes (a, b, c, w) that keep the box [lo, hi], in the order x - lo[0], hi[0] - x, y - lo[1], hi[1] - y, z - lo[2],
+    hi[2] - z, as a list of 4-tuples of floats - the library's MC33_clip_box (include/marching_cubes_33.h), host C that needs no
+    GPU: there is no second implementation.  ValueError for what it refuses: a bound that is not finite, lo >= hi on an axis."""
+    lib = load_library("f32")
+    out = SurfaceClip()
+    try:
+        r = lib.MC33_clip_box(C.byref((C.c_double * 3)(*[float(x) for x in lo])), C.byref((C.c_double * 3)(*[float(x) for x in hi])), C.byref(out))
+    except (C.ArgumentError, OverflowError, TypeError, ValueError):
+        r = -1
+    if r != 0:
+        raise ValueError("MC33_clip_box refused lo=%r hi=%r" % (lo, hi))
+    return [tuple(out.plane[k][j] for j in range(4)) for k in range(out.n)]
 
 
 class GridSpectrum:
@@ -820,6 +859,59 @@ class DeviceGrid:
         V2, N2, T2, attrs2, _, info = self.simplify(got[0], got[2], cell, attrs=(got[4],) if with_property else (), **kw)
         out = (V2, N2, T2, info)
         return out + (attrs2[0],) if with_property else out
+
+    # -- clip a finished mesh by a plane on the device (mc33_hip.h: mc33hip_clip_surface) ------------------------------------------
+    def clip(self, V, N, T, plane, attrs=(), attr_modes=()):
+        """The mesh V [n, 3], N [n, 3] (or None), T [m, 3] (device tensors, as extract() returns them) cut by the plane
+        (a, b, c, w): the half space a x + b y + c z + w >= 0 stays, triangles the plane crosses are cut, the new vertices are
+        shared.  Returns (V2, N2, T2, attrs2, vmap, info): exact-size device tensors - N2 None without N; attrs: up to two device
+        tensors of one 4-byte word per vertex, attr_modes "copy" (a new vertex takes the word of its end inside; the default) or
+        "lerp_f32" (the words are floats and are interpolated); vmap int32 [n], the uint32 words of the new index of a kept vertex,
+        0xFFFFFFFF where it left - and a dict of the call's ten counts.  Raises MC33Error(ERUNTIME) when a triangle names a
+        vertex >= n (the outputs are complete without it)."""
+        import torch
+        self._vertex_rows(V)
+        self._triangle_rows(T)
+        nV = V.shape[0]
+        if N is not None:
+            assert N.is_cuda and N.is_contiguous() and N.dtype == torch.float32 and tuple(N.shape) == (nV, 3)
+        attrs = tuple(attrs)
+        for x in attrs:
+            assert x.is_cuda and x.is_contiguous() and x.numel() == nV and x.element_size() == 4, "an attribute is one 4-byte word per vertex"
+        modes = [CLIP_MODES[m] if isinstance(m, str) else int(m) for m in attr_modes] + [0] * (len(attrs) - len(attr_modes))
+        a = Clipping()
+        a.V, a.N, a.T, a.nV, a.nT = V.data_ptr(), (N.data_ptr() if N is not None else None), T.data_ptr(), nV, T.shape[0]
+        for k, x in enumerate(attrs[:2]):
+            a.attr[k], a.attr_mode[k] = x.data_ptr(), modes[k]
+        a.n_attr = len(attrs)
+        a.plane = (C.c_double * 4)(*[float(x) for x in plane])
+        _check(self.lib, self.lib.mc33hip_clip_surface(self.ctx, C.byref(a)), allow=(ECAPACITY,))  # null outputs: the size query
+        nV2, nT2 = int(a.nV_out), int(a.nT_out)
+        V2 = torch.empty((max(nV2, 1), 3), dtype=V.dtype, device=self.device)
+        N2 = torch.empty((max(nV2, 1), 3), dtype=torch.float32, device=self.device) if N is not None else None
+        T2 = torch.empty((max(nT2, 1), 3), dtype=torch.int32, device=self.device)
+        attrs2 = [torch.empty((max(nV2, 1),), dtype=x.dtype, device=self.device) for x in attrs]
+        vmap = torch.empty((max(nV, 1),), dtype=torch.int32, device=self.device)
+        a.oV, a.oT, a.oN, a.oMap, a.capV, a.capT = V2.data_ptr(), T2.data_ptr(), (N2.data_ptr() if N is not None else None), vmap.data_ptr(), nV2, nT2
+        for k, x in enumerate(attrs2):
+            a.oAttr[k] = x.data_ptr()
+        _check(self.lib, self.lib.mc33hip_clip_surface(self.ctx, C.byref(a)))
+        info = {n: int(getattr(a, n)) for n in CLIP_COUNTS}
+        return V2[:nV2], (N2[:nV2] if N is not None else None), T2[:nT2], [x[:nV2] for x in attrs2], vmap[:nV], info
+
+    def extract_clipped(self, iso, planes, rng=None, with_property=False):
+        """extract, then clip by every plane of `planes` (4-tuples a, b, c, w; clip_box(lo, hi) makes the six of a box) one after
+        another - the whole surface never leaves the device.  Returns (V, N, T, infos) - infos: the dict of every clip - and,
+        with with_property, the attached property grid's value at the FINAL vertices as a fifth element: a new vertex gets the
+        value of its own position."""
+        got = self.extract(iso, rng)
+        V, N, T = got[0], got[1], got[2]
+        infos = []
+        for plane in planes:
+            V, N, T, _, _, info = self.clip(V, N, T, plane)
+            infos.append(info)
+        out = (V, N, T, infos)
+        return out + (self.sample_property(V),) if with_property else out
 
     # -- the grid resampled into a second device grid (mc33_hip.h: mc33hip_resample_grid) ------------------------------------------
     def _resampling(self, taps, stride, sigma):

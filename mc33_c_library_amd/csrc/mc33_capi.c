@@ -73,6 +73,7 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_compact_components
 #pragma weak mc33hip_smooth_surface
 #pragma weak mc33hip_simplify_surface
+#pragma weak mc33hip_clip_surface
 /* ... and the resampling ones (MC33_create_resampled): without them it returns NULL */
 #pragma weak mc33hip_resampled_size
 #pragma weak mc33hip_resample_grid
@@ -1327,6 +1328,95 @@ surface *MC33_calculate_simplified_isosurface(MC33 *M, MC33_real iso, const mc33
 	M->memoryfault = 0;
 	M->iso = iso;
 	surface *S = simplified_surface(p, iso, sp);
+	if (!S) {
+		M->memoryfault = 1;
+		return 0;
+	}
+	if (S->nV) { /* as calculate_isosurface leaves the public prefix */
+		M->T = S->T; M->V = S->V; M->N = S->N; M->color = S->color;
+		M->nT = S->nT; M->capt = S->capt; M->capv = S->capv;
+	}
+	return S;
+}
+
+/* --- extension: an isosurface clipped by planes --------------------------------------------------------------------------------
+ * MC33_clip_box is host C.  The surface of `iso` into staging set 0, then plane after plane from one staging set into the other
+ * (each grown to the sizes a refused call reports), the colours of the FINAL vertices from the property grid, then the kept
+ * rows into a caller-owned surface. */
+static int clip_finite(double x) { return x >= -DBL_MAX && x <= DBL_MAX; } /* (false for a NaN) */
+
+static int clip_plane_ok(const double *pl) {
+	for (int j = 0; j != 4; j++)
+		if (!clip_finite(pl[j]))
+			return 0;
+	return pl[0] != 0.0 || pl[1] != 0.0 || pl[2] != 0.0;
+}
+
+int MC33_clip_box(const double lo[3], const double hi[3], mc33_clip *out) {
+	if (!lo || !hi || !out)
+		return -1;
+	for (int j = 0; j != 3; j++)
+		if (!clip_finite(lo[j]) || !clip_finite(hi[j]) || !(lo[j] < hi[j]))
+			return -1;
+	memset(out, 0, sizeof *out);
+	out->n = 6;
+	for (int j = 0; j != 3; j++) { /* x - lo0, hi0 - x, y - lo1, hi1 - y, z - lo2, hi2 - z */
+		out->plane[2 * j][j] = 1.0; out->plane[2 * j][3] = -lo[j];
+		out->plane[2 * j + 1][j] = -1.0; out->plane[2 * j + 1][3] = hi[j];
+	}
+	return 0;
+}
+
+static surface *clipped_surface(mc33_private *p, MC33_real iso, const mc33_clip *cl) {
+	mc33_slab *s = &p->slab[0];
+	mc33hip_counts cnt;
+	int cur = 0;
+	if (extract_geometry(p, &s->set[0], iso, &cnt) != MC33HIP_OK)
+		return 0;
+	for (unsigned k = 0; k != cl->n && cnt.nT; k++) {
+		struct staging *g = &s->set[cur], *h = &s->set[cur ^ 1];
+		mc33hip_clipping a;
+		memset(&a, 0, sizeof a);
+		a.V = g->dV; a.N = g->dN; a.T = g->dT; a.nV = cnt.nV; a.nT = cnt.nT;
+		for (int j = 0; j != 4; j++) a.plane[j] = cl->plane[k][j];
+		int rc = MC33HIP_ECAPACITY;
+		for (int attempt = 0; attempt != 2 && rc == MC33HIP_ECAPACITY; attempt++) { /* with the set as it is; grown to the sizes that came back */
+			if (attempt && staging_room(s, h, a.nV_out, a.nT_out)) {
+				rc = MC33HIP_ENOMEM;
+				break;
+			}
+			a.oV = h->dV; a.oN = (float *)h->dN; a.oT = h->dT;
+			a.capV = h->capV; a.capT = h->capT;
+			rc = mc33hip_clip_surface(s->ctx, &a);
+		}
+		if (rc != MC33HIP_OK)
+			return 0;
+		cnt.nV = a.nV_out; cnt.nT = a.nT_out;
+		cur ^= 1;
+	}
+	if (!cnt.nT)
+		cnt.nV = 0; /* (a plane that removes everything leaves no vertex either) */
+	if (coloured(p) && cnt.nV) { /* a new vertex gets the colour of its own position */
+		p->nan_color = DefaultColorMC;
+		if (enqueue_colors(s, &s->set[cur], cnt.nV) != MC33HIP_OK)
+			return 0;
+	}
+	return surface_from_staging(p, &s->set[cur], &cnt, iso, 0);
+}
+
+surface *MC33_calculate_clipped_isosurface(MC33 *M, MC33_real iso, const mc33_clip *cl) {
+	mc33_private *p = priv(M);
+	if (!p || !cl || p->nslab != 1 || !mc33hip_clip_surface || !mc33hip_color_vertices)
+		return 0;
+	if (cl->n > 6u)
+		return 0;
+	for (unsigned k = 0; k != cl->n; k++)
+		if (!clip_plane_ok(cl->plane[k]))
+			return 0; /* (what mc33hip_clip_surface refuses, before anything is extracted) */
+	M->nT = M->nV = 0;
+	M->memoryfault = 0;
+	M->iso = iso;
+	surface *S = clipped_surface(p, iso, cl);
 	if (!S) {
 		M->memoryfault = 1;
 		return 0;

@@ -47,6 +47,9 @@
 //                   k_simp_* - vertex clustering of a finished V, T on a lattice: a table of clusters filled by 64-bit compare-and-swap,
 //                   duplicate triangles through a table of triangle indices, two exclusive scans, two writing passes;
 //                   k_simp_cluster is its hot path (mc33_simplify.hip.h).
+//                   k_clip_* - a finished V, N, T cut by a plane: classes, a table of cut edges filled by 64-bit compare-and-swap and
+//                   atomicMin of the owner, three exclusive scans, three writing passes; k_clip_tri is its hot path
+//                   (mc33_clip.hip.h).
 // Before an extraction: k_rs_resample - the resident grid into a second device grid, a separable correlation of up to 17 taps per axis
 //                   with an integer stride, one pass over the source: a block stages the rows its tile of outputs needs in LDS,
 //                   sums along x and y into a ring of planes and along z out of it (mc33_resample.hip.h).
@@ -115,5 +118,6 @@ typedef float sample_t;
 #include "mc33_filter.hip.h"
 #include "mc33_smooth.hip.h"
 #include "mc33_simplify.hip.h"
+#include "mc33_clip.hip.h"
 #include "mc33_resample.hip.h"
 #include "mc33_spectrum.hip.h"

@@ -40,6 +40,7 @@ struct MeasureState {       // scratch of these passes: on the context from the 
 	struct FilterState *filt;  // scratch of the compaction (mc33_filter.hip.h), likewise
 	struct SmoothState *smooth;  // scratch of the smoothing (mc33_smooth.hip.h), likewise
 	struct SimpState *simp;  // scratch of the simplification (mc33_simplify.hip.h), likewise
+	struct ClipState *clip;  // scratch of the clipping (mc33_clip.hip.h), likewise
 	struct ResampleState *resample;  // the taps of the grid resampling (mc33_resample.hip.h), likewise
 	struct SpectrumState *spectrum;  // isovalues and counters of the contour spectrum (mc33_spectrum.hip.h), likewise
 };
@@ -49,6 +50,7 @@ static void smooth_destroy(MeasureState *m);
 static void simp_destroy(MeasureState *m);
 static void rs_destroy(MeasureState *m);
 static void sp_destroy(MeasureState *m);
+static void clip_destroy(MeasureState *m);
 
 constexpr uint32_t CC_TILE = 1024u;  // vertices per block of k_cc_count / k_cc_rank: 256 lanes x 4
 
@@ -509,6 +511,7 @@ static void meas_destroy(mc33hip_ctx *c) {
 	simp_destroy(m);
 	rs_destroy(m);
 	sp_destroy(m);
+	clip_destroy(m);
 	dev_release(&m->d_out); dev_release(&m->d_part); dev_release(&m->d_flags); dev_release(&m->d_rank); dev_release(&m->d_bsum); dev_release(&m->d_table);
 	if (m->h_out) (void)hipHostFree(m->h_out);
 	free(m);
