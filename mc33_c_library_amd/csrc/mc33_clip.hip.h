@@ -1,4 +1,4 @@
-// mc33_clip.hip.h -- part of the ONE translation unit mc33_kernels.hip (included there, behind mc33_simplify.hip.h; not a header to include elsewhere):
+// mc33_clip.hip.h -- part of the ONE translation unit mc33_kernels.hip (builds on mc33_mesh.hip.h; not a header to include elsewhere):
 // a FINISHED mesh in device memory cut by one plane - the half space s >= 0 stays, triangles the plane crosses are cut, the new
 // vertices on the cut edges are shared between the triangles on either side - so that only the part a viewer shows crosses the
 // link (include/mc33_hip.h: mc33hip_clip_surface).  DESIGN.md 17.
@@ -7,22 +7,19 @@
 // owns a cut edge, where a row lands and what it holds are decided by integer atomics, exclusive scans and IEEE double arithmetic
 // with nothing fused: the result is an exact function of the input.
 // The passes: k_clip_class, a lane per vertex, leaves the class of every vertex in a byte; k_clip_tri, the hot path, a lane per
-// triangle, validates, classifies, counts 0, 1 or 2 output triangles, marks the kept vertices and enters each cut side into an
-// open-addressing table of 16-byte slots - the key lo << 32 | hi claimed by 64-bit compare-and-swap (the table of
-// mc33_topology.hip.h), the owner word i << 2 | e by a 64-bit atomicMin - but not where the lane before it in the wave, the
-// triangle before it in T, holds the same edge: that lane's word is the smaller one; k_clip_own flags the sides that find their
-// own word in the slot; k_clip_tile_sum / k_filt_scan_top / k_filt_new are the scans of section 12 over the kept flags, the owned
-// sides and the output triangles; k_clip_rows moves the kept rows and writes oMap; k_clip_new, the owner's lane, computes t and
+// triangle, validates, classifies, counts 0, 1 or 2 output triangles, marks the kept vertices and enters each cut side into a
+// table of 16-byte slots - the key lo << 32 | hi claimed by 64-bit compare-and-swap (the table of mc33_mesh.hip.h), the owner
+// word i << 2 | e by a 64-bit atomicMin - but not where the lane before it in the wave, the triangle before it in T, holds the
+// same edge: that lane's word is the smaller one; k_clip_own flags the sides that find their own word in the slot; the tile
+// scans of mc33_mesh.hip.h run over the kept flags, the owned sides and the output triangles; k_clip_rows moves the kept rows and writes oMap; k_clip_new, the owner's lane, computes t and
 // writes the new rows at kept_vertices + rank and leaves the rank in the slot; k_clip_emit repeats the walk and writes the
 // triangles at their scanned place.  Nothing a block wrote with plain stores is read by another block of the same kernel: the
 // words of the table are touched only by atomics in k_clip_tri, their readers are later kernels; the rank is stored by
 // k_clip_new and read by k_clip_emit.
 
-struct ClipSlot { unsigned long long key, owner; };  // 16 bytes; key all ones: empty (lo < hi, so no key has it)
+struct ClipSlot { unsigned long long key, owner; };  // 16 bytes (lo < hi, so no key is MESH_EMPTY)
 struct ClipPlane { double a, b, c, w; };
 
-constexpr unsigned long long CLIP_EMPTY = ~0ull;
-constexpr uint64_t CLIP_NOSLOT = ~0ull;
 enum { CLIP_OUT = 0, CLIP_ON = 1, CLIP_IN = 2, CLIP_NONFINITE = 4 };  // the class byte of a vertex: low two bits, and s not finite
 // the byte of a triangle: output triangles (0, 1, 2) | cut sides << 2 | owned sides << 5
 
@@ -32,20 +29,15 @@ struct ClipOut {            // what a call brings to the host (device copy and p
 	unsigned long long pad_[2];
 };
 
-struct ClipState {          // scratch of these passes: on the MeasureState from the first call on, grown on demand, freed with it
+struct ClipState {          // scratch of these passes besides the shared keep (1: an output triangle names the vertex), map (new[v]) and tile sums
+                            // (the vertex tiles, behind them the triangle tiles twice: owned sides, outputs): on the MeasureState from the first call on, grown on demand, freed with it
 	ClipOut *d_out, *h_out;
 	uint8_t *d_cls;         // [nV] class of the vertex
 	uint64_t cls_cap;
-	uint8_t *d_keep;        // [nV] 1: an output triangle names the vertex
-	uint64_t keep_cap;
 	uint8_t *d_nf;          // [nV] 1: a valid triangle names the vertex and its s is not finite
 	uint64_t nf_cap;
-	uint32_t *d_map;        // [nV] new[v], FILT_NONE where v is not kept
-	uint64_t map_cap;
 	uint8_t *d_info;        // [nT] the byte of the triangle
 	uint64_t info_cap;
-	uint32_t *d_bsum;       // per tile, scanned in place: the vertex tiles, behind them the triangle tiles twice (owned sides, outputs)
-	uint64_t bsum_cap;
 	ClipSlot *d_slots;      // the edge table: a power of two >= 4 nT slots
 	uint64_t slots_cap;
 };
@@ -66,33 +58,12 @@ __device__ __forceinline__ uint32_t clip_cuts(uint32_t a0, uint32_t a1, uint32_t
 	return ((a0 ^ a1) == 2u ? 1u : 0u) | ((a1 ^ a2) == 2u ? 2u : 0u) | ((a2 ^ a0) == 2u ? 4u : 0u);
 }
 
-// One use of a cut edge.  What the compare-and-swap on the key RETURNS decides - empty or equal: this is the edge's slot;
-// anything else: probe on, linearly.  The slot is never read with a plain load here.  Returns false when every slot was tried.
+// one use of a cut edge: the slot claimed, the owner word lowered.  Returns false when every slot was tried.
 __device__ __forceinline__ bool clip_enter(ClipSlot *slots, uint64_t mask, unsigned long long key, unsigned long long owner) {
-	uint64_t s = topo_mix(key) & mask;
-	for (uint64_t tries = 0; tries <= mask; tries++, s = (s + 1u) & mask) {
-		const unsigned long long old = atomicCAS(&slots[s].key, CLIP_EMPTY, key);
-		if (old == CLIP_EMPTY || old == key) {
-			atomicMin(&slots[s].owner, owner);
-			return true;
-		}
-	}
-	return false;
-}
-// the slot of a key a finished table holds (a later kernel: plain loads), CLIP_NOSLOT when it does not
-__device__ __forceinline__ uint64_t clip_find(const ClipSlot *__restrict__ slots, uint64_t mask, unsigned long long key) {
-	uint64_t s = topo_mix(key) & mask;
-	for (uint64_t tries = 0; tries <= mask; tries++, s = (s + 1u) & mask) {
-		const unsigned long long k = slots[s].key;
-		if (k == key) return s;
-		if (k == CLIP_EMPTY) break;
-	}
-	return CLIP_NOSLOT;
-}
-
-__global__ __launch_bounds__(256) void k_clip_clear(ClipSlot *__restrict__ slots, uint64_t n) {
-	for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < n; s += (uint64_t)gridDim.x * 256u)
-		*(ulonglong2 *)(slots + s) = make_ulonglong2(CLIP_EMPTY, ~0ull);
+	const uint64_t s = mesh_claim(slots, mask, key);
+	if (s == MESH_NOSLOT) return false;
+	atomicMin(&slots[s].owner, owner);
+	return true;
 }
 
 template <typename R>
@@ -117,7 +88,7 @@ __global__ __launch_bounds__(256) void k_clip_tri(const uint32_t *__restrict__ T
 	uint32_t bad = 0u, whole = 0u, cut = 0u, dropped = 0u, full = 0u;
 	for (uint64_t base = (uint64_t)blockIdx.x * 256u + (threadIdx.x & ~63u); base < nT; base += (uint64_t)gridDim.x * 256u) {  // (wave-uniform)
 		const uint64_t i = base + lane;
-		unsigned long long k0 = CLIP_EMPTY, k1 = CLIP_EMPTY, w0 = 0ull, w1 = 0ull;
+		unsigned long long k0 = MESH_EMPTY, k1 = MESH_EMPTY, w0 = 0ull, w1 = 0ull;
 		if (i < nT) {
 			const uint32_t *t = T + i * 3u;
 			const uint32_t t0 = t[0], t1 = t[1], t2 = t[2];
@@ -143,13 +114,13 @@ __global__ __launch_bounds__(256) void k_clip_tri(const uint32_t *__restrict__ T
 					if (cuts & 1u) { k0 = clip_key(t0, t1); w0 = (unsigned long long)i << 2; }
 					if (cuts & 2u) {
 						const unsigned long long k = clip_key(t1, t2), w = ((unsigned long long)i << 2) | 1ull;
-						if (k0 == CLIP_EMPTY) { k0 = k; w0 = w; } else { k1 = k; w1 = w; }
+						if (k0 == MESH_EMPTY) { k0 = k; w0 = w; } else { k1 = k; w1 = w; }
 					}
 					if (cuts & 4u) {
 						const unsigned long long k = clip_key(t2, t0), w = ((unsigned long long)i << 2) | 2ull;
-						if (k0 == CLIP_EMPTY) { k0 = k; w0 = w; } else { k1 = k; w1 = w; }
+						if (k0 == MESH_EMPTY) { k0 = k; w0 = w; } else { k1 = k; w1 = w; }
 					}
-					if (k1 == k0) k1 = CLIP_EMPTY;  // (a triangle with two equal indices: the side that comes first owns)
+					if (k1 == k0) k1 = MESH_EMPTY;  // (a triangle with two equal indices: the side that comes first owns)
 				}
 			}
 			info[i] = (uint8_t)word;
@@ -157,17 +128,17 @@ __global__ __launch_bounds__(256) void k_clip_tri(const uint32_t *__restrict__ T
 		const unsigned long long p0 = ((unsigned long long)__shfl_up((uint32_t)(k0 >> 32), 1, 64) << 32) | __shfl_up((uint32_t)k0, 1, 64);
 		const unsigned long long p1 = ((unsigned long long)__shfl_up((uint32_t)(k1 >> 32), 1, 64) << 32) | __shfl_up((uint32_t)k1, 1, 64);
 		if (lane != 0u) {
-			if (k0 == p0 || k0 == p1) k0 = CLIP_EMPTY;  // (an empty word never equals a key; two empty words need no atomic either)
-			if (k1 == p0 || k1 == p1) k1 = CLIP_EMPTY;
+			if (k0 == p0 || k0 == p1) k0 = MESH_EMPTY;  // (an empty word never equals a key; two empty words need no atomic either)
+			if (k1 == p0 || k1 == p1) k1 = MESH_EMPTY;
 		}
-		if (k0 != CLIP_EMPTY && !clip_enter(slots, mask, k0, w0)) full++;
-		if (k1 != CLIP_EMPTY && !clip_enter(slots, mask, k1, w1)) full++;
+		if (k0 != MESH_EMPTY && !clip_enter(slots, mask, k0, w0)) full++;
+		if (k1 != MESH_EMPTY && !clip_enter(slots, mask, k1, w1)) full++;
 	}
-	bad = topo_block_sum(bad, sh);
-	whole = topo_block_sum(whole, sh);
-	cut = topo_block_sum(cut, sh);
-	dropped = topo_block_sum(dropped, sh);
-	full = topo_block_sum(full, sh);
+	bad = block_sum_u32_256(bad, sh);
+	whole = block_sum_u32_256(whole, sh);
+	cut = block_sum_u32_256(cut, sh);
+	dropped = block_sum_u32_256(dropped, sh);
+	full = block_sum_u32_256(full, sh);
 	if (threadIdx.x == 0u) {
 		if (bad) atomicAdd(&out->bad, (unsigned long long)bad);
 		if (whole) atomicAdd(&out->whole, (unsigned long long)whole);
@@ -188,18 +159,18 @@ __global__ __launch_bounds__(256) void k_clip_own(const uint32_t *__restrict__ T
 		const uint32_t t0 = t[0], t1 = t[1], t2 = t[2];  // (a triangle with a cut side is valid)
 		uint32_t own = 0u;
 		if (cuts & 1u) {
-			const uint64_t s = clip_find(slots, mask, clip_key(t0, t1));
-			if (s == CLIP_NOSLOT) full++;
+			const uint64_t s = mesh_find(slots, mask, clip_key(t0, t1));
+			if (s == MESH_NOSLOT) full++;
 			else if (slots[s].owner == ((unsigned long long)i << 2)) own |= 1u;
 		}
 		if (cuts & 2u) {
-			const uint64_t s = clip_find(slots, mask, clip_key(t1, t2));
-			if (s == CLIP_NOSLOT) full++;
+			const uint64_t s = mesh_find(slots, mask, clip_key(t1, t2));
+			if (s == MESH_NOSLOT) full++;
 			else if (slots[s].owner == (((unsigned long long)i << 2) | 1ull)) own |= 2u;
 		}
 		if (cuts & 4u) {
-			const uint64_t s = clip_find(slots, mask, clip_key(t2, t0));
-			if (s == CLIP_NOSLOT) full++;
+			const uint64_t s = mesh_find(slots, mask, clip_key(t2, t0));
+			if (s == MESH_NOSLOT) full++;
 			else if (slots[s].owner == (((unsigned long long)i << 2) | 2ull)) own |= 4u;
 		}
 		if (own) info[i] = (uint8_t)(word | (own << 5));
@@ -207,30 +178,15 @@ __global__ __launch_bounds__(256) void k_clip_own(const uint32_t *__restrict__ T
 	if (full) atomicAdd(&out->full, (unsigned long long)full);
 }
 
-// what a byte counts for one of the three scans: a kept flag, the owned sides of a triangle, its output triangles
-template <int WHAT>
-__device__ __forceinline__ uint32_t clip_count(uint32_t b) {
-	return WHAT == 0 ? (b ? 1u : 0u) : WHAT == 1 ? (uint32_t)__popc(b >> 5) : (b & 3u);
-}
-
-// the counts of a tile of CC_TILE elements, 4 per lane
-template <int WHAT>
-__global__ __launch_bounds__(256) void k_clip_tile_sum(const uint8_t *__restrict__ bytes, uint64_t n, uint32_t *__restrict__ bsum) {
-	__shared__ uint32_t sh[4];
-	const uint64_t e0 = (uint64_t)blockIdx.x * CC_TILE + threadIdx.x * 4u;
-	uint32_t own = 0u;
-#pragma unroll
-	for (uint32_t k = 0; k < 4u; k++)
-		if (e0 + k < n) own += clip_count<WHAT>(bytes[e0 + k]);
-	const uint32_t tot = block_sum_u32_256(own, sh);
-	if (threadIdx.x == 0u) bsum[blockIdx.x] = tot;
-}
+// what the byte of a triangle counts for the tile scans: its owned sides, its output triangles
+struct ClipOwned { using E = uint8_t; static __device__ __forceinline__ uint32_t count(uint32_t b) { return (uint32_t)__popc(b >> 5); } };
+struct ClipOutputs { using E = uint8_t; static __device__ __forceinline__ uint32_t count(uint32_t b) { return b & 3u; } };
 
 __device__ __forceinline__ bool clip_fits(const ClipOut *__restrict__ out, uint64_t capV, uint64_t capT) {
 	return out->kept + out->cutv <= capV && out->nT_out <= capT;
 }
 
-// oMap for every vertex; the kept rows of V, N and the attribute words to their new places, as k_filt_rows moves them; the two
+// oMap for every vertex; the kept rows of V, N and the attribute words to their new places, as words; the two
 // counts over the vertices (they are taken whether the caller's arrays are large enough or not).  R: MC33_real.
 template <typename R>
 __global__ __launch_bounds__(256) void k_clip_rows(const R *__restrict__ V, const float *__restrict__ N, const uint32_t *__restrict__ A0, const uint32_t *__restrict__ A1,
@@ -243,25 +199,16 @@ __global__ __launch_bounds__(256) void k_clip_rows(const R *__restrict__ V, cons
 	for (uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x; v < nV; v += (uint64_t)gridDim.x * 256u) {
 		const uint32_t m = map[v];
 		nonf += nf[v] ? 1u : 0u;
-		if (m != FILT_NONE && (cls[v] & 3u) == CLIP_ON) onp++;
+		if (m != MESH_NONE && (cls[v] & 3u) == CLIP_ON) onp++;
 		if (!fits) continue;
 		if (oMap) oMap[v] = m;
-		if (m == FILT_NONE) continue;
-		const R *q = V + v * 3u;
-		R *oq = oV + (uint64_t)m * 3u;
-		const R q0 = q[0], q1 = q[1], q2 = q[2];
-		oq[0] = q0; oq[1] = q1; oq[2] = q2;
-		if (oN) {
-			const float *n = N + v * 3u;
-			float *on = oN + (uint64_t)m * 3u;
-			const float n0 = n[0], n1 = n[1], n2 = n[2];
-			on[0] = n0; on[1] = n1; on[2] = n2;
-		}
+		if (m == MESH_NONE) continue;
+		mesh_copy_row(V, N, v, oV, oN, m);
 		if (A0) oA0[m] = A0[v];
 		if (A1) oA1[m] = A1[v];
 	}
-	onp = topo_block_sum(onp, sh);
-	nonf = topo_block_sum(nonf, sh);
+	onp = block_sum_u32_256(onp, sh);
+	nonf = block_sum_u32_256(nonf, sh);
 	if (threadIdx.x == 0u) {
 		if (onp) atomicAdd(&out->on_plane, (unsigned long long)onp);
 		if (nonf) atomicAdd(&out->nonfinite, (unsigned long long)nonf);
@@ -287,17 +234,8 @@ __device__ __forceinline__ void clip_new_row(const R *__restrict__ V, const floa
 	const bool copy = !clip_finite(slo) || !clip_finite(shi);
 	const double t = slo / (slo - shi);
 	R *oq = oV + row * 3u;
-	if (copy) {  // the bytes of the end that is in
-		const R *s = V + (uint64_t)in * 3u;
-		const R s0 = s[0], s1 = s[1], s2 = s[2];
-		oq[0] = s0; oq[1] = s1; oq[2] = s2;
-		if (oN) {
-			const float *n = N + (uint64_t)in * 3u;
-			float *on = oN + row * 3u;
-			const float n0 = n[0], n1 = n[1], n2 = n[2];
-			on[0] = n0; on[1] = n1; on[2] = n2;
-		}
-	} else {
+	if (copy) mesh_copy_row(V, N, in, oV, oN, row);  // the bytes of the end that is in
+	else {
 		const R *a = V + (uint64_t)lo * 3u, *b = V + (uint64_t)hi * 3u;
 #pragma unroll
 		for (int k = 0; k < 3; k++) {
@@ -330,17 +268,13 @@ __global__ __launch_bounds__(256) void k_clip_new(const R *__restrict__ V, const
 	__shared__ uint32_t sh[256];
 	if (!clip_fits(out, capV, capT)) return;  // (block-uniform: the caller's arrays are too small, nothing is written)
 	const uint64_t kept = out->kept;
-	const uint64_t i0 = (uint64_t)blockIdx.x * CC_TILE + threadIdx.x * 4u;
-	uint32_t f[4], own = 0u;
+	const uint64_t i0 = mesh_tile_e0();
+	uint32_t f[4];
+	const uint32_t own = mesh_tile_load<ClipOwned>(info, nT, f);
+	uint64_t r = mesh_tile_place(bsum, own, sh);
 #pragma unroll
 	for (uint32_t k = 0; k < 4u; k++) {
-		f[k] = i0 + k < nT ? (uint32_t)info[i0 + k] >> 5 : 0u;
-		own += (uint32_t)__popc(f[k]);
-	}
-	uint32_t tot;
-	uint64_t r = (uint64_t)bsum[blockIdx.x] + block_excl_scan_256(own, sh, &tot);
-#pragma unroll
-	for (uint32_t k = 0; k < 4u; k++) {
+		f[k] >>= 5;  // (the owned sides)
 		if (!f[k]) continue;
 		const uint32_t *t = T + (i0 + k) * 3u;
 		const uint32_t t0 = t[0], t1 = t[1], t2 = t[2];
@@ -349,8 +283,8 @@ __global__ __launch_bounds__(256) void k_clip_new(const R *__restrict__ V, const
 			if (!((f[k] >> e) & 1u)) continue;
 			const uint32_t p = e == 0u ? t0 : e == 1u ? t1 : t2, q = e == 0u ? t1 : e == 1u ? t2 : t0;
 			clip_new_row(V, N, A0, A1, lerp0, lerp1, P, p, q, kept + r, oV, oN, oA0, oA1);
-			const uint64_t s = clip_find(slots, mask, clip_key(p, q));
-			if (s != CLIP_NOSLOT) slots[s].owner = r;  // (the owner found its slot in k_clip_own)
+			const uint64_t s = mesh_find(slots, mask, clip_key(p, q));
+			if (s != MESH_NOSLOT) slots[s].owner = r;  // (the owner found its slot in k_clip_own)
 			r++;
 		}
 	}
@@ -373,15 +307,10 @@ __global__ __launch_bounds__(256) void k_clip_emit(const uint32_t *__restrict__ 
 	__shared__ uint32_t sh[256];
 	if (!clip_fits(out, capV, capT)) return;
 	const uint32_t kept = (uint32_t)out->kept;
-	const uint64_t i0 = (uint64_t)blockIdx.x * CC_TILE + threadIdx.x * 4u;
-	uint32_t f[4], own = 0u;
-#pragma unroll
-	for (uint32_t k = 0; k < 4u; k++) {
-		f[k] = i0 + k < nT ? (uint32_t)info[i0 + k] : 0u;
-		own += f[k] & 3u;
-	}
-	uint32_t tot;
-	uint64_t r = (uint64_t)bsum[blockIdx.x] + block_excl_scan_256(own, sh, &tot);
+	const uint64_t i0 = mesh_tile_e0();
+	uint32_t f[4];
+	const uint32_t own = mesh_tile_load<ClipOutputs>(info, nT, f);
+	uint64_t r = mesh_tile_place(bsum, own, sh);
 #pragma unroll
 	for (uint32_t k = 0; k < 4u; k++) {
 		const uint32_t n = f[k] & 3u, cuts = (f[k] >> 2) & 7u;
@@ -394,10 +323,10 @@ __global__ __launch_bounds__(256) void k_clip_emit(const uint32_t *__restrict__ 
 		for (uint32_t e = 0; e < 3u; e++) {
 			const uint32_t p = e == 0u ? t0 : e == 1u ? t1 : t2, q = e == 0u ? t1 : e == 1u ? t2 : t0;
 			const uint32_t m = map[p];
-			if (m != FILT_NONE) g.push(m);
+			if (m != MESH_NONE) g.push(m);
 			if ((cuts >> e) & 1u) {
-				const uint64_t s = clip_find(slots, mask, clip_key(p, q));
-				g.push(kept + (s != CLIP_NOSLOT ? (uint32_t)slots[s].owner : 0u));
+				const uint64_t s = mesh_find(slots, mask, clip_key(p, q));
+				g.push(kept + (s != MESH_NOSLOT ? (uint32_t)slots[s].owner : 0u));
 			}
 		}
 		uint32_t *o = oT + r * 3u;
@@ -409,27 +338,13 @@ __global__ __launch_bounds__(256) void k_clip_emit(const uint32_t *__restrict__ 
 
 // --- host side ----------------------------------------------------------------------------------------------------------
 
-static void clip_destroy(MeasureState *m) {
-	ClipState *s = m->clip;
-	if (!s) return;
-	dev_release(&s->d_out); dev_release(&s->d_cls); dev_release(&s->d_keep); dev_release(&s->d_nf); dev_release(&s->d_map); dev_release(&s->d_info);
-	dev_release(&s->d_bsum); dev_release(&s->d_slots);
-	if (s->h_out) (void)hipHostFree(s->h_out);
-	free(s);
-	m->clip = nullptr;
+static void clip_release(void *state) {
+	ClipState *s = (ClipState *)state;
+	dev_release(&s->d_cls); dev_release(&s->d_nf); dev_release(&s->d_info); dev_release(&s->d_slots);
 }
-
-static int clip_state(mc33hip_ctx *c) {
-	int rc = meas_state(c);
-	if (rc) return rc;
-	ClipState *s = c->meas->clip;
-	if (!s) {
-		if (!(s = (ClipState *)calloc(1, sizeof *s))) return MC33HIP_ENOMEM;
-		c->meas->clip = s;  // (what it holds so far goes with the context)
-	}
-	if (!s->d_out) HIP_TRY(hipMalloc(&s->d_out, sizeof(ClipOut)));
-	if (!s->h_out) HIP_TRY(hipHostMalloc(&s->h_out, sizeof(ClipOut), hipHostMallocDefault));
-	return 0;
+static int clip_state(mc33hip_ctx *c, ClipState **s) {
+	const int rc = meas_state(c);
+	return rc ? rc : mesh_op_state(&c->meas->mesh, clip_release, s);
 }
 
 static void clip_fill(mc33hip_clipping *a, const ClipOut &h) {
@@ -442,8 +357,7 @@ extern "C" int mc33hip_clip_surface(mc33hip_ctx *c, mc33hip_clipping *a) {
 	a->nV_out = a->nT_out = a->kept_vertices = a->cut_vertices = a->on_plane_vertices = a->whole_triangles = a->cut_triangles = a->dropped_triangles =
 	    a->invalid_triangles = a->nonfinite_vertices = 0;
 	const unsigned long long nV = a->nV, nT = a->nT;
-	if (a->n_attr > 2u) { set_err("at most two attribute arrays, not %u", a->n_attr); return MC33HIP_EINVAL; }
-	if (!meas_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
+	if (!mesh_counts_ok(a->n_attr, nV, nT)) return MC33HIP_EINVAL;
 	for (unsigned k = 0; k < a->n_attr; k++)
 		if (a->attr_mode[k] != MC33HIP_CLIP_COPY && a->attr_mode[k] != MC33HIP_CLIP_LERP_F32) {
 			set_err("attr_mode[%u] = %d is neither MC33HIP_CLIP_COPY nor MC33HIP_CLIP_LERP_F32", k, a->attr_mode[k]);
@@ -452,43 +366,33 @@ extern "C" int mc33hip_clip_surface(mc33hip_ctx *c, mc33hip_clipping *a) {
 	for (int k = 0; k < 4; k++)
 		if (!clip_finite(a->plane[k])) { set_err("plane[%d] must be finite", k); return MC33HIP_EINVAL; }
 	if (a->plane[0] == 0.0 && a->plane[1] == 0.0 && a->plane[2] == 0.0) { set_err("the plane has no normal: a, b and c are all zero"); return MC33HIP_EINVAL; }
-	const uint64_t capV = std::min<unsigned long long>(a->capV, 0xFFFFFFFFull), capT = std::min<unsigned long long>(a->capT, 0xFFFFFFFFull);
-	bool null = (nV && !a->V) || (nT && !a->T) || (capV && !a->oV) || (capT && !a->oT);
-	for (unsigned k = 0; k < a->n_attr; k++) null = null || (nV && !a->attr[k]) || (capV && !a->oAttr[k]);
-	if (null) { set_err("a null pointer where the size is not zero"); return MC33HIP_EINVAL; }
+	const uint64_t capV = mesh_cap(a->capV), capT = mesh_cap(a->capT);
+	if (!mesh_pointers_ok((nV && !a->V) || (nT && !a->T) || (capV && !a->oV) || (capT && !a->oT), a->n_attr, a->attr, a->oAttr, nV, capV)) return MC33HIP_EINVAL;
 	if (a->oN && !a->N) { set_err("oN without N: the normals of the output are interpolated from those of the input"); return MC33HIP_EINVAL; }
 	// the call is not in place: no output may share a byte with an input or with another output
-	const void *in[5] = {a->V, a->N, a->T, a->n_attr > 0u ? a->attr[0] : nullptr, a->n_attr > 1u ? a->attr[1] : nullptr};
-	const uint64_t in_bytes[5] = {nV * 3u * sizeof(real_t), nV * 12u, nT * 12u, nV * 4u, nV * 4u};
-	const void *outp[6] = {a->oV, a->oT, a->oN, a->oMap, a->n_attr > 0u ? a->oAttr[0] : nullptr, a->n_attr > 1u ? a->oAttr[1] : nullptr};
-	const uint64_t out_bytes[6] = {capV * 3u * sizeof(real_t), capT * 12u, capV * 12u, nV * 4u, capV * 4u, capV * 4u};
-	for (int o = 0; o < 6; o++) {
-		for (int i = 0; i < 5; i++)
-			if (filt_ranges_meet(in[i], in_bytes[i], outp[o], out_bytes[o])) { set_err("an output array overlaps an input array: the clipping is not in place"); return MC33HIP_EINVAL; }
-		for (int p = o + 1; p < 6; p++)
-			if (filt_ranges_meet(outp[p], out_bytes[p], outp[o], out_bytes[o])) { set_err("two output arrays overlap"); return MC33HIP_EINVAL; }
-	}
+	const MeshRange in[5] = {{a->V, nV * 3u * sizeof(real_t)}, {a->N, nV * 12u}, {a->T, nT * 12u}, {a->n_attr > 0u ? a->attr[0] : nullptr, nV * 4u},
+	                         {a->n_attr > 1u ? a->attr[1] : nullptr, nV * 4u}};
+	const MeshRange out[6] = {{a->oV, capV * 3u * sizeof(real_t)}, {a->oT, capT * 12u}, {a->oN, capV * 12u}, {a->oMap, nV * 4u}, {a->n_attr > 0u ? a->oAttr[0] : nullptr, capV * 4u},
+	                          {a->n_attr > 1u ? a->oAttr[1] : nullptr, capV * 4u}};
+	if (!mesh_ranges_ok(in, 5, out, 6, true, "clipping")) return MC33HIP_EINVAL;
 	int rc = use_device(c);
 	if (rc) return rc;
-	if ((rc = clip_state(c))) return rc;
-	ClipState *s = c->meas->clip;
-	if (!nT || !nV) {  // no valid triangle: nothing is kept, every count is 0 (nV == 0: every triangle is invalid)
-		if (nV && a->oMap) HIP_TRY(hipMemsetAsync(a->oMap, 0xFF, nV * 4u, c->stream));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		if ((rc = prop_check(c))) return rc;
+	ClipState *s;
+	if ((rc = clip_state(c, &s))) return rc;
+	if (!nT || !nV) {  // every count is 0
+		if ((rc = mesh_empty(c, a->oMap, nV))) return rc;
 		a->invalid_triangles = nT;
-		return meas_bad(nT, nV);
+		return mesh_bad(nT, nV);
 	}
-	const uint64_t tilesV = (nV + CC_TILE - 1u) / CC_TILE, tilesT = (nT + CC_TILE - 1u) / CC_TILE;
-	const uint64_t nslots = topo_slots(nT);
+	MeshHost &h = c->meas->mesh;
+	const uint64_t tilesV = (nV + MESH_TILE - 1u) / MESH_TILE, tilesT = (nT + MESH_TILE - 1u) / MESH_TILE;
+	const uint64_t nslots = mesh_table_size(nT, 4u, 1ull << 40);
+	if ((rc = meas_scratch(c, nV, tilesV + 2u * tilesT))) return rc;
 	if ((rc = meas_room(&s->d_cls, &s->cls_cap, nV))) return rc;
-	if ((rc = meas_room(&s->d_keep, &s->keep_cap, nV))) return rc;
 	if ((rc = meas_room(&s->d_nf, &s->nf_cap, nV))) return rc;
-	if ((rc = meas_room(&s->d_map, &s->map_cap, nV))) return rc;
 	if ((rc = meas_room(&s->d_info, &s->info_cap, nT))) return rc;
-	if ((rc = meas_room(&s->d_bsum, &s->bsum_cap, tilesV + 2u * tilesT))) return rc;
 	if ((s->slots_cap < nslots || !s->d_slots) && (rc = dev_room("cut edge table", &s->d_slots, &s->slots_cap, nslots))) return rc;  // (a power of two as it is: no slack)
-	uint32_t *bsumV = s->d_bsum, *bsumO = s->d_bsum + tilesV, *bsumT = bsumO + tilesT;
+	uint32_t *bsumV = h.d_bsum, *bsumO = h.d_bsum + tilesV, *bsumT = bsumO + tilesT;
 	const real_t *V = (const real_t *)a->V;
 	const float *N = a->oN ? (const float *)a->N : nullptr;
 	const uint32_t *T = (const uint32_t *)a->T;
@@ -500,38 +404,27 @@ extern "C" int mc33hip_clip_surface(mc33hip_ctx *c, mc33hip_clipping *a) {
 	// (8 blocks per CU where a block ends with a set of atomics, as for the component table)
 	const uint32_t gridV = meas_grid(c, nV, 16u), gridT = meas_grid(c, nT, 16u), gridH = meas_grid(c, nT, 8u);
 	HIP_TRY(hipMemsetAsync(s->d_out, 0, sizeof(ClipOut), c->stream));
-	HIP_TRY(hipMemsetAsync(s->d_keep, 0, nV, c->stream));
+	HIP_TRY(hipMemsetAsync(h.d_keep, 0, nV, c->stream));
 	HIP_TRY(hipMemsetAsync(s->d_nf, 0, nV, c->stream));
-	hipLaunchKernelGGL(k_clip_clear, dim3(meas_grid(c, nslots, 16u)), dim3(256), 0, c->stream, s->d_slots, nslots);
+	hipLaunchKernelGGL(k_mesh_clear, dim3(meas_grid(c, nslots, 16u)), dim3(256), 0, c->stream, (ulonglong2 *)s->d_slots, nslots, ~0ull);  // (the owner: above every word)
 	hipLaunchKernelGGL((k_clip_class<real_t>), dim3(gridV), dim3(256), 0, c->stream, V, (uint64_t)nV, P, s->d_cls);
-	hipLaunchKernelGGL(k_clip_tri, dim3(gridH), dim3(256), 0, c->stream, T, (uint64_t)nT, (uint64_t)nV, s->d_cls, s->d_slots, nslots - 1u, s->d_keep, s->d_nf, s->d_info,
+	hipLaunchKernelGGL(k_clip_tri, dim3(gridH), dim3(256), 0, c->stream, T, (uint64_t)nT, (uint64_t)nV, s->d_cls, s->d_slots, nslots - 1u, h.d_keep, s->d_nf, s->d_info,
 	                   s->d_out);
 	hipLaunchKernelGGL(k_clip_own, dim3(gridT), dim3(256), 0, c->stream, T, (uint64_t)nT, s->d_slots, nslots - 1u, s->d_info, s->d_out);
-	hipLaunchKernelGGL((k_clip_tile_sum<0>), dim3((uint32_t)tilesV), dim3(256), 0, c->stream, s->d_keep, (uint64_t)nV, bsumV);
-	hipLaunchKernelGGL(k_filt_scan_top, dim3(1), dim3(256), 0, c->stream, bsumV, tilesV, &s->d_out->kept);
-	hipLaunchKernelGGL(k_filt_new, dim3((uint32_t)tilesV), dim3(256), 0, c->stream, s->d_keep, bsumV, (uint64_t)nV, s->d_map);
-	hipLaunchKernelGGL((k_clip_tile_sum<1>), dim3((uint32_t)tilesT), dim3(256), 0, c->stream, s->d_info, (uint64_t)nT, bsumO);
-	hipLaunchKernelGGL(k_filt_scan_top, dim3(1), dim3(256), 0, c->stream, bsumO, tilesT, &s->d_out->cutv);
-	hipLaunchKernelGGL((k_clip_tile_sum<2>), dim3((uint32_t)tilesT), dim3(256), 0, c->stream, s->d_info, (uint64_t)nT, bsumT);
-	hipLaunchKernelGGL(k_filt_scan_top, dim3(1), dim3(256), 0, c->stream, bsumT, tilesT, &s->d_out->nT_out);
+	mesh_scan<MeshFlag, MESH_NEW>(c, h.d_keep, nV, bsumV, &s->d_out->kept, h.d_map);
+	mesh_scan<ClipOwned>(c, s->d_info, nT, bsumO, &s->d_out->cutv);    // (k_clip_new places)
+	mesh_scan<ClipOutputs>(c, s->d_info, nT, bsumT, &s->d_out->nT_out);  // (k_clip_emit places)
 	// the writing passes: they compare the totals with the capacities on the device, so that the host waits once
-	hipLaunchKernelGGL((k_clip_rows<real_t>), dim3(gridV), dim3(256), 0, c->stream, V, N, A0, A1, s->d_map, s->d_cls, s->d_nf, (uint64_t)nV, s->d_out, capV, capT,
+	hipLaunchKernelGGL((k_clip_rows<real_t>), dim3(gridV), dim3(256), 0, c->stream, V, N, A0, A1, h.d_map, s->d_cls, s->d_nf, (uint64_t)nV, s->d_out, capV, capT,
 	                   (real_t *)a->oV, (float *)a->oN, oA0, oA1, (uint32_t *)a->oMap);
 	hipLaunchKernelGGL((k_clip_new<real_t>), dim3((uint32_t)tilesT), dim3(256), 0, c->stream, V, N, A0, A1, lerp0, lerp1, P, T, (uint64_t)nT, s->d_info, bsumO, s->d_slots,
 	                   nslots - 1u, s->d_out, capV, capT, (real_t *)a->oV, (float *)a->oN, oA0, oA1);
-	hipLaunchKernelGGL(k_clip_emit, dim3((uint32_t)tilesT), dim3(256), 0, c->stream, T, (uint64_t)nT, s->d_info, s->d_map, s->d_slots, nslots - 1u, bsumT, s->d_out, capV,
+	hipLaunchKernelGGL(k_clip_emit, dim3((uint32_t)tilesT), dim3(256), 0, c->stream, T, (uint64_t)nT, s->d_info, h.d_map, s->d_slots, nslots - 1u, bsumT, s->d_out, capV,
 	                   capT, (uint32_t *)a->oT);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, sizeof(ClipOut), hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	if ((rc = prop_check(c))) return rc;
-	const ClipOut h = *s->h_out;
-	clip_fill(a, h);
-	if (h.full) { set_err("%llu cut sides found no slot in the table", h.full); return MC33HIP_ERUNTIME; }
-	if (h.kept + h.cutv > capV || h.nT_out > capT) {
-		set_err("the clipped mesh needs %llu rows of V and %llu of T, the caller's arrays have %llu and %llu", h.kept + h.cutv, h.nT_out, (unsigned long long)capV,
-		        (unsigned long long)capT);
-		return MC33HIP_ECAPACITY;
-	}
-	return meas_bad(h.bad, nV);
+	if ((rc = mesh_op_fetch(c, s))) return rc;
+	const ClipOut o = *s->h_out;
+	clip_fill(a, o);
+	if (o.full) { set_err("%llu cut sides found no slot in the table", o.full); return MC33HIP_ERUNTIME; }
+	if ((rc = mesh_capacity("clipped", o.kept + o.cutv, o.nT_out, capV, capT))) return rc;
+	return mesh_bad(o.bad, nV);
 }

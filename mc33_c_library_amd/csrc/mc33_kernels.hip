@@ -36,11 +36,14 @@
 //                   stream beside the fast passes, when they are many.
 // Not part of an extraction: k_property<R,COLOR> - a property grid sampled at the vertices of a finished V array, one lane per
 //                   vertex; float values or palette colours (mc33_property.hip.h).
+//                   k_mesh_* - what the passes over a finished mesh share: the tile scan (sums per tile, one block over them, a
+//                   placing pass), the table of 64-bit keys claimed by compare-and-swap, referenced flags; the registration of
+//                   the parts' states and their shared scratch (mc33_mesh.hip.h).
 //                   k_measure_* / k_cc_* - area, volume, moments, bounding box and connected components of a finished V, T pair;
 //                   a few doubles come back instead of the mesh (mc33_measure.hip.h).
 //                   k_topo_* - an edge table of a finished T in device memory: boundary, non-manifold and misoriented edges,
 //                   boundary loops, Euler number and genus, for the surface and per component (mc33_topology.hip.h).
-//                   k_filt_* - keep or drop whole components of a finished V, N, T: flags, two exclusive scans, two copying passes;
+//                   k_filt_* - keep or drop whole components of a finished V, N, T: flags, two tile scans, two copying passes;
 //                   the rows keep their order (mc33_filter.hip.h).
 //                   k_sm_* - Taubin smoothing of a finished V over the adjacency of T, a CSR list made on the device, and vertex
 //                   normals recomputed from the triangles; k_sm_pass is its hot path (mc33_smooth.hip.h).
@@ -113,6 +116,7 @@ typedef float sample_t;
 #include "mc33_context.hip.h"
 #include "mc33_extract.hip.h"
 #include "mc33_property.hip.h"
+#include "mc33_mesh.hip.h"
 #include "mc33_measure.hip.h"
 #include "mc33_topology.hip.h"
 #include "mc33_filter.hip.h"

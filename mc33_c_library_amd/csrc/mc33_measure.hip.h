@@ -1,4 +1,4 @@
-// mc33_measure.hip.h -- part of the ONE translation unit mc33_kernels.hip (included there, last; not a header to include elsewhere):
+// mc33_measure.hip.h -- part of the ONE translation unit mc33_kernels.hip (builds on mc33_mesh.hip.h; not a header to include elsewhere):
 // questions about a FINISHED mesh in device memory, answered there - area, signed volume, first moments, bounding box, the
 // integral of a sampled property, connected components - so that a few doubles cross the link instead of the mesh
 // (include/mc33_hip.h: mc33hip_measure_surface, mc33hip_label_components, mc33hip_measure_components).  DESIGN.md 10.
@@ -32,29 +32,10 @@ struct MeasureState {       // scratch of these passes: on the context from the 
 	uint64_t flags_cap;
 	uint32_t *d_rank;       // [nV] exclusive sum of the flags: the component's row in the table
 	uint64_t rank_cap;
-	uint32_t *d_bsum;       // flags per block of CC_TILE vertices, scanned in place
-	uint64_t bsum_cap;
 	mc33hip_component *d_table;
 	uint64_t table_cap;
-	struct TopoState *topo;  // scratch of the topology passes (mc33_topology.hip.h), made by the first of them
-	struct FilterState *filt;  // scratch of the compaction (mc33_filter.hip.h), likewise
-	struct SmoothState *smooth;  // scratch of the smoothing (mc33_smooth.hip.h), likewise
-	struct SimpState *simp;  // scratch of the simplification (mc33_simplify.hip.h), likewise
-	struct ClipState *clip;  // scratch of the clipping (mc33_clip.hip.h), likewise
-	struct ResampleState *resample;  // the taps of the grid resampling (mc33_resample.hip.h), likewise
-	struct SpectrumState *spectrum;  // isovalues and counters of the contour spectrum (mc33_spectrum.hip.h), likewise
+	MeshHost mesh;          // the states of the parts behind this one, and the scratch they share with it (mc33_mesh.hip.h)
 };
-static void topo_destroy(MeasureState *m);
-static void filt_destroy(MeasureState *m);
-static void smooth_destroy(MeasureState *m);
-static void simp_destroy(MeasureState *m);
-static void rs_destroy(MeasureState *m);
-static void sp_destroy(MeasureState *m);
-static void clip_destroy(MeasureState *m);
-
-constexpr uint32_t CC_TILE = 1024u;  // vertices per block of k_cc_count / k_cc_rank: 256 lanes x 4
-
-__device__ __forceinline__ double shfl_down_f64(double x, int d) { return __shfl_down(x, d, 64); }
 
 // sum over the block's 256 lanes in a fixed order: offsets 32 .. 1 inside a wave, the four waves in index order.  Lane 0 of the
 // block holds the result.
@@ -284,27 +265,11 @@ __global__ __launch_bounds__(256) void k_cc_flag(const uint32_t *__restrict__ T,
 	if (bad && bad_out) atomicAdd(bad_out, (unsigned long long)bad);
 }
 
-// exclusive sum over the block's 256 lanes of x (a count <= 4); *total: the block's sum.  sh: [256]
-__device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t x, uint32_t *sh, uint32_t *total) {
-	const uint32_t t = threadIdx.x;
-	__syncthreads();
-	sh[t] = x;
-	__syncthreads();
-	for (uint32_t d = 1u; d < 256u; d <<= 1) {
-		const uint32_t o = t >= d ? sh[t - d] : 0u;
-		__syncthreads();
-		sh[t] += o;
-		__syncthreads();
-	}
-	*total = sh[255];
-	return sh[t] - x;
-}
-
 // components (flagged roots) and unreferenced vertices (roots of themselves that own nothing), and the flags per tile for the scan
 __global__ __launch_bounds__(256) void k_cc_count(const uint32_t *__restrict__ label, const uint8_t *__restrict__ flags, uint64_t nV,
                                                   uint32_t *__restrict__ bsum, MeasOut *__restrict__ out) {
-	__shared__ uint32_t sh[256];
-	const uint64_t v0 = (uint64_t)blockIdx.x * CC_TILE + threadIdx.x * 4u;
+	__shared__ uint32_t sh[4];
+	const uint64_t v0 = mesh_tile_e0();
 	uint32_t own = 0u, lone = 0u;
 #pragma unroll
 	for (uint32_t k = 0; k < 4u; k++) {
@@ -315,69 +280,12 @@ __global__ __launch_bounds__(256) void k_cc_count(const uint32_t *__restrict__ l
 			lone += (!f && label[v] == (uint32_t)v) ? 1u : 0u;
 		}
 	}
-	uint32_t tot_own, tot_lone;
-	(void)block_excl_scan_256(own, sh, &tot_own);
-	(void)block_excl_scan_256(lone, sh, &tot_lone);
+	const uint32_t tot_own = block_sum_u32_256(own, sh), tot_lone = block_sum_u32_256(lone, sh);
 	if (threadIdx.x == 0u) {
 		bsum[blockIdx.x] = tot_own;
 		if (tot_own) atomicAdd(&out->comps, (unsigned long long)tot_own);
 		if (tot_lone) atomicAdd(&out->unref, (unsigned long long)tot_lone);
 	}
-}
-
-// one block: bsum -> its exclusive sums, in place
-__global__ __launch_bounds__(256) void k_cc_scan_top(uint32_t *__restrict__ bsum, uint64_t n) {
-	__shared__ uint32_t sh[256];
-	uint32_t carry = 0u;
-	for (uint64_t base = 0; base < n; base += 256u) {
-		const uint64_t k = base + threadIdx.x;
-		const uint32_t x = k < n ? bsum[k] : 0u;
-		uint32_t tot;
-		const uint32_t e = block_excl_scan_256(x, sh, &tot);
-		if (k < n) bsum[k] = carry + e;
-		carry += tot;
-	}
-}
-
-// rank[v] = flagged roots below v: the row of v's component in the table, where v is such a root
-__global__ __launch_bounds__(256) void k_cc_rank(const uint8_t *__restrict__ flags, const uint32_t *__restrict__ bsum, uint64_t nV, uint32_t *__restrict__ rank) {
-	__shared__ uint32_t sh[256];
-	const uint64_t v0 = (uint64_t)blockIdx.x * CC_TILE + threadIdx.x * 4u;
-	uint32_t f[4], own = 0u;
-#pragma unroll
-	for (uint32_t k = 0; k < 4u; k++) {
-		f[k] = v0 + k < nV ? flags[v0 + k] : 0u;
-		own += f[k];
-	}
-	uint32_t tot;
-	uint32_t r = bsum[blockIdx.x] + block_excl_scan_256(own, sh, &tot);
-#pragma unroll
-	for (uint32_t k = 0; k < 4u; k++) {
-		if (v0 + k < nV) rank[v0 + k] = r;
-		r += f[k];
-	}
-}
-
-// Sums over runs of equal keys in consecutive lanes of a wave: `heads` has a bit for every lane that begins a run; after the
-// call the first lane of each run holds the run's sum.
-__device__ __forceinline__ bool run_open(unsigned long long heads, uint32_t lane, int d) {  // lane + d belongs to lane's run
-	return lane + (uint32_t)d < 64u && ((heads >> (lane + 1u)) & ((1ull << d) - 1ull)) == 0ull;
-}
-__device__ __forceinline__ double run_sum_f64(double x, unsigned long long heads, uint32_t lane) {
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const double o = shfl_down_f64(x, d);
-		if (run_open(heads, lane, d)) x += o;
-	}
-	return x;
-}
-__device__ __forceinline__ uint32_t run_sum_u32(uint32_t x, unsigned long long heads, uint32_t lane) {
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const uint32_t o = __shfl_down(x, d, 64);
-		if (run_open(heads, lane, d)) x += o;
-	}
-	return x;
 }
 
 __device__ __forceinline__ void table_flush(mc33hip_component *table, uint32_t key, uint32_t n, double a, double w) {
@@ -505,14 +413,8 @@ __global__ __launch_bounds__(256) void k_cc_table_vertices(const uint32_t *__res
 static void meas_destroy(mc33hip_ctx *c) {
 	MeasureState *m = c->meas;
 	if (!m) return;
-	topo_destroy(m);
-	filt_destroy(m);
-	smooth_destroy(m);
-	simp_destroy(m);
-	rs_destroy(m);
-	sp_destroy(m);
-	clip_destroy(m);
-	dev_release(&m->d_out); dev_release(&m->d_part); dev_release(&m->d_flags); dev_release(&m->d_rank); dev_release(&m->d_bsum); dev_release(&m->d_table);
+	mesh_host_destroy(&m->mesh);
+	dev_release(&m->d_out); dev_release(&m->d_part); dev_release(&m->d_flags); dev_release(&m->d_rank); dev_release(&m->d_table);
 	if (m->h_out) (void)hipHostFree(m->h_out);
 	free(m);
 	c->meas = nullptr;
@@ -550,27 +452,20 @@ static int meas_zero_counters(mc33hip_ctx *c) {
 	return 0;
 }
 
-// the result block to the host behind everything enqueued; waits
-static int meas_fetch(mc33hip_ctx *c) {
-	HIP_TRY(hipMemcpyAsync(c->meas->h_out, c->meas->d_out, sizeof(MeasOut), hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	return prop_check(c);
-}
+static int meas_fetch(mc33hip_ctx *c) { return mesh_op_fetch(c, c->meas); }
 
-static int meas_bad(unsigned long long n, unsigned long long nV) {
-	if (!n) return 0;
-	set_err("%llu triangle%s name%s a vertex outside the %llu rows of V (or of the label array): left out of every sum", n, n == 1 ? "" : "s", n == 1 ? "s" : "", nV);
-	return MC33HIP_ERUNTIME;
-}
-
-static bool meas_sizes_ok(unsigned long long nV, unsigned long long nT) {
-	if (nV > 0xFFFFFFFFull || nT > 0xFFFFFFFFull) { set_err("more than 2^32-1 vertices or triangles"); return false; }
-	return true;
+// room in the scratch the mesh parts share: flags and new indices of nV vertices, `tiles` tile sums
+static int meas_scratch(mc33hip_ctx *c, uint64_t nV, uint64_t tiles) {
+	MeshHost &h = c->meas->mesh;
+	int rc;
+	if ((rc = meas_room(&h.d_keep, &h.keep_cap, nV))) return rc;
+	if ((rc = meas_room(&h.d_map, &h.map_cap, nV))) return rc;
+	return meas_room(&h.d_bsum, &h.bsum_cap, tiles);
 }
 
 extern "C" int mc33hip_measure_surface(mc33hip_ctx *c, const void *dV, unsigned long long nV, const void *dT, unsigned long long nT, const float *dP,
                                        mc33hip_measures *out) {
-	if (!c || !out || (nV && !dV) || (nT && !dT) || !meas_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
+	if (!c || !out || (nV && !dV) || (nT && !dT) || !mesh_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
 	int rc = use_device(c);
 	if (rc) return rc;
 	if ((rc = meas_state(c))) return rc;
@@ -591,7 +486,6 @@ extern "C" int mc33hip_measure_surface(mc33hip_ctx *c, const void *dV, unsigned 
 	}
 	if (nV) hipLaunchKernelGGL((k_measure_bbox<real_t>), dim3(gridV), dim3(256), 0, c->stream, (const real_t *)dV, (uint64_t)nV, bpart);
 	hipLaunchKernelGGL(k_measure_finish, dim3(1), dim3(256), 0, c->stream, m->d_part, gridT, bpart, gridV, m->d_out);
-	HIP_TRY(hipGetLastError());
 	if ((rc = meas_fetch(c))) return rc;
 	const MeasOut &h = *m->h_out;
 	memset(out, 0, sizeof *out);
@@ -600,7 +494,7 @@ extern "C" int mc33hip_measure_surface(mc33hip_ctx *c, const void *dV, unsigned 
 	for (int a = 0; a < 3; a++) { out->moment[a] = h.sum[2 + a]; out->origin[a] = o[a]; out->bbox_min[a] = h.bbox[a]; out->bbox_max[a] = h.bbox[3 + a]; }
 	out->has_property = dP ? 1 : 0;
 	out->property_integral = dP ? h.sum[5] : 0.0;
-	return meas_bad(h.bad, nV);
+	return mesh_bad(h.bad, nV);
 }
 
 // flags of the roots that own a triangle, their number and the unreferenced vertices (enqueues; the counters were zeroed).
@@ -608,21 +502,21 @@ extern "C" int mc33hip_measure_surface(mc33hip_ctx *c, const void *dV, unsigned 
 static int cc_flag_and_count(mc33hip_ctx *c, const void *dT, unsigned long long nT, unsigned long long nV, const unsigned *dLabel, bool check) {
 	MeasureState *m = c->meas;
 	int rc;
-	const uint64_t tiles = (nV + CC_TILE - 1u) / CC_TILE;
+	const uint64_t tiles = (nV + MESH_TILE - 1u) / MESH_TILE;
 	if ((rc = meas_room(&m->d_flags, &m->flags_cap, nV))) return rc;
-	if ((rc = meas_room(&m->d_bsum, &m->bsum_cap, tiles))) return rc;
+	if ((rc = meas_room(&m->mesh.d_bsum, &m->mesh.bsum_cap, tiles))) return rc;
 	if (!nV) return 0;
 	HIP_TRY(hipMemsetAsync(m->d_flags, 0, nV, c->stream));
 	if (nT) hipLaunchKernelGGL(k_cc_flag, dim3(meas_grid(c, nT, 16u)), dim3(256), 0, c->stream, (const uint32_t *)dT, (uint64_t)nT, (uint64_t)nV, dLabel, m->d_flags,
 	                           check ? &m->d_out->bad : (unsigned long long *)nullptr);
-	hipLaunchKernelGGL(k_cc_count, dim3((uint32_t)tiles), dim3(256), 0, c->stream, dLabel, m->d_flags, (uint64_t)nV, m->d_bsum, m->d_out);
+	hipLaunchKernelGGL(k_cc_count, dim3((uint32_t)tiles), dim3(256), 0, c->stream, dLabel, m->d_flags, (uint64_t)nV, m->mesh.d_bsum, m->d_out);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
 
 extern "C" int mc33hip_label_components(mc33hip_ctx *c, const void *dT, unsigned long long nT, unsigned long long nV, unsigned *dLabel,
                                         unsigned long long *components, unsigned long long *unreferenced) {
-	if (!c || (nV && !dLabel) || (nT && !dT) || !meas_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
+	if (!c || (nV && !dLabel) || (nT && !dT) || !mesh_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
 	int rc = use_device(c);
 	if (rc) return rc;
 	if ((rc = meas_state(c))) return rc;
@@ -636,12 +530,12 @@ extern "C" int mc33hip_label_components(mc33hip_ctx *c, const void *dT, unsigned
 	if ((rc = meas_fetch(c))) return rc;
 	if (components) *components = m->h_out->comps;
 	if (unreferenced) *unreferenced = m->h_out->unref;
-	return meas_bad(m->h_out->bad, nV);
+	return mesh_bad(m->h_out->bad, nV);
 }
 
 extern "C" int mc33hip_measure_components(mc33hip_ctx *c, const void *dV, unsigned long long nV, const void *dT, unsigned long long nT, const unsigned *dLabel,
                                           mc33hip_component *host_table, unsigned long long capacity, unsigned long long *components) {
-	if (!c || !components || (nV && (!dV || !dLabel)) || (nT && !dT) || (capacity && !host_table) || !meas_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
+	if (!c || !components || (nV && (!dV || !dLabel)) || (nT && !dT) || (capacity && !host_table) || !mesh_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
 	int rc = use_device(c);
 	if (rc) return rc;
 	if ((rc = meas_state(c))) return rc;
@@ -650,12 +544,11 @@ extern "C" int mc33hip_measure_components(mc33hip_ctx *c, const void *dV, unsign
 	if ((rc = meas_zero_counters(c))) return rc;
 	if ((rc = cc_flag_and_count(c, dT, nT, nV, dLabel, true))) return rc;
 	if ((rc = meas_fetch(c))) return rc;
-	if ((rc = meas_bad(m->h_out->bad, nV))) return rc;
+	if ((rc = mesh_bad(m->h_out->bad, nV))) return rc;
 	const unsigned long long ncomp = m->h_out->comps;
 	*components = ncomp;
 	if (capacity < ncomp) { set_err("the component table needs %llu rows, the caller's has %llu", ncomp, capacity); return MC33HIP_ECAPACITY; }
 	if (!ncomp) return MC33HIP_OK;
-	const uint64_t tiles = (nV + CC_TILE - 1u) / CC_TILE;
 	if ((rc = meas_room(&m->d_rank, &m->rank_cap, nV))) return rc;
 	if ((rc = meas_room(&m->d_table, &m->table_cap, ncomp))) return rc;
 	HIP_TRY(hipMemsetAsync(m->d_table, 0, ncomp * sizeof(mc33hip_component), c->stream));
@@ -665,13 +558,12 @@ extern "C" int mc33hip_measure_components(mc33hip_ctx *c, const void *dV, unsign
 	// (8 blocks per CU: every block ends with a set of atomics, and on a one-component surface they all meet in one row)
 	const uint32_t gridT = meas_grid(c, nT, 8u), gridV = meas_grid(c, nV, 8u);
 	const uint64_t chunk = ((nT + gridT - 1u) / gridT + 255u) / 256u * 256u, chunkV = ((nV + gridV - 1u) / gridV + 255u) / 256u * 256u;
-	hipLaunchKernelGGL(k_cc_scan_top, dim3(1), dim3(256), 0, c->stream, m->d_bsum, tiles);
-	hipLaunchKernelGGL(k_cc_rank, dim3((uint32_t)tiles), dim3(256), 0, c->stream, m->d_flags, m->d_bsum, (uint64_t)nV, m->d_rank);
+	mesh_scan_sums<MeshFlag, MESH_RANK>(c, m->d_flags, nV, m->mesh.d_bsum, nullptr, m->d_rank);
 	hipLaunchKernelGGL((k_cc_table_triangles<real_t>), dim3(gridT), dim3(256), 0, c->stream, (const real_t *)dV, (uint64_t)nV, (const uint32_t *)dT, (uint64_t)nT, dLabel,
 	                   m->d_flags, m->d_rank, o[0], o[1], o[2], chunk, m->d_table, &m->d_out->bad);
 	hipLaunchKernelGGL(k_cc_table_vertices, dim3(gridV), dim3(256), 0, c->stream, dLabel, m->d_flags, m->d_rank, (uint64_t)nV, chunkV, m->d_table);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(host_table, m->d_table, ncomp * sizeof(mc33hip_component), hipMemcpyDeviceToHost, c->stream));
 	if ((rc = meas_fetch(c))) return rc;
-	return meas_bad(m->h_out->bad, nV);
+	return mesh_bad(m->h_out->bad, nV);
 }

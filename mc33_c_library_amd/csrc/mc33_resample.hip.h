@@ -265,13 +265,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_resample(const T *__restrict_
 
 // --- host side ----------------------------------------------------------------------------------------------------------
 
-static void rs_destroy(MeasureState *m) {
-	ResampleState *s = m->resample;
-	if (!s) return;
-	dev_release(&s->d_taps);
-	free(s);
-	m->resample = nullptr;
-}
+static void rs_release(void *state) { dev_release(&((ResampleState *)state)->d_taps); }
 
 // arguments -> plan and taps; MC33HIP_EINVAL with the reason in mc33hip_last_error
 static int rs_check(mc33hip_ctx *c, const mc33hip_resampling *r, RsPlan &p, double taps[RS_TAP_WORDS]) {
@@ -322,18 +316,16 @@ extern "C" int mc33hip_resample_grid(mc33hip_ctx *c, const mc33hip_resampling *r
 	// not in place: the bytes from the first to the last grid point of either grid must not meet
 	const uint64_t src_bytes = (((uint64_t)p.ax[2].n_src - 1u) * c->slice + ((uint64_t)p.ax[1].n_src - 1u) * c->pitch + (uint64_t)p.ax[0].n_src) * sizeof(sample_t);
 	const uint64_t dst_bytes = (((uint64_t)p.ax[2].n_out - 1u) * slice + ((uint64_t)p.ax[1].n_out - 1u) * pitch + (uint64_t)p.ax[0].n_out) * sizeof(sample_t);
-	if (filt_ranges_meet(c->d_grid, src_bytes, dst, dst_bytes)) { set_err("dst overlaps the source grid: the resampling is not in place"); return MC33HIP_EINVAL; }
+	if (mesh_ranges_meet(c->d_grid, src_bytes, dst, dst_bytes)) { set_err("dst overlaps the source grid: the resampling is not in place"); return MC33HIP_EINVAL; }
 	p.spitch = c->pitch; p.sslice = c->slice; p.dpitch = pitch; p.dslice = slice;
 	rs_plan_tiles(p);
 	const long long blocks = p.tiles_x * p.tiles_y * p.chunks_z;
 	if (blocks > 0x7FFFFFFFll) { set_err("%lld tiles: more than a launch takes", blocks); return MC33HIP_EINVAL; }
 	if ((rc = use_device(c))) return rc;
 	if ((rc = meas_state(c))) return rc;
-	ResampleState *s = c->meas->resample;
-	if (!s) {
-		if (!(s = (ResampleState *)calloc(1, sizeof *s))) return MC33HIP_ENOMEM;
-		c->meas->resample = s;
-	}
+	MeshOp *op;
+	if ((rc = mesh_op_find(&c->meas->mesh, rs_release, sizeof(ResampleState), &op))) return rc;
+	ResampleState *s = (ResampleState *)op->state;
 	if (!s->d_taps) HIP_TRY(hipMalloc(&s->d_taps, RS_TAP_WORDS * sizeof(double)));
 	// (the taps are in pageable host memory: the copy has left it when the call returns, and is ordered on the stream)
 	HIP_TRY(hipMemcpyAsync(s->d_taps, taps, RS_TAP_WORDS * sizeof(double), hipMemcpyHostToDevice, c->stream));

@@ -1,25 +1,22 @@
-// mc33_simplify.hip.h -- part of the ONE translation unit mc33_kernels.hip (included there, last; not a header to include elsewhere):
+// mc33_simplify.hip.h -- part of the ONE translation unit mc33_kernels.hip (builds on mc33_mesh.hip.h, and on mc33_smooth.hip.h for the normals of its output; not a header to include elsewhere):
 // vertex clustering of a FINISHED mesh in device memory on an axis-aligned lattice - every lattice cell's vertices become one,
 // triangles that lose a corner or repeat another go - so that a surface of the resolution a caller wants crosses the link
 // (include/mc33_hip.h: mc33hip_simplify_surface).  DESIGN.md 14.
 //
 // The definition is in include/mc33_hip.h; tests/simplify_oracle.py restates it in numpy.  Integer atomics and exclusive scans
 // decide everything: the result is an exact function of the input.
-// The passes: k_simp_ref flags the referenced vertices (the form of k_filt_ref); k_simp_cluster, the hot path, a lane per vertex,
-// claims the slot of the vertex's key in an open-addressing table by 64-bit compare-and-swap (the table of mc33_topology.hip.h)
-// and adds into it - atomicMin of the representative, atomicAdd of the member count and of the three 64-bit sums - once per run
-// of equal keys in a wave (the run sums of TopoHeld); k_simp_reps gathers rep(v) and counts clusters; k_simp_tri_insert enters
-// the images that are not collapsed into a table of 32-bit words that hold TRIANGLE INDICES - the key of a word is recomputed
+// The passes: k_mesh_ref flags the referenced vertices; k_simp_cluster, the hot path, a lane per vertex, claims the slot of the
+// vertex's key in the table of mc33_mesh.hip.h and adds into it - atomicMin of the representative, atomicAdd of the member count
+// and of the three 64-bit sums - once per run of equal keys in a wave; k_simp_reps gathers rep(v) and counts clusters;
+// k_simp_tri_insert enters the images that are not collapsed into a table of 32-bit words that hold TRIANGLE INDICES - the key of a word is recomputed
 // from the triangle it names, the smallest index of an image stays by atomicMin -; k_simp_tri_keep flags the survivors and
-// their representatives; k_simp_tile_count / k_filt_scan_top / k_filt_new are the scans of section 12; k_simp_rows and
+// their representatives; the tile scans of mc33_mesh.hip.h place vertices and triangles; k_simp_rows and
 // k_simp_tris write.  Nothing a block wrote with plain stores is read by another block of the same kernel: slots, reps, counts
 // and sums are atomics, their readers are later kernels.
 
-struct SimpSlot { unsigned long long key; uint32_t rep, cnt; unsigned long long sum[3]; };  // 40 bytes; key all ones: empty
+struct SimpSlot { unsigned long long key; uint32_t rep, cnt; unsigned long long sum[3]; };  // 40 bytes; keys have 63 bits
 struct SimpLattice { double origin[3], cell[3]; };
 
-constexpr unsigned long long SIMP_EMPTY = ~0ull;  // (keys have 63 bits)
-constexpr uint32_t SIMP_NONE = 0xFFFFFFFFu;
 constexpr double SIMP_CELLS = 2097152.0;          // 2^21 cells per axis
 constexpr double SIMP_UNIT = 4294967296.0;        // 2^32 steps inside a cell
 
@@ -29,22 +26,17 @@ struct SimpOut {            // what a call brings to the host (device copy and p
 	unsigned long long pad_[3];
 };
 
-struct SimpState {          // scratch of these passes: on the MeasureState from the first call on, grown on demand, freed with it
+struct SimpState {          // scratch of these passes besides the shared keep (1: a surviving triangle names this representative), map (new[r]) and
+                            // tile sums (the vertex tiles, behind them the triangle tiles): on the MeasureState from the first call on, grown on demand, freed with it
 	SimpOut *d_out, *h_out;
 	uint8_t *d_ref;         // [nV] referenced
 	uint64_t ref_cap;
-	uint32_t *d_slot;       // [nV] the slot of the vertex's cluster, SIMP_NONE where no triangle names it
+	uint32_t *d_slot;       // [nV] the slot of the vertex's cluster, MESH_NONE where no triangle names it
 	uint64_t slot_cap;
-	uint32_t *d_rep;        // [nV] rep(v), SIMP_NONE likewise
+	uint32_t *d_rep;        // [nV] rep(v), MESH_NONE likewise
 	uint64_t rep_cap;
-	uint8_t *d_keep;        // [nV] 1: a surviving triangle names this representative
-	uint64_t keep_cap;
-	uint32_t *d_map;        // [nV] new[r], FILT_NONE where r is not a kept representative
-	uint64_t map_cap;
 	uint8_t *d_surv;        // [nT] 1: the triangle survives
 	uint64_t surv_cap;
-	uint32_t *d_bsum;       // flags per tile, scanned in place: the vertex tiles, behind them the triangle tiles
-	uint64_t bsum_cap;
 	SimpSlot *d_slots;      // the cluster table: a power of two >= 2 nV slots
 	uint64_t slots_cap;
 	uint32_t *d_tri;        // the image table: a power of two >= 2 nT words
@@ -66,42 +58,17 @@ __device__ __forceinline__ uint32_t simp_axis(double x, double origin, double ce
 	return clamped;
 }
 
-__device__ __forceinline__ unsigned long long shfl_down_u64(unsigned long long x, int d) {
-	const uint32_t lo = __shfl_down((uint32_t)x, d, 64), hi = __shfl_down((uint32_t)(x >> 32), d, 64);
-	return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned long long run_sum_u64(unsigned long long x, unsigned long long heads, uint32_t lane) {
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const unsigned long long o = shfl_down_u64(x, d);
-		if (run_open(heads, lane, d)) x += o;
-	}
-	return x;
-}
-
 __global__ __launch_bounds__(256) void k_simp_clear(SimpSlot *__restrict__ slots, uint64_t n) {
 	for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < n; s += (uint64_t)gridDim.x * 256u) {
 		SimpSlot e;
-		e.key = SIMP_EMPTY; e.rep = SIMP_NONE; e.cnt = 0u; e.sum[0] = e.sum[1] = e.sum[2] = 0ull;
+		e.key = MESH_EMPTY; e.rep = MESH_NONE; e.cnt = 0u; e.sum[0] = e.sum[1] = e.sum[2] = 0ull;
 		slots[s] = e;
 	}
 }
 
-__global__ __launch_bounds__(256) void k_simp_ref(const uint32_t *__restrict__ T, uint64_t nT, uint64_t nV, uint8_t *__restrict__ ref, SimpOut *__restrict__ out) {
-	uint32_t bad = 0u;
-	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < nT; i += (uint64_t)gridDim.x * 256u) {
-		const uint32_t *t = T + i * 3u;
-		const uint32_t t0 = t[0], t1 = t[1], t2 = t[2];
-		if (t0 >= nV || t1 >= nV || t2 >= nV) { bad++; continue; }
-		ref[t0] = 1; ref[t1] = 1; ref[t2] = 1;  // (every racing store writes the same 1)
-	}
-	if (bad) atomicAdd(&out->bad, (unsigned long long)bad);
-}
-
 // The hot path.  Every block a contiguous piece of V, every wave 64 consecutive vertices a step; every lane of the wave takes
 // every step.  The emit stage's order is spatially coherent: most of a step's lanes share a few keys, and consecutive lanes with
-// one key are a run - its first lane (the smallest v of the run) claims the slot and adds the run's sums.  What the
-// compare-and-swap on the key RETURNS decides - empty or equal: this is the cluster's slot; anything else: probe on, linearly.
+// one key are a run - its first lane (the smallest v of the run) claims the slot (mesh_claim) and adds the run's sums.
 // A slot that takes thousands of members scattered over the array takes as many atomics: slow, and as right as any other.
 template <typename R>
 __global__ __launch_bounds__(256) void k_simp_cluster(const R *__restrict__ V, const uint8_t *__restrict__ ref, uint64_t nV, uint64_t chunk, SimpLattice L, uint32_t mean,
@@ -112,7 +79,7 @@ __global__ __launch_bounds__(256) void k_simp_cluster(const R *__restrict__ V, c
 	uint32_t clamped = 0u, full = 0u;
 	for (uint64_t base = beg + (threadIdx.x & ~63u); base < end; base += 256u) {  // (wave-uniform)
 		const uint64_t v = base + lane;
-		unsigned long long key = SIMP_EMPTY, q[3] = {0ull, 0ull, 0ull};
+		unsigned long long key = MESH_EMPTY, q[3] = {0ull, 0ull, 0ull};
 		if (v < end && ref[v]) {
 			const R *p = V + v * 3u;
 			unsigned long long k[3];
@@ -129,19 +96,16 @@ __global__ __launch_bounds__(256) void k_simp_cluster(const R *__restrict__ V, c
 		const uint32_t before_lo = __shfl_up((uint32_t)key, 1, 64), before_hi = __shfl_up((uint32_t)(key >> 32), 1, 64);
 		const bool head = lane == 0u || (((unsigned long long)before_hi << 32) | before_lo) != key;
 		const unsigned long long heads = __ballot(head);
-		const uint32_t n = run_sum_u32(key != SIMP_EMPTY ? 1u : 0u, heads, lane);
+		const uint32_t n = run_sum_u32(key != MESH_EMPTY ? 1u : 0u, heads, lane);
 		if (mean) {  // (uniform)
 #pragma unroll
 			for (int a = 0; a < 3; a++) q[a] = run_sum_u64(q[a], heads, lane);
 		}
-		uint32_t slot = SIMP_NONE;
-		if (head && key != SIMP_EMPTY) {
-			uint64_t s = topo_mix(key) & mask;
-			for (uint64_t tries = 0; tries <= mask; tries++, s = (s + 1u) & mask) {
-				const unsigned long long old = atomicCAS(&slots[s].key, SIMP_EMPTY, key);
-				if (old == SIMP_EMPTY || old == key) { slot = (uint32_t)s; break; }
-			}
-			if (slot != SIMP_NONE) {
+		uint32_t slot = MESH_NONE;
+		if (head && key != MESH_EMPTY) {
+			const uint64_t s = mesh_claim(slots, mask, key);
+			if (s != MESH_NOSLOT) {
+				slot = (uint32_t)s;
 				atomicMin(&slots[slot].rep, (uint32_t)v);
 				atomicAdd(&slots[slot].cnt, n);
 				if (mean) {
@@ -153,10 +117,10 @@ __global__ __launch_bounds__(256) void k_simp_cluster(const R *__restrict__ V, c
 		}
 		const int first = 63 - __clzll((long long)(heads & (~0ull >> (63u - lane))));  // the lane that began this lane's run (lane 0 begins one)
 		slot = __shfl(slot, first, 64);
-		if (v < end) slotof[v] = key != SIMP_EMPTY ? slot : SIMP_NONE;
+		if (v < end) slotof[v] = key != MESH_EMPTY ? slot : MESH_NONE;
 	}
-	clamped = topo_block_sum(clamped, sh);
-	full = topo_block_sum(full, sh);
+	clamped = block_sum_u32_256(clamped, sh);
+	full = block_sum_u32_256(full, sh);
 	if (threadIdx.x == 0u) {
 		if (clamped) atomicAdd(&out->clamped, (unsigned long long)clamped);
 		if (full) atomicAdd(&out->full, (unsigned long long)full);
@@ -169,8 +133,8 @@ __global__ __launch_bounds__(256) void k_simp_reps(const SimpSlot *__restrict__ 
 	uint32_t n = 0u, maxc = 0u;
 	for (uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x; v < nV; v += (uint64_t)gridDim.x * 256u) {
 		const uint32_t s = slotof[v];
-		uint32_t r = SIMP_NONE;
-		if (s != SIMP_NONE) {
+		uint32_t r = MESH_NONE;
+		if (s != MESH_NONE) {
 			r = slots[s].rep;
 			if (r == (uint32_t)v) {
 				const uint32_t c = slots[s].cnt;
@@ -193,7 +157,7 @@ __device__ __forceinline__ uint32_t simp_image(const uint32_t *__restrict__ T, u
 	const uint32_t t0 = t[0], t1 = t[1], t2 = t[2];
 	if (t0 >= nV || t1 >= nV || t2 >= nV) return 0u;  // (tested before anything is gathered through it)
 	r[0] = rep[t0]; r[1] = rep[t1]; r[2] = rep[t2];
-	if (r[0] == SIMP_NONE || r[1] == SIMP_NONE || r[2] == SIMP_NONE) return 0u;
+	if (r[0] == MESH_NONE || r[1] == MESH_NONE || r[2] == MESH_NONE) return 0u;
 	if (r[0] == r[1] || r[1] == r[2] || r[2] == r[0]) return 1u;
 	uint32_t a = r[0], b = r[1], c = r[2], x;
 	if (a > b) { x = a; a = b; b = x; }
@@ -203,7 +167,7 @@ __device__ __forceinline__ uint32_t simp_image(const uint32_t *__restrict__ T, u
 	return 2u;
 }
 __device__ __forceinline__ uint64_t simp_image_home(const uint32_t s[3]) {
-	return topo_mix(topo_mix(((uint64_t)s[0] << 32) | s[1]) + s[2]);
+	return mesh_mix(mesh_mix(((uint64_t)s[0] << 32) | s[1]) + s[2]);
 }
 
 // Duplicate removal, first half.  A word of the table names a triangle; the word's key is that triangle's sorted image, read
@@ -218,8 +182,8 @@ __global__ __launch_bounds__(256) void k_simp_tri_insert(const uint32_t *__restr
 		uint64_t h = simp_image_home(s) & mask;
 		bool placed = false;
 		for (uint64_t tries = 0; tries <= mask; tries++, h = (h + 1u) & mask) {
-			const uint32_t old = atomicCAS(&tab[h], SIMP_NONE, (uint32_t)i);
-			if (old == SIMP_NONE) { placed = true; break; }
+			const uint32_t old = atomicCAS(&tab[h], MESH_NONE, (uint32_t)i);
+			if (old == MESH_NONE) { placed = true; break; }
 			if (simp_image(T, old, nV, rep, rj, sj) == 2u && sj[0] == s[0] && sj[1] == s[1] && sj[2] == s[2]) {
 				atomicMin(&tab[h], (uint32_t)i);
 				placed = true;
@@ -248,7 +212,7 @@ __global__ __launch_bounds__(256) void k_simp_tri_keep(const uint32_t *__restric
 			bool found = false;
 			for (uint64_t tries = 0; tries <= mask; tries++, h = (h + 1u) & mask) {
 				const uint32_t j = tab[h];
-				if (j == SIMP_NONE) break;  // (the insertion found no slot: counted there)
+				if (j == MESH_NONE) break;  // (the insertion found no slot: counted there)
 				if (j == (uint32_t)i) { found = true; break; }
 				if (simp_image(T, j, nV, rep, rj, sj) == 2u && sj[0] == s[0] && sj[1] == s[1] && sj[2] == s[2]) { found = true; alive = 0u; dup++; break; }
 			}
@@ -257,26 +221,14 @@ __global__ __launch_bounds__(256) void k_simp_tri_keep(const uint32_t *__restric
 		surv[i] = (uint8_t)alive;
 		if (alive) { keep[r[0]] = 1; keep[r[1]] = 1; keep[r[2]] = 1; }
 	}
-	collapsed = topo_block_sum(collapsed, sh);
-	dup = topo_block_sum(dup, sh);
-	full = topo_block_sum(full, sh);
+	collapsed = block_sum_u32_256(collapsed, sh);
+	dup = block_sum_u32_256(dup, sh);
+	full = block_sum_u32_256(full, sh);
 	if (threadIdx.x == 0u) {
 		if (collapsed) atomicAdd(&out->collapsed, (unsigned long long)collapsed);
 		if (dup) atomicAdd(&out->duplicates, (unsigned long long)dup);
 		if (full) atomicAdd(&out->full, (unsigned long long)full);
 	}
-}
-
-// the flags of a tile of CC_TILE elements, 4 per lane, counted
-__global__ __launch_bounds__(256) void k_simp_tile_count(const uint8_t *__restrict__ flag, uint64_t n, uint32_t *__restrict__ bsum) {
-	__shared__ uint32_t sh[4];
-	const uint64_t e0 = (uint64_t)blockIdx.x * CC_TILE + threadIdx.x * 4u;
-	uint32_t own = 0u;
-#pragma unroll
-	for (uint32_t k = 0; k < 4u; k++)
-		if (e0 + k < n) own += flag[e0 + k] ? 1u : 0u;
-	const uint32_t tot = block_sum_u32_256(own, sh);
-	if (threadIdx.x == 0u) bsum[blockIdx.x] = tot;
 }
 
 // the survivors of a tile, renumbered, at the tile's place in oT
@@ -285,15 +237,10 @@ __global__ __launch_bounds__(256) void k_simp_tris(const uint32_t *__restrict__ 
                                                    uint64_t capT, uint32_t *__restrict__ oT) {
 	__shared__ uint32_t sh[256];
 	if (out->nV_out > capV || out->nT_out > capT) return;  // (block-uniform: the caller's arrays are too small, nothing is written)
-	const uint64_t i0 = (uint64_t)blockIdx.x * CC_TILE + threadIdx.x * 4u;
-	uint32_t f[4], own = 0u;
-#pragma unroll
-	for (uint32_t k = 0; k < 4u; k++) {
-		f[k] = i0 + k < nT && surv[i0 + k] ? 1u : 0u;
-		own += f[k];
-	}
-	uint32_t tot;
-	uint64_t r = (uint64_t)bsum[blockIdx.x] + block_excl_scan_256(own, sh, &tot);
+	const uint64_t i0 = mesh_tile_e0();
+	uint32_t f[4];
+	const uint32_t own = mesh_tile_load<MeshFlag>(surv, nT, f);
+	uint64_t r = mesh_tile_place(bsum, own, sh);
 #pragma unroll
 	for (uint32_t k = 0; k < 4u; k++) {
 		if (f[k]) {
@@ -317,9 +264,9 @@ __global__ __launch_bounds__(256) void k_simp_rows(const R *__restrict__ V, cons
 	if (out->nV_out > capV || out->nT_out > capT) return;
 	for (uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x; v < nV; v += (uint64_t)gridDim.x * 256u) {
 		const uint32_t r = rep[v];
-		const uint32_t m = r != SIMP_NONE ? map[r] : FILT_NONE;
+		const uint32_t m = r != MESH_NONE ? map[r] : MESH_NONE;
 		if (oMap) oMap[v] = m;
-		if (m == FILT_NONE || r != (uint32_t)v) continue;
+		if (m == MESH_NONE || r != (uint32_t)v) continue;
 		R *oq = oV + (uint64_t)m * 3u;
 		if (mean) {
 			const SimpSlot *s = slots + slotof[v];
@@ -332,9 +279,7 @@ __global__ __launch_bounds__(256) void k_simp_rows(const R *__restrict__ V, cons
 				oq[a] = (R)(L.origin[a] + L.cell[a] * (k + mm));
 			}
 		} else {
-			const R *q = V + v * 3u;
-			const R q0 = q[0], q1 = q[1], q2 = q[2];
-			oq[0] = q0; oq[1] = q1; oq[2] = q2;
+			mesh_copy_row(V, (const float *)nullptr, v, oV, (float *)nullptr, m);
 		}
 		if (A0) oA0[m] = A0[v];
 		if (A1) oA1[m] = A1[v];
@@ -343,33 +288,13 @@ __global__ __launch_bounds__(256) void k_simp_rows(const R *__restrict__ V, cons
 
 // --- host side ----------------------------------------------------------------------------------------------------------
 
-static void simp_destroy(MeasureState *m) {
-	SimpState *s = m->simp;
-	if (!s) return;
-	dev_release(&s->d_out); dev_release(&s->d_ref); dev_release(&s->d_slot); dev_release(&s->d_rep); dev_release(&s->d_keep); dev_release(&s->d_map);
-	dev_release(&s->d_surv); dev_release(&s->d_bsum); dev_release(&s->d_slots); dev_release(&s->d_tri);
-	if (s->h_out) (void)hipHostFree(s->h_out);
-	free(s);
-	m->simp = nullptr;
+static void simp_release(void *state) {
+	SimpState *s = (SimpState *)state;
+	dev_release(&s->d_ref); dev_release(&s->d_slot); dev_release(&s->d_rep); dev_release(&s->d_surv); dev_release(&s->d_slots); dev_release(&s->d_tri);
 }
-
-static int simp_state(mc33hip_ctx *c) {
-	int rc = meas_state(c);
-	if (rc) return rc;
-	SimpState *s = c->meas->simp;
-	if (!s) {
-		if (!(s = (SimpState *)calloc(1, sizeof *s))) return MC33HIP_ENOMEM;
-		c->meas->simp = s;  // (what it holds so far goes with the context)
-	}
-	if (!s->d_out) HIP_TRY(hipMalloc(&s->d_out, sizeof(SimpOut)));
-	if (!s->h_out) HIP_TRY(hipHostMalloc(&s->h_out, sizeof(SimpOut), hipHostMallocDefault));
-	return 0;
-}
-
-static uint64_t simp_table_size(uint64_t n) {  // a power of two >= 2 n, at most 2^32 (> n all the same: slot numbers are 32-bit words)
-	uint64_t s = 256u;
-	while (s < 2u * n && s < (1ull << 32)) s <<= 1;
-	return s;
+static int simp_state(mc33hip_ctx *c, SimpState **s) {
+	const int rc = meas_state(c);
+	return rc ? rc : mesh_op_state(&c->meas->mesh, simp_release, s);
 }
 
 static void simp_fill(mc33hip_simplification *a, const SimpOut &h) {
@@ -381,51 +306,39 @@ extern "C" int mc33hip_simplify_surface(mc33hip_ctx *c, mc33hip_simplification *
 	if (!c || !a) return MC33HIP_EINVAL;
 	a->nV_out = a->nT_out = a->clusters = a->max_cluster = a->collapsed_triangles = a->duplicate_triangles = a->invalid_triangles = a->clamped_vertices = 0;
 	const unsigned long long nV = a->nV, nT = a->nT;
-	if (a->n_attr > 2u) { set_err("at most two attribute arrays, not %u", a->n_attr); return MC33HIP_EINVAL; }
-	if (!meas_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
+	if (!mesh_counts_ok(a->n_attr, nV, nT)) return MC33HIP_EINVAL;
 	if (a->mode != MC33HIP_SIMPLIFY_MEAN && a->mode != MC33HIP_SIMPLIFY_FIRST) { set_err("mode %d is neither MC33HIP_SIMPLIFY_MEAN nor MC33HIP_SIMPLIFY_FIRST", a->mode); return MC33HIP_EINVAL; }
 	for (int k = 0; k < 3; k++) {
 		if (!(a->cell[k] > 0.0 && a->cell[k] < __builtin_huge_val())) { set_err("cell[%d] must be finite and > 0", k); return MC33HIP_EINVAL; }
 		if (!(a->origin[k] > -__builtin_huge_val() && a->origin[k] < __builtin_huge_val())) { set_err("origin[%d] must be finite", k); return MC33HIP_EINVAL; }
 	}
-	const uint64_t capV = std::min<unsigned long long>(a->capV, 0xFFFFFFFFull), capT = std::min<unsigned long long>(a->capT, 0xFFFFFFFFull);
-	bool null = (nV && !a->V) || (nT && !a->T) || (capV && !a->oV) || (capT && !a->oT);
-	for (unsigned k = 0; k < a->n_attr; k++) null = null || (nV && !a->attr[k]) || (capV && !a->oAttr[k]);
-	if (null) { set_err("a null pointer where the size is not zero"); return MC33HIP_EINVAL; }
+	const uint64_t capV = mesh_cap(a->capV), capT = mesh_cap(a->capT);
+	if (!mesh_pointers_ok((nV && !a->V) || (nT && !a->T) || (capV && !a->oV) || (capT && !a->oT), a->n_attr, a->attr, a->oAttr, nV, capV)) return MC33HIP_EINVAL;
 	// the call is not in place: no output may share a byte with an input or with another output
-	const void *in[4] = {a->V, a->T, a->n_attr > 0u ? a->attr[0] : nullptr, a->n_attr > 1u ? a->attr[1] : nullptr};
-	const uint64_t in_bytes[4] = {nV * 3u * sizeof(real_t), nT * 12u, nV * 4u, nV * 4u};
-	const void *outp[6] = {a->oV, a->oT, a->oN, a->oMap, a->n_attr > 0u ? a->oAttr[0] : nullptr, a->n_attr > 1u ? a->oAttr[1] : nullptr};
-	const uint64_t out_bytes[6] = {capV * 3u * sizeof(real_t), capT * 12u, capV * 12u, nV * 4u, capV * 4u, capV * 4u};
-	for (int o = 0; o < 6; o++) {
-		for (int i = 0; i < 4; i++)
-			if (filt_ranges_meet(in[i], in_bytes[i], outp[o], out_bytes[o])) { set_err("an output array overlaps an input array: the simplification is not in place"); return MC33HIP_EINVAL; }
-		for (int p = o + 1; p < 6; p++)
-			if (filt_ranges_meet(outp[p], out_bytes[p], outp[o], out_bytes[o])) { set_err("two output arrays overlap"); return MC33HIP_EINVAL; }
-	}
+	const MeshRange in[4] = {{a->V, nV * 3u * sizeof(real_t)}, {a->T, nT * 12u}, {a->n_attr > 0u ? a->attr[0] : nullptr, nV * 4u}, {a->n_attr > 1u ? a->attr[1] : nullptr, nV * 4u}};
+	const MeshRange out[6] = {{a->oV, capV * 3u * sizeof(real_t)}, {a->oT, capT * 12u}, {a->oN, capV * 12u}, {a->oMap, nV * 4u}, {a->n_attr > 0u ? a->oAttr[0] : nullptr, capV * 4u},
+	                          {a->n_attr > 1u ? a->oAttr[1] : nullptr, capV * 4u}};
+	if (!mesh_ranges_ok(in, 4, out, 6, true, "simplification")) return MC33HIP_EINVAL;
 	int rc = use_device(c);
 	if (rc) return rc;
-	if ((rc = simp_state(c))) return rc;
-	SimpState *s = c->meas->simp;
-	if (!nT || !nV) {  // no valid triangle: nothing is referenced, every count is 0 (nV == 0: every triangle is invalid)
-		if (nV && a->oMap) HIP_TRY(hipMemsetAsync(a->oMap, 0xFF, nV * 4u, c->stream));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		if ((rc = prop_check(c))) return rc;
+	SimpState *s;
+	if ((rc = simp_state(c, &s))) return rc;
+	if (!nT || !nV) {  // every count is 0
+		if ((rc = mesh_empty(c, a->oMap, nV))) return rc;
 		a->invalid_triangles = nT;
-		return meas_bad(nT, nV);
+		return mesh_bad(nT, nV);
 	}
-	const uint64_t tilesV = (nV + CC_TILE - 1u) / CC_TILE, tilesT = (nT + CC_TILE - 1u) / CC_TILE;
-	const uint64_t nslots = simp_table_size(nV), ntri = a->drop_duplicates ? simp_table_size(nT) : 0u;
+	MeshHost &h = c->meas->mesh;
+	const uint64_t tilesV = (nV + MESH_TILE - 1u) / MESH_TILE, tilesT = (nT + MESH_TILE - 1u) / MESH_TILE;
+	const uint64_t nslots = mesh_table_size(nV, 2u, 1ull << 32), ntri = a->drop_duplicates ? mesh_table_size(nT, 2u, 1ull << 32) : 0u;  // (slot numbers are 32-bit words)
+	if ((rc = meas_scratch(c, nV, tilesV + tilesT))) return rc;
 	if ((rc = meas_room(&s->d_ref, &s->ref_cap, nV))) return rc;
 	if ((rc = meas_room(&s->d_slot, &s->slot_cap, nV))) return rc;
 	if ((rc = meas_room(&s->d_rep, &s->rep_cap, nV))) return rc;
-	if ((rc = meas_room(&s->d_keep, &s->keep_cap, nV))) return rc;
-	if ((rc = meas_room(&s->d_map, &s->map_cap, nV))) return rc;
 	if ((rc = meas_room(&s->d_surv, &s->surv_cap, nT))) return rc;
-	if ((rc = meas_room(&s->d_bsum, &s->bsum_cap, tilesV + tilesT))) return rc;
 	if ((s->slots_cap < nslots || !s->d_slots) && (rc = dev_room("cluster table", &s->d_slots, &s->slots_cap, nslots))) return rc;  // (powers of two as they are: no slack)
 	if (ntri && (s->tri_cap < ntri || !s->d_tri) && (rc = dev_room("image table", &s->d_tri, &s->tri_cap, ntri))) return rc;
-	uint32_t *bsumV = s->d_bsum, *bsumT = s->d_bsum + tilesV;
+	uint32_t *bsumV = h.d_bsum, *bsumT = h.d_bsum + tilesV;
 	const real_t *V = (const real_t *)a->V;
 	const uint32_t *T = (const uint32_t *)a->T;
 	const uint32_t mean = a->mode == MC33HIP_SIMPLIFY_MEAN ? 1u : 0u, drop = a->drop_duplicates ? 1u : 0u;
@@ -436,49 +349,31 @@ extern "C" int mc33hip_simplify_surface(mc33hip_ctx *c, mc33hip_simplification *
 	const uint64_t chunkC = ((nV + gridC - 1u) / gridC + 255u) / 256u * 256u;
 	HIP_TRY(hipMemsetAsync(s->d_out, 0, sizeof(SimpOut), c->stream));
 	HIP_TRY(hipMemsetAsync(s->d_ref, 0, nV, c->stream));
-	HIP_TRY(hipMemsetAsync(s->d_keep, 0, nV, c->stream));
+	HIP_TRY(hipMemsetAsync(h.d_keep, 0, nV, c->stream));
 	if (ntri) HIP_TRY(hipMemsetAsync(s->d_tri, 0xFF, ntri * sizeof(uint32_t), c->stream));
 	hipLaunchKernelGGL(k_simp_clear, dim3(meas_grid(c, nslots, 16u)), dim3(256), 0, c->stream, s->d_slots, nslots);
-	hipLaunchKernelGGL(k_simp_ref, dim3(gridT), dim3(256), 0, c->stream, T, (uint64_t)nT, (uint64_t)nV, s->d_ref, s->d_out);
+	hipLaunchKernelGGL(k_mesh_ref, dim3(gridT), dim3(256), 0, c->stream, T, (uint64_t)nT, (uint64_t)nV, s->d_ref, &s->d_out->bad);
 	hipLaunchKernelGGL((k_simp_cluster<real_t>), dim3(gridC), dim3(256), 0, c->stream, V, s->d_ref, (uint64_t)nV, chunkC, L, mean, s->d_slots, nslots - 1u, s->d_slot,
 	                   s->d_out);
 	hipLaunchKernelGGL(k_simp_reps, dim3(gridV), dim3(256), 0, c->stream, s->d_slots, s->d_slot, (uint64_t)nV, s->d_rep, s->d_out);
 	if (drop) hipLaunchKernelGGL(k_simp_tri_insert, dim3(gridT), dim3(256), 0, c->stream, T, (uint64_t)nT, (uint64_t)nV, s->d_rep, s->d_tri, ntri - 1u, s->d_out);
 	hipLaunchKernelGGL(k_simp_tri_keep, dim3(gridT), dim3(256), 0, c->stream, T, (uint64_t)nT, (uint64_t)nV, s->d_rep, s->d_tri, ntri ? ntri - 1u : 0u, drop, s->d_surv,
-	                   s->d_keep, s->d_out);
-	hipLaunchKernelGGL(k_simp_tile_count, dim3((uint32_t)tilesV), dim3(256), 0, c->stream, s->d_keep, (uint64_t)nV, bsumV);
-	hipLaunchKernelGGL(k_filt_scan_top, dim3(1), dim3(256), 0, c->stream, bsumV, tilesV, &s->d_out->nV_out);
-	hipLaunchKernelGGL(k_filt_new, dim3((uint32_t)tilesV), dim3(256), 0, c->stream, s->d_keep, bsumV, (uint64_t)nV, s->d_map);
-	hipLaunchKernelGGL(k_simp_tile_count, dim3((uint32_t)tilesT), dim3(256), 0, c->stream, s->d_surv, (uint64_t)nT, bsumT);
-	hipLaunchKernelGGL(k_filt_scan_top, dim3(1), dim3(256), 0, c->stream, bsumT, tilesT, &s->d_out->nT_out);
+	                   h.d_keep, s->d_out);
+	mesh_scan<MeshFlag, MESH_NEW>(c, h.d_keep, nV, bsumV, &s->d_out->nV_out, h.d_map);
+	mesh_scan<MeshFlag>(c, s->d_surv, nT, bsumT, &s->d_out->nT_out);  // (k_simp_tris places)
 	// the copies: they compare the totals with the capacities on the device, so that the host waits once before the normals
 	hipLaunchKernelGGL((k_simp_rows<real_t>), dim3(gridV), dim3(256), 0, c->stream, V, (const uint32_t *)(a->n_attr > 0u ? a->attr[0] : nullptr),
-	                   (const uint32_t *)(a->n_attr > 1u ? a->attr[1] : nullptr), s->d_rep, s->d_slot, s->d_slots, s->d_map, (uint64_t)nV, L, mean, s->d_out, capV, capT,
+	                   (const uint32_t *)(a->n_attr > 1u ? a->attr[1] : nullptr), s->d_rep, s->d_slot, s->d_slots, h.d_map, (uint64_t)nV, L, mean, s->d_out, capV, capT,
 	                   (real_t *)a->oV, (uint32_t *)(a->n_attr > 0u ? a->oAttr[0] : nullptr), (uint32_t *)(a->n_attr > 1u ? a->oAttr[1] : nullptr), (uint32_t *)a->oMap);
-	hipLaunchKernelGGL(k_simp_tris, dim3((uint32_t)tilesT), dim3(256), 0, c->stream, T, (uint64_t)nT, s->d_rep, s->d_surv, s->d_map, bsumT, s->d_out, capV, capT,
+	hipLaunchKernelGGL(k_simp_tris, dim3((uint32_t)tilesT), dim3(256), 0, c->stream, T, (uint64_t)nT, s->d_rep, s->d_surv, h.d_map, bsumT, s->d_out, capV, capT,
 	                   (uint32_t *)a->oT);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, sizeof(SimpOut), hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	if ((rc = prop_check(c))) return rc;
-	const SimpOut h = *s->h_out;
-	simp_fill(a, h);
-	if (h.full) { set_err("%llu keys or images found no slot in the tables", h.full); return MC33HIP_ERUNTIME; }
-	if (h.nV_out > capV || h.nT_out > capT) {
-		set_err("the simplified mesh needs %llu rows of V and %llu of T, the caller's arrays have %llu and %llu", h.nV_out, h.nT_out, (unsigned long long)capV,
-		        (unsigned long long)capT);
-		return MC33HIP_ECAPACITY;
-	}
-	// the normals of the output, by the passes of mc33hip_vertex_normals (oT names no vertex outside oV)
-	if (a->oN && h.nV_out) {
-		if ((rc = smooth_state(c))) return rc;
-		SmoothState *sm = c->meas->smooth;
-		sm->timers.adjacency = sm->timers.normals = false;
-		sm->timers.passes = 0u;
-		if ((rc = sm_room(c, h.nV_out, h.nT_out, false, 0u))) return rc;
-		HIP_TRY(hipMemsetAsync(sm->d_out, 0, sizeof(SmOut), c->stream));
-		if ((rc = sm_normals(c, (const real_t *)a->oV, (const uint32_t *)a->oT, h.nT_out, h.nV_out, a->oN, false))) return rc;
-		if ((rc = sm_fetch(c))) return rc;
-	}
-	return meas_bad(h.bad, nV);
+	if ((rc = mesh_op_fetch(c, s))) return rc;
+	const SimpOut o = *s->h_out;
+	simp_fill(a, o);
+	if (o.full) { set_err("%llu keys or images found no slot in the tables", o.full); return MC33HIP_ERUNTIME; }
+	if ((rc = mesh_capacity("simplified", o.nV_out, o.nT_out, capV, capT))) return rc;
+	// The normals of the output.  Every kernel of this call has run: of the shared scratch its map and keep are dead, and the tile
+	// sums - all the normals overwrite - have been read for the last time.
+	if (a->oN && o.nV_out && (rc = sm_normals_call(c, (const real_t *)a->oV, (const uint32_t *)a->oT, o.nT_out, o.nV_out, a->oN, nullptr))) return rc;
+	return mesh_bad(o.bad, nV);
 }

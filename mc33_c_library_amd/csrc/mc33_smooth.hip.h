@@ -1,4 +1,4 @@
-// mc33_smooth.hip.h -- part of the ONE translation unit mc33_kernels.hip (included there, last; not a header to include elsewhere):
+// mc33_smooth.hip.h -- part of the ONE translation unit mc33_kernels.hip (builds on mc33_mesh.hip.h; not a header to include elsewhere):
 // Taubin's lambda | mu smoothing of a FINISHED mesh in device memory and vertex normals recomputed from its triangles
 // (include/mc33_hip.h: mc33hip_smooth_surface, mc33hip_vertex_normals).  DESIGN.md 13.
 //
@@ -13,7 +13,7 @@
 //                    that order, starting from the first; oN[v] = (float)(n / sqrt((n.x*n.x + n.y*n.y) + n.z*n.z)) where that
 //                    length is > 0 and finite, else (0, 0, 0)
 // The passes: both lists are CSR arrays made straight from T - k_sm_count adds 2 directed entries per side (1 per distinct corner
-// for the incidence list) with integer atomics, k_sm_tile_sum / k_filt_scan_top / k_sm_starts turn the counts into row starts,
+// for the incidence list) with integer atomics, the tile scan of mc33_mesh.hip.h turns the counts into row starts,
 // k_sm_fill places the entries through an atomic cursor.  The order inside a row depends on scheduling until a LATER kernel - one
 // lane per row - has sorted it: k_sm_rows sorts, collapses equal neighbours (a neighbour that stood once in the row is an edge with
 // one use: boundary) and leaves deg and the fixed flag; k_sm_normals sorts its row of triangles before it adds.  Nothing a block
@@ -33,7 +33,7 @@ struct SmoothTimers {       // a measurement aid (tools/time_smooth.py), not par
 	uint32_t passes;
 };
 
-struct SmoothState {        // scratch of these passes: on the MeasureState from the first call on, grown on demand, freed with it
+struct SmoothState {        // scratch of these passes besides the shared tile sums: on the MeasureState from the first call on, grown on demand, freed with it
 	SmOut *d_out, *h_out;
 	uint32_t *d_start;      // [nV + 1] counts, then row starts
 	uint64_t start_cap;
@@ -43,8 +43,6 @@ struct SmoothState {        // scratch of these passes: on the MeasureState from
 	uint64_t ent_cap;
 	uint8_t *d_fixed;       // [nV]
 	uint64_t fixed_cap;
-	uint32_t *d_bsum;       // entries per tile of 1024 vertices, scanned in place
-	uint64_t bsum_cap;
 	void *d_tmp;            // [nV x 3 MC33_real] the other side of the ping-pong
 	uint64_t tmp_cap;       // in bytes
 	SmoothTimers timers;
@@ -73,37 +71,6 @@ __global__ __launch_bounds__(256) void k_sm_count(const uint32_t *__restrict__ T
 		}
 	}
 	if (bad && bad_out) atomicAdd(bad_out, (unsigned long long)bad);
-}
-
-__global__ __launch_bounds__(256) void k_sm_tile_sum(const uint32_t *__restrict__ cnt, uint64_t nV, uint32_t *__restrict__ bsum) {
-	__shared__ uint32_t sh[4];
-	const uint64_t v0 = (uint64_t)blockIdx.x * CC_TILE + threadIdx.x * 4u;
-	uint32_t n = 0u;
-#pragma unroll
-	for (uint32_t k = 0; k < 4u; k++)
-		if (v0 + k < nV) n += cnt[v0 + k];
-	const uint32_t tot = block_sum_u32_256(n, sh);
-	if (threadIdx.x == 0u) bsum[blockIdx.x] = tot;
-}
-
-// counts -> row starts, in place (a lane reads its four counts before it writes over them); start[nV] = the total
-__global__ __launch_bounds__(256) void k_sm_starts(uint32_t *__restrict__ start, const uint32_t *__restrict__ bsum, uint64_t nV) {
-	__shared__ uint32_t sh[256];
-	const uint64_t v0 = (uint64_t)blockIdx.x * CC_TILE + threadIdx.x * 4u;
-	uint32_t f[4], own = 0u;
-#pragma unroll
-	for (uint32_t k = 0; k < 4u; k++) {
-		f[k] = v0 + k < nV ? start[v0 + k] : 0u;
-		own += f[k];
-	}
-	uint32_t tot;
-	uint32_t r = bsum[blockIdx.x] + block_excl_scan_256(own, sh, &tot);
-#pragma unroll
-	for (uint32_t k = 0; k < 4u; k++) {
-		if (v0 + k < nV) start[v0 + k] = r;
-		r += f[k];
-		if (v0 + k + 1u == nV) start[nV] = r;
-	}
 }
 
 __device__ __forceinline__ void sm_put(const uint32_t *__restrict__ start, uint32_t *__restrict__ cur, uint32_t *__restrict__ ent, uint32_t row, uint32_t what) {
@@ -169,17 +136,6 @@ __device__ __forceinline__ void sm_sort_row(uint32_t *r, uint32_t n) {
 		r[m] = top;
 		sm_sift(r, 0u, m);
 	}
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x) {
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d, 64);
-	return x;  // (lane 0)
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_down(x, d, 64); x = o > x ? o : x; }
-	return x;
 }
 
 // a lane per row of the adjacency: sort, collapse, deg (over the cursor), fixed, and the call's three counts of vertices
@@ -279,34 +235,24 @@ __global__ __launch_bounds__(256) void k_sm_normals(const R *__restrict__ Q, con
 
 // --- host side ----------------------------------------------------------------------------------------------------------
 
-static void smooth_destroy(MeasureState *m) {
-	SmoothState *s = m->smooth;
-	if (!s) return;
-	dev_release(&s->d_out); dev_release(&s->d_start); dev_release(&s->d_deg); dev_release(&s->d_ent); dev_release(&s->d_fixed); dev_release(&s->d_bsum);
-	dev_release(&s->d_tmp);
-	if (s->h_out) (void)hipHostFree(s->h_out);
+static void smooth_release(void *state) {
+	SmoothState *s = (SmoothState *)state;
+	dev_release(&s->d_start); dev_release(&s->d_deg); dev_release(&s->d_ent); dev_release(&s->d_fixed); dev_release(&s->d_tmp);
 	if (s->timers.made)
 		for (hipEvent_t &e : s->timers.ev) (void)hipEventDestroy(e);
-	free(s);
-	m->smooth = nullptr;
 }
-
-static int smooth_state(mc33hip_ctx *c) {
+// the state, with no timing taken yet by this call
+static int smooth_state(mc33hip_ctx *c, SmoothState **s) {
 	int rc = meas_state(c);
-	if (rc) return rc;
-	SmoothState *s = c->meas->smooth;
-	if (!s) {
-		if (!(s = (SmoothState *)calloc(1, sizeof *s))) return MC33HIP_ENOMEM;
-		c->meas->smooth = s;  // (what it holds so far goes with the context)
-	}
-	if (!s->d_out) HIP_TRY(hipMalloc(&s->d_out, sizeof(SmOut)));
-	if (!s->h_out) HIP_TRY(hipHostMalloc(&s->h_out, sizeof(SmOut), hipHostMallocDefault));
+	if (rc || (rc = mesh_op_state(&c->meas->mesh, smooth_release, s))) return rc;
+	(*s)->timers.adjacency = (*s)->timers.normals = false;
+	(*s)->timers.passes = 0u;
 	return 0;
 }
 
 // the events of mc33hip_smooth_timing: recorded only at timing level 2 (mc33hip_set_timing), never waited for by the call itself
-static int sm_mark(mc33hip_ctx *c, uint32_t k) {
-	SmoothTimers &t = c->meas->smooth->timers;
+static int sm_mark(mc33hip_ctx *c, SmoothState *s, uint32_t k) {
+	SmoothTimers &t = s->timers;
 	if (c->timing_level < 2 || k >= SM_TIMED_PASSES + 4u) return 0;
 	if (!t.made) {
 		for (hipEvent_t &e : t.ev) HIP_TRY(hipEventCreate(&e));
@@ -318,23 +264,18 @@ static int sm_mark(mc33hip_ctx *c, uint32_t k) {
 
 // the CSR list of T in d_start / d_deg (the cursor) / d_ent: enqueues
 template <int INC>
-static int sm_build_list(mc33hip_ctx *c, const uint32_t *T, uint64_t nT, uint64_t nV, bool count_bad) {
-	SmoothState *s = c->meas->smooth;
-	const uint64_t tiles = (nV + CC_TILE - 1u) / CC_TILE;
+static int sm_build_list(mc33hip_ctx *c, SmoothState *s, const uint32_t *T, uint64_t nT, uint64_t nV, bool count_bad) {
 	const uint32_t gridT = meas_grid(c, nT, 16u);
 	HIP_TRY(hipMemsetAsync(s->d_start, 0, (nV + 1u) * sizeof(uint32_t), c->stream));
 	HIP_TRY(hipMemsetAsync(s->d_deg, 0, nV * sizeof(uint32_t), c->stream));
 	hipLaunchKernelGGL((k_sm_count<INC>), dim3(gridT), dim3(256), 0, c->stream, T, nT, nV, s->d_start, count_bad ? &s->d_out->bad : (unsigned long long *)nullptr);
-	hipLaunchKernelGGL(k_sm_tile_sum, dim3((uint32_t)tiles), dim3(256), 0, c->stream, s->d_start, nV, s->d_bsum);
-	hipLaunchKernelGGL(k_filt_scan_top, dim3(1), dim3(256), 0, c->stream, s->d_bsum, tiles, &s->d_out->entries);
-	hipLaunchKernelGGL(k_sm_starts, dim3((uint32_t)tiles), dim3(256), 0, c->stream, s->d_start, s->d_bsum, nV);
+	mesh_scan<MeshCount, MESH_STARTS>(c, s->d_start, nV, c->meas->mesh.d_bsum, &s->d_out->entries, s->d_start);  // (in place: counts -> row starts, start[nV] = the total)
 	hipLaunchKernelGGL((k_sm_fill<INC>), dim3(gridT), dim3(256), 0, c->stream, T, nT, nV, s->d_start, s->d_deg, s->d_ent);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
 
-static int sm_room(mc33hip_ctx *c, uint64_t nV, uint64_t nT, bool adjacency, uint64_t tmp_bytes) {
-	SmoothState *s = c->meas->smooth;
+static int sm_room(mc33hip_ctx *c, SmoothState *s, uint64_t nV, uint64_t nT, bool adjacency, uint64_t tmp_bytes) {
 	int rc;
 	// (row starts are 32-bit words)
 	if ((adjacency ? 6u : 3u) * nT > 0xFFFFFFFFull) { set_err("the lists of %llu triangles need more than 2^32-1 entries", (unsigned long long)nT); return MC33HIP_ENOMEM; }
@@ -342,7 +283,7 @@ static int sm_room(mc33hip_ctx *c, uint64_t nV, uint64_t nT, bool adjacency, uin
 	if ((rc = meas_room(&s->d_deg, &s->deg_cap, nV))) return rc;
 	if ((rc = meas_room(&s->d_ent, &s->ent_cap, (adjacency ? 6u : 3u) * nT))) return rc;
 	if ((rc = meas_room(&s->d_fixed, &s->fixed_cap, nV))) return rc;
-	if ((rc = meas_room(&s->d_bsum, &s->bsum_cap, (nV + CC_TILE - 1u) / CC_TILE))) return rc;
+	if ((rc = meas_room(&c->meas->mesh.d_bsum, &c->meas->mesh.bsum_cap, (nV + MESH_TILE - 1u) / MESH_TILE))) return rc;  // (of the shared scratch only the tile sums)
 	if (tmp_bytes > s->tmp_cap || !s->d_tmp) {
 		dev_release(&s->d_tmp);
 		s->tmp_cap = 0;
@@ -353,47 +294,51 @@ static int sm_room(mc33hip_ctx *c, uint64_t nV, uint64_t nT, bool adjacency, uin
 	return 0;
 }
 
-static int sm_normals(mc33hip_ctx *c, const real_t *Q, const uint32_t *T, uint64_t nT, uint64_t nV, float *oN, bool count_bad) {
-	SmoothState *s = c->meas->smooth;
+static int sm_normals(mc33hip_ctx *c, SmoothState *s, const real_t *Q, const uint32_t *T, uint64_t nT, uint64_t nV, float *oN, bool count_bad) {
 	int rc;
-	if ((rc = sm_mark(c, 2u))) return rc;
-	if ((rc = sm_build_list<1>(c, T, nT, nV, count_bad))) return rc;
+	if ((rc = sm_mark(c, s, 2u))) return rc;
+	if ((rc = sm_build_list<1>(c, s, T, nT, nV, count_bad))) return rc;
 	hipLaunchKernelGGL((k_sm_normals<real_t>), dim3(meas_grid(c, nV, 16u)), dim3(256), 0, c->stream, Q, T, s->d_start, s->d_ent, nV, oN);
 	HIP_TRY(hipGetLastError());
 	s->timers.normals = c->timing_level >= 2;
-	return sm_mark(c, 3u);
+	return sm_mark(c, s, 3u);
 }
 
-static int sm_fetch(mc33hip_ctx *c) {
-	SmoothState *s = c->meas->smooth;
-	HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, sizeof(SmOut), hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	return prop_check(c);
+// The normals of a mesh with nV, nT > 0, as mc33hip_vertex_normals takes them and as a part takes those of the mesh it has just
+// written (T names no vertex outside V then).  It overwrites the shared tile sums - nothing else of the shared scratch - behind
+// what the caller enqueued, and waits.
+static int sm_normals_call(mc33hip_ctx *c, const real_t *V, const uint32_t *T, uint64_t nT, uint64_t nV, float *oN, unsigned long long *bad) {
+	SmoothState *s;
+	int rc = smooth_state(c, &s);
+	if (rc || (rc = sm_room(c, s, nV, nT, false, 0u))) return rc;
+	HIP_TRY(hipMemsetAsync(s->d_out, 0, sizeof(SmOut), c->stream));
+	if ((rc = sm_normals(c, s, V, T, nT, nV, oN, bad != nullptr))) return rc;
+	if ((rc = mesh_op_fetch(c, s))) return rc;
+	if (bad) *bad = s->h_out->bad;
+	return 0;
 }
 
 extern "C" int mc33hip_smooth_surface(mc33hip_ctx *c, mc33hip_smoothing *a) {
 	if (!c || !a) return MC33HIP_EINVAL;
 	a->max_degree = a->isolated_vertices = a->boundary_vertices = a->invalid_triangles = 0;
 	const unsigned long long nV = a->nV, nT = a->nT;
-	if (!meas_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
+	if (!mesh_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
 	if ((nV && (!a->V || !a->oV)) || (nT && !a->T)) { set_err("a null pointer where the size is not zero"); return MC33HIP_EINVAL; }
 	if (!(a->lambda > 0.0 && a->lambda <= 1.0) || !(a->mu >= -1.0 && a->mu <= 0.0)) { set_err("lambda must lie in (0, 1] and mu in [-1, 0]"); return MC33HIP_EINVAL; }
 	if (a->iterations > 1000u) { set_err("at most 1000 iterations, not %u", a->iterations); return MC33HIP_EINVAL; }
 	const uint64_t vbytes = nV * 3u * sizeof(real_t), nbytes = nV * 12u, tbytes = nT * 12u;
-	if ((a->oV != a->V && filt_ranges_meet(a->oV, vbytes, a->V, vbytes)) || filt_ranges_meet(a->oV, vbytes, a->T, tbytes) || filt_ranges_meet(a->oN, nbytes, a->V, vbytes) ||
-	    filt_ranges_meet(a->oN, nbytes, a->T, tbytes) || filt_ranges_meet(a->oN, nbytes, a->oV, vbytes)) {
+	if ((a->oV != a->V && mesh_ranges_meet(a->oV, vbytes, a->V, vbytes)) || mesh_ranges_meet(a->oV, vbytes, a->T, tbytes) || mesh_ranges_meet(a->oN, nbytes, a->V, vbytes) ||
+	    mesh_ranges_meet(a->oN, nbytes, a->T, tbytes) || mesh_ranges_meet(a->oN, nbytes, a->oV, vbytes)) {
 		set_err("an output array overlaps another array of the call (oV may be exactly V, nothing else)");
 		return MC33HIP_EINVAL;
 	}
 	int rc = use_device(c);
 	if (rc) return rc;
-	if ((rc = smooth_state(c))) return rc;
-	SmoothState *s = c->meas->smooth;
+	SmoothState *s;
+	if ((rc = smooth_state(c, &s))) return rc;
 	const real_t *V = (const real_t *)a->V;
 	real_t *oV = (real_t *)a->oV;
 	const uint32_t *T = (const uint32_t *)a->T;
-	s->timers.adjacency = s->timers.normals = false;
-	s->timers.passes = 0u;
 	if (!nV || !nT) {  // nothing to build: every vertex is isolated, every triangle (of no vertices) invalid
 		if (nV && oV != V) HIP_TRY(hipMemcpyAsync(oV, V, vbytes, hipMemcpyDeviceToDevice, c->stream));
 		if (nV && a->oN) HIP_TRY(hipMemsetAsync(a->oN, 0, nbytes, c->stream));
@@ -401,17 +346,17 @@ extern "C" int mc33hip_smooth_surface(mc33hip_ctx *c, mc33hip_smoothing *a) {
 		if ((rc = prop_check(c))) return rc;
 		a->isolated_vertices = nV;
 		a->invalid_triangles = nT;
-		return meas_bad(nT, nV);
+		return mesh_bad(nT, nV);
 	}
 	const uint32_t passes = a->iterations * (a->mu != 0.0 ? 2u : 1u);
-	if ((rc = sm_room(c, nV, nT, true, passes ? vbytes : 0u))) return rc;
+	if ((rc = sm_room(c, s, nV, nT, true, passes ? vbytes : 0u))) return rc;
 	HIP_TRY(hipMemsetAsync(s->d_out, 0, sizeof(SmOut), c->stream));
-	if ((rc = sm_mark(c, 0u))) return rc;
-	if ((rc = sm_build_list<0>(c, T, nT, nV, true))) return rc;
+	if ((rc = sm_mark(c, s, 0u))) return rc;
+	if ((rc = sm_build_list<0>(c, s, T, nT, nV, true))) return rc;
 	const uint32_t gridV = meas_grid(c, nV, 16u);
 	hipLaunchKernelGGL(k_sm_rows, dim3(gridV), dim3(256), 0, c->stream, s->d_start, s->d_ent, s->d_deg, s->d_fixed, (uint64_t)nV, a->pin_boundary ? 1u : 0u, s->d_out);
 	HIP_TRY(hipGetLastError());
-	if ((rc = sm_mark(c, 1u))) return rc;
+	if ((rc = sm_mark(c, s, 1u))) return rc;
 	s->timers.adjacency = c->timing_level >= 2;
 	// The ping-pong: pass j writes oV when an even number of passes follows it, the scratch rows otherwise, so that the last pass
 	// lands in oV.  In place with an odd number of passes the first one would write the rows it gathers from: the passes then
@@ -425,43 +370,39 @@ extern "C" int mc33hip_smooth_surface(mc33hip_ctx *c, mc33hip_smoothing *a) {
 			real_t *dst = (((passes - 1u - j) & 1u) != 0u) != shifted ? tmp : oV;
 			hipLaunchKernelGGL((k_sm_pass<real_t>), dim3(gridV), dim3(256), 0, c->stream, src, dst, s->d_start, s->d_deg, s->d_ent, s->d_fixed, (uint64_t)nV,
 			                   half ? a->mu : a->lambda);
-			if ((rc = sm_mark(c, 4u + j))) return rc;
+			if ((rc = sm_mark(c, s, 4u + j))) return rc;
 			src = dst;
 		}
 	HIP_TRY(hipGetLastError());
 	s->timers.passes = c->timing_level >= 2 ? std::min(passes, SM_TIMED_PASSES) : 0u;
 	if (src != oV) HIP_TRY(hipMemcpyAsync(oV, src, vbytes, hipMemcpyDeviceToDevice, c->stream));  // (no pass at all, or the shifted ones)
-	if (a->oN && (rc = sm_normals(c, oV, T, nT, nV, a->oN, false))) return rc;
-	if ((rc = sm_fetch(c))) return rc;
+	if (a->oN && (rc = sm_normals(c, s, oV, T, nT, nV, a->oN, false))) return rc;
+	if ((rc = mesh_op_fetch(c, s))) return rc;
 	const SmOut &h = *s->h_out;
 	a->max_degree = h.max_degree; a->isolated_vertices = h.isolated; a->boundary_vertices = h.boundary; a->invalid_triangles = h.bad;
-	return meas_bad(h.bad, nV);
+	return mesh_bad(h.bad, nV);
 }
 
 extern "C" int mc33hip_vertex_normals(mc33hip_ctx *c, const void *dV, unsigned long long nV, const void *dT, unsigned long long nT, float *oN) {
-	if (!c || !meas_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
+	if (!c || !mesh_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
 	if ((nV && (!dV || !oN)) || (nT && !dT)) { set_err("a null pointer where the size is not zero"); return MC33HIP_EINVAL; }
-	if (filt_ranges_meet(oN, nV * 12u, dV, nV * 3u * sizeof(real_t)) || filt_ranges_meet(oN, nV * 12u, dT, nT * 12u)) {
+	if (mesh_ranges_meet(oN, nV * 12u, dV, nV * 3u * sizeof(real_t)) || mesh_ranges_meet(oN, nV * 12u, dT, nT * 12u)) {
 		set_err("oN overlaps an input array");
 		return MC33HIP_EINVAL;
 	}
 	int rc = use_device(c);
 	if (rc) return rc;
-	if ((rc = smooth_state(c))) return rc;
-	SmoothState *s = c->meas->smooth;
-	s->timers.adjacency = s->timers.normals = false;
-	s->timers.passes = 0u;
 	if (!nV || !nT) {
+		SmoothState *s;
+		if ((rc = smooth_state(c, &s))) return rc;
 		if (nV) HIP_TRY(hipMemsetAsync(oN, 0, nV * 12u, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		if ((rc = prop_check(c))) return rc;
-		return meas_bad(nT, nV);
+		return mesh_bad(nT, nV);
 	}
-	if ((rc = sm_room(c, nV, nT, false, 0u))) return rc;
-	HIP_TRY(hipMemsetAsync(s->d_out, 0, sizeof(SmOut), c->stream));
-	if ((rc = sm_normals(c, (const real_t *)dV, (const uint32_t *)dT, nT, nV, oN, true))) return rc;
-	if ((rc = sm_fetch(c))) return rc;
-	return meas_bad(s->h_out->bad, nV);
+	unsigned long long bad;
+	if ((rc = sm_normals_call(c, (const real_t *)dV, (const uint32_t *)dT, nT, nV, oN, &bad))) return rc;
+	return mesh_bad(bad, nV);
 }
 
 extern "C" int mc33hip_smooth_timing(mc33hip_ctx *c, float *adjacency_ms, float *normals_ms, float *pass_ms, unsigned capacity, unsigned *passes) {
@@ -469,8 +410,9 @@ extern "C" int mc33hip_smooth_timing(mc33hip_ctx *c, float *adjacency_ms, float 
 	*passes = 0;
 	if (adjacency_ms) *adjacency_ms = 0.f;
 	if (normals_ms) *normals_ms = 0.f;
-	if (!c->meas || !c->meas->smooth) return MC33HIP_OK;
-	const SmoothTimers &t = c->meas->smooth->timers;
+	const MeshOp *op = c->meas ? mesh_op_peek(&c->meas->mesh, smooth_release) : nullptr;
+	if (!op) return MC33HIP_OK;
+	const SmoothTimers &t = ((const SmoothState *)op->state)->timers;
 	if (adjacency_ms && t.adjacency) { HIP_TRY(hipEventElapsedTime(adjacency_ms, t.ev[0], t.ev[1])); }
 	if (normals_ms && t.normals) { HIP_TRY(hipEventElapsedTime(normals_ms, t.ev[2], t.ev[3])); }
 	*passes = t.passes;

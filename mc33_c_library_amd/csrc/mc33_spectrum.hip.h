@@ -296,14 +296,11 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_spectrum(const T *__restrict_
 
 // --- host side ----------------------------------------------------------------------------------------------------------
 
-static void sp_destroy(MeasureState *m) {
-	SpectrumState *s = m->spectrum;
-	if (!s) return;
+static void sp_release(void *state) {  // (the result block is an array of words, not a struct: made and freed here)
+	SpectrumState *s = (SpectrumState *)state;
 	dev_release(&s->d_isos);
 	dev_release(&s->d_out);
 	if (s->h_out) (void)hipHostFree(s->h_out);
-	free(s);
-	m->spectrum = nullptr;
 }
 
 // As many blocks as the device holds at once - a block keeps its counters until it has no work left, and a second round of blocks
@@ -345,11 +342,9 @@ extern "C" int mc33hip_grid_spectrum(mc33hip_ctx *c, const mc33hip_range *range,
 	int rc;
 	if ((rc = use_device(c))) return rc;
 	if ((rc = meas_state(c))) return rc;
-	SpectrumState *s = c->meas->spectrum;
-	if (!s) {
-		if (!(s = (SpectrumState *)calloc(1, sizeof *s))) return MC33HIP_ENOMEM;
-		c->meas->spectrum = s;
-	}
+	MeshOp *op;
+	if ((rc = mesh_op_find(&c->meas->mesh, sp_release, sizeof(SpectrumState), &op))) return rc;
+	SpectrumState *s = (SpectrumState *)op->state;
 	if (!s->d_isos) HIP_TRY(hipMalloc(&s->d_isos, 256 * sizeof(real_t)));
 	if (!s->d_out) HIP_TRY(hipMalloc(&s->d_out, SP_OUT_WORDS * sizeof(unsigned long long)));
 	if (!s->h_out) HIP_TRY(hipHostMalloc(&s->h_out, SP_OUT_WORDS * sizeof(unsigned long long), hipHostMallocDefault));

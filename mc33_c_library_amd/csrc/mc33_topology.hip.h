@@ -1,22 +1,21 @@
-// mc33_topology.hip.h -- part of the ONE translation unit mc33_kernels.hip (included there, last; not a header to include elsewhere):
+// mc33_topology.hip.h -- part of the ONE translation unit mc33_kernels.hip (builds on mc33_mesh.hip.h and mc33_measure.hip.h; not a header to include elsewhere):
 // the topology of a FINISHED triangle list in device memory - distinct edges, boundary / non-manifold / misoriented edges,
 // degenerate triangles, boundary loops, Euler number and genus, for the surface and per connected component - so that a few
 // integers cross the link instead of the mesh (include/mc33_hip.h: mc33hip_surface_topology, mc33hip_component_topology).
-// DESIGN.md 11.  Only T is read; labels, flags and ranks are those of mc33_measure.hip.h.
+// DESIGN.md 11.  Only T is read; labels, flags, ranks and the union-find (k_cc_*, cc_unite) are those of mc33_measure.hip.h.
 //
 // The definition: a triangle that names a vertex >= nV is counted and contributes nothing; a valid one with two equal indices
 // is degenerate: its sides a -> a are skipped, its other sides enter like any side.  Every other side a -> b, in the order
 // T0 -> T1, T1 -> T2, T2 -> T0, is a use of the edge {lo, hi} = {min, max}, forward when a < b.  tests/topology_oracle.py restates
 // it in numpy.  Everything is an integer and added with integer atomics: the results do not depend on scheduling.
 //
-// The edge table: open addressing in device memory, 16 bytes per slot - the key lo << 32 | hi (all ones: empty; lo < hi, so no
+// The edge table: the table of mc33_mesh.hip.h, 16 bytes per slot - the key lo << 32 | hi (all ones: empty; lo < hi, so no
 // key has it) and one word of two exact 32-bit use counters, forward in the low half, backward in the high half (either is at
 // most nT <= 2^32 - 1: the low half never carries).  A power of two >= 4 nT slots for at most 3 nT edges.  Insert-only.
 
 struct TopoSlot { unsigned long long key, uses; };
 using TopoRow = struct mc33hip_component_topology;  // (the plain name is the function's)
 
-constexpr unsigned long long TOPO_EMPTY = ~0ull;
 constexpr uint32_t TOPO_NONE = 0xFFFFFFFFu;
 // counters of the component rows the kernels add into (unsigned long long [components][TOPO_COLS])
 enum { TC_NV = 0, TC_NT, TC_EDGES, TC_BOUNDARY, TC_NONMANIFOLD, TC_MISORIENTED, TC_DEGENERATE, TC_LOOPS, TC_ROOT, TOPO_COLS };
@@ -44,43 +43,13 @@ struct TopoState {          // scratch of these passes: on the MeasureState from
 	uint64_t table_cap;
 };
 
-// the splitmix64 finalizer: every bit of the key reaches every bit of the home slot
-__device__ __forceinline__ uint64_t topo_mix(uint64_t x) {
-	x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-	x ^= x >> 27; x *= 0x94D049BB133111EBull;
-	return x ^ (x >> 31);
-}
-
-// One use of the edge {a, b}, a != b.  What the compare-and-swap on the key RETURNS decides - empty or equal: this is the
-// edge's slot; anything else: probe on, linearly.  The slot is never read with a plain load (the XCDs' L2s are not coherent
-// for those).  Returns false when every slot was tried.
+// One use of the edge {a, b}, a != b: the slot claimed, the use added to its counter.  Returns false when every slot was tried.
 __device__ __forceinline__ bool topo_use(TopoSlot *slots, uint64_t mask, uint32_t a, uint32_t b) {
 	const bool fwd = a < b;
-	const unsigned long long key = fwd ? ((unsigned long long)a << 32) | b : ((unsigned long long)b << 32) | a;
-	uint64_t s = topo_mix(key) & mask;
-	for (uint64_t tries = 0; tries <= mask; tries++, s = (s + 1u) & mask) {
-		const unsigned long long old = atomicCAS(&slots[s].key, TOPO_EMPTY, key);
-		if (old == TOPO_EMPTY || old == key) {
-			atomicAdd(&slots[s].uses, fwd ? 1ull : 1ull << 32);
-			return true;
-		}
-	}
-	return false;
-}
-
-__global__ __launch_bounds__(256) void k_topo_clear(TopoSlot *__restrict__ slots, uint64_t n) {
-	for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < n; s += (uint64_t)gridDim.x * 256u)
-		*(ulonglong2 *)(slots + s) = make_ulonglong2(TOPO_EMPTY, 0ull);
-}
-
-// sum over the block's 256 lanes; lane 0 of the block holds the result.  sh: [4]
-__device__ __forceinline__ uint32_t topo_block_sum(uint32_t x, uint32_t *sh) {
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d, 64);
-	__syncthreads();
-	if ((threadIdx.x & 63u) == 0u) sh[threadIdx.x >> 6] = x;
-	__syncthreads();
-	return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+	const uint64_t s = mesh_claim(slots, mask, fwd ? ((unsigned long long)a << 32) | b : ((unsigned long long)b << 32) | a);
+	if (s == MESH_NOSLOT) return false;
+	atomicAdd(&slots[s].uses, fwd ? 1ull : 1ull << 32);
+	return true;
 }
 
 // one pass over T: validate, count, and enter the sides (a lane a triangle: neighbouring lanes name neighbouring vertices)
@@ -97,9 +66,9 @@ __global__ __launch_bounds__(256) void k_topo_insert(const uint32_t *__restrict_
 		if (t1 != t2 && !topo_use(slots, mask, t1, t2)) full++;
 		if (t2 != t0 && !topo_use(slots, mask, t2, t0)) full++;
 	}
-	bad = topo_block_sum(bad, sh);
-	deg = topo_block_sum(deg, sh);
-	full = topo_block_sum(full, sh);
+	bad = block_sum_u32_256(bad, sh);
+	deg = block_sum_u32_256(deg, sh);
+	full = block_sum_u32_256(full, sh);
 	if (threadIdx.x == 0u) {
 		if (bad) atomicAdd(&out->invalid, (unsigned long long)bad);
 		if (deg) atomicAdd(&out->degenerate, (unsigned long long)deg);
@@ -164,7 +133,7 @@ __global__ __launch_bounds__(256) void k_topo_classify(const TopoSlot *__restric
 		uint32_t key = TOPO_NONE, x[4] = {0u, 0u, 0u, 0u};
 		if (s < end) {
 			const ulonglong2 e = *(const ulonglong2 *)(slots + s);
-			if (e.x != TOPO_EMPTY) {
+			if (e.x != MESH_EMPTY) {
 				const uint32_t lo = (uint32_t)(e.x >> 32), hi = (uint32_t)e.x;
 				const uint32_t f = (uint32_t)e.y, b = (uint32_t)(e.y >> 32);
 				const uint64_t uses = (uint64_t)f + b;
@@ -188,10 +157,10 @@ __global__ __launch_bounds__(256) void k_topo_classify(const TopoSlot *__restric
 	unsigned long long *const dst[4] = {&out->edges, &out->boundary, &out->nonmanifold, &out->misoriented};
 #pragma unroll
 	for (int k = 0; k < 4; k++) {
-		const uint32_t t = topo_block_sum(tot[k], sh);
+		const uint32_t t = block_sum_u32_256(tot[k], sh);
 		if (threadIdx.x == 0u && t) atomicAdd(dst[k], (unsigned long long)t);
 	}
-	bad = topo_block_sum(bad, sh);
+	bad = block_sum_u32_256(bad, sh);
 	if (threadIdx.x == 0u && bad) atomicAdd(bad_out, (unsigned long long)bad);
 }
 
@@ -250,7 +219,7 @@ __global__ __launch_bounds__(256) void k_topo_rows_vertices(uint64_t nV, uint64_
 		held.step(rows, col, key, x);
 	}
 	held.flush(rows, col);
-	loops = topo_block_sum(loops, sh);
+	loops = block_sum_u32_256(loops, sh);
 	if (threadIdx.x == 0u && loops) atomicAdd(&out->loops, (unsigned long long)loops);
 }
 
@@ -275,8 +244,8 @@ __global__ __launch_bounds__(256) void k_topo_finish(const unsigned long long *_
 		if (defined) gsum += (unsigned long long)(twice / 2);
 		else undefined++;
 	}
-	closed = topo_block_sum(closed, sh);
-	undefined = topo_block_sum(undefined, sh);
+	closed = block_sum_u32_256(closed, sh);
+	undefined = block_sum_u32_256(undefined, sh);
 	if (threadIdx.x == 0u) {
 		if (closed) atomicAdd(&out->closed_components, (unsigned long long)closed);
 		if (undefined) atomicAdd(&out->genus_undefined, (unsigned long long)undefined);
@@ -286,41 +255,21 @@ __global__ __launch_bounds__(256) void k_topo_finish(const unsigned long long *_
 
 // --- host side ----------------------------------------------------------------------------------------------------------
 
-static void topo_destroy(MeasureState *m) {
-	TopoState *t = m->topo;
-	if (!t) return;
-	dev_release(&t->d_out); dev_release(&t->d_slots); dev_release(&t->d_loop); dev_release(&t->d_bflag); dev_release(&t->d_label);
-	dev_release(&t->d_rows); dev_release(&t->d_table);
-	if (t->h_out) (void)hipHostFree(t->h_out);
-	free(t);
-	m->topo = nullptr;
+static void topo_release(void *state) {
+	TopoState *t = (TopoState *)state;
+	dev_release(&t->d_slots); dev_release(&t->d_loop); dev_release(&t->d_bflag); dev_release(&t->d_label); dev_release(&t->d_rows); dev_release(&t->d_table);
+}
+static int topo_state(mc33hip_ctx *c, TopoState **t) {
+	const int rc = meas_state(c);
+	return rc ? rc : mesh_op_state(&c->meas->mesh, topo_release, t);
 }
 
-static int topo_state(mc33hip_ctx *c) {
-	int rc = meas_state(c);
-	if (rc) return rc;
-	if (c->meas->topo) return 0;
-	TopoState *t = (TopoState *)calloc(1, sizeof *t);
-	if (!t) return MC33HIP_ENOMEM;
-	c->meas->topo = t;  // (what it holds so far goes with the context)
-	HIP_TRY(hipMalloc(&t->d_out, sizeof(TopoOut)));
-	HIP_TRY(hipHostMalloc(&t->h_out, sizeof(TopoOut), hipHostMallocDefault));
-	return 0;
-}
-
-static uint64_t topo_slots(uint64_t nT) {  // a power of two >= 4 nT
-	uint64_t n = 256u;
-	while (n < 4u * nT) n <<= 1;
-	return n;
-}
-
-// Everything behind the labels, flags and the number of components (m->d_flags, m->d_bsum as cc_flag_and_count left them):
+// Everything behind the labels, flags and the number of components (m->d_flags, the tile sums as cc_flag_and_count left them):
 // ranks, the edge table, the rows, the table in t->d_table and the totals in t->d_out.  Enqueues; nT, nV, ncomp > 0.
-static int topo_enqueue(mc33hip_ctx *c, const void *dT, uint64_t nT, uint64_t nV, const uint32_t *dLabel, uint64_t ncomp) {
+static int topo_enqueue(mc33hip_ctx *c, TopoState *t, const void *dT, uint64_t nT, uint64_t nV, const uint32_t *dLabel, uint64_t ncomp) {
 	MeasureState *m = c->meas;
-	TopoState *t = m->topo;
 	int rc;
-	const uint64_t tiles = (nV + CC_TILE - 1u) / CC_TILE, nslots = topo_slots(nT);
+	const uint64_t nslots = mesh_table_size(nT, 4u, 1ull << 40);
 	if ((rc = meas_room(&m->d_rank, &m->rank_cap, nV))) return rc;
 	if (t->slots_cap < nslots || !t->d_slots) {  // (a power of two as it is: no slack)
 		if ((rc = dev_room("edge table", &t->d_slots, &t->slots_cap, nslots))) return rc;
@@ -336,9 +285,8 @@ static int topo_enqueue(mc33hip_ctx *c, const void *dT, uint64_t nT, uint64_t nV
 	const uint32_t gridS = meas_grid(c, nslots, 8u), gridT = meas_grid(c, nT, 8u), gridV = meas_grid(c, nV, 8u);
 	const uint64_t chunkS = ((nslots + gridS - 1u) / gridS + 255u) / 256u * 256u, chunkT = ((nT + gridT - 1u) / gridT + 255u) / 256u * 256u,
 	               chunkV = ((nV + gridV - 1u) / gridV + 255u) / 256u * 256u;
-	hipLaunchKernelGGL(k_cc_scan_top, dim3(1), dim3(256), 0, c->stream, m->d_bsum, tiles);
-	hipLaunchKernelGGL(k_cc_rank, dim3((uint32_t)tiles), dim3(256), 0, c->stream, m->d_flags, m->d_bsum, nV, m->d_rank);
-	hipLaunchKernelGGL(k_topo_clear, dim3(meas_grid(c, nslots, 16u)), dim3(256), 0, c->stream, t->d_slots, nslots);
+	mesh_scan_sums<MeshFlag, MESH_RANK>(c, m->d_flags, nV, m->mesh.d_bsum, nullptr, m->d_rank);
+	hipLaunchKernelGGL(k_mesh_clear, dim3(meas_grid(c, nslots, 16u)), dim3(256), 0, c->stream, (ulonglong2 *)t->d_slots, nslots, 0ull);
 	hipLaunchKernelGGL(k_cc_init, dim3(meas_grid(c, nV, 16u)), dim3(256), 0, c->stream, t->d_loop, nV);
 	hipLaunchKernelGGL(k_topo_insert, dim3(meas_grid(c, nT, 16u)), dim3(256), 0, c->stream, (const uint32_t *)dT, nT, nV, t->d_slots, nslots - 1u, t->d_out);
 	hipLaunchKernelGGL(k_topo_classify, dim3(gridS), dim3(256), 0, c->stream, t->d_slots, nslots, chunkS, nV, dLabel, m->d_flags, m->d_rank, t->d_loop, t->d_bflag,
@@ -360,17 +308,17 @@ static int topo_full(unsigned long long n) {
 }
 
 extern "C" int mc33hip_surface_topology(mc33hip_ctx *c, const void *dT, unsigned long long nT, unsigned long long nV, mc33hip_topology *out) {
-	if (!c || !out || (nT && !dT) || !meas_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
+	if (!c || !out || (nT && !dT) || !mesh_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
 	int rc = use_device(c);
 	if (rc) return rc;
-	if ((rc = topo_state(c))) return rc;
+	TopoState *t;
+	if ((rc = topo_state(c, &t))) return rc;
 	MeasureState *m = c->meas;
-	TopoState *t = m->topo;
 	memset(out, 0, sizeof *out);
 	out->nV = nV; out->nT = nT;
 	out->closed = out->manifold = out->oriented = out->genus_defined = 1;
 	if (!nT) return MC33HIP_OK;
-	if (!nV) return meas_bad(nT, nV);  // (every triangle names a vertex outside the 0 rows of V)
+	if (!nV) return mesh_bad(nT, nV);  // (every triangle names a vertex outside the 0 rows of V)
 	// the labels, in scratch of this call's own: what mc33hip_label_components does
 	if ((rc = meas_room(&t->d_label, &t->label_cap, nV))) return rc;
 	if ((rc = meas_zero_counters(c))) return rc;
@@ -384,9 +332,9 @@ extern "C" int mc33hip_surface_topology(mc33hip_ctx *c, const void *dT, unsigned
 	out->referenced_vertices = nV - unref;
 	out->components = ncomp;
 	out->euler = (long long)out->referenced_vertices;
-	if (!ncomp) return meas_bad(invalid, nV);  // (no valid triangle)
+	if (!ncomp) return mesh_bad(invalid, nV);  // (no valid triangle)
 	if ((rc = meas_zero_counters(c))) return rc;
-	if ((rc = topo_enqueue(c, dT, nT, nV, t->d_label, ncomp))) return rc;
+	if ((rc = topo_enqueue(c, t, dT, nT, nV, t->d_label, ncomp))) return rc;
 	if ((rc = meas_fetch(c))) return rc;
 	const TopoOut &h = *t->h_out;
 	if ((rc = topo_full(h.full))) return rc;
@@ -396,30 +344,30 @@ extern "C" int mc33hip_surface_topology(mc33hip_ctx *c, const void *dT, unsigned
 	out->euler = ((long long)out->referenced_vertices - (long long)h.edges) + (long long)(nT - h.invalid);
 	out->closed = h.boundary == 0; out->manifold = h.nonmanifold == 0 && h.degenerate == 0; out->oriented = h.misoriented == 0;
 	out->genus_defined = h.genus_undefined == 0;
-	return meas_bad(h.invalid + m->h_out->bad, nV);
+	return mesh_bad(h.invalid + m->h_out->bad, nV);
 }
 
 extern "C" int mc33hip_component_topology(mc33hip_ctx *c, const void *dT, unsigned long long nT, unsigned long long nV, const unsigned *dLabel,
                                           struct mc33hip_component_topology *host_table, unsigned long long capacity, unsigned long long *components) {
-	if (!c || !components || (nV && !dLabel) || (nT && !dT) || (capacity && !host_table) || !meas_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
+	if (!c || !components || (nV && !dLabel) || (nT && !dT) || (capacity && !host_table) || !mesh_sizes_ok(nV, nT)) return MC33HIP_EINVAL;
 	int rc = use_device(c);
 	if (rc) return rc;
-	if ((rc = topo_state(c))) return rc;
+	TopoState *t;
+	if ((rc = topo_state(c, &t))) return rc;
 	MeasureState *m = c->meas;
-	TopoState *t = m->topo;
 	*components = 0;
 	if ((rc = meas_zero_counters(c))) return rc;
 	if ((rc = cc_flag_and_count(c, dT, nT, nV, dLabel, true))) return rc;
 	if ((rc = meas_fetch(c))) return rc;
-	if ((rc = meas_bad(m->h_out->bad, nV))) return rc;
+	if ((rc = mesh_bad(m->h_out->bad, nV))) return rc;
 	const unsigned long long ncomp = m->h_out->comps;
 	*components = ncomp;
 	if (capacity < ncomp) { set_err("the component table needs %llu rows, the caller's has %llu", ncomp, capacity); return MC33HIP_ECAPACITY; }
 	if (!ncomp) return MC33HIP_OK;
 	if ((rc = meas_zero_counters(c))) return rc;
-	if ((rc = topo_enqueue(c, dT, nT, nV, dLabel, ncomp))) return rc;
+	if ((rc = topo_enqueue(c, t, dT, nT, nV, dLabel, ncomp))) return rc;
 	HIP_TRY(hipMemcpyAsync(host_table, t->d_table, ncomp * sizeof(TopoRow), hipMemcpyDeviceToHost, c->stream));
 	if ((rc = meas_fetch(c))) return rc;
 	if ((rc = topo_full(t->h_out->full))) return rc;
-	return meas_bad(t->h_out->invalid + m->h_out->bad, nV);
+	return mesh_bad(t->h_out->invalid + m->h_out->bad, nV);
 }

@@ -110,7 +110,7 @@ def tile_edge(nV, unreferenced):
     """lengths for exactly nV vertices, `unreferenced` of them behind the pieces: strips of STRIP triangles, one or two shorter
     strips that take what is left over, and a single triangle last - in "identity" order its root is nV - 3 - unreferenced"""
     body = nV - unreferenced - 3
-    assert body >= 3
+    assert body == 0 or body >= 3  # (0: the single triangle alone)
     q, r = divmod(body, STRIP + 2)
     if r in (1, 2):  # too few vertices for a strip: a full strip less, and two shorter ones
         q, r = q - 1, r + STRIP + 2

@@ -22,13 +22,15 @@ import fixtures as fx
 import measure_oracle as mo
 import topology_oracle as to
 from mc33_capi import MC33Lib, product_path
+from test_mesh_common_cpu import launched
 from test_simplify_cpu import mesh
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 HIP_NAMES = ["mc33hip_clip_surface"]
 C_NAMES = ["MC33_calculate_clipped_isosurface", "MC33_clip_box"]
-KERNELS = ["k_clip_clear", "k_clip_tri", "k_clip_own", "k_clip_emit", "k_clip_tile_sum<0>", "k_clip_tile_sum<1>", "k_clip_tile_sum<2>"]
+KERNELS = ["k_clip_tri", "k_clip_own", "k_clip_emit"] + launched("k_mesh_clear", "k_mesh_tile_sum<MeshFlag>", "k_mesh_tile_sum<ClipOwned>", "k_mesh_tile_sum<ClipOutputs>",
+                                                           "k_mesh_scan_top", "k_mesh_place<MeshFlag, 1>")
 PLANES = ("oblique", "on-grid", "miss", "all")
 MODES = (co.LERP_F32, co.COPY)
 

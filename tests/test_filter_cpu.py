@@ -19,12 +19,13 @@ import fixtures as fx
 import measure_oracle as mo
 import topology_oracle as to
 from mc33_capi import MC33Lib, product_path
+from test_mesh_common_cpu import launched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 HIP_NAMES = ["mc33hip_compact_components"]
 C_NAMES = ["MC33_select_components", "MC33_calculate_filtered_isosurface"]
-KERNELS = ["k_filt_roots", "k_filt_ref", "k_filt_keep", "k_filt_scan_top", "k_filt_new", "k_filt_tri_count", "k_filt_tris"]
+KERNELS = ["k_filt_roots", "k_filt_keep", "k_filt_tri_count", "k_filt_tris"] + launched("k_mesh_ref", "k_mesh_scan_top", "k_mesh_place<MeshFlag, 1>")
 
 
 class CComponent(C.Structure):

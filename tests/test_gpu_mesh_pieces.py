@@ -26,7 +26,7 @@ import topology_oracle as to
 pytestmark = pytest.mark.gpu
 
 SEED = 7
-CC_TILE = 1024  # vertices per block of k_cc_count / k_cc_rank; k_cc_scan_top takes 256 tiles per round
+MESH_TILE = 1024  # vertices per block of k_cc_count / k_mesh_place; k_mesh_scan_top takes 256 tiles per round
 _mesh, _want, _fresh = {}, {}, {}
 
 
@@ -263,12 +263,12 @@ def test_tile_and_scan_edges(nV, unreferenced):
     assert V.shape[0] == nV
     root = int(exp["table"]["root"][-1])
     assert root == nV - 3 - unreferenced and T[-1].tolist() == [root, root + 1, root + 2] and int(exp["table"]["nT"][-1]) == 1
-    last = (nV - 1) // CC_TILE
-    assert root // CC_TILE == (last if (nV - 1) % CC_TILE >= 2 + unreferenced else last - 1)
+    last = (nV - 1) // MESH_TILE
+    assert root // MESH_TILE == (last if (nV - 1) % MESH_TILE >= 2 + unreferenced else last - 1)
     if nV in (1027, 262147) and not unreferenced:
-        assert root == last * CC_TILE
+        assert root == last * MESH_TILE
     if nV - unreferenced >= 262147:
-        assert root // CC_TILE >= 256
+        assert root // MESH_TILE >= 256
     run(key)
 
 

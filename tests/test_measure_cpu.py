@@ -14,13 +14,14 @@ import pytest
 import fixtures as fx
 import measure_oracle as mo
 from mc33_capi import MC33Lib, product_path
+from test_mesh_common_cpu import launched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 HIP_NAMES = ["mc33hip_measure_surface", "mc33hip_label_components", "mc33hip_measure_components"]
 C_NAMES = ["MC33_measure_isosurface", "MC33_measure_isosurfaces", "MC33_measure_components"]
 KERNELS = ["k_measure_triangles<float, true>", "k_measure_triangles<float, false>", "k_measure_bbox<float>", "k_measure_finish", "k_cc_init", "k_cc_union",
-           "k_cc_flatten", "k_cc_flag", "k_cc_count", "k_cc_scan_top", "k_cc_rank", "k_cc_table_triangles<float>", "k_cc_table_vertices"]
+           "k_cc_flatten", "k_cc_flag", "k_cc_count", "k_cc_table_triangles<float>", "k_cc_table_vertices"] + launched("k_mesh_scan_top", "k_mesh_place<MeshFlag, 0>")
 
 # what the issue's table adds to mo.FIXTURES: total area and signed volume of the reference's mesh, to the digits it quotes
 FIGURES = {"sphere": (12.561676, -4.185969), "blobs": (759.193278, 375.618205)}

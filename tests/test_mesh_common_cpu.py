@@ -1,0 +1,43 @@
+"""The layer the passes over a finished mesh share (mc33_c_library_amd/csrc/mc33_mesh.hip.h), the part that needs no
+GPU: its kernels in the gfx950 code object of every sample type, and its place in the translation unit and in both builds.
+
+MESH_KERNELS is the one list of the shared kernels.  The tests of the parts that launch them (test_measure_cpu.py,
+test_topology_cpu.py, test_filter_cpu.py, test_smooth_cpu.py, test_simplify_cpu.py, test_clip_cpu.py) take the names their entry
+points launch from it through launched(), beside the kernels of their own.  On the device the layer is held to the oracles by
+the GPU tests of those parts and by tests/test_gpu_mesh_scratch.py."""
+import os
+
+import pytest
+
+from mc33_capi import product_path
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# (the second argument of k_mesh_place: 0 a rank, 1 the new index or none, 2 row starts with the total behind them)
+MESH_KERNELS = ["k_mesh_tile_sum<MeshFlag>", "k_mesh_tile_sum<MeshCount>", "k_mesh_tile_sum<ClipOwned>", "k_mesh_tile_sum<ClipOutputs>", "k_mesh_scan_top",
+                "k_mesh_place<MeshFlag, 0>", "k_mesh_place<MeshFlag, 1>", "k_mesh_place<MeshCount, 2>", "k_mesh_clear", "k_mesh_ref"]
+
+
+def launched(*names):
+    """the shared kernels a part launches, by their names in MESH_KERNELS"""
+    for n in names:
+        assert n in MESH_KERNELS, n
+    return list(names)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
+def test_shared_kernels_are_in_the_code_object(dtype):
+    from test_code_objects import kernel_metadata
+    ks = {k["pretty"]: k for k in kernel_metadata(product_path(dtype))}
+    for name in MESH_KERNELS:
+        assert name in ks, (name, sorted(ks))
+        assert ks[name]["private_segment_fixed_size"] == 0 and ks[name]["vgpr_spill_count"] == 0, (name, ks[name])
+        assert ks[name]["vgpr_count"] <= 64, (name, ks[name])  # (eight waves per SIMD)
+
+
+def test_the_part_is_built_and_included_before_the_parts_that_use_it():
+    from mc33_c_library_amd import build
+    assert "mc33_mesh.hip.h" in build.HIP_HEADERS
+    assert " mc33_mesh.hip.h" in open(os.path.join(ROOT, "mc33_c_library_amd", "csrc", "Makefile")).read()
+    kernels = open(os.path.join(ROOT, "mc33_c_library_amd", "csrc", "mc33_kernels.hip")).read()
+    assert '#include "mc33_property.hip.h"\n#include "mc33_mesh.hip.h"\n#include "mc33_measure.hip.h"\n' in kernels and "k_mesh_" in kernels

@@ -19,12 +19,14 @@ import fixtures as fx
 import measure_oracle as mo
 import simplify_oracle as sp
 from mc33_capi import MC33Lib, product_path
+from test_mesh_common_cpu import launched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 HIP_NAMES = ["mc33hip_simplify_surface"]
 C_NAMES = ["MC33_calculate_simplified_isosurface"]
-KERNELS = ["k_simp_clear", "k_simp_ref", "k_simp_reps", "k_simp_tri_insert", "k_simp_tri_keep", "k_simp_tile_count", "k_simp_tris"]
+KERNELS = ["k_simp_clear", "k_simp_reps", "k_simp_tri_insert", "k_simp_tri_keep", "k_simp_tris"] + launched("k_mesh_ref", "k_mesh_tile_sum<MeshFlag>", "k_mesh_scan_top",
+                                                                                                 "k_mesh_place<MeshFlag, 1>")
 CELLS = {"2x2x2": (2.0, 2.0, 2.0), "3x2x5": (3.0, 2.0, 5.0)}  # in grid cells
 MODES = {"mean": sp.MEAN, "first": sp.FIRST}
 

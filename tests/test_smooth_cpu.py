@@ -18,12 +18,13 @@ import fixtures as fx
 import measure_oracle as mo
 import smooth_oracle as so
 from mc33_capi import MC33Lib, product_path
+from test_mesh_common_cpu import launched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 HIP_NAMES = ["mc33hip_smooth_surface", "mc33hip_vertex_normals"]
 C_NAMES = ["MC33_calculate_smoothed_isosurface"]
-KERNELS = ["k_sm_count<0>", "k_sm_count<1>", "k_sm_tile_sum", "k_sm_starts", "k_sm_fill<0>", "k_sm_fill<1>", "k_sm_rows"]
+KERNELS = ["k_sm_count<0>", "k_sm_count<1>", "k_sm_fill<0>", "k_sm_fill<1>", "k_sm_rows"] + launched("k_mesh_tile_sum<MeshCount>", "k_mesh_scan_top", "k_mesh_place<MeshCount, 2>")
 
 # fixture -> max_degree, isolated, boundary_vertices, area before, after 10 iterations (0.5, -0.53) pinned, not pinned
 TABLE = {

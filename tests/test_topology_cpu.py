@@ -15,12 +15,13 @@ import fixtures as fx
 import measure_oracle as mo
 import topology_oracle as to
 from mc33_capi import MC33Lib, product_path
+from test_mesh_common_cpu import launched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 HIP_NAMES = ["mc33hip_surface_topology", "mc33hip_component_topology"]
 C_NAMES = ["MC33_isosurface_topology", "MC33_component_topology"]
-KERNELS = ["k_topo_clear", "k_topo_insert", "k_topo_classify", "k_topo_rows_triangles", "k_topo_rows_vertices", "k_topo_finish"]
+KERNELS = ["k_topo_insert", "k_topo_classify", "k_topo_rows_triangles", "k_topo_rows_vertices", "k_topo_finish"] + launched("k_mesh_clear", "k_mesh_scan_top", "k_mesh_place<MeshFlag, 0>")
 
 # fixture -> unique edges, used once, used more than twice, most uses of one edge, used twice in the same direction, degenerate
 # triangles, Euler number nV_ref - E + nT, boundary loops, boundary vertices that do not end exactly two boundary edges

@@ -25,7 +25,7 @@ if "--trace-summary" in sys.argv:  # (the device part runs its calls on the one-
     per = collections.defaultdict(list)
     for r in rows:
         name = r["Kernel_Name"].split("(")[0].replace("void ", "")
-        if name.startswith(("k_measure", "k_cc_")):
+        if name.startswith(("k_measure", "k_cc_", "k_mesh_")):  # (k_mesh_*: the shared scan the component table launches)
             per[name].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     for name, us in per.items():
         a, b = sorted(us[:len(us) // 2]), sorted(us[len(us) // 2:])

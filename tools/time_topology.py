@@ -26,7 +26,7 @@ if "--trace-summary" in sys.argv:
     per = collections.defaultdict(list)
     for r in rows:
         name = r["Kernel_Name"].split("(")[0].replace("void ", "")
-        if name.startswith(("k_topo_", "k_cc_")):
+        if name.startswith(("k_topo_", "k_cc_", "k_mesh_")):  # (k_mesh_*: the shared scan and table clear these calls launch)
             per[name].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     for name, us in per.items():
         k = len(us) // len(names)
