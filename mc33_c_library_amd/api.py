@@ -565,17 +565,21 @@ class DeviceGrid:
         _check(self.lib, self.lib.mc33hip_synchronize(self.ctx))
         return out
 
-    def extract(self, iso, rng=None, with_property=False):
-        """Count, allocate exact-size outputs with torch, emit.  Returns (V, N, T, Counts); with_property: and the attached
-        property grid's value at every vertex as a fifth element."""
+    def _extract_rows(self, iso, rng):
+        """count, outputs of the counted sizes (one row at least) from torch, emit - enqueued only: (V, N, T, Counts)"""
         import torch
-        rng = rng or self.full_range()
-        cnt = self.count(iso, rng)
+        cnt = self.count(iso, rng or self.full_range())
         V = torch.empty((max(cnt.nV, 1), 3), dtype=torch.float64 if self.dtype == "f64" else torch.float32, device=self.device)
         N = torch.empty((max(cnt.nV, 1), 3), dtype=torch.float32, device=self.device)
         T = torch.empty((max(cnt.nT, 1), 3), dtype=torch.int32, device=self.device)
         _check(self.lib, self.lib.mc33hip_emit(self.ctx, C.c_void_p(V.data_ptr()), C.c_void_p(N.data_ptr()),
                                                C.c_void_p(T.data_ptr()), V.shape[0], T.shape[0]))
+        return V, N, T, cnt
+
+    def extract(self, iso, rng=None, with_property=False):
+        """Count, allocate exact-size outputs with torch, emit.  Returns (V, N, T, Counts); with_property: and the attached
+        property grid's value at every vertex as a fifth element."""
+        V, N, T, cnt = self._extract_rows(iso, rng)
         if with_property:
             return V[:cnt.nV], N[:cnt.nV], T[:cnt.nT], cnt, self.sample_property(V[:cnt.nV])
         self.stream.synchronize()
@@ -614,31 +618,29 @@ class DeviceGrid:
     def measure_components(self, V, T, labels=None):
         """The component table - root, nV, nT, area, volume per component, in ascending order of root - as a numpy structured
         array; labels: what label_components returned for T (made here when None)."""
-        import numpy as np
         self._vertex_rows(V)
         self._triangle_rows(T)
         if labels is None:
             labels = self.label_components(T, V.shape[0])[0]
         assert labels.is_cuda and labels.is_contiguous() and labels.numel() == V.shape[0] and labels.element_size() == 4
-        args = (self.ctx, C.c_void_p(V.data_ptr()), V.shape[0], C.c_void_p(T.data_ptr()), T.shape[0], C.c_void_p(labels.data_ptr()))
+        return self._component_table(self.lib.mc33hip_measure_components, Component,
+                                     C.c_void_p(V.data_ptr()), V.shape[0], C.c_void_p(T.data_ptr()), T.shape[0], C.c_void_p(labels.data_ptr()))
+
+    def _component_table(self, fn, row, *args):
+        """fn(ctx, *args, table, capacity, &n) twice: without a table for the number of rows, then into a numpy array of them"""
+        import numpy as np
         n = C.c_ulonglong()
-        _check(self.lib, self.lib.mc33hip_measure_components(*args, None, 0, C.byref(n)), allow=(ECAPACITY,))
-        table = np.zeros(n.value, dtype=np.dtype(Component))
+        _check(self.lib, fn(self.ctx, *args, None, 0, C.byref(n)), allow=(ECAPACITY,))
+        table = np.zeros(n.value, dtype=np.dtype(row))
         if n.value:
-            _check(self.lib, self.lib.mc33hip_measure_components(*args, C.c_void_p(table.ctypes.data), n.value, C.byref(n)))
+            _check(self.lib, fn(self.ctx, *args, C.c_void_p(table.ctypes.data), n.value, C.byref(n)))
         return table
 
     def measure_iso(self, iso, rng=None, with_property=False):
         """Count, emit into torch tensors, measure - nothing but the result crosses the link; with_property: the attached
         property grid is sampled at the vertices first and its integral over the surface filled in."""
         import torch
-        rng = rng or self.full_range()
-        cnt = self.count(iso, rng)
-        V = torch.empty((max(cnt.nV, 1), 3), dtype=torch.float64 if self.dtype == "f64" else torch.float32, device=self.device)
-        N = torch.empty((max(cnt.nV, 1), 3), dtype=torch.float32, device=self.device)
-        T = torch.empty((max(cnt.nT, 1), 3), dtype=torch.int32, device=self.device)
-        _check(self.lib, self.lib.mc33hip_emit(self.ctx, C.c_void_p(V.data_ptr()), C.c_void_p(N.data_ptr()),
-                                               C.c_void_p(T.data_ptr()), V.shape[0], T.shape[0]))
+        V, N, T, cnt = self._extract_rows(iso, rng)
         P = None
         if with_property:
             P = torch.empty((max(cnt.nV, 1),), dtype=torch.float32, device=self.device)
@@ -661,29 +663,16 @@ class DeviceGrid:
     def component_topology(self, T, nV, labels=None):
         """The same counts per component, with euler and genus (-1: not defined) - the rows of measure_components, in ascending
         order of root - as a numpy structured array; labels: what label_components returned for T (made here when None)."""
-        import numpy as np
         self._triangle_rows(T)
         if labels is None:
             labels = self.label_components(T, nV)[0]
         assert labels.is_cuda and labels.is_contiguous() and labels.numel() == int(nV) and labels.element_size() == 4
-        args = (self.ctx, C.c_void_p(T.data_ptr()), T.shape[0], int(nV), C.c_void_p(labels.data_ptr()))
-        n = C.c_ulonglong()
-        _check(self.lib, self.lib.mc33hip_component_topology(*args, None, 0, C.byref(n)), allow=(ECAPACITY,))
-        table = np.zeros(n.value, dtype=np.dtype(ComponentTopology))
-        if n.value:
-            _check(self.lib, self.lib.mc33hip_component_topology(*args, C.c_void_p(table.ctypes.data), n.value, C.byref(n)))
-        return table
+        return self._component_table(self.lib.mc33hip_component_topology, ComponentTopology,
+                                     C.c_void_p(T.data_ptr()), T.shape[0], int(nV), C.c_void_p(labels.data_ptr()))
 
     def topology_iso(self, iso, rng=None):
         """Count, emit into torch tensors, topology - nothing but the result crosses the link."""
-        import torch
-        rng = rng or self.full_range()
-        cnt = self.count(iso, rng)
-        V = torch.empty((max(cnt.nV, 1), 3), dtype=torch.float64 if self.dtype == "f64" else torch.float32, device=self.device)
-        N = torch.empty((max(cnt.nV, 1), 3), dtype=torch.float32, device=self.device)
-        T = torch.empty((max(cnt.nT, 1), 3), dtype=torch.int32, device=self.device)
-        _check(self.lib, self.lib.mc33hip_emit(self.ctx, C.c_void_p(V.data_ptr()), C.c_void_p(N.data_ptr()),
-                                               C.c_void_p(T.data_ptr()), V.shape[0], T.shape[0]))
+        V, N, T, cnt = self._extract_rows(iso, rng)
         t = Topology()
         _check(self.lib, self.lib.mc33hip_surface_topology(self.ctx, C.c_void_p(T.data_ptr()), cnt.nT, cnt.nV, C.byref(t)))
         return SurfaceTopology(t)
@@ -707,6 +696,31 @@ class DeviceGrid:
             raise ValueError("MC33_select_components refused its arguments (closed_only needs topo_table)")
         return roots[:n].copy()
 
+    def _attribute_words(self, attrs, nV):
+        """attrs as a tuple, each asserted to be a contiguous device tensor of one 4-byte word per vertex"""
+        attrs = tuple(attrs)
+        for x in attrs:
+            assert x.is_cuda and x.is_contiguous() and x.numel() == nV and x.element_size() == 4, "an attribute is one 4-byte word per vertex"
+        return attrs
+
+    def _into_new_rows(self, fn, a, normals, vdtype, attrs):
+        """A mesh pass with outputs of its own (fn: the library's function, a: its argument struct with the inputs filled in): the
+        size query - null outputs, which the library refuses for room -, exact-size outputs from torch (one row at least), the
+        call proper.  Returns (V2, N2, T2, attrs2, vmap) cut to a.nV_out / a.nT_out rows; N2 None unless `normals`."""
+        import torch
+        _check(self.lib, fn(self.ctx, C.byref(a)), allow=(ECAPACITY,))
+        nV, nV2, nT2 = int(a.nV), int(a.nV_out), int(a.nT_out)
+        V2 = torch.empty((max(nV2, 1), 3), dtype=vdtype, device=self.device)
+        N2 = torch.empty((max(nV2, 1), 3), dtype=torch.float32, device=self.device) if normals else None
+        T2 = torch.empty((max(nT2, 1), 3), dtype=torch.int32, device=self.device)
+        attrs2 = [torch.empty((max(nV2, 1),), dtype=x.dtype, device=self.device) for x in attrs]
+        vmap = torch.empty((max(nV, 1),), dtype=torch.int32, device=self.device)
+        a.oV, a.oT, a.oN, a.oMap, a.capV, a.capT = V2.data_ptr(), T2.data_ptr(), (N2.data_ptr() if normals else None), vmap.data_ptr(), nV2, nT2
+        for k, x in enumerate(attrs2):
+            a.oAttr[k] = x.data_ptr()
+        _check(self.lib, fn(self.ctx, C.byref(a)))
+        return V2[:nV2], (N2[:nV2] if normals else None), T2[:nT2], [x[:nV2] for x in attrs2], vmap[:nV]
+
     def compact_components(self, V, N, T, labels, roots, invert=False, attrs=()):
         """Keeps the components of the mesh V, N, T (device tensors, as extract() returns them) whose root is in `roots` - or, with
         invert, all others - and drops every vertex no triangle names: (V2, N2, T2, attrs2, vmap, components_kept), exact-size
@@ -720,9 +734,7 @@ class DeviceGrid:
         nV = V.shape[0]
         assert N.is_cuda and N.is_contiguous() and N.dtype == torch.float32 and tuple(N.shape) == (nV, 3)
         assert labels.is_cuda and labels.is_contiguous() and labels.numel() == nV and labels.element_size() == 4
-        attrs = tuple(attrs)
-        for a in attrs:
-            assert a.is_cuda and a.is_contiguous() and a.numel() == nV and a.element_size() == 4, "an attribute is one 4-byte word per vertex"
+        attrs = self._attribute_words(attrs, nV)
         roots = np.ascontiguousarray(np.asarray(roots).reshape(-1), dtype=np.uint32)
         a = Compaction()
         a.V, a.N, a.T, a.label, a.nV, a.nT = V.data_ptr(), N.data_ptr(), T.data_ptr(), labels.data_ptr(), nV, T.shape[0]
@@ -730,18 +742,7 @@ class DeviceGrid:
             a.attr[k] = x.data_ptr()
         a.n_attr, a.invert = len(attrs), int(bool(invert))
         a.roots, a.n_roots = (roots.ctypes.data if roots.size else None), roots.size
-        _check(self.lib, self.lib.mc33hip_compact_components(self.ctx, C.byref(a)), allow=(ECAPACITY,))  # null outputs: the size query
-        nV2, nT2 = int(a.nV_out), int(a.nT_out)
-        V2 = torch.empty((max(nV2, 1), 3), dtype=V.dtype, device=self.device)
-        N2 = torch.empty((max(nV2, 1), 3), dtype=torch.float32, device=self.device)
-        T2 = torch.empty((max(nT2, 1), 3), dtype=torch.int32, device=self.device)
-        attrs2 = [torch.empty((max(nV2, 1),), dtype=x.dtype, device=self.device) for x in attrs]
-        vmap = torch.empty((max(nV, 1),), dtype=torch.int32, device=self.device)
-        a.oV, a.oN, a.oT, a.oMap, a.capV, a.capT = V2.data_ptr(), N2.data_ptr(), T2.data_ptr(), vmap.data_ptr(), nV2, nT2
-        for k, x in enumerate(attrs2):
-            a.oAttr[k] = x.data_ptr()
-        _check(self.lib, self.lib.mc33hip_compact_components(self.ctx, C.byref(a)))
-        return V2[:nV2], N2[:nV2], T2[:nT2], [x[:nV2] for x in attrs2], vmap[:nV], int(a.components_kept)
+        return self._into_new_rows(self.lib.mc33hip_compact_components, a, True, V.dtype, attrs) + (int(a.components_kept),)
 
     def extract_filtered(self, iso, rng=None, with_property=False, **criteria):
         """extract, label, measure (and component_topology, only for closed_only), select_components(**criteria), compact - the
@@ -817,13 +818,10 @@ class DeviceGrid:
         output (None with normals=False); attrs: up to two device tensors of one 4-byte word per vertex, the word of a cell's first
         vertex is kept; vmap int32 [n], the uint32 words of the new index, 0xFFFFFFFF where the vertex left - and a dict of the
         call's counts and `ratio`, output over input triangles.  Raises MC33Error(ERUNTIME) when a triangle names a vertex >= n."""
-        import torch
         self._vertex_rows(V)
         self._triangle_rows(T)
         nV = V.shape[0]
-        attrs = tuple(attrs)
-        for x in attrs:
-            assert x.is_cuda and x.is_contiguous() and x.numel() == nV and x.element_size() == 4, "an attribute is one 4-byte word per vertex"
+        attrs = self._attribute_words(attrs, nV)
         cell = (float(cell),) * 3 if not hasattr(cell, "__len__") else tuple(float(x) for x in cell)
         origin = tuple(self.desc.r0) if origin is None else tuple(float(x) for x in origin)
         a = Simplification()
@@ -833,21 +831,11 @@ class DeviceGrid:
         a.n_attr = len(attrs)
         a.origin, a.cell = (C.c_double * 3)(*origin), (C.c_double * 3)(*cell)
         a.mode, a.drop_duplicates = SIMPLIFY_MODES[mode], int(bool(drop_duplicates))
-        _check(self.lib, self.lib.mc33hip_simplify_surface(self.ctx, C.byref(a)), allow=(ECAPACITY,))  # null outputs: the size query
-        nV2, nT2 = int(a.nV_out), int(a.nT_out)
-        V2 = torch.empty((max(nV2, 1), 3), dtype=V.dtype, device=self.device)
-        N2 = torch.empty((max(nV2, 1), 3), dtype=torch.float32, device=self.device) if normals else None
-        T2 = torch.empty((max(nT2, 1), 3), dtype=torch.int32, device=self.device)
-        attrs2 = [torch.empty((max(nV2, 1),), dtype=x.dtype, device=self.device) for x in attrs]
-        vmap = torch.empty((max(nV, 1),), dtype=torch.int32, device=self.device)
-        a.oV, a.oT, a.oN, a.oMap, a.capV, a.capT = V2.data_ptr(), T2.data_ptr(), (N2.data_ptr() if normals else None), vmap.data_ptr(), nV2, nT2
-        for k, x in enumerate(attrs2):
-            a.oAttr[k] = x.data_ptr()
-        _check(self.lib, self.lib.mc33hip_simplify_surface(self.ctx, C.byref(a)))
+        out = self._into_new_rows(self.lib.mc33hip_simplify_surface, a, normals, V.dtype, attrs)
         info = {n: int(getattr(a, n)) for n in ("nV_out", "nT_out", "clusters", "max_cluster", "collapsed_triangles", "duplicate_triangles",
                                                 "invalid_triangles", "clamped_vertices")}
-        info["ratio"] = nT2 / T.shape[0] if T.shape[0] else 0.0
-        return V2[:nV2], (N2[:nV2] if normals else None), T2[:nT2], [x[:nV2] for x in attrs2], vmap[:nV], info
+        info["ratio"] = info["nT_out"] / T.shape[0] if T.shape[0] else 0.0
+        return out + (info,)
 
     def extract_simplified(self, iso, cell_in_grid_cells, rng=None, with_property=False, **kw):
         """extract, then simplify on the lattice of the grid - origin r0, cells of cell_in_grid_cells (a number or three) grid
@@ -875,9 +863,7 @@ class DeviceGrid:
         nV = V.shape[0]
         if N is not None:
             assert N.is_cuda and N.is_contiguous() and N.dtype == torch.float32 and tuple(N.shape) == (nV, 3)
-        attrs = tuple(attrs)
-        for x in attrs:
-            assert x.is_cuda and x.is_contiguous() and x.numel() == nV and x.element_size() == 4, "an attribute is one 4-byte word per vertex"
+        attrs = self._attribute_words(attrs, nV)
         modes = [CLIP_MODES[m] if isinstance(m, str) else int(m) for m in attr_modes] + [0] * (len(attrs) - len(attr_modes))
         a = Clipping()
         a.V, a.N, a.T, a.nV, a.nT = V.data_ptr(), (N.data_ptr() if N is not None else None), T.data_ptr(), nV, T.shape[0]
@@ -885,19 +871,8 @@ class DeviceGrid:
             a.attr[k], a.attr_mode[k] = x.data_ptr(), modes[k]
         a.n_attr = len(attrs)
         a.plane = (C.c_double * 4)(*[float(x) for x in plane])
-        _check(self.lib, self.lib.mc33hip_clip_surface(self.ctx, C.byref(a)), allow=(ECAPACITY,))  # null outputs: the size query
-        nV2, nT2 = int(a.nV_out), int(a.nT_out)
-        V2 = torch.empty((max(nV2, 1), 3), dtype=V.dtype, device=self.device)
-        N2 = torch.empty((max(nV2, 1), 3), dtype=torch.float32, device=self.device) if N is not None else None
-        T2 = torch.empty((max(nT2, 1), 3), dtype=torch.int32, device=self.device)
-        attrs2 = [torch.empty((max(nV2, 1),), dtype=x.dtype, device=self.device) for x in attrs]
-        vmap = torch.empty((max(nV, 1),), dtype=torch.int32, device=self.device)
-        a.oV, a.oT, a.oN, a.oMap, a.capV, a.capT = V2.data_ptr(), T2.data_ptr(), (N2.data_ptr() if N is not None else None), vmap.data_ptr(), nV2, nT2
-        for k, x in enumerate(attrs2):
-            a.oAttr[k] = x.data_ptr()
-        _check(self.lib, self.lib.mc33hip_clip_surface(self.ctx, C.byref(a)))
-        info = {n: int(getattr(a, n)) for n in CLIP_COUNTS}
-        return V2[:nV2], (N2[:nV2] if N is not None else None), T2[:nT2], [x[:nV2] for x in attrs2], vmap[:nV], info
+        out = self._into_new_rows(self.lib.mc33hip_clip_surface, a, N is not None, V.dtype, attrs)
+        return out + ({n: int(getattr(a, n)) for n in CLIP_COUNTS},)
 
     def extract_clipped(self, iso, planes, rng=None, with_property=False):
         """extract, then clip by every plane of `planes` (4-tuples a, b, c, w; clip_box(lo, hi) makes the six of a box) one after

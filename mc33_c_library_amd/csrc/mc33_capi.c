@@ -262,41 +262,58 @@ static int g_objects; /* MC33 objects alive (the host block cache is trimmed whe
 static void cache_trim(size_t keep);
 static size_t cache_limit(int *is_set);
 
-MC33 *create_MC33(_GRD *G) {
-	if (!G || !G->F)
-		return 0;
+/* A new private object for a grid of nx x ny x nz cells at r0 with spacing d - A, Ai: the cell matrices of an inclined grid (nine
+ * doubles each, row major), or null: the public sizes, O and D, the matrices MC33_spnC multiplies with or ca / cb, and one more
+ * object alive.  free_MC33 is what undoes it.  NULL without memory. */
+static mc33_private *new_object(unsigned nx, unsigned ny, unsigned nz, const double *r0, const double *d, const double *A, const double *Ai) {
 	mc33_private *p = (mc33_private *)calloc(1, sizeof *p);
 	if (!p)
 		return 0;
 	p->magic = MC33_MAGIC;
 	MC33 *M = &p->pub;
-	M->nx = G->N[0]; M->ny = G->N[1]; M->nz = G->N[2];
-	M->F = (const GRD_data_type ***)G->F;
+	M->nx = nx; M->ny = ny; M->nz = nz;
 	for (int j = 0; j != 3; j++) { /* MC:1779-1782 */
-		M->O[j] = (MC33_real)G->r0[j];
-		M->D[j] = (MC33_real)G->d[j];
-		p->grd_r0[j] = G->r0[j]; p->grd_d[j] = G->d[j];
+		M->O[j] = (MC33_real)r0[j];
+		M->D[j] = (MC33_real)d[j];
+		p->grd_r0[j] = r0[j]; p->grd_d[j] = d[j];
 	}
 #ifndef GRD_ORTHOGONAL
-	if (G->nonortho) { /* MC:1763-1770: the matrices MC33_spnC multiplies with */
+	if (A) { /* MC:1763-1770 */
 		for (int j = 0; j != 3; j++)
 			for (int i = 0; i != 3; i++) {
-				M->_A[j][i] = G->_A[j][i] * G->d[i];
-				M->A_[j][i] = G->A_[j][i] / G->d[j];
+				M->_A[j][i] = A[3 * j + i] * d[i];
+				M->A_[j][i] = Ai[3 * j + i] / d[j];
 			}
 		p->inclined = 1;
-		memcpy(p->grd_A, G->_A, sizeof p->grd_A);
-		memcpy(p->grd_Ai, G->A_, sizeof p->grd_Ai);
+		memcpy(p->grd_A, A, sizeof p->grd_A);
+		memcpy(p->grd_Ai, Ai, sizeof p->grd_Ai);
 	} else
+#else
+	(void)A; (void)Ai;
 #endif
-	if (G->d[0] != G->d[1] || G->d[1] != G->d[2]) { /* MC:1772-1775 */
-		M->ca = (MC33_real)(G->d[2] / G->d[0]);
-		M->cb = (MC33_real)(G->d[2] / G->d[1]);
+	if (d[0] != d[1] || d[1] != d[2]) { /* MC:1772-1775 */
+		M->ca = (MC33_real)(d[2] / d[0]);
+		M->cb = (MC33_real)(d[2] / d[1]);
 	}
+	__atomic_add_fetch(&g_objects, 1, __ATOMIC_RELAXED);
+	return p;
+}
+
+MC33 *create_MC33(_GRD *G) {
+	if (!G || !G->F)
+		return 0;
+	const double *A = 0, *Ai = 0;
+#ifndef GRD_ORTHOGONAL
+	if (G->nonortho) { A = &G->_A[0][0]; Ai = &G->A_[0][0]; }
+#endif
+	mc33_private *p = new_object(G->N[0], G->N[1], G->N[2], G->r0, G->d, A, Ai);
+	if (!p)
+		return 0;
+	MC33 *M = &p->pub;
+	M->F = (const GRD_data_type ***)G->F;
 	const char *e = getenv("MC33_HIP_REUPLOAD");
 	p->reupload = e && *e && *e != '0';
 	p->grid = G;
-	__atomic_add_fetch(&g_objects, 1, __ATOMIC_RELAXED);
 	int dev[MC33_MAX_DEVICES];
 	int n = parse_devices(dev);
 	if (G->N[0] < 1 || G->N[1] < 1 || G->N[2] < 1 || n < 0) {
@@ -531,16 +548,22 @@ static int extract_geometry(mc33_private *p, struct staging *g, MC33_real iso, m
 	return rc;
 }
 
-/* GPU part of one surface of calculate_isosurfaces: extract_geometry, and the colours where they come from the device */
-static int extract_to_staging(mc33_private *p, struct staging *g, MC33_real iso, mc33hip_counts *cnt) {
-	mc33_slab *s = &p->slab[0];
+/* extract_geometry, and behind it the colours of the vertices into the set where they come from the device (enqueued only): the
+ * grey for a NaN is the DefaultColorMC of this moment */
+static int extract_coloured(mc33_private *p, struct staging *g, MC33_real iso, mc33hip_counts *cnt) {
 	int rc = extract_geometry(p, g, iso, cnt);
-	if (rc == MC33HIP_OK && coloured(p) && cnt->nV) { /* the colours into the set as well, complete like its other arrays */
+	if (rc == MC33HIP_OK && coloured(p) && cnt->nV) {
 		p->nan_color = DefaultColorMC;
-		rc = enqueue_colors(s, g, cnt->nV);
-		if (rc == MC33HIP_OK)
-			rc = mc33hip_synchronize(s->ctx);
+		rc = enqueue_colors(&p->slab[0], g, cnt->nV);
 	}
+	return rc;
+}
+
+/* GPU part of one surface of calculate_isosurfaces: extract_coloured, the colours complete like the set's other arrays */
+static int extract_to_staging(mc33_private *p, struct staging *g, MC33_real iso, mc33hip_counts *cnt) {
+	int rc = extract_coloured(p, g, iso, cnt);
+	if (rc == MC33HIP_OK && coloured(p) && cnt->nV)
+		rc = mc33hip_synchronize(p->slab[0].ctx);
 	return rc;
 }
 
@@ -819,6 +842,15 @@ static void *slab_emit(void *arg) {
 	return 0;
 }
 
+/* mirror of the copy MC:1873 makes into the MC33 object's public prefix; an empty surface leaves the prefix as it is */
+static surface *publish(MC33 *M, surface *S) {
+	if (S->nV) {
+		M->T = S->T; M->V = S->V; M->N = S->N; M->color = S->color;
+		M->nT = S->nT; M->capt = S->capt; M->capv = S->capv;
+	}
+	return S;
+}
+
 /* MC:1816-1889.  Count on every slab (one, unless MC33_HIP_DEVICES names several devices) -> the sizes of the surface and where
  * each slab's part begins -> the caller's arrays (recycled blocks, see above) -> every slab emits its vertices and triangles at
  * its global base and copies them straight to their place in those arrays, each array as soon as the passes that write it are
@@ -877,11 +909,7 @@ surface *calculate_isosurface(MC33 *M, MC33_real iso) {
 		M->memoryfault = 1;
 		return 0;
 	}
-	if (S->nV) { /* mirror of the copy MC:1873 makes into the MC33 object's public prefix */
-		M->T = S->T; M->V = S->V; M->N = S->N; M->color = S->color;
-		M->nT = S->nT; M->capt = S->capt; M->capv = S->capv;
-	}
-	return S;
+	return publish(M, S);
 }
 
 /* --- extension: several isovalues of the resident grid ---------------------------------------------------- */
@@ -965,15 +993,89 @@ unsigned int calculate_isosurfaces(MC33 *M, const MC33_real *iso, unsigned int n
 	return done;
 }
 
-/* --- extension: measures of an isosurface, taken on the device ----------------------------------------------------------------
- * The surface goes into staging set 0 - count, grow, emit, without the colour pass - and is measured there. */
-static mc33_private *measurable(MC33 *M) {
+/* --- the extensions that work on an extracted surface: what they share -----------------------------------------------------------
+ * The gate of every one of them: M's private object when it is live and on one slab and `have` - the caller's own "the device
+ * layer has these weak entry points" - holds; otherwise null, and the caller refuses without having touched M or the device. */
+static mc33_private *one_slab(MC33 *M, int have) {
 	mc33_private *p = priv(M);
-	if (!p || p->nslab != 1 || !mc33hip_measure_surface || !mc33hip_label_components || !mc33hip_measure_components || !mc33hip_sample_property)
+	return p && p->nslab == 1 && have ? p : 0;
+}
+#define MEASURE_ENTRIES (mc33hip_measure_surface && mc33hip_label_components && mc33hip_measure_components && mc33hip_sample_property)
+#define TOPOLOGY_ENTRIES (mc33hip_surface_topology && mc33hip_component_topology && mc33hip_label_components)
+
+/* The frame of a call that returns a derived surface, once its arguments have passed: the public counts reset as calculate_isosurface
+ * resets them, the part's worker, then memoryfault for a NULL or the public prefix for a surface. */
+typedef surface *derived_worker(mc33_private *p, MC33_real iso, const void *arg);
+static surface *derived_call(mc33_private *p, MC33_real iso, derived_worker *worker, const void *arg) {
+	MC33 *M = &p->pub;
+	M->nT = M->nV = 0;
+	M->memoryfault = 0;
+	M->iso = iso;
+	surface *S = worker(p, iso, arg);
+	if (!S) {
+		M->memoryfault = 1;
 		return 0;
-	return p;
+	}
+	return publish(M, S);
 }
 
+/* A mesh pass that writes a new V, N, T - `call`, whose argument struct `a` names its outputs as the other two do - into staging
+ * set h: first with the set as it stands, and when that is refused for room, once more with the set grown to the sizes that came
+ * back (MC33HIP_ENOMEM when it cannot grow).  Where an attribute rides along the colour array grows too, and the vertex capacity
+ * is the smaller of capV and capC.  (oAttr[0] is set for every pass; the device layer reads n_attr of them.) */
+#define INTO_STAGING(rc, call, s, h, a) \
+	do { \
+		(rc) = MC33HIP_ECAPACITY; \
+		for (int attempt = 0; attempt != 2 && (rc) == MC33HIP_ECAPACITY; attempt++) { \
+			if (attempt && (staging_room(s, h, (a).nV_out, (a).nT_out) || ((a).n_attr && dev_room((s)->ctx, &(h)->dC, &(h)->capC, (a).nV_out, sizeof(int))))) { \
+				(rc) = MC33HIP_ENOMEM; \
+				break; \
+			} \
+			(a).oV = (h)->dV; (a).oN = (h)->dN; (a).oT = (h)->dT; (a).oAttr[0] = (h)->dC; \
+			(a).capV = (a).n_attr && (h)->capC < (h)->capV ? (h)->capC : (h)->capV; \
+			(a).capT = (h)->capT; \
+			(rc) = call((s)->ctx, &(a)); \
+		} \
+	} while (0)
+
+/* nV vertices and nT triangles of staging set g into a caller-owned surface */
+static surface *surface_of_rows(mc33_private *p, const struct staging *g, unsigned long long nV, unsigned long long nT, MC33_real iso) {
+	mc33hip_counts out;
+	memset(&out, 0, sizeof out);
+	out.nV = nV; out.nT = nT;
+	return surface_from_staging(p, g, &out, iso, 0);
+}
+
+/* The surface of `iso` into staging set 0 - with its colours, when `colours` - and the component labels of its vertices into p->dL:
+ * the sizes in *cnt, the components in *nc, the vertices no triangle names in *nu.  0, or -1. */
+static int extract_labelled(mc33_private *p, MC33_real iso, int colours, mc33hip_counts *cnt, unsigned long long *nc, unsigned long long *nu) {
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0];
+	*nc = *nu = 0;
+	if ((colours ? extract_coloured(p, g, iso, cnt) : extract_geometry(p, g, iso, cnt)) != MC33HIP_OK)
+		return -1;
+	if (dev_room(s->ctx, &p->dL, &p->capL, cnt->nV, sizeof(unsigned)))
+		return -1;
+	return mc33hip_label_components(s->ctx, g->dT, cnt->nT, cnt->nV, (unsigned *)p->dL, nc, nu) == MC33HIP_OK ? 0 : -1;
+}
+
+/* ... for a call that fills a table of `capacity` rows: the counts reported where asked for.  Positive: the rows are to be made.
+ * Zero or negative: the call is over and returns this (0: no component, -1: failed, -2: the table is too small). */
+static int labelled_for_table(mc33_private *p, MC33_real iso, unsigned capacity, unsigned *components, unsigned *unreferenced, mc33hip_counts *cnt,
+                              unsigned long long *nc) {
+	unsigned long long nu;
+	p->pub.iso = iso;
+	if (extract_labelled(p, iso, 0, cnt, nc, &nu))
+		return -1;
+	if (components) *components = (unsigned)*nc;
+	if (unreferenced) *unreferenced = (unsigned)nu;
+	if (capacity < *nc)
+		return -2;
+	return *nc != 0;
+}
+
+/* --- extension: measures of an isosurface, taken on the device ----------------------------------------------------------------
+ * The surface goes into staging set 0 - count, grow, emit, without the colour pass - and is measured there. */
 static int measure_one(mc33_private *p, MC33_real iso, mc33_measure *out) {
 	mc33_slab *s = &p->slab[0];
 	struct staging *g = &s->set[0];
@@ -1003,14 +1105,14 @@ static int measure_one(mc33_private *p, MC33_real iso, mc33_measure *out) {
 }
 
 int MC33_measure_isosurface(MC33 *M, MC33_real iso, mc33_measure *out) {
-	mc33_private *p = measurable(M);
+	mc33_private *p = one_slab(M, MEASURE_ENTRIES);
 	if (!p || !out)
 		return -1;
 	return measure_one(p, iso, out);
 }
 
 unsigned MC33_measure_isosurfaces(MC33 *M, const MC33_real *iso, unsigned count, mc33_measure *out) {
-	mc33_private *p = measurable(M);
+	mc33_private *p = one_slab(M, MEASURE_ENTRIES);
 	unsigned done = 0;
 	if (!out)
 		return 0;
@@ -1031,7 +1133,7 @@ unsigned MC33_measure_isosurfaces(MC33 *M, const MC33_real *iso, unsigned count,
 }
 
 int MC33_measure_components(MC33 *M, MC33_real iso, mc33_component *table, unsigned capacity, unsigned *components, unsigned *unreferenced) {
-	mc33_private *p = measurable(M);
+	mc33_private *p = one_slab(M, MEASURE_ENTRIES);
 	if (components) *components = 0;
 	if (unreferenced) *unreferenced = 0;
 	if (!p || (capacity && !table))
@@ -1039,31 +1141,16 @@ int MC33_measure_components(MC33 *M, MC33_real iso, mc33_component *table, unsig
 	mc33_slab *s = &p->slab[0];
 	struct staging *g = &s->set[0];
 	mc33hip_counts cnt;
-	M->iso = iso;
-	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK || dev_room(s->ctx, &p->dL, &p->capL, cnt.nV, sizeof(unsigned)))
-		return -1;
-	unsigned long long nc = 0, nu = 0;
-	if (mc33hip_label_components(s->ctx, g->dT, cnt.nT, cnt.nV, (unsigned *)p->dL, &nc, &nu) != MC33HIP_OK)
-		return -1;
-	if (components) *components = (unsigned)nc;
-	if (unreferenced) *unreferenced = (unsigned)nu;
-	if (capacity < nc)
-		return -2;
-	if (!nc)
-		return 0;
+	unsigned long long nc;
+	const int r = labelled_for_table(p, iso, capacity, components, unreferenced, &cnt, &nc);
+	if (r <= 0) /* the call's own result: failed, table too small, or no component */
+		return r;
 	return mc33hip_measure_components(s->ctx, g->dV, cnt.nV, g->dT, cnt.nT, (const unsigned *)p->dL, (mc33hip_component *)table, capacity, &nc) == MC33HIP_OK ? 0 : -1;
 }
 
 /* --- extension: topology of an isosurface, from its triangle list in staging set 0 ------------------------------------------ */
-static mc33_private *topology_capable(MC33 *M) {
-	mc33_private *p = priv(M);
-	if (!p || p->nslab != 1 || !mc33hip_surface_topology || !mc33hip_component_topology || !mc33hip_label_components)
-		return 0;
-	return p;
-}
-
 int MC33_isosurface_topology(MC33 *M, MC33_real iso, mc33_topology *out) {
-	mc33_private *p = topology_capable(M);
+	mc33_private *p = one_slab(M, TOPOLOGY_ENTRIES);
 	if (!p || !out)
 		return -1;
 	mc33_slab *s = &p->slab[0];
@@ -1084,24 +1171,17 @@ int MC33_isosurface_topology(MC33 *M, MC33_real iso, mc33_topology *out) {
 }
 
 int MC33_component_topology(MC33 *M, MC33_real iso, mc33_component_topology *table, unsigned capacity, unsigned *components) {
-	mc33_private *p = topology_capable(M);
+	mc33_private *p = one_slab(M, TOPOLOGY_ENTRIES);
 	if (components) *components = 0;
 	if (!p || (capacity && !table))
 		return -1;
 	mc33_slab *s = &p->slab[0];
 	struct staging *g = &s->set[0];
 	mc33hip_counts cnt;
-	M->iso = iso;
-	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK || dev_room(s->ctx, &p->dL, &p->capL, cnt.nV, sizeof(unsigned)))
-		return -1;
-	unsigned long long nc = 0, nu = 0;
-	if (mc33hip_label_components(s->ctx, g->dT, cnt.nT, cnt.nV, (unsigned *)p->dL, &nc, &nu) != MC33HIP_OK)
-		return -1;
-	if (components) *components = (unsigned)nc;
-	if (capacity < nc)
-		return -2;
-	if (!nc)
-		return 0;
+	unsigned long long nc;
+	const int r = labelled_for_table(p, iso, capacity, components, 0, &cnt, &nc);
+	if (r <= 0) /* the call's own result: failed, table too small, or no component */
+		return r;
 	/* (mc33_component_topology has the members of struct mc33hip_component_topology, in its order) */
 	return mc33hip_component_topology(s->ctx, g->dT, cnt.nT, cnt.nV, (const unsigned *)p->dL, (struct mc33hip_component_topology *)table, capacity, &nc) == MC33HIP_OK ? 0 : -1;
 }
@@ -1146,22 +1226,18 @@ int MC33_select_components(const mc33_component *table, const mc33_component_top
 
 /* the surface of `iso` into staging set 0, its colours, labels, tables -> the roots to keep -> compacted into staging set 1 ->
  * the kept rows into a caller-owned surface */
-static surface *filtered_surface(mc33_private *p, MC33_real iso, const mc33_component_filter *f, unsigned *kept, unsigned *dropped) {
+struct filter_call {
+	const mc33_component_filter *f;
+	unsigned *kept, *dropped;
+};
+static surface *filtered_surface(mc33_private *p, MC33_real iso, const void *arg) {
+	const struct filter_call *fc = (const struct filter_call *)arg;
+	const mc33_component_filter *f = fc->f;
 	mc33_slab *s = &p->slab[0];
 	struct staging *g = &s->set[0], *h = &s->set[1];
 	mc33hip_counts cnt;
-	const int col = coloured(p);
-	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK)
-		return 0;
-	if (col && cnt.nV) {
-		p->nan_color = DefaultColorMC;
-		if (enqueue_colors(s, g, cnt.nV) != MC33HIP_OK)
-			return 0;
-	}
-	if (dev_room(s->ctx, &p->dL, &p->capL, cnt.nV, sizeof(unsigned)))
-		return 0;
-	unsigned long long nc = 0, nu = 0;
-	if (mc33hip_label_components(s->ctx, g->dT, cnt.nT, cnt.nV, (unsigned *)p->dL, &nc, &nu) != MC33HIP_OK)
+	unsigned long long nc, nu;
+	if (extract_labelled(p, iso, 1, &cnt, &nc, &nu))
 		return 0;
 	mc33_component *table = (mc33_component *)malloc((size_t)(nc ? nc : 1) * sizeof *table);
 	mc33_component_topology *topo = f->closed_only ? (mc33_component_topology *)malloc((size_t)(nc ? nc : 1) * sizeof *topo) : 0;
@@ -1180,27 +1256,12 @@ static surface *filtered_surface(mc33_private *p, MC33_real iso, const mc33_comp
 		a.V = g->dV; a.N = g->dN; a.T = g->dT; a.label = (const unsigned *)p->dL;
 		a.nV = cnt.nV; a.nT = cnt.nT;
 		a.roots = roots; a.n_roots = (unsigned long long)nk;
-		if (col && cnt.nV) { a.attr[0] = g->dC; a.n_attr = 1; }
-		int rc = MC33HIP_ECAPACITY;
-		for (int attempt = 0; attempt != 2 && rc == MC33HIP_ECAPACITY; attempt++) { /* with the set as it is; grown to the sizes that came back */
-			if (attempt && (staging_room(s, h, a.nV_out, a.nT_out) || (a.n_attr && dev_room(s->ctx, &h->dC, &h->capC, a.nV_out, sizeof(int))))) {
-				rc = MC33HIP_ENOMEM;
-				break;
-			}
-			a.oV = h->dV; a.oN = h->dN; a.oT = h->dT; a.oAttr[0] = h->dC;
-			a.capV = a.n_attr && h->capC < h->capV ? h->capC : h->capV;
-			a.capT = h->capT;
-			rc = mc33hip_compact_components(s->ctx, &a);
-		}
-		if (rc == MC33HIP_OK) {
-			mc33hip_counts out;
-			memset(&out, 0, sizeof out);
-			out.nV = a.nV_out; out.nT = a.nT_out;
-			S = surface_from_staging(p, h, &out, iso, 0);
-			if (S) {
-				if (kept) *kept = (unsigned)a.components_kept;
-				if (dropped) *dropped = (unsigned)(nc - a.components_kept);
-			}
+		if (coloured(p) && cnt.nV) { a.attr[0] = g->dC; a.n_attr = 1; }
+		int rc;
+		INTO_STAGING(rc, mc33hip_compact_components, s, h, a);
+		if (rc == MC33HIP_OK && (S = surface_of_rows(p, h, a.nV_out, a.nT_out, iso)) != 0) {
+			if (fc->kept) *fc->kept = (unsigned)a.components_kept;
+			if (fc->dropped) *fc->dropped = (unsigned)(nc - a.components_kept);
 		}
 	}
 	free(table); free(topo); free(roots);
@@ -1208,48 +1269,25 @@ static surface *filtered_surface(mc33_private *p, MC33_real iso, const mc33_comp
 }
 
 surface *MC33_calculate_filtered_isosurface(MC33 *M, MC33_real iso, const mc33_component_filter *f, unsigned *kept, unsigned *dropped) {
-	mc33_private *p = priv(M);
+	mc33_private *p = one_slab(M, mc33hip_compact_components && mc33hip_label_components && mc33hip_measure_components && mc33hip_component_topology &&
+	                                  mc33hip_color_vertices);
 	if (kept) *kept = 0;
 	if (dropped) *dropped = 0;
-	if (!p || !f || p->nslab != 1 || !mc33hip_compact_components || !mc33hip_label_components || !mc33hip_measure_components || !mc33hip_component_topology ||
-	    !mc33hip_color_vertices)
+	if (!p || !f)
 		return 0;
-	M->nT = M->nV = 0;
-	M->memoryfault = 0;
-	M->iso = iso;
-	surface *S = filtered_surface(p, iso, f, kept, dropped);
-	if (!S) {
-		M->memoryfault = 1;
-		return 0;
-	}
-	if (S->nV) { /* as calculate_isosurface leaves the public prefix */
-		M->T = S->T; M->V = S->V; M->N = S->N; M->color = S->color;
-		M->nT = S->nT; M->capt = S->capt; M->capv = S->capv;
-	}
-	return S;
+	const struct filter_call fc = {f, kept, dropped};
+	return derived_call(p, iso, filtered_surface, &fc);
 }
 
 /* --- extension: a smoothed isosurface -----------------------------------------------------------------------------------------
  * The surface of `iso` into staging set 0, its colours from the vertices as they were extracted, the Taubin passes in place,
  * the normals from the smoothed positions, then the download: T, nV and nT are those of calculate_isosurface. */
-surface *MC33_calculate_smoothed_isosurface(MC33 *M, MC33_real iso, const mc33_smoothing *sm) {
-	mc33_private *p = priv(M);
-	if (!p || !sm || p->nslab != 1 || !mc33hip_smooth_surface || !mc33hip_color_vertices)
-		return 0;
-	if (!(sm->lambda > 0.0 && sm->lambda <= 1.0) || !(sm->mu >= -1.0 && sm->mu <= 0.0) || sm->iterations > 1000u)
-		return 0; /* (what mc33hip_smooth_surface refuses, before anything is extracted) */
-	M->nT = M->nV = 0;
-	M->memoryfault = 0;
-	M->iso = iso;
+static surface *smoothed_surface(mc33_private *p, MC33_real iso, const void *arg) {
+	const mc33_smoothing *sm = (const mc33_smoothing *)arg;
 	mc33_slab *s = &p->slab[0];
 	struct staging *g = &s->set[0];
 	mc33hip_counts cnt;
-	surface *S = 0;
-	int rc = extract_geometry(p, g, iso, &cnt);
-	if (rc == MC33HIP_OK && coloured(p) && cnt.nV) {
-		p->nan_color = DefaultColorMC;
-		rc = enqueue_colors(s, g, cnt.nV);
-	}
+	int rc = extract_coloured(p, g, iso, &cnt);
 	if (rc == MC33HIP_OK && cnt.nV) {
 		mc33hip_smoothing a;
 		memset(&a, 0, sizeof a);
@@ -1258,17 +1296,16 @@ surface *MC33_calculate_smoothed_isosurface(MC33 *M, MC33_real iso, const mc33_s
 		a.oV = g->dV; a.oN = (float *)g->dN;
 		rc = mc33hip_smooth_surface(s->ctx, &a);
 	}
-	if (rc == MC33HIP_OK)
-		S = surface_from_staging(p, g, &cnt, iso, 0);
-	if (!S) {
-		M->memoryfault = 1;
+	return rc == MC33HIP_OK ? surface_from_staging(p, g, &cnt, iso, 0) : 0;
+}
+
+surface *MC33_calculate_smoothed_isosurface(MC33 *M, MC33_real iso, const mc33_smoothing *sm) {
+	mc33_private *p = one_slab(M, mc33hip_smooth_surface && mc33hip_color_vertices);
+	if (!p || !sm)
 		return 0;
-	}
-	if (S->nV) { /* as calculate_isosurface leaves the public prefix */
-		M->T = S->T; M->V = S->V; M->N = S->N; M->color = S->color;
-		M->nT = S->nT; M->capt = S->capt; M->capv = S->capv;
-	}
-	return S;
+	if (!(sm->lambda > 0.0 && sm->lambda <= 1.0) || !(sm->mu >= -1.0 && sm->mu <= 0.0) || sm->iterations > 1000u)
+		return 0; /* (what mc33hip_smooth_surface refuses, before anything is extracted) */
+	return derived_call(p, iso, smoothed_surface, sm);
 }
 
 /* --- extension: a simplified isosurface ------------------------------------------------------------------------------------------
@@ -1281,62 +1318,31 @@ static int simplification_ok(const mc33_simplification *sp) {
 	return sp->mode == MC33HIP_SIMPLIFY_MEAN || sp->mode == MC33HIP_SIMPLIFY_FIRST;
 }
 
-static surface *simplified_surface(mc33_private *p, MC33_real iso, const mc33_simplification *sp) {
+static surface *simplified_surface(mc33_private *p, MC33_real iso, const void *arg) {
+	const mc33_simplification *sp = (const mc33_simplification *)arg;
 	mc33_slab *s = &p->slab[0];
 	struct staging *g = &s->set[0], *h = &s->set[1];
 	mc33hip_counts cnt;
-	const int col = coloured(p);
-	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK)
+	if (extract_coloured(p, g, iso, &cnt) != MC33HIP_OK)
 		return 0;
-	if (col && cnt.nV) {
-		p->nan_color = DefaultColorMC;
-		if (enqueue_colors(s, g, cnt.nV) != MC33HIP_OK)
-			return 0;
-	}
 	mc33hip_simplification a;
 	memset(&a, 0, sizeof a);
 	a.V = g->dV; a.T = g->dT; a.nV = cnt.nV; a.nT = cnt.nT;
-	if (col && cnt.nV) { a.attr[0] = g->dC; a.n_attr = 1; }
+	if (coloured(p) && cnt.nV) { a.attr[0] = g->dC; a.n_attr = 1; }
 	for (int j = 0; j != 3; j++) { a.origin[j] = p->grd_r0[j]; a.cell[j] = sp->cell[j] * p->grd_d[j]; }
 	a.mode = sp->mode; a.drop_duplicates = sp->drop_duplicates;
-	int rc = MC33HIP_ECAPACITY;
-	for (int attempt = 0; attempt != 2 && rc == MC33HIP_ECAPACITY; attempt++) { /* with the set as it is; grown to the sizes that came back */
-		if (attempt && (staging_room(s, h, a.nV_out, a.nT_out) || (a.n_attr && dev_room(s->ctx, &h->dC, &h->capC, a.nV_out, sizeof(int))))) {
-			rc = MC33HIP_ENOMEM;
-			break;
-		}
-		a.oV = h->dV; a.oN = (float *)h->dN; a.oT = h->dT; a.oAttr[0] = h->dC;
-		a.capV = a.n_attr && h->capC < h->capV ? h->capC : h->capV;
-		a.capT = h->capT;
-		rc = mc33hip_simplify_surface(s->ctx, &a);
-	}
-	if (rc != MC33HIP_OK)
-		return 0;
-	mc33hip_counts out;
-	memset(&out, 0, sizeof out);
-	out.nV = a.nV_out; out.nT = a.nT_out;
-	return surface_from_staging(p, h, &out, iso, 0);
+	int rc;
+	INTO_STAGING(rc, mc33hip_simplify_surface, s, h, a);
+	return rc == MC33HIP_OK ? surface_of_rows(p, h, a.nV_out, a.nT_out, iso) : 0;
 }
 
 surface *MC33_calculate_simplified_isosurface(MC33 *M, MC33_real iso, const mc33_simplification *sp) {
-	mc33_private *p = priv(M);
-	if (!p || !sp || p->nslab != 1 || p->inclined || !mc33hip_simplify_surface || !mc33hip_color_vertices)
+	mc33_private *p = one_slab(M, mc33hip_simplify_surface && mc33hip_color_vertices);
+	if (!p || !sp || p->inclined)
 		return 0;
 	if (!simplification_ok(sp))
 		return 0; /* (what mc33hip_simplify_surface refuses, before anything is extracted) */
-	M->nT = M->nV = 0;
-	M->memoryfault = 0;
-	M->iso = iso;
-	surface *S = simplified_surface(p, iso, sp);
-	if (!S) {
-		M->memoryfault = 1;
-		return 0;
-	}
-	if (S->nV) { /* as calculate_isosurface leaves the public prefix */
-		M->T = S->T; M->V = S->V; M->N = S->N; M->color = S->color;
-		M->nT = S->nT; M->capt = S->capt; M->capv = S->capv;
-	}
-	return S;
+	return derived_call(p, iso, simplified_surface, sp);
 }
 
 /* --- extension: an isosurface clipped by planes --------------------------------------------------------------------------------
@@ -1367,7 +1373,8 @@ int MC33_clip_box(const double lo[3], const double hi[3], mc33_clip *out) {
 	return 0;
 }
 
-static surface *clipped_surface(mc33_private *p, MC33_real iso, const mc33_clip *cl) {
+static surface *clipped_surface(mc33_private *p, MC33_real iso, const void *arg) {
+	const mc33_clip *cl = (const mc33_clip *)arg;
 	mc33_slab *s = &p->slab[0];
 	mc33hip_counts cnt;
 	int cur = 0;
@@ -1379,16 +1386,8 @@ static surface *clipped_surface(mc33_private *p, MC33_real iso, const mc33_clip 
 		memset(&a, 0, sizeof a);
 		a.V = g->dV; a.N = g->dN; a.T = g->dT; a.nV = cnt.nV; a.nT = cnt.nT;
 		for (int j = 0; j != 4; j++) a.plane[j] = cl->plane[k][j];
-		int rc = MC33HIP_ECAPACITY;
-		for (int attempt = 0; attempt != 2 && rc == MC33HIP_ECAPACITY; attempt++) { /* with the set as it is; grown to the sizes that came back */
-			if (attempt && staging_room(s, h, a.nV_out, a.nT_out)) {
-				rc = MC33HIP_ENOMEM;
-				break;
-			}
-			a.oV = h->dV; a.oN = (float *)h->dN; a.oT = h->dT;
-			a.capV = h->capV; a.capT = h->capT;
-			rc = mc33hip_clip_surface(s->ctx, &a);
-		}
+		int rc;
+		INTO_STAGING(rc, mc33hip_clip_surface, s, h, a);
 		if (rc != MC33HIP_OK)
 			return 0;
 		cnt.nV = a.nV_out; cnt.nT = a.nT_out;
@@ -1405,27 +1404,15 @@ static surface *clipped_surface(mc33_private *p, MC33_real iso, const mc33_clip 
 }
 
 surface *MC33_calculate_clipped_isosurface(MC33 *M, MC33_real iso, const mc33_clip *cl) {
-	mc33_private *p = priv(M);
-	if (!p || !cl || p->nslab != 1 || !mc33hip_clip_surface || !mc33hip_color_vertices)
+	mc33_private *p = one_slab(M, mc33hip_clip_surface && mc33hip_color_vertices);
+	if (!p || !cl)
 		return 0;
 	if (cl->n > 6u)
 		return 0;
 	for (unsigned k = 0; k != cl->n; k++)
 		if (!clip_plane_ok(cl->plane[k]))
 			return 0; /* (what mc33hip_clip_surface refuses, before anything is extracted) */
-	M->nT = M->nV = 0;
-	M->memoryfault = 0;
-	M->iso = iso;
-	surface *S = clipped_surface(p, iso, cl);
-	if (!S) {
-		M->memoryfault = 1;
-		return 0;
-	}
-	if (S->nV) { /* as calculate_isosurface leaves the public prefix */
-		M->T = S->T; M->V = S->V; M->N = S->N; M->color = S->color;
-		M->nT = S->nT; M->capt = S->capt; M->capv = S->capv;
-	}
-	return S;
+	return derived_call(p, iso, clipped_surface, cl);
 }
 
 void free_surface_memory(surface *S) { /* MC:84-92 */
@@ -1600,8 +1587,8 @@ static size_t resampled_pitch(size_t npx) {
 }
 
 MC33 *MC33_create_resampled(MC33 *source, const mc33_resampling *r) {
-	mc33_private *sp = priv(source);
-	if (!sp || !r || sp->nslab != 1 || !mc33hip_resampled_size || !mc33hip_resample_grid || !mc33hip_context_device || !mc33hip_adopt_device)
+	mc33_private *sp = one_slab(source, mc33hip_resampled_size && mc33hip_resample_grid && mc33hip_context_device && mc33hip_adopt_device);
+	if (!sp || !r)
 		return 0;
 	double w[3][17];
 	mc33hip_resampling hr;
@@ -1615,35 +1602,13 @@ MC33 *MC33_create_resampled(MC33 *source, const mc33_resampling *r) {
 	mc33_slab *ss = &sp->slab[0];
 	if (mc33hip_resampled_size(ss->ctx, &hr, npo) != MC33HIP_OK) /* (fewer than 2 points left on an axis) */
 		return 0;
-	mc33_private *p = (mc33_private *)calloc(1, sizeof *p);
+	double step[3];
+	for (int j = 0; j != 3; j++) step[j] = sp->grd_d[j] * (double)r->stride[j];
+	/* (an inclined source: the matrices of its _GRD, scaled by the new spacing) */
+	mc33_private *p = new_object(npo[0] - 1u, npo[1] - 1u, npo[2] - 1u, sp->grd_r0, step, sp->inclined ? sp->grd_A : 0, sp->inclined ? sp->grd_Ai : 0);
 	if (!p)
 		return 0;
-	p->magic = MC33_MAGIC;
 	MC33 *M = &p->pub;
-	M->nx = npo[0] - 1u; M->ny = npo[1] - 1u; M->nz = npo[2] - 1u;
-	for (int j = 0; j != 3; j++) {
-		p->grd_r0[j] = sp->grd_r0[j];
-		p->grd_d[j] = sp->grd_d[j] * (double)r->stride[j];
-		M->O[j] = (MC33_real)p->grd_r0[j];
-		M->D[j] = (MC33_real)p->grd_d[j];
-	}
-#ifndef GRD_ORTHOGONAL
-	if (sp->inclined) { /* the matrices of the source's _GRD, scaled by the new spacing (create_MC33) */
-		p->inclined = 1;
-		memcpy(p->grd_A, sp->grd_A, sizeof p->grd_A);
-		memcpy(p->grd_Ai, sp->grd_Ai, sizeof p->grd_Ai);
-		for (int j = 0; j != 3; j++)
-			for (int i = 0; i != 3; i++) {
-				M->_A[j][i] = p->grd_A[3 * j + i] * p->grd_d[i];
-				M->A_[j][i] = p->grd_Ai[3 * j + i] / p->grd_d[j];
-			}
-	} else
-#endif
-	if (p->grd_d[0] != p->grd_d[1] || p->grd_d[1] != p->grd_d[2]) {
-		M->ca = (MC33_real)(p->grd_d[2] / p->grd_d[0]);
-		M->cb = (MC33_real)(p->grd_d[2] / p->grd_d[1]);
-	}
-	__atomic_add_fetch(&g_objects, 1, __ATOMIC_RELAXED);
 	p->nslab = 1;
 	mc33_slab *s = &p->slab[0];
 	s->owner = p;

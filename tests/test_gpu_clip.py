@@ -5,12 +5,11 @@ V, N and T come from the reference twin (oracle/_ref) or are made up (tests/clip
 tests/clip_oracle.py, the definition in numpy.  Everything is compared bit for bit - oV, oN, oT, both attributes, oMap and the ten
 counts; nothing here has a tolerance.  Every output of every call sits in a larger tensor whose spare rows are canaried."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
+from capi_slab_refusals import refusal
 import clip_cases as cc
 import clip_oracle as co
 import fixtures as fx
@@ -22,8 +21,6 @@ from test_clip_cpu import MODES, PLANES, TABLE, CClip, attributes, clipped, plan
 from test_simplify_cpu import mesh
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 SPARE = 16  # canaried rows behind every output
 FILL = 0x55
@@ -556,6 +553,6 @@ def test_c_api_on_an_inclined_grid(reflibs):
 
 
 def test_c_api_refuses_an_object_on_several_slabs(launcher):
-    """MC33_HIP_DEVICES=0,0 in a fresh process, before the library is loaded: two slabs on one device (tests/clip_slab_worker.py)."""
-    out = launcher.run([sys.executable, os.path.join(HERE, "clip_slab_worker.py")], env={"MC33_HIP_DEVICES": "0,0"}, timeout=300)
+    """MC33_HIP_DEVICES=0,0 in a fresh process, before the library is loaded: two slabs on one device (tests/capi_slab_refusals_worker.py)."""
+    out = refusal(launcher, "clip")
     assert out["rc"] == 0 and "refused: 1 0" in out["stdout"], out

@@ -5,13 +5,12 @@ V, N, T come from the reference twin (oracle/_ref) or are synthetic; the expecte
 definition in numpy.  Everything is compared bit for bit - oV, oN, oT, both attributes, oMap and the three counts; nothing here has
 a tolerance.  Every output of every call sits in a larger tensor whose spare rows are canaried."""
 import ctypes as C
-import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
+from capi_slab_refusals import refusal
 import filter_oracle as fo
 import fixtures as fx
 import measure_oracle as mo
@@ -21,7 +20,6 @@ from test_filter_cpu import CFilter, ROWS, SIZED, mesh
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SPARE = 16  # canaried rows behind every output
 FILL = 0x55
 # the rows of the issue's table that a filter struct expresses (the others name their roots)
@@ -506,6 +504,6 @@ def test_c_api_nneg_flavour():
 
 
 def test_c_api_refuses_an_object_on_several_slabs(launcher):
-    """MC33_HIP_DEVICES=0,0 in a fresh process, before the library is loaded: two slabs on one device (tests/filter_slab_worker.py)."""
-    out = launcher.run([sys.executable, os.path.join(HERE, "filter_slab_worker.py")], env={"MC33_HIP_DEVICES": "0,0"}, timeout=300)
+    """MC33_HIP_DEVICES=0,0 in a fresh process, before the library is loaded: two slabs on one device (tests/capi_slab_refusals_worker.py)."""
+    out = refusal(launcher, "filter")
     assert out["rc"] == 0 and "refused: 1 0 0" in out["stdout"], out

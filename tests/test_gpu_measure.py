@@ -6,13 +6,12 @@ expected values come from tests/measure_oracle.py, the definition in numpy float
 must satisfy |got - fsum(x)| <= (n + 8) * 2^-53 * fsum(|x_i|) - a bound that holds for every order of the additions as long as
 they are made in double - integers, labels and the bounding box are compared exactly."""
 import ctypes as C
-import os
 import struct
-import sys
 
 import numpy as np
 import pytest
 
+from capi_slab_refusals import refusal
 import fixtures as fx
 import measure_oracle as mo
 import property_oracle as po
@@ -20,7 +19,6 @@ from mc33_capi import MC33Lib, product_path, ref_path
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 AWKWARD_R0, AWKWARD_D = mo.AWKWARD_R0, mo.AWKWARD_D
 
 
@@ -425,8 +423,8 @@ def test_c_api_nneg_flavour_has_the_opposite_sign():
 
 def test_c_api_refuses_an_object_on_several_slabs(launcher):
     """MC33_HIP_DEVICES=0,0 in a fresh process, before the library is loaded: two slabs on one device, and all three functions
-    return -1 (tests/measure_slab_worker.py)."""
-    out = launcher.run([sys.executable, os.path.join(HERE, "measure_slab_worker.py")], env={"MC33_HIP_DEVICES": "0,0"}, timeout=300)
+    return -1 (tests/capi_slab_refusals_worker.py)."""
+    out = refusal(launcher, "measure")
     assert out["rc"] == 0 and "refused: -1 0 -1" in out["stdout"], out
 
 

@@ -6,12 +6,11 @@ tests/simplify_oracle.py, the definition in numpy, and the normals from tests/sm
 Everything is compared bit for bit - oV, oN, oT, both attributes, oMap and the eight counts; nothing here has a tolerance.  Every
 output of every call sits in a larger tensor whose spare rows are canaried."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
+from capi_slab_refusals import refusal
 import fixtures as fx
 import measure_oracle as mo
 import mesh_pieces as mp
@@ -23,8 +22,6 @@ from mc33_capi import MC33Lib, product_path, ref_path
 from test_simplify_cpu import CELLS, MODES, TABLE, CSimplification, mesh, simplified
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 SPARE = 16  # canaried rows behind every output
 FILL = 0x55
@@ -534,6 +531,6 @@ def test_c_api_refuses_an_inclined_grid():
 
 
 def test_c_api_refuses_an_object_on_several_slabs(launcher):
-    """MC33_HIP_DEVICES=0,0 in a fresh process, before the library is loaded: two slabs on one device (tests/simplify_slab_worker.py)."""
-    out = launcher.run([sys.executable, os.path.join(HERE, "simplify_slab_worker.py")], env={"MC33_HIP_DEVICES": "0,0"}, timeout=300)
+    """MC33_HIP_DEVICES=0,0 in a fresh process, before the library is loaded: two slabs on one device (tests/capi_slab_refusals_worker.py)."""
+    out = refusal(launcher, "simplify")
     assert out["rc"] == 0 and "refused: 1 0" in out["stdout"], out

@@ -5,12 +5,11 @@ V and T come from the reference twin (oracle/_ref) or are synthetic; the expecte
 definition in numpy.  oV and oN are compared bit for bit, the four counts exactly; nothing here has a tolerance.  Every output
 of every call sits in a larger tensor whose spare rows are canaried."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
+from capi_slab_refusals import refusal
 import fixtures as fx
 import measure_oracle as mo
 import property_oracle as po
@@ -20,7 +19,6 @@ from test_smooth_cpu import CSmoothing, TABLE, mesh
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SPARE = 16  # canaried rows behind every output
 FILL = 0x55
 
@@ -410,6 +408,6 @@ def test_c_api_nneg_flavour():
 
 
 def test_c_api_refuses_an_object_on_several_slabs(launcher):
-    """MC33_HIP_DEVICES=0,0 in a fresh process, before the library is loaded: two slabs on one device (tests/smooth_slab_worker.py)."""
-    out = launcher.run([sys.executable, os.path.join(HERE, "smooth_slab_worker.py")], env={"MC33_HIP_DEVICES": "0,0"}, timeout=300)
+    """MC33_HIP_DEVICES=0,0 in a fresh process, before the library is loaded: two slabs on one device (tests/capi_slab_refusals_worker.py)."""
+    out = refusal(launcher, "smooth")
     assert out["rc"] == 0 and "refused: 1 0" in out["stdout"], out

@@ -5,13 +5,12 @@ T always comes from the reference twin (oracle/_ref), which tests/test_gpu_parit
 made up here; the expected figures come from tests/topology_oracle.py, the definition in numpy.  Everything is an integer and
 is compared exactly, field for field and row for row."""
 import ctypes as C
-import os
-import sys
 import time
 
 import numpy as np
 import pytest
 
+from capi_slab_refusals import refusal
 import fixtures as fx
 import measure_oracle as mo
 import topology_oracle as to
@@ -21,7 +20,6 @@ from test_topology_cpu import CComponentTopology, CTopology, bind_topology_api
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 _oracle = {}
 _grid = []
 
@@ -306,6 +304,6 @@ def test_c_api_nneg_flavour_gives_the_same_figures(reflibs, name):
 
 def test_c_api_refuses_an_object_on_several_slabs(launcher):
     """MC33_HIP_DEVICES=0,0 in a fresh process, before the library is loaded: two slabs on one device, and both functions return
-    -1 (tests/topology_slab_worker.py)."""
-    out = launcher.run([sys.executable, os.path.join(HERE, "topology_slab_worker.py")], env={"MC33_HIP_DEVICES": "0,0"}, timeout=300)
+    -1 (tests/capi_slab_refusals_worker.py)."""
+    out = refusal(launcher, "topology")
     assert out["rc"] == 0 and "refused: -1 -1 0" in out["stdout"], out
