@@ -10,18 +10,16 @@ tests/test_gpu_clip.py."""
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import clip_cases as cc
 import clip_oracle as co
-import fixtures as fx
 import measure_oracle as mo
 import topology_oracle as to
-from mc33_capi import MC33Lib, product_path
+from mc33_capi import product_path
+from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets
 from test_mesh_common_cpu import launched
 from test_simplify_cpu import mesh
 
@@ -233,39 +231,20 @@ def test_new_names_are_declared():
 
 @pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
 def test_every_library_exports_the_new_names(dtype):
-    for ortho, nneg in ((False, False), (True, False), (False, True), (True, True)):
-        path = product_path(dtype, ortho=ortho, nneg=nneg)
-        assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
-        syms = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        defined = set(line.split()[-1] for line in syms.splitlines() if line.split())
-        for n in HIP_NAMES + C_NAMES:
-            assert n in defined, "%s not exported by %s" % (n, os.path.basename(path))
+    assert_exported(HIP_NAMES + C_NAMES, dtype)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
 def test_clipping_kernels_are_in_the_code_object(dtype):
-    from test_code_objects import kernel_metadata
     real = "double" if dtype == "f64" else "float"
-    ks = {k["pretty"]: k for k in kernel_metadata(product_path(dtype))}
-    for name in KERNELS + ["k_clip_class<%s>" % real, "k_clip_rows<%s>" % real, "k_clip_new<%s>" % real]:
-        assert name in ks, (name, sorted(ks))
-        assert ks[name]["private_segment_fixed_size"] == 0 and ks[name]["vgpr_spill_count"] == 0, (name, ks[name])
-        assert ks[name]["vgpr_count"] <= 64, (name, ks[name])  # (eight waves per SIMD)
+    assert_kernels(dtype, KERNELS + ["k_clip_class<%s>" % real, "k_clip_rows<%s>" % real, "k_clip_new<%s>" % real])
 
 
 def test_python_structs_match_the_header():
     from mc33_c_library_amd.api import Clipping, SurfaceClip
     members = ["N", "T", "nV", "nT", "attr", "n_attr", "attr_mode", "plane", "oV", "oN", "oT", "oAttr", "oMap", "capV", "capT", "nV_out", "kept_vertices",
                "on_plane_vertices", "nonfinite_vertices"]
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"marching_cubes_33.h\"\n#include \"mc33_hip.h\"\nint main(void) {\n"
-    src += "\tprintf(\"%zu %zu %zu\\n\", sizeof(mc33hip_clipping), sizeof(mc33_clip), offsetof(mc33_clip, plane));\n"
-    for m in members:
-        src += "\tprintf(\"%%zu\\n\", offsetof(mc33hip_clipping, %s));\n" % m
-    src += "\treturn 0;\n}\n"
-    with tempfile.TemporaryDirectory() as tmp:
-        open(os.path.join(tmp, "sizes.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(tmp, "sizes.c"), "-o", os.path.join(tmp, "sizes")])
-        want = [int(x) for x in subprocess.check_output([os.path.join(tmp, "sizes")], text=True).split()]
+    want = c_layout(["sizeof(mc33hip_clipping)", "sizeof(mc33_clip)", "offsetof(mc33_clip, plane)"] + offsets("mc33hip_clipping", members))
     got = [C.sizeof(Clipping), C.sizeof(SurfaceClip), SurfaceClip.plane.offset] + [getattr(Clipping, m).offset for m in members]
     assert got == want
     assert [C.sizeof(CClip), CClip.plane.offset] == want[1:3]
@@ -305,19 +284,12 @@ def test_host_logic_library_refuses_to_clip(dtype):
     MC33_calculate_clipped_isosurface returns NULL and leaves the object alone - for good arguments and, which needs no device
     in any build, for a null struct, too many planes and every refused plane -, MC33_clip_box works, and the object extracts as
     before."""
-    from mc33_emu import build_hostlogic
-    lib = MC33Lib(build_hostlogic(dtype), dtype)
-    L = lib.lib
-    L.MC33_calculate_clipped_isosurface.restype = C.POINTER(lib.SURFACE)
-    L.MC33_calculate_clipped_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CClip)]
-    L.MC33_clip_box.restype = C.c_int
-    L.MC33_clip_box.argtypes = [C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3), C.POINTER(CClip)]
-    data = fx.cos_field(20)[0] if dtype == "f32" else fx.cos_field_u16(20, 20, 20)
-    iso = 0.0 if dtype == "f32" else 30000.0
-    G, keep = lib.make_grid(data)
-    M = L.create_MC33(G)
-    assert M
-    try:
+    with host_logic(dtype) as h:
+        lib, L, M, iso = h.lib, h.L, h.M, h.iso
+        L.MC33_calculate_clipped_isosurface.restype = C.POINTER(lib.SURFACE)
+        L.MC33_calculate_clipped_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CClip)]
+        L.MC33_clip_box.restype = C.c_int
+        L.MC33_clip_box.argtypes = [C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3), C.POINTER(CClip)]
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         before = (M.contents.iso, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V)
@@ -340,7 +312,3 @@ def test_host_logic_library_refuses_to_clip(dtype):
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         L.free_surface_memory(S)
-    finally:
-        L.free_MC33(M)
-        L.free_memory_grd(G)
-        del keep

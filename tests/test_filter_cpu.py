@@ -9,16 +9,15 @@ code-object and host-logic tests below and, on the device, by tests/test_gpu_fil
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import filter_oracle as fo
-import fixtures as fx
 import measure_oracle as mo
 import topology_oracle as to
-from mc33_capi import MC33Lib, product_path
+from mc33_capi import product_path
+from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets, reference_mesh
 from test_mesh_common_cpu import launched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,16 +45,14 @@ _meshes = {}
 def mesh(reflibs, name):
     """the reference's surface of a fixture row with its labels and both component tables, computed once and left unchanged"""
     if name not in _meshes:
-        field, iso, (nV, nT, ncomp, unref, _) = mo.FIXTURES[name]
-        data, r0, d = field()
-        s = reflibs["f32"].isosurface(data, iso, r0, d)
-        assert (s.nV, s.nT) == (nV, nT), "fixture %s drifted: %d vertices, %d triangles" % (name, s.nV, s.nT)
+        data, r0, d, iso, s = reference_mesh(reflibs, name)
+        ncomp, unref = mo.FIXTURES[name][2][2:4]
         lab, gc, gu, _ = mo.label_components(s.T, s.nV)
         assert (gc, gu) == (ncomp, unref)
         c = mo.reference_point(r0, d, data.shape)
         tab = mo.component_table(s.V, s.T, lab, c)[0]
         topo = to.component_table(s.T, s.nV, lab)
-        for a in (s.V, s.N, s.T, lab, tab, topo):
+        for a in (lab, tab, topo):
             a.setflags(write=False)
         _meshes[name] = (data, r0, d, iso, s, lab, tab, topo, c)
     return _meshes[name]
@@ -199,44 +196,18 @@ def test_new_names_are_declared():
 
 @pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
 def test_every_library_exports_the_new_names(dtype):
-    for ortho, nneg in ((False, False), (True, False), (False, True), (True, True)):
-        path = product_path(dtype, ortho=ortho, nneg=nneg)
-        assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
-        syms = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        defined = set(line.split()[-1] for line in syms.splitlines() if line.split())
-        for n in HIP_NAMES + C_NAMES:
-            assert n in defined, "%s not exported by %s" % (n, os.path.basename(path))
+    assert_exported(HIP_NAMES + C_NAMES, dtype)
 
 
 @pytest.mark.parametrize("dtype,real", [("f32", "float"), ("f64", "double")])
 def test_filter_kernels_are_in_the_code_object(dtype, real):
-    from test_code_objects import kernel_metadata
-    ks = {k["pretty"]: k for k in kernel_metadata(product_path(dtype))}
-    for name in KERNELS + ["k_filt_rows<%s>" % real]:
-        assert name in ks, (name, sorted(ks))
-        assert ks[name]["private_segment_fixed_size"] == 0 and ks[name]["vgpr_spill_count"] == 0, (name, ks[name])
-        assert ks[name]["vgpr_count"] <= 64, (name, ks[name])  # (eight waves per SIMD)
+    assert_kernels(dtype, KERNELS + ["k_filt_rows<%s>" % real])
 
 
 def test_python_structs_match_the_header():
     from mc33_c_library_amd.api import Compaction, ComponentFilter
-    src = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "marching_cubes_33.h"
-#include "mc33_hip.h"
-int main(void) {
-	printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(mc33hip_compaction), offsetof(mc33hip_compaction, n_attr), offsetof(mc33hip_compaction, roots),
-	       offsetof(mc33hip_compaction, oMap), offsetof(mc33hip_compaction, components_kept), sizeof(mc33_component_filter),
-	       offsetof(mc33_component_filter, largest), offsetof(mc33_component_filter, closed_only));
-	return 0;
-}
-"""
-    import tempfile
-    with tempfile.TemporaryDirectory() as tmp:
-        open(os.path.join(tmp, "sizes.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(tmp, "sizes.c"), "-o", os.path.join(tmp, "sizes")])
-        want = [int(x) for x in subprocess.check_output([os.path.join(tmp, "sizes")], text=True).split()]
+    want = c_layout(["sizeof(mc33hip_compaction)"] + offsets("mc33hip_compaction", ["n_attr", "roots", "oMap", "components_kept"]) +
+                    ["sizeof(mc33_component_filter)"] + offsets("mc33_component_filter", ["largest", "closed_only"]))
     got = [C.sizeof(Compaction), Compaction.n_attr.offset, Compaction.roots.offset, Compaction.oMap.offset, Compaction.components_kept.offset,
            C.sizeof(ComponentFilter), ComponentFilter.largest.offset, ComponentFilter.closed_only.offset]
     assert got == want
@@ -247,17 +218,10 @@ int main(void) {
 def test_host_logic_library_refuses_to_filter(dtype):
     """mc33_capi.c linked with the emulated device layer, which cannot compact: the library still loads (a weak reference),
     MC33_calculate_filtered_isosurface returns NULL, the selection rule - plain host C - works, and the object extracts as before."""
-    from mc33_emu import build_hostlogic
-    lib = MC33Lib(build_hostlogic(dtype), dtype)
-    L = bind_select(lib.lib)
-    L.MC33_calculate_filtered_isosurface.restype = C.POINTER(lib.SURFACE)
-    L.MC33_calculate_filtered_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CFilter), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
-    data = fx.cos_field(20)[0] if dtype == "f32" else fx.cos_field_u16(20, 20, 20)
-    iso = 0.0 if dtype == "f32" else 30000.0
-    G, keep = lib.make_grid(data)
-    M = L.create_MC33(G)
-    assert M
-    try:
+    with host_logic(dtype) as h:
+        lib, L, M, iso = h.lib, bind_select(h.L), h.M, h.iso
+        L.MC33_calculate_filtered_isosurface.restype = C.POINTER(lib.SURFACE)
+        L.MC33_calculate_filtered_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CFilter), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
         f, k, dr = CFilter(), C.c_uint(7), C.c_uint(7)
         assert not L.MC33_calculate_filtered_isosurface(M, lib.real(iso), C.byref(f), C.byref(k), C.byref(dr)) and (k.value, dr.value) == (0, 0)
         tab = np.zeros(2, mo.COMPONENT)
@@ -266,7 +230,3 @@ def test_host_logic_library_refuses_to_filter(dtype):
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         L.free_surface_memory(S)
-    finally:
-        L.free_MC33(M)
-        L.free_memory_grd(G)
-        del keep

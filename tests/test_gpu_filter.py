@@ -3,7 +3,7 @@ MC33_calculate_filtered_isosurface; DeviceGrid.compact_components / select_compo
 
 V, N, T come from the reference twin (oracle/_ref) or are synthetic; the expected arrays come from tests/filter_oracle.py, the
 definition in numpy.  Everything is compared bit for bit - oV, oN, oT, both attributes, oMap and the three counts; nothing here has
-a tolerance.  Every output of every call sits in a larger tensor whose spare rows are canaried."""
+a tolerance.  Every output of every call is canaried (tests/mesh_harness.py: CanariedCall)."""
 import ctypes as C
 import re
 
@@ -16,61 +16,29 @@ import fixtures as fx
 import measure_oracle as mo
 import property_oracle as po
 from mc33_capi import MC33Lib, product_path, ref_path
+from mesh_harness import CanariedCall, bits, ctx, device_grid, to_device  # noqa: F401 (ctx: the module's fixture)
 from test_filter_cpu import CFilter, ROWS, SIZED, mesh
 
 pytestmark = pytest.mark.gpu
 
-SPARE = 16  # canaried rows behind every output
-FILL = 0x55
 # the rows of the issue's table that a filter struct expresses (the others name their roots)
 CRITERIA = {"noise-min16": {"min_triangles": 16}, "noise-closed": {"closed_only": True}, "quant-min8": {"min_triangles": 8}, "quant-all": {},
             "quant-closed": {"closed_only": True}}
 
 
-def to_device(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return torch.from_numpy(a).cuda()
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype.itemsize == 8 else np.uint32)
-
-
-def device_grid(data, r0, d, prop=None):
-    from mc33_c_library_amd import DeviceGrid
-    g = DeviceGrid(to_device(data), r0=r0, d=d)
-    if prop is not None:
-        g.attach_property(to_device(prop))
-    return g
-
-
-def tiny_grid():
-    """a context for meshes that come from no grid"""
-    return device_grid(np.zeros((4, 4, 4), np.float32), (0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
-
-
-class Call:
-    """one mc33hip_compact_components call with every output inside a larger, canaried tensor"""
+class Call(CanariedCall):
+    """one mc33hip_compact_components call"""
 
     def __init__(self, g, V, N, T, labels, roots, invert=False, attrs=(), capV=None, capT=None, with_map=True):
         import torch
         from mc33_c_library_amd.api import Compaction
-        self.g, self.nV, self.nT = g, V.shape[0], T.shape[0]
+        super().__init__(g)
+        self.nV, self.nT = V.shape[0], T.shape[0]
         self.capV = self.nV if capV is None else capV
         self.capT = self.nT if capT is None else capT
-
-        def room(rows, width, dtype):
-            return torch.empty((rows + SPARE, width) if width else (rows + SPARE,), dtype=dtype, device="cuda")
-        self.oV, self.oN, self.oT = room(self.capV, 3, V.dtype), room(self.capV, 3, torch.float32), room(self.capT, 3, torch.int32)
-        self.oA = [room(self.capV, 0, torch.int32) for _ in attrs]
-        self.oMap = room(self.nV, 0, torch.int32) if with_map else None
-        for t in [self.oV, self.oN, self.oT, self.oMap] + self.oA:
-            if t is not None:
-                t.view(torch.uint8).fill_(FILL)
+        self.oV, self.oN, self.oT = self.room(self.capV, 3, V.dtype), self.room(self.capV, 3, torch.float32), self.room(self.capT, 3, torch.int32)
+        self.oA = [self.room(self.capV, 0, torch.int32) for _ in attrs]
+        self.oMap = self.room(self.nV, 0, torch.int32) if with_map else None
         roots = np.ascontiguousarray(np.asarray(roots).reshape(-1), dtype=np.uint32)
         a = Compaction()
         a.V, a.N, a.T, a.label, a.nV, a.nT = V.data_ptr(), N.data_ptr(), T.data_ptr(), labels.data_ptr(), self.nV, self.nT
@@ -81,36 +49,21 @@ class Call:
         a.oV, a.oN, a.oT, a.capV, a.capT = self.oV.data_ptr(), self.oN.data_ptr(), self.oT.data_ptr(), self.capV, self.capT
         a.oMap = self.oMap.data_ptr() if with_map else None
         self.keep = (V, N, T, labels, attrs, roots)
-        self.a = a
-        self.rc = g.lib.mc33hip_compact_components(g.ctx, C.byref(a))
-        self.message = g.lib.mc33hip_last_error().decode(errors="replace")
+        self.call(g.lib.mc33hip_compact_components, a)
         self.counts = (int(a.nV_out), int(a.nT_out), int(a.components_kept))
-
-    def host(self, t):
-        return t.cpu().numpy()
-
-    def spare_intact(self, written=True):
-        """the canaries behind the rows the call may write - behind row 0 when it must write nothing"""
-        nV2, nT2 = (self.counts[0], self.counts[1]) if written else (0, 0)
-        for t, used in [(self.oV, nV2), (self.oN, nV2), (self.oT, nT2)] + [(x, nV2) for x in self.oA] + ([(self.oMap, self.nV if written else 0)] if self.oMap is not None else []):
-            tail = self.host(t[used:]).view(np.uint8)
-            assert np.all(tail == FILL), "%d bytes behind the output rows were written" % np.count_nonzero(tail != FILL)
 
     def check(self, want):
         """bit for bit against the oracle"""
         assert self.counts == (want.nV_out, want.nT_out, want.components_kept), (self.counts, (want.nV_out, want.nT_out, want.components_kept))
         nV2, nT2 = want.nV_out, want.nT_out
-        assert np.array_equal(bits(self.host(self.oV[:nV2])), bits(want.V)), "oV"
-        assert np.array_equal(bits(self.host(self.oN[:nV2])), bits(want.N)), "oN"
-        assert np.array_equal(self.host(self.oT[:nT2]).view(np.uint32), want.T), "oT"
+        self.equal_bits("oV", self.oV[:nV2], want.V)
+        self.equal_bits("oN", self.oN[:nV2], want.N)
+        self.equal_bits("oT", self.oT[:nT2], want.T)
         for k, x in enumerate(self.oA):
-            assert np.array_equal(bits(self.host(x[:nV2])), bits(want.attrs[k])), "attribute %d" % k
+            self.equal_bits("attribute %d" % k, x[:nV2], want.attrs[k])
         if self.oMap is not None:
-            assert np.array_equal(self.host(self.oMap[:self.nV]).view(np.uint32), want.vmap), "oMap"
+            self.equal_bits("oMap", self.oMap[:self.nV], want.vmap)
         self.spare_intact()
-
-    def all_bytes(self):
-        return [self.host(t).tobytes() for t in [self.oV, self.oN, self.oT, self.oMap] + self.oA if t is not None]
 
 
 def check_python(got, want):
@@ -189,13 +142,6 @@ def synthetic(nV, seed):
 
 # around a wave, a block, a tile of 4 per lane, and one and four rounds of a 256-tile top-level scan
 SIZES = [0, 3, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 262143, 262144, 262145, 1048577]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    g = tiny_grid()
-    yield g
-    g.close()
 
 
 @pytest.mark.parametrize("nV", SIZES)

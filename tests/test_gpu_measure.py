@@ -14,38 +14,20 @@ import pytest
 from capi_slab_refusals import refusal
 import fixtures as fx
 import measure_oracle as mo
+import mesh_checks
 import property_oracle as po
 from mc33_capi import MC33Lib, product_path, ref_path
+from mesh_harness import device_grid, to_device
 
 pytestmark = pytest.mark.gpu
 
 AWKWARD_R0, AWKWARD_D = mo.AWKWARD_R0, mo.AWKWARD_D
 
 
-def to_device(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)
-    elif a.dtype == np.uint16:
-        a = a.view(np.int16)
-    return torch.from_numpy(a).cuda()
-
-
-def device_grid(data, r0, d, prop=None):
-    from mc33_c_library_amd import DeviceGrid
-    g = DeviceGrid(to_device(data), r0=r0, d=d)
-    if prop is not None:
-        g.attach_property(to_device(prop))
-    return g
-
-
-def reference_mesh(reflibs, name, dtype="f32"):
+def reference_mesh(reflibs, name):
     """(data, r0, d, iso, reference surface) of a fixture row; the row's figures are asserted on the reference's mesh first"""
-    field, iso, (nV, nT, _, _, edges) = mo.FIXTURES[name]
-    data, r0, d = field()
-    s = reflibs[dtype].isosurface(data, iso, r0, d)
-    assert (s.nV, s.nT) == (nV, nT) and mo.open_edges(s.T) == edges, "fixture %s drifted: %d vertices, %d triangles" % (name, s.nV, s.nT)
+    data, r0, d, iso, s = mesh_checks.reference_mesh(reflibs, name)
+    assert mo.open_edges(s.T) == mo.FIXTURES[name][2][4], "fixture %s drifted: %d open edges" % (name, mo.open_edges(s.T))
     return data, r0, d, iso, s
 
 

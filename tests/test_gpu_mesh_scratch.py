@@ -14,18 +14,14 @@ import measure_oracle as mo
 import simplify_oracle as sp
 import smooth_oracle as so
 from test_clip_cpu import MODES
+from mesh_harness import bits, tiny_grid, to_device, words
 from test_gpu_clip import Call as Clip
-from test_gpu_clip import bits, device_grid, to_device
 from test_gpu_filter import Call as Compact
 from test_gpu_simplify import Call as Simplify
 
 pytestmark = pytest.mark.gpu
 
 CELL, ORIGIN = (0.5, 0.5, 0.5), (-16.0, -16.0, -16.0)  # standard-normal positions: several vertices to a cell, none clamped
-
-
-def words(n, seed):
-    return np.random.default_rng(seed).integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
 
 
 def compact(g, nV):
@@ -68,7 +64,7 @@ def vertex_normals(g, nV):
 
 
 def test_one_context_calls_of_shrinking_sizes():
-    g = device_grid(np.zeros((4, 4, 4), np.float32))
+    g = tiny_grid()
     try:
         for call, nV in ((compact, 263169), (clip, 1025), (simplify, 4097), (vertex_normals, 1025), (compact, 262145), (clip, 3)):
             call(g, nV)

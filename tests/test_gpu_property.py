@@ -11,6 +11,7 @@ import pytest
 import fixtures as fx
 import property_oracle as po
 from mc33_capi import MC33Lib, product_path
+from mesh_harness import bits, device_grid, to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -25,28 +26,6 @@ def palette(n):
 
 def as_i32(words):
     return np.array([w & 0xFFFFFFFF for w in words], np.uint32).view(np.int32)
-
-
-def to_device(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    if t.dtype == torch.uint16:
-        t = t.view(torch.int16)
-    elif t.dtype == torch.uint32:
-        t = t.view(torch.int32)
-    return t.cuda()
-
-
-def device_grid(data, r0, d, prop=None, **kw):
-    from mc33_c_library_amd import DeviceGrid
-    g = DeviceGrid(to_device(data), r0=r0, d=d, **kw)
-    if prop is not None:
-        g.attach_property(to_device(prop))
-    return g
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 CASES = {

@@ -4,7 +4,7 @@ MC33_calculate_simplified_isosurface; DeviceGrid.simplify / extract_simplified).
 V and T come from the reference twin (oracle/_ref) or are made up (tests/simplify_cases.py); the expected arrays come from
 tests/simplify_oracle.py, the definition in numpy, and the normals from tests/smooth_oracle.py applied to the oracle's output.
 Everything is compared bit for bit - oV, oN, oT, both attributes, oMap and the eight counts; nothing here has a tolerance.  Every
-output of every call sits in a larger tensor whose spare rows are canaried."""
+output of every call is canaried (tests/mesh_harness.py: CanariedCall)."""
 import ctypes as C
 
 import numpy as np
@@ -19,63 +19,32 @@ import simplify_cases as sc
 import simplify_oracle as sp
 import smooth_oracle as so
 from mc33_capi import MC33Lib, product_path, ref_path
+from mesh_harness import SPARE, CanariedCall, bits, ctx, device_grid, once_per_key, to_device, words  # noqa: F401 (ctx: the module's fixture)
 from test_simplify_cpu import CELLS, MODES, TABLE, CSimplification, mesh, simplified
 
 pytestmark = pytest.mark.gpu
 
-SPARE = 16  # canaried rows behind every output
-FILL = 0x55
 COUNTS = sp.Simplified.COUNTS
-
-
-def to_device(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return torch.from_numpy(a).cuda()
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype.itemsize == 8 else np.uint32)
-
-
-def device_grid(data, r0=(0.0, 0.0, 0.0), d=(1.0, 1.0, 1.0), prop=None):
-    from mc33_c_library_amd import DeviceGrid
-    g = DeviceGrid(to_device(data), r0=r0, d=d)
-    if prop is not None:
-        g.attach_property(to_device(prop))
-    return g
-
-
-def words(n, seed):
-    return np.random.default_rng(seed).integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
 
 
 def normals_of(want):
     return so.vertex_normals(want.V, want.T) if want.nV_out else np.zeros((0, 3), np.float32)
 
 
-class Call:
-    """one mc33hip_simplify_surface call with every output inside a larger, canaried tensor"""
+class Call(CanariedCall):
+    """one mc33hip_simplify_surface call"""
 
     def __init__(self, g, V, T, cell, origin=(0.0, 0.0, 0.0), mode=sp.MEAN, drop=True, attrs=(), capV=None, capT=None, with_map=True, with_normals=True, change=None):
         import torch
         from mc33_c_library_amd.api import Simplification
-        self.g, self.nV, self.nT = g, V.shape[0], T.shape[0]
+        super().__init__(g)
+        self.nV, self.nT = V.shape[0], T.shape[0]
         self.capV = self.nV if capV is None else capV
         self.capT = self.nT if capT is None else capT
-
-        def room(rows, width, dtype):
-            return torch.empty((rows + SPARE, width) if width else (rows + SPARE,), dtype=dtype, device="cuda")
-        self.oV, self.oT = room(self.capV, 3, V.dtype), room(self.capT, 3, torch.int32)
-        self.oN = room(self.capV, 3, torch.float32) if with_normals else None
-        self.oA = [room(self.capV, 0, torch.int32) for _ in attrs]
-        self.oMap = room(self.nV, 0, torch.int32) if with_map else None
-        for t in [self.oV, self.oN, self.oT, self.oMap] + self.oA:
-            if t is not None:
-                t.view(torch.uint8).fill_(FILL)
+        self.oV, self.oT = self.room(self.capV, 3, V.dtype), self.room(self.capT, 3, torch.int32)
+        self.oN = self.room(self.capV, 3, torch.float32) if with_normals else None
+        self.oA = [self.room(self.capV, 0, torch.int32) for _ in attrs]
+        self.oMap = self.room(self.nV, 0, torch.int32) if with_map else None
         a = Simplification()
         a.V, a.T, a.nV, a.nT = V.data_ptr(), T.data_ptr(), self.nV, self.nT
         for k, x in enumerate(attrs):
@@ -86,46 +55,23 @@ class Call:
         a.oV, a.oT, a.capV, a.capT = self.oV.data_ptr(), self.oT.data_ptr(), self.capV, self.capT
         a.oN = self.oN.data_ptr() if with_normals else None
         a.oMap = self.oMap.data_ptr() if with_map else None
-        for name, value in (change or {}).items():
-            if name in ("origin", "cell"):
-                setattr(a, name, (C.c_double * 3)(*value))
-            elif name in ("attr0", "oAttr0"):
-                getattr(a, name[:-1])[0] = value
-            else:
-                setattr(a, name, value)
         self.keep = (V, T, attrs)
-        self.a = a
-        self.rc = g.lib.mc33hip_simplify_surface(g.ctx, C.byref(a))
-        self.message = g.lib.mc33hip_last_error().decode(errors="replace")
+        self.call(g.lib.mc33hip_simplify_surface, a, change)
         self.counts = tuple(int(getattr(a, n)) for n in COUNTS)
-
-    def host(self, t):
-        return t.cpu().numpy()
-
-    def spare_intact(self, written=True):
-        """the canaries behind the rows the call may write - behind row 0 when it must write nothing"""
-        nV2, nT2 = (self.counts[0], self.counts[1]) if written else (0, 0)
-        for t, used in [(self.oV, nV2), (self.oN, nV2), (self.oT, nT2), (self.oMap, self.nV if written else 0)] + [(x, nV2) for x in self.oA]:
-            if t is not None:
-                tail = self.host(t[used:]).view(np.uint8)
-                assert np.all(tail == FILL), "%d bytes behind the output rows were written" % np.count_nonzero(tail != FILL)
 
     def check(self, want, attrs=()):
         """bit for bit against the oracle; attrs: the input words on the host"""
         assert self.counts == want.counts(), (self.counts, want.counts())
         nV2, nT2 = want.nV_out, want.nT_out
-        assert np.array_equal(bits(self.host(self.oV[:nV2])), bits(want.V)), "oV"
-        assert np.array_equal(self.host(self.oT[:nT2]).view(np.uint32), want.T), "oT"
+        self.equal_bits("oV", self.oV[:nV2], want.V)
+        self.equal_bits("oT", self.oT[:nT2], want.T)
         if self.oN is not None:
-            assert np.array_equal(bits(self.host(self.oN[:nV2])), bits(normals_of(want))), "oN"
+            self.equal_bits("oN", self.oN[:nV2], normals_of(want))
         for k, x in enumerate(self.oA):
-            assert np.array_equal(bits(self.host(x[:nV2])), bits(np.asarray(attrs[k])[want.keep])), "attribute %d" % k
+            self.equal_bits("attribute %d" % k, x[:nV2], np.asarray(attrs[k])[want.keep])
         if self.oMap is not None:
-            assert np.array_equal(self.host(self.oMap[:self.nV]).view(np.uint32), want.vmap), "oMap"
+            self.equal_bits("oMap", self.oMap[:self.nV], want.vmap)
         self.spare_intact()
-
-    def all_bytes(self):
-        return [self.host(t).tobytes() for t in [self.oV, self.oN, self.oT, self.oMap] + self.oA if t is not None]
 
 
 def check_topology(g, call):
@@ -136,23 +82,12 @@ def check_topology(g, call):
         assert t.degenerate_triangles == 0 and t.referenced_vertices == nV2
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    g = device_grid(np.zeros((4, 4, 4), np.float32))
-    yield g
-    g.close()
-
-
-_on_device = {}
-
-
+@once_per_key
 def uploaded(reflibs, name):
     """a fixture's surface and two attribute arrays on the device, uploaded once"""
-    if name not in _on_device:
-        data, r0, d, iso, s = mesh(reflibs, name)
-        A = (words(s.nV, 11), words(s.nV, 12))
-        _on_device[name] = (to_device(s.V), to_device(s.T), A, [to_device(x) for x in A])
-    return _on_device[name]
+    data, r0, d, iso, s = mesh(reflibs, name)
+    A = (words(s.nV, 11), words(s.nV, 12))
+    return (to_device(s.V), to_device(s.T), A, [to_device(x) for x in A])
 
 
 # ---- the five fixtures x the two cells x both modes x duplicates dropped and kept ------------------------------------------------

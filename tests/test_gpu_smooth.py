@@ -3,7 +3,7 @@ MC33_calculate_smoothed_isosurface; DeviceGrid.smooth / vertex_normals / extract
 
 V and T come from the reference twin (oracle/_ref) or are synthetic; the expected arrays come from tests/smooth_oracle.py, the
 definition in numpy.  oV and oN are compared bit for bit, the four counts exactly; nothing here has a tolerance.  Every output
-of every call sits in a larger tensor whose spare rows are canaried."""
+of every call is canaried (tests/mesh_harness.py: CanariedCall)."""
 import ctypes as C
 
 import numpy as np
@@ -15,60 +15,25 @@ import measure_oracle as mo
 import property_oracle as po
 import smooth_oracle as so
 from mc33_capi import MC33Lib, product_path, ref_path
+from mesh_harness import FILL, SPARE, CanariedCall, bits, ctx, device_grid, to_device  # noqa: F401 (ctx: the module's fixture)
 from test_smooth_cpu import CSmoothing, TABLE, mesh
 
 pytestmark = pytest.mark.gpu
-
-SPARE = 16  # canaried rows behind every output
-FILL = 0x55
-
-
-def to_device(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if not a.flags.writeable:  # (the shared fixtures are read-only; torch wants to own what it wraps)
-        a = a.copy()
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return torch.from_numpy(a).cuda()
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype.itemsize == 8 else np.uint32)
-
-
-def device_grid(data, r0=(0.0, 0.0, 0.0), d=(1.0, 1.0, 1.0), prop=None):
-    from mc33_c_library_amd import DeviceGrid
-    g = DeviceGrid(to_device(data), r0=r0, d=d)
-    if prop is not None:
-        g.attach_property(to_device(prop))
-    return g
-
-
-def tiny_grid():
-    """a context for meshes that come from no grid"""
-    return device_grid(np.zeros((4, 4, 4), np.float32))
 
 
 def info_of(A):
     return (A.max_degree, A.isolated_vertices, A.boundary_vertices, A.invalid_triangles)
 
 
-class Call:
-    """one mc33hip_smooth_surface call with every output inside a larger, canaried tensor; in_place: V is copied into such a
-    tensor first and oV == V"""
+class Call(CanariedCall):
+    """one mc33hip_smooth_surface call; in_place: V is copied into the canaried oV first and oV == V"""
 
     def __init__(self, g, V, T, iterations=10, lam=0.5, mu=-0.53, pin=True, normals=True, in_place=False, change=None):
         import torch
         from mc33_c_library_amd.api import Smoothing
-        self.g, self.nV, self.nT = g, V.shape[0], T.shape[0]
-
-        def room(dtype):
-            t = torch.empty((self.nV + SPARE, 3), dtype=dtype, device="cuda")
-            t.view(torch.uint8).fill_(FILL)
-            return t
-        self.oV, self.oN = room(V.dtype), (room(torch.float32) if normals else None)
+        super().__init__(g)
+        self.nV, self.nT = V.shape[0], T.shape[0]
+        self.oV, self.oN = self.room(self.nV, 3, V.dtype), (self.room(self.nV, 3, torch.float32) if normals else None)
         if in_place:
             self.oV[:self.nV] = V
             V = self.oV[:self.nV]
@@ -77,33 +42,21 @@ class Call:
         a.iterations, a.lam, a.mu, a.pin_boundary = iterations, lam, mu, int(bool(pin))
         a.oV, a.oN = self.oV.data_ptr(), (self.oN.data_ptr() if normals else None)
         a.max_degree = a.isolated_vertices = a.boundary_vertices = a.invalid_triangles = 77
-        for k, v in (change or {}).items():  # (fields of the struct set to something else: the refused calls)
-            setattr(a, k, v)
-        self.keep, self.a = (V, T), a
-        self.rc = g.lib.mc33hip_smooth_surface(g.ctx, C.byref(a))
-        self.message = g.lib.mc33hip_last_error().decode(errors="replace")
+        self.keep = (V, T)
+        self.call(g.lib.mc33hip_smooth_surface, a, change)
         self.info = (int(a.max_degree), int(a.isolated_vertices), int(a.boundary_vertices), int(a.invalid_triangles))
 
-    def spare_intact(self, written=True):
-        """the canaries behind the rows the call may write - behind row 0 when it must write nothing"""
-        for t in (self.oV, self.oN):
-            if t is not None:
-                tail = t[self.nV if written else 0:].cpu().numpy().view(np.uint8)
-                assert np.all(tail == FILL), "%d bytes behind the output rows were written" % np.count_nonzero(tail != FILL)
+    def outputs(self):
+        return [(self.oV, self.nV), (self.oN, self.nV)]
 
     def check(self, P, N=None, info=None):
         """bit for bit against the oracle"""
-        assert np.array_equal(bits(self.oV[:self.nV].cpu().numpy()), bits(P)), "oV: %d rows differ" % np.count_nonzero(
-            (bits(self.oV[:self.nV].cpu().numpy()) != bits(P)).any(axis=1))
+        self.equal_bits("oV", self.oV[:self.nV], P)
         if N is not None:
-            assert np.array_equal(bits(self.oN[:self.nV].cpu().numpy()), bits(N)), "oN: %d rows differ" % np.count_nonzero(
-                (bits(self.oN[:self.nV].cpu().numpy()) != bits(N)).any(axis=1))
+            self.equal_bits("oN", self.oN[:self.nV], N)
         if info is not None:
             assert self.info == tuple(info), (self.info, info)
         self.spare_intact()
-
-    def all_bytes(self):
-        return [t.cpu().numpy().tobytes() for t in (self.oV, self.oN) if t is not None]
 
 
 _normals = {}
@@ -181,13 +134,6 @@ def test_skipped_passes_and_normals_alone(reflibs, name):
 
 # around a wave, a block, a tile of 4 per lane, and one round of a 256-tile top-level scan
 SIZES = [0, 3, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 262143, 262144, 262145]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    g = tiny_grid()
-    yield g
-    g.close()
 
 
 @pytest.mark.parametrize("nV", SIZES)

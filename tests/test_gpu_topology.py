@@ -15,7 +15,8 @@ import fixtures as fx
 import measure_oracle as mo
 import topology_oracle as to
 from mc33_capi import MC33Lib, product_path, ref_path
-from test_gpu_measure import AWKWARD_D, AWKWARD_R0, device_grid, reference_mesh, to_device
+from mesh_harness import device_grid, to_device
+from test_gpu_measure import AWKWARD_D, AWKWARD_R0, reference_mesh
 from test_topology_cpu import CComponentTopology, CTopology, bind_topology_api
 
 pytestmark = pytest.mark.gpu

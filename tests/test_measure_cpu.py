@@ -6,14 +6,12 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import fixtures as fx
 import measure_oracle as mo
-from mc33_capi import MC33Lib, product_path
+from mesh_checks import assert_exported, assert_kernels, host_logic, reference_mesh
 from test_mesh_common_cpu import launched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,9 +26,8 @@ FIGURES = {"sphere": (12.561676, -4.185969), "blobs": (759.193278, 375.618205)}
 
 
 def mesh(reflibs, name):
-    field, iso, _ = mo.FIXTURES[name]
-    data, r0, d = field()
-    return data, r0, d, reflibs["f32"].isosurface(data, iso, r0, d)
+    data, r0, d, iso, s = reference_mesh(reflibs, name)
+    return data, r0, d, s
 
 
 @pytest.mark.parametrize("name", list(mo.FIXTURES))
@@ -120,22 +117,11 @@ def test_new_names_are_declared():
 
 @pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
 def test_every_library_exports_the_new_names(dtype):
-    for ortho, nneg in ((False, False), (True, False), (False, True), (True, True)):
-        path = product_path(dtype, ortho=ortho, nneg=nneg)
-        assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
-        syms = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        defined = set(line.split()[-1] for line in syms.splitlines() if line.split())
-        for n in HIP_NAMES + C_NAMES:
-            assert n in defined, "%s not exported by %s" % (n, os.path.basename(path))
+    assert_exported(HIP_NAMES + C_NAMES, dtype)
 
 
 def test_measure_kernels_are_in_the_code_object():
-    from test_code_objects import kernel_metadata
-    ks = {k["pretty"]: k for k in kernel_metadata(product_path("f32"))}
-    for name in KERNELS:
-        assert name in ks, (name, sorted(ks))
-        assert ks[name]["private_segment_fixed_size"] == 0 and ks[name]["vgpr_spill_count"] == 0, (name, ks[name])
-        assert ks[name]["vgpr_count"] <= 128, (name, ks[name])  # (two blocks of 256 per SIMD at least)
+    assert_kernels("f32", KERNELS, max_vgprs=128)  # (two blocks of 256 per SIMD at least)
 
 
 def test_python_structs_match_the_header():
@@ -148,17 +134,10 @@ def test_python_structs_match_the_header():
 def test_host_logic_library_refuses_to_measure(dtype):
     """mc33_capi.c linked with the emulated device layer, which has none of the measuring entry points: the library still loads
     (they are weak references), the three functions return -1 / 0 surfaces, and the object extracts as before."""
-    from mc33_emu import build_hostlogic
     from test_gpu_measure import CComponent, CMeasure, bind_measure_api
-    lib = MC33Lib(build_hostlogic(dtype), dtype)
-    bind_measure_api(lib)
-    L = lib.lib
-    data = fx.cos_field(20)[0] if dtype == "f32" else fx.cos_field_u16(20, 20, 20)
-    iso = 0.0 if dtype == "f32" else 30000.0
-    G, keep = lib.make_grid(data)
-    M = L.create_MC33(G)
-    assert M
-    try:
+    with host_logic(dtype) as h:
+        lib, L, M, iso = h.lib, h.L, h.M, h.iso
+        bind_measure_api(lib)
         m, many, rows, n, u = CMeasure(), (CMeasure * 3)(), (CComponent * 4)(), C.c_uint(7), C.c_uint(7)
         many[1].nT = 5
         assert L.MC33_measure_isosurface(M, lib.real(iso), C.byref(m)) == -1
@@ -167,7 +146,3 @@ def test_host_logic_library_refuses_to_measure(dtype):
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         L.free_surface_memory(S)
-    finally:
-        L.free_MC33(M)
-        L.free_memory_grd(G)
-        del keep

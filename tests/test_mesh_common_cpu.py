@@ -9,7 +9,7 @@ import os
 
 import pytest
 
-from mc33_capi import product_path
+from mesh_checks import assert_kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -27,12 +27,7 @@ def launched(*names):
 
 @pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
 def test_shared_kernels_are_in_the_code_object(dtype):
-    from test_code_objects import kernel_metadata
-    ks = {k["pretty"]: k for k in kernel_metadata(product_path(dtype))}
-    for name in MESH_KERNELS:
-        assert name in ks, (name, sorted(ks))
-        assert ks[name]["private_segment_fixed_size"] == 0 and ks[name]["vgpr_spill_count"] == 0, (name, ks[name])
-        assert ks[name]["vgpr_count"] <= 64, (name, ks[name])  # (eight waves per SIMD)
+    assert_kernels(dtype, MESH_KERNELS)  # (at most 64 registers: eight waves per SIMD)
 
 
 def test_the_part_is_built_and_included_before_the_parts_that_use_it():

@@ -4,14 +4,13 @@ emulated device layer cannot sample and must say so."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import fixtures as fx
 import property_oracle as po
-from mc33_capi import MC33Lib, product_path
+from mesh_checks import assert_exported, assert_kernels, host_logic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -72,41 +71,23 @@ def test_new_names_are_declared():
 
 @pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
 def test_every_library_exports_the_new_names(dtype):
-    for ortho, nneg in ((False, False), (True, False), (False, True), (True, True)):
-        path = product_path(dtype, ortho=ortho, nneg=nneg)
-        assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
-        syms = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        defined = set(line.split()[-1] for line in syms.splitlines() if line.split())
-        for n in HIP_NAMES + C_NAMES:
-            assert n in defined, "%s not exported by %s" % (n, os.path.basename(path))
+    assert_exported(HIP_NAMES + C_NAMES, dtype)
 
 
 def test_property_kernel_is_in_the_code_object():
-    from test_code_objects import kernel_metadata
-    ks = {k["pretty"]: k for k in kernel_metadata(product_path("f32"))}
-    for name in ("k_property<float, true>", "k_property<float, false>"):
-        assert name in ks, sorted(ks)
-        assert ks[name]["private_segment_fixed_size"] == 0 and ks[name]["vgpr_spill_count"] == 0 and ks[name]["vgpr_count"] <= 64
+    assert_kernels("f32", ("k_property<float, true>", "k_property<float, false>"))
 
 
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
 def test_host_logic_library_refuses_a_property_grid(dtype):
     """mc33_capi.c linked with the emulated device layer, which has none of the property entry points: the library still loads
     (they are weak references), MC33_set_property_grid returns -1, a colour map alone changes nothing."""
-    from mc33_emu import build_hostlogic
-    lib = MC33Lib(build_hostlogic(dtype), dtype)
-    L = lib.lib
-    L.MC33_set_property_grid.restype = C.c_int
-    L.MC33_set_property_grid.argtypes = [C.POINTER(lib.MC33), C.POINTER(lib.GRD)]
-    L.MC33_set_color_map.restype = C.c_int
-    L.MC33_set_color_map.argtypes = [C.POINTER(lib.MC33), C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
-    data = fx.cos_field(20)[0] if dtype == "f32" else fx.cos_field_u16(20, 20, 20)
-    iso = 0.0 if dtype == "f32" else 30000.0
-    G, keep = lib.make_grid(data)
-    Pg, keep2 = lib.make_grid(linear_property(data.shape, lib.np_dtype))
-    M = L.create_MC33(G)
-    assert M
-    try:
+    with host_logic(dtype, prop=linear_property) as h:
+        lib, L, M, iso, Pg = h.lib, h.L, h.M, h.iso, h.Pg
+        L.MC33_set_property_grid.restype = C.c_int
+        L.MC33_set_property_grid.argtypes = [C.POINTER(lib.MC33), C.POINTER(lib.GRD)]
+        L.MC33_set_color_map.restype = C.c_int
+        L.MC33_set_color_map.argtypes = [C.POINTER(lib.MC33), C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
         assert L.MC33_set_property_grid(M, Pg) == -1
         assert L.MC33_set_property_grid(M, None) == -1
         pal = (C.c_int * 3)(1, 2, 3)
@@ -119,8 +100,3 @@ def test_host_logic_library_refuses_a_property_grid(dtype):
         L.free_surface_memory(S)
         assert s.nV > 0 and np.all(s.color == po.DEFAULT_COLOR)
         assert L.MC33_set_color_map(M, None, 0, 0.0, 0.0) == 0
-    finally:
-        L.free_MC33(M)
-        L.free_memory_grd(G)
-        L.free_memory_grd(Pg)
-        del keep, keep2

@@ -12,16 +12,15 @@ import os
 import re
 import struct
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-import fixtures as fx
 import layouts
 import resample_cases as rc
 import resample_oracle as ro
 from mc33_capi import MC33Lib, product_path
+from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, kernels_of, offsets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "mc33_c_library_amd", "csrc", "mc33_resample.hip.h")
@@ -135,38 +134,24 @@ def test_new_names_are_declared():
 
 @pytest.mark.parametrize("dtype", TYPES)
 def test_every_library_exports_the_new_names(dtype):
-    for ortho, nneg in ((False, False), (True, False), (False, True), (True, True)):
-        path = product_path(dtype, ortho=ortho, nneg=nneg)
-        assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
-        syms = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        defined = set(line.split()[-1] for line in syms.splitlines() if line.split())
-        for n in HIP_NAMES + C_NAMES:
-            assert n in defined, "%s not exported by %s" % (n, os.path.basename(path))
+    assert_exported(HIP_NAMES + C_NAMES, dtype)
 
 
 @pytest.mark.parametrize("dtype", TYPES)
 def test_resampling_kernel_is_in_the_code_object(dtype):
-    from test_code_objects import kernel_metadata
     ctype = {"f32": "float", "f64": "double", "u8": "unsigned char", "u16": "unsigned short", "u32": "unsigned int"}[dtype]
-    ks = {k["pretty"]: k for k in kernel_metadata(product_path(dtype))}
+    ks = kernels_of(dtype)
     mine = [n for n in ks if n.startswith("k_rs_")]
     assert mine == ["k_rs_resample<%s>" % ctype], (mine, sorted(ks))
+    assert_kernels(dtype, mine, MAX_VGPRS)
     for name in mine:
-        assert ks[name]["private_segment_fixed_size"] == 0 and ks[name]["vgpr_spill_count"] == 0, (name, ks[name])
-        assert ks[name]["vgpr_count"] <= MAX_VGPRS, (name, ks[name])
         assert ks[name]["group_segment_fixed_size"] == 0, (name, ks[name])   # (all of its LDS is sized by the plan at launch)
 
 
 def test_python_structs_match_the_header():
     from mc33_c_library_amd.api import GridResampling, Resampling
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"marching_cubes_33.h\"\n#include \"mc33_hip.h\"\nint main(void) {\n"
-    src += "\tprintf(\"%zu %zu %zu %zu\\n\", sizeof(mc33hip_resampling), offsetof(mc33hip_resampling, taps), offsetof(mc33hip_resampling, ntaps), offsetof(mc33hip_resampling, stride));\n"
-    src += "\tprintf(\"%zu %zu %zu %zu\\n\", sizeof(mc33_resampling), offsetof(mc33_resampling, sigma), offsetof(mc33_resampling, radius), offsetof(mc33_resampling, stride));\n"
-    src += "\treturn 0;\n}\n"
-    with tempfile.TemporaryDirectory() as tmp:
-        open(os.path.join(tmp, "sizes.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(tmp, "sizes.c"), "-o", os.path.join(tmp, "sizes")])
-        want = [int(x) for x in subprocess.check_output([os.path.join(tmp, "sizes")], text=True).split()]
+    want = c_layout(["sizeof(mc33hip_resampling)"] + offsets("mc33hip_resampling", ["taps", "ntaps", "stride"]) +
+                    ["sizeof(mc33_resampling)"] + offsets("mc33_resampling", ["sigma", "radius", "stride"]))
     R, G = Resampling, GridResampling
     got = [C.sizeof(R), R.taps.offset, R.ntaps.offset, R.stride.offset, C.sizeof(G), G.sigma.offset, G.radius.offset, G.stride.offset]
     assert got == want
@@ -179,19 +164,12 @@ def test_python_structs_match_the_header():
 def test_host_logic_library_refuses_to_resample(dtype):
     """MC33_create_resampled returns NULL for good and for refused structs, the source object is unchanged and extracts as before,
     and MC33_resampled_grid of an ordinary object is NULL."""
-    from mc33_emu import build_hostlogic
-    lib = MC33Lib(build_hostlogic(dtype), dtype)
-    L = lib.lib
-    L.MC33_create_resampled.restype = C.POINTER(lib.MC33)
-    L.MC33_create_resampled.argtypes = [C.POINTER(lib.MC33), C.POINTER(CResampling)]
-    L.MC33_resampled_grid.restype = C.POINTER(lib.GRD)
-    L.MC33_resampled_grid.argtypes = [C.POINTER(lib.MC33)]
-    data = fx.cos_field(20)[0] if dtype == "f32" else fx.cos_field_u16(20, 20, 20)
-    iso = 0.0 if dtype == "f32" else 30000.0
-    G, keep = lib.make_grid(data)
-    M = L.create_MC33(G)
-    assert M
-    try:
+    with host_logic(dtype) as h:
+        lib, L, M, iso = h.lib, h.L, h.M, h.iso
+        L.MC33_create_resampled.restype = C.POINTER(lib.MC33)
+        L.MC33_create_resampled.argtypes = [C.POINTER(lib.MC33), C.POINTER(CResampling)]
+        L.MC33_resampled_grid.restype = C.POINTER(lib.GRD)
+        L.MC33_resampled_grid.argtypes = [C.POINTER(lib.MC33)]
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         first = lib.copy_surface(S)
@@ -215,10 +193,6 @@ def test_host_logic_library_refuses_to_resample(dtype):
         again = lib.copy_surface(S)
         L.free_surface_memory(S)
         assert np.array_equal(again.T, first.T) and ro.same_bits(again.V, first.V) and ro.same_bits(again.N, first.N)
-    finally:
-        L.free_MC33(M)
-        L.free_memory_grd(G)
-        del keep
 
 
 # ---- the kernel's text compiled for the host ---------------------------------------------------------------------------------------------

@@ -8,17 +8,14 @@ code-object and host-logic tests below - these fail without the feature - and, o
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import filter_oracle as fo
-import fixtures as fx
 import measure_oracle as mo
 import simplify_oracle as sp
-from mc33_capi import MC33Lib, product_path
+from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets, reference_mesh
 from test_mesh_common_cpu import launched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,20 +50,9 @@ class CSimplification(C.Structure):
     _fields_ = [("cell", C.c_double * 3), ("mode", C.c_int), ("drop_duplicates", C.c_int)]
 
 
-_meshes = {}
-
-
 def mesh(reflibs, name):
     """the reference's surface of a fixture row, computed once and left unchanged"""
-    if name not in _meshes:
-        field, iso, (nV, nT, _, _, _) = mo.FIXTURES[name]
-        data, r0, d = field()
-        s = reflibs["f32"].isosurface(data, iso, r0, d)
-        assert (s.nV, s.nT) == (nV, nT), "fixture %s drifted: %d vertices, %d triangles" % (name, s.nV, s.nT)
-        for a in (s.V, s.N, s.T):
-            a.setflags(write=False)
-        _meshes[name] = (data, r0, d, iso, s)
-    return _meshes[name]
+    return reference_mesh(reflibs, name)
 
 
 _results = {}
@@ -194,39 +180,21 @@ def test_new_names_are_declared():
 
 @pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
 def test_every_library_exports_the_new_names(dtype):
-    for ortho, nneg in ((False, False), (True, False), (False, True), (True, True)):
-        path = product_path(dtype, ortho=ortho, nneg=nneg)
-        assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
-        syms = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        defined = set(line.split()[-1] for line in syms.splitlines() if line.split())
-        for n in HIP_NAMES + C_NAMES:
-            assert n in defined, "%s not exported by %s" % (n, os.path.basename(path))
+    assert_exported(HIP_NAMES + C_NAMES, dtype)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
 def test_simplification_kernels_are_in_the_code_object(dtype):
-    from test_code_objects import kernel_metadata
     real = "double" if dtype == "f64" else "float"
-    ks = {k["pretty"]: k for k in kernel_metadata(product_path(dtype))}
-    for name in KERNELS + ["k_simp_cluster<%s>" % real, "k_simp_rows<%s>" % real]:
-        assert name in ks, (name, sorted(ks))
-        assert ks[name]["private_segment_fixed_size"] == 0 and ks[name]["vgpr_spill_count"] == 0, (name, ks[name])
-        assert ks[name]["vgpr_count"] <= 64, (name, ks[name])  # (eight waves per SIMD)
+    assert_kernels(dtype, KERNELS + ["k_simp_cluster<%s>" % real, "k_simp_rows<%s>" % real])
 
 
 def test_python_structs_match_the_header():
     from mc33_c_library_amd.api import Simplification, SurfaceSimplification
     members = ["nT", "attr", "n_attr", "origin", "cell", "mode", "drop_duplicates", "oV", "oT", "oN", "oAttr", "oMap", "capV", "capT", "nV_out", "max_cluster",
                "clamped_vertices"]
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"marching_cubes_33.h\"\n#include \"mc33_hip.h\"\nint main(void) {\n"
-    src += "\tprintf(\"%zu %zu %zu %zu\\n\", sizeof(mc33hip_simplification), sizeof(mc33_simplification), offsetof(mc33_simplification, mode), offsetof(mc33_simplification, drop_duplicates));\n"
-    for m in members:
-        src += "\tprintf(\"%%zu\\n\", offsetof(mc33hip_simplification, %s));\n" % m
-    src += "\treturn 0;\n}\n"
-    with tempfile.TemporaryDirectory() as tmp:
-        open(os.path.join(tmp, "sizes.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(tmp, "sizes.c"), "-o", os.path.join(tmp, "sizes")])
-        want = [int(x) for x in subprocess.check_output([os.path.join(tmp, "sizes")], text=True).split()]
+    want = c_layout(["sizeof(mc33hip_simplification)", "sizeof(mc33_simplification)"] + offsets("mc33_simplification", ["mode", "drop_duplicates"]) +
+                    offsets("mc33hip_simplification", members))
     S, Z = Simplification, SurfaceSimplification
     got = [C.sizeof(S), C.sizeof(Z), Z.mode.offset, Z.drop_duplicates.offset] + [getattr(S, m).offset for m in members]
     assert got == want
@@ -238,17 +206,10 @@ def test_host_logic_library_refuses_to_simplify(dtype):
     """mc33_capi.c linked with the emulated device layer, which cannot simplify: the library still loads (a weak reference),
     MC33_calculate_simplified_isosurface returns NULL and leaves the object alone - for good arguments and, which needs no
     device in any build, for a null struct and every refused parameter -, and the object extracts as before."""
-    from mc33_emu import build_hostlogic
-    lib = MC33Lib(build_hostlogic(dtype), dtype)
-    L = lib.lib
-    L.MC33_calculate_simplified_isosurface.restype = C.POINTER(lib.SURFACE)
-    L.MC33_calculate_simplified_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CSimplification)]
-    data = fx.cos_field(20)[0] if dtype == "f32" else fx.cos_field_u16(20, 20, 20)
-    iso = 0.0 if dtype == "f32" else 30000.0
-    G, keep = lib.make_grid(data)
-    M = L.create_MC33(G)
-    assert M
-    try:
+    with host_logic(dtype) as h:
+        lib, L, M, iso = h.lib, h.L, h.M, h.iso
+        L.MC33_calculate_simplified_isosurface.restype = C.POINTER(lib.SURFACE)
+        L.MC33_calculate_simplified_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CSimplification)]
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         before = (M.contents.iso, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V)
@@ -266,7 +227,3 @@ def test_host_logic_library_refuses_to_simplify(dtype):
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         L.free_surface_memory(S)
-    finally:
-        L.free_MC33(M)
-        L.free_memory_grd(G)
-        del keep

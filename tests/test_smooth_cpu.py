@@ -9,15 +9,13 @@ code-object and host-logic tests below and, on the device, by tests/test_gpu_smo
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import fixtures as fx
 import measure_oracle as mo
 import smooth_oracle as so
-from mc33_capi import MC33Lib, product_path
+from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets, reference_mesh
 from test_mesh_common_cpu import launched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,13 +44,10 @@ _meshes = {}
 def mesh(reflibs, name):
     """the reference's surface of a fixture row, its adjacency and both smoothed copies, computed once and left unchanged"""
     if name not in _meshes:
-        field, iso, (nV, nT, _, _, _) = mo.FIXTURES[name]
-        data, r0, d = field()
-        s = reflibs["f32"].isosurface(data, iso, r0, d)
-        assert (s.nV, s.nT) == (nV, nT), "fixture %s drifted: %d vertices, %d triangles" % (name, s.nV, s.nT)
+        data, r0, d, iso, s = reference_mesh(reflibs, name)
         A = so.adjacency(s.T, s.nV)
         P = {pin: so.smooth(s.V, s.T, 10, 0.5, -0.53, pin, A=A)[0] for pin in (True, False)}
-        for a in (s.V, s.N, s.T, P[True], P[False]):
+        for a in (P[True], P[False]):
             a.setflags(write=False)
         _meshes[name] = (data, r0, d, iso, s, A, P)
     return _meshes[name]
@@ -144,44 +139,18 @@ def test_new_names_are_declared():
 
 @pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
 def test_every_library_exports_the_new_names(dtype):
-    for ortho, nneg in ((False, False), (True, False), (False, True), (True, True)):
-        path = product_path(dtype, ortho=ortho, nneg=nneg)
-        assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
-        syms = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        defined = set(line.split()[-1] for line in syms.splitlines() if line.split())
-        for n in HIP_NAMES + C_NAMES:
-            assert n in defined, "%s not exported by %s" % (n, os.path.basename(path))
+    assert_exported(HIP_NAMES + C_NAMES, dtype)
 
 
 @pytest.mark.parametrize("dtype,real", [("f32", "float"), ("f64", "double")])
 def test_smoothing_kernels_are_in_the_code_object(dtype, real):
-    from test_code_objects import kernel_metadata
-    ks = {k["pretty"]: k for k in kernel_metadata(product_path(dtype))}
-    for name in KERNELS + ["k_sm_pass<%s>" % real, "k_sm_normals<%s>" % real]:
-        assert name in ks, (name, sorted(ks))
-        assert ks[name]["private_segment_fixed_size"] == 0 and ks[name]["vgpr_spill_count"] == 0, (name, ks[name])
-        assert ks[name]["vgpr_count"] <= 64, (name, ks[name])  # (eight waves per SIMD)
+    assert_kernels(dtype, KERNELS + ["k_sm_pass<%s>" % real, "k_sm_normals<%s>" % real])
 
 
 def test_python_structs_match_the_header():
     from mc33_c_library_amd.api import Smoothing, SurfaceSmoothing
-    src = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "marching_cubes_33.h"
-#include "mc33_hip.h"
-int main(void) {
-	printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(mc33hip_smoothing), offsetof(mc33hip_smoothing, nT), offsetof(mc33hip_smoothing, iterations),
-	       offsetof(mc33hip_smoothing, lambda), offsetof(mc33hip_smoothing, pin_boundary), offsetof(mc33hip_smoothing, oV), offsetof(mc33hip_smoothing, oN),
-	       offsetof(mc33hip_smoothing, max_degree), offsetof(mc33hip_smoothing, invalid_triangles), sizeof(mc33_smoothing), offsetof(mc33_smoothing, pin_boundary));
-	return 0;
-}
-"""
-    import tempfile
-    with tempfile.TemporaryDirectory() as tmp:
-        open(os.path.join(tmp, "sizes.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(tmp, "sizes.c"), "-o", os.path.join(tmp, "sizes")])
-        want = [int(x) for x in subprocess.check_output([os.path.join(tmp, "sizes")], text=True).split()]
+    members = ["nT", "iterations", "lambda", "pin_boundary", "oV", "oN", "max_degree", "invalid_triangles"]
+    want = c_layout(["sizeof(mc33hip_smoothing)"] + offsets("mc33hip_smoothing", members) + ["sizeof(mc33_smoothing)", "offsetof(mc33_smoothing, pin_boundary)"])
     S = Smoothing
     got = [C.sizeof(S), S.nT.offset, S.iterations.offset, S.lam.offset, S.pin_boundary.offset, S.oV.offset, S.oN.offset, S.max_degree.offset,
            S.invalid_triangles.offset, C.sizeof(SurfaceSmoothing), SurfaceSmoothing.pin_boundary.offset]
@@ -193,24 +162,13 @@ int main(void) {
 def test_host_logic_library_refuses_to_smooth(dtype):
     """mc33_capi.c linked with the emulated device layer, which cannot smooth: the library still loads (a weak reference),
     MC33_calculate_smoothed_isosurface returns NULL and leaves the object alone, and the object extracts as before."""
-    from mc33_emu import build_hostlogic
-    lib = MC33Lib(build_hostlogic(dtype), dtype)
-    L = lib.lib
-    L.MC33_calculate_smoothed_isosurface.restype = C.POINTER(lib.SURFACE)
-    L.MC33_calculate_smoothed_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CSmoothing)]
-    data = fx.cos_field(20)[0] if dtype == "f32" else fx.cos_field_u16(20, 20, 20)
-    iso = 0.0 if dtype == "f32" else 30000.0
-    G, keep = lib.make_grid(data)
-    M = L.create_MC33(G)
-    assert M
-    try:
+    with host_logic(dtype) as h:
+        lib, L, M, iso = h.lib, h.L, h.M, h.iso
+        L.MC33_calculate_smoothed_isosurface.restype = C.POINTER(lib.SURFACE)
+        L.MC33_calculate_smoothed_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CSmoothing)]
         sm = CSmoothing(10, 0.5, -0.53, 1)
         assert not L.MC33_calculate_smoothed_isosurface(M, lib.real(iso), C.byref(sm)) and M.contents.memoryfault == 0
         assert not L.MC33_calculate_smoothed_isosurface(M, lib.real(iso), None)
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         L.free_surface_memory(S)
-    finally:
-        L.free_MC33(M)
-        L.free_memory_grd(G)
-        del keep

@@ -12,17 +12,16 @@ import re
 import struct
 import subprocess
 import sys
-import tempfile
 import textwrap
 
 import numpy as np
 import pytest
 
-import fixtures as fx
 import layouts
 import spectrum_cases as sc
 import spectrum_oracle as so
 from mc33_capi import MC33Lib, product_path
+from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, kernels_of, offsets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -164,42 +163,27 @@ def test_new_names_are_declared():
 
 @pytest.mark.parametrize("dtype", TYPES)
 def test_every_library_exports_the_new_names(dtype):
-    for ortho, nneg in ((False, False), (True, False), (False, True), (True, True)):
-        path = product_path(dtype, ortho=ortho, nneg=nneg)
-        assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
-        syms = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        defined = set(line.split()[-1] for line in syms.splitlines() if line.split())
-        for n in HIP_NAMES + C_NAMES:
-            assert n in defined, "%s not exported by %s" % (n, os.path.basename(path))
+    assert_exported(HIP_NAMES + C_NAMES, dtype)
 
 
 @pytest.mark.parametrize("dtype", TYPES)
 def test_spectrum_kernels_are_in_the_code_object(dtype):
-    from test_code_objects import kernel_metadata
     ctype = {"f32": "float", "f64": "double", "u8": "unsigned char", "u16": "unsigned short", "u32": "unsigned int"}[dtype]
     pack = {"u8": 4, "u16": 2}.get(dtype)
-    ks = {k["pretty"]: k for k in kernel_metadata(product_path(dtype))}
+    ks = kernels_of(dtype)
     mine = sorted(n for n in ks if n.startswith("k_sp_"))
     want = ["k_sp_init", "k_sp_spectrum<%s, 1>" % ctype] + (["k_sp_spectrum<%s, %d>" % (ctype, pack)] if pack else [])
     assert mine == sorted(want), (mine, sorted(ks))
-    for name in mine:
-        assert ks[name]["private_segment_fixed_size"] == 0 and ks[name]["vgpr_spill_count"] == 0, (name, ks[name])
-        # every counter, the isovalues and both rank planes in LDS: eight blocks and more to a CU
-        assert ks[name]["group_segment_fixed_size"] <= 8192 and ks[name]["vgpr_count"] <= 96, (name, ks[name])
+    assert_kernels(dtype, mine, max_vgprs=96)
+    for name in mine:  # every counter, the isovalues and both rank planes in LDS: eight blocks and more to a CU
+        assert ks[name]["group_segment_fixed_size"] <= 8192, (name, ks[name])
 
 
 def test_python_structs_match_the_header():
     from mc33_c_library_amd.api import Spectrum, SpectrumInfo
     hf = ("isos", "n", "cut_cells", "histogram", "points", "cells", "nan_samples", "sample_min", "sample_max")
     cf = ("points", "cells", "nan_samples", "sample_min", "sample_max")
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"marching_cubes_33.h\"\n#include \"mc33_hip.h\"\nint main(void) {\n"
-    src += "\tprintf(\"%zu" + " %zu" * len(hf) + "\\n\", sizeof(mc33hip_spectrum), " + ", ".join("offsetof(mc33hip_spectrum, %s)" % f for f in hf) + ");\n"
-    src += "\tprintf(\"%zu" + " %zu" * len(cf) + "\\n\", sizeof(mc33_spectrum_info), " + ", ".join("offsetof(mc33_spectrum_info, %s)" % f for f in cf) + ");\n"
-    src += "\treturn 0;\n}\n"
-    with tempfile.TemporaryDirectory() as tmp:
-        open(os.path.join(tmp, "sizes.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(tmp, "sizes.c"), "-o", os.path.join(tmp, "sizes")])
-        want = [int(x) for x in subprocess.check_output([os.path.join(tmp, "sizes")], text=True).split()]
+    want = c_layout(["sizeof(mc33hip_spectrum)"] + offsets("mc33hip_spectrum", hf) + ["sizeof(mc33_spectrum_info)"] + offsets("mc33_spectrum_info", cf))
     got = [C.sizeof(Spectrum)] + [getattr(Spectrum, f).offset for f in hf] + [C.sizeof(SpectrumInfo)] + [getattr(SpectrumInfo, f).offset for f in cf]
     assert got == want
     assert [C.sizeof(CSpectrumInfo)] + [getattr(CSpectrumInfo, f).offset for f in cf] == want[len(hf) + 1:]
@@ -211,19 +195,12 @@ def test_python_structs_match_the_header():
 def test_host_logic_library_refuses_the_spectrum(dtype):
     """MC33_grid_spectrum returns -1 whatever it is given, writes nothing, and leaves the object byte for byte as it was; the
     ladder is host C and works."""
-    from mc33_emu import build_hostlogic
-    lib = MC33Lib(build_hostlogic(dtype), dtype)
-    L = lib.lib
-    L.MC33_grid_spectrum.restype = C.c_int
-    L.MC33_grid_spectrum.argtypes = [C.POINTER(lib.MC33), C.POINTER(lib.real), C.c_uint, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(CSpectrumInfo)]
-    L.MC33_isovalue_ladder.restype = C.c_int
-    L.MC33_isovalue_ladder.argtypes = [C.c_double, C.c_double, C.c_uint, C.POINTER(lib.real)]
-    data = fx.cos_field(12)[0] if dtype == "f32" else fx.cos_field_u16(12, 12, 12)
-    iso = 0.0 if dtype == "f32" else 30000.0
-    G, keep = lib.make_grid(data)
-    M = L.create_MC33(G)
-    assert M
-    try:
+    with host_logic(dtype, n=12) as h:
+        lib, L, M, iso = h.lib, h.L, h.M, h.iso
+        L.MC33_grid_spectrum.restype = C.c_int
+        L.MC33_grid_spectrum.argtypes = [C.POINTER(lib.MC33), C.POINTER(lib.real), C.c_uint, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(CSpectrumInfo)]
+        L.MC33_isovalue_ladder.restype = C.c_int
+        L.MC33_isovalue_ladder.argtypes = [C.c_double, C.c_double, C.c_uint, C.POINTER(lib.real)]
         nV, nT = C.c_uint(), C.c_uint()
         L.size_of_isosurface(M, lib.real(iso), C.byref(nV), C.byref(nT))
         assert nV.value > 0
@@ -242,10 +219,6 @@ def test_host_logic_library_refuses_the_spectrum(dtype):
         assert (n2.value, t2.value) == (nV.value, nT.value)
         buf = (lib.real * 8)()
         assert L.MC33_isovalue_ladder(0.0, 1.0, 3, buf) == 3 and [buf[k] for k in range(3)] == [0.25, 0.5, 0.75]
-    finally:
-        L.free_MC33(M)
-        L.free_memory_grd(G)
-        del keep
 
 
 # ---- the kernel's text compiled for the host ---------------------------------------------------------------------------------------------

@@ -6,15 +6,13 @@ import collections
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import fixtures as fx
 import measure_oracle as mo
 import topology_oracle as to
-from mc33_capi import MC33Lib, product_path
+from mesh_checks import assert_exported, assert_kernels, host_logic, reference_mesh
 from test_mesh_common_cpu import launched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,10 +45,7 @@ _cache = {}
 def figures(reflibs, name):
     """(surface dict, component table, edge table) of the oracle on the reference's mesh of a fixture, made once"""
     if name not in _cache:
-        field, iso, (nV, nT, _, _, _) = mo.FIXTURES[name]
-        data, r0, d = field()
-        s = reflibs["f32"].isosurface(data, iso, r0, d)
-        assert (s.nV, s.nT) == (nV, nT)
+        s = reference_mesh(reflibs, name)[4]
         lab = mo.label_components(s.T, s.nV)[0]
         e = to.EdgeTable(s.T, s.nV)
         surf, tab = to.surface(s.T, s.nV, lab, e)
@@ -131,22 +126,11 @@ def test_new_names_are_declared():
 
 @pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
 def test_every_library_exports_the_new_names(dtype):
-    for ortho, nneg in ((False, False), (True, False), (False, True), (True, True)):
-        path = product_path(dtype, ortho=ortho, nneg=nneg)
-        assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
-        syms = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        defined = set(line.split()[-1] for line in syms.splitlines() if line.split())
-        for n in HIP_NAMES + C_NAMES:
-            assert n in defined, "%s not exported by %s" % (n, os.path.basename(path))
+    assert_exported(HIP_NAMES + C_NAMES, dtype)
 
 
 def test_topology_kernels_are_in_the_code_object():
-    from test_code_objects import kernel_metadata
-    ks = {k["pretty"].split("(")[0]: k for k in kernel_metadata(product_path("f32"))}
-    for name in KERNELS:
-        assert name in ks, (name, sorted(ks))
-        assert ks[name]["private_segment_fixed_size"] == 0 and ks[name]["vgpr_spill_count"] == 0, (name, ks[name])
-        assert ks[name]["vgpr_count"] <= 128, (name, ks[name])  # (two blocks of 256 per SIMD at least)
+    assert_kernels("f32", KERNELS, max_vgprs=128)  # (two blocks of 256 per SIMD at least)
 
 
 def test_python_structs_match_the_header():
@@ -181,23 +165,12 @@ def bind_topology_api(lib):
 def test_host_logic_library_refuses(dtype):
     """mc33_capi.c linked with the emulated device layer, which has neither entry point: the library still loads (they are weak
     references), both functions return -1, and the object extracts as before."""
-    from mc33_emu import build_hostlogic
-    lib = MC33Lib(build_hostlogic(dtype), dtype)
-    bind_topology_api(lib)
-    L = lib.lib
-    data = fx.cos_field(20)[0] if dtype == "f32" else fx.cos_field_u16(20, 20, 20)
-    iso = 0.0 if dtype == "f32" else 30000.0
-    G, keep = lib.make_grid(data)
-    M = L.create_MC33(G)
-    assert M
-    try:
+    with host_logic(dtype) as h:
+        lib, L, M, iso = h.lib, h.L, h.M, h.iso
+        bind_topology_api(lib)
         t, rows, n = CTopology(), (CComponentTopology * 4)(), C.c_uint(7)
         assert L.MC33_isosurface_topology(M, lib.real(iso), C.byref(t)) == -1
         assert L.MC33_component_topology(M, lib.real(iso), rows, 4, C.byref(n)) == -1 and n.value == 0
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         L.free_surface_memory(S)
-    finally:
-        L.free_MC33(M)
-        L.free_memory_grd(G)
-        del keep
