@@ -287,6 +287,50 @@ typedef struct { unsigned n; double plane[6][4]; } mc33_clip;   /* the coordinat
 surface *MC33_calculate_clipped_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_clip *planes);
 int MC33_clip_box(const double lo[3], const double hi[3], mc33_clip *out);
 
+/* extension (not in the reference): the section of an isosurface by a plane - the outline a viewer draws over a slice image, its
+ * length, the area it encloses, and the same along a stack of parallel planes: the cross-sectional area profile of a vessel, a
+ * bone or a pore.  The surface stays in device memory; only the outline, or a few numbers per plane, come back.  plane[4] = a, b,
+ * c, w in the coordinates of surface.V (inclined grids are accepted); the section is the boundary that
+ * MC33_calculate_clipped_isosurface opens with the same plane.  The exact definition is in mc33_hip.h (mc33hip_section_surface).
+ * MC33_section_isosurface extracts, sections on the device, colours the points - each at its own position - when a property grid
+ * and a colour map are set (DefaultColorMC otherwise) and downloads the section into malloc blocks that MC33_free_section
+ * releases: P (nP points), S (nS directed segments a -> b of point indices, in the order of the surface's triangles: the
+ * orientation follows the winding), contour (per point: the smallest point index joined to it through segments), next (per point:
+ * the end of the one segment that starts there, 0xFFFFFFFF when none or several do - a closed contour is walked with it), color,
+ * the counts, length, area and the plane.  area is SIGNED: area has the sign of the volume that MC33_measure_isosurface reports for
+ * a closed surface - it follows the stored winding, so the MC33_NORMAL_NEG flavours give the opposite sign (for the reference's
+ * README sphere, samples growing outwards, the plain libraries give volume < 0 and area < 0) - and |area| is the enclosed area only
+ * where every contour is closed (closed_contours == contours).  A plane that misses gives an empty section, not a failure.
+ * MC33_section_contours fills one row per contour, in ascending order of root (= the contour word of its points): 0; -1 on
+ * failure; -2 when the table is too small - *contours is filled, the table untouched (capacity 0 with a NULL table asks for the
+ * number).  The double columns are added with atomics on the device and may differ in their last bits from call to call.
+ * MC33_section_profile: n <= 255 finite offsets w_k, strictly ascending; out[k] holds what MC33_section_isosurface would report
+ * for the plane (normal, w_k) - segments exactly, length and area up to the order of their additions - from one pass over the
+ * triangles: 0, or -1.
+ * All three set the extractor's iso and leave nV, nT and memoryfault alone, as the measuring calls do.  NULL / -1 and the extractor
+ * untouched: a null pointer, a plane or normal with a component that is not finite or with a, b, c all zero, bad offsets, an
+ * extractor spread over several devices. */
+typedef struct {
+	unsigned nP, nS;
+	MC33_real (*P)[3];
+	unsigned (*S)[2];
+	unsigned *contour, *next;
+	int *color;
+	unsigned on_points, cut_points, contours, closed_contours, open_ends, branch_points, degenerate_segments;
+	double length, area;
+	double plane[4];
+} mc33_section;
+typedef struct {
+	unsigned root, points, segments, open_ends, branch_points;
+	int closed;
+	double length, area;
+} mc33_contour;
+typedef struct { unsigned long long segments; double length, area; } mc33_section_level;
+mc33_section *MC33_section_isosurface(MC33 *extractor, MC33_real isovalue, const double plane[4]);
+void MC33_free_section(mc33_section *section);
+int MC33_section_contours(MC33 *extractor, MC33_real isovalue, const double plane[4], mc33_contour *table, unsigned capacity, unsigned *contours);
+int MC33_section_profile(MC33 *extractor, MC33_real isovalue, const double normal[3], const double *offsets, unsigned n, mc33_section_level *out);
+
 /* extension (not in the reference): the grid resampled on the GPU before anything is extracted from it.  A Gaussian of about one
  * sample removes the speckle of CT / MRI volumes that otherwise becomes thousands of tiny components; a stride of 2 or 3 per axis
  * gives a preview surface of an eighth or a twenty-seventh of the triangles without extracting the full one first.  Per axis a

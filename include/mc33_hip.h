@@ -657,6 +657,108 @@ typedef struct {
 } mc33hip_clipping;
 int mc33hip_clip_surface(mc33hip_ctx *c, mc33hip_clipping *a);
 
+/* --- section a finished mesh by a plane on the device: contour points and segments, length, area (no counterpart in the reference) --
+ * V (nV x 3 MC33_real) and T (nT x 3 unsigned, id base 0) in device memory, n_attr <= 2 arrays of one 4-byte word per vertex, and
+ * plane[4] = a, b, c, w.  The section is the boundary that mc33hip_clip_surface opens on the same input: the outline where the
+ * plane meets the surface, as points and directed segments.  Integer atomics and exclusive sums decide who makes a point and where
+ * every row lands; the arithmetic is IEEE double, nothing fused: the outputs are an exact function of the input, two calls on the
+ * same inputs return the same bytes - the doubles included.
+ *   s[v], classes    IN / ON / OUT (a NaN is OUT) and the valid triangle: word for word those of mc33hip_clip_surface.
+ *   segment          a valid triangle with an IN corner is walked exactly as clip walks it.  Of its polygon of 3 or 4 entries the
+ *                    on-plane entries are the ON corners and the cut vertices; there are at most two, and they are neighbours in
+ *                    the cyclic polygon.  With two of them the triangle yields one directed segment a -> b, in the polygon's order:
+ *                    the orientation follows the stored winding.  A triangle without an IN corner yields nothing (triangles in the
+ *                    plane, triangles that touch it from outside).  A segment whose two ends are the same point - a triangle that
+ *                    names a vertex twice across or on the plane - is dropped and counted in degenerate_segments.
+ *   points           first the ON vertices that a kept segment names, in ascending v (on_points of them); then the cut_points cut
+ *                    points at on_points + rank: every cut edge of clip, in clip's owner order (the smallest i << 2 | e over its
+ *                    uses), with clip's t and clip's interpolation, the byte copy of the IN end when s is not finite included:
+ *                    oP[on_points + r] equals oV[kept_vertices + r] of mc33hip_clip_surface on the same input, bit for bit.
+ *                    nP_out = on_points + cut_points.  isolated_points: points no kept segment names (cut points all of whose
+ *                    segments were dropped).
+ *   attributes       an ON point carries its vertex's word; a cut point follows attr_mode[k] as in clip.
+ *   oS               nS_out x 2 unsigned into oP, in the order of the input triangles.
+ *   oLabel[p]        the smallest point index joined to p through kept segments; a point no kept segment names keeps p (optional).
+ *   oNext[p]         the end of the one kept segment that starts at p when exactly one does, otherwise 0xFFFFFFFF (optional): a
+ *                    host walks a closed loop with it in O(n).
+ *   oPointMap[v]     the point of an ON vertex that became one, otherwise 0xFFFFFFFF (nV words, optional).
+ *   contours         sets of points joined by kept segments (with at least one segment); closed_contours: those in which every
+ *                    point starts exactly one segment and ends exactly one; open_ends: points whose counts of starting and ending
+ *                    segments differ; branch_points: points that start more than one segment, or end more than one.
+ *   crossing_triangles  valid triangles with an IN and an OUT corner (clip's cut_triangles); invalid_triangles, nonfinite_vertices
+ *                    as in clip.
+ *   the doubles      per kept segment, with p = (double)oP[a] - o and q = (double)oP[b] - o, o = origin, the reference point of the
+ *                    measures: length = sum sqrt(((q-p).x^2 + (q-p).y^2) + (q-p).z^2); area_vector = sum 0.5 * (p x q) with
+ *                    (p x q) = (p.y q.z - p.z q.y, p.z q.x - p.x q.z, p.x q.y - p.y q.x); area = ((G0 a + G1 b) + G2 c) /
+ *                    sqrt((a a + b b) + c c) with G = area_vector.  The sums are taken as mc33hip_measure_surface takes its own:
+ *                    per lane, wave, block, then the rows of block partials in a fixed order - no floating-point atomic.
+ *                    area is SIGNED and follows the winding, as volume does: for a closed surface area has the sign of the volume
+ *                    that mc33hip_measure_surface reports, whichever side of the plane is called IN (negating the plane turns
+ *                    every segment and the normal round).  The reference's README sphere - samples growing outwards - extracted
+ *                    by the plain libraries has volume < 0 and area < 0; the _nneg flavours, which store the opposite winding,
+ *                    give the opposite sign.  |area| is the enclosed area only where every contour is closed.
+ *   MC33HIP_ERUNTIME   invalid triangles, as in clip: the outputs are complete without them.
+ *   MC33HIP_ECAPACITY  capP < nP_out or capS < nS_out: nP_out, nS_out, on_points, cut_points, degenerate_segments,
+ *                      crossing_triangles, invalid_triangles and nonfinite_vertices are valid, no output array is touched, and the
+ *                      counts over points and contours and the doubles are 0 (null outputs with capacity 0 are the size query; 2 nT
+ *                      points and nT segments are always enough).
+ *   MC33HIP_EINVAL     checked on the host, nothing is written: a null pointer where a size is not zero (oLabel, oNext and
+ *                      oPointMap may be NULL); nV or nT above 2^32-1; n_attr > 2; a mode of a used attribute that is neither; a
+ *                      plane with a component that is not finite or with a, b, c all zero; an output byte range (capP rows of oP,
+ *                      oLabel, oNext and the attributes, capS of oS, nV words of oPointMap) that meets an input range or another
+ *                      output range.
+ *   MC33HIP_ENOMEM     the scratch cannot be had.
+ *   nT == 0 is success with every count 0 (oPointMap, when given, is all 0xFFFFFFFF).
+ * The call enqueues on the context's stream, waits once, and brings the integers and doubles to the host.  Scratch, with the
+ * context until mc33hip_destroy: clip's (it is shared with mc33hip_clip_surface) and 1 byte per vertex, 1 per triangle, a word per
+ * 1024 triangles, 17 bytes per point of min(capP, 2 nT) and 32 bytes per block of the sums. */
+typedef struct {
+	const void *V, *T;  unsigned long long nV, nT;       /* in (device): nV x 3 MC33_real, nT x 3 unsigned */
+	const void *attr[2]; unsigned n_attr;                /* in: <= 2 arrays of nV 4-byte words (device) */
+	int attr_mode[2];                                    /* MC33HIP_CLIP_COPY 0, MC33HIP_CLIP_LERP_F32 1 */
+	double plane[4];                                     /* a, b, c, w: s = a x + b y + c z + w */
+	void *oP;  void *oS;  void *oAttr[2];                /* out (device): capP x 3 MC33_real, capS x 2 unsigned, capP words each */
+	unsigned *oLabel, *oNext /* capP words, or NULL */, *oPointMap /* nV words, or NULL */;
+	unsigned long long capP, capS;
+	unsigned long long nP_out, nS_out, on_points, cut_points, isolated_points, degenerate_segments, crossing_triangles,
+	                   invalid_triangles, nonfinite_vertices, contours, closed_contours, open_ends, branch_points;   /* filled */
+	double length, area_vector[3], area, origin[3];      /* filled */
+} mc33hip_section;
+int mc33hip_section_surface(mc33hip_ctx *c, mc33hip_section *a);
+
+/* The contour table of a section: from its oP (nP x 3 MC33_real), oS (nS x 2 unsigned), oLabel (nP words) in device memory and the
+ * plane, one row per contour - per label set that holds a segment - in ascending order of root, as mc33hip_measure_components
+ * lists components.  A segment belongs to the label of its start.  points: the points of the set that a segment names; open_ends,
+ * branch_points as in mc33hip_section_surface, over the set; closed: 1 where every point of the set starts exactly one segment and
+ * ends exactly one.  length and area are the sums of the section's own per-segment terms - the segment's term of area is ((g.x a +
+ * g.y b) + g.z c) / sqrt((a a + b b) + c c), g = 0.5 * (p x q) - added with floating-point atomics: they may differ in their last
+ * bits from call to call, and their sums over the rows from the totals of the section.  host_table / capacity / *contours work as
+ * for the component table: *contours is always filled; capacity < *contours is MC33HIP_ECAPACITY and leaves the table untouched
+ * (capacity 0 with a NULL table is the size query).  MC33HIP_ERUNTIME: segments that name a point >= nP, or a label >= nP, are
+ * counted (the words of the measuring calls) and left out.  MC33HIP_EINVAL: a null pointer where a size is not zero, nP or nS above
+ * 2^32-1, a plane that is not finite or has no normal. */
+typedef struct {
+	unsigned root, points, segments, open_ends, branch_points;
+	int closed;
+	double length, area;
+} mc33hip_contour;
+int mc33hip_section_contours(mc33hip_ctx *c, const void *dP, unsigned long long nP, const void *dS, unsigned long long nS,
+                             const unsigned *dLabel, const double plane[4], mc33hip_contour *host_table,
+                             unsigned long long capacity, unsigned long long *contours);
+
+/* The same along a stack of parallel planes, without geometry: V, T as above, a normal (a, b, c) and a HOST array of n <= 255
+ * finite offsets w_k, strictly ascending.  HOST outputs: segments[n], length[n], area[n] and *invalid_triangles.  One pass over T,
+ * V gathered once per triangle, no table: t depends only on {lo, hi}, so every triangle computes the same cut point.  s_k[v] is
+ * formed as ((x a + y b) + z c) + w_k, so the classes of plane k are those of mc33hip_section_surface for plane (a, b, c, w_k) bit
+ * for bit: segments[k] == nS_out of that call, exactly; length[k] and area[k] are sums of the very same terms, but added with
+ * floating-point atomics - they may differ from that call, and from call to call, in their last bits.
+ *   MC33HIP_EINVAL   n > 255; an offset that is not finite or not above the one before; a null pointer where a size is not
+ *                    zero; a normal with a component that is not finite or all zero; nV or nT above 2^32-1.
+ *   MC33HIP_ERUNTIME invalid triangles: counted and left out.  With n == 0 or nT == 0 nothing is read. */
+int mc33hip_section_ladder(mc33hip_ctx *c, const void *dV, unsigned long long nV, const void *dT, unsigned long long nT,
+                           const double normal[3], const double *offsets, unsigned n, unsigned long long *segments, double *length,
+                           double *area, unsigned long long *invalid_triangles);
+
 /* Plain device allocations on the context's device (for language bindings). */
 int mc33hip_device_alloc(mc33hip_ctx *c, void **dptr, size_t bytes);
 int mc33hip_device_free(mc33hip_ctx *c, void *dptr);

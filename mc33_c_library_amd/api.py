@@ -121,6 +121,41 @@ CLIP_COUNTS = ("nV_out", "nT_out", "kept_vertices", "cut_vertices", "on_plane_ve
                "invalid_triangles", "nonfinite_vertices")
 
 
+class Sectioning(C.Structure):
+    """mc33hip_section (include/mc33_hip.h)"""
+    _fields_ = [("V", C.c_void_p), ("T", C.c_void_p), ("nV", C.c_ulonglong), ("nT", C.c_ulonglong),
+                ("attr", C.c_void_p * 2), ("n_attr", C.c_uint), ("attr_mode", C.c_int * 2), ("plane", C.c_double * 4),
+                ("oP", C.c_void_p), ("oS", C.c_void_p), ("oAttr", C.c_void_p * 2), ("oLabel", C.c_void_p), ("oNext", C.c_void_p), ("oPointMap", C.c_void_p),
+                ("capP", C.c_ulonglong), ("capS", C.c_ulonglong)] + \
+               [(n, C.c_ulonglong) for n in ("nP_out", "nS_out", "on_points", "cut_points", "isolated_points", "degenerate_segments", "crossing_triangles",
+                                             "invalid_triangles", "nonfinite_vertices", "contours", "closed_contours", "open_ends", "branch_points")] + \
+               [("length", C.c_double), ("area_vector", C.c_double * 3), ("area", C.c_double), ("origin", C.c_double * 3)]
+
+
+class Contour(C.Structure):
+    """mc33hip_contour (include/mc33_hip.h), mc33_contour (include/marching_cubes_33.h): a row of the contour table"""
+    _fields_ = [("root", C.c_uint), ("points", C.c_uint), ("segments", C.c_uint), ("open_ends", C.c_uint), ("branch_points", C.c_uint), ("closed", C.c_int),
+                ("length", C.c_double), ("area", C.c_double)]
+
+
+class SurfaceSection(C.Structure):
+    """mc33_section (include/marching_cubes_33.h): the malloc blocks of MC33_section_isosurface; MC33_real is float here - the
+    double library's P is read through its own pointer type"""
+    _fields_ = [("nP", C.c_uint), ("nS", C.c_uint), ("P", C.c_void_p), ("S", C.POINTER(C.c_uint * 2)), ("contour", C.POINTER(C.c_uint)), ("next", C.POINTER(C.c_uint)),
+                ("color", C.POINTER(C.c_int))] + \
+               [(n, C.c_uint) for n in ("on_points", "cut_points", "contours", "closed_contours", "open_ends", "branch_points", "degenerate_segments")] + \
+               [("length", C.c_double), ("area", C.c_double), ("plane", C.c_double * 4)]
+
+
+class SectionLevel(C.Structure):
+    """mc33_section_level (include/marching_cubes_33.h): one plane of MC33_section_profile"""
+    _fields_ = [("segments", C.c_ulonglong), ("length", C.c_double), ("area", C.c_double)]
+
+
+SECTION_COUNTS = ("nP_out", "nS_out", "on_points", "cut_points", "isolated_points", "degenerate_segments", "crossing_triangles", "invalid_triangles",
+                  "nonfinite_vertices", "contours", "closed_contours", "open_ends", "branch_points")
+
+
 class Resampling(C.Structure):
     """mc33hip_resampling (include/mc33_hip.h): taps are HOST arrays of doubles, NULL = the single tap 1.0"""
     _fields_ = [("taps", C.POINTER(C.c_double) * 3), ("ntaps", C.c_uint * 3), ("stride", C.c_uint * 3)]
@@ -156,7 +191,7 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_surface_topology", "mc33hip_component_topology", "mc33hip_compact_components",
            "mc33hip_smooth_surface", "mc33hip_vertex_normals", "mc33hip_smooth_timing", "mc33hip_simplify_surface",
            "mc33hip_resampled_size", "mc33hip_resample_grid", "mc33hip_context_device", "mc33hip_grid_spectrum",
-           "mc33hip_clip_surface"]
+           "mc33hip_clip_surface", "mc33hip_section_surface", "mc33hip_section_contours", "mc33hip_section_ladder"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -169,7 +204,8 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "MC33_calculate_simplified_isosurface",
                  "MC33_gaussian_taps", "MC33_create_resampled", "MC33_resampled_grid",
                  "MC33_grid_spectrum", "MC33_isovalue_ladder",
-                 "MC33_calculate_clipped_isosurface", "MC33_clip_box"]
+                 "MC33_calculate_clipped_isosurface", "MC33_clip_box",
+                 "MC33_section_isosurface", "MC33_free_section", "MC33_section_contours", "MC33_section_profile"]
 
 
 class MC33Error(RuntimeError):
@@ -254,6 +290,10 @@ def load_library(dtype="f32"):
     lib.MC33_isovalue_ladder.argtypes = [C.c_double, C.c_double, C.c_uint, V]
     lib.mc33hip_clip_surface.argtypes = [V, P(Clipping)]
     lib.MC33_clip_box.argtypes = [P(C.c_double * 3), P(C.c_double * 3), P(SurfaceClip)]
+    lib.mc33hip_section_surface.argtypes = [V, P(Sectioning)]
+    lib.mc33hip_section_contours.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V, P(C.c_double * 4), V, C.c_ulonglong, P(C.c_ulonglong)]
+    lib.mc33hip_section_ladder.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, P(C.c_double * 3), P(C.c_double), C.c_uint, P(C.c_ulonglong), P(C.c_double),
+                                           P(C.c_double), P(C.c_ulonglong)]
     _libs[dtype] = lib
     return lib
 
@@ -302,6 +342,17 @@ def clip_box(lo, hi):
     if r != 0:
         raise ValueError("MC33_clip_box refused lo=%r hi=%r" % (lo, hi))
     return [tuple(out.plane[k][j] for j in range(4)) for k in range(out.n)]
+
+
+class SectionResult:
+    """What DeviceGrid.section returns (include/mc33_hip.h: mc33hip_section_surface): P, S, attrs, label, next, point_map (device
+    tensors), plane, info (the dict of the thirteen counts), length, area_vector, area, origin."""
+
+    def __init__(self, a, P, S, attrs, label, nxt, pmap):
+        self.P, self.S, self.attrs, self.label, self.next, self.point_map = P, S, attrs, label, nxt, pmap
+        self.plane = tuple(a.plane)
+        self.info = {n: int(getattr(a, n)) for n in SECTION_COUNTS}
+        self.length, self.area, self.area_vector, self.origin = a.length, a.area, tuple(a.area_vector), tuple(a.origin)
 
 
 class GridSpectrum:
@@ -887,6 +938,81 @@ class DeviceGrid:
             infos.append(info)
         out = (V, N, T, infos)
         return out + (self.sample_property(V),) if with_property else out
+
+    # -- section a finished mesh by planes on the device (mc33_hip.h: mc33hip_section_surface and its siblings) ----------------------
+    def section(self, V, T, plane, attrs=(), attr_modes=()):
+        """The contour where the plane (a, b, c, w) meets the mesh V [n, 3], T [m, 3] (device tensors, as extract() returns them):
+        the boundary clip() opens on the same input, as points and directed segments.  Returns a SectionResult: exact-size
+        device tensors P [p, 3], S [s, 2] (int32, the uint32 words of point indices), attrs (attr_modes as for clip), label and
+        next (int32 [p]), point_map (int32 [n]), the thirteen counts in .info, and length, area_vector, area (signed: it
+        follows the winding, as the volume does), origin.  Raises MC33Error(ERUNTIME) when a triangle names a vertex >= n."""
+        import torch
+        self._vertex_rows(V)
+        self._triangle_rows(T)
+        nV = V.shape[0]
+        attrs = self._attribute_words(attrs, nV)
+        modes = [CLIP_MODES[m] if isinstance(m, str) else int(m) for m in attr_modes] + [0] * (len(attrs) - len(attr_modes))
+        a = Sectioning()
+        a.V, a.T, a.nV, a.nT = V.data_ptr(), T.data_ptr(), nV, T.shape[0]
+        for k, x in enumerate(attrs[:2]):
+            a.attr[k], a.attr_mode[k] = x.data_ptr(), modes[k]
+        a.n_attr = len(attrs)
+        a.plane = (C.c_double * 4)(*[float(x) for x in plane])
+        fn = self.lib.mc33hip_section_surface
+        _check(self.lib, fn(self.ctx, C.byref(a)), allow=(ECAPACITY,))  # the size query
+        nP, nS = int(a.nP_out), int(a.nS_out)
+        P = torch.empty((max(nP, 1), 3), dtype=V.dtype, device=self.device)
+        S = torch.empty((max(nS, 1), 2), dtype=torch.int32, device=self.device)
+        attrs2 = [torch.empty((max(nP, 1),), dtype=x.dtype, device=self.device) for x in attrs]
+        label, nxt = (torch.empty((max(nP, 1),), dtype=torch.int32, device=self.device) for _ in range(2))
+        pmap = torch.empty((max(nV, 1),), dtype=torch.int32, device=self.device)
+        a.oP, a.oS, a.oLabel, a.oNext, a.oPointMap, a.capP, a.capS = P.data_ptr(), S.data_ptr(), label.data_ptr(), nxt.data_ptr(), pmap.data_ptr(), nP, nS
+        for k, x in enumerate(attrs2):
+            a.oAttr[k] = x.data_ptr()
+        _check(self.lib, fn(self.ctx, C.byref(a)))
+        return SectionResult(a, P[:nP], S[:nS], [x[:nP] for x in attrs2], label[:nP], nxt[:nP], pmap[:nV])
+
+    def section_contours(self, section):
+        """The contour table of a SectionResult - root, points, segments, open_ends, branch_points, closed, length, area per
+        contour, in ascending order of root - as a numpy structured array.  length and area are added with atomics on the
+        device: their last bits may differ from call to call."""
+        plane = (C.c_double * 4)(*section.plane)
+        return self._component_table(lambda ctx, *args: self.lib.mc33hip_section_contours(ctx, *args[:5], C.byref(plane), *args[5:]), Contour,
+                                     C.c_void_p(section.P.data_ptr()), section.P.shape[0], C.c_void_p(section.S.data_ptr()), section.S.shape[0],
+                                     C.c_void_p(section.label.data_ptr()))
+
+    def section_ladder(self, V, T, normal, offsets):
+        """What section() reports along a stack of parallel planes (a, b, c, w_k) - up to 255 offsets w_k, strictly ascending -
+        in one pass over T and without geometry: (segments uint64 [n], length float64 [n], area float64 [n]) as numpy arrays.
+        segments[k] is section()'s nS_out exactly; the doubles are added with atomics."""
+        import numpy as np
+        self._vertex_rows(V)
+        self._triangle_rows(T)
+        offsets = [float(x) for x in offsets]
+        n = len(offsets)
+        w = (C.c_double * max(n, 1))(*offsets)
+        seg, length, area = np.zeros(n, np.uint64), np.zeros(n, np.float64), np.zeros(n, np.float64)
+        bad = C.c_ulonglong()
+        nrm = (C.c_double * 3)(*[float(x) for x in normal])
+        _check(self.lib, self.lib.mc33hip_section_ladder(self.ctx, C.c_void_p(V.data_ptr()), V.shape[0], C.c_void_p(T.data_ptr()), T.shape[0], C.byref(nrm),
+                                                         C.cast(w, C.POINTER(C.c_double)), min(n, 0xFFFFFFFF),
+                                                         seg.ctypes.data_as(C.POINTER(C.c_ulonglong)) if n else None,
+                                                         length.ctypes.data_as(C.POINTER(C.c_double)) if n else None,
+                                                         area.ctypes.data_as(C.POINTER(C.c_double)) if n else None, C.byref(bad)))
+        return seg, length, area
+
+    def extract_section(self, iso, plane, rng=None, with_property=False):
+        """extract, then section by the plane - the surface never leaves the device.  Returns the SectionResult and, with
+        with_property, the attached property grid's value at the points of the section (each at its own position) as a second
+        element."""
+        V, N, T, cnt = self._extract_rows(iso, rng)
+        sec = self.section(V[:cnt.nV], T[:cnt.nT], plane)
+        return (sec, self.sample_property(sec.P)) if with_property else sec
+
+    def section_profile(self, iso, normal, offsets, rng=None):
+        """extract, then section_ladder(normal, offsets): the cross-section profile of the isosurface - (segments, length, area)."""
+        V, N, T, cnt = self._extract_rows(iso, rng)
+        return self.section_ladder(V[:cnt.nV], T[:cnt.nT], normal, offsets)
 
     # -- the grid resampled into a second device grid (mc33_hip.h: mc33hip_resample_grid) ------------------------------------------
     def _resampling(self, taps, stride, sigma):

@@ -74,6 +74,10 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_smooth_surface
 #pragma weak mc33hip_simplify_surface
 #pragma weak mc33hip_clip_surface
+#pragma weak mc33hip_section_surface
+#pragma weak mc33hip_section_contours
+#pragma weak mc33hip_section_ladder
+#pragma weak mc33hip_download /* (the host layer uses it for the blocks of a section only) */
 /* ... and the resampling ones (MC33_create_resampled): without them it returns NULL */
 #pragma weak mc33hip_resampled_size
 #pragma weak mc33hip_resample_grid
@@ -1413,6 +1417,130 @@ surface *MC33_calculate_clipped_isosurface(MC33 *M, MC33_real iso, const mc33_cl
 		if (!clip_plane_ok(cl->plane[k]))
 			return 0; /* (what mc33hip_clip_surface refuses, before anything is extracted) */
 	return derived_call(p, iso, clipped_surface, cl);
+}
+
+/* --- extension: the section of an isosurface by a plane ------------------------------------------------------------------------
+ * The surface goes into staging set 0, its section into the arrays of set 1 under other names - the points in dV, the segments
+ * in dT (12 bytes a row there: capT rows hold capT segments and more), the contour words and the next words side by side in dN
+ * (three words a row there), the colours in dC - first with the set as it stands and, when that is refused for room, once more
+ * with the set grown to the sizes that came back. */
+#define SECTION_ENTRIES (mc33hip_section_surface && mc33hip_section_contours && mc33hip_section_ladder && mc33hip_color_vertices && mc33hip_download)
+_Static_assert(sizeof(mc33_contour) == sizeof(mc33hip_contour) && offsetof(mc33_contour, length) == offsetof(mc33hip_contour, length),
+               "mc33_contour and mc33hip_contour are one layout");
+
+static int section_to_staging(mc33_private *p, MC33_real iso, const double plane[4], mc33hip_section *a) {
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0], *h = &s->set[1];
+	mc33hip_counts cnt;
+	p->pub.iso = iso;
+	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK)
+		return -1;
+	memset(a, 0, sizeof *a);
+	a->V = g->dV; a->T = g->dT; a->nV = cnt.nV; a->nT = cnt.nT;
+	for (int j = 0; j != 4; j++) a->plane[j] = plane[j];
+	int rc = MC33HIP_ECAPACITY;
+	for (int attempt = 0; attempt != 2 && rc == MC33HIP_ECAPACITY; attempt++) {
+		if (attempt && staging_room(s, h, a->nP_out, a->nS_out))
+			return -1;
+		a->oP = h->dV; a->oS = h->dT; a->capP = h->capV; a->capS = h->capT;
+		a->oLabel = (unsigned *)h->dN; a->oNext = h->dN ? (unsigned *)h->dN + h->capV : 0;
+		rc = mc33hip_section_surface(s->ctx, a);
+	}
+	return rc == MC33HIP_OK ? 0 : -1;
+}
+
+void MC33_free_section(mc33_section *S) {
+	if (S) {
+		free(S->P); free(S->S); free(S->contour); free(S->next); free(S->color);
+		free(S);
+	}
+}
+
+mc33_section *MC33_section_isosurface(MC33 *M, MC33_real iso, const double plane[4]) {
+	mc33_private *p = one_slab(M, SECTION_ENTRIES);
+	if (!p || !plane || !clip_plane_ok(plane))
+		return 0;
+	mc33_slab *s = &p->slab[0];
+	struct staging *h = &s->set[1];
+	mc33hip_section a;
+	if (section_to_staging(p, iso, plane, &a))
+		return 0;
+	const size_t nP = (size_t)a.nP_out, nS = (size_t)a.nS_out;
+	const int paint = coloured(p) && nP;
+	if (paint) { /* a point gets the colour of its own position */
+		p->nan_color = DefaultColorMC;
+		if (enqueue_colors(s, h, nP) != MC33HIP_OK)
+			return 0;
+	}
+	mc33_section *S = (mc33_section *)calloc(1, sizeof *S);
+	if (!S)
+		return 0;
+	S->P = malloc((nP ? nP : 1) * sizeof *S->P); S->S = malloc((nS ? nS : 1) * sizeof *S->S);
+	S->contour = (unsigned *)malloc((nP ? nP : 1) * sizeof(unsigned)); S->next = (unsigned *)malloc((nP ? nP : 1) * sizeof(unsigned));
+	S->color = (int *)malloc((nP ? nP : 1) * sizeof(int));
+	int ok = S->P && S->S && S->contour && S->next && S->color;
+	if (ok && nP)
+		ok = mc33hip_download(s->ctx, S->P, h->dV, nP * sizeof *S->P) == MC33HIP_OK && mc33hip_download(s->ctx, S->contour, a.oLabel, nP * sizeof(unsigned)) == MC33HIP_OK &&
+		     mc33hip_download(s->ctx, S->next, a.oNext, nP * sizeof(unsigned)) == MC33HIP_OK;
+	if (ok && nS)
+		ok = mc33hip_download(s->ctx, S->S, h->dT, nS * sizeof *S->S) == MC33HIP_OK;
+	if (ok && paint)
+		ok = mc33hip_download(s->ctx, S->color, h->dC, nP * sizeof(int)) == MC33HIP_OK;
+	if (!ok) {
+		MC33_free_section(S);
+		return 0;
+	}
+	if (!paint)
+		for (size_t k = 0; k != nP; k++) S->color[k] = DefaultColorMC;
+	S->nP = (unsigned)nP; S->nS = (unsigned)nS;
+	S->on_points = (unsigned)a.on_points; S->cut_points = (unsigned)a.cut_points; S->contours = (unsigned)a.contours;
+	S->closed_contours = (unsigned)a.closed_contours; S->open_ends = (unsigned)a.open_ends; S->branch_points = (unsigned)a.branch_points;
+	S->degenerate_segments = (unsigned)a.degenerate_segments;
+	S->length = a.length; S->area = a.area;
+	for (int j = 0; j != 4; j++) S->plane[j] = plane[j];
+	return S;
+}
+
+int MC33_section_contours(MC33 *M, MC33_real iso, const double plane[4], mc33_contour *table, unsigned capacity, unsigned *contours) {
+	mc33_private *p = one_slab(M, SECTION_ENTRIES);
+	if (contours) *contours = 0;
+	if (!p || !plane || !clip_plane_ok(plane) || (capacity && !table))
+		return -1;
+	mc33_slab *s = &p->slab[0];
+	mc33hip_section a;
+	if (section_to_staging(p, iso, plane, &a))
+		return -1;
+	if (contours) *contours = (unsigned)a.contours;
+	if (capacity < a.contours)
+		return -2;
+	if (!a.contours)
+		return 0;
+	unsigned long long n = 0;
+	return mc33hip_section_contours(s->ctx, a.oP, a.nP_out, a.oS, a.nS_out, a.oLabel, plane, (mc33hip_contour *)table, capacity, &n) == MC33HIP_OK ? 0 : -1;
+}
+
+int MC33_section_profile(MC33 *M, MC33_real iso, const double normal[3], const double *offsets, unsigned n, mc33_section_level *out) {
+	mc33_private *p = one_slab(M, SECTION_ENTRIES);
+	if (!p || !normal || n > 255u || (n && (!offsets || !out)))
+		return -1;
+	const double pl[4] = {normal[0], normal[1], normal[2], 0.0};
+	if (!clip_plane_ok(pl))
+		return -1;
+	for (unsigned k = 0; k != n; k++)
+		if (!clip_finite(offsets[k]) || (k && !(offsets[k] > offsets[k - 1])))
+			return -1; /* (what mc33hip_section_ladder refuses, before anything is extracted) */
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0];
+	mc33hip_counts cnt;
+	unsigned long long seg[255], bad = 0;
+	double len[255], area[255];
+	p->pub.iso = iso;
+	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK)
+		return -1;
+	if (mc33hip_section_ladder(s->ctx, g->dV, cnt.nV, g->dT, cnt.nT, normal, offsets, n, seg, len, area, &bad) != MC33HIP_OK)
+		return -1;
+	for (unsigned k = 0; k != n; k++) { out[k].segments = seg[k]; out[k].length = len[k]; out[k].area = area[k]; }
+	return 0;
 }
 
 void free_surface_memory(surface *S) { /* MC:84-92 */

@@ -53,6 +53,9 @@
 //                   k_clip_* - a finished V, N, T cut by a plane: classes, a table of cut edges filled by 64-bit compare-and-swap and
 //                   atomicMin of the owner, three exclusive scans, three writing passes; k_clip_tri is its hot path
 //                   (mc33_clip.hip.h).
+//                   k_section_* - a finished V, T met by a plane: clip's classes, table and owners as they stand, then the contour
+//                   as points and directed segments, a union-find over the points, length and enclosed area in the fixed order of
+//                   the measures; k_section_ladder - many parallel planes in one pass over T (mc33_section.hip.h).
 // Before an extraction: k_rs_resample - the resident grid into a second device grid, a separable correlation of up to 17 taps per axis
 //                   with an integer stride, one pass over the source: a block stages the rows its tile of outputs needs in LDS,
 //                   sums along x and y into a ring of planes and along z out of it (mc33_resample.hip.h).
@@ -123,5 +126,6 @@ typedef float sample_t;
 #include "mc33_smooth.hip.h"
 #include "mc33_simplify.hip.h"
 #include "mc33_clip.hip.h"
+#include "mc33_section.hip.h"
 #include "mc33_resample.hip.h"
 #include "mc33_spectrum.hip.h"

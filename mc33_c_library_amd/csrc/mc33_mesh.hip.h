@@ -1,6 +1,6 @@
 // mc33_mesh.hip.h -- part of the ONE translation unit mc33_kernels.hip (builds on mc33_context.hip.h; not a header to include elsewhere):
 // what the passes over a FINISHED V, N, T in device memory have in common - mc33_measure, mc33_topology, mc33_filter, mc33_smooth,
-// mc33_simplify and mc33_clip build on it and on nothing of each other's but what their opening lines name.  DESIGN.md 18.
+// mc33_simplify, mc33_clip and mc33_section build on it and on nothing of each other's but what their opening lines name.  DESIGN.md 18.
 //   block primitives   sums and scans over the 256 lanes of a block, sums over runs of equal keys in a wave
 //   the tile scan      an exclusive scan of what the elements of an array count, in tiles of MESH_TILE: a sum per tile, one block
 //                      over the tile sums, a placing pass - or a writing kernel of a part's own that opens like one
@@ -124,8 +124,7 @@ __global__ __launch_bounds__(256) void k_mesh_tile_sum(const typename W::E *__re
 }
 
 // one block: bsum -> its exclusive sums, in place, 256 tiles a round; *total (where not null): their sum
-__global__ __launch_bounds__(256) void k_mesh_scan_top(uint32_t *__restrict__ bsum, uint64_t n, unsigned long long *__restrict__ total) {
-	__shared__ uint32_t sh[256];
+__device__ __forceinline__ void mesh_scan_top_block(uint32_t *__restrict__ bsum, uint64_t n, unsigned long long *__restrict__ total, uint32_t *sh /* [256] */) {
 	uint32_t carry = 0u;
 	for (uint64_t base = 0; base < n; base += 256u) {
 		const uint64_t k = base + threadIdx.x;
@@ -136,6 +135,18 @@ __global__ __launch_bounds__(256) void k_mesh_scan_top(uint32_t *__restrict__ bs
 		carry += tot;
 	}
 	if (total && threadIdx.x == 0u) *total = carry;
+}
+__global__ __launch_bounds__(256) void k_mesh_scan_top(uint32_t *__restrict__ bsum, uint64_t n, unsigned long long *__restrict__ total) {
+	__shared__ uint32_t sh[256];
+	mesh_scan_top_block(bsum, n, total, sh);
+}
+// the same for three arrays of tile sums side by side, a block each: a part whose scans do not depend on each other waits for one
+// chain of rounds, not three
+struct MeshTop { uint32_t *bsum; uint64_t n; unsigned long long *total; };
+__global__ __launch_bounds__(256) void k_mesh_scan_top3(MeshTop a, MeshTop b, MeshTop c) {
+	__shared__ uint32_t sh[256];
+	const MeshTop t = blockIdx.x == 0u ? a : blockIdx.x == 1u ? b : c;
+	mesh_scan_top_block(t.bsum, t.n, t.total, sh);
 }
 
 // what the placing pass leaves in out[e]: the sum below e (a rank); that where e counts and MESH_NONE where it does not (the
@@ -258,7 +269,7 @@ struct MeshOp {
 	void (*release)(void *state);  // the device arrays the state holds; it is the key of the registration too
 };
 struct MeshHost {
-	MeshOp op[8];               // topology, filter, smooth, simplify, clip, resample, spectrum - and one to spare: a part beyond that makes this larger
+	MeshOp op[10];              // topology, filter, smooth, simplify, clip, resample, spectrum, section - and two to spare: a part beyond that makes this larger
 	uint32_t nops;
 	// scratch no two parts use at once (every entry point waits before it returns), grown on demand by meas_room
 	uint8_t *d_keep;            // [nV] a flag per vertex: referenced, kept

@@ -1,0 +1,642 @@
+"""GPU tests of the sections by planes (include/mc33_hip.h: mc33hip_section_surface, mc33hip_section_contours,
+mc33hip_section_ladder; include/marching_cubes_33.h: MC33_section_isosurface and its siblings; DeviceGrid.section ...).
+
+V and T come from the reference twin (oracle/_ref) or are made up (tests/section_cases.py); the expected arrays come from
+tests/section_oracle.py, the definition in numpy.  Every integer and every output array is compared bit for bit; length and
+area_vector are held to math.fsum of the oracle's terms within measure_oracle.sum_bound of them, and two calls must return the
+same bits.  Every output of every call is canaried (tests/mesh_harness.py: CanariedCall)."""
+import ctypes as C
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import clip_oracle as co
+import fixtures as fx
+import measure_oracle as mo
+import mesh_pieces as mp
+import property_oracle as po
+import section_cases as sc
+import section_oracle as so
+from mc33_capi import MC33Lib, product_path, ref_path
+from mesh_harness import SPARE, CanariedCall, bits, ctx, device_grid, once_per_key, to_device, words  # noqa: F401 (ctx: the module's fixture)
+from test_clip_cpu import MODES, PLANES, attributes, clipped, plane_of
+from test_section_cpu import ORIGIN, c_section_api, sectioned
+from test_simplify_cpu import mesh
+
+pytestmark = pytest.mark.gpu
+
+COUNTS = so.Sectioned.COUNTS
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def within(got, terms, what):
+    """a device sum against math.fsum of the oracle's terms (skipped where a term is not finite: a vertex at infinity)"""
+    terms = np.asarray(terms, np.float64).ravel()
+    if not np.isfinite(terms).all():
+        return
+    want, bound = mo.fsum(terms), mo.sum_bound(terms)
+    assert abs(got - want) <= bound, "%s: %r, fsum %r, bound %r" % (what, got, want, bound)
+
+
+def area_within(got, terms, normal, what):
+    """a device area - ((G0 a + G1 b) + G2 c) / |n| of three device sums - against the same expression of the math.fsum sums: each
+    sum within its sum_bound, weighted by its |component| / |n|, and 8 roundings of the result for the expression itself"""
+    t = np.asarray(terms, np.float64)
+    if not np.isfinite(t).all():
+        return
+    nrm = math.sqrt(normal[0] ** 2 + normal[1] ** 2 + normal[2] ** 2)
+    want = so.area_of([mo.fsum(t[:, j]) for j in (1, 2, 3)], normal)
+    bound = sum(mo.sum_bound(t[:, j]) * abs(normal[j - 1]) for j in (1, 2, 3)) / nrm * (1 + 8 * mo.U) + 8 * mo.U * abs(want)
+    assert abs(got - want) <= bound, "%s: %r, from fsum %r, bound %r" % (what, got, want, bound)
+
+
+class Call(CanariedCall):
+    """one mc33hip_section_surface call; the default capacities are the ones that are always enough: 2 nT points, nT segments"""
+
+    def __init__(self, g, V, T, plane, attrs=(), modes=(), capP=None, capS=None, extras=True, change=None):
+        import torch
+        from mc33_c_library_amd.api import Sectioning
+        super().__init__(g)
+        self.nV, self.nT = V.shape[0], T.shape[0]
+        self.capP = 2 * self.nT if capP is None else capP
+        self.capS = self.nT if capS is None else capS
+        self.oP, self.oS = self.room(self.capP, 3, V.dtype), self.room(self.capS, 2, torch.int32)
+        self.oA = [self.room(self.capP, 0, torch.int32) for _ in attrs]
+        self.oLabel, self.oNext = (self.room(self.capP, 0, torch.int32) if extras else None for _ in range(2))
+        self.oMap = self.room(self.nV, 0, torch.int32) if extras else None
+        a = Sectioning()
+        a.V, a.T, a.nV, a.nT = V.data_ptr(), T.data_ptr(), self.nV, self.nT
+        for k, x in enumerate(attrs):
+            a.attr[k], a.oAttr[k] = x.data_ptr(), self.oA[k].data_ptr()
+            a.attr_mode[k] = int(modes[k]) if k < len(modes) else co.COPY
+        a.n_attr = len(attrs)
+        a.plane = (C.c_double * 4)(*plane)
+        a.oP, a.oS, a.capP, a.capS = self.oP.data_ptr(), self.oS.data_ptr(), self.capP, self.capS
+        if extras:
+            a.oLabel, a.oNext, a.oPointMap = self.oLabel.data_ptr(), self.oNext.data_ptr(), self.oMap.data_ptr()
+        self.keep = (V, T, attrs)
+        self.plane = tuple(plane)
+        self.call(g.lib.mc33hip_section_surface, a, change)
+        self.counts = tuple(int(getattr(a, n)) for n in COUNTS)
+        self.sizes = tuple(int(getattr(a, n)) for n in so.Sectioned.SIZES)
+        self.length, self.area, self.G, self.origin = a.length, a.area, tuple(a.area_vector), tuple(a.origin)
+
+    def outputs(self):
+        nP, nS = self.counts[0], self.counts[1]
+        return [(self.oP, nP), (self.oS, nS), (self.oLabel, nP), (self.oNext, nP), (self.oMap, self.nV)] + [(x, nP) for x in self.oA]
+
+    def doubles(self):
+        return np.array([self.length, self.area] + list(self.G), np.float64).tobytes()
+
+    def check(self, want):
+        """every integer and array bit for bit against the oracle, the sums within their bounds"""
+        assert self.counts == want.counts(), (self.counts, want.counts())
+        assert self.origin == tuple(want.origin)
+        nP, nS = want.nP_out, want.nS_out
+        self.equal_bits("oP", self.oP[:nP], want.P)
+        self.equal_bits("oS", self.oS[:nS], want.S)
+        if self.oLabel is not None:
+            self.equal_bits("oLabel", self.oLabel[:nP], want.label)
+            self.equal_bits("oNext", self.oNext[:nP], want.next)
+            self.equal_bits("oPointMap", self.oMap[:self.nV], want.pmap)
+        assert len(self.oA) == len(want.attrs)
+        for k, x in enumerate(self.oA):
+            self.equal_bits("attribute %d" % k, x[:nP], want.attrs[k])
+        within(self.length, want.terms[:, 0], "length")
+        for k in range(3):
+            within(self.G[k], want.terms[:, 1 + k], "area_vector[%d]" % k)
+        if np.isfinite(self.G).all():  # the host's own arithmetic on the device's sums: exact
+            assert self.area == so.area_of(self.G, self.plane)
+        self.spare_intact()
+
+
+@once_per_key
+def uploaded(reflibs, name):
+    """a fixture's surface and two attribute arrays on the device, uploaded once"""
+    s = mesh(reflibs, name)[4]
+    return (to_device(s.V), to_device(s.T), [to_device(x) for x in attributes(s.nV)])
+
+
+# ---- the five fixtures x the four planes, an interpolated and a copied attribute --------------------------------------------------
+
+@pytest.mark.parametrize("which", PLANES)
+@pytest.mark.parametrize("name", list(mo.FIXTURES))
+def test_fixtures_f32(reflibs, ctx, name, which):
+    s = mesh(reflibs, name)[4]
+    want = sectioned(reflibs, name, which)
+    V, T, dA = uploaded(reflibs, name)
+    plane = plane_of(s.V, which)
+    first = Call(ctx, V, T, plane, dA, MODES)
+    assert first.rc == 0, first.message
+    assert first.origin == ORIGIN
+    first.check(want)
+    again = Call(ctx, V, T, plane, dA, MODES)
+    assert again.rc == 0 and again.all_bytes() == first.all_bytes() and again.doubles() == first.doubles(), "two calls on the same inputs differ"
+    # the points behind on_points are the new vertices of mc33hip_clip_surface on the same input
+    cl = clipped(reflibs, name, which)
+    first.equal_bits("cut points", first.oP[want.on_points:want.nP_out], cl.V[cl.kept_vertices:])
+    if which == "oblique":  # no attributes, no optional outputs
+        bare = Call(ctx, V, T, plane, extras=False)
+        assert bare.rc == 0 and bare.counts == want.counts() and bare.doubles() == first.doubles()
+        bare.equal_bits("oS", bare.oS[:want.nS_out], want.S)
+        bare.spare_intact()
+
+
+# ---- made-up meshes: where the kernels can still go wrong ---------------------------------------------------------------------------
+
+def run_made_up(ctx, V, T, plane=sc.PLANE_Z, A=None):
+    A = (sc.cc.floats(V.shape[0], 21), words(V.shape[0], 22)) if A is None else A
+    want = so.section(V, T, plane, A, MODES, ORIGIN)
+    call = Call(ctx, to_device(V), to_device(T), plane, [to_device(x) for x in A], MODES)
+    assert call.rc == (0 if want.invalid_triangles == 0 else -5), call.message
+    call.check(want)
+    return want
+
+
+@pytest.mark.parametrize("nV", mp.TILE_EDGE_SIZES)
+def test_scan_tiles(ctx, nV):
+    """vertex counts around 1 and 256 tiles of the scans; the plane cuts about half of the shuffled strips"""
+    V, T = sc.tile_edge(nV, nV)
+    assert V.shape[0] == nV
+    want = run_made_up(ctx, V, T)
+    assert want.nS_out > nV // 4 and want.on_points > nV // 100 and want.cut_points > nV // 4
+
+
+def test_runs_of_crossing_triangles(ctx):
+    """runs of 1 .. 1025 consecutive crossing triangles between whole and dropped ones: neighbouring lanes hold the same edge"""
+    V, T, kinds = sc.runs(4)
+    want = run_made_up(ctx, V, T)
+    assert want.crossing_triangles == sum(sc.RUNS) == want.nS_out and want.contours == len(sc.RUNS) and want.open_ends == 2 * len(sc.RUNS)
+
+
+def test_one_edge_shared_by_5000_triangles(ctx):
+    """the cut edge {0, 1} in 5000 triangles, in both directions: one point that starts and ends thousands of segments"""
+    V, T, first = sc.shared_edge(5)
+    want = run_made_up(ctx, V, T)
+    row = np.nonzero((want.edges == [0, 1]).all(axis=1))[0]
+    assert row.size == 1
+    p = want.on_points + row[0]
+    assert want.starts[p] + want.stops[p] == 5000 and want.starts[p] > 1000 and want.stops[p] > 1000 and want.next[p] == so.NONE
+
+
+def test_copies_before_originals(ctx):
+    want = run_made_up(ctx, *sc.duplicated(6))
+    assert want.nS_out > 2000 and want.branch_points > 100
+
+
+def test_every_triangle_crossing_and_none(ctx):
+    V, T, kinds = sc.runs(8, lengths=(3000, 1, 700))
+    every = run_made_up(ctx, V, T[kinds == 0])
+    assert every.nS_out == 3701 and every.crossing_triangles == 3701
+    none = run_made_up(ctx, V, T, plane=(0.0, 0.0, 1.0, 10.0))
+    assert none.counts() == (0,) * 13
+    gone = run_made_up(ctx, V, T, plane=(0.0, 0.0, -1.0, -10.0))
+    assert gone.counts() == (0,) * 13
+
+
+def test_all_patterns_over_several_blocks(ctx):
+    """the tiny mesh 40 times: every pattern in every rotation in many lane positions; 40 invalid triangles among them"""
+    V, T, A, W = sc.tiny_repeated(40)
+    want = run_made_up(ctx, V, T, A=(A, W))
+    assert want.counts() == tuple(40 * x for x in (13, 19, 3, 10, 0, 4, 16, 1, 2, 2, 0, 12, 9)) and T.shape[0] > 1024
+
+
+def test_nonfinite_vertices(ctx):
+    V, T = sc.nonfinite(7)
+    want = run_made_up(ctx, V, T)
+    assert want.nonfinite_vertices > 200 and not np.isnan(want.P[:, 2]).any()  # (a NaN is out: it never reaches the output)
+
+
+# ---- error paths ----------------------------------------------------------------------------------------------------------------------
+
+def test_invalid_triangles_are_counted_not_read(reflibs, ctx):
+    """mesh_pieces.spoil(..., "invalid"): 300 triangles name row nV.  V is the first nV rows of a tensor with spare rows behind
+    them, so that not even a wrong kernel could touch memory this test does not own."""
+    import torch
+    from mc33_c_library_amd.api import ERUNTIME
+    s = mesh(reflibs, "blobs")[4]
+    roomV = torch.zeros((s.nV + SPARE, 3), dtype=torch.float32, device="cuda")
+    roomV[:s.nV] = to_device(s.V)
+    badT = mp.spoil(s.T, s.nV, 3, "invalid")
+    plane = plane_of(s.V, "oblique")
+    A = attributes(s.nV)
+    want = so.section(s.V, badT, plane, A, MODES, ORIGIN)
+    assert want.invalid_triangles == mp.SPOILED_EACH
+    bad = Call(ctx, roomV[:s.nV], to_device(badT), plane, [to_device(x) for x in A], MODES)
+    assert bad.rc == ERUNTIME and "300 triangles " in bad.message, (bad.rc, bad.message)
+    bad.check(want)  # the outputs are the oracle's without those triangles
+    V, T, dA = uploaded(reflibs, "blobs")
+    good = Call(ctx, V, T, plane, dA, MODES)  # the next call on the context succeeds
+    assert good.rc == 0, good.message
+    good.check(sectioned(reflibs, "blobs", "oblique"))
+
+
+def test_capacity_and_the_size_query(reflibs, ctx):
+    from mc33_c_library_amd.api import ECAPACITY
+    s = mesh(reflibs, "quant")[4]
+    want = sectioned(reflibs, "quant", "oblique")
+    V, T, dA = uploaded(reflibs, "quant")
+    plane = plane_of(s.V, "oblique")
+    for capP, capS in ((want.nP_out - 1, want.nS_out), (want.nP_out, want.nS_out - 1), (0, want.nS_out), (want.nP_out, 0)):
+        short = Call(ctx, V, T, plane, dA, MODES, capP=capP, capS=capS)
+        assert short.rc == ECAPACITY and short.sizes == want.sizes(), (short.rc, short.message)
+        assert str(want.nP_out) in short.message and str(want.nS_out) in short.message
+        assert short.counts[9:] == (0, 0, 0, 0) and short.length == 0.0 and short.area == 0.0
+        short.spare_intact(written=False)  # nothing is written, the map included
+    query = Call(ctx, V, T, plane, capP=0, capS=0, extras=False, change=dict(oP=None, oS=None))
+    assert query.rc == ECAPACITY and query.sizes == want.sizes()
+    exact = Call(ctx, V, T, plane, dA, MODES, capP=want.nP_out, capS=want.nS_out)
+    assert exact.rc == 0, exact.message
+    exact.check(want)
+
+
+def test_invalid_arguments(reflibs, ctx):
+    import torch
+    from mc33_c_library_amd.api import EINVAL, Sectioning
+    s = mesh(reflibs, "sheet")[4]
+    V, T, dA = uploaded(reflibs, "sheet")
+    nan, inf = float("nan"), float("inf")
+    cases = [dict(V=None), dict(T=None), dict(oP=None), dict(oS=None), dict(attr0=None), dict(oAttr0=None), dict(nV=1 << 32), dict(nT=1 << 32), dict(n_attr=3),
+             dict(attr_mode0=2), dict(attr_mode1=-1),
+             dict(plane=(0.0, 0.0, 0.0, 1.0)), dict(plane=(nan, 0.0, 1.0, 0.0)), dict(plane=(1.0, inf, 0.0, 0.0)), dict(plane=(1.0, 0.0, -inf, 0.0)),
+             dict(plane=(1.0, 0.0, 0.0, nan)), dict(plane=(1.0, 0.0, 0.0, inf))]
+    for change in cases:
+        call = Call(ctx, V, T, (1.0, 0.0, 0.0, 0.0), dA, MODES, change=change)
+        assert call.rc == EINVAL, (change, call.rc, call.message)
+        call.spare_intact(written=False)  # every output still at its fill
+    L = ctx.lib.mc33hip_section_surface
+    assert L(ctx.ctx, None) == EINVAL and L(None, C.byref(Sectioning())) == EINVAL
+    # every overlapping pair of ranges: each array gets a place of its own in one buffer, then one output at a time is moved onto
+    # the last byte of an input or of another output, or so that its own last byte meets the other's first
+    nV, nT, capP, capS = 1000, 2000, 900, 2000
+    size = {"V": nV * 12, "T": nT * 12, "attr0": nV * 4, "attr1": nV * 4, "oP": capP * 12, "oS": capS * 8, "oLabel": capP * 4, "oNext": capP * 4,
+            "oPointMap": nV * 4, "oAttr0": capP * 4, "oAttr1": capP * 4}
+    buf = torch.zeros((sum(size.values()) + 64 * len(size),), dtype=torch.uint8, device="cuda")
+    at, off = {}, 0
+    for n, b in size.items():
+        at[n] = buf.data_ptr() + off
+        off += b + 64
+
+    def struct(moved=None, onto=None, end=True):
+        a = Sectioning()
+        p = dict(at)
+        if moved:
+            p[moved] = at[onto] + size[onto] - 1 if end else at[onto] - size[moved] + 1
+        a.V, a.T, a.nV, a.nT, a.n_attr = p["V"], p["T"], nV, nT, 2
+        a.attr[0], a.attr[1], a.oAttr[0], a.oAttr[1] = p["attr0"], p["attr1"], p["oAttr0"], p["oAttr1"]
+        a.plane = (C.c_double * 4)(0.0, 0.0, 1.0, 1.0)
+        a.oP, a.oS, a.oLabel, a.oNext, a.oPointMap, a.capP, a.capS = p["oP"], p["oS"], p["oLabel"], p["oNext"], p["oPointMap"], capP, capS
+        return a
+    outs, ins = ["oP", "oS", "oLabel", "oNext", "oPointMap", "oAttr0", "oAttr1"], ["V", "T", "attr0", "attr1"]
+    pairs = [(o, i) for o in outs for i in ins] + [(o, p) for o in outs for p in outs if o != p]
+    assert len(pairs) == 28 + 42
+    for o, other in pairs:
+        for end in (True, False):
+            assert L(ctx.ctx, C.byref(struct(o, other, end))) == EINVAL, (o, other, end)
+    assert not buf.any().item()  # nothing was written
+    a = struct()
+    assert L(ctx.ctx, C.byref(a)) == 0  # the same arrays side by side: zeros - every triangle is (0, 0, 0), in: no section
+    assert (a.nP_out, a.nS_out, a.contours) == (0, 0, 0)
+    assert np.array_equal(bits(V.cpu().numpy()), bits(s.V)) and np.array_equal(T.cpu().numpy().view(np.uint32), s.T)
+    assert Call(ctx, V, T, (1.0, 0.0, 0.0, 0.0)).rc == 0  # the context is still good
+
+
+# ---- the other builds ------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("case", ["u8", "f64"])
+def test_other_sample_types(reflibs, case):
+    """MC33_real is double in libMC33_f64: rows of 24 bytes, and the cut points are not rounded to float"""
+    dtype, n = case, 40
+    r0, d = mo.AWKWARD_R0, mo.AWKWARD_D
+    if dtype == "f64":
+        data, iso = fx.cos_field(n, dtype=np.float64)[0], 0.0
+    else:
+        data, iso = fx.cos_field_int(n, np.uint8, 40.0, 128.0), 128.5
+    s = reflibs[dtype].isosurface(data, iso, r0, d)
+    assert s.V.dtype == (np.float64 if dtype == "f64" else np.float32) and s.nV > 1000
+    g = device_grid(data, r0, d)
+    origin = tuple(mo.reference_point(r0, d, data.shape))
+    V, T = to_device(s.V), to_device(s.T)
+    A = attributes(s.nV)
+    for which in ("oblique", "on-grid"):
+        plane = plane_of(s.V, which)
+        want = so.section(s.V, s.T, plane, A, MODES, origin)
+        assert want.P.dtype == s.V.dtype and want.nS_out > 50
+        call = Call(g, V, T, plane, [to_device(x) for x in A], MODES)
+        assert call.rc == 0, call.message
+        call.check(want)
+    normal = (0.3, -0.5, 0.8)
+    ws = sc.ladder_offsets(s.V, normal, 9)
+    seg, length, area = g.section_ladder(V, T, normal, ws)
+    check_ladder(seg, length, area, so.ladder(s.V, s.T, normal, ws, origin), normal)
+    g.close()
+
+
+# ---- the contour table ------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name,which", [("noise", "oblique"), ("quant", "on-grid"), ("blobs", "oblique")])
+def test_contour_table(reflibs, ctx, name, which):
+    from mc33_c_library_amd.api import ECAPACITY, Contour
+    s = mesh(reflibs, name)[4]
+    want = sectioned(reflibs, name, which)
+    rows = so.contour_table(want)
+    V, T, dA = uploaded(reflibs, name)
+    plane = plane_of(s.V, which)
+    call = Call(ctx, V, T, plane)
+    assert call.rc == 0
+    L = ctx.lib.mc33hip_section_contours
+    pl = (C.c_double * 4)(*plane)
+    n = C.c_ulonglong(0)
+    args = (C.c_void_p(call.oP.data_ptr()), want.nP_out, C.c_void_p(call.oS.data_ptr()), want.nS_out, C.c_void_p(call.oLabel.data_ptr()), C.byref(pl))
+    assert L(ctx.ctx, *args, None, 0, C.byref(n)) == ECAPACITY and n.value == len(rows) > 4
+    table = np.full(len(rows) + 1, 0x55, np.uint8).repeat(C.sizeof(Contour)).view(np.dtype(Contour))
+    assert L(ctx.ctx, *args, C.c_void_p(table.ctypes.data), len(rows) - 1, C.byref(n)) == ECAPACITY and n.value == len(rows)
+    assert np.all(table.view(np.uint8) == 0x55)  # untouched
+    assert L(ctx.ctx, *args, C.c_void_p(table.ctypes.data), len(rows), C.byref(n)) == 0 and n.value == len(rows)
+    assert np.all(table[len(rows):].view(np.uint8) == 0x55)
+    nrm = math.sqrt(plane[0] ** 2 + plane[1] ** 2 + plane[2] ** 2)
+    lab = want.label.astype(np.int64)[want.S[:, 0].astype(np.int64)]
+    for got, (root, points, segments, ends, branch, closed, length, G) in zip(table[:len(rows)], rows):
+        assert (got["root"], got["points"], got["segments"], got["open_ends"], got["branch_points"], got["closed"]) == (root, points, segments, ends, branch, closed)
+        t = want.terms[lab == root]
+        within(got["length"], t[:, 0], "length of contour %d" % root)
+        with np.errstate(invalid="ignore"):
+            within(got["area"], ((t[:, 1] * plane[0] + t[:, 2] * plane[1]) + t[:, 3] * plane[2]) / nrm, "area of contour %d" % root)
+    # what the host refuses
+    from mc33_c_library_amd.api import EINVAL
+    bad_plane = (C.c_double * 4)(0.0, 0.0, 0.0, 1.0)
+    assert L(ctx.ctx, None, *args[1:], None, 0, C.byref(n)) == EINVAL and L(ctx.ctx, *args[:4], None, args[5], None, 0, C.byref(n)) == EINVAL
+    assert L(ctx.ctx, *args, None, 0, None) == EINVAL and L(ctx.ctx, *args[:5], C.byref(bad_plane), None, 0, C.byref(n)) == EINVAL
+    assert L(ctx.ctx, *args, None, 4, C.byref(n)) == EINVAL and L(ctx.ctx, args[0], 1 << 32, *args[2:], None, 0, C.byref(n)) == EINVAL
+    # through Python
+    sec = ctx.section(V, T, plane)
+    tab = ctx.section_contours(sec)
+    assert tab["root"].tolist() == [r[0] for r in rows] and tab["segments"].tolist() == [r[2] for r in rows] and tab["closed"].tolist() == [r[5] for r in rows]
+
+
+# ---- the ladder ------------------------------------------------------------------------------------------------------------------------
+
+def check_ladder(seg, length, area, rungs, normal):
+    assert seg.tolist() == [r.nS_out for r in rungs]
+    for k, r in enumerate(rungs):
+        within(length[k], r.terms[:, 0], "length[%d]" % k)
+        area_within(area[k], r.terms, normal, "area[%d]" % k)
+
+
+@pytest.mark.parametrize("n", [0, 1, 2, 255])
+@pytest.mark.parametrize("name", ["noise", "sheet"])
+def test_ladder(reflibs, ctx, name, n):
+    s = mesh(reflibs, name)[4]
+    V, T, dA = uploaded(reflibs, name)
+    normal = (0.0, 0.0, 1.0) if name == "sheet" else (0.3, -0.5, 0.8)
+    ws = sc.ladder_offsets(s.V, normal, n)
+    seg, length, area = ctx.section_ladder(V, T, normal, ws)
+    rungs = so.ladder(s.V, s.T, normal, ws, ORIGIN)
+    check_ladder(seg, length, area, rungs, normal)
+    if n > 1:  # (the first and the last plane miss; with two there is no other)
+        assert seg[0] == 0 and seg[-1] == 0 and (n == 2 or seg.max() > 100)
+    singles = [Call(ctx, V, T, normal + (w,), extras=False) for w in ws]
+    assert all(c.rc == 0 for c in singles) and [c.counts[1] for c in singles] == seg.tolist()
+    for k, c in enumerate(singles):  # the same terms, added in another order
+        assert abs(c.length - length[k]) <= 2 * mo.sum_bound(rungs[k].terms[:, 0])
+
+
+def test_ladder_offsets_on_vertex_planes_and_refusals(reflibs, ctx):
+    """offsets that land exactly on grid planes of vertices (ON classes): the counts are still those of the single calls"""
+    from mc33_c_library_amd.api import EINVAL, MC33Error
+    s = mesh(reflibs, "quant")[4]
+    V, T, dA = uploaded(reflibs, "quant")
+    x, count = np.unique(s.V[:, 0], return_counts=True)
+    planes = np.sort(x[np.argsort(count)[-6:]].astype(np.float64))
+    ws = sorted(-float(p) for p in planes)
+    normal = (1.0, 0.0, 0.0)
+    rungs = so.ladder(s.V, s.T, normal, ws, ORIGIN)
+    assert all(r.on_points > 50 for r in rungs)
+    seg, length, area = ctx.section_ladder(V, T, normal, ws)
+    check_ladder(seg, length, area, rungs, normal)
+    assert seg.tolist() == [so.section(s.V, s.T, normal + (w,)).nS_out for w in ws]
+    nan, inf = float("nan"), float("inf")
+    for bad in ([0.0, 0.0], [1.0, 0.5], [0.0, nan], [0.0, inf], [float(k) for k in range(256)]):
+        with pytest.raises(MC33Error) as e:
+            ctx.section_ladder(V, T, normal, bad)
+        assert e.value.code == EINVAL
+    for nrm in ((0.0, 0.0, 0.0), (nan, 0.0, 1.0), (0.0, inf, 1.0)):
+        with pytest.raises(MC33Error) as e:
+            ctx.section_ladder(V, T, nrm, [0.0])
+        assert e.value.code == EINVAL
+    L = ctx.lib.mc33hip_section_ladder
+    three, one = (C.c_double * 3)(1.0, 0.0, 0.0), (C.c_double * 1)(0.0)
+    bad = C.c_ulonglong()
+    assert L(ctx.ctx, C.c_void_p(V.data_ptr()), V.shape[0], C.c_void_p(T.data_ptr()), T.shape[0], C.byref(three), one, 1, None, None, None, C.byref(bad)) == EINVAL
+    assert L(ctx.ctx, None, V.shape[0], C.c_void_p(T.data_ptr()), T.shape[0], C.byref(three), one, 0, None, None, None, C.byref(bad)) == EINVAL
+    # invalid triangles are counted and left out
+    badT = mp.spoil(s.T, s.nV, 3, "invalid")
+    with pytest.raises(MC33Error) as e:
+        ctx.section_ladder(V, to_device(badT), normal, ws)
+    assert "300 triangles " in str(e.value)
+
+
+# ---- Python ------------------------------------------------------------------------------------------------------------------------------
+
+def test_python_methods(reflibs):
+    data, r0, d, iso, s = mesh(reflibs, "quant")
+    P = fx.noise_f32(0, 77, shape=data.shape) * np.float32(1000.0)
+    g = device_grid(data, r0, d, P)
+    origin = tuple(mo.reference_point(r0, d, data.shape))
+    V, T = to_device(s.V), to_device(s.T)
+    A = attributes(s.nV)
+    plane = plane_of(s.V, "oblique")
+    want = so.section(s.V, s.T, plane, A, MODES, origin)
+    sec = g.section(V, T, plane, attrs=[to_device(x) for x in A], attr_modes=("lerp_f32", "copy"))
+    assert tuple(sec.info[n] for n in COUNTS) == want.counts() and sec.origin == origin and sec.plane == tuple(plane)
+    assert np.array_equal(bits(sec.P.cpu().numpy()), bits(want.P)) and np.array_equal(sec.S.cpu().numpy().view(np.uint32), want.S)
+    assert np.array_equal(sec.label.cpu().numpy().view(np.uint32), want.label) and np.array_equal(sec.next.cpu().numpy().view(np.uint32), want.next)
+    assert np.array_equal(sec.point_map.cpu().numpy().view(np.uint32), want.pmap)
+    for x, w in zip(sec.attrs, want.attrs):
+        assert np.array_equal(bits(x.cpu().numpy()), w)
+    within(sec.length, want.terms[:, 0], "length")
+    assert sec.area == so.area_of(sec.area_vector, plane)
+    # the product's own extraction (its V, T are the reference's bit for bit), the property at the points of the section
+    sec2, P2 = g.extract_section(iso, plane, with_property=True)
+    assert tuple(sec2.info[n] for n in COUNTS) == want.counts() and np.array_equal(bits(sec2.P.cpu().numpy()), bits(want.P))
+    assert np.array_equal(bits(P2.cpu().numpy()), bits(po.sample_property(want.P, r0, d, P)))
+    void = g.extract_section(iso, (1.0, 0.0, 0.0, -1e6))  # the plane misses: empty tensors
+    assert void.P.shape[0] == 0 and void.S.shape[0] == 0 and void.area == 0.0
+    normal = (0.0, 0.0, 1.0)
+    ws = sc.ladder_offsets(s.V, normal, 12)
+    seg, length, area = g.section_profile(iso, normal, ws)
+    check_ladder(seg, length, area, so.ladder(s.V, s.T, normal, ws, origin), normal)
+    g.close()
+
+
+def test_after_the_other_mesh_passes_on_one_context(reflibs, ctx):
+    """clip, filter and simplify on the large mesh first, then sections of the large and of a small one: the scratch the parts
+    share on the context (MeshHost) and clip's own, which the section borrows, are as good as fresh"""
+    big, small = mesh(reflibs, "noise")[4], mesh(reflibs, "sheet")[4]
+    V, T, dA = uploaded(reflibs, "noise")
+    N = to_device(big.N)
+    plane = plane_of(big.V, "oblique")
+    cl = ctx.clip(V, N, T, plane)
+    assert cl[5]["cut_vertices"] == clipped(reflibs, "noise", "oblique").cut_vertices
+    labels = ctx.label_components(T, big.nV)[0]
+    ctx.compact_components(V, N, T, labels, [0])
+    ctx.simplify(V, T, 0.3)
+    first = Call(ctx, V, T, plane, dA, MODES)
+    assert first.rc == 0, first.message
+    first.check(sectioned(reflibs, "noise", "oblique"))
+    Vs, Ts, dAs = uploaded(reflibs, "sheet")
+    second = Call(ctx, Vs, Ts, plane_of(small.V, "on-grid"), dAs, MODES)
+    assert second.rc == 0, second.message
+    second.check(sectioned(reflibs, "sheet", "on-grid"))
+    cl = ctx.clip(Vs, to_device(small.N), Ts, plane_of(small.V, "on-grid"))  # and clip after the section that borrowed its scratch
+    want = clipped(reflibs, "sheet", "on-grid")
+    assert np.array_equal(bits(cl[0].cpu().numpy()), bits(want.V)) and np.array_equal(cl[2].cpu().numpy().view(np.uint32), want.T)
+
+
+# ---- the C API -----------------------------------------------------------------------------------------------------------------------
+
+def section_copy(lib, S):
+    """the malloc blocks of an mc33_section as numpy arrays, and its scalars; the section is freed"""
+    from types import SimpleNamespace
+    r = S.contents
+    nP, nS = r.nP, r.nS
+    real = np.float64 if lib.dtype == "f64" else np.float32
+    out = SimpleNamespace(nP=nP, nS=nS)
+    out.P = np.ctypeslib.as_array(C.cast(r.P, C.POINTER(C.c_double if real == np.float64 else C.c_float)), shape=(max(nP, 1) * 3,))[:nP * 3].reshape(-1, 3).astype(real)
+    out.S = np.ctypeslib.as_array(C.cast(r.S, C.POINTER(C.c_uint)), shape=(max(nS, 1) * 2,))[:nS * 2].reshape(-1, 2).copy()
+    for name, t in (("contour", np.uint32), ("next", np.uint32), ("color", np.int32)):
+        setattr(out, name, np.ctypeslib.as_array(getattr(r, name), shape=(max(nP, 1),))[:nP].astype(t))
+    for name in ("on_points", "cut_points", "contours", "closed_contours", "open_ends", "branch_points", "degenerate_segments", "length", "area"):
+        setattr(out, name, getattr(r, name))
+    out.plane = tuple(r.plane)
+    out.P = out.P.copy()
+    lib.lib.MC33_free_section(S)
+    return out
+
+
+def check_c_section(got, want, plane):
+    assert (got.nP, got.nS, got.on_points, got.cut_points, got.contours, got.closed_contours, got.open_ends, got.branch_points, got.degenerate_segments) == \
+        (want.nP_out, want.nS_out, want.on_points, want.cut_points, want.contours, want.closed_contours, want.open_ends, want.branch_points, want.degenerate_segments)
+    assert np.array_equal(bits(got.P), bits(want.P)) and np.array_equal(got.S, want.S) and np.array_equal(got.contour, want.label) and np.array_equal(got.next, want.next)
+    assert got.plane == tuple(plane)
+    within(got.length, want.terms[:, 0], "length")
+    area_within(got.area, want.terms, plane, "area")
+
+
+@pytest.mark.parametrize("nneg", [False, True], ids=["plain", "nneg"])
+def test_c_api(reflibs, nneg):
+    """the oracle applied to the reference's surface - the _nneg reference's for the _nneg flavour, whose area has the other sign"""
+    from mc33_c_library_amd.api import Contour, SectionLevel
+    from test_gpu_property import c_palette, palette
+    name = "sphere"
+    field, iso, _ = mo.FIXTURES[name]
+    data, r0, d = field()
+    s = MC33Lib(ref_path("f32", nneg=True), "f32").isosurface(data, iso, r0, d) if nneg else mesh(reflibs, name)[4]
+    origin = tuple(mo.reference_point(r0, d, data.shape))
+    lib = MC33Lib(product_path("f32", nneg=nneg), "f32")
+    L = c_section_api(lib)
+    M_t = C.POINTER(lib.MC33)
+    L.MC33_set_property_grid.restype = C.c_int
+    L.MC33_set_property_grid.argtypes = [M_t, C.POINTER(lib.GRD)]
+    L.MC33_set_color_map.restype = C.c_int
+    L.MC33_set_color_map.argtypes = [M_t, C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
+    G, keep = lib.make_grid(data, r0, d)
+    prop = fx.noise_f32(0, 79, shape=data.shape) * np.float32(10.0)
+    Pg, keep2 = lib.make_grid(prop, r0, d)
+    M = L.create_MC33(G)
+    assert M
+    four, three = C.c_double * 4, C.c_double * 3
+    try:
+        for which in ("oblique", "on-grid", "miss"):
+            plane = plane_of(s.V, which)
+            want = so.section(s.V, s.T, plane, origin=origin)
+            for attempt in range(2):  # the staging sets as they come, and as the first call left them
+                S = L.MC33_section_isosurface(M, lib.real(iso), C.byref(four(*plane)))
+                assert S
+                m = M.contents
+                assert (m.iso, m.memoryfault) == (np.float32(iso), 0)
+                got = section_copy(lib, S)
+                check_c_section(got, want, plane)
+                assert np.all(got.color == po.DEFAULT_COLOR) and got.color.size == want.nP_out
+            if which != "miss":  # the sign: the plain flavour's sphere has volume < 0 and area < 0, the _nneg flavour's the opposite
+                assert got.contours == 1 and got.closed_contours == 1 and (got.area > 0.0) == nneg and abs(abs(got.area) - math.pi) < 0.06 * math.pi
+            # the table
+            rows = so.contour_table(want)
+            table, n = (Contour * 4)(), C.c_uint(7)
+            assert L.MC33_section_contours(M, lib.real(iso), C.byref(four(*plane)), table, 4, C.byref(n)) == 0 and n.value == len(rows)
+            for got_row, row in zip(table, rows):
+                assert (got_row.root, got_row.points, got_row.segments, got_row.open_ends, got_row.branch_points, got_row.closed) == row[:6]
+                within(got_row.length, want.terms[:, 0], "length")
+            if rows:
+                assert L.MC33_section_contours(M, lib.real(iso), C.byref(four(*plane)), None, 0, C.byref(n)) == -2 and n.value == len(rows)
+        # colours: those of the points at their own positions
+        plane = plane_of(s.V, "oblique")
+        want = so.section(s.V, s.T, plane, origin=origin)
+        pal, plo, phi = palette(7), -2.5, 3.25
+        assert L.MC33_set_property_grid(M, Pg) == 0 and L.MC33_set_color_map(M, c_palette(pal), len(pal), plo, phi) == 0
+        painted = section_copy(lib, L.MC33_section_isosurface(M, lib.real(iso), C.byref(four(*plane))))
+        assert np.array_equal(painted.color, po.color_vertices(want.P, r0, d, prop, pal, plo, phi)) and np.unique(painted.color).size > 2
+        check_c_section(painted, want, plane)
+        assert L.MC33_set_property_grid(M, None) == 0
+        # the profile
+        normal = (0.0, 0.0, 1.0)
+        ws = sc.ladder_offsets(s.V, normal, 11)
+        levels = (SectionLevel * 11)()
+        assert L.MC33_section_profile(M, lib.real(iso), C.byref(three(*normal)), (C.c_double * 11)(*ws), 11, levels) == 0
+        rungs = so.ladder(s.V, s.T, normal, ws, origin)
+        check_ladder(np.array([x.segments for x in levels]), [x.length for x in levels], [x.area for x in levels], rungs, normal)
+        assert all((x.area > 0.0) == nneg for x in levels[1:-1]) and levels[0].segments == 0
+        # refusals leave the object alone; its surface is the reference's still
+        Sf = L.calculate_isosurface(M, lib.real(iso))
+        assert Sf
+        mine = lib.copy_surface(Sf)
+        before = (M.contents.iso, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V)
+        nan, inf = float("nan"), float("inf")
+        for pl in ((0.0, 0.0, 0.0, 1.0), (nan, 0.0, 1.0, 0.0), (1.0, 0.0, 0.0, inf), (1.0, -inf, 0.0, 0.0)):
+            assert not L.MC33_section_isosurface(M, lib.real(iso + 1.0), C.byref(four(*pl)))
+            assert L.MC33_section_contours(M, lib.real(iso + 1.0), C.byref(four(*pl)), None, 0, None) == -1
+        assert not L.MC33_section_isosurface(M, lib.real(iso + 1.0), None)
+        assert L.MC33_section_profile(M, lib.real(iso + 1.0), C.byref(three(0.0, 0.0, 0.0)), (C.c_double * 1)(0.0), 1, levels) == -1
+        assert L.MC33_section_profile(M, lib.real(iso + 1.0), C.byref(three(*normal)), (C.c_double * 2)(1.0, 1.0), 2, levels) == -1
+        assert L.MC33_section_profile(M, lib.real(iso + 1.0), C.byref(three(*normal)), (C.c_double * 2)(0.0, nan), 2, levels) == -1
+        assert (M.contents.iso, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V) == before
+        L.free_surface_memory(Sf)
+        assert np.array_equal(bits(mine.V), bits(s.V)) and np.array_equal(mine.T, s.T)
+    finally:
+        L.free_MC33(M)
+        L.free_memory_grd(G)
+        L.free_memory_grd(Pg)
+        del keep, keep2
+
+
+def test_c_api_on_an_inclined_grid(reflibs):
+    """the plane is in the coordinates of the returned vertices: an inclined grid is sectioned like any other"""
+    data = fx.cos_field(24)[0]
+    A = [[1.0, 0.2, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
+    Ai = np.linalg.inv(np.array(A)).tolist()
+    s = reflibs["f32"].isosurface(data, 0.0, inclined=(A, Ai))
+    lib = MC33Lib(product_path("f32"), "f32")
+    L = c_section_api(lib)
+    G, keep = lib.make_grid(data, inclined=(A, Ai))
+    M = L.create_MC33(G)
+    assert M
+    try:
+        plane = plane_of(s.V, "oblique")
+        want = so.section(s.V, s.T, plane, origin=tuple(mo.reference_point((0.0, 0.0, 0.0), (1.0, 1.0, 1.0), data.shape)))
+        assert want.cut_points > 20
+        S = L.MC33_section_isosurface(M, lib.real(0.0), C.byref((C.c_double * 4)(*plane)))
+        assert S
+        check_c_section(section_copy(lib, S), want, plane)
+    finally:
+        L.free_MC33(M)
+        L.free_memory_grd(G)
+        del keep
+
+
+def test_c_api_refuses_an_object_on_several_slabs(launcher):
+    """MC33_HIP_DEVICES=0,0 in a fresh process, before the library is loaded: two slabs on one device (tests/section_slab_worker.py)."""
+    out = launcher.run([sys.executable, os.path.join(HERE, "section_slab_worker.py")], env={"MC33_HIP_DEVICES": "0,0"}, timeout=300)
+    assert out["rc"] == 0 and "section refused: 1 -1 -1 1" in out["stdout"], out
