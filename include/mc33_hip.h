@@ -88,6 +88,36 @@ int mc33hip_upload_rows(mc33hip_ctx *c, const void *const *const *F);
 int mc33hip_upload_contiguous(mc33hip_ctx *c, const void *host_samples);
 int mc33hip_adopt_device(mc33hip_ctx *c, const void *device_samples, size_t pitch, size_t slice);
 
+/* Who must say what when samples change.  The sweep can leave out the parts of the volume whose samples all lie on one side of
+ * the isovalue, from a table of sample ranges (minimum and maximum per plane of a 256 x 63 cell strip, 0.01 % of the grid) that
+ * it makes by the second sweep over the same samples - one extra pass over the grid, once - and keeps for as long as it KNOWS
+ * the samples to be what they were:
+ *   - the library's own copy (mc33hip_upload*): always; every upload drops the table.  Nothing to say.
+ *   - an adopted buffer (mc33hip_adopt_device): never, unless the caller says so.  Its samples may change without this library
+ *     knowing, and as adopted the buffer is volatile: every sweep reads all of it, exactly as before these calls existed.
+ *       mc33hip_grid_stable(c, 1)  the caller promises to call mc33hip_grid_changed after every write to the samples, by
+ *                                  whatever road (its own kernels, copies, another library), before the next call that
+ *                                  classifies (count, count_async, extract, sweep_many, prepare_many).  From then on a table
+ *                                  may be kept.  mc33hip_grid_stable(c, 0) takes the promise back and drops the table.
+ *       mc33hip_grid_changed(c)    the samples have changed: the table is dropped (and made again by the second sweep from
+ *                                  now), sweeps made ahead and a count waiting for its emit are forgotten.  Legal, and
+ *                                  harmless, on any context.
+ *     mc33hip_adopt_device itself drops the table and leaves the new buffer volatile.
+ *   mc33hip_set_stream / mc33hip_own_stream drop the table too (it is made on the context's stream, and a new stream is not
+ *   ordered behind the old one); the promise stands, the table is made again by the second sweep on the new stream.
+ * A stale table is the one way to a wrong surface here: a caller that cannot keep the promise does not make it.
+ * MC33_HIP_RANGES=0 in the environment when a context is created: that context never makes a table.
+ * The surface never depends on whether a table exists: it is bit for bit the one every tile streamed gives. */
+int mc33hip_grid_stable(mc33hip_ctx *c, int stable);
+int mc33hip_grid_changed(mc33hip_ctx *c);
+/* For tests, not part of any extraction.  mc33hip_range_table: the table as it is, [resident plane][y tile][row segment]{min, max}
+ * of MC33_real (y tiles of 63 cell rows, row segments of 256 cells; both ends of a strip inclusive; {-inf, +inf} for a strip
+ * that holds a NaN) into host memory; bytes must be the table's size; MC33HIP_EINVAL when there is no table.
+ * mc33hip_sweep_skipped: {tiles of the sweep, tiles left out below the isovalue, above it} of the last single-isovalue sweep
+ * made at timing level >= 1 (mc33hip_set_timing); MC33HIP_EINVAL when there was none.  Nothing is counted at level 0. */
+int mc33hip_range_table(mc33hip_ctx *c, void *host_out, size_t bytes);
+int mc33hip_sweep_skipped(mc33hip_ctx *c, unsigned long long out[3]);
+
 /* Inclined (non-orthogonal) grid: vertices and normals go through the cell matrices like MC33_spnC does
  * (reference marching_cubes_33.c:587-621).  grd_A / grd_Ai = _GRD._A / _GRD.A_ (3x3 row major, before the
  * scaling by d that create_MC33 applies, MC:1763-1770); triangular != 0 = the caller's mult_Abf is

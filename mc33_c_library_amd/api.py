@@ -191,7 +191,8 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_surface_topology", "mc33hip_component_topology", "mc33hip_compact_components",
            "mc33hip_smooth_surface", "mc33hip_vertex_normals", "mc33hip_smooth_timing", "mc33hip_simplify_surface",
            "mc33hip_resampled_size", "mc33hip_resample_grid", "mc33hip_context_device", "mc33hip_grid_spectrum",
-           "mc33hip_clip_surface", "mc33hip_section_surface", "mc33hip_section_contours", "mc33hip_section_ladder"]
+           "mc33hip_clip_surface", "mc33hip_section_surface", "mc33hip_section_contours", "mc33hip_section_ladder",
+           "mc33hip_grid_stable", "mc33hip_grid_changed", "mc33hip_range_table", "mc33hip_sweep_skipped"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -294,6 +295,11 @@ def load_library(dtype="f32"):
     lib.mc33hip_section_contours.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V, P(C.c_double * 4), V, C.c_ulonglong, P(C.c_ulonglong)]
     lib.mc33hip_section_ladder.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, P(C.c_double * 3), P(C.c_double), C.c_uint, P(C.c_ulonglong), P(C.c_double),
                                            P(C.c_double), P(C.c_ulonglong)]
+    if hasattr(lib, "mc33hip_grid_stable"):  # (MC33_LIB_DIR may name an older build, for a comparison side by side: every grid is volatile there)
+        lib.mc33hip_grid_stable.argtypes = [V, C.c_int]
+        lib.mc33hip_grid_changed.argtypes = [V]
+        lib.mc33hip_range_table.argtypes = [V, V, C.c_size_t]
+        lib.mc33hip_sweep_skipped.argtypes = [V, P(C.c_ulonglong * 3)]
     _libs[dtype] = lib
     return lib
 
@@ -441,9 +447,23 @@ class DeviceGrid:
     extraction context working on it.  dtype float32 or uint16 (carried as torch.int16 bit patterns).
     The tensor is used in place with its strides: any stride(1) >= npx, any stride(0) >= stride(1) * rows, any storage offset
     (include/mc33_hip.h, mc33hip_adopt_device: which alignment allows which kernel form, and what must be readable behind the
-    last row); npx: the grid's points per row when the tensor's rows are wider."""
+    last row); npx: the grid's points per row when the tensor's rows are wider.
 
-    def __init__(self, tensor, nz_total=None, plane0=0, r0=(0.0, 0.0, 0.0), d=(1.0, 1.0, 1.0), npx=None):
+    Who must say what when samples change.  The library may keep a table of sample ranges over the grid and leave out the parts of
+    the volume that cannot hold the isovalue (include/mc33_hip.h: mc33hip_grid_stable) - only over samples it knows to be
+    unchanged.  This class declares the tensor stable and keeps that true with torch's own bookkeeping: before every call that
+    classifies samples (count, count_async, sweep_many, prepare_many, extract_into, and everything built on them) it compares
+    tensor._version with the value it saw last and tells the library when it differs.  So:
+      - a write torch counts - t[...] = x, t.neg_(), t.copy_(...), an out= argument, through any view or detach() of the tensor,
+        which share the counter - is seen by the next call with nothing said;
+      - a write torch does NOT count needs grid.changed() before the next call: t.data[...] = x, a foreign kernel or library given
+        data_ptr(), another DeviceGrid's resample_into(out) when out is this grid's tensor;
+      - volatile=True never declares the tensor stable: every call reads the whole grid, as an adopted buffer always did.  A
+        tensor whose _version cannot be read (inference tensors) is volatile by itself.
+    The table is made by the second sweep since the samples last changed - one extra pass over the grid, once; a grid extracted
+    once, or rewritten before every extraction, never pays for it."""
+
+    def __init__(self, tensor, nz_total=None, plane0=0, r0=(0.0, 0.0, 0.0), d=(1.0, 1.0, 1.0), npx=None, volatile=False):
         import torch
         assert tensor.is_cuda and tensor.dim() == 3 and tensor.stride(2) == 1, "need a device tensor [z, y, x]"
         if tensor.dtype == torch.float32:
@@ -474,6 +494,25 @@ class DeviceGrid:
         _check(self.lib, self.lib.mc33hip_adopt_device(self.ctx, C.c_void_p(tensor.data_ptr()), pitch, tensor.stride(0)))
         self.device = tensor.device
         self.use_stream(torch.cuda.current_stream(self.device))
+        self._version = None  # tensor._version when the samples were last known to be what the library has seen; None: volatile
+        if not volatile and hasattr(self.lib, "mc33hip_grid_stable"):
+            try:
+                self._version = tensor._version
+                _check(self.lib, self.lib.mc33hip_grid_stable(self.ctx, 1))
+            except RuntimeError:  # (inference tensors do not track versions)
+                self._version = None
+
+    def changed(self):
+        """The samples were written by a road torch does not count (see the class docstring): forget what was derived from them."""
+        if hasattr(self.lib, "mc33hip_grid_changed"):
+            _check(self.lib, self.lib.mc33hip_grid_changed(self.ctx))
+        if self._version is not None:
+            self._version = self.tensor._version
+
+    def _fresh(self):
+        """Before every call that sweeps: a write torch has counted since the last look means the samples changed."""
+        if self._version is not None and self.tensor._version != self._version:
+            self.changed()
 
     def set_timing(self, level):
         """0: no events (the production path), 1: whole call, 2: per pass (timing() then reports sweep / scan / emit)."""
@@ -505,6 +544,7 @@ class DeviceGrid:
         return Range(0, self.desc.nz_total, 0, 0)
 
     def count(self, iso, rng=None):
+        self._fresh()
         rng = rng or self.full_range()
         cnt = Counts()
         _check(self.lib, self.lib.mc33hip_count(self.ctx, C.c_double(iso), C.byref(rng), C.byref(cnt)))
@@ -513,6 +553,7 @@ class DeviceGrid:
     def sweep_many(self, isos, rng=None):
         """Classify up to 8 isovalues in one go (the grid is streamed once per 4 of them); the count / extract calls
         for these isovalues over the same range then skip their sweep."""
+        self._fresh()
         rng = rng or self.full_range()
         arr = (C.c_double * len(isos))(*[float(x) for x in isos])
         _check(self.lib, self.lib.mc33hip_sweep_many(self.ctx, arr, len(isos), C.byref(rng)))
@@ -520,6 +561,7 @@ class DeviceGrid:
     def prepare_many(self, isos, rng=None):
         """sweep_many plus everything else a count needs, every isovalue into buffers of its own: count / emit_into for these
         isovalues then run in any order, any number of times (slabs: all counts first, ONE exchange, then the emits)."""
+        self._fresh()
         rng = rng or self.full_range()
         arr = (C.c_double * len(isos))(*[float(x) for x in isos])
         _check(self.lib, self.lib.mc33hip_prepare_many(self.ctx, arr, len(isos), C.byref(rng)))
@@ -527,6 +569,7 @@ class DeviceGrid:
     def extract_into(self, iso, V, N, T, rng=None):
         """One extraction into caller-owned device tensors V, N [capV,3] float32 and T [capT,3] int32.
         Returns (Counts, enough_capacity)."""
+        self._fresh()
         rng = rng or self.full_range()
         cnt = Counts()
         rc = self.lib.mc33hip_extract(self.ctx, C.c_double(iso), C.byref(rng), C.c_void_p(V.data_ptr()),
@@ -545,6 +588,7 @@ class DeviceGrid:
     # -- a z-slab's count, count exchange and emit without a host round trip in between (slabs.py: extract_slab) --------------
     def count_async(self, iso, rng=None):
         """What count() does, enqueued only: the counters stay on the device until count_finish()."""
+        self._fresh()
         rng = rng or self.full_range()
         _check(self.lib, self.lib.mc33hip_count_async(self.ctx, C.c_double(iso), C.byref(rng)))
 

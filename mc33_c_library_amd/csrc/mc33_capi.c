@@ -83,6 +83,7 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_resample_grid
 #pragma weak mc33hip_context_device
 #pragma weak mc33hip_adopt_device /* (the host layer uses it for the resampled grid only) */
+#pragma weak mc33hip_grid_stable  /* (... whose samples nobody but this library writes) */
 /* ... and the contour spectrum (MC33_grid_spectrum): without it that function returns -1 */
 #pragma weak mc33hip_grid_spectrum
 _Static_assert(sizeof(mc33_component) == sizeof(mc33hip_component) && offsetof(mc33_component, area) == offsetof(mc33hip_component, area),
@@ -1758,6 +1759,8 @@ MC33 *MC33_create_resampled(MC33 *source, const mc33_resampling *r) {
 		rc = mc33hip_device_alloc(s->ctx, &p->own_grid, (p->own_slice * npo[2] + 64) * sizeof(GRD_data_type));
 	if (rc == MC33HIP_OK) rc = mc33hip_resample_grid(ss->ctx, &hr, p->own_grid, p->own_pitch, p->own_slice); /* (waits) */
 	if (rc == MC33HIP_OK) rc = mc33hip_adopt_device(s->ctx, p->own_grid, p->own_pitch, p->own_slice);
+	if (rc == MC33HIP_OK && mc33hip_grid_stable) /* (own_grid is written by the resampling above and never again: the sweeps may keep a range table over it) */
+		rc = mc33hip_grid_stable(s->ctx, 1);
 	if (rc != MC33HIP_OK) {
 		free_MC33(M);
 		return 0;

@@ -151,6 +151,16 @@ struct mc33hip_ctx {
 	uint64_t tiles_cap, ntiles, nbounds;
 	uint32_t tiles_zs, tiles_ze, tiles_depth;
 	uint32_t resident_blocks; // k_sweep blocks the device holds at once
+	// the range table (RangeEntry, sweep_ranges): made for a grid whose samples this library knows to be unchanged - its own copy,
+	// or an adopted buffer the caller has declared stable - by the second sweep since they last changed
+	RangeEntry *d_ranges;
+	uint64_t ranges_cap;
+	bool ranges_valid;        // the table holds the ranges of the samples as they are
+	bool ranges_off;          // MC33_HIP_RANGES=0: never made (read at create)
+	bool grid_stable;         // mc33hip_grid_stable(c, 1) since the buffer was adopted
+	uint32_t sweeps_seen;     // sweeps since the samples last changed, while there is no table
+	uint32_t *d_skipped;      // mc33hip_sweep_skipped: SweepArgs::skipped of the last single-isovalue sweep at timing level >= 1
+	uint64_t skipped_tiles;   // ... its tiles (0: no such sweep yet)
 	int cus;                  // compute units of the device
 	int emit_v_blocks_per_cu; // blocks of k_emit_vertices a CU holds
 	hipEvent_t ev[4];
@@ -214,6 +224,10 @@ static void read_switches(Switches &w) {
 	w.trace_cells = getenv("MC33_HIP_TRACE_CELLS") ? strdup(getenv("MC33_HIP_TRACE_CELLS")) : nullptr;
 	w.trace_file = getenv("MC33_HIP_TRACE_FILE") ? strdup(getenv("MC33_HIP_TRACE_FILE")) : nullptr;
 	w.debug = env_u32("MC33_HIP_DEBUG", 0); w.cells_dev = env_u32("MC33_HIP_CELLS_DEV", 0);
+}
+static void forget_ranges(mc33hip_ctx *c) {  // the samples changed, or may have: no table until the second sweep from now
+	c->ranges_valid = false;
+	c->sweeps_seen = 0;
 }
 
 // An extraction on a caller's stream returns when its counts are known (count_until_fits), with its emit passes still queued or
@@ -355,6 +369,7 @@ extern "C" int mc33hip_create(mc33hip_ctx **out, const mc33hip_grid_desc *d) {
 	CREATE_TRY(pool_take(c->device, &c->copy));
 	c->timing_level = getenv("MC33_HIP_TIMING") ? atoi(getenv("MC33_HIP_TIMING")) : 0;
 	c->epoch_wrap = std::min(1u << 30, std::max(3u, env_u32("MC33_HIP_EPOCH_WRAP", 1u << 30)));
+	c->ranges_off = env_flag("MC33_HIP_RANGES") == 0;
 	CREATE_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
 	CREATE_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
 	CREATE_TRY(hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming));
@@ -380,6 +395,7 @@ extern "C" void mc33hip_destroy(mc33hip_ctx *c) {
 	}
 	dev_release(&c->d_tiles);
 	dev_release(&c->d_bounds);
+	dev_release(&c->d_ranges); dev_release(&c->d_skipped);
 	dev_release(&c->d_bases);
 	dev_release(&c->trace); dev_release(&c->trace_cells);
 	if (c->aux) (void)hipStreamSynchronize(c->aux);
@@ -400,6 +416,22 @@ extern "C" void mc33hip_destroy(mc33hip_ctx *c) {
 
 static void forget_sweeps(mc33hip_ctx *c) {  // the grid changed: sweeps made ahead of time are worthless
 	for (int k = 0; k < MC33_LANES; k++) { c->lanes[k].swept = false; c->lanes[k].tail_done = false; }
+	forget_ranges(c);  // (every upload and mc33hip_adopt_device come through here)
+}
+
+// Who may keep a table over which samples (include/mc33_hip.h): the library's own copy is written by the uploads alone, which drop
+// the table; an adopted buffer is the caller's, and only the caller can say that it stays as it is.
+extern "C" int mc33hip_grid_stable(mc33hip_ctx *c, int stable) {
+	if (!c) return MC33HIP_EINVAL;
+	c->grid_stable = stable != 0;
+	if (!c->grid_stable && !c->owns_grid) forget_ranges(c);
+	return MC33HIP_OK;
+}
+extern "C" int mc33hip_grid_changed(mc33hip_ctx *c) {
+	if (!c) return MC33HIP_EINVAL;
+	c->counted = false;
+	forget_sweeps(c);
+	return MC33HIP_OK;
 }
 
 extern "C" int mc33hip_set_stream(mc33hip_ctx *c, void *s) {
@@ -407,6 +439,7 @@ extern "C" int mc33hip_set_stream(mc33hip_ctx *c, void *s) {
 	if (int rc = use_device(c)) return rc;  // (what the old stream still holds is finished on the old stream)
 	if (c->own_stream) { pool_give(c->device, c->stream); c->own_stream = false; }
 	c->stream = (hipStream_t)s;
+	forget_ranges(c);  // (the new stream is not ordered behind the old one, on which the table may still be in the making)
 	c->stream_given = true;
 	return MC33HIP_OK;
 }
@@ -420,6 +453,7 @@ extern "C" int mc33hip_own_stream(mc33hip_ctx *c) {
 	HIP_TRY(pool_take(c->device, &st));
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	c->stream = st;
+	forget_ranges(c);
 	c->own_stream = true;
 	c->stream_given = false;
 	return MC33HIP_OK;
@@ -557,6 +591,7 @@ extern "C" int mc33hip_adopt_device(mc33hip_ctx *c, const void *dptr, size_t pit
 	if (c->owns_grid) dev_release(&c->d_grid);
 	c->d_grid = (sample_t *)dptr;
 	c->owns_grid = false;
+	c->grid_stable = false;  // (volatile until the caller says otherwise: mc33hip_grid_stable)
 	c->pitch = pitch;
 	c->slice = slice;
 	c->tiles_ze = 0u;  // (the plan counts its work in batches of the form - packed or not - this buffer's alignment allows)

@@ -284,9 +284,34 @@ static void sweep_args(mc33hip_ctx *c, const SlotGeom &g, SweepArgs &a) {
 	a.ntiles = (uint32_t)c->ntiles;
 	a.z_end = c->range.z_end;
 	a.trace = nullptr;
+	a.ranges = nullptr;
+	a.skipped = nullptr;
 	a.debug = 0;
 	for (int q = 0; q < SWEEP_MAXNI; q++) a.lane[q] = SweepLane{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, (real_t)0, 0, 0xFFFFFFFFu};
 }
+// The range table for the sweep that is about to be enqueued on st, or nullptr: no table (the sweep streams every tile).
+// Trust: only over samples this library knows to be unchanged - its own copy (every upload comes through forget_sweeps), or an
+// adopted buffer between mc33hip_grid_stable(c, 1) and the next mc33hip_grid_changed / mc33hip_adopt_device.
+// When: by the SECOND sweep since the samples last changed - a one-shot extraction and a caller whose samples change every step
+// never pay for it.  The build is one launch on st in front of the sweep; the host waits for nothing.  No memory for the table,
+// or a grid beyond one launch: no table, which is not an error.
+static const RangeEntry *sweep_ranges(mc33hip_ctx *c, hipStream_t st) {
+	if (c->ranges_off || !c->d_grid || !(c->owns_grid || c->grid_stable)) return nullptr;
+	if (c->ranges_valid) return c->d_ranges;
+	if (++c->sweeps_seen < 2u) return nullptr;
+	const Params &P = c->P;
+	const uint32_t nYT = (P.ny + 62) / 63, nXG = (P.nseg + 3) / 4, npl = c->desc.npz_resident;
+	const uint64_t n = (uint64_t)npl * nYT * P.nseg, blocks = (uint64_t)npl * nYT * nXG;
+	if (blocks > 0x7FFFFFFFull) return nullptr;
+	if (c->ranges_cap < n && dev_room("range table", &c->d_ranges, &c->ranges_cap, n) != 0) { (void)hipGetLastError(); return nullptr; }
+	const bool vec = (uintptr_t)c->d_grid % 16u == 0 && (c->pitch * sizeof(sample_t)) % 16u == 0 && (c->slice * sizeof(sample_t)) % 16u == 0;
+	if (vec) hipLaunchKernelGGL(k_ranges<true>, dim3((uint32_t)blocks), dim3(256), 0, st, grid_view(c), P, nYT, npl, c->d_ranges);
+	else hipLaunchKernelGGL(k_ranges<false>, dim3((uint32_t)blocks), dim3(256), 0, st, grid_view(c), P, nYT, npl, c->d_ranges);
+	if (hipGetLastError() != hipSuccess) return nullptr;
+	c->ranges_valid = true;
+	return c->d_ranges;
+}
+
 // SweepLane::iso_gt / iso_eq of an isovalue for packed samples of `top` as their largest value
 static void sweep_iso_words(real_t v, real_t top, int32_t &gt, uint32_t &eq) {
 	const real_t fl = std::floor(v);
@@ -319,10 +344,12 @@ static uint32_t launch_sweep_zm(mc33hip_ctx *c, const SweepArgs &a, hipStream_t 
 	// with four isovalues, 20 for ushort, 8 for uchar with two; that corner takes the unpacked form, which has none)
 	constexpr bool packed_form = !(SWEEP_PACK >= 2 && NI >= 2 && ZM == 0);
 	if (packed_form && sweep_packed(c)) {
-		hipLaunchKernelGGL((k_sweep<packed_form ? SWEEP_PACK : 1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
+		if (a.ranges) hipLaunchKernelGGL((k_sweep<packed_form ? SWEEP_PACK : 1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
+		else hipLaunchKernelGGL((k_sweep_all<packed_form ? SWEEP_PACK : 1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
 		return (uint32_t)SWEEP_PACK;
 	}
-	hipLaunchKernelGGL((k_sweep<1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
+	if (a.ranges) hipLaunchKernelGGL((k_sweep<1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
+	else hipLaunchKernelGGL((k_sweep_all<1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
 	return 1u;
 }
 template <int NI>
@@ -515,6 +542,13 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 		SweepArgs a;
 		sweep_args(c, g, a);
 		set_lane(a, 0, *L, P.iso);
+		a.ranges = sweep_ranges(c, st);
+		c->skipped_tiles = 0;
+		if (c->timing_level > 0 && (c->d_skipped || hipMalloc(&c->d_skipped, 4 * sizeof(uint32_t)) == hipSuccess)) {  // (mc33hip_sweep_skipped; never on the production path)
+			HIP_TRY(hipMemsetAsync(c->d_skipped, 0, 4 * sizeof(uint32_t), st));
+			a.skipped = c->d_skipped;
+			c->skipped_tiles = c->ntiles;
+		} else if (c->timing_level > 0) (void)hipGetLastError();
 #ifdef MC33_DEV
 		a.debug = c->sw.debug;
 		if (a.debug) {  // never silent: with this set the call measures the sweep's read stream and finds no surface
@@ -600,6 +634,7 @@ static int enqueue_sweep_many(mc33hip_ctx *c, const double *isos, int n, bool ta
 			if (int rc = begin_lane(c, L, g, st)) return rc;
 			set_lane(a, q, L, isos[k + q]);
 		}
+		a.ranges = sweep_ranges(c, st);
 		// (events around the pass are only recorded; read_timing asks for the elapsed time when the lane is consumed)
 		const bool timed = c->timing_level > 0 && pass < MC33_MANY_PASSES;
 		if (timed) HIP_TRY(hipEventRecord(c->ev_many[pass][0], st));
@@ -1171,6 +1206,28 @@ extern "C" int mc33hip_probe_read(mc33hip_ctx *c, int reps, float *ms_best, floa
 	if (ms_best) *ms_best = t.front();
 	if (ms_median) *ms_median = t[t.size() / 2];
 	if (bytes) *bytes = n16 * 16ull;
+	return MC33HIP_OK;
+}
+
+// ---- what the tests look at of the range table (include/mc33_hip.h); neither is on the path of an extraction ----
+extern "C" int mc33hip_range_table(mc33hip_ctx *c, void *host_out, size_t bytes) {
+	if (!c || !host_out) return MC33HIP_EINVAL;
+	if (!c->ranges_valid || !c->d_ranges) { set_err("no range table (none built yet, dropped, or the grid is volatile)"); return MC33HIP_EINVAL; }
+	const uint64_t n = (uint64_t)c->desc.npz_resident * ((c->desc.npy - 1u + 62u) / 63u) * ((c->desc.npx - 1u + SEG_CELLS - 1u) / SEG_CELLS);
+	if (bytes != n * sizeof(RangeEntry)) { set_err("range table: %llu bytes, not %llu", (unsigned long long)(n * sizeof(RangeEntry)), (unsigned long long)bytes); return MC33HIP_EINVAL; }
+	if (int rc = use_device(c)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	HIP_TRY(hipMemcpy(host_out, c->d_ranges, bytes, hipMemcpyDeviceToHost));
+	return MC33HIP_OK;
+}
+extern "C" int mc33hip_sweep_skipped(mc33hip_ctx *c, unsigned long long *out /*[3]*/) {
+	if (!c || !out) return MC33HIP_EINVAL;
+	if (!c->skipped_tiles || !c->d_skipped) { set_err("no single-isovalue sweep at timing level >= 1 yet"); return MC33HIP_EINVAL; }
+	if (int rc = use_device(c)) return rc;
+	uint32_t w[4];
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	HIP_TRY(hipMemcpy(w, c->d_skipped, sizeof w, hipMemcpyDeviceToHost));
+	out[0] = c->skipped_tiles; out[1] = w[1]; out[2] = w[2];
 	return MC33HIP_OK;
 }
 

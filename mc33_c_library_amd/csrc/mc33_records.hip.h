@@ -100,8 +100,17 @@ struct SweepLane {
 	uint32_t iso_eq;         // the isovalue when it is a sample value, else a word no sample equals
 };
 
+// Sample range of one strip of the grid - one plane of one wave tile's footprint: x in [256 seg, min(256 seg + 256, nx)],
+// y in [63 yt, min(63 yt + 63, ny)], both ends inclusive (the halo column and the row shared with the next y tile belong to the
+// strip) - as MC33_real, converted as the sweep converts; {-inf, +inf} for a strip that holds a NaN.  k_ranges writes the table
+// [plane - G.z0][yt][seg] once for a grid whose samples are known to stay (sweep_ranges); k_sweep leaves out the tiles whose
+// strips all lie on one side of every isovalue of the pass.
+struct alignas(2 * sizeof(real_t)) RangeEntry { real_t lo, hi; };
+
 struct SweepArgs {
 	GridView<sample_t> G;
+	const RangeEntry *ranges;  // the range table, nullptr: none (every tile is streamed)
+	uint32_t *skipped;         // timing level >= 1, single-isovalue sweeps: {-, tiles left out below, above the isovalue}; else nullptr
 	Params P;                // (P.iso is not used by the sweep: every lane has its own)
 	const SweepTile *tiles;  // [wave]: the waves of a block are independent, a block is any four consecutive tiles
 	uint32_t ntiles;

@@ -33,6 +33,99 @@ constexpr int SWEEP_PACK = 4;
 constexpr int SWEEP_PACK = 1;
 #endif
 
+// ---------------------------------------------------------------------------------------------------
+// k_ranges: the range table (RangeEntry) of the resident planes, one streaming pass.  A wave per strip, the four waves of a block
+// the four strips of a 1024-sample group of row segments (the 4 KiB row pieces the sweep reads).  Minimum and maximum are taken of
+// the CONVERTED samples ((MC33_real)F, what MC33_LOAD makes of them: the conversion is monotone, but not one to one for 32-bit
+// integers).  Addresses past the strip are clamped into it - a sample taken twice changes no minimum - so every lane has the same
+// number of loads in flight and only grid points are ever read.
+// V: rows in 16-byte pieces (base, pitch and slice all multiples of 16 bytes - the library's own copy, any whole tensor), taken
+// by the strips that are 256 samples wide; the strips at the end of a row, and every strip of a buffer aligned otherwise, go
+// sample by sample, which is correct for any base, pitch and slice.
+// ---------------------------------------------------------------------------------------------------
+template <bool V>
+__global__ __launch_bounds__(256) void k_ranges(const GridView<sample_t> G, const Params P, const uint32_t nYT, const uint32_t nplanes, RangeEntry *out) {
+	constexpr uint32_t U = 8;                                   // loads in flight per lane
+	constexpr uint32_t VS = 16u / (uint32_t)sizeof(sample_t);  // samples of a 16-byte piece
+	struct alignas(16) Piece { sample_t s[VS]; };
+	constexpr real_t INF = std::numeric_limits<real_t>::infinity();
+	// The halo column of a strip is column 0 of the next one: a wave keeps the range of its column 0 apart and hands it to the wave
+	// on its left through LDS (one barrier per block); only a wave with no wave to its right in the block loads that column itself -
+	// a 64-byte line per row for one sample, which for every strip was 12 % more traffic than the grid holds.
+	__shared__ real_t s_col0[4][2];
+	__shared__ uint32_t s_nan0[4];
+	const uint32_t lane = threadIdx.x & 63u, nXG = (P.nseg + 3u) / 4u, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	const uint32_t xg = blockIdx.x % nXG, yt = (blockIdx.x / nXG) % nYT, pl = blockIdx.x / nXG / nYT;
+	const uint32_t seg = xg * 4u + wv;
+	const bool active = seg < P.nseg && pl < nplanes;  // (wave-uniform; an idle wave still comes to the barrier)
+	const uint32_t xbase = seg * SEG_CELLS, y0 = yt * 63u, nrows = min(64u, P.ny + 1u - y0), xlast = min(xbase + SEG_CELLS, P.nx);
+	const sample_t *base = G.p + (uint64_t)pl * G.slice + (uint64_t)y0 * G.pitch;
+	real_t lo = INF, hi = -INF, lo0 = INF, hi0 = -INF;
+	bool nan = false, nan0 = false;
+	auto take = [&](sample_t s, bool col0) __attribute__((always_inline)) {
+		const real_t f = (real_t)s;
+		lo = real_min(lo, f); hi = f > hi ? f : hi;  // (a NaN changes neither)
+		lo0 = col0 ? real_min(lo0, f) : lo0; hi0 = (col0 && f > hi0) ? f : hi0;
+#ifdef MC33_NAN_SAMPLES
+		nan = nan || f != f; nan0 = nan0 || (col0 && f != f);
+#endif
+	};
+	if (active) {
+		if (V && xbase + SEG_CELLS - 1u <= P.nx) {  // (wave-uniform)
+			constexpr uint32_t VR = SEG_CELLS / VS;  // pieces per row of the strip
+			const uint32_t total = nrows * VR;
+			for (uint32_t e0 = 0; e0 < total; e0 += 64u * U) {
+				Piece v[U];
+				bool first[U];
+#pragma unroll
+				for (uint32_t k = 0; k < U; k++) {
+					const uint32_t e = min(e0 + 64u * k + lane, total - 1u);
+					first[k] = (e % VR) == 0u;
+					v[k] = *(const Piece *)(base + (uint64_t)(e / VR) * G.pitch + xbase + (e % VR) * VS);
+				}
+#pragma unroll
+				for (uint32_t k = 0; k < U; k++)
+#pragma unroll
+					for (uint32_t j = 0; j < VS; j++) take(v[k].s[j], j == 0u && first[k]);
+			}
+		} else {
+			const uint32_t total = nrows * 4u;  // 64 samples of a row per load
+			for (uint32_t e0 = 0; e0 < total; e0 += U) {
+				sample_t v[U];
+#pragma unroll
+				for (uint32_t k = 0; k < U; k++) {
+					const uint32_t e = min(e0 + k, total - 1u);
+					v[k] = base[(uint64_t)(e >> 2) * G.pitch + min(xbase + 64u * (e & 3u) + lane, xlast)];
+				}
+#pragma unroll
+				for (uint32_t k = 0; k < U; k++) take(v[k], lane == 0u && (min(e0 + k, total - 1u) & 3u) == 0u);
+			}
+		}
+		// Column xbase + 256, where the strip has one (xlast == xbase + 256; a narrower last strip ends inside the loops above), is
+		// beyond both loops.  It is the right neighbour's column 0 - unless there is no wave to the right in this block: the
+		// block's last wave, and the row's last segment when nx is a multiple of 256, where that column is the grid's last.
+		if (xlast == xbase + SEG_CELLS && (wv == 3u || seg + 1u == P.nseg)) take(base[(uint64_t)min(lane, nrows - 1u) * G.pitch + xlast], false);
+	}
+#pragma unroll
+	for (int dlt = 32; dlt; dlt >>= 1) {
+		const real_t l2 = __shfl_xor(lo, dlt), h2 = __shfl_xor(hi, dlt), l3 = __shfl_xor(lo0, dlt), h3 = __shfl_xor(hi0, dlt);
+		lo = real_min(lo, l2); hi = h2 > hi ? h2 : hi;
+		lo0 = real_min(lo0, l3); hi0 = h3 > hi0 ? h3 : hi0;
+	}
+	bool anynan = __ballot(nan) != 0ull;
+	const bool anynan0 = __ballot(nan0) != 0ull;
+	if (lane == 0) { s_col0[wv][0] = lo0; s_col0[wv][1] = hi0; s_nan0[wv] = anynan0 ? 1u : 0u; }
+	__syncthreads();
+	if (!active) return;
+	if (wv < 3u && seg + 1u < P.nseg) {  // (the wave to the right is active: it has this strip's halo column as its column 0, over the same rows)
+		const real_t l2 = s_col0[wv + 1u][0], h2 = s_col0[wv + 1u][1];
+		lo = real_min(lo, l2); hi = h2 > hi ? h2 : hi;
+		anynan = anynan || s_nan0[wv + 1u] != 0u;
+	}
+	if (anynan) { lo = -INF; hi = INF; }
+	if (lane == 0) out[((uint64_t)pl * nYT + yt) * P.nseg + seg] = RangeEntry{lo, hi};
+}
+
 // S: samples per lane and load.  S = 1: every lane loads single samples (all types); S = SWEEP_PACK > 1: dwords of 2
 // unsigned shorts / 4 unsigned chars - needs rows that start on a dword boundary (the host checks), and makes a batch
 // 8 / 16 sample rows instead of 4, so that a wave keeps the same 16 x 256 bytes in flight.
@@ -42,8 +135,12 @@ constexpr int SWEEP_PACK = 1;
 // subtraction, the |d| and the running minimum go: 1: one compare for the sign, one for "equals the isovalue"; 2: no
 // isovalue of the pass is an integer of the sample type's range - nothing can equal it, one compare per sample and isovalue
 // (the 4-isovalue pass over ushort samples is bound by its instructions: 94 -> 58 per sample row).
-template <int S, int NI, int ZM = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_sweep(const SweepArgs a) {  // (3 waves per SIMD: at most 168 VGPRs - the 4-lane form sits right at that edge)
+// R: the form that looks at the range table first (k_sweep); without it (k_sweep_all, what a sweep without a table launches - a
+// volatile grid, the first sweep over new samples, MC33_HIP_RANGES=0) the body is the one the kernel had before there was a table,
+// instruction for instruction: the preamble being THERE cost the packed passes over several isovalues 3 % whether or not it ran
+// (profiles/r08_range_skip.txt D), and a caller without a table pays nothing for it.
+template <int S, int NI, int ZM, bool R>
+__device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 	constexpr int LPR = 4 / S;    // loads per sample row
 	constexpr int RB = 16 / LPR;  // sample rows per batch
 	const uint32_t lane = threadIdx.x & 63u;
@@ -74,10 +171,80 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 			}
 		}
 	}
-	__shared__ uint64_t s_mail[2][4][NI][2];  // [plane parity][wave][isovalue]{column-0 bits of the rows, rows whose column-0 sample may equal the isovalue}
-	const bool from_right = grouped && (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) < 3u;  // this wave's halo bits come from the wave to its right
 	const unsigned long long t_start = a.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
 	const unsigned long long c_start = a.trace ? __builtin_amdgcn_s_memtime() : 0ull;
+	// The range table (RangeEntry): a tile whose strips - of the planes it would READ, pl0 .. z_hi - all lie strictly above, or all
+	// strictly below, every isovalue of the pass holds no cut cell and no sample equal to an isovalue, and is not streamed.  Lane l
+	// looks at the strips of the planes pl0 + l, + 64, ...: one 8- / 16-byte load per lane and 64 planes, the comparisons in the lane,
+	// one AND over the wave.  Both comparisons are strict and made in MC33_real, on the values the sweep would have compared:
+	//   lo > iso: every sample F of the tile has F > iso, so d = iso - F is negative and NOT zero - the difference of two different
+	//     floating-point numbers is never zero while denormals are kept, and the code objects keep them (float_denorm_mode 3; no
+	//     flush-to-zero option in the build) - its sign bit is 1 (the integer forms classify by F > iso itself): all bits 1;
+	//   hi < iso: d is positive and not zero: all bits 0.
+	//   iso == +-0 against a sample +-0 compares equal: neither holds, the tile is streamed.  A NaN isovalue: neither holds.  A strip
+	//   with a NaN sample has {-inf, +inf}: neither holds for any isovalue.
+	// What a dead wave leaves behind is what a live one would have for k_boundary, and nothing else: the headers of the edge records
+	// of its first plane (when the tile below exists) and last plane (when a tile above does) - halo bits all 0 / all 1, no row and
+	// no lane with a sample equal to the isovalue, PLANE_UNIFORM0 / PLANE_UNIFORM1 (no record) - from lane 0.  No slice header (an
+	// older one carries an older epoch), nothing added to slot_part, no log.
+	// The mailbox: every wave of a block that could be grouped works out the verdicts of all four tiles - they are the same four
+	// computations in all four waves, so the result is block-uniform - and a block with a dead tile runs UNGROUPED: its live waves
+	// load their own halo column, as in every ungrouped block, and there is no barrier in such a block at all.  A dead wave does not
+	// return here (a second exit in the middle of the kernel gave the packed forms over several isovalues a scratch segment): its
+	// tile has no batches - T = 0 below - so it walks past the loop, flushes an empty log, and ends where every wave ends.  The one
+	// batch issued ahead of the loop goes through a descriptor of zero bytes: no memory access.
+	bool dead_me = false;
+	if (R && a.ranges) {
+		const uint32_t wme = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+		// (a grouped block: the four tiles are the segments seg .. seg + 3 of one y tile over the same planes - four neighbouring
+		// entries of the table per plane, all four verdicts from one pass; any other block: the wave's own tile only)
+		const uint32_t seg0 = grouped ? seg - wme : seg, nk = grouped ? 4u : 1u, me = grouped ? wme : 0u;
+		const uint32_t p0r = tile.z_lo == a.P.zs ? tile.z_lo : tile.z_lo + 1u;
+		uint32_t m = 0xFFFFFFFFu;  // bit 2 NI k + 2 q: all strips of tile k of the block lie below isovalue q; + 1: all above
+		for (uint32_t p = p0r + lane; p <= tile.z_hi; p += 64u) {
+			const RangeEntry *row = a.ranges + (((uint64_t)(p - a.G.z0) * a.sd.nYT + yt) * a.sd.nseg + seg0);
+			static_for<4>([&](auto kc) __attribute__((always_inline)) {
+				constexpr int k = decltype(kc)::value;
+				if ((uint32_t)k < nk) {  // (wave-uniform)
+					const RangeEntry e = row[k];
+					static_for<NI>([&](auto qc) __attribute__((always_inline)) {
+						constexpr int q = decltype(qc)::value;
+						const real_t v = a.lane[q].iso;
+						m &= ~(((e.hi < v ? 0u : 1u) | (e.lo > v ? 0u : 2u)) << (2 * NI * k + 2 * q));
+					});
+				}
+			});
+		}
+#pragma unroll
+		for (int dlt = 32; dlt; dlt >>= 1) m &= (uint32_t)__shfl_xor((int)m, dlt);
+		m = (uint32_t)__builtin_amdgcn_readfirstlane((int)m);
+		// a tile is dead when each of its isovalues has one of its two bits
+		constexpr uint32_t EVEN = NI == 4 ? 0x55u : NI == 2 ? 0x5u : 0x1u, ALLQ = (1u << (2 * NI)) - 1u;
+		const uint32_t one_side = (m | m >> 1);  // bit 2 NI k + 2 q: isovalue q of tile k has a side
+		bool dead_any = false;
+		static_for<4>([&](auto kc) __attribute__((always_inline)) {
+			constexpr int k = decltype(kc)::value;
+			if ((uint32_t)k < nk) dead_any = dead_any || ((one_side >> (2 * NI * k)) & EVEN) == EVEN;
+		});
+		const uint32_t mine = (m >> (2u * NI * me)) & ALLQ;  // bit 2q: all strips of this wave's tile below isovalue q; bit 2q + 1: all above
+		dead_me = ((mine | mine >> 1) & EVEN) == EVEN;
+		if (dead_any) grouped = false;
+		if (dead_me) {
+			if (lane == 0) {
+				static_for<NI>([&](auto qc) __attribute__((always_inline)) {
+					constexpr int q = decltype(qc)::value;
+					const bool above = ((mine >> (2 * q)) & 2u) != 0u;
+					const uint32_t hb = above ? 0xFFFFFFFFu : 0u;
+					uint4 *h = a.lane[q].edge_hdr + (uint64_t)wtile * 2u * 2u;
+					if (p0r != tile.z_lo) { h[0] = uint4{hb, hb, 0u, 0u}; h[1] = uint4{0u, 0u, above ? PLANE_UNIFORM1 : PLANE_UNIFORM0, 0u}; }
+					if (tile.z_hi < a.z_end) { h[2] = uint4{hb, hb, 0u, 0u}; h[3] = uint4{0u, 0u, above ? PLANE_UNIFORM1 : PLANE_UNIFORM0, 0u}; }
+				});
+				if (NI == 1 && a.skipped) atomicAdd(a.skipped + ((mine & 2u) ? 2 : 1), 1u);
+			}
+		}
+	}
+	__shared__ uint64_t s_mail[2][4][NI][2];  // [plane parity][wave][isovalue]{column-0 bits of the rows, rows whose column-0 sample may equal the isovalue}
+	const bool from_right = grouped && (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) < 3u;  // this wave's halo bits come from the wave to its right
 	const uint32_t xbase = seg * SEG_CELLS, y0 = yt * 63u;
 	const uint32_t nrows = min(64u, P.ny + 1 - y0);  // sample rows of this tile
 	const uint32_t z_lo = tile.z_lo, z_hi = tile.z_hi;
@@ -148,8 +315,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 	// is turned into bit rows.  Loads go through a buffer descriptor per plane (scalar base + 32-bit
 	// offsets, hardware range check).
 	const uint32_t NB = (nrows + (uint32_t)RB - 1u) / (uint32_t)RB;
-	const uint32_t T = (z_hi - pl0 + 1u) * NB;
-	const uint32_t tile_bytes = nrows * rowbytes;
+	const uint32_t T = dead_me ? 0u : (z_hi - pl0 + 1u) * NB;  // (a tile the range table rules out: nothing to stream)
+	const uint32_t tile_bytes = dead_me ? 0u : nrows * rowbytes;
 // Cache policy of the sweep's loads (every sample is read once).  `nt` (aux bit 1) for 4- and 8-byte samples: 0.866 - 0.875 ->
 // 0.78 - 0.85 ms at 1024^3 float over four processes each way; the narrow types, whose sweep is bound by instructions rather
 // than by the stream, lose with it (ushort 4-isovalue pass + 1.5 %, uchar + 10 %) and keep the default.
@@ -565,6 +732,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 #undef MC33_ADV_ISSUE
 #undef MC33_ADV
 #undef MC33_LOAD
+}
+template <int S, int NI, int ZM = 0>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_sweep(const SweepArgs a) {  // (3 waves per SIMD: at most 168 VGPRs - the 4-lane form sits right at that edge)
+	sweep_tile<S, NI, ZM, true>(a);
+}
+template <int S, int NI, int ZM = 0>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_sweep_all(const SweepArgs a) {
+	sweep_tile<S, NI, ZM, false>(a);
 }
 
 // ---------------------------------------------------------------------------------------------------
