@@ -117,6 +117,14 @@ int mc33hip_grid_changed(mc33hip_ctx *c);
  * made at timing level >= 1 (mc33hip_set_timing); MC33HIP_EINVAL when there was none.  Nothing is counted at level 0. */
 int mc33hip_range_table(mc33hip_ctx *c, void *host_out, size_t bytes);
 int mc33hip_sweep_skipped(mc33hip_ctx *c, unsigned long long out[3]);
+/* For tests and tracing as well.  mc33hip_sweep_plan: the sweep's plan in force - the one the last sweep, or the last tail, went
+ * by - as tiles {row segment, y tile, z_lo, z_hi} in launch order, four consecutive tiles a block, into tiles_out (room for
+ * cap_tiles tiles; NULL: info only); info = {tiles, blocks the device holds at once, 0: the plan of a sweep without a range
+ * table / 1: with one}.  mc33hip_sweep_live: the live list of the last sweep made with a table, one word per block that had a
+ * tile to stream, in plan order: block << 4 | mask of its waves with nothing to stream; info = {entries, blocks of that sweep's
+ * plan}.  MC33HIP_EINVAL when there is no plan / was no such sweep. */
+int mc33hip_sweep_plan(mc33hip_ctx *c, unsigned int *tiles_out, size_t cap_tiles, unsigned long long info[3]);
+int mc33hip_sweep_live(mc33hip_ctx *c, unsigned int *live_out, size_t cap_entries, unsigned long long info[2]);
 
 /* Inclined (non-orthogonal) grid: vertices and normals go through the cell matrices like MC33_spnC does
  * (reference marching_cubes_33.c:587-621).  grd_A / grd_Ai = _GRD._A / _GRD.A_ (3x3 row major, before the

@@ -70,7 +70,17 @@ struct IsoLane {
 	double iso;
 	mc33hip_range range;
 	uint32_t pack;            // samples per lane and load of the sweep that filled it (lane_of_column)
+	int plan;                 // the plan (mc33hip_ctx::plan) that sweep went by: its edge records are indexed by that plan's tiles
 	int many_pass, many_ni;   // which pass of mc33hip_sweep_many filled it (its events), and how many isovalues that pass classified
+};
+
+// A block plan of k_sweep (plan_sweep): the tiles, and the pairs of tiles that meet in z.  What a sweep leaves for k_boundary is indexed
+// by the tiles of the plan it went by, so a lane keeps the plan's number (IsoLane::plan) until its tail is made.
+struct SweepPlan {
+	SweepTile *d_tiles;
+	TileBoundary *d_bounds;   // (made to measure for every plan: nbounds is its capacity)
+	uint64_t tiles_cap, ntiles, nbounds;
+	uint32_t zs, ze, depth;
 };
 
 // Everything a tail (k_slots ... k_scan_apply) writes and the emit passes read, for ONE isovalue.  Lane k of the sweep buffers
@@ -118,7 +128,9 @@ struct Switches {
 	int slow_count, no_fork, slow_slots, tri_first;  // -1: not set
 	char *trace_cells, *trace_file;                               // (developer tracing: file names; copies)
 	uint32_t debug, cells_dev;  // (looked at by -DMC33_DEV builds only)
-	uint32_t pad_[6];           // (the words of five removed developer switches: with the context 24 bytes smaller, the C3 emit stage measured 4 us slower)
+	uint32_t rz_table;          // MC33_HIP_RZ_TABLE: depth of the plan a sweep with a range table goes by (plan_sweep)
+	int live;                   // MC33_HIP_LIVE: 1 / 0 = a sweep with a table always / never goes by a live list; -1 (not set): sweep_live decides
+	uint32_t pad_[4];           // (the words of five removed developer switches: with the context 24 bytes smaller, the C3 emit stage measured 4 us slower)
 };
 
 struct mc33hip_ctx {
@@ -146,11 +158,16 @@ struct mc33hip_ctx {
 	IsoLane *cur_lane;        // the lane the last count used (its epoch is what the emit pass needs)
 	bool lane_presweeped;     // ... and it had been filled by mc33hip_sweep_many
 	bool lane_pretailed;      // ... tail included
-	SweepTile *d_tiles;       // block plan of k_sweep for the current range
-	TileBoundary *d_bounds;   // pairs of tiles that meet in z (k_boundary)
-	uint64_t tiles_cap, ntiles, nbounds;
-	uint32_t tiles_zs, tiles_ze, tiles_depth;
+	SweepPlan plan[2];        // the plans of k_sweep for the current range (plan_sweep): [0] without a range table, [1] with one
+	int cur_plan;             // ... and the one in force: what the sweep to be launched, or the lane whose tail is being made, goes by
 	uint32_t resident_blocks; // k_sweep blocks the device holds at once
+	uint8_t *d_verdict;       // with a table: k_tile_verdicts' byte per block of the plan, and the live list k_live_compact makes of
+	uint32_t *d_live;         // them (SweepArgs::live: the count, then the entries) - of the last sweep with a table
+	uint64_t verdict_cap, live_cap;
+	uint64_t live_blocks;     // blocks of the plan that sweep went by (0: no such sweep yet)
+	unsigned long long *h_live;  // pinned: what k_live_compact published last (live tiles << 32 | tiles << 1 | plan; 0: nothing yet)
+	uint32_t coarse_sweeps;   // ... sweeps made that way since (sweep_live: one in 16 goes by a list)
+	bool table_coarse;        // sweeps with a table go by plan 0 for now: the last ones left too little out for the finer plan to pay (table_plan)
 	// the range table (RangeEntry, sweep_ranges): made for a grid whose samples this library knows to be unchanged - its own copy,
 	// or an adopted buffer the caller has declared stable - by the second sweep since they last changed
 	RangeEntry *d_ranges;
@@ -215,7 +232,7 @@ static int env_flag(const char *name) {  // -1: not set
 	return s && *s ? (atoi(s) != 0 ? 1 : 0) : -1;
 }
 static void read_switches(Switches &w) {
-	w.rz = env_u32("MC33_HIP_RZ", 0); w.sweep_blocks_per_cu = env_u32("MC33_HIP_SWEEP_BLOCKS_PER_CU", 0); w.min_depth = env_u32("MC33_HIP_MIN_DEPTH", 0);
+	w.rz = env_u32("MC33_HIP_RZ", 0); w.sweep_blocks_per_cu = env_u32("MC33_HIP_SWEEP_BLOCKS_PER_CU", 0); w.min_depth = env_u32("MC33_HIP_MIN_DEPTH", 0); w.rz_table = env_u32("MC33_HIP_RZ_TABLE", 0); w.live = env_flag("MC33_HIP_LIVE");
 	w.cells_blocks = env_u32("MC33_HIP_CELLS_BLOCKS", 0); w.slow_blocks = env_u32("MC33_HIP_SLOW_BLOCKS", 0); w.emit_blocks = env_u32("MC33_HIP_EMIT_BLOCKS", 0);
 	w.emit_v_blocks_per_cu = env_u32("MC33_HIP_EMIT_V_BLOCKS_PER_CU", 0); w.slow_slots_max = env_u32("MC33_HIP_SLOW_SLOTS_MAX", 0);
 	w.no_pack = env_u32("MC33_HIP_NO_PACK", 0) != 0; w.no_stage = env_u32("MC33_HIP_NO_STAGE", 0) != 0; w.verbose = getenv("MC33_HIP_VERBOSE") != nullptr;
@@ -228,6 +245,8 @@ static void read_switches(Switches &w) {
 static void forget_ranges(mc33hip_ctx *c) {  // the samples changed, or may have: no table until the second sweep from now
 	c->ranges_valid = false;
 	c->sweeps_seen = 0;
+	c->table_coarse = false;  // (new samples: the finer plan until a sweep says otherwise)
+	if (c->h_live) __atomic_store_n(c->h_live, 0ull, __ATOMIC_RELAXED);
 }
 
 // An extraction on a caller's stream returns when its counts are known (count_until_fits), with its emit passes still queued or
@@ -393,8 +412,10 @@ extern "C" void mc33hip_destroy(mc33hip_ctx *c) {
 		IsoLane &L = c->lanes[k];
 		dev_release(&L.slice_hdr); dev_release(&L.slice_bits); dev_release(&L.slice_compact); dev_release(&L.plane_fmt); dev_release(&L.slot_part); dev_release(&L.edge_bits); dev_release(&L.edge_hdr);
 	}
-	dev_release(&c->d_tiles);
-	dev_release(&c->d_bounds);
+	for (SweepPlan &pl : c->plan) { dev_release(&pl.d_tiles); dev_release(&pl.d_bounds); }
+	dev_release(&c->d_verdict); dev_release(&c->d_live);
+	if (c->h_live) (void)hipHostFree(c->h_live);
+	c->h_live = nullptr;
 	dev_release(&c->d_ranges); dev_release(&c->d_skipped);
 	dev_release(&c->d_bases);
 	dev_release(&c->trace); dev_release(&c->trace_cells);
@@ -594,7 +615,7 @@ extern "C" int mc33hip_adopt_device(mc33hip_ctx *c, const void *dptr, size_t pit
 	c->grid_stable = false;  // (volatile until the caller says otherwise: mc33hip_grid_stable)
 	c->pitch = pitch;
 	c->slice = slice;
-	c->tiles_ze = 0u;  // (the plan counts its work in batches of the form - packed or not - this buffer's alignment allows)
+	c->plan[0].ze = c->plan[1].ze = 0u;  // (the plan counts its work in batches of the form - packed or not - this buffer's alignment allows)
 	c->counted = false;
 	forget_sweeps(c);
 	return MC33HIP_OK;

@@ -107,10 +107,23 @@ static int grow_entries(TailSet &w, uint64_t need) {
 // once whenever the grid is large enough.  Measured on MI355X at 1024^3: with 1088 equal tiles on 256 CUs
 // the 64 CUs that got a fifth block finished 12 % after the others.
 static bool sweep_packed(const mc33hip_ctx *c);
-static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze) {
+//
+// Two plans are kept, and `which` says which one is put in force (c->cur_plan): 0, for a sweep without a range table, is about
+// SWEEP_DEPTH slices deep - one tile per wave slot of the device, one round; 1, for a sweep with one, about SWEEP_DEPTH_TABLE.  With a table
+// most tiles of a smooth field are dead and never streamed (k_tile_verdicts), and the live ones have to fill the device by
+// themselves: the plan is several rounds of the resident set, k_sweep's live blocks come first in the launch, and the hardware
+// hands a freed slot to the next of them.  An explicit MC33_HIP_RZ is the depth of both, which are then one plan (number 0);
+// MC33_HIP_RZ_TABLE is the depth of plan 1 alone (the tests make the two differ on small grids with it, the profiles try depths).
+// A lane swept ahead keeps the number of its plan (IsoLane::plan), and its tail asks for that plan again: the plan is a function
+// of the range, the depth and the device, so a plan made again for a range is the plan the lane's edge records are indexed by.
+constexpr uint32_t SWEEP_DEPTH = 16u, SWEEP_DEPTH_TABLE = 5u;  // (measured, 1024^3 float: profiles/r09_sweep_refill.txt A, B)
+static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, int which) {
 	const Params &P = c->P;
-	const uint32_t depth = c->sw.rz ? c->sw.rz : 16u;
-	if (c->d_tiles && c->tiles_zs == zs && c->tiles_ze == ze && c->tiles_depth == depth) return 0;
+	if (c->sw.rz && !c->sw.rz_table) which = 0;
+	const uint32_t depth = which ? (c->sw.rz_table ? c->sw.rz_table : SWEEP_DEPTH_TABLE) : (c->sw.rz ? c->sw.rz : SWEEP_DEPTH);
+	SweepPlan &pl = c->plan[which];
+	c->cur_plan = which;
+	if (pl.d_tiles && pl.zs == zs && pl.ze == ze && pl.depth == depth) return 0;
 	if (!c->resident_blocks) {
 		int per_cu = 0, cus = 0;
 		HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sweep<1, 1>, 256, 0));
@@ -185,20 +198,21 @@ static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze) {
 	// A sweep made ahead by mc33hip_sweep_many may still be reading the old plan: the copies below go through the null stream,
 	// which a non-blocking stream (any torch.cuda.Stream) is not ordered with
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (c->tiles_cap < tiles.size())
-		if (int rc = dev_room("sweep tiles", &c->d_tiles, &c->tiles_cap, tiles.size())) return rc;
-	HIP_TRY(hipMemcpy(c->d_tiles, tiles.data(), tiles.size() * sizeof(SweepTile), hipMemcpyHostToDevice));
-	c->ntiles = tiles.size();
-	dev_release(&c->d_bounds);  // (made to measure for every plan: nbounds is its capacity)
-	c->nbounds = 0;
+	pl.ze = 0u;  // (not a plan until both arrays are in place)
+	if (pl.tiles_cap < tiles.size())
+		if (int rc = dev_room("sweep tiles", &pl.d_tiles, &pl.tiles_cap, tiles.size())) return rc;
+	HIP_TRY(hipMemcpy(pl.d_tiles, tiles.data(), tiles.size() * sizeof(SweepTile), hipMemcpyHostToDevice));
+	pl.ntiles = tiles.size();
+	dev_release(&pl.d_bounds);  // (made to measure for every plan: nbounds is its capacity)
+	pl.nbounds = 0;
 	if (!bounds.empty()) {
-		if (int rc = dev_room("tile boundaries", &c->d_bounds, &c->nbounds, bounds.size())) return rc;
-		HIP_TRY(hipMemcpy(c->d_bounds, bounds.data(), bounds.size() * sizeof(TileBoundary), hipMemcpyHostToDevice));
+		if (int rc = dev_room("tile boundaries", &pl.d_bounds, &pl.nbounds, bounds.size())) return rc;
+		HIP_TRY(hipMemcpy(pl.d_bounds, bounds.data(), bounds.size() * sizeof(TileBoundary), hipMemcpyHostToDevice));
 	}
-	c->tiles_zs = zs; c->tiles_ze = ze; c->tiles_depth = depth;
+	pl.zs = zs; pl.ze = ze; pl.depth = depth;
 	if (c->sw.verbose)
-		fprintf(stderr, "[mc33hip] sweep plan: %llu wave tiles (%u resident), %llu columns, depth %.1f\n", (unsigned long long)c->ntiles,
-		        c->resident_blocks * 4, (unsigned long long)nYT * P.nseg, (double)nzc * nYT * P.nseg / (double)c->ntiles);
+		fprintf(stderr, "[mc33hip] sweep plan %d: %llu wave tiles (%u resident), %llu columns, depth %.1f\n", which, (unsigned long long)pl.ntiles,
+		        c->resident_blocks * 4, (unsigned long long)nYT * P.nseg, (double)nzc * nYT * P.nseg / (double)pl.ntiles);
 	return 0;
 }
 
@@ -220,7 +234,7 @@ static int slot_geometry(mc33hip_ctx *c, SlotGeom &g) {
 	return 0;
 }
 
-// buffers of one isovalue lane for the current range and tile plan; a new extraction number (epoch)
+// buffers of one isovalue lane for the current range and the tile plan in force; a new extraction number (epoch)
 static int begin_lane(mc33hip_ctx *c, IsoLane &L, const SlotGeom &g, hipStream_t st) {
 	if (L.slice_cap < g.nslots) {
 		const uint64_t part_bytes = ((g.nslots + SLOT_CHUNK - 1) / SLOT_CHUNK) * 8;
@@ -236,10 +250,12 @@ static int begin_lane(mc33hip_ctx *c, IsoLane &L, const SlotGeom &g, hipStream_t
 		L.tail_pending = false;
 		L.slice_cap = g.nslots;
 	}
-	if (L.edge_cap < c->ntiles)
-		if (int rc = dev_room_all("tile edge buffers", &L.edge_cap, c->ntiles,
-		                          {dev_array(&L.edge_bits, c->ntiles, 2 * 128 * sizeof(uint4)), dev_array(&L.edge_hdr, c->ntiles, 2 * 2 * sizeof(uint4))}))
+	const uint64_t ntiles = c->plan[c->cur_plan].ntiles;  // (the buffers follow the larger plan: they only grow)
+	if (L.edge_cap < ntiles)
+		if (int rc = dev_room_all("tile edge buffers", &L.edge_cap, ntiles,
+		                          {dev_array(&L.edge_bits, ntiles, 2 * 128 * sizeof(uint4)), dev_array(&L.edge_hdr, ntiles, 2 * 2 * sizeof(uint4))}))
 			return rc;
+	L.plan = c->cur_plan;
 	const uint64_t nchunks = (L.slice_cap + SLOT_CHUNK - 1) / SLOT_CHUNK;  // (capacity: the halves keep their place)
 	if (++L.epoch >= c->epoch_wrap) {  // stamps wrap: start over with clean headers AND clean partial sums - the call before
 		// accumulated into the half an odd epoch selects and cleared only the other one, and epoch 1 is odd again
@@ -280,12 +296,13 @@ static void sweep_args(mc33hip_ctx *c, const SlotGeom &g, SweepArgs &a) {
 	a.G = grid_view(c);
 	a.P = c->P;
 	a.sd = g.sd;
-	a.tiles = c->d_tiles;
-	a.ntiles = (uint32_t)c->ntiles;
+	a.tiles = c->plan[c->cur_plan].d_tiles;
+	a.ntiles = (uint32_t)c->plan[c->cur_plan].ntiles;
 	a.z_end = c->range.z_end;
 	a.trace = nullptr;
 	a.ranges = nullptr;
 	a.skipped = nullptr;
+	a.live = nullptr;
 	a.debug = 0;
 	for (int q = 0; q < SWEEP_MAXNI; q++) a.lane[q] = SweepLane{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, (real_t)0, 0, 0xFFFFFFFFu};
 }
@@ -310,6 +327,50 @@ static const RangeEntry *sweep_ranges(mc33hip_ctx *c, hipStream_t st) {
 	if (hipGetLastError() != hipSuccess) return nullptr;
 	c->ranges_valid = true;
 	return c->d_ranges;
+}
+
+// Whether the sweep about to be launched with a table goes by a live list (k_tile_verdicts, k_live_compact, k_sweep_live) or works
+// its verdicts out itself (k_sweep), and room for the list.  The list pays where dead tiles have to make room for live ones: a plan
+// of at least one round of the device.  Below that every tile has a slot of its own anyway, and the two small launches are a
+// loss - 7.5 us of the 110 a 256^3 step takes (profiles/r09_sweep_refill.txt D).  MC33_HIP_LIVE=1 / 0: always / never (the tests
+// of the list run on small grids).  No memory for the list: the preamble form, which is not an error.
+// Which plan a sweep with a table goes by: 1, the finer one, unless the sweeps say it does not pay.  A finer plan is a gain by the
+// slots dead tiles free for live ones, and a loss by its per-tile start and end and three times the boundaries.  Measured at 1024^3
+// float (profiles/r09_sweep_refill.txt C, D): 63 % of the one-round plan's tiles dead, 12 % faster; nothing dead, 5 - 8 % slower; between
+// the two, taken as linear in the dead share, they break even near four tiles in five live.  So: a sweep by the finer plan that
+// found more than 90 % of its tiles live sends the following ones to plan 0, the one-round plan (with the table and its list all
+// the same), and a sweep by plan 0 that found fewer than 75 % live sends them back.  The finer plan never has the larger live share of
+// the two, so a field stays where it was sent.  The count is k_live_compact's published word, read as it stands - of the last
+// sweep or of one or two before it; nobody waits for it.  New samples start from the finer plan (forget_ranges).
+static int table_plan(mc33hip_ctx *c) {
+	if (c->h_live) {
+		const unsigned long long w = __atomic_load_n(c->h_live, __ATOMIC_RELAXED);
+		const uint64_t tiles = (w & 0xFFFFFFFFull) >> 1, live = w >> 32;
+		if (tiles) {
+			if ((w & 1ull) && live * 100 > tiles * 90) { c->coarse_sweeps = c->table_coarse ? c->coarse_sweeps : 0u; c->table_coarse = true; }
+			else if (!(w & 1ull) && live * 100 < tiles * 75) c->table_coarse = false;
+		}
+	}
+	return c->table_coarse ? 0 : 1;
+}
+static void sweep_live(mc33hip_ctx *c, SweepArgs &a) {
+	c->live_blocks = 0;
+	if (!a.ranges) return;
+	const uint64_t ntiles = c->plan[c->cur_plan].ntiles, blocks = (ntiles + 3) / 4;
+	// While the one-round plan stands in for the finer one (table_plan) every tile has its slot and the preamble form is the faster
+	// one - it is the parent's sweep, where the list's two launches cost 10 us of 940 (r09 F) - but only a list's count can end the
+	// stand-in: one sweep in 16 goes by a list, the first of them at once.
+	bool want = ntiles >= (uint64_t)c->resident_blocks * 4;
+	if (c->table_coarse) want = (c->coarse_sweeps++ % 16u) == 0u;
+	if (!(c->sw.live > 0 || (c->sw.live < 0 && want))) return;
+	if (!c->h_live && hipHostMalloc(&c->h_live, sizeof *c->h_live, hipHostMallocDefault) == hipSuccess) *c->h_live = 0ull;
+	else if (!c->h_live) (void)hipGetLastError();  // (no pinned word: nothing is published, the finer plan stays)
+	if ((c->verdict_cap < blocks && dev_room("tile verdicts", &c->d_verdict, &c->verdict_cap, blocks) != 0) ||
+	    (c->live_cap < blocks + 1 && dev_room("live list", &c->d_live, &c->live_cap, blocks + 1) != 0)) {
+		(void)hipGetLastError();
+		return;
+	}
+	a.live = c->d_live;
 }
 
 // SweepLane::iso_gt / iso_eq of an isovalue for packed samples of `top` as their largest value
@@ -338,17 +399,24 @@ static bool sweep_packed(const mc33hip_ctx *c) {
 // (all return the samples per lane and load of the form that was launched: k_cells needs it - lane_of_column)
 template <int NI, int ZM>
 static uint32_t launch_sweep_zm(mc33hip_ctx *c, const SweepArgs &a, hipStream_t st) {
-	const uint64_t blocks = (c->ntiles + 3) / 4;
+	const uint64_t blocks = (c->plan[c->cur_plan].ntiles + 3) / 4;
+	if (a.live) {  // the verdicts and the live list, in front of the sweep that goes by them (sweep_live)
+		hipLaunchKernelGGL(k_tile_verdicts<NI>, dim3((uint32_t)((blocks + 3) / 4)), dim3(256), 0, st, a, c->d_verdict, (uint32_t)blocks);
+		hipLaunchKernelGGL(k_live_compact, dim3(1), dim3(1024), 0, st, c->d_verdict, (uint32_t)blocks, c->d_live, c->h_live, (uint32_t)c->cur_plan, a.ntiles);
+		c->live_blocks = blocks;
+	}
 	// (packed narrow samples, several isovalues, classified by subtraction - an isovalue of -0.0 among them: the conversions of
 	// a batch and the sets of bit rows do not fit the registers of 3 waves per SIMD - 468 bytes of scratch per lane for uchar
 	// with four isovalues, 20 for ushort, 8 for uchar with two; that corner takes the unpacked form, which has none)
 	constexpr bool packed_form = !(SWEEP_PACK >= 2 && NI >= 2 && ZM == 0);
 	if (packed_form && sweep_packed(c)) {
-		if (a.ranges) hipLaunchKernelGGL((k_sweep<packed_form ? SWEEP_PACK : 1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
+		if (a.live) hipLaunchKernelGGL((k_sweep_live<packed_form ? SWEEP_PACK : 1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
+		else if (a.ranges) hipLaunchKernelGGL((k_sweep<packed_form ? SWEEP_PACK : 1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
 		else hipLaunchKernelGGL((k_sweep_all<packed_form ? SWEEP_PACK : 1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
 		return (uint32_t)SWEEP_PACK;
 	}
-	if (a.ranges) hipLaunchKernelGGL((k_sweep<1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
+	if (a.live) hipLaunchKernelGGL((k_sweep_live<1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
+	else if (a.ranges) hipLaunchKernelGGL((k_sweep<1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
 	else hipLaunchKernelGGL((k_sweep_all<1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
 	return 1u;
 }
@@ -384,6 +452,9 @@ static Params lane_params(const mc33hip_ctx *c, double iso) {
 static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const double *isos, int n, const SlotGeom &g) {
 	hipStream_t st = c->stream;
 	const uint32_t ze = c->range.z_end;
+	// (the lanes of a call were swept by one pass, so by one plan: the one their edge records are paired by)
+	if (int rc = plan_sweep(c, c->P.zs, ze, c->lanes[idx[0]].plan)) return rc;
+	const SweepPlan &pl = c->plan[c->cur_plan];
 	SweepArgs a;
 	sweep_args(c, g, a);
 #ifdef MC33_DEV
@@ -465,8 +536,8 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 		w.ctr_published = false;  // (the counters of THIS tail are on the device until somebody brings them over)
 	}
 	const uint32_t ny = (uint32_t)n;
-	if (c->nbounds && boundaries && !(MC33_DEBUG_BITS(a) & 2u))  // (the lanes of a call are all fresh, or it is one lane)
-		hipLaunchKernelGGL(k_boundary, dim3((uint32_t)((c->nbounds + 3) / 4), ny), dim3(256), 0, st, a, c->d_bounds, (uint32_t)c->nbounds);
+	if (pl.nbounds && boundaries && !(MC33_DEBUG_BITS(a) & 2u))  // (the lanes of a call are all fresh, or it is one lane)
+		hipLaunchKernelGGL(k_boundary, dim3((uint32_t)((pl.nbounds + 3) / 4), ny), dim3(256), 0, st, a, pl.d_bounds, (uint32_t)pl.nbounds);
 	for (int q = 0; q < n; q++) c->lanes[idx[q]].boundary_done = true;  // (its slices are in the partial sums now: a repeated tail - more room for records - must not add them again)
 	hipLaunchKernelGGL(k_slots, dim3((uint32_t)((g.nslots + SLOT_CHUNK - 1) / SLOT_CHUNK), ny), dim3(256), 0, st, SA, g.nslots);
 	for (int q = 0; q < n; q++) c->lanes[idx[q]].tail_pending = false;  // k_slots has read this epoch's partial sums and cleared the half of the next one
@@ -515,7 +586,6 @@ static bool same_range(const mc33hip_range &x, const mc33hip_range &y) {
 static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 	const Params &P = c->P;
 	hipStream_t st = c->stream;
-	if (int rc = plan_sweep(c, P.zs, c->range.z_end)) return rc;
 	SlotGeom g;
 	if (int rc = slot_geometry(c, g)) return rc;
 	IsoLane *L = nullptr;
@@ -524,7 +594,11 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 	else
 		for (int k = 0; k < MC33_LANES && !L; k++)
 			if (c->lanes[k].swept && same_bits((real_t)c->lanes[k].iso, P.iso) && same_range(c->lanes[k].range, c->range) &&
-			    c->lanes[k].slice_cap >= g.nslots && c->lanes[k].edge_cap >= c->ntiles) {
+			    c->lanes[k].slice_cap >= g.nslots) {
+				// (the plan it was swept by is looked at, not put in force: when its place holds another range's plan by now, the tail
+				// makes it again - the same plan, which the lane's edge buffers had room for)
+				const SweepPlan &lp = c->plan[c->lanes[k].plan];
+				if (lp.d_tiles && lp.zs == P.zs && lp.ze == c->range.z_end && c->lanes[k].edge_cap < lp.ntiles) continue;
 				L = &c->lanes[k];
 				tail_made = L->tail_done;
 			}
@@ -537,17 +611,20 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 		c->lane_presweeped = true;
 	} else {
 		L = &c->lanes[0];
+		const RangeEntry *ranges = sweep_ranges(c, st);
+		if (int rc = plan_sweep(c, P.zs, c->range.z_end, ranges ? table_plan(c) : 0)) return rc;
 		if (int rc = begin_lane(c, *L, g, st)) return rc;
 		c->lane_presweeped = false;
 		SweepArgs a;
 		sweep_args(c, g, a);
 		set_lane(a, 0, *L, P.iso);
-		a.ranges = sweep_ranges(c, st);
+		a.ranges = ranges;
+		sweep_live(c, a);
 		c->skipped_tiles = 0;
 		if (c->timing_level > 0 && (c->d_skipped || hipMalloc(&c->d_skipped, 4 * sizeof(uint32_t)) == hipSuccess)) {  // (mc33hip_sweep_skipped; never on the production path)
 			HIP_TRY(hipMemsetAsync(c->d_skipped, 0, 4 * sizeof(uint32_t), st));
 			a.skipped = c->d_skipped;
-			c->skipped_tiles = c->ntiles;
+			c->skipped_tiles = a.ntiles;
 		} else if (c->timing_level > 0) (void)hipGetLastError();
 #ifdef MC33_DEV
 		a.debug = c->sw.debug;
@@ -559,7 +636,7 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 #endif
 		if (c->sw.trace_file) {
 			c->trace_waves = 0;  // (a new one for every sweep)
-			if (int rc = dev_room("sweep trace", &c->trace, &c->trace_waves, ((c->ntiles + 3) / 4) * 4, 32)) return rc;
+			if (int rc = dev_room("sweep trace", &c->trace, &c->trace_waves, (((uint64_t)a.ntiles + 3) / 4) * 4, 32)) return rc;
 			HIP_TRY(hipMemsetAsync(c->trace, 0, c->trace_waves * 32, st));
 			a.trace = c->trace;
 			if (c->timing_level > 0) HIP_TRY(hipEventRecord(c->ev[0], st));
@@ -603,7 +680,6 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 // one exchange of counts per step instead of one per isovalue).
 static int enqueue_sweep_many(mc33hip_ctx *c, const double *isos, int n, bool tails_ahead) {
 	hipStream_t st = c->stream;
-	if (int rc = plan_sweep(c, c->P.zs, c->range.z_end)) return rc;
 	SlotGeom g;
 	if (int rc = slot_geometry(c, g)) return rc;
 	if (tails_ahead) {
@@ -624,6 +700,9 @@ static int enqueue_sweep_many(mc33hip_ctx *c, const double *isos, int n, bool ta
 	int k = 0, pass = 0;
 	while (k < n) {
 		const int ni = (n - k >= 4) ? 4 : (n - k >= 2) ? 2 : 1;
+		// (the table may be built in front of the second pass: every pass goes by the plan of what it has, and its lanes keep it)
+		const RangeEntry *ranges = sweep_ranges(c, st);
+		if (int rc = plan_sweep(c, c->P.zs, c->range.z_end, ranges ? table_plan(c) : 0)) return rc;
 		SweepArgs a;
 		sweep_args(c, g, a);
 #ifdef MC33_DEV
@@ -634,7 +713,8 @@ static int enqueue_sweep_many(mc33hip_ctx *c, const double *isos, int n, bool ta
 			if (int rc = begin_lane(c, L, g, st)) return rc;
 			set_lane(a, q, L, isos[k + q]);
 		}
-		a.ranges = sweep_ranges(c, st);
+		a.ranges = ranges;
+		sweep_live(c, a);
 		// (events around the pass are only recorded; read_timing asks for the elapsed time when the lane is consumed)
 		const bool timed = c->timing_level > 0 && pass < MC33_MANY_PASSES;
 		if (timed) HIP_TRY(hipEventRecord(c->ev_many[pass][0], st));
@@ -1228,6 +1308,33 @@ extern "C" int mc33hip_sweep_skipped(mc33hip_ctx *c, unsigned long long *out /*[
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	HIP_TRY(hipMemcpy(w, c->d_skipped, sizeof w, hipMemcpyDeviceToHost));
 	out[0] = c->skipped_tiles; out[1] = w[1]; out[2] = w[2];
+	return MC33HIP_OK;
+}
+
+// ---- ... and of the plan and the live list (tests/test_gpu_sweep_refill.py, tools/trace_sweep.py) ----
+extern "C" int mc33hip_sweep_plan(mc33hip_ctx *c, unsigned int *tiles_out, size_t cap_tiles, unsigned long long *info /*[3]*/) {
+	if (!c || !info) return MC33HIP_EINVAL;
+	const SweepPlan &pl = c->plan[c->cur_plan];
+	if (!pl.d_tiles || !pl.ze) { set_err("no sweep plan yet"); return MC33HIP_EINVAL; }
+	info[0] = pl.ntiles; info[1] = c->resident_blocks; info[2] = (unsigned long long)c->cur_plan;
+	if (!tiles_out) return MC33HIP_OK;
+	if (cap_tiles < pl.ntiles) { set_err("sweep plan: %llu tiles, room for %llu", (unsigned long long)pl.ntiles, (unsigned long long)cap_tiles); return MC33HIP_EINVAL; }
+	if (int rc = use_device(c)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	HIP_TRY(hipMemcpy(tiles_out, pl.d_tiles, pl.ntiles * sizeof(SweepTile), hipMemcpyDeviceToHost));
+	return MC33HIP_OK;
+}
+extern "C" int mc33hip_sweep_live(mc33hip_ctx *c, unsigned int *live_out, size_t cap_entries, unsigned long long *info /*[2]*/) {
+	if (!c || !info) return MC33HIP_EINVAL;
+	if (!c->live_blocks || !c->d_live) { set_err("the last sweep went by no live list"); return MC33HIP_EINVAL; }
+	if (int rc = use_device(c)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	uint32_t n = 0;
+	HIP_TRY(hipMemcpy(&n, c->d_live, sizeof n, hipMemcpyDeviceToHost));
+	info[0] = n; info[1] = c->live_blocks;
+	if (!live_out) return MC33HIP_OK;
+	if (n > c->live_blocks || cap_entries < n) { set_err("live list: %u entries of %llu blocks, room for %llu", n, (unsigned long long)c->live_blocks, (unsigned long long)cap_entries); return MC33HIP_EINVAL; }
+	if (n) HIP_TRY(hipMemcpy(live_out, c->d_live + 1, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	return MC33HIP_OK;
 }
 

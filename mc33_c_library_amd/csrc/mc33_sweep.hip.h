@@ -126,6 +126,126 @@ __global__ __launch_bounds__(256) void k_ranges(const GridView<sample_t> G, cons
 	if (lane == 0) out[((uint64_t)pl * nYT + yt) * P.nseg + seg] = RangeEntry{lo, hi};
 }
 
+// ---------------------------------------------------------------------------------------------------
+// k_tile_verdicts / k_live_compact: which tiles of the plan the sweep with a range table (k_sweep) has to stream, decided in front
+// of it.  A tile whose strips - of the planes it would READ, pl0 .. z_hi - all lie strictly above, or all strictly below, every
+// isovalue of the pass holds no cut cell and no sample equal to an isovalue, and is not streamed.  Both comparisons are strict and
+// made in MC33_real, on the values the sweep would have compared:
+//   lo > iso: every sample F of the tile has F > iso, so d = iso - F is negative and NOT zero - the difference of two different
+//     floating-point numbers is never zero while denormals are kept, and the code objects keep them (float_denorm_mode 3; no
+//     flush-to-zero option in the build) - its sign bit is 1 (the integer forms classify by F > iso itself): all bits 1;
+//   hi < iso: d is positive and not zero: all bits 0.
+//   iso == +-0 against a sample +-0 compares equal: neither holds, the tile is streamed.  A NaN isovalue: neither holds.  A strip
+//   with a NaN sample has {-inf, +inf}: neither holds for any isovalue.
+// A wave of k_tile_verdicts per block of the sweep (four consecutive tiles of the plan).  Lane l looks at the strips of the planes
+// pl0 + l, + 64, ...: one 8- / 16-byte load per lane, tile and 64 planes, the comparisons in the lane, one AND over the wave; the four
+// tiles of a block the plan has grouped (the segments seg .. seg + 3 of one y tile over the same planes) are four neighbouring
+// entries of the table per plane and take one pass.
+// What a dead tile leaves behind is what a streamed one would have for k_boundary, and nothing else: the headers of the edge
+// records of its first plane (when the tile below exists) and last plane (when a tile above does) - halo bits all 0 / all 1, no
+// row and no lane with a sample equal to the isovalue, PLANE_UNIFORM0 / PLANE_UNIFORM1 (no record) - per isovalue lane.  No slice
+// header (an older one carries an older epoch), nothing added to slot_part.
+// The block's verdict is a byte: bit k, wave k has nothing to stream (its tile is dead, or the plan ends before it).  k_live_compact -
+// ONE block - turns the bytes into the live list (SweepArgs::live) in plan order, which is ascending z_lo, the locality the plan's
+// sort exists for: no atomic decides the order.  Both are ordered with the sweep by the stream and by nothing else.
+// ---------------------------------------------------------------------------------------------------
+// bit 2 NI k + 2 q of the result: all strips of tile k (k < nk: the segments seg0 + k over the planes of `tile`) lie below isovalue q; + 1: all above
+template <int NI>
+__device__ __forceinline__ uint32_t tile_sides(const SweepArgs &a, const SweepTile &tile, uint32_t seg0, uint32_t nk, uint32_t lane) {
+	const uint32_t p0r = tile.z_lo == a.P.zs ? tile.z_lo : tile.z_lo + 1u;
+	uint32_t m = 0xFFFFFFFFu;
+	for (uint32_t p = p0r + lane; p <= tile.z_hi; p += 64u) {
+		const RangeEntry *row = a.ranges + (((uint64_t)(p - a.G.z0) * a.sd.nYT + tile.yt) * a.sd.nseg + seg0);
+		static_for<4>([&](auto kc) __attribute__((always_inline)) {
+			constexpr int k = decltype(kc)::value;
+			if ((uint32_t)k < nk) {  // (wave-uniform)
+				const RangeEntry e = row[k];
+				static_for<NI>([&](auto qc) __attribute__((always_inline)) {
+					constexpr int q = decltype(qc)::value;
+					const real_t v = a.lane[q].iso;
+					m &= ~(((e.hi < v ? 0u : 1u) | (e.lo > v ? 0u : 2u)) << (2 * NI * k + 2 * q));
+				});
+			}
+		});
+	}
+#pragma unroll
+	for (int dlt = 32; dlt; dlt >>= 1) m &= (uint32_t)__shfl_xor((int)m, dlt);
+	return (uint32_t)__builtin_amdgcn_readfirstlane((int)m);
+}
+template <int NI>
+__global__ __launch_bounds__(256) void k_tile_verdicts(const SweepArgs a, uint8_t *verdict, const uint32_t nblocks) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t b = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	if (b >= nblocks) return;
+	const uint32_t t0 = b * 4u, nt = min(4u, a.ntiles - t0);
+	SweepTile t[4];
+#pragma unroll
+	for (uint32_t k = 0; k < 4; k++) t[k] = a.tiles[min(t0 + k, a.ntiles - 1u)];
+	bool grouped = nt == 4u;  // (as k_sweep decides it)
+#pragma unroll
+	for (uint32_t k = 1; k < 4; k++) grouped = grouped && t[k].seg == t[0].seg + k && t[k].yt == t[0].yt && t[k].z_lo == t[0].z_lo && t[k].z_hi == t[0].z_hi;
+	constexpr uint32_t EVEN = NI == 4 ? 0x55u : NI == 2 ? 0x5u : 0x1u, ALLQ = (1u << (2 * NI)) - 1u;
+	uint32_t m = 0u;
+	if (grouped) m = tile_sides<NI>(a, t[0], t[0].seg, 4u, lane);
+	else
+		static_for<4>([&](auto kc) __attribute__((always_inline)) {
+			constexpr int k = decltype(kc)::value;
+			if ((uint32_t)k < nt) m |= (tile_sides<NI>(a, t[k], t[k].seg, 1u, lane) & ALLQ) << (2 * NI * k);
+		});
+	uint32_t dead = 0u;
+	static_for<4>([&](auto kc) __attribute__((always_inline)) {
+		constexpr int k = decltype(kc)::value;
+		if ((uint32_t)k >= nt) { dead |= 1u << k; return; }
+		const uint32_t mine = (m >> (2 * NI * k)) & ALLQ;  // bit 2q: all strips of the tile below isovalue q; bit 2q + 1: all above
+		if (((mine | mine >> 1) & EVEN) != EVEN) return;   // a tile is dead when each of its isovalues has one of its two bits
+		dead |= 1u << k;
+		if (lane == 0) {
+			const bool has_below = t[k].z_lo != a.P.zs, has_above = t[k].z_hi < a.z_end;
+			static_for<NI>([&](auto qc) __attribute__((always_inline)) {
+				constexpr int q = decltype(qc)::value;
+				const bool above = ((mine >> (2 * q)) & 2u) != 0u;
+				const uint32_t hb = above ? 0xFFFFFFFFu : 0u;
+				uint4 *h = a.lane[q].edge_hdr + (uint64_t)(t0 + k) * 2u * 2u;
+				if (has_below) { h[0] = uint4{hb, hb, 0u, 0u}; h[1] = uint4{0u, 0u, above ? PLANE_UNIFORM1 : PLANE_UNIFORM0, 0u}; }
+				if (has_above) { h[2] = uint4{hb, hb, 0u, 0u}; h[3] = uint4{0u, 0u, above ? PLANE_UNIFORM1 : PLANE_UNIFORM0, 0u}; }
+			});
+			if (NI == 1 && a.skipped) atomicAdd(a.skipped + ((mine & 2u) ? 2 : 1), 1u);
+		}
+	});
+	if (lane == 0) verdict[b] = (uint8_t)dead;
+}
+// published (pinned host memory, nullptr: none): live TILES << 32 | tiles << 1 | plan, in ONE 8-byte store - what the host's choice
+// between the two plans of a sweep with a table goes by (table_plan), read there whenever it comes by, never waited for.
+__global__ __launch_bounds__(1024) void k_live_compact(const uint8_t *verdict, const uint32_t nblocks, uint32_t *live, unsigned long long *published, const uint32_t plan, const uint32_t ntiles) {
+	__shared__ uint32_t s_wave[16], s_tiles;
+	if (threadIdx.x == 0) s_tiles = 0u;
+	__syncthreads();
+	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+	const uint32_t per = (nblocks + 1023u) / 1024u, b0 = min(tid * per, nblocks), b1 = min(b0 + per, nblocks);  // thread tid: the blocks b0 .. b1 - 1
+	uint32_t n = 0;
+	uint32_t nt = 0;  // live tiles (a wave past the plan's end counts as dead: k_tile_verdicts)
+	for (uint32_t b = b0; b < b1; b++) { const uint32_t v = verdict[b] & 15u; n += v != 15u ? 1u : 0u; nt += 4u - (uint32_t)__popc(v); }
+	if (nt) atomicAdd(&s_tiles, nt);  // (a sum: the order does not matter)
+	uint32_t incl = n;
+#pragma unroll
+	for (int dlt = 1; dlt < 64; dlt <<= 1) {
+		const uint32_t o = __shfl_up(incl, dlt);
+		incl += lane >= (uint32_t)dlt ? o : 0u;
+	}
+	if (lane == 63u) s_wave[wv] = incl;
+	__syncthreads();
+	uint32_t before = incl - n, total = 0;
+	for (uint32_t w = 0; w < 16u; w++) { before += w < wv ? s_wave[w] : 0u; total += s_wave[w]; }
+	for (uint32_t b = b0; b < b1; b++) {
+		const uint32_t v = verdict[b] & 15u;
+		if (v != 15u) live[1u + before++] = b << 4 | v;
+	}
+	if (tid == 0) {
+		live[0] = total;
+		if (published) __atomic_store_n(published, (unsigned long long)s_tiles << 32 | (unsigned long long)ntiles << 1 | (plan & 1u), __ATOMIC_RELAXED);
+	}
+}
+
 // S: samples per lane and load.  S = 1: every lane loads single samples (all types); S = SWEEP_PACK > 1: dwords of 2
 // unsigned shorts / 4 unsigned chars - needs rows that start on a dword boundary (the host checks), and makes a batch
 // 8 / 16 sample rows instead of 4, so that a wave keeps the same 16 x 256 bytes in flight.
@@ -135,16 +255,33 @@ __global__ __launch_bounds__(256) void k_ranges(const GridView<sample_t> G, cons
 // subtraction, the |d| and the running minimum go: 1: one compare for the sign, one for "equals the isovalue"; 2: no
 // isovalue of the pass is an integer of the sample type's range - nothing can equal it, one compare per sample and isovalue
 // (the 4-isovalue pass over ushort samples is bound by its instructions: 94 -> 58 per sample row).
-// R: the form that looks at the range table first (k_sweep); without it (k_sweep_all, what a sweep without a table launches - a
-// volatile grid, the first sweep over new samples, MC33_HIP_RANGES=0) the body is the one the kernel had before there was a table,
-// instruction for instruction: the preamble being THERE cost the packed passes over several isovalues 3 % whether or not it ran
-// (profiles/r08_range_skip.txt D), and a caller without a table pays nothing for it.
-template <int S, int NI, int ZM, bool R>
+// R: what the kernel knows of the range table.  0 (k_sweep_all, what a sweep without a table launches - a volatile grid, the first
+// sweep over new samples, MC33_HIP_RANGES=0): nothing; block b streams the tiles 4 b .. 4 b + 3 and the body is the one the kernel
+// had before there was a table, instruction for instruction: code for the table being THERE cost the packed passes over several
+// isovalues 3 % whether or not it ran (profiles/r08_range_skip.txt D), and a caller without a table pays nothing for it.
+// 1 (k_sweep): every wave works out its verdict itself, in a preamble - plans of less than one round of the device (small grids).
+// 2 (k_sweep_live): the verdicts were made in front of the kernel, and block blockIdx.x streams the tiles of live[1 + blockIdx.x] -
+// plans of one round and more, whose live tiles have to fill the device by themselves.
+template <int S, int NI, int ZM, int R>
 __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 	constexpr int LPR = 4 / S;    // loads per sample row
 	constexpr int RB = 16 / LPR;  // sample rows per batch
 	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t wtile = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform, in an SGPR
+	// R: the block's place in the plan comes from the live list.  The launch is one block per planned block; those beyond the list
+	// end here, at their first instructions.  The wave of a dead tile in a block that has live ones does not return here (a second exit
+	// gave the packed forms over several isovalues a quarter more SGPRs parked in VGPR lanes): its tile has no batches - T = 0 below -
+	// so it walks past the loop, flushes an empty log, and ends where every wave ends.  The one batch issued ahead of the loop goes
+	// through a descriptor of zero bytes: no memory access.
+	uint32_t wtile = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform, in an SGPR
+	bool whole = true;  // (block-uniform) every wave of the block has a tile to stream
+	bool dead_me = false;
+	if constexpr (R == 2) {
+		if (blockIdx.x >= a.live[0]) return;
+		const uint32_t e = a.live[1u + blockIdx.x];
+		dead_me = ((e >> (wtile & 3u)) & 1u) != 0u;
+		wtile = (e >> 4) * 4u + (wtile & 3u);
+		whole = (e & 15u) == 0u;
+	}
 	if (wtile >= a.ntiles) return;
 	const SweepTile tile = a.tiles[wtile];
 	const uint32_t yt = tile.yt, seg = tile.seg;
@@ -160,8 +297,8 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 	// of planes (same rows, same z range), so every wave reaches every barrier; blocks of unrelated tiles keep the load.
 	bool grouped = true;
 	{
-		const uint32_t t0 = blockIdx.x * 4u;
-		if (t0 + 3u >= a.ntiles) grouped = false;
+		const uint32_t t0 = wtile & ~3u;
+		if (t0 + 3u >= a.ntiles || !whole) grouped = false;  // (a block with a dead wave runs ungrouped: its live waves load their own halo column, and there is no barrier in it)
 		else {
 			const SweepTile first = a.tiles[t0];
 #pragma unroll
@@ -173,28 +310,12 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 	}
 	const unsigned long long t_start = a.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
 	const unsigned long long c_start = a.trace ? __builtin_amdgcn_s_memtime() : 0ull;
-	// The range table (RangeEntry): a tile whose strips - of the planes it would READ, pl0 .. z_hi - all lie strictly above, or all
-	// strictly below, every isovalue of the pass holds no cut cell and no sample equal to an isovalue, and is not streamed.  Lane l
-	// looks at the strips of the planes pl0 + l, + 64, ...: one 8- / 16-byte load per lane and 64 planes, the comparisons in the lane,
-	// one AND over the wave.  Both comparisons are strict and made in MC33_real, on the values the sweep would have compared:
-	//   lo > iso: every sample F of the tile has F > iso, so d = iso - F is negative and NOT zero - the difference of two different
-	//     floating-point numbers is never zero while denormals are kept, and the code objects keep them (float_denorm_mode 3; no
-	//     flush-to-zero option in the build) - its sign bit is 1 (the integer forms classify by F > iso itself): all bits 1;
-	//   hi < iso: d is positive and not zero: all bits 0.
-	//   iso == +-0 against a sample +-0 compares equal: neither holds, the tile is streamed.  A NaN isovalue: neither holds.  A strip
-	//   with a NaN sample has {-inf, +inf}: neither holds for any isovalue.
-	// What a dead wave leaves behind is what a live one would have for k_boundary, and nothing else: the headers of the edge records
-	// of its first plane (when the tile below exists) and last plane (when a tile above does) - halo bits all 0 / all 1, no row and
-	// no lane with a sample equal to the isovalue, PLANE_UNIFORM0 / PLANE_UNIFORM1 (no record) - from lane 0.  No slice header (an
-	// older one carries an older epoch), nothing added to slot_part, no log.
-	// The mailbox: every wave of a block that could be grouped works out the verdicts of all four tiles - they are the same four
-	// computations in all four waves, so the result is block-uniform - and a block with a dead tile runs UNGROUPED: its live waves
-	// load their own halo column, as in every ungrouped block, and there is no barrier in such a block at all.  A dead wave does not
-	// return here (a second exit in the middle of the kernel gave the packed forms over several isovalues a scratch segment): its
-	// tile has no batches - T = 0 below - so it walks past the loop, flushes an empty log, and ends where every wave ends.  The one
-	// batch issued ahead of the loop goes through a descriptor of zero bytes: no memory access.
-	bool dead_me = false;
-	if (R && a.ranges) {
+	// R == 1, the preamble: the verdicts (see k_tile_verdicts for the arithmetic - it is the same) worked out by the wave itself, for
+	// plans of less than one round of the device, where two small launches in front of the sweep cost more than they give.  Lane l
+	// looks at the strips of the planes pl0 + l, + 64, ...; every wave of a block that could be grouped works out the verdicts of all
+	// four tiles - the same four computations in all four waves, so the result is block-uniform - and a block with a dead tile runs
+	// UNGROUPED.  A dead wave leaves the headers of its edge records from lane 0 and has no batches (T = 0 below).
+	if (R == 1 && a.ranges) {
 		const uint32_t wme = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 		// (a grouped block: the four tiles are the segments seg .. seg + 3 of one y tile over the same planes - four neighbouring
 		// entries of the table per plane, all four verdicts from one pass; any other block: the wave's own tile only)
@@ -726,7 +847,7 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 			if (pend_sum[q] && lane == 0) atomicAdd(a.lane[q].slot_part + pend_chunk[q], pend_sum[q]);
 	}
 	if (a.trace && lane == 0) {
-		unsigned long long *tr = a.trace + 4ull * wtile;
+		unsigned long long *tr = a.trace + 4ull * (blockIdx.x * 4u + wv);  // (by launched wave: block index mod 8 is the XCD; the tile is live[1 + block])
 		tr[0] = t_start; tr[1] = __builtin_amdgcn_s_memrealtime(); tr[2] = c_start; tr[3] = __builtin_amdgcn_s_memtime();
 	}
 #undef MC33_ADV_ISSUE
@@ -735,11 +856,15 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 }
 template <int S, int NI, int ZM = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_sweep(const SweepArgs a) {  // (3 waves per SIMD: at most 168 VGPRs - the 4-lane form sits right at that edge)
-	sweep_tile<S, NI, ZM, true>(a);
+	sweep_tile<S, NI, ZM, 1>(a);
+}
+template <int S, int NI, int ZM = 0>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_sweep_live(const SweepArgs a) {
+	sweep_tile<S, NI, ZM, 2>(a);
 }
 template <int S, int NI, int ZM = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_sweep_all(const SweepArgs a) {
-	sweep_tile<S, NI, ZM, false>(a);
+	sweep_tile<S, NI, ZM, 0>(a);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -757,9 +882,16 @@ __global__ __launch_bounds__(256) void k_boundary(const SweepArgs a, const TileB
 	const Params &P = a.P;
 	const uint32_t seg = b.seg;
 	const uint64_t rp = (uint64_t)b.below * 2u + 1u, rc = (uint64_t)b.above * 2u;  // top of below, bottom of above
+	const uint4 hp = L.edge_hdr[rp * 2u], hc = L.edge_hdr[rc * 2u], zp = L.edge_hdr[rp * 2u + 1u], zc = L.edge_hdr[rc * 2u + 1u];
+	// Both planes wholly on the same side, halo columns included - every pair of dead tiles (k_tile_verdicts), and most pairs of a
+	// smooth field under a plan with a table, which has three times the pairs: no cell between them is cut, whatever equals the
+	// isovalue (such a sample has bit 0), and the wave ends on the four header words without asking for a record.
+	if (zp.z >= PLANE_UNIFORM0 && zp.z == zc.z) {  // (wave-uniform)
+		const uint32_t side = zp.z == PLANE_UNIFORM1 ? 0xFFFFFFFFu : 0u;
+		if (hp.x == side && hp.y == side && hc.x == side && hc.y == side) return;
+	}
 	const uint4 p0 = L.edge_bits[rp * 128u + lane], p1 = L.edge_bits[rp * 128u + 64u + lane];
 	const uint4 c0 = L.edge_bits[rc * 128u + lane], c1 = L.edge_bits[rc * 128u + 64u + lane];
-	const uint4 hp = L.edge_hdr[rp * 2u], hc = L.edge_hdr[rc * 2u], zp = L.edge_hdr[rp * 2u + 1u], zc = L.edge_hdr[rc * 2u + 1u];
 	// (both forms of both records are asked for at once - which one a plane has stands in its header, zp.z / zc.z)
 	const uint32_t dp = ((const uint32_t *)(L.edge_bits + rp * 128u))[lane], dc = ((const uint32_t *)(L.edge_bits + rc * 128u))[lane];
 	uint64_t prev[4] = {u64(p0.x, p0.y), u64(p0.z, p0.w), u64(p1.x, p1.y), u64(p1.z, p1.w)};
