@@ -215,6 +215,34 @@ int MC33_isosurface_topology(MC33 *extractor, MC33_real isovalue, mc33_topology 
 int MC33_component_topology(MC33 *extractor, MC33_real isovalue, mc33_component_topology *table, unsigned capacity,
                             unsigned *components);
 
+/* extension (not in the reference): how the surface bends - mean, Gaussian and principal curvatures of the level set of the grid
+ * through every vertex, from the grid's gradient and second differences on the GPU (orthogonal grids, one device, at least 2
+ * cells per axis; the operations one by one are in mc33_hip.h, mc33hip_curvature_vertices).  mean > 0 is convex seen from the
+ * side N points to, in the plain flavours and in the _nneg ones alike: for a blob of high samples extracted by the plain library.
+ * MC33_set_color_source chooses what a colour map (MC33_set_color_map) paints: MC33_COLOR_PROPERTY - the default - the property
+ * grid, as before; MC33_COLOR_MEAN, _GAUSS, _K1, _K2 one of the curvatures, for which no property grid is needed.  With a map and
+ * a curvature source calculate_isosurface(s), the filtered, smoothed, simplified and clipped calls and the points of a section
+ * fill surface.color from the curvature of the FIELD at the vertices they colour today (a smoothed or simplified vertex has left
+ * the field's surface: it gets the curvature of the level set it now lies on).  It returns 0, or -1 with nothing changed: an
+ * unknown source; for a curvature source an inclined grid, an extractor spread over several devices, an axis with fewer than 2
+ * cells, a device layer without the pass.
+ * MC33_isosurface_curvature extracts into device memory like MC33_measure_isosurface and returns only the struct: the sizes,
+ * lo[q] / hi[q] - the extremes of the finite values of mean, gauss, k1, k2 (q = 0 .. 3; +inf / -inf when there are none), what a
+ * caller needs to choose the colour map's range -, the vertices whose four values are all finite and the others, and
+ * total_mean / total_gauss: sum area_i * (C(q0) + C(q1) + C(q2)) / 3 of the mean and the Gaussian curvature, exactly the sum
+ * MC33_measure_isosurface makes of a property (NaN, both, when a vertex is undefined).  For a closed surface total_gauss
+ * approximates 2 pi times the Euler number of MC33_isosurface_topology.  It returns 0, or -1; sets extractor->iso, leaves
+ * memoryfault alone, and refuses what MC33_set_color_source refuses for a curvature source. */
+#define MC33_COLOR_PROPERTY 0
+#define MC33_COLOR_MEAN 1
+#define MC33_COLOR_GAUSS 2
+#define MC33_COLOR_K1 3
+#define MC33_COLOR_K2 4
+typedef struct mc33_curvature { unsigned nV, nT; double lo[4], hi[4]; unsigned long long finite, undefined;
+                                double total_mean, total_gauss; } mc33_curvature;
+int MC33_set_color_source(MC33 *extractor, int source);
+int MC33_isosurface_curvature(MC33 *extractor, MC33_real isovalue, mc33_curvature *out);
+
 /* extension (not in the reference): keep or drop whole components of an isosurface on the GPU, so that only the kept rows cross
  * the link.  MC33_select_components is the ONE place where components are chosen - host C, no GPU: from the n rows of
  * MC33_measure_components (and, for closed_only, the n rows of MC33_component_topology; NULL otherwise) it writes the roots of the

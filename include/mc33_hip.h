@@ -797,6 +797,57 @@ int mc33hip_section_ladder(mc33hip_ctx *c, const void *dV, unsigned long long nV
                            const double normal[3], const double *offsets, unsigned n, unsigned long long *segments, double *length,
                            double *area, unsigned long long *invalid_triangles);
 
+/* --- curvature of the implicit surface at the vertices, from the grid's second differences (no counterpart in the reference) ------
+ * Mean, Gaussian and principal curvatures of the surface F = iso at nV vertices dV (nV x 3 MC33_real in device memory, what
+ * mc33hip_emit wrote, or any points), taken from the gradient g and the Hessian H of the RESIDENT grid - the curvature of the field's
+ * level set through the vertex, which is where N comes from too; nothing is taken from the triangles.  Orthogonal grids only.
+ * Everything in IEEE double, nothing fused, only + - * / and sqrt: the outputs are an exact function of the inputs.
+ *   grid        N[a] cells, points 0 .. N[a], spacing d[a], origin r0[a] (the doubles of the descriptor), N[a] >= 2 on every axis;
+ *               S(i, j, k) the resident sample converted to double.
+ *   per node    for node index n along axis a, the other two indices the node's own:
+ *                 p = min(n + 1, N[a]);  m = max(n - 1, 0);  c = min(max(n, 1), N[a] - 1)
+ *                 g_a  = (S(p) - S(m)) / ((double)(p - m) * d[a])
+ *                 H_aa = ((S(c + 1) - S(c)) - (S(c) - S(c - 1))) / (d[a] * d[a])
+ *               (on a grid face the second difference is taken about the nearest interior point), and for a < b
+ *                 H_ab = ((S(pa, pb) - S(pa, mb)) - (S(ma, pb) - S(ma, mb))) / (((double)(pa - ma) * d[a]) * ((double)(pb - mb) * d[b]))
+ *   per vertex  1. g[a], i[a], f[a] of mc33hip_sample_property, word for word: the clamps, f = 0 where i == N, a NaN coordinate.
+ *               2. each of gx, gy, gz, hxx, hyy, hzz, hxy, hxz, hyz of the nodes i + {0, 1} is interpolated with that definition's
+ *                  lerp along x, then y, then z; a node with f == 0 on its axis is not evaluated and its samples are not read.
+ *               3. g2 = (gx*gx + gy*gy) + gz*gz;  gl = sqrt(g2);  tr = (hxx + hyy) + hzz
+ *               4. gHg = (((gx*gx)*hxx + (gy*gy)*hyy) + (gz*gz)*hzz) + 2.0 * ((((gx*gy)*hxy) + ((gx*gz)*hxz)) + ((gy*gz)*hyz))
+ *               5. mean = sign * ((gHg - g2*tr) / ((2.0*g2) * gl))
+ *               6. axx = hyy*hzz - hyz*hyz;  ayy = hxx*hzz - hxz*hxz;  azz = hxx*hyy - hxy*hxy
+ *                  axy = hxz*hyz - hxy*hzz;  axz = hxy*hyz - hxz*hyy;  ayz = hxy*hxz - hxx*hyz
+ *               7. gAg = step 4 with a.. in place of h..;  gauss = gAg / (g2*g2)
+ *               8. disc = mean*mean - gauss;  r = sqrt(disc < 0 ? 0 : disc);  k1 = mean + r;  k2 = mean - r
+ *               9. oMean, oGauss, oK1, oK2 [v] = those doubles rounded to float.
+ *               Nothing is special-cased: a vanishing gradient gives 0/0 = NaN, NaN and infinite samples propagate.
+ *   sign        +1 or -1.  With +1 a blob of HIGH samples is convex and has mean > 0 - seen from the side the plain libraries' N
+ *               points to; the MC33_NORMAL_NEG flavours of the C API pass -1.
+ *   outputs     device arrays of nV floats; each may be NULL, all NULL asks for the summary alone.
+ *   summary     lo[q], hi[q], q = mean, gauss, k1, k2: minimum and maximum of the FINITE floats of output q as doubles, +inf / -inf
+ *               when it has none; finite: the vertices whose four floats are all finite; undefined = nV - finite.  Taken with
+ *               integer atomics on ordered keys: two calls return the same bytes.
+ * The grid may be the library's copy or an adopted buffer at any pitch, slice and alignment; only grid points are read.  The call
+ * enqueues on the context's stream behind whatever is on it, waits, and brings the summary to the host; nV == 0 succeeds and
+ * touches nothing.  MC33HIP_EINVAL, checked on the host, nothing is written: no resident grid; a z-slab context (plane0 != 0 or
+ * npz_resident != nz_total + 1); an inclined context; an axis with fewer than 2 cells; a sign other than +-1; dV == NULL with
+ * nV > 0.  Scratch, with the context until mc33hip_destroy: 40 bytes. */
+typedef struct {
+	const void *dV;  unsigned long long nV;  int sign;   /* in */
+	float *oMean, *oGauss, *oK1, *oK2;                   /* out (device), each nV floats or NULL */
+	double lo[4], hi[4];                                 /* filled: mean, gauss, k1, k2 */
+	unsigned long long finite, undefined;                /* filled */
+} mc33hip_curvature;
+int mc33hip_curvature_vertices(mc33hip_ctx *c, mc33hip_curvature *a);
+/* The colour step of mc33hip_color_vertices over any nV floats dP in device memory - what mc33hip_sample_property or
+ * mc33hip_curvature_vertices left: dC[v] = palette[(int)floor(s * (n - 1) + 0.5)], s = ((double)dP[v] - lo) / (hi - lo) clamped to
+ * [0, 1], nan_color where dP[v] is NaN.  For the floats of mc33hip_sample_property these are the words mc33hip_color_vertices
+ * gives.  Only enqueues on the context's stream; needs no property grid and takes an inclined context.  MC33HIP_EINVAL: a null
+ * pointer where the size is not zero, a NULL palette, n outside 2..256, lo >= hi or a NaN bound. */
+int mc33hip_color_values(mc33hip_ctx *c, const float *dP, unsigned long long nV, const int *palette, unsigned int n, double lo,
+                         double hi, int nan_color, int *dC);
+
 /* Plain device allocations on the context's device (for language bindings). */
 int mc33hip_device_alloc(mc33hip_ctx *c, void **dptr, size_t bytes);
 int mc33hip_device_free(mc33hip_ctx *c, void *dptr);

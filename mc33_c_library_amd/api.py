@@ -179,6 +179,21 @@ class SpectrumInfo(C.Structure):
                 ("sample_min", C.c_double), ("sample_max", C.c_double)]
 
 
+class Curvature(C.Structure):
+    """mc33hip_curvature (include/mc33_hip.h): dV and the four outputs are DEVICE arrays, each output may be NULL"""
+    _fields_ = [("dV", C.c_void_p), ("nV", C.c_ulonglong), ("sign", C.c_int),
+                ("oMean", C.c_void_p), ("oGauss", C.c_void_p), ("oK1", C.c_void_p), ("oK2", C.c_void_p),
+                ("lo", C.c_double * 4), ("hi", C.c_double * 4), ("finite", C.c_ulonglong), ("undefined", C.c_ulonglong)]
+
+
+class IsosurfaceCurvature(C.Structure):
+    """mc33_curvature (include/marching_cubes_33.h)"""
+    _fields_ = [("nV", C.c_uint), ("nT", C.c_uint), ("lo", C.c_double * 4), ("hi", C.c_double * 4),
+                ("finite", C.c_ulonglong), ("undefined", C.c_ulonglong), ("total_mean", C.c_double), ("total_gauss", C.c_double)]
+
+
+CURVATURES = ("mean", "gauss", "k1", "k2")
+
 HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_last_error", "mc33hip_upload_rows",
            "mc33hip_upload_contiguous", "mc33hip_adopt_device", "mc33hip_set_stream", "mc33hip_count",
            "mc33hip_emit", "mc33hip_extract", "mc33hip_last_timing", "mc33hip_download",
@@ -193,7 +208,7 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_resampled_size", "mc33hip_resample_grid", "mc33hip_context_device", "mc33hip_grid_spectrum",
            "mc33hip_clip_surface", "mc33hip_section_surface", "mc33hip_section_contours", "mc33hip_section_ladder",
            "mc33hip_grid_stable", "mc33hip_grid_changed", "mc33hip_range_table", "mc33hip_sweep_skipped",
-           "mc33hip_sweep_plan", "mc33hip_sweep_live"]
+           "mc33hip_sweep_plan", "mc33hip_sweep_live", "mc33hip_curvature_vertices", "mc33hip_color_values"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -207,7 +222,8 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "MC33_gaussian_taps", "MC33_create_resampled", "MC33_resampled_grid",
                  "MC33_grid_spectrum", "MC33_isovalue_ladder",
                  "MC33_calculate_clipped_isosurface", "MC33_clip_box",
-                 "MC33_section_isosurface", "MC33_free_section", "MC33_section_contours", "MC33_section_profile"]
+                 "MC33_section_isosurface", "MC33_free_section", "MC33_section_contours", "MC33_section_profile",
+                 "MC33_set_color_source", "MC33_isosurface_curvature"]
 
 
 class MC33Error(RuntimeError):
@@ -296,6 +312,9 @@ def load_library(dtype="f32"):
     lib.mc33hip_section_contours.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V, P(C.c_double * 4), V, C.c_ulonglong, P(C.c_ulonglong)]
     lib.mc33hip_section_ladder.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, P(C.c_double * 3), P(C.c_double), C.c_uint, P(C.c_ulonglong), P(C.c_double),
                                            P(C.c_double), P(C.c_ulonglong)]
+    if hasattr(lib, "mc33hip_curvature_vertices"):
+        lib.mc33hip_curvature_vertices.argtypes = [V, P(Curvature)]
+        lib.mc33hip_color_values.argtypes = [V, V, C.c_ulonglong, P(C.c_int), C.c_uint, C.c_double, C.c_double, C.c_int, V]
     if hasattr(lib, "mc33hip_grid_stable"):  # (MC33_LIB_DIR may name an older build, for a comparison side by side: every grid is volatile there)
         lib.mc33hip_grid_stable.argtypes = [V, C.c_int]
         lib.mc33hip_grid_changed.argtypes = [V]
@@ -382,6 +401,22 @@ class GridSpectrum:
     def __repr__(self):
         return "GridSpectrum(n=%d, points=%d, cells=%d, nan_samples=%d, range=[%r, %r])" % (
             len(self.isovalues), self.points, self.cells, self.nan_samples, self.sample_min, self.sample_max)
+
+
+class VertexCurvature:
+    """What DeviceGrid.curvature returns: the chosen float32 device tensors mean, gauss, k1, k2 [n] (None where not asked for) and
+    the summary - lo / hi: {name: extreme of the finite values of that output} (+inf / -inf when it has none, whether or not its
+    tensor was asked for); finite: the vertices whose four values are all finite; undefined: the others."""
+
+    def __init__(self, a, tensors):
+        self.mean, self.gauss, self.k1, self.k2 = (tensors.get(k) for k in CURVATURES)
+        self.lo = {k: a.lo[q] for q, k in enumerate(CURVATURES)}
+        self.hi = {k: a.hi[q] for q, k in enumerate(CURVATURES)}
+        self.finite, self.undefined = int(a.finite), int(a.undefined)
+
+    def __repr__(self):
+        return "VertexCurvature(finite=%d, undefined=%d, mean in [%g, %g], gauss in [%g, %g])" % (
+            self.finite, self.undefined, self.lo["mean"], self.hi["mean"], self.lo["gauss"], self.hi["gauss"])
 
 
 class SurfaceMeasures:
@@ -661,6 +696,37 @@ class DeviceGrid:
         out = torch.empty((V.shape[0],), dtype=torch.int32, device=self.device)
         _check(self.lib, self.lib.mc33hip_color_vertices(self.ctx, C.c_void_p(V.data_ptr()), V.shape[0], pal, len(palette), C.c_double(lo),
                                                          C.c_double(hi), int(nan_color), C.c_void_p(out.data_ptr())))
+        _check(self.lib, self.lib.mc33hip_synchronize(self.ctx))
+        return out
+
+    # -- curvature of the level set at the vertices, from the resident grid (mc33_hip.h: mc33hip_curvature_vertices) -------------------
+    def curvature(self, V, sign=1, which=CURVATURES):
+        """Mean, Gaussian and principal curvatures of the grid's level set through the vertices V [n, 3] (device, as extract()
+        returns them): a VertexCurvature with a float32 tensor [n] for every name in `which` and the summary of all four.  sign
+        +1: a blob of high samples is convex and has mean > 0; -1 the opposite.  Raises MC33Error(EINVAL) for a z-slab or
+        inclined context, an axis with fewer than 2 cells, a sign other than +-1."""
+        import torch
+        self._vertex_rows(V)
+        unknown = [k for k in which if k not in CURVATURES]
+        if unknown:
+            raise ValueError("which: names among %r, not %r" % (CURVATURES, unknown))
+        tensors = {k: torch.empty((V.shape[0],), dtype=torch.float32, device=self.device) for k in which}
+        a = Curvature()
+        a.dV, a.nV, a.sign = V.data_ptr(), V.shape[0], int(sign)
+        for k, member in zip(CURVATURES, ("oMean", "oGauss", "oK1", "oK2")):
+            setattr(a, member, tensors[k].data_ptr() if k in tensors else None)
+        _check(self.lib, self.lib.mc33hip_curvature_vertices(self.ctx, C.byref(a)))
+        return VertexCurvature(a, tensors)
+
+    def color_values(self, P, palette, lo, hi, nan_color=0xff5c5c5c - (1 << 32)):
+        """The colour step of color_vertices over any float32 device tensor P [n] - what sample_property or curvature returned:
+        an int32 tensor [n].  Needs no property grid."""
+        import torch
+        assert P.is_cuda and P.dim() == 1 and P.dtype == torch.float32 and P.is_contiguous()
+        pal = (C.c_int * len(palette))(*[((int(x) + (1 << 31)) % (1 << 32)) - (1 << 31) for x in palette])
+        out = torch.empty((P.shape[0],), dtype=torch.int32, device=self.device)
+        _check(self.lib, self.lib.mc33hip_color_values(self.ctx, C.c_void_p(P.data_ptr()), P.shape[0], pal, len(palette), C.c_double(lo),
+                                                       C.c_double(hi), int(nan_color), C.c_void_p(out.data_ptr())))
         _check(self.lib, self.lib.mc33hip_synchronize(self.ctx))
         return out
 

@@ -86,6 +86,9 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_grid_stable  /* (... whose samples nobody but this library writes) */
 /* ... and the contour spectrum (MC33_grid_spectrum): without it that function returns -1 */
 #pragma weak mc33hip_grid_spectrum
+/* ... and the curvature pass (MC33_set_color_source, MC33_isosurface_curvature): without it both refuse a curvature */
+#pragma weak mc33hip_curvature_vertices
+#pragma weak mc33hip_color_values
 _Static_assert(sizeof(mc33_component) == sizeof(mc33hip_component) && offsetof(mc33_component, area) == offsetof(mc33hip_component, area),
                "mc33_component and mc33hip_component are one layout");
 
@@ -138,6 +141,9 @@ typedef struct mc33_private_s {
 	size_t own_pitch, own_slice; /* ... its layout, in samples */
 	void *dP, *dL;       /* MC33_measure_*: property values / component labels of the vertices in slab[0].set[0] (device) */
 	unsigned long long capP, capL;
+	int color_source;    /* MC33_set_color_source: MC33_COLOR_PROPERTY, or the curvature the map paints (one slab then) */
+	void *dG;            /* MC33_isosurface_curvature: the Gaussian curvature beside the mean in dP (device) */
+	unsigned long long capG;
 } mc33_private;
 #define MC33_MAGIC 0x4D43333348495031ull /* "MC33HIP1" */
 
@@ -355,7 +361,7 @@ void free_MC33(MC33 *M) {
 			continue;
 		for (int k = 0; k != 2; k++)
 			staging_release(s->ctx, &s->set[k]);
-		if (q == 0) { dev_release(s->ctx, &p->dP, &p->capP); dev_release(s->ctx, &p->dL, &p->capL); }
+		if (q == 0) { dev_release(s->ctx, &p->dP, &p->capP); dev_release(s->ctx, &p->dL, &p->capL); dev_release(s->ctx, &p->dG, &p->capG); }
 		if (q == 0 && p->own_grid) { /* the grid of MC33_create_resampled: through the context while it lives, when nothing reads it any more */
 			(void)mc33hip_synchronize(s->ctx);
 			(void)mc33hip_device_free(s->ctx, p->own_grid);
@@ -428,7 +434,7 @@ static void *slab_property(void *arg) {
 	return 0;
 }
 
-static int coloured(const mc33_private *p) { return p->prop != 0 && p->has_map; }
+static int coloured(const mc33_private *p) { return (p->prop != 0 || p->color_source != MC33_COLOR_PROPERTY) && p->has_map; }
 
 int MC33_set_property_grid(MC33 *M, _GRD *P) {
 	mc33_private *p = priv(M);
@@ -470,10 +476,31 @@ int MC33_set_color_map(MC33 *M, const int *palette, unsigned n, double lo, doubl
 	return 0;
 }
 
-/* the colour kernel over the nV vertices in g->dV, behind whatever wrote them on the context's stream (enqueues only) */
+int MC33_set_color_source(MC33 *M, int source) {
+	mc33_private *p = priv(M);
+	if (!p || source < MC33_COLOR_PROPERTY || source > MC33_COLOR_K2)
+		return -1;
+	if (source != MC33_COLOR_PROPERTY &&
+	    (!mc33hip_curvature_vertices || !mc33hip_color_values || p->inclined || p->nslab != 1 || M->nx < 2u || M->ny < 2u || M->nz < 2u))
+		return -1;
+	p->color_source = source;
+	return 0;
+}
+
+/* the colour kernel over the nV vertices in g->dV, behind whatever wrote them on the context's stream (enqueues only; with a
+ * curvature for its source the curvature pass has been waited for, the colour kernel is enqueued) */
 static int enqueue_colors(mc33_slab *s, struct staging *g, unsigned long long nV) {
-	const mc33_private *p = s->owner;
+	mc33_private *p = s->owner;
 	if (dev_room(s->ctx, &g->dC, &g->capC, nV, sizeof(int))) return MC33HIP_ENOMEM;
+	if (p->color_source != MC33_COLOR_PROPERTY) { /* the chosen curvature into p->dP (one slab: MC33_set_color_source), the map over it */
+		mc33hip_curvature a;
+		if (dev_room(s->ctx, &p->dP, &p->capP, nV, sizeof(float))) return MC33HIP_ENOMEM;
+		memset(&a, 0, sizeof a);
+		a.dV = g->dV; a.nV = nV; a.sign = MC33_NORMAL_NEG ? -1 : 1;
+		*(p->color_source == MC33_COLOR_MEAN ? &a.oMean : p->color_source == MC33_COLOR_GAUSS ? &a.oGauss : p->color_source == MC33_COLOR_K1 ? &a.oK1 : &a.oK2) = (float *)p->dP;
+		const int rc = mc33hip_curvature_vertices(s->ctx, &a);
+		return rc != MC33HIP_OK ? rc : mc33hip_color_values(s->ctx, (const float *)p->dP, nV, p->map, p->map_n, p->map_lo, p->map_hi, p->nan_color, (int *)g->dC);
+	}
 	return mc33hip_color_vertices(s->ctx, g->dV, nV, p->map, p->map_n, p->map_lo, p->map_hi, p->nan_color, (int *)g->dC);
 }
 
@@ -1106,6 +1133,39 @@ static int measure_one(mc33_private *p, MC33_real iso, mc33_measure *out) {
 	}
 	out->property_integral = m.property_integral;
 	out->has_property = m.has_property;
+	return 0;
+}
+
+/* --- extension: curvature of an isosurface, taken on the device ------------------------------------------------------------------
+ * The surface goes into staging set 0 like measure_one's; mean and Gaussian curvature at its vertices into p->dP and p->dG, and
+ * each through mc33hip_measure_surface as its dP. */
+int MC33_isosurface_curvature(MC33 *M, MC33_real iso, mc33_curvature *out) {
+	mc33_private *p = one_slab(M, mc33hip_curvature_vertices && mc33hip_measure_surface);
+	if (!p || !out || p->inclined || M->nx < 2u || M->ny < 2u || M->nz < 2u)
+		return -1;
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0];
+	mc33hip_counts cnt;
+	mc33hip_curvature a;
+	mc33hip_measures m[2];
+	memset(out, 0, sizeof *out);
+	p->pub.iso = iso;
+	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK)
+		return -1;
+	if (dev_room(s->ctx, &p->dP, &p->capP, cnt.nV, sizeof(float)) || dev_room(s->ctx, &p->dG, &p->capG, cnt.nV, sizeof(float)))
+		return -1;
+	memset(&a, 0, sizeof a);
+	a.dV = g->dV; a.nV = cnt.nV; a.sign = MC33_NORMAL_NEG ? -1 : 1;
+	a.oMean = (float *)p->dP; a.oGauss = (float *)p->dG;
+	if (mc33hip_curvature_vertices(s->ctx, &a) != MC33HIP_OK ||
+	    mc33hip_measure_surface(s->ctx, g->dV, cnt.nV, g->dT, cnt.nT, (const float *)p->dP, &m[0]) != MC33HIP_OK ||
+	    mc33hip_measure_surface(s->ctx, g->dV, cnt.nV, g->dT, cnt.nT, (const float *)p->dG, &m[1]) != MC33HIP_OK)
+		return -1;
+	out->nV = (unsigned)cnt.nV; out->nT = (unsigned)cnt.nT;
+	for (int q = 0; q != 4; q++) { out->lo[q] = a.lo[q]; out->hi[q] = a.hi[q]; }
+	out->finite = a.finite; out->undefined = a.undefined;
+	out->total_mean = a.undefined ? (double)NAN : m[0].property_integral;
+	out->total_gauss = a.undefined ? (double)NAN : m[1].property_integral;
 	return 0;
 }
 

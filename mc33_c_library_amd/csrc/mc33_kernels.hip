@@ -47,6 +47,10 @@
 //                   the rows keep their order (mc33_filter.hip.h).
 //                   k_sm_* - Taubin smoothing of a finished V over the adjacency of T, a CSR list made on the device, and vertex
 //                   normals recomputed from the triangles; k_sm_pass is its hot path (mc33_smooth.hip.h).
+//                   k_curvature<R> - mean, Gaussian and principal curvatures of the level set at the vertices of a finished V, from
+//                   the gradient and Hessian of the resident grid: one lane per vertex walks the nodes its vertex has, 19 samples
+//                   each; k_curv_init clears its summary; k_color_values - a palette over any float array (mc33_curvature.hip.h,
+//                   DESIGN.md 22).
 //                   k_simp_* - vertex clustering of a finished V, T on a lattice: a table of clusters filled by 64-bit compare-and-swap,
 //                   duplicate triangles through a table of triangle indices, two exclusive scans, two writing passes;
 //                   k_simp_cluster is its hot path (mc33_simplify.hip.h).
@@ -128,4 +132,5 @@ typedef float sample_t;
 #include "mc33_clip.hip.h"
 #include "mc33_section.hip.h"
 #include "mc33_resample.hip.h"
+#include "mc33_curvature.hip.h"
 #include "mc33_spectrum.hip.h"

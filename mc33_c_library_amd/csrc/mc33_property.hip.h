@@ -189,13 +189,9 @@ static int prop_check(mc33hip_ctx *c) {
 	return MC33HIP_ERUNTIME;
 }
 
-static int prop_enqueue(mc33hip_ctx *c, const void *dV, unsigned long long nV, const int *palette, unsigned n, double lo, double hi, int nan_color, void *out) {
-	if (!c || (nV && (!dV || !out))) return MC33HIP_EINVAL;
-	if (!c->d_prop) { set_err("no property grid attached"); return MC33HIP_EINVAL; }
-	if (c->inclined) { set_err("property sampling is defined for orthogonal grids only"); return MC33HIP_EINVAL; }
-	if (palette && (n < 2u || n > 256u || !(lo < hi))) { set_err("colour map needs 2..256 colours and lo < hi"); return MC33HIP_EINVAL; }
-	int rc = use_device(c);
-	if (rc) return rc;
+// the violation counter with its pinned twin and the palette's 256 words in device memory (mc33hip_color_values stages its palette
+// there too): made by the first call that needs them, freed with the context
+static int prop_scratch(mc33hip_ctx *c) {
 	if (!c->d_prop_viol) {
 		HIP_TRY(hipMalloc(&c->d_prop_viol, sizeof(unsigned long long)));
 		HIP_TRY(hipMemset(c->d_prop_viol, 0, sizeof(unsigned long long)));
@@ -203,6 +199,16 @@ static int prop_enqueue(mc33hip_ctx *c, const void *dV, unsigned long long nV, c
 		*c->h_prop_viol = 0ull;
 		HIP_TRY(hipMalloc(&c->d_prop_pal, 256 * sizeof(uint32_t)));
 	}
+	return 0;
+}
+
+static int prop_enqueue(mc33hip_ctx *c, const void *dV, unsigned long long nV, const int *palette, unsigned n, double lo, double hi, int nan_color, void *out) {
+	if (!c || (nV && (!dV || !out))) return MC33HIP_EINVAL;
+	if (!c->d_prop) { set_err("no property grid attached"); return MC33HIP_EINVAL; }
+	if (c->inclined) { set_err("property sampling is defined for orthogonal grids only"); return MC33HIP_EINVAL; }
+	if (palette && (n < 2u || n > 256u || !(lo < hi))) { set_err("colour map needs 2..256 colours and lo < hi"); return MC33HIP_EINVAL; }
+	int rc = use_device(c);
+	if (rc || (rc = prop_scratch(c))) return rc;
 	if (!nV) return MC33HIP_OK;
 	PropArgs a;
 	a.p = c->d_prop; a.slice = c->prop_slice; a.pitch = (uint32_t)c->prop_pitch;
