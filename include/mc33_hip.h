@@ -122,9 +122,21 @@ int mc33hip_sweep_skipped(mc33hip_ctx *c, unsigned long long out[3]);
  * cap_tiles tiles; NULL: info only); info = {tiles, blocks the device holds at once, 0: the plan of a sweep without a range
  * table / 1: with one}.  mc33hip_sweep_live: the live list of the last sweep made with a table, one word per block that had a
  * tile to stream, in plan order: block << 4 | mask of its waves with nothing to stream; info = {entries, blocks of that sweep's
- * plan}.  MC33HIP_EINVAL when there is no plan / was no such sweep. */
+ * plan}.  mc33hip_sweep_packed: the list that sweep's kernel went by, one 16-byte entry per block that had work (room for
+ * cap_entries entries; NULL: info only): four tile indices of the plan, wave k of the block streamed tile k of its entry -
+ * 0xFFFFFFFF: none (only in the last entry that is not a whole block of the plan); bit 31 of the first word: the entry is a whole group of the plan, all four tiles
+ * live.  A block of the plan with four live tiles stays one entry, the live tiles of the other blocks are packed four at a time in
+ * plan order, and the two kinds are merged by the plan position of their first tile.  info = {entries, live tiles, tiles of the
+ * plan}; entries = ceil(live tiles / 4).  MC33HIP_EINVAL when there is no plan / was no such sweep.
+ * The plan of a single-isovalue sweep with a table is sized by the live tiles the sweeps find, so that the packed blocks are a set
+ * share of one round of the device; MC33_HIP_TABLE_TILES=<n> in the environment when a context is created asks for n tiles whatever they find, and an
+ * explicit MC33_HIP_RZ or MC33_HIP_RZ_TABLE (a depth in planes) switches the sizing off.  Precedence: MC33_HIP_RZ alone makes the
+ * plans with and without a table one plan of that depth, and nothing else is looked at; otherwise MC33_HIP_TABLE_TILES, a switch
+ * for tests and curves, comes before MC33_HIP_RZ_TABLE and holds for grids of less than one round too; then MC33_HIP_RZ_TABLE; then
+ * the sizing.  MC33_HIP_LIST_LDS=0 (tests): k_live_compact keeps the places of its quads in memory, as for plans above 4 096 blocks. */
 int mc33hip_sweep_plan(mc33hip_ctx *c, unsigned int *tiles_out, size_t cap_tiles, unsigned long long info[3]);
 int mc33hip_sweep_live(mc33hip_ctx *c, unsigned int *live_out, size_t cap_entries, unsigned long long info[2]);
+int mc33hip_sweep_packed(mc33hip_ctx *c, unsigned int *out, size_t cap_entries, unsigned long long info[3]);
 
 /* Inclined (non-orthogonal) grid: vertices and normals go through the cell matrices like MC33_spnC does
  * (reference marching_cubes_33.c:587-621).  grd_A / grd_Ai = _GRD._A / _GRD.A_ (3x3 row major, before the

@@ -70,7 +70,8 @@ struct IsoLane {
 	double iso;
 	mc33hip_range range;
 	uint32_t pack;            // samples per lane and load of the sweep that filled it (lane_of_column)
-	int plan;                 // the plan (mc33hip_ctx::plan) that sweep went by: its edge records are indexed by that plan's tiles
+	int plan;                 // the plan (mc33hip_ctx::plan) that sweep went by: its edge records are indexed by that plan's tiles ...
+	uint32_t plan_target;     // ... and the tile count plan 1 had been asked for (SweepPlan::target): number and target make the plan again
 	int many_pass, many_ni;   // which pass of mc33hip_sweep_many filled it (its events), and how many isovalues that pass classified
 };
 
@@ -81,6 +82,7 @@ struct SweepPlan {
 	TileBoundary *d_bounds;   // (made to measure for every plan: nbounds is its capacity)
 	uint64_t tiles_cap, ntiles, nbounds;
 	uint32_t zs, ze, depth;
+	uint32_t target;          // plan 1: the tile count it was asked for in place of a depth (table_retarget), 0: by its depth
 };
 
 // Everything a tail (k_slots ... k_scan_apply) writes and the emit passes read, for ONE isovalue.  Lane k of the sweep buffers
@@ -130,7 +132,9 @@ struct Switches {
 	uint32_t debug, cells_dev;  // (looked at by -DMC33_DEV builds only)
 	uint32_t rz_table;          // MC33_HIP_RZ_TABLE: depth of the plan a sweep with a range table goes by (plan_sweep)
 	int live;                   // MC33_HIP_LIVE: 1 / 0 = a sweep with a table always / never goes by a live list; -1 (not set): sweep_live decides
-	uint32_t pad_[4];           // (the words of five removed developer switches: with the context 24 bytes smaller, the C3 emit stage measured 4 us slower)
+	uint32_t table_tiles;       // MC33_HIP_TABLE_TILES: the tile count plan 1 is asked for, whatever the sweeps find (the tests, the curve of profiles/r10_sweep_pack.txt)
+	uint32_t list_lds;          // MC33_HIP_LIST_LDS: plans of up to this many blocks keep the places of their quads in LDS (k_live_compact; 4096, the most; the tests set 0)
+	uint32_t pad_[2];           // (the words of five removed developer switches: with the context 24 bytes smaller, the C3 emit stage measured 4 us slower)
 };
 
 struct mc33hip_ctx {
@@ -158,16 +162,19 @@ struct mc33hip_ctx {
 	IsoLane *cur_lane;        // the lane the last count used (its epoch is what the emit pass needs)
 	bool lane_presweeped;     // ... and it had been filled by mc33hip_sweep_many
 	bool lane_pretailed;      // ... tail included
-	SweepPlan plan[2];        // the plans of k_sweep for the current range (plan_sweep): [0] without a range table, [1] with one
+	SweepPlan plan[3];        // the plans of k_sweep for the current range (plan_sweep): [0] without a range table, [1] with one, [2] with one and sized (table_retarget)
 	int cur_plan;             // ... and the one in force: what the sweep to be launched, or the lane whose tail is being made, goes by
 	uint32_t resident_blocks; // k_sweep blocks the device holds at once
 	uint8_t *d_verdict;       // with a table: k_tile_verdicts' byte per block of the plan, and the live list k_live_compact makes of
-	uint32_t *d_live;         // them (SweepArgs::live: the count, then the entries) - of the last sweep with a table
-	uint64_t verdict_cap, live_cap;
+	uint32_t *d_live;         // them (the count, then a word per block with a live tile: mc33hip_sweep_live) - of the last sweep with a table
+	uint32_t *d_packed;       // ... and the packed list k_sweep_live goes by (SweepArgs::live; k_live_compact for the layout)
+	uint64_t verdict_cap, live_cap, packed_cap;
 	uint64_t live_blocks;     // blocks of the plan that sweep went by (0: no such sweep yet)
 	unsigned long long *h_live;  // pinned: what k_live_compact published last (live tiles << 32 | tiles << 1 | plan; 0: nothing yet)
 	uint32_t coarse_sweeps;   // ... sweeps made that way since (sweep_live: one in 16 goes by a list)
 	bool table_coarse;        // sweeps with a table go by plan 0 for now: the last ones left too little out for the finer plan to pay (table_plan)
+	uint32_t table_target;    // the tile count plan 1 is asked for (table_retarget), 0: its default depth
+	uint32_t table_pending;   // ... and the one the last call would have asked for instead: replaced when the next call agrees
 	// the range table (RangeEntry, sweep_ranges): made for a grid whose samples this library knows to be unchanged - its own copy,
 	// or an adopted buffer the caller has declared stable - by the second sweep since they last changed
 	RangeEntry *d_ranges;
@@ -232,7 +239,7 @@ static int env_flag(const char *name) {  // -1: not set
 	return s && *s ? (atoi(s) != 0 ? 1 : 0) : -1;
 }
 static void read_switches(Switches &w) {
-	w.rz = env_u32("MC33_HIP_RZ", 0); w.sweep_blocks_per_cu = env_u32("MC33_HIP_SWEEP_BLOCKS_PER_CU", 0); w.min_depth = env_u32("MC33_HIP_MIN_DEPTH", 0); w.rz_table = env_u32("MC33_HIP_RZ_TABLE", 0); w.live = env_flag("MC33_HIP_LIVE");
+	w.rz = env_u32("MC33_HIP_RZ", 0); w.sweep_blocks_per_cu = env_u32("MC33_HIP_SWEEP_BLOCKS_PER_CU", 0); w.min_depth = env_u32("MC33_HIP_MIN_DEPTH", 0); w.rz_table = env_u32("MC33_HIP_RZ_TABLE", 0); w.live = env_flag("MC33_HIP_LIVE"); w.table_tiles = env_u32("MC33_HIP_TABLE_TILES", 0); w.list_lds = std::min(4096u, env_u32("MC33_HIP_LIST_LDS", 4096u));
 	w.cells_blocks = env_u32("MC33_HIP_CELLS_BLOCKS", 0); w.slow_blocks = env_u32("MC33_HIP_SLOW_BLOCKS", 0); w.emit_blocks = env_u32("MC33_HIP_EMIT_BLOCKS", 0);
 	w.emit_v_blocks_per_cu = env_u32("MC33_HIP_EMIT_V_BLOCKS_PER_CU", 0); w.slow_slots_max = env_u32("MC33_HIP_SLOW_SLOTS_MAX", 0);
 	w.no_pack = env_u32("MC33_HIP_NO_PACK", 0) != 0; w.no_stage = env_u32("MC33_HIP_NO_STAGE", 0) != 0; w.verbose = getenv("MC33_HIP_VERBOSE") != nullptr;
@@ -245,7 +252,9 @@ static void read_switches(Switches &w) {
 static void forget_ranges(mc33hip_ctx *c) {  // the samples changed, or may have: no table until the second sweep from now
 	c->ranges_valid = false;
 	c->sweeps_seen = 0;
-	c->table_coarse = false;  // (new samples: the finer plan until a sweep says otherwise)
+	c->table_coarse = false;  // (new samples: the finer plan until a sweep says otherwise ...
+	c->table_target = 0u;     // ... at its default depth until one has published a count)
+	c->table_pending = 0u;
 	if (c->h_live) __atomic_store_n(c->h_live, 0ull, __ATOMIC_RELAXED);
 }
 
@@ -413,7 +422,7 @@ extern "C" void mc33hip_destroy(mc33hip_ctx *c) {
 		dev_release(&L.slice_hdr); dev_release(&L.slice_bits); dev_release(&L.slice_compact); dev_release(&L.plane_fmt); dev_release(&L.slot_part); dev_release(&L.edge_bits); dev_release(&L.edge_hdr);
 	}
 	for (SweepPlan &pl : c->plan) { dev_release(&pl.d_tiles); dev_release(&pl.d_bounds); }
-	dev_release(&c->d_verdict); dev_release(&c->d_live);
+	dev_release(&c->d_verdict); dev_release(&c->d_live); dev_release(&c->d_packed);
 	if (c->h_live) (void)hipHostFree(c->h_live);
 	c->h_live = nullptr;
 	dev_release(&c->d_ranges); dev_release(&c->d_skipped);
@@ -615,7 +624,7 @@ extern "C" int mc33hip_adopt_device(mc33hip_ctx *c, const void *dptr, size_t pit
 	c->grid_stable = false;  // (volatile until the caller says otherwise: mc33hip_grid_stable)
 	c->pitch = pitch;
 	c->slice = slice;
-	c->plan[0].ze = c->plan[1].ze = 0u;  // (the plan counts its work in batches of the form - packed or not - this buffer's alignment allows)
+	c->plan[0].ze = c->plan[1].ze = c->plan[2].ze = 0u;  // (the plan counts its work in batches of the form - packed or not - this buffer's alignment allows)
 	c->counted = false;
 	forget_sweeps(c);
 	return MC33HIP_OK;

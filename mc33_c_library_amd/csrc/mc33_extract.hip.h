@@ -107,6 +107,22 @@ static int grow_entries(TailSet &w, uint64_t need) {
 // once whenever the grid is large enough.  Measured on MI355X at 1024^3: with 1088 equal tiles on 256 CUs
 // the 64 CUs that got a fifth block finished 12 % after the others.
 static bool sweep_packed(const mc33hip_ctx *c);
+// work of one WAVE of y tile yt per slice: its sample rows
+// (in whole BATCHES of sample rows - 4 rows of float samples, 8 / 16 of packed ushort / uchar ones: a wave's time is the
+// number of batches it waits for, and a y tile of 2 rows costs a batch per plane like one of 4.  Counted in rows, the
+// 2-row last y tile of a 128^3 grid got pieces twice as deep as its time allows and the sweep took 0.060 ms where the
+// 256^3 one takes 0.035: VERDICT r4 weak 12)
+static double column_work(const mc33hip_ctx *c, uint32_t yt) {
+	const uint32_t rb = sweep_packed(c) ? 4u * (uint32_t)SWEEP_PACK : 4u;
+	return (double)((std::min(64u, c->P.ny + 1 - yt * 63u) + rb - 1u) / rb * rb);
+}
+// the tiles the slices [zs, ze) would make at ONE plane per tile: the work of all waves x slices / 64 rows (what plan_sweep divides by a depth)
+static double sweep_unit(const mc33hip_ctx *c, uint32_t zs, uint32_t ze) {
+	const uint32_t nYT = (c->P.ny + 62) / 63;
+	double W = 0;
+	for (uint32_t yt = 0; yt < nYT; yt++) W += column_work(c, yt) * c->P.nseg;
+	return W * (ze - zs) / 64.0;
+}
 //
 // Two plans are kept, and `which` says which one is put in force (c->cur_plan): 0, for a sweep without a range table, is about
 // SWEEP_DEPTH slices deep - one tile per wave slot of the device, one round; 1, for a sweep with one, about SWEEP_DEPTH_TABLE.  With a table
@@ -116,14 +132,22 @@ static bool sweep_packed(const mc33hip_ctx *c);
 // MC33_HIP_RZ_TABLE is the depth of plan 1 alone (the tests make the two differ on small grids with it, the profiles try depths).
 // A lane swept ahead keeps the number of its plan (IsoLane::plan), and its tail asks for that plan again: the plan is a function
 // of the range, the depth and the device, so a plan made again for a range is the plan the lane's edge records are indexed by.
+// target (plan 1 only; 0: none): the number of tiles wanted, in place of a depth - what table_retarget makes of the live tiles the
+// sweeps find, so that the packed live blocks are a set share of ONE round of the device.  The chunks are shared out as for a depth, only the
+// sum is no whole number of rounds: dead tiles cost nothing.  A sized plan has a slot of its own, number 2 (c->plan[2]; `which` 1
+// with a target, or 2), so that a caller who mixes single-isovalue calls (sized) with passes over several isovalues (the default
+// depth, slot 1) has both resident and makes neither again.  A lane keeps the slot and the target (IsoLane::plan, plan_target).
 constexpr uint32_t SWEEP_DEPTH = 16u, SWEEP_DEPTH_TABLE = 5u;  // (measured, 1024^3 float: profiles/r09_sweep_refill.txt A, B)
-static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, int which) {
+static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, int which, uint32_t target = 0u) {
 	const Params &P = c->P;
 	if (c->sw.rz && !c->sw.rz_table) which = 0;
+	if (which == 2) which = 1;  // (a lane's slot: the plan with a table, sized - its target comes with it)
+	if (!which) target = 0u;
 	const uint32_t depth = which ? (c->sw.rz_table ? c->sw.rz_table : SWEEP_DEPTH_TABLE) : (c->sw.rz ? c->sw.rz : SWEEP_DEPTH);
-	SweepPlan &pl = c->plan[which];
-	c->cur_plan = which;
-	if (pl.d_tiles && pl.zs == zs && pl.ze == ze && pl.depth == depth) return 0;
+	const int slot = (which && target) ? 2 : which;
+	SweepPlan &pl = c->plan[slot];
+	c->cur_plan = slot;
+	if (pl.d_tiles && pl.zs == zs && pl.ze == ze && pl.depth == depth && pl.target == target) return 0;
 	if (!c->resident_blocks) {
 		int per_cu = 0, cus = 0;
 		HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sweep<1, 1>, 256, 0));
@@ -144,18 +168,14 @@ static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, int which) {
 		for (uint32_t xg = 0; xg < nXG; xg++) {
 			const uint64_t i = (uint64_t)yt * nXG + xg;
 			waves[i] = std::min(4u, P.nseg - xg * 4);
-			// (in whole BATCHES of sample rows - 4 rows of float samples, 8 / 16 of packed ushort / uchar ones: a wave's time is the
-			// number of batches it waits for, and a y tile of 2 rows costs a batch per plane like one of 4.  Counted in rows, the
-			// 2-row last y tile of a 128^3 grid got pieces twice as deep as its time allows and the sweep took 0.060 ms where the
-			// 256^3 one takes 0.035: VERDICT r4 weak 12)
-			const uint32_t rb = sweep_packed(c) ? 4u * (uint32_t)SWEEP_PACK : 4u;
-			w[i] = (double)((std::min(64u, P.ny + 1 - yt * 63u) + rb - 1u) / rb * rb);
+			w[i] = column_work(c, yt);
 			W += w[i] * waves[i];
 		}
 	// wave tiles wanted: W * nzc / (64 * depth), rounded to whole rounds of the resident set
 	const double pref = W * nzc / (64.0 * depth);
 	uint64_t B = (uint64_t)c->resident_blocks * 4;
-	if (pref >= (double)B) B *= (uint64_t)(pref / (double)B + 0.5);
+	if (target) B = target;
+	else if (pref >= (double)B) B *= (uint64_t)(pref / (double)B + 0.5);
 	else B = std::max<uint64_t>(1, std::min<uint64_t>(B, (uint64_t)(W * nzc / (64.0 * std::max(1u, c->sw.min_depth)))));  // small grid: fill the GPU, tiles down to one plane deep (k_boundary then does the slices)
 	std::vector<uint32_t> chunks(ncol);  // z pieces of the group (each is one tile per wave of the group)
 	std::vector<std::pair<double, uint64_t>> frac(ncol);
@@ -209,10 +229,10 @@ static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, int which) {
 		if (int rc = dev_room("tile boundaries", &pl.d_bounds, &pl.nbounds, bounds.size())) return rc;
 		HIP_TRY(hipMemcpy(pl.d_bounds, bounds.data(), bounds.size() * sizeof(TileBoundary), hipMemcpyHostToDevice));
 	}
-	pl.zs = zs; pl.ze = ze; pl.depth = depth;
+	pl.zs = zs; pl.ze = ze; pl.depth = depth; pl.target = target;
 	if (c->sw.verbose)
-		fprintf(stderr, "[mc33hip] sweep plan %d: %llu wave tiles (%u resident), %llu columns, depth %.1f\n", which, (unsigned long long)pl.ntiles,
-		        c->resident_blocks * 4, (unsigned long long)nYT * P.nseg, (double)nzc * nYT * P.nseg / (double)pl.ntiles);
+		fprintf(stderr, "[mc33hip] sweep plan %d: %llu wave tiles (%u resident, %u asked for), %llu columns, depth %.1f\n", slot, (unsigned long long)pl.ntiles,
+		        c->resident_blocks * 4, target, (unsigned long long)nYT * P.nseg, (double)nzc * nYT * P.nseg / (double)pl.ntiles);
 	return 0;
 }
 
@@ -256,6 +276,7 @@ static int begin_lane(mc33hip_ctx *c, IsoLane &L, const SlotGeom &g, hipStream_t
 		                          {dev_array(&L.edge_bits, ntiles, 2 * 128 * sizeof(uint4)), dev_array(&L.edge_hdr, ntiles, 2 * 2 * sizeof(uint4))}))
 			return rc;
 	L.plan = c->cur_plan;
+	L.plan_target = c->plan[c->cur_plan].target;
 	const uint64_t nchunks = (L.slice_cap + SLOT_CHUNK - 1) / SLOT_CHUNK;  // (capacity: the halves keep their place)
 	if (++L.epoch >= c->epoch_wrap) {  // stamps wrap: start over with clean headers AND clean partial sums - the call before
 		// accumulated into the half an odd epoch selects and cleared only the other one, and epoch 1 is odd again
@@ -353,6 +374,55 @@ static int table_plan(mc33hip_ctx *c) {
 	}
 	return c->table_coarse ? 0 : 1;
 }
+// How many tiles the finer plan is asked for (c->table_target; 0: its default depth).  The packed live blocks of a sweep are
+// ceil(live tiles / 4) (k_live_compact), and the kernel's length is a whole number of rounds of the resident set times the life of
+// a tile: the plan is sized so that they are LESS than one round - TABLE_FILL of the resident blocks (mc33_sweep_pack.h:
+// table_target) - from the count the last sweep by plan 1 published; the live share hardly depends on the size of the plan.  A
+// new plan costs a wait for the stream and two copies (plan_sweep), so the plan stays while the count says its packed blocks lie
+// between TABLE_BAND_LO and TABLE_BAND_HI of a round.  Tiles are never asked shallower than TABLE_MIN_DEPTH planes; a grid whose
+// default plan is shallower than that already - cut down to MC33_HIP_MIN_DEPTH to make one round at all - goes by that depth
+// instead.
+// The constants are read off the measured curve of the flagship, profiles/r10_sweep_pack.txt C, D: every size between 0.63 and
+// 0.73 of a round (7 168 - 8 350 tiles) takes 0.572 - 0.580 ms per step against the parent's 0.60 - 0.61, the sizes between 0.75
+// and 0.81 (8 564 - 9 216) are SLOWER than the parent (a tail of late tiles at a regular spacing in z, not understood), a full
+// round (0.91: 10 400) gains 1 %, 0.95 - 1.0 gain 3 %, and past one round the gain is gone.  So the fill is 0.68 and the band
+// ends at 0.72, a margin short of the sizes that lose while their cause is not known.  Nothing shallower than 3.4 planes was measured.
+// Never fewer tiles than ONE ROUND (4 x resident blocks; table_target): with more than 0.68 of its tiles live a plan would be
+// asked for less, the sweep would go without a list (sweep_live), nothing would publish a count again, and the context would sit
+// on that plan whatever isovalue came next.  For the same reason a sized plan always gets its list.
+// Left alone: an explicit MC33_HIP_RZ / MC33_HIP_RZ_TABLE, plans of less than one round (small grids), sweeps by plan 0, no count
+// yet (new samples: forget_ranges).  MC33_HIP_TABLE_TILES forces a target: it is for tests and curves, comes before
+// MC33_HIP_RZ_TABLE and holds for small plans too; only MC33_HIP_RZ alone, which makes the two plans one, comes before it.
+// Two calls in a row have to ask for about the same size (5 %) before the plan is replaced: a caller that moves between isovalues
+// with very different live shares would otherwise pay for a new plan in every call - 0.31 -> 0.52 ms per count at 1024^3 with the
+// isovalues 0 and 1.5 alternated (profiles/r10_sweep_pack.txt F) - and now stays on the plan it has.
+// Only the single-isovalue calls are sized (enqueue_count).  The passes of mc33hip_sweep_many / mc33hip_prepare_many go by the
+// default depth: their forms over several isovalues hold three blocks per CU, not four, a tile is live when ANY of its isovalues
+// cuts it, and sized by this rule c5 (2048 x 2048 x 1024 ushort, 8 isovalues) was 5 % slower (r10 F).
+constexpr double TABLE_FILL = 0.68, TABLE_BAND_LO = 0.62, TABLE_BAND_HI = 0.72, TABLE_MIN_DEPTH = 3.0;
+static void table_retarget(mc33hip_ctx *c, uint32_t zs, uint32_t ze) {
+	if (c->sw.table_tiles) { c->table_target = c->sw.table_tiles; return; }
+	if (c->sw.rz || c->sw.rz_table || !c->h_live || !c->resident_blocks || ze <= zs) return;
+	const unsigned long long w = __atomic_load_n(c->h_live, __ATOMIC_RELAXED);
+	const uint64_t tiles = (w & 0xFFFFFFFFull) >> 1, live = w >> 32;
+	if (!(w & 1ull) || !tiles || !live) return;
+	const double unit = sweep_unit(c, zs, ze), one_round = 4.0 * c->resident_blocks;
+	double min_depth = TABLE_MIN_DEPTH;
+	if (unit / SWEEP_DEPTH_TABLE < one_round) {  // (plan_sweep: such a grid gets one round, or what its slices make at the smallest depth)
+		min_depth = (double)std::max(1u, c->sw.min_depth);
+		if (unit / min_depth < one_round) return;
+	}
+	// (the word is read as it stands: its count may be of the plan before the one in force)
+	const SweepPlan &pl = c->plan[c->table_target ? 2 : 1];
+	const uint64_t cur = (pl.d_tiles && pl.zs == zs && pl.ze == ze && pl.target == c->table_target) ? pl.ntiles : tiles;
+	if (table_keeps(live * cur / tiles, c->resident_blocks, TABLE_BAND_LO, TABLE_BAND_HI)) { c->table_pending = 0u; return; }
+	const uint32_t t = table_target(live, tiles, c->resident_blocks, unit, min_depth, TABLE_FILL);
+	if (!t || t == c->table_target) { c->table_pending = 0u; return; }
+	if (!c->table_pending || std::fabs((double)t - (double)c->table_pending) > 0.05 * (double)c->table_pending) { c->table_pending = t; return; }  // (a second call has to agree)
+	c->table_pending = 0u;
+	if (c->sw.verbose) fprintf(stderr, "[mc33hip] table plan: %llu of %llu tiles live, %u tiles asked for (were %u)\n", (unsigned long long)live, (unsigned long long)tiles, t, c->table_target);
+	c->table_target = t;
+}
 static void sweep_live(mc33hip_ctx *c, SweepArgs &a) {
 	c->live_blocks = 0;
 	if (!a.ranges) return;
@@ -360,17 +430,18 @@ static void sweep_live(mc33hip_ctx *c, SweepArgs &a) {
 	// While the one-round plan stands in for the finer one (table_plan) every tile has its slot and the preamble form is the faster
 	// one - it is the parent's sweep, where the list's two launches cost 10 us of 940 (r09 F) - but only a list's count can end the
 	// stand-in: one sweep in 16 goes by a list, the first of them at once.
-	bool want = ntiles >= (uint64_t)c->resident_blocks * 4;
+	bool want = ntiles >= (uint64_t)c->resident_blocks * 4 || c->cur_plan == 2;  // (a sized plan always: only a list's count can size it again)
 	if (c->table_coarse) want = (c->coarse_sweeps++ % 16u) == 0u;
 	if (!(c->sw.live > 0 || (c->sw.live < 0 && want))) return;
 	if (!c->h_live && hipHostMalloc(&c->h_live, sizeof *c->h_live, hipHostMallocDefault) == hipSuccess) *c->h_live = 0ull;
 	else if (!c->h_live) (void)hipGetLastError();  // (no pinned word: nothing is published, the finer plan stays)
 	if ((c->verdict_cap < blocks && dev_room("tile verdicts", &c->d_verdict, &c->verdict_cap, blocks) != 0) ||
-	    (c->live_cap < blocks + 1 && dev_room("live list", &c->d_live, &c->live_cap, blocks + 1) != 0)) {
+	    (c->live_cap < blocks + 1 && dev_room("live list", &c->d_live, &c->live_cap, blocks + 1) != 0) ||
+	    (c->packed_cap < 5 * blocks + 4 && dev_room("packed live list", &c->d_packed, &c->packed_cap, 5 * blocks + 4) != 0)) {  // (header, entries, a word per quad: k_live_compact)
 		(void)hipGetLastError();
 		return;
 	}
-	a.live = c->d_live;
+	a.live = c->d_packed;
 }
 
 // SweepLane::iso_gt / iso_eq of an isovalue for packed samples of `top` as their largest value
@@ -402,7 +473,7 @@ static uint32_t launch_sweep_zm(mc33hip_ctx *c, const SweepArgs &a, hipStream_t 
 	const uint64_t blocks = (c->plan[c->cur_plan].ntiles + 3) / 4;
 	if (a.live) {  // the verdicts and the live list, in front of the sweep that goes by them (sweep_live)
 		hipLaunchKernelGGL(k_tile_verdicts<NI>, dim3((uint32_t)((blocks + 3) / 4)), dim3(256), 0, st, a, c->d_verdict, (uint32_t)blocks);
-		hipLaunchKernelGGL(k_live_compact, dim3(1), dim3(1024), 0, st, c->d_verdict, (uint32_t)blocks, c->d_live, c->h_live, (uint32_t)c->cur_plan, a.ntiles);
+		hipLaunchKernelGGL(k_live_compact, dim3(1), dim3(1024), 0, st, c->d_verdict, (uint32_t)blocks, c->d_live, c->d_packed, c->h_live, c->cur_plan ? 1u : 0u, a.ntiles, c->sw.list_lds);
 		c->live_blocks = blocks;
 	}
 	// (packed narrow samples, several isovalues, classified by subtraction - an isovalue of -0.0 among them: the conversions of
@@ -453,7 +524,7 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 	hipStream_t st = c->stream;
 	const uint32_t ze = c->range.z_end;
 	// (the lanes of a call were swept by one pass, so by one plan: the one their edge records are paired by)
-	if (int rc = plan_sweep(c, c->P.zs, ze, c->lanes[idx[0]].plan)) return rc;
+	if (int rc = plan_sweep(c, c->P.zs, ze, c->lanes[idx[0]].plan, c->lanes[idx[0]].plan_target)) return rc;
 	const SweepPlan &pl = c->plan[c->cur_plan];
 	SweepArgs a;
 	sweep_args(c, g, a);
@@ -598,7 +669,7 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 				// (the plan it was swept by is looked at, not put in force: when its place holds another range's plan by now, the tail
 				// makes it again - the same plan, which the lane's edge buffers had room for)
 				const SweepPlan &lp = c->plan[c->lanes[k].plan];
-				if (lp.d_tiles && lp.zs == P.zs && lp.ze == c->range.z_end && c->lanes[k].edge_cap < lp.ntiles) continue;
+				if (lp.d_tiles && lp.zs == P.zs && lp.ze == c->range.z_end && lp.target == c->lanes[k].plan_target && c->lanes[k].edge_cap < lp.ntiles) continue;
 				L = &c->lanes[k];
 				tail_made = L->tail_done;
 			}
@@ -612,7 +683,8 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 	} else {
 		L = &c->lanes[0];
 		const RangeEntry *ranges = sweep_ranges(c, st);
-		if (int rc = plan_sweep(c, P.zs, c->range.z_end, ranges ? table_plan(c) : 0)) return rc;
+		table_retarget(c, P.zs, c->range.z_end);
+		if (int rc = plan_sweep(c, P.zs, c->range.z_end, ranges ? table_plan(c) : 0, c->table_target)) return rc;
 		if (int rc = begin_lane(c, *L, g, st)) return rc;
 		c->lane_presweeped = false;
 		SweepArgs a;
@@ -702,7 +774,8 @@ static int enqueue_sweep_many(mc33hip_ctx *c, const double *isos, int n, bool ta
 		const int ni = (n - k >= 4) ? 4 : (n - k >= 2) ? 2 : 1;
 		// (the table may be built in front of the second pass: every pass goes by the plan of what it has, and its lanes keep it)
 		const RangeEntry *ranges = sweep_ranges(c, st);
-		if (int rc = plan_sweep(c, c->P.zs, c->range.z_end, ranges ? table_plan(c) : 0)) return rc;
+		// (every pass of the call by the same plan with a table: its default depth, or the size MC33_HIP_TABLE_TILES forces - table_retarget)
+		if (int rc = plan_sweep(c, c->P.zs, c->range.z_end, ranges ? table_plan(c) : 0, c->sw.table_tiles)) return rc;
 		SweepArgs a;
 		sweep_args(c, g, a);
 #ifdef MC33_DEV
@@ -1316,12 +1389,25 @@ extern "C" int mc33hip_sweep_plan(mc33hip_ctx *c, unsigned int *tiles_out, size_
 	if (!c || !info) return MC33HIP_EINVAL;
 	const SweepPlan &pl = c->plan[c->cur_plan];
 	if (!pl.d_tiles || !pl.ze) { set_err("no sweep plan yet"); return MC33HIP_EINVAL; }
-	info[0] = pl.ntiles; info[1] = c->resident_blocks; info[2] = (unsigned long long)c->cur_plan;
+	info[0] = pl.ntiles; info[1] = c->resident_blocks; info[2] = c->cur_plan ? 1ull : 0ull;  // (sized or not: the plan with a table)
 	if (!tiles_out) return MC33HIP_OK;
 	if (cap_tiles < pl.ntiles) { set_err("sweep plan: %llu tiles, room for %llu", (unsigned long long)pl.ntiles, (unsigned long long)cap_tiles); return MC33HIP_EINVAL; }
 	if (int rc = use_device(c)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	HIP_TRY(hipMemcpy(tiles_out, pl.d_tiles, pl.ntiles * sizeof(SweepTile), hipMemcpyDeviceToHost));
+	return MC33HIP_OK;
+}
+extern "C" int mc33hip_sweep_packed(mc33hip_ctx *c, unsigned int *out, size_t cap_entries, unsigned long long *info /*[3]*/) {
+	if (!c || !info) return MC33HIP_EINVAL;
+	if (!c->live_blocks || !c->d_packed) { set_err("the last sweep went by no live list"); return MC33HIP_EINVAL; }
+	if (int rc = use_device(c)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	uint32_t h[4] = {0u, 0u, 0u, 0u};
+	HIP_TRY(hipMemcpy(h, c->d_packed, sizeof h, hipMemcpyDeviceToHost));
+	info[0] = h[0]; info[1] = h[1]; info[2] = h[2];
+	if (!out) return MC33HIP_OK;
+	if (h[0] > c->live_blocks || cap_entries < h[0]) { set_err("packed live list: %u entries of %llu blocks, room for %llu", h[0], (unsigned long long)c->live_blocks, (unsigned long long)cap_entries); return MC33HIP_EINVAL; }
+	if (h[0]) HIP_TRY(hipMemcpy(out, c->d_packed + 4, (size_t)h[0] * 16u, hipMemcpyDeviceToHost));
 	return MC33HIP_OK;
 }
 extern "C" int mc33hip_sweep_live(mc33hip_ctx *c, unsigned int *live_out, size_t cap_entries, unsigned long long *info /*[2]*/) {

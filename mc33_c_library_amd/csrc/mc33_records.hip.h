@@ -111,8 +111,8 @@ struct SweepArgs {
 	GridView<sample_t> G;
 	const RangeEntry *ranges;  // the range table, nullptr: none (every tile is streamed)
 	uint32_t *skipped;         // timing level >= 1, single-isovalue sweeps: {-, tiles left out below, above the isovalue}; else nullptr
-	const uint32_t *live;      // with a table: the live list k_tile_verdicts / k_live_compact made in front of the sweep - word 0 the number of
-	                           // blocks with a live tile, then one word per such block, in plan order: block (of four tiles) << 4 | its dead waves
+	const uint32_t *live;      // with a table: the PACKED live list k_tile_verdicts / k_live_compact made in front of the sweep - words 0 .. 3 {entries,
+	                           // live tiles, tiles of the plan, 0}, then one 16-byte entry per block that has work: four tiles of the plan (mc33_sweep_pack.h)
 	Params P;                // (P.iso is not used by the sweep: every lane has its own)
 	const SweepTile *tiles;  // [wave]: the waves of a block are independent, a block is any four consecutive tiles
 	uint32_t ntiles;

@@ -212,37 +212,70 @@ __global__ __launch_bounds__(256) void k_tile_verdicts(const SweepArgs a, uint8_
 			if (NI == 1 && a.skipped) atomicAdd(a.skipped + ((mine & 2u) ? 2 : 1), 1u);
 		}
 	});
-	if (lane == 0) verdict[b] = (uint8_t)dead;
+	if (lane == 0) verdict[b] = (uint8_t)(dead | (grouped ? MC33_VERDICT_GROUPED : 0u));  // (bit 4: what k_sweep_live need not find out again from four tiles)
 }
 // published (pinned host memory, nullptr: none): live TILES << 32 | tiles << 1 | plan, in ONE 8-byte store - what the host's choice
-// between the two plans of a sweep with a table goes by (table_plan), read there whenever it comes by, never waited for.
-__global__ __launch_bounds__(1024) void k_live_compact(const uint8_t *verdict, const uint32_t nblocks, uint32_t *live, unsigned long long *published, const uint32_t plan, const uint32_t ntiles) {
-	__shared__ uint32_t s_wave[16], s_tiles;
-	if (threadIdx.x == 0) s_tiles = 0u;
-	__syncthreads();
+// between the two plans of a sweep with a table, and of the finer plan's size, goes by (table_plan, table_retarget), read there
+// whenever it comes by, never waited for.
+// Two lists are written.  live: word 0 the number of blocks of the plan with a live tile, then a word per such block, in plan
+// order: block << 4 | its dead waves (mc33hip_sweep_live).  packed: what k_sweep_live goes by - words 0 .. 3 {entries, live tiles,
+// tiles of the plan, 0}, the 16-byte entries (mc33_sweep_pack.h: whole blocks stay, the live tiles of mixed blocks go four to an
+// entry), and behind room for nblocks entries a word per quad: where it goes.  Every thread walks a contiguous run of blocks, so
+// an entry's place is two prefix sums (whole blocks, leftover tiles) - and the place of a quad is known to the thread that holds
+// its FIRST tile only, which leaves it in memory for the threads that hold the others (one block: a barrier orders them).
+__global__ __launch_bounds__(1024) void k_live_compact(const uint8_t *verdict, const uint32_t nblocks, uint32_t *live, uint32_t *packed, unsigned long long *published, const uint32_t plan, const uint32_t ntiles, const uint32_t lds_blocks) {
+	constexpr uint32_t LDS_QUADS = 4096u;  // (plans of up to lds_blocks <= 4 096 blocks, 16 384 tiles, keep the places of their quads in LDS: a round trip to memory less in a kernel that is nothing but latency; MC33_HIP_LIST_LDS)
+	__shared__ uint32_t s_wave[3][16], s_quad[LDS_QUADS];
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
 	const uint32_t per = (nblocks + 1023u) / 1024u, b0 = min(tid * per, nblocks), b1 = min(b0 + per, nblocks);  // thread tid: the blocks b0 .. b1 - 1
-	uint32_t n = 0;
-	uint32_t nt = 0;  // live tiles (a wave past the plan's end counts as dead: k_tile_verdicts)
-	for (uint32_t b = b0; b < b1; b++) { const uint32_t v = verdict[b] & 15u; n += v != 15u ? 1u : 0u; nt += 4u - (uint32_t)__popc(v); }
-	if (nt) atomicAdd(&s_tiles, nt);  // (a sum: the order does not matter)
-	uint32_t incl = n;
-#pragma unroll
-	for (int dlt = 1; dlt < 64; dlt <<= 1) {
-		const uint32_t o = __shfl_up(incl, dlt);
-		incl += lane >= (uint32_t)dlt ? o : 0u;
-	}
-	if (lane == 63u) s_wave[wv] = incl;
-	__syncthreads();
-	uint32_t before = incl - n, total = 0;
-	for (uint32_t w = 0; w < 16u; w++) { before += w < wv ? s_wave[w] : 0u; total += s_wave[w]; }
+	uint32_t val[3] = {0u, 0u, 0u};  // blocks with a live tile, whole blocks, leftover tiles (a wave past the plan's end counts as dead: k_tile_verdicts)
 	for (uint32_t b = b0; b < b1; b++) {
 		const uint32_t v = verdict[b] & 15u;
-		if (v != 15u) live[1u + before++] = b << 4 | v;
+		val[0] += v != 15u ? 1u : 0u; val[1] += v == 0u ? 1u : 0u; val[2] += v == 0u ? 0u : 4u - (uint32_t)__popc(v);
+	}
+	uint32_t incl[3];
+#pragma unroll
+	for (int j = 0; j < 3; j++) {
+		incl[j] = val[j];
+#pragma unroll
+		for (int dlt = 1; dlt < 64; dlt <<= 1) {
+			const uint32_t o = __shfl_up(incl[j], dlt);
+			incl[j] += lane >= (uint32_t)dlt ? o : 0u;
+		}
+		if (lane == 63u) s_wave[j][wv] = incl[j];
+	}
+	__syncthreads();
+	uint32_t before[3], total[3];
+#pragma unroll
+	for (int j = 0; j < 3; j++) {
+		before[j] = incl[j] - val[j]; total[j] = 0u;
+		for (uint32_t w = 0; w < 16u; w++) { before[j] += w < wv ? s_wave[j][w] : 0u; total[j] += s_wave[j][w]; }
+	}
+	uint4 *ent = (uint4 *)(packed + 4);
+	uint32_t *ent_w = packed + 4, *quad_at = nblocks <= min(lds_blocks, LDS_QUADS) ? s_quad : packed + 4u + 4u * (uint64_t)nblocks;  // (quads <= blocks)
+	uint32_t at = before[0], W = before[1], L = before[2];
+	for (uint32_t b = b0; b < b1; b++) {
+		const uint32_t vb = verdict[b], v = vb & 15u;
+		if (v != 15u) live[1u + at++] = b << 4 | v;
+		if (v == 0u) { ent[pack_whole_at(W, L)] = uint4{(4u * b) | ((vb & MC33_VERDICT_GROUPED) ? MC33_PACK_GROUP : 0u), 4u * b + 1u, 4u * b + 2u, 4u * b + 3u}; W++; }
+		else
+			for (uint32_t k = 0; k < 4u; k++)
+				if (!((v >> k) & 1u)) { if ((L & 3u) == 0u) quad_at[L >> 2] = pack_quad_at(L >> 2, W); L++; }
+	}
+	__syncthreads();
+	L = before[2];
+	for (uint32_t b = b0; b < b1; b++) {
+		const uint32_t v = verdict[b] & 15u;
+		if (v == 0u) continue;
+		for (uint32_t k = 0; k < 4u; k++)
+			if (!((v >> k) & 1u)) { ent_w[4u * (uint64_t)quad_at[L >> 2] + (L & 3u)] = 4u * b + k; L++; }
 	}
 	if (tid == 0) {
-		live[0] = total;
-		if (published) __atomic_store_n(published, (unsigned long long)s_tiles << 32 | (unsigned long long)ntiles << 1 | (plan & 1u), __ATOMIC_RELAXED);
+		const uint32_t Lt = total[2], tiles_live = 4u * total[1] + Lt;
+		for (uint32_t s = Lt & 3u; s && s < 4u; s++) ent_w[4u * (uint64_t)quad_at[Lt >> 2] + s] = MC33_PACK_NONE;  // (only the last quad may be short)
+		live[0] = total[0];
+		packed[0] = total[1] + (Lt + 3u) / 4u; packed[1] = tiles_live; packed[2] = ntiles; packed[3] = 0u;
+		if (published) __atomic_store_n(published, (unsigned long long)tiles_live << 32 | (unsigned long long)ntiles << 1 | (plan & 1u), __ATOMIC_RELAXED);
 	}
 }
 
@@ -260,27 +293,32 @@ __global__ __launch_bounds__(1024) void k_live_compact(const uint8_t *verdict, c
 // had before there was a table, instruction for instruction: code for the table being THERE cost the packed passes over several
 // isovalues 3 % whether or not it ran (profiles/r08_range_skip.txt D), and a caller without a table pays nothing for it.
 // 1 (k_sweep): every wave works out its verdict itself, in a preamble - plans of less than one round of the device (small grids).
-// 2 (k_sweep_live): the verdicts were made in front of the kernel, and block blockIdx.x streams the tiles of live[1 + blockIdx.x] -
-// plans of one round and more, whose live tiles have to fill the device by themselves.
+// 2 (k_sweep_live): the verdicts were made in front of the kernel, and block blockIdx.x streams the four tiles of entry blockIdx.x
+// of the packed live list - plans of one round and more, whose live tiles have to fill the device by themselves: four to a block,
+// so that no block holds wave slots for dead tiles.
 template <int S, int NI, int ZM, int R>
 __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 	constexpr int LPR = 4 / S;    // loads per sample row
 	constexpr int RB = 16 / LPR;  // sample rows per batch
 	const uint32_t lane = threadIdx.x & 63u;
-	// R: the block's place in the plan comes from the live list.  The launch is one block per planned block; those beyond the list
-	// end here, at their first instructions.  The wave of a dead tile in a block that has live ones does not return here (a second exit
-	// gave the packed forms over several isovalues a quarter more SGPRs parked in VGPR lanes): its tile has no batches - T = 0 below -
-	// so it walks past the loop, flushes an empty log, and ends where every wave ends.  The one batch issued ahead of the loop goes
+	// R: the block's tiles come from the packed live list.  The launch is one block per planned block; those beyond the list
+	// end here, at their first instructions.  A wave without a tile in a block that has some (the last quad of the list; R == 1: a
+	// dead tile) does not return here (a second exit gave the packed forms over several isovalues a quarter more SGPRs parked in VGPR
+	// lanes): it has no batches - T = 0 below - so it walks past the loop, flushes an empty log, and ends where every wave ends.  The one batch issued ahead of the loop goes
 	// through a descriptor of zero bytes: no memory access.
 	uint32_t wtile = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform, in an SGPR
-	bool whole = true;  // (block-uniform) every wave of the block has a tile to stream
+	bool whole = true;  // (block-uniform) R == 2: the block's entry is a whole group of the plan
 	bool dead_me = false;
 	if constexpr (R == 2) {
+		// (a.live: the packed list - its entry gives every wave of the block its tile of the plan, any four live tiles in plan order, and
+		// says whether they are a group the plan made: nothing is read from the other three tiles)
 		if (blockIdx.x >= a.live[0]) return;
-		const uint32_t e = a.live[1u + blockIdx.x];
-		dead_me = ((e >> (wtile & 3u)) & 1u) != 0u;
-		wtile = (e >> 4) * 4u + (wtile & 3u);
-		whole = (e & 15u) == 0u;
+		const uint4 e = ((const uint4 *)a.live)[1u + blockIdx.x];
+		const uint32_t wme = wtile & 3u, first = e.x & ~MC33_PACK_GROUP;
+		const uint32_t mine = wme == 0u ? first : wme == 1u ? e.y : wme == 2u ? e.z : e.w;
+		dead_me = mine == MC33_PACK_NONE;  // (the last quad of a list: such a wave walks through with the entry's first tile and T = 0)
+		wtile = dead_me ? first : mine;
+		whole = (e.x & MC33_PACK_GROUP) != 0u;
 	}
 	if (wtile >= a.ntiles) return;
 	const SweepTile tile = a.tiles[wtile];
@@ -296,9 +334,10 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 	// ~270 loads), and only the last segment of the group still loads its halo.  All four waves complete the same number
 	// of planes (same rows, same z range), so every wave reaches every barrier; blocks of unrelated tiles keep the load.
 	bool grouped = true;
-	{
+	if constexpr (R == 2) grouped = whole;  // (any other entry runs ungrouped: its live waves load their own halo column, and there is no barrier in it)
+	else {
 		const uint32_t t0 = wtile & ~3u;
-		if (t0 + 3u >= a.ntiles || !whole) grouped = false;  // (a block with a dead wave runs ungrouped: its live waves load their own halo column, and there is no barrier in it)
+		if (t0 + 3u >= a.ntiles) grouped = false;
 		else {
 			const SweepTile first = a.tiles[t0];
 #pragma unroll
@@ -847,7 +886,7 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 			if (pend_sum[q] && lane == 0) atomicAdd(a.lane[q].slot_part + pend_chunk[q], pend_sum[q]);
 	}
 	if (a.trace && lane == 0) {
-		unsigned long long *tr = a.trace + 4ull * (blockIdx.x * 4u + wv);  // (by launched wave: block index mod 8 is the XCD; the tile is live[1 + block])
+		unsigned long long *tr = a.trace + 4ull * (blockIdx.x * 4u + wv);  // (by launched wave: block index mod 8 is the XCD; the tile is that of the block's entry in the packed list)
 		tr[0] = t_start; tr[1] = __builtin_amdgcn_s_memrealtime(); tr[2] = c_start; tr[3] = __builtin_amdgcn_s_memtime();
 	}
 #undef MC33_ADV_ISSUE

@@ -24,12 +24,15 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 dev = torch.device("cuda:0")
 grid, r0, d = fields.cos_field_cube(n, dev)
 g = api.DeviceGrid(grid, r0=r0, d=d)
-for iso in (0.002, 0.001, 0.0):  # (three sweeps - a repeated count of one isovalue is answered from the last; the second builds the table)
+for iso in (0.004, 0.003, 0.002, 0.001, 0.0):  # (five sweeps - a repeated count of one isovalue is answered from the last; the second
+    # builds the table and publishes its live count, the third asks for a size, the fourth agrees and is the first by the sized
+    # plan - it pays for making it - and the fifth, the one traced, goes by a plan that stays)
     cnt = g.count(iso)
 torch.cuda.synchronize()
 print("nV", cnt.nV, "nT", cnt.nT, "timing", g.timing())
-# one record per LAUNCHED wave (block index * 4 + wave): with a range table block b streams the tiles of live[1 + b]
-# (mc33hip_sweep_live), blocks beyond the live count leave no stamp
+# one record per LAUNCHED wave (block index * 4 + wave): with a range table block b streams the four tiles of entry b of the packed
+# live list (mc33hip_sweep_packed; a library from before it: the tiles of live[1 + b], mc33hip_sweep_live), blocks beyond the list
+# leave no stamp
 t = np.fromfile(out, dtype=np.uint64).reshape(-1, 4).astype(np.int64)
 import ctypes as C  # noqa: E402
 wave = np.arange(len(t))            # launched wave = launched block * 4 + wave of the block
@@ -42,7 +45,19 @@ if hasattr(g.lib, "mc33hip_sweep_plan") and g.lib.mc33hip_sweep_plan(g.ctx, None
     assert g.lib.mc33hip_sweep_plan(g.ctx, C.c_void_p(tiles.ctypes.data), tiles.shape[0], C.byref(info)) == 0
     print("plan %d: %d tiles, %d blocks resident" % (info[2], len(tiles), info[1]))
 linfo = (C.c_ulonglong * 2)()
-if hasattr(g.lib, "mc33hip_sweep_live") and g.lib.mc33hip_sweep_live(g.ctx, None, 0, C.byref(linfo)) == 0:
+pinfo = (C.c_ulonglong * 3)()
+if hasattr(g.lib, "mc33hip_sweep_packed") and g.lib.mc33hip_sweep_packed(g.ctx, None, 0, C.byref(pinfo)) == 0:
+    ent = np.zeros((max(int(pinfo[0]), 1), 4), np.uint32)
+    assert g.lib.mc33hip_sweep_packed(g.ctx, C.c_void_p(ent.ctypes.data), ent.shape[0], C.byref(pinfo)) == 0
+    nlive = int(pinfo[0])
+    whole = int(((ent[:nlive, 0] >> 31) != 0).sum())
+    print("packed blocks %d (%d whole groups) for %d live tiles of %d planned: %.2f of the %d resident blocks" % (nlive, whole, pinfo[1], pinfo[2], nlive / max(int(info[1]), 1), info[1]))
+    ent[:, 0] &= 0x7FFFFFFF
+    b = np.minimum(wave // 4, max(nlive - 1, 0))
+    tile = ent[b, wave % 4].astype(np.int64)
+    dead_wave = tile == 0xFFFFFFFF
+    tile[dead_wave | (wave // 4 >= nlive)] = -1
+elif hasattr(g.lib, "mc33hip_sweep_live") and g.lib.mc33hip_sweep_live(g.ctx, None, 0, C.byref(linfo)) == 0:
     live = np.zeros(max(int(linfo[1]), 1), np.uint32)
     assert g.lib.mc33hip_sweep_live(g.ctx, C.c_void_p(live.ctypes.data), live.shape[0], C.byref(linfo)) == 0
     nlive = int(linfo[0])
