@@ -315,6 +315,29 @@ typedef struct { unsigned n; double plane[6][4]; } mc33_clip;   /* the coordinat
 surface *MC33_calculate_clipped_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_clip *planes);
 int MC33_clip_box(const double lo[3], const double hi[3], mc33_clip *out);
 
+/* extension (not in the reference): an isosurface closed where it runs into the faces of the grid - MC33 stops there and leaves
+ * the surface open, so that its signed volume means nothing, its components do not count as closed and a printer or a mesher
+ * cannot take it.  The caps are made on the device: on every face of a box of grid points lo .. hi (lo[a] < hi[a] <= N[a]; hi all
+ * zero: the whole grid) the solid side of the face's samples is triangulated cell by cell, with new vertices at the solid grid
+ * points, joined to the surface's own rim vertices: one consistently wound mesh without boundary.  The solid side is the one the
+ * surface's winding turns its back on - F > isovalue in the plain libraries, F < isovalue in the _nneg flavours; invert != 0 caps
+ * the other side and returns the surface with its winding and normals reversed (a dark object in a bright field).  Face cells
+ * with a sample equal to the isovalue (integer isovalues in CT data) or a NaN are skipped and counted: the result keeps boundary
+ * edges there and closed is 0.  The exact definition is in mc33_hip.h (mc33hip_cap_surface).
+ * MC33_calculate_capped_isosurface extracts the surface into device memory, caps it there, colours the FINAL vertices when a
+ * property grid and a colour map are set (a new vertex gets the colour of its own position) and downloads once into a caller-owned
+ * `surface` like calculate_isosurface's.  options NULL: the whole grid, invert 0; info NULL: no counts wanted.  The extractor's iso,
+ * nV, nT and memoryfault are left as calculate_isosurface leaves them for a surface of the returned size.  NULL for an inclined
+ * grid, for an extractor spread over several devices and for a refused box - the extractor is not touched then - and on failure
+ * (memoryfault 1). */
+typedef struct { unsigned lo[3], hi[3]; int invert; } mc33_cap;
+typedef struct {
+	unsigned nV, nT;                  /* of the returned surface */
+	unsigned cap_vertices, cap_triangles, rim_segments, capped_cells, skipped_cells, off_face_edges;
+	int solid_above, closed;          /* the side that was capped (1: F > isovalue); 1: nothing was skipped, the surface has no boundary */
+} mc33_cap_info;
+surface *MC33_calculate_capped_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_cap *options, mc33_cap_info *info);
+
 /* extension (not in the reference): the section of an isosurface by a plane - the outline a viewer draws over a slice image, its
  * length, the area it encloses, and the same along a stack of parallel planes: the cross-sectional area profile of a vessel, a
  * bone or a pore.  The surface stays in device memory; only the outline, or a few numbers per plane, come back.  plane[4] = a, b,

@@ -809,6 +809,90 @@ int mc33hip_section_ladder(mc33hip_ctx *c, const void *dV, unsigned long long nV
                            const double normal[3], const double *offsets, unsigned n, unsigned long long *segments, double *length,
                            double *area, unsigned long long *invalid_triangles);
 
+/* --- close a finished mesh at the faces of a box of grid points: caps, new vertices (no counterpart in the reference) ---------------
+ * V (nV x 3 MC33_real), N (nV x 3 float), T (nT x 3 unsigned, id base 0) in device memory, in arrays of capV and capT rows, as
+ * mc33hip_extract left them over the RESIDENT grid for the isovalue `iso`; n_attr <= 2 arrays of capV 4-byte words per vertex.  The
+ * call appends, in place, the faces that close the surface on the six faces of the box lo .. hi of grid points (lo[a] < hi[a] <=
+ * N[a]; the whole grid, or the z bounds of a z-range extraction): new vertices at the solid grid points of the faces, new triangles
+ * joined to the surface's rim vertices by their ids.  Integer atomics whose result does not depend on their order, exclusive sums
+ * and IEEE double arithmetic with nothing fused decide everything: the result is an exact function of the input, two calls return
+ * the same bytes.  tests/cap_oracle.py restates the steps below.
+ *   samples          v = iso - F in MC33_real, the extractor's classification: a grid point is above when v has its sign bit
+ *                    (F > iso), below when it has not, on when v == 0; a NaN sample is neither.
+ *   solid            the side the surface's stored winding turns its back on.  The extractor winds a triangle so that its normal
+ *                    by winding points where F falls and stores N on that side: above is solid in the plain libraries (the
+ *                    reference's README sphere, whose inside is below, has volume < 0), below after mc33hip_set_normal_neg(c, 1) -
+ *                    the _nneg flavours.  invert != 0 caps the other side - a dark object in a bright field: the second and third
+ *                    index of every triangle of T are exchanged and the rows of N negated (their sign bits), in place, and the
+ *                    steps below see that surface.  solid_above: 1 or 0, the side that was capped.
+ *   faces            0 .. 5: x-lo, x-hi, y-lo, y-hi, z-lo, z-hi, outward normal the box's.  The plane of a face has the axes (u, w) =
+ *                    (y, z), (x, z), (x, y); a face cell is the square (cu, cw) .. (cu + 1, cw + 1) of four neighbouring points;
+ *                    "counterclockwise" is as seen from outside the box; the corners Q0 .. Q3 of a cell run counterclockwise from
+ *                    its point with the smallest grid point index.
+ *   1. face bits     per vertex and axis: g = ((double)V[v][a] - r0[a]) * (1.0 / d[a]), r = floor(g + 0.5), and g = r where |g - r| <=
+ *                    tol[a] = min(2^-21 max(|r0[a]|, |r0[a] + N[a] d[a]|) / |d[a]|, 1/4): a vertex on grid plane k has the
+ *                    coordinate (R)k * (R)d + (R)r0, rounded three times in MC33_real, which lies that close to k.  The vertex is
+ *                    on face lo of the axis when g == lo[a], on face hi when g == hi[a].  nonfinite_vertices: the rows of V with a
+ *                    coordinate that is not finite.
+ *      sides         a valid triangle has its three indices below nV (invalid_triangles: the others, which contribute nothing).
+ *                    Its sides e = T[e] -> T[(e + 1) % 3] with two different ends are counted per undirected pair.  A side used
+ *                    once whose ends share no face bit is counted in off_face_edges and left alone - the rim of a hole, of a box
+ *                    smaller than the surface.  Otherwise it is a rim segment a -> b of the lowest face the ends share
+ *                    (rim_segments), unless its midpoint below lies outside the box: off_face_edges again.
+ *   2. its cell      m = (g_a + g_b) * 0.5 on u and w with the snapped coordinates decides whether the midpoint lies in the box (lo
+ *                    <= m <= hi on both axes); the cell is floor of the same midpoint of the coordinates as they were before the
+ *                    snapping, clamped to lo .. hi - 1 - an end that was snapped onto a grid line must not carry the midpoint
+ *                    over it.  The segments of a cell are ordered by i << 2 | e of the triangle i and side e that own them.
+ *   3. regular       a cell none of whose four samples is on or a NaN, with the segments marching squares expects of its solid
+ *                    corners: none for 0 or 4, one for 1, 2 adjacent or 3, two for 2 diagonal ones - and, with two, a decision
+ *                    that step 4 can read.  Every other cell that has a solid corner or a segment is skipped (skipped_cells): no
+ *                    triangle; the mesh stays edge-manifold and consistently wound and keeps boundary edges there.
+ *   4. polygons      convex, fanned from the first entry: (p0, p1, p2), (p0, p2, p3) ...  One segment: [b, a, c1 .. ck], the
+ *                    solid corners counterclockwise from the one whose clockwise neighbour is not solid.  Four solid corners:
+ *                    [Q0, Q1, Q2, Q3].  Two segments, (a1, b1) before (a2, b2): corner c lies on the positive side of b -> a when
+ *                    s = (g_a[u] - g_b[u]) * (c[w] - g_b[w]) - (g_a[w] - g_b[w]) * (c[u] - g_b[u]), negated on the faces x-lo,
+ *                    y-hi, z-lo, is > 0.  When each segment has exactly one solid corner on its positive side, and not the
+ *                    same: two triangles [b1, a1, cA], [b2, a2, cB].  When each has both solid corners there and exactly one
+ *                    other corner Qj not there, and not the same: the hexagon [b1, a1, cA, b2, a2, cB] with c = Q(j + 1) mod 4.
+ *                    The surface's own face-test decision is read off its segments, not made again.  Anything else: skipped.
+ *                    capped_cells: the regular cells that have a polygon.
+ *   5. new vertices  one per grid point that a polygon names, a point on a box edge or corner shared by the faces that meet
+ *                    there; numbered from nV on in ascending order of the grid point index (z npy + y) npx + x.  V: (R)index *
+ *                    (R)d[a] + (R)r0[a] per axis in MC33_real, what the vertex pass stores for t = 0.  N: n[a] = +1 / -1 / 0 where a
+ *                    polygon of face hi / lo / no face of the axis names the point, (float)((double)n[a] / sqrt(n . n)), +0 where
+ *                    n[a] == 0 - the sign the extractor's N has relative to its winding, in every flavour and with invert (which
+ *                    exchanges both).  Attributes: by attr_mode[k], MC33HIP_CAP_WORD the word 0, MC33HIP_CAP_F32 the float NaN
+ *                    0x7FC00000.  The rows below nV keep their bytes (invert apart).
+ *   6. new triangles from nT on: by face, then by cell with u the faster index, then in polygon order.
+ *   closed           1 when skipped_cells == 0, off_face_edges == 0 and every rim segment lies in a regular cell.
+ *   MC33HIP_ERUNTIME   invalid triangles, in the words of the measuring calls; the outputs are complete without them.
+ *   MC33HIP_ECAPACITY  capV < nV_out or capT < nT_out: every filled field is valid and nothing is written, invert included
+ *                      (capV = capT = 0 is the size query; 2^32-1 rows are the most a mesh may have).
+ *   MC33HIP_EINVAL     checked on the host, nothing is written: an inclined context; a z-slab context (plane0 != 0 or fewer
+ *                      resident planes than the grid); no resident grid; a box with lo[a] >= hi[a] or hi[a] > N[a]; nV or nT
+ *                      above 2^32-1; an isovalue that is a NaN; n_attr > 2 or a mode that is neither; a null pointer where a size
+ *                      is not zero.
+ *   An empty surface is legal: a box whose faces are all solid gets its whole shell, a box with nothing solid gets nothing.
+ * Out of scope: cells with a sample equal to the isovalue (skipped and counted), caps at other planes, inclined grids.
+ * The call enqueues on the context's stream behind whatever is on it, waits once, and brings the counts to the host.  Scratch, with
+ * the context until mc33hip_destroy: 1 byte per vertex, 25 bytes per face cell and 8 per point of the box's surface, and the table
+ * of sides: 16 bytes per slot, a power of two >= 4 nT slots.  A side with 2^24 uses would wrap the count in its word. */
+#define MC33HIP_CAP_WORD 0
+#define MC33HIP_CAP_F32 1
+typedef struct {
+	void *V, *N, *T;  unsigned long long nV, nT;         /* in and out (device): capV x 3 MC33_real, capV x 3 float, capT x 3 unsigned */
+	unsigned long long capV, capT;
+	double iso;                                          /* the isovalue of the extraction; used as MC33_real */
+	unsigned lo[3], hi[3];                               /* the box, grid point indices: lo[a] < hi[a] <= N[a] */
+	int invert;
+	void *attr[2]; unsigned n_attr;                      /* in and out: <= 2 arrays of capV 4-byte words (device) */
+	int attr_mode[2];                                    /* MC33HIP_CAP_WORD 0, MC33HIP_CAP_F32 1 */
+	unsigned long long nV_out, nT_out, cap_vertices, cap_triangles, rim_segments, capped_cells, skipped_cells, off_face_edges,
+	                   invalid_triangles, nonfinite_vertices;   /* filled */
+	int solid_above, closed;                             /* filled */
+} mc33hip_capping;
+int mc33hip_cap_surface(mc33hip_ctx *c, mc33hip_capping *a);
+
 /* --- curvature of the implicit surface at the vertices, from the grid's second differences (no counterpart in the reference) ------
  * Mean, Gaussian and principal curvatures of the surface F = iso at nV vertices dV (nV x 3 MC33_real in device memory, what
  * mc33hip_emit wrote, or any points), taken from the gradient g and the Hessian H of the RESIDENT grid - the curvature of the field's

@@ -121,6 +121,31 @@ CLIP_COUNTS = ("nV_out", "nT_out", "kept_vertices", "cut_vertices", "on_plane_ve
                "invalid_triangles", "nonfinite_vertices")
 
 
+class Capping(C.Structure):
+    """mc33hip_capping (include/mc33_hip.h)"""
+    _fields_ = [("V", C.c_void_p), ("N", C.c_void_p), ("T", C.c_void_p), ("nV", C.c_ulonglong), ("nT", C.c_ulonglong),
+                ("capV", C.c_ulonglong), ("capT", C.c_ulonglong), ("iso", C.c_double), ("lo", C.c_uint * 3), ("hi", C.c_uint * 3), ("invert", C.c_int),
+                ("attr", C.c_void_p * 2), ("n_attr", C.c_uint), ("attr_mode", C.c_int * 2)] + \
+               [(n, C.c_ulonglong) for n in ("nV_out", "nT_out", "cap_vertices", "cap_triangles", "rim_segments", "capped_cells", "skipped_cells", "off_face_edges",
+                                             "invalid_triangles", "nonfinite_vertices")] + [("solid_above", C.c_int), ("closed", C.c_int)]
+
+
+class SurfaceCap(C.Structure):
+    """mc33_cap (include/marching_cubes_33.h): the box in grid points (hi all 0: the whole grid) and invert"""
+    _fields_ = [("lo", C.c_uint * 3), ("hi", C.c_uint * 3), ("invert", C.c_int)]
+
+
+class SurfaceCapInfo(C.Structure):
+    """mc33_cap_info (include/marching_cubes_33.h)"""
+    _fields_ = [(n, C.c_uint) for n in ("nV", "nT", "cap_vertices", "cap_triangles", "rim_segments", "capped_cells", "skipped_cells", "off_face_edges")] + \
+               [("solid_above", C.c_int), ("closed", C.c_int)]
+
+
+CAP_MODES = {"word": 0, "f32": 1}
+CAP_COUNTS = ("nV_out", "nT_out", "cap_vertices", "cap_triangles", "rim_segments", "capped_cells", "skipped_cells", "off_face_edges", "invalid_triangles",
+              "nonfinite_vertices", "solid_above", "closed")
+
+
 class Sectioning(C.Structure):
     """mc33hip_section (include/mc33_hip.h)"""
     _fields_ = [("V", C.c_void_p), ("T", C.c_void_p), ("nV", C.c_ulonglong), ("nT", C.c_ulonglong),
@@ -208,7 +233,8 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_resampled_size", "mc33hip_resample_grid", "mc33hip_context_device", "mc33hip_grid_spectrum",
            "mc33hip_clip_surface", "mc33hip_section_surface", "mc33hip_section_contours", "mc33hip_section_ladder",
            "mc33hip_grid_stable", "mc33hip_grid_changed", "mc33hip_range_table", "mc33hip_sweep_skipped",
-           "mc33hip_sweep_plan", "mc33hip_sweep_live", "mc33hip_sweep_packed", "mc33hip_curvature_vertices", "mc33hip_color_values"]
+           "mc33hip_sweep_plan", "mc33hip_sweep_live", "mc33hip_sweep_packed", "mc33hip_curvature_vertices", "mc33hip_color_values",
+           "mc33hip_cap_surface"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -223,7 +249,8 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "MC33_grid_spectrum", "MC33_isovalue_ladder",
                  "MC33_calculate_clipped_isosurface", "MC33_clip_box",
                  "MC33_section_isosurface", "MC33_free_section", "MC33_section_contours", "MC33_section_profile",
-                 "MC33_set_color_source", "MC33_isosurface_curvature"]
+                 "MC33_set_color_source", "MC33_isosurface_curvature",
+                 "MC33_calculate_capped_isosurface"]
 
 
 class MC33Error(RuntimeError):
@@ -312,6 +339,8 @@ def load_library(dtype="f32"):
     lib.mc33hip_section_contours.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V, P(C.c_double * 4), V, C.c_ulonglong, P(C.c_ulonglong)]
     lib.mc33hip_section_ladder.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, P(C.c_double * 3), P(C.c_double), C.c_uint, P(C.c_ulonglong), P(C.c_double),
                                            P(C.c_double), P(C.c_ulonglong)]
+    if hasattr(lib, "mc33hip_cap_surface"):
+        lib.mc33hip_cap_surface.argtypes = [V, P(Capping)]
     if hasattr(lib, "mc33hip_curvature_vertices"):
         lib.mc33hip_curvature_vertices.argtypes = [V, P(Curvature)]
         lib.mc33hip_color_values.argtypes = [V, V, C.c_ulonglong, P(C.c_int), C.c_uint, C.c_double, C.c_double, C.c_int, V]
@@ -1053,6 +1082,69 @@ class DeviceGrid:
             V, N, T, _, _, info = self.clip(V, N, T, plane)
             infos.append(info)
         out = (V, N, T, infos)
+        return out + (self.sample_property(V),) if with_property else out
+
+    # -- close a finished mesh at the faces of a box of grid points (mc33_hip.h: mc33hip_cap_surface) ---------------------------------
+    def cap(self, V, N, T, iso, box=None, invert=False, attrs=()):
+        """The mesh V [n, 3], N [n, 3], T [m, 3] (device tensors, as extract() of `iso` returns them) closed at the six faces of
+        `box` = (lo, hi) in grid points - None: the whole grid; the z bounds of the range for a z-range extraction: new vertices at
+        the solid grid points of the faces, new triangles joined to the surface's rim by its own vertex ids.  invert: cap the
+        other side - the triangles come back with their second and third index exchanged, the normals negated.  attrs: up to two
+        device tensors of one 4-byte word per vertex; a new vertex gets NaN in a float32 tensor, 0 in any other.  Returns (V2, N2,
+        T2, attrs2, info): NEW exact-size device tensors whose first n / m rows are the input's (the input is left alone), and a dict
+        of the call's counts - closed: 1 when nothing was skipped.  Raises MC33Error(ERUNTIME) when a triangle names a vertex >= n
+        (the outputs are complete without it)."""
+        import torch
+        self._vertex_rows(V)
+        self._triangle_rows(T)
+        nV, nT = V.shape[0], T.shape[0]
+        assert N.is_cuda and N.is_contiguous() and N.dtype == torch.float32 and tuple(N.shape) == (nV, 3)
+        attrs = self._attribute_words(attrs, nV)
+        lo, hi = box if box is not None else ((0, 0, 0), (self.desc.npx - 1, self.desc.npy - 1, self.desc.nz_total))
+        a = Capping()
+        a.V, a.N, a.T, a.nV, a.nT = V.data_ptr(), N.data_ptr(), T.data_ptr(), nV, nT
+        a.iso, a.invert = float(iso), int(bool(invert))
+        a.lo, a.hi = (C.c_uint * 3)(*[int(x) for x in lo]), (C.c_uint * 3)(*[int(x) for x in hi])
+        for k, x in enumerate(attrs[:2]):
+            a.attr[k], a.attr_mode[k] = x.data_ptr(), (1 if x.dtype == torch.float32 else 0)
+        a.n_attr = len(attrs)
+        _check(self.lib, self.lib.mc33hip_cap_surface(self.ctx, C.byref(a)), allow=(ECAPACITY,))  # the size query: no room, nothing is written
+        nV2, nT2 = int(a.nV_out), int(a.nT_out)
+        V2 = torch.empty((max(nV2, 1), 3), dtype=V.dtype, device=self.device)
+        N2 = torch.empty((max(nV2, 1), 3), dtype=torch.float32, device=self.device)
+        T2 = torch.empty((max(nT2, 1), 3), dtype=torch.int32, device=self.device)
+        attrs2 = [torch.empty((max(nV2, 1),), dtype=x.dtype, device=self.device) for x in attrs]
+        V2[:nV].copy_(V)
+        N2[:nV].copy_(N)
+        T2[:nT].copy_(T)
+        for x2, x in zip(attrs2, attrs):
+            x2[:nV].copy_(x)
+        a.V, a.N, a.T, a.capV, a.capT = V2.data_ptr(), N2.data_ptr(), T2.data_ptr(), V2.shape[0], T2.shape[0]
+        for k, x in enumerate(attrs2):
+            a.attr[k] = x.data_ptr()
+        _check(self.lib, self.lib.mc33hip_cap_surface(self.ctx, C.byref(a)))
+        return V2[:nV2], N2[:nV2], T2[:nT2], [x[:nV2] for x in attrs2], {n: int(getattr(a, n)) for n in CAP_COUNTS}
+
+    def extract_capped(self, iso, rng=None, invert=False, with_property=False):
+        """extract, then close the surface at the faces of the grid - of the planes z_begin .. z_end of rng, where one is given, whose
+        surface is extracted on its own - on the device.
+        Returns (V, N, T, info) - what measure, topology, smooth, simplify, clip and section take - and, with with_property, the
+        attached property grid's value at the FINAL vertices as a fifth element: a new vertex gets the value of its own position."""
+        if rng is None or (rng.z_begin == 0 and rng.z_end == self.desc.nz_total):
+            got, box = self.extract(iso), None
+        else:
+            # A z range of this context is a slab's piece: its triangles name vertices of the slice below.  The surface of the planes
+            # z_begin .. z_end alone comes from a context on those planes of the same tensor; the caps need the whole grid, here.
+            assert self.desc.plane0 == 0 and rng.z_begin < rng.z_end <= self.desc.nz_total, "a z range of a whole grid"
+            r0, d = tuple(self.desc.r0), tuple(self.desc.d)
+            sub = DeviceGrid(self.tensor[rng.z_begin:rng.z_end + 1], r0=(r0[0], r0[1], r0[2] + rng.z_begin * d[2]), d=d, npx=self.desc.npx, volatile=True)
+            try:
+                got = sub.extract(iso)
+            finally:
+                sub.close()
+            box = ((0, 0, rng.z_begin), (self.desc.npx - 1, self.desc.npy - 1, rng.z_end))
+        V, N, T, _, info = self.cap(got[0], got[1], got[2], iso, box, invert)
+        out = (V, N, T, info)
         return out + (self.sample_property(V),) if with_property else out
 
     # -- section a finished mesh by planes on the device (mc33_hip.h: mc33hip_section_surface and its siblings) ----------------------

@@ -74,6 +74,7 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_smooth_surface
 #pragma weak mc33hip_simplify_surface
 #pragma weak mc33hip_clip_surface
+#pragma weak mc33hip_cap_surface
 #pragma weak mc33hip_section_surface
 #pragma weak mc33hip_section_contours
 #pragma weak mc33hip_section_ladder
@@ -1478,6 +1479,75 @@ surface *MC33_calculate_clipped_isosurface(MC33 *M, MC33_real iso, const mc33_cl
 		if (!clip_plane_ok(cl->plane[k]))
 			return 0; /* (what mc33hip_clip_surface refuses, before anything is extracted) */
 	return derived_call(p, iso, clipped_surface, cl);
+}
+
+/* --- extension: an isosurface closed at the faces of the grid ------------------------------------------------------------------
+ * The surface of `iso` into staging set 0 and the caps behind it, in place: first with the set as it stands (an extraction leaves an
+ * eighth to spare), and when that is refused for room, the set grown to the sizes that came back, the surface extracted into it
+ * again - what a set held does not survive its growth - and capped there.  Then the colours of the FINAL vertices and one download. */
+struct cap_job { const mc33_cap *options; mc33_cap_info *info; };
+
+static void cap_box(const MC33 *M, const mc33_cap *o, unsigned lo[3], unsigned hi[3]) {
+	const unsigned N[3] = {M->nx, M->ny, M->nz};
+	const int whole = !o || (o->hi[0] == 0u && o->hi[1] == 0u && o->hi[2] == 0u);
+	for (int a = 0; a != 3; a++) {
+		lo[a] = whole ? 0u : o->lo[a];
+		hi[a] = whole ? N[a] : o->hi[a];
+	}
+}
+
+static surface *capped_surface(mc33_private *p, MC33_real iso, const void *arg) {
+	const struct cap_job *job = (const struct cap_job *)arg;
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0];
+	mc33hip_counts cnt;
+	mc33hip_capping a;
+	int rc = MC33HIP_ECAPACITY;
+	memset(&a, 0, sizeof a);
+	for (int attempt = 0; attempt != 2 && rc == MC33HIP_ECAPACITY; attempt++) {
+		if (attempt && staging_room(s, g, a.nV_out, a.nT_out))
+			return 0;
+		if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK)
+			return 0;
+		memset(&a, 0, sizeof a);
+		a.V = g->dV; a.N = g->dN; a.T = g->dT; a.nV = cnt.nV; a.nT = cnt.nT;
+		a.capV = g->capV; a.capT = g->capT;
+		a.iso = (double)iso;
+		cap_box(&p->pub, job->options, a.lo, a.hi);
+		a.invert = job->options ? job->options->invert : 0;
+		rc = mc33hip_cap_surface(s->ctx, &a);
+	}
+	if (rc != MC33HIP_OK)
+		return 0;
+	cnt.nV = a.nV_out; cnt.nT = a.nT_out;
+	if (coloured(p) && cnt.nV) { /* a new vertex gets the colour of its own position */
+		p->nan_color = DefaultColorMC;
+		if (enqueue_colors(s, g, cnt.nV) != MC33HIP_OK)
+			return 0;
+	}
+	if (job->info) {
+		mc33_cap_info *q = job->info;
+		q->nV = (unsigned)a.nV_out; q->nT = (unsigned)a.nT_out;
+		q->cap_vertices = (unsigned)a.cap_vertices; q->cap_triangles = (unsigned)a.cap_triangles; q->rim_segments = (unsigned)a.rim_segments;
+		q->capped_cells = (unsigned)a.capped_cells; q->skipped_cells = (unsigned)a.skipped_cells; q->off_face_edges = (unsigned)a.off_face_edges;
+		q->solid_above = a.solid_above; q->closed = a.closed;
+	}
+	return surface_from_staging(p, g, &cnt, iso, 0);
+}
+
+surface *MC33_calculate_capped_isosurface(MC33 *M, MC33_real iso, const mc33_cap *options, mc33_cap_info *info) {
+	mc33_private *p = one_slab(M, mc33hip_cap_surface && mc33hip_color_vertices);
+	if (!p || p->inclined || iso != iso)
+		return 0;
+	unsigned lo[3], hi[3];
+	cap_box(M, options, lo, hi);
+	const unsigned N[3] = {M->nx, M->ny, M->nz};
+	for (int a = 0; a != 3; a++)
+		if (!(lo[a] < hi[a] && hi[a] <= N[a]))
+			return 0; /* (what mc33hip_cap_surface refuses, before anything is extracted) */
+	struct cap_job job = {options, info};
+	if (info) memset(info, 0, sizeof *info);
+	return derived_call(p, iso, capped_surface, &job);
 }
 
 /* --- extension: the section of an isosurface by a plane ------------------------------------------------------------------------

@@ -60,6 +60,10 @@
 //                   k_section_* - a finished V, T met by a plane: clip's classes, table and owners as they stand, then the contour
 //                   as points and directed segments, a union-find over the points, length and enclosed area in the fixed order of
 //                   the measures; k_section_ladder - many parallel planes in one pass over T (mc33_section.hip.h).
+//                   k_cap_* - a finished V, N, T closed at the faces of a box of grid points: face bits of the vertices, the table of
+//                   sides for the ones used once, a minimum, a maximum and a count of rim segments per face cell, marching squares
+//                   over the resident samples of the faces, two exclusive scans, two writing passes; k_cap_sides is its hot path
+//                   (mc33_cap.hip.h).
 // Before an extraction: k_rs_resample - the resident grid into a second device grid, a separable correlation of up to 17 taps per axis
 //                   with an integer stride, one pass over the source: a block stages the rows its tile of outputs needs in LDS,
 //                   sums along x and y into a ring of planes and along z out of it (mc33_resample.hip.h).
@@ -129,6 +133,7 @@ typedef float sample_t;
 #include "mc33_topology.hip.h"
 #include "mc33_filter.hip.h"
 #include "mc33_smooth.hip.h"
+#include "mc33_cap.hip.h"
 #include "mc33_simplify.hip.h"
 #include "mc33_clip.hip.h"
 #include "mc33_section.hip.h"
