@@ -338,6 +338,51 @@ typedef struct {
 } mc33_cap_info;
 surface *MC33_calculate_capped_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_cap *options, mc33_cap_info *info);
 
+/* extension (not in the reference, whose only callers are two interactive viewers): pictures of an isosurface made on the device - a
+ * depth-tested, shaded image, a depth buffer and an id buffer (the triangle under every pixel: picking).  A card without a display
+ * usually sits in a machine nobody sits at; a 1024 x 1024 picture is 4 MB where the surface it shows is hundreds.
+ * mc33_view: m, row major, takes (x, y, z, 1) in the coordinates of the vertices to clip coordinates - x, y in -1 .. 1 over the image
+ * after the division by w, y up, depth 0 .. 1; cull 0 none, 1 back, 2 front (the front is the side the normals point to);
+ * two_sided != 0 lights both sides; light is a direction in the coordinates of the vertices; a pixel's colour is the interpolated
+ * vertex colour times ambient + diffuse cos; background is a colour word 0xAABBGGRR like surface.color.  The exact definition is
+ * in mc33_hip.h (mc33hip_render_surface).
+ * MC33_render_isosurface extracts once into device memory - colours from the property grid or the curvature source when a colour
+ * map is set, else DefaultColorMC -, renders the n views one after another and downloads only the arrays `want` names (MC33_IMAGE_RGBA
+ * | MC33_IMAGE_DEPTH | MC33_IMAGE_IDS) into malloc blocks that MC33_free_image releases; row 0 is the top row.  Returns n, or -1 with
+ * out untouched.  It sets the extractor's iso like size_of_isosurface and leaves memoryfault, nV, nT, T and V alone.  -1 with the
+ * extractor untouched as well: a null pointer, n == 0, `want` without a known bit, a view the device call refuses (a size outside
+ * 1 .. 4096, a matrix entry, light component, ambient or diffuse that is not finite, a light without direction, a cull outside 0 ..
+ * 2), an extractor spread over several devices.
+ * MC33_view_fit (host only) fills *out with a view that frames the grid's bounding box - of an inclined grid, its sheared box - seen
+ * along dir with up upwards: fov_degrees 0 is orthographic, up to 170 a perspective with that vertical field of view; pixels are
+ * square; depth 0 .. 1 spans the box; light = -dir (a headlight), ambient 0.2, diffuse 0.8, cull 0, two_sided 1, background opaque
+ * black.  -1 with nothing written: a null pointer, a zero or non-finite dir or up, up parallel to dir, fov outside [0, 170], a size
+ * outside 1 .. 4096.
+ * MC33_write_image_ppm writes rgba as a binary P6 file; -1 without an rgba array or when the file cannot be written. */
+#define MC33_IMAGE_RGBA 1u
+#define MC33_IMAGE_DEPTH 2u
+#define MC33_IMAGE_IDS 4u
+typedef struct {
+	double m[16];
+	unsigned width, height;
+	int cull, two_sided;
+	double light[3], ambient, diffuse;
+	unsigned background;
+} mc33_view;
+typedef struct {
+	unsigned width, height;
+	unsigned *rgba;                   /* width x height words 0xAABBGGRR, or NULL */
+	float *depth;                     /* +inf where nothing was drawn */
+	unsigned *triangle;               /* 0xFFFFFFFF where nothing was drawn */
+	unsigned drawn, culled, degenerate, rejected, offscreen, invalid_triangles;   /* triangles by class */
+	unsigned long long fragments, covered;
+	unsigned nV, nT;                  /* of the surface that was drawn */
+} mc33_image;
+int MC33_render_isosurface(MC33 *extractor, MC33_real isovalue, const mc33_view *views, unsigned n, unsigned want, mc33_image *out);
+void MC33_free_image(mc33_image *image);
+int MC33_view_fit(MC33 *extractor, const double dir[3], const double up[3], double fov_degrees, unsigned width, unsigned height, mc33_view *out);
+int MC33_write_image_ppm(const mc33_image *image, const char *filename);
+
 /* extension (not in the reference): the section of an isosurface by a plane - the outline a viewer draws over a slice image, its
  * length, the area it encloses, and the same along a stack of parallel planes: the cross-sectional area profile of a vessel, a
  * bone or a pore.  The surface stays in device memory; only the outline, or a few numbers per plane, come back.  plane[4] = a, b,

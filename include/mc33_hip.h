@@ -893,6 +893,66 @@ typedef struct {
 } mc33hip_capping;
 int mc33hip_cap_surface(mc33hip_ctx *c, mc33hip_capping *a);
 
+/* --- draw a finished mesh on the device: a depth-tested, shaded image and an id buffer (no counterpart in the reference) ------------
+ * V (nV x 3 MC33_real), N (nV x 3 float), T (nT x 3 unsigned, id base 0) in device memory, and C: nV colour words 0xAABBGGRR (NULL:
+ * base_color for every vertex).  The call reads only these arrays: an inclined context and a z-slab context are accepted.  Outputs,
+ * each a device array of width x height, row 0 at the top, each may be NULL (all NULL asks for the counts alone): oRGBA uint32
+ * 0xAABBGGRR, oDepth float, oTri uint32 - the triangle under the pixel, 0xFFFFFFFF where nothing was drawn.  Everything below is
+ * IEEE double arithmetic with nothing fused, or 64-bit integers; the depth test is an integer minimum and the counts are integer
+ * sums: the result is an exact function of the input, two calls return the same bytes.  tests/render_oracle.py restates the steps.
+ *   vertex       cx = ((m[0] x + m[1] y) + m[2] z) + m[3]; cy, cz, cw likewise from the next rows of m (row major: clip = m (x, y, z,
+ *                1)).  Usable when all four are finite and cw > 0.  ix = cx / cw, iy = cy / cw, z = cz / cw; sx = (ix 0.5 + 0.5) width,
+ *                sy = (0.5 - iy 0.5) height; X = floor(sx 256 + 0.5), Y likewise - 1/256 pixel.  Usable only if |X|, |Y| <= 2^23: that
+ *                guard band is 8 x the largest viewport, and every edge function below stays under 2^49, exact in int64 and in double.
+ *   triangle     in this order: invalid_triangles - an index >= nV; rejected - a corner is not usable (there is no near-plane clipping
+ *                of geometry: MC33_calculate_clipped_isosurface cuts); area2 = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0); degenerate -
+ *                area2 == 0; front-facing when area2 < 0 - for a matrix that does not mirror that is the side the stored N points to, in
+ *                the plain and the _nneg flavours alike; culled - cull 1 and not front-facing, cull 2 and front-facing; offscreen - the
+ *                bounding box of the corners holds no pixel centre of the viewport; drawn - all others.
+ *   coverage     pixel (px, py) has its centre at P = (256 px + 128, 256 py + 128).  Edge A -> B in T's order (0 -> 1, 1 -> 2, 2 -> 0):
+ *                dx = Bx - Ax, dy = By - Ay, E = dx (Py - Ay) - dy (Px - Ax), all three negated when area2 < 0.  The pixel is inside
+ *                when for all three edges E > 0, or E == 0 and (dy < 0 or (dy == 0 and dx > 0)): a pixel centre on an edge two
+ *                triangles share belongs to exactly one of them.
+ *   depth        w_i = E of the edge opposite corner i (w0 of 1 -> 2, w1 of 2 -> 0, w2 of 0 -> 1); zf = (((double)w0 z0 + (double)w1
+ *                z1) + (double)w2 z2) / (double)|area2|.  A fragment exists where the pixel is inside and 0 <= zf <= 1 - near and far
+ *                clipping per pixel (fragments: their number).  zq = (uint32)floor(zf 4294967295.0 + 0.5), key = (uint64)zq << 32 |
+ *                triangle index; the pixel keeps the minimum key: the nearest fragment, the lower index at equal zq.  covered: the
+ *                pixels that hold a key.
+ *   resolve      for a covered pixel and its triangle: b_i = (double)w_i / (double)|area2|, q_i = b_i / cw_i, s = (q0 + q1) + q2,
+ *                L_i = q_i / s.  oDepth = (float)zf, oTri = the index.  n = ((L0 N0 + L1 N1) + L2 N2) per component, len = sqrt((nx nx +
+ *                ny ny) + nz nz); l = light / |light| with |light| taken the same way, once, on the host; t = ((nx lx + ny ly) + nz
+ *                lz) / len, |t| with two_sided, else t where t > 0 and 0 elsewhere; t = 0 where len is 0 or not finite.  shade =
+ *                ambient + diffuse t.  For R, G, B (bits 0-7, 8-15, 16-23) with c_i the channel of corner i's word as double: x = shade
+ *                ((L0 c0 + L1 c1) + L2 c2); x where x > 0, else 0 (a NaN gives 0); x where x < 255, else 255; floor(x + 0.5).  A = 255.
+ *                An uncovered pixel gets background, +inf and 0xFFFFFFFF.
+ *   MC33HIP_ERUNTIME   invalid triangles, in the words of the measuring calls; the outputs are complete without them.  Also when the
+ *                      boxes of the triangles too large for one lane hold more than 2^32-1 screen tiles of 16 x 16 pixels (65 536
+ *                      triangles that each fill a 4096 x 4096 viewport): the image is not complete then.
+ *   MC33HIP_EINVAL     checked on the host, nothing is written: width or height 0 or above 4096; a matrix entry, a light component,
+ *                      ambient or diffuse that is not finite; a light whose length is 0 (or overflows); a cull value outside 0 .. 2;
+ *                      nV or nT above 2^32-1; a null V, N or T where its size is not zero.
+ *   nT == 0 is legal and gives the background.
+ * Out of scope: geometric near-plane clipping, transparency, anti-aliasing, shadows, textures, compositing several images by depth.
+ * The call enqueues on the context's stream behind whatever is on it, waits once, and brings the counts to the host.  Scratch, with
+ * the context until mc33hip_destroy: 8 bytes per pixel (the keys), a screen record of 24 bytes per vertex (X, Y, z, cw), and 8 bytes
+ * per triangle for the list of the triangles too large for one lane and their work items.  MC33_HIP_RENDER_SMALL=<pixels>, read when
+ * the context is created, is the largest box of pixel centres a single lane walks (default 16; 0: every triangle goes down the tiled
+ * path); the bytes are the same in every setting. */
+typedef struct {
+	const void *V, *N, *T, *C;  unsigned long long nV, nT;   /* in (device): nV x 3 MC33_real, nV x 3 float, nT x 3 unsigned, nV words or NULL */
+	double m[16];                                            /* row major: clip = m (x, y, z, 1) */
+	unsigned width, height;                                  /* 1 .. 4096 */
+	int cull, two_sided;                                     /* cull: 0 none, 1 back, 2 front */
+	double light[3], ambient, diffuse;                       /* light: a direction in the coordinates of V */
+	unsigned base_color, background;                         /* colour words 0xAABBGGRR */
+	void *oRGBA, *oDepth, *oTri;                             /* out (device), each width x height or NULL */
+	unsigned long long drawn, culled, degenerate, rejected, offscreen, invalid_triangles, fragments, covered;   /* filled */
+} mc33hip_rendering;
+int mc33hip_render_surface(mc33hip_ctx *c, mc33hip_rendering *a);
+/* Developer timing: with MC33_HIP_TIMING >= 2 when the context is created, hipEvent times in ms of the stages of the last
+ * mc33hip_render_surface call - clear, vertex pass, triangle pass, scan of the list, tiled pass, resolve; MC33HIP_EINVAL otherwise. */
+int mc33hip_render_timing(mc33hip_ctx *c, float ms[6]);
+
 /* --- curvature of the implicit surface at the vertices, from the grid's second differences (no counterpart in the reference) ------
  * Mean, Gaussian and principal curvatures of the surface F = iso at nV vertices dV (nV x 3 MC33_real in device memory, what
  * mc33hip_emit wrote, or any points), taken from the gradient g and the Hessian H of the RESIDENT grid - the curvature of the field's

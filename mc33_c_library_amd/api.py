@@ -146,6 +146,32 @@ CAP_COUNTS = ("nV_out", "nT_out", "cap_vertices", "cap_triangles", "rim_segments
               "nonfinite_vertices", "solid_above", "closed")
 
 
+class Rendering(C.Structure):
+    """mc33hip_rendering (include/mc33_hip.h)"""
+    _fields_ = [("V", C.c_void_p), ("N", C.c_void_p), ("T", C.c_void_p), ("C", C.c_void_p), ("nV", C.c_ulonglong), ("nT", C.c_ulonglong),
+                ("m", C.c_double * 16), ("width", C.c_uint), ("height", C.c_uint), ("cull", C.c_int), ("two_sided", C.c_int),
+                ("light", C.c_double * 3), ("ambient", C.c_double), ("diffuse", C.c_double), ("base_color", C.c_uint), ("background", C.c_uint),
+                ("oRGBA", C.c_void_p), ("oDepth", C.c_void_p), ("oTri", C.c_void_p)] + \
+               [(n, C.c_ulonglong) for n in ("drawn", "culled", "degenerate", "rejected", "offscreen", "invalid_triangles", "fragments", "covered")]
+
+
+class View(C.Structure):
+    """mc33_view (include/marching_cubes_33.h): what DeviceGrid.render takes for its view, too"""
+    _fields_ = [("m", C.c_double * 16), ("width", C.c_uint), ("height", C.c_uint), ("cull", C.c_int), ("two_sided", C.c_int),
+                ("light", C.c_double * 3), ("ambient", C.c_double), ("diffuse", C.c_double), ("background", C.c_uint)]
+
+
+class Image(C.Structure):
+    """mc33_image (include/marching_cubes_33.h)"""
+    _fields_ = [("width", C.c_uint), ("height", C.c_uint), ("rgba", C.POINTER(C.c_uint)), ("depth", C.POINTER(C.c_float)), ("triangle", C.POINTER(C.c_uint))] + \
+               [(n, C.c_uint) for n in ("drawn", "culled", "degenerate", "rejected", "offscreen", "invalid_triangles")] + \
+               [("fragments", C.c_ulonglong), ("covered", C.c_ulonglong), ("nV", C.c_uint), ("nT", C.c_uint)]
+
+
+RENDER_COUNTS = ("drawn", "culled", "degenerate", "rejected", "offscreen", "invalid_triangles", "fragments", "covered")
+IMAGE_RGBA, IMAGE_DEPTH, IMAGE_IDS = 1, 2, 4
+
+
 class Sectioning(C.Structure):
     """mc33hip_section (include/mc33_hip.h)"""
     _fields_ = [("V", C.c_void_p), ("T", C.c_void_p), ("nV", C.c_ulonglong), ("nT", C.c_ulonglong),
@@ -234,7 +260,7 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_clip_surface", "mc33hip_section_surface", "mc33hip_section_contours", "mc33hip_section_ladder",
            "mc33hip_grid_stable", "mc33hip_grid_changed", "mc33hip_range_table", "mc33hip_sweep_skipped",
            "mc33hip_sweep_plan", "mc33hip_sweep_live", "mc33hip_sweep_packed", "mc33hip_curvature_vertices", "mc33hip_color_values",
-           "mc33hip_cap_surface"]
+           "mc33hip_cap_surface", "mc33hip_render_surface", "mc33hip_render_timing"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -250,7 +276,8 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "MC33_calculate_clipped_isosurface", "MC33_clip_box",
                  "MC33_section_isosurface", "MC33_free_section", "MC33_section_contours", "MC33_section_profile",
                  "MC33_set_color_source", "MC33_isosurface_curvature",
-                 "MC33_calculate_capped_isosurface"]
+                 "MC33_calculate_capped_isosurface",
+                 "MC33_render_isosurface", "MC33_free_image", "MC33_view_fit", "MC33_write_image_ppm"]
 
 
 class MC33Error(RuntimeError):
@@ -341,6 +368,9 @@ def load_library(dtype="f32"):
                                            P(C.c_double), P(C.c_ulonglong)]
     if hasattr(lib, "mc33hip_cap_surface"):
         lib.mc33hip_cap_surface.argtypes = [V, P(Capping)]
+    if hasattr(lib, "mc33hip_render_surface"):
+        lib.mc33hip_render_surface.argtypes = [V, P(Rendering)]
+        lib.mc33hip_render_timing.argtypes = [V, P(C.c_float * 6)]
     if hasattr(lib, "mc33hip_curvature_vertices"):
         lib.mc33hip_curvature_vertices.argtypes = [V, P(Curvature)]
         lib.mc33hip_color_values.argtypes = [V, V, C.c_ulonglong, P(C.c_int), C.c_uint, C.c_double, C.c_double, C.c_int, V]
@@ -1146,6 +1176,43 @@ class DeviceGrid:
         V, N, T, _, info = self.cap(got[0], got[1], got[2], iso, box, invert)
         out = (V, N, T, info)
         return out + (self.sample_property(V),) if with_property else out
+
+    # -- draw a finished mesh on the device (mc33_hip.h: mc33hip_render_surface) ---------------------------------------------------------
+    def render(self, V, N, T, colors, view, want=IMAGE_RGBA | IMAGE_DEPTH | IMAGE_IDS, base_color=0xff5c5c5c):
+        """The mesh V [n, 3], N [n, 3], T [m, 3] (device tensors, as extract() returns them) drawn as `view` (a View: matrix, image
+        size, cull, two_sided, light, ambient, diffuse, background) sees it.  colors: an int32 device tensor [n] of words 0xAABBGGRR
+        (what color_vertices returns), or None: base_color for every vertex.  want: IMAGE_RGBA | IMAGE_DEPTH | IMAGE_IDS; 0 asks for
+        the counts alone.  Returns (rgba, depth, ids, info): device tensors [height, width] - int32 words, float32 with +inf where
+        nothing was drawn, int32 triangle indices with -1 there -, None for an array not wanted, and a dict of the call's counts.
+        Raises MC33Error(ERUNTIME) when a triangle names a vertex >= n (the image is complete without it)."""
+        import torch
+        self._vertex_rows(V)
+        self._triangle_rows(T)
+        nV, nT = V.shape[0], T.shape[0]
+        assert N.is_cuda and N.is_contiguous() and N.dtype == torch.float32 and tuple(N.shape) == (nV, 3)
+        if colors is not None:
+            (colors,) = self._attribute_words((colors,), nV)
+        a = Rendering()
+        a.V, a.N, a.T, a.nV, a.nT = V.data_ptr(), N.data_ptr(), T.data_ptr(), nV, nT
+        a.C = colors.data_ptr() if colors is not None and nV else None
+        a.m, a.light = view.m, view.light
+        a.width, a.height, a.cull, a.two_sided = view.width, view.height, view.cull, view.two_sided
+        a.ambient, a.diffuse, a.background, a.base_color = view.ambient, view.diffuse, view.background, int(base_color) & 0xFFFFFFFF
+        shape = (max(int(view.height), 1), max(int(view.width), 1))
+        rgba = torch.empty(shape, dtype=torch.int32, device=self.device) if want & IMAGE_RGBA else None
+        depth = torch.empty(shape, dtype=torch.float32, device=self.device) if want & IMAGE_DEPTH else None
+        ids = torch.empty(shape, dtype=torch.int32, device=self.device) if want & IMAGE_IDS else None
+        a.oRGBA, a.oDepth, a.oTri = (x.data_ptr() if x is not None else None for x in (rgba, depth, ids))
+        _check(self.lib, self.lib.mc33hip_render_surface(self.ctx, C.byref(a)))
+        return rgba, depth, ids, {n: int(getattr(a, n)) for n in RENDER_COUNTS}
+
+    def extract_rendered(self, iso, view, want=IMAGE_RGBA | IMAGE_DEPTH | IMAGE_IDS, colors=None):
+        """extract, then draw the surface on the device: (rgba, depth, ids, info) as render() returns them, info with the surface's
+        nV and nT.  colors(V) -> an int32 tensor of colour words for the vertices (color_vertices, say), or None."""
+        V, N, T, cnt = self.extract(iso)
+        rgba, depth, ids, info = self.render(V, N, T, colors(V) if colors is not None else None, view, want)
+        info["nV"], info["nT"] = int(cnt.nV), int(cnt.nT)
+        return rgba, depth, ids, info
 
     # -- section a finished mesh by planes on the device (mc33_hip.h: mc33hip_section_surface and its siblings) ----------------------
     def section(self, V, T, plane, attrs=(), attr_modes=()):

@@ -75,6 +75,7 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_simplify_surface
 #pragma weak mc33hip_clip_surface
 #pragma weak mc33hip_cap_surface
+#pragma weak mc33hip_render_surface
 #pragma weak mc33hip_section_surface
 #pragma weak mc33hip_section_contours
 #pragma weak mc33hip_section_ladder
@@ -145,6 +146,8 @@ typedef struct mc33_private_s {
 	int color_source;    /* MC33_set_color_source: MC33_COLOR_PROPERTY, or the curvature the map paints (one slab then) */
 	void *dG;            /* MC33_isosurface_curvature: the Gaussian curvature beside the mean in dP (device) */
 	unsigned long long capG;
+	void *dImg[3];       /* MC33_render_isosurface: colour, depth and id image of the view under way (device) */
+	unsigned long long capImg[3];
 } mc33_private;
 #define MC33_MAGIC 0x4D43333348495031ull /* "MC33HIP1" */
 
@@ -363,6 +366,7 @@ void free_MC33(MC33 *M) {
 		for (int k = 0; k != 2; k++)
 			staging_release(s->ctx, &s->set[k]);
 		if (q == 0) { dev_release(s->ctx, &p->dP, &p->capP); dev_release(s->ctx, &p->dL, &p->capL); dev_release(s->ctx, &p->dG, &p->capG); }
+		for (int k = 0; q == 0 && k != 3; k++) dev_release(s->ctx, &p->dImg[k], &p->capImg[k]);
 		if (q == 0 && p->own_grid) { /* the grid of MC33_create_resampled: through the context while it lives, when nothing reads it any more */
 			(void)mc33hip_synchronize(s->ctx);
 			(void)mc33hip_device_free(s->ctx, p->own_grid);
@@ -1548,6 +1552,167 @@ surface *MC33_calculate_capped_isosurface(MC33 *M, MC33_real iso, const mc33_cap
 	struct cap_job job = {options, info};
 	if (info) memset(info, 0, sizeof *info);
 	return derived_call(p, iso, capped_surface, &job);
+}
+
+/* --- extension: pictures of an isosurface ------------------------------------------------------------------------------------
+ * The surface of `iso` with its colours into staging set 0, once; every view drawn from there into p->dImg and only the arrays the
+ * caller wants brought to the host.  The images are collected beside `out` and copied there when all views are done. */
+static int view_ok(const mc33_view *v) { /* what mc33hip_render_surface refuses, before anything is extracted */
+	int finite = isfinite(v->ambient) && isfinite(v->diffuse);
+	for (int k = 0; k != 16; k++) finite = finite && isfinite(v->m[k]);
+	for (int k = 0; k != 3; k++) finite = finite && isfinite(v->light[k]);
+	if (!finite || v->width == 0u || v->width > 4096u || v->height == 0u || v->height > 4096u || v->cull < 0 || v->cull > 2)
+		return 0;
+	const double len = sqrt((v->light[0] * v->light[0] + v->light[1] * v->light[1]) + v->light[2] * v->light[2]);
+	return len > 0.0 && isfinite(len);
+}
+
+void MC33_free_image(mc33_image *image) {
+	if (!image)
+		return;
+	free(image->rgba); free(image->depth); free(image->triangle);
+	image->rgba = 0; image->depth = 0; image->triangle = 0;
+}
+
+static int render_view(mc33_private *p, const struct staging *g, const mc33hip_counts *cnt, const mc33_view *v, unsigned want, mc33_image *img) {
+	mc33_slab *s = &p->slab[0];
+	const unsigned long long pixels = (unsigned long long)v->width * v->height;
+	mc33hip_rendering a;
+	memset(&a, 0, sizeof a);
+	for (int b = 0; b != 3; b++)
+		if ((want >> b & 1u) && dev_room(s->ctx, &p->dImg[b], &p->capImg[b], pixels, 4))
+			return -1;
+	a.V = g->dV; a.N = g->dN; a.T = g->dT; a.nV = cnt->nV; a.nT = cnt->nT;
+	a.C = coloured(p) && cnt->nV ? g->dC : 0;
+	a.base_color = (unsigned)DefaultColorMC;
+	memcpy(a.m, v->m, sizeof a.m);
+	a.width = v->width; a.height = v->height; a.cull = v->cull; a.two_sided = v->two_sided;
+	memcpy(a.light, v->light, sizeof a.light);
+	a.ambient = v->ambient; a.diffuse = v->diffuse; a.background = v->background;
+	a.oRGBA = want & MC33_IMAGE_RGBA ? p->dImg[0] : 0;
+	a.oDepth = want & MC33_IMAGE_DEPTH ? p->dImg[1] : 0;
+	a.oTri = want & MC33_IMAGE_IDS ? p->dImg[2] : 0;
+	if (mc33hip_render_surface(s->ctx, &a) != MC33HIP_OK)
+		return -1;
+	void **host[3] = {(void **)&img->rgba, (void **)&img->depth, (void **)&img->triangle};
+	for (int b = 0; b != 3; b++) {
+		if (!(want >> b & 1u))
+			continue;
+		if (!(*host[b] = malloc((size_t)pixels * 4)) || mc33hip_download(s->ctx, *host[b], p->dImg[b], (size_t)pixels * 4) != MC33HIP_OK)
+			return -1;
+	}
+	img->width = v->width; img->height = v->height;
+	img->drawn = (unsigned)a.drawn; img->culled = (unsigned)a.culled; img->degenerate = (unsigned)a.degenerate; img->rejected = (unsigned)a.rejected;
+	img->offscreen = (unsigned)a.offscreen; img->invalid_triangles = (unsigned)a.invalid_triangles;
+	img->fragments = a.fragments; img->covered = a.covered;
+	img->nV = (unsigned)cnt->nV; img->nT = (unsigned)cnt->nT;
+	return 0;
+}
+
+int MC33_render_isosurface(MC33 *M, MC33_real iso, const mc33_view *views, unsigned n, unsigned want, mc33_image *out) {
+	mc33_private *p = one_slab(M, mc33hip_render_surface != 0);
+	if (!p || !views || !out || n == 0u || !(want & (MC33_IMAGE_RGBA | MC33_IMAGE_DEPTH | MC33_IMAGE_IDS)))
+		return -1;
+	for (unsigned k = 0; k != n; k++)
+		if (!view_ok(&views[k]))
+			return -1;
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0];
+	mc33hip_counts cnt;
+	M->iso = iso;
+	mc33_image *img = (mc33_image *)calloc(n, sizeof *img);
+	if (!img)
+		return -1;
+	int ok = extract_coloured(p, g, iso, &cnt) == MC33HIP_OK;
+	for (unsigned k = 0; ok && k != n; k++) ok = render_view(p, g, &cnt, &views[k], want, &img[k]) == 0;
+	if (ok)
+		memcpy(out, img, n * sizeof *img);
+	else
+		for (unsigned k = 0; k != n; k++) MC33_free_image(&img[k]);
+	free(img);
+	return ok ? (int)n : -1;
+}
+
+/* the eight corners of the grid's box in the coordinates of the vertices: r0 + A (i d0, j d1, k d2), A the identity unless the grid
+ * is inclined (MC:608-610) */
+static void box_corners(const mc33_private *p, double c[8][3]) {
+	const unsigned N[3] = {p->pub.nx, p->pub.ny, p->pub.nz};
+	for (int q = 0; q != 8; q++) {
+		double g[3];
+		for (int a = 0; a != 3; a++) g[a] = (q >> a & 1) ? (double)N[a] * p->grd_d[a] : 0.0;
+		for (int a = 0; a != 3; a++)
+			c[q][a] = p->grd_r0[a] + (p->inclined ? (p->grd_A[3 * a] * g[0] + p->grd_A[3 * a + 1] * g[1]) + p->grd_A[3 * a + 2] * g[2] : g[a]);
+	}
+}
+
+static double dot3(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+int MC33_view_fit(MC33 *M, const double dir[3], const double up[3], double fov_degrees, unsigned width, unsigned height, mc33_view *out) {
+	const mc33_private *p = priv(M);
+	if (!p || !dir || !up || !out || !(fov_degrees >= 0.0 && fov_degrees <= 170.0) || width == 0u || width > 4096u || height == 0u || height > 4096u)
+		return -1;
+	for (int a = 0; a != 3; a++)
+		if (!isfinite(dir[a]) || !isfinite(up[a]))
+			return -1;
+	/* f: the viewing direction, r: to the right, u: upwards in the image; the vectors are scaled by their largest component first
+	 * so that no square overflows */
+	double f[3], r[3], u[3], w[3];
+	const double dm = fmax(fabs(dir[0]), fmax(fabs(dir[1]), fabs(dir[2]))), um = fmax(fabs(up[0]), fmax(fabs(up[1]), fabs(up[2])));
+	if (!(dm > 0.0) || !(um > 0.0))
+		return -1;
+	for (int a = 0; a != 3; a++) { f[a] = dir[a] / dm; w[a] = up[a] / um; }
+	const double fl = sqrt(dot3(f, f)), wl = sqrt(dot3(w, w));
+	for (int a = 0; a != 3; a++) { f[a] /= fl; w[a] /= wl; }
+	r[0] = f[1] * w[2] - f[2] * w[1]; r[1] = f[2] * w[0] - f[0] * w[2]; r[2] = f[0] * w[1] - f[1] * w[0];
+	const double rl = sqrt(dot3(r, r));
+	if (!(rl > 1e-7)) /* up (anti)parallel to dir, as far as doubles can tell */
+		return -1;
+	for (int a = 0; a != 3; a++) r[a] /= rl;
+	u[0] = r[1] * f[2] - r[2] * f[1]; u[1] = r[2] * f[0] - r[0] * f[2]; u[2] = r[0] * f[1] - r[1] * f[0];
+	double c[8][3], mid[3] = {0.0, 0.0, 0.0};
+	box_corners(p, c);
+	for (int q = 0; q != 8; q++)
+		for (int a = 0; a != 3; a++) mid[a] += 0.125 * c[q][a];
+	/* the corners about the middle of the box, in the view's axes */
+	double e[8][3], zmin = DBL_MAX, zmax = -DBL_MAX, hx = 0.0, hy = 0.0;
+	for (int q = 0; q != 8; q++) {
+		const double d[3] = {c[q][0] - mid[0], c[q][1] - mid[1], c[q][2] - mid[2]};
+		e[q][0] = dot3(r, d); e[q][1] = dot3(u, d); e[q][2] = dot3(f, d);
+		hx = fmax(hx, fabs(e[q][0])); hy = fmax(hy, fabs(e[q][1]));
+		zmin = fmin(zmin, e[q][2]); zmax = fmax(zmax, e[q][2]);
+	}
+	const double span = zmax - zmin, aspect = (double)width / (double)height, margin = 1.02, zpad = span * 0x1p-10;
+	if (!(span > 0.0) || !isfinite(span))
+		return -1;
+	mc33_view v;
+	memset(&v, 0, sizeof v);
+	double row[4][3], off[4]; /* clip row = row . (p - mid) + off */
+	if (fov_degrees == 0.0) {
+		const double a = margin * fmax(hx / (double)width, hy / (double)height); /* half a pixel's worth ... x width, x height: the half extents */
+		const double zn = zmin - zpad, zf = zmax + zpad;
+		for (int k = 0; k != 3; k++) { row[0][k] = r[k] / (a * (double)width); row[1][k] = u[k] / (a * (double)height); row[2][k] = f[k] / (zf - zn); row[3][k] = 0.0; }
+		off[0] = 0.0; off[1] = 0.0; off[2] = -zn / (zf - zn); off[3] = 1.0;
+	} else {
+		const double th = tan(fov_degrees * (3.14159265358979323846 / 360.0));
+		double D = 0.0; /* the eye sits D behind the middle of the box: every corner inside the pyramid */
+		for (int q = 0; q != 8; q++) D = fmax(D, fmax(fabs(e[q][0]) / (th * aspect), fabs(e[q][1]) / th) - e[q][2]);
+		D = fmax(margin * D, 0.05 * span - zmin);
+		const double zn = D + zmin - 0x1p-10 * fmin(span, D + zmin), zf = D + zmax + zpad, A = zf / (zf - zn), B = -(zf * zn) / (zf - zn);
+		for (int k = 0; k != 3; k++) { row[0][k] = r[k] / (th * aspect); row[1][k] = u[k] / th; row[3][k] = f[k]; row[2][k] = A * f[k]; }
+		off[0] = 0.0; off[1] = 0.0; off[3] = D; off[2] = A * D + B;
+	}
+	for (int j = 0; j != 4; j++) {
+		for (int k = 0; k != 3; k++) v.m[4 * j + k] = row[j][k];
+		v.m[4 * j + 3] = off[j] - dot3(row[j], mid);
+	}
+	for (int k = 0; k != 16; k++)
+		if (!isfinite(v.m[k]))
+			return -1;
+	v.width = width; v.height = height; v.cull = 0; v.two_sided = 1;
+	for (int a = 0; a != 3; a++) v.light[a] = -f[a];
+	v.ambient = 0.2; v.diffuse = 0.8; v.background = 0xFF000000u;
+	*out = v;
+	return 0;
 }
 
 /* --- extension: the section of an isosurface by a plane ------------------------------------------------------------------------

@@ -64,6 +64,10 @@
 //                   sides for the ones used once, a minimum, a maximum and a count of rim segments per face cell, marching squares
 //                   over the resident samples of the faces, two exclusive scans, two writing passes; k_cap_sides is its hot path
 //                   (mc33_cap.hip.h).
+//                   k_render_* - a finished V, N, T and a colour word per vertex drawn into an image, a depth buffer and an id buffer: a
+//                   screen record per vertex, a lane per triangle lowering 64-bit depth | id keys with atomicMin, a wave per screen tile
+//                   of the triangles too large for a lane, a lane per pixel to shade; k_render_triangles is its hot path
+//                   (mc33_render.hip.h).
 // Before an extraction: k_rs_resample - the resident grid into a second device grid, a separable correlation of up to 17 taps per axis
 //                   with an integer stride, one pass over the source: a block stages the rows its tile of outputs needs in LDS,
 //                   sums along x and y into a ring of planes and along z out of it (mc33_resample.hip.h).
@@ -134,6 +138,7 @@ typedef float sample_t;
 #include "mc33_filter.hip.h"
 #include "mc33_smooth.hip.h"
 #include "mc33_cap.hip.h"
+#include "mc33_render.hip.h"
 #include "mc33_simplify.hip.h"
 #include "mc33_clip.hip.h"
 #include "mc33_section.hip.h"

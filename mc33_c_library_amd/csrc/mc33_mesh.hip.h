@@ -1,6 +1,6 @@
 // mc33_mesh.hip.h -- part of the ONE translation unit mc33_kernels.hip (builds on mc33_context.hip.h; not a header to include elsewhere):
 // what the passes over a FINISHED V, N, T in device memory have in common - mc33_measure, mc33_topology, mc33_filter, mc33_smooth,
-// mc33_simplify, mc33_clip, mc33_section and mc33_cap build on it and on nothing of each other's but what their opening lines name.  DESIGN.md 18.
+// mc33_simplify, mc33_clip, mc33_section, mc33_cap and mc33_render build on it and on nothing of each other's but what their opening lines name.  DESIGN.md 18.
 //   block primitives   sums and scans over the 256 lanes of a block, sums over runs of equal keys in a wave
 //   the tile scan      an exclusive scan of what the elements of an array count, in tiles of MESH_TILE: a sum per tile, one block
 //                      over the tile sums, a placing pass - or a writing kernel of a part's own that opens like one
@@ -269,7 +269,7 @@ struct MeshOp {
 	void (*release)(void *state);  // the device arrays the state holds; it is the key of the registration too
 };
 struct MeshHost {
-	MeshOp op[10];              // topology, filter, smooth, simplify, clip, resample, spectrum, section, curvature, cap: a part beyond that makes this larger
+	MeshOp op[11];              // topology, filter, smooth, simplify, clip, resample, spectrum, section, curvature, cap, render: a part beyond that makes this larger
 	uint32_t nops;
 	// scratch no two parts use at once (every entry point waits before it returns), grown on demand by meas_room
 	uint8_t *d_keep;            // [nV] a flag per vertex: referenced, kept

@@ -160,3 +160,27 @@ int write_ply_s(surface *S, const char *filename, const char *author, const char
 	fclose(f);
 	return tail ? 0 : -1;
 }
+
+/* extension (not in the reference): a picture made by MC33_render_isosurface as a binary PPM (P6, three bytes a pixel, top row
+ * first) - the one image format that needs no library.  -1 without an rgba array or when the file cannot be written. */
+int MC33_write_image_ppm(const mc33_image *image, const char *filename) {
+	if (!image || !image->rgba || !filename || image->width == 0u || image->height == 0u)
+		return -1;
+	FILE *f = fopen(filename, "wb");
+	if (!f)
+		return -1;
+	const size_t pixels = (size_t)image->width * image->height;
+	unsigned char *row = (unsigned char *)malloc((size_t)image->width * 3);
+	int ok = row != 0 && fprintf(f, "P6\n%u %u\n255\n", image->width, image->height) > 0;
+	for (size_t p = 0; ok && p != pixels; p += image->width) {
+		for (unsigned x = 0; x != image->width; x++) {
+			const unsigned w = image->rgba[p + x];
+			row[3 * x] = (unsigned char)(w & 255u); row[3 * x + 1] = (unsigned char)(w >> 8 & 255u); row[3 * x + 2] = (unsigned char)(w >> 16 & 255u);
+		}
+		ok = fwrite(row, (size_t)image->width * 3, 1, f) == 1;
+	}
+	free(row);
+	if (fclose(f) != 0)
+		ok = 0;
+	return ok ? 0 : -1;
+}
