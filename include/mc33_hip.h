@@ -117,6 +117,23 @@ int mc33hip_grid_changed(mc33hip_ctx *c);
  * made at timing level >= 1 (mc33hip_set_timing); MC33HIP_EINVAL when there was none.  Nothing is counted at level 0. */
 int mc33hip_range_table(mc33hip_ctx *c, void *host_out, size_t bytes);
 int mc33hip_sweep_skipped(mc33hip_ctx *c, unsigned long long out[3]);
+/* The block table kept beside the range table, and what a sweep makes of it.  mc33hip_range_blocks: 20 entries
+ * {min, max} per strip, [resident plane][y tile][row segment][entry] - entry 4 g + k: sample rows 16 g .. 16 g + 15 of the strip,
+ * samples 64 k .. 64 k + 63 of the segment; entry 16 + g: the halo column over the rows of group g; rows and columns past the grid
+ * clamped into it as the sweep's loads are; {-inf, +inf} for a block that holds a NaN.  mc33hip_block_words: the verdict word per
+ * strip, [resident plane][y tile][row segment], of the last single-isovalue sweep that went by a live list - two bits per entry,
+ * 0 live, 1 all samples strictly below the isovalue, 2 all strictly above; all ones where no sweep has written a word (the strips
+ * of dead tiles).  mc33hip_sweep_skipped_blocks: {blocks of the live tiles, blocks left out below the isovalue, above it} of the
+ * sweep mc33hip_sweep_skipped speaks of (its out[3] stays what it was: callers hand it three words).  MC33HIP_EINVAL when there is
+ * no table / was no such sweep.  MC33_HIP_BLOCKS=0 in the environment when a context is created: no block table, no block left out;
+ * =1: blocks are left out in every sweep that goes by a live list; not set: in those over rows of at least four segments.
+ * Only the library for float samples leaves blocks out; the others keep the table. */
+int mc33hip_range_blocks(mc33hip_ctx *c, void *host_out, size_t bytes);
+int mc33hip_block_words(mc33hip_ctx *c, void *host_out, size_t bytes);
+int mc33hip_sweep_skipped_blocks(mc33hip_ctx *c, unsigned long long out[3]);
+/* mc33hip_alias_cells: the cut cells of the last count that have a corner equal to the isovalue (they take the general per-cell
+ * kernels), as the device counted them; for tests. */
+int mc33hip_alias_cells(mc33hip_ctx *c, unsigned long long *out);
 /* For tests and tracing as well.  mc33hip_sweep_plan: the sweep's plan in force - the one the last sweep, or the last tail, went
  * by - as tiles {row segment, y tile, z_lo, z_hi} in launch order, four consecutive tiles a block, into tiles_out (room for
  * cap_tiles tiles; NULL: info only); info = {tiles, blocks the device holds at once, 0: the plan of a sweep without a range

@@ -186,6 +186,14 @@ struct mc33hip_ctx {
 	uint32_t sweeps_seen;     // sweeps since the samples last changed, while there is no table
 	uint32_t *d_skipped;      // mc33hip_sweep_skipped: SweepArgs::skipped of the last single-isovalue sweep at timing level >= 1
 	uint64_t skipped_tiles;   // ... its tiles (0: no such sweep yet)
+	// the block table (k_ranges: RANGE_BLOCKS entries per strip), made with the range table, in the same launch, and good exactly as
+	// long as it is (ranges_valid); and the verdict word per strip of the last sweep that left blocks out (k_block_verdicts)
+	RangeEntry *d_blocks;
+	unsigned long long *d_blockw;
+	uint64_t blocks_cap, blockw_cap;
+	bool blocks_made;         // the last k_ranges wrote the block table too
+	bool blocks_off;          // MC33_HIP_BLOCKS=0: no block table, no block left out (read at create)
+	bool blocks_always;       // MC33_HIP_BLOCKS=1: blocks are left out wherever a sweep goes by a list; not set: where it pays (launch_sweep_zm)
 	int cus;                  // compute units of the device
 	int emit_v_blocks_per_cu; // blocks of k_emit_vertices a CU holds
 	hipEvent_t ev[4];
@@ -254,6 +262,7 @@ static void read_switches(Switches &w) {
 }
 static void forget_ranges(mc33hip_ctx *c) {  // the samples changed, or may have: no table until the second sweep from now
 	c->ranges_valid = false;
+	c->blocks_made = false;
 	c->sweeps_seen = 0;
 	c->table_coarse = false;  // (new samples: the finer plan until a sweep says otherwise ...
 	c->table_target = 0u;     // ... at its default depth until one has published a count)
@@ -401,6 +410,8 @@ extern "C" int mc33hip_create(mc33hip_ctx **out, const mc33hip_grid_desc *d) {
 	c->timing_level = getenv("MC33_HIP_TIMING") ? atoi(getenv("MC33_HIP_TIMING")) : 0;
 	c->epoch_wrap = std::min(1u << 30, std::max(3u, env_u32("MC33_HIP_EPOCH_WRAP", 1u << 30)));
 	c->ranges_off = env_flag("MC33_HIP_RANGES") == 0;
+	c->blocks_off = env_flag("MC33_HIP_BLOCKS") == 0;
+	c->blocks_always = env_flag("MC33_HIP_BLOCKS") == 1;
 	CREATE_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
 	CREATE_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
 	CREATE_TRY(hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming));
@@ -428,7 +439,7 @@ extern "C" void mc33hip_destroy(mc33hip_ctx *c) {
 	dev_release(&c->d_verdict); dev_release(&c->d_live); dev_release(&c->d_packed);
 	if (c->h_live) (void)hipHostFree(c->h_live);
 	c->h_live = nullptr;
-	dev_release(&c->d_ranges); dev_release(&c->d_skipped);
+	dev_release(&c->d_ranges); dev_release(&c->d_skipped); dev_release(&c->d_blocks); dev_release(&c->d_blockw);
 	dev_release(&c->d_bases);
 	dev_release(&c->trace); dev_release(&c->trace_cells);
 	if (c->aux) (void)hipStreamSynchronize(c->aux);

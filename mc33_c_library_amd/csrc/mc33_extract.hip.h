@@ -324,6 +324,7 @@ static void sweep_args(mc33hip_ctx *c, const SlotGeom &g, SweepArgs &a) {
 	a.ranges = nullptr;
 	a.skipped = nullptr;
 	a.live = nullptr;
+	a.blockw = nullptr;
 	a.debug = 0;
 	for (int q = 0; q < SWEEP_MAXNI; q++) a.lane[q] = SweepLane{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, (real_t)0, 0, 0xFFFFFFFFu};
 }
@@ -342,11 +343,18 @@ static const RangeEntry *sweep_ranges(mc33hip_ctx *c, hipStream_t st) {
 	const uint64_t n = (uint64_t)npl * nYT * P.nseg, blocks = (uint64_t)npl * nYT * nXG;
 	if (blocks > 0x7FFFFFFFull) return nullptr;
 	if (c->ranges_cap < n && dev_room("range table", &c->d_ranges, &c->ranges_cap, n) != 0) { (void)hipGetLastError(); return nullptr; }
+	// (the block table beside it, from the same pass: no memory for it, or MC33_HIP_BLOCKS=0, and the sweeps leave no block out)
+	RangeEntry *fine = nullptr;
+	if (!c->blocks_off) {
+		if (c->blocks_cap >= n * RANGE_BLOCKS || dev_room("block table", &c->d_blocks, &c->blocks_cap, n * RANGE_BLOCKS) == 0) fine = c->d_blocks;
+		else (void)hipGetLastError();
+	}
 	const bool vec = (uintptr_t)c->d_grid % 16u == 0 && (c->pitch * sizeof(sample_t)) % 16u == 0 && (c->slice * sizeof(sample_t)) % 16u == 0;
-	if (vec) hipLaunchKernelGGL(k_ranges<true>, dim3((uint32_t)blocks), dim3(256), 0, st, grid_view(c), P, nYT, npl, c->d_ranges);
-	else hipLaunchKernelGGL(k_ranges<false>, dim3((uint32_t)blocks), dim3(256), 0, st, grid_view(c), P, nYT, npl, c->d_ranges);
+	if (vec) hipLaunchKernelGGL(k_ranges<true>, dim3((uint32_t)blocks), dim3(256), 0, st, grid_view(c), P, nYT, npl, c->d_ranges, fine);
+	else hipLaunchKernelGGL(k_ranges<false>, dim3((uint32_t)blocks), dim3(256), 0, st, grid_view(c), P, nYT, npl, c->d_ranges, fine);
 	if (hipGetLastError() != hipSuccess) return nullptr;
 	c->ranges_valid = true;
+	c->blocks_made = fine != nullptr;
 	return c->d_ranges;
 }
 
@@ -469,10 +477,27 @@ static bool sweep_packed(const mc33hip_ctx *c) {
 // one k_sweep launch over NI = 1, 2 or 4 lanes that begin_lane has prepared
 // (all return the samples per lane and load of the form that was launched: k_cells needs it - lane_of_column)
 template <int NI, int ZM>
-static uint32_t launch_sweep_zm(mc33hip_ctx *c, const SweepArgs &a, hipStream_t st) {
+static uint32_t launch_sweep_zm(mc33hip_ctx *c, const SweepArgs &a_in, hipStream_t st) {
+	SweepArgs a = a_in;
 	const uint64_t blocks = (c->plan[c->cur_plan].ntiles + 3) / 4;
 	if (a.live) {  // the verdicts and the live list, in front of the sweep that goes by them (sweep_live)
 		hipLaunchKernelGGL(k_tile_verdicts<NI>, dim3((uint32_t)((blocks + 3) / 4)), dim3(256), 0, st, a, c->d_verdict, (uint32_t)blocks);
+		// The block verdicts of the live tiles, for the one form of the sweep that leaves blocks out (sweep_tile: BS) - a word per strip
+		// of the resident planes, so the room does not depend on the plan.  No block table or no memory: every block is streamed.
+		// Where it pays: rows of at least four segments, whose blocks are grouped - three waves in four take their halo bits from the
+		// mailbox and a dead quarter is a whole instruction less.  On narrower grids every wave loads its own halo column and the launch
+		// in front (11 us at 1024^3) was not won back: 768^3 measured 0.8 % slower with it (profiles/r11_block_skip.txt D).
+		// MC33_HIP_BLOCKS=1: wherever there is a list (the tests run on narrow grids).
+		if (MC33_BLOCK_SKIP && NI == 1 && ZM == 0 && a.ranges && c->blocks_made && c->d_blocks && !c->blocks_off && (c->blocks_always || a.sd.nseg >= 4u)) {
+			const uint64_t n = (uint64_t)c->desc.npz_resident * a.sd.nYT * a.sd.nseg;
+			bool room = c->blockw_cap >= n;
+			if (!room && dev_room("block verdicts", &c->d_blockw, &c->blockw_cap, n) == 0)  // (new memory: all ones, which no verdict is - mc33hip_block_words shows the strips no sweep has written)
+				room = hipMemsetAsync(c->d_blockw, 0xFF, n * sizeof(unsigned long long), st) == hipSuccess;
+			if (room) {
+				hipLaunchKernelGGL(k_block_verdicts, dim3(a.ntiles), dim3(256), 0, st, a, c->d_verdict, c->d_blocks, c->d_blockw);
+				a.blockw = c->d_blockw;
+			} else (void)hipGetLastError();
+		}
 		hipLaunchKernelGGL(k_live_compact, dim3(1), dim3(1024), 0, st, c->d_verdict, (uint32_t)blocks, c->d_live, c->d_packed, c->h_live, c->cur_plan ? 1u : 0u, a.ntiles, c->sw.list_lds);
 		c->live_blocks = blocks;
 	}
@@ -485,6 +510,9 @@ static uint32_t launch_sweep_zm(mc33hip_ctx *c, const SweepArgs &a, hipStream_t 
 		else if (a.ranges) hipLaunchKernelGGL((k_sweep<packed_form ? SWEEP_PACK : 1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
 		else hipLaunchKernelGGL((k_sweep_all<packed_form ? SWEEP_PACK : 1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
 		return (uint32_t)SWEEP_PACK;
+	}
+	if constexpr (MC33_BLOCK_SKIP && NI == 1 && ZM == 0) {
+		if (a.live && a.blockw) { hipLaunchKernelGGL((k_sweep_live_blocks<ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a); return 1u; }
 	}
 	if (a.live) hipLaunchKernelGGL((k_sweep_live<1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
 	else if (a.ranges) hipLaunchKernelGGL((k_sweep<1, NI, ZM>), dim3((uint32_t)blocks), dim3(256), 0, st, a);
@@ -693,8 +721,8 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 		a.ranges = ranges;
 		sweep_live(c, a);
 		c->skipped_tiles = 0;
-		if (c->timing_level > 0 && (c->d_skipped || hipMalloc(&c->d_skipped, 4 * sizeof(uint32_t)) == hipSuccess)) {  // (mc33hip_sweep_skipped; never on the production path)
-			HIP_TRY(hipMemsetAsync(c->d_skipped, 0, 4 * sizeof(uint32_t), st));
+		if (c->timing_level > 0 && (c->d_skipped || hipMalloc(&c->d_skipped, 8 * sizeof(uint32_t)) == hipSuccess)) {  // (mc33hip_sweep_skipped; never on the production path)
+			HIP_TRY(hipMemsetAsync(c->d_skipped, 0, 8 * sizeof(uint32_t), st));
 			a.skipped = c->d_skipped;
 			c->skipped_tiles = a.ntiles;
 		} else if (c->timing_level > 0) (void)hipGetLastError();
@@ -1381,6 +1409,44 @@ extern "C" int mc33hip_sweep_skipped(mc33hip_ctx *c, unsigned long long *out /*[
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	HIP_TRY(hipMemcpy(w, c->d_skipped, sizeof w, hipMemcpyDeviceToHost));
 	out[0] = c->skipped_tiles; out[1] = w[1]; out[2] = w[2];
+	return MC33HIP_OK;
+}
+extern "C" int mc33hip_sweep_skipped_blocks(mc33hip_ctx *c, unsigned long long *out /*[3]*/) {
+	if (!c || !out) return MC33HIP_EINVAL;
+	if (!c->skipped_tiles || !c->d_skipped) { set_err("no single-isovalue sweep at timing level >= 1 yet"); return MC33HIP_EINVAL; }
+	if (int rc = use_device(c)) return rc;
+	uint32_t w[8];
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	HIP_TRY(hipMemcpy(w, c->d_skipped, sizeof w, hipMemcpyDeviceToHost));
+	out[0] = w[4]; out[1] = w[5]; out[2] = w[6];
+	return MC33HIP_OK;
+}
+extern "C" int mc33hip_alias_cells(mc33hip_ctx *c, unsigned long long *out) {
+	if (!c || !out) return MC33HIP_EINVAL;
+	if (!c->counted || !c->w || !c->w->h_ctr) { set_err("no count yet"); return MC33HIP_EINVAL; }
+	if (int rc = use_device(c)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	*out = c->w->alias_known ? c->w->alias_last : c->w->h_ctr->alias_cells;
+	return MC33HIP_OK;
+}
+extern "C" int mc33hip_range_blocks(mc33hip_ctx *c, void *host_out, size_t bytes) {
+	if (!c || !host_out) return MC33HIP_EINVAL;
+	if (!c->ranges_valid || !c->blocks_made || !c->d_blocks) { set_err("no block table (no range table yet, dropped, the grid is volatile, or MC33_HIP_BLOCKS=0)"); return MC33HIP_EINVAL; }
+	const uint64_t n = (uint64_t)c->desc.npz_resident * ((c->desc.npy - 1u + 62u) / 63u) * ((c->desc.npx - 1u + SEG_CELLS - 1u) / SEG_CELLS) * RANGE_BLOCKS;
+	if (bytes != n * sizeof(RangeEntry)) { set_err("block table: %llu bytes, not %llu", (unsigned long long)(n * sizeof(RangeEntry)), (unsigned long long)bytes); return MC33HIP_EINVAL; }
+	if (int rc = use_device(c)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	HIP_TRY(hipMemcpy(host_out, c->d_blocks, bytes, hipMemcpyDeviceToHost));
+	return MC33HIP_OK;
+}
+extern "C" int mc33hip_block_words(mc33hip_ctx *c, void *host_out, size_t bytes) {
+	if (!c || !host_out) return MC33HIP_EINVAL;
+	if (!c->ranges_valid || !c->blocks_made || !c->d_blockw) { set_err("no sweep has left blocks out yet"); return MC33HIP_EINVAL; }
+	const uint64_t n = (uint64_t)c->desc.npz_resident * ((c->desc.npy - 1u + 62u) / 63u) * ((c->desc.npx - 1u + SEG_CELLS - 1u) / SEG_CELLS);
+	if (bytes != n * 8u) { set_err("block verdicts: %llu bytes, not %llu", (unsigned long long)(n * 8u), (unsigned long long)bytes); return MC33HIP_EINVAL; }
+	if (int rc = use_device(c)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	HIP_TRY(hipMemcpy(host_out, c->d_blockw, bytes, hipMemcpyDeviceToHost));
 	return MC33HIP_OK;
 }
 

@@ -106,11 +106,21 @@ struct SweepLane {
 // [plane - G.z0][yt][seg] once for a grid whose samples are known to stay (sweep_ranges); k_sweep leaves out the tiles whose
 // strips all lie on one side of every isovalue of the pass.
 struct alignas(2 * sizeof(real_t)) RangeEntry { real_t lo, hi; };
+// ... and of the blocks of a strip (k_ranges): 4 row groups of 16 rows x 4 quarters of 64 samples, then the halo column per row group
+constexpr uint32_t RANGE_BLOCKS = 20u;
+// The sweeps that leave dead blocks out inside live tiles (sweep_tile, R == 2, NI == 1, S == 1): the float library.  The libraries
+// of the other sample types keep the table (mc33hip_range_blocks) and sweep as they did: their single-sample forms are the
+// exception there (the narrow types sweep packed), and none of them was measured with the skip.
+#if defined(MC33_GRD_U16) || defined(MC33_GRD_U8) || defined(MC33_GRD_U32) || defined(MC33_GRD_F64)
+constexpr bool MC33_BLOCK_SKIP = false;
+#else
+constexpr bool MC33_BLOCK_SKIP = true;
+#endif
 
 struct SweepArgs {
 	GridView<sample_t> G;
 	const RangeEntry *ranges;  // the range table, nullptr: none (every tile is streamed)
-	uint32_t *skipped;         // timing level >= 1, single-isovalue sweeps: {-, tiles left out below, above the isovalue}; else nullptr
+	uint32_t *skipped;         // timing level >= 1, single-isovalue sweeps: {-, tiles left out below, above the isovalue, -, blocks of live tiles, blocks left out below, above}; else nullptr
 	const uint32_t *live;      // with a table: the PACKED live list k_tile_verdicts / k_live_compact made in front of the sweep - words 0 .. 3 {entries,
 	                           // live tiles, tiles of the plan, 0}, then one 16-byte entry per block that has work: four tiles of the plan (mc33_sweep_pack.h)
 	Params P;                // (P.iso is not used by the sweep: every lane has its own)
@@ -122,6 +132,8 @@ struct SweepArgs {
 	uint32_t debug;          // MC33_HIP_DEBUG, developer builds (-DMC33_DEV) only - timing experiments, results are wrong: 2 = stream
 	                         // only, 16 = stream + the cut-cell test of every slice but no slice is handed on, 64 = no halo-column load
 	SweepLane lane[SWEEP_MAXNI];
+	const unsigned long long *blockw;  // k_block_verdicts' word per strip, [plane - G.z0][yt][seg]; nullptr: no block is left out.  (Last: the
+	                                   // kernels that do not look at it find every other argument where it was.)
 };
 #ifdef MC33_DEV
 #define MC33_DEBUG_BITS(a) ((a).debug)

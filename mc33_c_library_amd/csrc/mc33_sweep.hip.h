@@ -43,87 +43,170 @@ constexpr int SWEEP_PACK = 1;
 // by the strips that are 256 samples wide; the strips at the end of a row, and every strip of a buffer aligned otherwise, go
 // sample by sample, which is correct for any base, pitch and slice.
 // ---------------------------------------------------------------------------------------------------
+// The block table (RangeEntry, RANGE_BLOCKS entries per strip, [strip][entry]; `blocks`, nullptr: not kept): the ranges of the 64 x 16
+// sample blocks one load instruction of the float sweep covers.  Entry 4 g + k: the sample rows 16 g .. 16 g + 15 of the strip (g = 3
+// holds the row shared with the next y tile) and the samples 64 k .. 64 k + 63 of the segment; entries 16 + g: the halo column over
+// the rows of group g.  A block's range is taken over what the sweep's loads of that block return, its addresses clamped as the sweep
+// clamps them (xo[], so, xh in sweep_tile): a row past the tile is the tile's last row, a sample past the grid is the grid's last
+// column - so a block wholly beyond the grid has the range of the clamped column or row, and the strip's entry is the minimum and
+// maximum over its 20 blocks, which is how it is made here.  A NaN makes its block {-inf, +inf}, and with it the strip.
+// The wave works through the four row groups one after the other.  V: a lane's pieces of a group all lie in the same quarter of the
+// row (rows of 8 bytes per sample: in one of two), so a quarter is reduced over the lanes that share it - 16 neighbouring lanes, a DPP
+// row, for 4-byte samples - and nothing but the finished ranges goes through LDS.
 template <bool V>
-__global__ __launch_bounds__(256) void k_ranges(const GridView<sample_t> G, const Params P, const uint32_t nYT, const uint32_t nplanes, RangeEntry *out) {
-	constexpr uint32_t U = 8;                                   // loads in flight per lane
+__global__ __launch_bounds__(256) void k_ranges(const GridView<sample_t> G, const Params P, const uint32_t nYT, const uint32_t nplanes, RangeEntry *out, RangeEntry *blocks) {
 	constexpr uint32_t VS = 16u / (uint32_t)sizeof(sample_t);  // samples of a 16-byte piece
 	struct alignas(16) Piece { sample_t s[VS]; };
 	constexpr real_t INF = std::numeric_limits<real_t>::infinity();
-	// The halo column of a strip is column 0 of the next one: a wave keeps the range of its column 0 apart and hands it to the wave
-	// on its left through LDS (one barrier per block); only a wave with no wave to its right in the block loads that column itself -
+	// The halo column of a strip is column 0 of the next one: a wave keeps the ranges of its column 0 apart and hands them to the wave
+	// on its left through LDS; only a wave with no wave to its right in the block loads that column itself -
 	// a 64-byte line per row for one sample, which for every strip was 12 % more traffic than the grid holds.
-	__shared__ real_t s_col0[4][2];
-	__shared__ uint32_t s_nan0[4];
+	__shared__ real_t s_col0[4][4][2];             // [wave][row group]{min, max} of column 0
+	__shared__ real_t s_blk[4][RANGE_BLOCKS][2];   // [wave][entry]{min, max}
 	const uint32_t lane = threadIdx.x & 63u, nXG = (P.nseg + 3u) / 4u, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	const uint32_t xg = blockIdx.x % nXG, yt = (blockIdx.x / nXG) % nYT, pl = blockIdx.x / nXG / nYT;
 	const uint32_t seg = xg * 4u + wv;
-	const bool active = seg < P.nseg && pl < nplanes;  // (wave-uniform; an idle wave still comes to the barrier)
+	const bool active = seg < P.nseg && pl < nplanes;  // (wave-uniform; an idle wave still comes to the barriers)
 	const uint32_t xbase = seg * SEG_CELLS, y0 = yt * 63u, nrows = min(64u, P.ny + 1u - y0), xlast = min(xbase + SEG_CELLS, P.nx);
 	const sample_t *base = G.p + (uint64_t)pl * G.slice + (uint64_t)y0 * G.pitch;
-	real_t lo = INF, hi = -INF, lo0 = INF, hi0 = -INF;
-	bool nan = false, nan0 = false;
-	auto take = [&](sample_t s, bool col0) __attribute__((always_inline)) {
+	const bool right = wv < 3u && seg + 1u < P.nseg;  // the wave to the right is active: it has this strip's halo column as its column 0, over the same rows
+	auto take = [&](real_t &lo, real_t &hi, sample_t s) __attribute__((always_inline)) {
 		const real_t f = (real_t)s;
 		lo = real_min(lo, f); hi = f > hi ? f : hi;  // (a NaN changes neither)
-		lo0 = col0 ? real_min(lo0, f) : lo0; hi0 = (col0 && f > hi0) ? f : hi0;
 #ifdef MC33_NAN_SAMPLES
-		nan = nan || f != f; nan0 = nan0 || (col0 && f != f);
+		lo = f != f ? -INF : lo; hi = f != f ? INF : hi;
 #endif
 	};
-	if (active) {
-		if (V && xbase + SEG_CELLS - 1u <= P.nx) {  // (wave-uniform)
-			constexpr uint32_t VR = SEG_CELLS / VS;  // pieces per row of the strip
-			const uint32_t total = nrows * VR;
-			for (uint32_t e0 = 0; e0 < total; e0 += 64u * U) {
-				Piece v[U];
-				bool first[U];
-#pragma unroll
-				for (uint32_t k = 0; k < U; k++) {
-					const uint32_t e = min(e0 + 64u * k + lane, total - 1u);
-					first[k] = (e % VR) == 0u;
-					v[k] = *(const Piece *)(base + (uint64_t)(e / VR) * G.pitch + xbase + (e % VR) * VS);
-				}
-#pragma unroll
-				for (uint32_t k = 0; k < U; k++)
-#pragma unroll
-					for (uint32_t j = 0; j < VS; j++) take(v[k].s[j], j == 0u && first[k]);
-			}
-		} else {
-			const uint32_t total = nrows * 4u;  // 64 samples of a row per load
-			for (uint32_t e0 = 0; e0 < total; e0 += U) {
-				sample_t v[U];
-#pragma unroll
-				for (uint32_t k = 0; k < U; k++) {
-					const uint32_t e = min(e0 + k, total - 1u);
-					v[k] = base[(uint64_t)(e >> 2) * G.pitch + min(xbase + 64u * (e & 3u) + lane, xlast)];
-				}
-#pragma unroll
-				for (uint32_t k = 0; k < U; k++) take(v[k], lane == 0u && (min(e0 + k, total - 1u) & 3u) == 0u);
-			}
-		}
-		// Column xbase + 256, where the strip has one (xlast == xbase + 256; a narrower last strip ends inside the loops above), is
-		// beyond both loops.  It is the right neighbour's column 0 - unless there is no wave to the right in this block: the
-		// block's last wave, and the row's last segment when nx is a multiple of 256, where that column is the grid's last.
-		if (xlast == xbase + SEG_CELLS && (wv == 3u || seg + 1u == P.nseg)) take(base[(uint64_t)min(lane, nrows - 1u) * G.pitch + xlast], false);
-	}
-#pragma unroll
-	for (int dlt = 32; dlt; dlt >>= 1) {
-		const real_t l2 = __shfl_xor(lo, dlt), h2 = __shfl_xor(hi, dlt), l3 = __shfl_xor(lo0, dlt), h3 = __shfl_xor(hi0, dlt);
+	auto merge = [&](real_t &lo, real_t &hi, int dlt) __attribute__((always_inline)) {
+		const real_t l2 = __shfl_xor(lo, dlt), h2 = __shfl_xor(hi, dlt);
 		lo = real_min(lo, l2); hi = h2 > hi ? h2 : hi;
-		lo0 = real_min(lo0, l3); hi0 = h3 > hi0 ? h3 : hi0;
+	};
+	if (active) {
+		const bool vec = V && xbase + SEG_CELLS - 1u <= P.nx;  // (wave-uniform)
+#pragma unroll 1
+		for (uint32_t g = 0; g < 4u; g++) {
+			real_t lo0 = INF, hi0 = -INF;
+			const bool past = 16u * g >= nrows;  // a row group wholly past a short tile is the tile's last row 16 times: one round of loads covers it
+			if (vec) {
+				constexpr uint32_t VR = SEG_CELLS / VS;           // pieces per row of the strip
+				constexpr uint32_t NA = VR > 64u ? VR / 64u : 1u;  // quarters a lane's pieces fall into
+				constexpr uint32_t GP = 16u * VR;                  // pieces of a row group
+				constexpr uint32_t U = GP / 64u < 8u ? GP / 64u : 8u;  // loads in flight per lane
+				static_assert(U % NA == 0u && GP % (64u * U) == 0u, "a round of loads covers whole rows");
+				real_t lo[NA], hi[NA];
+#pragma unroll
+				for (uint32_t j = 0; j < NA; j++) { lo[j] = INF; hi[j] = -INF; }
+				for (uint32_t e0 = 0; e0 < (past ? 64u * U : GP); e0 += 64u * U) {
+					Piece v[U];
+					bool first[U];
+#pragma unroll
+					for (uint32_t k = 0; k < U; k++) {
+						const uint32_t e = e0 + 64u * k + lane;
+						first[k] = (e % VR) == 0u;
+						v[k] = *(const Piece *)(base + (uint64_t)min(16u * g + e / VR, nrows - 1u) * G.pitch + xbase + (e % VR) * VS);
+					}
+#pragma unroll
+					for (uint32_t k = 0; k < U; k++) {
+#pragma unroll
+						for (uint32_t j = 0; j < VS; j++) take(lo[k % NA], hi[k % NA], v[k].s[j]);
+						if (first[k]) take(lo0, hi0, v[k].s[0]);
+					}
+				}
+#pragma unroll
+				for (uint32_t j = 0; j < NA; j++) {
+#pragma unroll
+					for (int dlt = 32; dlt; dlt >>= 1)
+						if ((uint32_t)dlt < VR / 4u || (uint32_t)dlt >= VR) merge(lo[j], hi[j], dlt);  // (the lanes whose pieces lie in the same quarter)
+					const uint32_t q = (((64u * j + lane) % VR) * 4u) / VR;
+					s_blk[wv][4u * g + q][0] = lo[j]; s_blk[wv][4u * g + q][1] = hi[j];  // (every lane of the quarter, the same words)
+				}
+			} else {
+				real_t lo[4], hi[4];  // 64 samples of a row per load: a quarter
+#pragma unroll
+				for (uint32_t q = 0; q < 4u; q++) { lo[q] = INF; hi[q] = -INF; }
+				for (uint32_t e0 = 0; e0 < (past ? 8u : 64u); e0 += 8u) {
+					sample_t v[8];
+#pragma unroll
+					for (uint32_t k = 0; k < 8u; k++)
+						v[k] = base[(uint64_t)min(16u * g + ((e0 + k) >> 2), nrows - 1u) * G.pitch + min(xbase + 64u * (k & 3u) + lane, xlast)];
+#pragma unroll
+					for (uint32_t k = 0; k < 8u; k++) {
+						take(lo[k & 3u], hi[k & 3u], v[k]);
+						if (lane == 0u && (k & 3u) == 0u) take(lo0, hi0, v[k]);
+					}
+				}
+#pragma unroll
+				for (uint32_t q = 0; q < 4u; q++) {
+#pragma unroll
+					for (int dlt = 32; dlt; dlt >>= 1) merge(lo[q], hi[q], dlt);
+					if (lane == 0u) { s_blk[wv][4u * g + q][0] = lo[q]; s_blk[wv][4u * g + q][1] = hi[q]; }
+				}
+			}
+#pragma unroll
+			for (int dlt = 32; dlt; dlt >>= 1) merge(lo0, hi0, dlt);
+			if (lane == 0u) { s_col0[wv][g][0] = lo0; s_col0[wv][g][1] = hi0; }
+		}
+		// The halo column - xlast: column 0 of the next segment, or the grid's last column where the strip ends at it or inside it -
+		// is loaded by the wave that has no wave to its right in this block: lane r the sample of row r, a row group 16 lanes.
+		if (!right) {
+			real_t lo = INF, hi = -INF;
+			take(lo, hi, base[(uint64_t)min(lane, nrows - 1u) * G.pitch + xlast]);
+#pragma unroll
+			for (int dlt = 8; dlt; dlt >>= 1) merge(lo, hi, dlt);
+			if ((lane & 15u) == 0u) { s_blk[wv][16u + (lane >> 4)][0] = lo; s_blk[wv][16u + (lane >> 4)][1] = hi; }
+		}
 	}
-	bool anynan = __ballot(nan) != 0ull;
-	const bool anynan0 = __ballot(nan0) != 0ull;
-	if (lane == 0) { s_col0[wv][0] = lo0; s_col0[wv][1] = hi0; s_nan0[wv] = anynan0 ? 1u : 0u; }
+	__syncthreads();
+	if (active && right && lane < 4u) { s_blk[wv][16u + lane][0] = s_col0[wv + 1u][lane][0]; s_blk[wv][16u + lane][1] = s_col0[wv + 1u][lane][1]; }
 	__syncthreads();
 	if (!active) return;
-	if (wv < 3u && seg + 1u < P.nseg) {  // (the wave to the right is active: it has this strip's halo column as its column 0, over the same rows)
-		const real_t l2 = s_col0[wv + 1u][0], h2 = s_col0[wv + 1u][1];
-		lo = real_min(lo, l2); hi = h2 > hi ? h2 : hi;
-		anynan = anynan || s_nan0[wv + 1u] != 0u;
+	const uint64_t strip = ((uint64_t)pl * nYT + yt) * P.nseg + seg;
+	real_t lo = INF, hi = -INF;
+	if (lane < RANGE_BLOCKS) {
+		lo = s_blk[wv][lane][0]; hi = s_blk[wv][lane][1];
+		if (blocks) blocks[strip * RANGE_BLOCKS + lane] = RangeEntry{lo, hi};
 	}
-	if (anynan) { lo = -INF; hi = INF; }
-	if (lane == 0) out[((uint64_t)pl * nYT + yt) * P.nseg + seg] = RangeEntry{lo, hi};
+#pragma unroll
+	for (int dlt = 16; dlt; dlt >>= 1) merge(lo, hi, dlt);  // (the entries sit in lanes 0 .. 19)
+	if (lane == 0) out[strip] = RangeEntry{lo, hi};
+}
+
+// ---------------------------------------------------------------------------------------------------
+// k_block_verdicts: the block verdicts of a single-isovalue sweep that goes by the live list - one 64-bit word per strip a live tile
+// reads, [plane - G.z0][y tile][segment] like the tables (so the word does not depend on the plan): bits 2 j, 2 j + 1 for entry j of
+// the strip's 20 blocks - 0 the block is live, 1 all its samples lie strictly below the isovalue, 2 all strictly above; both
+// comparisons strict and in MC33_real, as k_tile_verdicts makes them and for the reasons given there.  A block per tile of the plan,
+// half a wave per plane; the tiles k_tile_verdicts found dead have no words.  SweepArgs::skipped (timing level >= 1): words 4 .. 6
+// count the blocks of live tiles, those left out below and those left out above.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_block_verdicts(const SweepArgs a, const uint8_t *verdict, const RangeEntry *blocks, unsigned long long *words) {
+	const uint32_t j = threadIdx.x & 31u, half = threadIdx.x >> 5;  // (eight planes at a time: a tile of the flagship's plan is one round trip)
+	const uint32_t t = blockIdx.x;
+	if ((verdict[t >> 2] >> (t & 3u)) & 1u) return;  // (block-uniform: a dead tile)
+	const SweepTile tile = a.tiles[t];
+	const uint32_t p0r = tile.z_lo == a.P.zs ? tile.z_lo : tile.z_lo + 1u;
+	const real_t v = a.lane[0].iso;
+	for (uint32_t pp = p0r; pp <= tile.z_hi; pp += 8u) {
+		const uint32_t p = pp + half;
+		const bool there = p <= tile.z_hi;
+		const uint64_t strip = ((uint64_t)(min(p, tile.z_hi) - a.G.z0) * a.sd.nYT + tile.yt) * a.sd.nseg + tile.seg;
+		uint32_t code = 0u;
+		if (there && j < RANGE_BLOCKS) {
+			const RangeEntry e = blocks[strip * RANGE_BLOCKS + j];
+			code = e.hi < v ? 1u : e.lo > v ? 2u : 0u;
+		}
+		uint32_t wlo = j < 16u ? code << (2u * j) : 0u, whi = j >= 16u ? code << (2u * (j - 16u)) : 0u;
+#pragma unroll
+		for (int dlt = 16; dlt; dlt >>= 1) { wlo |= (uint32_t)__shfl_xor((int)wlo, dlt); whi |= (uint32_t)__shfl_xor((int)whi, dlt); }
+		if (there && j == 0u) {
+			words[strip] = u64(wlo, whi);
+			if (a.skipped) {
+				atomicAdd(a.skipped + 4, RANGE_BLOCKS);
+				atomicAdd(a.skipped + 5, (uint32_t)(__popc(wlo & 0x55555555u) + __popc(whi & 0x55u)));
+				atomicAdd(a.skipped + 6, (uint32_t)(__popc(wlo & 0xAAAAAAAAu) + __popc(whi & 0xAAu)));
+			}
+		}
+	}
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -296,7 +379,7 @@ __global__ __launch_bounds__(1024) void k_live_compact(const uint8_t *verdict, c
 // 2 (k_sweep_live): the verdicts were made in front of the kernel, and block blockIdx.x streams the four tiles of entry blockIdx.x
 // of the packed live list - plans of one round and more, whose live tiles have to fill the device by themselves: four to a block,
 // so that no block holds wave slots for dead tiles.
-template <int S, int NI, int ZM, int R>
+template <int S, int NI, int ZM, int R, bool BLOCKS = false>
 __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 	constexpr int LPR = 4 / S;    // loads per sample row
 	constexpr int RB = 16 / LPR;  // sample rows per batch
@@ -499,6 +582,28 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 #define MC33_LOAD(rs, vo, so) (__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, so, MC33_SWEEP_AUX)))
 #endif
 	typedef typename std::conditional<S == 1, real_t, uint32_t>::type raw_t;  // what a load leaves in a register
+	// BS: dead blocks inside the live tile are left out (k_block_verdicts).  A quarter of a sample row is one load instruction of this
+	// form and a row group is four batches, so what is dead is decided per instruction, wave-uniformly, from the word of the plane:
+	// bwi of the plane being issued, bwp of the plane being processed, each with the word of the plane behind it asked for a plane
+	// ahead (scalar loads).  A dead load keeps its place in the batch - the waits the compiler derives count on a fixed number of loads
+	// (see `issue`) - and is aimed outside the descriptor, offset 0xFFFFFFF0 like the lanes of the halo load that stay out: no memory
+	// access.  What it returns (0 - and the isovalue may well be 0) is never looked at: `process` puts -inf / +inf in its place, which
+	// classifies as strictly below / above for every isovalue that gave the block that verdict and can never count as "equal to the
+	// isovalue" (|iso - F| is infinite).  The column-0 bits a wave posts in the mailbox come from those samples where its quarter 0
+	// is dead, and are right.  No word (SweepArgs::blockw == nullptr): every block is live.
+	// A kernel of its own (k_sweep_live_blocks) has this form: k_sweep_live stays the code it was, for the sweeps without words.
+	constexpr bool BS = BLOCKS;
+	static_assert(!BLOCKS || (MC33_BLOCK_SKIP && R == 2 && NI == 1 && S == 1), "blocks are left out by the float single-isovalue sweep with a live list");
+	auto block_word = [&](uint32_t p) __attribute__((always_inline)) -> uint64_t {
+		if constexpr (BS) {
+			if (a.blockw) {
+				const unsigned long long w = a.blockw[((uint64_t)(min(p, z_hi) - a.G.z0) * a.sd.nYT + yt) * a.sd.nseg + seg];
+				return u64((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w), (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w >> 32)));
+			}
+		}
+		return 0ull;
+	};
+	uint64_t bwi = block_word(pl0), bwi_n = block_word(pl0 + 1u), bwp = bwi, bwp_n = bwi_n;
 	// A batch is the same number of loads whatever the position in the tile, so that the wait counts the compiler derives keep
 	// the prefetched batch in flight: exactly 17 in the forms that always issue the halo load (several isovalues, double
 	// samples); 16 or 17 in the single-isovalue forms over 1- to 4-byte samples, whose halo load stands behind a branch (below)
@@ -506,11 +611,17 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 		const sample_t *base = a.G.p + (uint64_t)(p - a.G.z0) * a.G.slice + (uint64_t)y0 * a.G.pitch;
 		const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, tile_bytes, 0x00020000);
 		const uint32_t r = bi * (uint32_t)RB;
+		uint32_t codes = 0u, hcode = 0u;  // (BS) the verdicts of the four quarters of this batch's row group, and of its halo block
+		if constexpr (BS) { codes = (uint32_t)(bwi >> (8u * (bi >> 2))) & 0xFFu; hcode = (uint32_t)(bwi >> (32u + 2u * (bi >> 2))) & 3u; }
 #pragma unroll
 		for (int rr = 0; rr < RB; rr++) {
 			const uint32_t so = min(r + rr, nrows - 1) * rowbytes;
 #pragma unroll
 			for (int k = 0; k < LPR; k++) {
+				if constexpr (BS) {
+					const bool dk = ((codes >> (2 * k)) & 3u) != 0u;  // (wave-uniform)
+					d[rr * LPR + k] = MC33_LOAD(rs, dk ? 0xFFFFFFF0u : xo[k], dk ? 0u : so);
+				} else
 				if constexpr (S == 1) d[rr * LPR + k] = MC33_LOAD(rs, xo[k], so);
 				else d[rr * LPR + k] = __builtin_amdgcn_raw_buffer_load_b32(rs, xo[k], so, MC33_SWEEP_AUX);
 			}
@@ -529,7 +640,7 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 			// prefetched batch has come back as well, the other 16 still in flight.  Two copies of the batch loop, one per kind of
 			// wave, would make the counts exact in both and double a 30 KB kernel; measured instead, grouped and ungrouped shapes:
 			// profiles/r07_dead_time.txt.  The lanes left out keep the value they had, which `process` does not look at.
-			const bool wanted = ((lane / (uint32_t)RB) == bi) & !from_right & !(MC33_DEBUG_BITS(a) & 64u);
+			const bool wanted = ((lane / (uint32_t)RB) == bi) & !from_right & !(MC33_DEBUG_BITS(a) & 64u) & (hcode == 0u);  // (BS: a dead halo block is no load at all)
 			if (wanted) hv = MC33_LOAD(rs, xh, 0u);
 		} else
 		hv = MC33_LOAD(rs, ((lane / (uint32_t)RB) == bi && !from_right && !(MC33_DEBUG_BITS(a) & 64u)) ? xh : 0xFFFFFFF0u, 0u);
@@ -638,12 +749,28 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 	// compiler made a real FUNCTION of it, every captured array behind a pointer into 1.5 KiB of scratch memory per lane)
 	auto process = [&](const raw_t (&dd)[16], const real_t &hv, uint32_t p, uint32_t bi) __attribute__((always_inline)) {
 		const uint32_t r = bi * (uint32_t)RB;
+		uint32_t codes = 0u;  // (BS) as in `issue`, of the plane being processed
+		if constexpr (BS) {
+			constexpr real_t INF = std::numeric_limits<real_t>::infinity();
+			codes = (uint32_t)(bwp >> (8u * (bi >> 2))) & 0xFFu;
+			const uint32_t hcode = (uint32_t)(bwp >> (32u + 2u * (bi >> 2))) & 3u;
+			const real_t hsub = hcode == 1u ? -INF : INF;
+			halo = (lane / (uint32_t)RB) == bi ? (hcode ? hsub : hv) : halo;
+		} else
 		halo = (lane / (uint32_t)RB) == bi ? hv : halo;
 		unrolled_for<RB, (S >= 4)>([&](auto rc) __attribute__((always_inline)) {
 			const int rr = rc;
 			real_t f[4];
 #pragma unroll
 			for (int k = 0; k < 4; k++) f[k] = sample(dd, rr, k);
+			if constexpr (BS) {
+				constexpr real_t INF = std::numeric_limits<real_t>::infinity();
+#pragma unroll
+				for (int k = 0; k < 4; k++) {
+					const uint32_t ck = (codes >> (2 * k)) & 3u;  // (wave-uniform)
+					f[k] = ck ? (ck == 1u ? -INF : INF) : f[k];
+				}
+			}
 			uint64_t bwq[NI][4];  // (NI >= 2: the ballots of the row for all isovalues, parked two isovalues per EXEC switch)
 			static_for<NI>([&](auto qc) __attribute__((always_inline)) {
 				constexpr int q = decltype(qc)::value;
@@ -848,8 +975,9 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 	real_t hA = 0, hB = 0;
 	uint32_t ip = pl0, ib = 0, pp = pl0, pb = 0;  // (plane, batch) of the next issue / of the next process
 	// past the end of the tile the prefetch simply re-reads the last batch (it is never processed)
-#define MC33_ADV(p_, b_) do { if (++(b_) == NB) { (b_) = 0; ++(p_); } } while (0)
-#define MC33_ADV_ISSUE() do { if (ip != z_hi || ib + 1 != NB) MC33_ADV(ip, ib); } while (0)
+	// (BS: a new plane takes the word that was asked for when the plane before it began, and asks for the next one)
+#define MC33_ADV(p_, b_, w_, wn_) do { if (++(b_) == NB) { (b_) = 0; ++(p_); if constexpr (BS) { (w_) = (wn_); (wn_) = block_word((p_) + 1u); } } } while (0)
+#define MC33_ADV_ISSUE() do { if (ip != z_hi || ib + 1 != NB) MC33_ADV(ip, ib, bwi, bwi_n); } while (0)
 	// (Tried in round 3: the loads that refill a buffer issued as soon as its rows are bit rows, BEFORE the work on a complete
 	// plane, so that two batches stay in flight during that work and a hand-over's stores are younger than the refill.  The
 	// refill's registers are then live across the plane's work: 92 -> 134 VGPRs for one isovalue per pass = 3 waves per SIMD
@@ -875,9 +1003,9 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 #endif
 	for (uint32_t t = 0; t < T; t += 2) {
 		issue(dB, hB, ip, ib); MC33_ADV_ISSUE();
-		process(dA, hA, pp, pb); MC33_ADV(pp, pb);
+		process(dA, hA, pp, pb); MC33_ADV(pp, pb, bwp, bwp_n);
 		issue(dA, hA, ip, ib); MC33_ADV_ISSUE();
-		if (t + 1 < T) { process(dB, hB, pp, pb); MC33_ADV(pp, pb); }
+		if (t + 1 < T) { process(dB, hB, pp, pb); MC33_ADV(pp, pb, bwp, bwp_n); }
 	}
 	log_flush();  // (DEFER: everything the tile hands on, behind its last load)
 	if constexpr (NI >= 2) {
@@ -900,6 +1028,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 template <int S, int NI, int ZM = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_sweep_live(const SweepArgs a) {
 	sweep_tile<S, NI, ZM, 2>(a);
+}
+// ... and leaves the dead blocks of its live tiles out (SweepArgs::blockw; sweep_tile: BS)
+template <int ZM = 0>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_sweep_live_blocks(const SweepArgs a) {
+	if constexpr (MC33_BLOCK_SKIP) sweep_tile<1, 1, ZM, 2, true>(a);
 }
 template <int S, int NI, int ZM = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_sweep_all(const SweepArgs a) {
