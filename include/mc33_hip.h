@@ -150,8 +150,13 @@ int mc33hip_alias_cells(mc33hip_ctx *c, unsigned long long *out);
  * explicit MC33_HIP_RZ or MC33_HIP_RZ_TABLE (a depth in planes) switches the sizing off.  Precedence: MC33_HIP_RZ alone makes the
  * plans with and without a table one plan of that depth, and nothing else is looked at; otherwise MC33_HIP_TABLE_TILES, a switch
  * for tests and curves, comes before MC33_HIP_RZ_TABLE and holds for grids of less than one round too; then MC33_HIP_RZ_TABLE; then
- * the sizing.  MC33_HIP_LIST_LDS=0 (tests): k_live_compact keeps the places of its quads in memory, as for plans above 4 096 blocks. */
+ * the sizing.  MC33_HIP_LIST_LDS=0 (tests): k_live_compact keeps the places of its quads in memory, as for plans above 4 096 blocks.
+ * mc33hip_sweep_plan_weight: the weight of a plane, in batches of sample rows, that the columns of the plan in force were cut
+ * with - 0: by batches alone, as every plan but the sized plan of a single-isovalue sweep that leaves blocks out.
+ * MC33_HIP_PLANE_WEIGHT=<w> in the environment when a context is created: that weight in place of the measured one (curves,
+ * tests); 0: none. */
 int mc33hip_sweep_plan(mc33hip_ctx *c, unsigned int *tiles_out, size_t cap_tiles, unsigned long long info[3]);
+int mc33hip_sweep_plan_weight(mc33hip_ctx *c, double *weight_out);
 int mc33hip_sweep_live(mc33hip_ctx *c, unsigned int *live_out, size_t cap_entries, unsigned long long info[2]);
 int mc33hip_sweep_packed(mc33hip_ctx *c, unsigned int *out, size_t cap_entries, unsigned long long info[3]);
 

@@ -259,7 +259,7 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_resampled_size", "mc33hip_resample_grid", "mc33hip_context_device", "mc33hip_grid_spectrum",
            "mc33hip_clip_surface", "mc33hip_section_surface", "mc33hip_section_contours", "mc33hip_section_ladder",
            "mc33hip_grid_stable", "mc33hip_grid_changed", "mc33hip_range_table", "mc33hip_sweep_skipped",
-           "mc33hip_sweep_plan", "mc33hip_sweep_live", "mc33hip_sweep_packed", "mc33hip_range_blocks", "mc33hip_block_words",
+           "mc33hip_sweep_plan", "mc33hip_sweep_plan_weight", "mc33hip_sweep_live", "mc33hip_sweep_packed", "mc33hip_range_blocks", "mc33hip_block_words",
            "mc33hip_alias_cells", "mc33hip_sweep_skipped_blocks", "mc33hip_curvature_vertices", "mc33hip_color_values",
            "mc33hip_cap_surface", "mc33hip_render_surface", "mc33hip_render_timing"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
@@ -385,6 +385,8 @@ def load_library(dtype="f32"):
         lib.mc33hip_sweep_live.argtypes = [V, V, C.c_size_t, P(C.c_ulonglong * 2)]
     if hasattr(lib, "mc33hip_sweep_packed"):
         lib.mc33hip_sweep_packed.argtypes = [V, V, C.c_size_t, P(C.c_ulonglong * 3)]
+    if hasattr(lib, "mc33hip_sweep_plan_weight"):
+        lib.mc33hip_sweep_plan_weight.argtypes = [V, P(C.c_double)]
     if hasattr(lib, "mc33hip_range_blocks"):
         lib.mc33hip_range_blocks.argtypes = [V, V, C.c_size_t]
         lib.mc33hip_block_words.argtypes = [V, V, C.c_size_t]

@@ -72,6 +72,7 @@ struct IsoLane {
 	uint32_t pack;            // samples per lane and load of the sweep that filled it (lane_of_column)
 	int plan;                 // the plan (mc33hip_ctx::plan) that sweep went by: its edge records are indexed by that plan's tiles ...
 	uint32_t plan_target;     // ... and the tile count plan 1 had been asked for (SweepPlan::target): number and target make the plan again
+	double plan_weight;       // ... and the weight of a plane it was cut with (SweepPlan::weight)
 	int many_pass, many_ni;   // which pass of mc33hip_sweep_many filled it (its events), and how many isovalues that pass classified
 };
 
@@ -83,6 +84,7 @@ struct SweepPlan {
 	uint64_t tiles_cap, ntiles, nbounds;
 	uint32_t zs, ze, depth;
 	uint32_t target;          // plan 1: the tile count it was asked for in place of a depth (table_retarget), 0: by its depth
+	double weight;            // ... and the weight of a plane in batches its columns were cut by (plan_sweep), 0: by batches alone
 };
 
 // Everything a tail (k_slots ... k_scan_apply) writes and the emit passes read, for ONE isovalue.  Lane k of the sweep buffers
@@ -194,6 +196,7 @@ struct mc33hip_ctx {
 	bool blocks_made;         // the last k_ranges wrote the block table too
 	bool blocks_off;          // MC33_HIP_BLOCKS=0: no block table, no block left out (read at create)
 	bool blocks_always;       // MC33_HIP_BLOCKS=1: blocks are left out wherever a sweep goes by a list; not set: where it pays (launch_sweep_zm)
+	double plane_weight;      // the weight of a plane the sized plans of sweeps that leave blocks out are cut with (sweep_plane_weight; MC33_HIP_PLANE_WEIGHT, read at create, for curves: 0 none)
 	int cus;                  // compute units of the device
 	int emit_v_blocks_per_cu; // blocks of k_emit_vertices a CU holds
 	hipEvent_t ev[4];
@@ -243,6 +246,7 @@ static int prop_check(mc33hip_ctx *c);
 extern "C" const char *mc33hip_last_error(void) { return g_err; }
 static uint32_t env_u32(const char *name, uint32_t dflt);
 static uint32_t render_small_switch();
+static double plane_weight_switch();
 
 static int env_flag(const char *name) {  // -1: not set
 	const char *s = getenv(name);
@@ -412,6 +416,7 @@ extern "C" int mc33hip_create(mc33hip_ctx **out, const mc33hip_grid_desc *d) {
 	c->ranges_off = env_flag("MC33_HIP_RANGES") == 0;
 	c->blocks_off = env_flag("MC33_HIP_BLOCKS") == 0;
 	c->blocks_always = env_flag("MC33_HIP_BLOCKS") == 1;
+	c->plane_weight = plane_weight_switch();
 	CREATE_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
 	CREATE_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
 	CREATE_TRY(hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming));

@@ -137,17 +137,40 @@ static double sweep_unit(const mc33hip_ctx *c, uint32_t zs, uint32_t ze) {
 // sum is no whole number of rounds: dead tiles cost nothing.  A sized plan has a slot of its own, number 2 (c->plan[2]; `which` 1
 // with a target, or 2), so that a caller who mixes single-isovalue calls (sized) with passes over several isovalues (the default
 // depth, slot 1) has both resident and makes neither again.  A lane keeps the slot and the target (IsoLane::plan, plan_target).
+// weight (sized plans only; 0: none): the weight of a plane in batches the columns are cut by (mc33_sweep_plan.h).  Equal numbers
+// of BATCHES per tile make equal lives while the batches carry a wave's life.  A sweep that leaves dead blocks out pays for a batch
+// of a dead quarter with no memory access, and what it does once per plane weighs about PLANE_WEIGHT_BLOCKS batches
+// (profiles/r12_plan_balance.txt A): cut by batches alone, the tiles of a short last y tile - 4 batches per plane where the others
+// have 16 - were four times as deep as the others and ended last, 246 us into a kernel whose median wave lived 159
+// (profiles/r11_block_skip.txt E).  So the share of a column of such a plan goes by batches + weight per plane; the sum stays the
+// target, and sweep_unit and table_target's cap stay counted in batches.  The weight is that of a single-isovalue sweep of a
+// context that leaves blocks out (sweep_plane_weight: decided by the build, MC33_HIP_BLOCKS and the width of the grid - things
+// fixed when the context is made, never by whether a block table happens to exist); every other plan, and every plan of the
+// double and integer libraries, is cut by batches as before.  It is part of what names a plan: a lane keeps it beside its target
+// (IsoLane::plan_weight), and it is compared wherever the target is.
 constexpr uint32_t SWEEP_DEPTH = 16u, SWEEP_DEPTH_TABLE = 5u;  // (measured, 1024^3 float: profiles/r09_sweep_refill.txt A, B)
-static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, int which, uint32_t target = 0u) {
+constexpr double PLANE_WEIGHT_BLOCKS = 3.0;  // b / a of k_sweep_live_blocks: 2.4 fitted on the plan cut by batches, 3.3 on one cut with 3 (profiles/r12_plan_balance.txt A)
+static double plane_weight_switch() {  // MC33_HIP_PLANE_WEIGHT, read when a context is created: for curves and tests; 0: plans are cut by batches alone
+	const char *s = getenv("MC33_HIP_PLANE_WEIGHT");
+	if (!s || !*s) return PLANE_WEIGHT_BLOCKS;
+	const double v = atof(s);
+	return v > 0.0 && v <= 1024.0 ? v : 0.0;
+}
+static double sweep_plane_weight(const mc33hip_ctx *c) {
+	if (!MC33_BLOCK_SKIP || c->blocks_off || !(c->blocks_always || c->P.nseg >= 4u)) return 0.0;
+	return c->plane_weight;
+}
+static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, int which, uint32_t target = 0u, double weight = 0.0) {
 	const Params &P = c->P;
 	if (c->sw.rz && !c->sw.rz_table) which = 0;
 	if (which == 2) which = 1;  // (a lane's slot: the plan with a table, sized - its target comes with it)
 	if (!which) target = 0u;
+	if (!target || !(weight > 0.0)) weight = 0.0;
 	const uint32_t depth = which ? (c->sw.rz_table ? c->sw.rz_table : SWEEP_DEPTH_TABLE) : (c->sw.rz ? c->sw.rz : SWEEP_DEPTH);
 	const int slot = (which && target) ? 2 : which;
 	SweepPlan &pl = c->plan[slot];
 	c->cur_plan = slot;
-	if (pl.d_tiles && pl.zs == zs && pl.ze == ze && pl.depth == depth && pl.target == target) return 0;
+	if (pl.d_tiles && pl.zs == zs && pl.ze == ze && pl.depth == depth && pl.target == target && pl.weight == weight) return 0;
 	if (!c->resident_blocks) {
 		int per_cu = 0, cus = 0;
 		HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sweep<1, 1>, 256, 0));
@@ -178,17 +201,10 @@ static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, int which, uint3
 	else if (pref >= (double)B) B *= (uint64_t)(pref / (double)B + 0.5);
 	else B = std::max<uint64_t>(1, std::min<uint64_t>(B, (uint64_t)(W * nzc / (64.0 * std::max(1u, c->sw.min_depth)))));  // small grid: fill the GPU, tiles down to one plane deep (k_boundary then does the slices)
 	std::vector<uint32_t> chunks(ncol);  // z pieces of the group (each is one tile per wave of the group)
-	std::vector<std::pair<double, uint64_t>> frac(ncol);
-	uint64_t total = 0;
-	for (uint64_t i = 0; i < ncol; i++) {
-		const double share = (double)B * w[i] / W;
-		const uint32_t n = (uint32_t)std::min<double>(std::max(1.0, std::floor(share)), (double)nzc);
-		chunks[i] = n; total += (uint64_t)n * waves[i];
-		frac[i] = {share - std::floor(share), i};
-	}
-	std::sort(frac.begin(), frac.end(), [](const std::pair<double, uint64_t> &x, const std::pair<double, uint64_t> &y) { return x.first > y.first; });
-	for (uint64_t k = 0; k < ncol && total < B; k++)
-		if (chunks[frac[k].second] < nzc) { chunks[frac[k].second]++; total += waves[frac[k].second]; }
+	std::vector<PlanFrac> frac(ncol);
+	if (weight > 0.0)  // (a plane's own cost on top of its batches: mc33_sweep_plan.h)
+		for (uint64_t i = 0; i < ncol; i++) w[i] = plan_column_weight(w[i], sweep_packed(c) ? 4u * (uint32_t)SWEEP_PACK : 4u, weight);
+	const uint64_t total = plan_shares(w.data(), waves.data(), ncol, B, nzc, chunks.data(), frac.data());
 	if (total > 0x3FFFFFFFull) { set_err("grid too large for one launch"); return MC33HIP_EINVAL; }
 	struct Planned { SweepTile t; uint64_t col; };  // col: the wave's column (yt, seg)
 	std::vector<Planned> planned;
@@ -229,10 +245,10 @@ static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, int which, uint3
 		if (int rc = dev_room("tile boundaries", &pl.d_bounds, &pl.nbounds, bounds.size())) return rc;
 		HIP_TRY(hipMemcpy(pl.d_bounds, bounds.data(), bounds.size() * sizeof(TileBoundary), hipMemcpyHostToDevice));
 	}
-	pl.zs = zs; pl.ze = ze; pl.depth = depth; pl.target = target;
+	pl.zs = zs; pl.ze = ze; pl.depth = depth; pl.target = target; pl.weight = weight;
 	if (c->sw.verbose)
-		fprintf(stderr, "[mc33hip] sweep plan %d: %llu wave tiles (%u resident, %u asked for), %llu columns, depth %.1f\n", slot, (unsigned long long)pl.ntiles,
-		        c->resident_blocks * 4, target, (unsigned long long)nYT * P.nseg, (double)nzc * nYT * P.nseg / (double)pl.ntiles);
+		fprintf(stderr, "[mc33hip] sweep plan %d: %llu wave tiles (%u resident, %u asked for, plane weight %.2f), %llu columns, depth %.1f\n", slot, (unsigned long long)pl.ntiles,
+		        c->resident_blocks * 4, target, weight, (unsigned long long)nYT * P.nseg, (double)nzc * nYT * P.nseg / (double)pl.ntiles);
 	return 0;
 }
 
@@ -277,6 +293,7 @@ static int begin_lane(mc33hip_ctx *c, IsoLane &L, const SlotGeom &g, hipStream_t
 			return rc;
 	L.plan = c->cur_plan;
 	L.plan_target = c->plan[c->cur_plan].target;
+	L.plan_weight = c->plan[c->cur_plan].weight;
 	const uint64_t nchunks = (L.slice_cap + SLOT_CHUNK - 1) / SLOT_CHUNK;  // (capacity: the halves keep their place)
 	if (++L.epoch >= c->epoch_wrap) {  // stamps wrap: start over with clean headers AND clean partial sums - the call before
 		// accumulated into the half an odd epoch selects and cleared only the other one, and epoch 1 is odd again
@@ -404,10 +421,24 @@ static int table_plan(mc33hip_ctx *c) {
 // Two calls in a row have to ask for about the same size (5 %) before the plan is replaced: a caller that moves between isovalues
 // with very different live shares would otherwise pay for a new plan in every call - 0.31 -> 0.52 ms per count at 1024^3 with the
 // isovalues 0 and 1.5 alternated (profiles/r10_sweep_pack.txt F) - and now stays on the plan it has.
+// Those constants hold for plans cut by batches alone and for every context whose residency is forced.  Cut to the batches of a
+// full y tile, the tiles of a short last one are several times as many planes deep, and with blocks left out a plane costs about
+// three batches' worth of time whatever its rows (plan_sweep): they ended last.  A plan cut with that weight has no such tail and
+// gains most right below one round, so it goes by a second fill and band (TABLE_FILL_BALANCED below; table_band in
+// mc33_sweep_plan.h makes the choice).  (The sizes at 0.75 - 0.81 of a round are still 0.01 ms behind 0.68 with the balanced cut,
+// profiles/r12_plan_balance.txt B: the deep tiles were not the whole of that loss.)
 // Only the single-isovalue calls are sized (enqueue_count).  The passes of mc33hip_sweep_many / mc33hip_prepare_many go by the
 // default depth: their forms over several isovalues hold three blocks per CU, not four, a tile is live when ANY of its isovalues
 // cuts it, and sized by this rule c5 (2048 x 2048 x 1024 ushort, 8 isovalues) was 5 % slower (r10 F).
 constexpr double TABLE_FILL = 0.68, TABLE_BAND_LO = 0.62, TABLE_BAND_HI = 0.72, TABLE_MIN_DEPTH = 3.0;
+// Plans cut with a plane weight (plan_sweep), at the device's own residency: read off profiles/r12_plan_balance.txt B.  With the cut
+// balanced the step falls all the way to one round: 0.525 ms at 0.69 of a round, 0.516 - 0.523 between 0.86 and 0.97, and 0.493 -
+// 0.501 on the three sizes between 0.978 and 0.996 (11 200 - 11 400 tiles; parents 0.559 - 0.570, noise 0.008) - the widest run
+// within the noise of the best, so the band is that run and the fill its centre.  Past one round (1.01) the step is 0.539: worse
+// than the best by 0.045 and than 0.69 of a round by 0.013, still ahead of the parent.  A plan that misses the band on either side
+// is sized again by the next two calls; hi stays below 1 (table_keeps).  The curve was measured at four blocks per compute unit
+// and nowhere else: a context whose residency is forced (MC33_HIP_SWEEP_BLOCKS_PER_CU) keeps the constants above (table_band).
+constexpr double TABLE_FILL_BALANCED = 0.987, TABLE_BAND_BALANCED_LO = 0.978, TABLE_BAND_BALANCED_HI = 0.997;
 static void table_retarget(mc33hip_ctx *c, uint32_t zs, uint32_t ze) {
 	if (c->sw.table_tiles) { c->table_target = c->sw.table_tiles; return; }
 	if (c->sw.rz || c->sw.rz_table || !c->h_live || !c->resident_blocks || ze <= zs) return;
@@ -422,9 +453,12 @@ static void table_retarget(mc33hip_ctx *c, uint32_t zs, uint32_t ze) {
 	}
 	// (the word is read as it stands: its count may be of the plan before the one in force)
 	const SweepPlan &pl = c->plan[c->table_target ? 2 : 1];
-	const uint64_t cur = (pl.d_tiles && pl.zs == zs && pl.ze == ze && pl.target == c->table_target) ? pl.ntiles : tiles;
-	if (table_keeps(live * cur / tiles, c->resident_blocks, TABLE_BAND_LO, TABLE_BAND_HI)) { c->table_pending = 0u; return; }
-	const uint32_t t = table_target(live, tiles, c->resident_blocks, unit, min_depth, TABLE_FILL);
+	const double weight = sweep_plane_weight(c);
+	const uint64_t cur = (pl.d_tiles && pl.zs == zs && pl.ze == ze && pl.target == c->table_target && (!c->table_target || pl.weight == weight)) ? pl.ntiles : tiles;
+	const TableBand band = table_band(weight, c->sw.sweep_blocks_per_cu != 0u, TableBand{TABLE_FILL, TABLE_BAND_LO, TABLE_BAND_HI},
+	                                  TableBand{TABLE_FILL_BALANCED, TABLE_BAND_BALANCED_LO, TABLE_BAND_BALANCED_HI});
+	if (table_keeps(live * cur / tiles, c->resident_blocks, band.lo, band.hi)) { c->table_pending = 0u; return; }
+	const uint32_t t = table_target(live, tiles, c->resident_blocks, unit, min_depth, band.fill);
 	if (!t || t == c->table_target) { c->table_pending = 0u; return; }
 	if (!c->table_pending || std::fabs((double)t - (double)c->table_pending) > 0.05 * (double)c->table_pending) { c->table_pending = t; return; }  // (a second call has to agree)
 	c->table_pending = 0u;
@@ -552,7 +586,7 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 	hipStream_t st = c->stream;
 	const uint32_t ze = c->range.z_end;
 	// (the lanes of a call were swept by one pass, so by one plan: the one their edge records are paired by)
-	if (int rc = plan_sweep(c, c->P.zs, ze, c->lanes[idx[0]].plan, c->lanes[idx[0]].plan_target)) return rc;
+	if (int rc = plan_sweep(c, c->P.zs, ze, c->lanes[idx[0]].plan, c->lanes[idx[0]].plan_target, c->lanes[idx[0]].plan_weight)) return rc;
 	const SweepPlan &pl = c->plan[c->cur_plan];
 	SweepArgs a;
 	sweep_args(c, g, a);
@@ -697,7 +731,7 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 				// (the plan it was swept by is looked at, not put in force: when its place holds another range's plan by now, the tail
 				// makes it again - the same plan, which the lane's edge buffers had room for)
 				const SweepPlan &lp = c->plan[c->lanes[k].plan];
-				if (lp.d_tiles && lp.zs == P.zs && lp.ze == c->range.z_end && lp.target == c->lanes[k].plan_target && c->lanes[k].edge_cap < lp.ntiles) continue;
+				if (lp.d_tiles && lp.zs == P.zs && lp.ze == c->range.z_end && lp.target == c->lanes[k].plan_target && lp.weight == c->lanes[k].plan_weight && c->lanes[k].edge_cap < lp.ntiles) continue;
 				L = &c->lanes[k];
 				tail_made = L->tail_done;
 			}
@@ -712,7 +746,7 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 		L = &c->lanes[0];
 		const RangeEntry *ranges = sweep_ranges(c, st);
 		table_retarget(c, P.zs, c->range.z_end);
-		if (int rc = plan_sweep(c, P.zs, c->range.z_end, ranges ? table_plan(c) : 0, c->table_target)) return rc;
+		if (int rc = plan_sweep(c, P.zs, c->range.z_end, ranges ? table_plan(c) : 0, c->table_target, sweep_plane_weight(c))) return rc;
 		if (int rc = begin_lane(c, *L, g, st)) return rc;
 		c->lane_presweeped = false;
 		SweepArgs a;
@@ -1461,6 +1495,13 @@ extern "C" int mc33hip_sweep_plan(mc33hip_ctx *c, unsigned int *tiles_out, size_
 	if (int rc = use_device(c)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	HIP_TRY(hipMemcpy(tiles_out, pl.d_tiles, pl.ntiles * sizeof(SweepTile), hipMemcpyDeviceToHost));
+	return MC33HIP_OK;
+}
+extern "C" int mc33hip_sweep_plan_weight(mc33hip_ctx *c, double *out) {
+	if (!c || !out) return MC33HIP_EINVAL;
+	const SweepPlan &pl = c->plan[c->cur_plan];
+	if (!pl.d_tiles || !pl.ze) { set_err("no sweep plan yet"); return MC33HIP_EINVAL; }
+	*out = pl.weight;
 	return MC33HIP_OK;
 }
 extern "C" int mc33hip_sweep_packed(mc33hip_ctx *c, unsigned int *out, size_t cap_entries, unsigned long long *info /*[3]*/) {
