@@ -383,6 +383,24 @@ void MC33_free_image(mc33_image *image);
 int MC33_view_fit(MC33 *extractor, const double dir[3], const double up[3], double fov_degrees, unsigned width, unsigned height, mc33_view *out);
 int MC33_write_image_ppm(const mc33_image *image, const char *filename);
 
+/* extension (not in the reference): how far two surfaces are from each other, taken on the device - the nearest triangle of one for
+ * every vertex of the other.  The surfaces stay in device memory; a few numbers come back.  The exact definition is in mc33_hip.h
+ * (mc33hip_surface_distance); the distance is a property of V and T alone, so inclined grids are accepted.
+ * MC33_isosurface_distance: the vertices of the surface of iso_from against the triangles of the surface of iso_to, of the same
+ * grid - the thickness of the shell between two isovalues, seen from the first.
+ * MC33_simplification_error: what MC33_calculate_simplified_isosurface(iso, s) gives away - out[0] the simplified surface's vertices
+ * against the full surface, out[1] the full surface's vertices against the simplified one.  Orthogonal grids only, as the
+ * simplification itself.
+ * Both are SAMPLED AT VERTICES: the interior of a coarse triangle can be farther from the other surface than any of its corners.
+ * points: the vertices with a nearest triangle; unmatched: those without (a coordinate that is not finite); max, min, mean, rms over
+ * the former; argmax: the first vertex that attains max.
+ * 0; -1 when refused - a null pointer, parameters the simplification refuses, an extractor spread over several devices - with the
+ * extractor untouched, or when the device fails; -2 when either surface is empty, with out zeroed.  Both set the extractor's iso
+ * and leave nV, nT and memoryfault alone, as the measuring calls do. */
+typedef struct { unsigned long long points, unmatched; double max, min, mean, rms; unsigned argmax; } mc33_distance;
+int MC33_isosurface_distance(MC33 *extractor, MC33_real iso_from, MC33_real iso_to, mc33_distance *out);
+int MC33_simplification_error(MC33 *extractor, MC33_real isovalue, const mc33_simplification *s, mc33_distance out[2]);
+
 /* extension (not in the reference): the section of an isosurface by a plane - the outline a viewer draws over a slice image, its
  * length, the area it encloses, and the same along a stack of parallel planes: the cross-sectional area profile of a vessel, a
  * bone or a pore.  The surface stays in device memory; only the outline, or a few numbers per plane, come back.  plane[4] = a, b,

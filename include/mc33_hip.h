@@ -975,6 +975,81 @@ int mc33hip_render_surface(mc33hip_ctx *c, mc33hip_rendering *a);
  * mc33hip_render_surface call - clear, vertex pass, triangle pass, scan of the list, tiled pass, resolve; MC33HIP_EINVAL otherwise. */
 int mc33hip_render_timing(mc33hip_ctx *c, float ms[6]);
 
+/* --- distance between surfaces on the device: the nearest triangle per point (no counterpart in the reference) ---------------------
+ * Query points P (nP x 3 MC33_real) and a target mesh V (nV x 3 MC33_real), T (nT x 3 unsigned, id base 0), all in device memory.
+ * For every point the nearest point of the mesh: how far a simplified, smoothed or clipped surface has moved from the one it came
+ * from, how thick the shell between two isovalues is, which triangle is nearest to a probe.  The call reads only these arrays: an
+ * inclined context and a z-slab context are accepted.  Arithmetic is IEEE double, nothing fused; a dot product x . x' is
+ * (x*x' + y*y') + z*z'.  The result is an exact function of the input - it does not depend on how the triangles are searched - and
+ * two calls return the same bytes.  tests/distance_oracle.py restates the definition over all pairs.
+ *   usable triangle   its three indices are below nV and its nine coordinates are finite.  A triangle with an index >= nV counts in
+ *                     invalid_triangles and nothing outside V is read; a valid triangle with a coordinate that is not finite counts
+ *                     in nonfinite_triangles - a statistic, not an error.  Neither kind takes part in the search.
+ *   q_i(p)            the closest point of usable triangle i with corners a, b, c (rows of V as doubles): the region walk of Ericson,
+ *                     Real-Time Collision Detection 5.1.5, in this order and with these comparisons:
+ *                       ab = b-a; ac = c-a; ap = p-a; d1 = ab.ap; d2 = ac.ap;
+ *                           if (d1 <= 0 && d2 <= 0) q = a;
+ *                       else bp = p-b; d3 = ab.bp; d4 = ac.bp;
+ *                           if (d3 >= 0 && d4 <= d3) q = b;
+ *                       else vc = d1*d4 - d3*d2;
+ *                           if (vc <= 0 && d1 >= 0 && d3 <= 0) { v = d1/(d1-d3); q = a + v*ab; }
+ *                       else cp = p-c; d5 = ab.cp; d6 = ac.cp;
+ *                           if (d6 >= 0 && d5 <= d6) q = c;
+ *                       else vb = d5*d2 - d1*d6;
+ *                           if (vb <= 0 && d2 >= 0 && d6 <= 0) { w = d2/(d2-d6); q = a + w*ac; }
+ *                       else va = d3*d6 - d5*d4;
+ *                           if (va <= 0 && (d4-d3) >= 0 && (d5-d6) >= 0) { w = (d4-d3)/((d4-d3)+(d5-d6)); q = b + w*(c-b); }
+ *                       else { den = 1.0/((va+vb)+vc); v = vb*den; w = vc*den; q = (a + ab*v) + ac*w; }
+ *                     then per axis, with lo / hi the smallest / largest of the three corners (lo = a; if (b < lo) lo = b; if (c < lo)
+ *                     lo = c; hi likewise with >):  if (!(q >= lo)) q = lo;  if (!(q <= hi)) q = hi;
+ *                     The clamp is part of the definition.  It does nothing on a sane triangle; on a sliver whose den is garbage q
+ *                     still lies in the triangle's box and is never NaN, which is what the search's pruning rests on.
+ *   D2_i              e = p - q;  D2_i = (e.x*e.x + e.y*e.y) + e.z*e.z.
+ *   winner for p      triangle i beats the best so far when D2_i < best, or D2_i == best and i < best_i: the smallest D2 over all
+ *                     usable triangles, ties to the smallest index.  A NaN or infinite D2 never wins; a point with a coordinate that
+ *                     is not finite has no winner, and neither has any point when no triangle is usable.
+ *   oDist[p]          (float)sqrt(D2); with signed_distance != 0 negated when e . (ab x ac) < 0 for the winning triangle, the cross
+ *                     product taken component-wise as y*z' - z*y' etc.  Near an edge or a corner of the mesh the sign is only as good
+ *                     as the winning triangle's plane: it is the side of THAT plane p lies on, not an inside / outside test.
+ *   oTri[p]           the winner's index;   oPoint[p] (3 MC33_real): the winner's q, converted.
+ *                     Without a winner: +inf, 0xFFFFFFFF and three quiet NaN (0x7FC00000 / 0x7FF8000000000000); the point counts in
+ *                     unmatched_points.  Each of the three pointers may be NULL.
+ *   filled            over matched points only: matched_points, unmatched_points; max and min - sqrt of the largest / smallest
+ *                     winning D2, unsigned even with signed_distance; argmax and argmin - the smallest point index that attains
+ *                     them; sum (of sqrt(D2)) and sum_sq (of D2), accumulated in double in a fixed order without floating-point
+ *                     atomics: two calls on one context return the same bits.  All six are 0 when no point is matched.
+ *                     lattice[3] and triangle_tests: the cells per axis the search used and the point-triangle evaluations it made -
+ *                     implementation statistics, outside the definition.
+ *   MC33HIP_ERUNTIME   invalid triangles: the count is in mc33hip_last_error, in the words of the measuring calls; the outputs are
+ *                      complete without them.
+ *   MC33HIP_EINVAL     checked on the host, nothing is written: a null P, V or T where its size is not zero; nP, nV or nT above
+ *                      2^32-1; an output byte range (nP rows) that meets an input range or another output range.
+ *   MC33HIP_ENOMEM     the scratch cannot be had.
+ *   nP == 0 or nT == 0 is success; in the latter case every point is unmatched.
+ * The search is a uniform lattice over the box of the usable triangles, made anew by every call: a list of triangles per cell, and
+ * per point shells of cells of growing radius until a lower bound on everything not yet visited exceeds the point's best (DESIGN.md
+ * 25).  The call enqueues on the context's stream behind whatever is on it, waits for the box and for the size of the lists, and a
+ * last time for the summary.  Scratch, with the context until mc33hip_destroy: 8 bytes per lattice cell (at most 256 cells per axis),
+ * 4 bytes per list entry, 8 bytes per point.  MC33_HIP_DISTANCE_CELLS=<n>, read when the context is created, forces n cells on every
+ * axis of the lattice (within the library's own limits; 1: every point tests every triangle); the bytes are the same in every
+ * setting.
+ * Out of scope: distance fields on the grid, a lattice kept between calls, samples inside the query mesh's triangles. */
+typedef struct {
+	const void *P;  unsigned long long nP;                   /* in (device): nP x 3 MC33_real */
+	const void *V, *T;  unsigned long long nV, nT;           /* in (device): nV x 3 MC33_real, nT x 3 unsigned, id base 0 */
+	int signed_distance;
+	float *oDist;  unsigned *oTri;  void *oPoint;            /* out (device), nP rows each, or NULL */
+	unsigned long long matched_points, unmatched_points, invalid_triangles, nonfinite_triangles;   /* filled */
+	double max, min, sum, sum_sq;
+	unsigned long long argmax, argmin;
+	unsigned lattice[3];
+	unsigned long long triangle_tests;
+} mc33hip_distance;
+int mc33hip_surface_distance(mc33hip_ctx *c, mc33hip_distance *a);
+/* Developer timing: with MC33_HIP_TIMING >= 2 when the context is created, hipEvent times in ms of the passes of the last
+ * mc33hip_surface_distance call - build (box, count, scan, fill), query, reduce; MC33HIP_EINVAL otherwise. */
+int mc33hip_distance_timing(mc33hip_ctx *c, float ms[3]);
+
 /* --- curvature of the implicit surface at the vertices, from the grid's second differences (no counterpart in the reference) ------
  * Mean, Gaussian and principal curvatures of the surface F = iso at nV vertices dV (nV x 3 MC33_real in device memory, what
  * mc33hip_emit wrote, or any points), taken from the gradient g and the Hessian H of the RESIDENT grid - the curvature of the field's

@@ -5,6 +5,7 @@ inside libMC33_{f32,f64,u8,u16,u32}.so (one library per grid sample type).  Ther
 missing, and every call into it fails loudly when no GPU is present.
 """
 import ctypes as C
+import math
 import os
 
 PKG = os.path.dirname(os.path.abspath(__file__))
@@ -155,6 +156,25 @@ class Rendering(C.Structure):
                [(n, C.c_ulonglong) for n in ("drawn", "culled", "degenerate", "rejected", "offscreen", "invalid_triangles", "fragments", "covered")]
 
 
+class Distance(C.Structure):
+    """mc33hip_distance (include/mc33_hip.h)"""
+    _fields_ = [("P", C.c_void_p), ("nP", C.c_ulonglong), ("V", C.c_void_p), ("T", C.c_void_p), ("nV", C.c_ulonglong), ("nT", C.c_ulonglong),
+                ("signed_distance", C.c_int), ("oDist", C.c_void_p), ("oTri", C.c_void_p), ("oPoint", C.c_void_p)] + \
+               [(n, C.c_ulonglong) for n in ("matched_points", "unmatched_points", "invalid_triangles", "nonfinite_triangles")] + \
+               [(n, C.c_double) for n in ("max", "min", "sum", "sum_sq")] + [("argmax", C.c_ulonglong), ("argmin", C.c_ulonglong)] + \
+               [("lattice", C.c_uint * 3), ("triangle_tests", C.c_ulonglong)]
+
+
+class SurfaceDistance(C.Structure):
+    """mc33_distance (include/marching_cubes_33.h)"""
+    _fields_ = [("points", C.c_ulonglong), ("unmatched", C.c_ulonglong), ("max", C.c_double), ("min", C.c_double), ("mean", C.c_double), ("rms", C.c_double),
+                ("argmax", C.c_uint)]
+
+
+DISTANCE_FIELDS = ("matched_points", "unmatched_points", "invalid_triangles", "nonfinite_triangles", "max", "min", "sum", "sum_sq", "argmax", "argmin",
+                   "triangle_tests")
+
+
 class View(C.Structure):
     """mc33_view (include/marching_cubes_33.h): what DeviceGrid.render takes for its view, too"""
     _fields_ = [("m", C.c_double * 16), ("width", C.c_uint), ("height", C.c_uint), ("cull", C.c_int), ("two_sided", C.c_int),
@@ -261,7 +281,7 @@ HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_
            "mc33hip_grid_stable", "mc33hip_grid_changed", "mc33hip_range_table", "mc33hip_sweep_skipped",
            "mc33hip_sweep_plan", "mc33hip_sweep_plan_weight", "mc33hip_sweep_live", "mc33hip_sweep_packed", "mc33hip_range_blocks", "mc33hip_block_words",
            "mc33hip_alias_cells", "mc33hip_sweep_skipped_blocks", "mc33hip_curvature_vertices", "mc33hip_color_values",
-           "mc33hip_cap_surface", "mc33hip_render_surface", "mc33hip_render_timing"]
+           "mc33hip_cap_surface", "mc33hip_render_surface", "mc33hip_render_timing", "mc33hip_surface_distance", "mc33hip_distance_timing"]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -278,7 +298,8 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "MC33_section_isosurface", "MC33_free_section", "MC33_section_contours", "MC33_section_profile",
                  "MC33_set_color_source", "MC33_isosurface_curvature",
                  "MC33_calculate_capped_isosurface",
-                 "MC33_render_isosurface", "MC33_free_image", "MC33_view_fit", "MC33_write_image_ppm"]
+                 "MC33_render_isosurface", "MC33_free_image", "MC33_view_fit", "MC33_write_image_ppm",
+                 "MC33_isosurface_distance", "MC33_simplification_error"]
 
 
 class MC33Error(RuntimeError):
@@ -372,6 +393,9 @@ def load_library(dtype="f32"):
     if hasattr(lib, "mc33hip_render_surface"):
         lib.mc33hip_render_surface.argtypes = [V, P(Rendering)]
         lib.mc33hip_render_timing.argtypes = [V, P(C.c_float * 6)]
+    if hasattr(lib, "mc33hip_surface_distance"):
+        lib.mc33hip_surface_distance.argtypes = [V, P(Distance)]
+        lib.mc33hip_distance_timing.argtypes = [V, P(C.c_float * 3)]
     if hasattr(lib, "mc33hip_curvature_vertices"):
         lib.mc33hip_curvature_vertices.argtypes = [V, P(Curvature)]
         lib.mc33hip_color_values.argtypes = [V, V, C.c_ulonglong, P(C.c_int), C.c_uint, C.c_double, C.c_double, C.c_int, V]
@@ -1026,14 +1050,19 @@ class DeviceGrid:
                                                          C.c_void_p(N2.data_ptr())))
         return N2
 
-    def extract_smoothed(self, iso, rng=None, with_property=False, **smoothing):
+    def extract_smoothed(self, iso, rng=None, with_property=False, error=False, **smoothing):
         """extract, then smooth(**smoothing) in place - the surface never leaves the device.  Returns (V, N, T, Counts) with the
         smoothed vertices and their recomputed normals (the extracted N with normals=False) and, with with_property, the attached
-        property grid's value at the UNSMOOTHED vertices as a fifth element."""
+        property grid's value at the UNSMOOTHED vertices as a fifth element.  error=True: a dict `info` behind the Counts whose
+        "error" is surface_distance(smoothed, extracted) - how far the passes moved the surface; the extracted vertices are kept
+        in a second tensor for it."""
         got = self.extract(iso, rng, with_property)
         V, N, T, cnt = got[:4]
+        V0 = V.clone() if error else None
         V2, N2, _ = self.smooth(V, T, out=V, **smoothing)
         out = (V2, N2 if N2 is not None else N, T, cnt)
+        if error:
+            out = out + ({"error": self.surface_distance(V2, T, V0, T)},)
         return out + (got[4],) if with_property else out
 
     def smooth_timing(self):
@@ -1071,14 +1100,17 @@ class DeviceGrid:
         info["ratio"] = info["nT_out"] / T.shape[0] if T.shape[0] else 0.0
         return out + (info,)
 
-    def extract_simplified(self, iso, cell_in_grid_cells, rng=None, with_property=False, **kw):
+    def extract_simplified(self, iso, cell_in_grid_cells, rng=None, with_property=False, error=False, **kw):
         """extract, then simplify on the lattice of the grid - origin r0, cells of cell_in_grid_cells (a number or three) grid
         spacings - the whole surface never leaves the device.  Returns (V, N, T, info) and, with with_property, the attached
-        property grid's value at the first vertex of every kept cell as a fifth element.  **kw: mode, drop_duplicates."""
+        property grid's value at the first vertex of every kept cell as a fifth element.  **kw: mode, drop_duplicates.
+        error=True: info["error"] is surface_distance(simplified, extracted) - what the clustering gave away, both directions."""
         got = self.extract(iso, rng, with_property)
         c = (float(cell_in_grid_cells),) * 3 if not hasattr(cell_in_grid_cells, "__len__") else tuple(float(x) for x in cell_in_grid_cells)
         cell = tuple(c[k] * self.desc.d[k] for k in range(3))
         V2, N2, T2, attrs2, _, info = self.simplify(got[0], got[2], cell, attrs=(got[4],) if with_property else (), **kw)
+        if error:
+            info["error"] = self.surface_distance(V2, T2, got[0], got[2])
         out = (V2, N2, T2, info)
         return out + (attrs2[0],) if with_property else out
 
@@ -1221,6 +1253,56 @@ class DeviceGrid:
         rgba, depth, ids, info = self.render(V, N, T, colors(V) if colors is not None else None, view, want)
         info["nV"], info["nT"] = int(cnt.nV), int(cnt.nT)
         return rgba, depth, ids, info
+
+    # -- distance between surfaces on the device (mc33_hip.h: mc33hip_surface_distance) --------------------------------------------------
+    def distance(self, P, V, T, signed=False, nearest_point=False):
+        """For every point of P [p, 3] the nearest point of the mesh V [n, 3], T [m, 3] (device tensors, P and V of one dtype, as
+        extract() returns them).  Returns (dist, tri, point, info): dist float32 [p] - with signed=True negative behind the plane
+        of the nearest triangle, which near an edge is only as good as that plane -, tri int32 [p], the uint32 words of the nearest
+        triangle's index, point [p, 3] the nearest point itself (None without nearest_point), and a dict of the call's summary over
+        the matched points: matched_points, unmatched_points, invalid_triangles, nonfinite_triangles, max, min, argmax, argmin, sum,
+        sum_sq, mean, rms, and the search's own lattice and triangle_tests.  A point without a winner - not finite, or no usable
+        triangle - has +inf, -1 and NaN.  Raises MC33Error(ERUNTIME) when a triangle names a vertex >= n (the outputs are complete
+        without it)."""
+        import torch
+        self._vertex_rows(P)
+        self._vertex_rows(V)
+        self._triangle_rows(T)
+        assert P.dtype == V.dtype
+        nP = P.shape[0]
+        dist = torch.empty((max(nP, 1),), dtype=torch.float32, device=self.device)
+        tri = torch.empty((max(nP, 1),), dtype=torch.int32, device=self.device)
+        point = torch.empty((max(nP, 1), 3), dtype=P.dtype, device=self.device) if nearest_point else None
+        a = Distance()
+        a.P, a.nP, a.V, a.T, a.nV, a.nT = P.data_ptr(), nP, V.data_ptr(), T.data_ptr(), V.shape[0], T.shape[0]
+        a.signed_distance = int(bool(signed))
+        a.oDist, a.oTri, a.oPoint = dist.data_ptr(), tri.data_ptr(), (point.data_ptr() if nearest_point else None)
+        _check(self.lib, self.lib.mc33hip_surface_distance(self.ctx, C.byref(a)))
+        return dist[:nP], tri[:nP], (point[:nP] if nearest_point else None), self._distance_info(a)
+
+    @staticmethod
+    def _distance_info(a):
+        info = {n: getattr(a, n) for n in DISTANCE_FIELDS}
+        info["lattice"] = tuple(a.lattice)
+        m = info["matched_points"]
+        info["mean"] = info["sum"] / m if m else 0.0
+        info["rms"] = math.sqrt(info["sum_sq"] / m) if m else 0.0
+        return info
+
+    def surface_distance(self, V1, T1, V2, T2):
+        """How far two meshes are from each other, SAMPLED AT THEIR VERTICES ONLY: the vertices of V1 against the triangles of V2,
+        T2 ("forward") and the vertices of V2 against V1, T1 ("backward"), each the info dict of distance(), and "hausdorff", the
+        larger of the two max.  The interior of a coarse triangle can be farther from the other surface than any of its corners:
+        the figure is a lower bound of the true Hausdorff distance.  T1 itself is only the target of the backward direction:
+        vertices no triangle names count as points too."""
+        fwd, bwd = self.distance(V1, V2, T2)[3], self.distance(V2, V1, T1)[3]
+        return {"forward": fwd, "backward": bwd, "hausdorff": max(fwd["max"], bwd["max"])}
+
+    def distance_timing(self):
+        """hipEvent times in ms of the last distance() after set_timing(2): (build, query, reduce)."""
+        ms = (C.c_float * 3)()
+        _check(self.lib, self.lib.mc33hip_distance_timing(self.ctx, C.byref(ms)))
+        return tuple(ms)
 
     # -- section a finished mesh by planes on the device (mc33_hip.h: mc33hip_section_surface and its siblings) ----------------------
     def section(self, V, T, plane, attrs=(), attr_modes=()):

@@ -76,6 +76,7 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_clip_surface
 #pragma weak mc33hip_cap_surface
 #pragma weak mc33hip_render_surface
+#pragma weak mc33hip_surface_distance
 #pragma weak mc33hip_section_surface
 #pragma weak mc33hip_section_contours
 #pragma weak mc33hip_section_ladder
@@ -1413,6 +1414,69 @@ surface *MC33_calculate_simplified_isosurface(MC33 *M, MC33_real iso, const mc33
 	if (!simplification_ok(sp))
 		return 0; /* (what mc33hip_simplify_surface refuses, before anything is extracted) */
 	return derived_call(p, iso, simplified_surface, sp);
+}
+
+/* --- extension: the distance between two surfaces, taken on the device ------------------------------------------------------------
+ * Both surfaces in the two staging sets of the one slab; the vertices of one against the triangles of the other. */
+#define DISTANCE_ENTRIES (mc33hip_surface_distance != 0)
+
+static int distance_one(mc33_slab *s, const void *dP, unsigned long long nP, const struct staging *target, unsigned long long nV, unsigned long long nT,
+                        mc33_distance *out) {
+	mc33hip_distance a;
+	memset(&a, 0, sizeof a);
+	a.P = dP; a.nP = nP; a.V = target->dV; a.T = target->dT; a.nV = nV; a.nT = nT;
+	if (mc33hip_surface_distance(s->ctx, &a) != MC33HIP_OK)
+		return -1;
+	out->points = a.matched_points; out->unmatched = a.unmatched_points;
+	out->max = a.max; out->min = a.min;
+	out->mean = a.matched_points ? a.sum / (double)a.matched_points : 0.0;
+	out->rms = a.matched_points ? sqrt(a.sum_sq / (double)a.matched_points) : 0.0;
+	out->argmax = (unsigned)a.argmax;
+	return 0;
+}
+
+int MC33_isosurface_distance(MC33 *M, MC33_real iso_from, MC33_real iso_to, mc33_distance *out) {
+	mc33_private *p = one_slab(M, DISTANCE_ENTRIES);
+	if (!p || !out)
+		return -1;
+	mc33_slab *s = &p->slab[0];
+	mc33hip_counts from, to;
+	memset(out, 0, sizeof *out);
+	p->pub.iso = iso_to;
+	if (extract_geometry(p, &s->set[0], iso_from, &from) != MC33HIP_OK || extract_geometry(p, &s->set[1], iso_to, &to) != MC33HIP_OK)
+		return -1;
+	if (!from.nV || !from.nT || !to.nV || !to.nT)
+		return -2;
+	return distance_one(s, s->set[0].dV, from.nV, &s->set[1], to.nV, to.nT, out);
+}
+
+int MC33_simplification_error(MC33 *M, MC33_real iso, const mc33_simplification *sp, mc33_distance out[2]) {
+	mc33_private *p = one_slab(M, DISTANCE_ENTRIES && mc33hip_simplify_surface);
+	if (!p || !sp || !out || p->inclined || !simplification_ok(sp))
+		return -1;
+	mc33_slab *s = &p->slab[0];
+	struct staging *g = &s->set[0], *h = &s->set[1];
+	mc33hip_counts cnt;
+	memset(out, 0, 2 * sizeof *out);
+	p->pub.iso = iso;
+	if (extract_geometry(p, g, iso, &cnt) != MC33HIP_OK)
+		return -1;
+	mc33hip_simplification a;
+	memset(&a, 0, sizeof a);
+	a.V = g->dV; a.T = g->dT; a.nV = cnt.nV; a.nT = cnt.nT;
+	for (int j = 0; j != 3; j++) { a.origin[j] = p->grd_r0[j]; a.cell[j] = sp->cell[j] * p->grd_d[j]; }
+	a.mode = sp->mode; a.drop_duplicates = sp->drop_duplicates;
+	int rc;
+	INTO_STAGING(rc, mc33hip_simplify_surface, s, h, a);
+	if (rc != MC33HIP_OK)
+		return -1;
+	if (!cnt.nV || !cnt.nT || !a.nV_out || !a.nT_out)
+		return -2;
+	if (distance_one(s, h->dV, a.nV_out, g, cnt.nV, cnt.nT, &out[0]) || distance_one(s, g->dV, cnt.nV, h, a.nV_out, a.nT_out, &out[1])) {
+		memset(out, 0, 2 * sizeof *out);
+		return -1;
+	}
+	return 0;
 }
 
 /* --- extension: an isosurface clipped by planes --------------------------------------------------------------------------------

@@ -137,7 +137,8 @@ struct Switches {
 	uint32_t table_tiles;       // MC33_HIP_TABLE_TILES: the tile count plan 1 is asked for, whatever the sweeps find (the tests, the curve of profiles/r10_sweep_pack.txt)
 	uint32_t list_lds;          // MC33_HIP_LIST_LDS: plans of up to this many blocks keep the places of their quads in LDS (k_live_compact; 4096, the most; the tests set 0)
 	uint32_t render_small;      // MC33_HIP_RENDER_SMALL: the largest box of pixel centres one lane of k_render_triangles walks (mc33_render.hip.h; the tests set 0 and a huge value)
-	uint32_t pad_[1];           // (the words of five removed developer switches: with the context 24 bytes smaller, the C3 emit stage measured 4 us slower)
+	uint32_t distance_cells;    // MC33_HIP_DISTANCE_CELLS: cells per axis of the lattice of mc33hip_surface_distance, 0: it decides (mc33_distance.hip.h; the tests set 1 and a huge value;
+	                            //  the word was padding: with the context 24 bytes smaller, the C3 emit stage measured 4 us slower)
 };
 
 struct mc33hip_ctx {
@@ -246,6 +247,7 @@ static int prop_check(mc33hip_ctx *c);
 extern "C" const char *mc33hip_last_error(void) { return g_err; }
 static uint32_t env_u32(const char *name, uint32_t dflt);
 static uint32_t render_small_switch();
+static uint32_t distance_cells_switch();
 static double plane_weight_switch();
 
 static int env_flag(const char *name) {  // -1: not set
@@ -262,6 +264,7 @@ static void read_switches(Switches &w) {
 	w.trace_cells = getenv("MC33_HIP_TRACE_CELLS") ? strdup(getenv("MC33_HIP_TRACE_CELLS")) : nullptr;
 	w.trace_file = getenv("MC33_HIP_TRACE_FILE") ? strdup(getenv("MC33_HIP_TRACE_FILE")) : nullptr;
 	w.render_small = render_small_switch();
+	w.distance_cells = distance_cells_switch();
 	w.debug = env_u32("MC33_HIP_DEBUG", 0); w.cells_dev = env_u32("MC33_HIP_CELLS_DEV", 0);
 }
 static void forget_ranges(mc33hip_ctx *c) {  // the samples changed, or may have: no table until the second sweep from now

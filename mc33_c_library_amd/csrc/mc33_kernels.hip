@@ -68,6 +68,10 @@
 //                   screen record per vertex, a lane per triangle lowering 64-bit depth | id keys with atomicMin, a wave per screen tile
 //                   of the triangles too large for a lane, a lane per pixel to shade; k_render_triangles is its hot path
 //                   (mc33_render.hip.h).
+//                   k_dist_* - the nearest triangle of a finished V, T for each of many points: the box of the usable triangles, a
+//                   uniform lattice over it, a count, an exclusive scan and a fill of the cell lists, a lane per point visiting shells
+//                   of cells until a lower bound on the rest exceeds its best; k_dist_query is its hot path (mc33_distance.hip.h,
+//                   DESIGN.md 25).
 // Before an extraction: k_rs_resample - the resident grid into a second device grid, a separable correlation of up to 17 taps per axis
 //                   with an integer stride, one pass over the source: a block stages the rows its tile of outputs needs in LDS,
 //                   sums along x and y into a ring of planes and along z out of it (mc33_resample.hip.h).
@@ -140,6 +144,7 @@ typedef float sample_t;
 #include "mc33_smooth.hip.h"
 #include "mc33_cap.hip.h"
 #include "mc33_render.hip.h"
+#include "mc33_distance.hip.h"
 #include "mc33_simplify.hip.h"
 #include "mc33_clip.hip.h"
 #include "mc33_section.hip.h"

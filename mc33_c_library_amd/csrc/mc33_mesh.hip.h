@@ -269,7 +269,7 @@ struct MeshOp {
 	void (*release)(void *state);  // the device arrays the state holds; it is the key of the registration too
 };
 struct MeshHost {
-	MeshOp op[11];              // topology, filter, smooth, simplify, clip, resample, spectrum, section, curvature, cap, render: a part beyond that makes this larger
+	MeshOp op[12];              // topology, filter, smooth, simplify, clip, resample, spectrum, section, curvature, cap, render, distance: a part beyond that makes this larger
 	uint32_t nops;
 	// scratch no two parts use at once (every entry point waits before it returns), grown on demand by meas_room
 	uint8_t *d_keep;            // [nV] a flag per vertex: referenced, kept
