@@ -70,21 +70,17 @@ struct IsoLane {
 	double iso;
 	mc33hip_range range;
 	uint32_t pack;            // samples per lane and load of the sweep that filled it (lane_of_column)
-	int plan;                 // the plan (mc33hip_ctx::plan) that sweep went by: its edge records are indexed by that plan's tiles ...
-	uint32_t plan_target;     // ... and the tile count plan 1 had been asked for (SweepPlan::target): number and target make the plan again
-	double plan_weight;       // ... and the weight of a plane it was cut with (SweepPlan::weight)
+	PlanRef plan;             // the plan (slot of mc33hip_ctx::plan, target, weight) that sweep went by: its edge records are indexed by that plan's tiles
 	int many_pass, many_ni;   // which pass of mc33hip_sweep_many filled it (its events), and how many isovalues that pass classified
 };
 
 // A block plan of k_sweep (plan_sweep): the tiles, and the pairs of tiles that meet in z.  What a sweep leaves for k_boundary is indexed
-// by the tiles of the plan it went by, so a lane keeps the plan's number (IsoLane::plan) until its tail is made.
+// by the tiles of the plan it went by, so a lane keeps a PlanRef (IsoLane::plan) until its tail is made.
 struct SweepPlan {
 	SweepTile *d_tiles;
 	TileBoundary *d_bounds;   // (made to measure for every plan: nbounds is its capacity)
 	uint64_t tiles_cap, ntiles, nbounds;
-	uint32_t zs, ze, depth;
-	uint32_t target;          // plan 1: the tile count it was asked for in place of a depth (table_retarget), 0: by its depth
-	double weight;            // ... and the weight of a plane in batches its columns were cut by (plan_sweep), 0: by batches alone
+	PlanKey key;              // what names it (mc33_sweep_plan.h); ze == 0: not a plan
 };
 
 // Everything a tail (k_slots ... k_scan_apply) writes and the emit passes read, for ONE isovalue.  Lane k of the sweep buffers
@@ -175,10 +171,7 @@ struct mc33hip_ctx {
 	uint64_t verdict_cap, live_cap, packed_cap;
 	uint64_t live_blocks;     // blocks of the plan that sweep went by (0: no such sweep yet)
 	unsigned long long *h_live;  // pinned: what k_live_compact published last (live tiles << 32 | tiles << 1 | plan; 0: nothing yet)
-	uint32_t coarse_sweeps;   // ... sweeps made that way since (sweep_live: one in 16 goes by a list)
-	bool table_coarse;        // sweeps with a table go by plan 0 for now: the last ones left too little out for the finer plan to pay (table_plan)
-	uint32_t table_target;    // the tile count plan 1 is asked for (table_retarget), 0: its default depth
-	uint32_t table_pending;   // ... and the one the last call would have asked for instead: replaced when the next call agrees
+	TablePolicy table;        // which plan the sweeps with a table go by, at what size, and which of them get a list (mc33_sweep_plan.h)
 	// the range table (RangeEntry, sweep_ranges): made for a grid whose samples this library knows to be unchanged - its own copy,
 	// or an adopted buffer the caller has declared stable - by the second sweep since they last changed
 	RangeEntry *d_ranges;
@@ -271,9 +264,7 @@ static void forget_ranges(mc33hip_ctx *c) {  // the samples changed, or may have
 	c->ranges_valid = false;
 	c->blocks_made = false;
 	c->sweeps_seen = 0;
-	c->table_coarse = false;  // (new samples: the finer plan until a sweep says otherwise ...
-	c->table_target = 0u;     // ... at its default depth until one has published a count)
-	c->table_pending = 0u;
+	table_forget(c->table);
 	if (c->h_live) __atomic_store_n(c->h_live, 0ull, __ATOMIC_RELAXED);
 }
 
@@ -646,7 +637,7 @@ extern "C" int mc33hip_adopt_device(mc33hip_ctx *c, const void *dptr, size_t pit
 	c->grid_stable = false;  // (volatile until the caller says otherwise: mc33hip_grid_stable)
 	c->pitch = pitch;
 	c->slice = slice;
-	c->plan[0].ze = c->plan[1].ze = c->plan[2].ze = 0u;  // (the plan counts its work in batches of the form - packed or not - this buffer's alignment allows)
+	c->plan[0].key.ze = c->plan[1].key.ze = c->plan[2].key.ze = 0u;  // (the plan counts its work in batches of the form - packed or not - this buffer's alignment allows)
 	c->counted = false;
 	forget_sweeps(c);
 	return MC33HIP_OK;

@@ -101,55 +101,10 @@ static int grow_entries(TailSet &w, uint64_t need) {
 	return alloc_entries(w, cap);
 }
 
-// Block plan of k_sweep for cell slices [zs, ze): every (segment group, y tile) column is cut along z into
-// chunks of about equal work (sample rows x waves x planes; a chunk re-reads one plane, so they are kept
-// about `depth` slices deep), and the number of chunks is a whole multiple of what the device holds at
-// once whenever the grid is large enough.  Measured on MI355X at 1024^3: with 1088 equal tiles on 256 CUs
-// the 64 CUs that got a fifth block finished 12 % after the others.
+// The plans of k_sweep: what they are, what names them and how their tiles are made is mc33_sweep_plan.h; here the context's
+// share - the batch of its samples, the weight its sized plans are cut with, and putting a plan in force on the device.
 static bool sweep_packed(const mc33hip_ctx *c);
-// work of one WAVE of y tile yt per slice: its sample rows
-// (in whole BATCHES of sample rows - 4 rows of float samples, 8 / 16 of packed ushort / uchar ones: a wave's time is the
-// number of batches it waits for, and a y tile of 2 rows costs a batch per plane like one of 4.  Counted in rows, the
-// 2-row last y tile of a 128^3 grid got pieces twice as deep as its time allows and the sweep took 0.060 ms where the
-// 256^3 one takes 0.035: VERDICT r4 weak 12)
-static double column_work(const mc33hip_ctx *c, uint32_t yt) {
-	const uint32_t rb = sweep_packed(c) ? 4u * (uint32_t)SWEEP_PACK : 4u;
-	return (double)((std::min(64u, c->P.ny + 1 - yt * 63u) + rb - 1u) / rb * rb);
-}
-// the tiles the slices [zs, ze) would make at ONE plane per tile: the work of all waves x slices / 64 rows (what plan_sweep divides by a depth)
-static double sweep_unit(const mc33hip_ctx *c, uint32_t zs, uint32_t ze) {
-	const uint32_t nYT = (c->P.ny + 62) / 63;
-	double W = 0;
-	for (uint32_t yt = 0; yt < nYT; yt++) W += column_work(c, yt) * c->P.nseg;
-	return W * (ze - zs) / 64.0;
-}
-//
-// Two plans are kept, and `which` says which one is put in force (c->cur_plan): 0, for a sweep without a range table, is about
-// SWEEP_DEPTH slices deep - one tile per wave slot of the device, one round; 1, for a sweep with one, about SWEEP_DEPTH_TABLE.  With a table
-// most tiles of a smooth field are dead and never streamed (k_tile_verdicts), and the live ones have to fill the device by
-// themselves: the plan is several rounds of the resident set, k_sweep's live blocks come first in the launch, and the hardware
-// hands a freed slot to the next of them.  An explicit MC33_HIP_RZ is the depth of both, which are then one plan (number 0);
-// MC33_HIP_RZ_TABLE is the depth of plan 1 alone (the tests make the two differ on small grids with it, the profiles try depths).
-// A lane swept ahead keeps the number of its plan (IsoLane::plan), and its tail asks for that plan again: the plan is a function
-// of the range, the depth and the device, so a plan made again for a range is the plan the lane's edge records are indexed by.
-// target (plan 1 only; 0: none): the number of tiles wanted, in place of a depth - what table_retarget makes of the live tiles the
-// sweeps find, so that the packed live blocks are a set share of ONE round of the device.  The chunks are shared out as for a depth, only the
-// sum is no whole number of rounds: dead tiles cost nothing.  A sized plan has a slot of its own, number 2 (c->plan[2]; `which` 1
-// with a target, or 2), so that a caller who mixes single-isovalue calls (sized) with passes over several isovalues (the default
-// depth, slot 1) has both resident and makes neither again.  A lane keeps the slot and the target (IsoLane::plan, plan_target).
-// weight (sized plans only; 0: none): the weight of a plane in batches the columns are cut by (mc33_sweep_plan.h).  Equal numbers
-// of BATCHES per tile make equal lives while the batches carry a wave's life.  A sweep that leaves dead blocks out pays for a batch
-// of a dead quarter with no memory access, and what it does once per plane weighs about PLANE_WEIGHT_BLOCKS batches
-// (profiles/r12_plan_balance.txt A): cut by batches alone, the tiles of a short last y tile - 4 batches per plane where the others
-// have 16 - were four times as deep as the others and ended last, 246 us into a kernel whose median wave lived 159
-// (profiles/r11_block_skip.txt E).  So the share of a column of such a plan goes by batches + weight per plane; the sum stays the
-// target, and sweep_unit and table_target's cap stay counted in batches.  The weight is that of a single-isovalue sweep of a
-// context that leaves blocks out (sweep_plane_weight: decided by the build, MC33_HIP_BLOCKS and the width of the grid - things
-// fixed when the context is made, never by whether a block table happens to exist); every other plan, and every plan of the
-// double and integer libraries, is cut by batches as before.  It is part of what names a plan: a lane keeps it beside its target
-// (IsoLane::plan_weight), and it is compared wherever the target is.
-constexpr uint32_t SWEEP_DEPTH = 16u, SWEEP_DEPTH_TABLE = 5u;  // (measured, 1024^3 float: profiles/r09_sweep_refill.txt A, B)
-constexpr double PLANE_WEIGHT_BLOCKS = 3.0;  // b / a of k_sweep_live_blocks: 2.4 fitted on the plan cut by batches, 3.3 on one cut with 3 (profiles/r12_plan_balance.txt A)
+static PlanGrid plan_grid(const mc33hip_ctx *c) { return PlanGrid{c->P.ny, c->P.nseg, sweep_packed(c) ? 4u * (uint32_t)SWEEP_PACK : 4u}; }
 static double plane_weight_switch() {  // MC33_HIP_PLANE_WEIGHT, read when a context is created: for curves and tests; 0: plans are cut by batches alone
 	const char *s = getenv("MC33_HIP_PLANE_WEIGHT");
 	if (!s || !*s) return PLANE_WEIGHT_BLOCKS;
@@ -160,17 +115,14 @@ static double sweep_plane_weight(const mc33hip_ctx *c) {
 	if (!MC33_BLOCK_SKIP || c->blocks_off || !(c->blocks_always || c->P.nseg >= 4u)) return 0.0;
 	return c->plane_weight;
 }
-static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, int which, uint32_t target = 0u, double weight = 0.0) {
-	const Params &P = c->P;
-	if (c->sw.rz && !c->sw.rz_table) which = 0;
-	if (which == 2) which = 1;  // (a lane's slot: the plan with a table, sized - its target comes with it)
-	if (!which) target = 0u;
-	if (!target || !(weight > 0.0)) weight = 0.0;
-	const uint32_t depth = which ? (c->sw.rz_table ? c->sw.rz_table : SWEEP_DEPTH_TABLE) : (c->sw.rz ? c->sw.rz : SWEEP_DEPTH);
-	const int slot = (which && target) ? 2 : which;
-	SweepPlan &pl = c->plan[slot];
-	c->cur_plan = slot;
-	if (pl.d_tiles && pl.zs == zs && pl.ze == ze && pl.depth == depth && pl.target == target && pl.weight == weight) return 0;
+// Puts the plan for [zs, ze) in force (c->cur_plan), making it when its slot holds another.  table: the plan of a sweep with a range
+// table, sized to `target` tiles cut with `weight` (plan_slot), or without.  This runs in every count call: nothing is allocated
+// while the slot holds the plan.
+static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, bool table, uint32_t target = 0u, double weight = 0.0) {
+	const PlanSlot ps = plan_slot(table, zs, ze, target, weight, c->sw.rz, c->sw.rz_table);
+	SweepPlan &pl = c->plan[ps.slot];
+	c->cur_plan = ps.slot;
+	if (pl.d_tiles && pl.key == ps.key) return 0;
 	if (!c->resident_blocks) {
 		int per_cu = 0, cus = 0;
 		HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sweep<1, 1>, 256, 0));
@@ -178,63 +130,13 @@ static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, int which, uint3
 		const uint32_t want = c->sw.sweep_blocks_per_cu ? c->sw.sweep_blocks_per_cu : 4u;
 		c->resident_blocks = (uint32_t)std::max(1, cus) * (uint32_t)std::max(1, std::min(per_cu, (int)want));
 	}
-	// A tile is what ONE wave streams: a row segment (256 samples in x) x a y tile (64 sample rows) x a run of planes.
-	// Planning is done per group of up to 4 neighbouring segments (they read the same 4 KiB rows and are launched
-	// side by side), but every wave gets a tile of its own, so a group with fewer than 4 segments (grids that are
-	// not a multiple of 1024 samples wide, narrow grids) does not leave the waves of a block idle.
-	const uint32_t nXG = (P.nseg + 3) / 4, nYT = (P.ny + 62) / 63, nzc = ze - zs;
-	const uint64_t ncol = (uint64_t)nXG * nYT;  // groups
-	std::vector<double> w(ncol);       // work of one WAVE of the group per slice: its sample rows
-	std::vector<uint32_t> waves(ncol);
-	double W = 0;                      // ... summed over all waves
-	for (uint32_t yt = 0; yt < nYT; yt++)
-		for (uint32_t xg = 0; xg < nXG; xg++) {
-			const uint64_t i = (uint64_t)yt * nXG + xg;
-			waves[i] = std::min(4u, P.nseg - xg * 4);
-			w[i] = column_work(c, yt);
-			W += w[i] * waves[i];
-		}
-	// wave tiles wanted: W * nzc / (64 * depth), rounded to whole rounds of the resident set
-	const double pref = W * nzc / (64.0 * depth);
-	uint64_t B = (uint64_t)c->resident_blocks * 4;
-	if (target) B = target;
-	else if (pref >= (double)B) B *= (uint64_t)(pref / (double)B + 0.5);
-	else B = std::max<uint64_t>(1, std::min<uint64_t>(B, (uint64_t)(W * nzc / (64.0 * std::max(1u, c->sw.min_depth)))));  // small grid: fill the GPU, tiles down to one plane deep (k_boundary then does the slices)
-	std::vector<uint32_t> chunks(ncol);  // z pieces of the group (each is one tile per wave of the group)
-	std::vector<PlanFrac> frac(ncol);
-	if (weight > 0.0)  // (a plane's own cost on top of its batches: mc33_sweep_plan.h)
-		for (uint64_t i = 0; i < ncol; i++) w[i] = plan_column_weight(w[i], sweep_packed(c) ? 4u * (uint32_t)SWEEP_PACK : 4u, weight);
-	const uint64_t total = plan_shares(w.data(), waves.data(), ncol, B, nzc, chunks.data(), frac.data());
-	if (total > 0x3FFFFFFFull) { set_err("grid too large for one launch"); return MC33HIP_EINVAL; }
-	struct Planned { SweepTile t; uint64_t col; };  // col: the wave's column (yt, seg)
-	std::vector<Planned> planned;
-	planned.reserve(total);
-	for (uint64_t i = 0; i < ncol; i++)
-		for (uint32_t k = 0; k < chunks[i]; k++) {
-			const uint32_t lo = zs + (uint32_t)((uint64_t)nzc * k / chunks[i]), hi = zs + (uint32_t)((uint64_t)nzc * (k + 1) / chunks[i]);
-			if (hi <= lo) continue;
-			const uint32_t yt = (uint32_t)(i / nXG), xg = (uint32_t)(i % nXG);
-			for (uint32_t sgm = xg * 4; sgm < xg * 4 + waves[i]; sgm++)
-				planned.push_back(Planned{SweepTile{sgm, yt, lo, hi}, (uint64_t)yt * P.nseg + sgm});
-		}
-	// launch order: by depth first, so that waves running together read neighbouring memory (the segments of a group
-	// stay next to each other: the sort is stable)
-	std::stable_sort(planned.begin(), planned.end(), [](const Planned &x, const Planned &y) { return x.t.z_lo < y.t.z_lo; });
-	std::vector<SweepTile> tiles(planned.size());
-	std::vector<TileBoundary> bounds;
-	{
-		std::vector<uint32_t> below((uint64_t)nYT * P.nseg, 0xFFFFFFFFu);  // the tile of the column that ends where the next one begins
-		for (uint32_t b = 0; b < planned.size(); b++) {   // (ascending z_lo: a column's tiles come in order)
-			const SweepTile &t = planned[b].t;
-			tiles[b] = t;
-			if (below[planned[b].col] != 0xFFFFFFFFu) bounds.push_back(TileBoundary{below[planned[b].col], b, t.z_lo, t.yt, t.seg, {0, 0, 0}});
-			below[planned[b].col] = b;
-		}
-	}
+	std::vector<SweepTile> tiles; std::vector<TileBoundary> bounds;
+	uint64_t total = 0;
+	if (!plan_tiles(plan_grid(c), ps.key, c->resident_blocks, c->sw.min_depth, tiles, bounds, total)) { set_err("grid too large for one launch"); return MC33HIP_EINVAL; }
 	// A sweep made ahead by mc33hip_sweep_many may still be reading the old plan: the copies below go through the null stream,
 	// which a non-blocking stream (any torch.cuda.Stream) is not ordered with
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	pl.ze = 0u;  // (not a plan until both arrays are in place)
+	pl.key.ze = 0u;  // (not a plan until both arrays are in place)
 	if (pl.tiles_cap < tiles.size())
 		if (int rc = dev_room("sweep tiles", &pl.d_tiles, &pl.tiles_cap, tiles.size())) return rc;
 	HIP_TRY(hipMemcpy(pl.d_tiles, tiles.data(), tiles.size() * sizeof(SweepTile), hipMemcpyHostToDevice));
@@ -245,10 +147,10 @@ static int plan_sweep(mc33hip_ctx *c, uint32_t zs, uint32_t ze, int which, uint3
 		if (int rc = dev_room("tile boundaries", &pl.d_bounds, &pl.nbounds, bounds.size())) return rc;
 		HIP_TRY(hipMemcpy(pl.d_bounds, bounds.data(), bounds.size() * sizeof(TileBoundary), hipMemcpyHostToDevice));
 	}
-	pl.zs = zs; pl.ze = ze; pl.depth = depth; pl.target = target; pl.weight = weight;
-	if (c->sw.verbose)
-		fprintf(stderr, "[mc33hip] sweep plan %d: %llu wave tiles (%u resident, %u asked for, plane weight %.2f), %llu columns, depth %.1f\n", slot, (unsigned long long)pl.ntiles,
-		        c->resident_blocks * 4, target, weight, (unsigned long long)nYT * P.nseg, (double)nzc * nYT * P.nseg / (double)pl.ntiles);
+	pl.key = ps.key;
+	if (const uint64_t columns = c->sw.verbose ? (uint64_t)plan_y_tiles(plan_grid(c)) * c->P.nseg : 0u)
+		fprintf(stderr, "[mc33hip] sweep plan %d: %llu wave tiles (%u resident, %u asked for, plane weight %.2f), %llu columns, depth %.1f\n", ps.slot, (unsigned long long)pl.ntiles,
+		        c->resident_blocks * 4, ps.key.target, ps.key.weight, (unsigned long long)columns, (double)(ze - zs) * columns / (double)pl.ntiles);
 	return 0;
 }
 
@@ -291,9 +193,7 @@ static int begin_lane(mc33hip_ctx *c, IsoLane &L, const SlotGeom &g, hipStream_t
 		if (int rc = dev_room_all("tile edge buffers", &L.edge_cap, ntiles,
 		                          {dev_array(&L.edge_bits, ntiles, 2 * 128 * sizeof(uint4)), dev_array(&L.edge_hdr, ntiles, 2 * 2 * sizeof(uint4))}))
 			return rc;
-	L.plan = c->cur_plan;
-	L.plan_target = c->plan[c->cur_plan].target;
-	L.plan_weight = c->plan[c->cur_plan].weight;
+	L.plan = PlanRef{c->cur_plan, c->plan[c->cur_plan].key.target, c->plan[c->cur_plan].key.weight};
 	const uint64_t nchunks = (L.slice_cap + SLOT_CHUNK - 1) / SLOT_CHUNK;  // (capacity: the halves keep their place)
 	if (++L.epoch >= c->epoch_wrap) {  // stamps wrap: start over with clean headers AND clean partial sums - the call before
 		// accumulated into the half an odd epoch selects and cleared only the other one, and epoch 1 is odd again
@@ -375,106 +275,29 @@ static const RangeEntry *sweep_ranges(mc33hip_ctx *c, hipStream_t st) {
 	return c->d_ranges;
 }
 
-// Whether the sweep about to be launched with a table goes by a live list (k_tile_verdicts, k_live_compact, k_sweep_live) or works
-// its verdicts out itself (k_sweep), and room for the list.  The list pays where dead tiles have to make room for live ones: a plan
-// of at least one round of the device.  Below that every tile has a slot of its own anyway, and the two small launches are a
-// loss - 7.5 us of the 110 a 256^3 step takes (profiles/r09_sweep_refill.txt D).  MC33_HIP_LIVE=1 / 0: always / never (the tests
-// of the list run on small grids).  No memory for the list: the preamble form, which is not an error.
-// Which plan a sweep with a table goes by: 1, the finer one, unless the sweeps say it does not pay.  A finer plan is a gain by the
-// slots dead tiles free for live ones, and a loss by its per-tile start and end and three times the boundaries.  Measured at 1024^3
-// float (profiles/r09_sweep_refill.txt C, D): 63 % of the one-round plan's tiles dead, 12 % faster; nothing dead, 5 - 8 % slower; between
-// the two, taken as linear in the dead share, they break even near four tiles in five live.  So: a sweep by the finer plan that
-// found more than 90 % of its tiles live sends the following ones to plan 0, the one-round plan (with the table and its list all
-// the same), and a sweep by plan 0 that found fewer than 75 % live sends them back.  The finer plan never has the larger live share of
-// the two, so a field stays where it was sent.  The count is k_live_compact's published word, read as it stands - of the last
-// sweep or of one or two before it; nobody waits for it.  New samples start from the finer plan (forget_ranges).
-static int table_plan(mc33hip_ctx *c) {
-	if (c->h_live) {
-		const unsigned long long w = __atomic_load_n(c->h_live, __ATOMIC_RELAXED);
-		const uint64_t tiles = (w & 0xFFFFFFFFull) >> 1, live = w >> 32;
-		if (tiles) {
-			if ((w & 1ull) && live * 100 > tiles * 90) { c->coarse_sweeps = c->table_coarse ? c->coarse_sweeps : 0u; c->table_coarse = true; }
-			else if (!(w & 1ull) && live * 100 < tiles * 75) c->table_coarse = false;
-		}
-	}
-	return c->table_coarse ? 0 : 1;
+// The policy of the sweeps with a table - which plan, what size, who gets a list - is mc33_sweep_plan.h (TablePolicy); here the
+// context's share: the published word as it stands, the facts, the list's buffers.
+static unsigned long long live_word(const mc33hip_ctx *c) { return c->h_live ? __atomic_load_n(c->h_live, __ATOMIC_RELAXED) : 0ull; }
+// plan: the plan in force, or the one the policy's target names - nullptr when its slot holds another (table_retarget)
+static TableFacts table_facts(const mc33hip_ctx *c, uint32_t zs, uint32_t ze, const SweepPlan *plan) {
+	return TableFacts{sweep_unit(plan_grid(c), zs, ze), c->resident_blocks, c->sw.min_depth, sweep_plane_weight(c), c->sw.sweep_blocks_per_cu != 0u, c->sw.rz, c->sw.rz_table, c->sw.table_tiles, c->sw.live, plan ? plan->ntiles : 0u, plan == &c->plan[2]};
 }
-// How many tiles the finer plan is asked for (c->table_target; 0: its default depth).  The packed live blocks of a sweep are
-// ceil(live tiles / 4) (k_live_compact), and the kernel's length is a whole number of rounds of the resident set times the life of
-// a tile: the plan is sized so that they are LESS than one round - TABLE_FILL of the resident blocks (mc33_sweep_pack.h:
-// table_target) - from the count the last sweep by plan 1 published; the live share hardly depends on the size of the plan.  A
-// new plan costs a wait for the stream and two copies (plan_sweep), so the plan stays while the count says its packed blocks lie
-// between TABLE_BAND_LO and TABLE_BAND_HI of a round.  Tiles are never asked shallower than TABLE_MIN_DEPTH planes; a grid whose
-// default plan is shallower than that already - cut down to MC33_HIP_MIN_DEPTH to make one round at all - goes by that depth
-// instead.
-// The constants are read off the measured curve of the flagship, profiles/r10_sweep_pack.txt C, D: every size between 0.63 and
-// 0.73 of a round (7 168 - 8 350 tiles) takes 0.572 - 0.580 ms per step against the parent's 0.60 - 0.61, the sizes between 0.75
-// and 0.81 (8 564 - 9 216) are SLOWER than the parent (a tail of late tiles at a regular spacing in z, not understood), a full
-// round (0.91: 10 400) gains 1 %, 0.95 - 1.0 gain 3 %, and past one round the gain is gone.  So the fill is 0.68 and the band
-// ends at 0.72, a margin short of the sizes that lose while their cause is not known.  Nothing shallower than 3.4 planes was measured.
-// Never fewer tiles than ONE ROUND (4 x resident blocks; table_target): with more than 0.68 of its tiles live a plan would be
-// asked for less, the sweep would go without a list (sweep_live), nothing would publish a count again, and the context would sit
-// on that plan whatever isovalue came next.  For the same reason a sized plan always gets its list.
-// Left alone: an explicit MC33_HIP_RZ / MC33_HIP_RZ_TABLE, plans of less than one round (small grids), sweeps by plan 0, no count
-// yet (new samples: forget_ranges).  MC33_HIP_TABLE_TILES forces a target: it is for tests and curves, comes before
-// MC33_HIP_RZ_TABLE and holds for small plans too; only MC33_HIP_RZ alone, which makes the two plans one, comes before it.
-// Two calls in a row have to ask for about the same size (5 %) before the plan is replaced: a caller that moves between isovalues
-// with very different live shares would otherwise pay for a new plan in every call - 0.31 -> 0.52 ms per count at 1024^3 with the
-// isovalues 0 and 1.5 alternated (profiles/r10_sweep_pack.txt F) - and now stays on the plan it has.
-// Those constants hold for plans cut by batches alone and for every context whose residency is forced.  Cut to the batches of a
-// full y tile, the tiles of a short last one are several times as many planes deep, and with blocks left out a plane costs about
-// three batches' worth of time whatever its rows (plan_sweep): they ended last.  A plan cut with that weight has no such tail and
-// gains most right below one round, so it goes by a second fill and band (TABLE_FILL_BALANCED below; table_band in
-// mc33_sweep_plan.h makes the choice).  (The sizes at 0.75 - 0.81 of a round are still 0.01 ms behind 0.68 with the balanced cut,
-// profiles/r12_plan_balance.txt B: the deep tiles were not the whole of that loss.)
-// Only the single-isovalue calls are sized (enqueue_count).  The passes of mc33hip_sweep_many / mc33hip_prepare_many go by the
-// default depth: their forms over several isovalues hold three blocks per CU, not four, a tile is live when ANY of its isovalues
-// cuts it, and sized by this rule c5 (2048 x 2048 x 1024 ushort, 8 isovalues) was 5 % slower (r10 F).
-constexpr double TABLE_FILL = 0.68, TABLE_BAND_LO = 0.62, TABLE_BAND_HI = 0.72, TABLE_MIN_DEPTH = 3.0;
-// Plans cut with a plane weight (plan_sweep), at the device's own residency: read off profiles/r12_plan_balance.txt B.  With the cut
-// balanced the step falls all the way to one round: 0.525 ms at 0.69 of a round, 0.516 - 0.523 between 0.86 and 0.97, and 0.493 -
-// 0.501 on the three sizes between 0.978 and 0.996 (11 200 - 11 400 tiles; parents 0.559 - 0.570, noise 0.008) - the widest run
-// within the noise of the best, so the band is that run and the fill its centre.  Past one round (1.01) the step is 0.539: worse
-// than the best by 0.045 and than 0.69 of a round by 0.013, still ahead of the parent.  A plan that misses the band on either side
-// is sized again by the next two calls; hi stays below 1 (table_keeps).  The curve was measured at four blocks per compute unit
-// and nowhere else: a context whose residency is forced (MC33_HIP_SWEEP_BLOCKS_PER_CU) keeps the constants above (table_band).
-constexpr double TABLE_FILL_BALANCED = 0.987, TABLE_BAND_BALANCED_LO = 0.978, TABLE_BAND_BALANCED_HI = 0.997;
 static void table_retarget(mc33hip_ctx *c, uint32_t zs, uint32_t ze) {
-	if (c->sw.table_tiles) { c->table_target = c->sw.table_tiles; return; }
-	if (c->sw.rz || c->sw.rz_table || !c->h_live || !c->resident_blocks || ze <= zs) return;
-	const unsigned long long w = __atomic_load_n(c->h_live, __ATOMIC_RELAXED);
-	const uint64_t tiles = (w & 0xFFFFFFFFull) >> 1, live = w >> 32;
-	if (!(w & 1ull) || !tiles || !live) return;
-	const double unit = sweep_unit(c, zs, ze), one_round = 4.0 * c->resident_blocks;
-	double min_depth = TABLE_MIN_DEPTH;
-	if (unit / SWEEP_DEPTH_TABLE < one_round) {  // (plan_sweep: such a grid gets one round, or what its slices make at the smallest depth)
-		min_depth = (double)std::max(1u, c->sw.min_depth);
-		if (unit / min_depth < one_round) return;
-	}
-	// (the word is read as it stands: its count may be of the plan before the one in force)
-	const SweepPlan &pl = c->plan[c->table_target ? 2 : 1];
-	const double weight = sweep_plane_weight(c);
-	const uint64_t cur = (pl.d_tiles && pl.zs == zs && pl.ze == ze && pl.target == c->table_target && (!c->table_target || pl.weight == weight)) ? pl.ntiles : tiles;
-	const TableBand band = table_band(weight, c->sw.sweep_blocks_per_cu != 0u, TableBand{TABLE_FILL, TABLE_BAND_LO, TABLE_BAND_HI},
-	                                  TableBand{TABLE_FILL_BALANCED, TABLE_BAND_BALANCED_LO, TABLE_BAND_BALANCED_HI});
-	if (table_keeps(live * cur / tiles, c->resident_blocks, band.lo, band.hi)) { c->table_pending = 0u; return; }
-	const uint32_t t = table_target(live, tiles, c->resident_blocks, unit, min_depth, band.fill);
-	if (!t || t == c->table_target) { c->table_pending = 0u; return; }
-	if (!c->table_pending || std::fabs((double)t - (double)c->table_pending) > 0.05 * (double)c->table_pending) { c->table_pending = t; return; }  // (a second call has to agree)
-	c->table_pending = 0u;
-	if (c->sw.verbose) fprintf(stderr, "[mc33hip] table plan: %llu of %llu tiles live, %u tiles asked for (were %u)\n", (unsigned long long)live, (unsigned long long)tiles, t, c->table_target);
-	c->table_target = t;
+	const SweepPlan &pl = c->plan[c->table.target ? 2 : 1];
+	const bool held = pl.d_tiles && plan_is_sized_as(pl.key, zs, ze, c->table.target, sweep_plane_weight(c));  // (else the slot holds another plan, and the count goes by the word's own tiles)
+	const unsigned long long w = live_word(c), was = c->table.target;
+	table_retarget(c->table, w, table_facts(c, zs, ze, held ? &pl : nullptr));
+	if (c->sw.verbose && !c->sw.table_tiles && c->table.target != was)
+		fprintf(stderr, "[mc33hip] table plan: %llu of %llu tiles live, %u tiles asked for (were %u)\n", (unsigned long long)(w >> 32), (unsigned long long)((w & 0xFFFFFFFFull) >> 1), c->table.target, (uint32_t)was);
 }
+// Room for the live list of the sweep about to be launched, when it goes by one (table_wants_list).  No memory for the list: the
+// preamble form, which is not an error.
 static void sweep_live(mc33hip_ctx *c, SweepArgs &a) {
 	c->live_blocks = 0;
 	if (!a.ranges) return;
-	const uint64_t ntiles = c->plan[c->cur_plan].ntiles, blocks = (ntiles + 3) / 4;
-	// While the one-round plan stands in for the finer one (table_plan) every tile has its slot and the preamble form is the faster
-	// one - it is the parent's sweep, where the list's two launches cost 10 us of 940 (r09 F) - but only a list's count can end the
-	// stand-in: one sweep in 16 goes by a list, the first of them at once.
-	bool want = ntiles >= (uint64_t)c->resident_blocks * 4 || c->cur_plan == 2;  // (a sized plan always: only a list's count can size it again)
-	if (c->table_coarse) want = (c->coarse_sweeps++ % 16u) == 0u;
-	if (!(c->sw.live > 0 || (c->sw.live < 0 && want))) return;
+	const SweepPlan &pl = c->plan[c->cur_plan];
+	const uint64_t blocks = (pl.ntiles + 3) / 4;
+	if (!table_wants_list(c->table, table_facts(c, pl.key.zs, pl.key.ze, &pl))) return;
 	if (!c->h_live && hipHostMalloc(&c->h_live, sizeof *c->h_live, hipHostMallocDefault) == hipSuccess) *c->h_live = 0ull;
 	else if (!c->h_live) (void)hipGetLastError();  // (no pinned word: nothing is published, the finer plan stays)
 	if ((c->verdict_cap < blocks && dev_room("tile verdicts", &c->d_verdict, &c->verdict_cap, blocks) != 0) ||
@@ -586,7 +409,8 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 	hipStream_t st = c->stream;
 	const uint32_t ze = c->range.z_end;
 	// (the lanes of a call were swept by one pass, so by one plan: the one their edge records are paired by)
-	if (int rc = plan_sweep(c, c->P.zs, ze, c->lanes[idx[0]].plan, c->lanes[idx[0]].plan_target, c->lanes[idx[0]].plan_weight)) return rc;
+	const PlanRef &lr = c->lanes[idx[0]].plan;
+	if (int rc = plan_sweep(c, c->P.zs, ze, lr.slot != 0, lr.target, lr.weight)) return rc;
 	const SweepPlan &pl = c->plan[c->cur_plan];
 	SweepArgs a;
 	sweep_args(c, g, a);
@@ -730,8 +554,8 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 			    c->lanes[k].slice_cap >= g.nslots) {
 				// (the plan it was swept by is looked at, not put in force: when its place holds another range's plan by now, the tail
 				// makes it again - the same plan, which the lane's edge buffers had room for)
-				const SweepPlan &lp = c->plan[c->lanes[k].plan];
-				if (lp.d_tiles && lp.zs == P.zs && lp.ze == c->range.z_end && lp.target == c->lanes[k].plan_target && lp.weight == c->lanes[k].plan_weight && c->lanes[k].edge_cap < lp.ntiles) continue;
+				const SweepPlan &lp = c->plan[c->lanes[k].plan.slot];
+				if (lp.d_tiles && plan_is_lanes(lp.key, c->lanes[k].plan, P.zs, c->range.z_end) && c->lanes[k].edge_cap < lp.ntiles) continue;
 				L = &c->lanes[k];
 				tail_made = L->tail_done;
 			}
@@ -746,7 +570,7 @@ static int enqueue_count(mc33hip_ctx *c, bool rerun = false) {
 		L = &c->lanes[0];
 		const RangeEntry *ranges = sweep_ranges(c, st);
 		table_retarget(c, P.zs, c->range.z_end);
-		if (int rc = plan_sweep(c, P.zs, c->range.z_end, ranges ? table_plan(c) : 0, c->table_target, sweep_plane_weight(c))) return rc;
+		if (int rc = plan_sweep(c, P.zs, c->range.z_end, ranges && table_plan(c->table, live_word(c)), c->table.target, sweep_plane_weight(c))) return rc;
 		if (int rc = begin_lane(c, *L, g, st)) return rc;
 		c->lane_presweeped = false;
 		SweepArgs a;
@@ -837,7 +661,7 @@ static int enqueue_sweep_many(mc33hip_ctx *c, const double *isos, int n, bool ta
 		// (the table may be built in front of the second pass: every pass goes by the plan of what it has, and its lanes keep it)
 		const RangeEntry *ranges = sweep_ranges(c, st);
 		// (every pass of the call by the same plan with a table: its default depth, or the size MC33_HIP_TABLE_TILES forces - table_retarget)
-		if (int rc = plan_sweep(c, c->P.zs, c->range.z_end, ranges ? table_plan(c) : 0, c->sw.table_tiles)) return rc;
+		if (int rc = plan_sweep(c, c->P.zs, c->range.z_end, ranges && table_plan(c->table, live_word(c)), c->sw.table_tiles)) return rc;
 		SweepArgs a;
 		sweep_args(c, g, a);
 #ifdef MC33_DEV
@@ -1488,7 +1312,7 @@ extern "C" int mc33hip_block_words(mc33hip_ctx *c, void *host_out, size_t bytes)
 extern "C" int mc33hip_sweep_plan(mc33hip_ctx *c, unsigned int *tiles_out, size_t cap_tiles, unsigned long long *info /*[3]*/) {
 	if (!c || !info) return MC33HIP_EINVAL;
 	const SweepPlan &pl = c->plan[c->cur_plan];
-	if (!pl.d_tiles || !pl.ze) { set_err("no sweep plan yet"); return MC33HIP_EINVAL; }
+	if (!pl.d_tiles || !pl.key.ze) { set_err("no sweep plan yet"); return MC33HIP_EINVAL; }
 	info[0] = pl.ntiles; info[1] = c->resident_blocks; info[2] = c->cur_plan ? 1ull : 0ull;  // (sized or not: the plan with a table)
 	if (!tiles_out) return MC33HIP_OK;
 	if (cap_tiles < pl.ntiles) { set_err("sweep plan: %llu tiles, room for %llu", (unsigned long long)pl.ntiles, (unsigned long long)cap_tiles); return MC33HIP_EINVAL; }
@@ -1500,8 +1324,8 @@ extern "C" int mc33hip_sweep_plan(mc33hip_ctx *c, unsigned int *tiles_out, size_
 extern "C" int mc33hip_sweep_plan_weight(mc33hip_ctx *c, double *out) {
 	if (!c || !out) return MC33HIP_EINVAL;
 	const SweepPlan &pl = c->plan[c->cur_plan];
-	if (!pl.d_tiles || !pl.ze) { set_err("no sweep plan yet"); return MC33HIP_EINVAL; }
-	*out = pl.weight;
+	if (!pl.d_tiles || !pl.key.ze) { set_err("no sweep plan yet"); return MC33HIP_EINVAL; }
+	*out = pl.key.weight;
 	return MC33HIP_OK;
 }
 extern "C" int mc33hip_sweep_packed(mc33hip_ctx *c, unsigned int *out, size_t cap_entries, unsigned long long *info /*[3]*/) {

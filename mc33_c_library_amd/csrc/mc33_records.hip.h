@@ -48,11 +48,7 @@ constexpr uint32_t SLICE_VALID = 1u, SLICE_HAS_ISO = 2u;
 // of earlier calls are simply not valid any more, and the 2 MB of headers need no clearing between calls.
 __host__ __device__ inline bool slice_valid(uint32_t flags, uint32_t epoch) { return (flags & ~SLICE_HAS_ISO) == (epoch << 2 | SLICE_VALID); }
 
-// One block of k_sweep: the 4 row segments of group xg, the 63 cell rows of y tile yt, cell slices [z_lo, z_hi).
-// The host cuts every (xg, yt) column into chunks of equal WORK (rows x planes), as many in total as the
-// GPU holds blocks at once: waves of one SIMD are served oldest first, so a CU that got one block more
-// than the others ends that much later, and short tiles (the last y tile) get deeper chunks.
-struct SweepTile { uint32_t seg, yt, z_lo, z_hi; };  // the piece of the volume ONE WAVE of k_sweep streams: row segment, y tile, planes
+// (SweepTile, the piece of the volume one wave of k_sweep streams: mc33_sweep_plan.h, with the planner that makes them)
 
 // slice record of (cell slice z, y tile, row segment): groups of 4 consecutive slices of one tile column are
 // adjacent (one k_cells block).  The order of the groups is the order the work records are stored in and the emit

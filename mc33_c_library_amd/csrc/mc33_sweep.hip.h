@@ -1043,8 +1043,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 // k_boundary: the slice between the last plane of a tile and the first plane of the tile above it, from the bit
 // rows the two left behind.  One wave per pair of tiles.
 // ---------------------------------------------------------------------------------------------------
-struct TileBoundary { uint32_t below, above, z, yt, seg, pad_[3]; };  // tile (wave) indices of k_sweep; slice z
-
+// (TileBoundary - tile (wave) indices of k_sweep, slice z: mc33_sweep_plan.h)
 __global__ __launch_bounds__(256) void k_boundary(const SweepArgs a, const TileBoundary *bounds, uint32_t nbounds) {
 	const SweepLane &L = a.lane[blockIdx.y];  // (the isovalue lanes of the sweep that left the edge records)
 	const uint32_t lane = threadIdx.x & 63u;

@@ -1,9 +1,11 @@
-// mc33_sweep_pack.h -- the two rules of the sweep with a range table that need no device, as plain functions (no HIP type): where
-// the entries of the packed live list go (k_live_compact), and how many tiles the plan of such a sweep is asked for (table_plan).
+// mc33_sweep_pack.h -- the layout of the packed live list of a sweep with a range table, as plain functions (no HIP type): where
+// its entries go (k_live_compact).  How many tiles the plan of such a sweep is asked for: mc33_sweep_plan.h.
 // Included by mc33_kernels.hip and by host programs (tests/sweep_pack_host.cpp).
 #ifndef MC33_SWEEP_PACK_H
 #define MC33_SWEEP_PACK_H
 #include <stdint.h>
+
+#include "mc33_sweep_plan.h"  // (the size of the plan - table_target, table_keeps - comes with this header for the programs that include it alone)
 
 #if defined(__HIPCC__)
 #define MC33_PACK_FN __host__ __device__ static inline
@@ -54,31 +56,5 @@ static inline uint32_t pack_live_list(const uint8_t *verdict, uint32_t nblocks, 
 	for (uint32_t s = L & 3u; s && s < 4u; s++) entries[4u * at + s] = MC33_PACK_NONE;
 	if (live_tiles) *live_tiles = 4u * W + L;
 	return W + (L + 3u) / 4u;
-}
-
-// ---- the size of the plan --------------------------------------------------------------------------------------------------------------
-// A sweep with a table streams its live tiles only, and a block keeps its four wave slots for the life of a tile: the kernel's
-// length is a whole number of rounds of the resident set times that life.  So the plan is asked for as many tiles as make the
-// PACKED live blocks - ceil(live / 4) - the share `fill` of one round of the device.  The live share of a field hardly depends on
-// the size of the plan, so the count one sweep published (`live` of `tiles`) predicts the live tiles of a plan of another size:
-//   target = fill * 4 * resident_blocks * tiles / live,
-// but never more tiles than are `min_depth` planes deep: `unit` is the number of tiles the range would have at a depth of one
-// plane, and the target is cut to unit / min_depth.  (A cut plan has FEWER packed blocks than a round, never more: one round is
-// always enough, and there is no case for a second.)  And never fewer tiles than one round, 4 * resident_blocks: a plan below
-// that gets no list, so no count would ever size it again.  0: no count, nothing to go by.
-MC33_PACK_FN uint32_t table_target(uint64_t live, uint64_t tiles, uint32_t resident_blocks, double unit, double min_depth, double fill) {
-	if (!live || !tiles || !resident_blocks) return 0u;
-	double t = fill * 4.0 * (double)resident_blocks * (double)tiles / (double)live;
-	const double cap = unit / (min_depth > 0.0 ? min_depth : 1.0);
-	if (t > cap) t = cap;
-	if (t < 4.0 * (double)resident_blocks) t = 4.0 * (double)resident_blocks;
-	if (t > 1073741823.0) t = 1073741823.0;
-	return t < 1.0 ? 1u : (uint32_t)t;
-}
-// A plan is kept while the packed blocks its sweeps find stay inside a band around the target: lo .. hi of the resident blocks.
-// hi is never above 1: a block more than the device holds costs a whole tile's life (the caller's band ends well below).
-MC33_PACK_FN int table_keeps(uint64_t live, uint32_t resident_blocks, double lo, double hi) {
-	const double packed = (double)((live + 3u) / 4u), r = (double)resident_blocks;
-	return packed >= lo * r && packed <= hi * r;
 }
 #endif

@@ -1,5 +1,5 @@
-// The two device-free rules of the sweep with a range table (mc33_c_library_amd/csrc/mc33_sweep_pack.h) in a stand-alone host
-// program: the same text the library compiles.  Test infrastructure (tests/test_sweep_pack_cpu.py builds it with g++ and holds its
+// The two device-free rules of the sweep with a range table - the packed live list (mc33_c_library_amd/csrc/mc33_sweep_pack.h) and the
+// size of the plan (mc33_sweep_plan.h) - in a stand-alone host program: the same text the library compiles.  Test infrastructure (tests/test_sweep_pack_cpu.py builds it with g++ and holds its
 // output to a numpy restatement); a stand-alone program, so that it can also be built with -fsanitize=address,undefined.
 //
 //   sweep_pack_host pack <verdict file> <threads>
@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../mc33_c_library_amd/csrc/mc33_sweep_pack.h"
+#include "../mc33_c_library_amd/csrc/mc33_sweep_plan.h"
 
 static int popc4(uint32_t v) { return (int)((v & 1u) + ((v >> 1) & 1u) + ((v >> 2) & 1u) + ((v >> 3) & 1u)); }
 

@@ -1,5 +1,5 @@
-"""numpy restatements of the two device-free rules of the sweep with a range table (mc33_c_library_amd/csrc/mc33_sweep_pack.h,
-DESIGN.md 21): the order of the packed live list, and the size of the plan.  Written from the rules as DESIGN.md states them, not
+"""numpy restatements of the two device-free rules of the sweep with a range table: the order of the packed live
+list (mc33_c_library_amd/csrc/mc33_sweep_pack.h), and the size of the plan (mc33_sweep_plan.h).  Written from the rules as DESIGN.md states them, not
 from the header's code: tests/test_sweep_pack_cpu.py holds the header to them, tests/test_gpu_sweep_pack.py the device."""
 import numpy as np
 

@@ -81,3 +81,83 @@ def plan_chunks(tiles, shape):
         m = (t[:, 1] == yt) & (t[:, 0] == 4 * xg)
         out.append(int(m.sum()))
     return out
+
+
+# ---- the policy of the sweeps with a range table ("The size of the plan", "A field with a table and little dead
+# goes back to the one-round plan") -------------------------------------------------------------------------------------------------
+
+def word(live, tiles, plan):
+    """what k_live_compact publishes: live tiles << 32 | tiles << 1 | plan; 0: nothing yet"""
+    return (live << 32) | (tiles << 1) | plan
+
+
+class Facts:
+    """what the policy is told of the context and of the range about to be swept (TableFacts, in the order of the struct)"""
+
+    def __init__(self, unit, resident, min_depth=0, weight=0.0, forced=False, rz=0, rz_table=0, table_tiles=0, live=-1, plan_tiles=0, plan_sized=False):
+        self.unit, self.resident, self.min_depth, self.weight, self.forced = float(unit), resident, min_depth, float(weight), forced
+        self.rz, self.rz_table, self.table_tiles, self.live, self.plan_tiles, self.plan_sized = rz, rz_table, table_tiles, live, plan_tiles, plan_sized
+
+    def line(self):
+        return "%r %d %d %r %d %d %d %d %d %d %d" % (self.unit, self.resident, self.min_depth, self.weight, int(self.forced), self.rz, self.rz_table,
+                                                    self.table_tiles, self.live, self.plan_tiles, int(self.plan_sized))
+
+
+class Policy:
+    """the state the sweeps with a table go by, as DESIGN.md states the rules; every method returns the decision"""
+
+    def __init__(self):
+        self.coarse, self.coarse_sweeps, self.target, self.pending = False, 0, 0, 0
+
+    def state(self):
+        return (int(self.coarse), self.coarse_sweeps, self.target, self.pending)
+
+    def plan(self, w):
+        """a sweep by the finer plan that found more than 90 % of its tiles live sends the following ones to plan 0; a sweep by
+        plan 0 that found fewer than 75 % live sends them back; the one-in-16 counter starts when the stand-in does"""
+        tiles, live = (w & 0xFFFFFFFF) >> 1, w >> 32
+        if tiles:
+            if (w & 1) and 100 * live > 90 * tiles:
+                if not self.coarse:
+                    self.coarse_sweeps = 0
+                self.coarse = True
+            elif not (w & 1) and 100 * live < 75 * tiles:
+                self.coarse = False
+        return 0 if self.coarse else 1
+
+    def retarget(self, w, f):
+        """precedence: MC33_HIP_TABLE_TILES, then an explicit depth (left alone), then the sizing by a count of plan 1"""
+        if f.table_tiles:
+            self.target = f.table_tiles
+            return
+        tiles, live = (w & 0xFFFFFFFF) >> 1, w >> 32
+        if f.rz or f.rz_table or not f.resident or not (w & 1) or not tiles or not live:
+            return
+        depth = pr.floor_depth(f.unit, f.resident, f.min_depth)
+        if depth is None:   # less than one round at the smallest depth
+            return
+        fill, lo, hi = band(f.weight, f.forced, (FILL_BALANCED, BAND_BALANCED_LO, BAND_BALANCED_HI))
+        now = f.plan_tiles if f.plan_tiles else tiles   # the live share scaled to the plan in force
+        if pr.keeps(live * now // tiles, f.resident, lo, hi):
+            self.pending = 0
+            return
+        t = pr.target(live, tiles, f.resident, f.unit, depth, fill)
+        if not t or t == self.target:
+            self.pending = 0
+        elif not self.pending or abs(t - self.pending) > 0.05 * self.pending:
+            self.pending = t   # a second call has to agree
+        else:
+            self.pending, self.target = 0, t
+
+    def wants_list(self, f):
+        """a plan of at least one round, or a sized plan; while plan 0 stands in, one sweep in 16, the first at once; MC33_HIP_LIVE
+        overrides either way (the sweeps are still counted)"""
+        want = f.plan_tiles >= 4 * f.resident or f.plan_sized
+        if self.coarse:
+            want = self.coarse_sweeps % 16 == 0
+            self.coarse_sweeps += 1
+        return f.live > 0 or (f.live < 0 and want)
+
+    def forget(self):
+        """new samples: the finer plan, at its default depth, nothing pending"""
+        self.coarse, self.target, self.pending = False, 0, 0

@@ -223,7 +223,7 @@ def dead_columns(data, iso, dtype="f32"):
 
 
 def planned_tiles(shape, depth):
-    """{(yt, seg): tiles} - a lower bound of the tiles plan_sweep (mc33_extract.hip.h) cuts every column into, restated from its
+    """{(yt, seg): tiles} - a lower bound of the tiles plan_tiles (mc33_sweep_plan.h) cuts every column into, restated from its
     arithmetic for float samples (batches of 4 sample rows) with MC33_HIP_RZ = MC33_HIP_MIN_DEPTH = depth, on a grid so small that
     what the device holds at once does not cap the plan: the work of a wave per slice is its sample rows in whole batches, the
     plan wants B = W nzc / (64 depth) tiles, and a group of segments gets floor(B w / W) z pieces (one at least, a slice each at

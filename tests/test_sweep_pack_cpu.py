@@ -138,9 +138,9 @@ def test_plan_size_is_the_rules(host_program):
 
 
 def test_the_librarys_constants_are_the_rules():
-    """the constants of table_retarget (mc33_extract.hip.h) are the ones the restatement and the GPU tests go by"""
+    """the constants of table_retarget (mc33_sweep_plan.h) are the ones the restatement and the GPU tests go by"""
     import re
-    text = open(os.path.join(HERE, "..", "mc33_c_library_amd", "csrc", "mc33_extract.hip.h")).read()
+    text = open(os.path.join(HERE, "..", "mc33_c_library_amd", "csrc", "mc33_sweep_plan.h")).read()
     m = re.search(r"TABLE_FILL = ([0-9.]+), TABLE_BAND_LO = ([0-9.]+), TABLE_BAND_HI = ([0-9.]+), TABLE_MIN_DEPTH = ([0-9.]+);", text)
     assert m and tuple(float(x) for x in m.groups()) == (pr.FILL, pr.BAND_LO, pr.BAND_HI, pr.MIN_DEPTH)
     assert re.search(r"SWEEP_DEPTH_TABLE = %du" % int(pr.DEFAULT_DEPTH), text)
