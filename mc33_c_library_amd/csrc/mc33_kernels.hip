@@ -129,6 +129,7 @@ typedef float sample_t;
 
 // The translation unit in parts (round 5: it had grown to 4 500 lines), included in this order:
 #include "mc33_sweep_plan.h"
+#include "mc33_sweep_blocks.h"
 #include "mc33_records.hip.h"
 #include "mc33_sweep_pack.h"
 #include "mc33_sweep.hip.h"

@@ -582,28 +582,24 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 #define MC33_LOAD(rs, vo, so) (__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, so, MC33_SWEEP_AUX)))
 #endif
 	typedef typename std::conditional<S == 1, real_t, uint32_t>::type raw_t;  // what a load leaves in a register
-	// BS: dead blocks inside the live tile are left out (k_block_verdicts).  A quarter of a sample row is one load instruction of this
-	// form and a row group is four batches, so what is dead is decided per instruction, wave-uniformly, from the word of the plane:
-	// bwi of the plane being issued, bwp of the plane being processed, each with the word of the plane behind it asked for a plane
-	// ahead (scalar loads).  A dead load keeps its place in the batch - the waits the compiler derives count on a fixed number of loads
-	// (see `issue`) - and is aimed outside the descriptor, offset 0xFFFFFFF0 like the lanes of the halo load that stay out: no memory
-	// access.  What it returns (0 - and the isovalue may well be 0) is never looked at: `process` puts -inf / +inf in its place, which
-	// classifies as strictly below / above for every isovalue that gave the block that verdict and can never count as "equal to the
-	// isovalue" (|iso - F| is infinite).  The column-0 bits a wave posts in the mailbox come from those samples where its quarter 0
-	// is dead, and are right.  No word (SweepArgs::blockw == nullptr): every block is live.
-	// A kernel of its own (k_sweep_live_blocks) has this form: k_sweep_live stays the code it was, for the sweeps without words.
+	// BS: dead blocks inside the live tile are left out (k_block_verdicts): this form has a batch stream of its own, below (`the block
+	// stream`) - a batch is one live block of the plane, and the word of the plane (block_word) says which those are, what the bit rows
+	// of the dead ones are worth and what their halo samples.  A kernel of its own (k_sweep_live_blocks) has this form: k_sweep_live stays
+	// the code it was, for the sweeps without words.  No word (SweepArgs::blockw == nullptr): every block is live.
 	constexpr bool BS = BLOCKS;
 	static_assert(!BLOCKS || (MC33_BLOCK_SKIP && R == 2 && NI == 1 && S == 1), "blocks are left out by the float single-isovalue sweep with a live list");
 	auto block_word = [&](uint32_t p) __attribute__((always_inline)) -> uint64_t {
 		if constexpr (BS) {
 			if (a.blockw) {
-				const unsigned long long w = a.blockw[((uint64_t)(min(p, z_hi) - a.G.z0) * a.sd.nYT + yt) * a.sd.nseg + seg];
-				return u64((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w), (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w >> 32)));
+				// (through the constant address space - the words were written in front of this kernel and nothing in it writes them: a SCALAR
+				// load, which the waits of the batches in flight do not count.  As a global load behind the kernel's stores it was a vector
+				// load, and the wave waited for it with vmcnt(0): every batch in flight drained once per plane.)
+				typedef const __attribute__((address_space(4))) unsigned long long *const_words_t;
+				return ((const_words_t)(uintptr_t)a.blockw)[((uint64_t)(min(p, z_hi) - a.G.z0) * a.sd.nYT + yt) * a.sd.nseg + seg];
 			}
 		}
 		return 0ull;
 	};
-	uint64_t bwi = block_word(pl0), bwi_n = block_word(pl0 + 1u), bwp = bwi, bwp_n = bwi_n;
 	// A batch is the same number of loads whatever the position in the tile, so that the wait counts the compiler derives keep
 	// the prefetched batch in flight: exactly 17 in the forms that always issue the halo load (several isovalues, double
 	// samples); 16 or 17 in the single-isovalue forms over 1- to 4-byte samples, whose halo load stands behind a branch (below)
@@ -611,17 +607,11 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 		const sample_t *base = a.G.p + (uint64_t)(p - a.G.z0) * a.G.slice + (uint64_t)y0 * a.G.pitch;
 		const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, tile_bytes, 0x00020000);
 		const uint32_t r = bi * (uint32_t)RB;
-		uint32_t codes = 0u, hcode = 0u;  // (BS) the verdicts of the four quarters of this batch's row group, and of its halo block
-		if constexpr (BS) { codes = (uint32_t)(bwi >> (8u * (bi >> 2))) & 0xFFu; hcode = (uint32_t)(bwi >> (32u + 2u * (bi >> 2))) & 3u; }
 #pragma unroll
 		for (int rr = 0; rr < RB; rr++) {
 			const uint32_t so = min(r + rr, nrows - 1) * rowbytes;
 #pragma unroll
 			for (int k = 0; k < LPR; k++) {
-				if constexpr (BS) {
-					const bool dk = ((codes >> (2 * k)) & 3u) != 0u;  // (wave-uniform)
-					d[rr * LPR + k] = MC33_LOAD(rs, dk ? 0xFFFFFFF0u : xo[k], dk ? 0u : so);
-				} else
 				if constexpr (S == 1) d[rr * LPR + k] = MC33_LOAD(rs, xo[k], so);
 				else d[rr * LPR + k] = __builtin_amdgcn_raw_buffer_load_b32(rs, xo[k], so, MC33_SWEEP_AUX);
 			}
@@ -640,7 +630,7 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 			// prefetched batch has come back as well, the other 16 still in flight.  Two copies of the batch loop, one per kind of
 			// wave, would make the counts exact in both and double a 30 KB kernel; measured instead, grouped and ungrouped shapes:
 			// profiles/r07_dead_time.txt.  The lanes left out keep the value they had, which `process` does not look at.
-			const bool wanted = ((lane / (uint32_t)RB) == bi) & !from_right & !(MC33_DEBUG_BITS(a) & 64u) & (hcode == 0u);  // (BS: a dead halo block is no load at all)
+			const bool wanted = ((lane / (uint32_t)RB) == bi) & !from_right & !(MC33_DEBUG_BITS(a) & 64u);
 			if (wanted) hv = MC33_LOAD(rs, xh, 0u);
 		} else
 		hv = MC33_LOAD(rs, ((lane / (uint32_t)RB) == bi && !from_right && !(MC33_DEBUG_BITS(a) & 64u)) ? xh : 0xFFFFFFF0u, 0u);
@@ -749,28 +739,13 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 	// compiler made a real FUNCTION of it, every captured array behind a pointer into 1.5 KiB of scratch memory per lane)
 	auto process = [&](const raw_t (&dd)[16], const real_t &hv, uint32_t p, uint32_t bi) __attribute__((always_inline)) {
 		const uint32_t r = bi * (uint32_t)RB;
-		uint32_t codes = 0u;  // (BS) as in `issue`, of the plane being processed
-		if constexpr (BS) {
-			constexpr real_t INF = std::numeric_limits<real_t>::infinity();
-			codes = (uint32_t)(bwp >> (8u * (bi >> 2))) & 0xFFu;
-			const uint32_t hcode = (uint32_t)(bwp >> (32u + 2u * (bi >> 2))) & 3u;
-			const real_t hsub = hcode == 1u ? -INF : INF;
-			halo = (lane / (uint32_t)RB) == bi ? (hcode ? hsub : hv) : halo;
-		} else
+		if constexpr (!BS) {  // (the block form has its own batches - process_next - and comes here, with bi = NB - 1, for the completion of a plane alone)
 		halo = (lane / (uint32_t)RB) == bi ? hv : halo;
 		unrolled_for<RB, (S >= 4)>([&](auto rc) __attribute__((always_inline)) {
 			const int rr = rc;
 			real_t f[4];
 #pragma unroll
 			for (int k = 0; k < 4; k++) f[k] = sample(dd, rr, k);
-			if constexpr (BS) {
-				constexpr real_t INF = std::numeric_limits<real_t>::infinity();
-#pragma unroll
-				for (int k = 0; k < 4; k++) {
-					const uint32_t ck = (codes >> (2 * k)) & 3u;  // (wave-uniform)
-					f[k] = ck ? (ck == 1u ? -INF : INF) : f[k];
-				}
-			}
 			uint64_t bwq[NI][4];  // (NI >= 2: the ballots of the row for all isovalues, parked two isovalues per EXEC switch)
 			static_for<NI>([&](auto qc) __attribute__((always_inline)) {
 				constexpr int q = decltype(qc)::value;
@@ -850,6 +825,7 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 				if (zb) { zacc[q] |= ((1ull << RB) - 1ull) << r; zcacc[q] |= zb; }
 				zmin[q] = 1; zeq[q] = 0;
 			});
+		}
 		if (bi != NB - 1) return;
 		// ---- the plane is complete ----
 		// (the forms over several isovalues sit at their register limit: the lane's number is computed afresh here - fresh_lane)
@@ -973,11 +949,146 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 
 	raw_t dA[16], dB[16];
 	real_t hA = 0, hB = 0;
+	if constexpr (BS) {
+		// ---- the block stream: a batch is one LIVE block (g, k) of the plane - the sample rows 16 g .. 16 g + 15 of quarter k, 16 loads - and
+		// a dead block costs no instruction.  Two cursors walk (plane, live block) through the functions of mc33_sweep_blocks.h: the
+		// one that issues, a batch ahead of the one that processes; each keeps the blocks of its plane it has not taken yet (rem_i, rem_p)
+		// and the word of the plane behind, asked for a plane ahead.  There is no count of batches: the loop ends when the processing
+		// cursor has completed plane z_hi.  A plane's bit rows and halo samples START as what its dead blocks are worth (plane_start)
+		// and the batches overwrite the rows of the live ones; a plane is completed when the processing cursor leaves it - at once
+		// after its last batch, and one after the other the planes in which this wave has no batch at all, so that every wave of a
+		// grouped block reaches every plane's mailbox barrier exactly once.
+		// Rows and lanes: the per-quarter form, whose batches were 4 rows, wrote the rows below 4 NB and left the lanes above them
+		// zero; so does this one (lane_in, rows_in), and the records it leaves are the same bytes.
+		// Registers (gfx950 code of k_sweep_live_blocks<0>): 115 VGPRs, no scratch, 4 waves per SIMD; 50 SGPRs parked in VGPR lanes where
+		// the per-quarter form had 43 - each cursor now carries its plane, the blocks left of it and two words through the loop.
+		const uint32_t nrg = (NB + 3u) >> 2;      // row groups that hold a row of the tile
+		const bool own_halo = !from_right;
+		const uint32_t lg = lane >> 4;            // the row group of the sample row this lane holds
+		const bool lane_in = lane < NB * 4u;
+		const uint64_t rows_in = NB >= 16u ? ~0ull : (1ull << (4u * NB)) - 1ull;
+		const uint32_t xl = xbase + lane, so_last = (nrows - 1u) * rowbytes;
+		uint64_t bwi = block_word(pl0), bwi_n = block_word(pl0 + 1u), bwp = bwi, bwp_n = bwi_n;
+		uint32_t ip = pl0, pp = pl0;
+		uint32_t rem_i = sweep_live_mask(bwi, nrg, own_halo), rem_p = rem_i;
+		// the next live block at or after the issuing cursor, through the planes that have none; past the last one (`false`) the
+		// 16 loads go through a descriptor of zero bytes - no memory access - and are never looked at.  Always 16 loads, and the halo
+		// column of the row group as the 17th with the batch of quarter 3 (sweep_live_mask sees to it that this batch exists wherever
+		// the halo block is live) under the lane condition of the other forms: see `issue`.
+		auto issue_next = [&](raw_t (&d)[16], real_t &hv) __attribute__((always_inline)) -> bool {
+			while (rem_i == 0u && ip < z_hi) {
+				++ip; bwi = bwi_n; bwi_n = block_word(ip + 1u);
+				rem_i = sweep_live_mask(bwi, nrg, own_halo);
+			}
+			const bool there = rem_i != 0u;
+			const uint32_t j = there ? sweep_next_block(rem_i, 0u) : 0u;
+			rem_i &= rem_i - 1u;
+			const uint32_t g = j >> 2, k = j & 3u;
+			const sample_t *base = a.G.p + (uint64_t)(ip - a.G.z0) * a.G.slice + (uint64_t)y0 * a.G.pitch;
+			const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, there ? tile_bytes : 0u, 0x00020000);
+			const uint32_t vo = min(xl + 64u * k, P.nx) * (uint32_t)sizeof(sample_t);
+			uint32_t so = 16u * g * rowbytes;  // (16 g < nrows: the row group holds a row of the tile)
+#pragma unroll
+			for (int rr = 0; rr < 16; rr++) {
+				d[rr] = MC33_LOAD(rs, vo, so);
+				so = min(so + rowbytes, so_last);  // (a row past the tile is the tile's last row)
+			}
+			const bool wanted = (lg == g) & lane_in & (k == 3u) & own_halo & there & !(MC33_DEBUG_BITS(a) & 64u) & (sweep_halo_code(bwi, g) == 0u);
+			if (wanted) hv = MC33_LOAD(rs, xh, 0u);
+			return there;
+		};
+		auto plane_start = [&]() __attribute__((always_inline)) {
+#pragma unroll
+			for (int k = 0; k < 4; k++) c64[0][k] = lane_in ? sweep_const_word(bwp, lg, (uint32_t)k) : 0ull;
+			halo = lane_in ? __uint_as_float(sweep_const_halo_bits(bwp, lg)) : 0.0f;
+		};
+		// the batch in dd, when there is one (`have`: only the very first call can come without), is the next block of the processing
+		// cursor; then every plane that has no block left is completed.  true: plane z_hi is complete, the tile is done.
+		auto process_next = [&](const raw_t (&dd)[16], const real_t &hv, bool have) __attribute__((always_inline)) -> bool {
+			if (have) {
+				const uint32_t j = sweep_next_block(rem_p, 0u);
+				rem_p &= rem_p - 1u;
+				const uint32_t g = j >> 2, k = j & 3u;
+				uint64_t row = 0;  // lane 16 g + rr: the bit row of sample row rr of the block
+#pragma unroll
+				for (int rr = 0; rr < 16; rr++) {
+					const real_t d = iso[0] - dd[rr];                     // MC:1852-1855
+					uint64_t bb = __ballot(sign_of(d) != 0);              // MC:1856-1859 (sign bit)
+#ifdef MC33_NAN_SAMPLES
+					bb ^= __ballot(d != d);
+#endif
+					zmin[0] = real_min(zmin[0], real_abs(d));
+					// (one lane of EXEC, one 64-bit move from the SGPR pair: see `process`)
+					const uint32_t rowsel = (uint32_t)__builtin_amdgcn_readfirstlane((int)(16u * g + (uint32_t)rr));
+					uint64_t saved;
+					asm volatile(
+					    "s_mov_b64 %1, exec\n\t"
+					    "s_lshl_b64 exec, 1, %3\n\t"
+					    "v_mov_b64 %0, %2\n\t"
+					    "s_mov_b64 exec, %1"
+					    : "+v"(row), "=&s"(saved)
+					    : "s"(bb), "s"(rowsel)
+					    : "scc");
+				}
+				const bool mine = (lg == g) & lane_in;
+#pragma unroll
+				for (int kk = 0; kk < 4; kk++) c64[0][kk] = (mine & (k == (uint32_t)kk)) ? row : c64[0][kk];
+				if (k == 3u && sweep_halo_code(bwp, g) == 0u) halo = mine ? hv : halo;  // (wave-uniform; a wave that takes its halo bits from the mailbox never looks at `halo`)
+				// a sample of the block equals the isovalue: its 16 rows are marked (a superset - k_cells lets the cell's own samples decide)
+				const uint64_t zb = __ballot(zmin[0] == 0);
+				if (zb) { zacc[0] |= (0xFFFFull << (16u * g)) & rows_in; zcacc[0] |= zb; }
+				zmin[0] = 1;
+			}
+			while (rem_p == 0u) {
+				process(dd, hv, pp, NB - 1u);  // (the completion of plane pp: its bit rows, halo samples and marks are handed on)
+				if (pp == z_hi) {
+					// (the batch prefetched past the end is waited for HERE: left in flight, the way out met the loop's back edge with loads
+					// pending on registers the plane's rows had moved into, and the compiler's wait for them - vmcnt(0), read in the gfx950
+					// code - stood in the block both paths share: every second batch waited for the one just issued)
+					__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+					return true;
+				}
+				++pp; bwp = bwp_n; bwp_n = block_word(pp + 1u);
+				rem_p = sweep_live_mask(bwp, nrg, own_halo);
+				plane_start();
+			}
+			return false;
+		};
+		if (!dead_me) {  // (a wave without a tile - the last quad of a list, never in a grouped block - has no plane to complete)
+			plane_start();
+			bool have = rem_p != 0u;
+#ifdef MC33_DEV  // MC33_HIP_DEBUG 16384: the loads alone - every batch waited for and dropped, no classification at all
+			if (MC33_DEBUG_BITS(a) & 16384u) {
+				auto drop = [&](const raw_t (&dd)[16], const real_t &hv) __attribute__((always_inline)) {
+#pragma unroll
+					for (int k = 0; k < 16; k++) asm volatile("" ::"v"(dd[k]));
+					asm volatile("" ::"v"(hv));
+				};
+				bool more = issue_next(dA, hA);
+				while (more) {
+					more = issue_next(dB, hB);
+					drop(dA, hA);
+					if (!more) break;
+					more = issue_next(dA, hA);
+					drop(dB, hB);
+				}
+				return;
+			}
+#endif
+			if (have) issue_next(dA, hA);
+			for (;;) {
+				issue_next(dB, hB);
+				if (process_next(dA, hA, have)) break;
+				issue_next(dA, hA);
+				if (process_next(dB, hB, true)) break;
+				have = true;
+			}
+		}
+	} else {
 	uint32_t ip = pl0, ib = 0, pp = pl0, pb = 0;  // (plane, batch) of the next issue / of the next process
 	// past the end of the tile the prefetch simply re-reads the last batch (it is never processed)
-	// (BS: a new plane takes the word that was asked for when the plane before it began, and asks for the next one)
-#define MC33_ADV(p_, b_, w_, wn_) do { if (++(b_) == NB) { (b_) = 0; ++(p_); if constexpr (BS) { (w_) = (wn_); (wn_) = block_word((p_) + 1u); } } } while (0)
-#define MC33_ADV_ISSUE() do { if (ip != z_hi || ib + 1 != NB) MC33_ADV(ip, ib, bwi, bwi_n); } while (0)
+#define MC33_ADV(p_, b_) do { if (++(b_) == NB) { (b_) = 0; ++(p_); } } while (0)
+#define MC33_ADV_ISSUE() do { if (ip != z_hi || ib + 1 != NB) MC33_ADV(ip, ib); } while (0)
 	// (Tried in round 3: the loads that refill a buffer issued as soon as its rows are bit rows, BEFORE the work on a complete
 	// plane, so that two batches stay in flight during that work and a hand-over's stores are younger than the refill.  The
 	// refill's registers are then live across the plane's work: 92 -> 134 VGPRs for one isovalue per pass = 3 waves per SIMD
@@ -1003,9 +1114,10 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs &a) {
 #endif
 	for (uint32_t t = 0; t < T; t += 2) {
 		issue(dB, hB, ip, ib); MC33_ADV_ISSUE();
-		process(dA, hA, pp, pb); MC33_ADV(pp, pb, bwp, bwp_n);
+		process(dA, hA, pp, pb); MC33_ADV(pp, pb);
 		issue(dA, hA, ip, ib); MC33_ADV_ISSUE();
-		if (t + 1 < T) { process(dB, hB, pp, pb); MC33_ADV(pp, pb, bwp, bwp_n); }
+		if (t + 1 < T) { process(dB, hB, pp, pb); MC33_ADV(pp, pb); }
+	}
 	}
 	log_flush();  // (DEFER: everything the tile hands on, behind its last load)
 	if constexpr (NI >= 2) {
