@@ -3,33 +3,16 @@ tests/test_gpu_sweep_plan_golden.py: after every step the plan in force as mc33h
 z_hi} in launch order, info[] = tiles, resident blocks, plan bit - and mc33hip_sweep_plan_weight.  The file records what the
 library planned BEFORE planning moved into mc33_sweep_plan.h; a change that is meant to alter a plan records it again.
 
-Fields and isovalues are those of tests/test_gpu_range_skip.py, test_gpu_sweep_refill.py and test_gpu_sweep_pack.py.  Shapes are
-points z, y, x.  A sequence is (name, shape, environment, steps); the environment is read when the context is made."""
+Shapes, isovalues and fields (steep, banded) are those of tests/sweep_harness.py.  Shapes are points z, y, x.  A sequence is (name, shape, environment, steps); the environment is read when the context is made."""
 import ctypes as C
 import os
 
 import numpy as np
 
-A, B, BIG, SHALLOW = (48, 200, 520), (40, 70, 1030), (160, 130, 1030), (12, 130, 1030)
-STEEP_ISO = {A: 1840.0, B: 1930.5, BIG: 2600.5, SHALLOW: 2600.5}
-LOW = (100.5, 50.5, 150.25, 200.0, 20.5, 120.75, 180.5, 220.0)
-HIGH = 1100.5
+from sweep_harness import A, B, BIG, HIGH, LOW, SHALLOW, STEEP_ISO, banded, steep
+
 ONE_ROUND = {"MC33_HIP_SWEEP_BLOCKS_PER_CU": "1", "MC33_HIP_LIVE": "1"}   # BIG: one block per compute unit, every sweep with a table by a list
 GHOST_FROM = 17                                                       # the sub-range of B: slices 17 .. 39 with a ghost slice below
-
-
-def steep(shape):
-    z, y, x = np.ogrid[:shape[0], :shape[1], :shape[2]]
-    return (3 * x + 5 * y + z).astype(np.float32)
-
-
-def banded(z0):
-    """BIG: every strip below plane z0 straddles the isovalues LOW, every strip from z0 on HIGH"""
-    x = np.arange(BIG[2])
-    row = np.where(x < 1024, x % 256, 50 * (x - 1024)).astype(np.float32)
-    data = np.ascontiguousarray(np.broadcast_to(row, BIG))
-    data[z0:] += 1000.0
-    return data
 
 
 def thrice(iso):

@@ -1,7 +1,7 @@
 """GPU tests of the block sweep's batch stream (a batch of k_sweep_live_blocks is one LIVE 64 x 16 block of a plane,
 a dead block costs no instruction, and a plane's bit rows start as what its dead blocks are worth): surfaces against the
 unmodified reference's (oracle/_ref) on the dense numpy array, bit for bit, with the fields, helpers and comparison of
-tests/test_gpu_range_skip.py and tests/test_gpu_range_blocks.py.  There is no tolerance in this file.
+tests/sweep_harness.py.  There is no tolerance in this file.
 
 Shapes (points z, y, x): B = 40 x 70 x 1030 - five segments: one grouped block of four waves, whose first three take their halo
 bits from the mailbox, and one ungrouped wave; two y tiles, the second of 7 rows (one row group, two batches' worth of rows in
@@ -15,20 +15,12 @@ import numpy as np
 import pytest
 
 import range_blocks_rules as br
-import test_gpu_range_skip as rs
-from test_gpu_range_blocks import C3, alias_cells, left_out, live_mask, words_of
-from test_gpu_range_skip import B, grid_of, reference, same, steep, to_device
+from sweep_harness import (B, C3, alias_cells, blocks_always, grid_of, left_out, live_list_always, live_mask, plan_of, reference, same,  # noqa: F401
+                           same_arrays, steep, to_device, words_of)   # (blocks_always, live_list_always: the module's fixtures)
 
 pytestmark = pytest.mark.gpu
 
 C3_ISO = 700.5   # (steep(C3) runs from 0 to 1565)
-
-
-@pytest.fixture(autouse=True)
-def live_list_always(monkeypatch):
-    """the grids of this file are small: MC33_HIP_LIVE=1, read when a context is made, gives every sweep with a table its list"""
-    monkeypatch.setenv("MC33_HIP_LIVE", "1")
-    monkeypatch.setenv("MC33_HIP_BLOCKS", "1")
 
 
 def two_slabs(shape):
@@ -158,7 +150,7 @@ def test_nothing_dead(reflibs, monkeypatch):
     g0 = grid_of(to_device(data))
     for rep in range(3):
         off = g0.extract(0.5)
-    rs.same_arrays(on, off, "every block live, with and without the block stream")
+    same_arrays(on, off, "every block live, with and without the block stream")
     g.close(); g0.close()
 
 
@@ -189,7 +181,7 @@ def test_equal_to_the_isovalue_beside_dead_blocks(reflibs, monkeypatch):
     g0 = grid_of(to_device(data))
     for rep in range(3):
         off = g0.extract(0.0)
-    rs.same_arrays(on, off, "samples equal to the isovalue")
+    same_arrays(on, off, "samples equal to the isovalue")
     assert on_alias == alias_cells(g0) and on_alias > 0
     g.close(); g0.close()
 
@@ -208,7 +200,7 @@ def test_negative_zero_on_zeros_with_a_bump(monkeypatch):
     g0 = grid_of(to_device(data))
     for rep in range(3):
         off = g0.extract(-0.0)
-    rs.same_arrays(on, off, "iso -0.0 on zeros")
+    same_arrays(on, off, "iso -0.0 on zeros")
     assert alias_cells(g) == alias_cells(g0)
     g.close(); g0.close()
 
@@ -229,7 +221,6 @@ def test_a_deep_tile(reflibs, monkeypatch):
     monkeypatch.setenv("MC33_HIP_MIN_DEPTH", str(B[0] - 1))
     data = wandering(B)
     g, ref = run_case(reflibs, data, 0.0, ("batches", "wandering B"), "deep tile")
-    from test_gpu_sweep_refill import plan_of
     tiles = plan_of(g)[0]
     assert (tiles[:, 3] - tiles[:, 2]).min() == B[0] - 1, "the tiles are not the grid's depth"
     g.close()

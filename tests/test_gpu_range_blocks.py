@@ -2,73 +2,19 @@
 include/mc33_hip.h: mc33hip_range_blocks, mc33hip_block_words, mc33hip_sweep_skipped_blocks): k_ranges' block entries and
 k_block_verdicts' words against the numpy restatement of tests/range_blocks_rules.py, and the surfaces of sweeps whose loads are
 left out against the unmodified reference's (oracle/_ref) on the dense numpy array, bit for bit, with the fields, helpers and
-comparison of tests/test_gpu_range_skip.py and tests/test_gpu_sweep_pack.py.  There is no tolerance in this file.
+comparison of tests/sweep_harness.py.  There is no tolerance in this file.
 
 Shapes (points z, y, x): A = 48 x 200 x 520, B = 40 x 70 x 1030, and C3 = 24 x 130 x 300, whose second segment has 44 samples -
 quarter 0 of it partly, quarters 1 - 3 wholly clamped to the grid's last column - and whose third y tile has 4 rows."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import range_blocks_rules as br
-import test_gpu_range_skip as rs
-from test_gpu_range_skip import A, B, STEEP_ISO, grid_of, numpy_table, reference, same, steep, to_device
-from test_gpu_sweep_pack import mixed_whole
-from test_gpu_sweep_refill import numpy_verdicts, plan_of
+from sweep_harness import (A, B, C3, REAL, STEEP_ISO, alias_cells, blocks_always, blocks_of, grid_of, left_out, live_list_always, live_mask,  # noqa: F401
+                           mixed_whole, reference, same, same_arrays, steep, table_of, to_device, two_slab_case, typed, words,
+                           words_of)   # (blocks_always, live_list_always: the module's fixtures)
 
 pytestmark = pytest.mark.gpu
-
-C3 = (24, 130, 300)
-
-
-@pytest.fixture(autouse=True)
-def live_list_always(monkeypatch):
-    """the grids of this file are small: MC33_HIP_LIVE=1, read when a context is made, gives every sweep with a table its list"""
-    monkeypatch.setenv("MC33_HIP_LIVE", "1")
-    monkeypatch.setenv("MC33_HIP_BLOCKS", "1")
-
-
-def blocks_of(g, dtype):
-    a = g.tensor
-    nyt, nseg = br.dims((a.shape[0], a.shape[1], g.desc.npx))
-    t = np.empty((a.shape[0], nyt, nseg, br.BLOCKS, 2), rs.REAL[dtype])
-    rc = g.lib.mc33hip_range_blocks(g.ctx, C.c_void_p(t.ctypes.data), t.nbytes)
-    assert rc in (0, rs.EINVAL), rc
-    return t if rc == 0 else None
-
-
-def words_of(g):
-    a = g.tensor
-    nyt, nseg = br.dims((a.shape[0], a.shape[1], g.desc.npx))
-    w = np.empty((a.shape[0], nyt, nseg), np.uint64)
-    assert g.lib.mc33hip_block_words(g.ctx, C.c_void_p(w.ctypes.data), w.nbytes) == 0
-    return w
-
-
-def left_out(g):
-    out = (C.c_ulonglong * 3)()
-    assert g.lib.mc33hip_sweep_skipped_blocks(g.ctx, C.byref(out)) == 0
-    return tuple(int(x) for x in out)
-
-
-def alias_cells(g):
-    out = C.c_ulonglong(0)
-    assert g.lib.mc33hip_alias_cells(g.ctx, C.byref(out)) == 0
-    return int(out.value)
-
-
-def live_mask(g, data, iso, zs=0, plane0=0):
-    """the strips the live tiles of the plan in force read, from numpy's own verdicts"""
-    tiles = plan_of(g)[0]
-    dead = numpy_verdicts(tiles, numpy_table(data, "f32"), (iso,), zs, plane0)[0]
-    nyt, nseg = br.dims(data.shape)
-    return br.live_strips(tiles, dead, data.shape[0], nyt, nseg, zs, plane0)
-
-
-def typed(dtype, shape):
-    r = rs.ramp(shape, 3, 5, 1)
-    return (r // 16).astype(np.uint8) if dtype == "u8" else r.astype(rs.NP[dtype])
 
 
 # ---- 1. the block table against numpy ---------------------------------------------------------------------------------------------------
@@ -84,10 +30,10 @@ def test_block_table_is_numpys(shape, dtype):
     g.extract(iso)
     t = blocks_of(g, dtype)
     assert t is not None
-    want = br.numpy_blocks(data, rs.REAL[dtype])
-    assert np.array_equal(rs.words(t), rs.words(want)), (shape, dtype, np.argwhere(rs.words(t) != rs.words(want))[:5])
+    want = br.numpy_blocks(data, REAL[dtype])
+    assert np.array_equal(words(t), words(want)), (shape, dtype, np.argwhere(words(t) != words(want))[:5])
     # the strip's own entry is the minimum and maximum over its blocks
-    coarse = rs.table_of(g, dtype)
+    coarse = table_of(g, dtype)
     assert np.array_equal(coarse[..., 0], want[..., 0].min(axis=3)) and np.array_equal(coarse[..., 1], want[..., 1].max(axis=3))
     g.close()
 
@@ -104,7 +50,7 @@ def test_block_table_sample_by_sample():
     g = grid_of(view)
     for rep in range(2):
         g.extract(STEEP_ISO[A])
-    assert np.array_equal(rs.words(blocks_of(g, "f32")), rs.words(br.numpy_blocks(data, np.float32)))
+    assert np.array_equal(words(blocks_of(g, "f32")), words(br.numpy_blocks(data, np.float32)))
     g.close()
 
 
@@ -115,7 +61,7 @@ def test_one_nan_is_one_block():
     for rep in range(2):
         g.extract(STEEP_ISO[A])
     t = blocks_of(g, "f32")
-    assert np.array_equal(rs.words(t), rs.words(br.numpy_blocks(data, np.float32)))
+    assert np.array_equal(words(t), words(br.numpy_blocks(data, np.float32)))
     inf = np.argwhere(np.isinf(t[..., 0]))
     assert inf.tolist() == [[5, 0, 0, 0]] and t[5, 0, 0, 0].tolist() == [-np.inf, np.inf] and np.isfinite(t[5, 0, 0, 1:]).all()
     g.close()
@@ -222,39 +168,13 @@ def test_surface_with_blocks_left_out(reflibs, monkeypatch, case):
 
 def test_sub_range_with_a_ghost_plane(reflibs):
     """the upper z-slab of B as a window with plane0 > 0 and a ghost slice; the two slabs together are the whole surface"""
-    import torch
-    from mc33_c_library_amd import DeviceGrid, Range
-    data = steep(B)
     iso = STEEP_ISO[B]
-    ref = reference(reflibs, ("steep", B), "f32", data, iso)
-    t = to_device(data)
-    nz_total = B[0] - 1
-    zb = 17
-    parts = []
-    for lo_plane, hi_plane, r in ((0, zb + 2, Range(0, zb, 0, 0)), (zb - 2, B[0], Range(zb, nz_total, 1, 0))):
-        g = DeviceGrid(t[lo_plane:hi_plane], nz_total=nz_total, plane0=lo_plane)
-        g.set_timing(1)
-        cnts = [g.count(iso, r) for rep in range(3)]
-        assert len({(c.nV, c.nT) for c in cnts}) == 1
-        window = data[lo_plane:hi_plane]
-        tiles = plan_of(g)[0]
-        zs = zb - 1 if lo_plane else 0
-        dead = numpy_verdicts(tiles, numpy_table(window, "f32"), (iso,), zs, lo_plane)[0]
-        nyt, nseg = br.dims(window.shape)
-        live = br.live_strips(tiles, dead, window.shape[0], nyt, nseg, zs, lo_plane)
+
+    def blocks_were_left_out(g, window, lo_plane, zs, cnts):
+        live = live_mask(g, window, iso, zs, lo_plane)
         want = br.left_out(br.numpy_blocks(window, np.float32), iso, live)
         assert left_out(g) == want and want[1] > 0 and want[2] > 0, (lo_plane, left_out(g), want)
-        c = cnts[-1]
-        V = torch.empty((max(c.nV, 1), 3), dtype=torch.float32, device="cuda")
-        N = torch.empty_like(V)
-        T = torch.empty((max(c.nT, 1), 3), dtype=torch.int32, device="cuda")
-        g.emit_into(V, N, T, sum(p[3] for p in parts))
-        torch.cuda.synchronize()
-        parts.append((V[:c.nV].cpu().numpy(), N[:c.nV].cpu().numpy(), T[:c.nT].cpu().numpy().view(np.uint32), c.nV))
-        g.close()
-    assert np.array_equal(np.concatenate([p[2] for p in parts]), ref.T)
-    assert np.array_equal(rs.words(np.concatenate([p[0] for p in parts])), rs.words(ref.V))
-    assert np.array_equal(rs.words(np.concatenate([p[1] for p in parts])), rs.words(ref.N))
+    two_slab_case(reflibs, blocks_were_left_out, timing=1)
 
 
 # ---- 5. the switch, and samples that change ------------------------------------------------------------------------------------------
@@ -275,8 +195,8 @@ def test_blocks_off_gives_the_same_bytes(reflibs, monkeypatch):
     for rep in range(3):
         off = g0.extract(iso)
     same(off, ref, "MC33_HIP_BLOCKS=0")
-    rs.same_arrays(on, off, "with and without blocks left out")
-    assert left_out(g0) == (0, 0, 0) and blocks_of(g0, "f32") is None and rs.table_of(g0, "f32") is not None
+    same_arrays(on, off, "with and without blocks left out")
+    assert left_out(g0) == (0, 0, 0) and blocks_of(g0, "f32") is None and table_of(g0, "f32") is not None
     g.close(); g0.close()
 
 
@@ -302,7 +222,7 @@ def test_a_write_into_a_block_that_was_left_out(reflibs):
     assert ref1.nV > reference(reflibs, ("steep", A), "f32", steep(A), iso).nV
     for rep in range(3):
         same(g.extract(iso), ref1, ("after the write", rep))
-    assert np.array_equal(rs.words(blocks_of(g, "f32")), rs.words(br.numpy_blocks(data, np.float32)))
+    assert np.array_equal(words(blocks_of(g, "f32")), words(br.numpy_blocks(data, np.float32)))
     g.close()
 
 

@@ -10,163 +10,21 @@ Shapes (points z, y, x): A = 48 x 200 x 520 - three row segments, the last one 8
 four y tiles, the last of 11 sample rows.  B = 40 x 70 x 1030 - a whole group of four segments and a fifth; a second y tile of 7
 rows.  Both with tiles 1, 2 and 16 planes deep (MC33_HIP_RZ / MC33_HIP_MIN_DEPTH, read when a context is made).
 Each case extracts three times - without a table, with the table just built, with the table kept - and once more in a context
-that never builds one."""
+that never builds one.  Fields, helpers and the comparison are those of tests/sweep_harness.py."""
 import ctypes as C
-import warnings
 
 import numpy as np
 import pytest
 
+from sweep_harness import (A, B, DEPTHS, MANY, NP, STEEP_ISO, dead_columns, depth_fixture, four_runs, grid_of, numpy_table, planned_tiles, ramp,
+                           ramp_isos, reference, same, same_arrays, skipped, steep, table_of, to_device, two_slab_case, typed_ramp, words)
+
 pytestmark = pytest.mark.gpu
 
-NP = {"f32": np.float32, "f64": np.float64, "u8": np.uint8, "u16": np.uint16, "u32": np.uint32}
-REAL = {"f32": np.float32, "f64": np.float64, "u8": np.float32, "u16": np.float32, "u32": np.float32}
-A, B = (48, 200, 520), (40, 70, 1030)
-DEPTHS = (1, 2, 16)
-EINVAL = -1
-
-
-def ramp(shape, cx=1, cy=2, cz=3, off=0):
-    z, y, x = np.ogrid[:shape[0], :shape[1], :shape[2]]
-    return cx * x + cy * y + cz * z + off  # int64
-
-
-def strips(shape):
-    """(yt, seg, rows, columns) of every strip of a plane: both ends inclusive"""
-    ny, nx = shape[1] - 1, shape[2] - 1
-    for yt in range((ny + 62) // 63):
-        for seg in range((nx + 255) // 256):
-            yield yt, seg, slice(63 * yt, min(63 * yt + 63, ny) + 1), slice(256 * seg, min(256 * seg + 256, nx) + 1)
-
-
-def numpy_table(a, dtype):
-    """[plane][yt][seg]{min, max} of the samples converted to MC33_real; {-inf, +inf} where a strip holds a NaN"""
-    r = a.astype(REAL[dtype])
-    nyt, nseg = (a.shape[1] - 1 + 62) // 63, (a.shape[2] - 1 + 255) // 256
-    t = np.empty((a.shape[0], nyt, nseg, 2), REAL[dtype])
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        for yt, seg, ys, xs in strips(a.shape):
-            blk = r[:, ys, xs].reshape(a.shape[0], -1)
-            bad = np.isnan(blk).any(axis=1)
-            t[:, yt, seg, 0] = np.where(bad, -np.inf, np.nanmin(blk, axis=1))
-            t[:, yt, seg, 1] = np.where(bad, np.inf, np.nanmax(blk, axis=1))
-    return t
-
-
-def to_device(a):
-    import torch
-    v = a.view(np.int16) if a.dtype == np.uint16 else a.view(np.int32) if a.dtype == np.uint32 else a
-    return torch.from_numpy(np.ascontiguousarray(v)).cuda()
-
-
-def words(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype.itemsize == 8 else np.uint32)
-
-
-def same(got, ref, what):
-    V, N, T, cnt = got
-    assert (cnt.nV, cnt.nT) == (ref.nV, ref.nT), what
-    v, n, t = V.cpu().numpy(), N.cpu().numpy(), T.cpu().numpy().view(np.uint32)
-    assert v.dtype == ref.V.dtype and v.shape == ref.V.shape and n.shape == ref.N.shape, what
-    assert np.array_equal(t, ref.T), what
-    # (a NaN of the surface - a vertex interpolated from a NaN or infinite sample - is a NaN in the same place; which NaN is not
-    # defined, as everywhere in this suite: tests/test_gpu_parity.py, test_gpu_sweep_halo.py)
-    bad = []
-    for x, y in ((v, ref.V), (n, ref.N)):
-        assert np.array_equal(np.isnan(x), np.isnan(y)), what
-        bad.append(int(np.count_nonzero((words(x) != words(y)) & ~np.isnan(y))))
-    assert bad == [0, 0], "%s: %d position words, %d normal words differ" % (what, bad[0], bad[1])
-
-
-def same_arrays(got, want, what):
-    (V, N, T, cnt), (V2, N2, T2, cnt2) = got, want
-    assert (cnt.nV, cnt.nT) == (cnt2.nV, cnt2.nT), what
-    for x, y in ((V, V2), (N, N2), (T, T2)):
-        assert np.array_equal(words(x.cpu().numpy()), words(y.cpu().numpy())), what
-
-
-def table_of(g, dtype):
-    """the library's table, or None when it has none (EINVAL)"""
-    a = g.tensor
-    t = np.empty((a.shape[0], (a.shape[1] - 1 + 62) // 63, (g.desc.npx - 1 + 255) // 256, 2), REAL[dtype])
-    rc = g.lib.mc33hip_range_table(g.ctx, C.c_void_p(t.ctypes.data), t.nbytes)
-    assert rc in (0, EINVAL), rc
-    return t if rc == 0 else None
-
-
-def skipped(g):
-    out = (C.c_ulonglong * 3)()
-    assert g.lib.mc33hip_sweep_skipped(g.ctx, C.byref(out)) == 0
-    return tuple(out)
-
-
-_refs = {}
-
-
-def reference(reflibs, key, dtype, data, iso):
-    k = (key, dtype, repr(float(iso)))
-    if k not in _refs:
-        _refs[k] = reflibs[dtype].isosurface(data, iso)
-    return _refs[k]
-
-
-@pytest.fixture(params=DEPTHS)
-def depth(request, monkeypatch):
-    monkeypatch.setenv("MC33_HIP_RZ", str(request.param))
-    monkeypatch.setenv("MC33_HIP_MIN_DEPTH", str(request.param))
-    return request.param
-
-
-def four_runs(monkeypatch, make, isos, refs, dtype, data, what):
-    """first extraction (no table), second (built and used), third (kept), and a context that never builds one"""
-    g = make()
-    assert table_of(g, dtype) is None
-    for rep in range(3):
-        for iso, ref in zip(isos, refs):
-            same(g.extract(iso), ref, (what, iso, "extraction %d" % (rep + 1)))
-        if rep == 0 and len(isos) == 1:
-            assert table_of(g, dtype) is None, "a table after ONE sweep"
-    t = table_of(g, dtype)
-    assert t is not None
-    assert np.array_equal(words(t), words(numpy_table(data, dtype))), (what, "the table differs from numpy's")
-    g.close()
-    monkeypatch.setenv("MC33_HIP_RANGES", "0")
-    g = make()
-    for rep in range(2):
-        for iso, ref in zip(isos, refs):
-            same(g.extract(iso), ref, (what, iso, "MC33_HIP_RANGES=0"))
-    assert table_of(g, dtype) is None
-    g.close()
-    monkeypatch.delenv("MC33_HIP_RANGES")
-
-
-def grid_of(t, **kw):
-    from mc33_c_library_amd import DeviceGrid
-    return DeviceGrid(t, **kw)
+depth = depth_fixture(DEPTHS)   # (no live_list_always here: these tests run without MC33_HIP_LIVE)
 
 
 # ---- integer-valued ramps, isovalues on the strips' own ends ---------------------------------------------------------------------------
-
-def typed_ramp(dtype, shape):
-    r = ramp(shape)
-    if dtype == "u8":
-        return (r // 5).astype(np.uint8)        # 0 .. 211
-    if dtype == "u32":
-        return (r * 4000000 + 77).astype(np.uint32)  # up to 4.2e9: (float)F is not one to one
-    return r.astype(NP[dtype])
-
-
-def ramp_isos(dtype, data):
-    """of the strip (plane 20, y tile 1, segment 1): exactly its minimum, exactly its maximum - which is its halo-column sample of the
-    row it shares with the next y tile - and half-integers beside both"""
-    t = numpy_table(data, dtype)
-    lo, hi = float(t[20, 1, 1, 0]), float(t[20, 1, 1, 1])
-    assert hi == float(REAL[dtype](data[20, min(126, data.shape[1] - 1), 512]))
-    half = 0.5 if dtype != "u32" else 2000000.0
-    return (lo, hi, lo + half, hi - half)
-
 
 @pytest.mark.parametrize("shape", [A, B], ids=["A", "B"])
 def test_float_ramp(reflibs, monkeypatch, depth, shape):
@@ -207,40 +65,6 @@ def test_either_zero_on_a_ramp_through_zero(reflibs, monkeypatch, depth):
 
 
 # ---- a steep ramp: whole columns of tiles on one side ------------------------------------------------------------------------------------
-
-STEEP_ISO = {A: 1840.0, B: 1930.5}
-
-
-def steep(shape):
-    return ramp(shape, 3, 5, 1).astype(np.float32)
-
-
-def dead_columns(data, iso, dtype="f32"):
-    """(columns all of whose strips lie below the isovalue, above it, columns in all) - from numpy alone"""
-    t = numpy_table(data, dtype)
-    below, above = (t[..., 1] < iso).all(axis=0), (t[..., 0] > iso).all(axis=0)
-    return int(below.sum()), int(above.sum()), below.size
-
-
-def planned_tiles(shape, depth):
-    """{(yt, seg): tiles} - a lower bound of the tiles plan_tiles (mc33_sweep_plan.h) cuts every column into, restated from its
-    arithmetic for float samples (batches of 4 sample rows) with MC33_HIP_RZ = MC33_HIP_MIN_DEPTH = depth, on a grid so small that
-    what the device holds at once does not cap the plan: the work of a wave per slice is its sample rows in whole batches, the
-    plan wants B = W nzc / (64 depth) tiles, and a group of segments gets floor(B w / W) z pieces (one at least, a slice each at
-    most); the remainder goes to the groups with the largest fractions, one piece more each - not counted here."""
-    ny, nx, nzc = shape[1] - 1, shape[2] - 1, shape[0] - 1
-    nseg, nyt = (nx + 255) // 256, (ny + 62) // 63
-    groups = [(yt, xg, min(4, nseg - 4 * xg), (min(64, ny + 1 - 63 * yt) + 3) // 4 * 4) for yt in range(nyt) for xg in range((nseg + 3) // 4)]
-    W = float(sum(w * waves for _, _, waves, w in groups))
-    Bt = max(1, int(W * nzc / (64.0 * depth)))
-    assert Bt < 1024  # (far below the wave slots of any device this runs on)
-    out = {}
-    for yt, xg, waves, w in groups:
-        n = int(min(max(1.0, np.floor(Bt * w / W)), nzc))
-        for seg in range(4 * xg, 4 * xg + waves):
-            out[(yt, seg)] = n
-    return out
-
 
 @pytest.mark.parametrize("shape", [A, B], ids=["A", "B"])
 def test_skipping_really_happens(reflibs, depth, shape):
@@ -305,11 +129,6 @@ def test_nan_and_infinities_in_dead_strips(reflibs, monkeypatch, depth):
 
 # ---- several isovalues per pass: dead for one, live for another ------------------------------------------------------------------------------
 
-MANY = {("f32", A): (1840.0, 300.5, 2400.0, 1200.25), ("u8", A): (100.5, 20.5, 180.5, 60.5), ("u16", A): (500.5, 100.5, 900.5, 700.5),
-        # shape B: inside the group of four segments, segment 0 lies below all four isovalues, segment 3 above, 1 and 2 are cut
-        ("f32", B): (1930.5, 1700.5, 2100.25, 1800.0), ("u16", B): (600.5, 560.5, 700.5, 650.5)}
-
-
 @pytest.mark.parametrize("dtype,shape", [("f32", A), ("u8", A), ("u16", A), ("f32", B), ("u16", B)], ids=["f32-A", "u8-A", "u16-A", "f32-B", "u16-B"])
 def test_several_isovalues_per_pass(reflibs, monkeypatch, depth, dtype, shape):
     data = steep(shape) if dtype == "f32" else typed_ramp(dtype, shape)
@@ -351,35 +170,10 @@ def test_several_isovalues_per_pass(reflibs, monkeypatch, depth, dtype, shape):
 @pytest.mark.parametrize("shape", [A, B], ids=["A", "B"])
 def test_sub_range_with_a_ghost_plane_and_a_slab_above_plane_zero(reflibs, depth, shape):
     """two z-slabs as windows of one tensor: the upper one with plane0 > 0 and a ghost slice below its range"""
-    import torch
-    from mc33_c_library_amd import DeviceGrid, Range
-    data = steep(shape)
-    iso = STEEP_ISO[shape]
-    ref = reference(reflibs, ("steep", shape), "f32", data, iso)
-    t = to_device(data)
-    nz_total = shape[0] - 1
-    bounds = [0, 17, nz_total]
-    Vs, Ns, Ts, base = [], [], [], 0
-    for zb, ze in zip(bounds[:-1], bounds[1:]):
-        ghost = 1 if zb else 0
-        p_lo, p_hi = max(zb - ghost - 1, 0), min(ze + 1, nz_total)
-        g = DeviceGrid(t[p_lo:p_hi + 1], nz_total=nz_total, plane0=p_lo)
-        rng = Range(zb, ze, ghost, 0)
-        cnts = [g.count(iso, rng) for rep in range(3)]
-        assert len({(c.nV, c.nT) for c in cnts}) == 1
+    def the_table_is_numpys(g, window, lo_plane, zs, cnts):
         tab = table_of(g, "f32")
-        assert tab is not None and np.array_equal(words(tab), words(numpy_table(data[p_lo:p_hi + 1], "f32")))
-        c = cnts[-1]
-        V = torch.empty((max(c.nV, 1), 3), dtype=torch.float32, device="cuda")
-        N = torch.empty_like(V)
-        T = torch.empty((max(c.nT, 1), 3), dtype=torch.int32, device="cuda")
-        g.emit_into(V, N, T, base)
-        torch.cuda.synchronize()
-        Vs.append(V[:c.nV].cpu().numpy()); Ns.append(N[:c.nV].cpu().numpy()); Ts.append(T[:c.nT].cpu().numpy().view(np.uint32))
-        base += c.nV
-        g.close()
-    assert np.array_equal(np.concatenate(Ts), ref.T)
-    assert np.array_equal(words(np.concatenate(Vs)), words(ref.V)) and np.array_equal(words(np.concatenate(Ns)), words(ref.N))
+        assert tab is not None and np.array_equal(words(tab), words(numpy_table(window, "f32")))
+    two_slab_case(reflibs, the_table_is_numpys, shape)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "u8", "f64"])

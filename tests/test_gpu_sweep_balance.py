@@ -3,62 +3,17 @@ blocks out shares its tiles out by batches + the weight of a plane, every other 
 weight of its plan beside the target; and at the device's own residency such a plan goes by a fill and a band of its own.
 
 Every surface is compared with the unmodified reference's (oracle/_ref) on the dense numpy array, bit for bit, with the fields,
-helpers and comparison of tests/test_gpu_range_skip.py, tests/test_gpu_sweep_refill.py and tests/test_gpu_sweep_pack.py.  There is
-no tolerance in this file.  The plans are held to the numpy restatement of the share rule (tests/sweep_plan_rules.py)."""
-import ctypes as C
-
+helpers and comparison of tests/sweep_harness.py.  There is no tolerance in this file.  The plans are held to the numpy restatement of the share rule (tests/sweep_plan_rules.py)."""
 import numpy as np
 import pytest
 
 import sweep_pack_rules as pr
 import sweep_plan_rules as sp
-import test_gpu_range_skip as rs
-from test_gpu_range_skip import A, B, STEEP_ISO, grid_of, reference, same, steep, table_of, to_device
-from test_gpu_sweep_pack import HIGH, LOW, banded, by_the_rule, check_packed, packed_of
-from test_gpu_sweep_refill import BIG, plan_of
+from sweep_harness import (A, B, BIG, HIGH, LOW, STEEP_ISO, banded, by_the_rule, check_packed, check_plan, grid_of, live_everywhere,  # noqa: F401
+                           live_list_always, numpy_table, packed_of, plan_of, reference, same, steep, table_of, to_device, two_slab_case,
+                           weight_of, words_of)   # (live_list_always: the module's fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def live_list_always(monkeypatch):
-    """the grids of this file are small: MC33_HIP_LIVE=1, read when a context is made, gives every sweep with a table its list"""
-    monkeypatch.setenv("MC33_HIP_LIVE", "1")
-
-
-def weight_of(g):
-    w = C.c_double(-1.0)
-    assert g.lib.mc33hip_sweep_plan_weight(g.ctx, C.byref(w)) == 0
-    return w.value
-
-
-def check_plan(g, shape, what, asked=None):
-    """the plan in force is the share rule's with the weight the library reports: chunks per column for the target `asked` - or,
-    where only the fill rule knows the target, for some target no more than a block of waves per column below the tiles there
-    are - and every column cut into that many pieces of planes as equal as whole planes allow.  Returns (weight, chunks)."""
-    tiles, resident, which = plan_of(g)
-    weight = weight_of(g)
-    t = tiles.astype(np.int64)
-    zs, ze = int(t[:, 2].min()), int(t[:, 3].max())
-    nzc = ze - zs
-    cols = sp.columns(shape)
-    chunks = sp.plan_chunks(tiles, shape)
-    assert sum(c * col[2] for c, col in zip(chunks, cols)) == len(tiles), what
-    for (yt, xg, waves, _), n in zip(cols, chunks):
-        for seg in range(4 * xg, 4 * xg + waves):
-            mine = t[(t[:, 0] == seg) & (t[:, 1] == yt)]
-            mine = mine[np.argsort(mine[:, 2])]
-            k = np.arange(n)
-            assert np.array_equal(mine[:, 2], zs + nzc * k // n) and np.array_equal(mine[:, 3], zs + nzc * (k + 1) // n), (what, yt, seg)
-    fits = []
-    for target in ([asked] if asked else range(max(1, len(tiles) - 4 * len(cols)), len(tiles) + 1)):
-        try:
-            sp.check_chunks(chunks, cols, target, nzc, weight, unit=4.0)
-            fits.append(target)
-        except AssertionError:
-            pass
-    assert fits, (what, "the plan is not the share rule's", weight, chunks)
-    return weight, chunks
 
 
 # ---- 1. the plan of a sweep that leaves blocks out, sized twice --------------------------------------------------------------------
@@ -80,7 +35,7 @@ def test_sized_plans_are_cut_by_the_weight(reflibs, monkeypatch):
         assert (full - 1.0) / (short + 1.0) <= (16.0 + weight) / (1.0 + weight) <= (full + 1.0) / max(short - 1.0, 0.5), chunks
         seen.append((len(plan_of(g)[0]), chunks))
     assert seen[1][0] >= 1.2 * seen[0][0], seen
-    assert g.lib.mc33hip_block_words(g.ctx, C.c_void_p(np.zeros(BIG[0] * 3 * 5, np.uint64).ctypes.data), BIG[0] * 3 * 5 * 8) == 0   # blocks were left out
+    assert words_of(g).shape == (BIG[0], 3, 5)   # blocks were left out: mc33hip_block_words has words to give
     g.close()
 
 
@@ -121,7 +76,7 @@ def test_weighted_plan_on_a_narrow_grid(reflibs, monkeypatch):
             same(g.extract(iso), ref, ("narrow", blocks, rep))
         weight, chunks[blocks] = check_plan(g, A, ("narrow", blocks), asked=150)
         assert plan_of(g)[2] == 1 and (weight > 0.0) == (blocks == "1"), (blocks, weight)
-        tiles, dead, grouped, e = check_packed(g, rs.numpy_table(data, "f32"), (iso,), ("narrow", blocks))
+        tiles, dead, grouped, e = check_packed(g, numpy_table(data, "f32"), (iso,), ("narrow", blocks))
         assert not grouped.any() and dead.any() and not dead.all()
         g.close()
     assert chunks["1"] != chunks[None] and chunks["1"][-1] > chunks[None][-1], chunks   # the last y tile (12 sample rows) gets more, shallower tiles
@@ -132,35 +87,13 @@ def test_weighted_plan_on_a_narrow_grid(reflibs, monkeypatch):
 def test_sub_range_with_a_ghost_plane_under_a_weighted_plan(reflibs, monkeypatch):
     """the upper z-slab of B as a window with plane0 > 0 and a ghost slice, each slab by a sized, weighted plan; the two slabs
     together are the whole surface"""
-    import torch
-    from mc33_c_library_amd import DeviceGrid, Range
     monkeypatch.setenv("MC33_HIP_TABLE_TILES", "90")
-    data = steep(B)
-    iso = STEEP_ISO[B]
-    ref = reference(reflibs, ("steep", B), "f32", data, iso)
-    t = to_device(data)
-    nz_total = B[0] - 1
-    zb = 17
-    p_lo = zb - 2
-    parts = []
-    for lo_plane, hi_plane, r in ((0, zb + 2, Range(0, zb, 0, 0)), (p_lo, B[0], Range(zb, nz_total, 1, 0))):
-        g = DeviceGrid(t[lo_plane:hi_plane], nz_total=nz_total, plane0=lo_plane)
-        cnts = [g.count(iso, r) for rep in range(3)]
-        assert len({(c.nV, c.nT) for c in cnts}) == 1
+
+    def the_plan_is_weighted(g, window, lo_plane, zs, cnts):
         weight, chunks = check_plan(g, B, ("slab", lo_plane), asked=90)
         assert weight > 0.0 and plan_of(g)[2] == 1
-        check_packed(g, table_of(g, "f32"), (iso,), ("slab", lo_plane), zs=zb - 1 if lo_plane else 0, plane0=lo_plane)
-        c = cnts[-1]
-        V = torch.empty((max(c.nV, 1), 3), dtype=torch.float32, device="cuda")
-        N = torch.empty_like(V)
-        T = torch.empty((max(c.nT, 1), 3), dtype=torch.int32, device="cuda")
-        g.emit_into(V, N, T, sum(p[3] for p in parts))
-        torch.cuda.synchronize()
-        parts.append((V[:c.nV].cpu().numpy(), N[:c.nV].cpu().numpy(), T[:c.nT].cpu().numpy().view(np.uint32), c.nV))
-        g.close()
-    assert np.array_equal(np.concatenate([p[2] for p in parts]), ref.T)
-    assert np.array_equal(rs.words(np.concatenate([p[0] for p in parts])), rs.words(ref.V))
-    assert np.array_equal(rs.words(np.concatenate([p[1] for p in parts])), rs.words(ref.N))
+        check_packed(g, table_of(g, "f32"), (STEEP_ISO[B],), ("slab", lo_plane), zs=zs, plane0=lo_plane)
+    two_slab_case(reflibs, the_plan_is_weighted)
 
 
 # ---- 4. a re-target under swept lanes -------------------------------------------------------------------------------------------------
@@ -210,9 +143,7 @@ def test_weighted_plans_fill_the_device_at_its_own_residency(reflibs, monkeypatc
     nzc = int(np.ceil(sp.FILL_BALANCED * 4 * resident / 0.8 / per_slice))
     shape = (nzc + 1,) + BIG[1:]
     z0 = int(round(0.85 * nzc))
-    x = np.arange(shape[2])
-    row = np.where(x < 1024, x % 256, 50 * (x - 1024)).astype(np.float32)   # (live_everywhere of tests/test_gpu_sweep_refill.py)
-    data = np.ascontiguousarray(np.broadcast_to(row, shape))
+    data = live_everywhere(shape)
     data[z0:] += 1000.0
     iso = LOW[0]
     ref = reference(reflibs, ("balance", "own residency", shape, z0), "f32", data, iso)

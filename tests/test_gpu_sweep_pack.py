@@ -3,86 +3,22 @@ k_sweep_live against a numpy restatement of its order rule, the surfaces of pack
 under one size of plan while another comes into force.
 
 Every surface is compared with the unmodified reference's (oracle/_ref) on the dense numpy array, bit for bit, with the fields,
-helpers and comparison of tests/test_gpu_range_skip.py and tests/test_gpu_sweep_refill.py.  There is no tolerance in this file.
+helpers and comparison of tests/sweep_harness.py.  There is no tolerance in this file.
 
 Shapes (points z, y, x): A = 48 x 200 x 520 (no grouped block), B = 40 x 70 x 1030 (a group of four segments and a fifth), and
 BIG = 160 x 130 x 1030 with MC33_HIP_SWEEP_BLOCKS_PER_CU=1, whose plan is one round of a device of 256 compute units at its
 default size and which can have more packed blocks than such a device holds."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import sweep_pack_rules as pr
-import test_gpu_range_skip as rs
-from test_gpu_range_skip import A, B, STEEP_ISO, grid_of, numpy_table, reference, same, steep, table_of, to_device
-from test_gpu_sweep_refill import BIG, live_everywhere, mixed_field, numpy_verdicts, plan_of
+from sweep_harness import (A, B, BIG, HIGH, LOW, MANY, STEEP_ISO, banded, by_the_rule, check_packed, grid_of, live_everywhere,  # noqa: F401
+                           live_list_always, mixed_field, mixed_whole, numpy_table, numpy_verdicts, one_bump, packed_of, plan_of, ramp,
+                           reference, same, steep, table_of, to_device, two_slab_case, typed_ramp)   # (live_list_always: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(autouse=True)
-def live_list_always(monkeypatch):
-    """the grids of this file are small: MC33_HIP_LIVE=1, read when a context is made, gives every sweep with a table its list"""
-    monkeypatch.setenv("MC33_HIP_LIVE", "1")
-
-
-def packed_of(g):
-    """(entries [n][4], live tiles, tiles of the plan) of the last sweep with a table"""
-    info = (C.c_ulonglong * 3)()
-    assert g.lib.mc33hip_sweep_packed(g.ctx, None, 0, C.byref(info)) == 0
-    e = np.zeros((max(int(info[0]), 1), 4), np.uint32)
-    assert g.lib.mc33hip_sweep_packed(g.ctx, C.c_void_p(e.ctypes.data), e.shape[0], C.byref(info)) == 0
-    return e[:int(info[0])], int(info[1]), int(info[2])
-
-
-def check_packed(g, tab, isos, what, zs=0, plane0=0):
-    tiles, resident, which = plan_of(g)
-    dead = numpy_verdicts(tiles, tab, isos, zs, plane0)[0]
-    grouped = pr.grouped_blocks(tiles)
-    want = pr.packed_entries(dead, grouped)
-    got, live, ntiles = packed_of(g)
-    assert ntiles == len(tiles) and live == int((~dead).sum()) and len(got) == (live + 3) // 4, (what, ntiles, live)
-    pr.check_entries(got, dead)
-    assert np.array_equal(got, want), (what, "packed list")
-    return tiles, dead, grouped, got
-
-
-def banded(z0=120):
-    """BIG: every strip of the planes below z0 straddles 100.5 (x mod 256; 50 (x - 1024) in the narrow last segment), every strip
-    from z0 on straddles 1100.5, and few cells are cut: z0 / 160 of the tiles live for isovalues below 256 (three in four at 120),
-    the others for isovalues between 1000 and 1256"""
-    data = live_everywhere(BIG).copy()
-    data[z0:] += 1000.0
-    return data
-
-
-LOW = (100.5, 50.5, 150.25, 200.0, 20.5, 120.75, 180.5, 220.0)   # isovalues of banded() with three tiles in four live
-HIGH = 1100.5                                                      # ... and with one in four
-
-
 # ---- 1. the packed list against numpy ---------------------------------------------------------------------------------------------------
-
-def one_bump():
-    data = np.zeros(B, np.float32)
-    data[20, 20:24, 100:104] = 1.0
-    return data
-
-
-MIXED = (56, 70, 1030)
-
-
-def mixed_whole():
-    """mixed_field of tests/test_gpu_sweep_refill.py on a grid 16 planes taller, with a fourth band: y tile 0 below 0.5 everywhere but
-    for one cell-sized bump per chosen (segment, plane) - planes 1 .. 12: segment 0 only (three waves of the group of four dead),
-    14 .. 25: segments 0 and 2 (two), 27 .. 38: segments 0, 1 and 3 (one), 40 .. 51: all four (a whole group)"""
-    data = np.zeros(MIXED, np.float32)
-    for planes, segs in ((range(1, 13), (0,)), (range(14, 26), (0, 2)), (range(27, 39), (0, 1, 3)), (range(40, 52), (0, 1, 2, 3))):
-        for p in planes:
-            for sg in segs:
-                data[p, 20:24, 256 * sg + 100:256 * sg + 104] = 1.0
-    return data
-
 
 LIST_CASES = {
     "steep A": (lambda: steep(A), STEEP_ISO[A], ("steep", A), 0),
@@ -143,7 +79,7 @@ def test_packed_list_is_numpys(reflibs, monkeypatch, case):
 
 # ---- 2. packed blocks over the same samples as the table-less sweep ------------------------------------------------------------------
 
-FOUR = {A: rs.MANY[("f32", A)], B: rs.MANY[("f32", B)], BIG: LOW[:4]}
+FOUR = {A: MANY[("f32", A)], B: MANY[("f32", B)], BIG: LOW[:4]}
 
 
 @pytest.mark.parametrize("ni", [1, 2, 4])
@@ -181,8 +117,8 @@ def test_packed_blocks_give_the_reference(reflibs, monkeypatch, shape, ni):
 
 @pytest.mark.parametrize("dtype", ["u16", "u8"])
 def test_narrow_samples_on_b(reflibs, dtype):
-    data = rs.typed_ramp("u16", B) if dtype == "u16" else (rs.ramp(B) // 6).astype(np.uint8)
-    isos = rs.MANY[("u16", B)] if dtype == "u16" else (100.5, 90.5, 120.5, 107.0)
+    data = typed_ramp("u16", B) if dtype == "u16" else (ramp(B) // 6).astype(np.uint8)
+    isos = MANY[("u16", B)] if dtype == "u16" else (100.5, 90.5, 120.5, 107.0)
     refs = [reference(reflibs, ("pack", "narrow B"), dtype, data, iso) for iso in isos]
     assert all(r.nV > 200 for r in refs)
     tab = numpy_table(data, dtype)
@@ -218,51 +154,12 @@ def test_a_strip_with_a_nan(reflibs):
 
 def test_sub_range_with_a_ghost_plane(reflibs):
     """the upper z-slab of B as a window with plane0 > 0 and a ghost slice; the two slabs together are the whole surface"""
-    import torch
-    from mc33_c_library_amd import DeviceGrid, Range
-    data = steep(B)
-    iso = STEEP_ISO[B]
-    ref = reference(reflibs, ("steep", B), "f32", data, iso)
-    t = to_device(data)
-    nz_total = B[0] - 1
-    zb = 17
-    p_lo = zb - 2
-    parts = []
-    for lo_plane, hi_plane, r in ((0, zb + 2, Range(0, zb, 0, 0)), (p_lo, B[0], Range(zb, nz_total, 1, 0))):
-        g = DeviceGrid(t[lo_plane:hi_plane], nz_total=nz_total, plane0=lo_plane)
-        cnts = [g.count(iso, r) for rep in range(3)]
-        assert len({(c.nV, c.nT) for c in cnts}) == 1
-        check_packed(g, table_of(g, "f32"), (iso,), ("slab", lo_plane), zs=zb - 1 if lo_plane else 0, plane0=lo_plane)
-        c = cnts[-1]
-        V = torch.empty((max(c.nV, 1), 3), dtype=torch.float32, device="cuda")
-        N = torch.empty_like(V)
-        T = torch.empty((max(c.nT, 1), 3), dtype=torch.int32, device="cuda")
-        g.emit_into(V, N, T, sum(p[3] for p in parts))
-        torch.cuda.synchronize()
-        parts.append((V[:c.nV].cpu().numpy(), N[:c.nV].cpu().numpy(), T[:c.nT].cpu().numpy().view(np.uint32), c.nV))
-        g.close()
-    assert np.array_equal(np.concatenate([p[2] for p in parts]), ref.T)
-    assert np.array_equal(rs.words(np.concatenate([p[0] for p in parts])), rs.words(ref.V))
-    assert np.array_equal(rs.words(np.concatenate([p[1] for p in parts])), rs.words(ref.N))
+    def the_list_is_numpys(g, window, lo_plane, zs, cnts):
+        check_packed(g, table_of(g, "f32"), (STEEP_ISO[B],), ("slab", lo_plane), zs=zs, plane0=lo_plane)
+    two_slab_case(reflibs, the_list_is_numpys)
 
 
 # ---- 3. the size of the plan ---------------------------------------------------------------------------------------------------------------
-
-def by_the_rule(g, what):
-    """the plan in force is the finer one, and the packed blocks of the last sweep lie inside the band of the rule - or the plan is
-    as fine as the rule's smallest depth allows (the chunks of a plan add up to a few tiles more or less than were asked for)"""
-    tiles, resident, which = plan_of(g)
-    e, live, ntiles = packed_of(g)
-    assert which == 1 and ntiles == len(tiles) and len(e) == (live + 3) // 4, what
-    unit = pr.unit_of(BIG)
-    depth = pr.floor_depth(unit, resident)
-    assert depth is not None, (what, "BIG is less than one round of this device", resident)
-    cap = int(unit / depth)
-    print("%s: %d tiles, %d live, %d packed blocks of %d resident (%.2f); cap %d" % (what, ntiles, live, len(e), resident, len(e) / resident, cap))
-    one_round = abs(ntiles - 4 * resident) <= 8 and len(e) > pr.BAND_HI * resident   # (more than the fill live: one round, never less)
-    assert pr.keeps(live, resident) or abs(ntiles - cap) <= 8 or one_round, (what, ntiles, live, resident, cap)
-    return ntiles
-
 
 def test_plan_is_sized_by_the_live_count(reflibs, monkeypatch):
     monkeypatch.setenv("MC33_HIP_SWEEP_BLOCKS_PER_CU", "1")

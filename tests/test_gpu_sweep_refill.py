@@ -2,8 +2,8 @@
 sweep, the live list k_sweep goes by, the two plans - one for a sweep without a table, a finer one for a sweep with one - and the
 lanes that are swept under one plan while the other comes into force.
 
-Every surface is compared with the unmodified reference's (oracle/_ref) on the dense numpy array, bit for bit, as in
-tests/test_gpu_range_skip.py, whose helpers and fields these tests use.  There is no tolerance in this file.
+Every surface is compared with the unmodified reference's (oracle/_ref) on the dense numpy array, bit for bit, with the fields,
+helpers and comparison of tests/sweep_harness.py.  There is no tolerance in this file.
 
 Shapes (points z, y, x): A = 48 x 200 x 520 (no grouped block), B = 40 x 70 x 1030 (a group of four segments and a fifth), and
 BIG = 160 x 130 x 1030 (85 MB of float samples), which with MC33_HIP_SWEEP_BLOCKS_PER_CU=1 and tiles one plane deep is more blocks
@@ -14,85 +14,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_gpu_range_skip as rs
-from test_gpu_range_skip import A, B, STEEP_ISO, grid_of, numpy_table, reference, same, skipped, steep, table_of, to_device
+from sweep_harness import (A, B, BIG, EINVAL, STEEP_ISO, check_live, depth_fixture, emit_slab, grid_of, live_everywhere, live_list_always,  # noqa: F401
+                           live_of, mixed_field, numpy_table, numpy_verdicts, plan_of, reference, same, skipped, slabs_are_the_surface, steep,
+                           switching, table_of, to_device, words)   # (live_list_always, switching: the module's fixtures)
 
 pytestmark = pytest.mark.gpu
 
-BIG = (160, 130, 1030)
-
-
-@pytest.fixture(autouse=True)
-def live_list_always(monkeypatch):
-    """by itself a sweep goes by a live list only under a plan of at least one round of the device (test_who_gets_a_live_list); the
-    grids of this file are small, and MC33_HIP_LIVE=1, read when a context is made, gives every sweep with a table one"""
-    monkeypatch.setenv("MC33_HIP_LIVE", "1")
-
-
-# ---- the plan and the live list, and numpy's own verdicts -------------------------------------------------------------------------------
-
-def plan_of(g):
-    """(tiles [n][4] = seg, yt, z_lo, z_hi in launch order, blocks the device holds at once, which plan: 0 without a table, 1 with)"""
-    info = (C.c_ulonglong * 3)()
-    assert g.lib.mc33hip_sweep_plan(g.ctx, None, 0, C.byref(info)) == 0
-    t = np.zeros((int(info[0]), 4), np.uint32)
-    assert g.lib.mc33hip_sweep_plan(g.ctx, C.c_void_p(t.ctypes.data), t.shape[0], C.byref(info)) == 0
-    return t, int(info[1]), int(info[2])
-
-
-def live_of(g):
-    """(entries, count word, blocks of the plan) of the last sweep with a table"""
-    info = (C.c_ulonglong * 2)()
-    assert g.lib.mc33hip_sweep_live(g.ctx, None, 0, C.byref(info)) == 0
-    e = np.zeros(max(int(info[1]), 1), np.uint32)
-    assert g.lib.mc33hip_sweep_live(g.ctx, C.c_void_p(e.ctypes.data), e.shape[0], C.byref(info)) == 0
-    return e[:int(info[0])], int(info[0]), int(info[1])
-
-
-def numpy_verdicts(tiles, tab, isos, zs=0, plane0=0):
-    """per tile: (dead for every isovalue, below the FIRST isovalue, above it) - the planes a tile would read are z_lo + 1 .. z_hi, and
-    z_lo too in the lowest tile of a column; both comparisons strict"""
-    dead, below, above = np.zeros(len(tiles), bool), np.zeros(len(tiles), bool), np.zeros(len(tiles), bool)
-    for i, (seg, yt, z_lo, z_hi) in enumerate(tiles.tolist()):
-        p0 = z_lo if z_lo == zs else z_lo + 1
-        s = tab[p0 - plane0:z_hi + 1 - plane0, yt, seg]
-        lo = [bool((s[:, 1] < iso).all()) for iso in isos]
-        hi = [bool((s[:, 0] > iso).all()) for iso in isos]
-        dead[i] = all(x or y for x, y in zip(lo, hi))
-        below[i], above[i] = dead[i] and lo[0], dead[i] and hi[0] and not lo[0]
-    return dead, below, above
-
-
-def expected_live(dead):
-    """the live list of a plan whose tiles have these verdicts: a word per block with a live tile, in plan order"""
-    n = len(dead)
-    out = []
-    for b in range((n + 3) // 4):
-        mask = sum(1 << k for k in range(4) if 4 * b + k >= n or dead[4 * b + k])
-        if mask != 15:
-            out.append(b << 4 | mask)
-    return np.array(out, np.uint32)
-
-
-def check_live(g, tab, isos, what, zs=0, plane0=0):
-    tiles, resident, which = plan_of(g)
-    dead, below, above = numpy_verdicts(tiles, tab, isos, zs, plane0)
-    want = expected_live(dead)
-    got, count, blocks = live_of(g)
-    assert blocks == (len(tiles) + 3) // 4, what
-    assert count == len(want) and np.array_equal(got, want), (what, "live list", count, len(want))
-    return tiles, dead, below, above
+depth = depth_fixture([0, 1, 2, 16], ids=["default", "rz1", "rz2", "rz16"])
 
 
 # ---- 1. verdicts against numpy ------------------------------------------------------------------------------------------------------------
-
-@pytest.fixture(params=[0, 1, 2, 16], ids=["default", "rz1", "rz2", "rz16"])
-def depth(request, monkeypatch):
-    if request.param:
-        monkeypatch.setenv("MC33_HIP_RZ", str(request.param))
-        monkeypatch.setenv("MC33_HIP_MIN_DEPTH", str(request.param))
-    return request.param
-
 
 @pytest.mark.parametrize("shape", [A, B], ids=["A", "B"])
 def test_verdicts_are_numpys(reflibs, depth, shape):
@@ -108,18 +39,11 @@ def test_verdicts_are_numpys(reflibs, depth, shape):
         tiles, dead, below, above = check_live(g, tab, (iso,), (shape, depth, rep))
         assert skipped(g) == (len(tiles), int(below.sum()), int(above.sum())), (shape, depth, rep)
         assert below.sum() > 0 and above.sum() > 0 and not dead.all()
-    assert np.array_equal(rs.words(table_of(g, "f32")), rs.words(tab))
+    assert np.array_equal(words(table_of(g, "f32")), words(tab))
     g.close()
 
 
 # ---- 2. more blocks than the device holds ----------------------------------------------------------------------------------------------
-
-def live_everywhere(shape):
-    """every strip straddles 100.5 and few cells are cut: x mod 256 in the whole segments, 50 (x - 1024) in the narrow last one"""
-    x = np.arange(shape[2])
-    row = np.where(x < 1024, x % 256, 50 * (x - 1024)).astype(np.float32)
-    return np.ascontiguousarray(np.broadcast_to(row, shape))
-
 
 BIG_FIELDS = {"steep": (lambda: steep(BIG), 2600.5), "dead": (lambda: steep(BIG), 1e6), "live": (lambda: live_everywhere(BIG), 100.5)}
 
@@ -154,15 +78,6 @@ def test_more_blocks_than_the_device_holds(reflibs, monkeypatch, field):
 
 EIGHT = {B: (1930.5, 1700.5, 2100.25, 1800.0, 1650.5, 2000.75, 1875.5, 2050.0),
          BIG: (2600.5, 2300.5, 2900.25, 2450.0, 2200.5, 2750.75, 2525.5, 2825.0)}
-
-
-@pytest.fixture(params=[B, BIG], ids=["B", "BIG-two-plans"])
-def switching(request, monkeypatch):
-    """B as it comes; BIG with a device of one block per CU and a plan with a table of tiles one plane deep: the two plans differ"""
-    if request.param == BIG:
-        monkeypatch.setenv("MC33_HIP_SWEEP_BLOCKS_PER_CU", "1")
-        monkeypatch.setenv("MC33_HIP_RZ_TABLE", "1")
-    return request.param
 
 
 def test_plan_switch_under_swept_lanes(reflibs, switching):
@@ -211,8 +126,9 @@ def test_count_then_a_table_then_extract_into(reflibs, switching):
 
 def test_sub_range_with_a_ghost_plane_across_the_switch(reflibs, switching):
     """the upper z-slab of the grid as a window with plane0 > 0 and a ghost slice: count without a table, with the table just built,
-    with it kept - every count the same - then sweep_many over the slab and the emits"""
-    import torch
+    with it kept - every count the same - then sweep_many over the slab and the emits.  (Not two_slab_case of the harness: the upper
+    window is counted and checked before the lower one exists and stays open beside it, and each slab is swept for two isovalues
+    twice in front of the one count its emit goes by.)"""
     from mc33_c_library_amd import DeviceGrid, Range
     shape = switching
     data = steep(shape)
@@ -234,34 +150,12 @@ def test_sub_range_with_a_ghost_plane_across_the_switch(reflibs, switching):
     for gg, r in ((lower, Range(0, zb, 0, 0)), (g, rng)):
         gg.sweep_many([iso, EIGHT[shape][1]], r)
         gg.sweep_many([iso, EIGHT[shape][1]], r)
-        c = gg.count(iso, r)
-        V = torch.empty((max(c.nV, 1), 3), dtype=torch.float32, device="cuda")
-        N = torch.empty_like(V)
-        T = torch.empty((max(c.nT, 1), 3), dtype=torch.int32, device="cuda")
-        gg.emit_into(V, N, T, sum(p[3] for p in parts))
-        torch.cuda.synchronize()
-        parts.append((V[:c.nV].cpu().numpy(), N[:c.nV].cpu().numpy(), T[:c.nT].cpu().numpy().view(np.uint32), c.nV))
+        parts.append(emit_slab(gg, gg.count(iso, r), sum(p[3] for p in parts)))
         gg.close()
-    assert np.array_equal(np.concatenate([p[2] for p in parts]), ref.T)
-    assert np.array_equal(rs.words(np.concatenate([p[0] for p in parts])), rs.words(ref.V))
-    assert np.array_equal(rs.words(np.concatenate([p[1] for p in parts])), rs.words(ref.N))
+    slabs_are_the_surface(parts, ref)
 
 
 # ---- 4. blocks with dead and live waves ------------------------------------------------------------------------------------------------
-
-def mixed_field():
-    """shape B, y tile 0: below 0.5 everywhere, but for one cell-sized bump per chosen (segment, plane) - planes 1 .. 12: segment 0
-    only (three waves of the group of four dead), 14 .. 25: segments 0 and 2 (two), 27 .. 38: segments 0, 1 and 3 (one).  A block of
-    the sweep is any four consecutive tiles of the plan, and with the fifth segment in between only every fourth z level's block is
-    the group itself: every band is longer than that period at tiles two planes deep.  The bumps are 1.0, but for 3.0 in segment
-    0, planes 4 .. 7 - the only thing above 2.5: every other tile with a bump is dead for 2.5 and live for 0.5."""
-    data = np.zeros(B, np.float32)
-    for planes, segs in ((range(1, 13), (0,)), (range(14, 26), (0, 2)), (range(27, 39), (0, 1, 3))):
-        for p in planes:
-            for s in segs:
-                data[p, 20:24, 256 * s + 100:256 * s + 104] = 3.0 if (s == 0 and 4 <= p <= 7) else 1.0
-    return data
-
 
 def test_mixed_blocks(reflibs, monkeypatch):
     monkeypatch.setenv("MC33_HIP_RZ", "2")
@@ -332,7 +226,7 @@ def test_who_gets_a_live_list(reflibs, monkeypatch):
     for rep in range(3):
         same(g.extract(STEEP_ISO[B]), ref, ("B", rep))
     info = (C.c_ulonglong * 2)()
-    assert table_of(g, "f32") is not None and g.lib.mc33hip_sweep_live(g.ctx, None, 0, C.byref(info)) == rs.EINVAL
+    assert table_of(g, "f32") is not None and g.lib.mc33hip_sweep_live(g.ctx, None, 0, C.byref(info)) == EINVAL
     tiles, resident, which = plan_of(g)
     assert len(tiles) < 4 * resident
     dead, below, above = numpy_verdicts(tiles, numpy_table(data, "f32"), (STEEP_ISO[B],))

@@ -8,34 +8,26 @@ is never written; the header takes it as "not live": below for a block, above fo
 
 Cases: all 4^5 code combinations of one row group (four quarters and the halo block), in every row group, with every number of
 row groups and both halo modes, the other groups' bits random; and a few thousand random words, the unused upper bits included."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-HOST_FLAGS = ["-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror"]
-SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
+from host_program import SANITIZE, build_host_program
+
 NONE = 16
 NEG_INF, POS_INF = 0xFF800000, 0x7F800000
 
 
-def build(tmp_path_factory, name, flags):
-    out = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["g++"] + HOST_FLAGS + flags + [os.path.join(HERE, "sweep_blocks_host.cpp"), "-o", out])
-    return out
-
-
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
-    return build(tmp_path_factory, "sweep_blocks_host", [])
+    return build_host_program(tmp_path_factory, "sweep_blocks_host.cpp", [])
 
 
 @pytest.fixture(scope="module")
 def host_program_sanitized(tmp_path_factory):
     """the same program under AddressSanitizer and UndefinedBehaviorSanitizer: stand-alone, with its own main"""
-    return build(tmp_path_factory, "sweep_blocks_host_san", SANITIZE)
+    return build_host_program(tmp_path_factory, "sweep_blocks_host.cpp", SANITIZE)
 
 
 # ---- the restatement --------------------------------------------------------------------------------------------------------------------

@@ -9,25 +9,18 @@ import numpy as np
 import pytest
 
 import sweep_pack_rules as pr
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-HOST_FLAGS = ["-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror"]
-SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
+from host_program import HERE, SANITIZE, build_host_program
 
 
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("sweep_pack_host") / "sweep_pack_host")
-    subprocess.check_call(["g++"] + HOST_FLAGS + [os.path.join(HERE, "sweep_pack_host.cpp"), "-o", out])
-    return out
+    return build_host_program(tmp_path_factory, "sweep_pack_host.cpp", [])
 
 
 @pytest.fixture(scope="module")
 def host_program_sanitized(tmp_path_factory):
     """the same program under AddressSanitizer and UndefinedBehaviorSanitizer: stand-alone, with its own main"""
-    out = str(tmp_path_factory.mktemp("sweep_pack_host_san") / "sweep_pack_host_san")
-    subprocess.check_call(["g++"] + HOST_FLAGS + SANITIZE + [os.path.join(HERE, "sweep_pack_host.cpp"), "-o", out])
-    return out
+    return build_host_program(tmp_path_factory, "sweep_pack_host.cpp", SANITIZE)
 
 
 def verdict_bytes(dead, grouped):

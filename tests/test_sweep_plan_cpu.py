@@ -17,30 +17,21 @@ import pytest
 
 import sweep_pack_rules as pr
 import sweep_plan_rules as sp
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-HOST_FLAGS = ["-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror"]
-SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
+from host_program import HERE, SANITIZE, build_host_program
 
 BIG, FLAGSHIP, ONE_YT, SHALLOW = (160, 130, 1030), (1024, 1024, 1024), (40, 60, 520), (12, 130, 1030)
 WEIGHTS = (0.0, 1.0, 3.5, 4.0, 16.0)
 
 
-def build(tmp_path_factory, name, flags):
-    out = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["g++"] + HOST_FLAGS + flags + [os.path.join(HERE, "sweep_plan_host.cpp"), "-o", out])
-    return out
-
-
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
-    return build(tmp_path_factory, "sweep_plan_host", [])
+    return build_host_program(tmp_path_factory, "sweep_plan_host.cpp", [])
 
 
 @pytest.fixture(scope="module")
 def host_program_sanitized(tmp_path_factory):
     """the same program under AddressSanitizer and UndefinedBehaviorSanitizer: stand-alone, with its own main"""
-    return build(tmp_path_factory, "sweep_plan_host_san", SANITIZE)
+    return build_host_program(tmp_path_factory, "sweep_plan_host.cpp", SANITIZE)
 
 
 def run(program, *args):
