@@ -265,23 +265,116 @@ class IsosurfaceCurvature(C.Structure):
 
 CURVATURES = ("mean", "gauss", "k1", "k2")
 
-HIP_API = ["mc33hip_set_id_base", "mc33hip_create", "mc33hip_destroy", "mc33hip_last_error", "mc33hip_upload_rows",
-           "mc33hip_upload_contiguous", "mc33hip_adopt_device", "mc33hip_set_stream", "mc33hip_count",
-           "mc33hip_emit", "mc33hip_extract", "mc33hip_last_timing", "mc33hip_download",
-           "mc33hip_device_alloc", "mc33hip_device_free", "mc33hip_set_inclined", "mc33hip_download_concurrent", "mc33hip_synchronize", "mc33hip_download_many", "mc33hip_set_normal_neg", "mc33hip_sweep_many", "mc33hip_set_timing", "mc33hip_probe_read", "mc33hip_prepare_many",
-           "mc33hip_emit_download", "mc33hip_download_wait", "mc33hip_own_stream", "mc33hip_device_count", "mc33hip_count_async",
-           "mc33hip_counts_to_device", "mc33hip_bases_from_table", "mc33hip_emit_at_device_bases", "mc33hip_count_finish",
-           "mc33hip_property_upload_rows", "mc33hip_property_upload_contiguous", "mc33hip_property_adopt_device", "mc33hip_property_drop",
-           "mc33hip_sample_property", "mc33hip_color_vertices", "mc33hip_download_enqueue",
-           "mc33hip_measure_surface", "mc33hip_label_components", "mc33hip_measure_components",
-           "mc33hip_surface_topology", "mc33hip_component_topology", "mc33hip_compact_components",
-           "mc33hip_smooth_surface", "mc33hip_vertex_normals", "mc33hip_smooth_timing", "mc33hip_simplify_surface",
-           "mc33hip_resampled_size", "mc33hip_resample_grid", "mc33hip_context_device", "mc33hip_grid_spectrum",
-           "mc33hip_clip_surface", "mc33hip_section_surface", "mc33hip_section_contours", "mc33hip_section_ladder",
-           "mc33hip_grid_stable", "mc33hip_grid_changed", "mc33hip_range_table", "mc33hip_sweep_skipped",
-           "mc33hip_sweep_plan", "mc33hip_sweep_plan_weight", "mc33hip_sweep_live", "mc33hip_sweep_packed", "mc33hip_range_blocks", "mc33hip_block_words",
-           "mc33hip_alias_cells", "mc33hip_sweep_skipped_blocks", "mc33hip_curvature_vertices", "mc33hip_color_values",
-           "mc33hip_cap_surface", "mc33hip_render_surface", "mc33hip_render_timing", "mc33hip_surface_distance", "mc33hip_distance_timing"]
+# Every ctypes.Structure above and the C type it mirrors (a class that mirrors two identical structs has two rows);
+# tests/test_bindings_cpu.py compares size and every field with the compiler.  FIELD_ALIASES: (class, field) -> C member where
+# the names differ ("lambda" cannot be read as a Python attribute).
+STRUCTS = {
+    "mc33hip_grid_desc": GridDesc, "mc33hip_range": Range, "mc33hip_counts": Counts, "mc33hip_timing": Timing,
+    "mc33hip_measures": Measures, "mc33hip_component": Component, "mc33_component": Component,
+    "mc33hip_topology": Topology, "struct mc33hip_component_topology": ComponentTopology, "mc33_component_topology": ComponentTopology,
+    "mc33hip_compaction": Compaction, "mc33_component_filter": ComponentFilter,
+    "mc33hip_smoothing": Smoothing, "mc33_smoothing": SurfaceSmoothing,
+    "mc33hip_simplification": Simplification, "mc33_simplification": SurfaceSimplification,
+    "mc33hip_clipping": Clipping, "mc33_clip": SurfaceClip,
+    "mc33hip_capping": Capping, "mc33_cap": SurfaceCap, "mc33_cap_info": SurfaceCapInfo,
+    "mc33hip_rendering": Rendering, "mc33_view": View, "mc33_image": Image,
+    "mc33hip_distance": Distance, "mc33_distance": SurfaceDistance,
+    "mc33hip_section": Sectioning, "mc33hip_contour": Contour, "mc33_contour": Contour, "mc33_section": SurfaceSection,
+    "mc33_section_level": SectionLevel,
+    "mc33hip_resampling": Resampling, "mc33_resampling": GridResampling,
+    "mc33hip_spectrum": Spectrum, "mc33_spectrum_info": SpectrumInfo,
+    "mc33hip_curvature": Curvature, "mc33_curvature": IsosurfaceCurvature,
+}
+FIELD_ALIASES = {(Smoothing, "lam"): "lambda", (SurfaceSmoothing, "lam"): "lambda"}
+
+# name -> (restype, argtypes, optional): what load_library declares of the device-level ABI (include/mc33_hip.h) and of the host C
+# helpers of include/marching_cubes_33.h that this module calls.  optional: MC33_LIB_DIR may name an older build without it.
+# tests/test_bindings_cpu.py compares every row with the headers.
+_P, _V, _I, _U, _D, _Q, _Z = C.POINTER, C.c_void_p, C.c_int, C.c_uint, C.c_double, C.c_ulonglong, C.c_size_t
+SIGNATURES = {
+    "mc33hip_set_id_base": (_I, [_V, _U], False),
+    "mc33hip_create": (_I, [_P(_V), _P(GridDesc)], False),
+    "mc33hip_destroy": (None, [_V], False),
+    "mc33hip_last_error": (C.c_char_p, [], False),
+    "mc33hip_upload_rows": (_I, [_V, _V], False),
+    "mc33hip_upload_contiguous": (_I, [_V, _V], False),
+    "mc33hip_adopt_device": (_I, [_V, _V, _Z, _Z], False),
+    "mc33hip_set_stream": (_I, [_V, _V], False),
+    "mc33hip_count": (_I, [_V, _D, _P(Range), _P(Counts)], False),
+    "mc33hip_emit": (_I, [_V, _V, _V, _V, _Q, _Q], False),
+    "mc33hip_extract": (_I, [_V, _D, _P(Range), _V, _V, _V, _Q, _Q, _P(Counts)], False),
+    "mc33hip_last_timing": (_I, [_V, _P(Timing)], False),
+    "mc33hip_download": (_I, [_V, _V, _V, _Z], False),
+    "mc33hip_device_alloc": (_I, [_V, _P(_V), _Z], False),
+    "mc33hip_device_free": (_I, [_V, _V], False),
+    "mc33hip_set_inclined": (_I, [_V, _V, _V, _I], False),
+    "mc33hip_download_concurrent": (_I, [_V, _V, _V, _Z], False),
+    "mc33hip_synchronize": (_I, [_V], False),
+    "mc33hip_download_many": (_I, [_V, _I, _P(_V), _P(_V), _P(_Z), _I], False),
+    "mc33hip_set_normal_neg": (_I, [_V, _I], False),
+    "mc33hip_sweep_many": (_I, [_V, _P(_D), _I, _P(Range)], False),
+    "mc33hip_set_timing": (_I, [_V, _I], False),
+    "mc33hip_probe_read": (_I, [_V, _I, _P(C.c_float), _P(C.c_float), _P(_Q)], False),
+    "mc33hip_prepare_many": (_I, [_V, _P(_D), _I, _P(Range)], False),
+    "mc33hip_emit_download": (_I, [_V, _V, _V, _V, _Q, _Q, _V, _V, _V], False),
+    "mc33hip_download_wait": (_I, [_V], False),
+    "mc33hip_own_stream": (_I, [_V], False),
+    "mc33hip_device_count": (_I, [], False),
+    "mc33hip_count_async": (_I, [_V, _D, _P(Range)], False),
+    "mc33hip_counts_to_device": (_I, [_V, _V], False),
+    "mc33hip_bases_from_table": (_I, [_V, _V, _I, _I, _I], False),
+    "mc33hip_emit_at_device_bases": (_I, [_V, _V, _V, _V, _Q, _Q], False),
+    "mc33hip_count_finish": (_I, [_V, _P(Counts)], False),
+    "mc33hip_property_upload_rows": (_I, [_V, _V, _U, _U], False),
+    "mc33hip_property_upload_contiguous": (_I, [_V, _V, _U, _U], False),
+    "mc33hip_property_adopt_device": (_I, [_V, _V, _Z, _Z, _U, _U], False),
+    "mc33hip_property_drop": (_I, [_V], False),
+    "mc33hip_sample_property": (_I, [_V, _V, _Q, _V], False),
+    "mc33hip_color_vertices": (_I, [_V, _V, _Q, _P(_I), _U, _D, _D, _I, _V], False),
+    "mc33hip_download_enqueue": (_I, [_V, _V, _V, _Z], False),
+    "mc33hip_measure_surface": (_I, [_V, _V, _Q, _V, _Q, _V, _P(Measures)], False),
+    "mc33hip_label_components": (_I, [_V, _V, _Q, _Q, _V, _P(_Q), _P(_Q)], False),
+    "mc33hip_measure_components": (_I, [_V, _V, _Q, _V, _Q, _V, _V, _Q, _P(_Q)], False),
+    "mc33hip_surface_topology": (_I, [_V, _V, _Q, _Q, _P(Topology)], False),
+    "mc33hip_component_topology": (_I, [_V, _V, _Q, _Q, _V, _V, _Q, _P(_Q)], False),
+    "mc33hip_compact_components": (_I, [_V, _P(Compaction)], False),
+    "mc33hip_smooth_surface": (_I, [_V, _P(Smoothing)], False),
+    "mc33hip_vertex_normals": (_I, [_V, _V, _Q, _V, _Q, _V], False),
+    "mc33hip_smooth_timing": (_I, [_V, _P(C.c_float), _P(C.c_float), _P(C.c_float), _U, _P(_U)], False),
+    "mc33hip_simplify_surface": (_I, [_V, _P(Simplification)], False),
+    "mc33hip_resampled_size": (_I, [_V, _P(Resampling), _P(_U * 3)], False),
+    "mc33hip_resample_grid": (_I, [_V, _P(Resampling), _V, _Z, _Z], False),
+    "mc33hip_context_device": (_I, [_V], False),
+    "mc33hip_grid_spectrum": (_I, [_V, _P(Range), _P(Spectrum)], False),
+    "mc33hip_clip_surface": (_I, [_V, _P(Clipping)], False),
+    "mc33hip_section_surface": (_I, [_V, _P(Sectioning)], False),
+    "mc33hip_section_contours": (_I, [_V, _V, _Q, _V, _Q, _V, _P(_D * 4), _V, _Q, _P(_Q)], False),
+    "mc33hip_section_ladder": (_I, [_V, _V, _Q, _V, _Q, _P(_D * 3), _P(_D), _U, _P(_Q), _P(_D), _P(_D), _P(_Q)], False),
+    "mc33hip_grid_stable": (_I, [_V, _I], True),  # (every grid is volatile in a build without it)
+    "mc33hip_grid_changed": (_I, [_V], True),
+    "mc33hip_range_table": (_I, [_V, _V, _Z], True),
+    "mc33hip_sweep_skipped": (_I, [_V, _P(_Q * 3)], True),
+    "mc33hip_sweep_plan": (_I, [_V, _V, _Z, _P(_Q * 3)], True),
+    "mc33hip_sweep_plan_weight": (_I, [_V, _P(_D)], True),
+    "mc33hip_sweep_live": (_I, [_V, _V, _Z, _P(_Q * 2)], True),
+    "mc33hip_sweep_packed": (_I, [_V, _V, _Z, _P(_Q * 3)], True),
+    "mc33hip_range_blocks": (_I, [_V, _V, _Z], True),
+    "mc33hip_block_words": (_I, [_V, _V, _Z], True),
+    "mc33hip_alias_cells": (_I, [_V, _P(_Q)], True),
+    "mc33hip_sweep_skipped_blocks": (_I, [_V, _P(_Q * 3)], True),
+    "mc33hip_curvature_vertices": (_I, [_V, _P(Curvature)], True),
+    "mc33hip_color_values": (_I, [_V, _V, _Q, _P(_I), _U, _D, _D, _I, _V], True),
+    "mc33hip_cap_surface": (_I, [_V, _P(Capping)], True),
+    "mc33hip_render_surface": (_I, [_V, _P(Rendering)], True),
+    "mc33hip_render_timing": (_I, [_V, _P(C.c_float * 6)], True),
+    "mc33hip_surface_distance": (_I, [_V, _P(Distance)], True),
+    "mc33hip_distance_timing": (_I, [_V, _P(C.c_float * 3)], True),
+    "MC33_select_components": (_I, [_V, _V, _U, _P(ComponentFilter), _V], False),
+    "MC33_gaussian_taps": (_I, [_D, _U, _P(_D)], False),
+    "MC33_isovalue_ladder": (_I, [_D, _D, _U, _V], False),
+    "MC33_clip_box": (_I, [_P(_D * 3), _P(_D * 3), _P(SurfaceClip)], False),
+}
+HIP_API = [name for name in SIGNATURES if name.startswith("mc33hip_")]
 REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "free_MC33", "free_surface_memory",
                  "adjustvectorlenght_s", "DefaultColorMC", "free_memory_grd", "alloc_F", "grid_from_data_pointer",
                  "generate_grid_from_fn", "_multTSA_bf", "_multA_bf", "mult_Abf",
@@ -329,93 +422,11 @@ def load_library(dtype="f32"):
     except Exception:
         pass
     lib = C.CDLL(path)
-    P, V = C.POINTER, C.c_void_p
-    lib.mc33hip_create.argtypes = [P(V), P(GridDesc)]
-    lib.mc33hip_destroy.argtypes = [V]
-    lib.mc33hip_destroy.restype = None
-    lib.mc33hip_last_error.restype = C.c_char_p
-    lib.mc33hip_upload_rows.argtypes = [V, V]
-    lib.mc33hip_upload_contiguous.argtypes = [V, V]
-    lib.mc33hip_adopt_device.argtypes = [V, V, C.c_size_t, C.c_size_t]
-    lib.mc33hip_set_stream.argtypes = [V, V]
-    lib.mc33hip_count.argtypes = [V, C.c_double, P(Range), P(Counts)]
-    lib.mc33hip_set_id_base.argtypes = [V, C.c_uint]
-    lib.mc33hip_emit.argtypes = [V, V, V, V, C.c_ulonglong, C.c_ulonglong]
-    lib.mc33hip_extract.argtypes = [V, C.c_double, P(Range), V, V, V, C.c_ulonglong, C.c_ulonglong, P(Counts)]
-    lib.mc33hip_last_timing.argtypes = [V, P(Timing)]
-    lib.mc33hip_download.argtypes = [V, V, V, C.c_size_t]
-    lib.mc33hip_device_alloc.argtypes = [V, P(V), C.c_size_t]
-    lib.mc33hip_device_free.argtypes = [V, V]
-    lib.mc33hip_set_inclined.argtypes = [V, V, V, C.c_int]
-    lib.mc33hip_set_normal_neg.argtypes = [V, C.c_int]
-    lib.mc33hip_sweep_many.argtypes = [V, P(C.c_double), C.c_int, P(Range)]
-    lib.mc33hip_set_timing.argtypes = [V, C.c_int]
-    lib.mc33hip_prepare_many.argtypes = [V, P(C.c_double), C.c_int, P(Range)]
-    lib.mc33hip_probe_read.argtypes = [V, C.c_int, P(C.c_float), P(C.c_float), P(C.c_ulonglong)]
-    lib.mc33hip_count_async.argtypes = [V, C.c_double, P(Range)]
-    lib.mc33hip_counts_to_device.argtypes = [V, V]
-    lib.mc33hip_bases_from_table.argtypes = [V, V, C.c_int, C.c_int, C.c_int]
-    lib.mc33hip_emit_at_device_bases.argtypes = [V, V, V, V, C.c_ulonglong, C.c_ulonglong]
-    lib.mc33hip_count_finish.argtypes = [V, P(Counts)]
-    lib.mc33hip_synchronize.argtypes = [V]
-    lib.mc33hip_property_upload_rows.argtypes = [V, V, C.c_uint, C.c_uint]
-    lib.mc33hip_property_upload_contiguous.argtypes = [V, V, C.c_uint, C.c_uint]
-    lib.mc33hip_property_adopt_device.argtypes = [V, V, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint]
-    lib.mc33hip_property_drop.argtypes = [V]
-    lib.mc33hip_sample_property.argtypes = [V, V, C.c_ulonglong, V]
-    lib.mc33hip_color_vertices.argtypes = [V, V, C.c_ulonglong, P(C.c_int), C.c_uint, C.c_double, C.c_double, C.c_int, V]
-    lib.mc33hip_download_enqueue.argtypes = [V, V, V, C.c_size_t]
-    lib.mc33hip_measure_surface.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V, P(Measures)]
-    lib.mc33hip_label_components.argtypes = [V, V, C.c_ulonglong, C.c_ulonglong, V, P(C.c_ulonglong), P(C.c_ulonglong)]
-    lib.mc33hip_measure_components.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V, V, C.c_ulonglong, P(C.c_ulonglong)]
-    lib.mc33hip_surface_topology.argtypes = [V, V, C.c_ulonglong, C.c_ulonglong, P(Topology)]
-    lib.mc33hip_component_topology.argtypes = [V, V, C.c_ulonglong, C.c_ulonglong, V, V, C.c_ulonglong, P(C.c_ulonglong)]
-    lib.mc33hip_compact_components.argtypes = [V, P(Compaction)]
-    lib.mc33hip_smooth_surface.argtypes = [V, P(Smoothing)]
-    lib.mc33hip_vertex_normals.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V]
-    lib.mc33hip_smooth_timing.argtypes = [V, P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint, P(C.c_uint)]
-    lib.mc33hip_simplify_surface.argtypes = [V, P(Simplification)]
-    lib.MC33_select_components.argtypes = [V, V, C.c_uint, P(ComponentFilter), V]
-    lib.mc33hip_resampled_size.argtypes = [V, P(Resampling), P(C.c_uint * 3)]
-    lib.mc33hip_resample_grid.argtypes = [V, P(Resampling), V, C.c_size_t, C.c_size_t]
-    lib.mc33hip_context_device.argtypes = [V]
-    lib.MC33_gaussian_taps.argtypes = [C.c_double, C.c_uint, P(C.c_double)]
-    lib.mc33hip_grid_spectrum.argtypes = [V, P(Range), P(Spectrum)]
-    lib.MC33_isovalue_ladder.argtypes = [C.c_double, C.c_double, C.c_uint, V]
-    lib.mc33hip_clip_surface.argtypes = [V, P(Clipping)]
-    lib.MC33_clip_box.argtypes = [P(C.c_double * 3), P(C.c_double * 3), P(SurfaceClip)]
-    lib.mc33hip_section_surface.argtypes = [V, P(Sectioning)]
-    lib.mc33hip_section_contours.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, V, P(C.c_double * 4), V, C.c_ulonglong, P(C.c_ulonglong)]
-    lib.mc33hip_section_ladder.argtypes = [V, V, C.c_ulonglong, V, C.c_ulonglong, P(C.c_double * 3), P(C.c_double), C.c_uint, P(C.c_ulonglong), P(C.c_double),
-                                           P(C.c_double), P(C.c_ulonglong)]
-    if hasattr(lib, "mc33hip_cap_surface"):
-        lib.mc33hip_cap_surface.argtypes = [V, P(Capping)]
-    if hasattr(lib, "mc33hip_render_surface"):
-        lib.mc33hip_render_surface.argtypes = [V, P(Rendering)]
-        lib.mc33hip_render_timing.argtypes = [V, P(C.c_float * 6)]
-    if hasattr(lib, "mc33hip_surface_distance"):
-        lib.mc33hip_surface_distance.argtypes = [V, P(Distance)]
-        lib.mc33hip_distance_timing.argtypes = [V, P(C.c_float * 3)]
-    if hasattr(lib, "mc33hip_curvature_vertices"):
-        lib.mc33hip_curvature_vertices.argtypes = [V, P(Curvature)]
-        lib.mc33hip_color_values.argtypes = [V, V, C.c_ulonglong, P(C.c_int), C.c_uint, C.c_double, C.c_double, C.c_int, V]
-    if hasattr(lib, "mc33hip_grid_stable"):  # (MC33_LIB_DIR may name an older build, for a comparison side by side: every grid is volatile there)
-        lib.mc33hip_grid_stable.argtypes = [V, C.c_int]
-        lib.mc33hip_grid_changed.argtypes = [V]
-        lib.mc33hip_range_table.argtypes = [V, V, C.c_size_t]
-        lib.mc33hip_sweep_skipped.argtypes = [V, P(C.c_ulonglong * 3)]
-    if hasattr(lib, "mc33hip_sweep_plan"):
-        lib.mc33hip_sweep_plan.argtypes = [V, V, C.c_size_t, P(C.c_ulonglong * 3)]
-        lib.mc33hip_sweep_live.argtypes = [V, V, C.c_size_t, P(C.c_ulonglong * 2)]
-    if hasattr(lib, "mc33hip_sweep_packed"):
-        lib.mc33hip_sweep_packed.argtypes = [V, V, C.c_size_t, P(C.c_ulonglong * 3)]
-    if hasattr(lib, "mc33hip_sweep_plan_weight"):
-        lib.mc33hip_sweep_plan_weight.argtypes = [V, P(C.c_double)]
-    if hasattr(lib, "mc33hip_range_blocks"):
-        lib.mc33hip_range_blocks.argtypes = [V, V, C.c_size_t]
-        lib.mc33hip_block_words.argtypes = [V, V, C.c_size_t]
-        lib.mc33hip_alias_cells.argtypes = [V, P(C.c_ulonglong)]
-        lib.mc33hip_sweep_skipped_blocks.argtypes = [V, P(C.c_ulonglong * 3)]
+    for name, (restype, argtypes, optional) in SIGNATURES.items():
+        if optional and not hasattr(lib, name):  # (MC33_LIB_DIR may name an older build, for a comparison side by side)
+            continue
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _libs[dtype] = lib
     return lib
 

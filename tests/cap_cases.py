@@ -8,6 +8,7 @@ import numpy as np
 NAMES = ("dome", "corner", "saddle", "noise", "one", "flat", "full", "none", "spaced", "sub", "quant", "hole")
 VARIANTS = ("dome_f64", "dome_u8", "dome_u16")  # dome in the other sample types
 OPEN = ("quant", "hole")  # the cases whose result keeps boundary edges
+ALL = NAMES + VARIANTS
 LARGE = ("big",)  # for the device: more face cells and box points than a tile of the scans, more triangles than a block
 
 NP = {"f32": np.float32, "f64": np.float64, "u8": np.uint8, "u16": np.uint16}

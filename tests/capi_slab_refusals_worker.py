@@ -14,18 +14,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [HERE, os.path.dirname(HERE)]
 
 import fixtures as fx  # noqa: E402
-import test_gpu_clip as clip  # noqa: E402
-import test_gpu_filter as filt  # noqa: E402
-import test_gpu_measure as meas  # noqa: E402
-import test_gpu_simplify as simp  # noqa: E402
-import test_gpu_smooth as smooth  # noqa: E402
-from test_filter_cpu import CFilter  # noqa: E402
-from test_smooth_cpu import CSmoothing  # noqa: E402
-from test_topology_cpu import CComponentTopology, CTopology, bind_topology_api  # noqa: E402
+from clip_cases import cclip  # noqa: E402
+from mc33_c_library_amd.api import Component, ComponentFilter, ComponentTopology, SurfaceSmoothing  # noqa: E402
+from mc33_capi import CMeasure, CTopology  # noqa: E402
+from mesh_harness import capi  # noqa: E402
+from simplify_cases import csimp  # noqa: E402
 
 assert os.environ.get("MC33_HIP_DEVICES") == "0,0"
-lib = meas.capi()  # (every capi() opens the one library: the object of one is the object of all)
-bind_topology_api(lib)
+lib = capi()
 L = lib.lib
 iso = lib.real(0.0)
 data, r0, d = fx.cos_field(32)
@@ -41,38 +37,38 @@ def still_extracts():
     L.free_surface_memory(S)
 
 
-m, many, rows, n = meas.CMeasure(), (meas.CMeasure * 2)(), (meas.CComponent * 4)(), C.c_uint()
+m, many, rows, n = CMeasure(), (CMeasure * 2)(), (Component * 4)(), C.c_uint()
 a = L.MC33_measure_isosurface(M, iso, C.byref(m))
 b = L.MC33_measure_isosurfaces(M, (lib.real * 2)(0.0, 0.5), 2, many)
 c = L.MC33_measure_components(M, iso, rows, 4, C.byref(n), None)
 still_extracts()
 lines.append("measure refused: %d %d %d" % (a, b, c))
 
-t, trows, n = CTopology(), (CComponentTopology * 4)(), C.c_uint(7)
+t, trows, n = CTopology(), (ComponentTopology * 4)(), C.c_uint(7)
 a = L.MC33_isosurface_topology(M, iso, C.byref(t))
 b = L.MC33_component_topology(M, iso, trows, 4, C.byref(n))
 still_extracts()
 lines.append("topology refused: %d %d %d" % (a, b, n.value))
 
-f, k, dr = CFilter(), C.c_uint(5), C.c_uint(5)
-F = filt.capi().lib.MC33_calculate_filtered_isosurface(M, iso, C.byref(f), C.byref(k), C.byref(dr))
+f, k, dr = ComponentFilter(), C.c_uint(5), C.c_uint(5)
+F = L.MC33_calculate_filtered_isosurface(M, iso, C.byref(f), C.byref(k), C.byref(dr))
 still_extracts()
 lines.append("filter refused: %d %d %d" % (0 if F else 1, k.value, dr.value))
 
-sm = CSmoothing(10, 0.5, -0.53, 1)
-F = smooth.capi().lib.MC33_calculate_smoothed_isosurface(M, iso, C.byref(sm))
+sm = SurfaceSmoothing(10, 0.5, -0.53, 1)
+F = L.MC33_calculate_smoothed_isosurface(M, iso, C.byref(sm))
 fault = M.contents.memoryfault
 still_extracts()
 lines.append("smooth refused: %d %d" % (0 if F else 1, fault))
 
-sp = simp.csimp((2.0, 2.0, 2.0), 0, 1)
-F = simp.capi().lib.MC33_calculate_simplified_isosurface(M, iso, C.byref(sp))
+sp = csimp((2.0, 2.0, 2.0), 0, 1)
+F = L.MC33_calculate_simplified_isosurface(M, iso, C.byref(sp))
 fault = M.contents.memoryfault
 still_extracts()
 lines.append("simplify refused: %d %d" % (0 if F else 1, fault))
 
-cl = clip.cclip([(0.0, 0.0, 1.0, 0.0)])
-F = clip.capi().lib.MC33_calculate_clipped_isosurface(M, iso, C.byref(cl))
+cl = cclip([(0.0, 0.0, 1.0, 0.0)])
+F = L.MC33_calculate_clipped_isosurface(M, iso, C.byref(cl))
 fault = M.contents.memoryfault
 still_extracts()
 lines.append("clip refused: %d %d" % (0 if F else 1, fault))

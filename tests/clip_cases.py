@@ -1,10 +1,16 @@
 """Made-up meshes for the clipping by a plane (tests/test_clip_cpu.py, tests/test_gpu_clip.py): the triangle lists of
 tests/mesh_pieces.py with positions assigned here, so that the plane z = 0 meets them where the test chooses, and the tiny mesh
-with every in / on / out pattern.  numpy only."""
+with every in / on / out pattern; and what the CPU and the GPU tests of the part share: the cases on the reference's meshes with
+the oracle's results, made once, and the structs of the C API filled."""
+import ctypes as C
+
 import numpy as np
 
+import clip_oracle as co
 import mesh_pieces as mp
 import simplify_cases as sc
+from mc33_c_library_amd.api import SurfaceClip
+from mesh_checks import reference_mesh
 
 PLANE_Z = (0.0, 0.0, 1.0, 0.0)  # z >= 0 stays
 RUNS = (1, 2, 63, 64, 65, 255, 256, 257, 1025)
@@ -120,3 +126,85 @@ def nonfinite(seed):
     rows = rng.permutation(5000)[:300]
     V[rows, rng.integers(0, 3, 300)] = rng.choice(np.array([np.nan, np.inf, -np.inf], np.float32), 300)
     return V, N, T
+
+
+# ---- the cases on the reference's meshes (tests/test_clip_cpu.py pins the oracle to TABLE, tests/test_gpu_clip.py the device) ----
+
+PLANES = ("oblique", "on-grid", "miss", "all")
+MODES = (co.LERP_F32, co.COPY)
+
+# (fixture, plane) -> nV_out, nT_out, kept, cut vertices, on the plane, whole, cut, dropped triangles (no invalid triangle, no
+# vertex whose s is not finite)
+TABLE = {
+    ("sphere", "oblique"): (11112, 21625, 10515, 597, 0, 20730, 597, 20729),
+    ("sphere", "on-grid"): (11793, 23316, 11793, 0, 268, 23316, 0, 18740),
+    ("sphere", "miss"): (21030, 42056, 21030, 0, 0, 42056, 0, 0),
+    ("sphere", "all"): (0, 0, 0, 0, 0, 0, 0, 42056),
+    ("blobs", "oblique"): (13564, 26578, 13068, 496, 0, 25834, 496, 25834),
+    ("blobs", "on-grid"): (13596, 26610, 13596, 0, 528, 26610, 0, 25554),
+    ("blobs", "miss"): (26136, 52164, 26136, 0, 0, 52164, 0, 0),
+    ("blobs", "all"): (0, 0, 0, 0, 0, 0, 0, 52164),
+    ("sheet", "oblique"): (7993, 15171, 7536, 457, 0, 14486, 455, 14491),
+    ("sheet", "on-grid"): (11648, 22496, 11648, 0, 288, 22496, 0, 6936),
+    ("sheet", "miss"): (15072, 29432, 15072, 0, 0, 29432, 0, 0),
+    ("sheet", "all"): (0, 0, 0, 0, 0, 0, 0, 29432),
+    ("noise", "oblique"): (27552, 54401, 24307, 3245, 0, 49592, 3212, 50080),
+    ("noise", "on-grid"): (25547, 53093, 25547, 0, 822, 53093, 0, 49791),
+    ("noise", "miss"): (48809, 102884, 48809, 0, 0, 102884, 0, 0),
+    ("noise", "all"): (0, 0, 0, 0, 0, 0, 0, 102884),
+    ("quant", "oblique"): (9289, 18449, 7946, 1343, 16, 16454, 1358, 16136),
+    ("quant", "on-grid"): (8499, 17781, 8499, 0, 480, 17781, 0, 16167),
+    ("quant", "miss"): (15775, 33948, 15775, 0, 0, 33948, 0, 0),
+    ("quant", "all"): (0, 0, 0, 0, 0, 0, 0, 33948),
+}
+
+
+def plane_of(V, which):
+    """the four planes of a mesh, exact functions of its vertices: oblique through the middle of the bounding box; x - x0 with x0
+    the most frequent x of the vertices - a whole grid plane of them has s == 0 exactly; one that misses; one that removes all"""
+    lo, hi = V.min(axis=0).astype(np.float64), V.max(axis=0).astype(np.float64)
+    if which == "oblique":
+        n = np.array([0.3, -0.5, 0.8])
+        c = 0.5 * (lo + hi)
+        return (n[0], n[1], n[2], -float((n[0] * c[0] + n[1] * c[1]) + n[2] * c[2]))
+    if which == "on-grid":
+        x, count = np.unique(V[:, 0], return_counts=True)
+        inner = (x > lo[0] + 0.25 * (hi[0] - lo[0])) & (x < hi[0] - 0.25 * (hi[0] - lo[0]))
+        return (1.0, 0.0, 0.0, -float(x[inner][np.argmax(count[inner])]))
+    if which == "miss":
+        return (1.0, 0.0, 0.0, 1.0 - float(lo[0]))
+    return (1.0, 0.0, 0.0, -1.0 - float(hi[0]))
+
+
+def attributes(nV):
+    """a float per vertex (interpolated) and a word per vertex (copied)"""
+    return (floats(nV, 11), np.random.default_rng(12).integers(0, 1 << 32, nV, dtype=np.uint64).astype(np.uint32))
+
+
+_results = {}
+
+
+def clipped(reflibs, name, which):
+    """the oracle's result of one case on a fixture row's reference surface, computed once, shared and left unchanged"""
+    key = (name, which)
+    if key not in _results:
+        s = reference_mesh(reflibs, name)[4]
+        _results[key] = co.clip(s.V, s.N, s.T, plane_of(s.V, which), attributes(s.nV), MODES)
+    return _results[key]
+
+
+def cclip(planes):
+    """an mc33_clip of the planes"""
+    cl = SurfaceClip(len(planes))
+    for k, pl in enumerate(planes[:6]):
+        for j in range(4):
+            cl.plane[k][j] = pl[j]
+    return cl
+
+
+def cbox(lib, lo, hi):
+    """MC33_clip_box of an MC33Lib: the mc33_clip and its six planes as tuples"""
+    three = C.c_double * 3
+    cl = SurfaceClip()
+    assert lib.lib.MC33_clip_box(C.byref(three(*lo)), C.byref(three(*hi)), C.byref(cl)) == 0
+    return cl, [tuple(cl.plane[k][j] for j in range(4)) for k in range(6)]

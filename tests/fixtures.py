@@ -214,3 +214,18 @@ def reference_field(name, coarsen=1):
     else:
         raise KeyError(name)
     return np.broadcast_to(f, (n[2], n[1], n[0])).astype(np.float32), tuple(lo), (step, step, step)
+
+
+def write_grd_text(path, N, L, ang, lo, order, values):
+    """a DMol .grd text file as read_grd takes it: N intervals, extent L, cell angles, first indices lo, the order of the samples"""
+    nx, ny, nz = (n + 1 for n in N)
+    with open(path, "w") as f:
+        f.write("a title line for the grid\n(1p,e12.5)\n")
+        f.write("%8.4f %8.4f %8.4f %8.4f %8.4f %8.4f\n" % (L + ang))
+        f.write("%5d %5d %5d\n" % N)
+        f.write("%5d %5d %5d %5d %5d %5d %5d\n" % (order, lo[0], lo[0] + N[0], lo[1], lo[1] + N[1], lo[2], lo[2] + N[2]))
+        v = values.reshape(nz, ny, nx)
+        for k in range(nz):
+            block = v[k] if order == 1 else v[k].T
+            for x in block.ravel():
+                f.write("%.7e\n" % x)

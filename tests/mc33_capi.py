@@ -7,13 +7,22 @@ export the reference's C API:
   * mc33_c_library_amd/libMC33_{f32,u8,u16,u32}.so - the product (HIP kernels behind the C-ABI shim)
 
 so a parity test reads like "run the reference's own usage snippet twice and diff the surfaces".
+
+The C API is declared ONCE, here: signatures() is the table of every function of include/marching_cubes_33.h, MC33Lib applies
+it to the library it opens.  Every struct of that header has one ctypes mirror: the class in mc33_c_library_amd/api.py (STRUCTS)
+where there is one, else a class of this module (MIRRORS).  tests/test_bindings_cpu.py holds all of it to the header.
 """
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:  # (a program that put only tests/ on its path: the package lies beside it)
+    sys.path.insert(0, ROOT)
+
+from mc33_c_library_amd import api  # noqa: E402
 
 
 class GRD(C.Structure):
@@ -104,8 +113,8 @@ def _mc33_fields(real):
         ("_A", (C.c_double * 3) * 3),
         ("A_", (C.c_double * 3) * 3),
         ("Dx", C.c_void_p),
-        ("Ux", C.c_void_p),
         ("Dy", C.c_void_p),
+        ("Ux", C.c_void_p),
         ("Uy", C.c_void_p),
         ("Lz", C.c_void_p),
     ]
@@ -134,6 +143,100 @@ REF_API = [
     "free_surface_memory", "adjustvectorlenght_s", "grid_from_data_pointer",
     "generate_grid_from_fn", "free_memory_grd", "alloc_F",
 ]
+
+
+class CMeasure(C.Structure):
+    """mc33_measure (api.py has mc33hip_measures only: 64-bit counts)"""
+    _fields_ = [("nV", C.c_uint), ("nT", C.c_uint), ("area", C.c_double), ("volume", C.c_double), ("moment", C.c_double * 3),
+                ("origin", C.c_double * 3), ("bbox_min", C.c_double * 3), ("bbox_max", C.c_double * 3), ("property_integral", C.c_double),
+                ("has_property", C.c_int)]
+
+
+class CTopology(C.Structure):
+    """mc33_topology (api.py has mc33hip_topology only: 64-bit counts)"""
+    _fields_ = [("nV", C.c_uint), ("nT", C.c_uint)] + \
+               [(n, C.c_ulonglong) for n in ("referenced_vertices", "edges", "boundary_edges", "nonmanifold_edges", "misoriented_edges", "degenerate_triangles",
+                                             "boundary_loops", "components", "closed_components", "genus_sum")] + \
+               [("euler", C.c_longlong)] + [(n, C.c_int) for n in ("closed", "manifold", "oriented", "genus_defined")]
+
+
+# The mirrors of marching_cubes_33.h that live here, not in api.py's STRUCTS: C type -> {(double build, GRD_ORTHOGONAL): class}
+# where MC33_real or the grid flavour changes the layout, else the class.  tests/test_bindings_cpu.py compares every field of
+# every one with the compiler.  (MC33 and MC3364 name _A / A_: they are not the GRD_ORTHOGONAL layout, and no test reads a member
+# behind `store` of such a build.)
+MIRRORS = {
+    "_GRD": {(False, False): GRD, (True, False): GRD, (False, True): GRDO, (True, True): GRDO},
+    "surface": {(False, False): SURFACE, (True, False): SURFACE64, (False, True): SURFACE, (True, True): SURFACE64},
+    "MC33": {(False, False): MC33, (True, False): MC3364},
+    "mc33_user_data": USER,
+    "mc33_measure": CMeasure,
+    "mc33_topology": CTopology,
+}
+
+FN = C.CFUNCTYPE(C.c_double, C.c_double, C.c_double, C.c_double)  # generate_grid_from_fn's callback
+
+
+def signatures(real, GRD, SURFACE, MC33):
+    """name -> (restype, argtypes) of every function of include/marching_cubes_33.h, for one flavour's MC33_real and mirrors of
+    _GRD, surface and MC33: the form of api.py's SIGNATURES.  MC33Lib applies it to the library it opens;
+    tests/test_bindings_cpu.py compares every row with the header."""
+    P, I, U, D, Q, S = C.POINTER, C.c_int, C.c_uint, C.c_double, C.c_ulonglong, C.c_char_p
+    M, G, SF = P(MC33), P(GRD), P(SURFACE)
+    return {
+        "create_MC33": (M, [G]),
+        "calculate_isosurface": (SF, [M, real]),
+        "size_of_isosurface": (Q, [M, real, P(U), P(U)]),
+        "free_MC33": (None, [M]),
+        "free_surface_memory": (None, [SF]),
+        "adjustvectorlenght_s": (None, [SF]),
+        "calculate_isosurfaces": (U, [M, P(real), U, P(SF)]),
+        "MC33_grid_changed": (None, [M]),
+        "MC33_set_property_grid": (I, [M, G]),
+        "MC33_set_color_map": (I, [M, P(I), U, D, D]),
+        "MC33_measure_isosurface": (I, [M, real, P(CMeasure)]),
+        "MC33_measure_isosurfaces": (U, [M, P(real), U, P(CMeasure)]),
+        "MC33_measure_components": (I, [M, real, P(api.Component), U, P(U), P(U)]),
+        "MC33_isosurface_topology": (I, [M, real, P(CTopology)]),
+        "MC33_component_topology": (I, [M, real, P(api.ComponentTopology), U, P(U)]),
+        "MC33_set_color_source": (I, [M, I]),
+        "MC33_isosurface_curvature": (I, [M, real, P(api.IsosurfaceCurvature)]),
+        "MC33_select_components": (I, [C.c_void_p, C.c_void_p, U, P(api.ComponentFilter), C.c_void_p]),
+        "MC33_calculate_filtered_isosurface": (SF, [M, real, P(api.ComponentFilter), P(U), P(U)]),
+        "MC33_calculate_smoothed_isosurface": (SF, [M, real, P(api.SurfaceSmoothing)]),
+        "MC33_calculate_simplified_isosurface": (SF, [M, real, P(api.SurfaceSimplification)]),
+        "MC33_calculate_clipped_isosurface": (SF, [M, real, P(api.SurfaceClip)]),
+        "MC33_clip_box": (I, [P(D * 3), P(D * 3), P(api.SurfaceClip)]),
+        "MC33_calculate_capped_isosurface": (SF, [M, real, P(api.SurfaceCap), P(api.SurfaceCapInfo)]),
+        "MC33_render_isosurface": (I, [M, real, P(api.View), U, U, P(api.Image)]),
+        "MC33_free_image": (None, [P(api.Image)]),
+        "MC33_view_fit": (I, [M, P(D * 3), P(D * 3), D, U, U, P(api.View)]),
+        "MC33_write_image_ppm": (I, [P(api.Image), S]),
+        "MC33_isosurface_distance": (I, [M, real, real, P(api.SurfaceDistance)]),
+        "MC33_simplification_error": (I, [M, real, P(api.SurfaceSimplification), P(api.SurfaceDistance)]),
+        "MC33_section_isosurface": (P(api.SurfaceSection), [M, real, P(D * 4)]),
+        "MC33_free_section": (None, [P(api.SurfaceSection)]),
+        "MC33_section_contours": (I, [M, real, P(D * 4), P(api.Contour), U, P(U)]),
+        "MC33_section_profile": (I, [M, real, P(D * 3), P(D), U, P(api.SectionLevel)]),
+        "MC33_gaussian_taps": (I, [D, U, P(D)]),
+        "MC33_create_resampled": (M, [M, P(api.GridResampling)]),
+        "MC33_resampled_grid": (G, [M]),
+        "MC33_grid_spectrum": (I, [M, P(real), U, P(Q), P(Q), P(api.SpectrumInfo)]),
+        "MC33_isovalue_ladder": (I, [D, D, U, P(real)]),
+        "write_bin_s": (I, [SF, S]),
+        "read_bin_s": (SF, [S]),
+        "write_txt_s": (I, [SF, S]),
+        "write_obj_s": (I, [SF, S]),
+        "write_ply_s": (I, [SF, S, S, S]),
+        "alloc_F": (I, [G]),
+        "free_memory_grd": (None, [G]),
+        "grid_from_data_pointer": (G, [U, U, U, C.c_void_p]),
+        "generate_grid_from_fn": (G, [D] * 9 + [FN]),
+        "read_grd": (G, [S]),
+        "read_grd_binary": (G, [S]),
+        "read_scanfiles": (G, [S, U, I]),
+        "read_raw_file": (G, [S, P(U), I, I]),
+        "read_dat_file": (G, [S]),
+    }
 
 
 def preload_torch():
@@ -172,23 +275,11 @@ class MC33Lib:
             preload_torch()
         # RTLD_LOCAL (default): several of these libraries define the same symbols.
         self.lib = C.CDLL(path)
-        L = self.lib
-        L.grid_from_data_pointer.restype = C.POINTER(self.GRD)
-        L.grid_from_data_pointer.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
-        L.create_MC33.restype = C.POINTER(self.MC33)
-        L.create_MC33.argtypes = [C.POINTER(self.GRD)]
-        L.calculate_isosurface.restype = C.POINTER(self.SURFACE)
-        L.calculate_isosurface.argtypes = [C.POINTER(self.MC33), self.real]
-        L.size_of_isosurface.restype = C.c_ulonglong
-        L.size_of_isosurface.argtypes = [C.POINTER(self.MC33), self.real, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
-        L.free_MC33.restype = None
-        L.free_MC33.argtypes = [C.POINTER(self.MC33)]
-        L.free_surface_memory.restype = None
-        L.free_surface_memory.argtypes = [C.POINTER(self.SURFACE)]
-        L.adjustvectorlenght_s.restype = None
-        L.adjustvectorlenght_s.argtypes = [C.POINTER(self.SURFACE)]
-        L.free_memory_grd.restype = None
-        L.free_memory_grd.argtypes = [C.POINTER(self.GRD)]
+        self.signatures = signatures(self.real, self.GRD, self.SURFACE, self.MC33)
+        for name, (restype, argtypes) in self.signatures.items():
+            if name in REF_API or hasattr(self.lib, name):  # (the reference has none of the extensions, the emulated device layer not all)
+                fn = getattr(self.lib, name)
+                fn.restype, fn.argtypes = restype, argtypes
 
     # -- grid ------------------------------------------------------------------------------
     def make_grid(self, data, r0=None, d=None, inclined=None):

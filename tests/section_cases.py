@@ -4,6 +4,8 @@ adds to it.  numpy only."""
 import numpy as np
 
 import clip_cases as cc
+import section_oracle as so
+from mesh_checks import reference_mesh
 
 PLANE_Z = cc.PLANE_Z
 RUNS = cc.RUNS
@@ -68,3 +70,19 @@ def ladder_offsets(V, normal, n):
     lo, hi = float(b.min()), float(b.max())
     pad = 0.05 * (hi - lo) + 1e-3
     return [-(hi + pad) + (hi - lo + 2 * pad) * (k / (n - 1) if n > 1 else 0.5) for k in range(n)]
+
+
+# ---- the cases on the reference's meshes: the planes, attributes and modes of tests/clip_cases.py ----------------------------------
+
+ORIGIN = (1.5, 1.5, 1.5)  # the reference point of the context of mesh_harness.tiny_grid: r0 + 0.5 * N * d of a 4^3 grid
+
+_results = {}
+
+
+def sectioned(reflibs, name, which):
+    """the oracle's result of one case on a fixture row's reference surface, computed once, shared and left unchanged"""
+    key = (name, which)
+    if key not in _results:
+        s = reference_mesh(reflibs, name)[4]
+        _results[key] = so.section(s.V, s.T, cc.plane_of(s.V, which), cc.attributes(s.nV), cc.MODES, ORIGIN)
+    return _results[key]

@@ -13,11 +13,10 @@ sys.path[:0] = [HERE, os.path.dirname(HERE)]
 import fixtures as fx  # noqa: E402
 from mc33_capi import MC33Lib, product_path  # noqa: E402
 from mc33_c_library_amd.api import Contour, SectionLevel  # noqa: E402
-from test_section_cpu import c_section_api  # noqa: E402
 
 assert os.environ.get("MC33_HIP_DEVICES") == "0,0"
 lib = MC33Lib(product_path("f32"), "f32")
-L = c_section_api(lib)
+L = lib.lib
 iso = lib.real(0.0)
 data, r0, d = fx.cos_field(32)
 G, keep = lib.make_grid(data, r0, d)

@@ -1,8 +1,14 @@
 """Made-up meshes for the vertex clustering (tests/test_gpu_simplify.py): the triangle lists of tests/mesh_pieces.py with positions
-assigned here, so that the referenced vertices fall into lattice cells in numbers the test chooses.  numpy only."""
+assigned here, so that the referenced vertices fall into lattice cells in numbers the test chooses; and what the CPU and the GPU
+tests of the part share: the cases on the reference's meshes with the oracle's results, made once."""
+import ctypes as C
+
 import numpy as np
 
 import mesh_pieces as mp
+import simplify_oracle as sp
+from mc33_c_library_amd.api import SurfaceSimplification
+from mesh_checks import reference_mesh
 
 ORIGIN, CELL = (-3.0, 1.0, 0.5), (0.5, 0.25, 2.0)  # cells whose edges float32 holds exactly
 SIDE = 160  # clusters per row and rows per layer of the made-up lattices: 65 000 clusters take three layers
@@ -81,3 +87,40 @@ def edge_of_the_lattice(seed):
     clamped = int(np.count_nonzero((kind >= 3) & (kind <= 6))) + int(rows[kind == 7][::9].size)
     V = np.concatenate([V, np.array([[np.nan] * 3, [-1.0, 5.0, 5.0], [5.0, 5.0, 5.0]], np.float32)])
     return V, np.ascontiguousarray(T), clamped
+
+
+# ---- the cases on the reference's meshes (tests/test_simplify_cpu.py pins the oracle to TABLE, tests/test_gpu_simplify.py the device) ----
+
+CELLS = {"2x2x2": (2.0, 2.0, 2.0), "3x2x5": (3.0, 2.0, 5.0)}  # in grid cells
+MODES = {"mean": sp.MEAN, "first": sp.FIRST}
+
+# (fixture, cell) -> nV_out, nT_out, clusters, max_cluster, collapsed, duplicates (duplicates dropped; the mode changes none of them)
+TABLE = {
+    ("sphere", "2x2x2"): (4568, 9132, 4568, 14, 32924, 0),
+    ("sphere", "3x2x5"): (2136, 4268, 2136, 31, 37788, 0),
+    ("blobs", "2x2x2"): (5611, 11114, 5611, 15, 41050, 0),
+    ("blobs", "3x2x5"): (2551, 5045, 2551, 36, 47062, 57),
+    ("sheet", "2x2x2"): (3220, 6106, 3220, 11, 23326, 0),
+    ("sheet", "3x2x5"): (1558, 2889, 1558, 27, 26542, 1),
+    ("noise", "2x2x2"): (3892, 17388, 3898, 38, 83001, 2495),
+    ("noise", "3x2x5"): (1258, 6913, 1258, 90, 92975, 2996),
+    ("quant", "2x2x2"): (1728, 7271, 1728, 20, 25911, 766),
+    ("quant", "3x2x5"): (480, 2596, 480, 55, 30313, 1039),
+}
+
+_results = {}
+
+
+def simplified(reflibs, name, cell, mode, drop=True):
+    """the oracle's result of one case on a fixture row's reference surface, computed once, shared and left unchanged"""
+    key = (name, cell, mode, drop)
+    if key not in _results:
+        data, r0, d, iso, s = reference_mesh(reflibs, name)
+        c = tuple(CELLS[cell][k] * d[k] for k in range(3))
+        _results[key] = sp.simplify(s.V, s.T, c, r0, MODES[mode], drop)
+    return _results[key]
+
+
+def csimp(cell, mode, drop):
+    """an mc33_simplification"""
+    return SurfaceSimplification((C.c_double * 3)(*cell), mode, int(drop))

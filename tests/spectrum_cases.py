@@ -1,10 +1,13 @@
 """The case table of the contour spectrum, shared by the host build of the kernel's text (test_spectrum_cpu.py) and
 the device (test_gpu_spectrum.py): the smallest shapes at which the tiling, the packed loads and the counters can go wrong, not the
 workload's.  The oracle's result of a case is computed once, shared and left unchanged."""
+import ctypes as C
+
 import numpy as np
 
 import fixtures as fx
 import spectrum_oracle as so
+from mc33_c_library_amd.api import SpectrumInfo
 
 # restated from mc33_c_library_amd/csrc/mc33_spectrum.hip.h (test_spectrum_cpu.py checks that they are the header's)
 SP_TILE_X, SP_TILE_Y = 64, 16   # cells
@@ -144,3 +147,20 @@ def split(nz, parts):
     """`parts` disjoint ranges that tile cell slices [0, nz): as even as they come, one-slice ranges where parts >= nz / 2"""
     edges = sorted(set(int(round(k * nz / parts)) for k in range(parts + 1)))
     return [(a, b) for a, b in zip(edges[:-1], edges[1:])]
+
+
+def report(got, want):
+    return "cut_cells %s\n     want %s\nhistogram %s\n     want %s\n%s\n%s" % (got.cut_cells.tolist(), want.cut_cells.tolist(), got.histogram.tolist(), want.histogram.tolist(), got[2:], want[2:])
+
+
+def c_spectrum(lib, L, M, isos):
+    """MC33_grid_spectrum of an MC33Lib's object as the oracle's tuple, or its return code when it refuses"""
+    n = len(isos)
+    arr = (lib.real * max(n, 1))(*isos)
+    cut = (C.c_ulonglong * max(n, 1))()
+    hist = (C.c_ulonglong * (n + 1))()
+    info = SpectrumInfo()
+    rc = L.MC33_grid_spectrum(M, arr, n, cut, hist, C.byref(info))
+    if rc:
+        return rc
+    return so.Spectrum(np.array(cut[:n], np.uint64), np.array(hist[:], np.uint64), info.points, info.cells, info.nan_samples, info.sample_min, info.sample_max)

@@ -13,8 +13,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 import spectrum_cases as sc  # noqa: E402
 import spectrum_oracle as so  # noqa: E402
 from mc33_capi import MC33Lib, product_path  # noqa: E402
-from test_gpu_spectrum import c_spectrum, capi  # noqa: E402
-from test_spectrum_cpu import report  # noqa: E402
+from spectrum_cases import c_spectrum, report  # noqa: E402
 
 
 def main():
@@ -22,7 +21,7 @@ def main():
     done = 0
     for dtype, name in (("f32", "special_values"), ("u8", "one_point_beyond_noise"), ("u16", "tile_minus_1_beyond_cos"), ("f64", "narrow_dword_plus_3_noise")):
         lib = MC33Lib(product_path(dtype), dtype)
-        L = capi(lib)
+        L = lib.lib
         F, isos, want = sc.case(name, dtype)
         G, keep = lib.make_grid(np.array(F))
         M = L.create_MC33(G)

@@ -23,8 +23,8 @@ import cap_cases as cc
 import cap_oracle as co
 import measure_oracle as mo
 import topology_oracle as to
-from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets
-from test_mesh_common_cpu import launched
+from mc33_c_library_amd.api import SurfaceCap, SurfaceCapInfo
+from mesh_checks import assert_exported, assert_kernels, host_logic, launched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -33,7 +33,7 @@ C_NAMES = ["MC33_calculate_capped_isosurface"]
 # (the tile scans over what this part counts are instances of its own of the shared kernels)
 KERNELS = ["k_cap_sides", "k_cap_invert", "k_mesh_tile_sum<CapTris>", "k_mesh_tile_sum<CapNamed>", "k_mesh_place<CapTris, 0>", "k_mesh_place<CapNamed, 1>"] + \
           launched("k_mesh_clear", "k_mesh_scan_top")
-ALL = cc.NAMES + cc.VARIANTS
+ALL = cc.ALL
 CLOSED = tuple(n for n in ALL if n not in cc.OPEN)
 
 _results = {}
@@ -268,15 +268,6 @@ def test_attributes_of_new_vertices(oracles):
 
 # ---- names, kernels, structs ------------------------------------------------------------------------------------------------------
 
-class CCap(C.Structure):
-    _fields_ = [("lo", C.c_uint * 3), ("hi", C.c_uint * 3), ("invert", C.c_int)]
-
-
-class CCapInfo(C.Structure):
-    _fields_ = [(n, C.c_uint) for n in ("nV", "nT", "cap_vertices", "cap_triangles", "rim_segments", "capped_cells", "skipped_cells", "off_face_edges")] + \
-               [("solid_above", C.c_int), ("closed", C.c_int)]
-
-
 def test_new_names_are_declared():
     hip = open(os.path.join(ROOT, "include", "mc33_hip.h")).read()
     pub = open(os.path.join(ROOT, "include", "marching_cubes_33.h")).read()
@@ -306,18 +297,6 @@ def test_cap_kernels_are_in_the_code_object(dtype):
     assert_kernels(dtype, KERNELS + ["k_cap_%s<%s>" % (k, real) for k in ("flag", "rim", "cell", "emit", "verts")])
 
 
-def test_python_structs_match_the_header():
-    from mc33_c_library_amd.api import Capping, SurfaceCap, SurfaceCapInfo
-    members = ["N", "T", "nV", "nT", "capV", "capT", "iso", "lo", "hi", "invert", "attr", "n_attr", "attr_mode", "nV_out", "cap_vertices", "off_face_edges",
-               "nonfinite_vertices", "solid_above", "closed"]
-    want = c_layout(["sizeof(mc33hip_capping)", "sizeof(mc33_cap)", "sizeof(mc33_cap_info)", "offsetof(mc33_cap, invert)", "offsetof(mc33_cap_info, closed)"] +
-                    offsets("mc33hip_capping", members))
-    got = [C.sizeof(Capping), C.sizeof(SurfaceCap), C.sizeof(SurfaceCapInfo), SurfaceCap.invert.offset, SurfaceCapInfo.closed.offset] + \
-          [getattr(Capping, m).offset for m in members]
-    assert got == want
-    assert [C.sizeof(CCap), C.sizeof(CCapInfo), CCap.invert.offset, CCapInfo.closed.offset] == want[1:5]
-
-
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
 def test_host_logic_library_refuses_to_cap(dtype):
     """mc33_capi.c linked with the emulated device layer, which cannot cap: the library still loads (a weak reference),
@@ -325,16 +304,14 @@ def test_host_logic_library_refuses_to_cap(dtype):
     no device in any build, for a refused box -, and the object extracts as before."""
     with host_logic(dtype) as h:
         lib, L, M, iso = h.lib, h.L, h.M, h.iso
-        L.MC33_calculate_capped_isosurface.restype = C.POINTER(lib.SURFACE)
-        L.MC33_calculate_capped_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CCap), C.POINTER(CCapInfo)]
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         before = (M.contents.iso, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V)
         L.free_surface_memory(S)
-        info = CCapInfo()
+        info = SurfaceCapInfo()
         info.nV, info.closed = 77, 5
-        good = CCap((C.c_uint * 3)(1, 1, 1), (C.c_uint * 3)(9, 9, 9), 0)
-        cases = [None, good, CCap((C.c_uint * 3)(3, 0, 0), (C.c_uint * 3)(3, 9, 9), 0), CCap((C.c_uint * 3)(0, 0, 0), (C.c_uint * 3)(9, 99, 9), 1)]
+        good = SurfaceCap((C.c_uint * 3)(1, 1, 1), (C.c_uint * 3)(9, 9, 9), 0)
+        cases = [None, good, SurfaceCap((C.c_uint * 3)(3, 0, 0), (C.c_uint * 3)(3, 9, 9), 0), SurfaceCap((C.c_uint * 3)(0, 0, 0), (C.c_uint * 3)(9, 99, 9), 1)]
         for opt in cases:
             assert not L.MC33_calculate_capped_isosurface(M, lib.real(iso + 1), C.byref(opt) if opt is not None else None, C.byref(info))
             assert (M.contents.iso, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V) == before

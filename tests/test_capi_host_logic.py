@@ -85,10 +85,6 @@ def test_object_reuse_sizes_and_batches(host, want, devices, monkeypatch):
         monkeypatch.setenv("MC33_HIP_DEVICES", devices)
     lib, ref = host["f32"], want["f32"]
     L = lib.lib
-    L.calculate_isosurfaces.restype = C.c_uint
-    L.calculate_isosurfaces.argtypes = [C.POINTER(lib.MC33), C.POINTER(C.c_float), C.c_uint, C.POINTER(C.POINTER(SURFACE))]
-    L.MC33_grid_changed.restype = None
-    L.MC33_grid_changed.argtypes = [C.POINTER(lib.MC33)]
     a, r0, d = fx.cos_field(36)
     a = a.copy()
     G, keep = lib.make_grid(a, r0, d)

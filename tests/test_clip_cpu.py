@@ -18,10 +18,9 @@ import clip_cases as cc
 import clip_oracle as co
 import measure_oracle as mo
 import topology_oracle as to
-from mc33_capi import product_path
-from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets
-from test_mesh_common_cpu import launched
-from test_simplify_cpu import mesh
+from clip_cases import MODES, PLANES, TABLE, attributes, clipped, plane_of
+from mc33_c_library_amd.api import SurfaceClip
+from mesh_checks import assert_exported, assert_kernels, host_logic, launched, reference_mesh as mesh
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -29,69 +28,6 @@ HIP_NAMES = ["mc33hip_clip_surface"]
 C_NAMES = ["MC33_calculate_clipped_isosurface", "MC33_clip_box"]
 KERNELS = ["k_clip_tri", "k_clip_own", "k_clip_emit"] + launched("k_mesh_clear", "k_mesh_tile_sum<MeshFlag>", "k_mesh_tile_sum<ClipOwned>", "k_mesh_tile_sum<ClipOutputs>",
                                                            "k_mesh_scan_top", "k_mesh_place<MeshFlag, 1>")
-PLANES = ("oblique", "on-grid", "miss", "all")
-MODES = (co.LERP_F32, co.COPY)
-
-# (fixture, plane) -> nV_out, nT_out, kept, cut vertices, on the plane, whole, cut, dropped triangles (no invalid triangle, no
-# vertex whose s is not finite)
-TABLE = {
-    ("sphere", "oblique"): (11112, 21625, 10515, 597, 0, 20730, 597, 20729),
-    ("sphere", "on-grid"): (11793, 23316, 11793, 0, 268, 23316, 0, 18740),
-    ("sphere", "miss"): (21030, 42056, 21030, 0, 0, 42056, 0, 0),
-    ("sphere", "all"): (0, 0, 0, 0, 0, 0, 0, 42056),
-    ("blobs", "oblique"): (13564, 26578, 13068, 496, 0, 25834, 496, 25834),
-    ("blobs", "on-grid"): (13596, 26610, 13596, 0, 528, 26610, 0, 25554),
-    ("blobs", "miss"): (26136, 52164, 26136, 0, 0, 52164, 0, 0),
-    ("blobs", "all"): (0, 0, 0, 0, 0, 0, 0, 52164),
-    ("sheet", "oblique"): (7993, 15171, 7536, 457, 0, 14486, 455, 14491),
-    ("sheet", "on-grid"): (11648, 22496, 11648, 0, 288, 22496, 0, 6936),
-    ("sheet", "miss"): (15072, 29432, 15072, 0, 0, 29432, 0, 0),
-    ("sheet", "all"): (0, 0, 0, 0, 0, 0, 0, 29432),
-    ("noise", "oblique"): (27552, 54401, 24307, 3245, 0, 49592, 3212, 50080),
-    ("noise", "on-grid"): (25547, 53093, 25547, 0, 822, 53093, 0, 49791),
-    ("noise", "miss"): (48809, 102884, 48809, 0, 0, 102884, 0, 0),
-    ("noise", "all"): (0, 0, 0, 0, 0, 0, 0, 102884),
-    ("quant", "oblique"): (9289, 18449, 7946, 1343, 16, 16454, 1358, 16136),
-    ("quant", "on-grid"): (8499, 17781, 8499, 0, 480, 17781, 0, 16167),
-    ("quant", "miss"): (15775, 33948, 15775, 0, 0, 33948, 0, 0),
-    ("quant", "all"): (0, 0, 0, 0, 0, 0, 0, 33948),
-}
-
-
-def plane_of(V, which):
-    """the four planes of a mesh, exact functions of its vertices: oblique through the middle of the bounding box; x - x0 with x0
-    the most frequent x of the vertices - a whole grid plane of them has s == 0 exactly; one that misses; one that removes all"""
-    lo, hi = V.min(axis=0).astype(np.float64), V.max(axis=0).astype(np.float64)
-    if which == "oblique":
-        n = np.array([0.3, -0.5, 0.8])
-        c = 0.5 * (lo + hi)
-        return (n[0], n[1], n[2], -float((n[0] * c[0] + n[1] * c[1]) + n[2] * c[2]))
-    if which == "on-grid":
-        x, count = np.unique(V[:, 0], return_counts=True)
-        inner = (x > lo[0] + 0.25 * (hi[0] - lo[0])) & (x < hi[0] - 0.25 * (hi[0] - lo[0]))
-        return (1.0, 0.0, 0.0, -float(x[inner][np.argmax(count[inner])]))
-    if which == "miss":
-        return (1.0, 0.0, 0.0, 1.0 - float(lo[0]))
-    return (1.0, 0.0, 0.0, -1.0 - float(hi[0]))
-
-
-def attributes(nV):
-    """a float per vertex (interpolated) and a word per vertex (copied)"""
-    return (cc.floats(nV, 11), np.random.default_rng(12).integers(0, 1 << 32, nV, dtype=np.uint64).astype(np.uint32))
-
-
-_results = {}
-
-
-def clipped(reflibs, name, which):
-    """the oracle's result of one case, computed once, shared (tests/test_gpu_clip.py uses it too) and left unchanged"""
-    key = (name, which)
-    if key not in _results:
-        s = mesh(reflibs, name)[4]
-        _results[key] = co.clip(s.V, s.N, s.T, plane_of(s.V, which), attributes(s.nV), MODES)
-    return _results[key]
-
-
 @pytest.mark.parametrize("which", PLANES)
 @pytest.mark.parametrize("name", list(mo.FIXTURES))
 def test_oracle_on_the_reference_meshes(reflibs, name, which):
@@ -207,10 +143,6 @@ def test_made_up_meshes_are_what_they_claim():
 
 # ---- names, kernels, structs ------------------------------------------------------------------------------------------------------
 
-class CClip(C.Structure):
-    _fields_ = [("n", C.c_uint), ("plane", (C.c_double * 4) * 6)]
-
-
 def test_new_names_are_declared():
     hip = open(os.path.join(ROOT, "include", "mc33_hip.h")).read()
     pub = open(os.path.join(ROOT, "include", "marching_cubes_33.h")).read()
@@ -240,26 +172,15 @@ def test_clipping_kernels_are_in_the_code_object(dtype):
     assert_kernels(dtype, KERNELS + ["k_clip_class<%s>" % real, "k_clip_rows<%s>" % real, "k_clip_new<%s>" % real])
 
 
-def test_python_structs_match_the_header():
-    from mc33_c_library_amd.api import Clipping, SurfaceClip
-    members = ["N", "T", "nV", "nT", "attr", "n_attr", "attr_mode", "plane", "oV", "oN", "oT", "oAttr", "oMap", "capV", "capT", "nV_out", "kept_vertices",
-               "on_plane_vertices", "nonfinite_vertices"]
-    want = c_layout(["sizeof(mc33hip_clipping)", "sizeof(mc33_clip)", "offsetof(mc33_clip, plane)"] + offsets("mc33hip_clipping", members))
-    got = [C.sizeof(Clipping), C.sizeof(SurfaceClip), SurfaceClip.plane.offset] + [getattr(Clipping, m).offset for m in members]
-    assert got == want
-    assert [C.sizeof(CClip), CClip.plane.offset] == want[1:3]
-
-
 def test_clip_box_is_exact_and_refuses_bad_bounds():
     """host C of the product library; no GPU is touched"""
-    L = C.CDLL(product_path("f32"))
-    L.MC33_clip_box.restype = C.c_int
-    L.MC33_clip_box.argtypes = [C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3), C.POINTER(CClip)]
+    from mc33_c_library_amd import load_library
+    L = load_library("f32")
     three = C.c_double * 3
 
     def box(lo, hi, out):
         return L.MC33_clip_box(C.byref(three(*lo)), C.byref(three(*hi)), C.byref(out))
-    out = CClip()
+    out = SurfaceClip()
     lo, hi = (0.1, -2.5, 1e-300), (0.30000000000000004, 7.0, 1e300)
     assert box(lo, hi, out) == 0 and out.n == 6
     got = [[out.plane[k][j] for j in range(4)] for k in range(6)]
@@ -267,7 +188,7 @@ def test_clip_box_is_exact_and_refuses_bad_bounds():
     inf, nan = float("inf"), float("nan")
     bad = [((0, 0, 0), (1, 1, 0)), ((0, 2, 0), (1, 1, 1)), ((0, 0, 0), (inf, 1, 1)), ((-inf, 0, 0), (1, 1, 1)), ((nan, 0, 0), (1, 1, 1)), ((0, 0, 0), (1, nan, 1))]
     for lo, hi in bad:
-        canary = CClip()
+        canary = SurfaceClip()
         canary.n = 77
         canary.plane[5][3] = 42.0
         assert box(lo, hi, canary) == -1 and canary.n == 77 and canary.plane[5][3] == 42.0, (lo, hi)
@@ -286,21 +207,17 @@ def test_host_logic_library_refuses_to_clip(dtype):
     before."""
     with host_logic(dtype) as h:
         lib, L, M, iso = h.lib, h.L, h.M, h.iso
-        L.MC33_calculate_clipped_isosurface.restype = C.POINTER(lib.SURFACE)
-        L.MC33_calculate_clipped_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CClip)]
-        L.MC33_clip_box.restype = C.c_int
-        L.MC33_clip_box.argtypes = [C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3), C.POINTER(CClip)]
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         before = (M.contents.iso, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V)
         L.free_surface_memory(S)
         three = C.c_double * 3
-        boxed = CClip()
+        boxed = SurfaceClip()
         assert L.MC33_clip_box(C.byref(three(1, 1, 1)), C.byref(three(9, 9, 9)), C.byref(boxed)) == 0 and boxed.n == 6
         inf, nan = float("inf"), float("nan")
-        cases = [boxed, CClip(0), CClip(7)]
+        cases = [boxed, SurfaceClip(0), SurfaceClip(7)]
         for pl in ((1, 0, 0, -5), (0, 0, 0, 1), (nan, 0, 1, 0), (1, inf, 0, 0), (1, 0, 0, -inf)):
-            one = CClip(1)
+            one = SurfaceClip(1)
             for j in range(4):
                 one.plane[0][j] = pl[j]
             cases.append(one)

@@ -7,15 +7,12 @@ and every kernel of the hot path must have `.private_segment_fixed_size: 0` and 
 segment pays for it at every wave launch, and spills in a streaming loop are HBM traffic that is not algorithmic.
 """
 import os
-import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
+from mesh_checks import kernel_metadata
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
 TYPES = ("f32", "u16", "u8", "u32", "f64")
 
 # kernels allowed a scratch segment (bytes), by demangled-name prefix: none of the hot path.  The generic per-cell kernels
@@ -32,45 +29,6 @@ MAX_VGPRS = {"k_sweep<1, 1, 0>": 128, "k_cells": 128, "k_emit_fast_triangles": 6
 MAX_SGPR_SPILLS = {"k_sweep<": 1300, "k_sweep<1, 1,": 32, "k_sweep<2, 1,": 32, "k_sweep<4, 1,": 32, "k_sweep<2, 4, 2>": 320, "k_sweep<4, 4, 2>": 320,
                    "k_cells": 0, "k_slots": 0, "k_boundary": 0, "k_scan_reduce": 0, "k_scan_apply": 0, "k_emit_fast_triangles": 0,
                    "k_emit_vertices<": 64, "k_emit_vertices<0>": 8, "k_emit_vertices<1>": 8, "k_emit_vertices<2>": 8}
-
-
-def _tool(name):
-    p = os.path.join(LLVM, name)
-    return p if os.path.exists(p) else shutil.which(name)
-
-
-def kernel_metadata(lib):
-    """[{name, scratch, vgprs, vgpr_spills, sgpr_spills, lds}] of the gfx950 code object inside a product library."""
-    objcopy, bundler, readelf, filt = _tool("llvm-objcopy"), _tool("clang-offload-bundler"), _tool("llvm-readelf"), shutil.which("c++filt")
-    if not (objcopy and bundler and readelf):
-        pytest.skip("LLVM binutils of ROCm not found")
-    with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
-        subprocess.check_call([objcopy, "--dump-section", ".hip_fatbin=" + fat, lib, os.path.join(d, "copy.so")])
-        subprocess.check_call([bundler, "--type=o", "--unbundle", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co])
-        notes = subprocess.check_output([readelf, "--notes", co], text=True)
-    kernels, cur = [], {}
-    for line in notes.splitlines():
-        m = re.match(r"\s*-?\s*\.(\w+):\s+(\S.*)$", line)
-        if not m:
-            continue
-        k, v = m.group(1), m.group(2).strip().strip("'")
-        if k == "agpr_count" or (k == "args" and cur.get("name")):
-            pass
-        if k == "name" and v.startswith("_Z"):
-            cur["name"] = v
-        elif k in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size"):
-            cur[k] = int(v)
-        if k == "wavefront_size":  # last key of a kernel's record (keys are sorted)
-            if "name" in cur:
-                kernels.append(cur)
-            cur = {}
-    for kd in kernels:
-        if filt:
-            kd["pretty"] = subprocess.check_output([filt, kd["name"]], text=True).strip().split("(")[0].replace("void ", "")
-        else:
-            kd["pretty"] = kd["name"]
-    return kernels
 
 
 @pytest.mark.parametrize("dtype", TYPES)

@@ -17,7 +17,8 @@ import pytest
 
 import curvature_cases as cc
 import curvature_oracle as co
-from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets, reference_mesh
+from mc33_c_library_amd.api import IsosurfaceCurvature
+from mesh_checks import assert_exported, assert_kernels, host_logic, reference_mesh
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -27,11 +28,6 @@ HIP_NAMES = ["mc33hip_curvature_vertices", "mc33hip_color_values"]
 C_NAMES = ["MC33_set_color_source", "MC33_isosurface_curvature"]
 TYPES = ("f32", "f64", "u8", "u16", "u32")
 UNIT = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
-
-
-class CCurvature(C.Structure):
-    _fields_ = [("nV", C.c_uint), ("nT", C.c_uint), ("lo", C.c_double * 4), ("hi", C.c_double * 4), ("finite", C.c_ulonglong), ("undefined", C.c_ulonglong),
-                ("total_mean", C.c_double), ("total_gauss", C.c_double)]
 
 
 # ---- the oracle against closed forms ------------------------------------------------------------------------------------------------
@@ -195,33 +191,17 @@ def test_curvature_kernels_are_in_the_code_object(dtype):
     assert ks[mine[1]]["group_segment_fixed_size"] == 0 and ks["k_color_values"]["group_segment_fixed_size"] == 1024
 
 
-def test_python_structs_match_the_header():
-    from mc33_c_library_amd.api import Curvature, IsosurfaceCurvature
-    hf = ("dV", "nV", "sign", "oMean", "oGauss", "oK1", "oK2", "lo", "hi", "finite", "undefined")
-    cf = ("nV", "nT", "lo", "hi", "finite", "undefined", "total_mean", "total_gauss")
-    want = c_layout(["sizeof(mc33hip_curvature)"] + offsets("mc33hip_curvature", hf) + ["sizeof(mc33_curvature)"] + offsets("mc33_curvature", cf))
-    got = [C.sizeof(Curvature)] + [getattr(Curvature, f).offset for f in hf] + [C.sizeof(IsosurfaceCurvature)] + [getattr(IsosurfaceCurvature, f).offset for f in cf]
-    assert got == want
-    assert [C.sizeof(CCurvature)] + [getattr(CCurvature, f).offset for f in cf] == want[len(hf) + 1:]
-
-
 # ---- the host-logic build: mc33_capi.c on a device layer without the curvature pass ------------------------------------------------------
 
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
 def test_host_logic_library_refuses_a_curvature(dtype):
     with host_logic(dtype, n=12) as h:
         lib, L, M, iso = h.lib, h.L, h.M, h.iso
-        L.MC33_set_color_source.restype = C.c_int
-        L.MC33_set_color_source.argtypes = [C.POINTER(lib.MC33), C.c_int]
-        L.MC33_isosurface_curvature.restype = C.c_int
-        L.MC33_isosurface_curvature.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CCurvature)]
-        L.MC33_set_color_map.restype = C.c_int
-        L.MC33_set_color_map.argtypes = [C.POINTER(lib.MC33), C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
         before = bytes(C.string_at(C.addressof(M.contents), C.sizeof(lib.MC33)))
         for source in (1, 2, 3, 4, 5, -1):
             assert L.MC33_set_color_source(M, source) == -1
         assert L.MC33_set_color_source(M, 0) == 0 and L.MC33_set_color_source(None, 0) == -1
-        out = CCurvature(7, 8)
+        out = IsosurfaceCurvature(7, 8)
         assert L.MC33_isosurface_curvature(M, lib.real(iso), C.byref(out)) == -1 and L.MC33_isosurface_curvature(M, lib.real(iso), None) == -1
         assert (out.nV, out.nT) == (7, 8)
         assert bytes(C.string_at(C.addressof(M.contents), C.sizeof(lib.MC33))) == before

@@ -16,8 +16,8 @@ import pytest
 import distance_cases as dc
 import distance_oracle as do
 import measure_oracle as mo
-from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets, reference_mesh
-from test_mesh_common_cpu import launched
+from mc33_c_library_amd.api import SurfaceDistance, SurfaceSimplification
+from mesh_checks import assert_exported, assert_kernels, host_logic, launched, reference_mesh
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -25,11 +25,6 @@ HIP_NAMES = ["mc33hip_surface_distance", "mc33hip_distance_timing"]
 C_NAMES = ["MC33_isosurface_distance", "MC33_simplification_error"]
 KERNELS = ["k_dist_arg", "k_dist_sum"] + launched("k_mesh_tile_sum<MeshCount>", "k_mesh_scan_top", "k_mesh_place<MeshCount, 2>")
 MAX_VGPRS = 168  # the closest-point walk in doubles: three waves per SIMD (512 / 3, in granules of 8) - three blocks of 256 per CU
-
-
-class CDistance(C.Structure):
-    _fields_ = [("points", C.c_ulonglong), ("unmatched", C.c_ulonglong), ("max", C.c_double), ("min", C.c_double), ("mean", C.c_double), ("rms", C.c_double),
-                ("argmax", C.c_uint)]
 
 
 # ---- the oracle against hand-computed cases ----------------------------------------------------------------------------------------
@@ -203,16 +198,6 @@ def test_the_part_is_built_and_included_behind_the_renderer():
     assert "distance_cells_switch()" in context  # the knob is read where the renderer's is: when a context is created
 
 
-def test_python_structs_match_the_header():
-    from mc33_c_library_amd.api import Distance, SurfaceDistance
-    members = [n for n, _ in Distance._fields_]
-    small = [n for n, _ in SurfaceDistance._fields_]
-    want = c_layout(["sizeof(mc33hip_distance)", "sizeof(mc33_distance)"] + offsets("mc33_distance", small) + offsets("mc33hip_distance", members))
-    got = [C.sizeof(Distance), C.sizeof(SurfaceDistance)] + [getattr(SurfaceDistance, m).offset for m in small] + [getattr(Distance, m).offset for m in members]
-    assert got == want
-    assert [C.sizeof(CDistance)] + [getattr(CDistance, m).offset for m in small] == want[1:2 + len(small)]
-
-
 def test_documents_name_the_part():
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert re.search(r"^## 25\.", design, re.M) and "profiles/distance_timing.txt" in design and "mc33_distance.hip.h" in open(os.path.join(ROOT, "README.md")).read()
@@ -225,17 +210,12 @@ def test_host_logic_library_refuses_the_distance_calls(dtype):
     reference), both calls return -1 and leave the object alone, and the object extracts as before."""
     with host_logic(dtype) as h:
         lib, L, M, iso = h.lib, h.L, h.M, h.iso
-        from test_simplify_cpu import CSimplification
-        L.MC33_isosurface_distance.restype = C.c_int
-        L.MC33_isosurface_distance.argtypes = [C.POINTER(lib.MC33), lib.real, lib.real, C.POINTER(CDistance)]
-        L.MC33_simplification_error.restype = C.c_int
-        L.MC33_simplification_error.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CSimplification), C.POINTER(CDistance)]
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         before = (M.contents.iso, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V)
         L.free_surface_memory(S)
-        out = (CDistance * 2)()
-        sm = CSimplification((C.c_double * 3)(2, 2, 2), 0, 1)
+        out = (SurfaceDistance * 2)()
+        sm = SurfaceSimplification((C.c_double * 3)(2, 2, 2), 0, 1)
         assert L.MC33_isosurface_distance(M, lib.real(iso + 1), lib.real(iso), out) == -1
         assert L.MC33_isosurface_distance(M, lib.real(iso + 1), lib.real(iso), None) == -1
         assert L.MC33_simplification_error(M, lib.real(iso + 1), C.byref(sm), out) == -1

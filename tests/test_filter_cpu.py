@@ -17,62 +17,15 @@ import filter_oracle as fo
 import measure_oracle as mo
 import topology_oracle as to
 from mc33_capi import product_path
-from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets, reference_mesh
-from test_mesh_common_cpu import launched
+from filter_cases import ROWS, mesh
+from mc33_c_library_amd.api import Component, ComponentFilter, ComponentTopology
+from mesh_checks import assert_exported, assert_kernels, host_logic, launched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 HIP_NAMES = ["mc33hip_compact_components"]
 C_NAMES = ["MC33_select_components", "MC33_calculate_filtered_isosurface"]
 KERNELS = ["k_filt_roots", "k_filt_keep", "k_filt_tri_count", "k_filt_tris"] + launched("k_mesh_ref", "k_mesh_scan_top", "k_mesh_place<MeshFlag, 1>")
-
-
-class CComponent(C.Structure):
-    _fields_ = [("root", C.c_uint), ("nV", C.c_uint), ("nT", C.c_uint), ("area", C.c_double), ("volume", C.c_double)]
-
-
-class CComponentTopology(C.Structure):
-    _fields_ = [("root", C.c_uint), ("nV", C.c_uint), ("nT", C.c_uint)] + [(n, C.c_ulonglong) for n in to.COUNTS] + [("euler", C.c_longlong), ("genus", C.c_int)]
-
-
-class CFilter(C.Structure):
-    _fields_ = [("min_triangles", C.c_uint), ("min_area", C.c_double), ("min_abs_volume", C.c_double), ("largest", C.c_uint), ("closed_only", C.c_int)]
-
-
-_meshes = {}
-
-
-def mesh(reflibs, name):
-    """the reference's surface of a fixture row with its labels and both component tables, computed once and left unchanged"""
-    if name not in _meshes:
-        data, r0, d, iso, s = reference_mesh(reflibs, name)
-        ncomp, unref = mo.FIXTURES[name][2][2:4]
-        lab, gc, gu, _ = mo.label_components(s.T, s.nV)
-        assert (gc, gu) == (ncomp, unref)
-        c = mo.reference_point(r0, d, data.shape)
-        tab = mo.component_table(s.V, s.T, lab, c)[0]
-        topo = to.component_table(s.T, s.nV, lab)
-        for a in (lab, tab, topo):
-            a.setflags(write=False)
-        _meshes[name] = (data, r0, d, iso, s, lab, tab, topo, c)
-    return _meshes[name]
-
-
-# id -> (fixture, how the roots are chosen from (tab, topo), invert, components kept, nV_out, nT_out; None: the issue gives none)
-ROWS = {
-    "blobs-every-second": ("blobs", lambda tab, topo: tab["root"][1::2], False, 13, 12600, 25148),
-    "blobs-the-1868-row": ("blobs", lambda tab, topo: tab["root"][tab["nT"] == 1868], False, 1, 936, 1868),
-    "noise-min16": ("noise", lambda tab, topo: fo.select(tab, min_triangles=16), False, 8, 47990, 101970),
-    "noise-not-the-big-one": ("noise", lambda tab, topo: tab["root"][tab["nT"] >= 100], True, 151, 901, 1042),
-    "noise-closed": ("noise", lambda tab, topo: fo.select(tab, topo, closed_only=True), False, 86, 548, 752),
-    "noise-min-area": ("noise", lambda tab, topo: fo.select(tab, min_area=0.06), False, 2, None, None),
-    "quant-min8": ("quant", lambda tab, topo: fo.select(tab, min_triangles=8), False, 9, 15750, 33928),
-    "quant-all": ("quant", lambda tab, topo: tab["root"], False, 14, 15775, 33948),
-    "quant-closed": ("quant", lambda tab, topo: fo.select(tab, topo, closed_only=True), False, 7, 46, 64),
-    "quant-min-volume": ("quant", lambda tab, topo: fo.select(tab, min_abs_volume=5.0), False, 2, None, None),
-    "blobs-largest3": ("blobs", lambda tab, topo: fo.select(tab, largest=3), False, 3, None, 5820),
-}
-SIZED = [k for k, r in ROWS.items() if r[4] is not None and r[5] is not None]  # the eight rows that give both sizes
 
 
 @pytest.mark.parametrize("row", list(ROWS))
@@ -118,24 +71,19 @@ def test_oracle_on_the_reference_meshes(reflibs, row):
 
 # ---- the selection rule: host C in the product library, no GPU -------------------------------------------------------------------
 
-def bind_select(lib):
-    lib.MC33_select_components.restype = C.c_int
-    lib.MC33_select_components.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(CFilter), C.c_void_p]
-    return lib
-
-
 @pytest.fixture(scope="module")
 def select_lib():
     path = product_path("f32")
     assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
-    return bind_select(C.CDLL(path))
+    from mc33_c_library_amd import load_library
+    return load_library("f32")
 
 
 def c_select(lib, tab, topo=None, **criteria):
-    t = np.ascontiguousarray(tab, dtype=np.dtype(CComponent))
-    p = np.ascontiguousarray(topo, dtype=np.dtype(CComponentTopology)) if topo is not None else None
+    t = np.ascontiguousarray(tab, dtype=np.dtype(Component))
+    p = np.ascontiguousarray(topo, dtype=np.dtype(ComponentTopology)) if topo is not None else None
     roots = np.full(t.shape[0] + 1, 0xDEADBEEF, np.uint32)
-    f = CFilter(**{k: (int(v) if k == "closed_only" else v) for k, v in criteria.items()})
+    f = ComponentFilter(**{k: (int(v) if k == "closed_only" else v) for k, v in criteria.items()})
     n = lib.MC33_select_components(t.ctypes.data if t.shape[0] else None, p.ctypes.data if p is not None else None, t.shape[0], C.byref(f), roots.ctypes.data)
     assert roots[-1] == 0xDEADBEEF
     return None if n < 0 else roots[:n].copy()
@@ -173,9 +121,9 @@ def test_select_components_on_synthetic_tables(select_lib):
     assert c_select(select_lib, tab[:0]).tolist() == []  # n == 0
     # -1: closed_only without topology rows, null arguments
     assert c_select(select_lib, tab, None, closed_only=True) is None and fo.select(tab, None, closed_only=True) is None
-    t = np.ascontiguousarray(tab, dtype=np.dtype(CComponent))
+    t = np.ascontiguousarray(tab, dtype=np.dtype(Component))
     roots = np.zeros(9, np.uint32)
-    f = CFilter()
+    f = ComponentFilter()
     assert select_lib.MC33_select_components(t.ctypes.data, None, 9, None, roots.ctypes.data) == -1
     assert select_lib.MC33_select_components(None, None, 9, C.byref(f), roots.ctypes.data) == -1
     assert select_lib.MC33_select_components(t.ctypes.data, None, 9, C.byref(f), None) == -1
@@ -204,25 +152,13 @@ def test_filter_kernels_are_in_the_code_object(dtype, real):
     assert_kernels(dtype, KERNELS + ["k_filt_rows<%s>" % real])
 
 
-def test_python_structs_match_the_header():
-    from mc33_c_library_amd.api import Compaction, ComponentFilter
-    want = c_layout(["sizeof(mc33hip_compaction)"] + offsets("mc33hip_compaction", ["n_attr", "roots", "oMap", "components_kept"]) +
-                    ["sizeof(mc33_component_filter)"] + offsets("mc33_component_filter", ["largest", "closed_only"]))
-    got = [C.sizeof(Compaction), Compaction.n_attr.offset, Compaction.roots.offset, Compaction.oMap.offset, Compaction.components_kept.offset,
-           C.sizeof(ComponentFilter), ComponentFilter.largest.offset, ComponentFilter.closed_only.offset]
-    assert got == want
-    assert [C.sizeof(CFilter), CFilter.largest.offset, CFilter.closed_only.offset] == want[5:]
-
-
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
 def test_host_logic_library_refuses_to_filter(dtype):
     """mc33_capi.c linked with the emulated device layer, which cannot compact: the library still loads (a weak reference),
     MC33_calculate_filtered_isosurface returns NULL, the selection rule - plain host C - works, and the object extracts as before."""
     with host_logic(dtype) as h:
-        lib, L, M, iso = h.lib, bind_select(h.L), h.M, h.iso
-        L.MC33_calculate_filtered_isosurface.restype = C.POINTER(lib.SURFACE)
-        L.MC33_calculate_filtered_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CFilter), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
-        f, k, dr = CFilter(), C.c_uint(7), C.c_uint(7)
+        lib, L, M, iso = h.lib, h.L, h.M, h.iso
+        f, k, dr = ComponentFilter(), C.c_uint(7), C.c_uint(7)
         assert not L.MC33_calculate_filtered_isosurface(M, lib.real(iso), C.byref(f), C.byref(k), C.byref(dr)) and (k.value, dr.value) == (0, 0)
         tab = np.zeros(2, mo.COMPONENT)
         tab["root"], tab["nT"] = [0, 5], [3, 9]

@@ -13,9 +13,9 @@ import pytest
 import cap_cases as cc
 import cap_oracle as co
 import measure_oracle as mo
-from mc33_capi import MC33Lib, product_path
-from mesh_harness import CanariedCall, bits, device_grid, to_device
-from test_cap_cpu import ALL, CCap, CCapInfo
+from cap_cases import ALL
+from mc33_c_library_amd.api import SurfaceCap, SurfaceCapInfo
+from mesh_harness import CanariedCall, bits, capi, device_grid, to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -244,13 +244,6 @@ def test_call_order():
 
 # ---- the C API -----------------------------------------------------------------------------------------------------------------------
 
-def capi(dtype, nneg=False):
-    lib = MC33Lib(product_path(dtype, nneg=nneg), dtype)
-    lib.lib.MC33_calculate_capped_isosurface.restype = C.POINTER(lib.SURFACE)
-    lib.lib.MC33_calculate_capped_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CCap), C.POINTER(CCapInfo)]
-    return lib
-
-
 def capped_surface(lib, M, iso, options, info):
     S = lib.lib.MC33_calculate_capped_isosurface(M, lib.real(iso), C.byref(options) if options is not None else None, C.byref(info) if info is not None else None)
     if not S:
@@ -274,8 +267,8 @@ def test_c_api(name):
     try:
         V, N, T, pinfo = g.extract_capped(c.iso)
         for attempt in range(2):  # the staging set as it comes, and as the first call left it
-            info = CCapInfo()
-            got = capped_surface(lib, M, c.iso, None if attempt else CCap((C.c_uint * 3)(*c.lo), (C.c_uint * 3)(*c.hi), 0), info)
+            info = SurfaceCapInfo()
+            got = capped_surface(lib, M, c.iso, None if attempt else SurfaceCap((C.c_uint * 3)(*c.lo), (C.c_uint * 3)(*c.hi), 0), info)
             assert got is not None and (got.nV, got.nT) == (V.shape[0], T.shape[0]) and got.color.size == got.nV
             assert np.array_equal(bits(got.V), bits(V.cpu().numpy())) and np.array_equal(bits(got.N), bits(N.cpu().numpy()))
             assert np.array_equal(got.T, T.cpu().numpy().view(np.uint32))
@@ -283,13 +276,13 @@ def test_c_api(name):
             assert tuple(getattr(info, n) for n in co.COUNTS[2:8]) == tuple(pinfo[n] for n in co.COUNTS[2:8]) and (info.solid_above, info.closed) == (pinfo["solid_above"], pinfo["closed"])
         assert capped_surface(lib, M, c.iso, None, None).nV == V.shape[0]
         Vi, Ni, Ti, iinfo = g.extract_capped(c.iso, invert=True)
-        info = CCapInfo()
-        inv = capped_surface(lib, M, c.iso, CCap((C.c_uint * 3)(0, 0, 0), (C.c_uint * 3)(0, 0, 0), 1), info)
+        info = SurfaceCapInfo()
+        inv = capped_surface(lib, M, c.iso, SurfaceCap((C.c_uint * 3)(0, 0, 0), (C.c_uint * 3)(0, 0, 0), 1), info)
         assert np.array_equal(bits(inv.V), bits(Vi.cpu().numpy())) and np.array_equal(inv.T, Ti.cpu().numpy().view(np.uint32)) and np.array_equal(bits(inv.N), bits(Ni.cpu().numpy()))
         assert info.solid_above == 0 and info.closed == iinfo["closed"]
         # a refused box gives NULL and leaves the object alone
         before = (M.contents.iso, M.contents.nT, M.contents.memoryfault)
-        bad = CCap((C.c_uint * 3)(0, 0, 0), (C.c_uint * 3)(c.hi[0] + 1, c.hi[1], c.hi[2]), 0)
+        bad = SurfaceCap((C.c_uint * 3)(0, 0, 0), (C.c_uint * 3)(c.hi[0] + 1, c.hi[1], c.hi[2]), 0)
         assert capped_surface(lib, M, c.iso + 1.0, bad, None) is None and (M.contents.iso, M.contents.nT, M.contents.memoryfault) == before
     finally:
         L.free_MC33(M)
@@ -312,7 +305,7 @@ def test_c_api_nneg_flavour_caps_below():
         s = lib.copy_surface(S)
         L.free_surface_memory(S)
         want = co.cap(s.V, s.N, s.T, c.data, c.iso, c.r0, c.d, c.lo, c.hi, normal_neg=True)
-        info = CCapInfo()
+        info = SurfaceCapInfo()
         got = capped_surface(lib, M, c.iso, None, info)
         assert (info.solid_above, info.closed, got.nV, got.nT) == (0, 1, want.nV_out, want.nT_out)
         assert np.array_equal(bits(got.V), bits(want.V)) and np.array_equal(got.T, want.T) and np.array_equal(bits(got.N), bits(want.N))

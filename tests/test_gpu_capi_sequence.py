@@ -9,15 +9,11 @@ import numpy as np
 import pytest
 
 import fixtures as fx
-import test_gpu_clip as clip
-import test_gpu_filter as filt
-import test_gpu_measure as meas
-import test_gpu_simplify as simp
-import test_gpu_smooth as smooth
-from mc33_capi import SURFACE
-from test_filter_cpu import CFilter
-from test_gpu_property import c_palette, palette
-from test_smooth_cpu import CSmoothing
+from clip_cases import cbox, cclip
+from mc33_c_library_amd.api import ComponentFilter, SurfaceSmoothing
+from mc33_capi import SURFACE, CMeasure
+from mesh_harness import c_palette, capi, palette
+from simplify_cases import csimp
 
 pytestmark = pytest.mark.gpu
 
@@ -30,15 +26,11 @@ def rows(s):
 
 
 class Calls:
-    """the f32 product library with the prototypes of every part (each part's capi() opens the same library)"""
+    """the f32 product library, every prototype declared (tests/mc33_capi.py)"""
 
     def __init__(self):
-        self.lib = meas.capi()
-        self.L = self.lib.lib
-        self.filt, self.clip, self.simp, self.smooth = filt.capi().lib, clip.capi().lib, simp.capi().lib, smooth.capi().lib
-        M = C.POINTER(self.lib.MC33)
-        self.L.calculate_isosurfaces.restype = C.c_uint
-        self.L.calculate_isosurfaces.argtypes = [M, C.POINTER(C.c_float), C.c_uint, C.POINTER(C.POINTER(SURFACE))]
+        self.lib = capi()
+        self.L = self.filt = self.clip = self.simp = self.smooth = self.lib.lib
 
     def surface(self, M, iso, S):
         """a derived surface copied and freed, after the checks of clipped_surface() in tests/test_gpu_clip.py"""
@@ -53,7 +45,7 @@ class Calls:
             self.L.free_surface_memory(S)
 
     def filtered(self, M, iso):
-        f, k, dr = CFilter(largest=1), C.c_uint(77), C.c_uint(77)
+        f, k, dr = ComponentFilter(largest=1), C.c_uint(77), C.c_uint(77)
         S = self.filt.MC33_calculate_filtered_isosurface(M, C.c_float(iso), C.byref(f), C.byref(k), C.byref(dr))
         return self.surface(M, iso, S) + (k.value, dr.value)
 
@@ -61,15 +53,15 @@ class Calls:
         return self.surface(M, iso, self.clip.MC33_calculate_clipped_isosurface(M, C.c_float(iso), C.byref(cl)))
 
     def simplified(self, M, iso):
-        sp = simp.csimp((2.0, 2.0, 2.0), 0, 1)
+        sp = csimp((2.0, 2.0, 2.0), 0, 1)
         return self.surface(M, iso, self.simp.MC33_calculate_simplified_isosurface(M, C.c_float(iso), C.byref(sp)))
 
     def smoothed(self, M, iso):
-        sm = CSmoothing(3, 0.5, -0.53, 1)
+        sm = SurfaceSmoothing(3, 0.5, -0.53, 1)
         return self.surface(M, iso, self.smooth.MC33_calculate_smoothed_isosurface(M, C.c_float(iso), C.byref(sm)))
 
     def measured(self, M, iso):
-        m = meas.CMeasure()
+        m = CMeasure()
         assert self.L.MC33_measure_isosurface(M, C.c_float(iso), C.byref(m)) == 0
         assert M.contents.iso == np.float32(iso) and M.contents.memoryfault == 0
         return (bytes(m),)
@@ -91,8 +83,8 @@ def test_one_object_through_every_derived_call():
     data, r0, d = fx.cos_field(64)  # the "sheet" of tests/measure_oracle.py: 15072 vertices at 0, far fewer at 2.5
     G, keep = lib.make_grid(data, r0, d)
     Pg, keep2 = lib.make_grid(fx.noise_f32(0, 79, shape=data.shape) * np.float32(10.0), r0, d)
-    box, _ = clip.cbox(lib, (-2.0, -2.0, -2.0), (1.6, 1.6, 1.6))
-    one = clip.cclip([(1.0, 0.5, 0.25, 0.125)])
+    box, _ = cbox(lib, (-2.0, -2.0, -2.0), (1.6, 1.6, 1.6))
+    one = cclip([(1.0, 0.5, 0.25, 0.125)])
 
     def colour_map(M):
         assert c.filt.MC33_set_color_map(M, c_palette(PALETTE), len(PALETTE), MAP_LO, MAP_HI) == 0

@@ -16,59 +16,14 @@ import fixtures as fx
 import measure_oracle as mo
 import mesh_pieces as mp
 import property_oracle as po
-from mc33_capi import MC33Lib, product_path, ref_path
-from mesh_harness import SPARE, CanariedCall, bits, ctx, device_grid, once_per_key, to_device, words  # noqa: F401 (ctx: the module's fixture)
-from test_clip_cpu import MODES, PLANES, TABLE, CClip, attributes, clipped, plane_of
-from test_simplify_cpu import mesh
+from clip_cases import MODES, PLANES, TABLE, attributes, cbox, cclip, clipped, plane_of
+from mc33_capi import MC33Lib, ref_path
+from mesh_checks import reference_mesh as mesh
+from mesh_harness import SPARE, ClipCall as Call, bits, capi, c_palette, ctx, device_grid, once_per_key, palette, to_device, words  # noqa: F401 (ctx: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
 COUNTS = co.Clipped.COUNTS
-
-
-class Call(CanariedCall):
-    """one mc33hip_clip_surface call; the default capacities are the ones that are always enough: nV + 2 nT rows, 2 nT triangles"""
-
-    def __init__(self, g, V, N, T, plane, attrs=(), modes=(), capV=None, capT=None, with_map=True, with_normals=True, change=None):
-        import torch
-        from mc33_c_library_amd.api import Clipping
-        super().__init__(g)
-        self.nV, self.nT = V.shape[0], T.shape[0]
-        self.capV = self.nV + 2 * self.nT if capV is None else capV
-        self.capT = 2 * self.nT if capT is None else capT
-        with_normals = with_normals and N is not None
-        self.oV, self.oT = self.room(self.capV, 3, V.dtype), self.room(self.capT, 3, torch.int32)
-        self.oN = self.room(self.capV, 3, torch.float32) if with_normals else None
-        self.oA = [self.room(self.capV, 0, torch.int32) for _ in attrs]
-        self.oMap = self.room(self.nV, 0, torch.int32) if with_map else None
-        a = Clipping()
-        a.V, a.N, a.T, a.nV, a.nT = V.data_ptr(), (N.data_ptr() if N is not None else None), T.data_ptr(), self.nV, self.nT
-        for k, x in enumerate(attrs):
-            a.attr[k], a.oAttr[k] = x.data_ptr(), self.oA[k].data_ptr()
-            a.attr_mode[k] = int(modes[k]) if k < len(modes) else co.COPY
-        a.n_attr = len(attrs)
-        a.plane = (C.c_double * 4)(*plane)
-        a.oV, a.oT, a.capV, a.capT = self.oV.data_ptr(), self.oT.data_ptr(), self.capV, self.capT
-        a.oN = self.oN.data_ptr() if with_normals else None
-        a.oMap = self.oMap.data_ptr() if with_map else None
-        self.keep = (V, N, T, attrs)
-        self.call(g.lib.mc33hip_clip_surface, a, change)
-        self.counts = tuple(int(getattr(a, n)) for n in COUNTS)
-
-    def check(self, want):
-        """bit for bit against the oracle"""
-        assert self.counts == want.counts(), (self.counts, want.counts())
-        nV2, nT2 = want.nV_out, want.nT_out
-        self.equal_bits("oV", self.oV[:nV2], want.V)
-        self.equal_bits("oT", self.oT[:nT2], want.T)
-        if self.oN is not None:
-            self.equal_bits("oN", self.oN[:nV2], want.N)
-        assert len(self.oA) == len(want.attrs)
-        for k, x in enumerate(self.oA):
-            self.equal_bits("attribute %d" % k, x[:nV2], want.attrs[k])
-        if self.oMap is not None:
-            self.equal_bits("oMap", self.oMap[:self.nV], want.vmap)
-        self.spare_intact()
 
 
 def check_topology(g, call, manifold=False):
@@ -356,36 +311,6 @@ def test_python_methods(reflibs):
 
 # ---- the C API -----------------------------------------------------------------------------------------------------------------------
 
-def capi(dtype="f32", nneg=False):
-    lib = MC33Lib(product_path(dtype, nneg=nneg), dtype)
-    L = lib.lib
-    M = C.POINTER(lib.MC33)
-    L.MC33_calculate_clipped_isosurface.restype = C.POINTER(lib.SURFACE)
-    L.MC33_calculate_clipped_isosurface.argtypes = [M, lib.real, C.POINTER(CClip)]
-    L.MC33_clip_box.restype = C.c_int
-    L.MC33_clip_box.argtypes = [C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3), C.POINTER(CClip)]
-    L.MC33_set_property_grid.restype = C.c_int
-    L.MC33_set_property_grid.argtypes = [M, C.POINTER(lib.GRD)]
-    L.MC33_set_color_map.restype = C.c_int
-    L.MC33_set_color_map.argtypes = [M, C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
-    return lib
-
-
-def cclip(planes):
-    cl = CClip(len(planes))
-    for k, pl in enumerate(planes[:6]):
-        for j in range(4):
-            cl.plane[k][j] = pl[j]
-    return cl
-
-
-def cbox(lib, lo, hi):
-    three = C.c_double * 3
-    cl = CClip()
-    assert lib.lib.MC33_clip_box(C.byref(three(*lo)), C.byref(three(*hi)), C.byref(cl)) == 0
-    return cl, [tuple(cl.plane[k][j] for j in range(4)) for k in range(6)]
-
-
 def clipped_surface(lib, M, iso, cl):
     S = lib.lib.MC33_calculate_clipped_isosurface(M, lib.real(iso), C.byref(cl) if cl is not None else None)
     if not S:
@@ -430,7 +355,6 @@ def test_c_api(reflibs, nneg):
         got = clipped_surface(lib, M, iso, cclip([one]))
         assert np.array_equal(bits(got.V), bits(V1)) and np.array_equal(bits(got.N), bits(N1)) and np.array_equal(got.T, T1)
         # colours: those of the FINAL vertices, the new ones included
-        from test_gpu_property import c_palette, palette
         pal, plo, phi = palette(7), -2.5, 3.25
         assert L.MC33_set_property_grid(M, Pg) == 0 and L.MC33_set_color_map(M, c_palette(pal), len(pal), plo, phi) == 0
         painted = clipped_surface(lib, M, iso, box)

@@ -13,22 +13,13 @@ import curvature_oracle as co
 import fixtures as fx
 import layouts
 import property_oracle as po
-from mc33_capi import MC33Lib, product_path
-from mesh_harness import CanariedCall, bits, device_grid, to_device
+from mc33_c_library_amd.api import IsosurfaceCurvature
+from mesh_harness import CanariedCall, bits, c_palette, capi, device_grid, palette, to_device
 
 pytestmark = pytest.mark.gpu
 
 MEMBERS = ("oMean", "oGauss", "oK1", "oK2")
 R0, D = cc.AWKWARD_R0, cc.AWKWARD_D
-
-
-def palette(n):
-    """n distinct 0xAABBGGRR words, some with the top bit set (the property tests')"""
-    return [int((0xff000000 if k % 2 else 0x7f000000) | ((k * 2654435761) & 0xffffff)) for k in range(n)]
-
-
-def c_palette(words):
-    return (C.c_int * len(words))(*[int(x) for x in np.array([w & 0xFFFFFFFF for w in words], np.uint32).view(np.int32)])
 
 
 def one_nan(a):
@@ -244,23 +235,6 @@ def test_color_values_of_the_sampled_property_equal_color_vertices(n):
 
 # ---- the C API -----------------------------------------------------------------------------------------------------------
 
-class CCurvature(C.Structure):
-    _fields_ = [("nV", C.c_uint), ("nT", C.c_uint), ("lo", C.c_double * 4), ("hi", C.c_double * 4), ("finite", C.c_ulonglong), ("undefined", C.c_ulonglong),
-                ("total_mean", C.c_double), ("total_gauss", C.c_double)]
-
-
-def capi(dtype, nneg=False):
-    lib = MC33Lib(product_path(dtype, nneg=nneg), dtype)
-    L = lib.lib
-    L.MC33_set_color_map.restype = C.c_int
-    L.MC33_set_color_map.argtypes = [C.POINTER(lib.MC33), C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
-    L.MC33_set_color_source.restype = C.c_int
-    L.MC33_set_color_source.argtypes = [C.POINTER(lib.MC33), C.c_int]
-    L.MC33_isosurface_curvature.restype = C.c_int
-    L.MC33_isosurface_curvature.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CCurvature)]
-    return lib
-
-
 def one_surface(lib, M, iso):
     S = lib.lib.calculate_isosurface(M, lib.real(iso))
     assert S, "calculate_isosurface returned NULL"
@@ -309,7 +283,7 @@ def test_c_api_colours_and_struct(dtype, nneg):
         assert L.MC33_set_color_source(M, 0) == 0
         assert np.all(one_surface(lib, M, iso).color == po.DEFAULT_COLOR)   # back at the property: what it was before
         # the struct
-        out = CCurvature()
+        out = IsosurfaceCurvature()
         assert L.MC33_isosurface_curvature(M, lib.real(iso), C.byref(out)) == 0 and L.MC33_isosurface_curvature(M, lib.real(iso), None) == -1
         assert (out.nV, out.nT) == (plain.nV, plain.nT)
         assert (tuple(out.lo), tuple(out.hi), out.finite, out.undefined) == (summ.lo, summ.hi, summ.finite, summ.undefined)
@@ -333,7 +307,7 @@ def test_c_api_colours_and_struct(dtype, nneg):
             M2 = other.lib.create_MC33(G)
             assert M2
             try:
-                out2 = CCurvature()
+                out2 = IsosurfaceCurvature()
                 assert other.lib.MC33_isosurface_curvature(M2, other.real(iso), C.byref(out2)) == 0
             finally:
                 other.lib.free_MC33(M2)
@@ -368,7 +342,7 @@ def test_c_api_totals_are_nan_when_a_vertex_is_undefined():
         s = one_surface(lib, M, iso)
         summ = co.summary(co.curvature(s.V, R0, D, data))
         assert summ.undefined > 0 and summ.finite > 1000
-        out = CCurvature()
+        out = IsosurfaceCurvature()
         assert L.MC33_isosurface_curvature(M, lib.real(iso), C.byref(out)) == 0
         assert (out.nV, out.finite, out.undefined) == (s.nV, summ.finite, summ.undefined) and (tuple(out.lo), tuple(out.hi)) == (summ.lo, summ.hi)
         assert np.isnan(out.total_mean) and np.isnan(out.total_gauss)
@@ -382,7 +356,7 @@ def test_c_api_refusals(monkeypatch):
     lib = capi("f32")
     L = lib.lib
     data, iso = c_field("f32")
-    out = CCurvature(7, 8)
+    out = IsosurfaceCurvature(7, 8)
     # an inclined grid
     G, keep = lib.make_grid(data, None, (0.1, 0.1, 0.1), inclined=fx.cell_matrices(80.0, 75.0, 100.0))
     M = L.create_MC33(G)

@@ -20,10 +20,11 @@ import fixtures as fx
 import measure_oracle as mo
 import mesh_pieces as mp
 import simplify_oracle as sp
-from mc33_capi import MC33Lib, product_path, ref_path
-from mesh_harness import SPARE, CanariedCall, bits, device_grid, once_per_key, tiny_grid, to_device
-from test_distance_cpu import CDistance
-from test_simplify_cpu import CELLS, CSimplification, mesh, simplified
+from mc33_c_library_amd.api import SurfaceDistance, SurfaceSimplification
+from mc33_capi import MC33Lib, ref_path
+from mesh_checks import reference_mesh as mesh
+from mesh_harness import SPARE, CanariedCall, bits, capi, device_grid, once_per_key, tiny_grid, to_device
+from simplify_cases import CELLS, simplified
 
 pytestmark = pytest.mark.gpu
 
@@ -394,17 +395,6 @@ def test_python_methods(reflibs):
     g.close()
 
 
-def capi(dtype="f32", nneg=False):
-    lib = MC33Lib(product_path(dtype, nneg=nneg), dtype)
-    L = lib.lib
-    M = C.POINTER(lib.MC33)
-    L.MC33_isosurface_distance.restype = C.c_int
-    L.MC33_isosurface_distance.argtypes = [M, lib.real, lib.real, C.POINTER(CDistance)]
-    L.MC33_simplification_error.restype = C.c_int
-    L.MC33_simplification_error.argtypes = [M, lib.real, C.POINTER(CSimplification), C.POINTER(CDistance)]
-    return lib
-
-
 def c_matches(out, want):
     """mean and rms within the bound of the sums, the rest exact"""
     assert (out.points, out.unmatched, out.argmax) == (want.matched_points, want.unmatched_points, want.argmax)
@@ -436,20 +426,20 @@ def test_c_api(reflibs, nneg, monkeypatch):
     M = L.create_MC33(G)
     assert M
     try:
-        out = (CDistance * 2)()
+        out = (SurfaceDistance * 2)()
         assert L.MC33_isosurface_distance(M, lib.real(iso), lib.real(iso + 0.25), out) == 0
         c_matches(out[0], do.distance(s0.V, s1.V, s1.T))
         assert out[0].min > 0.0 and M.contents.memoryfault == 0
         c = tuple(2.0 * x for x in d)
         simp = sp.simplify(s0.V, s0.T, c, r0, sp.MEAN, True)
-        sm = CSimplification((C.c_double * 3)(2, 2, 2), sp.MEAN, 1)
+        sm = SurfaceSimplification((C.c_double * 3)(2, 2, 2), sp.MEAN, 1)
         assert L.MC33_simplification_error(M, lib.real(iso), C.byref(sm), out) == 0
         c_matches(out[0], do.distance(simp.V, s0.V, s0.T))
         c_matches(out[1], do.distance(s0.V, simp.V, simp.T))
         # an empty surface: -2 and zeros
         assert L.MC33_isosurface_distance(M, lib.real(iso), lib.real(1e9), out) == -2 and (out[0].points, out[0].max) == (0, 0.0)
         assert L.MC33_isosurface_distance(M, lib.real(1e9), lib.real(iso), out) == -2
-        sm_all = CSimplification((C.c_double * 3)(1000, 1000, 1000), sp.MEAN, 1)
+        sm_all = SurfaceSimplification((C.c_double * 3)(1000, 1000, 1000), sp.MEAN, 1)
         assert L.MC33_simplification_error(M, lib.real(iso), C.byref(sm_all), out) == -2 and (out[1].points, out[1].rms) == (0, 0.0)
         # refused calls leave M as it was
         S = L.calculate_isosurface(M, lib.real(iso))
@@ -458,7 +448,7 @@ def test_c_api(reflibs, nneg, monkeypatch):
         nan = float("nan")
         assert L.MC33_isosurface_distance(M, lib.real(iso + 1), lib.real(iso), None) == -1
         assert L.MC33_simplification_error(M, lib.real(iso + 1), None, out) == -1 and L.MC33_simplification_error(M, lib.real(iso + 1), C.byref(sm), None) == -1
-        for bad in (CSimplification((C.c_double * 3)(0, 2, 2), 0, 1), CSimplification((C.c_double * 3)(nan, 2, 2), 0, 1), CSimplification((C.c_double * 3)(2, 2, 2), 2, 1)):
+        for bad in (SurfaceSimplification((C.c_double * 3)(0, 2, 2), 0, 1), SurfaceSimplification((C.c_double * 3)(nan, 2, 2), 0, 1), SurfaceSimplification((C.c_double * 3)(2, 2, 2), 2, 1)):
             assert L.MC33_simplification_error(M, lib.real(iso + 1), C.byref(bad), out) == -1
         assert state(M) == before
         L.free_surface_memory(S)
@@ -481,7 +471,7 @@ def test_c_api_accepts_an_inclined_grid(monkeypatch):
     M = L.create_MC33(G)
     assert M
     try:
-        out = (CDistance * 2)()
+        out = (SurfaceDistance * 2)()
         assert L.MC33_isosurface_distance(M, lib.real(0.0), lib.real(0.2), out) == 0
         S = L.calculate_isosurface(M, lib.real(0.0))
         a = lib.copy_surface(S)
@@ -491,7 +481,7 @@ def test_c_api_accepts_an_inclined_grid(monkeypatch):
         L.free_surface_memory(S)
         c_matches(out[0], do.distance(a.V, b.V, b.T))
         before = state(M)
-        sm = CSimplification((C.c_double * 3)(2, 2, 2), 0, 1)
+        sm = SurfaceSimplification((C.c_double * 3)(2, 2, 2), 0, 1)
         assert L.MC33_simplification_error(M, lib.real(0.1), C.byref(sm), out) == -1 and state(M) == before
     finally:
         L.free_MC33(M)
@@ -510,8 +500,8 @@ def test_c_api_refuses_several_slabs(monkeypatch):
     assert M
     try:
         before = state(M)
-        out = (CDistance * 2)()
-        sm = CSimplification((C.c_double * 3)(2, 2, 2), 0, 1)
+        out = (SurfaceDistance * 2)()
+        sm = SurfaceSimplification((C.c_double * 3)(2, 2, 2), 0, 1)
         assert L.MC33_isosurface_distance(M, lib.real(0.0), lib.real(0.2), out) == -1
         assert L.MC33_simplification_error(M, lib.real(0.0), C.byref(sm), out) == -1
         assert state(M) == before

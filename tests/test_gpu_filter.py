@@ -15,64 +15,16 @@ import filter_oracle as fo
 import fixtures as fx
 import measure_oracle as mo
 import property_oracle as po
-from mc33_capi import MC33Lib, product_path, ref_path
-from mesh_harness import CanariedCall, bits, ctx, device_grid, to_device  # noqa: F401 (ctx: the module's fixture)
-from test_filter_cpu import CFilter, ROWS, SIZED, mesh
+from filter_cases import ROWS, SIZED, mesh
+from mc33_c_library_amd.api import ComponentFilter
+from mc33_capi import MC33Lib, ref_path
+from mesh_harness import CompactCall as Call, bits, capi, check_python, c_palette, ctx, device_grid, palette, to_device  # noqa: F401 (ctx: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
 # the rows of the issue's table that a filter struct expresses (the others name their roots)
 CRITERIA = {"noise-min16": {"min_triangles": 16}, "noise-closed": {"closed_only": True}, "quant-min8": {"min_triangles": 8}, "quant-all": {},
             "quant-closed": {"closed_only": True}}
-
-
-class Call(CanariedCall):
-    """one mc33hip_compact_components call"""
-
-    def __init__(self, g, V, N, T, labels, roots, invert=False, attrs=(), capV=None, capT=None, with_map=True):
-        import torch
-        from mc33_c_library_amd.api import Compaction
-        super().__init__(g)
-        self.nV, self.nT = V.shape[0], T.shape[0]
-        self.capV = self.nV if capV is None else capV
-        self.capT = self.nT if capT is None else capT
-        self.oV, self.oN, self.oT = self.room(self.capV, 3, V.dtype), self.room(self.capV, 3, torch.float32), self.room(self.capT, 3, torch.int32)
-        self.oA = [self.room(self.capV, 0, torch.int32) for _ in attrs]
-        self.oMap = self.room(self.nV, 0, torch.int32) if with_map else None
-        roots = np.ascontiguousarray(np.asarray(roots).reshape(-1), dtype=np.uint32)
-        a = Compaction()
-        a.V, a.N, a.T, a.label, a.nV, a.nT = V.data_ptr(), N.data_ptr(), T.data_ptr(), labels.data_ptr(), self.nV, self.nT
-        for k, x in enumerate(attrs):
-            a.attr[k], a.oAttr[k] = x.data_ptr(), self.oA[k].data_ptr()
-        a.n_attr, a.invert = len(attrs), int(bool(invert))
-        a.roots, a.n_roots = (roots.ctypes.data if roots.size else None), roots.size
-        a.oV, a.oN, a.oT, a.capV, a.capT = self.oV.data_ptr(), self.oN.data_ptr(), self.oT.data_ptr(), self.capV, self.capT
-        a.oMap = self.oMap.data_ptr() if with_map else None
-        self.keep = (V, N, T, labels, attrs, roots)
-        self.call(g.lib.mc33hip_compact_components, a)
-        self.counts = (int(a.nV_out), int(a.nT_out), int(a.components_kept))
-
-    def check(self, want):
-        """bit for bit against the oracle"""
-        assert self.counts == (want.nV_out, want.nT_out, want.components_kept), (self.counts, (want.nV_out, want.nT_out, want.components_kept))
-        nV2, nT2 = want.nV_out, want.nT_out
-        self.equal_bits("oV", self.oV[:nV2], want.V)
-        self.equal_bits("oN", self.oN[:nV2], want.N)
-        self.equal_bits("oT", self.oT[:nT2], want.T)
-        for k, x in enumerate(self.oA):
-            self.equal_bits("attribute %d" % k, x[:nV2], want.attrs[k])
-        if self.oMap is not None:
-            self.equal_bits("oMap", self.oMap[:self.nV], want.vmap)
-        self.spare_intact()
-
-
-def check_python(got, want):
-    V2, N2, T2, attrs2, vmap, kept = got
-    assert (V2.shape[0], T2.shape[0], kept) == (want.nV_out, want.nT_out, want.components_kept)
-    assert np.array_equal(bits(V2.cpu().numpy()), bits(want.V)) and np.array_equal(bits(N2.cpu().numpy()), bits(want.N))
-    assert np.array_equal(T2.cpu().numpy().view(np.uint32), want.T) and np.array_equal(vmap.cpu().numpy().view(np.uint32), want.vmap)
-    for x, w in zip(attrs2, want.attrs):
-        assert np.array_equal(bits(x.cpu().numpy()), bits(w))
 
 
 # ---- the eight rows of the table that give sizes, float, two attributes ----------------------------------------------------------
@@ -337,19 +289,6 @@ def test_invalid_arguments(reflibs):
 
 # ---- the C API -------------------------------------------------------------------------------------------------------------------
 
-def capi(dtype="f32", nneg=False):
-    lib = MC33Lib(product_path(dtype, nneg=nneg), dtype)
-    L = lib.lib
-    M = C.POINTER(lib.MC33)
-    L.MC33_calculate_filtered_isosurface.restype = C.POINTER(lib.SURFACE)
-    L.MC33_calculate_filtered_isosurface.argtypes = [M, lib.real, C.POINTER(CFilter), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
-    L.MC33_set_property_grid.restype = C.c_int
-    L.MC33_set_property_grid.argtypes = [M, C.POINTER(lib.GRD)]
-    L.MC33_set_color_map.restype = C.c_int
-    L.MC33_set_color_map.argtypes = [M, C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
-    return lib
-
-
 def filtered(lib, M, iso, f):
     k, dr = C.c_uint(77), C.c_uint(77)
     S = lib.lib.MC33_calculate_filtered_isosurface(M, lib.real(iso), C.byref(f) if f is not None else None, C.byref(k), C.byref(dr))
@@ -382,7 +321,7 @@ def test_c_api(reflibs, row):
     M = L.create_MC33(G)
     assert M
     try:
-        f = CFilter(**{k: int(v) for k, v in CRITERIA[row].items()})
+        f = ComponentFilter(**{k: int(v) for k, v in CRITERIA[row].items()})
         got, k, dr = filtered(lib, M, iso, f)
         assert got is not None and (k, dr) == (kept, tab.shape[0] - kept)
         check_surface(got, want)
@@ -392,7 +331,6 @@ def test_c_api(reflibs, row):
         again, _, _ = filtered(lib, M, iso, f)
         check_surface(again, want)
         # colours: those of the unfiltered surface at the kept vertices
-        from test_gpu_property import c_palette, palette
         pal, lo, hi = palette(7), -2.5, 3.25
         assert L.MC33_set_property_grid(M, Pg) == 0 and L.MC33_set_color_map(M, c_palette(pal), len(pal), lo, hi) == 0
         S = L.calculate_isosurface(M, lib.real(iso))
@@ -416,7 +354,7 @@ def test_c_api(reflibs, row):
         L.free_surface_memory(S)
         assert np.array_equal(bits(mine.V), bits(s.V)) and np.array_equal(mine.T, s.T) and np.array_equal(bits(mine.N), bits(s.N))
         # keep nothing: an empty surface, not a failure
-        nothing, k, dr = filtered(lib, M, iso, CFilter(min_triangles=1 << 30))
+        nothing, k, dr = filtered(lib, M, iso, ComponentFilter(min_triangles=1 << 30))
         assert nothing is not None and (nothing.nV, nothing.nT, k, dr) == (0, 0, 0, tab.shape[0])
     finally:
         L.free_MC33(M)
@@ -440,7 +378,7 @@ def test_c_api_nneg_flavour():
     M = L.create_MC33(G)
     assert M
     try:
-        got, k, dr = filtered(lib, M, iso, CFilter(min_triangles=16))
+        got, k, dr = filtered(lib, M, iso, ComponentFilter(min_triangles=16))
         assert (k, dr) == (8, tab.shape[0] - 8)
         check_surface(got, want)
     finally:

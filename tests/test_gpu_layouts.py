@@ -259,7 +259,7 @@ def _property_field(dtype, shape):
 def test_property_grid_with_a_layout_of_its_own(reflibs, dtype, grid_layout, prop_layout):
     import measure_oracle as mo
     import property_oracle as po
-    from test_gpu_measure import check_measures
+    from measure_cases import check_measures
     iso = {"f32": 1.0, "f64": 1.0, "u8": 168.5}[dtype]
     r0, d = (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)
     data = dense(dtype, "smooth258")

@@ -6,7 +6,6 @@ expected values come from tests/measure_oracle.py, the definition in numpy float
 must satisfy |got - fsum(x)| <= (n + 8) * 2^-53 * fsum(|x_i|) - a bound that holds for every order of the additions as long as
 they are made in double - integers, labels and the bounding box are compared exactly."""
 import ctypes as C
-import struct
 
 import numpy as np
 import pytest
@@ -14,62 +13,16 @@ import pytest
 from capi_slab_refusals import refusal
 import fixtures as fx
 import measure_oracle as mo
-import mesh_checks
 import property_oracle as po
-from mc33_capi import MC33Lib, product_path, ref_path
-from mesh_harness import device_grid, to_device
+from mc33_c_library_amd.api import Component
+from mc33_capi import CMeasure, MC33Lib, ref_path
+from measure_cases import all_bits, check_measures, check_sum, check_table
+from mesh_checks import reference_mesh
+from mesh_harness import capi, device_grid, to_device
 
 pytestmark = pytest.mark.gpu
 
 AWKWARD_R0, AWKWARD_D = mo.AWKWARD_R0, mo.AWKWARD_D
-
-
-def reference_mesh(reflibs, name):
-    """(data, r0, d, iso, reference surface) of a fixture row; the row's figures are asserted on the reference's mesh first"""
-    data, r0, d, iso, s = mesh_checks.reference_mesh(reflibs, name)
-    assert mo.open_edges(s.T) == mo.FIXTURES[name][2][4], "fixture %s drifted: %d open edges" % (name, mo.open_edges(s.T))
-    return data, r0, d, iso, s
-
-
-def check_sum(what, got, want, bound):
-    err = abs(got - want)
-    print("%-22s got %.17g  oracle %.17g  |diff| %.3g  bound %.3g" % (what, got, want, err, bound))
-    assert err <= bound, "%s: |%.17g - %.17g| = %.3g exceeds the bound %.3g" % (what, got, want, err, bound)
-
-
-def check_measures(label, got, want):
-    assert (got.nV, got.nT) == (want.nV, want.nT)
-    check_sum(label + " area", got.area, want.area, want.area_bound)
-    check_sum(label + " volume", got.volume, want.volume, want.volume_bound)
-    for a in range(3):
-        check_sum(label + " moment[%d]" % a, got.moment[a], want.moment[a], want.moment_bound[a])
-    assert tuple(got.origin) == tuple(want.origin.tolist())
-    assert tuple(got.bbox_min) == tuple(want.bbox_min.tolist()) and tuple(got.bbox_max) == tuple(want.bbox_max.tolist()), (got.bbox_min, got.bbox_max, want.bbox_min, want.bbox_max)
-    assert got.has_property == want.has_property
-    if want.has_property:
-        check_sum(label + " property", got.property_integral, want.property_integral, want.property_bound)
-    else:
-        assert got.property_integral == 0.0
-
-
-def all_bits(m):
-    return struct.pack("<15d", m.area, m.volume, *m.moment, *m.origin, *m.bbox_min, *m.bbox_max, m.property_integral)
-
-
-def check_table(label, got, want, ab, wb, totals=None):
-    assert got.shape[0] == want.shape[0], "%s: %d components, oracle %d" % (label, got.shape[0], want.shape[0])
-    for col in ("root", "nV", "nT"):
-        assert np.array_equal(got[col], want[col]), "%s: column %s differs in %d rows" % (label, col, np.count_nonzero(got[col] != want[col]))
-    assert np.all(np.diff(got["root"].astype(np.int64)) > 0)
-    ea, ew = np.abs(got["area"] - want["area"]), np.abs(got["volume"] - want["volume"])
-    def worst(e, b):  # (for the printout only; a row whose terms are all 0 has the bound 0)
-        return float(np.max(np.divide(e, b, out=np.where(e > 0, np.inf, 0.0), where=b > 0), initial=0.0))
-    print("%s: %d components; worst area diff / bound %.3g, volume %.3g" % (label, got.shape[0], worst(ea, ab), worst(ew, wb)))
-    assert np.all(ea <= ab) and np.all(ew <= wb)
-    if totals is not None:  # the columns add up to the surface's totals
-        check_sum(label + " sum of areas", mo.fsum(got["area"]), totals.area, totals.area_bound)
-        check_sum(label + " sum of volumes", mo.fsum(got["volume"]), totals.volume, totals.volume_bound)
-        assert int(got["nT"].sum()) == totals.nT
 
 
 # ---- 1 - 3: the five fixture rows, float ---------------------------------------------------------------------------------------
@@ -105,7 +58,7 @@ def test_label_components_f32(reflibs, name):
 
 @pytest.mark.parametrize("name", list(mo.FIXTURES))
 def test_measure_components_f32(reflibs, name):
-    from mc33_c_library_amd.api import Component, ECAPACITY
+    from mc33_c_library_amd.api import ECAPACITY
     data, r0, d, iso, s = reference_mesh(reflibs, name)
     totals = mo.measure(s.V, s.T, r0, d, data.shape)
     lab = mo.label_components(s.T, s.nV)[0]
@@ -253,35 +206,6 @@ def test_a_triangle_outside_v_is_counted_not_read(reflibs):
 
 # ---- 7: the C API -------------------------------------------------------------------------------------------------------------
 
-class CMeasure(C.Structure):
-    _fields_ = [("nV", C.c_uint), ("nT", C.c_uint), ("area", C.c_double), ("volume", C.c_double), ("moment", C.c_double * 3),
-                ("origin", C.c_double * 3), ("bbox_min", C.c_double * 3), ("bbox_max", C.c_double * 3), ("property_integral", C.c_double),
-                ("has_property", C.c_int)]
-
-
-class CComponent(C.Structure):
-    _fields_ = [("root", C.c_uint), ("nV", C.c_uint), ("nT", C.c_uint), ("area", C.c_double), ("volume", C.c_double)]
-
-
-def capi(dtype="f32", nneg=False):
-    lib = MC33Lib(product_path(dtype, nneg=nneg), dtype)
-    bind_measure_api(lib)
-    return lib
-
-
-def bind_measure_api(lib):
-    L = lib.lib
-    M = C.POINTER(lib.MC33)
-    L.MC33_measure_isosurface.restype = C.c_int
-    L.MC33_measure_isosurface.argtypes = [M, lib.real, C.POINTER(CMeasure)]
-    L.MC33_measure_isosurfaces.restype = C.c_uint
-    L.MC33_measure_isosurfaces.argtypes = [M, C.POINTER(lib.real), C.c_uint, C.POINTER(CMeasure)]
-    L.MC33_measure_components.restype = C.c_int
-    L.MC33_measure_components.argtypes = [M, lib.real, C.POINTER(CComponent), C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
-    L.MC33_set_property_grid.restype = C.c_int
-    L.MC33_set_property_grid.argtypes = [M, C.POINTER(lib.GRD)]
-
-
 class View:
     """a CMeasure with tuples where check_measures wants them"""
 
@@ -310,11 +234,11 @@ def test_c_api(reflibs, name):
         tab, ab, wb = mo.component_table(s.V, s.T, lab, want.origin)
         nc, nu = C.c_uint(), C.c_uint(99)
         assert L.MC33_measure_components(M, lib.real(iso), None, 0, C.byref(nc), C.byref(nu)) == -2 and (nc.value, nu.value) == (tab.shape[0], 0)
-        rows = (CComponent * tab.shape[0])()
+        rows = (Component * tab.shape[0])()
         if tab.shape[0] > 1:
             assert L.MC33_measure_components(M, lib.real(iso), rows, tab.shape[0] - 1, C.byref(nc), None) == -2 and nc.value == tab.shape[0]
         assert L.MC33_measure_components(M, lib.real(iso), rows, tab.shape[0], C.byref(nc), C.byref(nu)) == 0
-        got = np.frombuffer(rows, dtype=np.dtype(CComponent)).copy()
+        got = np.frombuffer(rows, dtype=np.dtype(Component)).copy()
         check_table(name + " (C API)", got, tab, ab, wb, want)
         # the object is still good for calculate_isosurface, and that surface is the reference's
         S = L.calculate_isosurface(M, lib.real(iso))

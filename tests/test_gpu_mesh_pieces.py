@@ -19,9 +19,10 @@ import fixtures as fx
 import measure_oracle as mo
 import mesh_pieces as mp
 import smooth_oracle as so
-import test_gpu_measure as tm
-import test_gpu_topology as tt
+import measure_cases as tm
+import topology_cases as tt
 import topology_oracle as to
+from mesh_harness import bits, check_python, device_grid, info_of, to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -47,7 +48,7 @@ def field(dtype="f32"):
 
 def new_grid(dtype="f32"):
     """a context for meshes that come from no grid"""
-    return tm.device_grid(*field(dtype))
+    return device_grid(*field(dtype))
 
 
 def mesh(key):
@@ -97,8 +98,8 @@ def want(key):
 
 def device_mesh(g, V, T):
     import torch
-    dV = tm.to_device(V.astype(np.float64 if g.dtype == "f64" else np.float32))  # (copies: the shared arrays are read-only)
-    dT = tm.to_device(T.copy()) if T.shape[0] else torch.zeros((0, 3), dtype=torch.int32, device="cuda")
+    dV = to_device(V.astype(np.float64 if g.dtype == "f64" else np.float32))  # (copies: the shared arrays are read-only)
+    dT = to_device(T.copy()) if T.shape[0] else torch.zeros((0, 3), dtype=torch.int32, device="cuda")
     return dV, dT
 
 
@@ -171,7 +172,7 @@ def check_refused(g, label, dV, dT, nV, nT, w):
     made: of them only the code and the count are checked."""
     import torch
     from mc33_c_library_amd.api import ERUNTIME, Measures, SurfaceMeasures, SurfaceTopology, Topology
-    given = tm.to_device(w.lab)
+    given = to_device(w.lab)
     refused(lambda: g.measure(dV, dT), w.invalid)
     refused(lambda: g.label_components(dT, nV), w.invalid)
     refused(lambda: g.measure_components(dV, dT, given), w.invalid)
@@ -312,7 +313,6 @@ def fresh(key):
 
 
 def compact_every_third(g):
-    from test_gpu_filter import check_python
     V, T, exp = mesh(("ladder", "permuted", "shuffle"))
     w = want(("ladder", "permuted", "shuffle"))
     N = np.random.default_rng(3).standard_normal(V.shape).astype(np.float32)
@@ -321,11 +321,10 @@ def compact_every_third(g):
     assert expected.components_kept == 40 and expected.left_out == 0
     dV, dT = device_mesh(g, V, T)
     labels = g.label_components(dT, V.shape[0])[0]
-    check_python(g.compact_components(dV, tm.to_device(N), dT, labels, roots), expected)
+    check_python(g.compact_components(dV, to_device(N), dT, labels, roots), expected)
 
 
 def smooth_soup(g):
-    from test_gpu_smooth import bits, info_of
     V, T, _ = mesh(("random", 4097))
     if "smooth" not in _want:
         P, A = so.smooth(V, T, 2, 0.5, -0.53, True)

@@ -13,11 +13,8 @@ import filter_oracle as fo
 import measure_oracle as mo
 import simplify_oracle as sp
 import smooth_oracle as so
-from test_clip_cpu import MODES
-from mesh_harness import bits, tiny_grid, to_device, words
-from test_gpu_clip import Call as Clip
-from test_gpu_filter import Call as Compact
-from test_gpu_simplify import Call as Simplify
+from clip_cases import MODES
+from mesh_harness import ClipCall as Clip, CompactCall as Compact, SimplifyCall as Simplify, bits, tiny_grid, to_device, words
 
 pytestmark = pytest.mark.gpu
 

@@ -327,8 +327,6 @@ def test_count_reused_for_the_same_isovalue(products, reflibs, devices, monkeypa
         monkeypatch.setenv("MC33_HIP_DEVICES", devices)
     lib, ref = products["f32"], reflibs["f32"]
     L = lib.lib
-    L.MC33_grid_changed.restype = None
-    L.MC33_grid_changed.argtypes = [C.POINTER(lib.MC33)]
     a = fx.noise_quant(40, 3).copy()
     G, keep = lib.make_grid(a)
     M = L.create_MC33(G)
@@ -528,8 +526,7 @@ def test_file_to_file_pipeline(products, reflibs, tmp_path):
     write the surface.  An inclined DMol .grd text grid through read_grd -> create_MC33 -> calculate_isosurface ->
     write_bin_s / write_ply_s; the files of the product and of the reference must be identical."""
     import ctypes as C
-    from test_grid_io import declare as declare_grid, write_grd_text
-    from test_surface_io import declare as declare_surf
+    from fixtures import write_grd_text
     import mc33_capi
     N = (30, 26, 22)
     data, _, _ = fx.cos_field(40)
@@ -538,8 +535,7 @@ def test_file_to_file_pipeline(products, reflibs, tmp_path):
     write_grd_text(path, N, (6.0, 5.2, 4.4), (80.0, 95.0, 70.0), (0, 0, 0), 3, vals.ravel())
     out = {}
     for tag, lib in (("p", products["f32"]), ("r", reflibs["f32"])):
-        L = declare_grid(lib)
-        declare_surf(lib)
+        L = lib.lib
         lib.set_triangular(True)  # what the examples do for .grd cells (upper triangular matrices)
         try:
             G = L.read_grd(path.encode())
@@ -680,8 +676,6 @@ def test_grid_changed_uploads_the_samples_again(reflibs, devices, monkeypatch):
     from mc33_capi import MC33Lib, product_path
     lib = MC33Lib(product_path("f32"), "f32")
     L = lib.lib
-    L.MC33_grid_changed.restype = None
-    L.MC33_grid_changed.argtypes = [C.POINTER(lib.MC33)]
     if devices:
         monkeypatch.setenv("MC33_HIP_DEVICES", devices)
     a = fx.cos_field(48)[0].copy()
@@ -749,8 +743,6 @@ def test_batched_isovalues_equal_single_calls(products, reflibs, devices, monkey
         monkeypatch.setenv("MC33_HIP_DEVICES", devices)
     lib = products["f32"]
     L = lib.lib
-    L.calculate_isosurfaces.restype = C.c_uint
-    L.calculate_isosurfaces.argtypes = [C.POINTER(lib.MC33), C.POINTER(C.c_float), C.c_uint, C.POINTER(C.POINTER(SURFACE))]
     data, r0, d = fx.cos_field(160)
     G, keep = lib.make_grid(data, r0, d)
     M = L.create_MC33(G)
@@ -851,8 +843,6 @@ def test_batched_isovalues_with_fresh_staging_sets(products, reflibs):
         data = rng.randint(0, 8, shape).astype(lib.np_dtype) if dtype == "u16" else rng.randint(-3, 4, shape).astype(lib.np_dtype)
         want = [ref.isosurface(data, iso) for iso in isos]
         L = lib.lib
-        L.calculate_isosurfaces.restype = C.c_uint
-        L.calculate_isosurfaces.argtypes = [C.POINTER(lib.MC33), C.POINTER(lib.real), C.c_uint, C.POINTER(C.POINTER(lib.SURFACE))]
         for rep in range(6):
             G, keep = lib.make_grid(data)
             M = L.create_MC33(G)
@@ -978,8 +968,6 @@ def test_config4_u16_full_size(products, reflibs):
     # --- the reference's C API -------------------------------------------------------------------------------
     lib, ref = products["u16"], reflibs["u16"]
     L, R = lib.lib, ref.lib
-    L.calculate_isosurfaces.restype = C.c_uint
-    L.calculate_isosurfaces.argtypes = [C.POINTER(lib.MC33), C.POINTER(C.c_float), C.c_uint, C.POINTER(C.POINTER(lib.SURFACE))]
     G, keep = lib.make_grid(data)
     M = L.create_MC33(G)
     assert M

@@ -10,22 +10,13 @@ import pytest
 
 import fixtures as fx
 import property_oracle as po
-from mc33_capi import MC33Lib, product_path
-from mesh_harness import bits, device_grid, to_device
+from mc33_capi import FN
+from mesh_harness import bits, c_palette, capi, device_grid, palette, to_device
 
 pytestmark = pytest.mark.gpu
 
 AWKWARD_R0, AWKWARD_D = (-1.3, 0.7, 2.9), (0.1, 0.07, 0.13)
 UNIT_R0, UNIT_D = (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)
-
-
-def palette(n):
-    """n distinct 0xAABBGGRR words, some with the top bit set"""
-    return [int((0xff000000 if k % 2 else 0x7f000000) | ((k * 2654435761) & 0xffffff)) for k in range(n)]
-
-
-def as_i32(words):
-    return np.array([w & 0xFFFFFFFF for w in words], np.uint32).view(np.int32)
 
 
 CASES = {
@@ -113,22 +104,6 @@ def test_other_sample_types(reflibs, dtype):
 
 
 # ---- the C API -----------------------------------------------------------------------------------------------------------
-
-def capi(dtype="f32", nneg=False):
-    lib = MC33Lib(product_path(dtype, nneg=nneg), dtype)
-    L = lib.lib
-    L.MC33_set_property_grid.restype = C.c_int
-    L.MC33_set_property_grid.argtypes = [C.POINTER(lib.MC33), C.POINTER(lib.GRD)]
-    L.MC33_set_color_map.restype = C.c_int
-    L.MC33_set_color_map.argtypes = [C.POINTER(lib.MC33), C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
-    L.calculate_isosurfaces.restype = C.c_uint
-    L.calculate_isosurfaces.argtypes = [C.POINTER(lib.MC33), C.POINTER(lib.real), C.c_uint, C.POINTER(C.POINTER(lib.SURFACE))]
-    return lib
-
-
-def c_palette(words):
-    return (C.c_int * len(words))(*[int(x) for x in as_i32(words)])
-
 
 def one_surface(lib, M, iso):
     S = lib.lib.calculate_isosurface(M, lib.real(iso))
@@ -354,10 +329,7 @@ def test_c_api_upload_paths(reflibs):
     # float, every row of the property grid a malloc block of its own
     lib = capi("f32")
     L = lib.lib
-    FN = C.CFUNCTYPE(C.c_double, C.c_double, C.c_double, C.c_double)
     fn = FN(lambda x, y, z: 3.0 * x - 2.0 * y + 5.0 * z + 7.0)
-    L.generate_grid_from_fn.restype = C.POINTER(lib.GRD)
-    L.generate_grid_from_fn.argtypes = [C.c_double] * 9 + [FN]
     data = fx.cos_field(n)[0]
     refV = reflibs["f32"].isosurface(data, 0.0, AWKWARD_R0, AWKWARD_D).V
     k, j, i = np.meshgrid(np.arange(n), np.arange(n), np.arange(n), indexing="ij")

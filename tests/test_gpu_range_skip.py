@@ -285,8 +285,6 @@ def test_c_api_in_place_edit_with_a_table_in_between(products, reflibs):
     from parity import assert_surface_parity
     lib, ref = products["f32"], reflibs["f32"]
     L = lib.lib
-    L.MC33_grid_changed.restype = None
-    L.MC33_grid_changed.argtypes = [C.POINTER(lib.MC33)]
     a = steep(A).copy()
     iso = STEEP_ISO[A]
     G, keep = lib.make_grid(a)

@@ -13,9 +13,8 @@ import pytest
 import fixtures as fx
 import render_cases as rc
 import render_oracle as ro
-from mc33_capi import MC33Lib, product_path
-from mesh_harness import CanariedCall, device_grid, tiny_grid, to_device
-from test_render_cpu import CImage, CView, declare
+from mc33_c_library_amd.api import Image, View
+from mesh_harness import CanariedCall, capi, device_grid, tiny_grid, to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -287,7 +286,6 @@ def test_refusals_leave_the_images_alone():
 # ---- Python and the C API --------------------------------------------------------------------------------------------------------
 
 def as_view(vw):
-    from mc33_c_library_amd import View
     v = View()
     v.m, v.light = (C.c_double * 16)(*vw.m), (C.c_double * 3)(*vw.light)
     v.width, v.height, v.cull, v.two_sided, v.ambient, v.diffuse, v.background = vw.width, vw.height, vw.cull, vw.two_sided, vw.ambient, vw.diffuse, vw.background
@@ -311,18 +309,8 @@ def test_python_methods():
         g.render(to_device(m.V), to_device(m.N), to_device(m.T), None, as_view(variant(c.view, cull=5)))
 
 
-def capi(dtype):
-    lib = MC33Lib(product_path(dtype), dtype)
-    L = declare(lib)
-    L.MC33_set_property_grid.restype = C.c_int
-    L.MC33_set_property_grid.argtypes = [C.POINTER(lib.MC33), C.POINTER(lib.GRD)]
-    L.MC33_set_color_map.restype = C.c_int
-    L.MC33_set_color_map.argtypes = [C.POINTER(lib.MC33), C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
-    return lib
-
-
 def c_view(vw):
-    v = CView()
+    v = View()
     v.m, v.light = (C.c_double * 16)(*vw.m), (C.c_double * 3)(*vw.light)
     v.width, v.height, v.cull, v.two_sided, v.ambient, v.diffuse, v.background = vw.width, vw.height, vw.cull, vw.two_sided, vw.ambient, vw.diffuse, vw.background
     return v
@@ -363,9 +351,9 @@ def test_c_api(dtype, monkeypatch, tmp_path):
         eye, target = (44.0, 36.0, 31.0), (11.3, 10.6, 9.4)
         views = [ro.view(rc.perspective(eye, target, (0, 0, 1), 30.0, 80, 56, 25.0, 75.0), 80, 56, light=(1.0, 0.5, 0.8), background=0xFF102030),
                  ro.view(rc.orthographic(target, (-1.0, 0.3, -0.4), (0, 0, 1), 10.0, 48, 64, -15.0, 15.0), 48, 64, cull=1, two_sided=0, light=(1.0, -0.3, 0.4))]
-        cviews = (CView * 2)(*[c_view(v) for v in views])
+        cviews = (View * 2)(*[c_view(v) for v in views])
         for want in (RGBA | DEPTH | IDS, RGBA, DEPTH | IDS):
-            out = (CImage * 2)()
+            out = (Image * 2)()
             assert L.MC33_render_isosurface(M, lib.real(iso), cviews, 2, want, out) == 2
             assert (M.contents.iso, M.contents.nV, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V) == (lib.np_real(iso),) + before
             for vw, img in zip(views, out):
@@ -385,7 +373,7 @@ def test_c_api(dtype, monkeypatch, tmp_path):
                 assert not img.rgba and not img.depth and not img.triangle
         # without the map: DefaultColorMC for every vertex
         assert L.MC33_set_color_map(M, None, 0, 0.0, 0.0) == 0
-        out = (CImage * 1)()
+        out = (Image * 1)()
         assert L.MC33_render_isosurface(M, lib.real(iso), cviews, 1, RGBA, out) == 1
         ref = ro.render(s.V, s.N, s.T, None, views[0], base_color=0xFF5C5C5C)
         assert np.array_equal(host_image(out[0], "rgba", np.uint32), ref.rgba)
@@ -393,14 +381,14 @@ def test_c_api(dtype, monkeypatch, tmp_path):
         # a refused view: the object and out are left alone
         out[0].width, out[0].covered = 77, 9
         state = (M.contents.iso, M.contents.nV, M.contents.nT, M.contents.memoryfault)
-        bad = (CView * 2)(c_view(views[0]), c_view(variant(views[1], cull=7)))
+        bad = (View * 2)(c_view(views[0]), c_view(variant(views[1], cull=7)))
         assert L.MC33_render_isosurface(M, lib.real(iso + 1), bad, 2, 7, out) == -1 and L.MC33_render_isosurface(M, lib.real(iso + 1), cviews, 2, 8, out) == -1
         assert (M.contents.iso, M.contents.nV, M.contents.nT, M.contents.memoryfault) == state and (out[0].width, out[0].covered) == (77, 9) and not out[0].rgba
         # MC33_view_fit frames the grid: most of the ball is in the picture
-        v = CView()
+        v = View()
         D3 = C.c_double * 3
         assert L.MC33_view_fit(M, C.byref(D3(-1.0, -0.8, -0.5)), C.byref(D3(0, 0, 1)), 35.0, 64, 64, C.byref(v)) == 0
-        one = (CImage * 1)()
+        one = (Image * 1)()
         assert L.MC33_render_isosurface(M, lib.real(iso), C.pointer(v), 1, IDS, one) == 1
         assert one[0].rejected == 0 and one[0].offscreen + one[0].drawn + one[0].degenerate == s.nT and one[0].covered > 300
         L.MC33_free_image(C.byref(one[0]))
@@ -427,12 +415,12 @@ def test_c_api_refuses_several_slabs(monkeypatch):
     M = L.create_MC33(G)
     assert M
     try:
-        out = (CImage * 1)()
+        out = (Image * 1)()
         out[0].width = 77
         state = (M.contents.iso, M.contents.nV, M.contents.nT, M.contents.memoryfault)
         assert L.MC33_render_isosurface(M, lib.real(c.iso), C.pointer(c_view(c.view)), 1, 7, out) == -1
         assert (M.contents.iso, M.contents.nV, M.contents.nT, M.contents.memoryfault) == state and out[0].width == 77 and not out[0].rgba
-        v = CView()
+        v = View()
         D3 = C.c_double * 3
         assert L.MC33_view_fit(M, C.byref(D3(1, 0, 0)), C.byref(D3(0, 0, 1)), 0.0, 32, 32, C.byref(v)) == 0  # (host only: no slab is asked)
         S = L.calculate_isosurface(M, lib.real(c.iso))

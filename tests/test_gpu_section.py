@@ -21,10 +21,10 @@ import property_oracle as po
 import section_cases as sc
 import section_oracle as so
 from mc33_capi import MC33Lib, product_path, ref_path
-from mesh_harness import SPARE, CanariedCall, bits, ctx, device_grid, once_per_key, to_device, words  # noqa: F401 (ctx: the module's fixture)
-from test_clip_cpu import MODES, PLANES, attributes, clipped, plane_of
-from test_section_cpu import ORIGIN, c_section_api, sectioned
-from test_simplify_cpu import mesh
+from mesh_harness import SPARE, CanariedCall, bits, c_palette, ctx, device_grid, once_per_key, palette, to_device, words  # noqa: F401 (ctx: the module's fixture)
+from clip_cases import MODES, PLANES, attributes, clipped, plane_of
+from mesh_checks import reference_mesh as mesh
+from section_cases import ORIGIN, sectioned
 
 pytestmark = pytest.mark.gpu
 
@@ -530,19 +530,13 @@ def check_c_section(got, want, plane):
 def test_c_api(reflibs, nneg):
     """the oracle applied to the reference's surface - the _nneg reference's for the _nneg flavour, whose area has the other sign"""
     from mc33_c_library_amd.api import Contour, SectionLevel
-    from test_gpu_property import c_palette, palette
     name = "sphere"
     field, iso, _ = mo.FIXTURES[name]
     data, r0, d = field()
     s = MC33Lib(ref_path("f32", nneg=True), "f32").isosurface(data, iso, r0, d) if nneg else mesh(reflibs, name)[4]
     origin = tuple(mo.reference_point(r0, d, data.shape))
     lib = MC33Lib(product_path("f32", nneg=nneg), "f32")
-    L = c_section_api(lib)
-    M_t = C.POINTER(lib.MC33)
-    L.MC33_set_property_grid.restype = C.c_int
-    L.MC33_set_property_grid.argtypes = [M_t, C.POINTER(lib.GRD)]
-    L.MC33_set_color_map.restype = C.c_int
-    L.MC33_set_color_map.argtypes = [M_t, C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
+    L = lib.lib
     G, keep = lib.make_grid(data, r0, d)
     prop = fx.noise_f32(0, 79, shape=data.shape) * np.float32(10.0)
     Pg, keep2 = lib.make_grid(prop, r0, d)
@@ -619,7 +613,7 @@ def test_c_api_on_an_inclined_grid(reflibs):
     Ai = np.linalg.inv(np.array(A)).tolist()
     s = reflibs["f32"].isosurface(data, 0.0, inclined=(A, Ai))
     lib = MC33Lib(product_path("f32"), "f32")
-    L = c_section_api(lib)
+    L = lib.lib
     G, keep = lib.make_grid(data, inclined=(A, Ai))
     M = L.create_MC33(G)
     assert M

@@ -17,61 +17,14 @@ import mesh_pieces as mp
 import property_oracle as po
 import simplify_cases as sc
 import simplify_oracle as sp
-import smooth_oracle as so
-from mc33_capi import MC33Lib, product_path, ref_path
-from mesh_harness import SPARE, CanariedCall, bits, ctx, device_grid, once_per_key, to_device, words  # noqa: F401 (ctx: the module's fixture)
-from test_simplify_cpu import CELLS, MODES, TABLE, CSimplification, mesh, simplified
+from mc33_capi import MC33Lib, ref_path
+from mesh_checks import reference_mesh as mesh
+from mesh_harness import SPARE, SimplifyCall as Call, bits, capi, c_palette, ctx, device_grid, normals_of, once_per_key, palette, to_device, words  # noqa: F401 (ctx: the module's fixture)
+from simplify_cases import CELLS, MODES, TABLE, csimp, simplified
 
 pytestmark = pytest.mark.gpu
 
 COUNTS = sp.Simplified.COUNTS
-
-
-def normals_of(want):
-    return so.vertex_normals(want.V, want.T) if want.nV_out else np.zeros((0, 3), np.float32)
-
-
-class Call(CanariedCall):
-    """one mc33hip_simplify_surface call"""
-
-    def __init__(self, g, V, T, cell, origin=(0.0, 0.0, 0.0), mode=sp.MEAN, drop=True, attrs=(), capV=None, capT=None, with_map=True, with_normals=True, change=None):
-        import torch
-        from mc33_c_library_amd.api import Simplification
-        super().__init__(g)
-        self.nV, self.nT = V.shape[0], T.shape[0]
-        self.capV = self.nV if capV is None else capV
-        self.capT = self.nT if capT is None else capT
-        self.oV, self.oT = self.room(self.capV, 3, V.dtype), self.room(self.capT, 3, torch.int32)
-        self.oN = self.room(self.capV, 3, torch.float32) if with_normals else None
-        self.oA = [self.room(self.capV, 0, torch.int32) for _ in attrs]
-        self.oMap = self.room(self.nV, 0, torch.int32) if with_map else None
-        a = Simplification()
-        a.V, a.T, a.nV, a.nT = V.data_ptr(), T.data_ptr(), self.nV, self.nT
-        for k, x in enumerate(attrs):
-            a.attr[k], a.oAttr[k] = x.data_ptr(), self.oA[k].data_ptr()
-        a.n_attr = len(attrs)
-        a.origin, a.cell = (C.c_double * 3)(*origin), (C.c_double * 3)(*cell)
-        a.mode, a.drop_duplicates = int(mode), int(bool(drop))
-        a.oV, a.oT, a.capV, a.capT = self.oV.data_ptr(), self.oT.data_ptr(), self.capV, self.capT
-        a.oN = self.oN.data_ptr() if with_normals else None
-        a.oMap = self.oMap.data_ptr() if with_map else None
-        self.keep = (V, T, attrs)
-        self.call(g.lib.mc33hip_simplify_surface, a, change)
-        self.counts = tuple(int(getattr(a, n)) for n in COUNTS)
-
-    def check(self, want, attrs=()):
-        """bit for bit against the oracle; attrs: the input words on the host"""
-        assert self.counts == want.counts(), (self.counts, want.counts())
-        nV2, nT2 = want.nV_out, want.nT_out
-        self.equal_bits("oV", self.oV[:nV2], want.V)
-        self.equal_bits("oT", self.oT[:nT2], want.T)
-        if self.oN is not None:
-            self.equal_bits("oN", self.oN[:nV2], normals_of(want))
-        for k, x in enumerate(self.oA):
-            self.equal_bits("attribute %d" % k, x[:nV2], np.asarray(attrs[k])[want.keep])
-        if self.oMap is not None:
-            self.equal_bits("oMap", self.oMap[:self.nV], want.vmap)
-        self.spare_intact()
 
 
 def check_topology(g, call):
@@ -360,23 +313,6 @@ def test_python_methods(reflibs):
 
 # ---- the C API -----------------------------------------------------------------------------------------------------------------------
 
-def capi(dtype="f32", nneg=False):
-    lib = MC33Lib(product_path(dtype, nneg=nneg), dtype)
-    L = lib.lib
-    M = C.POINTER(lib.MC33)
-    L.MC33_calculate_simplified_isosurface.restype = C.POINTER(lib.SURFACE)
-    L.MC33_calculate_simplified_isosurface.argtypes = [M, lib.real, C.POINTER(CSimplification)]
-    L.MC33_set_property_grid.restype = C.c_int
-    L.MC33_set_property_grid.argtypes = [M, C.POINTER(lib.GRD)]
-    L.MC33_set_color_map.restype = C.c_int
-    L.MC33_set_color_map.argtypes = [M, C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
-    return lib
-
-
-def csimp(cell, mode, drop):
-    return CSimplification((C.c_double * 3)(*cell), mode, int(drop))
-
-
 def simplified_surface(lib, M, iso, sm):
     S = lib.lib.MC33_calculate_simplified_isosurface(M, lib.real(iso), C.byref(sm) if sm is not None else None)
     if not S:
@@ -415,7 +351,6 @@ def test_c_api(reflibs, nneg):
             assert np.array_equal(bits(got.V), bits(want.V)) and np.array_equal(bits(got.N), bits(normals_of(want)))
             assert np.all(got.color == po.DEFAULT_COLOR) and got.color.size == want.nV_out
         # colours: those of the extracted vertices, the first of every cell
-        from test_gpu_property import c_palette, palette
         pal, lo, hi = palette(7), -2.5, 3.25
         assert L.MC33_set_property_grid(M, Pg) == 0 and L.MC33_set_color_map(M, c_palette(pal), len(pal), lo, hi) == 0
         painted = simplified_surface(lib, M, iso, csimp(CELLS[cell], mode, drop))

@@ -14,15 +14,12 @@ import fixtures as fx
 import measure_oracle as mo
 import property_oracle as po
 import smooth_oracle as so
-from mc33_capi import MC33Lib, product_path, ref_path
-from mesh_harness import FILL, SPARE, CanariedCall, bits, ctx, device_grid, to_device  # noqa: F401 (ctx: the module's fixture)
-from test_smooth_cpu import CSmoothing, TABLE, mesh
+from mc33_c_library_amd.api import SurfaceSmoothing
+from mc33_capi import MC33Lib, ref_path
+from mesh_harness import FILL, SPARE, CanariedCall, bits, capi, c_palette, ctx, device_grid, info_of, palette, to_device  # noqa: F401 (ctx: the module's fixture)
+from smooth_cases import TABLE, mesh
 
 pytestmark = pytest.mark.gpu
-
-
-def info_of(A):
-    return (A.max_degree, A.isolated_vertices, A.boundary_vertices, A.invalid_triangles)
 
 
 class Call(CanariedCall):
@@ -256,19 +253,6 @@ def test_invalid_arguments(reflibs):
 
 # ---- the C API -----------------------------------------------------------------------------------------------------------------------
 
-def capi(dtype="f32", nneg=False):
-    lib = MC33Lib(product_path(dtype, nneg=nneg), dtype)
-    L = lib.lib
-    M = C.POINTER(lib.MC33)
-    L.MC33_calculate_smoothed_isosurface.restype = C.POINTER(lib.SURFACE)
-    L.MC33_calculate_smoothed_isosurface.argtypes = [M, lib.real, C.POINTER(CSmoothing)]
-    L.MC33_set_property_grid.restype = C.c_int
-    L.MC33_set_property_grid.argtypes = [M, C.POINTER(lib.GRD)]
-    L.MC33_set_color_map.restype = C.c_int
-    L.MC33_set_color_map.argtypes = [M, C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
-    return lib
-
-
 def smoothed_surface(lib, M, iso, sm):
     S = lib.lib.MC33_calculate_smoothed_isosurface(M, lib.real(iso), C.byref(sm) if sm is not None else None)
     if not S:
@@ -295,23 +279,22 @@ def test_c_api(reflibs, name):
     try:
         for pin in (1, 0):
             P, N = smoothed(reflibs, name, bool(pin))
-            got = smoothed_surface(lib, M, iso, CSmoothing(10, 0.5, -0.53, pin))
+            got = smoothed_surface(lib, M, iso, SurfaceSmoothing(10, 0.5, -0.53, pin))
             assert got is not None and (got.nV, got.nT) == (s.nV, s.nT) and np.array_equal(got.T, s.T)
             assert np.array_equal(bits(got.V), bits(P)) and np.array_equal(bits(got.N), bits(N))
             assert np.all(got.color == po.DEFAULT_COLOR) and got.color.size == s.nV
             assert M.contents.iso == np.float32(iso) and M.contents.memoryfault == 0 and M.contents.nT == s.nT
         # colours: those of the unsmoothed surface
-        from test_gpu_property import c_palette, palette
         pal, lo, hi = palette(7), -2.5, 3.25
         assert L.MC33_set_property_grid(M, Pg) == 0 and L.MC33_set_color_map(M, c_palette(pal), len(pal), lo, hi) == 0
-        painted = smoothed_surface(lib, M, iso, CSmoothing(10, 0.5, -0.53, 0))
+        painted = smoothed_surface(lib, M, iso, SurfaceSmoothing(10, 0.5, -0.53, 0))
         want_color = po.color_vertices(s.V, r0, d, prop, pal, lo, hi)
         assert np.array_equal(painted.color, want_color) and np.unique(painted.color).size > 2
         assert np.array_equal(bits(painted.V), bits(P)) and np.array_equal(bits(painted.N), bits(N))
         assert L.MC33_set_property_grid(M, None) == 0
         # a null struct and refused parameters give NULL; the object is still good, and its surface is the reference's
         assert smoothed_surface(lib, M, iso, None) is None
-        for sm in (CSmoothing(10, 0.0, -0.53, 1), CSmoothing(10, 0.5, 0.53, 1), CSmoothing(1001, 0.5, -0.53, 1), CSmoothing(10, float("nan"), -0.53, 1)):
+        for sm in (SurfaceSmoothing(10, 0.0, -0.53, 1), SurfaceSmoothing(10, 0.5, 0.53, 1), SurfaceSmoothing(1001, 0.5, -0.53, 1), SurfaceSmoothing(10, float("nan"), -0.53, 1)):
             assert smoothed_surface(lib, M, iso, sm) is None and M.contents.memoryfault == 0
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S
@@ -319,7 +302,7 @@ def test_c_api(reflibs, name):
         L.free_surface_memory(S)
         assert np.array_equal(bits(mine.V), bits(s.V)) and np.array_equal(mine.T, s.T) and np.array_equal(bits(mine.N), bits(s.N))
         # iterations 0: the extracted vertices with recomputed normals
-        plain = smoothed_surface(lib, M, iso, CSmoothing(0, 0.5, -0.53, 1))
+        plain = smoothed_surface(lib, M, iso, SurfaceSmoothing(0, 0.5, -0.53, 1))
         assert np.array_equal(bits(plain.V), bits(s.V)) and np.array_equal(bits(plain.N), bits(so.vertex_normals(s.V, s.T)))
     finally:
         L.free_MC33(M)
@@ -341,9 +324,9 @@ def test_c_api_nneg_flavour():
     M = L.create_MC33(G)
     assert M
     try:
-        got = smoothed_surface(lib, M, iso, CSmoothing(10, 0.5, -0.53, 1))
+        got = smoothed_surface(lib, M, iso, SurfaceSmoothing(10, 0.5, -0.53, 1))
         assert np.array_equal(got.T, s.T) and np.array_equal(bits(got.V), bits(P)) and np.array_equal(bits(got.N), bits(N))
-        plain = smoothed_surface(lib, M, iso, CSmoothing(0, 0.5, -0.53, 1))
+        plain = smoothed_surface(lib, M, iso, SurfaceSmoothing(0, 0.5, -0.53, 1))
         dots = (plain.N.astype(np.float64) * s.N).sum(1)
         print("nneg: smallest dot product of the recomputed normals with the emitted N %.4f" % dots.min())
         assert dots.min() > 0.0

@@ -12,7 +12,8 @@ import pytest
 import layouts as lo
 import spectrum_cases as sc
 import spectrum_oracle as so
-from test_spectrum_cpu import CSpectrumInfo, report
+from mc33_c_library_amd.api import GridResampling
+from spectrum_cases import c_spectrum, report
 
 pytestmark = pytest.mark.gpu
 
@@ -331,32 +332,10 @@ def test_two_calls_return_the_same_bytes():
 
 # ---- the C API ----------------------------------------------------------------------------------------------------------------------------------
 
-def capi(lib):
-    L = lib.lib
-    L.MC33_grid_spectrum.restype = C.c_int
-    L.MC33_grid_spectrum.argtypes = [C.POINTER(lib.MC33), C.POINTER(lib.real), C.c_uint, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(CSpectrumInfo)]
-    L.MC33_grid_changed.restype = None
-    L.MC33_grid_changed.argtypes = [C.POINTER(lib.MC33)]
-    return L
-
-
-def c_spectrum(lib, L, M, isos):
-    n = len(isos)
-    arr = (lib.real * max(n, 1))(*isos)
-    cut = (C.c_ulonglong * max(n, 1))()
-    hist = (C.c_ulonglong * (n + 1))()
-    info = CSpectrumInfo()
-    rc = L.MC33_grid_spectrum(M, arr, n, cut, hist, C.byref(info))
-    if rc:
-        return rc
-    return so.Spectrum(np.array(cut[:n], np.uint64), np.array(hist[:], np.uint64), info.points, info.cells, info.nan_samples, info.sample_min, info.sample_max)
-
-
 @pytest.mark.parametrize("dtype", ["f32", "u16", "f64", "u8"])
 def test_c_api(products, dtype):
-    from test_resample_cpu import CResampling
     lib = products[dtype]
-    L = capi(lib)
+    L = lib.lib
     F, isos, want = sc.case("one_point_beyond_noise", dtype)
     data = np.array(F)
     G, keep = lib.make_grid(data)
@@ -380,9 +359,7 @@ def test_c_api(products, dtype):
         assert so.same(c_spectrum(lib, L, M, isos), so.spectrum(keep, isos))
         assert bytes(C.string_at(C.addressof(M.contents), C.sizeof(lib.MC33))) == before
         # an object made by MC33_create_resampled: every second point, no taps
-        L.MC33_create_resampled.restype = C.POINTER(lib.MC33)
-        L.MC33_create_resampled.argtypes = [C.POINTER(lib.MC33), C.POINTER(CResampling)]
-        R = L.MC33_create_resampled(M, C.byref(CResampling((C.c_double * 3)(0, 0, 0), (C.c_uint * 3)(0, 0, 0), (C.c_uint * 3)(2, 2, 2))))
+        R = L.MC33_create_resampled(M, C.byref(GridResampling((C.c_double * 3)(0, 0, 0), (C.c_uint * 3)(0, 0, 0), (C.c_uint * 3)(2, 2, 2))))
         assert R
         try:
             rb = bytes(C.string_at(C.addressof(R.contents), C.sizeof(lib.MC33)))

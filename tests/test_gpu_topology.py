@@ -14,10 +14,12 @@ from capi_slab_refusals import refusal
 import fixtures as fx
 import measure_oracle as mo
 import topology_oracle as to
-from mc33_capi import MC33Lib, product_path, ref_path
-from mesh_harness import device_grid, to_device
-from test_gpu_measure import AWKWARD_D, AWKWARD_R0, reference_mesh
-from test_topology_cpu import CComponentTopology, CTopology, bind_topology_api
+from mc33_c_library_amd.api import ComponentTopology
+from mc33_capi import CTopology, MC33Lib, ref_path
+from measure_oracle import AWKWARD_D, AWKWARD_R0
+from mesh_checks import reference_mesh
+from mesh_harness import capi, device_grid, to_device
+from topology_cases import check_surface, check_table
 
 pytestmark = pytest.mark.gpu
 
@@ -38,18 +40,6 @@ def small_grid():
     if not _grid:
         _grid.append(device_grid(*fx.cos_field(16)))
     return _grid[0]
-
-
-def check_surface(label, got, want):
-    print("%s: %r" % (label, got))
-    for n in to.SURFACE_FIELDS:
-        assert getattr(got, n) == want[n], "%s: %s is %d, oracle %d" % (label, n, getattr(got, n), want[n])
-
-
-def check_table(label, got, want):
-    assert got.shape[0] == want.shape[0], "%s: %d components, oracle %d" % (label, got.shape[0], want.shape[0])
-    for col in to.COMPONENT.names:
-        assert np.array_equal(got[col], want[col]), "%s: column %s differs in %d rows" % (label, col, np.count_nonzero(got[col] != want[col]))
 
 
 def check_all(label, g, T, nV, want, tab, labels=None):
@@ -235,12 +225,6 @@ def test_validation(reflibs):
 
 # ---- 5: the C API ---------------------------------------------------------------------------------------------------------------
 
-def capi(dtype="f32", nneg=False):
-    lib = MC33Lib(product_path(dtype, nneg=nneg), dtype)
-    bind_topology_api(lib)
-    return lib
-
-
 def c_surface(t):
     class View:
         pass
@@ -262,13 +246,13 @@ def run_c_api(lib, data, r0, d, iso, want, tab, label, surface=None):
         assert M.contents.iso == np.float32(iso) and M.contents.memoryfault == 0
         nc = C.c_uint()
         assert L.MC33_component_topology(M, lib.real(iso), None, 0, C.byref(nc)) == -2 and nc.value == tab.shape[0]
-        rows = (CComponentTopology * tab.shape[0])()
+        rows = (ComponentTopology * tab.shape[0])()
         if tab.shape[0] > 1:
             C.memset(rows, 0x55, C.sizeof(rows))
             assert L.MC33_component_topology(M, lib.real(iso), rows, tab.shape[0] - 1, C.byref(nc)) == -2 and nc.value == tab.shape[0]
             assert bytes(rows) == b"\x55" * C.sizeof(rows)
         assert L.MC33_component_topology(M, lib.real(iso), rows, tab.shape[0], C.byref(nc)) == 0 and nc.value == tab.shape[0]
-        check_table(label + " (C API)", np.frombuffer(rows, dtype=np.dtype(CComponentTopology)).copy(), tab)
+        check_table(label + " (C API)", np.frombuffer(rows, dtype=np.dtype(ComponentTopology)).copy(), tab)
         assert L.MC33_isosurface_topology(M, lib.real(iso), None) == -1
         if surface is not None:  # the object is still good for calculate_isosurface, and that surface is the reference's
             S = L.calculate_isosurface(M, lib.real(iso))

@@ -8,24 +8,13 @@ import struct
 import numpy as np
 import pytest
 
-from mc33_capi import GRD, MC33Lib, product_path
+from fixtures import write_grd_text
+from mc33_capi import MC33Lib, product_path
 
 
 @pytest.fixture(scope="module")
 def prods():
     return {d: MC33Lib(product_path(d), d) for d in ("f32", "u16", "f64")}
-
-
-def declare(lib):
-    L = lib.lib
-    for n in ("read_grd", "read_grd_binary", "read_dat_file"):
-        getattr(L, n).restype = C.POINTER(GRD)
-        getattr(L, n).argtypes = [C.c_char_p]
-    L.read_scanfiles.restype = C.POINTER(GRD)
-    L.read_scanfiles.argtypes = [C.c_char_p, C.c_uint, C.c_int]
-    L.read_raw_file.restype = C.POINTER(GRD)
-    L.read_raw_file.argtypes = [C.c_char_p, C.POINTER(C.c_uint), C.c_int, C.c_int]
-    return L
 
 
 def samples(lib, G):
@@ -62,24 +51,10 @@ def free_both(pl, Gp, rl, Gr):
     rl.lib.free_memory_grd(Gr)
 
 
-def write_grd_text(path, N, L, ang, lo, order, values):
-    nx, ny, nz = (n + 1 for n in N)
-    with open(path, "w") as f:
-        f.write("a title line for the grid\n(1p,e12.5)\n")
-        f.write("%8.4f %8.4f %8.4f %8.4f %8.4f %8.4f\n" % (L + ang))
-        f.write("%5d %5d %5d\n" % N)
-        f.write("%5d %5d %5d %5d %5d %5d %5d\n" % (order, lo[0], lo[0] + N[0], lo[1], lo[1] + N[1], lo[2], lo[2] + N[2]))
-        v = values.reshape(nz, ny, nx)
-        for k in range(nz):
-            block = v[k] if order == 1 else v[k].T
-            for x in block.ravel():
-                f.write("%.7e\n" % x)
-
-
 @pytest.mark.parametrize("ang,order,lo", [((90.0, 90.0, 90.0), 1, (0, 0, 0)), ((90.0, 90.0, 90.0), 3, (-2, 0, 5)),
                                           ((80.0, 95.0, 70.0), 1, (0, 3, 0)), ((60.0, 60.0, 60.0), 3, (1, 1, 1))])
 def test_read_grd_text(prods, reflibs, tmp_path, ang, order, lo):
-    P, R = declare(prods["f32"]), declare(reflibs["f32"])
+    P, R = prods["f32"].lib, reflibs["f32"].lib
     N = (5, 4, 3)
     rng = np.random.RandomState(11)
     vals = rng.normal(size=(N[2] + 1) * (N[1] + 1) * (N[0] + 1)) * rng.choice([1.0, 1e-6, 1e5], (N[2] + 1) * (N[1] + 1) * (N[0] + 1))
@@ -97,7 +72,7 @@ def test_read_grd_text(prods, reflibs, tmp_path, ang, order, lo):
 
 
 def test_read_grd_text_rejects_bad_headers(prods, reflibs, tmp_path):
-    P, R = declare(prods["f32"]), declare(reflibs["f32"])
+    P, R = prods["f32"].lib, reflibs["f32"].lib
     path = str(tmp_path / "bad.grd")
     write_grd_text(path, (5, 4, 3), (1.0, 1.0, 1.0), (90.0, 90.0, 90.0), (0, 0, 0), 2, np.zeros(120))  # order must be 1 or 3
     assert not P.read_grd(path.encode()) and not R.read_grd(path.encode())
@@ -122,7 +97,7 @@ def write_grd_binary(path, dtype, N, L, r0, d, data, inclined=None, title=b"bina
 @pytest.mark.parametrize("inclined", [False, True])
 def test_read_grd_binary(prods, reflibs, tmp_path, dtype, inclined):
     import fixtures as fx
-    P, R = declare(prods[dtype]), declare(reflibs[dtype])
+    P, R = prods[dtype].lib, reflibs[dtype].lib
     N = (6, 3, 4)
     rng = np.random.RandomState(2)
     data = rng.normal(size=(5, 4, 7)).astype(prods[dtype].np_dtype) if dtype != "u16" else rng.randint(0, 65535, (5, 4, 7)).astype(np.uint16)
@@ -143,7 +118,7 @@ def test_read_grd_binary(prods, reflibs, tmp_path, dtype, inclined):
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
 @pytest.mark.parametrize("nfiles,order", [(1, 0), (4, 1), (5, 0)])
 def test_read_scanfiles(prods, reflibs, tmp_path, dtype, nfiles, order):
-    P, R = declare(prods[dtype]), declare(reflibs[dtype])
+    P, R = prods[dtype].lib, reflibs[dtype].lib
     res = 6
     rng = np.random.RandomState(nfiles)
     slices = rng.randint(0, 65535, (nfiles, res, res)).astype(np.uint16)
@@ -161,7 +136,7 @@ def test_read_scanfiles(prods, reflibs, tmp_path, dtype, nfiles, order):
 @pytest.mark.parametrize("dtype", ["f32", "u16", "f64"])
 @pytest.mark.parametrize("byte,isfloat", [(1, 0), (2, 0), (-2, 0), (4, 0), (-4, 0), (4, 1), (-4, 1), (8, 1), (-8, 1)])
 def test_read_raw_file(prods, reflibs, tmp_path, dtype, byte, isfloat):
-    P, R = declare(prods[dtype]), declare(reflibs[dtype])
+    P, R = prods[dtype].lib, reflibs[dtype].lib
     n = (5, 4, 3)  # points in x, y, z
     rng = np.random.RandomState(abs(byte) + isfloat)
     count = n[0] * n[1] * n[2]
@@ -186,7 +161,7 @@ def test_read_raw_file(prods, reflibs, tmp_path, dtype, byte, isfloat):
 
 
 def test_read_raw_file_rejects_bad_widths(prods, reflibs, tmp_path):
-    P, R = declare(prods["f32"]), declare(reflibs["f32"])
+    P, R = prods["f32"].lib, reflibs["f32"].lib
     path = str(tmp_path / "v.raw")
     open(path, "wb").write(bytes(600))
     N = (C.c_uint * 3)(5, 4, 3)
@@ -196,7 +171,7 @@ def test_read_raw_file_rejects_bad_widths(prods, reflibs, tmp_path):
 
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
 def test_read_dat_file(prods, reflibs, tmp_path, dtype):
-    P, R = declare(prods[dtype]), declare(reflibs[dtype])
+    P, R = prods[dtype].lib, reflibs[dtype].lib
     nx, ny, nz = 7, 5, 4
     data = np.random.RandomState(8).randint(0, 4096, (nz, ny, nx)).astype(np.uint16)
     path = str(tmp_path / "v.dat")
@@ -217,7 +192,7 @@ def test_truncated_files_never_crash_or_hang(prods, tmp_path):
     import signal
     import fixtures as fx
     lib = prods["f32"]
-    P = declare(lib)
+    P = lib.lib
     rng = np.random.RandomState(1)
     data = rng.normal(size=(5, 4, 7)).astype(np.float32)
     files = []

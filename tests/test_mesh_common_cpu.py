@@ -1,7 +1,7 @@
 """The layer the passes over a finished mesh share (mc33_c_library_amd/csrc/mc33_mesh.hip.h), the part that needs no
 GPU: its kernels in the gfx950 code object of every sample type, and its place in the translation unit and in both builds.
 
-MESH_KERNELS is the one list of the shared kernels.  The tests of the parts that launch them (test_measure_cpu.py,
+MESH_KERNELS (tests/mesh_checks.py) is the one list of the shared kernels.  The tests of the parts that launch them (test_measure_cpu.py,
 test_topology_cpu.py, test_filter_cpu.py, test_smooth_cpu.py, test_simplify_cpu.py, test_clip_cpu.py) take the names their entry
 points launch from it through launched(), beside the kernels of their own.  On the device the layer is held to the oracles by
 the GPU tests of those parts and by tests/test_gpu_mesh_scratch.py."""
@@ -9,21 +9,9 @@ import os
 
 import pytest
 
-from mesh_checks import assert_kernels
+from mesh_checks import MESH_KERNELS, assert_kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# (the second argument of k_mesh_place: 0 a rank, 1 the new index or none, 2 row starts with the total behind them)
-MESH_KERNELS = ["k_mesh_tile_sum<MeshFlag>", "k_mesh_tile_sum<MeshCount>", "k_mesh_tile_sum<ClipOwned>", "k_mesh_tile_sum<ClipOutputs>", "k_mesh_scan_top",
-                "k_mesh_place<MeshFlag, 0>", "k_mesh_place<MeshFlag, 1>", "k_mesh_place<MeshCount, 2>", "k_mesh_clear", "k_mesh_ref"]
-
-
-def launched(*names):
-    """the shared kernels a part launches, by their names in MESH_KERNELS"""
-    for n in names:
-        assert n in MESH_KERNELS, n
-    return list(names)
-
 
 @pytest.mark.parametrize("dtype", ["f32", "u16", "u8", "u32", "f64"])
 def test_shared_kernels_are_in_the_code_object(dtype):

@@ -84,10 +84,6 @@ def test_host_logic_library_refuses_a_property_grid(dtype):
     (they are weak references), MC33_set_property_grid returns -1, a colour map alone changes nothing."""
     with host_logic(dtype, prop=linear_property) as h:
         lib, L, M, iso, Pg = h.lib, h.L, h.M, h.iso, h.Pg
-        L.MC33_set_property_grid.restype = C.c_int
-        L.MC33_set_property_grid.argtypes = [C.POINTER(lib.MC33), C.POINTER(lib.GRD)]
-        L.MC33_set_color_map.restype = C.c_int
-        L.MC33_set_color_map.argtypes = [C.POINTER(lib.MC33), C.POINTER(C.c_int), C.c_uint, C.c_double, C.c_double]
         assert L.MC33_set_property_grid(M, Pg) == -1
         assert L.MC33_set_property_grid(M, None) == -1
         pal = (C.c_int * 3)(1, 2, 3)

@@ -15,7 +15,8 @@ import pytest
 
 import render_cases as rc
 import render_oracle as ro
-from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets
+from mc33_c_library_amd.api import Image, View
+from mesh_checks import assert_exported, assert_kernels, host_logic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -184,36 +185,11 @@ def test_cases_show_what_they_are_for(oracles):
 
 # ---- MC33_view_fit: host C, through the host-logic build ---------------------------------------------------------------------------
 
-class CView(C.Structure):
-    _fields_ = [("m", C.c_double * 16), ("width", C.c_uint), ("height", C.c_uint), ("cull", C.c_int), ("two_sided", C.c_int),
-                ("light", C.c_double * 3), ("ambient", C.c_double), ("diffuse", C.c_double), ("background", C.c_uint)]
-
-
-class CImage(C.Structure):
-    _fields_ = [("width", C.c_uint), ("height", C.c_uint), ("rgba", C.POINTER(C.c_uint)), ("depth", C.POINTER(C.c_float)), ("triangle", C.POINTER(C.c_uint))] + \
-               [(n, C.c_uint) for n in ("drawn", "culled", "degenerate", "rejected", "offscreen", "invalid_triangles")] + \
-               [("fragments", C.c_ulonglong), ("covered", C.c_ulonglong), ("nV", C.c_uint), ("nT", C.c_uint)]
-
-
 D3 = C.c_double * 3
 
 
-def declare(lib):
-    L = lib.lib
-    L.MC33_view_fit.restype = C.c_int
-    L.MC33_view_fit.argtypes = [C.POINTER(lib.MC33), C.POINTER(D3), C.POINTER(D3), C.c_double, C.c_uint, C.c_uint, C.POINTER(CView)]
-    L.MC33_render_isosurface.restype = C.c_int
-    L.MC33_render_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CView), C.c_uint, C.c_uint, C.POINTER(CImage)]
-    L.MC33_free_image.restype = None
-    L.MC33_free_image.argtypes = [C.POINTER(CImage)]
-    if hasattr(L, "MC33_write_image_ppm"):  # (mc33_surface_io.c: in the product libraries, not in the host-logic build)
-        L.MC33_write_image_ppm.restype = C.c_int
-        L.MC33_write_image_ppm.argtypes = [C.POINTER(CImage), C.c_char_p]
-    return L
-
-
 def fit(L, M, direction, up, fov, width, height, out=None):
-    v = out if out is not None else CView()
+    v = out if out is not None else View()
     return L.MC33_view_fit(M, C.byref(D3(*direction)) if direction is not None else None, C.byref(D3(*up)) if up is not None else None, fov, width, height, C.byref(v)), v
 
 
@@ -225,7 +201,7 @@ def test_view_fit_frames_the_box(inclined):
     """the eight corners of the grid's box - of an inclined grid, the sheared box - land inside the viewport with depth in [0, 1]"""
     with host_logic("f32") as h:
         lib = h.lib
-        L = declare(lib)
+        L = lib.lib
         data = np.zeros((7, 10, 13), np.float32)
         r0, d = (1.0, -20.0, 300.0), (0.5, 1.0, 2.0)
         A = np.array(INCLINED) if inclined else np.eye(3)
@@ -262,9 +238,9 @@ def test_view_fit_frames_the_box(inclined):
 
 def test_view_fit_refusals():
     with host_logic("f32") as h:
-        L = declare(h.lib)
+        L = h.lib.lib
         nan, inf = float("nan"), float("inf")
-        v = CView()
+        v = View()
         v.width, v.ambient = 77, 5.0
         bad = [((0, 0, 0), (0, 0, 1), 0.0, 64, 64), ((nan, 0, 1), (0, 0, 1), 0.0, 64, 64), ((1, 0, 0), (0, inf, 1), 0.0, 64, 64), ((1, 0, 0), (0, 0, 0), 0.0, 64, 64),
                ((1, 2, 3), (2, 4, 6), 30.0, 64, 64), ((1, 2, 3), (-1, -2, -3), 30.0, 64, 64), ((1, 0, 0), (0, 0, 1), -1.0, 64, 64), ((1, 0, 0), (0, 0, 1), 170.5, 64, 64),
@@ -309,20 +285,6 @@ def test_render_kernels_are_in_the_code_object(dtype):
     assert_kernels(dtype, WIDE_KERNELS, max_vgprs=80)
 
 
-def test_python_structs_match_the_header():
-    from mc33_c_library_amd.api import Image, Rendering, View
-    members = ["N", "T", "C", "nV", "nT", "m", "width", "height", "cull", "two_sided", "light", "ambient", "diffuse", "base_color", "background", "oRGBA", "oDepth", "oTri",
-               "drawn", "invalid_triangles", "fragments", "covered"]
-    vmembers = ["width", "height", "cull", "two_sided", "light", "ambient", "diffuse", "background"]
-    imembers = ["height", "rgba", "depth", "triangle", "drawn", "invalid_triangles", "fragments", "covered", "nV", "nT"]
-    want = c_layout(["sizeof(mc33hip_rendering)", "sizeof(mc33_view)", "sizeof(mc33_image)"] + offsets("mc33hip_rendering", members) + offsets("mc33_view", vmembers) +
-                    offsets("mc33_image", imembers))
-    for view, image in ((View, Image), (CView, CImage)):
-        got = [C.sizeof(Rendering), C.sizeof(view), C.sizeof(image)] + [getattr(Rendering, m).offset for m in members] + [getattr(view, m).offset for m in vmembers] + \
-              [getattr(image, m).offset for m in imembers]
-        assert got == want
-
-
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
 def test_host_logic_library_refuses_to_render(dtype):
     """mc33_capi.c linked with the emulated device layer, which cannot render: the library still loads (a weak reference),
@@ -330,23 +292,23 @@ def test_host_logic_library_refuses_to_render(dtype):
     object extracts as before."""
     with host_logic(dtype) as h:
         lib, M, iso = h.lib, h.M, h.iso
-        L = declare(lib)
+        L = lib.lib
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         before = (M.contents.iso, M.contents.nV, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V)
         L.free_surface_memory(S)
         good = fit(L, M, (1, 2, -1), (0, 0, 1), 30.0, 48, 32)[1]
-        views = (CView * 2)(good, good)
-        out = (CImage * 2)()
+        views = (View * 2)(good, good)
+        out = (Image * 2)()
         for o in out:
             o.width, o.nT, o.covered = 77, 5, 9
         calls = [(views, 2, 7, out), (views, 1, 1, out), (views, 0, 7, out), (views, 2, 0, out), (views, 2, 8, out), (None, 2, 7, out), (views, 2, 7, None)]
         for change in ({"width": 0}, {"height": 4097}, {"cull": 3}, {"ambient": float("nan")}, {"light": (0.0, 0.0, 0.0)}):
-            bad = (CView * 2)(good, good)
+            bad = (View * 2)(good, good)
             for k, x in change.items():
                 setattr(bad[1], k, D3(*x) if k == "light" else x)
             calls.append((bad, 2, 7, out))
-        bad = (CView * 2)(good, good)
+        bad = (View * 2)(good, good)
         bad[0].m[5] = float("inf")
         calls.append((bad, 2, 7, out))
         for views_, n, want, out_ in calls:
@@ -362,10 +324,10 @@ def test_ppm_round_trip(tmp_path):
     """a made-up image through MC33_write_image_ppm: the header, then R, G, B of every word, the top row first; alpha is not written"""
     from mc33_capi import MC33Lib, product_path
     if True:
-        L = declare(MC33Lib(product_path("f32"), "f32"))  # (mc33_surface_io.c is host C: the product library serves it without a device)
+        L = MC33Lib(product_path("f32"), "f32").lib  # (mc33_surface_io.c is host C: the product library serves it without a device)
         width, height = 7, 5
         words = np.random.default_rng(3).integers(0, 1 << 32, width * height, dtype=np.uint64).astype(np.uint32)
-        img = CImage()
+        img = Image()
         img.width, img.height = width, height
         img.rgba = words.ctypes.data_as(C.POINTER(C.c_uint))
         path = str(tmp_path / "picture.ppm")
@@ -378,6 +340,6 @@ def test_ppm_round_trip(tmp_path):
         assert L.MC33_write_image_ppm(C.byref(img), str(tmp_path / "no" / "such" / "dir.ppm").encode()) == -1
         img.rgba = None
         assert L.MC33_write_image_ppm(C.byref(img), path.encode()) == -1 and L.MC33_write_image_ppm(None, path.encode()) == -1
-        empty = CImage()
+        empty = Image()
         L.MC33_free_image(C.byref(empty))
         L.MC33_free_image(None)

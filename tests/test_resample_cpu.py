@@ -20,7 +20,8 @@ import layouts
 import resample_cases as rc
 import resample_oracle as ro
 from mc33_capi import MC33Lib, product_path
-from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, kernels_of, offsets
+from mc33_c_library_amd.api import GridResampling
+from mesh_checks import assert_exported, assert_kernels, host_logic, kernels_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "mc33_c_library_amd", "csrc", "mc33_resample.hip.h")
@@ -29,10 +30,6 @@ HIP_NAMES = ["mc33hip_resampled_size", "mc33hip_resample_grid", "mc33hip_context
 C_NAMES = ["MC33_gaussian_taps", "MC33_create_resampled", "MC33_resampled_grid"]
 TYPES = ["f32", "u16", "u8", "u32", "f64"]
 MAX_VGPRS = 64   # with identity taps eight blocks of four waves share a CU, eight waves on every SIMD - 64 registers per lane
-
-
-class CResampling(C.Structure):
-    _fields_ = [("sigma", C.c_double * 3), ("radius", C.c_uint * 3), ("stride", C.c_uint * 3)]
 
 
 # ---- the oracle ---------------------------------------------------------------------------------------------------------------------
@@ -84,8 +81,6 @@ def _taps_fn(dtype="f32"):
     path = product_path(dtype)
     assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
     lib = MC33Lib(path, dtype).lib
-    lib.MC33_gaussian_taps.restype = C.c_int
-    lib.MC33_gaussian_taps.argtypes = [C.c_double, C.c_uint, C.POINTER(C.c_double)]
     return lib.MC33_gaussian_taps
 
 
@@ -148,16 +143,6 @@ def test_resampling_kernel_is_in_the_code_object(dtype):
         assert ks[name]["group_segment_fixed_size"] == 0, (name, ks[name])   # (all of its LDS is sized by the plan at launch)
 
 
-def test_python_structs_match_the_header():
-    from mc33_c_library_amd.api import GridResampling, Resampling
-    want = c_layout(["sizeof(mc33hip_resampling)"] + offsets("mc33hip_resampling", ["taps", "ntaps", "stride"]) +
-                    ["sizeof(mc33_resampling)"] + offsets("mc33_resampling", ["sigma", "radius", "stride"]))
-    R, G = Resampling, GridResampling
-    got = [C.sizeof(R), R.taps.offset, R.ntaps.offset, R.stride.offset, C.sizeof(G), G.sigma.offset, G.radius.offset, G.stride.offset]
-    assert got == want
-    assert [C.sizeof(CResampling), CResampling.sigma.offset, CResampling.radius.offset, CResampling.stride.offset] == want[4:]
-
-
 # ---- the host-logic build: mc33_capi.c on a device layer that cannot resample ------------------------------------------------------------
 
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
@@ -166,10 +151,6 @@ def test_host_logic_library_refuses_to_resample(dtype):
     and MC33_resampled_grid of an ordinary object is NULL."""
     with host_logic(dtype) as h:
         lib, L, M, iso = h.lib, h.L, h.M, h.iso
-        L.MC33_create_resampled.restype = C.POINTER(lib.MC33)
-        L.MC33_create_resampled.argtypes = [C.POINTER(lib.MC33), C.POINTER(CResampling)]
-        L.MC33_resampled_grid.restype = C.POINTER(lib.GRD)
-        L.MC33_resampled_grid.argtypes = [C.POINTER(lib.MC33)]
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         first = lib.copy_surface(S)
@@ -177,11 +158,11 @@ def test_host_logic_library_refuses_to_resample(dtype):
         before = bytes(C.string_at(C.addressof(M.contents), C.sizeof(lib.MC33)))
         d3, u3 = C.c_double * 3, C.c_uint * 3
         nan, inf = float("nan"), float("inf")
-        cases = [CResampling(d3(1, 1, 1), u3(0, 0, 0), u3(1, 1, 1)), CResampling(d3(0, 0, 0), u3(0, 0, 0), u3(2, 2, 2)),
-                 CResampling(d3(-1, 1, 1), u3(0, 0, 0), u3(1, 1, 1)), CResampling(d3(1, nan, 1), u3(0, 0, 0), u3(1, 1, 1)),
-                 CResampling(d3(1, 1, inf), u3(0, 0, 0), u3(1, 1, 1)), CResampling(d3(3, 1, 1), u3(0, 0, 0), u3(1, 1, 1)),
-                 CResampling(d3(1, 1, 1), u3(0, 9, 0), u3(1, 1, 1)), CResampling(d3(1, 1, 1), u3(0, 0, 0), u3(1, 0, 1)),
-                 CResampling(d3(0, 0, 0), u3(0, 0, 0), u3(1, 1, 19))]
+        cases = [GridResampling(d3(1, 1, 1), u3(0, 0, 0), u3(1, 1, 1)), GridResampling(d3(0, 0, 0), u3(0, 0, 0), u3(2, 2, 2)),
+                 GridResampling(d3(-1, 1, 1), u3(0, 0, 0), u3(1, 1, 1)), GridResampling(d3(1, nan, 1), u3(0, 0, 0), u3(1, 1, 1)),
+                 GridResampling(d3(1, 1, inf), u3(0, 0, 0), u3(1, 1, 1)), GridResampling(d3(3, 1, 1), u3(0, 0, 0), u3(1, 1, 1)),
+                 GridResampling(d3(1, 1, 1), u3(0, 9, 0), u3(1, 1, 1)), GridResampling(d3(1, 1, 1), u3(0, 0, 0), u3(1, 0, 1)),
+                 GridResampling(d3(0, 0, 0), u3(0, 0, 0), u3(1, 1, 19))]
         for r in cases:
             assert not L.MC33_create_resampled(M, C.byref(r))
             assert bytes(C.string_at(C.addressof(M.contents), C.sizeof(lib.MC33))) == before

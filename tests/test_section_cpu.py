@@ -19,10 +19,9 @@ import measure_oracle as mo
 import section_cases as sc
 import section_oracle as so
 import topology_oracle as to
-from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets
-from test_clip_cpu import MODES, PLANES, attributes, clipped, plane_of
-from test_mesh_common_cpu import launched
-from test_simplify_cpu import mesh
+from clip_cases import MODES, PLANES, attributes, clipped, plane_of
+from mesh_checks import assert_exported, assert_kernels, host_logic, launched, reference_mesh as mesh
+from section_cases import ORIGIN, sectioned
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -32,20 +31,6 @@ KERNELS = ["k_section_tri", "k_section_init", "k_section_emit", "k_section_point
            "k_section_table_points", "k_section_table_roots", "k_mesh_scan_top3", "k_clip_tri", "k_clip_own"] + \
     launched("k_mesh_clear", "k_mesh_tile_sum<MeshFlag>", "k_mesh_tile_sum<ClipOwned>", "k_mesh_scan_top", "k_mesh_place<MeshFlag, 0>", "k_mesh_place<MeshFlag, 1>")
 TEMPLATED = ["k_section_rows", "k_section_new", "k_section_sums", "k_section_table_segments", "k_section_ladder", "k_clip_class"]
-ORIGIN = (1.5, 1.5, 1.5)  # the reference point of the context of mesh_harness.tiny_grid: r0 + 0.5 * N * d of a 4^3 grid
-
-_results = {}
-
-
-def sectioned(reflibs, name, which):
-    """the oracle's result of one case, computed once, shared (tests/test_gpu_section.py uses it too) and left unchanged"""
-    key = (name, which)
-    if key not in _results:
-        s = mesh(reflibs, name)[4]
-        _results[key] = so.section(s.V, s.T, plane_of(s.V, which), attributes(s.nV), MODES, ORIGIN)
-    return _results[key]
-
-
 @pytest.mark.parametrize("which", PLANES)
 @pytest.mark.parametrize("name", list(mo.FIXTURES))
 def test_the_two_restatements_agree_and_the_cut_points_are_clips(reflibs, name, which):
@@ -233,38 +218,6 @@ def test_section_kernels_are_in_the_code_object(dtype):
     assert_kernels(dtype, KERNELS + ["%s<%s>" % (k, real) for k in TEMPLATED])  # no scratch, no spill, at most 64 registers
 
 
-def test_python_structs_match_the_header():
-    from mc33_c_library_amd.api import Contour, SectionLevel, Sectioning, SurfaceSection
-    members = ["T", "nV", "nT", "attr", "n_attr", "attr_mode", "plane", "oP", "oS", "oAttr", "oLabel", "oNext", "oPointMap", "capP", "capS", "nP_out",
-               "cut_points", "branch_points", "length", "area_vector", "area", "origin"]
-    rows = ["root", "points", "segments", "open_ends", "branch_points", "closed", "length", "area"]
-    pub = ["nP", "nS", "P", "S", "contour", "next", "color", "on_points", "cut_points", "contours", "closed_contours", "open_ends", "branch_points",
-           "degenerate_segments", "length", "area", "plane"]
-    level = ["segments", "length", "area"]
-    want = c_layout(["sizeof(mc33hip_section)", "sizeof(mc33hip_contour)", "sizeof(mc33_contour)", "sizeof(mc33_section)", "sizeof(mc33_section_level)"] +
-                    offsets("mc33hip_section", members) + offsets("mc33hip_contour", rows) + offsets("mc33_contour", rows) + offsets("mc33_section", pub) +
-                    offsets("mc33_section_level", level))
-    got = [C.sizeof(Sectioning), C.sizeof(Contour), C.sizeof(Contour), C.sizeof(SurfaceSection), C.sizeof(SectionLevel)] + \
-        [getattr(Sectioning, m).offset for m in members] + [getattr(Contour, m).offset for m in rows] * 2 + [getattr(SurfaceSection, m).offset for m in pub] + \
-        [getattr(SectionLevel, m).offset for m in level]
-    assert got == want
-
-
-def c_section_api(lib):
-    """argument and result types of the four entry points on an MC33Lib"""
-    from mc33_c_library_amd.api import Contour, SectionLevel, SurfaceSection
-    L, M = lib.lib, C.POINTER(lib.MC33)
-    L.MC33_section_isosurface.restype = C.POINTER(SurfaceSection)
-    L.MC33_section_isosurface.argtypes = [M, lib.real, C.POINTER(C.c_double * 4)]
-    L.MC33_free_section.restype = None
-    L.MC33_free_section.argtypes = [C.POINTER(SurfaceSection)]
-    L.MC33_section_contours.restype = C.c_int
-    L.MC33_section_contours.argtypes = [M, lib.real, C.POINTER(C.c_double * 4), C.POINTER(Contour), C.c_uint, C.POINTER(C.c_uint)]
-    L.MC33_section_profile.restype = C.c_int
-    L.MC33_section_profile.argtypes = [M, lib.real, C.POINTER(C.c_double * 3), C.POINTER(C.c_double), C.c_uint, C.POINTER(SectionLevel)]
-    return L
-
-
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
 def test_host_logic_library_refuses_to_section(dtype):
     """mc33_capi.c linked with the emulated device layer, which cannot section: the library still loads (weak references), the
@@ -273,7 +226,7 @@ def test_host_logic_library_refuses_to_section(dtype):
     from mc33_c_library_amd.api import Contour, SectionLevel
     with host_logic(dtype) as h:
         lib, M, iso = h.lib, h.M, h.iso
-        L = c_section_api(lib)
+        L = lib.lib
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         before = (M.contents.iso, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V)

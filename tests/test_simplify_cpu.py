@@ -15,8 +15,9 @@ import pytest
 import filter_oracle as fo
 import measure_oracle as mo
 import simplify_oracle as sp
-from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets, reference_mesh
-from test_mesh_common_cpu import launched
+from mc33_c_library_amd.api import SurfaceSimplification
+from mesh_checks import assert_exported, assert_kernels, host_logic, launched, reference_mesh as mesh
+from simplify_cases import CELLS, MODES, TABLE, simplified
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -24,48 +25,8 @@ HIP_NAMES = ["mc33hip_simplify_surface"]
 C_NAMES = ["MC33_calculate_simplified_isosurface"]
 KERNELS = ["k_simp_clear", "k_simp_reps", "k_simp_tri_insert", "k_simp_tri_keep", "k_simp_tris"] + launched("k_mesh_ref", "k_mesh_tile_sum<MeshFlag>", "k_mesh_scan_top",
                                                                                                  "k_mesh_place<MeshFlag, 1>")
-CELLS = {"2x2x2": (2.0, 2.0, 2.0), "3x2x5": (3.0, 2.0, 5.0)}  # in grid cells
-MODES = {"mean": sp.MEAN, "first": sp.FIRST}
-
-# (fixture, cell) -> nV_out, nT_out, clusters, max_cluster, collapsed, duplicates (duplicates dropped; the mode changes none of them)
-TABLE = {
-    ("sphere", "2x2x2"): (4568, 9132, 4568, 14, 32924, 0),
-    ("sphere", "3x2x5"): (2136, 4268, 2136, 31, 37788, 0),
-    ("blobs", "2x2x2"): (5611, 11114, 5611, 15, 41050, 0),
-    ("blobs", "3x2x5"): (2551, 5045, 2551, 36, 47062, 57),
-    ("sheet", "2x2x2"): (3220, 6106, 3220, 11, 23326, 0),
-    ("sheet", "3x2x5"): (1558, 2889, 1558, 27, 26542, 1),
-    ("noise", "2x2x2"): (3892, 17388, 3898, 38, 83001, 2495),
-    ("noise", "3x2x5"): (1258, 6913, 1258, 90, 92975, 2996),
-    ("quant", "2x2x2"): (1728, 7271, 1728, 20, 25911, 766),
-    ("quant", "3x2x5"): (480, 2596, 480, 55, 30313, 1039),
-}
-
-
 # vertices that share a cell of d / 1024 with a vertex of smaller index (test_one_cell_and_tiny_cells)
 TINY_MERGED = {"sphere": 0, "blobs": 24, "sheet": 0, "noise": 6, "quant": 0}
-
-
-class CSimplification(C.Structure):
-    _fields_ = [("cell", C.c_double * 3), ("mode", C.c_int), ("drop_duplicates", C.c_int)]
-
-
-def mesh(reflibs, name):
-    """the reference's surface of a fixture row, computed once and left unchanged"""
-    return reference_mesh(reflibs, name)
-
-
-_results = {}
-
-
-def simplified(reflibs, name, cell, mode, drop=True):
-    """the oracle's result of one case, computed once, shared (tests/test_gpu_simplify.py uses it too) and left unchanged"""
-    key = (name, cell, mode, drop)
-    if key not in _results:
-        data, r0, d, iso, s = mesh(reflibs, name)
-        c = tuple(CELLS[cell][k] * d[k] for k in range(3))
-        _results[key] = sp.simplify(s.V, s.T, c, r0, MODES[mode], drop)
-    return _results[key]
 
 
 @pytest.mark.parametrize("cell", list(CELLS))
@@ -189,18 +150,6 @@ def test_simplification_kernels_are_in_the_code_object(dtype):
     assert_kernels(dtype, KERNELS + ["k_simp_cluster<%s>" % real, "k_simp_rows<%s>" % real])
 
 
-def test_python_structs_match_the_header():
-    from mc33_c_library_amd.api import Simplification, SurfaceSimplification
-    members = ["nT", "attr", "n_attr", "origin", "cell", "mode", "drop_duplicates", "oV", "oT", "oN", "oAttr", "oMap", "capV", "capT", "nV_out", "max_cluster",
-               "clamped_vertices"]
-    want = c_layout(["sizeof(mc33hip_simplification)", "sizeof(mc33_simplification)"] + offsets("mc33_simplification", ["mode", "drop_duplicates"]) +
-                    offsets("mc33hip_simplification", members))
-    S, Z = Simplification, SurfaceSimplification
-    got = [C.sizeof(S), C.sizeof(Z), Z.mode.offset, Z.drop_duplicates.offset] + [getattr(S, m).offset for m in members]
-    assert got == want
-    assert [C.sizeof(CSimplification), CSimplification.mode.offset, CSimplification.drop_duplicates.offset] == want[1:4]
-
-
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
 def test_host_logic_library_refuses_to_simplify(dtype):
     """mc33_capi.c linked with the emulated device layer, which cannot simplify: the library still loads (a weak reference),
@@ -208,17 +157,15 @@ def test_host_logic_library_refuses_to_simplify(dtype):
     device in any build, for a null struct and every refused parameter -, and the object extracts as before."""
     with host_logic(dtype) as h:
         lib, L, M, iso = h.lib, h.L, h.M, h.iso
-        L.MC33_calculate_simplified_isosurface.restype = C.POINTER(lib.SURFACE)
-        L.MC33_calculate_simplified_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CSimplification)]
         S = L.calculate_isosurface(M, lib.real(iso))
         assert S and S.contents.nV > 0
         before = (M.contents.iso, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V)
         L.free_surface_memory(S)
         three = C.c_double * 3
         inf, nan = float("inf"), float("nan")
-        cases = [CSimplification(three(2, 2, 2), 0, 1), CSimplification(three(2, 2, 2), 1, 0)] + \
-                [CSimplification(three(*c), 0, 1) for c in ((0, 2, 2), (2, -1, 2), (2, 2, inf), (nan, 2, 2))] + \
-                [CSimplification(three(2, 2, 2), m, 1) for m in (2, -1)]
+        cases = [SurfaceSimplification(three(2, 2, 2), 0, 1), SurfaceSimplification(three(2, 2, 2), 1, 0)] + \
+                [SurfaceSimplification(three(*c), 0, 1) for c in ((0, 2, 2), (2, -1, 2), (2, 2, inf), (nan, 2, 2))] + \
+                [SurfaceSimplification(three(2, 2, 2), m, 1) for m in (2, -1)]
         for sm in cases:
             assert not L.MC33_calculate_simplified_isosurface(M, lib.real(iso + 1), C.byref(sm))
             assert (M.contents.iso, M.contents.nT, M.contents.memoryfault, M.contents.T, M.contents.V) == before

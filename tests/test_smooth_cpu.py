@@ -15,43 +15,15 @@ import pytest
 
 import measure_oracle as mo
 import smooth_oracle as so
-from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, offsets, reference_mesh
-from test_mesh_common_cpu import launched
+from mc33_c_library_amd.api import SurfaceSmoothing
+from mesh_checks import assert_exported, assert_kernels, host_logic, launched
+from smooth_cases import TABLE, mesh
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 HIP_NAMES = ["mc33hip_smooth_surface", "mc33hip_vertex_normals"]
 C_NAMES = ["MC33_calculate_smoothed_isosurface"]
 KERNELS = ["k_sm_count<0>", "k_sm_count<1>", "k_sm_fill<0>", "k_sm_fill<1>", "k_sm_rows"] + launched("k_mesh_tile_sum<MeshCount>", "k_mesh_scan_top", "k_mesh_place<MeshCount, 2>")
-
-# fixture -> max_degree, isolated, boundary_vertices, area before, after 10 iterations (0.5, -0.53) pinned, not pinned
-TABLE = {
-    "sphere": (9, 0, 0, 12.5617, 12.5646, 12.5646),
-    "blobs": (9, 0, 0, 759.1933, 761.8437, 761.8437),
-    "sheet": (9, 0, 720, 150.2069, 150.2014, 148.4636),
-    "noise": (13, 0, 5778, 328.3539, 282.8174, 271.7802),
-    "quant": (17, 25, 2543, 13919.5392, 11875.7812, 11193.6348),
-}
-
-
-class CSmoothing(C.Structure):
-    _fields_ = [("iterations", C.c_uint), ("lam", C.c_double), ("mu", C.c_double), ("pin_boundary", C.c_int)]
-
-
-_meshes = {}
-
-
-def mesh(reflibs, name):
-    """the reference's surface of a fixture row, its adjacency and both smoothed copies, computed once and left unchanged"""
-    if name not in _meshes:
-        data, r0, d, iso, s = reference_mesh(reflibs, name)
-        A = so.adjacency(s.T, s.nV)
-        P = {pin: so.smooth(s.V, s.T, 10, 0.5, -0.53, pin, A=A)[0] for pin in (True, False)}
-        for a in (P[True], P[False]):
-            a.setflags(write=False)
-        _meshes[name] = (data, r0, d, iso, s, A, P)
-    return _meshes[name]
-
 
 @pytest.mark.parametrize("name", list(TABLE))
 def test_oracle_on_the_reference_meshes(reflibs, name):
@@ -147,26 +119,13 @@ def test_smoothing_kernels_are_in_the_code_object(dtype, real):
     assert_kernels(dtype, KERNELS + ["k_sm_pass<%s>" % real, "k_sm_normals<%s>" % real])
 
 
-def test_python_structs_match_the_header():
-    from mc33_c_library_amd.api import Smoothing, SurfaceSmoothing
-    members = ["nT", "iterations", "lambda", "pin_boundary", "oV", "oN", "max_degree", "invalid_triangles"]
-    want = c_layout(["sizeof(mc33hip_smoothing)"] + offsets("mc33hip_smoothing", members) + ["sizeof(mc33_smoothing)", "offsetof(mc33_smoothing, pin_boundary)"])
-    S = Smoothing
-    got = [C.sizeof(S), S.nT.offset, S.iterations.offset, S.lam.offset, S.pin_boundary.offset, S.oV.offset, S.oN.offset, S.max_degree.offset,
-           S.invalid_triangles.offset, C.sizeof(SurfaceSmoothing), SurfaceSmoothing.pin_boundary.offset]
-    assert got == want
-    assert [C.sizeof(CSmoothing), CSmoothing.pin_boundary.offset] == want[9:]
-
-
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
 def test_host_logic_library_refuses_to_smooth(dtype):
     """mc33_capi.c linked with the emulated device layer, which cannot smooth: the library still loads (a weak reference),
     MC33_calculate_smoothed_isosurface returns NULL and leaves the object alone, and the object extracts as before."""
     with host_logic(dtype) as h:
         lib, L, M, iso = h.lib, h.L, h.M, h.iso
-        L.MC33_calculate_smoothed_isosurface.restype = C.POINTER(lib.SURFACE)
-        L.MC33_calculate_smoothed_isosurface.argtypes = [C.POINTER(lib.MC33), lib.real, C.POINTER(CSmoothing)]
-        sm = CSmoothing(10, 0.5, -0.53, 1)
+        sm = SurfaceSmoothing(10, 0.5, -0.53, 1)
         assert not L.MC33_calculate_smoothed_isosurface(M, lib.real(iso), C.byref(sm)) and M.contents.memoryfault == 0
         assert not L.MC33_calculate_smoothed_isosurface(M, lib.real(iso), None)
         S = L.calculate_isosurface(M, lib.real(iso))

@@ -21,7 +21,9 @@ import layouts
 import spectrum_cases as sc
 import spectrum_oracle as so
 from mc33_capi import MC33Lib, product_path
-from mesh_checks import assert_exported, assert_kernels, c_layout, host_logic, kernels_of, offsets
+from mc33_c_library_amd.api import SpectrumInfo
+from mesh_checks import assert_exported, assert_kernels, host_logic, kernels_of
+from spectrum_cases import report
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -30,10 +32,6 @@ HEADER = os.path.join(ROOT, "mc33_c_library_amd", "csrc", "mc33_spectrum.hip.h")
 HIP_NAMES = ["mc33hip_grid_spectrum"]
 C_NAMES = ["MC33_grid_spectrum", "MC33_isovalue_ladder"]
 TYPES = sc.TYPES
-
-
-class CSpectrumInfo(C.Structure):
-    _fields_ = [("points", C.c_ulonglong), ("cells", C.c_ulonglong), ("nan_samples", C.c_ulonglong), ("sample_min", C.c_double), ("sample_max", C.c_double)]
 
 
 # ---- the oracle ---------------------------------------------------------------------------------------------------------------------
@@ -109,8 +107,6 @@ def _ladder_fn(dtype):
     assert os.path.exists(path), "build the HIP libraries first (python -m mc33_c_library_amd.build)"
     lib = MC33Lib(path, dtype)
     fn = lib.lib.MC33_isovalue_ladder
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_double, C.c_double, C.c_uint, C.POINTER(lib.real)]
     return lib, fn
 
 
@@ -179,16 +175,6 @@ def test_spectrum_kernels_are_in_the_code_object(dtype):
         assert ks[name]["group_segment_fixed_size"] <= 8192, (name, ks[name])
 
 
-def test_python_structs_match_the_header():
-    from mc33_c_library_amd.api import Spectrum, SpectrumInfo
-    hf = ("isos", "n", "cut_cells", "histogram", "points", "cells", "nan_samples", "sample_min", "sample_max")
-    cf = ("points", "cells", "nan_samples", "sample_min", "sample_max")
-    want = c_layout(["sizeof(mc33hip_spectrum)"] + offsets("mc33hip_spectrum", hf) + ["sizeof(mc33_spectrum_info)"] + offsets("mc33_spectrum_info", cf))
-    got = [C.sizeof(Spectrum)] + [getattr(Spectrum, f).offset for f in hf] + [C.sizeof(SpectrumInfo)] + [getattr(SpectrumInfo, f).offset for f in cf]
-    assert got == want
-    assert [C.sizeof(CSpectrumInfo)] + [getattr(CSpectrumInfo, f).offset for f in cf] == want[len(hf) + 1:]
-
-
 # ---- the host-logic build: mc33_capi.c on a device layer without a spectrum ------------------------------------------------------------
 
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
@@ -197,10 +183,6 @@ def test_host_logic_library_refuses_the_spectrum(dtype):
     ladder is host C and works."""
     with host_logic(dtype, n=12) as h:
         lib, L, M, iso = h.lib, h.L, h.M, h.iso
-        L.MC33_grid_spectrum.restype = C.c_int
-        L.MC33_grid_spectrum.argtypes = [C.POINTER(lib.MC33), C.POINTER(lib.real), C.c_uint, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(CSpectrumInfo)]
-        L.MC33_isovalue_ladder.restype = C.c_int
-        L.MC33_isovalue_ladder.argtypes = [C.c_double, C.c_double, C.c_uint, C.POINTER(lib.real)]
         nV, nT = C.c_uint(), C.c_uint()
         L.size_of_isosurface(M, lib.real(iso), C.byref(nV), C.byref(nT))
         assert nV.value > 0
@@ -208,7 +190,7 @@ def test_host_logic_library_refuses_the_spectrum(dtype):
         isos = (lib.real * 3)(iso - 1, iso, iso + 1)
         cut = (C.c_ulonglong * 3)(*[0xA5A5] * 3)
         hist = (C.c_ulonglong * 4)(*[0xA5A5] * 4)
-        info = CSpectrumInfo(1, 2, 3, 4.0, 5.0)
+        info = SpectrumInfo(1, 2, 3, 4.0, 5.0)
         for n in (3, 1, 0):
             assert L.MC33_grid_spectrum(M, isos, n, cut, hist, C.byref(info)) == -1
         assert L.MC33_grid_spectrum(M, isos, 3, cut, hist, None) == -1 and L.MC33_grid_spectrum(None, isos, 3, cut, hist, C.byref(info)) == -1
@@ -281,10 +263,6 @@ def run_host_case(program, tmp, F, isos, lay_name="dense", pack=1, rng=None):
     assert not hist[n + 1:].any() and not diff[n + 1:].any() and int(diff.sum()) == 0
     planes = ze - zb + int(ze == npz - 1)
     return so.Spectrum(np.cumsum(diff)[:n].astype(np.uint64), hist[:n + 1].copy(), npx * npy * planes, (npx - 1) * (npy - 1) * (ze - zb), nan, lo, hi), r.stdout
-
-
-def report(got, want):
-    return "cut_cells %s\n     want %s\nhistogram %s\n     want %s\n%s\n%s" % (got.cut_cells.tolist(), want.cut_cells.tolist(), got.histogram.tolist(), want.histogram.tolist(), got[2:], want[2:])
 
 
 @pytest.mark.parametrize("name", list(sc.CASES))

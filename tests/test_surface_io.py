@@ -16,18 +16,6 @@ def prod():
     return MC33Lib(product_path("f32"), "f32")
 
 
-def declare(lib):
-    L = lib.lib
-    for n in ("write_bin_s", "write_txt_s", "write_obj_s"):
-        getattr(L, n).restype = C.c_int
-        getattr(L, n).argtypes = [C.POINTER(SURFACE), C.c_char_p]
-    L.write_ply_s.restype = C.c_int
-    L.write_ply_s.argtypes = [C.POINTER(SURFACE), C.c_char_p, C.c_char_p, C.c_char_p]
-    L.read_bin_s.restype = C.POINTER(SURFACE)
-    L.read_bin_s.argtypes = [C.c_char_p]
-    return L
-
-
 def make_surface(nV, nT, seed=3, iso=0.125):
     """A surface whose arrays live in numpy memory; capv == nV and capt == nT, so adjustvectorlenght_s (called by
     every writer) leaves them alone."""
@@ -46,7 +34,7 @@ def make_surface(nV, nT, seed=3, iso=0.125):
 
 @pytest.mark.parametrize("nV,nT", [(1, 0), (7, 3), (300, 611)])
 def test_writers_match_reference_bytes(prod, reflibs, tmp_path, nV, nT):
-    P, R = declare(prod), declare(reflibs["f32"])
+    P, R = prod.lib, reflibs["f32"].lib
     S, keep = make_surface(nV, nT)
     for fn, ext in (("write_bin_s", "sup"), ("write_txt_s", "txt"), ("write_obj_s", "obj")):
         a, b = str(tmp_path / ("p." + ext)).encode(), str(tmp_path / ("r." + ext)).encode()
@@ -60,7 +48,7 @@ def test_writers_match_reference_bytes(prod, reflibs, tmp_path, nV, nT):
 
 
 def test_writer_error_codes(prod, reflibs, tmp_path):
-    P, R = declare(prod), declare(reflibs["f32"])
+    P, R = prod.lib, reflibs["f32"].lib
     S, keep = make_surface(5, 2)
     bad = str(tmp_path / "no_such_dir" / "x").encode()
     for fn in ("write_bin_s", "write_txt_s", "write_obj_s"):
@@ -80,7 +68,7 @@ def surface_arrays(lib, Sp):
 
 
 def test_read_bin_roundtrip_both_ways(prod, reflibs, tmp_path):
-    P, R = declare(prod), declare(reflibs["f32"])
+    P, R = prod.lib, reflibs["f32"].lib
     S, (T, V, N, col) = make_surface(123, 77, seed=9, iso=-2.5)
     for writer, reader, rl in ((P, R, reflibs["f32"]), (R, P, prod)):
         path = str(tmp_path / "x.sup").encode()
@@ -102,7 +90,7 @@ def test_read_bin_roundtrip_both_ways(prod, reflibs, tmp_path):
 
 def test_read_bin_double_precision_file(prod, reflibs, tmp_path):
     """A ".sud" file, as a double build of the reference writes it (MC:128-136): iso and V are doubles."""
-    P, R = declare(prod), declare(reflibs["f32"])
+    P, R = prod.lib, reflibs["f32"].lib
     _, (T, V, N, col) = make_surface(40, 21, seed=4)
     path = tmp_path / "d.sud"
     with open(path, "wb") as f:
@@ -121,7 +109,7 @@ def test_read_bin_double_precision_file(prod, reflibs, tmp_path):
 
 
 def test_read_bin_sets_capacities(prod, tmp_path):
-    P = declare(prod)
+    P = prod.lib
     S, keep = make_surface(10, 4)
     path = str(tmp_path / "c.sup").encode()
     assert P.write_bin_s(C.byref(S), path) == 0
@@ -137,12 +125,7 @@ def test_double_build_files(reflibs, tmp_path):
     print the doubles; a ".sup" file of a float build is read and widened (MC:128-136, 178-204)."""
     from mc33_capi import SURFACE64
     P64, R64 = MC33Lib(product_path("f64"), "f64"), reflibs["f64"]
-    Pl, Rl = declare(P64), declare(R64)
-    for L in (Pl, Rl):
-        for n in ("write_bin_s", "write_txt_s", "write_obj_s"):
-            getattr(L, n).argtypes = [C.POINTER(SURFACE64), C.c_char_p]
-        L.write_ply_s.argtypes = [C.POINTER(SURFACE64), C.c_char_p, C.c_char_p, C.c_char_p]
-        L.read_bin_s.restype = C.POINTER(SURFACE64)
+    Pl, Rl = P64.lib, R64.lib
     rng = np.random.RandomState(21)
     nV, nT = 57, 40
     V = rng.uniform(-50, 50, (nV, 3)) * 1.0000001234567
@@ -162,7 +145,7 @@ def test_double_build_files(reflibs, tmp_path):
     assert open(str(tmp_path / "p.sud"), "rb").read()[:4] == struct.pack("<i", 0x6575732e)
     # a float-build file read by the double build
     Sf, keep = make_surface(33, 12, seed=5, iso=0.75)
-    f32 = declare(reflibs["f32"])
+    f32 = reflibs["f32"].lib
     sup = str(tmp_path / "f.sup").encode()
     assert f32.write_bin_s(C.byref(Sf), sup) == 0
     for L, lib in ((Pl, P64), (Rl, R64)):
@@ -180,7 +163,7 @@ def test_read_bin_on_damaged_files_never_crashes(prod, tmp_path):
     import os
     import signal
     import struct
-    P = declare(prod)
+    P = prod.lib
     S, keep = make_surface(40, 25, seed=4)
     path = str(tmp_path / "ok.sup")
     assert P.write_bin_s(C.byref(S), path.encode()) == 0

@@ -12,8 +12,9 @@ import pytest
 
 import measure_oracle as mo
 import topology_oracle as to
-from mesh_checks import assert_exported, assert_kernels, host_logic, reference_mesh
-from test_mesh_common_cpu import launched
+from mc33_c_library_amd.api import ComponentTopology
+from mc33_capi import CTopology
+from mesh_checks import assert_exported, assert_kernels, host_logic, launched, reference_mesh
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -133,42 +134,13 @@ def test_topology_kernels_are_in_the_code_object():
     assert_kernels("f32", KERNELS, max_vgprs=128)  # (two blocks of 256 per SIMD at least)
 
 
-def test_python_structs_match_the_header():
-    from mc33_c_library_amd.api import ComponentTopology, Topology
-    assert C.sizeof(Topology) == 12 * 8 + 8 + 4 * 4 and Topology.euler.offset == 96 and Topology.closed.offset == 104
-    assert C.sizeof(ComponentTopology) == 80 and ComponentTopology.edges.offset == 16 and ComponentTopology.genus.offset == 72
-    assert np.dtype(ComponentTopology).itemsize == to.COMPONENT.itemsize == 80
-    assert [to.COMPONENT.fields[n][1] for n in to.COMPONENT.names] == [np.dtype(ComponentTopology).fields[n][1] for n in to.COMPONENT.names]
-
-
-class CTopology(C.Structure):
-    _fields_ = [("nV", C.c_uint), ("nT", C.c_uint)] + \
-               [(n, C.c_ulonglong) for n in ("referenced_vertices", "edges", "boundary_edges", "nonmanifold_edges", "misoriented_edges", "degenerate_triangles",
-                                             "boundary_loops", "components", "closed_components", "genus_sum")] + \
-               [("euler", C.c_longlong)] + [(n, C.c_int) for n in ("closed", "manifold", "oriented", "genus_defined")]
-
-
-class CComponentTopology(C.Structure):
-    _fields_ = [("root", C.c_uint), ("nV", C.c_uint), ("nT", C.c_uint)] + [(n, C.c_ulonglong) for n in to.COUNTS] + [("euler", C.c_longlong), ("genus", C.c_int)]
-
-
-def bind_topology_api(lib):
-    L = lib.lib
-    M = C.POINTER(lib.MC33)
-    L.MC33_isosurface_topology.restype = C.c_int
-    L.MC33_isosurface_topology.argtypes = [M, lib.real, C.POINTER(CTopology)]
-    L.MC33_component_topology.restype = C.c_int
-    L.MC33_component_topology.argtypes = [M, lib.real, C.POINTER(CComponentTopology), C.c_uint, C.POINTER(C.c_uint)]
-
-
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
 def test_host_logic_library_refuses(dtype):
     """mc33_capi.c linked with the emulated device layer, which has neither entry point: the library still loads (they are weak
     references), both functions return -1, and the object extracts as before."""
     with host_logic(dtype) as h:
         lib, L, M, iso = h.lib, h.L, h.M, h.iso
-        bind_topology_api(lib)
-        t, rows, n = CTopology(), (CComponentTopology * 4)(), C.c_uint(7)
+        t, rows, n = CTopology(), (ComponentTopology * 4)(), C.c_uint(7)
         assert L.MC33_isosurface_topology(M, lib.real(iso), C.byref(t)) == -1
         assert L.MC33_component_topology(M, lib.real(iso), rows, 4, C.byref(n)) == -1 and n.value == 0
         S = L.calculate_isosurface(M, lib.real(iso))
