@@ -406,6 +406,9 @@ MC33_HD void plan_visit(CellPlan &p, const Tables &tab, const Params &P, const G
 			const uint32_t kind = w & 3u, arg = (w >> 9) & 15u;
 			if (kind == 1) {  // another edge of this cell, if already visited
 				if (p.visited & (1u << arg)) {
+#ifdef MC33_RULE_HOOK  // tests/host_emu only: count the rule word that gives the on-point vertex its id
+					MC33_RULE_HOOK(x, y, z, first + q, e, va != 0);
+#endif
 					plan_set_rank(p, e, plan_rank(p, arg));
 					plan_set_tgt(p, e, plan_tgt(p, arg));
 					return;
@@ -419,6 +422,9 @@ MC33_HD void plan_visit(CellPlan &p, const Tables &tab, const Params &P, const G
 			} else
 				pass = sign_of(v[(int)arg]);
 			if (!pass) continue;
+#ifdef MC33_RULE_HOOK
+			MC33_RULE_HOOK(x, y, z, first + q, e, va != 0);
+#endif
 			const uint32_t t = (w >> 20) & 0xFFu;  // axis | sx+1 | sy+1 | sz+1, same layout as make_tgt
 			plan_set_tgt(p, e, t);
 			const uint32_t also = w >> 28;
@@ -428,6 +434,9 @@ MC33_HD void plan_visit(CellPlan &p, const Tables &tab, const Params &P, const G
 			}
 			return;
 		}
+#ifdef MC33_RULE_HOOK  // (no rule applied: the fall-through, rule = NO_ID)
+		MC33_RULE_HOOK(x, y, z, NO_ID, e, va != 0);
+#endif
 		plan_set_rank(p, e, p.nnew++);  // MC33_surfint (MC:628)
 		p.created |= bit;
 		p.onpoint |= bit;

@@ -12,6 +12,15 @@ static unsigned g_plane_lo = 0, g_plane_hi = 0xFFFFFFFFu, g_px = 0xFFFFFFFFu, g_
 static unsigned long long g_violations = 0;
 #define MC33_BOUNDS_HOOK(x, y, z) \
 	do { if ((z) < g_plane_lo || (z) > g_plane_hi || (x) >= g_px || (y) >= g_py) g_violations++; } while (0)
+// where the vertices that lie on a grid point take their id from (plan_visit): hits per (face flags of the cell, rule word) and,
+// where no rule applies, per (face flags, edge, end point) - tests/atlas_cases.py: the rule atlas fires every reachable one
+static unsigned long long g_rule_hits[8][81], g_fall_hits[8][12][2];
+static inline void emu_rule_hit(unsigned x, unsigned y, unsigned z, unsigned rule, unsigned e, unsigned end) {
+	const unsigned flags = (x == 0 ? 1u : 0u) | (y == 0 ? 2u : 0u) | (z == 0 ? 4u : 0u);
+	if (rule == 0xFFFFFFFFu) g_fall_hits[flags][e][end]++;
+	else g_rule_hits[flags][rule]++;
+}
+#define MC33_RULE_HOOK(x, y, z, rule, e, end) emu_rule_hit((x), (y), (z), (rule), (e), (end) ? 1u : 0u)
 #include "../../mc33_c_library_amd/csrc/mc33_cell.h"
 #include "../../mc33_c_library_amd/csrc/mc33_lut_data.h"
 #include "../../mc33_c_library_amd/csrc/mc33_rules_data.h"
@@ -230,6 +239,74 @@ extern "C" int emu_slab_u16(const uint16_t *data, uint32_t npx, uint32_t npy, ui
 	return emu_slab_pitched_u16(data, npx, npy, npz, npx, (uint64_t)npx * npy, r0, d, iso, slab, out, violations);
 }
 extern "C" unsigned long long emu_last_violations(void) { return g_violations; }
+
+// Every witness cell of the row atlas (tests/atlas_cases.py: 8 samples as [z][y][x], isovalue 0, none equal to it) at every
+// face-flag value 0..7: the record k_cells makes from the pattern offset, the pattern-info and pattern-order tables and the owned
+// slots (make_face_entry; flags 0: make_tested_entry / the fast table) is the one the generic plan of that cell makes, and the tests
+// on register-held values choose the pattern the tests on a VRef choose.  index_out / pattern_out [n]: what the device logic makes
+// of each witness.  Returns the number of (witness, flags) pairs checked, or -(1 + 8 * witness + flags) of the first that fails.
+extern "C" long emu_check_atlas_records(const float *cells, uint32_t n, uint8_t *index_out, uint16_t *pattern_out) {
+	Tables tab{mc33_lut, mc33_rule_words, &mc33_rule_index[0][0]};
+	constexpr uint32_t lut_n = sizeof mc33_lut / sizeof mc33_lut[0];
+	static uint32_t info[lut_n];
+	static uint64_t order[lut_n];
+	build_pattern_info(mc33_lut, lut_n, info);
+	build_pattern_order(mc33_lut, lut_n, order);
+	uint32_t fast[256];
+	build_fast_table(mc33_lut, fast);
+	Params P{};
+	P.nx = P.ny = P.nz = 64;
+	GridView<float> G{nullptr, 0, 0, 0};
+	long checked = 0;
+	for (uint32_t w = 0; w < n; w++) {
+		float vb[8];
+		Corner8 c8;
+		uint32_t i = 0;
+		for (uint32_t k = 0; k < 8; k++) {
+			const uint32_t c = corner_code(k);
+			vb[k] = iso_diff(0.0f, cells[8 * w + 4 * (c >> 2) + 2 * ((c >> 1) & 1) + (c & 1)]);
+			c8.a[k] = vb[k];
+			i |= sign_of(vb[k]) << (7 - k);
+		}
+		uint32_t m, nn;
+		const uint32_t poff = pattern_offset(mc33_lut, i, c8, m, nn);
+		index_out[w] = (uint8_t)i;
+		pattern_out[w] = (uint16_t)poff;
+		for (uint32_t flags = 0; flags < 8; flags++) {
+			const long fail = -(long)(1 + 8 * w + flags);
+			const uint32_t x = (flags & 1) ? 0 : 5, y = (flags & 2) ? 0 : 6, z = (flags & 4) ? 0 : 7;
+			CellPlan p;
+			plan_cell(p, tab, P, G, x, y, z, i, VRef{vb, 1});
+			if (p.poff != poff || p.m != m || p.n != nn || p.zmask) return fail;
+			Entry want = make_entry(37, i, p, p.ntri, 11, 13, false);
+			want.w3 |= ENTRY_TESTED | (flags ? ENTRY_FACE : 0u);
+			Entry got = make_face_entry(37, i, poff, (info[poff] >> 16) & 15u, order[poff], owned_slots(flags), 11, 13);
+			if (!flags) got.w3 &= ~ENTRY_FACE;
+			if (got.w0 != want.w0 || got.w1 != want.w1 || got.w2 != want.w2 || got.w3 != want.w3) return fail;
+			if (!flags) {  // the interior forms of the same record
+				const Entry t = make_tested_entry(37, i, poff, info[poff], 11, 13);
+				if (t.w0 != want.w0 || t.w1 != want.w1 || t.w2 != want.w2 || t.w3 != want.w3) return fail;
+				if (fast[i] != FAST_NONE) {
+					const Entry f = make_fast_entry(37, i, fast[i], 11, 13);
+					if (f.w0 != want.w0 || f.w1 != want.w1 || f.w2 != want.w2 || (f.w3 | ENTRY_TESTED) != want.w3) return fail;
+				}
+			}
+			checked++;
+		}
+	}
+	return checked;
+}
+
+// the rule counters since the last reset: rules [8][81], falls [8][12][2]
+static_assert(MC33_RULE_WORDS == 81, "g_rule_hits is sized for 81 rule words");
+extern "C" void emu_rule_counts(unsigned long long *rules, unsigned long long *falls) {
+	memcpy(rules, g_rule_hits, sizeof g_rule_hits);
+	memcpy(falls, g_fall_hits, sizeof g_fall_hits);
+}
+extern "C" void emu_rule_counts_reset(void) {
+	memset(g_rule_hits, 0, sizeof g_rule_hits);
+	memset(g_fall_hits, 0, sizeof g_fall_hits);
+}
 
 // Every sign index with `per_index` random sets of corner values (no value 0): the record k_cells makes for an
 // interior cell from the pattern offset + the pattern-info table must be the one the generic plan makes, the tests on

@@ -67,6 +67,18 @@ class Emu:
         self.slab_fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                  C.c_float, C.POINTER(SLAB), C.POINTER(OSURF), C.POINTER(C.c_ulonglong)]
         self.lib.emu_last_violations.restype = C.c_ulonglong
+        self.lib.emu_rule_counts.argtypes = [C.c_void_p, C.c_void_p]
+
+    def rule_counts_reset(self):
+        self.lib.emu_rule_counts_reset()
+
+    def rule_counts(self):
+        """(rules [8, 81], falls [8, 12, 2]): how often, since the last reset, a vertex on a grid point took its id through rule
+        word r in a cell with face flags f (bit 0: x = 0, bit 1: y = 0, bit 2: z = 0), and how often no rule applied for the
+        vertex of edge e at its first / second end point (MC33_RULE_HOOK of mc33_cell.h; counters of the whole library)"""
+        rules, falls = np.zeros((8, 81), np.uint64), np.zeros((8, 12, 2), np.uint64)
+        self.lib.emu_rule_counts(rules.ctypes.data, falls.ctypes.data)
+        return rules, falls
 
     def isosurface(self, data, iso, r0=None, d=None, slab=None, layout=None):
         """slab = (z_begin, z_end, ghost, id_base, plane_lo, plane_hi) emulates one rank of a z-slab run;
