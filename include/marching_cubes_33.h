@@ -463,11 +463,32 @@ int MC33_section_profile(MC33 *extractor, MC33_real isovalue, const double norma
  * NULL, with `source` untouched: a null or refused struct (the rules of MC33_gaussian_taps, a zero stride, fewer than 2 points left
  * on an axis), a source spread over several devices (MC33_HIP_DEVICES), a failure of the device.
  * MC33_resampled_grid downloads that grid into a fresh _GRD with alloc_F rows - N, r0, the new d, the inclined members - to be
- * released with free_memory_grd; NULL for an object that MC33_create_resampled did not make. */
+ * released with free_memory_grd; NULL for an object that neither MC33_create_resampled nor MC33_create_ranked made. */
 typedef struct { double sigma[3]; unsigned radius[3]; unsigned stride[3]; } mc33_resampling;  /* sigma in samples; 0: none; radius 0: ceil(3 sigma) */
 int MC33_gaussian_taps(double sigma, unsigned radius, double *taps);
 MC33 *MC33_create_resampled(MC33 *source, const mc33_resampling *r);
 _GRD *MC33_resampled_grid(MC33 *resampled);
+
+/* extension (not in the reference): the grid rank-filtered on the GPU before anything is extracted from it.  Every grid point is
+ * replaced by the minimum, the median or the maximum of the samples in a box window of radius[a] samples along axis a (x, y, z)
+ * around it, edge samples replicated.  A 3 x 3 x 3 median (radius 1, 1, 1) removes isolated spikes and leaves a step edge where it
+ * is, which a Gaussian does not; radius (1, 1, 0) is the per-slice 3 x 3 median of anisotropic stacks.  A minimum followed by a
+ * maximum of the same radius is an opening (small specks go), the other order a closing (small gaps are bridged): the objects
+ * chain.  The filter selects one of its input samples and computes nothing new - NaN samples and -0 have a place in its order and
+ * keep their bytes; the exact definition is in mc33_hip.h (mc33hip_rank_grid).  MC33_RANK_MIN and MC33_RANK_MAX take radii up to 8,
+ * MC33_RANK_MEDIAN up to 1; all radii 0 copies the grid.
+ * MC33_create_ranked returns a NEW, independent extractor of the same nx, ny, nz, O and D whose grid exists only in device memory,
+ * with everything MC33_create_resampled says about its object: free_MC33 releases it and `source` may be freed first; F is NULL; an
+ * inclined source stays inclined; the property grid and the colour map are not carried over; MC33_grid_changed and
+ * MC33_HIP_REUPLOAD do nothing on it; every other entry point works as on any object, MC33_create_ranked and MC33_create_resampled
+ * included; MC33_resampled_grid downloads its grid.
+ * NULL, with `source` untouched: a null or refused struct (a rank that is none of the three, a radius above its limit), a source
+ * spread over several devices (MC33_HIP_DEVICES), a failure of the device. */
+#define MC33_RANK_MIN    0
+#define MC33_RANK_MEDIAN 1
+#define MC33_RANK_MAX    2
+typedef struct { unsigned radius[3]; int rank; } mc33_ranking;  /* radius per axis x, y, z, in samples */
+MC33 *MC33_create_ranked(MC33 *source, const mc33_ranking *r);
 
 /* extension (not in the reference): the contour spectrum of the grid - what a caller needs to choose an isovalue, from one pass
  * over the volume on the GPU instead of one size_of_isosurface per candidate.  For `count` <= 255 isovalues, strictly ascending as

@@ -625,6 +625,43 @@ int mc33hip_resample_grid(mc33hip_ctx *c, const mc33hip_resampling *r, void *dst
  * second context for the resampled grid is created on this device, whatever the current device has become since. */
 int mc33hip_context_device(mc33hip_ctx *c);
 
+/* --- rank-filter the resident grid into a second device grid: minimum, median, maximum windows (no counterpart in the reference) --
+ * A 3 x 3 x 3 median removes isolated spikes and leaves a step edge where it is; a minimum window followed by a maximum window of
+ * the same radius is an opening, the other order a closing.  A rank filter SELECTS one of its input samples and computes nothing
+ * new: the result is an exact function of the input, nothing has a tolerance, any tiling gives the same bytes.
+ *   source      the grid resident in the context - the library's own copy or an adopted buffer at any pitch, slice and alignment -
+ *               with np[a] points per axis (a: x = 0, y = 1, z = 2) and samples F[z][y][x] of the library's sample type.  The
+ *               context must hold a WHOLE grid: plane0 == 0 and npz_resident == nz_total + 1.
+ *   key         the only ordering the filter uses.  Unsigned char, short and int: the value itself.  Float with bit pattern b:
+ *               b ^ 0xFFFFFFFF when the sign bit is set, otherwise b | 0x80000000; double: the same on 64 bits.  Ascending keys
+ *               give: NaN with the sign bit set, -inf, ..., -0, +0, ..., +inf, NaN without the sign bit.  Two samples with equal
+ *               keys have equal bytes, so no tie rule is needed.  No floating-point comparison decides anything.
+ *   window      with cl(i, n) = min(max(i, 0), n - 1), the window of output point (x, y, z) is the multiset of the
+ *               n = (2 radius[0] + 1)(2 radius[1] + 1)(2 radius[2] + 1) samples F[cl(z + dz, np[2])][cl(y + dy, np[1])][cl(x + dx, np[0])]
+ *               for |dx| <= radius[0], |dy| <= radius[1], |dz| <= radius[2]: edge samples are replicated, and a replicated sample
+ *               counts once for every offset that lands on it.
+ *   output      out[z][y][x] holds the bytes of the window's sample of rank k in ascending key order: k = 0 for MC33HIP_RANK_MIN,
+ *               k = n - 1 for MC33HIP_RANK_MAX, k = (n - 1) / 2 for MC33HIP_RANK_MEDIAN (n is odd: the median is one sample).  The
+ *               bytes are kept as they are, NaN payloads and -0 included.  The output grid has the source's size, r0, d and
+ *               inclined matrices.
+ *   limits      MIN and MAX: radius[a] <= 8.  MEDIAN: radius[a] <= 1 - windows of 1, 3, 9 or 27 samples, the per-slice 3 x 3 median
+ *               of anisotropic stacks and the 3 x 3 x 3 median among them.  All radii 0 is a copy of the grid points.
+ *   separable   the minimum of a box is the minimum along z of the minima along y of the minima along x, and every step is a pure
+ *               selection: composing the three per-axis passes is exact, for the maximum likewise.  An implementation of MIN and
+ *               MAX may therefore work axis by axis (this one does, inside a block); the median is not separable.
+ *   dst         device memory with the layout mc33hip_adopt_device takes - pitch / slice in samples, pitch >= np[0],
+ *               slice >= pitch * np[1], any base address a sample may have.  ONLY grid points are written: padding keeps its
+ *               bytes.  Of the source only grid points are read.  The result never depends on either layout.
+ *   MC33HIP_EINVAL  checked on the host, with nothing enqueued or written: a null pointer; a rank that is none of the three; a
+ *               radius above its limit; a slab context or one without a grid; a bad pitch / slice; a dst byte range - first to
+ *               last grid point - that meets the source grid's (the call is not in place).
+ * The call needs no scratch memory.  It enqueues on the context's stream behind whatever is on it, and waits. */
+#define MC33HIP_RANK_MIN    0
+#define MC33HIP_RANK_MEDIAN 1
+#define MC33HIP_RANK_MAX    2
+typedef struct { unsigned radius[3]; int rank; } mc33hip_ranking;   /* radius per axis x, y, z, in samples */
+int mc33hip_rank_grid(mc33hip_ctx *c, const mc33hip_ranking *r, void *dst, size_t pitch, size_t slice);
+
 /* --- contour spectrum of the resident grid: cut cells and histogram per isovalue (Bajaj, Pascucci, Schikore 1997; no counterpart
  * in the reference) ---------------------------------------------------------------------------------------------------------------
  * For a ladder of isovalues: how many cells the surface cuts at each one, a histogram of the samples between the steps, and the

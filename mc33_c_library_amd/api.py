@@ -237,6 +237,15 @@ class GridResampling(C.Structure):
     _fields_ = [("sigma", C.c_double * 3), ("radius", C.c_uint * 3), ("stride", C.c_uint * 3)]
 
 
+class Ranking(C.Structure):
+    """mc33hip_ranking (include/mc33_hip.h) and mc33_ranking (include/marching_cubes_33.h): radius per axis x, y, z; rank RANK_*"""
+    _fields_ = [("radius", C.c_uint * 3), ("rank", C.c_int)]
+
+
+RANK_MIN, RANK_MEDIAN, RANK_MAX = 0, 1, 2
+RANKS = {"min": RANK_MIN, "median": RANK_MEDIAN, "max": RANK_MAX}
+
+
 class Spectrum(C.Structure):
     """mc33hip_spectrum (include/mc33_hip.h): isos, cut_cells and histogram are HOST arrays"""
     _fields_ = [("isos", C.POINTER(C.c_double)), ("n", C.c_uint), ("cut_cells", C.POINTER(C.c_ulonglong)), ("histogram", C.POINTER(C.c_ulonglong)),
@@ -282,6 +291,7 @@ STRUCTS = {
     "mc33hip_section": Sectioning, "mc33hip_contour": Contour, "mc33_contour": Contour, "mc33_section": SurfaceSection,
     "mc33_section_level": SectionLevel,
     "mc33hip_resampling": Resampling, "mc33_resampling": GridResampling,
+    "mc33hip_ranking": Ranking, "mc33_ranking": Ranking,
     "mc33hip_spectrum": Spectrum, "mc33_spectrum_info": SpectrumInfo,
     "mc33hip_curvature": Curvature, "mc33_curvature": IsosurfaceCurvature,
 }
@@ -345,6 +355,7 @@ SIGNATURES = {
     "mc33hip_resampled_size": (_I, [_V, _P(Resampling), _P(_U * 3)], False),
     "mc33hip_resample_grid": (_I, [_V, _P(Resampling), _V, _Z, _Z], False),
     "mc33hip_context_device": (_I, [_V], False),
+    "mc33hip_rank_grid": (_I, [_V, _P(Ranking), _V, _Z, _Z], False),
     "mc33hip_grid_spectrum": (_I, [_V, _P(Range), _P(Spectrum)], False),
     "mc33hip_clip_surface": (_I, [_V, _P(Clipping)], False),
     "mc33hip_section_surface": (_I, [_V, _P(Sectioning)], False),
@@ -385,7 +396,7 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "MC33_isosurface_topology", "MC33_component_topology",
                  "MC33_select_components", "MC33_calculate_filtered_isosurface", "MC33_calculate_smoothed_isosurface",
                  "MC33_calculate_simplified_isosurface",
-                 "MC33_gaussian_taps", "MC33_create_resampled", "MC33_resampled_grid",
+                 "MC33_gaussian_taps", "MC33_create_resampled", "MC33_resampled_grid", "MC33_create_ranked",
                  "MC33_grid_spectrum", "MC33_isovalue_ladder",
                  "MC33_calculate_clipped_isosurface", "MC33_clip_box",
                  "MC33_section_isosurface", "MC33_free_section", "MC33_section_contours", "MC33_section_profile",
@@ -1435,6 +1446,42 @@ class DeviceGrid:
         self.resample_into(out, npx, taps, stride, sigma)
         d = tuple(self.desc.d[k] * float(int(stride[k])) for k in range(3))
         g = DeviceGrid(out, r0=tuple(self.desc.r0), d=d, npx=npx)
+        if getattr(self, "inclined", None):
+            g.set_inclined(*self.inclined)
+        return g
+
+    # -- the grid rank-filtered into a second device grid (mc33_hip.h: mc33hip_rank_grid) ------------------------------------------
+    @staticmethod
+    def _ranking(rank, radius):
+        rank = RANKS.get(rank, rank) if isinstance(rank, str) else int(rank)
+        rad = (radius,) * 3 if not hasattr(radius, "__len__") else tuple(radius)
+        if isinstance(rank, str) or len(rad) != 3 or any(int(x) < 0 for x in rad):
+            raise ValueError("rank is 'min', 'median', 'max' or the integer; radius one number or three, none negative")
+        return Ranking((C.c_uint * 3)(*[min(int(x), 0xFFFFFFFF) for x in rad]), rank)
+
+    def rank_into(self, out, npx, rank="median", radius=(1, 1, 1)):
+        """mc33hip_rank_grid into `out`, a device tensor [npz, npy, >= npx] of the grid's dtype used with its strides (any
+        stride(1) >= npx, any stride(0)): only the grid points are written.  MC33Error(EINVAL) for what the library refuses."""
+        assert out.is_cuda and out.dim() == 3 and out.stride(2) == 1 and out.dtype == self.tensor.dtype and out.device == self.device
+        r = self._ranking(rank, radius)
+        _check(self.lib, self.lib.mc33hip_rank_grid(self.ctx, C.byref(r), C.c_void_p(out.data_ptr()), out.stride(1), out.stride(0)))
+
+    def ranked(self, rank="median", radius=(1, 1, 1)):
+        """The grid rank-filtered on the device - every point replaced by the minimum, the median or the maximum of the box window
+        of `radius` samples per axis x, y, z (one number: all three) around it, edge samples replicated; a selection, so the
+        samples keep their bytes - into a new torch tensor [npz, npy, pitch] with rows on 16-byte boundaries.  `rank` is "min",
+        "median", "max" or the integer; min and max take radii up to 8, the median up to 1 (3 x 3 x 3).  Returns a new DeviceGrid
+        over that tensor with the grid's r0, d, the current stream and the inclined matrices of this one:
+        grid.ranked("min", 1).ranked("max", 1) is an opening.  Whole grids only (not a z-slab).  The definition is in
+        include/mc33_hip.h."""
+        import torch
+        npx, npy, npz = self.desc.npx, self.desc.npy, self.desc.npz_resident
+        sb = self.tensor.element_size()
+        unit = max(1, 16 // sb)
+        pitch = (npx + unit - 1) // unit * unit
+        out = torch.empty((npz, npy, pitch), dtype=self.tensor.dtype, device=self.device)
+        self.rank_into(out, npx, rank, radius)
+        g = DeviceGrid(out, r0=tuple(self.desc.r0), d=tuple(self.desc.d), npx=npx)
         if getattr(self, "inclined", None):
             g.set_inclined(*self.inclined)
         return g

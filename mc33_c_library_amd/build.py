@@ -67,7 +67,7 @@ HIP_HEADERS = ["mc33_cell.h", "mc33_lut_data.h", "mc33_rules_data.h",
                "mc33_sweep_plan.h", "mc33_sweep_blocks.h", "mc33_records.hip.h", "mc33_sweep_pack.h", "mc33_sweep.hip.h", "mc33_tail.hip.h", "mc33_emit.hip.h", "mc33_context.hip.h", "mc33_extract.hip.h",
                "mc33_property.hip.h", "mc33_mesh.hip.h", "mc33_measure.hip.h", "mc33_topology.hip.h", "mc33_filter.hip.h", "mc33_smooth.hip.h", "mc33_cap.hip.h", "mc33_render.hip.h",
                "mc33_distance.hip.h",
-               "mc33_simplify.hip.h", "mc33_clip.hip.h", "mc33_section.hip.h", "mc33_resample.hip.h", "mc33_curvature.hip.h",
+               "mc33_simplify.hip.h", "mc33_clip.hip.h", "mc33_section.hip.h", "mc33_resample.hip.h", "mc33_rank.hip.h", "mc33_curvature.hip.h",
                "mc33_spectrum.hip.h"]
 
 

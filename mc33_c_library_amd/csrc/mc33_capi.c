@@ -85,6 +85,7 @@ int DefaultColorMC = (int)DEFAULT_SURFACE_COLOR;
 #pragma weak mc33hip_resampled_size
 #pragma weak mc33hip_resample_grid
 #pragma weak mc33hip_context_device
+#pragma weak mc33hip_rank_grid /* (MC33_create_ranked: without it NULL) */
 #pragma weak mc33hip_adopt_device /* (the host layer uses it for the resampled grid only) */
 #pragma weak mc33hip_grid_stable  /* (... whose samples nobody but this library writes) */
 /* ... and the contour spectrum (MC33_grid_spectrum): without it that function returns -1 */
@@ -140,7 +141,7 @@ typedef struct mc33_private_s {
 	int map[256];
 	double map_lo, map_hi;
 	int nan_color;       /* DefaultColorMC when the surface under way was made */
-	void *own_grid;      /* MC33_create_resampled: the grid, in device memory only, adopted by slab[0].ctx; released in free_MC33 */
+	void *own_grid;      /* MC33_create_resampled, MC33_create_ranked: the grid, in device memory only, adopted by slab[0].ctx; released in free_MC33 */
 	size_t own_pitch, own_slice; /* ... its layout, in samples */
 	void *dP, *dL;       /* MC33_measure_*: property values / component labels of the vertices in slab[0].set[0] (device) */
 	unsigned long long capP, capL;
@@ -2074,24 +2075,13 @@ static size_t resampled_pitch(size_t npx) {
 	return (npx + unit - 1) / unit * unit;
 }
 
-MC33 *MC33_create_resampled(MC33 *source, const mc33_resampling *r) {
-	mc33_private *sp = one_slab(source, mc33hip_resampled_size && mc33hip_resample_grid && mc33hip_context_device && mc33hip_adopt_device);
-	if (!sp || !r)
-		return 0;
-	double w[3][17];
-	mc33hip_resampling hr;
-	unsigned npo[3];
-	for (int a = 0; a != 3; a++) {
-		const int rad = MC33_gaussian_taps(r->sigma[a], r->radius[a], w[a]);
-		if (rad < 0 || !r->stride[a])
-			return 0;
-		hr.taps[a] = w[a]; hr.ntaps[a] = 2u * (unsigned)rad + 1u; hr.stride[a] = r->stride[a];
-	}
+/* What MC33_create_resampled and MC33_create_ranked share: the new object of npo points per axis and spacing `step` beside source
+ * object sp (whose inclined matrices it takes over), its context on the source's device, the grid allocated through that context at
+ * a 16-byte row pitch, written ONCE by `write` - a call of the device layer on the source's context that waits -, adopted and
+ * declared stable.  free_MC33 releases the grid through the context (own_grid) in every outcome; NULL after any failure. */
+typedef int grid_writer(mc33hip_ctx *source, const void *arg, void *dst, size_t pitch, size_t slice);
+static MC33 *create_device_grid_object(mc33_private *sp, const unsigned npo[3], const double step[3], grid_writer *write, const void *arg) {
 	mc33_slab *ss = &sp->slab[0];
-	if (mc33hip_resampled_size(ss->ctx, &hr, npo) != MC33HIP_OK) /* (fewer than 2 points left on an axis) */
-		return 0;
-	double step[3];
-	for (int j = 0; j != 3; j++) step[j] = sp->grd_d[j] * (double)r->stride[j];
 	/* (an inclined source: the matrices of its _GRD, scaled by the new spacing) */
 	mc33_private *p = new_object(npo[0] - 1u, npo[1] - 1u, npo[2] - 1u, sp->grd_r0, step, sp->inclined ? sp->grd_A : 0, sp->inclined ? sp->grd_Ai : 0);
 	if (!p)
@@ -2116,15 +2106,62 @@ MC33 *MC33_create_resampled(MC33 *source, const mc33_resampling *r) {
 	if (rc == MC33HIP_OK) rc = refresh_grid(sp); /* (samples the caller said it rewrote: uploaded first, as before an extraction) */
 	if (rc == MC33HIP_OK) /* (64 samples to spare behind the last row, like the device layer's own copy) */
 		rc = mc33hip_device_alloc(s->ctx, &p->own_grid, (p->own_slice * npo[2] + 64) * sizeof(GRD_data_type));
-	if (rc == MC33HIP_OK) rc = mc33hip_resample_grid(ss->ctx, &hr, p->own_grid, p->own_pitch, p->own_slice); /* (waits) */
+	if (rc == MC33HIP_OK) rc = write(ss->ctx, arg, p->own_grid, p->own_pitch, p->own_slice); /* (waits) */
 	if (rc == MC33HIP_OK) rc = mc33hip_adopt_device(s->ctx, p->own_grid, p->own_pitch, p->own_slice);
-	if (rc == MC33HIP_OK && mc33hip_grid_stable) /* (own_grid is written by the resampling above and never again: the sweeps may keep a range table over it) */
+	if (rc == MC33HIP_OK && mc33hip_grid_stable) /* (own_grid is written by the call above and never again: the sweeps may keep a range table over it) */
 		rc = mc33hip_grid_stable(s->ctx, 1);
 	if (rc != MC33HIP_OK) {
 		free_MC33(M);
 		return 0;
 	}
 	return M;
+}
+
+static int write_resampled(mc33hip_ctx *source, const void *arg, void *dst, size_t pitch, size_t slice) {
+	return mc33hip_resample_grid(source, (const mc33hip_resampling *)arg, dst, pitch, slice);
+}
+
+MC33 *MC33_create_resampled(MC33 *source, const mc33_resampling *r) {
+	mc33_private *sp = one_slab(source, mc33hip_resampled_size && mc33hip_resample_grid && mc33hip_context_device && mc33hip_adopt_device);
+	if (!sp || !r)
+		return 0;
+	double w[3][17];
+	mc33hip_resampling hr;
+	unsigned npo[3];
+	for (int a = 0; a != 3; a++) {
+		const int rad = MC33_gaussian_taps(r->sigma[a], r->radius[a], w[a]);
+		if (rad < 0 || !r->stride[a])
+			return 0;
+		hr.taps[a] = w[a]; hr.ntaps[a] = 2u * (unsigned)rad + 1u; hr.stride[a] = r->stride[a];
+	}
+	if (mc33hip_resampled_size(sp->slab[0].ctx, &hr, npo) != MC33HIP_OK) /* (fewer than 2 points left on an axis) */
+		return 0;
+	double step[3];
+	for (int j = 0; j != 3; j++) step[j] = sp->grd_d[j] * (double)r->stride[j];
+	return create_device_grid_object(sp, npo, step, write_resampled, &hr);
+}
+
+/* --- extension: the grid rank-filtered on the device before extraction ------------------------------------------------------------ */
+static int write_ranked(mc33hip_ctx *source, const void *arg, void *dst, size_t pitch, size_t slice) {
+	return mc33hip_rank_grid(source, (const mc33hip_ranking *)arg, dst, pitch, slice);
+}
+
+MC33 *MC33_create_ranked(MC33 *source, const mc33_ranking *r) {
+	mc33_private *sp = one_slab(source, mc33hip_rank_grid && mc33hip_context_device && mc33hip_adopt_device);
+	if (!sp || !r)
+		return 0;
+	/* (refused here, before anything is made: the limits of mc33hip_rank_grid) */
+	if (r->rank != MC33_RANK_MIN && r->rank != MC33_RANK_MEDIAN && r->rank != MC33_RANK_MAX)
+		return 0;
+	mc33hip_ranking hr;
+	for (int a = 0; a != 3; a++) {
+		if (r->radius[a] > (r->rank == MC33_RANK_MEDIAN ? 1u : 8u))
+			return 0;
+		hr.radius[a] = r->radius[a];
+	}
+	hr.rank = r->rank; /* (MC33_RANK_* are MC33HIP_RANK_*) */
+	const unsigned npo[3] = {source->nx + 1u, source->ny + 1u, source->nz + 1u};
+	return create_device_grid_object(sp, npo, sp->grd_d, write_ranked, &hr);
 }
 
 _GRD *MC33_resampled_grid(MC33 *M) {

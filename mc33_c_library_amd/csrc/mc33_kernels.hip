@@ -75,6 +75,10 @@
 // Before an extraction: k_rs_resample - the resident grid into a second device grid, a separable correlation of up to 17 taps per axis
 //                   with an integer stride, one pass over the source: a block stages the rows its tile of outputs needs in LDS,
 //                   sums along x and y into a ring of planes and along z out of it (mc33_resample.hip.h).
+//                   k_rk_minmax, k_rk_median - the resident grid into a second device grid through a box window's minimum, maximum
+//                   or median, one pass over the source: sample keys staged in LDS with the next plane's loads in flight, the
+//                   maximum axis by axis through a ring of planes, the median by a selection network in registers
+//                   (mc33_rank.hip.h).
 //                   k_sp_spectrum - the contour spectrum of the resident grid for up to 255 isovalues in one pass: every sample
 //                   ranked among the isovalues in LDS, cells cut and samples counted per rank in the block's LDS counters, 64-bit
 //                   device counters once per block; k_sp_init clears those (mc33_spectrum.hip.h).
@@ -128,6 +132,7 @@ typedef float sample_t;
 #endif
 
 // The translation unit in parts (round 5: it had grown to 4 500 lines), included in this order:
+// (mc33_resample.hip.h ends with #include "mc33_rank.hip.h": the rank filter of the grid follows its resampling)
 #include "mc33_sweep_plan.h"
 #include "mc33_sweep_blocks.h"
 #include "mc33_records.hip.h"

@@ -338,4 +338,7 @@ extern "C" int mc33hip_resample_grid(mc33hip_ctx *c, const mc33hip_resampling *r
 
 extern "C" int mc33hip_context_device(mc33hip_ctx *c) { return c ? c->device : MC33HIP_EINVAL; }
 
+// the other way from the resident grid to a second device grid, behind this one in the translation unit: rank windows
+#include "mc33_rank.hip.h"
+
 #endif  // __HIPCC__
