@@ -134,6 +134,16 @@ int mc33hip_sweep_skipped_blocks(mc33hip_ctx *c, unsigned long long out[3]);
 /* mc33hip_alias_cells: the cut cells of the last count that have a corner equal to the isovalue (they take the general per-cell
  * kernels), as the device counted them; for tests. */
 int mc33hip_alias_cells(mc33hip_ctx *c, unsigned long long *out);
+/* mc33hip_emit_shape: the launch shape of the emit passes enqueued last on this context (mc33hip_emit, mc33hip_extract and their
+ * siblings), once its counters are on the host - the call waits for the context's stream: out = {work records, slow records,
+ * record batches, blocks of the vertex pass, blocks of the triangle pass, blocks of the slow pass, the slow kernel (0: a thread
+ * per record, 1: a lane per pattern slot, 2: left out - the tail found no cell with a corner equal to the isovalue to plan), 1 if
+ * the triangle pass went first}.  The block counts are what was launched; the counts are the device's.  To be read before the
+ * next call that counts.  MC33HIP_EINVAL when the context has emitted nothing.  For tests and tracing.
+ * The grids follow the device and the counts of the extraction before; in the environment when a context is created,
+ * MC33_HIP_EMIT_V_BLOCKS=<n> sets the vertex pass's grid and MC33_HIP_EMIT_BLOCKS=<n> the triangle pass's, both rounded up to a
+ * multiple of 8 (blocks are dealt to the 8 XCDs in whole rounds), MC33_HIP_SLOW_BLOCKS=<n> the slow kernels'. */
+int mc33hip_emit_shape(mc33hip_ctx *c, unsigned long long out[8]);
 /* For tests and tracing as well.  mc33hip_sweep_plan: the sweep's plan in force - the one the last sweep, or the last tail, went
  * by - as tiles {row segment, y tile, z_lo, z_hi} in launch order, four consecutive tiles a block, into tiles_out (room for
  * cap_tiles tiles; NULL: info only); info = {tiles, blocks the device holds at once, 0: the plan of a sweep without a range

@@ -4,6 +4,7 @@ Plumbing only: device memory and streams come from PyTorch-ROCm, the work is don
 inside libMC33_{f32,f64,u8,u16,u32}.so (one library per grid sample type).  There is no CPU fallback: loading fails loudly when the shared object is
 missing, and every call into it fails loudly when no GPU is present.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -373,6 +374,7 @@ SIGNATURES = {
     "mc33hip_block_words": (_I, [_V, _V, _Z], True),
     "mc33hip_alias_cells": (_I, [_V, _P(_Q)], True),
     "mc33hip_sweep_skipped_blocks": (_I, [_V, _P(_Q * 3)], True),
+    "mc33hip_emit_shape": (_I, [_V, _P(_Q * 8)], True),
     "mc33hip_curvature_vertices": (_I, [_V, _P(Curvature)], True),
     "mc33hip_color_values": (_I, [_V, _V, _Q, _P(_I), _U, _D, _D, _I, _V], True),
     "mc33hip_cap_surface": (_I, [_V, _P(Capping)], True),
@@ -404,6 +406,10 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
                  "MC33_calculate_capped_isosurface",
                  "MC33_render_isosurface", "MC33_free_image", "MC33_view_fit", "MC33_write_image_ppm",
                  "MC33_isosurface_distance", "MC33_simplification_error"]
+
+
+# what DeviceGrid.emit_shape() returns: out[8] of mc33hip_emit_shape (slow_kernel: 0 a thread per record, 1 a lane per slot, 2 left out)
+EmitShape = collections.namedtuple("EmitShape", "records slow_records batches vertex_blocks triangle_blocks slow_blocks slow_kernel triangles_first")
 
 
 class MC33Error(RuntimeError):
@@ -1522,6 +1528,13 @@ class DeviceGrid:
         best, med, nbytes = C.c_float(), C.c_float(), C.c_ulonglong()
         _check(self.lib, self.lib.mc33hip_probe_read(self.ctx, int(reps), C.byref(best), C.byref(med), C.byref(nbytes)))
         return best.value, med.value, nbytes.value
+
+    def emit_shape(self):
+        """The launch shape of the emit enqueued last (include/mc33_hip.h: mc33hip_emit_shape), for tests and tracing: an
+        EmitShape; MC33Error(EINVAL) when the context has emitted nothing."""
+        out = (C.c_ulonglong * 8)()
+        _check(self.lib, self.lib.mc33hip_emit_shape(self.ctx, C.byref(out)))
+        return EmitShape(*[int(x) for x in out])
 
     def timing(self):
         t = Timing()

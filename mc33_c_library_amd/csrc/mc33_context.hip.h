@@ -135,6 +135,7 @@ struct Switches {
 	uint32_t render_small;      // MC33_HIP_RENDER_SMALL: the largest box of pixel centres one lane of k_render_triangles walks (mc33_render.hip.h; the tests set 0 and a huge value)
 	uint32_t distance_cells;    // MC33_HIP_DISTANCE_CELLS: cells per axis of the lattice of mc33hip_surface_distance, 0: it decides (mc33_distance.hip.h; the tests set 1 and a huge value;
 	                            //  the word was padding: with the context 24 bytes smaller, the C3 emit stage measured 4 us slower)
+	uint32_t emit_v_blocks;     // MC33_HIP_EMIT_V_BLOCKS: blocks of k_emit_vertices, whatever the device holds (the tests: fewer waves than batches, so that a wave walks several)
 };
 
 struct mc33hip_ctx {
@@ -232,6 +233,10 @@ struct mc33hip_ctx {
 	unsigned long long *d_prop_viol, *h_prop_viol;  // vertices that needed a plane outside the window: device word, pinned copy
 	hipEvent_t ev_prop;       // mc33hip_download_enqueue
 	struct MeasureState *meas;  // scratch of the measuring passes (mc33_measure.hip.h), made by the first of them
+	// the launch shape of the emit enqueued last (mc33hip_emit_shape): the set it read, the grids of the vertex, triangle and slow
+	// passes as launched, the slow kernel (0 a thread per record, 1 a lane per slot, 2 left out: alias-gated), the triangle pass first
+	TailSet *shape_set;       // (nullptr: no emit yet)
+	uint32_t shape[5];
 };
 static void prop_destroy(mc33hip_ctx *c);
 static void meas_destroy(mc33hip_ctx *c);
@@ -249,8 +254,8 @@ static int env_flag(const char *name) {  // -1: not set
 }
 static void read_switches(Switches &w) {
 	w.rz = env_u32("MC33_HIP_RZ", 0); w.sweep_blocks_per_cu = env_u32("MC33_HIP_SWEEP_BLOCKS_PER_CU", 0); w.min_depth = env_u32("MC33_HIP_MIN_DEPTH", 0); w.rz_table = env_u32("MC33_HIP_RZ_TABLE", 0); w.live = env_flag("MC33_HIP_LIVE"); w.table_tiles = env_u32("MC33_HIP_TABLE_TILES", 0); w.list_lds = std::min(4096u, env_u32("MC33_HIP_LIST_LDS", 4096u));
-	w.cells_blocks = env_u32("MC33_HIP_CELLS_BLOCKS", 0); w.slow_blocks = env_u32("MC33_HIP_SLOW_BLOCKS", 0); w.emit_blocks = env_u32("MC33_HIP_EMIT_BLOCKS", 0);
-	w.emit_v_blocks_per_cu = env_u32("MC33_HIP_EMIT_V_BLOCKS_PER_CU", 0); w.slow_slots_max = env_u32("MC33_HIP_SLOW_SLOTS_MAX", 0);
+	w.cells_blocks = env_u32("MC33_HIP_CELLS_BLOCKS", 0); w.slow_blocks = env_u32("MC33_HIP_SLOW_BLOCKS", 0); w.emit_blocks = (env_u32("MC33_HIP_EMIT_BLOCKS", 0) + 7u) & ~7u;  // (whole rounds of the 8 XCDs: XcdWalk)
+	w.emit_v_blocks = (env_u32("MC33_HIP_EMIT_V_BLOCKS", 0) + 7u) & ~7u; w.emit_v_blocks_per_cu = env_u32("MC33_HIP_EMIT_V_BLOCKS_PER_CU", 0); w.slow_slots_max = env_u32("MC33_HIP_SLOW_SLOTS_MAX", 0);
 	w.no_pack = env_u32("MC33_HIP_NO_PACK", 0) != 0; w.no_stage = env_u32("MC33_HIP_NO_STAGE", 0) != 0; w.verbose = getenv("MC33_HIP_VERBOSE") != nullptr;
 	w.slow_count = env_flag("MC33_HIP_SLOW_COUNT"); w.no_fork = env_flag("MC33_HIP_NO_FORK");
 	w.slow_slots = env_flag("MC33_HIP_SLOW_SLOTS"); w.tri_first = env_flag("MC33_HIP_TRI_FIRST");

@@ -34,6 +34,9 @@ struct EmitArgs {
 // Work split of the fast emit passes: blocks are dealt to the 8 XCDs round robin (block b runs on XCD b % 8), each
 // XCD has its own L2, and neighbouring records read neighbouring samples.  So every XCD gets ONE contiguous
 // eighth of the record array, and the blocks that are resident on it together walk it side by side.
+// The grid must be a multiple of 8: every XCD strides by blocks_per_xcd = ceil(grid / 8), which only the XCDs that have that many
+// blocks cover - with 12 blocks XCDs 4..7 own slot 0 alone and stride by 2, their odd chunks are never taken.  The host rounds
+// every grid it launches these walks with, the forced ones too (read_switches, enqueue_emit).
 struct XcdWalk {
 	uint32_t first, end, stride;
 	__device__ XcdWalk(uint32_t n) {

@@ -650,6 +650,7 @@ static int enqueue_sweep_many(mc33hip_ctx *c, const double *isos, int n, bool ta
 				for (int j = 1; j <= k; j++) free_set(c->ts[j]);
 				(void)hipGetLastError();
 				c->w = &c->ts[0];  // (the last count may have worked in one of the sets that are gone)
+				c->shape_set = nullptr;  // (... and the last emit)
 				c->counted = false;
 				tails_ahead = false;
 			}
@@ -805,8 +806,12 @@ static int enqueue_emit(mc33hip_ctx *c, void *dV, void *dN, void *dT, uint64_t c
 	// as many blocks as the device holds at once (one more round of blocks would run with most of the GPU idle); every wave
 	// walks many batches, its next batch's records in flight while it works on one
 	if (!c->emit_v_blocks_per_cu) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c->emit_v_blocks_per_cu, k_emit_vertices<3>, 256, 0));
-	const uint32_t vblocks = (uint32_t)std::max(1, c->cus) * (c->sw.emit_v_blocks_per_cu ? c->sw.emit_v_blocks_per_cu : (uint32_t)std::max(1, c->emit_v_blocks_per_cu));
+	// (MC33_HIP_EMIT_V_BLOCKS: the grid itself, below what the device holds - fewer waves than batches, every wave walks several)
+	const uint32_t vblocks = c->sw.emit_v_blocks ? c->sw.emit_v_blocks
+	                         : (uint32_t)std::max(1, c->cus) * (c->sw.emit_v_blocks_per_cu ? c->sw.emit_v_blocks_per_cu : (uint32_t)std::max(1, c->emit_v_blocks_per_cu));
 	const dim3 vgrid((vblocks + 7u) & ~7u);
+	c->shape_set = c->w;  // what was launched, for mc33hip_emit_shape
+	c->shape[0] = vgrid.x; c->shape[1] = blocks; c->shape[2] = slow_grid; c->shape[3] = a.alias_gated ? 2u : slow_slots ? 1u : 0u; c->shape[4] = tri_first ? 1u : 0u;
 	switch (c->P.store_mode) {
 	case 0: hipLaunchKernelGGL(k_emit_vertices<0>, vgrid, dim3(256), 0, c->stream, a); break;
 	case 1: hipLaunchKernelGGL(k_emit_vertices<1>, vgrid, dim3(256), 0, c->stream, a); break;
@@ -1285,6 +1290,16 @@ extern "C" int mc33hip_alias_cells(mc33hip_ctx *c, unsigned long long *out) {
 	if (int rc = use_device(c)) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	*out = c->w->alias_known ? c->w->alias_last : c->w->h_ctr->alias_cells;
+	return MC33HIP_OK;
+}
+extern "C" int mc33hip_emit_shape(mc33hip_ctx *c, unsigned long long *out /*[8]*/) {
+	if (!c || !out) return MC33HIP_EINVAL;
+	if (!c->shape_set || !c->shape_set->h_ctr) { set_err("no emit yet"); return MC33HIP_EINVAL; }
+	if (int rc = use_device(c)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));  // (the triangle pass of that emit has left the counters in h_ctr by now, if no count had)
+	const Counters &h = *c->shape_set->h_ctr;
+	out[0] = h.entry_cursor == 0xFFFFFFFFu ? 0u : h.entry_cursor; out[1] = h.slow_cursor; out[2] = h.batch_cursor;
+	for (int k = 0; k < 5; k++) out[3 + k] = c->shape[k];
 	return MC33HIP_OK;
 }
 extern "C" int mc33hip_range_blocks(mc33hip_ctx *c, void *host_out, size_t bytes) {

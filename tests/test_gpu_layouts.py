@@ -16,6 +16,7 @@ import pytest
 
 import fixtures as fx
 import layouts as lo
+from canaries import canaried as _canaried, only_the_rows_were_written as _only_the_rows_were_written, windows as _windows, words
 
 pytestmark = pytest.mark.gpu
 
@@ -106,11 +107,6 @@ def device_grid(dtype, grid, layout, **kw):
     g = DeviceGrid(view, npx=npx, **kw)
     g.flat = flat
     return g
-
-
-def words(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype.itemsize == 8 else np.uint32)
 
 
 def same(got, ref, what):
@@ -286,39 +282,6 @@ def test_property_grid_with_a_layout_of_its_own(reflibs, dtype, grid_layout, pro
 
 
 # ---- 5: outputs inside larger tensors ----------------------------------------------------------------------------------------------
-
-FRONT, SPARE, EXTRA = 5, 16, 37  # rows in front of the window, spare rows inside its capacity, rows more than needed in all
-CANARY32, CANARY64 = 0x7FC0BEEF, 0x7FF8BEEF7FC0BEEF  # NaN bit patterns
-
-
-def _canaried(nV, nT, v64):
-    """V, N [nV + 37, 3] and T [nT + 37, 3] holding the canary in every word"""
-    import torch
-    V = torch.full((nV + EXTRA, 3), CANARY64, dtype=torch.int64, device="cuda").view(torch.float64) if v64 else \
-        torch.full((nV + EXTRA, 3), CANARY32, dtype=torch.int32, device="cuda").view(torch.float32)
-    N = torch.full((nV + EXTRA, 3), CANARY32, dtype=torch.int32, device="cuda").view(torch.float32)
-    T = torch.full((nT + EXTRA, 3), -1, dtype=torch.int32, device="cuda")
-    return V, N, T
-
-
-def _windows(V, N, T, nV, nT):
-    """the row windows [5 : 5 + n + 16]: the base 60 bytes off alignment, 16 rows more capacity than needed"""
-    w = V[FRONT:FRONT + nV + SPARE], N[FRONT:FRONT + nV + SPARE], T[FRONT:FRONT + nT + SPARE]
-    assert all(x.is_contiguous() for x in w) and w[1].data_ptr() % 64 == 60 and w[2].data_ptr() % 64 == 60
-    return w
-
-
-def _only_the_rows_were_written(V, N, T, ref, what):
-    """rows [5 : 5 + n] equal the reference, every other word of the big tensors still holds the canary"""
-    for name, big, want, canary in (("V", V, ref.V, CANARY64 if ref.V.dtype == np.float64 else CANARY32), ("N", N, ref.N, CANARY32),
-                                    ("T", T, ref.T, 0xFFFFFFFF)):
-        got = words(big.cpu().numpy())
-        exp = np.full(got.shape, canary, got.dtype)
-        exp[FRONT:FRONT + want.shape[0]] = words(want)
-        bad = np.nonzero((got != exp).any(axis=1))[0]
-        assert bad.size == 0, "%s %s: %d rows differ, the first rows %s (rows %d .. %d are the surface)" % (
-            what, name, bad.size, bad[:8].tolist(), FRONT, FRONT + want.shape[0] - 1)
-
 
 @pytest.mark.parametrize("layout", ["padx16", "all"])
 @pytest.mark.parametrize("dtype,grid,iso", [("f32", "smooth258", 1.0), ("f32", "roughq", 0.0), ("u8", "rough", 3.0), ("f64", "smooth258", 1.0)])
