@@ -144,6 +144,16 @@ int mc33hip_alias_cells(mc33hip_ctx *c, unsigned long long *out);
  * MC33_HIP_EMIT_V_BLOCKS=<n> sets the vertex pass's grid and MC33_HIP_EMIT_BLOCKS=<n> the triangle pass's, both rounded up to a
  * multiple of 8 (blocks are dealt to the 8 XCDs in whole rounds), MC33_HIP_SLOW_BLOCKS=<n> the slow kernels'. */
 int mc33hip_emit_shape(mc33hip_ctx *c, unsigned long long out[8]);
+/* mc33hip_tail_shape: the shape of the tail (the passes between the sweep and the emit passes) of the last count on this context
+ * (mc33hip_count, mc33hip_extract and their siblings) - the call waits for the context's stream: out = {slice slots of the range,
+ * groups the slow-cell and dirty-segment lists were cut into, log2 of the slots per group, chunks of 2048 row segments of the
+ * prefix sums, 1 if the sums went by groups of 32 chunks (from 4096 chunks on), blocks of the slot pass, slow cells listed, dirty
+ * row segments listed}.  The two totals are the device's.  mc33hip_list_counts: the first n (at most 1024) group cursors of the
+ * slow-cell list and of the dirty-segment list of that tail, copied to the host after a wait for the context's stream; a group
+ * beyond those in use holds 0.  Both to be read before the next call that counts (the next tail clears the cursors).
+ * MC33HIP_EINVAL when the context has counted nothing.  For tests and tracing. */
+int mc33hip_tail_shape(mc33hip_ctx *c, unsigned long long out[8]);
+int mc33hip_list_counts(mc33hip_ctx *c, unsigned int *slow, unsigned int *dirty, size_t n);
 /* For tests and tracing as well.  mc33hip_sweep_plan: the sweep's plan in force - the one the last sweep, or the last tail, went
  * by - as tiles {row segment, y tile, z_lo, z_hi} in launch order, four consecutive tiles a block, into tiles_out (room for
  * cap_tiles tiles; NULL: info only); info = {tiles, blocks the device holds at once, 0: the plan of a sweep without a range

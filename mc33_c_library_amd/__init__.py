@@ -5,5 +5,5 @@ flavours): HIP kernels for gfx950 behind the C API of the reference's marching_c
 of include/mc33_hip.h.  This package only holds the build recipe, thin ctypes/torch plumbing around them (api.py)
 and the host-side z-slab orchestration over several GPUs (slabs.py).
 """
-from .api import (Contour, Counts, Curvature, DeviceGrid, Distance, EmitShape, GridDesc, GridResampling, GridSpectrum, Image, IsosurfaceCurvature, MC33Error, Range, Ranking, Rendering, Resampling, SectionLevel, SectionResult, Sectioning, Spectrum, SpectrumInfo, SurfaceDistance, SurfaceSection, Timing, VertexCurvature, View,  # noqa: F401
+from .api import (Contour, Counts, Curvature, DeviceGrid, Distance, EmitShape, GridDesc, GridResampling, GridSpectrum, Image, IsosurfaceCurvature, MC33Error, Range, Ranking, Rendering, Resampling, SectionLevel, SectionResult, Sectioning, Spectrum, SpectrumInfo, SurfaceDistance, SurfaceSection, TailShape, Timing, VertexCurvature, View,  # noqa: F401
                   HIP_API, REFERENCE_API, clip_box, gaussian_taps, isovalue_ladder, library_path, load_library)

@@ -375,6 +375,8 @@ SIGNATURES = {
     "mc33hip_alias_cells": (_I, [_V, _P(_Q)], True),
     "mc33hip_sweep_skipped_blocks": (_I, [_V, _P(_Q * 3)], True),
     "mc33hip_emit_shape": (_I, [_V, _P(_Q * 8)], True),
+    "mc33hip_tail_shape": (_I, [_V, _P(_Q * 8)], True),
+    "mc33hip_list_counts": (_I, [_V, _P(_U), _P(_U), _Z], True),
     "mc33hip_curvature_vertices": (_I, [_V, _P(Curvature)], True),
     "mc33hip_color_values": (_I, [_V, _V, _Q, _P(_I), _U, _D, _D, _I, _V], True),
     "mc33hip_cap_surface": (_I, [_V, _P(Capping)], True),
@@ -410,6 +412,8 @@ REFERENCE_API = ["create_MC33", "calculate_isosurface", "size_of_isosurface", "f
 
 # what DeviceGrid.emit_shape() returns: out[8] of mc33hip_emit_shape (slow_kernel: 0 a thread per record, 1 a lane per slot, 2 left out)
 EmitShape = collections.namedtuple("EmitShape", "records slow_records batches vertex_blocks triangle_blocks slow_blocks slow_kernel triangles_first")
+# what DeviceGrid.tail_shape() returns: out[8] of mc33hip_tail_shape
+TailShape = collections.namedtuple("TailShape", "nslots groups shift scan_chunks grouped slots_blocks slow_total dirty_total")
 
 
 class MC33Error(RuntimeError):
@@ -1535,6 +1539,22 @@ class DeviceGrid:
         out = (C.c_ulonglong * 8)()
         _check(self.lib, self.lib.mc33hip_emit_shape(self.ctx, C.byref(out)))
         return EmitShape(*[int(x) for x in out])
+
+    def tail_shape(self):
+        """The shape of the tail of the last count or extraction (include/mc33_hip.h: mc33hip_tail_shape), for tests and
+        tracing: a TailShape; MC33Error(EINVAL) when the context has counted nothing."""
+        out = (C.c_ulonglong * 8)()
+        _check(self.lib, self.lib.mc33hip_tail_shape(self.ctx, C.byref(out)))
+        return TailShape(*[int(x) for x in out])
+
+    def list_counts(self, n=1024):
+        """The first n group cursors of the slow-cell list and of the dirty-segment list of that tail (mc33hip_list_counts):
+        two uint32 arrays, valid until the next count."""
+        import numpy as np
+        slow, dirty = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        as_u = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint))
+        _check(self.lib, self.lib.mc33hip_list_counts(self.ctx, as_u(slow), as_u(dirty), n))
+        return slow, dirty
 
     def timing(self):
         t = Timing()

@@ -484,7 +484,7 @@ static int enqueue_tail(mc33hip_ctx *c, const int *idx, const int *sidx, const d
 		set_arrays(w, sa, sa);
 		sa.entries_c = w.entries_c; sa.fast_b = c->d_fast_b;
 		sa.seg_cnt = w.seg_cnt; sa.seg_tag = seg_tag; sa.dirty_list = w.dirty_list;
-		uint64_t *grV = nb >= SCAN_GROUPED_FROM ? w.bsV + 2 * w.bs_cap : nullptr, *grT = grV ? grV + scan_groups(w.bs_cap) : nullptr;
+		uint64_t *grV = scans_grouped(nb) ? w.bsV + 2 * w.bs_cap : nullptr, *grT = grV ? grV + scan_groups(w.bs_cap) : nullptr;
 		NA.a[q] = ScanArgs{w.seg_cnt, seg_tag, w.lc.slow_cnt, w.lc.n, w.bsV, w.bsT, grV, grT, w.seg_base, w.d_ctr};
 		// k_slots appends to live_list from Counters::live_cursor on, and k_scan_apply - the last kernel of a tail - leaves the
 		// cursor zero for the next.  A tail that was cut short (a launch error) leaves it wherever it was: the next one starts clean.
@@ -1300,6 +1300,31 @@ extern "C" int mc33hip_emit_shape(mc33hip_ctx *c, unsigned long long *out /*[8]*
 	const Counters &h = *c->shape_set->h_ctr;
 	out[0] = h.entry_cursor == 0xFFFFFFFFu ? 0u : h.entry_cursor; out[1] = h.slow_cursor; out[2] = h.batch_cursor;
 	for (int k = 0; k < 5; k++) out[3 + k] = c->shape[k];
+	return MC33HIP_OK;
+}
+extern "C" int mc33hip_tail_shape(mc33hip_ctx *c, unsigned long long *out /*[8]*/) {
+	if (!c || !out) return MC33HIP_EINVAL;
+	if (!c->counted || !c->w || !c->w->h_ctr) { set_err("no count yet"); return MC33HIP_EINVAL; }
+	if (int rc = use_device(c)) return rc;
+	SlotGeom g;
+	if (int rc = slot_geometry(c, g)) return rc;  // (c->P, c->range and c->nsegs are still those of the count: what enqueue_tail went by)
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	const Counters &h = *c->w->h_ctr;
+	const uint64_t nb = (c->nsegs + SCAN_CHUNK - 1) / SCAN_CHUNK;
+	out[0] = g.nslots; out[1] = c->w->lc.n; out[2] = c->w->lc.shift;
+	out[3] = nb; out[4] = scans_grouped(nb) ? 1u : 0u; out[5] = (g.nslots + SLOT_CHUNK - 1) / SLOT_CHUNK;
+	out[6] = h.slow_cursor; out[7] = h.dirty_cursor;
+	return MC33HIP_OK;
+}
+extern "C" int mc33hip_list_counts(mc33hip_ctx *c, unsigned int *slow, unsigned int *dirty, size_t n) {
+	if (!c || !slow || !dirty || n > LIST_CHUNKS) return MC33HIP_EINVAL;
+	if (!c->counted || !c->w || !c->w->lc.slow_cnt) { set_err("no count yet"); return MC33HIP_EINVAL; }
+	if (int rc = use_device(c)) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (n) {
+		HIP_TRY(hipMemcpy(slow, c->w->lc.slow_cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(dirty, c->w->lc.dirty_cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	}
 	return MC33HIP_OK;
 }
 extern "C" int mc33hip_range_blocks(mc33hip_ctx *c, void *host_out, size_t bytes) {

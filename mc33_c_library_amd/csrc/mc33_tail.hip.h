@@ -676,6 +676,7 @@ __global__ __launch_bounds__(256) void k_seg_fix(const PerLane<SlowArgs> A) {
 // ---------------------------------------------------------------------------------------------------
 constexpr uint32_t SCAN_PER_THREAD = 8, SCAN_CHUNK = 256 * SCAN_PER_THREAD, SCAN_GROUP = 32, SCAN_GROUPED_FROM = 4096;
 __host__ __device__ inline uint64_t scan_groups(uint64_t nchunks) { return (nchunks + SCAN_GROUP - 1) / SCAN_GROUP; }
+inline bool scans_grouped(uint64_t nchunks) { return nchunks >= SCAN_GROUPED_FROM; }  // (enqueue_tail: whether the scans get group sums)
 
 
 // position in sweep order -> storage index, advanced incrementally (one division per thread, not per element)
